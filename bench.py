@@ -11,11 +11,13 @@ stream's previous frame (best / second best / TH_LOW + ratio test inputs).  Stre
 independent, so with N GPUs each rank owns B streams (weak scaling) and only a per-frame result
 summary is all-gathered over RCCL.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu] [--no-ba] [--no-extras]   # + rooflines, stage times, CPU comparators, local-BA secondary
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --config pipeline [--streams 8]      # BASELINE configs[4]: 8 x 720p streams + per-GPU local BA + slot gather
 
-Prints ONE JSON line on rank 0.
+A plain run times exactly K steps once and reports only the headline; --full adds every other figure (and times 5
+regions of K steps, reporting the median one).  Prints ONE JSON line on rank 0.
 """
 import argparse
 import hashlib
@@ -363,24 +365,63 @@ def ba_secondary(device, steps, with_cpu=True):
         return {"error": repr(e)}
 
 
+# warm-up: at least --warmup steps and WARMUP_S seconds (on one MI355X the steps of the first tens of milliseconds run ~6 % slower),
+# extended in chunks of an even number of steps so that which frame pair a step reads does not depend on how long it took
+WARMUP_S = 1.0
+WARMUP_CHUNK = 8
+DUMP_BYTES = 60 * 10**6   # --dump-outputs: every file together stays under 64 MB, .npy headers included
+
+
+def dump_outputs(path, kps, desc, n, idx, best, second, ba_pose=None):
+    """Writes what the last timed step handed its caller as float32 / float64 .npy files under `path`: per stream the
+    keypoints (x, y, size, angle, response, octave, class_id), descriptors (one value per byte), keypoint counts, the
+    best / second-best matches against the stream's previous frame and (pipeline) the local-BA poses of the stream's
+    window.  Rows past a frame's keypoint count are zeroed (they hold nothing a caller reads).  Beyond DUMP_BYTES, a
+    fixed seeded sample of the streams, listed in stream_index.npy."""
+    from weiner_slamit_v2_amd import api
+
+    B, cap = desc.shape[:2]
+    per_stream = 4 * (cap * (7 + 32 + 3) + 2) + (ba_pose[0].nbytes if ba_pose is not None else 0)
+    keep = min(B, DUMP_BYTES // per_stream)
+    sel = np.arange(B) if keep == B else np.sort(np.random.RandomState(0).choice(B, keep, replace=False))
+    kp = np.ascontiguousarray(kps[sel]).view(api.KP_DTYPE).reshape(len(sel), cap)
+    valid = np.arange(cap)[None, :] < n[sel][:, None]
+    arrays = {"stream_index": sel, "n_keypoints": n[sel],
+              "keypoints": np.stack([kp[f] for f in api.KP_DTYPE.names], axis=2) * valid[:, :, None],
+              "descriptors": desc[sel] * valid[:, :, None],
+              "match_index": idx[sel] * valid, "match_best": best[sel] * valid, "match_second": second[sel] * valid}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
+    if ba_pose is not None:
+        np.save(os.path.join(path, "ba_pose.npy"), np.asarray(ba_pose[sel], np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=5, help="the --steps-long timed region is repeated this many times, each bracketed by barrier + "
-                    "synchronize; ms_per_step / value are the MEDIAN region's (SURVEY 8d), every region's figure is in repetitions_ms_per_step")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps before the timed region (at least; the warm-up also lasts "
+                    "at least WARMUP_S seconds)")
+    ap.add_argument("--full", action="store_true", help="measure more than the headline: the FAST kernel's roofline (events around it inside "
+                    "the timed regions), per-stage and matcher times, and at N = 1 the CPU comparators (--no-cpu), the local-BA secondary "
+                    "(--no-ba), the 720p roofline and the host-API latencies (--no-extras)")
+    ap.add_argument("--reps", type=int, default=None, help="the --steps-long timed region is repeated this many times (default 1, 5 with --full), "
+                    "each bracketed by barrier + synchronize; ms_per_step / value are the MEDIAN region's (SURVEY 8d), every region's figure "
+                    "is in repetitions_ms_per_step")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed to DIR/<name>.npy "
+                    "(dump_outputs)")
     # 256 streams per step: per-frame cost keeps falling with the batch (launch floor, ramp and tail of ~14 launches per step, the
     # octree's one long workgroup per frame, and the side stream's overlap all improve): 64 -> 218k frames/s, 128 -> 253k,
     # 256 -> 261k, 512 -> ~270k on one MI355X (DESIGN.md section 7); 256 keeps a step at one millisecond
     ap.add_argument("--batch", type=int, default=None, help="independent camera streams per GPU and step (default: 256 at VGA, 64 at 720p "
                     "as BASELINE configs[2] words it)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--scene", choices=["rich", "sparse"], default="rich",
                     help="synthetic frame content (synth.synth_frame): 'rich' is the benchmark's workload (about one pixel in eight is a FAST corner); "
                          "'sparse' has a few percent of corners and shows how much the FAST pass depends on content (DESIGN.md section 5)")
-    ap.add_argument("--no-ba", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the roofline_720p and latency blocks (A/B and profiling runs)")
+    ap.add_argument("--no-ba", action="store_true", help="--full: skip the local-BA secondary")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the roofline_720p and latency blocks (A/B and profiling runs)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL) for real runs; gloo only to rehearse the multi-rank flow with ranks sharing one GPU")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="vga",
@@ -393,6 +434,7 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group and run the collectives even on ONE rank (a one-GPU "
                     "test then drives RCCL: communicator, device-tensor all_gather_into_tensor, async work handles)")
     args = ap.parse_args()
+    full = args.full
     global W, H, NFEAT, FAST_BYTES_PER_FRAME
     W, H, NFEAT, FAST_BYTES_PER_FRAME, cfg_name = CONFIGS[args.config]
     pipeline = args.config == "pipeline"
@@ -550,19 +592,26 @@ def main():
             its += ba_take(ba.result(ba_jobs.pop(0)))
         return its
 
+    t_warm = time.perf_counter()
     for k in range(args.warmup):
         step(k)
+    k_next = args.warmup
+    torch.cuda.synchronize(dev)
+    while -shard.max_over_ranks(t_warm - time.perf_counter(), cdev, world) < WARMUP_S:   # every rank decides alike
+        for k in range(k_next, k_next + WARMUP_CHUNK):
+            step(k)
+        k_next += WARMUP_CHUNK
+        torch.cuda.synchronize(dev)
+    warmup_steps = k_next
     ba_drain()
     torch.cuda.synchronize(dev)
     ba_its[0] = 0
-    ext.profile(5)   # timed regions: events around the dominant kernel (FAST) only, on every 4th step
-    m0 = torch.cuda.Event(enable_timing=True)
-    m1 = torch.cuda.Event(enable_timing=True)
-    match_ms = 0.0
-    reps = max(1, args.reps if not pipeline else min(args.reps, 3))
+    if full:
+        ext.profile(5)   # timed regions: events around the dominant kernel (FAST) only, on every 4th step
+    reps = args.reps if args.reps is not None else (5 if full else 1)
+    reps = max(1, reps if not pipeline else min(reps, 3))
     regions, ba_regions = [], []
     last_slots = None
-    k_next = args.warmup
     for rep in range(reps):   # every region: EXACTLY --steps steps between barrier + synchronize pairs
         ba_its[0] = 0
         if world > 1:
@@ -586,29 +635,36 @@ def main():
     mid = sorted(range(reps), key=lambda i: regions[i])[reps // 2]   # the median region (same index on every rank: the times are the rank maxima)
     elapsed = regions[mid]
     ba_its_timed = ba_regions[mid]
-    stages = ext.profile(1)
-    # per-stage breakdown: a separate, untimed pass with events around every stage
-    for k in range(k_next, k_next + (1 if pipeline else 5)):
-        step(k)
-    if (world > 1 or args.force_dist) and not pipeline:
-        gather.flush()
-    if pipeline:
-        slots.flush()
-        ba_drain()
-    torch.cuda.synchronize(dev)
-    all_stages = ext.profile(0)
+    last = (k_next - 1) % NBUF
+    n_last = d_n[last].cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_kps[last].cpu().numpy(), d_desc[last].cpu().numpy(), n_last, d_idx.cpu().numpy(),
+                     d_best.cpu().numpy(), d_second.cpu().numpy(), last_ba["pose"] if pipeline else None)
+    if full:
+        stages = ext.profile(1)
+        # per-stage breakdown: a separate, untimed pass with events around every stage
+        for k in range(k_next, k_next + (1 if pipeline else 5)):
+            step(k)
+        if (world > 1 or args.force_dist) and not pipeline:
+            gather.flush()
+        if pipeline:
+            slots.flush()
+            ba_drain()
+        torch.cuda.synchronize(dev)
+        all_stages = ext.profile(0)
 
-    # matcher kernel time, measured separately on the same stream (it is one launch per step)
-    m0.record(torch.cuda.current_stream(dev))
-    for k in range(5):
-        api.ORBmatcher.best2_batch_dev(d_desc[0], d_n[0], d_desc[1], d_n[1], d_idx, d_best, d_second, cap,
-                                       device=dev.index, stream=stream)
-    m1.record(torch.cuda.current_stream(dev))
-    torch.cuda.synchronize(dev)
-    match_ms = m0.elapsed_time(m1) / 5
+        # matcher kernel time, measured separately on the same stream (it is one launch per step)
+        m0 = torch.cuda.Event(enable_timing=True)
+        m1 = torch.cuda.Event(enable_timing=True)
+        m0.record(torch.cuda.current_stream(dev))
+        for k in range(5):
+            api.ORBmatcher.best2_batch_dev(d_desc[0], d_n[0], d_desc[1], d_n[1], d_idx, d_best, d_second, cap,
+                                           device=dev.index, stream=stream)
+        m1.record(torch.cuda.current_stream(dev))
+        torch.cuda.synchronize(dev)
+        match_ms = m0.elapsed_time(m1) / 5
 
     # sanity of the timed work: every frame produced its keypoints and matches
-    n_last = d_n[(k_next - 1) % NBUF].cpu().numpy()
     assert (n_last >= NFEAT).all(), "extractor returned too few keypoints: %s" % n_last[:8]
     if pipeline:   # every stream's slot arrived on this rank, with its keypoints, descriptors and BA poses
         hdr = slots.header(last_slots).cpu().numpy()
@@ -618,10 +674,6 @@ def main():
         assert np.allclose((q * q).sum(2), 1.0, atol=1e-9), "BA slot poses are not unit quaternions"
 
     if rank == 0:
-        fast_ms, fast_calls = stages["fast"]
-        fast_avg_ms = fast_ms / max(fast_calls, 1)
-        achieved = FAST_BYTES_PER_FRAME * B / (fast_avg_ms * 1e-3) / 1e9 if fast_avg_ms > 0 else 0.0
-        traffic, traffic_src = measured_traffic(B) if args.config == "vga" else (None, "only collected for the vga configuration")
         out = {
             "metric": ("frames/sec ORB extract+match @%dx%dx8lvl" % (W, H)) + (" + per-stream local BA, %d streams" % args.streams if pipeline else ""),
             "value": round(world * B * args.steps / elapsed, 2),
@@ -629,10 +681,12 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "warmup_steps_run": warmup_steps,
             "ms_per_step": round(1e3 * elapsed / args.steps, 4),
             "repetitions": reps,
             "repetitions_ms_per_step": [round(1e3 * t / args.steps, 4) for t in regions],
-            "timing": "median of %d repetitions of the %d-step region, each bracketed by barrier + synchronize (max over ranks)" % (reps, args.steps),
+            "timing": ("median of %d repetitions of the %d-step region, each" % (reps, args.steps) if reps > 1 else "one %d-step region," % args.steps) +
+                      " bracketed by barrier + synchronize (max over ranks)",
             "higher_is_better": True,
             "scaling": "strong" if pipeline else "weak",
             "vs_baseline": None,
@@ -650,24 +704,29 @@ def main():
                        "ba_batches_in_flight": args.ba_workers if pipeline else None,
                        "parallelism": ("stream s on rank s %% %d, results gathered over RCCL" % world) if pipeline else
                                       "streams sharded over %d GPU(s), no data-path collective" % world},
-            "roofline": {"kernel": "fast_cells_kernel", "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
-                         "avg_launch_ms": round(fast_avg_ms, 5), "launches": fast_calls,
-                         "timing": "HIP events on the launch stream around every 4th launch of the timed region (an event pair drains the pipeline for ~20 us)",
-                         "algorithmic_bytes_per_launch": FAST_BYTES_PER_FRAME * B,
-                         "valu": measured_valu(B, fast_avg_ms, FAST_BYTES_PER_FRAME) if args.config == "vga" else None},
-            "stage_ms_per_step": {k: round(v[0] / max(v[1], 1), 4) for k, v in all_stages.items()},
-            "match_ms_per_step": round(match_ms, 4),
         }
         if pipeline:
             out["secondary"] = {"metric": "local-BA LM iterations/sec inside the pipeline (one window-8 window per stream and step)",
                                 "unit": "iters/s", "value": round(world * ba_its_timed / elapsed, 1), "note": "this rank's count x ranks"}
-        if not args.no_cpu and world == 1:   # CPU comparators: rank 0 at N = 1 only
+        if full:
+            fast_ms, fast_calls = stages["fast"]
+            fast_avg_ms = fast_ms / max(fast_calls, 1)
+            achieved = FAST_BYTES_PER_FRAME * B / (fast_avg_ms * 1e-3) / 1e9 if fast_avg_ms > 0 else 0.0
+            traffic, traffic_src = measured_traffic(B) if args.config == "vga" else (None, "only collected for the vga configuration")
+            out["roofline"] = {"kernel": "fast_cells_kernel", "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
+                               "avg_launch_ms": round(fast_avg_ms, 5), "launches": fast_calls,
+                               "timing": "HIP events on the launch stream around every 4th launch of the timed region (an event pair drains the pipeline for ~20 us)",
+                               "algorithmic_bytes_per_launch": FAST_BYTES_PER_FRAME * B,
+                               "valu": measured_valu(B, fast_avg_ms, FAST_BYTES_PER_FRAME) if args.config == "vga" else None}
+            out["stage_ms_per_step"] = {k: round(v[0] / max(v[1], 1), 4) for k, v in all_stages.items()}
+            out["match_ms_per_step"] = round(match_ms, 4)
+        if full and not args.no_cpu and world == 1:   # CPU comparators: rank 0 at N = 1 only
             out["cpu"] = cpu_info()
             out["cpu_baseline"] = cpu_baseline(fa, fb, NFEAT)
             out["speedup_vs_cpu_1core"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
             out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(fa, fb, NFEAT)
-        if world == 1 and args.config == "vga" and not args.no_extras:
+        if full and world == 1 and args.config == "vga" and not args.no_extras:
             # the driver's record also carries: the geometry the >= 70 % bar is stated on, and the host-pointer latencies
             try:
                 out["roofline_720p"] = roofline_720p(dev)
@@ -677,7 +736,7 @@ def main():
                 out["latency"] = host_api_latency(fa, fb)
             except Exception as e:
                 out["latency"] = {"error": repr(e)}
-        if not args.no_ba and world == 1 and not pipeline:
+        if full and not args.no_ba and world == 1 and not pipeline:
             out["secondary"] = ba_secondary(dev.index, args.steps, with_cpu=not args.no_cpu)
         print(json.dumps(out), flush=True)
     if pipeline:

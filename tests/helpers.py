@@ -75,6 +75,61 @@ def sim3_close(got, ref, tol=1e-5, strict_its=True):
         assert abs(a - b) <= 1e-4 * max(1.0, abs(b))
 
 
+REF_CASES_GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_g2o_cases.json.gz")
+
+
+def _jsonable(v):
+    if isinstance(v, np.ndarray):
+        return {"__array__": v.dtype.str, "shape": list(v.shape), "data": v.ravel().tolist()}
+    if isinstance(v, dict):
+        return {k: _jsonable(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_jsonable(x) for x in v]
+    if isinstance(v, np.generic):
+        return v.item()
+    return v
+
+
+def _from_json(d):
+    if "__array__" in d:
+        return np.array(d["data"], dtype=np.dtype(d["__array__"])).reshape(d["shape"])
+    return d
+
+
+def problem_crc(prob):
+    """Fingerprint of a synthesized problem: its arrays and numeric scalars, in key order (nested ground truth left out)."""
+    parts = [np.ascontiguousarray(v).tobytes() if isinstance(v, np.ndarray) else repr(v).encode()
+             for v in (prob[k] for k in sorted(prob)) if isinstance(v, (np.ndarray, int, float))]
+    return crc32(b"".join(parts))
+
+
+def save_ref_cases(cases):
+    """cases: {key: (problem, reference result)} -> tests/golden/ref_g2o_cases.json.gz (tools/gen_ref_cases_golden.py).
+    JSON keeps every float exactly (shortest round-trip repr) and the result dicts' nesting as it is."""
+    import gzip
+    import json
+    doc = {k: {"problem_crc": problem_crc(p), "result": _jsonable(r)} for k, (p, r) in sorted(cases.items())}
+    with gzip.GzipFile(REF_CASES_GOLDEN, "wb", mtime=0) as f:
+        f.write(json.dumps(doc, sort_keys=True).encode())
+
+
+_ref_cases = None
+
+
+def ref_case(key, prob):
+    """The reference g2o's stored result for `key`, solved on `prob`; fails loudly when the synthesized problem is not the
+    one the result was made from."""
+    global _ref_cases
+    if _ref_cases is None:
+        import gzip
+        import json
+        with gzip.open(REF_CASES_GOLDEN, "rb") as f:
+            _ref_cases = json.loads(f.read().decode(), object_hook=_from_json)
+    case = _ref_cases[key]
+    assert case["problem_crc"] == problem_crc(prob), "the problem of %s changed: regenerate with tools/gen_ref_cases_golden.py" % key
+    return case["result"]
+
+
 ORB_GOLDEN = ("vga", "vga2000", "720p")
 
 

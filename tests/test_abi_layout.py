@@ -47,7 +47,7 @@ def test_no_compute_without_gpu_fails_loudly():
     assert rc == -2
 
 
-def test_struct_layouts_match_the_header():
+def test_struct_layouts_match_the_header(tmp_path):
     from weiner_slamit_v2_amd import api
 
     src = r'''
@@ -63,11 +63,9 @@ def test_struct_layouts_match_the_header():
                sizeof(slamit_sim3_problem), offsetof(slamit_sim3_problem, fix_scale), sizeof(slamit_sim3_result), offsetof(slamit_sim3_result, inlier));
         return 0;
     }'''
-    d = os.path.join(ROOT, "gpurun_out")
-    os.makedirs(d, exist_ok=True)
-    c = os.path.join(d, "_layout.c")
+    c = str(tmp_path / "_layout.c")
     open(c, "w").write(src)
-    exe = os.path.join(d, "_layout")
+    exe = str(tmp_path / "_layout")
     subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), c, "-o", exe])  # the header is plain C
     sizes = [int(v) for v in subprocess.check_output([exe]).split()]
     assert sizes[0] == 28 == api.KP_DTYPE.itemsize

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +22,7 @@ def _line(out):
 
 
 def test_bench_line_schema_single_gpu():
-    out = subprocess.check_output([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--no-cpu", "--no-ba"], cwd=ROOT,
+    out = subprocess.check_output([sys.executable, "bench.py", "--full", "--steps", "4", "--warmup", "1", "--no-cpu", "--no-ba"], cwd=ROOT,
                                   stderr=subprocess.STDOUT, timeout=300)
     d = _line(out)
     for k in REQUIRED:
@@ -32,6 +33,48 @@ def test_bench_line_schema_single_gpu():
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-4 and r["launches"] >= 1
     frames = d["config"]["frames_per_step_per_gpu"]
     assert frames == 256 and abs(d["value"] - frames * 4 / (d["ms_per_step"] * 4e-3)) / d["value"] < 0.01
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run times exactly --steps steps, reports only the headline, and --dump-outputs writes what the last timed step
+    handed its caller: one stream's keypoints, descriptors and matches are the CPU oracle's on that stream's two frames."""
+    from oracle import bindings as ob
+    from weiner_slamit_v2_amd import synth
+
+    steps, warmup = 3, 1
+    out = subprocess.check_output([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                                   "--dump-outputs", str(tmp_path)], cwd=ROOT, stderr=subprocess.STDOUT, timeout=300)
+    d = _line(out)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == steps and d["repetitions"] == 1 and len(d["repetitions_ms_per_step"]) == 1 and d["dtype"] == "u8"
+    assert abs(d["value"] - 256 * steps / (d["ms_per_step"] * steps * 1e-3)) / d["value"] < 0.01
+    for k in ("roofline", "stage_ms_per_step", "match_ms_per_step", "cpu_baseline", "secondary", "roofline_720p", "latency"):
+        assert k not in d, k   # --full only
+    names = sorted(os.listdir(tmp_path))
+    assert sum(os.path.getsize(tmp_path / f) for f in names) <= 64e6
+    z = {f[:-4]: np.load(tmp_path / f) for f in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in z.values())
+    assert set(z) == {"stream_index", "n_keypoints", "keypoints", "descriptors", "match_index", "match_best", "match_second"}
+    assert (z["n_keypoints"] >= 1000).all()
+    # the last timed step (its index has the parity of warmup + steps - 1, odd: the warm-up grows by an even number of steps)
+    # extracts stream s's frame B and matches it against its frame A
+    assert (warmup + steps - 1) % 2 == 1 and (d["warmup_steps_run"] - warmup) % 2 == 0
+    row = len(z["stream_index"]) // 2
+    s = int(z["stream_index"][row])
+    fa = synth.synth_frame(640, 480, s % 16)
+    fb = synth.warp_frame(fa, s % 16)
+    orc = ob.OrbOracle(1000, 1.2, 8, 20, 7)
+    ka, da = orc.extract(fa)
+    kb, db = orc.extract(fb)
+    n = int(z["n_keypoints"][row])
+    assert n == len(kb) and (z["keypoints"][row, n:] == 0).all()
+    for c, f in enumerate(("x", "y", "size", "angle", "response", "octave", "class_id")):
+        assert np.array_equal(z["keypoints"][row, :n, c], kb[f].astype(np.float32)), f
+    assert np.array_equal(z["descriptors"][row, :n], db.astype(np.float32))
+    oi, obest, osec = ob.best2(db, da)
+    assert np.array_equal(z["match_index"][row, :n], oi) and np.array_equal(z["match_best"][row, :n], obest)
+    assert np.array_equal(z["match_second"][row, :n], osec)
 
 
 def test_bench_two_rank_rehearsal():

@@ -1,8 +1,8 @@
 """Pins the BA oracle (oracle/ba_oracle.cc) to the REFERENCE's own g2o.
 
 tests/golden/ba_*.npz were produced by tools/gen_ba_golden.py from g2o + Eigen compiled out of
-/root/reference (oracle/Makefile.ref); where that build exists (authoring container) the oracle
-is also compared with it live on fresh problems.
+the reference sources (oracle/Makefile.ref).  The oracle is also compared on fresh synthesized problems with that
+g2o's results on them (tests/golden/ref_g2o_cases.json.gz), and live where the build exists.
 """
 import glob
 import os
@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import bindings as ob
-from tests.helpers import ROOT, load_ba_golden
+from tests.helpers import ROOT, load_ba_golden, ref_case
 from weiner_slamit_v2_amd import synth
 
 GOLDEN = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "ba_*.npz")))
@@ -60,11 +60,18 @@ def test_golden_set_is_complete():
     assert ref["stats"]["n_its"][1] < 10            # Raul's stop rule fired (levenberg.cpp:155-161)
 
 
-@pytest.mark.skipif(not ob.ba_ref_available(), reason="reference g2o build (oracle/_ref) not present")
-@pytest.mark.parametrize("k,p,o,seed,nfix", [(6, 80, 3, 21, 1), (9, 120, 5, 22, 2), (20, 400, 6, 23, 1), (15, 250, None, 24, 1)])
+# (keyframes, points, observations per point, seed, fixed keyframes); the reference g2o's results on these problems are stored
+# in tests/golden/ref_g2o_cases.json.gz (tools/gen_ref_cases_golden.py)
+REF_CASES = [(6, 80, 3, 21, 1), (9, 120, 5, 22, 2), (20, 400, 6, 23, 1), (15, 250, None, 24, 1)]
+
+
+@pytest.mark.parametrize("k,p,o,seed,nfix", REF_CASES)
 def test_vs_reference_g2o(k, p, o, seed, nfix):
     prob = synth.synth_ba(k, p, o, seed=seed, n_fixed=nfix)
-    _compare(ob.ba_solve(prob), ob.ba_ref_solve(prob))
+    res = ob.ba_solve(prob)
+    _compare(res, ref_case("ba%s" % ((k, p, o, seed, nfix),), prob))
+    if ob.ba_ref_available():   # where the reference's g2o is built: also against it live
+        _compare(res, ob.ba_ref_solve(prob))
 
 
 def test_schedule_options_and_stop_flag():
@@ -115,10 +122,20 @@ def test_sim3_golden_set_covers_the_branches():
     assert ref["s12"] == 1.0                                                   # bFixScale: the scale never moves
 
 
-@pytest.mark.skipif(not ob.ba_ref_available(), reason="reference g2o build (oracle/_ref) only exists in the authoring container")
+SIM3_REF_SEEDS = range(20, 26)
+
+
+def sim3_ref_problem(seed):
+    return synth.synth_sim3(int(40 + 70 * (seed % 5)), 0.1 * (seed % 4), seed, 0.02 + 0.02 * (seed % 3), fix_scale=(seed % 5 == 0))
+
+
 def test_sim3_oracle_matches_live_reference_g2o():
+    """Fresh problems against the reference g2o's stored results on them, and live where its build exists."""
     from tests.helpers import sim3_close
 
-    for seed in range(20, 26):
-        pr = synth.synth_sim3(int(40 + 70 * (seed % 5)), 0.1 * (seed % 4), seed, 0.02 + 0.02 * (seed % 3), fix_scale=(seed % 5 == 0))
-        sim3_close(ob.sim3_solve(pr), ob.sim3_ref_solve(pr), tol=1e-6)
+    for seed in SIM3_REF_SEEDS:
+        pr = sim3_ref_problem(seed)
+        res = ob.sim3_solve(pr)
+        sim3_close(res, ref_case("sim3(%d,)" % seed, pr), tol=1e-6)
+        if ob.ba_ref_available():
+            sim3_close(res, ob.sim3_ref_solve(pr), tol=1e-6)

@@ -1,5 +1,6 @@
 """Pins the PoseOptimization oracle (oracle/ba_oracle.cc:pose_oracle_solve) to the reference's g2o:
-golden vectors from tools/gen_pose_golden.py, plus a live comparison where oracle/_ref exists."""
+golden vectors from tools/gen_pose_golden.py, and fresh synthesized problems against that g2o's stored results on them
+(live as well where oracle/_ref exists)."""
 import glob
 import os
 
@@ -7,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import bindings as ob
-from tests.helpers import ROOT, load_pose_golden
+from tests.helpers import ROOT, load_pose_golden, ref_case
 from weiner_slamit_v2_amd import synth
 
 GOLDEN = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "pose_*.npz")))
@@ -35,11 +36,18 @@ def test_golden_covers_the_edge_cases():
     assert r["n_inliers"] == 0 and np.array_equal(r["pose"], p["pose"])
 
 
-@pytest.mark.skipif(not ob.ba_ref_available(), reason="reference g2o build (oracle/_ref) not present")
-@pytest.mark.parametrize("n,of,seed,pert", [(250, 0.2, 31, 0.03), (900, 0.4, 32, 0.08), (12, 0.0, 33, 0.02)])
+# (observations, outlier fraction, seed, pose perturbation); the reference g2o's results on these problems are stored in
+# tests/golden/ref_g2o_cases.json.gz (tools/gen_ref_cases_golden.py)
+REF_CASES = [(250, 0.2, 31, 0.03), (900, 0.4, 32, 0.08), (12, 0.0, 33, 0.02)]
+
+
+@pytest.mark.parametrize("n,of,seed,pert", REF_CASES)
 def test_vs_reference_g2o(n, of, seed, pert):
     prob = synth.synth_pose(n, of, seed, pert)
-    compare_pose(ob.pose_solve(prob), ob.pose_ref_solve(prob))
+    res = ob.pose_solve(prob)
+    compare_pose(res, ref_case("pose%s" % ((n, of, seed, pert),), prob))
+    if ob.ba_ref_available():   # where the reference's g2o is built: also against it live
+        compare_pose(res, ob.pose_ref_solve(prob))
 
 
 def test_recovers_the_pose_and_the_outliers():

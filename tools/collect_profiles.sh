@@ -21,7 +21,7 @@ done
 # local BA: kernel stats and matrix-core counters, single windows and batches (tools/bench_ba.py runs both)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ba_trace -- python3 tools/bench_ba.py 3 > $OUT/ba_trace.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_MFMA SQ_WAVE_CYCLES SQ_WAVES --output-format csv -d $OUT/ba_mfma -- python3 tools/bench_ba.py 2 > $OUT/ba_mfma.log 2>&1 || true
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
-python3 bench.py --config 720p --no-ba > $OUT/bench_720p.json 2> $OUT/bench_720p.err
-python3 bench.py --config pipeline --no-cpu > $OUT/bench_pipeline.json 2> $OUT/bench_pipeline.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full --config 720p --no-ba > $OUT/bench_720p.json 2> $OUT/bench_720p.err
+python3 bench.py --full --config pipeline --no-cpu > $OUT/bench_pipeline.json 2> $OUT/bench_pipeline.err
 tail -1 $OUT/bench.json | cut -c1-300

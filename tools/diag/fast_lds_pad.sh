@@ -4,6 +4,6 @@
 export PYTHONPATH=$PWD TMPDIR=/tmp
 for rep in 1 2; do
   for pad in 0 2000 3800 6000; do
-    SLAMIT_FAST_LDS_PAD=$pad SLAMIT_LIB=$PWD/tools/diag/libpad.so python3 bench.py --no-ba --no-cpu --no-extras --steps 40 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('pad $pad', round(d['value']), d['ms_per_step'], d['roofline']['kernel_ms'] if 'kernel_ms' in d['roofline'] else d['roofline'])"
+    SLAMIT_FAST_LDS_PAD=$pad SLAMIT_LIB=$PWD/tools/diag/libpad.so python3 bench.py --full --no-ba --no-cpu --no-extras --steps 40 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('pad $pad', round(d['value']), d['ms_per_step'], d['roofline']['kernel_ms'] if 'kernel_ms' in d['roofline'] else d['roofline'])"
   done
 done

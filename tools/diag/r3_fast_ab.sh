@@ -12,5 +12,5 @@ for v in "$@"; do
 done
 tools/diag/ab.sh tools/diag/libbase.so $ok 2>&1 | tee $O/ab.txt
 for lib in tools/diag/libbase.so $ok; do
-  SLAMIT_LIB=$PWD/$lib python3 bench.py --config 720p --no-ba --no-cpu --steps 10 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('720p $lib', round(d['value']), d['ms_per_step'], d['roofline'])" | tee -a $O/ab.txt
+  SLAMIT_LIB=$PWD/$lib python3 bench.py --full --config 720p --no-ba --no-cpu --steps 10 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('720p $lib', round(d['value']), d['ms_per_step'], d['roofline'])" | tee -a $O/ab.txt
 done
