@@ -129,7 +129,7 @@ def test_banded_windows_in_lds_and_through_the_blocked_path(opt, k, p, o, seed, 
     assert (res["edge_outlier"] == d["edge_outlier"]).all() and list(d["n_its"]) == list(res["stats"]["n_its"])
 
 
-def test_schur_over_floating_windows_and_over_tile_pairs(monkeypatch):
+def test_schur_over_floating_windows_and_over_tile_pairs_one_handle_per_setting(monkeypatch):
     """The Schur product of a window whose k slabs each touch <= 63 rows runs over floating row windows (BaWin::sf_*, csrc/ba_api.hip:
     groups of slabs, one 64 x 64 partial tile each); SLAMIT_BA_SF=0 sends the same window through the 64 x 64 tile pairs.  Both give the
     same poses, points, flags and LM path, the floating form executes fewer flops, and a window it cannot take (dense visibility; ten keyframes
@@ -139,19 +139,20 @@ def test_schur_over_floating_windows_and_over_tile_pairs(monkeypatch):
              synth.synth_ba(12, 300, 4, seed=43), synth.synth_ba(41, 900, 5, seed=45), synth.synth_ba(50, 1000, 2, seed=47), synth.synth_ba(23, 500, 9, seed=48),
              synth.synth_ba(50, 500, None, seed=22), synth.synth_ba(5, 1500, 2, seed=49), synth.synth_ba(30, 800, 6, seed=44, stereo_frac=0.6)]
     probs += [synth.synth_ba(10 + 2 * i, 150 + 30 * i, 3 + i, seed=60 + i) for i in range(6)]   # 16 windows: a batch's launch shapes (eight splits, pose blocks on their own)
-    opt = api.Optimizer(max_kf=64, max_pt=2048, max_edge=110000, max_batch=16)
 
     def run(**env):
         for k in ("SLAMIT_BA_SF", "SLAMIT_BA_SF_CAP"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
+        opt = api.Optimizer(max_kf=64, max_pt=2048, max_edge=110000, max_batch=16)   # (a handle reads the switches when it is created)
         opt.profile(True)
         single = [opt.LocalBundleAdjustment(probs[0])]
         mflop1 = opt.profile_read()["schur_exec_mflop"]   # (of the window-8 window)
         single += [opt.LocalBundleAdjustment(q) for q in probs[1:3]]
         batch = opt.LocalBundleAdjustmentBatch(probs)
         opt.profile(False)
+        opt.close()
         return single, batch, mflop1
 
     s_tile, b_tile, m_tile = run(SLAMIT_BA_SF="0")
@@ -166,7 +167,6 @@ def test_schur_over_floating_windows_and_over_tile_pairs(monkeypatch):
             assert (a["edge_outlier"] == b["edge_outlier"]).all() and a["stats"]["n_its"] == b["stats"]["n_its"] and a["stats"]["trials"] == b["stats"]["trials"], (env, i)
     for i, (q, o) in enumerate(zip(probs, b_sf)):
         _close(o, ob.ba_solve(q), "sf[%d]" % i, prob=q)
-    opt.close()
 
 
 def _shuffle_keyframes(prob, seed):
@@ -182,7 +182,7 @@ def _shuffle_keyframes(prob, seed):
     return q, perm
 
 
-def test_keyframes_listed_out_of_trajectory_order(opt, monkeypatch):
+def test_keyframes_listed_out_of_trajectory_order_one_handle_per_setting(opt, monkeypatch):
     """ORB-SLAM2 lists a local window by co-visibility weight, not along the trajectory (Optimizer.cc:456-470): the reduced system of such a
     list has its couplings scattered.  ba_order_columns (csrc/ba_api.hip) renumbers the free keyframes by reverse Cuthill-McKee when that narrows the
     band, so the shuffled window-8 window takes the banded solve and the floating-window Schur product like the ordered one (executed flops
@@ -195,11 +195,14 @@ def test_keyframes_listed_out_of_trajectory_order(opt, monkeypatch):
     m_base = opt.profile_read()["schur_exec_mflop"]
     r_shuf = opt.LocalBundleAdjustment(shuf)
     m_shuf = opt.profile_read()["schur_exec_mflop"]
-    monkeypatch.setenv("SLAMIT_BA_KEEP_ORDER", "1")
-    r_keep = opt.LocalBundleAdjustment(shuf)
-    m_keep = opt.profile_read()["schur_exec_mflop"]
-    monkeypatch.delenv("SLAMIT_BA_KEEP_ORDER")
     opt.profile(False)
+    monkeypatch.setenv("SLAMIT_BA_KEEP_ORDER", "1")
+    keep = api.Optimizer(max_kf=64, max_pt=2048, max_edge=110000, max_batch=4)   # (a handle reads the switches when it is created)
+    monkeypatch.delenv("SLAMIT_BA_KEEP_ORDER")
+    keep.profile(True)
+    r_keep = keep.LocalBundleAdjustment(shuf)
+    m_keep = keep.profile_read()["schur_exec_mflop"]
+    keep.close()
     assert m_shuf <= 1.5 * m_base and m_keep >= 5 * m_base, (m_base, m_shuf, m_keep)
     ref = ob.ba_solve(shuf)
     _close(r_shuf, ref, "shuffled")

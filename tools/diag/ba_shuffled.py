@@ -13,15 +13,16 @@ shuf = dict(base)
 for k in ("kf_pose", "kf_fixed", "kf_intr"):
     shuf[k] = np.ascontiguousarray(np.asarray(base[k])[perm])
 shuf["edge_kf"] = inv[np.asarray(base["edge_kf"])].astype(np.int32)
-opt = api.Optimizer(64, 2048, len(base["edge_kf"]) + 64, 1, 0)
 
 
 def run(tag, prob):
+    opt = api.Optimizer(64, 2048, len(base["edge_kf"]) + 64, 1, 0)   # (reads the switches when it is created)
     opt.LocalBundleAdjustment(prob)
     ts = []
     for _ in range(10):
         t0 = time.perf_counter(); out = opt.LocalBundleAdjustment(prob); ts.append(time.perf_counter() - t0)
     print("%-34s %.3f ms  its %s" % (tag, 1e3 * sorted(ts)[5], out["stats"]["n_its"]))
+    opt.close()
 
 
 run("along the trajectory", base)

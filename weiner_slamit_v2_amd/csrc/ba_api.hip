@@ -26,7 +26,7 @@ hipError_t bak_prepare(int Npad);
 void bak_import(hipStream_t st, BaWin* wins, const BaIo* io, int max_kf, int max_pt, int max_edge, int Npad, int nwin);
 void bak_stage_begin(hipStream_t st, BaWin* wins, int nwin, int max_edge, int stage, int max_it, int robust, bool gate);
 void bak_slot(hipStream_t st, BaWin* wins, int nwin, int max_kf, int max_pt, int max_edge, int Npad, bool first, unsigned solvers, hipEvent_t* ev);
-int bak_solver_kind(int n, int band);
+int bak_solver_kind(int n, int band, bool no_band);
 int bak_nsplit(int nwin);
 void bak_final(hipStream_t st, BaWin* wins, const BaIo* io, int nwin, int max_kf, int max_pt, int max_edge);
 
@@ -55,6 +55,7 @@ struct slamit_ba {
     bool prof;
     std::vector<hipEvent_t> pev;
     slamit_ba_profile_out prof_last;
+    SlamitSwitches sw;         // the environment switches, read when the handle is created
 };
 
 namespace {
@@ -136,6 +137,7 @@ int slamit_ba_create(int max_kf, int max_pt, int max_edge, int max_batch, int de
     SLAMIT_USE_DEVICE(device);
     slamit_ba* h = new slamit_ba();
     h->device = device;
+    h->sw = slamit_read_switches();
     h->max_kf = max_kf; h->max_pt = max_pt; h->max_edge = max_edge; h->max_batch = max_batch;
     h->Npad_max = (int)rup((size_t)6 * max_kf + 1, BA_TILE);
     h->Kpad_max = (int)rup((size_t)3 * max_pt, (size_t)BA_KC * BA_SPLITS);
@@ -195,12 +197,12 @@ int slamit_ba_solve_batch(slamit_ba* h, int nwin, const slamit_ba_problem* probs
 // GetVectorCovisibleKeyFrames) instead of along the trajectory gives the same graph in a scattered order.  If a reverse Cuthill-McKee
 // order of the co-visibility graph (free keyframes; an edge = a shared point) has a narrower band than the caller's, `col` is renumbered
 // to it; g2o orders the same system by approximate minimum degree (linear_solver_eigen.h:77-92) -- any order gives the same solution up
-// to rounding.  The caller's order is kept when the banded solve takes it as it is, or when no order is narrower (SLAMIT_BA_KEEP_ORDER=1: always).
+// to rounding.  The caller's order is kept when the banded solve takes it as it is, or when no order is narrower (`keep_order`: always).
 // `span` = the widest point of the caller's order (last - first column it is seen from), `complete` = some point is seen from every
 // free keyframe (the graph is complete: no order is narrower): both come out of the pass over the edges the caller makes anyway, and
 // decide without one of their own -- an order whose band the banded solve already takes (<= 9 keyframes) is kept as it is.
-static bool ba_order_columns(const slamit_ba_problem& P, int32_t* col, int nfree, int span, bool complete) {
-    if (nfree < 3 || complete || 6 * span + 5 <= 59 || getenv("SLAMIT_BA_KEEP_ORDER")) return false;
+static bool ba_order_columns(const slamit_ba_problem& P, int32_t* col, int nfree, int span, bool complete, bool keep_order) {
+    if (nfree < 3 || complete || 6 * span + 5 <= 59 || keep_order) return false;
     const int W64 = (nfree + 63) / 64;
     std::vector<uint64_t> adj((size_t)nfree * W64, 0), seen((size_t)std::max(P.n_pt, 1) * W64, 0);
     for (int e = 0; e < P.n_edge; ++e) {
@@ -260,7 +262,6 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
     if (nwin == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(h->device);
     hipStream_t st = h->stream;
-    static const bool timing = getenv("SLAMIT_BA_TIMING") != nullptr;   // diagnostic: host phases of the call on stderr
     const auto tclk = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_in = tclk();
     double t_val = 0, t_prep = 0, t_queue = 0, t_loop = 0;
@@ -353,7 +354,7 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
                 if (maxc[p2] >= 0) span = std::max(span, maxc[p2] - minc[p2]);
                 complete = complete || (maxc[p2] - minc[p2] + 1 == nfree && seen_by[p2] >= nfree);
             }
-            if (ba_order_columns(P, col, nfree, span, complete)) {   // renumbered: the points' column ranges once more
+            if (ba_order_columns(P, col, nfree, span, complete, h->sw.ba_keep_order)) {   // renumbered: the points' column ranges once more
                 std::fill(minc.begin(), minc.end(), INT32_MAX); std::fill(maxc.begin(), maxc.end(), -1);
                 for (int e = 0; e < P.n_edge; ++e) {
                     const int c = col[P.edge_kf[e]], p2 = P.edge_pt[e];
@@ -406,12 +407,10 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
             int band = 0;   // a window whose keyframes only share points with their neighbours has a narrow band: LDLt inside LDS
             for (int c = 0; c < nfree; ++c) band = std::max(band, 6 * c + 5 - 6 * fcol[c]);
             w.band = std::min(band, std::max(n - 1, 0));
-            w.solver = bak_solver_kind(n, w.band);
+            w.solver = bak_solver_kind(n, w.band, h->sw.ba_no_band);
             // ---- the Schur product over floating row windows (BaWin::sf_*), when every k slab's rows fit one ----
             w.sf_groups = 0;
-            const char* sf_env = getenv("SLAMIT_BA_SF");        // 0: always the tiled product (A/B runs and the tests that compare the two)
-            const char* cap_env = getenv("SLAMIT_BA_SF_CAP");   // slabs per group
-            if (!(sf_env && atoi(sf_env) == 0) && nfree > 0) {
+            if (!h->sw.ba_no_sf && nfree > 0) {
                 const int nslab_all = w.Kpad / BA_KC;
                 std::vector<int32_t> slo(nslab_all, INT32_MAX), shi(nslab_all, -1);
                 for (int pn = 0; pn < P.n_pt; ++pn) {
@@ -423,7 +422,7 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
                     }
                 }
                 // a single window wants many short workgroups (latency), a batch fewer partial tiles to write and to add
-                const int cap = cap_env && atoi(cap_env) > 0 ? atoi(cap_env) : nwin >= 16 ? 8 : 4;
+                const int cap = h->sw.ba_sf_cap > 0 ? h->sw.ba_sf_cap : nwin >= 16 ? 8 : 4;
                 const int maxg = (int)std::min<size_t>(std::min<size_t>(BA_SF_MAXG, (size_t)BA_SPLITS * h->Npad_max * h->Npad_max / (BA_TILE * BA_TILE)),   // what `part` holds
                                                        (size_t)(T * (T + 1) / 2) * bak_nsplit(nwin));                                          // workgroups of the launch
                 bool ok = true;
@@ -555,16 +554,14 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
         int budget = its * 10 + 1;  // at most 10 LM trials per iteration
         int cur = 0, pending = -1;
         bool all_done = false, first = true;
-        static const int chunk_env = getenv("SLAMIT_BA_CHUNK") ? atoi(getenv("SLAMIT_BA_CHUNK")) : 0;   // > 0: fixed chunk size (A/B runs)
         while (!all_done) {
             if (opts->stop && *opts->stop) { stopped = true; break; }
             if (budget > 0) {
-                const int want = chunk_env > 0 ? chunk_env : first ? std::max(1, std::min(stage == 0 ? its : 3, std::min(its, 4))) : 1;
+                const int want = first ? std::max(1, std::min(stage == 0 ? its : 3, std::min(its, 4))) : 1;
                 const int nslots = std::min(want, budget);
                 const bool was_first = first;
                 first = false;
-                static const bool no_fuse = getenv("SLAMIT_BA_NO_FUSE") && atoi(getenv("SLAMIT_BA_NO_FUSE"));   // A/B runs: every slot as the first
-                for (int sl = 0; sl < nslots; ++sl) bak_slot(st, h->d_wins, nwin, mk, mp, me, Npad, (was_first && sl == 0) || no_fuse, solvers, slot_events());
+                for (int sl = 0; sl < nslots; ++sl) bak_slot(st, h->d_wins, nwin, mk, mp, me, Npad, was_first && sl == 0, solvers, slot_events());
                 budget -= nslots;
                 HIP_TRY(hipMemcpyAsync(hs[cur], reinterpret_cast<BaState*>(h->d_wins) - nwin, sizeof(BaState) * nwin, hipMemcpyDeviceToHost, st));   // (reverse order: only `done` of all is read)
                 HIP_TRY(hipEventRecord(h->ev[cur], st));
@@ -612,8 +609,8 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
             if (R.edge_stage1_outlier) memcpy(R.edge_stage1_outlier, H.out_out1, (size_t)P.n_edge);
         }
         const BaState& S0 = *H.out_state;
-        if (b == 0 && getenv("SLAMIT_BA_DIAG_WAVES")) fprintf(stderr, "[ba diag] busy cycles of waves 0..7: %llu %llu %llu %llu %llu %llu %llu %llu\n", S0.dbg[0], S0.dbg[1], S0.dbg[2], S0.dbg[3], S0.dbg[4], S0.dbg[5], S0.dbg[6], S0.dbg[7]);
-        if (b == 0 && getenv("SLAMIT_BA_DIAG")) {  // diagnostic builds only: in-kernel clock and phases of the last LDLt launch
+        if (b == 0 && h->sw.ba_diag_waves) fprintf(stderr, "[ba diag] busy cycles of waves 0..7: %llu %llu %llu %llu %llu %llu %llu %llu\n", S0.dbg[0], S0.dbg[1], S0.dbg[2], S0.dbg[3], S0.dbg[4], S0.dbg[5], S0.dbg[6], S0.dbg[7]);
+        if (b == 0 && h->sw.ba_diag) {  // diagnostic builds only: in-kernel clock and phases of the last LDLt launch
             fprintf(stderr, "[ba diag] ldlt shader cycles %llu, realtime ticks (100 MHz) %llu -> %.0f MHz, %.1f us\n",
                     S0.dbg[2] - S0.dbg[0], S0.dbg[3] - S0.dbg[1],
                     100.0 * (double)(S0.dbg[2] - S0.dbg[0]) / (double)(S0.dbg[3] - S0.dbg[1] + 1), (double)(S0.dbg[3] - S0.dbg[1]) / 100.0);
@@ -640,7 +637,7 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
         work();
         for (std::thread& t : pool) t.join();
     }
-    if (timing) {
+    if (h->sw.ba_timing) {   // diagnostic: host phases of the call on stderr
         const double t_out = tclk();
         fprintf(stderr, "[ba timing] %d windows: validate %.3f | prepare + pack %.3f | queue uploads %.3f | LM loop %.3f | download + unpack %.3f ms\n",
                 nwin, t_val - t_in, t_prep - t_val, t_queue - t_prep, t_loop - t_queue, t_out - t_loop);

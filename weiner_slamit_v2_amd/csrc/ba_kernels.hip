@@ -1356,7 +1356,6 @@ __global__ __launch_bounds__(LD_THREADS) void k_ldlt_blocked(BaWin* wins) {
         }
         // trailing update on MFMA: C[r][c] -= sum_k (w[r][k] invd[k]) w[c][k],  c <= r
         STAMP(3);
-#ifndef LD_DIAG_SKIP_TRAIL
         const int RT = rows16 >> 4, CT = (below + 15) >> 4;
         // lower-triangular tile list in row-major order: t -> (rt, ct), ct <= min(rt, CT-1).  Each wave takes a
         // contiguous run of it, so the A fragments (-w[r][k] / d_k, 8 doubles per lane) are loaded once per row tile
@@ -1418,7 +1417,6 @@ __global__ __launch_bounds__(LD_THREADS) void k_ldlt_blocked(BaWin* wins) {
                 }
             }
         }
-#endif
         __syncthreads();
         STAMP(4);
 #undef GROW
@@ -1427,7 +1425,6 @@ __global__ __launch_bounds__(LD_THREADS) void k_ldlt_blocked(BaWin* wins) {
         if (tid == 0) st->ok2 = 0;
         return;
     }
-#ifndef LD_DIAG_SKIP_BACK
     // ---- backward substitution x = L^-T y, y = row n of S ----
     // Right-looking over 32-row blocks from the bottom: wavefront 0 solves the block's triangular
     // system (lane k owns x_k, columns of L11 in registers, v_readlane broadcasts), then every
@@ -1480,7 +1477,6 @@ __global__ __launch_bounds__(LD_THREADS) void k_ldlt_blocked(BaWin* wins) {
         __syncthreads();
     }
     for (int i = tid; i < n; i += LD_THREADS) W.rhs[i] = xs[i];
-#endif
 #ifdef BA_DIAG_STAMPS
     STAMP(5);
     if (tid == 0) { st->dbg[2] = __builtin_amdgcn_s_memtime(); st->dbg[3] = __builtin_amdgcn_s_memrealtime();
@@ -1770,9 +1766,8 @@ hipError_t bak_prepare(int Npad) {
     return e;
 }
 
-// the reduced solve a window takes (host): its structure decides
-int bak_solver_kind(int n, int band) {
-    static const bool no_band = getenv("SLAMIT_BA_NO_BAND") != nullptr;   // A/B and parity runs: no window through the banded kernel
+// the reduced solve a window takes (host): its structure decides (`no_band`: SLAMIT_BA_NO_BAND, every window takes the blocked kernel)
+int bak_solver_kind(int n, int band, bool no_band) {
     if (!no_band && ldlt_band_ok(n, band)) return BA_SOLVER_BAND;
     return BA_SOLVER_BLOCKED;
 }
@@ -1792,10 +1787,9 @@ void bak_stage_begin(hipStream_t st, BaWin* wins, int nwin, int max_edge, int st
 }
 
 // split-K of the tiled Schur product (gridDim.y of its launch): a batch brings its own parallelism (64 windows: 2 / 4 / 8 / 16 splits -> 47.8k /
-// 49.7k / 52.8k / 50.0k LM it/s).  (SLAMIT_BA_NSPLIT: A/B runs.)
+// 49.7k / 52.8k / 50.0k LM it/s)
 int bak_nsplit(int nwin) {
-    static const int nsplit_env = getenv("SLAMIT_BA_NSPLIT") ? atoi(getenv("SLAMIT_BA_NSPLIT")) : 0;
-    return nsplit_env >= 1 && nsplit_env <= BA_SPLITS ? nsplit_env : nwin >= 16 ? 8 : BA_SPLITS;
+    return nwin >= 16 ? 8 : BA_SPLITS;
 }
 
 // one LM trial slot for every window of the batch

@@ -340,12 +340,9 @@ __global__ __launch_bounds__(64) void distinctive_kernel(const uint8_t* __restri
     if (lane == 0) { best_idx[p] = (int)(bestkey & 0xFFFF); best_median[p] = (int)(bestkey >> 16); }
 }
 
-// the matrix-core kernel carries the train index in 13 bits; larger train sets (and SLAMIT_HAMMING_VALU=1, for A/B
-// measurements) take the xor / popcount kernel.  Both give the same (index, best, second).
-static bool hm_use_mfma(int max_train) {
-    static const bool off = getenv("SLAMIT_HAMMING_VALU") != nullptr;
-    return !off && max_train <= HMM_MAX_TRAIN;
-}
+// the matrix-core kernel carries the train index in 13 bits; larger train sets take the xor / popcount kernel.  Both give
+// the same (index, best, second).
+static bool hm_use_mfma(int max_train) { return max_train <= HMM_MAX_TRAIN; }
 
 extern "C" {
 

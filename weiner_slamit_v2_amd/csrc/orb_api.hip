@@ -31,7 +31,7 @@ void orbk_resize_rows8(hipStream_t st, const uint8_t* src, size_t sstride, size_
 hipError_t orbk_pyramid_prepare(int smem_bytes);
 void orbk_pyramid(hipStream_t st, const OrbLevel* levels, int nlevels, const PyrBox* boxes, const PyrTabs* tabs,
                   int nregions, const uint8_t* img0, size_t img0_stride, size_t img0_frame, uint8_t* pyr, int bufA_bytes,
-                  int smem_bytes, int nframes, int l_first, int l_last, int threads);
+                  int smem_bytes, int nframes, int l_first, int l_last);
 size_t orbk_fast_smem(int max_wcell, int max_hcell);
 hipError_t orbk_fast_prepare(int max_wcell, int max_hcell);
 int orbk_fast_cells(const OrbLevel* host_levels, int nlevels, std::vector<uint32_t>& out);
@@ -95,14 +95,17 @@ void resize_axis(int dn, int sn, bool clampx, std::vector<int>& ofs, std::vector
 
 }  // namespace
 
+// levels 0 .. ORB_BLUR_SPLIT are blurred on the side stream beside the tail of the pyramid chain, the rest after it
+// (2 until the pyramid chain got its wide loads: its tail is shorter now)
+#define ORB_BLUR_SPLIT 1
+
 struct slamit_orb {
     slamit_orb_params p;
     int device;
     hipStream_t stream;
     hipStream_t stream_b;     // side stream: the blur of a call runs beside its FAST / octree / orientation launches
     hipEvent_t ev_pyr, ev_mid, ev_blur;
-    int blur_split;       // levels 0 .. blur_split are blurred beside the tail of the pyramid chain (-1: all after FAST)
-    int overlap;              // 0: everything on one stream (SLAMIT_ORB_SERIAL=1)
+    SlamitSwitches sw;        // the environment switches, read when the handle is created
     int nlevels;
     std::vector<float> scale, inv_scale, sigma2, inv_sigma2;
     std::vector<int> per_level;
@@ -131,11 +134,10 @@ struct slamit_orb {
     uint32_t* d_rs_col[ORB_MAX_LEVELS];   // resize_rows4_kernel tables (orbk_resize_tables)
     uint32_t* d_rs_row[ORB_MAX_LEVELS];
     uint32_t* d_rs_col8[ORB_MAX_LEVELS];  // resize_rows8_kernel column tables; null where the level's geometry does not fit it
-    int pyr_mode;                         // 0 per-level rows4 (default), 1 fused segments (SLAMIT_PYR_FUSED)
-    PyrBox* d_boxes;                      // fused pyramid: [nregions][nlevels]
+    int pyr_mode;                         // 0 per-level row kernels (default), 1 fused pyramid (a level they cannot take)
+    PyrBox* d_boxes;                      // fused pyramid: [pyr_regions][nlevels]
     PyrTabs* d_tabs;                      // [nlevels]
-    struct PyrSeg { int first, last, nregions, box_off, bufA, smem, threads; };
-    std::vector<PyrSeg> pyr_segs;          // empty = per-level fallback kernel
+    int pyr_regions, pyr_bufA, pyr_smem;  // fused pyramid plan; pyr_regions 0: none, the per-level generic kernel instead
     // staging for the host-pointer entry points
     uint8_t* d_in;
     size_t d_in_stride, d_in_frame;
@@ -187,6 +189,7 @@ int slamit_orb_create(const slamit_orb_params* p, int device, slamit_orb** out) 
     slamit_orb* h = new slamit_orb();
     h->p = *p;
     h->device = device;
+    h->sw = slamit_read_switches();
     h->stream = nullptr;
     h->last_img0 = nullptr; h->last_nframes = 0;
     const int nl = h->nlevels = p->nlevels;
@@ -307,7 +310,6 @@ int slamit_orb_create(const slamit_orb_params* p, int device, slamit_orb** out) 
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_pyr, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_mid, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_blur, hipEventDisableTiming);
-    h->overlap = getenv("SLAMIT_ORB_SERIAL") ? 0 : 1;
     if (e == hipSuccess && !empty) e = hipMemcpy(h->d_levels, h->levels.data(), sizeof(OrbLevel) * nl, hipMemcpyHostToDevice);
     {
         std::vector<uint32_t> cells;
@@ -326,7 +328,7 @@ int slamit_orb_create(const slamit_orb_params* p, int device, slamit_orb** out) 
             ALLOC(h->d_blur_str, sizeof(uint32_t) * std::max<size_t>(ts.size(), 4)); ALLOC(h->d_blur_edge, sizeof(uint32_t) * std::max<size_t>(te.size(), 4));
             if (e == hipSuccess && !ts.empty()) e = hipMemcpy(h->d_blur_str, ts.data(), sizeof(uint32_t) * ts.size(), hipMemcpyHostToDevice);
             if (e == hipSuccess && !te.empty()) e = hipMemcpy(h->d_blur_edge, te.data(), sizeof(uint32_t) * te.size(), hipMemcpyHostToDevice);
-            h->blur_stream_on = !empty && !(getenv("SLAMIT_BLUR_NO_STREAM") && atoi(getenv("SLAMIT_BLUR_NO_STREAM")));   // A/B runs: the tile kernel everywhere
+            h->blur_stream_on = !empty && !h->sw.blur_no_stream;
         }
     }
     bool rows4_ok = true;
@@ -348,17 +350,16 @@ int slamit_orb_create(const slamit_orb_params* p, int device, slamit_orb** out) 
         ALLOC(h->d_rs_col[l], ct.size() * 4); ALLOC(h->d_rs_row[l], rt.size() * 4);
         if (e == hipSuccess) e = hipMemcpy(h->d_rs_col[l], ct.data(), ct.size() * 4, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(h->d_rs_row[l], rt.data(), rt.size() * 4, hipMemcpyHostToDevice);
-        static const bool no_rows8 = getenv("SLAMIT_RESIZE_NO8") && atoi(getenv("SLAMIT_RESIZE_NO8"));   // A/B runs: the four-pixel kernel everywhere
         std::vector<uint32_t> c8;
-        if (!no_rows8 && orbk_resize_tables8(h->levels[l].w, h->levels[l - 1].w, (size_t)h->levels[l].stride, xo.data(), xa.data(), c8)) {
+        if (!h->sw.resize_no8 && orbk_resize_tables8(h->levels[l].w, h->levels[l - 1].w, (size_t)h->levels[l].stride, xo.data(), xa.data(), c8)) {
             ALLOC(h->d_rs_col8[l], c8.size() * 4);
             if (e == hipSuccess) e = hipMemcpy(h->d_rs_col8[l], c8.data(), c8.size() * 4, hipMemcpyHostToDevice);
         }
     }
-    // ---- fused pyramid: the levels are built in SEGMENTS (default: 0 -> 1,2 | 2 -> 3,4 | 4 -> 5..): one launch
-    // per segment, each workgroup reads its patch of the segment's first level and produces the following levels
-    // out of LDS.  Short segments keep the halo (pixels computed only because a deeper level needs them) small;
-    // per region and level the boxes say what it stores ("own") and what it has to compute ("need").
+    // ---- fused pyramid: ONE launch builds every level.  Each workgroup reads its region of level 0 (128x96 pixels) and
+    // produces the following levels out of LDS; per region and level the boxes say what it stores ("own") and what it has
+    // to compute because a deeper level reads it ("need").  The per-level row kernels above take aligned inputs; this
+    // kernel takes the rest, and the per-level generic kernel what it cannot plan.
     if (e == hipSuccess && !empty && nl > 1) {
         std::vector<std::vector<int> > XO(nl), YO(nl);
         for (int l = 1; l < nl; ++l) {
@@ -366,87 +367,54 @@ int slamit_orb_create(const slamit_orb_params* p, int device, slamit_orb** out) 
             resize_axis(h->levels[l].w, h->levels[l - 1].w, true, XO[l], dummy);
             resize_axis(h->levels[l].h, h->levels[l - 1].h, false, YO[l], dummy);
         }
-        // Default: ONE segment, regions of 128x96 level-0 pixels (what the unaligned / large-scale-factor fallback was
-        // tuned for).  SLAMIT_PYR_SEGS="2,4" / SLAMIT_PYR_TILE="64x48" (tile at the segment's last level) are
-        // diagnostic knobs for experiments with shorter chains.
-        std::vector<int> cuts;
-        if (const char* sv = getenv("SLAMIT_PYR_SEGS"))
-            for (const char* q = sv; *q;) { int v = atoi(q); if (v > 0 && v < nl - 1) cuts.push_back(v); while (*q && *q != ',') ++q; if (*q) ++q; }
-        std::sort(cuts.begin(), cuts.end());
-        cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
-        int tw = 0, th = 0;
-        if (const char* sv = getenv("SLAMIT_PYR_TILE")) { if (sscanf(sv, "%dx%d", &tw, &th) != 2 || tw < 8 || th < 8) tw = th = 0; }
-        std::vector<PyrBox> boxes;
-        bool okb = true;
-        // plans one segment first -> last with regions of tw x th pixels at its last level (0 = 128x96 level-0 pixels)
-        auto plan = [&](int first, int last, int tw, int th, slamit_orb::PyrSeg& seg) -> bool {
-            bool ok = true;
-            seg.first = first; seg.last = last; seg.box_off = (int)boxes.size();
-            const OrbLevel& LL = h->levels[last];
-            const int GX = tw ? std::max(1, (LL.w + tw - 1) / tw) : std::max(1, (p->width + 127) / 128);
-            const int GY = th ? std::max(1, (LL.h + th - 1) / th) : std::max(1, (p->height + 95) / 96);
-            seg.nregions = GX * GY;
-            boxes.resize(boxes.size() + (size_t)GX * GY * nl);
-            size_t capA = 16, capB = 16;
-            for (int gy = 0; gy < GY && ok; ++gy)
-                for (int gx = 0; gx < GX && ok; ++gx) {
-                    PyrBox* B = &boxes[seg.box_off + ((size_t)gy * GX + gx) * nl];
-                    for (int l = first; l <= last; ++l) {
-                        const OrbLevel& L = h->levels[l];
-                        B[l].ox0 = (int16_t)((long)gx * L.w / GX); B[l].ox1 = (int16_t)((long)(gx + 1) * L.w / GX);
-                        B[l].oy0 = (int16_t)((long)gy * L.h / GY); B[l].oy1 = (int16_t)((long)(gy + 1) * L.h / GY);
-                        if (l == first) { B[l].ox0 = B[l].ox1 = B[l].oy0 = B[l].oy1 = 0; }  // the segment's source is only read
-                        else if (B[l].ox1 <= B[l].ox0 || B[l].oy1 <= B[l].oy0) ok = false;
-                    }
-                    B[last].nx0 = B[last].ox0; B[last].nx1 = B[last].ox1;
-                    B[last].ny0 = B[last].oy0; B[last].ny1 = B[last].oy1;
-                    for (int l = last; l > first && ok; --l) {
-                        const int sw = h->levels[l - 1].w, sh = h->levels[l - 1].h;
-                        int sx0 = XO[l][B[l].nx0], sx1 = std::min(XO[l][B[l].nx1 - 1] + 1, sw - 1) + 1;
-                        int sy0 = std::min(std::max(YO[l][B[l].ny0], 0), sh - 1);
-                        int sy1 = std::min(std::max(YO[l][B[l].ny1 - 1] + 1, 0), sh - 1) + 1;
-                        if (l - 1 > first) {
-                            sx0 = std::min(sx0, (int)B[l - 1].ox0); sx1 = std::max(sx1, (int)B[l - 1].ox1);
-                            sy0 = std::min(sy0, (int)B[l - 1].oy0); sy1 = std::max(sy1, (int)B[l - 1].oy1);
-                        }
-                        if (l - 1 == first) sx0 &= ~3;  // dword-aligned source patch
-                        B[l - 1].nx0 = (int16_t)sx0; B[l - 1].nx1 = (int16_t)sx1; B[l - 1].ny0 = (int16_t)sy0; B[l - 1].ny1 = (int16_t)sy1;
-                    }
-                    for (int l = first; l <= last; ++l) {
-                        if (l > first && (B[l].nx1 - B[l].nx0 > 256 || B[l].ny1 - B[l].ny0 > 256)) ok = false;  // <= 4 columns per lane, row tables of 256
-                        size_t bytes = (size_t)(((B[l].nx1 - B[l].nx0) + 3) & ~3) * (B[l].ny1 - B[l].ny0);
-                        if ((l - first) & 1) capB = std::max(capB, bytes); else capA = std::max(capA, bytes);
-                    }
+        const int last = nl - 1;
+        const int GX = std::max(1, (p->width + 127) / 128), GY = std::max(1, (p->height + 95) / 96);
+        std::vector<PyrBox> boxes((size_t)GX * GY * nl);
+        bool ok = true;
+        size_t capA = 16, capB = 16;
+        for (int gy = 0; gy < GY && ok; ++gy)
+            for (int gx = 0; gx < GX && ok; ++gx) {
+                PyrBox* B = &boxes[((size_t)gy * GX + gx) * nl];
+                for (int l = 0; l <= last; ++l) {
+                    const OrbLevel& L = h->levels[l];
+                    B[l].ox0 = (int16_t)((long)gx * L.w / GX); B[l].ox1 = (int16_t)((long)(gx + 1) * L.w / GX);
+                    B[l].oy0 = (int16_t)((long)gy * L.h / GY); B[l].oy1 = (int16_t)((long)(gy + 1) * L.h / GY);
+                    if (l == 0) { B[l].ox0 = B[l].ox1 = B[l].oy0 = B[l].oy1 = 0; }  // the source is only read
+                    else if (B[l].ox1 <= B[l].ox0 || B[l].oy1 <= B[l].oy0) ok = false;
                 }
-            seg.bufA = (int)round_up(capA, 16);
-            seg.smem = seg.bufA + (int)round_up(capB, 16);
-            if (seg.smem > 150 * 1024) ok = false;
-            seg.threads = tw && (size_t)tw * th <= 64 * 48 ? 256 : 512;
-            return ok;
-        };
-        int first = 0;
-        h->pyr_segs.clear();
-        for (size_t si = 0; si <= cuts.size() && okb; ++si) {
-            const int last = si < cuts.size() ? cuts[si] : nl - 1;
-            slamit_orb::PyrSeg seg;
-            okb = plan(first, last, tw, th, seg);
-            h->pyr_segs.push_back(seg);
-            first = last;
-        }
-        h->pyr_mode = (getenv("SLAMIT_PYR_FUSED") || !rows4_ok) ? 1 : 0;
-        h->blur_split = getenv("SLAMIT_BLUR_SPLIT") ? atoi(getenv("SLAMIT_BLUR_SPLIT")) : 1;   // (2 until the pyramid chain got its wide loads: its tail is shorter now)
-        if (getenv("SLAMIT_PYR_PER_LEVEL")) { okb = false; h->pyr_mode = 1; }   // diagnostic: force the old per-level kernel
-        if (!okb) h->pyr_segs.clear();                      // fall back to the per-level kernel
-        if (!h->pyr_segs.empty()) {
+                B[last].nx0 = B[last].ox0; B[last].nx1 = B[last].ox1;
+                B[last].ny0 = B[last].oy0; B[last].ny1 = B[last].oy1;
+                for (int l = last; l > 0 && ok; --l) {
+                    const int sw = h->levels[l - 1].w, sh = h->levels[l - 1].h;
+                    int sx0 = XO[l][B[l].nx0], sx1 = std::min(XO[l][B[l].nx1 - 1] + 1, sw - 1) + 1;
+                    int sy0 = std::min(std::max(YO[l][B[l].ny0], 0), sh - 1);
+                    int sy1 = std::min(std::max(YO[l][B[l].ny1 - 1] + 1, 0), sh - 1) + 1;
+                    if (l - 1 > 0) {
+                        sx0 = std::min(sx0, (int)B[l - 1].ox0); sx1 = std::max(sx1, (int)B[l - 1].ox1);
+                        sy0 = std::min(sy0, (int)B[l - 1].oy0); sy1 = std::max(sy1, (int)B[l - 1].oy1);
+                    }
+                    if (l - 1 == 0) sx0 &= ~3;  // dword-aligned source patch
+                    B[l - 1].nx0 = (int16_t)sx0; B[l - 1].nx1 = (int16_t)sx1; B[l - 1].ny0 = (int16_t)sy0; B[l - 1].ny1 = (int16_t)sy1;
+                }
+                for (int l = 0; l <= last; ++l) {
+                    if (l > 0 && (B[l].nx1 - B[l].nx0 > 256 || B[l].ny1 - B[l].ny0 > 256)) ok = false;  // <= 4 columns per lane, row tables of 256
+                    size_t bytes = (size_t)(((B[l].nx1 - B[l].nx0) + 3) & ~3) * (B[l].ny1 - B[l].ny0);
+                    if (l & 1) capB = std::max(capB, bytes); else capA = std::max(capA, bytes);
+                }
+            }
+        h->pyr_bufA = (int)round_up(capA, 16);
+        h->pyr_smem = h->pyr_bufA + (int)round_up(capB, 16);
+        if (h->pyr_smem > 150 * 1024) ok = false;
+        h->pyr_mode = rows4_ok ? 0 : 1;
+        if (ok) {
+            h->pyr_regions = GX * GY;
             std::vector<PyrTabs> tabs(nl);
             for (int l = 0; l < nl; ++l) { tabs[l].xofs = h->d_tab_i[l][0]; tabs[l].ialpha = h->d_tab_s[l][0]; tabs[l].yofs = h->d_tab_i[l][1]; tabs[l].ibeta = h->d_tab_s[l][1]; }
             ALLOC(h->d_boxes, sizeof(PyrBox) * boxes.size());
             ALLOC(h->d_tabs, sizeof(PyrTabs) * nl);
             if (e == hipSuccess) e = hipMemcpy(h->d_boxes, boxes.data(), sizeof(PyrBox) * boxes.size(), hipMemcpyHostToDevice);
             if (e == hipSuccess) e = hipMemcpy(h->d_tabs, tabs.data(), sizeof(PyrTabs) * nl, hipMemcpyHostToDevice);
-            int smax = 0;
-            for (const slamit_orb::PyrSeg& sg : h->pyr_segs) smax = std::max(smax, sg.smem);
-            if (e == hipSuccess) e = orbk_pyramid_prepare(smax);
+            if (e == hipSuccess) e = orbk_pyramid_prepare(h->pyr_smem);
         }
     }
 #undef ALLOC
@@ -535,7 +503,8 @@ int slamit_orb_extract_batch_dev(slamit_orb* h, const uint8_t* d_gray, size_t st
     // K1: pyramid, level l from level l-1
     prof_mark(h, st, ST_RESIZE, true);
     const bool src0_aligned = ((((uintptr_t)d_gray) | stride | frame_stride) & 3) == 0;
-    const bool early_blur = h->overlap && h->prof_on != 1 && h->blur_split >= 1 && h->blur_split < nl - 1;
+    const bool side = h->prof_on != 1;   // while every stage is timed (slamit_orb_profile(h, 1)) everything stays on one stream
+    const bool early_blur = side && ORB_BLUR_SPLIT < nl - 1;
     bool early_done = false;
     if (h->pyr_mode == 0 && src0_aligned) {
         for (int l = 1; l < nl; ++l) {
@@ -548,7 +517,7 @@ int slamit_orb_extract_batch_dev(slamit_orb* h, const uint8_t* d_gray, size_t st
             else
                 orbk_resize_rows4(st, src, l == 1 ? stride : (size_t)S.stride, l == 1 ? frame_stride : h->pyr_frame_total, S.h,
                                   h->d_pyr + D.plane_off, D.w, D.h, (size_t)D.stride, h->pyr_frame_total, h->d_rs_col[l], h->d_rs_row[l], nframes);
-            if (early_blur && l == h->blur_split) {
+            if (early_blur && l == ORB_BLUR_SPLIT) {
                 // the blur of the big levels 0 .. l (most of its bytes) runs on the side stream beside the rest of the chain:
                 // the small levels are a few microseconds of work behind a kernel boundary each and leave the chip idle
                 HIP_TRY(hipEventRecord(h->ev_mid, st));
@@ -557,10 +526,9 @@ int slamit_orb_extract_batch_dev(slamit_orb* h, const uint8_t* d_gray, size_t st
                 early_done = true;
             }
         }
-    } else if (!h->pyr_segs.empty()) {
-        for (const slamit_orb::PyrSeg& sg : h->pyr_segs)
-            orbk_pyramid(st, h->d_levels, nl, h->d_boxes + sg.box_off, h->d_tabs, sg.nregions, d_gray, stride, frame_stride, h->d_pyr,
-                         sg.bufA, sg.smem, nframes, sg.first, sg.last, sg.threads);
+    } else if (h->pyr_regions) {
+        orbk_pyramid(st, h->d_levels, nl, h->d_boxes, h->d_tabs, h->pyr_regions, d_gray, stride, frame_stride, h->d_pyr,
+                     h->pyr_bufA, h->pyr_smem, nframes, 0, nl - 1);
     } else {
         for (int l = 1; l < nl; ++l) {
             const OrbLevel& S = h->levels[l - 1];
@@ -573,12 +541,6 @@ int slamit_orb_extract_batch_dev(slamit_orb* h, const uint8_t* d_gray, size_t st
         }
     }
     prof_mark(h, st, ST_RESIZE, false);
-    if (h->overlap && h->prof_on != 1 && getenv("SLAMIT_ORB_FORK_EARLY")) {
-        HIP_TRY(hipEventRecord(h->ev_pyr, st));
-        HIP_TRY(hipStreamWaitEvent(h->stream_b, h->ev_pyr, 0));
-        launch_blur(h->stream_b, 0, nl);
-        HIP_TRY(hipEventRecord(h->ev_blur, h->stream_b));
-    }
     // K2: FAST + NMS + per-cell threshold fallback -> candidate lists
     prof_mark(h, st, ST_FAST, true);
     orbk_fast(st, h->levels.data(), nl, h->d_cells, h->fast_cells, d_gray, stride, frame_stride, h->d_pyr, h->d_cand,
@@ -586,14 +548,11 @@ int slamit_orb_extract_batch_dev(slamit_orb* h, const uint8_t* d_gray, size_t st
     prof_mark(h, st, ST_FAST, false);
     // K6: blur every level.  Only the descriptor pass reads it, and it only needs the pyramid: it runs on the side stream
     // beside the octree / orientation launches (latency bound: a few hundred workgroups on 256 CUs) and joins before the
-    // descriptors.  FAST (issue bound, the kernel the roofline is quoted on) keeps the chip to itself.  While every stage
-    // is being timed (slamit_orb_profile(h, 1)) everything stays on one stream.
-    const bool side = h->overlap && h->prof_on != 1;
-    static const int fork_early = getenv("SLAMIT_ORB_FORK_EARLY") ? 1 : 0;
-    if (side && !fork_early) {
+    // descriptors.  FAST (issue bound, the kernel the roofline is quoted on) keeps the chip to itself.
+    if (side) {
         HIP_TRY(hipEventRecord(h->ev_pyr, st));
         HIP_TRY(hipStreamWaitEvent(h->stream_b, h->ev_pyr, 0));
-        launch_blur(h->stream_b, early_done ? h->blur_split + 1 : 0, nl);   // the levels the early launch left
+        launch_blur(h->stream_b, early_done ? ORB_BLUR_SPLIT + 1 : 0, nl);   // the levels the early launch left
         HIP_TRY(hipEventRecord(h->ev_blur, h->stream_b));
     }
     // K4: octree

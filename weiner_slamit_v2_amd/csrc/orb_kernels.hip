@@ -81,6 +81,8 @@ __device__ __forceinline__ uint32_t rs_dot2(uint32_t taps, uint32_t alpha) {
     return __builtin_amdgcn_udot2(__builtin_bit_cast(rs_us2, taps), __builtin_bit_cast(rs_us2, alpha), 0u, false);
 }
 
+#define RS_RP 2   // row pairs per lane of resize_rows4_kernel and resize_rows8_kernel
+
 template <int RP>   // RP row pairs (2 * RP dst rows) per lane; S / D: the frame's source and destination planes
 __device__ __forceinline__ void rs_item(const int item, const uint8_t* S, const unsigned ss, const unsigned sbytes, uint8_t* D, const unsigned dstride,
                                         const uint4* __restrict__ coltab, const uint2* __restrict__ rowtab, const int ngroups,
@@ -300,28 +302,18 @@ bool orbk_resize_tables8(int dw, int sw, size_t dstride, const int* xofs, const 
 
 void orbk_resize_rows8(hipStream_t st, const uint8_t* src, size_t sstride, size_t sframe, int sh, uint8_t* dst, int dw, int dh,
                        size_t dstride, size_t dframe, const uint32_t* d_col8, const uint32_t* d_row, int nframes) {
-    static const int rp_env = getenv("SLAMIT_RESIZE8_RP") ? atoi(getenv("SLAMIT_RESIZE8_RP")) : 0;
-    const int rp = rp_env == 1 || rp_env == 2 || rp_env == 4 ? rp_env : 2;
-    const int ng = (dw + 7) / 8, nitems = ng * ((dh + 2 * rp - 1) / (2 * rp));
+    const int ng = (dw + 7) / 8, nitems = ng * ((dh + 2 * RS_RP - 1) / (2 * RS_RP));
     const unsigned inv = (unsigned)((0x100000000ull + (unsigned)ng - 1) / (unsigned)ng);
-    const dim3 grid((nitems + 255) / 256, nframes);
-#define RS_LAUNCH8(RP) hipLaunchKernelGGL(resize_rows8_kernel<RP>, grid, dim3(256), 0, st, src, sstride, sframe, dst, dstride, dframe, \
-                                           reinterpret_cast<const uint4*>(d_col8), reinterpret_cast<const uint2*>(d_row), ng, inv, nitems, dh, (unsigned)(sstride * (size_t)sh))
-    if (rp == 1) RS_LAUNCH8(1); else if (rp == 2) RS_LAUNCH8(2); else RS_LAUNCH8(4);
-#undef RS_LAUNCH8
+    hipLaunchKernelGGL(resize_rows8_kernel<RS_RP>, dim3((nitems + 255) / 256, nframes), dim3(256), 0, st, src, sstride, sframe, dst, dstride, dframe,
+                       reinterpret_cast<const uint4*>(d_col8), reinterpret_cast<const uint2*>(d_row), ng, inv, nitems, dh, (unsigned)(sstride * (size_t)sh));
 }
 
 void orbk_resize_rows4(hipStream_t st, const uint8_t* src, size_t sstride, size_t sframe, int sh, uint8_t* dst, int dw, int dh,
                        size_t dstride, size_t dframe, const uint32_t* d_col, const uint32_t* d_row, int nframes) {
-    static const int rp_env = getenv("SLAMIT_RESIZE_RP") ? atoi(getenv("SLAMIT_RESIZE_RP")) : 0;
-    const int rp = rp_env == 1 || rp_env == 2 || rp_env == 4 ? rp_env : 2;
-    const int ng = (dw + 3) / 4, nitems = ng * ((dh + 2 * rp - 1) / (2 * rp));
+    const int ng = (dw + 3) / 4, nitems = ng * ((dh + 2 * RS_RP - 1) / (2 * RS_RP));
     const unsigned inv = (unsigned)((0x100000000ull + (unsigned)ng - 1) / (unsigned)ng);
-    const dim3 grid((nitems + 255) / 256, nframes);
-#define RS_LAUNCH(RP) hipLaunchKernelGGL(resize_rows4_kernel<RP>, grid, dim3(256), 0, st, src, sstride, sframe, dst, dstride, dframe, \
-                                          reinterpret_cast<const uint4*>(d_col), reinterpret_cast<const uint2*>(d_row), ng, inv, nitems, dh, (unsigned)(sstride * (size_t)sh))
-    if (rp == 1) RS_LAUNCH(1); else if (rp == 2) RS_LAUNCH(2); else RS_LAUNCH(4);
-#undef RS_LAUNCH
+    hipLaunchKernelGGL(resize_rows4_kernel<RS_RP>, dim3((nitems + 255) / 256, nframes), dim3(256), 0, st, src, sstride, sframe, dst, dstride, dframe,
+                       reinterpret_cast<const uint4*>(d_col), reinterpret_cast<const uint2*>(d_row), ng, inv, nitems, dh, (unsigned)(sstride * (size_t)sh));
 }
 
 // --------------------------------------------------------------------------------------------
@@ -331,7 +323,7 @@ void orbk_resize_rows4(hipStream_t st, const uint8_t* src, size_t sstride, size_
 // reference's (level l is always computed from level l-1), but no level is ever re-read from HBM
 // and six dependent launches disappear.  Boxes come from the host (orb_api.hip: build_pyr_boxes).
 // --------------------------------------------------------------------------------------------
-#define PYR_THREADS 512   // upper bound; the launch picks 256 or 512
+#define PYR_THREADS 512
 
 __global__ __launch_bounds__(PYR_THREADS) void pyramid_fused_kernel(
     const OrbLevel* __restrict__ levels, int nlevels, const PyrBox* __restrict__ boxes,
@@ -639,11 +631,7 @@ __device__ __forceinline__ void fast_cell_wave(
             const unsigned olo = elo >> 2, ohi = ehi >> 2;
             const uint8_t* qlo = tile + olo + (SC_COL0 - 3);
             const uint8_t* qhi = tile + ohi + (SC_COL0 - 3);
-#ifdef FAST_DIAG_NO_XOR   // timing experiment only (wrong scores for "darker" entries)
-            const uint32_t pm = 0u;
-#else
             const uint32_t pm = __umul24(((ehi << 16) | elo) & 0x00010001u, 0xFFu);   // 0xFF in the half of an entry scored as "darker": complements its bytes
-#endif
 #define PX(dx, dy) ((((uint32_t)qhi[((dy) + 3) * PITCH + (dx) + 3] << 16) | (uint32_t)qlo[((dy) + 3) * PITCH + (dx) + 3]) ^ pm)
             // ring in the order of cv::FAST's 16-pattern: (0,3)(1,3)(2,2)(3,1)(3,0)(3,-1)(2,-2)(1,-3)(0,-3)(-1,-3)(-2,-2)(-3,-1)(-3,0)(-3,1)(-2,2)(-1,3)
             uint32_t r[16];
@@ -741,17 +729,6 @@ __device__ __forceinline__ void fast_cell_wave(
                     // share of byte 3).  Four masks under the full exec, then each pixel's store under its own; every byte pick
                     // is an SDWA operand select -- written out, because the compiler shifts and masks bytes 1 and 2 by hand
                     // (16 vector instructions for the append instead of 27).
-#ifdef FAST_APPEND_C
-                    {
-                    const unsigned g = f6 + 0x0C080400u;
-                    const unsigned pf2 = __umul24(tb, 0x020200u) + (tb << 25);
-                    unsigned char* const slot0 = reinterpret_cast<unsigned char*>(s_ent + nE) + (excl << 1);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (((f6 >> (8 * j)) & 0xFFu) != 0u)
-                            *reinterpret_cast<unsigned short*>(slot0 + ((pf2 >> (8 * j)) & 0xFFu)) = (unsigned short)(e_base + ((g >> (8 * j)) & 0xFFu));
-                    }
-#else
                     const unsigned g = f6 + 0x0C080400u, zero = 0u;
                     const unsigned slot0 = (unsigned)(size_t)(s_ent + nE) + (excl << 1);   // LDS byte address (s_ent + nE is scalar)
                     unsigned pf2, dat, adr;
@@ -783,7 +760,6 @@ __device__ __forceinline__ void fast_cell_wave(
                         : [pf2] "=&v"(pf2), [dat] "=&v"(dat), [adr] "=&v"(adr), [sv] "=&s"(sv), [m0] "=&s"(m0), [m1] "=&s"(m1), [m2] "=&s"(m2), [m3] "=&s"(m3)
                         : [tb] "v"(tb), [k] "v"(0x020200u), [f6] "v"(f6), [z] "v"(zero), [eb] "v"(e_base), [g] "v"(g), [s0] "v"(slot0)
                         : "memory");
-#endif
                     nE += total;
                 }
             }
@@ -1981,8 +1957,8 @@ hipError_t orbk_pyramid_prepare(int smem_bytes) {
 
 void orbk_pyramid(hipStream_t st, const OrbLevel* levels, int nlevels, const PyrBox* boxes, const PyrTabs* tabs,
                   int nregions, const uint8_t* img0, size_t img0_stride, size_t img0_frame, uint8_t* pyr, int bufA_bytes,
-                  int smem_bytes, int nframes, int l_first, int l_last, int threads) {
-    hipLaunchKernelGGL(pyramid_fused_kernel, dim3(nregions, nframes), dim3(threads), smem_bytes, st, levels, nlevels, boxes,
+                  int smem_bytes, int nframes, int l_first, int l_last) {
+    hipLaunchKernelGGL(pyramid_fused_kernel, dim3(nregions, nframes), dim3(PYR_THREADS), smem_bytes, st, levels, nlevels, boxes,
                        tabs, img0, img0_stride, img0_frame, pyr, bufA_bytes, l_first, l_last);
 }
 
@@ -2044,11 +2020,8 @@ void orbk_fast(hipStream_t st, const OrbLevel* host_levels, int nlevels, const u
     // (cells differ 3x in work).  One wave (= one cell) per workgroup, cells dealt to the XCDs in runs of four (fast_cells_kernel):
     // 0.283 -> 0.278 ms per 256 VGA frames at the same HBM traffic; at 1280 x 720 (2,656 cells per frame) four per workgroup stay
     // 1 - 2 % ahead at 16 - 128 frames, so the choice goes by the frame's cell count -- two measured geometries, no model.
-    // (SLAMIT_FAST_WPB=1|2|4: A/B runs.)
-    static const int wpb_env = getenv("SLAMIT_FAST_WPB") ? atoi(getenv("SLAMIT_FAST_WPB")) : 0;
-    const int wpb = wpb_env == 1 || wpb_env == 2 || wpb_env == 4 ? wpb_env : cells_per_frame < 1600 ? 1 : 4;
-    static const int xcd_env = getenv("SLAMIT_XCD_FRAMES") ? atoi(getenv("SLAMIT_XCD_FRAMES")) : 1;
-    const int xcd_frames = xcd_env && nframes >= 16 ? nframes : 0;
+    const int wpb = cells_per_frame < 1600 ? 1 : 4;
+    const int xcd_frames = nframes >= 16 ? nframes : 0;
     const dim3 grid = xcd_frames ? dim3((unsigned)(((nframes + 7) / 8) * 8) * (unsigned)((cells_per_frame + wpb - 1) / wpb))
                                  : dim3(wpb == 1 ? (unsigned)((cells_per_frame + 31) & ~31) : (unsigned)((cells_per_frame + wpb - 1) / wpb), nframes);
     const size_t smem = orbk_fast_smem(max_wcell, max_hcell) / 4 * wpb;
@@ -2076,9 +2049,7 @@ void orbk_fast(hipStream_t st, const OrbLevel* host_levels, int nlevels, const u
 // than 5,000 candidates on a level, so their handles take 48 KB and the blur runs beside the octree on the side stream.
 int orbk_octree_key_cap(int node_cap, int width, int height) {
     long budget = (long)width * height <= 640L * 480L * 3 / 2 ? 48L * 1024 : (long)OCT_LDS_BUDGET;
-    if (getenv("SLAMIT_OCT_LDS_KB")) budget = 1024L * atol(getenv("SLAMIT_OCT_LDS_KB"));
     const long room = budget - (long)orbk_octree_node_bytes(node_cap);
-    if (getenv("SLAMIT_OCT_KEYS")) return atoi(getenv("SLAMIT_OCT_KEYS")) & ~7;
     return (int)std::min<long>(OCT_LDS_KEYS_MAX, std::max<long>(OCT_LDS_KEYS_MIN, room / 6)) & ~7;
 }
 size_t orbk_octree_smem(int node_cap, int key_cap) { return orbk_octree_node_bytes(node_cap) + (size_t)key_cap * 6; }
@@ -2103,16 +2074,14 @@ void orbk_octree(hipStream_t st, const OrbLevel* levels, int nlevels, const unsi
     // Workgroups of 512 threads finish a (frame, level) soonest; with a hundred frames or more per call 256-thread workgroups take 10 %
     // longer alone (74 vs 67 us at 128 frames) but leave the side stream's blur more of the chip, and the STEP is 2 % shorter
     // (0.551 vs 0.562 ms); at 64 frames they cost 5 %.
-    static const int nt_env = getenv("SLAMIT_OCT_THREADS") ? atoi(getenv("SLAMIT_OCT_THREADS")) : 0;
     // ... and with a handful of frames (<= 16: at most 128 workgroups, half a chip) the pass is the level-0 workgroup's critical path:
     // 1,024 threads shorten its key sweeps (8 frames of 720p: 0.095 -> 0.069 ms; 64 frames: 512 threads are better, 0.038 vs 0.054 at VGA)
-    const int nt = nt_env == 256 || nt_env == 512 || nt_env == 1024 ? nt_env : (nframes >= 96 ? 256 : nframes <= 16 ? 1024 : OCT_THREADS);
+    const int nt = nframes >= 96 ? 256 : nframes <= 16 ? 1024 : OCT_THREADS;
     // A big batch is bound by how many of its (frame, level) workgroups a CU holds at once, and that by their LDS: with the
     // handle's full key arrays (48 KB) three fit, with room for 2,048 keys five do, and the lists above that go through the HBM
     // workspace (L2 resident) at little cost: 0.116 -> 0.092 ms per 256 VGA frames.  (1,536 keys = six per CU: the pass alone
     // 0.088 ms, but the step 2 % LONGER -- the side stream's blur finds less of the chip.)  A few frames keep the big arrays.
-    static const bool keys_env = getenv("SLAMIT_OCT_KEYS") || getenv("SLAMIT_OCT_LDS_KB");
-    if (nframes >= 96 && !keys_env) key_cap = std::min(key_cap, 2048);
+    if (nframes >= 96) key_cap = std::min(key_cap, 2048);
     if (nt == 1024)
         hipLaunchKernelGGL(octree_kernel<1024>, grid, dim3(1024), orbk_octree_smem(node_cap, key_cap), st, levels, nlevels, cand,
                            cand_frame_stride, cand_count, ws_xy, ws_node, lkp, kp_frame_stride, kp_count, node_cap,
@@ -2131,8 +2100,7 @@ void orbk_ic_angle(hipStream_t st, const OrbLevel* levels, int nlevels, const ui
                    size_t img0_stride, size_t img0_frame, const uint8_t* pyr, OrbLevelKp* lkp,
                    size_t kp_frame_stride, const int* kp_count, int max_kp, int nframes) {
     const int kblocks = (max_kp + 4 * IC_KP_PER_WAVE - 1) / (4 * IC_KP_PER_WAVE);
-    static const int xcd_env = getenv("SLAMIT_XCD_FRAMES") ? atoi(getenv("SLAMIT_XCD_FRAMES")) : 1;
-    if (xcd_env && nframes >= 16)
+    if (nframes >= 16)
         hipLaunchKernelGGL(ic_angle_kernel, dim3((unsigned)(((nframes + 7) / 8) * 8 * nlevels * kblocks)), dim3(256), 0, st, levels,
                            nlevels, img0, img0_stride, img0_frame, pyr, lkp, kp_frame_stride, kp_count, nframes, kblocks);
     else
@@ -2188,8 +2156,7 @@ void orbk_describe(hipStream_t st, const OrbLevel* levels, int nlevels, const ui
                    const OrbLevelKp* lkp, size_t kp_frame_stride, const int* kp_count, slamit_kp* out_kps,
                    uint8_t* out_desc, int out_cap, int* out_n, int max_kp, int nframes) {
     const int kblocks = (max_kp + 4 * DESC_KP_PER_WAVE - 1) / (4 * DESC_KP_PER_WAVE);
-    static const int xcd_env = getenv("SLAMIT_XCD_FRAMES") ? atoi(getenv("SLAMIT_XCD_FRAMES")) : 1;   // 0: the (blocks, levels, frames) grid (A/B runs)
-    if (xcd_env && nframes >= 16)
+    if (nframes >= 16)
         hipLaunchKernelGGL(describe_kernel, dim3((unsigned)(((nframes + 7) / 8) * 8 * nlevels * kblocks)), dim3(256), 0, st, levels,
                            nlevels, blur, lkp, kp_frame_stride, kp_count, out_kps, out_desc, out_cap, out_n, nframes, kblocks);
     else

@@ -32,6 +32,21 @@ struct SlamitDeviceGuard {
 
 int slamit_default_device();   // slamit_set_device() of this thread, or the current device
 
+// The library's environment switches, read by slamit_read_switches() when a handle is created.
+// The first six let a test force a second path on the same input; the last three print diagnostics on stderr.
+struct SlamitSwitches {
+    bool resize_no8;       // SLAMIT_RESIZE_NO8=1: the four-pixel resize kernel on every level
+    bool blur_no_stream;   // SLAMIT_BLUR_NO_STREAM=1: the tile blur kernel on every level
+    bool ba_no_band;       // SLAMIT_BA_NO_BAND: every window through the blocked reduced solve
+    bool ba_no_sf;         // SLAMIT_BA_SF=0: the tiled Schur product for every window
+    int ba_sf_cap;         // SLAMIT_BA_SF_CAP: k slabs per floating-window group (0: the default)
+    bool ba_keep_order;    // SLAMIT_BA_KEEP_ORDER: the caller's keyframe order, never renumbered
+    bool ba_timing;        // SLAMIT_BA_TIMING: host phases of every solve
+    bool ba_diag;          // SLAMIT_BA_DIAG: in-kernel clock and phases of the last LDLt launch (BA_DIAG_STAMPS builds)
+    bool ba_diag_waves;    // SLAMIT_BA_DIAG_WAVES: busy cycles of the LDLt waves (BA_DIAG_WAVES builds)
+};
+SlamitSwitches slamit_read_switches();
+
 // One pinned staging block, one device slab and one stream per host thread and call site, kept between calls: the
 // per-frame entry points (pose, Sim3, guided search ...) are called every frame by a tracking thread, and a fresh
 // hipMalloc / hipFree pair per call costs more than their kernels.  The blocks are released when the thread exits

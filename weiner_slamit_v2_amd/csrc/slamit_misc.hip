@@ -1,11 +1,13 @@
-// slamit_misc.hip — error string, version, device count (include/slamit.h "misc").
+// slamit_misc.hip — error string, version, device count (include/slamit.h "misc"); the environment switches.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/slamit.h"
 #include "slamit_internal.h"
 
+#include <algorithm>
 #include <vector>
 
 static thread_local char g_err[512] = "";
@@ -22,6 +24,23 @@ int slamit_default_device() {
 void slamit_scratch_register(SlamitScratch* s) {
     if (!g_scratch) g_scratch = new std::vector<SlamitScratch*>();
     g_scratch->push_back(s);
+}
+
+// The library's only reads of the environment
+SlamitSwitches slamit_read_switches() {
+    auto set = [](const char* name) { return getenv(name) != nullptr; };
+    auto value = [](const char* name) { const char* v = getenv(name); return v ? atoi(v) : 0; };
+    SlamitSwitches s;
+    s.resize_no8 = value("SLAMIT_RESIZE_NO8") != 0;
+    s.blur_no_stream = value("SLAMIT_BLUR_NO_STREAM") != 0;
+    s.ba_no_band = set("SLAMIT_BA_NO_BAND");
+    s.ba_no_sf = set("SLAMIT_BA_SF") && value("SLAMIT_BA_SF") == 0;
+    s.ba_sf_cap = std::max(value("SLAMIT_BA_SF_CAP"), 0);
+    s.ba_keep_order = set("SLAMIT_BA_KEEP_ORDER");
+    s.ba_timing = set("SLAMIT_BA_TIMING");
+    s.ba_diag = set("SLAMIT_BA_DIAG");
+    s.ba_diag_waves = set("SLAMIT_BA_DIAG_WAVES");
+    return s;
 }
 
 int slamit_fail(int code, const char* msg) {
