@@ -130,7 +130,7 @@ def test_banded_windows_in_lds_and_through_the_blocked_path(opt, k, p, o, seed, 
 
 
 def test_schur_over_floating_windows_and_over_tile_pairs_one_handle_per_setting(monkeypatch):
-    """The Schur product of a window whose k slabs each touch <= 63 rows runs over floating row windows (BaWin::sf_*, csrc/ba_api.hip:
+    """The Schur product of a window whose k slabs each touch <= 63 rows runs over floating row windows (BaWin::sf_*, csrc/ba_plan.cc:
     groups of slabs, one 64 x 64 partial tile each); SLAMIT_BA_SF=0 sends the same window through the 64 x 64 tile pairs.  Both give the
     same poses, points, flags and LM path, the floating form executes fewer flops, and a window it cannot take (dense visibility; ten keyframes
     per point: a slab's rows span 66; more groups than the launch has workgroups) falls back inside the same batch.  Window widths 2 .. 10 keyframes, ragged system sizes, fixed
@@ -184,7 +184,7 @@ def _shuffle_keyframes(prob, seed):
 
 def test_keyframes_listed_out_of_trajectory_order_one_handle_per_setting(opt, monkeypatch):
     """ORB-SLAM2 lists a local window by co-visibility weight, not along the trajectory (Optimizer.cc:456-470): the reduced system of such a
-    list has its couplings scattered.  ba_order_columns (csrc/ba_api.hip) renumbers the free keyframes by reverse Cuthill-McKee when that narrows the
+    list has its couplings scattered.  ba_order_columns (csrc/ba_plan.cc) renumbers the free keyframes by reverse Cuthill-McKee when that narrows the
     band, so the shuffled window-8 window takes the banded solve and the floating-window Schur product like the ordered one (executed flops
     within 1.5x of it, against 10x in the caller's order: SLAMIT_BA_KEEP_ORDER=1), and either order gives the oracle's result on the
     shuffled problem and the ordered window's poses."""

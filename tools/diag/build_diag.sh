@@ -9,6 +9,6 @@ extra=""
 case $file in ba_kernels.hip|pose.hip) extra="-ffp-contract=fast";; esac
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=off -fno-fast-math -fno-gpu-rdc -Wno-unused-value $extra "$@" -c $C/$file -o /tmp/diag_$name.o
 objs=""
-for f in $C/*.hip; do b=$(basename $f); [ "$b" = "$file" ] && continue; objs="$objs ${f%.hip}.o"; done
+for f in $C/*.hip $C/*.cc; do b=$(basename $f); [ "$b" = "$file" ] && continue; objs="$objs ${f%.*}.o"; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/diag/libdiag_$name.so /tmp/diag_$name.o $objs
 echo tools/diag/libdiag_$name.so

@@ -6,8 +6,9 @@ cd "$(dirname "$0")/../.."
 name=$1; shift
 tmp=/tmp/here_$name; rm -rf $tmp; mkdir -p $tmp
 objs=""
-for f in weiner_slamit_v2_amd/csrc/*.hip; do
-  b=$(basename $f .hip)
+for f in weiner_slamit_v2_amd/csrc/*.hip weiner_slamit_v2_amd/csrc/*.cc; do
+  [ -e "$f" ] || continue
+  b=$(basename ${f%.*})
   extra=""
   case $b in ba_kernels|pose) extra="-ffp-contract=fast";; hamming) extra="-mllvm -amdgpu-mfma-vgpr-form";; esac
   if [ "$b" = "${HERE_TU:-orb_kernels}" ]; then extra="$extra $*"; fi

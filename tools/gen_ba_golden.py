@@ -34,7 +34,7 @@ CASES = {
     "stereo_rough": (8, 150, 4, 56, 1, 80.0, 0.6),      # very large initial error: a rejected LM trial, most edges gated out
     "stereo_window8": (50, 2000, 8, 54, 1, 1.0, 0.8),   # BASELINE config 4 geometry with 80 % stereo observations
     # a window-8 window whose keyframes are listed in a random order (ORB-SLAM2 lists them by co-visibility weight, Optimizer.cc:456-470):
-    # the free keyframes are renumbered on the host (csrc/ba_api.hip ba_order_columns) -- an 8th field = the seed of the permutation
+    # the free keyframes are renumbered on the host (csrc/ba_plan.cc ba_order_columns) -- an 8th field = the seed of the permutation
     "shuffled": (50, 1000, 8, 61, 2, 1.0, 0.0, 9),
 }
 # name -> (its_robust, its_final, huber_delta); everything else uses the local-BA schedule of Optimizer.cc:507-743

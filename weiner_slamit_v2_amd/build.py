@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libslamit_hip.so")
-SOURCES = ["slamit_misc.hip", "orb_kernels.hip", "orb_api.hip", "hamming.hip", "ba_kernels.hip", "ba_api.hip", "pose.hip", "search.hip", "frame.hip", "bow.hip", "sim3.hip"]
+SOURCES = ["slamit_misc.hip", "orb_kernels.hip", "orb_api.hip", "hamming.hip", "ba_kernels.hip", "ba_plan.cc", "ba_api.hip", "pose.hip", "search.hip", "frame.hip", "bow.hip", "sim3.hip"]
 # BA is fp64 with a 1e-5 tolerance, not bit-exact: let the compiler fuse multiply-adds there
 # hamming.hip: the i8 MFMA results feed VALU min / median directly, so its accumulators stay in VGPRs (no v_accvgpr moves)
 PER_FILE = {"ba_kernels.hip": ["-ffp-contract=fast"], "pose.hip": ["-ffp-contract=fast"],
@@ -49,20 +49,20 @@ def build(force=False, verbose=False):
     objs = []
     procs = []
     for src in sources():
-        obj = src[:-4] + ".o"
+        obj = os.path.splitext(src)[0] + ".o"
         cmd = [hipcc()] + FLAGS + PER_FILE.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd))
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
         objs.append(obj)
     failed = False
-    for src, p in procs:
+    for (src, p), obj in zip(procs, objs):
         out, _ = p.communicate()
         if p.returncode != 0 and "-mllvm" in PER_FILE.get(os.path.basename(src), []):
             # an internal compiler option (hamming.hip's accumulators in VGPRs) this hipcc may not know: the kernel is correct
             # without it (the compiler then moves the MFMA results out of the accumulator file itself), so build it plainly
             sys.stderr.write("%s: retrying without %s\n" % (os.path.basename(src), " ".join(PER_FILE[os.path.basename(src)])))
-            cmd = [hipcc()] + FLAGS + ["-c", src, "-o", src[:-4] + ".o"]
+            cmd = [hipcc()] + FLAGS + ["-c", src, "-o", obj]
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
             p.returncode, out = r.returncode, r.stdout
         if p.returncode != 0:

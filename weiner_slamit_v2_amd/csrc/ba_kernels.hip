@@ -531,15 +531,6 @@ __global__ __launch_bounds__(256) void k_point_pass(BaWin* wins) {
 // MFMA operand pattern lane -> [row = lane&15][k = lane>>4]).
 #define LDS_PITCH 34
 
-// does the reduced system need tile pair (I, J), I <= J, of the product?  Not when the two row tiles share no k range (the block
-// is zero: k_schur_reduce writes the zeros itself), and not when the banded solver takes the window and the whole tile lies
-// outside the band (nobody reads it) -- except for the tile column that holds the right-hand side (row nS of the operand)
-__device__ __forceinline__ bool schur_tile_needed(const BaWin& W, int I, int J) {
-    if (max(W.tile_alo[I], W.tile_blo[J]) >= min(W.tile_ahi[I], W.tile_bhi[J])) return false;
-    if (W.solver == BA_SOLVER_BAND && BA_TILE * J - (BA_TILE * I + BA_TILE - 1) > W.band && W.nS / BA_TILE != J) return false;
-    return true;
-}
-
 __device__ __forceinline__ void schur_body(const BaWin& W, const BaState* st, int tile, int s, int nsplit) {
     if (st->done) return;
     const int T = W.Npad / BA_TILE;
@@ -562,7 +553,7 @@ __device__ __forceinline__ void schur_body(const BaWin& W, const BaState* st, in
         const int J = I + rem;
         if (I >= T || !schur_tile_needed(W, I, J)) return;
         // Only the k range in which BOTH row tiles have non-zeros is multiplied (points are sorted by their first observing
-        // keyframe, ba_api.hip): its slabs of BA_KC are dealt to the launch's nsplit <= BA_SPLITS splits (gridDim.y: sixteen for a single
+        // keyframe, ba_plan.cc): its slabs of BA_KC are dealt to the launch's nsplit <= BA_SPLITS splits (gridDim.y: sixteen for a single
         // window, which needs the parallelism; eight for a batch, whose windows already fill the chip -- half of the partial
         // tiles to write and to sum); a split without a slab stores zeros.
         const int klo = max(W.tile_alo[I], W.tile_blo[J]), khi = min(W.tile_ahi[I], W.tile_bhi[J]);
@@ -647,9 +638,6 @@ __global__ __launch_bounds__(256) void k_schur_pose(BaWin* wins, int ntiles) {
     if ((int)blockIdx.x < ntiles) schur_body(W, BA_ST(wins, blockIdx.z), blockIdx.x, blockIdx.y, gridDim.y);
     else pose_reduce_body(W, BA_ST(wins, blockIdx.z), ((int)blockIdx.x - ntiles) * (int)gridDim.y + (int)blockIdx.y);
 }
-
-__host__ __device__ inline int ldlt_band_rs(int bw);
-__host__ __device__ inline bool ldlt_band_ok(int n, int bw);
 
 // ---- S7: S = Hpp + lambda*I - sum_s part[s],  b_s = bp - coeff --------------------------------------
 // A window of the blocked solver: thread -> entry (r, c) of the upper triangle, the full matrix is written (both halves).  A banded
@@ -902,16 +890,7 @@ __device__ __forceinline__ void ldlt_back_block(const gdouble* S, int N, double*
 #define LB_PIV_WAVE 3
 #define LB_RHS_WAVE 7
 #endif
-#define LD_BAND_LDS (150 * 1024)     // dynamic LDS the kernel may use (bak_ldlt_smem requests at least this much when it fits)
-// Row stride EVEN: a column of the band, A(c, k) for c = k + 1, k + 2, .., is a walk of RS - 1 doubles per row, and an odd number
-// of doubles per step spreads 32 lanes over 32 different bank pairs (with RS = 49 they all fell on two).
-__host__ __device__ inline int ldlt_band_rs(int bw) { return (bw + 5) & ~1; }
-__host__ __device__ inline int ldlt_band_ylen(int n) { return (n + 9) & ~1; }
-__host__ __device__ inline size_t ldlt_band_bytes(int n, int bw) {
-    return sizeof(double) * ((size_t)(n + 1) * ldlt_band_rs(bw) + ldlt_band_ylen(n) + 16 * (size_t)((n + 3) / 4 + 1));
-}
-// bw <= 59: the reachable rows k + 4 .. k + 3 + bw stay within five block rows of the pivot's block column
-__host__ __device__ inline bool ldlt_band_ok(int n, int bw) { return n > 0 && bw >= 8 && bw <= 59 && ldlt_band_bytes(n, bw) <= LD_BAND_LDS; }
+// (LD_BAND_LDS, the image's row stride ldlt_band_rs and the admission rule ldlt_band_ok: ba_types.h)
 
 // LDLt of a symmetric 4 x 4 block (lower entries e: 00 10 11 20 21 22 30 31 32 33; rows >= nv are padding and count as
 // identity) and its NEGATED inverse G (row-major, symmetric: every user subtracts).
@@ -1260,7 +1239,7 @@ __device__ __forceinline__ void ldlt_band_solve(const BaWin& W, BaState* st, dou
 }
 
 // The reduced solve of a window is ONE of two kernels, chosen on the host from the window's size and envelope
-// (BaWin::solver, ba_api.hip); a batch launches the kinds it contains and a workgroup whose window is of the other kind
+// (BaWin::solver, ba_plan.cc); a batch launches the kinds it contains and a workgroup whose window is of the other kind
 // returns at once.  (As one kernel with a run-time branch the register allocation was the union of the paths: 256 VGPRs
 // and 37 spilled; on its own the banded kernel takes 94.)  Each starts with k_iter_begin's bookkeeping for the slots without that launch (bak_slot, first ==
 // false): it is the first single-workgroup kernel behind the last reader of need_linearize (k_pose_reduce).
@@ -1303,7 +1282,7 @@ __global__ __launch_bounds__(LD_THREADS) void k_ldlt_blocked(BaWin* wins) {
     for (int jb = 0; jb < n; jb += LD_NB) {
         const int nb = min(LD_NB, n - jb);
         const int base = jb + nb;
-        // rows under the panel that can hold an entry in its columns (row envelope, ba_api.hip); LDLt without pivoting
+        // rows under the panel that can hold an entry in its columns (row envelope, ba_plan.cc); LDLt without pivoting
         // never fills outside the envelope, so the rows beyond keep exact zeros there and are not touched
         const int below = max((int)W.panel_hi[jb / LD_NB] + 1 - base, 0);
         const int rows = below + 1;          // + the rhs row, which is matrix row n
@@ -1766,12 +1745,6 @@ hipError_t bak_prepare(int Npad) {
     return e;
 }
 
-// the reduced solve a window takes (host): its structure decides (`no_band`: SLAMIT_BA_NO_BAND, every window takes the blocked kernel)
-int bak_solver_kind(int n, int band, bool no_band) {
-    if (!no_band && ldlt_band_ok(n, band)) return BA_SOLVER_BAND;
-    return BA_SOLVER_BLOCKED;
-}
-
 void bak_import(hipStream_t st, BaWin* wins, const BaIo* io, int max_kf, int max_pt, int max_edge, int Npad, int nwin) {
     const int nb = std::max(std::max(max_edge, 3 * max_pt), std::max(max_kf, (int)(sizeof(BaState) / 8)));
     hipLaunchKernelGGL(k_import, dim3((nb + 255) / 256, nwin), dim3(256), 0, st, wins, io);
@@ -1784,12 +1757,6 @@ void bak_stage_begin(hipStream_t st, BaWin* wins, int nwin, int max_edge, int st
     hipLaunchKernelGGL(k_stage_begin, dim3(1, nwin), dim3(256), 0, st, wins, stage, max_it, robust);
     hipLaunchKernelGGL(k_errors, ge, dim3(256), 0, st, wins);
     hipLaunchKernelGGL(k_stage_begin2, dim3(1, nwin), dim3(256), 0, st, wins);
-}
-
-// split-K of the tiled Schur product (gridDim.y of its launch): a batch brings its own parallelism (64 windows: 2 / 4 / 8 / 16 splits -> 47.8k /
-// 49.7k / 52.8k / 50.0k LM it/s)
-int bak_nsplit(int nwin) {
-    return nwin >= 16 ? 8 : BA_SPLITS;
 }
 
 // one LM trial slot for every window of the batch

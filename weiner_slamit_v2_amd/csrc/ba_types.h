@@ -1,8 +1,16 @@
-// ba_types.h — host/device shared layout of one local-BA window in HBM.
+// ba_types.h — host/device shared layout of one local-BA window in HBM, and the rules the host's planning (ba_plan.cc) and the
+// kernels (ba_kernels.hip) both apply to it.  Plain C++ outside a HIP compile.
 #ifndef SLAMIT_BA_TYPES_H
 #define SLAMIT_BA_TYPES_H
 
+#include <stddef.h>
 #include <stdint.h>
+
+#ifdef __HIPCC__
+#define BA_HD __host__ __device__
+#else
+#define BA_HD
+#endif
 
 #define BA_MAX_ITS 32       // == SLAMIT_BA_MAX_ITS
 #define BA_TILE 64          // Schur macro tile (rows/cols of S per workgroup)
@@ -16,6 +24,24 @@
 #define BA_SF_ROWS 63       // matrix rows one window holds (row 64 of its B operand is the right-hand side's row)
 #define BA_SOLVER_BAND 0      // narrow row envelope: block LDLt inside LDS (k_ldlt_band)
 #define BA_SOLVER_BLOCKED 1   // any other structure: 32-column panels through L2 (k_ldlt_blocked)
+#define BA_BAND_MAX 59        // widest half bandwidth k_ldlt_band takes: the reachable rows k + 4 .. k + 3 + bw stay within five block rows of the pivot's
+#define LD_BAND_LDS (150 * 1024)     // dynamic LDS k_ldlt_band may use (bak_ldlt_smem requests at least this much when it fits)
+
+// The banded solve's LDS image (ba_kernels.hip, banded path).  Row stride EVEN: a column of the band, A(c, k) for c = k + 1, k + 2, .., is a walk
+// of RS - 1 doubles per row, and an odd number of doubles per step spreads 32 lanes over 32 different bank pairs (with RS = 49 they all fell on two).
+BA_HD inline int ldlt_band_rs(int bw) { return (bw + 5) & ~1; }
+BA_HD inline int ldlt_band_ylen(int n) { return (n + 9) & ~1; }
+BA_HD inline size_t ldlt_band_bytes(int n, int bw) {
+    return sizeof(double) * ((size_t)(n + 1) * ldlt_band_rs(bw) + ldlt_band_ylen(n) + 16 * (size_t)((n + 3) / 4 + 1));
+}
+BA_HD inline bool ldlt_band_ok(int n, int bw) { return n > 0 && bw >= 8 && bw <= BA_BAND_MAX && ldlt_band_bytes(n, bw) <= LD_BAND_LDS; }
+
+// the reduced solve a window takes: its structure decides (`no_band`: SLAMIT_BA_NO_BAND, every window takes the blocked kernel)
+inline int bak_solver_kind(int n, int band, bool no_band) { return !no_band && ldlt_band_ok(n, band) ? BA_SOLVER_BAND : BA_SOLVER_BLOCKED; }
+
+// split-K of the tiled Schur product (gridDim.y of its launch): a batch brings its own parallelism (64 windows: 2 / 4 / 8 / 16 splits -> 47.8k /
+// 49.7k / 52.8k / 50.0k LM it/s)
+inline int bak_nsplit(int nwin) { return nwin >= 16 ? 8 : BA_SPLITS; }
 
 // LM control block of one window (device resident; the host only reads it back between chunks
 // of enqueued trial slots).  Mirrors the locals of OptimizationAlgorithmLevenberg::solve
@@ -63,7 +89,7 @@ struct BaWin {
     double huber_delta_s, chi2_gate_s;   // stereo edges (Optimizer.cc:570, :696)
     int32_t nrow;      // residual rows per edge record: 2 (every edge monocular) or 3 (the window has stereo observations)
     int32_t pad0;
-    // Structure of the window (host, ba_api.hip), conservative for both stages.  Points are stored sorted by the first
+    // Structure of the window (host, ba_plan.cc), conservative for both stages.  Points are stored sorted by the first
     // free keyframe that observes them, so the non-zeros of a 64-row tile of the Schur operand GA sit in ONE k range, and the reduced
     // system has a row envelope (first coupled column per pose) that LDLt without pivoting never leaves.
     int32_t tile_alo[BA_MAX_TILES], tile_ahi[BA_MAX_TILES];   // k range (multiples of BA_KC) of GA's rows 64 t .. 64 t + 63
@@ -72,7 +98,7 @@ struct BaWin {
     int16_t back_lo[BA_MAX_PANELS];    // first column any row of panel i's 32 rows reaches (back-substitution)
     int32_t band;      // half bandwidth of the reduced system's row envelope: max over rows r of r - first column of r (nS - 1: full)
     int32_t solver;    // which reduced solve takes the window (host, from nS and band): BA_SOLVER_*; one launch per kind present in a batch
-    // Schur product over FLOATING row windows (host, ba_api.hip; sf_groups == 0: 64 x 64 tile pairs over k ranges as above).  The points are sorted
+    // Schur product over FLOATING row windows (host, ba_plan.cc; sf_groups == 0: 64 x 64 tile pairs over k ranges as above).  The points are sorted
     // by their first observing keyframe, so the rows with non-zeros in one k slab of 32 (about eleven points) are a short run -- 48 rows
     // when every point is seen by eight consecutive keyframes.  Consecutive slabs whose rows fit ONE run of BA_SF_ROWS rows form a group:
     // one workgroup multiplies GA(rows, slabs) GA(rows + the right-hand side's row, slabs)^T into a 64 x 64 partial tile, and
@@ -132,5 +158,15 @@ struct BaIo {
     BaState* out_state;
 };
 
+// does the reduced system need tile pair (I, J), I <= J, of the product?  Not when the two row tiles share no k range (the block
+// is zero: k_schur_reduce writes the zeros itself), and not when the banded solver takes the window and the whole tile lies
+// outside the band (nobody reads it) -- except for the tile column that holds the right-hand side (row nS of the operand)
+BA_HD inline bool schur_tile_needed(const BaWin& W, int I, int J) {
+    const int klo = W.tile_alo[I] > W.tile_blo[J] ? W.tile_alo[I] : W.tile_blo[J];
+    const int khi = W.tile_ahi[I] < W.tile_bhi[J] ? W.tile_ahi[I] : W.tile_bhi[J];
+    if (klo >= khi) return false;
+    if (W.solver == BA_SOLVER_BAND && BA_TILE * J - (BA_TILE * I + BA_TILE - 1) > W.band && W.nS / BA_TILE != J) return false;
+    return true;
+}
 
 #endif
