@@ -114,7 +114,7 @@ def test_environment_switches_are_read_in_one_place_and_documented():
     """The library reads its environment in one function (slamit_read_switches, csrc/slamit_misc.hip, called when a handle is
     created), and the switches it reads are exactly the ones INTEGRATION.md section 6 lists."""
     csrc = os.path.join(ROOT, "weiner_slamit_v2_amd", "csrc")
-    readers = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")) and "getenv" in open(os.path.join(csrc, f)).read())
+    readers = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".cc")) and "getenv" in open(os.path.join(csrc, f)).read())
     assert readers == ["slamit_misc.hip"], readers
     read = set(re.findall(r'"(SLAMIT_[A-Z0-9_]+)"', open(os.path.join(csrc, "slamit_misc.hip")).read()))
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()

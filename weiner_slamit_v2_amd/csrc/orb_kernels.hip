@@ -16,7 +16,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <vector>
 
 #include "orb_types.h"
 #include "slamit_math.h"
@@ -67,7 +66,7 @@ __global__ __launch_bounds__(256) void resize_level_kernel(
 // K1 (per level, the path used when planes are 4-byte aligned): one lane = 4 adjacent dst pixels of
 // TWO adjacent dst rows, items flattened over (row pair, group) so every lane of every wave is busy.  All
 // per-column and per-row arithmetic the reference does at run time is in two host-built tables
-// (orbk_resize_tables):
+// (orb_plan.cc: rows4_tables):
 //   column group (3 x uint4): byte offset of the 12-byte source window | byte shift | offsets of its 2nd and
 //       3rd dword (clamped into the row) ; 4 x v_perm selector that lifts (left tap, right tap) of one dst
 //       column out of the 8-byte window as two zero-extended halfwords ; 4 x (ialpha0 | ialpha1 << 16)
@@ -157,7 +156,7 @@ __global__ __launch_bounds__(256) void resize_rows4_kernel(
 // inside one 16-byte source window, so a source row costs ONE 16-byte buffer load per eight pixels instead of one 12-byte
 // load per four, and a dst row one 8-byte store -- the kernel waits on vector-memory ISSUE, not on bytes.  After the
 // per-lane byte shift the taps of pixels 0 .. 3 lie in dwords (a0, a1) and those of pixels 4 .. 7 in (a1, a2): static
-// register pairs (orbk_resize_tables8 checks it and refuses other geometries, which keep the four-pixel kernel).
+// register pairs (orb_plan.cc: rows8_table checks it and refuses other geometries, which keep the four-pixel kernel).
 // Column group (5 x uint4): byte offset of the window | shift << 16 ; 8 x v_perm selector ; 8 x (ialpha0 | ialpha1 << 16).
 typedef unsigned rs_u4 __attribute__((ext_vector_type(4)));
 template <int RP>
@@ -227,79 +226,6 @@ __global__ __launch_bounds__(256) void resize_rows8_kernel(
                  ngroups, inv_groups, dh);
 }
 
-// Host: tables of resize_rows4_kernel for one level from the reference-shaped xofs/ialpha/yofs/ibeta tables.
-// Coefficients are non-negative (bilinear) and <= 2048, rows/columns < 65536 (checked by the caller).
-// Returns false when the geometry does not fit the kernel (scale factor > 2.3: taps of one group further than
-// 8 bytes apart; planes of 64K pixels or more): the caller then uses the fused / generic kernels.
-bool orbk_resize_tables(int dw, int dh, int sw, int sh, const int* xofs, const short* ialpha, const int* yofs,
-                        const short* ibeta, std::vector<uint32_t>& col, std::vector<uint32_t>& row) {
-    const int ng = (dw + 3) / 4, row_end = (sw + 3) & ~3;
-    if (sw >= 65536 || sh >= 65536) return false;
-    col.assign((size_t)ng * 12, 0u);
-    for (int g = 0; g < ng; ++g) {
-        int L[4], R[4];
-        uint32_t a[4];
-        for (int j = 0; j < 4; ++j) {
-            const int x = 4 * g + j;
-            if (x < dw) {
-                L[j] = xofs[x]; R[j] = std::min(xofs[x] + 1, sw - 1);
-                a[j] = (uint32_t)(unsigned short)ialpha[2 * x] | ((uint32_t)(unsigned short)ialpha[2 * x + 1] << 16);
-            } else { L[j] = L[0]; R[j] = L[0]; a[j] = 0; }   // padding pixels of the last dword: written as 0
-        }
-        const int base = L[0] & ~3, s = L[0] & 3;
-        const int off1 = base + 8 <= row_end ? 4 : 0, off2 = base + 12 <= row_end ? 8 : off1;
-        uint32_t* c = &col[(size_t)g * 12];
-        c[0] = (uint32_t)base | ((uint32_t)s << 16) | ((uint32_t)off1 << 20) | ((uint32_t)off2 << 24);
-        for (int j = 0; j < 4; ++j) {   // byte index inside the 8 bytes that start at L[0]; selector byte 0x0C reads as zero
-            if (L[j] < L[0] || R[j] < L[0] || L[j] - L[0] > 7 || R[j] - L[0] > 7 || ialpha[0] < 0) return false;
-            c[1 + j] = (uint32_t)(L[j] - L[0]) | 0x0C00u | ((uint32_t)(R[j] - L[0]) << 16) | 0x0C000000u;
-            c[5 + j] = a[j];
-        }
-    }
-    row.assign((size_t)(dh + 7) * 2, 0u);   // + 7 copies of the last row: a lane loads its (up to 8) rows as whole 16-byte pairs
-    for (int y = 0; y < dh; ++y) {
-        const int sy0 = std::min(std::max(yofs[y], 0), sh - 1), sy1 = std::min(std::max(yofs[y] + 1, 0), sh - 1);
-        row[2 * (size_t)y] = (uint32_t)sy0 | ((uint32_t)sy1 << 16);
-        row[2 * (size_t)y + 1] = (uint32_t)(unsigned short)ibeta[2 * y] | ((uint32_t)(unsigned short)ibeta[2 * y + 1] << 16);
-        if (ibeta[2 * y] < 0 || ibeta[2 * y + 1] < 0) return false;
-    }
-    for (int y = dh; y < dh + 7; ++y) { row[2 * (size_t)y] = row[2 * (size_t)(dh - 1)]; row[2 * (size_t)y + 1] = row[2 * (size_t)(dh - 1) + 1]; }
-    for (int x = 0; x < dw; ++x) if (ialpha[2 * x] < 0 || ialpha[2 * x + 1] < 0) return false;
-    return true;
-}
-
-// Column table of resize_rows8_kernel (the row table is orbk_resize_tables'); false when some group's taps do not lie as
-// the kernel assumes -- pixels 0 .. 3 within bytes 0 .. 7 of the window that starts at the group's first left tap, pixels
-// 4 .. 7 within bytes 4 .. 11 -- or the 8-byte stores of the last group would pass the row pitch.
-bool orbk_resize_tables8(int dw, int sw, size_t dstride, const int* xofs, const short* ialpha, std::vector<uint32_t>& col) {
-    const int ng = (dw + 7) / 8;
-    if (sw >= 65536 || (size_t)ng * 8 > dstride) return false;
-    col.assign((size_t)ng * 20, 0u);
-    for (int g = 0; g < ng; ++g) {
-        int L[8], R[8];
-        uint32_t a[8];
-        const int L0 = xofs[8 * g];
-        for (int j = 0; j < 8; ++j) {
-            const int x = 8 * g + j;
-            if (x < dw) {
-                L[j] = xofs[x]; R[j] = std::min(xofs[x] + 1, sw - 1);
-                if (ialpha[2 * x] < 0 || ialpha[2 * x + 1] < 0) return false;
-                a[j] = (uint32_t)(unsigned short)ialpha[2 * x] | ((uint32_t)(unsigned short)ialpha[2 * x + 1] << 16);
-            } else { L[j] = R[j] = L0 + (j >= 4 ? 4 : 0); a[j] = 0; }   // padding pixels of the last group: written as 0
-        }
-        uint32_t* c = &col[(size_t)g * 20];
-        c[0] = (uint32_t)(L0 & ~3) | ((uint32_t)(L0 & 3) << 16);
-        for (int j = 0; j < 8; ++j) {
-            const int lo = j >= 4 ? 4 : 0;   // byte index inside the dword pair the pixel reads
-            const int bl = L[j] - L0 - lo, br = R[j] - L0 - lo;
-            if (bl < 0 || bl > 7 || br < 0 || br > 7) return false;
-            c[1 + j] = (uint32_t)bl | 0x0C00u | ((uint32_t)br << 16) | 0x0C000000u;
-            c[9 + j] = a[j];
-        }
-    }
-    return true;
-}
-
 void orbk_resize_rows8(hipStream_t st, const uint8_t* src, size_t sstride, size_t sframe, int sh, uint8_t* dst, int dw, int dh,
                        size_t dstride, size_t dframe, const uint32_t* d_col8, const uint32_t* d_row, int nframes) {
     const int ng = (dw + 7) / 8, nitems = ng * ((dh + 2 * RS_RP - 1) / (2 * RS_RP));
@@ -321,7 +247,7 @@ void orbk_resize_rows4(hipStream_t st, const uint8_t* src, size_t sstride, size_
 // once, then produces level 1, 2, ... each from the previous level kept in LDS (two ping-pong
 // buffers), storing only the pixels it owns.  The chain of integer roundings is exactly the
 // reference's (level l is always computed from level l-1), but no level is ever re-read from HBM
-// and six dependent launches disappear.  Boxes come from the host (orb_api.hip: build_pyr_boxes).
+// and six dependent launches disappear.  Boxes come from the host plan (orb_plan.cc: plan_pyramid_boxes).
 // --------------------------------------------------------------------------------------------
 #define PYR_THREADS 512
 
@@ -540,7 +466,7 @@ __device__ __forceinline__ void fast_cell_wave(
     unsigned short* s_ent = reinterpret_cast<unsigned short*>(sc + fast_sc_bytes(PITCH, sc_rows));
     unsigned short* s_kp = s_ent + FAST_ENT_CAP;
 
-    // the cell's geometry and the division it needs, precomputed on the host (orbk_fast_cells): one scalar
+    // the cell's geometry and the division it needs, precomputed on the host (orb_plan.cc: fast_cells): one scalar
     // 16-byte load instead of ~400 instructions of level search and integer division per wave
     const uint4 ca = cells[cell];
     const int level = (int)(ca.x & 255u), c = (int)(ca.x >> 8);
@@ -954,12 +880,6 @@ extern "C" int slamit_diag_oct(unsigned long long* out) { return (int)hipMemcpyF
 #ifndef OCT_THREADS
 #define OCT_THREADS 512
 #endif
-__host__ __device__ inline size_t orbk_octree_node_bytes(int node_cap) {
-    return ((size_t)node_cap * (8 + 2 * 8 + 2 * 4 + 4 * 4 + 5 * 4 + 4 + 4) + 64 + 15) & ~(size_t)15;
-}
-#define OCT_LDS_KEYS_MAX 10240   // LDS key arrays hold at most this many candidates of one (frame, level), 6 bytes each
-#define OCT_LDS_KEYS_MIN 2048
-#define OCT_LDS_BUDGET (78 * 1024)   // per workgroup, so that two fit a CU
 
 // depth of the path table the full passes are served from: the deepest of 4, 3, 2 whose table (4 + .. + 4^depth ints per root)
 // fits `room` ints; 0 = no table (a sweep over the keys per pass)
@@ -1512,7 +1432,6 @@ __device__ __forceinline__ int reflect101(int p, int len) {
 // step s is being filtered, so the HBM/L2 latency is paid once per strip.  Dwords that lie fully
 // inside an image row are loaded whole (planes are 4-byte aligned); edge dwords go byte by byte
 // through the REFLECT_101 map.
-#define BLUR_STEPS 4
 
 typedef unsigned short blur_us2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c) {   // a.lo*b.lo + a.hi*b.hi + c (v_dot2_u32_u16)
@@ -1662,7 +1581,7 @@ __global__ __launch_bounds__(256) void blur_all_kernel(
     if (logical >= total) return;
     int frame = (int)__umulhi(logical, inv_tiles);
     if ((unsigned)frame * ntiles > logical) --frame;   // the rounded-up reciprocal can overshoot by one on huge grids
-    const uint4 tt = tiles[logical - (unsigned)frame * ntiles];   // host-built (orbk_blur_tiles): level, strip origin -- no level search
+    const uint4 tt = tiles[logical - (unsigned)frame * ntiles];   // host-built (orb_plan.cc: blur_strips): level, strip origin -- no level search
     const int level = (int)tt.x, bx = (int)tt.y, by0 = (int)tt.z;
     const OrbLevel& L = levels[level];
     const int w = L.w, h = L.h;
@@ -1673,7 +1592,7 @@ __global__ __launch_bounds__(256) void blur_all_kernel(
     const bool aligned = ((((uintptr_t)S) | sstride) & 3) == 0;
     uint8_t* D = blur + L.blur_off + (size_t)frame * L.blur_bytes;
     // most strips lie inside their level: they take the copy of the loop without reflection, byte path and predicates
-    const bool interior = aligned && bx >= 4 && bx + 68 <= w && by0 >= 3 && by0 + 16 * BLUR_STEPS + 3 <= h;
+    const bool interior = aligned && bx >= 4 && bx + 68 <= w && by0 >= 3 && by0 + ORB_BLUR_STRIP_H + 3 <= h;
     if (interior) blur_strip<true>(in, rp, S, sstride, aligned, D, (unsigned)L.stride, w, h, bx, by0, tid);
     else blur_strip<false>(in, rp, S, sstride, aligned, D, (unsigned)L.stride, w, h, bx, by0, tid);
 }
@@ -1715,7 +1634,7 @@ __global__ __launch_bounds__(256) void blur_stream_kernel(
     const uint32_t TA = 18u | (34u << 8) | (49u << 16) | (55u << 24), TB = 49u | (34u << 8) | (18u << 16);
     const uint32_t kA0 = 18u | (34u << 16), kA1 = 49u | (55u << 16), kA2 = 49u | (34u << 16), kA3 = 18u;           // output row 2p - 3
     const uint32_t kB0 = 18u << 16, kB1 = 34u | (49u << 16), kB2 = 55u | (49u << 16), kB3 = 34u | (18u << 16);     // output row 2p - 2
-    const int ylast = min(by0 + 16 * BLUR_STEPS, h) - 1;
+    const int ylast = min(by0 + ORB_BLUR_STRIP_H, h) - 1;
     const int p0 = (by0 - 3) >> 1, p1 = (ylast + 3) >> 1;   // pairs of rows (2p, 2p + 1); arithmetic shift: by0 - 3 may be negative
     typedef unsigned blur_u3 __attribute__((ext_vector_type(3)));
     auto fetch = [&](int yy) -> blur_u3 {
@@ -1986,31 +1905,7 @@ hipError_t orbk_fast_prepare(int max_wcell, int max_hcell) {
     return e;
 }
 
-// Cell table: the non-empty FAST cells of every level in the reference's visiting order (level, row, column;
-// ORBextractor.cc:805-822), 4 words per cell:
-//   0: level | cell index in the level << 8      1: iniX | iniY << 16      2: cw | ch << 8 (window size)
-//   3: division magic  floor(2^20 / g) + 1  for g = (sw + 3) / 4, the groups of four scan pixels per row
-int orbk_fast_cells(const OrbLevel* host_levels, int nlevels, std::vector<uint32_t>& out) {
-    out.clear();
-    auto magic = [](int g) { return (uint32_t)((1u << 20) / (unsigned)std::max(g, 1) + 1u); };
-    for (int l = 0; l < nlevels; ++l) {
-        const OrbLevel& L = host_levels[l];
-        for (int c = 0; c < L.ncells; ++c) {
-            const int ci = c / L.nCols, cj = c - ci * L.nCols;
-            const int iniX = ORB_MIN_BORDER + cj * L.wCell, iniY = ORB_MIN_BORDER + ci * L.hCell;
-            if (iniY >= L.maxBorderY - 3 || iniX >= L.maxBorderX - 6) continue;  // ORBextractor.cc:810,819
-            const int cw = std::min(L.wCell + 6, L.maxBorderX - iniX), ch = std::min(L.hCell + 6, L.maxBorderY - iniY);
-            const int sw = cw - 6, sh = ch - 6;
-            if (sw <= 0 || sh <= 0) continue;
-            const uint32_t w[4] = {(uint32_t)l | ((uint32_t)c << 8), (uint32_t)iniX | ((uint32_t)iniY << 16),
-                                   (uint32_t)cw | ((uint32_t)ch << 8), magic((sw + 3) >> 2)};
-            out.insert(out.end(), w, w + 4);
-        }
-    }
-    return (int)(out.size() / 4);
-}
-
-void orbk_fast(hipStream_t st, const OrbLevel* host_levels, int nlevels, const uint32_t* d_cells, int cells_per_frame,
+void orbk_fast(hipStream_t st, const FastTab& tab, int nlevels, const uint32_t* d_cells, int cells_per_frame,
                const uint8_t* img0, size_t img0_stride, size_t img0_frame, const uint8_t* pyr,
                unsigned long long* cand, size_t cand_frame_stride, int* cand_count, int iniTh, int minTh,
                int max_wcell, int max_hcell, int nframes) {
@@ -2025,14 +1920,6 @@ void orbk_fast(hipStream_t st, const OrbLevel* host_levels, int nlevels, const u
     const dim3 grid = xcd_frames ? dim3((unsigned)(((nframes + 7) / 8) * 8) * (unsigned)((cells_per_frame + wpb - 1) / wpb))
                                  : dim3(wpb == 1 ? (unsigned)((cells_per_frame + 31) & ~31) : (unsigned)((cells_per_frame + wpb - 1) / wpb), nframes);
     const size_t smem = orbk_fast_smem(max_wcell, max_hcell) / 4 * wpb;
-    FastTab tab = {};
-    for (int l = 0; l < nlevels && l < ORB_MAX_LEVELS; ++l) {
-        const OrbLevel& S = host_levels[l];
-        FastLevel& D = tab.lv[l];
-        D.cell_base = S.cell_base; D.nCols = S.nCols; D.wCell = S.wCell; D.hCell = S.hCell;
-        D.maxBorderX = S.maxBorderX; D.maxBorderY = S.maxBorderY; D.stride = S.stride; D.cand_cap = S.cand_cap;
-        D.plane_off = S.plane_off; D.plane_bytes = S.plane_bytes; D.cand_off = S.cand_off;
-    }
     if (fast_pitch(max_wcell) == FAST_PS)
         hipLaunchKernelGGL(fast_cells_kernel<FAST_PS>, grid, dim3(64 * wpb), smem, st, tab, reinterpret_cast<const uint4*>(d_cells), nlevels, cells_per_frame, img0,
                            (unsigned)img0_stride, img0_frame, pyr, cand, cand_frame_stride, cand_count, iniTh, minTh, tile_rows,
@@ -2042,17 +1929,6 @@ void orbk_fast(hipStream_t st, const OrbLevel* host_levels, int nlevels, const u
                            (unsigned)img0_stride, img0_frame, pyr, cand, cand_frame_stride, cand_count, iniTh, minTh, tile_rows,
                            sc_rows, kp_cap, xcd_frames);
 }
-
-// candidates kept in LDS: as many as fit beside the node arrays in half a CU's LDS (lists above that use the HBM workspace)
-// LDS budget of one octree workgroup.  Two 78 KB workgroups fill a CU's LDS, which also keeps every other kernel off
-// the chip while the octree pass (a few hundred workgroups, latency bound) runs; images up to about VGA rarely have more
-// than 5,000 candidates on a level, so their handles take 48 KB and the blur runs beside the octree on the side stream.
-int orbk_octree_key_cap(int node_cap, int width, int height) {
-    long budget = (long)width * height <= 640L * 480L * 3 / 2 ? 48L * 1024 : (long)OCT_LDS_BUDGET;
-    const long room = budget - (long)orbk_octree_node_bytes(node_cap);
-    return (int)std::min<long>(OCT_LDS_KEYS_MAX, std::max<long>(OCT_LDS_KEYS_MIN, room / 6)) & ~7;
-}
-size_t orbk_octree_smem(int node_cap, int key_cap) { return orbk_octree_node_bytes(node_cap) + (size_t)key_cap * 6; }
 
 hipError_t orbk_octree_prepare(int node_cap, int key_cap) {
     static int prepared = 0;   // the attribute is per function, not per handle: keep the largest request
@@ -2106,30 +1982,6 @@ void orbk_ic_angle(hipStream_t st, const OrbLevel* levels, int nlevels, const ui
     else
         hipLaunchKernelGGL(ic_angle_kernel, dim3(kblocks, nlevels, nframes), dim3(256), 0, st, levels,
                            nlevels, img0, img0_stride, img0_frame, pyr, lkp, kp_frame_stride, kp_count, 0, kblocks);
-}
-
-// Strip table of blur_all_kernel: (level, bx, by0, 0) for every 64 x 64 strip of every level, level-major
-int orbk_blur_tiles(const OrbLevel* host_levels, int nlevels, std::vector<uint32_t>& out) {
-    out.clear();
-    for (int l = 0; l < nlevels; ++l)
-        for (int by = 0; by < host_levels[l].h; by += 16 * BLUR_STEPS)
-            for (int bx = 0; bx < host_levels[l].w; bx += 64) { const uint32_t t[4] = {(uint32_t)l, (uint32_t)bx, (uint32_t)by, 0u}; out.insert(out.end(), t, t + 4); }
-    return (int)(out.size() / 4);
-}
-
-// The same strips as two tables (both level-major): those whose columns lie inside the level (blur_stream_kernel) and the
-// rest (blur_all_kernel); per level the number of entries of each.  The caller uses them when the planes are 4-byte aligned.
-void orbk_blur_tiles_split(const OrbLevel* host_levels, int nlevels, std::vector<uint32_t>& stream, std::vector<uint32_t>& edge,
-                           std::vector<int>& n_stream, std::vector<int>& n_edge) {
-    stream.clear(); edge.clear(); n_stream.assign(nlevels, 0); n_edge.assign(nlevels, 0);
-    for (int l = 0; l < nlevels; ++l)
-        for (int by = 0; by < host_levels[l].h; by += 16 * BLUR_STEPS)
-            for (int bx = 0; bx < host_levels[l].w; bx += 64) {
-                const uint32_t t[4] = {(uint32_t)l, (uint32_t)bx, (uint32_t)by, 0u};
-                const bool inside = bx >= 4 && bx + 68 <= host_levels[l].w && (host_levels[l].stride & 3) == 0;
-                (inside ? stream : edge).insert((inside ? stream : edge).end(), t, t + 4);
-                ++(inside ? n_stream : n_edge)[l];
-            }
 }
 
 void orbk_blur_stream(hipStream_t st, const OrbLevel* levels, const uint32_t* d_tiles, int ntiles, const uint8_t* img0,

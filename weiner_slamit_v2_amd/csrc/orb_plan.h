@@ -1,0 +1,69 @@
+// orb_plan.h — host-side plan of an ORB extractor handle: scale tables and quotas, level geometry, the FAST cell table, the blur
+// strip tables, the cv::resize tables of every pyramid path and the fused pyramid's boxes, and where each read-only table sits in
+// the handle's one device block.  Plain C++17 (no HIP): the extractor (orb_api.hip) and the CPU test of the plan
+// (tests/test_orb_plan.py) both build it.
+#ifndef SLAMIT_ORB_PLAN_H
+#define SLAMIT_ORB_PLAN_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/slamit.h"
+#include "orb_types.h"
+
+// What steers the plan besides the parameters: SlamitSwitches::resize_no8 (no resize_rows8_kernel tables).
+struct OrbPlanOptions {
+    bool resize_no8;
+};
+
+// Blur strips (64 columns x ORB_BLUR_STRIP_H rows), level-major, 4 words each: level | bx | by0 | 0.
+struct OrbStrips {
+    std::vector<uint32_t> tab;
+    int base[ORB_MAX_LEVELS + 1];   // first entry of level l; base[nlevels]: the total
+    size_t off;                     // in the table block
+};
+
+// Level l from level l-1 (l >= 1): the reference-shaped cv::resize INTER_LINEAR 8U tables and the row kernels' packed ones.
+struct OrbResizeTabs {
+    std::vector<int32_t> xofs, yofs;
+    std::vector<int16_t> ialpha, ibeta;
+    std::vector<uint32_t> col4, row4;   // resize_rows4_kernel; empty where the level's geometry does not fit it
+    std::vector<uint32_t> col8;         // resize_rows8_kernel (its row table is row4); empty where refused or resize_no8
+    size_t xofs_off, ialpha_off, yofs_off, ibeta_off, col4_off, row4_off, col8_off;   // in the table block
+};
+
+struct OrbPlan {
+    // ORBextractor's tables (mvScaleFactor, mvInvScaleFactor, mvLevelSigma2, mvInvLevelSigma2, mnFeaturesPerLevel)
+    std::vector<float> scale, inv_scale, sigma2, inv_sigma2;
+    std::vector<int> per_level;
+    std::vector<OrbLevel> levels;   // none for an empty image (and then no tables either)
+    // per-frame sizes: frames are the outer dimension of every per-frame array
+    size_t pyr_frame_total, blur_frame_total, cand_frame_stride, kp_frame_stride;
+    int max_out, node_cap, oct_key_cap, max_kp_level, max_wcell, max_hcell;
+    // FAST: the non-empty cells in the reference's visiting order, 4 words each, and the per-level table the kernel takes by value
+    std::vector<uint32_t> cells;
+    size_t cells_off;
+    FastTab fast;
+    // blur: every strip (blur_all_kernel), and the same strips split into those inside the level (blur_stream_kernel) and the rest
+    OrbStrips blur_all, blur_str, blur_edge;
+    // pyramid: per-level tables ([nlevels], entry 0 unused); rows4_ok: every level fits the row kernels
+    std::vector<OrbResizeTabs> rs;
+    bool rows4_ok;
+    // fused pyramid: [pyr_regions][nlevels] boxes and a PyrTabs per level; pyr_regions 0: no fused plan
+    int pyr_regions, pyr_bufA, pyr_smem;
+    std::vector<PyrBox> boxes;
+    size_t levels_off, boxes_off, tabs_off;
+    size_t table_bytes;   // the table block
+};
+
+// Plans a handle for p.  Returns false with *why set when the geometry cannot be extracted (a level smaller than one FAST cell,
+// an aspect ratio beyond ORB_MAX_ROOTS octree roots, or more features than the LDS octree holds).  p is range-checked already.
+bool orb_plan(const slamit_orb_params& p, const OrbPlanOptions& o, OrbPlan& plan, const char** why);
+
+// The table block as the device gets it (table_bytes): every table at its offset, the PyrTabs pointing into `base` (the block's
+// device address; null gives offsets).
+void orb_plan_image(const OrbPlan& plan, const uint8_t* base, std::vector<uint8_t>& img);
+
+#endif

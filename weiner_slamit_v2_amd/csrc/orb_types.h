@@ -1,9 +1,16 @@
-// orb_types.h — host/device shared descriptors of the ORB pipeline's HBM layout.
+// orb_types.h — host/device shared descriptors of the ORB pipeline's HBM layout, and the rules the host's planning (orb_plan.cc)
+// and the kernels (orb_kernels.hip) both apply to it.  Plain C++ outside a HIP compile.
 #ifndef SLAMIT_ORB_TYPES_H
 #define SLAMIT_ORB_TYPES_H
 
 #include <stddef.h>
 #include <stdint.h>
+
+#ifdef __HIPCC__
+#define ORB_HD __host__ __device__
+#else
+#define ORB_HD
+#endif
 
 #define ORB_MAX_LEVELS 16
 #define ORB_MAX_ROOTS 8          // octree root nodes = round(width/height) of the detection box
@@ -12,6 +19,17 @@
 #define ORB_TILE_MAX (ORB_CELL_MAX + 6)
 #define ORB_CC_PAD 32            // ints between two (frame, level) candidate counters: one 128-byte line each, so the
                                  // FAST waves' atomics do not serialise on one L2 line
+#define BLUR_STEPS 4             // 16-row steps of one blur strip
+#define ORB_BLUR_STRIP_H (16 * BLUR_STEPS)   // rows of one blur strip (strips are 64 columns wide)
+
+// LDS of one octree workgroup: the node arrays, then the key arrays (6 bytes per candidate)
+ORB_HD inline size_t orbk_octree_node_bytes(int node_cap) {
+    return ((size_t)node_cap * (8 + 2 * 8 + 2 * 4 + 4 * 4 + 5 * 4 + 4 + 4) + 64 + 15) & ~(size_t)15;
+}
+ORB_HD inline size_t orbk_octree_smem(int node_cap, int key_cap) { return orbk_octree_node_bytes(node_cap) + (size_t)key_cap * 6; }
+#define OCT_LDS_KEYS_MAX 10240   // LDS key arrays hold at most this many candidates of one (frame, level), 6 bytes each
+#define OCT_LDS_KEYS_MIN 2048
+#define OCT_LDS_BUDGET (78 * 1024)   // per workgroup, so that two fit a CU
 
 // One pyramid level.  Planes of all frames of a batch are stored level-major:
 //   plane(level, frame) = pyr + plane_off + frame * plane_bytes, rows of `stride` bytes
@@ -30,7 +48,7 @@ struct OrbLevel {
     int32_t maxBorderX, maxBorderY;   // w - 16, h - 16
     int32_t cell_base;         // index of this level's first cell in the per-frame cell list
     int32_t ncells;
-    int32_t blur_tile_base;    // index of this level's first 64x16 blur tile in the per-frame tile list
+    int32_t blur_tile_base;    // index of this level's first blur strip (64 x ORB_BLUR_STRIP_H) in the per-frame strip list
     // candidate list of (frame, level): cand + cand_off + frame * cand_frame_stride  (elements)
     uint64_t cand_off;
     int32_t cand_cap;
