@@ -380,7 +380,10 @@ typedef struct slamit_ba_result {
 typedef struct slamit_ba slamit_ba;
 
 /* A BA handle owns device workspaces sized for up to max_kf/max_pt/max_edge and max_batch
- * independent windows. */
+ * independent windows.  max_kf <= 85: the blocked LDLt of the reduced system keeps its panel
+ * (rup(6 * max_kf + 1, 64) rows: 512 at 85 keyframes, 576 at 86) in LDS, and the create call
+ * fails with SLAMIT_ERR_ARG when that panel does not fit.  Fixed keyframes count toward
+ * max_kf, although they do not enter the reduced system. */
 int slamit_ba_create(int max_kf, int max_pt, int max_edge, int max_batch, int device,
                      slamit_ba** out);
 void slamit_ba_destroy(slamit_ba* h);

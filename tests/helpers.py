@@ -38,6 +38,34 @@ def load_ba_golden(path):
     return prob, ref
 
 
+# Local-BA windows at a handle's capacity: max_kf = 85 is the largest slamit_ba_create accepts (include/slamit.h), Npad = 512.
+# name -> synth.synth_ba keyword arguments.  tests/test_ba_capacity_plan.py checks on the CPU that the planner sends each one to the
+# variant of the kernels named beside it; tests/test_gpu_ba.py runs them against the oracle.
+BA_CAPACITY = {
+    "band512": dict(n_kf=85, n_pt=1200, obs_per_pt=3, seed=92),           # nS 504: the banded solve at n = 504, Schur tiles 6-8
+    "blocked512": dict(n_kf=85, n_pt=2000, obs_per_pt=8, seed=94),        # the blocked solve over 16 panels, floating-window Schur
+    "tiles512": dict(n_kf=85, n_pt=600, obs_per_pt=None, seed=96),        # dense: blocked, the Schur product over 8 x 8 tile pairs
+    "kpad12k": dict(n_kf=85, n_pt=4000, obs_per_pt=8, seed=97),           # Kpad 12288
+    "kf70": dict(n_kf=70, n_pt=1500, obs_per_pt=5, seed=98),              # Npad 448, banded
+    "fixed40": dict(n_kf=85, n_pt=1000, obs_per_pt=6, seed=95, n_fixed=40),   # 40 fixed keyframes: nS 270 (run with them listed last)
+    "stereo512": dict(n_kf=85, n_pt=1200, obs_per_pt=4, seed=93, stereo_frac=0.5),   # monocular and stereo edges, Npad 512
+}
+
+
+def fixed_keyframes_last(prob):
+    """The same window with its fixed keyframes listed after the free ones, as the shim lists ORB-SLAM2's fixed cameras
+    (shim/Optimizer.h: LocalBundleAdjustment); -> (problem, perm): new position i holds old keyframe perm[i]."""
+    fixed = np.asarray(prob["kf_fixed"]) != 0
+    perm = np.concatenate([np.flatnonzero(~fixed), np.flatnonzero(fixed)])
+    inv = np.empty(len(perm), np.int64)
+    inv[perm] = np.arange(len(perm))
+    q = dict(prob)
+    for k in ("kf_pose", "kf_fixed", "kf_intr") + (("kf_bf",) if prob.get("kf_bf") is not None else ()):
+        q[k] = np.ascontiguousarray(np.asarray(prob[k])[perm])
+    q["edge_kf"] = inv[np.asarray(prob["edge_kf"])].astype(np.int32)
+    return q, perm
+
+
 def load_pose_golden(path):
     z = np.load(path)
     prob = {k: z[k].astype(np.float64) for k in ("pose", "intr", "xw", "uv", "inv_sigma2")}

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import bindings as ob
-from tests.helpers import ROOT, load_ba_golden
+from tests.helpers import BA_CAPACITY, ROOT, fixed_keyframes_last, load_ba_golden
 from weiner_slamit_v2_amd import api, synth
 
 pytestmark = pytest.mark.gpu
@@ -354,3 +354,85 @@ def test_stop_flag_aborts_a_running_solve(opt):
     # part of the measured interval, so the bound is the full solve itself
     assert latency < full_s + 1e-3, "stop latency %.2f ms (full solve %.2f ms)" % (1e3 * latency, 1e3 * full_s)
     big.close()
+
+
+# ---- windows at a handle's capacity: max_kf = 85, the largest slamit_ba_create accepts (Npad 512; tests/test_ba_capacity_plan.py) ----
+
+@pytest.fixture(scope="module")
+def opt85():
+    return api.Optimizer(max_kf=85, max_pt=4096, max_edge=60000, max_batch=16)
+
+
+def _capacity(name):
+    """BA_CAPACITY[name]; the 40-fixed window with its fixed keyframes listed last, where the shim lists ORB-SLAM2's fixed cameras."""
+    prob = synth.synth_ba(**BA_CAPACITY[name])
+    return fixed_keyframes_last(prob)[0] if name == "fixed40" else prob
+
+
+def test_create_at_the_keyframe_ceiling(opt85):
+    """85 keyframes (Npad 512) is the largest handle; at 86 (Npad 576) the blocked LDLt's panel no longer fits in LDS."""
+    with pytest.raises(api.SlamitError, match="LDLt"):
+        api.Optimizer(max_kf=86, max_pt=64, max_edge=64, max_batch=1)
+    assert opt85._h is not None
+
+
+@pytest.mark.parametrize("name", sorted(BA_CAPACITY))
+def test_capacity_windows_vs_oracle(opt85, name):
+    """Schur tiles 6-8 and tile pairs over the 8 x 8 grid, LDLt panels 11-16 (blocked) and the banded solve at n = 504, Kpad 12288, the
+    pose-reduction grids of an 85-keyframe handle, and 40 fixed keyframes listed after the free ones."""
+    prob = _capacity(name)
+    _close(opt85.LocalBundleAdjustment(prob), ob.ba_solve(prob), name, prob=prob)
+
+
+def test_capacity_band_window_through_the_blocked_path(opt85):
+    """The Npad 512 banded window through the blocked LDLt as well (SLAMIT_BA_NO_BAND=1 in a child process): the same solution."""
+    import subprocess, sys, tempfile
+    prob = _capacity("band512")
+    res = opt85.LocalBundleAdjustment(prob)
+    code = ("import sys, numpy as np; sys.path.insert(0, %r)\n"
+            "from weiner_slamit_v2_amd import api, synth\n"
+            "prob = synth.synth_ba(**%r)\n"
+            "o = api.Optimizer(max_kf=85, max_pt=4096, max_edge=60000, max_batch=1)\n"
+            "r = o.LocalBundleAdjustment(prob)\n"
+            "np.savez(sys.argv[1], kf_pose=r['kf_pose'], pt_xyz=r['pt_xyz'], edge_outlier=r['edge_outlier'], n_its=np.array(r['stats']['n_its']))\n"
+            % (ROOT, BA_CAPACITY["band512"]))
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "r.npz")
+        subprocess.check_call([sys.executable, "-c", code, out], env=dict(os.environ, SLAMIT_BA_NO_BAND="1"), cwd=ROOT, timeout=300)
+        d = np.load(out)
+    scale = max(np.abs(d["kf_pose"]).max(), 1.0)
+    assert np.abs(res["kf_pose"] - d["kf_pose"]).max() / scale <= 1e-7
+    assert np.abs(res["pt_xyz"] - d["pt_xyz"]).max() / max(np.abs(d["pt_xyz"]).max(), 1.0) <= 1e-7
+    assert (res["edge_outlier"] == d["edge_outlier"]).all() and list(d["n_its"]) == list(res["stats"]["n_its"])
+
+
+def test_capacity_schur_over_tile_pairs(opt85, monkeypatch):
+    """An Npad 512 window through the floating-window Schur product (default) and over the 8 x 8 tile pairs (SLAMIT_BA_SF=0): the same
+    poses, points, flags and LM path; the floating form executes fewer flops."""
+    prob = _capacity("blocked512")
+    monkeypatch.setenv("SLAMIT_BA_SF", "0")
+    tiles = api.Optimizer(max_kf=85, max_pt=4096, max_edge=60000, max_batch=1)   # (a handle reads the switches when it is created)
+    monkeypatch.delenv("SLAMIT_BA_SF")
+    out = []
+    for o in (opt85, tiles):
+        o.profile(True)
+        out.append((o.LocalBundleAdjustment(prob), o.profile_read()["schur_exec_mflop"]))
+        o.profile(False)
+    tiles.close()
+    (a, m_sf), (b, m_tile) = out
+    assert m_sf < 0.5 * m_tile, (m_sf, m_tile)
+    scale = max(np.abs(b["kf_pose"]).max(), 1.0)
+    assert np.abs(a["kf_pose"] - b["kf_pose"]).max() / scale <= 1e-7
+    assert np.abs(a["pt_xyz"] - b["pt_xyz"]).max() / max(np.abs(b["pt_xyz"]).max(), 1.0) <= 1e-7
+    assert (a["edge_outlier"] == b["edge_outlier"]).all() and a["stats"]["n_its"] == b["stats"]["n_its"] and a["stats"]["trials"] == b["stats"]["trials"]
+    _close(b, ob.ba_solve(prob), "blocked512, tile pairs")
+
+
+def test_capacity_batch_of_16(opt85):
+    """16 windows on the 85-keyframe handle (the batch's eight-split launch, pose blocks on their own): every capacity window, the
+    stereo one among them, beside small windows; each against the oracle."""
+    probs = [_capacity(n) for n in sorted(BA_CAPACITY)]
+    probs += [synth.synth_ba(8 + 3 * i, 120 + 40 * i, 3 + i % 4, seed=100 + i) for i in range(16 - len(probs))]
+    outs = opt85.LocalBundleAdjustmentBatch(probs)
+    for i, (p, o) in enumerate(zip(probs, outs)):
+        _close(o, ob.ba_solve(p), "capacity batch[%d]" % i, prob=p)

@@ -62,7 +62,10 @@ def test_golden_set_is_complete():
 
 # (keyframes, points, observations per point, seed, fixed keyframes); the reference g2o's results on these problems are stored
 # in tests/golden/ref_g2o_cases.json.gz (tools/gen_ref_cases_golden.py)
-REF_CASES = [(6, 80, 3, 21, 1), (9, 120, 5, 22, 2), (20, 400, 6, 23, 1), (15, 250, None, 24, 1)]
+REF_CASES = [(6, 80, 3, 21, 1), (9, 120, 5, 22, 2), (20, 400, 6, 23, 1), (15, 250, None, 24, 1),
+             # windows at a handle's capacity, max_kf = 85 (tests/test_ba_capacity_plan.py): Npad 512 through the banded solve and
+             # through the blocked one over 16 panels, and 40 fixed keyframes (they count toward max_kf, not toward the reduced system)
+             (85, 1200, 3, 92, 1), (85, 900, 8, 94, 1), (85, 1000, 6, 95, 40)]
 
 
 @pytest.mark.parametrize("k,p,o,seed,nfix", REF_CASES)

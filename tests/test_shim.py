@@ -132,6 +132,34 @@ def test_shim_optimizer_local_ba(tmp_path, name):
 
 
 @pytest.mark.gpu
+def test_shim_optimizer_local_ba_past_64_keyframes(tmp_path):
+    """A window of 70 keyframes through LocalMapping.cc:84's call: the shim's handle starts at 64 keyframes and must grow to one the
+    library accepts (slamit_ba_create takes at most 85, include/slamit.h), not to twice the window, which it refuses.  Two of the three
+    fixed keyframes see no local keyframe, so the shim lists them last, as fixed cameras (Optimizer.cc:480-504)."""
+    from oracle import bindings as ob
+    from weiner_slamit_v2_amd import synth
+
+    _build()
+    prob = synth.synth_ba(70, 1500, 5, seed=98, n_fixed=3)
+    for k in ("kf_pose", "kf_intr", "pt_xyz", "edge_uv", "edge_inv_sigma2"):   # what the shim's float32 KeyFrame / MapPoint types hold
+        prob[k] = prob[k].astype(np.float32).astype(np.float64)
+    ref = ob.ba_solve(prob)
+    blob, K, P = _ba_blob(prob)
+    pin, pout = tmp_path / "p.bin", tmp_path / "o.bin"
+    open(pin, "wb").write(blob)
+    subprocess.check_call([EXE, "ba", str(pin), str(pout)])
+    raw = open(pout, "rb").read()
+    f = np.frombuffer(raw, np.float32, 12 * K + 3 * P)
+    R, t, pts = f[:9 * K].reshape(K, 9), f[9 * K:12 * K].reshape(K, 3), f[12 * K:].reshape(P, 3)
+    erased, updates = struct.unpack_from("<ii", raw, 4 * (12 * K + 3 * P))
+    # float32 write-back, as in test_shim_optimizer_local_ba
+    assert np.abs(R - ref["kf_pose"][:, :9]).max() < 2e-6
+    assert np.abs(t - ref["kf_pose"][:, 9:]).max() < 1e-5 * max(np.abs(ref["kf_pose"][:, 9:]).max(), 1)
+    assert np.abs(pts - ref["pt_xyz"]).max() < 1e-5 * np.abs(ref["pt_xyz"]).max()
+    assert erased == int(ref["edge_outlier"].sum()) and updates == P
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("name", ["typical", "stereo_mixed"])
 def test_shim_optimizer_pose_optimization(tmp_path, name):
     """Tracking's Optimizer::PoseOptimization(&mCurrentFrame) against a mock Frame; "stereo_mixed": half of the keypoints carry

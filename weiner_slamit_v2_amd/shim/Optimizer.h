@@ -24,6 +24,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <list>
 #include <map>
 #include <mutex>
@@ -101,7 +102,11 @@ inline int Optimizer::SolvePOD(const slamit_ba_problem& prob, const slamit_ba_op
         cap[1] = prob.n_pt > 4096 ? 2 * prob.n_pt : 4096;
         cap[2] = prob.n_edge > 65536 ? 2 * prob.n_edge : 65536;
         int rc = slamit_ba_create(cap[0], cap[1], cap[2], 1, deviceRef(), &handleRef());
-        if (rc != SLAMIT_OK) { handleRef() = 0; cap[0] = cap[1] = cap[2] = 0; return lastStatus() = rc; }
+        if (rc != SLAMIT_OK) {   // no room to grow (max_kf <= 85, slamit.h): a handle of exactly this window
+            cap[0] = std::max<int>(prob.n_kf, 1); cap[1] = std::max<int>(prob.n_pt, 1); cap[2] = std::max<int>(prob.n_edge, 1);
+            rc = slamit_ba_create(cap[0], cap[1], cap[2], 1, deviceRef(), &handleRef());
+        }
+        if (rc != SLAMIT_OK) { handleRef() = 0; cap[0] = cap[1] = cap[2] = 0; return lastStatus() = rc; }   // slamit_last_error() says why
     }
     return lastStatus() = slamit_ba_solve(handleRef(), &prob, &opts, &res);
 }
