@@ -386,6 +386,23 @@ typedef struct slamit_ba slamit_ba;
  * max_kf, although they do not enter the reduced system. */
 int slamit_ba_create(int max_kf, int max_pt, int max_edge, int max_batch, int device,
                      slamit_ba** out);
+
+/* The same handle with the reduced system sized apart from the keyframe tables: max_kf counts free and fixed keyframes together
+ * (poses, intrinsics, bf: memory only), max_free_kf (1 .. max_kf) the free ones, which alone enter the reduced system
+ * (rup(6 * max_free_kf + 1, 64) rows).  Windows of up to 512 rows solve as on a slamit_ba_create handle (same plan, same kernels);
+ * larger ones take a tiled LDLt through HBM.  max_free_kf > SLAMIT_BA_MAX_FREE_KF fails with SLAMIT_ERR_ARG; a window with more
+ * free keyframes than max_free_kf fails its solve with SLAMIT_ERR_CAPACITY.  slamit_ba_create(k, ...) sizes like
+ * slamit_ba_create_ex(k, k, ...) and keeps its own limit, k <= 85.
+ *
+ *   limit                      slamit_ba_create        slamit_ba_create_ex
+ *   free keyframes per window  85 (with fixed ones)    max_free_kf <= 341 (reduced system <= 2048 rows)
+ *   fixed keyframes            within max_kf           max_kf - free ones: memory only (~0.4 KB per keyframe and window)
+ *   device bytes per window    16 Npad^2 + Npad^2 + Npad Kpad doubles and the edge / point arrays; at Npad 2048: 512 MiB
+ *   (Npad = rup(6 max_free_kf + 1, 64),        of split-K partials, 32 MiB for S, and Npad x Kpad doubles of the Schur
+ *    Kpad = rup(3 max_pt, 512))                operand (75 MiB per 1,000 points of max_pt) */
+#define SLAMIT_BA_MAX_FREE_KF 341
+int slamit_ba_create_ex(int max_kf, int max_free_kf, int max_pt, int max_edge, int max_batch, int device,
+                        slamit_ba** out);
 void slamit_ba_destroy(slamit_ba* h);
 
 /* One window, host buffers, synchronous. */

@@ -139,7 +139,7 @@ EXPORTS = [
     "slamit_orb_extract", "slamit_orb_extract_batch", "slamit_orb_extract_batch_dev", "slamit_orb_level",
     "slamit_orb_debug_candidates", "slamit_orb_debug_blurred", "slamit_orb_profile", "slamit_hamming_best2", "slamit_hamming_best2_batch_dev",
     "slamit_hamming_matrix", "slamit_distinctive_batch", "slamit_guided_search", "slamit_guided_search_workspace", "slamit_guided_search_batch_dev", "slamit_bow_search", "slamit_undistort_points", "slamit_frame_finish",
-    "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_destroy", "slamit_ba_solve",
+    "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
     "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
@@ -192,6 +192,8 @@ def lib():
         L.slamit_frame_finish_batch_dev.argtypes = [i32, C.POINTER(Camera), vp, vp, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp]
         if hasattr(L, "slamit_ba_create"):
             L.slamit_ba_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
+            if hasattr(L, "slamit_ba_create_ex"):
+                L.slamit_ba_create_ex.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
             L.slamit_ba_destroy.argtypes = [vp]
             L.slamit_ba_destroy.restype = None
             L.slamit_ba_solve.argtypes = [vp, C.POINTER(BaProblem), C.POINTER(BaOpts), C.POINTER(BaResult)]
@@ -602,9 +604,16 @@ class Optimizer:
     """Optimizer::LocalBundleAdjustment on POD inputs (the KeyFrame/MapPoint gathering of
     Optimizer.cc:456-504 stays with the caller)."""
 
-    def __init__(self, max_kf=64, max_pt=4096, max_edge=262144, max_batch=1, device=0):
+    MAX_FREE_KF = 341   # SLAMIT_BA_MAX_FREE_KF
+
+    def __init__(self, max_kf=64, max_pt=4096, max_edge=262144, max_batch=1, device=0, max_free_kf=None):
+        """max_free_kf: size the reduced system for that many free keyframes apart from max_kf, which then counts free and fixed
+        ones together (slamit_ba_create_ex; up to MAX_FREE_KF).  None: slamit_ba_create, max_kf <= 85 keyframes of either kind."""
         h = C.c_void_p()
-        _check(lib().slamit_ba_create(max_kf, max_pt, max_edge, max_batch, device, C.byref(h)), "slamit_ba_create")
+        if max_free_kf is None:
+            _check(lib().slamit_ba_create(max_kf, max_pt, max_edge, max_batch, device, C.byref(h)), "slamit_ba_create")
+        else:
+            _check(lib().slamit_ba_create_ex(max_kf, max_free_kf, max_pt, max_edge, max_batch, device, C.byref(h)), "slamit_ba_create_ex")
         self._h = h
 
     def close(self):

@@ -24,10 +24,12 @@ size_t bak_ldlt_smem(int Npad);
 hipError_t bak_prepare(int Npad);
 void bak_import(hipStream_t st, BaWin* wins, const BaIo* io, int max_kf, int max_pt, int max_edge, int Npad, int nwin);
 void bak_stage_begin(hipStream_t st, BaWin* wins, int nwin, int max_edge, int stage, int max_it, int robust, bool gate);
-void bak_slot(hipStream_t st, BaWin* wins, int nwin, int max_kf, int max_pt, int max_edge, int Npad, bool first, unsigned solvers, hipEvent_t* ev);
+void bak_slot(hipStream_t st, BaWin* wins, int nwin, int max_kf, int max_pt, int max_edge, int Npad, int Npad_ldlt, const int* tl_grid, int tl_npanel,
+              bool first, unsigned solvers, hipEvent_t* ev);
 void bak_final(hipStream_t st, BaWin* wins, const BaIo* io, int nwin, int max_kf, int max_pt, int max_edge);
 
 static_assert(BA_MAX_ITS == SLAMIT_BA_MAX_ITS, "stats capacity");
+static_assert(BA_MAX_FREE_KF == SLAMIT_BA_MAX_FREE_KF && BA_NPAD_CEIL == (6 * BA_MAX_FREE_KF + 1 + BA_TILE - 1) / BA_TILE * BA_TILE, "free keyframe ceiling");
 static_assert(sizeof(BaState) % 8 == 0, "BaState is copied as 64-bit words");
 
 struct slamit_ba {
@@ -35,6 +37,7 @@ struct slamit_ba {
     hipStream_t stream;
     hipEvent_t ev[2];          // state read-backs of the LM chunks in flight
     int max_kf, max_pt, max_edge, max_batch;
+    int max_free_kf;           // free keyframes of a window (the reduced system: Npad_max); max_kf counts free and fixed ones
     int Npad_max, Kpad_max, n_part;
     size_t win_bytes;          // device bytes of one window slab: io section (inputs | outputs) then the workspace
     size_t io_cap;             // bytes of the io section
@@ -79,26 +82,21 @@ bool for_each_window(int nwin, bool spread, F&& fn) {
 
 extern "C" {
 
-int slamit_ba_create(int max_kf, int max_pt, int max_edge, int max_batch, int device, slamit_ba** out) {
-    if (!out || max_kf < 1 || max_pt < 1 || max_edge < 1 || max_batch < 1)
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_create: bad argument");
+static int ba_create(int max_kf, int max_free_kf, int max_pt, int max_edge, int max_batch, int device, slamit_ba** out, const char* who) {
     *out = nullptr;
     SLAMIT_USE_DEVICE(device);
     slamit_ba* h = new slamit_ba();
     h->device = device;
     h->sw = slamit_read_switches();
-    h->max_kf = max_kf; h->max_pt = max_pt; h->max_edge = max_edge; h->max_batch = max_batch;
-    h->Npad_max = (int)ba_rup((size_t)6 * max_kf + 1, BA_TILE);
+    h->max_kf = max_kf; h->max_free_kf = max_free_kf; h->max_pt = max_pt; h->max_edge = max_edge; h->max_batch = max_batch;
+    h->Npad_max = (int)ba_rup((size_t)6 * max_free_kf + 1, BA_TILE);
     h->Kpad_max = (int)ba_rup((size_t)3 * max_pt, (size_t)BA_KC * BA_SPLITS);
     h->n_part = std::max((max_edge + 255) / 256, (std::max(8 * max_pt, max_kf) + 255) / 256) + 1;   // 8 = BA_PG lanes per point
-    if (bak_ldlt_smem(h->Npad_max) > 160 * 1024 - 2048 || h->Npad_max > BA_TILE * BA_MAX_TILES || h->Npad_max > 32 * BA_MAX_PANELS) {
-        delete h;
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_create: max_kf too large for the LDS-resident LDLt panel");
-    }
     {
         BaWin probe;
-        h->io_cap = carve_io(nullptr, max_kf, max_pt, max_edge, true).bytes;
-        h->win_bytes = h->io_cap + carve_work(nullptr, probe, max_kf, max_pt, max_edge, h->Npad_max, h->Kpad_max, h->n_part);
+        const size_t side_max = ba_side_needed(h->Npad_max, 6 * max_free_kf) ? ba_side_words(h->Npad_max, 6 * max_free_kf) : 0;
+        h->io_cap = carve_io(nullptr, max_kf, max_pt, max_edge, true, side_max).bytes;
+        h->win_bytes = h->io_cap + carve_work(nullptr, probe, max_kf, max_pt, max_edge, h->Npad_max, h->Kpad_max, h->n_part, max_free_kf);
     }
     hipError_t e = hipMalloc((void**)&h->d_slab, h->win_bytes * (size_t)max_batch);
     // one block: the LM states in REVERSE order right in front of the window table (state b = (BaState*)d_wins - (b + 1)): a kernel
@@ -108,13 +106,33 @@ int slamit_ba_create(int max_kf, int max_pt, int max_edge, int max_batch, int de
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_io, sizeof(BaIo) * max_batch);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&h->ev[i], hipEventDisableTiming);
-    if (e == hipSuccess) e = bak_prepare(h->Npad_max);
+    // (the LDS-resident solves only take windows of up to BA_BLOCKED_MAX_NPAD rows; larger ones take the tiled solve, which needs no attribute)
+    if (e == hipSuccess) e = bak_prepare(std::min(h->Npad_max, BA_BLOCKED_MAX_NPAD));
     if (e != hipSuccess) {
         slamit_ba_destroy(h);
-        return slamit_fail_hip(e, "slamit_ba_create");
+        return slamit_fail_hip(e, who);
     }
     *out = h;
     return SLAMIT_OK;
+}
+
+int slamit_ba_create(int max_kf, int max_pt, int max_edge, int max_batch, int device, slamit_ba** out) {
+    if (!out || max_kf < 1 || max_pt < 1 || max_edge < 1 || max_batch < 1)
+        return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_create: bad argument");
+    *out = nullptr;
+    const int Npad_max = (int)ba_rup((size_t)6 * max_kf + 1, BA_TILE);
+    if (bak_ldlt_smem(Npad_max) > 160 * 1024 - 2048 || Npad_max > BA_TILE * BA_MAX_TILES || Npad_max > 32 * BA_MAX_PANELS)
+        return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_create: max_kf too large for the LDS-resident LDLt panel");
+    return ba_create(max_kf, max_kf, max_pt, max_edge, max_batch, device, out, "slamit_ba_create");
+}
+
+int slamit_ba_create_ex(int max_kf, int max_free_kf, int max_pt, int max_edge, int max_batch, int device, slamit_ba** out) {
+    if (!out || max_kf < 1 || max_free_kf < 1 || max_free_kf > max_kf || max_pt < 1 || max_edge < 1 || max_batch < 1)
+        return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_create_ex: bad argument (1 <= max_free_kf <= max_kf, every maximum >= 1)");
+    *out = nullptr;
+    if (max_free_kf > BA_MAX_FREE_KF)
+        return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_create_ex: max_free_kf above SLAMIT_BA_MAX_FREE_KF (341: a reduced system of 2048 rows)");
+    return ba_create(max_kf, max_free_kf, max_pt, max_edge, max_batch, device, out, "slamit_ba_create_ex");
 }
 
 void slamit_ba_destroy(slamit_ba* h) {
@@ -152,7 +170,7 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
     const double t_in = tclk();
     double t_val = 0, t_prep = 0, t_queue = 0, t_loop = 0;
     // ---- validate ----
-    int mk = 1, mp = 1, me = 1, Npad = BA_TILE;
+    int mk = 1, mp = 1, me = 1, Npad = BA_TILE, Npad_ldlt = BA_TILE;
     for (int b = 0; b < nwin; ++b) {
         const slamit_ba_problem& P = probs[b];
         if (P.n_kf < 1 || P.n_pt < 0 || P.n_edge < 0 || P.n_kf > h->max_kf || P.n_pt > h->max_pt || P.n_edge > h->max_edge)
@@ -160,6 +178,10 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
         if (!P.kf_pose || !P.kf_fixed || !P.kf_intr || (P.n_pt && !P.pt_xyz) ||
             (P.n_edge && (!P.edge_kf || !P.edge_pt || !P.edge_uv || !P.edge_inv_sigma2)))
             return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_solve_batch: null input array");
+        int nfree = 0;
+        for (int k = 0; k < P.n_kf; ++k) nfree += P.kf_fixed[k] ? 0 : 1;
+        if (nfree > h->max_free_kf)
+            return slamit_fail(SLAMIT_ERR_CAPACITY, "slamit_ba_solve_batch: window has more free keyframes than the handle's max_free_kf");
         if (P.edge_ur && !P.kf_bf)
             return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_solve_batch: stereo observations (edge_ur) without the keyframes' bf (kf_bf)");
         if (!results[b].kf_pose || (P.n_pt && !results[b].pt_xyz))
@@ -169,11 +191,12 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
     // (the edges' indices are checked by the threads that prepare the windows, before anything is packed)
     t_val = tclk();
     // ---- one pinned block: [inputs of window 0 | inputs of window 1 | ...][outputs ...][2 x nwin LM states] ----
-    std::vector<size_t> in_off(nwin), out_off(nwin);
+    std::vector<size_t> in_off(nwin), out_off(nwin), side_w(nwin);
     std::vector<IoLayout> dio(nwin);   // device addresses inside the slabs
     size_t pin_need = 0;
     for (int b = 0; b < nwin; ++b) {
-        dio[b] = carve_io(h->d_slab + (size_t)b * h->win_bytes, probs[b].n_kf, probs[b].n_pt, probs[b].n_edge, probs[b].edge_ur != nullptr);
+        side_w[b] = ba_io_side_words(probs[b]);
+        dio[b] = carve_io(h->d_slab + (size_t)b * h->win_bytes, probs[b].n_kf, probs[b].n_pt, probs[b].n_edge, probs[b].edge_ur != nullptr, side_w[b]);
         in_off[b] = pin_need; pin_need += dio[b].in_bytes;
     }
     for (int b = 0; b < nwin; ++b) { out_off[b] = pin_need; pin_need += dio[b].bytes - dio[b].out_off; }
@@ -198,9 +221,10 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
         BaWin& w = wins[b];
         memset(&w, 0, sizeof(w));
         if (!ba_plan_window(P, lim, w, plans[b])) { bad_index = true; return; }
-        ba_pack_inputs(P, plans[b], carve_io(h->h_pin + in_off[b], P.n_kf, P.n_pt, P.n_edge, P.edge_ur != nullptr));   // the device's packing, in the pinned block
-        carve_work(h->d_slab + (size_t)b * h->win_bytes + h->io_cap, w, h->max_kf, h->max_pt, h->max_edge, h->Npad_max, h->Kpad_max, h->n_part);
+        ba_pack_inputs(P, plans[b], carve_io(h->h_pin + in_off[b], P.n_kf, P.n_pt, P.n_edge, P.edge_ur != nullptr, side_w[b]));   // the device's packing, in the pinned block
+        carve_work(h->d_slab + (size_t)b * h->win_bytes + h->io_cap, w, h->max_kf, h->max_pt, h->max_edge, h->Npad_max, h->Kpad_max, h->n_part, h->max_free_kf);
         const IoLayout& D = dio[b];
+        w.side = D.side;   // (null unless the window's structure outgrows BaWin's inline arrays)
         w.intr = D.intr; w.pose_col = D.pose_col; w.e_kf = D.e_kf; w.e_pt = D.e_pt; w.e_uv = D.e_uv; w.e_w = D.e_w;
         w.pt_edges = D.pt_edges; w.kf_edges = D.kf_edges; w.pt_ptr = D.pt_ptr; w.kf_ptr = D.kf_ptr;
         w.e_ur = D.e_ur; w.bf = D.bf;
@@ -219,10 +243,22 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
     if (bad_index) return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_solve_batch: edge index out of range");
     t_prep = tclk();
     unsigned solvers = 0;
+    // the tiled solve's launches per panel step: {panel workgroups, update workgroups} for the largest need among its windows
+    std::vector<int> tl_grid;
     for (int b = 0; b < nwin; ++b) {
         Npad = std::max(Npad, wins[b].Npad);
         solvers |= 1u << wins[b].solver;
         HIP_TRY(hipMemcpyAsync(h->d_slab + (size_t)b * h->win_bytes, h->h_pin + in_off[b], dio[b].in_bytes, hipMemcpyHostToDevice, st));
+        if (wins[b].solver != BA_SOLVER_TILED) { Npad_ldlt = std::max(Npad_ldlt, wins[b].Npad); continue; }
+        BaWin wh = wins[b];
+        wh.side = plans[b].side.data();
+        const int n = wh.nS, np = (n + 31) / 32;
+        if ((int)tl_grid.size() < 2 * np) tl_grid.resize(2 * np, 0);
+        for (int i = 0; i < np; ++i) {
+            const int base = std::min(32 * i + 32, n), below = std::max(ba_panel_hi(wh, i) + 1 - base, 0);
+            tl_grid[2 * i] = std::max(tl_grid[2 * i], (below + 1 + BA_TL_CHUNK - 1) / BA_TL_CHUNK);
+            tl_grid[2 * i + 1] = std::max(tl_grid[2 * i + 1], ldlt_tiled_ntiles(below));
+        }
     }
     HIP_TRY(hipMemcpyAsync(h->d_wins, wins.data(), sizeof(BaWin) * nwin, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->d_io, io.data(), sizeof(BaIo) * nwin, hipMemcpyHostToDevice, st));
@@ -263,7 +299,8 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
                 const int nslots = std::min(want, budget);
                 const bool was_first = first;
                 first = false;
-                for (int sl = 0; sl < nslots; ++sl) bak_slot(st, h->d_wins, nwin, mk, mp, me, Npad, was_first && sl == 0, solvers, slot_events());
+                for (int sl = 0; sl < nslots; ++sl)
+                    bak_slot(st, h->d_wins, nwin, mk, mp, me, Npad, Npad_ldlt, tl_grid.data(), (int)tl_grid.size() / 2, was_first && sl == 0, solvers, slot_events());
                 budget -= nslots;
                 HIP_TRY(hipMemcpyAsync(hs[cur], reinterpret_cast<BaState*>(h->d_wins) - nwin, sizeof(BaState) * nwin, hipMemcpyDeviceToHost, st));   // (reverse order: only `done` of all is read)
                 HIP_TRY(hipEventRecord(h->ev[cur], st));
@@ -300,7 +337,7 @@ static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* 
     auto unpack = [&](int b) {
         const slamit_ba_problem& P = probs[b];
         // the output section as the host sees it: same carve, shifted so that its output part starts at out_off[b]
-        const IoLayout H = carve_io(h->h_pin + out_off[b] - dio[b].out_off, P.n_kf, P.n_pt, P.n_edge, P.edge_ur != nullptr);
+        const IoLayout H = carve_io(h->h_pin + out_off[b] - dio[b].out_off, P.n_kf, P.n_pt, P.n_edge, P.edge_ur != nullptr, side_w[b]);
         ba_unpack_outputs(P, plans[b], H, results[b]);
         const BaState& S0 = *H.out_state;
         if (b == 0 && h->sw.ba_diag_waves) fprintf(stderr, "[ba diag] busy cycles of waves 0..7: %llu %llu %llu %llu %llu %llu %llu %llu\n", S0.dbg[0], S0.dbg[1], S0.dbg[2], S0.dbg[3], S0.dbg[4], S0.dbg[5], S0.dbg[6], S0.dbg[7]);

@@ -556,7 +556,7 @@ __device__ __forceinline__ void schur_body(const BaWin& W, const BaState* st, in
         // keyframe, ba_plan.cc): its slabs of BA_KC are dealt to the launch's nsplit <= BA_SPLITS splits (gridDim.y: sixteen for a single
         // window, which needs the parallelism; eight for a batch, whose windows already fill the chip -- half of the partial
         // tiles to write and to sum); a split without a slab stores zeros.
-        const int klo = max(W.tile_alo[I], W.tile_blo[J]), khi = min(W.tile_ahi[I], W.tile_bhi[J]);
+        const int klo = max(ba_tile_alo(W, I), ba_tile_blo(W, J)), khi = min(ba_tile_ahi(W, I), ba_tile_bhi(W, J));
         const int nslab = khi > klo ? (khi - klo) / BA_KC : 0;
         k0 = klo + (int)((long)nslab * s / nsplit) * BA_KC; kend = klo + (int)((long)nslab * (s + 1) / nsplit) * BA_KC;
         rbaseA = I * BA_TILE; rbaseB = J * BA_TILE; lastB = J * BA_TILE + BA_TILE - 1;
@@ -1284,7 +1284,7 @@ __global__ __launch_bounds__(LD_THREADS) void k_ldlt_blocked(BaWin* wins) {
         const int base = jb + nb;
         // rows under the panel that can hold an entry in its columns (row envelope, ba_plan.cc); LDLt without pivoting
         // never fills outside the envelope, so the rows beyond keep exact zeros there and are not touched
-        const int below = max((int)W.panel_hi[jb / LD_NB] + 1 - base, 0);
+        const int below = max(ba_panel_hi(W, jb / LD_NB) + 1 - base, 0);
         const int rows = below + 1;          // + the rhs row, which is matrix row n
 #define GROW(r) ((r) < below ? base + (r) : n)
         const int rows16 = (rows + 15) & ~15;
@@ -1462,6 +1462,183 @@ __global__ __launch_bounds__(LD_THREADS) void k_ldlt_blocked(BaWin* wins) {
                     st->dbg[4] = (ph[0] << 32) | ph[1]; st->dbg[5] = (ph[2] << 32) | ph[3]; st->dbg[6] = (ph[4] << 32) | ph[5]; }
 #endif
     if (tid == 0) st->ok2 = 1;
+}
+
+// ---- S8b: tiled LDLt of a reduced system too large for k_ldlt_blocked's LDS panel (BA_SOLVER_TILED: Npad > BA_BLOCKED_MAX_NPAD) ----
+// The same factorisation as k_ldlt_blocked -- right-looking, 32-column panels, no pivoting, in place on the lower triangle of S with the
+// right-hand side as row n, so that the forward substitution comes with it -- but every step is a launch of its own: the matrix stays in
+// HBM / L2, the rows below a panel and the trailing update are spread over workgroups, and the kernel boundaries order the steps (no
+// workgroup waits for another).  Per trial slot (bak_slot): begin, then per panel i a panel launch and an update launch, then the
+// back-substitution.  Every launch returns at once for a window of another kind, a finished one, or one whose factorisation failed.
+// Virtual row v of panel i: matrix row base + v for v < below (the rows up to the panel's envelope, panel_hi), row n (the right-hand
+// side's) for v == below; LDLt without pivoting never fills below the envelope, so the rows past it are not touched (exact).
+
+// k_ldlt_blocked's head: the iteration's bookkeeping (slots without k_iter_begin), ok2 = 1, and the right-hand side into row n
+__global__ __launch_bounds__(256) void k_ldlt_tiled_begin(BaWin* wins) {
+    const BaWin& W = wins[blockIdx.y];
+    BaState* st = BA_ST(wins, blockIdx.y);
+    if (W.solver != BA_SOLVER_TILED || st->done) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (st->need_linearize) { st->iniChi = st->currentChi; st->qmax = 0; st->need_linearize = 0; }
+        st->ok2 = 1;
+    }
+    const int n = W.nS, N = W.Npad;
+    gdouble* S = (gdouble*)W.S;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) S[(size_t)n * N + i] = W.rhs[i];
+}
+
+// Panel step: every workgroup factors the 32 x 32 diagonal block in LDS (the same loads and arithmetic in each: the same factor), then
+// solves its BA_TL_CHUNK virtual rows w = a L11^-T; workgroup 0 writes L11 / D to the panel's slot of Sb (32 x 32, unused by this
+// solver otherwise: (Npad + 1) x 64 doubles hold every panel's), every workgroup its rows' L21 = w / d into S.
+// A pivot that is exactly zero (or not finite) fails the solve like SimplicialLDLT's NumericalIssue: ok2 = 0, nothing written.
+__global__ __launch_bounds__(LD_THREADS) void k_ldlt_tiled_panel(BaWin* wins, int panel) {
+    const BaWin& W = wins[blockIdx.y];
+    BaState* st = BA_ST(wins, blockIdx.y);
+    if (W.solver != BA_SOLVER_TILED || st->done || !st->ok2) return;
+    const int n = W.nS, N = W.Npad, jb = LD_NB * panel;
+    if (jb >= n) return;
+    const int nb = min(LD_NB, n - jb), base = jb + nb;
+    const int below = max(ba_panel_hi(W, panel) + 1 - base, 0), rows = below + 1;
+    const int v0 = blockIdx.x * BA_TL_CHUNK;
+    if (v0 >= rows) return;
+    const int cr = min(BA_TL_CHUNK, rows - v0);
+    __shared__ __attribute__((aligned(16))) double Dg[LD_NB * LD_P];
+    __shared__ __attribute__((aligned(16))) double Wd[BA_TL_CHUNK * LD_P];
+    __shared__ int s_fail;
+    __shared__ double s_invd[LD_NB], s_corr[LD_NB], s_dval[LD_NB];
+    const int tid = threadIdx.x;
+    if (tid == 0) s_fail = 0;
+    const gdouble* Sr = (const gdouble*)W.S;
+    for (int i = tid; i < LD_NB * LD_NB; i += LD_THREADS) {
+        const int r = i >> 5, c = i & 31;
+        Dg[r * LD_P + c] = (r < nb && c < nb) ? Sr[(size_t)(jb + r) * N + jb + c] : 0.0;
+    }
+    for (int i = tid; i < cr * LD_NB; i += LD_THREADS) {
+        const int r = i >> 5, c = i & 31, v = v0 + r;
+        Wd[r * LD_P + c] = c < nb ? Sr[(size_t)(v < below ? base + v : n) * N + jb + c] : 0.0;
+    }
+    __syncthreads();
+    ldlt_factor_diag(Dg, s_invd, s_corr, s_dval, nb, tid, &s_fail);
+    __syncthreads();
+    if (s_fail) {
+        if (blockIdx.x == 0 && tid == 0) st->ok2 = 0;
+        return;
+    }
+    ldlt_rows(Wd, Dg, cr, tid);
+    __syncthreads();
+    gdouble* S = (gdouble*)W.S;
+    if (blockIdx.x == 0) {   // (not into S: the other workgroups of this launch may still be reading the block there)
+        gdouble* Dst = (gdouble*)W.Sb + (size_t)panel * (LD_NB * LD_NB);
+        for (int i = tid; i < LD_NB * LD_NB; i += LD_THREADS) Dst[i] = Dg[(i >> 5) * LD_P + (i & 31)];
+    }
+    for (int i = tid; i < cr * LD_NB; i += LD_THREADS) {
+        const int r = i >> 5, c = i & 31, v = v0 + r;
+        if (c < nb) S[(size_t)(v < below ? base + v : n) * N + jb + c] = Wd[r * LD_P + c] * s_invd[c];
+    }
+}
+
+// Update step: A22 -= L21 D L21^T on one lower 64 x 64 tile (rt, ct) of the virtual rows x the columns base .. panel_hi, as
+// k_ldlt_blocked's rank-32 update: v_mfma_f64_16x16x4_f64, wave w owns rows 16 w .. 16 w + 15 and four 16-column tiles; the
+// panel's L21 rows (A operand, negated) and L21 D rows (B operand) are staged in LDS (pitch LDS_PITCH: conflict-free operand reads).
+__global__ __launch_bounds__(256) void k_ldlt_tiled_update(BaWin* wins, int panel) {
+    const BaWin& W = wins[blockIdx.y];
+    BaState* st = BA_ST(wins, blockIdx.y);
+    if (W.solver != BA_SOLVER_TILED || st->done || !st->ok2) return;
+    const int n = W.nS, N = W.Npad, jb = LD_NB * panel;
+    if (jb >= n) return;
+    const int nb = min(LD_NB, n - jb), base = jb + nb;
+    const int below = max(ba_panel_hi(W, panel) + 1 - base, 0), rows = below + 1;
+    const int RT = (rows + BA_TILE - 1) / BA_TILE, CT = (below + BA_TILE - 1) / BA_TILE;
+    int t = blockIdx.x, rt = 0;
+    while (rt < RT && t >= min(rt + 1, CT)) { t -= min(rt + 1, CT); ++rt; }
+    if (rt >= RT) return;
+    const int ct = t;
+    __shared__ __attribute__((aligned(16))) double As[BA_TILE * LDS_PITCH];
+    __shared__ __attribute__((aligned(16))) double Bs[BA_TILE * LDS_PITCH];
+    __shared__ double s_d[LD_NB];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    gdouble* S = (gdouble*)W.S;
+    if (tid < LD_NB) s_d[tid] = tid < nb ? ((const gdouble*)W.Sb)[(size_t)panel * (LD_NB * LD_NB) + tid * (LD_NB + 1)] : 0.0;   // D (k_ldlt_tiled_panel)
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < (BA_TILE * LD_NB) / 256; ++u) {
+        const int i = tid + 256 * u, r = i >> 5, c = i & 31;
+        const int va = BA_TILE * rt + r, vb = BA_TILE * ct + r;
+        As[r * LDS_PITCH + c] = (va < rows && c < nb) ? -S[(size_t)(va < below ? base + va : n) * N + jb + c] : 0.0;
+        Bs[r * LDS_PITCH + c] = (vb < below && c < nb) ? S[(size_t)(base + vb) * N + jb + c] * s_d[c] : 0.0;
+    }
+    // C/D layout of v_mfma_f64_16x16x4: col = lane & 15, row = (lane >> 4) + 4 * reg
+    double4_t acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int vr = BA_TILE * rt + 16 * wv + (lane >> 4) + 4 * g, vc = BA_TILE * ct + 16 * j + (lane & 15);
+            acc[j][g] = (vr < rows && vc < below && vc <= vr) ? S[(size_t)(vr < below ? base + vr : n) * N + base + vc] : 0.0;
+        }
+    __syncthreads();
+#pragma unroll
+    for (int ks = 0; ks < LD_NB; ks += 4) {
+        const double a = As[(16 * wv + (lane & 15)) * LDS_PITCH + ks + (lane >> 4)];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double b = Bs[(16 * j + (lane & 15)) * LDS_PITCH + ks + (lane >> 4)];
+            acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int vr = BA_TILE * rt + 16 * wv + (lane >> 4) + 4 * g, vc = BA_TILE * ct + 16 * j + (lane & 15);
+            if (vr < rows && vc < below && vc <= vr) S[(size_t)(vr < below ? base + vr : n) * N + base + vc] = acc[j][g];
+        }
+}
+
+// Back-substitution x = L^-T y (y = row n of S after the last panel), one workgroup per window, blocked over the panels from the bottom as
+// in k_ldlt_blocked: wavefront 0 solves the block's unit triangle (lane k owns x_k, v_readlane broadcasts), then the unknowns i < jb take
+// y_i -= sum_m L[jb + m][i] x_m, reading rows of L (coalesced) -- only from column back_lo of the panel on: L is zero left of it.
+__global__ __launch_bounds__(LD_THREADS) void k_ldlt_tiled_back(BaWin* wins) {
+    const BaWin& W = wins[blockIdx.y];
+    BaState* st = BA_ST(wins, blockIdx.y);
+    if (W.solver != BA_SOLVER_TILED || st->done || !st->ok2) return;
+    const int n = W.nS, N = W.Npad;
+    if (n == 0) return;
+    __shared__ double xs[BA_NPAD_CEIL];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const gdouble* S = (const gdouble*)W.S;
+    for (int i = tid; i < n; i += LD_THREADS) xs[i] = S[(size_t)n * N + i];
+    __syncthreads();
+    for (int jb = ((n - 1) / LD_NB) * LD_NB; jb >= 0; jb -= LD_NB) {
+        const int nb = min(LD_NB, n - jb);
+        if (wv == 0) {
+            const int k = lane;
+            double v = (k < nb) ? xs[jb + k] : 0.0;
+            double col[LD_NB];
+            const gdouble* L11 = (const gdouble*)W.Sb + (size_t)(jb / LD_NB) * (LD_NB * LD_NB);   // the panel's factored block
+#pragma unroll
+            for (int m = 0; m < LD_NB; ++m) col[m] = (k < nb && m < nb && m > k) ? L11[m * LD_NB + k] : 0.0;
+#pragma unroll
+            for (int m = LD_NB - 1; m >= 0; --m) {
+                const double xm = readlane_d(v, m);   // final once every higher index has been applied
+                if (m < nb && k < m) v -= col[m] * xm;
+            }
+            if (k < nb) xs[jb + k] = v;
+        }
+        __syncthreads();
+        const int lo = ba_back_lo(W, jb / LD_NB);
+        for (int i = lo + tid; i < jb; i += LD_THREADS) {
+            double lv[LD_NB];
+#pragma unroll
+            for (int m = 0; m < LD_NB; ++m) lv[m] = m < nb ? S[(size_t)(jb + m) * N + i] : 0.0;
+            double acc = xs[i];
+#pragma unroll
+            for (int m = 0; m < LD_NB; ++m) acc -= lv[m] * xs[jb + min(m, nb - 1)];
+            xs[i] = acc;
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < n; i += LD_THREADS) W.rhs[i] = xs[i];
 }
 
 // ---- S9: landmark back-substitution, push(), oplus ------------------------------------------------
@@ -1642,10 +1819,11 @@ __global__ __launch_bounds__(256) void k_zero_operands(BaWin* wins) {
     const int t = blockIdx.y;
     if (t >= W.Npad / BA_TILE) return;
     const size_t K = (size_t)W.Kpad;
-    const bool ha = W.tile_ahi[t] > W.tile_alo[t], hb = W.tile_bhi[t] > W.tile_blo[t];
+    const int alo = ba_tile_alo(W, t), ahi = ba_tile_ahi(W, t), blo = ba_tile_blo(W, t), bhi = ba_tile_bhi(W, t);
+    const bool ha = ahi > alo, hb = bhi > blo;
     if (!ha && !hb) return;
-    const int lo = ha && hb ? min(W.tile_alo[t], W.tile_blo[t]) : ha ? W.tile_alo[t] : W.tile_blo[t];
-    const int hi = ha && hb ? max(W.tile_ahi[t], W.tile_bhi[t]) : ha ? W.tile_ahi[t] : W.tile_bhi[t];
+    const int lo = ha && hb ? min(alo, blo) : ha ? alo : blo;
+    const int hi = ha && hb ? max(ahi, bhi) : ha ? ahi : bhi;
     gdouble* M = (gdouble*)W.GA + (size_t)(BA_TILE * t) * K;
     const int wdt = (hi - lo) >> 1;   // double2 per row (ranges are multiples of BA_KC)
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < (long)BA_TILE * wdt; i += (long)gridDim.x * 256) {
@@ -1765,7 +1943,10 @@ void bak_stage_begin(hipStream_t st, BaWin* wins, int nwin, int max_edge, int st
 // instead of 11)
 // `ev` (profiling solves only, slamit_ba_profile): six events recorded at the phase boundaries of the slot -- before the
 // linearisation, after it, after the Schur complement, after the reduced solve, after the update, after residuals + decision
-void bak_slot(hipStream_t st, BaWin* wins, int nwin, int max_kf, int max_pt, int max_edge, int Npad, bool first, unsigned solvers, hipEvent_t* ev) {
+// `Npad`: the batch's largest system (grids of the Schur product and its reduction); `Npad_ldlt`: the largest among the windows of the
+// LDS-resident solves (their dynamic LDS, <= BA_BLOCKED_MAX_NPAD); `tl_grid`: per panel step of the tiled solve {panel, update} workgroups
+void bak_slot(hipStream_t st, BaWin* wins, int nwin, int max_kf, int max_pt, int max_edge, int Npad, int Npad_ldlt, const int* tl_grid, int tl_npanel,
+              bool first, unsigned solvers, hipEvent_t* ev) {
     const int nsplit = bak_nsplit(nwin);
     const dim3 ge((max_edge + 255) / 256, nwin), gp((max_pt * BA_PG + 255) / 256, nwin);
     if (ev) (void)hipEventRecord(ev[0], st);
@@ -1789,12 +1970,21 @@ void bak_slot(hipStream_t st, BaWin* wins, int nwin, int max_kf, int max_pt, int
     } else
     if (first) hipLaunchKernelGGL(k_schur, dim3(ntiles, nsplit, nwin), dim3(256), 0, st, wins);
     else hipLaunchKernelGGL(k_schur_pose, dim3(ntiles + (max_kf + nsplit - 1) / nsplit, nsplit, nwin), dim3(256), 0, st, wins, ntiles);
-    // (a batch without a window of the blocked solver only needs the banded mapping's workgroups: four rows each)
-    hipLaunchKernelGGL(k_schur_reduce, dim3((solvers & (1u << BA_SOLVER_BLOCKED)) ? (Npad * Npad + 255) / 256 : (Npad + 3) / 4, nwin), dim3(256), 0, st, wins, nsplit);
+    // (a batch without a window of the blocked or the tiled solver only needs the banded mapping's workgroups: four rows each)
+    const bool full = (solvers & ((1u << BA_SOLVER_BLOCKED) | (1u << BA_SOLVER_TILED))) != 0;
+    hipLaunchKernelGGL(k_schur_reduce, dim3(full ? (Npad * Npad + 255) / 256 : (Npad + 3) / 4, nwin), dim3(256), 0, st, wins, nsplit);
     if (ev) (void)hipEventRecord(ev[2], st);
     // `solvers`: bit BA_SOLVER_* set when a window of the batch takes that kernel
-    if (solvers & (1u << BA_SOLVER_BAND)) hipLaunchKernelGGL(k_ldlt_band, dim3(1, nwin), dim3(LD_THREADS), bak_ldlt_smem(Npad), st, wins);
-    if (solvers & (1u << BA_SOLVER_BLOCKED)) hipLaunchKernelGGL(k_ldlt_blocked, dim3(1, nwin), dim3(LD_THREADS), bak_ldlt_smem(Npad), st, wins);
+    if (solvers & (1u << BA_SOLVER_BAND)) hipLaunchKernelGGL(k_ldlt_band, dim3(1, nwin), dim3(LD_THREADS), bak_ldlt_smem(Npad_ldlt), st, wins);
+    if (solvers & (1u << BA_SOLVER_BLOCKED)) hipLaunchKernelGGL(k_ldlt_blocked, dim3(1, nwin), dim3(LD_THREADS), bak_ldlt_smem(Npad_ldlt), st, wins);
+    if (solvers & (1u << BA_SOLVER_TILED)) {
+        hipLaunchKernelGGL(k_ldlt_tiled_begin, dim3(8, nwin), dim3(256), 0, st, wins);
+        for (int i = 0; i < tl_npanel; ++i) {
+            if (tl_grid[2 * i] > 0) hipLaunchKernelGGL(k_ldlt_tiled_panel, dim3(tl_grid[2 * i], nwin), dim3(LD_THREADS), 0, st, wins, i);
+            if (tl_grid[2 * i + 1] > 0) hipLaunchKernelGGL(k_ldlt_tiled_update, dim3(tl_grid[2 * i + 1], nwin), dim3(256), 0, st, wins, i);
+        }
+        hipLaunchKernelGGL(k_ldlt_tiled_back, dim3(1, nwin), dim3(LD_THREADS), 0, st, wins);
+    }
     if (ev) (void)hipEventRecord(ev[3], st);
     const int nb = (max_pt * BA_PG > max_kf ? max_pt * BA_PG : max_kf);
     hipLaunchKernelGGL(k_backsub_update, dim3((nb + 255) / 256, nwin), dim3(256), 0, st, wins);

@@ -10,10 +10,10 @@
 
 #include <algorithm>
 
-IoLayout carve_io(uint8_t* base, int n_kf, int n_pt, int n_edge, bool stereo) {
+IoLayout carve_io(uint8_t* base, int n_kf, int n_pt, int n_edge, bool stereo, size_t side_words) {
     Carver c{base, 0};
     IoLayout L;
-    L.e_ur = nullptr; L.bf = nullptr;
+    L.e_ur = nullptr; L.bf = nullptr; L.side = nullptr;
     L.in_pose = c.take<double>(12 * (size_t)n_kf); L.intr = c.take<double>(4 * (size_t)n_kf); L.pose_col = c.take<int32_t>(n_kf);
     L.in_pt = c.take<double>(3 * (size_t)std::max(n_pt, 1));
     L.e_kf = c.take<int32_t>(std::max(n_edge, 1)); L.e_pt = c.take<int32_t>(std::max(n_edge, 1));
@@ -21,6 +21,7 @@ IoLayout carve_io(uint8_t* base, int n_kf, int n_pt, int n_edge, bool stereo) {
     L.pt_edges = c.take<int32_t>(std::max(n_edge, 1)); L.kf_edges = c.take<int32_t>(std::max(n_edge, 1));
     L.pt_ptr = c.take<int32_t>((size_t)n_pt + 1); L.kf_ptr = c.take<int32_t>((size_t)n_kf + 1);
     if (stereo) { L.e_ur = c.take<double>(std::max(n_edge, 1)); L.bf = c.take<double>(n_kf); }
+    if (side_words) L.side = c.take<int32_t>(side_words);
     L.in_bytes = ba_rup(c.off, 256);
     c.off = L.in_bytes;
     L.out_off = c.off;
@@ -31,7 +32,15 @@ IoLayout carve_io(uint8_t* base, int n_kf, int n_pt, int n_edge, bool stereo) {
     return L;
 }
 
-size_t carve_work(uint8_t* base, BaWin& w, int max_kf, int max_pt, int max_edge, int Npad, int Kpad, int n_part) {
+size_t ba_io_side_words(const slamit_ba_problem& P) {
+    int nfree = 0;
+    for (int k = 0; k < P.n_kf; ++k) nfree += P.kf_fixed[k] ? 0 : 1;
+    const int nS = 6 * nfree, Npad = (int)ba_rup((size_t)nS + 1, BA_TILE);
+    return ba_side_needed(Npad, nS) ? ba_side_words(Npad, nS) : 0;
+}
+
+size_t carve_work(uint8_t* base, BaWin& w, int max_kf, int max_pt, int max_edge, int Npad, int Kpad, int n_part, int max_free_kf) {
+    if (max_free_kf < 0) max_free_kf = max_kf;
     Carver c{base, 0};
     w.pose = c.take<double>(7 * (size_t)max_kf); w.pose_bak = c.take<double>(7 * (size_t)max_kf);
     w.pt = c.take<double>(3 * (size_t)max_pt); w.pt_bak = c.take<double>(3 * (size_t)max_pt);
@@ -39,7 +48,7 @@ size_t carve_work(uint8_t* base, BaWin& w, int max_kf, int max_pt, int max_edge,
     w.e_chi2 = c.take<double>(max_edge); w.e_jac = c.take<double>(BA_JAC_STEREO * (size_t)max_edge);
     w.Hll = c.take<double>(6 * (size_t)max_pt); w.bl = c.take<double>(3 * (size_t)max_pt);
     w.Dinv = c.take<double>(6 * (size_t)max_pt);
-    w.Hpp = c.take<double>(36 * (size_t)max_kf); w.bp = c.take<double>(6 * (size_t)max_kf + 8);
+    w.Hpp = c.take<double>(36 * (size_t)max_free_kf); w.bp = c.take<double>(6 * (size_t)max_free_kf + 8);
     w.GA = c.take<double>((size_t)Npad * Kpad);
     w.part = c.take<double>((size_t)BA_SPLITS * Npad * Npad);
     w.S = c.take<double>((size_t)Npad * Npad); w.Sb = c.take<double>(((size_t)Npad + 1) * 64); w.rhs = c.take<double>(Npad);
@@ -170,9 +179,25 @@ ColumnReach column_reach(const slamit_ba_problem& P, const BaWindowPlan& plan, c
     return R;
 }
 
+// The structural arrays of a window as the planner fills them: every entry, in BaWin::side's layout (ba_side_words), copied into BaWin's inline
+// arrays once planned (side_to_inline)
+struct SideView {
+    int32_t *alo, *ahi, *blo, *bhi, *panel_hi, *back_lo;
+    SideView(std::vector<int32_t>& s, int T, int P)
+        : alo(s.data()), ahi(alo + T), blo(ahi + T), bhi(blo + T), panel_hi(bhi + T), back_lo(panel_hi + P) {}
+};
+
+void side_to_inline(const SideView& S, int T, int P, BaWin& w) {
+    for (int t = 0; t < std::min(T, BA_MAX_TILES); ++t) { w.tile_alo[t] = S.alo[t]; w.tile_ahi[t] = S.ahi[t]; w.tile_blo[t] = S.blo[t]; w.tile_bhi[t] = S.bhi[t]; }
+    for (int i = 0; i < BA_MAX_PANELS; ++i) {   // (panels past the window's own: the defaults ldlt_envelope gives them)
+        w.panel_hi[i] = (int16_t)(i < P ? S.panel_hi[i] : std::max(w.nS - 1, 0));
+        w.back_lo[i] = (int16_t)(i < P ? S.back_lo[i] : 0);
+    }
+}
+
 // k range (multiples of BA_KC) of each 64-row tile of GA: the points its pose rows observe; the tile holding row nS (the right-hand side's) spans
 // every point as the B operand
-void tile_k_ranges(const ColumnReach& R, int nfree, BaWin& w) {
+void tile_k_ranges(const ColumnReach& R, int nfree, const BaWin& w, const SideView& S) {
     const int T = w.Npad / BA_TILE, kmax = w.Kpad;
     for (int t = 0; t < T; ++t) {
         int lo = INT32_MAX, hi = -1;
@@ -182,16 +207,16 @@ void tile_k_ranges(const ColumnReach& R, int nfree, BaWin& w) {
         }
         if (hi < 0) { lo = 0; hi = 0; }
         lo = lo / BA_KC * BA_KC; hi = std::min((hi + BA_KC - 1) / BA_KC * BA_KC, kmax);
-        w.tile_alo[t] = lo; w.tile_ahi[t] = hi; w.tile_blo[t] = lo; w.tile_bhi[t] = hi;
-        if (w.nS >= BA_TILE * t && w.nS < BA_TILE * (t + 1)) { w.tile_blo[t] = 0; w.tile_bhi[t] = kmax; }
+        S.alo[t] = lo; S.ahi[t] = hi; S.blo[t] = lo; S.bhi[t] = hi;
+        if (w.nS >= BA_TILE * t && w.nS < BA_TILE * (t + 1)) { S.blo[t] = 0; S.bhi[t] = kmax; }
     }
 }
 
 // LDLt: row envelope.  first[r] = 6 * fcol[r / 6]; panel i (columns 32 i ..) only touches rows r with first[r] < 32 i + 32.  A window whose
 // keyframes only share points with their neighbours has a narrow band: LDLt inside LDS
-void ldlt_envelope(const ColumnReach& R, int nfree, bool no_band, BaWin& w) {
+void ldlt_envelope(const ColumnReach& R, int nfree, bool no_band, BaWin& w, const SideView& S) {
     const int n = w.nS;
-    for (int i = 0; i < BA_MAX_PANELS; ++i) { w.panel_hi[i] = (int16_t)std::max(n - 1, 0); w.back_lo[i] = 0; }
+    for (int i = 0; i < ba_npanel(n); ++i) { S.panel_hi[i] = std::max(n - 1, 0); S.back_lo[i] = 0; }
     for (int i = 0; 32 * i < n; ++i) {
         const int jb = 32 * i, pend = std::min(jb + 32, n);
         int hi = pend - 1, lo = jb;
@@ -199,8 +224,8 @@ void ldlt_envelope(const ColumnReach& R, int nfree, bool no_band, BaWin& w) {
             if (6 * R.fcol[c] < pend) hi = std::max(hi, 6 * c + 5);                               // row block c reaches into the panel's columns
             if (6 * c + 5 >= jb && 6 * c < pend) lo = std::min(lo, 6 * R.fcol[c]);               // rows of the panel: leftmost column
         }
-        w.panel_hi[i] = (int16_t)std::min(hi, n - 1);
-        w.back_lo[i] = (int16_t)lo;
+        S.panel_hi[i] = std::min(hi, n - 1);
+        S.back_lo[i] = lo;
     }
     int band = 0;
     for (int c = 0; c < nfree; ++c) band = std::max(band, 6 * c + 5 - 6 * R.fcol[c]);
@@ -212,7 +237,7 @@ void ldlt_envelope(const ColumnReach& R, int nfree, bool no_band, BaWin& w) {
 // run of BA_SF_ROWS form a group.  Leaves sf_groups at 0 (the tiled product) when they do not, or when the groups outnumber what the
 // launch and the partial buffer hold.  Widens the tiles' k ranges to what the groups read: k_zero_operands clears those once per solve.
 void float_groups(const slamit_ba_problem& P, const BaPlanLimits& L, const BaWindowPlan& plan, const std::vector<int32_t>& minc,
-                  const std::vector<int32_t>& maxc, BaWin& w) {
+                  const std::vector<int32_t>& maxc, BaWin& w, const SideView& S) {
     const int T = w.Npad / BA_TILE, nslab_all = w.Kpad / BA_KC;
     std::vector<int32_t> slo(nslab_all, INT32_MAX), shi(nslab_all, -1);
     for (int pn = 0; pn < P.n_pt; ++pn) {
@@ -260,8 +285,8 @@ void float_groups(const slamit_ba_problem& P, const BaPlanLimits& L, const BaWin
     for (int g = 0; g < G; ++g) {
         const int t0 = w.sf_row[g] / BA_TILE, t1 = std::min(w.sf_row[g] + BA_SF_ROWS - 1, w.Npad - 1) / BA_TILE;
         for (int t = t0; t <= t1; ++t) {
-            widen(w.tile_alo[t], w.tile_ahi[t], w.sf_k0[g] * BA_KC, w.sf_k1[g] * BA_KC);
-            widen(w.tile_blo[t], w.tile_bhi[t], w.sf_k0[g] * BA_KC, w.sf_k1[g] * BA_KC);
+            widen(S.alo[t], S.ahi[t], w.sf_k0[g] * BA_KC, w.sf_k1[g] * BA_KC);
+            widen(S.blo[t], S.bhi[t], w.sf_k0[g] * BA_KC, w.sf_k1[g] * BA_KC);
         }
     }
 }
@@ -278,7 +303,7 @@ double executed_mflop(const BaWin& w) {
     for (int I = 0; I < T; ++I)
         for (int J = I; J < T; ++J)
             if (schur_tile_needed(w, I, J))
-                mflop += 2.0 * BA_TILE * BA_TILE * (std::min(w.tile_ahi[I], w.tile_bhi[J]) - std::max(w.tile_alo[I], w.tile_blo[J])) * 1e-6;
+                mflop += 2.0 * BA_TILE * BA_TILE * (std::min(ba_tile_ahi(w, I), ba_tile_bhi(w, J)) - std::max(ba_tile_alo(w, I), ba_tile_blo(w, J))) * 1e-6;
     return mflop;
 }
 
@@ -303,11 +328,18 @@ bool ba_plan_window(const slamit_ba_problem& P, const BaPlanLimits& L, BaWin& w,
         point_columns(P, plan.col, minc, maxc, nullptr);   // renumbered: the points' column ranges once more
     point_order(minc, maxc, plan);
     const ColumnReach R = column_reach(P, plan, minc, nfree);
-    tile_k_ranges(R, nfree, w);
-    ldlt_envelope(R, nfree, L.no_band, w);
+    const int T = w.Npad / BA_TILE, NP = ba_npanel(w.nS);
+    plan.side.assign(ba_side_words(w.Npad, w.nS), 0);
+    const SideView S(plan.side, T, NP);
+    tile_k_ranges(R, nfree, w, S);
+    ldlt_envelope(R, nfree, L.no_band, w, S);
     w.sf_groups = 0;
-    if (!L.no_sf && nfree > 0) float_groups(P, L, plan, minc, maxc, w);
+    // (floating windows: only a system BaWin::sf_glo / sf_ghi cover; a larger one takes the tile pairs)
+    if (!L.no_sf && nfree > 0 && w.Npad <= BA_TILE * BA_MAX_TILES) float_groups(P, L, plan, minc, maxc, w, S);
+    side_to_inline(S, T, NP, w);
+    w.side = plan.side.data();   // (the accessors read the host table while planning)
     plan.exec_mflop = executed_mflop(w);
+    w.side = nullptr;
     return true;
 }
 
@@ -331,6 +363,7 @@ void ba_pack_inputs(const slamit_ba_problem& P, const BaWindowPlan& plan, const 
     for (int k = 0; k < P.n_kf; ++k) kptr[k + 1] += kptr[k];
     std::vector<int32_t> pc(pptr, pptr + P.n_pt), kc(kptr, kptr + P.n_kf);
     for (int e = 0; e < P.n_edge; ++e) { H.pt_edges[pc[H.e_pt[e]]++] = e; H.kf_edges[kc[P.edge_kf[e]]++] = e; }
+    if (H.side) memcpy(H.side, plan.side.data(), sizeof(int32_t) * plan.side.size());
 }
 
 void ba_unpack_outputs(const slamit_ba_problem& P, const BaWindowPlan& plan, const IoLayout& H, slamit_ba_result& R) {

@@ -24,6 +24,11 @@
 #define BA_SF_ROWS 63       // matrix rows one window holds (row 64 of its B operand is the right-hand side's row)
 #define BA_SOLVER_BAND 0      // narrow row envelope: block LDLt inside LDS (k_ldlt_band)
 #define BA_SOLVER_BLOCKED 1   // any other structure: 32-column panels through L2 (k_ldlt_blocked)
+#define BA_SOLVER_TILED 2     // a reduced system too large for k_ldlt_blocked's LDS panel: one launch per panel step (k_ldlt_tiled_*)
+#define BA_BLOCKED_MAX_NPAD 512   // largest Npad whose rows below a panel k_ldlt_blocked keeps in LDS (bak_ldlt_smem within 160 KiB)
+#define BA_MAX_FREE_KF 341        // == SLAMIT_BA_MAX_FREE_KF: free keyframes of a handle (slamit_ba_create_ex); Npad 2048
+#define BA_NPAD_CEIL 2048         // rup(6 * BA_MAX_FREE_KF + 1, BA_TILE)
+#define BA_TL_CHUNK 128           // rows below a panel per workgroup of k_ldlt_tiled_panel
 #define BA_BAND_MAX 59        // widest half bandwidth k_ldlt_band takes: the reachable rows k + 4 .. k + 3 + bw stay within five block rows of the pivot's
 #define LD_BAND_LDS (150 * 1024)     // dynamic LDS k_ldlt_band may use (bak_ldlt_smem requests at least this much when it fits)
 
@@ -37,7 +42,12 @@ BA_HD inline size_t ldlt_band_bytes(int n, int bw) {
 BA_HD inline bool ldlt_band_ok(int n, int bw) { return n > 0 && bw >= 8 && bw <= BA_BAND_MAX && ldlt_band_bytes(n, bw) <= LD_BAND_LDS; }
 
 // the reduced solve a window takes: its structure decides (`no_band`: SLAMIT_BA_NO_BAND, every window takes the blocked kernel)
-inline int bak_solver_kind(int n, int band, bool no_band) { return !no_band && ldlt_band_ok(n, band) ? BA_SOLVER_BAND : BA_SOLVER_BLOCKED; }
+// A system of more than BA_BLOCKED_MAX_NPAD padded rows takes the tiled solve whatever its band: the LDS-resident kernels launch with
+// bak_ldlt_smem of their windows' Npad, which only fits a CU up to that size (ldlt_band_ok alone admits narrow bands of ~900 rows).
+inline int bak_solver_kind(int n, int band, bool no_band) {
+    if ((n + 1 + BA_TILE - 1) / BA_TILE * BA_TILE > BA_BLOCKED_MAX_NPAD) return BA_SOLVER_TILED;
+    return !no_band && ldlt_band_ok(n, band) ? BA_SOLVER_BAND : BA_SOLVER_BLOCKED;
+}
 
 // split-K of the tiled Schur product (gridDim.y of its launch): a batch brings its own parallelism (64 windows: 2 / 4 / 8 / 16 splits -> 47.8k /
 // 49.7k / 52.8k / 50.0k LM it/s)
@@ -138,12 +148,17 @@ struct BaWin {
     BA_G double* part;      // BA_SPLITS x Npad x Npad partial products
     BA_G double* S;         // Npad x Npad reduced system (symmetric, full)
     BA_G double* Sb;        // (Npad + 1) x 64: the same system as the banded solve's LDS image (rows of ldlt_band_rs(band) doubles; k_schur_reduce
-                            // writes the in-band entries, the zeros around them are laid once per solve by k_import)
+                            // writes the in-band entries, the zeros around them are laid once per solve by k_import); a window of the tiled solve
+                            // keeps its factored 32 x 32 diagonal blocks there instead, panel i at i x 1024 (k_ldlt_tiled_panel)
     BA_G double* rhs;       // Npad : b_schur in, x_pose out
     BA_G double* x_l;       // n_pt x 3 landmark increments
     BA_G double* chi_part;  // n_part partial robust-cost sums
     BA_G double* scale_part;// n_part partial sums of x(lambda x + b) over landmarks
     BA_G BaState* st;
+    // Structure of a window beyond the inline arrays above (more than BA_MAX_TILES row tiles or BA_MAX_PANELS panels; null otherwise): a side
+    // table in the window's io section, int32 [tile_alo T | tile_ahi T | tile_blo T | tile_bhi T | panel_hi P | back_lo P] with T = Npad / BA_TILE,
+    // P = ba_npanel(nS) -- every entry, the inline ones included.  Read through the accessors below.
+    BA_G const int32_t* side;
 };
 
 // Where one window's inputs and outputs sit in its slab (device addresses): the host fills / reads them with ONE copy each.
@@ -158,12 +173,36 @@ struct BaIo {
     BaState* out_state;
 };
 
+// the side table (BaWin::side): its length in int32, and whether a window needs one
+BA_HD inline int ba_npanel(int nS) { return nS > 0 ? (nS + 31) / 32 : 1; }
+BA_HD inline size_t ba_side_words(int Npad, int nS) { return 4 * (size_t)(Npad / BA_TILE) + 2 * (size_t)ba_npanel(nS); }
+BA_HD inline bool ba_side_needed(int Npad, int nS) { return Npad / BA_TILE > BA_MAX_TILES || ba_npanel(nS) > BA_MAX_PANELS; }
+
+// One accessor per structural array: the inline entry where there is one, else the side table's.  Kernels and host use these.
+BA_HD inline int ba_tile_alo(const BaWin& W, int t) { return t < BA_MAX_TILES ? W.tile_alo[t] : W.side[t]; }
+BA_HD inline int ba_tile_ahi(const BaWin& W, int t) { return t < BA_MAX_TILES ? W.tile_ahi[t] : W.side[W.Npad / BA_TILE + t]; }
+BA_HD inline int ba_tile_blo(const BaWin& W, int t) { return t < BA_MAX_TILES ? W.tile_blo[t] : W.side[2 * (W.Npad / BA_TILE) + t]; }
+BA_HD inline int ba_tile_bhi(const BaWin& W, int t) { return t < BA_MAX_TILES ? W.tile_bhi[t] : W.side[3 * (W.Npad / BA_TILE) + t]; }
+BA_HD inline int ba_panel_hi(const BaWin& W, int i) { return i < BA_MAX_PANELS ? W.panel_hi[i] : W.side[4 * (W.Npad / BA_TILE) + i]; }
+BA_HD inline int ba_back_lo(const BaWin& W, int i) {
+    return i < BA_MAX_PANELS ? W.back_lo[i] : W.side[4 * (W.Npad / BA_TILE) + ba_npanel(W.nS) + i];
+}
+
+// k_ldlt_tiled_update's workgroups for panel rows `below` (+ the right-hand side's row): the lower 64 x 64 tiles (rt, ct), ct <= min(rt, CT - 1)
+BA_HD inline int ldlt_tiled_ntiles(int below) {
+    const int RT = (below + 1 + BA_TILE - 1) / BA_TILE, CT = (below + BA_TILE - 1) / BA_TILE;
+    int nt = 0;
+    for (int rt = 0; rt < RT; ++rt) nt += rt + 1 < CT ? rt + 1 : CT;
+    return nt;
+}
+
 // does the reduced system need tile pair (I, J), I <= J, of the product?  Not when the two row tiles share no k range (the block
 // is zero: k_schur_reduce writes the zeros itself), and not when the banded solver takes the window and the whole tile lies
 // outside the band (nobody reads it) -- except for the tile column that holds the right-hand side (row nS of the operand)
 BA_HD inline bool schur_tile_needed(const BaWin& W, int I, int J) {
-    const int klo = W.tile_alo[I] > W.tile_blo[J] ? W.tile_alo[I] : W.tile_blo[J];
-    const int khi = W.tile_ahi[I] < W.tile_bhi[J] ? W.tile_ahi[I] : W.tile_bhi[J];
+    const int alo = ba_tile_alo(W, I), blo = ba_tile_blo(W, J), ahi = ba_tile_ahi(W, I), bhi = ba_tile_bhi(W, J);
+    const int klo = alo > blo ? alo : blo;
+    const int khi = ahi < bhi ? ahi : bhi;
     if (klo >= khi) return false;
     if (W.solver == BA_SOLVER_BAND && BA_TILE * J - (BA_TILE * I + BA_TILE - 1) > W.band && W.nS / BA_TILE != J) return false;
     return true;

@@ -88,25 +88,32 @@ private:
     static int& lastStatus() { static thread_local int s = 0; return s; }   // per calling thread: Tracking, LocalMapping and LoopClosing run concurrently
     static int& deviceRef() { static int d = 0; return d; }
     static slamit_ba*& handleRef() { static slamit_ba* h = 0; return h; }
-    static int* capRef() { static int c[3] = {0, 0, 0}; return c; }
+    static int* capRef() { static int c[4] = {0, 0, 0, 0}; return c; }   // max_kf, max_pt, max_edge, max_free_kf of the handle
     static std::mutex& solveMutex() { static std::mutex m; return m; }
 };
 
 inline int Optimizer::SolvePOD(const slamit_ba_problem& prob, const slamit_ba_opts& opts, slamit_ba_result& res) {
     std::lock_guard<std::mutex> guard(solveMutex());  // one LocalMapping thread in the reference; be safe anyway
     int* cap = capRef();
-    if (!handleRef() || prob.n_kf > cap[0] || prob.n_pt > cap[1] || prob.n_edge > cap[2]) {
+    int nfree = 0;
+    for (int k = 0; k < prob.n_kf; ++k) nfree += prob.kf_fixed[k] ? 0 : 1;
+    if (!handleRef() || prob.n_kf > cap[0] || prob.n_pt > cap[1] || prob.n_edge > cap[2] || nfree > cap[3]) {
         slamit_ba_destroy(handleRef());
         handleRef() = 0;
+        // keyframe tables by 2 n_kf, the reduced system by 2 n_free up to its ceiling (SLAMIT_BA_MAX_FREE_KF): a global BA over the whole
+        // map or a local window with a long tail of fixed observers fits.  (The plan depends on the handle's reduced-system size only for
+        // handles below 42 free keyframes, BaPlanLimits::Npad_max < 256: never here.)
         cap[0] = prob.n_kf > 64 ? 2 * prob.n_kf : 64;
         cap[1] = prob.n_pt > 4096 ? 2 * prob.n_pt : 4096;
         cap[2] = prob.n_edge > 65536 ? 2 * prob.n_edge : 65536;
-        int rc = slamit_ba_create(cap[0], cap[1], cap[2], 1, deviceRef(), &handleRef());
-        if (rc != SLAMIT_OK) {   // no room to grow (max_kf <= 85, slamit.h): a handle of exactly this window
+        cap[3] = std::min(nfree > 64 ? 2 * nfree : 64, SLAMIT_BA_MAX_FREE_KF);
+        int rc = slamit_ba_create_ex(cap[0], cap[3], cap[1], cap[2], 1, deviceRef(), &handleRef());
+        if (rc != SLAMIT_OK) {   // no room to grow (out of device memory, or past the free keyframe ceiling): a handle of exactly this window
             cap[0] = std::max<int>(prob.n_kf, 1); cap[1] = std::max<int>(prob.n_pt, 1); cap[2] = std::max<int>(prob.n_edge, 1);
-            rc = slamit_ba_create(cap[0], cap[1], cap[2], 1, deviceRef(), &handleRef());
+            cap[3] = std::max<int>(nfree, 1);
+            rc = slamit_ba_create_ex(cap[0], cap[3], cap[1], cap[2], 1, deviceRef(), &handleRef());
         }
-        if (rc != SLAMIT_OK) { handleRef() = 0; cap[0] = cap[1] = cap[2] = 0; return lastStatus() = rc; }   // slamit_last_error() says why
+        if (rc != SLAMIT_OK) { handleRef() = 0; cap[0] = cap[1] = cap[2] = cap[3] = 0; return lastStatus() = rc; }   // slamit_last_error() says why
     }
     return lastStatus() = slamit_ba_solve(handleRef(), &prob, &opts, &res);
 }

@@ -409,3 +409,92 @@ def synth_sim3(n=200, outlier_frac=0.15, seed=0, perturb=0.03, fix_scale=False, 
     return dict(n=n, p1=p1, p2=p2, obs1=obs1.astype(f32).astype(np.float64), obs2=obs2.astype(f32).astype(np.float64),
                 inv_sigma2_1=isig1, inv_sigma2_2=isig2, intr1=intr1, intr2=intr2, r12=R0.reshape(9), t12=t0, s12=s0,
                 th2=10.0, fix_scale=int(fix_scale), true=dict(R=R, t=t, s=s_true, bad=bad))
+
+
+def synth_map(n_kf, n_pt, obs_per_pt, n_fixed, seed, stereo_frac=0.0, loop=True, outlier_frac=0.03, baseline=0.08):
+    """A map-sized BA window (slamit_ba_problem layout, as synth_ba): n_kf cameras on a circle of radius 2 in the x-z plane, each looking
+    outward, and n_pt points on a cylinder of radius 6 around it.  loop=True: the trajectory closes (keyframe k at 2 pi k / n_kf), so the
+    last keyframes observe the first keyframes' points again and the reduced system's row envelope is not a band; loop=False: an arc of
+    1.6 pi.  Every point is observed by up to obs_per_pt keyframes nearest to it in angle (at least two); every observation has positive
+    depth and lands inside a 640 x 480 image.  The first n_fixed keyframes are fixed (0 .. n_fixed - 1).  Deterministic from `seed`."""
+    rs = np.random.RandomState(seed)
+    rs2 = np.random.RandomState(seed + 777)
+    fx, fy, cx, cy = INTRINSICS
+    span = 2.0 * np.pi if loop else 1.6 * np.pi
+    th = span * np.arange(n_kf) / n_kf
+    Rs, ts = [], []
+    for a in th:
+        z = np.array([np.cos(a), 0.0, np.sin(a)])
+        y = np.array([0.0, 1.0, 0.0])
+        R = np.stack([np.cross(y, z), y, z])
+        c = 2.0 * z
+        Rs.append(R)
+        ts.append(-R @ c)
+    inv_sig = _inv_sigma2_table()
+    quota = np.array([217, 181, 151, 126, 105, 87, 73, 60], dtype=np.float64)
+    quota /= quota.sum()
+    bf = float(np.float32(baseline * fx))
+    pts, e_kf, e_pt, e_uv, e_is, e_ur = [], [], [], [], [], []
+    margin = 8.0
+    while len(pts) < n_pt:
+        phi = rs.uniform(0.0, span)
+        X = np.array([6.0 * np.cos(phi), rs.uniform(-1.2, 1.2), 6.0 * np.sin(phi)])
+        near = np.argsort(np.abs((th - phi + np.pi) % (2.0 * np.pi) - np.pi) if loop else np.abs(th - phi), kind="stable")[:obs_per_pt]
+        obs = []
+        for k in sorted(int(k) for k in near):
+            Xc = Rs[k] @ X + ts[k]
+            if not Xc[2] > 0.5:
+                continue
+            u, v = fx * Xc[0] / Xc[2] + cx, fy * Xc[1] / Xc[2] + cy
+            if margin <= u <= 640 - margin and margin <= v <= 480 - margin:
+                obs.append((k, Xc))
+        if len(obs) < 2:
+            continue
+        p = len(pts)
+        pts.append(X)
+        for k, Xc in obs:
+            u = fx * Xc[0] / Xc[2] + cx + rs.normal(0.0, 1.0)
+            v = fy * Xc[1] / Xc[2] + cy + rs.normal(0.0, 1.0)
+            if rs.uniform() < outlier_frac:
+                u += rs.choice([-30.0, 30.0])
+                v += rs.choice([-30.0, 30.0])
+            u = min(max(u, 0.0), 639.0)
+            v = min(max(v, 0.0), 479.0)
+            e_kf.append(k)
+            e_pt.append(p)
+            e_uv.append((u, v))
+            e_is.append(inv_sig[rs.choice(8, p=quota)])
+            if stereo_frac > 0:
+                ur = u - bf / Xc[2] + rs2.normal(0.0, 1.0)
+                e_ur.append(ur if rs2.uniform() < stereo_frac else -1.0)
+    pts = np.array(pts)
+    poses = np.zeros((n_kf, 12))
+    for k in range(n_kf):
+        if k < n_fixed:
+            R, t = Rs[k], ts[k]
+        else:
+            dR, dt = se3_exp(rs.normal(0.0, 0.003, 6))
+            R, t = dR @ Rs[k], dR @ ts[k] + dt
+        poses[k, :9] = R.reshape(-1)
+        poses[k, 9:] = t
+    poses = poses.astype(np.float32).astype(np.float64)
+    pts0 = (pts + rs.normal(0.0, 0.02, pts.shape)).astype(np.float32).astype(np.float64)
+    fixed = np.zeros(n_kf, dtype=np.uint8)
+    fixed[:n_fixed] = 1
+    intr = np.tile(np.array([fx, fy, cx, cy], dtype=np.float32).astype(np.float64), (n_kf, 1))
+    extra = {}
+    if stereo_frac > 0:
+        extra = {"edge_ur": np.array(e_ur, dtype=np.float32).astype(np.float64), "kf_bf": np.full(n_kf, bf)}
+    return {
+        **extra,
+        "kf_pose": np.ascontiguousarray(poses),
+        "kf_fixed": fixed,
+        "kf_intr": np.ascontiguousarray(intr),
+        "pt_xyz": np.ascontiguousarray(pts0),
+        "edge_kf": np.array(e_kf, dtype=np.int32),
+        "edge_pt": np.array(e_pt, dtype=np.int32),
+        "edge_uv": np.array(e_uv, dtype=np.float32).astype(np.float64),
+        "edge_inv_sigma2": np.array(e_is, dtype=np.float32).astype(np.float64),
+        "truth_pose": np.array([np.concatenate([Rs[k].reshape(-1), ts[k]]) for k in range(n_kf)]),
+        "truth_pt": pts,
+    }
