@@ -161,49 +161,40 @@ extern "C" int slamit_bow_search(int device, const uint8_t* desc1, int32_t n1, c
     if (nq == 0 || ncand == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
     // one pinned staging block and one device slab per host thread, kept between calls (LocalMapping makes this call for
-    // every neighbour keyframe of every new keyframe); inputs first, outputs last
+    // every neighbour keyframe of every new keyframe)
     const bool m1 = rule->mode == 1;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_d1 = take(32 * (size_t)n1), o_d2 = take(32 * (size_t)n2), o_v1 = take((size_t)n1), o_v2 = take((size_t)n2);
-    const size_t o_qp = take(4 * (size_t)(ng + 1)), o_cp = take(4 * (size_t)(ng + 1)), o_qi = take(4 * (size_t)nq), o_ci = take(4 * (size_t)ncand);
-    const size_t o_k1 = take(m1 ? 8 * (size_t)n1 : 0), o_k2 = take(m1 ? 8 * (size_t)n2 : 0), o_oc = take(m1 ? 4 * (size_t)n2 : 0);
-    const size_t in_bytes = off;
-    const size_t o_m = take(4 * (size_t)n1), o_d = take(4 * (size_t)n1), o_nm = take(4);
-    const size_t io_bytes = off;
+    const size_t N1 = n1, N2 = n2;
+    StageLayout L;
+    const StageSpan<uint8_t> d1 = L.take<uint8_t>(32 * N1), d2 = L.take<uint8_t>(32 * N2), v1 = L.take<uint8_t>(N1), v2 = L.take<uint8_t>(N2);
+    const StageSpan<int> qp = L.take<int>((size_t)ng + 1), cp = L.take<int>((size_t)ng + 1), qi = L.take<int>(nq), ci = L.take<int>(ncand);
+    const StageSpan<float> k1 = L.take<float>(m1 ? 2 * N1 : 0), k2 = L.take<float>(m1 ? 2 * N2 : 0);
+    const StageSpan<int> oc = L.take<int>(m1 ? N2 : 0);
+    L.end_inputs();
+    const StageSpan<int> om = L.take<int>(N1), od = L.take<int>(N1), nm = L.take<int>(1);
+    L.end_outputs();
     static thread_local SlamitScratch S;
-    {
-        const hipError_t es = slamit_scratch_reserve(S, device, io_bytes);
-        if (es != hipSuccess) return slamit_fail_hip(es, "slamit_bow_search: scratch");
-    }
-    uint8_t* hb = S.host;
-    uint8_t* d = S.dev;
-    memcpy(hb + o_d1, desc1, 32 * (size_t)n1); memcpy(hb + o_d2, desc2, 32 * (size_t)n2);
-    if (valid1) memcpy(hb + o_v1, valid1, (size_t)n1);
-    if (valid2) memcpy(hb + o_v2, valid2, (size_t)n2);
-    memcpy(hb + o_qp, G->q_ptr, 4 * (size_t)(ng + 1)); memcpy(hb + o_cp, G->c_ptr, 4 * (size_t)(ng + 1));
-    memcpy(hb + o_qi, G->q_idx, 4 * (size_t)nq); memcpy(hb + o_ci, G->c_idx, 4 * (size_t)ncand);
-    if (m1) { memcpy(hb + o_k1, rule->kp1_xy, 8 * (size_t)n1); memcpy(hb + o_k2, rule->kp2_xy, 8 * (size_t)n2); memcpy(hb + o_oc, rule->kp2_octave, 4 * (size_t)n2); }
-    hipError_t e = hipMemcpyAsync(d, hb, in_bytes, hipMemcpyHostToDevice, S.st);
-    if (e == hipSuccess) {
-        BowDev D;
-        D.n_groups = ng; D.n1 = n1;
-        D.q_ptr = (const int*)(d + o_qp); D.q_idx = (const int*)(d + o_qi); D.c_ptr = (const int*)(d + o_cp); D.c_idx = (const int*)(d + o_ci);
-        D.desc1 = d + o_d1; D.desc2 = d + o_d2; D.valid1 = valid1 ? d + o_v1 : nullptr; D.valid2 = valid2 ? d + o_v2 : nullptr;
-        D.mode = rule->mode; D.th = rule->th; D.th_inclusive = rule->th_inclusive; D.nnratio = rule->nnratio;
-        memcpy(D.F, rule->F12, sizeof(D.F)); D.ex = rule->ex; D.ey = rule->ey;
-        D.kp1 = (const float*)(d + o_k1); D.kp2 = (const float*)(d + o_k2); D.oct2 = (const int*)(d + o_oc);
-        memcpy(D.scale, rule->scale_factor, sizeof(D.scale)); memcpy(D.sigma2, rule->level_sigma2, sizeof(D.sigma2));
-        D.match12 = (int*)(d + o_m); D.dist12 = (int*)(d + o_d); D.nmatches = (int*)(d + o_nm);
-        hipLaunchKernelGGL(bow_init_kernel, dim3((n1 + 255) / 256), dim3(256), 0, S.st, D);
-        hipLaunchKernelGGL(bow_search_kernel, dim3(ng), dim3(64), 0, S.st, D);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(hb + in_bytes, d + in_bytes, io_bytes - in_bytes, hipMemcpyDeviceToHost, S.st);
-    if (e == hipSuccess) e = hipStreamSynchronize(S.st);
-    if (e != hipSuccess) return slamit_fail_hip(e, "slamit_bow_search");
-    memcpy(match12, hb + o_m, 4 * (size_t)n1);
-    if (dist12) memcpy(dist12, hb + o_d, 4 * (size_t)n1);
-    memcpy(nmatches, hb + o_nm, 4);
+    HIP_TRY_AT("slamit_bow_search: scratch", slamit_stage_reserve(S, device, L));
+    memcpy(d1.at(S.host), desc1, d1.bytes()); memcpy(d2.at(S.host), desc2, d2.bytes());
+    if (valid1) memcpy(v1.at(S.host), valid1, v1.bytes());
+    if (valid2) memcpy(v2.at(S.host), valid2, v2.bytes());
+    memcpy(qp.at(S.host), G->q_ptr, qp.bytes()); memcpy(cp.at(S.host), G->c_ptr, cp.bytes());
+    memcpy(qi.at(S.host), G->q_idx, qi.bytes()); memcpy(ci.at(S.host), G->c_idx, ci.bytes());
+    if (m1) { memcpy(k1.at(S.host), rule->kp1_xy, k1.bytes()); memcpy(k2.at(S.host), rule->kp2_xy, k2.bytes()); memcpy(oc.at(S.host), rule->kp2_octave, oc.bytes()); }
+    HIP_TRY_AT("slamit_bow_search", slamit_stage_upload(S, L));
+    BowDev D;
+    D.n_groups = ng; D.n1 = n1;
+    D.q_ptr = qp.at(S.dev); D.q_idx = qi.at(S.dev); D.c_ptr = cp.at(S.dev); D.c_idx = ci.at(S.dev);
+    D.desc1 = d1.at(S.dev); D.desc2 = d2.at(S.dev); D.valid1 = valid1 ? v1.at(S.dev) : nullptr; D.valid2 = valid2 ? v2.at(S.dev) : nullptr;
+    D.mode = rule->mode; D.th = rule->th; D.th_inclusive = rule->th_inclusive; D.nnratio = rule->nnratio;
+    memcpy(D.F, rule->F12, sizeof(D.F)); D.ex = rule->ex; D.ey = rule->ey;
+    D.kp1 = k1.at(S.dev); D.kp2 = k2.at(S.dev); D.oct2 = oc.at(S.dev);
+    memcpy(D.scale, rule->scale_factor, sizeof(D.scale)); memcpy(D.sigma2, rule->level_sigma2, sizeof(D.sigma2));
+    D.match12 = om.at(S.dev); D.dist12 = od.at(S.dev); D.nmatches = nm.at(S.dev);
+    hipLaunchKernelGGL(bow_init_kernel, dim3((n1 + 255) / 256), dim3(256), 0, S.st, D);
+    hipLaunchKernelGGL(bow_search_kernel, dim3(ng), dim3(64), 0, S.st, D);
+    HIP_TRY_AT("slamit_bow_search", slamit_stage_download_and_wait(S, L));
+    memcpy(match12, om.at(S.host), om.bytes());
+    if (dist12) memcpy(dist12, od.at(S.host), od.bytes());
+    *nmatches = *nm.at(S.host);
     return SLAMIT_OK;
 }

@@ -140,24 +140,20 @@ extern "C" int slamit_undistort_points(int device, const slamit_camera* cam, con
     if (!cam || n < 0 || (n && (!xy_in || !xy_out))) return slamit_fail(SLAMIT_ERR_ARG, "slamit_undistort_points: bad argument");
     if (n == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
-    // one pinned staging block + one device slab per host thread (slamit_internal.h): [in | out], one copy each way
-    const size_t half = (8 * (size_t)n + 255) & ~(size_t)255;
+    StageLayout L;
+    const StageSpan<float> in = L.take<float>(2 * (size_t)n);
+    L.end_inputs();
+    const StageSpan<float> out = L.take<float>(2 * (size_t)n);
+    L.end_outputs();
     static thread_local SlamitScratch S;
-    hipError_t e = slamit_scratch_reserve(S, device, 2 * half);
-    if (e == hipSuccess) {
-        memcpy(S.host, xy_in, 8 * (size_t)n);
-        e = hipMemcpyAsync(S.dev, S.host, 8 * (size_t)n, hipMemcpyHostToDevice, S.st);
-    }
-    if (e == hipSuccess) {
-        CamD c = make_cam(cam);
-        c.identity = 0;   // cv::undistortPoints itself has no shortcut
-        hipLaunchKernelGGL(undistort_kernel, dim3((n + 255) / 256), dim3(256), 0, S.st, c, reinterpret_cast<const float*>(S.dev), n, reinterpret_cast<float*>(S.dev + half));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(S.host + half, S.dev + half, 8 * (size_t)n, hipMemcpyDeviceToHost, S.st);
-    if (e == hipSuccess) e = hipStreamSynchronize(S.st);
-    if (e == hipSuccess) memcpy(xy_out, S.host + half, 8 * (size_t)n);
-    if (e != hipSuccess) return slamit_fail_hip(e, "slamit_undistort_points");
+    HIP_TRY_AT("slamit_undistort_points", slamit_stage_reserve(S, device, L));
+    memcpy(in.at(S.host), xy_in, in.bytes());
+    HIP_TRY_AT("slamit_undistort_points", slamit_stage_upload(S, L));
+    CamD c = make_cam(cam);
+    c.identity = 0;   // cv::undistortPoints itself has no shortcut
+    hipLaunchKernelGGL(undistort_kernel, dim3((n + 255) / 256), dim3(256), 0, S.st, c, in.at(S.dev), n, out.at(S.dev));
+    HIP_TRY_AT("slamit_undistort_points", slamit_stage_download_and_wait(S, L));
+    memcpy(xy_out, out.at(S.host), out.bytes());
     return SLAMIT_OK;
 }
 
@@ -182,28 +178,23 @@ extern "C" int slamit_frame_finish(int device, const slamit_camera* cam, const s
     if (n > SLAMIT_FRAME_MAX_KP) return slamit_fail(SLAMIT_ERR_CAPACITY, "slamit_frame_finish: more than SLAMIT_FRAME_MAX_KP keypoints");
     SLAMIT_USE_DEVICE(device);
     const int cap = std::max(n, 1);
-    // one pinned staging block + one device slab per host thread: [keypoints in | keypoints out | cell_start | cell_items]
-    const size_t kb = (sizeof(slamit_kp) * (size_t)cap + 255) & ~(size_t)255, cs = (sizeof(int) * (FG_CELLS + 1) + 255) & ~(size_t)255;
-    const size_t o_un = kb, o_cs = 2 * kb, o_ci = o_cs + cs, bytes = o_ci + sizeof(int) * (size_t)cap;
+    StageLayout L;
+    const StageSpan<slamit_kp> in = L.take<slamit_kp>(n);
+    L.end_inputs();
+    const StageSpan<slamit_kp> un = L.take<slamit_kp>(n);
+    const StageSpan<int> cs = L.take<int>(FG_CELLS + 1), ci = L.take<int>(n);
+    L.end_outputs();
     static thread_local SlamitScratch S;
-    hipError_t e = slamit_scratch_reserve(S, device, bytes);
-    if (e == hipSuccess && n) {
-        memcpy(S.host, kps, sizeof(slamit_kp) * (size_t)n);
-        e = hipMemcpyAsync(S.dev, S.host, sizeof(slamit_kp) * (size_t)n, hipMemcpyHostToDevice, S.st);
+    HIP_TRY_AT("slamit_frame_finish", slamit_stage_reserve(S, device, L));
+    if (n) {   // (an empty frame still gets its cell_start)
+        memcpy(in.at(S.host), kps, in.bytes());
+        HIP_TRY_AT("slamit_frame_finish", slamit_stage_upload(S, L));
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(frame_finish_kernel, dim3(1), dim3(FF_THREADS), sizeof(short) * (size_t)cap, S.st, make_cam(cam),
-                           reinterpret_cast<const slamit_kp*>(S.dev), (const int*)nullptr, n, cap, min_x, min_y, inv_w, inv_h,
-                           reinterpret_cast<slamit_kp*>(S.dev + o_un), reinterpret_cast<int*>(S.dev + o_cs), reinterpret_cast<int*>(S.dev + o_ci));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(S.host + o_un, S.dev + o_un, bytes - o_un, hipMemcpyDeviceToHost, S.st);
-    if (e == hipSuccess) e = hipStreamSynchronize(S.st);
-    if (e == hipSuccess) {
-        if (n) memcpy(kps_un, S.host + o_un, sizeof(slamit_kp) * (size_t)n);
-        memcpy(cell_start, S.host + o_cs, sizeof(int) * (FG_CELLS + 1));
-        if (n) memcpy(cell_items, S.host + o_ci, sizeof(int) * (size_t)std::min(n, cell_start[FG_CELLS]));
-    }
-    if (e != hipSuccess) return slamit_fail_hip(e, "slamit_frame_finish");
+    hipLaunchKernelGGL(frame_finish_kernel, dim3(1), dim3(FF_THREADS), sizeof(short) * (size_t)cap, S.st, make_cam(cam), in.at(S.dev),
+                       (const int*)nullptr, n, cap, min_x, min_y, inv_w, inv_h, un.at(S.dev), cs.at(S.dev), ci.at(S.dev));
+    HIP_TRY_AT("slamit_frame_finish", slamit_stage_download_and_wait(S, L));
+    if (n) memcpy(kps_un, un.at(S.host), un.bytes());
+    memcpy(cell_start, cs.at(S.host), cs.bytes());
+    if (n) memcpy(cell_items, ci.at(S.host), sizeof(int) * (size_t)std::min(n, cell_start[FG_CELLS]));
     return SLAMIT_OK;
 }

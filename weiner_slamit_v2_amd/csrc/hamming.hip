@@ -357,30 +357,23 @@ int slamit_distinctive_batch(const uint8_t* desc, const int32_t* offsets, int np
     }
     const int total = offsets[npoints];
     if (total && !desc) return slamit_fail(SLAMIT_ERR_ARG, "slamit_distinctive_batch: null descriptors");
-    // one pinned staging block + one device slab per host thread (slamit_internal.h): [descriptors | offsets | out], one copy each way
-    const size_t o_off = ((size_t)total * 32 + 255) & ~(size_t)255, o_out = o_off + ((sizeof(int) * ((size_t)npoints + 1) + 255) & ~(size_t)255);
-    const size_t bytes = o_out + sizeof(int) * 2 * (size_t)npoints;
     const int cur_dev = slamit_default_device();   // slamit_set_device() of this thread, else the current device
     SLAMIT_USE_DEVICE(cur_dev);
+    StageLayout L;
+    const StageSpan<uint8_t> d = L.take<uint8_t>(32 * (size_t)total);
+    const StageSpan<int> off = L.take<int>((size_t)npoints + 1);
+    L.end_inputs();
+    const StageSpan<int> idx = L.take<int>(npoints), med = L.take<int>(npoints, alignof(int));
+    L.end_outputs();
     static thread_local SlamitScratch S;
-    hipError_t e = slamit_scratch_reserve(S, cur_dev, bytes);
-    if (e == hipSuccess) {
-        if (total) memcpy(S.host, desc, (size_t)total * 32);
-        memcpy(S.host + o_off, offsets, sizeof(int) * ((size_t)npoints + 1));
-        e = hipMemcpyAsync(S.dev, S.host, o_out, hipMemcpyHostToDevice, S.st);
-    }
-    if (e == hipSuccess) {
-        int* dout = reinterpret_cast<int*>(S.dev + o_out);
-        hipLaunchKernelGGL(distinctive_kernel, dim3(npoints), dim3(64), 0, S.st, S.dev, reinterpret_cast<const int*>(S.dev + o_off), dout, dout + npoints);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(S.host + o_out, S.dev + o_out, bytes - o_out, hipMemcpyDeviceToHost, S.st);
-    if (e == hipSuccess) e = hipStreamSynchronize(S.st);
-    if (e == hipSuccess) {
-        memcpy(best_idx, S.host + o_out, sizeof(int) * npoints);
-        memcpy(best_median, S.host + o_out + sizeof(int) * npoints, sizeof(int) * npoints);
-    }
-    if (e != hipSuccess) return slamit_fail_hip(e, "slamit_distinctive_batch");
+    HIP_TRY_AT("slamit_distinctive_batch", slamit_stage_reserve(S, cur_dev, L));
+    if (total) memcpy(d.at(S.host), desc, d.bytes());
+    memcpy(off.at(S.host), offsets, off.bytes());
+    HIP_TRY_AT("slamit_distinctive_batch", slamit_stage_upload(S, L));
+    hipLaunchKernelGGL(distinctive_kernel, dim3(npoints), dim3(64), 0, S.st, d.at(S.dev), off.at(S.dev), idx.at(S.dev), med.at(S.dev));
+    HIP_TRY_AT("slamit_distinctive_batch", slamit_stage_download_and_wait(S, L));
+    memcpy(best_idx, idx.at(S.host), idx.bytes());
+    memcpy(best_median, med.at(S.host), med.bytes());
     return SLAMIT_OK;
 }
 
@@ -413,35 +406,26 @@ int slamit_hamming_best2(const uint8_t* q, int nq, const uint8_t* t, int nt, int
         return slamit_fail(SLAMIT_ERR_ARG, "slamit_hamming_best2: bad argument");
     if (nq == 0) return SLAMIT_OK;
     if (nt > SLAMIT_HAMMING_MAX_TRAIN) return slamit_fail(SLAMIT_ERR_CAPACITY, "slamit_hamming_best2: more than SLAMIT_HAMMING_MAX_TRAIN train descriptors");
-    // one pinned staging block + one device slab per host thread: [query | train | out], one copy each way
-    const size_t o_t = ((size_t)nq * 32 + 255) & ~(size_t)255, o_out = o_t + ((std::max<size_t>((size_t)nt * 32, 32) + 255) & ~(size_t)255);
-    const size_t bytes = o_out + sizeof(int) * 3 * (size_t)nq;
     const int cur_dev = slamit_default_device();   // slamit_set_device() of this thread, else the current device
     SLAMIT_USE_DEVICE(cur_dev);
+    StageLayout L;
+    const StageSpan<uint8_t> dq = L.take<uint8_t>(32 * (size_t)nq), dt = L.take<uint8_t>(32 * (size_t)std::max(nt, 1));
+    L.end_inputs();
+    const StageSpan<int> idx = L.take<int>(nq), b1 = L.take<int>(nq, alignof(int)), b2 = L.take<int>(nq, alignof(int));   // contiguous
+    L.end_outputs();
     static thread_local SlamitScratch S;
-    hipError_t e = slamit_scratch_reserve(S, cur_dev, bytes);
-    if (e == hipSuccess) {
-        memcpy(S.host, q, (size_t)nq * 32);
-        if (nt) memcpy(S.host + o_t, t, (size_t)nt * 32);
-        e = hipMemcpyAsync(S.dev, S.host, o_out, hipMemcpyHostToDevice, S.st);
-    }
-    if (e == hipSuccess) {
-        int* dout = reinterpret_cast<int*>(S.dev + o_out);
-        if (hm_use_mfma(nt))
-            hipLaunchKernelGGL(hamming_best2_mfma_kernel, dim3((nq + 32 * HMM_NT - 1) / (32 * HMM_NT), 1), dim3(64 * HMM_WAVES), 0, S.st, S.dev, (const int*)nullptr, nq,
-                               (size_t)0, S.dev + o_t, (const int*)nullptr, nt, (size_t)0, dout, dout + nq, dout + 2 * (size_t)nq, (size_t)0);
-        else
-            hipLaunchKernelGGL(hamming_best2_kernel, dim3((nq + HM_QPB - 1) / HM_QPB, 1), dim3(256), 0, S.st, S.dev, (const int*)nullptr, nq,
-                               (size_t)0, S.dev + o_t, (const int*)nullptr, nt, (size_t)0, dout, dout + nq, dout + 2 * (size_t)nq, (size_t)0);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(S.host + o_out, S.dev + o_out, bytes - o_out, hipMemcpyDeviceToHost, S.st);
-    if (e == hipSuccess) e = hipStreamSynchronize(S.st);
-    if (e == hipSuccess) {
-        const int* o = reinterpret_cast<const int*>(S.host + o_out);
-        memcpy(best_idx, o, sizeof(int) * nq); memcpy(best, o + nq, sizeof(int) * nq); memcpy(second, o + 2 * (size_t)nq, sizeof(int) * nq);
-    }
-    if (e != hipSuccess) return slamit_fail_hip(e, "slamit_hamming_best2");
+    HIP_TRY_AT("slamit_hamming_best2", slamit_stage_reserve(S, cur_dev, L));
+    memcpy(dq.at(S.host), q, dq.bytes());
+    if (nt) memcpy(dt.at(S.host), t, 32 * (size_t)nt);
+    HIP_TRY_AT("slamit_hamming_best2", slamit_stage_upload(S, L));
+    if (hm_use_mfma(nt))
+        hipLaunchKernelGGL(hamming_best2_mfma_kernel, dim3((nq + 32 * HMM_NT - 1) / (32 * HMM_NT), 1), dim3(64 * HMM_WAVES), 0, S.st, dq.at(S.dev), (const int*)nullptr, nq,
+                           (size_t)0, dt.at(S.dev), (const int*)nullptr, nt, (size_t)0, idx.at(S.dev), b1.at(S.dev), b2.at(S.dev), (size_t)0);
+    else
+        hipLaunchKernelGGL(hamming_best2_kernel, dim3((nq + HM_QPB - 1) / HM_QPB, 1), dim3(256), 0, S.st, dq.at(S.dev), (const int*)nullptr, nq,
+                           (size_t)0, dt.at(S.dev), (const int*)nullptr, nt, (size_t)0, idx.at(S.dev), b1.at(S.dev), b2.at(S.dev), (size_t)0);
+    HIP_TRY_AT("slamit_hamming_best2", slamit_stage_download_and_wait(S, L));
+    memcpy(best_idx, idx.at(S.host), idx.bytes()); memcpy(best, b1.at(S.host), b1.bytes()); memcpy(second, b2.at(S.host), b2.bytes());
     return SLAMIT_OK;
 }
 
@@ -450,25 +434,19 @@ int slamit_hamming_matrix(const uint8_t* q, int nq, const uint8_t* t, int nt, ui
     if (nq == 0 || nt == 0) return SLAMIT_OK;
     const int cur_dev = slamit_default_device();
     SLAMIT_USE_DEVICE(cur_dev);
-    // one pinned staging block + one device slab per host thread: [query | train | matrix], one copy each way
-    const size_t o_t = ((size_t)nq * 32 + 255) & ~(size_t)255, o_out = o_t + (((size_t)nt * 32 + 255) & ~(size_t)255);
-    const size_t bytes = o_out + sizeof(uint16_t) * (size_t)nq * nt;
+    StageLayout L;
+    const StageSpan<uint8_t> dq = L.take<uint8_t>(32 * (size_t)nq), dt = L.take<uint8_t>(32 * (size_t)nt);
+    L.end_inputs();
+    const StageSpan<uint16_t> d = L.take<uint16_t>((size_t)nq * nt);
+    L.end_outputs();
     static thread_local SlamitScratch S;
-    hipError_t e = slamit_scratch_reserve(S, cur_dev, bytes);
-    if (e == hipSuccess) {
-        memcpy(S.host, q, (size_t)nq * 32);
-        memcpy(S.host + o_t, t, (size_t)nt * 32);
-        e = hipMemcpyAsync(S.dev, S.host, o_out, hipMemcpyHostToDevice, S.st);
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(hamming_matrix_kernel, dim3((nt + 63) / 64, (nq + 63) / 64), dim3(256), 0, S.st, S.dev, nq, S.dev + o_t, nt,
-                           reinterpret_cast<uint16_t*>(S.dev + o_out));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(S.host + o_out, S.dev + o_out, bytes - o_out, hipMemcpyDeviceToHost, S.st);
-    if (e == hipSuccess) e = hipStreamSynchronize(S.st);
-    if (e == hipSuccess) memcpy(out, S.host + o_out, bytes - o_out);
-    if (e != hipSuccess) return slamit_fail_hip(e, "slamit_hamming_matrix");
+    HIP_TRY_AT("slamit_hamming_matrix", slamit_stage_reserve(S, cur_dev, L));
+    memcpy(dq.at(S.host), q, dq.bytes());
+    memcpy(dt.at(S.host), t, dt.bytes());
+    HIP_TRY_AT("slamit_hamming_matrix", slamit_stage_upload(S, L));
+    hipLaunchKernelGGL(hamming_matrix_kernel, dim3((nt + 63) / 64, (nq + 63) / 64), dim3(256), 0, S.st, dq.at(S.dev), nq, dt.at(S.dev), nt, d.at(S.dev));
+    HIP_TRY_AT("slamit_hamming_matrix", slamit_stage_download_and_wait(S, L));
+    memcpy(out, d.at(S.host), d.bytes());
     return SLAMIT_OK;
 }
 

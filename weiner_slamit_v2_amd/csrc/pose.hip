@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/slamit.h"
+#include "lm_layout.h"
 #include "se3_device.h"
 #include "slamit_internal.h"
 
@@ -330,67 +331,53 @@ __global__ __launch_bounds__(256) void pose_opt_kernel(const PoseFrame* frames) 
 extern "C" {
 
 int slamit_pose_optimize_batch(int device, int nframes, const slamit_pose_problem* probs, slamit_pose_result* results) {
+    const char* const where = "slamit_pose_optimize_batch";
     if (nframes < 0 || (nframes && (!probs || !results))) return slamit_fail(SLAMIT_ERR_ARG, "slamit_pose_optimize_batch: bad argument");
     if (nframes == 0) return SLAMIT_OK;
-    SLAMIT_USE_DEVICE(device);
-    // one slab per host thread (slamit_internal.h): [doubles of every frame | ints | PoseFrame records | flags], one copy each way
-    size_t total = 0, flag_total = 0;
-    int nmax = 1;
-    std::vector<size_t> off(nframes), foff(nframes);
     for (int f = 0; f < nframes; ++f) {
         const slamit_pose_problem& P = probs[f];
         if (P.n < 0 || !P.pose || !P.intr || (P.n && (!P.xw || !P.uv || !P.inv_sigma2)) || !results[f].pose || (P.n && !results[f].outlier))
             return slamit_fail(SLAMIT_ERR_ARG, "slamit_pose_optimize_batch: null array");
-        off[f] = total; foff[f] = flag_total;
-        // per frame: pose 12 | intr 4 | xw 3n | uv 2n | w n | chi2 n | pose_out 12 | chi2_round 4 [| ur n]   (doubles)
-        total += 32 + (size_t)(P.ur ? 8 : 7) * P.n;
-        flag_total += ((size_t)P.n + 15) & ~(size_t)7;
-        nmax = std::max(nmax, (int)P.n);
     }
-    const size_t o_ints = sizeof(double) * total, o_frames = (o_ints + sizeof(int32_t) * 5 * nframes + 15) & ~(size_t)15;
-    const size_t o_flags = o_frames + sizeof(PoseFrame) * nframes, bytes = o_flags + flag_total;
+    SLAMIT_USE_DEVICE(device);
+    // [doubles of every frame (lm_layout.h) | ints | PoseFrame records | flags].  A frame's doubles mix what the kernel reads and
+    // writes, so everything but the flags goes up and the whole block comes down.
+    StageLayout L;
+    std::vector<PoseSpans> dbl(nframes);
+    std::vector<StageSpan<uint8_t>> flags(nframes);
+    int nmax = 1;
+    for (int f = 0; f < nframes; ++f) { dbl[f] = pose_take(L, probs[f].n, probs[f].ur != nullptr); nmax = std::max(nmax, (int)probs[f].n); }
+    const StageSpan<int32_t> ints = L.take<int32_t>(5 * (size_t)nframes, 4);   // per frame: n_inliers, n_its[4]
+    const StageSpan<PoseFrame> frames = L.take<PoseFrame>(nframes, 16);
+    L.end_inputs(1); L.out_off = 0;   // (the whole block comes down)
+    for (int f = 0; f < nframes; ++f) flags[f] = lm_take_flags(L, probs[f].n);
+    L.end_outputs();
     static thread_local SlamitScratch S;
-    hipError_t e = slamit_scratch_reserve(S, device, bytes);
-    if (e != hipSuccess) return slamit_fail_hip(e, "slamit_pose_optimize_batch");
-    double* stage = reinterpret_cast<double*>(S.host);
-    double* d_buf = reinterpret_cast<double*>(S.dev);
-    int32_t* d_ints = reinterpret_cast<int32_t*>(S.dev + o_ints);
-    PoseFrame* fr = reinterpret_cast<PoseFrame*>(S.host + o_frames);
-    uint8_t* d_flags = S.dev + o_flags;
+    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
     for (int f = 0; f < nframes; ++f) {
         const slamit_pose_problem& P = probs[f];
-        double* h = stage + off[f];
-        double* d = d_buf + off[f];
-        const size_t n = P.n;
-        memcpy(h, P.pose, 96); memcpy(h + 12, P.intr, 32);
-        if (n) { memcpy(h + 16, P.xw, 24 * n); memcpy(h + 16 + 3 * n, P.uv, 16 * n); memcpy(h + 16 + 5 * n, P.inv_sigma2, 8 * n); }
-        PoseFrame& F = fr[f];
-        F.n = P.n; F.pose_in = d; F.intr = d + 12; F.xw = d + 16; F.uv = d + 16 + 3 * n; F.w = d + 16 + 5 * n;
-        F.chi2 = d + 16 + 6 * n; F.pose_out = d + 16 + 7 * n; F.chi2_round = d + 28 + 7 * n;
+        const PoseSpans& s = dbl[f];
+        memcpy(s.pose_in.at(S.host), P.pose, s.pose_in.bytes()); memcpy(s.intr.at(S.host), P.intr, s.intr.bytes());
+        if (P.n) { memcpy(s.xw.at(S.host), P.xw, s.xw.bytes()); memcpy(s.uv.at(S.host), P.uv, s.uv.bytes()); memcpy(s.w.at(S.host), P.inv_sigma2, s.w.bytes()); }
+        PoseFrame& F = frames.at(S.host)[f];
+        F.n = P.n; F.pose_in = s.pose_in.at(S.dev); F.intr = s.intr.at(S.dev); F.xw = s.xw.at(S.dev); F.uv = s.uv.at(S.dev); F.w = s.w.at(S.dev);
+        F.chi2 = s.chi2.at(S.dev); F.pose_out = s.pose_out.at(S.dev); F.chi2_round = s.chi2_round.at(S.dev);
         F.ur = nullptr; F.bf = 0.0;
-        if (P.ur && n) { memcpy(h + 32 + 7 * n, P.ur, 8 * n); F.ur = d + 32 + 7 * n; F.bf = P.bf; }
-        F.outlier = d_flags + foff[f];
-        F.n_inliers = d_ints + 5 * f; F.n_its = d_ints + 5 * f + 1;
+        if (P.ur && P.n) { memcpy(s.ur.at(S.host), P.ur, s.ur.bytes()); F.ur = s.ur.at(S.dev); F.bf = P.bf; }
+        F.outlier = flags[f].at(S.dev);
+        F.n_inliers = ints.at(S.dev) + 5 * f; F.n_its = ints.at(S.dev) + 5 * f + 1;
     }
-    e = hipMemcpyAsync(S.dev, S.host, o_flags, hipMemcpyHostToDevice, S.st);
-    if (e == hipSuccess) {
-        if (nmax > 48 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(pose_opt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, nmax + 16);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(pose_opt_kernel, dim3(nframes), dim3(256), (size_t)nmax + 16, S.st, reinterpret_cast<const PoseFrame*>(S.dev + o_frames));
-            e = hipGetLastError();
-        }
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(S.host, S.dev, bytes, hipMemcpyDeviceToHost, S.st);
-    if (e == hipSuccess) e = hipStreamSynchronize(S.st);
-    if (e != hipSuccess) return slamit_fail_hip(e, "slamit_pose_optimize_batch");
-    const int32_t* ints = reinterpret_cast<const int32_t*>(S.host + o_ints);
+    HIP_TRY_AT(where, slamit_stage_upload(S, L));
+    if (nmax > 48 * 1024) HIP_TRY_AT(where, hipFuncSetAttribute(reinterpret_cast<const void*>(pose_opt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, nmax + 16));
+    hipLaunchKernelGGL(pose_opt_kernel, dim3(nframes), dim3(256), (size_t)nmax + 16, S.st, frames.at(S.dev));
+    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
     for (int f = 0; f < nframes; ++f) {
-        const size_t n = probs[f].n;
-        const double* h = stage + off[f];
-        memcpy(results[f].pose, h + 16 + 7 * n, 96);
-        for (int r = 0; r < 4; ++r) { results[f].chi2[r] = h[28 + 7 * n + r]; results[f].n_its[r] = ints[5 * f + 1 + r]; }
-        results[f].n_inliers = ints[5 * f];
-        if (n) memcpy(results[f].outlier, S.host + o_flags + foff[f], n);
+        const PoseSpans& s = dbl[f];
+        const int32_t* iv = ints.at(S.host) + 5 * f;
+        memcpy(results[f].pose, s.pose_out.at(S.host), s.pose_out.bytes());
+        for (int r = 0; r < 4; ++r) { results[f].chi2[r] = s.chi2_round.at(S.host)[r]; results[f].n_its[r] = iv[1 + r]; }
+        results[f].n_inliers = iv[0];
+        if (probs[f].n) memcpy(results[f].outlier, flags[f].at(S.host), flags[f].bytes());
     }
     return SLAMIT_OK;
 }

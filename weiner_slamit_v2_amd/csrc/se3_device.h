@@ -23,7 +23,7 @@ __device__ __forceinline__ void quat_to_R(const double* q, double* R) {
 // One case of Eigen's matrix -> quaternion branch for a negative trace, largest diagonal element I.  The indices are
 // compile-time constants: run-time indices into m[] would put the caller's rotation matrix into scratch memory.
 template <int I>
-__device__ __forceinline__ void R_to_quat_case(const double* m, double* q) {
+__host__ __device__ __forceinline__ void R_to_quat_case(const double* m, double* q) {
     constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
     double t = sqrt(m[4 * I] - m[4 * J] - m[4 * K] + 1.0);
     q[I] = 0.5 * t;
@@ -32,7 +32,7 @@ __device__ __forceinline__ void R_to_quat_case(const double* m, double* q) {
     q[J] = (m[3 * J + I] + m[3 * I + J]) * t;
     q[K] = (m[3 * K + I] + m[3 * I + K]) * t;
 }
-__device__ __forceinline__ void R_to_quat(const double* m, double* q) {
+__host__ __device__ __forceinline__ void R_to_quat(const double* m, double* q) {   // (the host packs Sim3 problems with it, sim3.hip)
     double t = m[0] + m[4] + m[8];
     if (t > 0) {
         t = sqrt(t + 1.0);

@@ -369,63 +369,53 @@ extern "C" int slamit_guided_search(int device, const slamit_frame_view* F, cons
         return slamit_fail(SLAMIT_ERR_ARG, "slamit_guided_search: null array");
     if (F->n > SLAMIT_SEARCH_MAX_KP) return slamit_fail(SLAMIT_ERR_CAPACITY, "slamit_guided_search: more than SLAMIT_SEARCH_MAX_KP keypoints");
     SLAMIT_USE_DEVICE(device);
-    const int n = F->n, m = Q->m, cap = std::min(std::max(n, 1), SLAMIT_SEARCH_MAX_CAND);
+    const size_t n = F->n, m = Q->m, cap = std::min(std::max(F->n, 1), SLAMIT_SEARCH_MAX_CAND);
     // One pinned staging block and one device slab per host thread, kept between calls (a Tracking thread makes this
-    // call every frame: a fresh hipMalloc + nine pageable copies cost more than the search itself).  Layout of both:
-    // inputs (keypoint records | descriptors | taken | queries ...) first, then outputs; the candidate lists and
-    // tentative pairs live only on the device.
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_kp = take(12 * (size_t)n), o_kd = take(32 * (size_t)n), o_tk = take((size_t)n);
-    const size_t o_uvr = take(12 * (size_t)m), o_l0 = take(4 * (size_t)m), o_l1 = take(4 * (size_t)m), o_qd = take(32 * (size_t)m), o_va = take((size_t)m), o_tq = take((size_t)m);
-    const size_t in_bytes = off;
-    const size_t o_mk = take(4 * (size_t)m), o_o4 = take(16 * (size_t)m), o_nm = take(4);
-    const size_t io_bytes = off;
-    const size_t o_cand = take(8 * (size_t)m * cap), o_cn = take(4 * (size_t)m), o_te = take(16 * (size_t)m);
+    // call every frame: a fresh hipMalloc + nine pageable copies cost more than the search itself).  The candidate lists
+    // and tentative pairs live only on the device.
+    StageLayout L;
+    const StageSpan<uint8_t> kp = L.take<uint8_t>(12 * n), kd = L.take<uint8_t>(32 * n), tk = L.take<uint8_t>(n);   // kp: {x, y, octave} records
+    const StageSpan<float> uvr = L.take<float>(3 * m);
+    const StageSpan<int> l0 = L.take<int>(m), l1 = L.take<int>(m);
+    const StageSpan<uint8_t> qd = L.take<uint8_t>(32 * m), va = L.take<uint8_t>(m), tq = L.take<uint8_t>(m);
+    L.end_inputs();
+    const StageSpan<int> mk = L.take<int>(m), o4 = L.take<int>(4 * m), nm = L.take<int>(1);
+    L.end_outputs();
+    const StageSpan<unsigned long long> cand = L.take<unsigned long long>(m * cap);
+    const StageSpan<int> cn = L.take<int>(m);
+    const StageSpan<unsigned long long> te = L.take<unsigned long long>(2 * m);
     static thread_local SlamitScratch S;
-    {
-        const hipError_t es = slamit_scratch_reserve(S, device, io_bytes, off);   // pinned: inputs + outputs; device: + candidate lists
-        if (es != hipSuccess) return slamit_fail_hip(es, "slamit_guided_search: scratch");
+    HIP_TRY_AT("slamit_guided_search: scratch", slamit_stage_reserve(S, device, L));
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(kp.at(S.host) + 12 * i, &F->kp_xy[2 * i], 8);
+        memcpy(kp.at(S.host) + 12 * i + 8, &F->kp_octave[i], 4);
     }
-    uint8_t* hb = S.host;
-    uint8_t* d = S.dev;
-    for (int i = 0; i < n; ++i) {   // keypoints as {x, y, octave} records
-        memcpy(hb + o_kp + 12 * (size_t)i, &F->kp_xy[2 * i], 8);
-        memcpy(hb + o_kp + 12 * (size_t)i + 8, &F->kp_octave[i], 4);
-    }
-    memcpy(hb + o_kd, F->desc, 32 * (size_t)n); memcpy(hb + o_tk, F->kp_taken, (size_t)n);
-    memcpy(hb + o_uvr, Q->uvr, 12 * (size_t)m); memcpy(hb + o_l0, Q->level_min, 4 * (size_t)m); memcpy(hb + o_l1, Q->level_max, 4 * (size_t)m);
-    memcpy(hb + o_qd, Q->desc, 32 * (size_t)m); memcpy(hb + o_va, Q->valid, (size_t)m);
-    if (Q->takes) memcpy(hb + o_tq, Q->takes, (size_t)m); else memset(hb + o_tq, 1, (size_t)m);
-    hipError_t e = hipMemcpyAsync(d, hb, in_bytes, hipMemcpyHostToDevice, S.st);
-    if (e == hipSuccess) {
-        SearchDev D;
-        D.nframes = 1; D.kp_cap = std::max(n, 1); D.q_cap = m; D.cand_cap = cap;
-        D.n_arr = nullptr; D.n_fixed = n; D.m_arr = nullptr; D.m_fixed = m;
-        D.kp = d + o_kp; D.kp_rec = 12; D.kp_oct_off = 8; D.kp_desc = d + o_kd; D.kp_taken = d + o_tk;
-        D.min_x = F->min_x; D.min_y = F->min_y; D.inv_w = F->inv_w; D.inv_h = F->inv_h;
-        D.uvr = (const float*)(d + o_uvr); D.lmin = (const int*)(d + o_l0); D.lmax = (const int*)(d + o_l1); D.qdesc = d + o_qd; D.valid = d + o_va; D.takes = d + o_tq;
-        D.cand = (unsigned long long*)(d + o_cand); D.cand_n = (int*)(d + o_cn); D.tent = (unsigned long long*)(d + o_te);
-        D.th_dist = rule->th_dist; D.use_ratio = rule->use_ratio; D.nnratio = rule->nnratio;
-        D.chi2_gate = rule->mode == 1 ? 0.f : rule->chi2_gate; memcpy(D.inv_sigma2, rule->inv_level_sigma2, sizeof(D.inv_sigma2));
-        D.mode = rule->mode;
-        D.match_kp = (int*)(d + o_mk); D.out4 = (int*)(d + o_o4); D.nmatches = (int*)(d + o_nm);
-        search_launch(S.st, D, m);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(hb + in_bytes, d + in_bytes, io_bytes - in_bytes, hipMemcpyDeviceToHost, S.st);
-    if (e == hipSuccess) e = hipStreamSynchronize(S.st);
-    if (e != hipSuccess) return slamit_fail_hip(e, "slamit_guided_search");
-    int nm = 0;
-    memcpy(&nm, hb + o_nm, 4);
-    memcpy(match_kp, hb + o_mk, 4 * (size_t)m);
-    *nmatches = nm;
-    const int* o4 = reinterpret_cast<const int*>(hb + o_o4);
-    for (int q = 0; q < m; ++q) {
-        if (best_dist) best_dist[q] = o4[4 * (size_t)q];
-        if (best_level) best_level[q] = o4[4 * (size_t)q + 1];
-        if (second_dist) second_dist[q] = o4[4 * (size_t)q + 2];
-        if (second_level) second_level[q] = o4[4 * (size_t)q + 3];
+    memcpy(kd.at(S.host), F->desc, kd.bytes()); memcpy(tk.at(S.host), F->kp_taken, tk.bytes());
+    memcpy(uvr.at(S.host), Q->uvr, uvr.bytes()); memcpy(l0.at(S.host), Q->level_min, l0.bytes()); memcpy(l1.at(S.host), Q->level_max, l1.bytes());
+    memcpy(qd.at(S.host), Q->desc, qd.bytes()); memcpy(va.at(S.host), Q->valid, va.bytes());
+    if (Q->takes) memcpy(tq.at(S.host), Q->takes, tq.bytes()); else memset(tq.at(S.host), 1, tq.bytes());
+    HIP_TRY_AT("slamit_guided_search", slamit_stage_upload(S, L));
+    SearchDev D;
+    D.nframes = 1; D.kp_cap = std::max(F->n, 1); D.q_cap = Q->m; D.cand_cap = (int)cap;
+    D.n_arr = nullptr; D.n_fixed = F->n; D.m_arr = nullptr; D.m_fixed = Q->m;
+    D.kp = kp.at(S.dev); D.kp_rec = 12; D.kp_oct_off = 8; D.kp_desc = kd.at(S.dev); D.kp_taken = tk.at(S.dev);
+    D.min_x = F->min_x; D.min_y = F->min_y; D.inv_w = F->inv_w; D.inv_h = F->inv_h;
+    D.uvr = uvr.at(S.dev); D.lmin = l0.at(S.dev); D.lmax = l1.at(S.dev); D.qdesc = qd.at(S.dev); D.valid = va.at(S.dev); D.takes = tq.at(S.dev);
+    D.cand = cand.at(S.dev); D.cand_n = cn.at(S.dev); D.tent = te.at(S.dev);
+    D.th_dist = rule->th_dist; D.use_ratio = rule->use_ratio; D.nnratio = rule->nnratio;
+    D.chi2_gate = rule->mode == 1 ? 0.f : rule->chi2_gate; memcpy(D.inv_sigma2, rule->inv_level_sigma2, sizeof(D.inv_sigma2));
+    D.mode = rule->mode;
+    D.match_kp = mk.at(S.dev); D.out4 = o4.at(S.dev); D.nmatches = nm.at(S.dev);
+    search_launch(S.st, D, Q->m);
+    HIP_TRY_AT("slamit_guided_search", slamit_stage_download_and_wait(S, L));
+    *nmatches = *nm.at(S.host);
+    memcpy(match_kp, mk.at(S.host), mk.bytes());
+    const int* r4 = o4.at(S.host);
+    for (size_t q = 0; q < m; ++q) {
+        if (best_dist) best_dist[q] = r4[4 * q];
+        if (best_level) best_level[q] = r4[4 * q + 1];
+        if (second_dist) second_dist[q] = r4[4 * q + 2];
+        if (second_level) second_level[q] = r4[4 * q + 3];
     }
     return SLAMIT_OK;
 }

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/slamit.h"
+#include "lm_layout.h"
 #include "se3_device.h"
 #include "slamit_internal.h"
 
@@ -359,96 +360,68 @@ __global__ __launch_bounds__(256) void sim3_opt_kernel(const Sim3Prob* probs) {
 extern "C" {
 
 int slamit_sim3_optimize_batch(int device, int nprob, const slamit_sim3_problem* probs, slamit_sim3_result* results) {
+    const char* const where = "slamit_sim3_optimize_batch";
     if (nprob < 0 || (nprob && (!probs || !results))) return slamit_fail(SLAMIT_ERR_ARG, "slamit_sim3_optimize_batch: bad argument");
     if (nprob == 0) return SLAMIT_OK;
-    size_t total = 0, flag_total = 0;
-    int nmax = 1;
-    std::vector<size_t> off(nprob), foff(nprob);
     for (int f = 0; f < nprob; ++f) {
         const slamit_sim3_problem& P = probs[f];
         if (P.n < 0 || (P.n && (!P.p1 || !P.p2 || !P.obs1 || !P.obs2 || !P.inv_sigma2_1 || !P.inv_sigma2_2 || !results[f].inlier)))
             return slamit_fail(SLAMIT_ERR_ARG, "slamit_sim3_optimize_batch: null array");
         if (!(P.s12 > 0) || !(P.th2 > 0)) return slamit_fail(SLAMIT_ERR_ARG, "slamit_sim3_optimize_batch: scale and th2 must be positive");
-        off[f] = total; foff[f] = flag_total;
-        total += (size_t)14 * P.n + 16;          // p1 3n | p2 3n | o1 2n | o2 2n | w1 n | w2 n | chi12 n | chi21 n | out 16   (doubles)
-        flag_total += ((size_t)P.n + 15) & ~(size_t)7;
-        nmax = std::max(nmax, (int)P.n);
     }
     SLAMIT_USE_DEVICE(device);
-    // one slab per host thread (slamit_internal.h): [doubles of every problem | ints | Sim3Prob records | flags], one copy each way
-    const size_t o_ints = sizeof(double) * total, o_probs = (o_ints + sizeof(int32_t) * 4 * nprob + 15) & ~(size_t)15;
-    const size_t o_flags = o_probs + sizeof(Sim3Prob) * nprob, bytes = o_flags + flag_total;
+    // [doubles of every problem (lm_layout.h) | ints | Sim3Prob records | flags].  A problem's doubles mix what the kernel reads and
+    // writes, so everything but the flags goes up and the whole block comes down.
+    StageLayout L;
+    std::vector<Sim3Spans> dbl(nprob);
+    std::vector<StageSpan<uint8_t>> flags(nprob);
+    int nmax = 1;
+    for (int f = 0; f < nprob; ++f) { dbl[f] = sim3_take(L, probs[f].n); nmax = std::max(nmax, (int)probs[f].n); }
+    const StageSpan<int32_t> ints = L.take<int32_t>(4 * (size_t)nprob, 4);   // per problem: Sim3Prob::ints
+    const StageSpan<Sim3Prob> recs = L.take<Sim3Prob>(nprob, 16);
+    L.end_inputs(1); L.out_off = 0;   // (the whole block comes down)
+    for (int f = 0; f < nprob; ++f) flags[f] = lm_take_flags(L, probs[f].n);
+    L.end_outputs();
     static thread_local SlamitScratch S;
-    hipError_t e = slamit_scratch_reserve(S, device, bytes);
-    if (e != hipSuccess) return slamit_fail_hip(e, "slamit_sim3_optimize_batch");
-    double* stage = reinterpret_cast<double*>(S.host);
-    double* d_buf = reinterpret_cast<double*>(S.dev);
-    int32_t* d_ints = reinterpret_cast<int32_t*>(S.dev + o_ints);
-    Sim3Prob* pr = reinterpret_cast<Sim3Prob*>(S.host + o_probs);
-    uint8_t* d_flags = S.dev + o_flags;
+    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
     for (int f = 0; f < nprob; ++f) {
         const slamit_sim3_problem& P = probs[f];
-        double* h = stage + off[f];
-        double* d = d_buf + off[f];
-        const size_t n = P.n;
-        if (n) {
-            memcpy(h, P.p1, 24 * n); memcpy(h + 3 * n, P.p2, 24 * n); memcpy(h + 6 * n, P.obs1, 16 * n); memcpy(h + 8 * n, P.obs2, 16 * n);
-            memcpy(h + 10 * n, P.inv_sigma2_1, 8 * n); memcpy(h + 11 * n, P.inv_sigma2_2, 8 * n);
+        const Sim3Spans& s = dbl[f];
+        if (P.n) {
+            memcpy(s.p1.at(S.host), P.p1, s.p1.bytes()); memcpy(s.p2.at(S.host), P.p2, s.p2.bytes());
+            memcpy(s.o1.at(S.host), P.obs1, s.o1.bytes()); memcpy(s.o2.at(S.host), P.obs2, s.o2.bytes());
+            memcpy(s.w1.at(S.host), P.inv_sigma2_1, s.w1.bytes()); memcpy(s.w2.at(S.host), P.inv_sigma2_2, s.w2.bytes());
         }
-        Sim3Prob& Q = pr[f];
+        Sim3Prob& Q = recs.at(S.host)[f];
         memset(&Q, 0, sizeof(Q));
         Q.n = P.n; Q.fix_scale = P.fix_scale; Q.th2 = P.th2;
         memcpy(Q.intr1, P.intr1, sizeof(Q.intr1)); memcpy(Q.intr2, P.intr2, sizeof(Q.intr2));
-        {   // Sim3(R, t, s): Quaterniond(R) by Eigen's rule, not normalised (host copy of se3_device.h:R_to_quat)
-            const double* m = P.r12;
-            double* q = Q.S0;
-            double t = m[0] + m[4] + m[8];
-            if (t > 0) {
-                t = sqrt(t + 1.0); q[3] = 0.5 * t; t = 0.5 / t;
-                q[0] = (m[7] - m[5]) * t; q[1] = (m[2] - m[6]) * t; q[2] = (m[3] - m[1]) * t;
-            } else {
-                int i = 0;
-                if (m[4] > m[0]) i = 1;
-                if (m[8] > m[4 * i]) i = 2;
-                const int j = (i + 1) % 3, k = (j + 1) % 3;
-                t = sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
-                q[i] = 0.5 * t; t = 0.5 / t;
-                q[3] = (m[3 * k + j] - m[3 * j + k]) * t; q[j] = (m[3 * j + i] + m[3 * i + j]) * t; q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
-            }
-            for (int i = 0; i < 3; ++i) Q.S0[4 + i] = P.t12[i];
-            Q.S0[7] = P.s12;
-        }
+        R_to_quat(P.r12, Q.S0);   // Sim3(R, t, s): Quaterniond(R) by Eigen's rule, not normalised
+        for (int i = 0; i < 3; ++i) Q.S0[4 + i] = P.t12[i];
+        Q.S0[7] = P.s12;
         typedef SIM3_G double gd;
-        Q.p1 = (const gd*)d; Q.p2 = (const gd*)(d + 3 * n); Q.o1 = (const gd*)(d + 6 * n); Q.o2 = (const gd*)(d + 8 * n);
-        Q.w1 = (const gd*)(d + 10 * n); Q.w2 = (const gd*)(d + 11 * n); Q.chi12 = (gd*)(d + 12 * n); Q.chi21 = (gd*)(d + 13 * n);
-        Q.out = (gd*)(d + 14 * n);
-        Q.inlier = (SIM3_G uint8_t*)(d_flags + foff[f]);
-        Q.ints = (SIM3_G int32_t*)(d_ints + 4 * f);
+        Q.p1 = (const gd*)s.p1.at(S.dev); Q.p2 = (const gd*)s.p2.at(S.dev); Q.o1 = (const gd*)s.o1.at(S.dev); Q.o2 = (const gd*)s.o2.at(S.dev);
+        Q.w1 = (const gd*)s.w1.at(S.dev); Q.w2 = (const gd*)s.w2.at(S.dev); Q.chi12 = (gd*)s.chi12.at(S.dev); Q.chi21 = (gd*)s.chi21.at(S.dev);
+        Q.out = (gd*)s.out.at(S.dev);
+        Q.inlier = (SIM3_G uint8_t*)flags[f].at(S.dev);
+        Q.ints = (SIM3_G int32_t*)(ints.at(S.dev) + 4 * f);
     }
-    e = hipMemcpyAsync(S.dev, S.host, o_flags, hipMemcpyHostToDevice, S.st);
-    if (e == hipSuccess) {
-        if (nmax > 32 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void*>(sim3_opt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, nmax + 16);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(sim3_opt_kernel, dim3(nprob), dim3(256), (size_t)nmax + 16, S.st, reinterpret_cast<const Sim3Prob*>(S.dev + o_probs));
-            e = hipGetLastError();
-        }
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(S.host, S.dev, bytes, hipMemcpyDeviceToHost, S.st);
-    if (e == hipSuccess) e = hipStreamSynchronize(S.st);
-    if (e != hipSuccess) return slamit_fail_hip(e, "slamit_sim3_optimize_batch");
-    const int32_t* ints = reinterpret_cast<const int32_t*>(S.host + o_ints);
+    HIP_TRY_AT(where, slamit_stage_upload(S, L));
+    if (nmax > 32 * 1024) HIP_TRY_AT(where, hipFuncSetAttribute(reinterpret_cast<const void*>(sim3_opt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, nmax + 16));
+    hipLaunchKernelGGL(sim3_opt_kernel, dim3(nprob), dim3(256), (size_t)nmax + 16, S.st, recs.at(S.dev));
+    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
     for (int f = 0; f < nprob; ++f) {
-        const size_t n = probs[f].n;
-        const double* o = stage + off[f] + 14 * n;
+        const double* o = dbl[f].out.at(S.host);
+        const int32_t* iv = ints.at(S.host) + 4 * f;
         memcpy(results[f].r12, o, 72); memcpy(results[f].t12, o + 9, 24);
         results[f].s12 = o[12];
         results[f].chi2[0] = o[13]; results[f].chi2[1] = o[14];
-        results[f].n_inliers = ints[4 * f]; results[f].n_its[0] = ints[4 * f + 1]; results[f].n_its[1] = ints[4 * f + 2];
-        if (ints[4 * f + 3]) {   // the reference returned before touching g2oS12: hand the input back bit for bit
+        results[f].n_inliers = iv[0]; results[f].n_its[0] = iv[1]; results[f].n_its[1] = iv[2];
+        if (iv[3]) {   // the reference returned before touching g2oS12: hand the input back bit for bit
             memcpy(results[f].r12, probs[f].r12, 72); memcpy(results[f].t12, probs[f].t12, 24);
             results[f].s12 = probs[f].s12;
         }
-        if (n) memcpy(results[f].inlier, S.host + o_flags + foff[f], n);
+        if (probs[f].n) memcpy(results[f].inlier, flags[f].at(S.host), flags[f].bytes());
     }
     return SLAMIT_OK;
 }

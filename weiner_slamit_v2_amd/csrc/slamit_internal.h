@@ -3,15 +3,18 @@
 #define SLAMIT_INTERNAL_H
 #include <hip/hip_runtime.h>
 
+#include "stage_layout.h"
+
 int slamit_fail(int code, const char* msg);                 // records msg, returns code
 int slamit_fail_hip(hipError_t e, const char* where);       // records "<where>: <hip error>", returns SLAMIT_ERR_DEVICE
 
-#define HIP_TRY(expr)                                                        \
+// `where` (an entry point, or the expression itself) goes into the error text
+#define HIP_TRY_AT(where, expr)                                              \
     do {                                                                     \
         hipError_t _e = (expr);                                              \
-        if (_e != hipSuccess) return slamit_fail_hip(_e, #expr);             \
+        if (_e != hipSuccess) return slamit_fail_hip(_e, where);             \
     } while (0)
-
+#define HIP_TRY(expr) HIP_TRY_AT(#expr, expr)
 
 // Every entry point works on the device it is given and leaves the caller's current device as it found it (a torch
 // host thread must not have its device changed under it).
@@ -86,6 +89,17 @@ inline hipError_t slamit_scratch_reserve(SlamitScratch& S, int device, size_t ho
     if (e == hipSuccess) { S.host_bytes = hw; S.dev_bytes = dw; }
     return e;
 }
-inline hipError_t slamit_scratch_reserve(SlamitScratch& S, int device, size_t bytes) { return slamit_scratch_reserve(S, device, bytes, bytes); }
+
+// A staged call (the host-pointer entry points): lay the block out (StageLayout: inputs | outputs | device-only), reserve, pack the
+// inputs into S.host through their spans, upload, launch on S.st with pointers from the same spans at S.dev, download and wait,
+// unpack the outputs from S.host.  One copy each way; each step returns the first error.
+inline hipError_t slamit_stage_reserve(SlamitScratch& S, int device, const StageLayout& L) { return slamit_scratch_reserve(S, device, L.io_bytes, L.dev_bytes); }
+inline hipError_t slamit_stage_upload(SlamitScratch& S, const StageLayout& L) { return hipMemcpyAsync(S.dev, S.host, L.in_bytes, hipMemcpyHostToDevice, S.st); }
+inline hipError_t slamit_stage_download_and_wait(SlamitScratch& S, const StageLayout& L) {   // the launches' error, the copy down, the stream
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(S.host + L.out_off, S.dev + L.out_off, L.io_bytes - L.out_off, hipMemcpyDeviceToHost, S.st);
+    if (e == hipSuccess) e = hipStreamSynchronize(S.st);
+    return e;
+}
 
 #endif
