@@ -357,12 +357,15 @@ bool solve_schur(const Problem& pb, const System& S, double lambda, const std::v
 // SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg
 int optimize(Problem& pb, int iterations, int stage, slamit_ba_stats* st) {
     // index mapping: free poses in id order (every free pose keeps a column even without active
-    // edges: it then has a zero Hessian and a zero update, equivalent to g2o leaving it out)
+    // edges: it then has a zero Hessian and a zero update; g2o leaves such a vertex out of the
+    // optimisation, so its estimate is not even re-normalised: in_graph[k] = 0 skips its oplus)
     pb.pose_col.assign(pb.K, -1);
     pb.nfree = 0;
     for (int k = 0; k < pb.K; ++k) if (!pb.fixed[k]) pb.pose_col[k] = pb.nfree++;
     std::vector<std::vector<int> > pt_edges(pb.P);
     for (int e = 0; e < pb.E; ++e) if (pb.edges[e].active) pt_edges[pb.edges[e].pt].push_back(e);
+    std::vector<char> in_graph(pb.K, 0);
+    for (int e = 0; e < pb.E; ++e) if (pb.edges[e].active) in_graph[pb.edges[e].kf] = 1;
     bool any_active = false;
     for (int e = 0; e < pb.E; ++e) any_active |= pb.edges[e].active;
     if (!any_active) return 0;  // g2o: "0 vertices to optimize" -> optimize() returns without iterating
@@ -393,7 +396,7 @@ int optimize(Problem& pb, int iterations, int stage, slamit_ba_stats* st) {
             bool ok2 = solve_schur(pb, S, lambda, pt_edges, x);
             if (ok2 || !x.empty()) {  // update(_solver->x())
                 if (x.size() == (size_t)6 * S.np + 3 * pb.P) {
-                    for (int k = 0; k < pb.K; ++k) if (pb.pose_col[k] >= 0) pose_oplus(pb.poses[k], &x[6 * pb.pose_col[k]]);
+                    for (int k = 0; k < pb.K; ++k) if (pb.pose_col[k] >= 0 && in_graph[k]) pose_oplus(pb.poses[k], &x[6 * pb.pose_col[k]]);
                     for (int i = 0; i < 3 * pb.P; ++i) pb.pts[i] += x[6 * S.np + i];
                 }
             }

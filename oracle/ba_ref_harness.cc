@@ -45,7 +45,10 @@ struct LambdaRecorder : public g2o::HyperGraphAction {
 
 }  // namespace
 
-extern "C" int ba_ref_solve(const slamit_ba_problem* pb, const slamit_ba_opts* op, slamit_ba_result* res) {
+// kf_pose_stage1 / pt_xyz_stage1 (optional, 12 * n_kf / 3 * n_pt doubles): the estimates after the robust stage, before the gate
+// re-initialises the optimiser -- what a vertex the gate leaves without active edges keeps to the end.
+extern "C" int ba_ref_solve_ex(const slamit_ba_problem* pb, const slamit_ba_opts* op, slamit_ba_result* res, double* kf_pose_stage1,
+                               double* pt_xyz_stage1) {
     g2o::SparseOptimizer optimizer;
     g2o::BlockSolver_6_3::LinearSolverType* linearSolver =
         new g2o::LinearSolverEigen<g2o::BlockSolver_6_3::PoseMatrixType>();
@@ -128,6 +131,16 @@ extern "C" int ba_ref_solve(const slamit_ba_problem* pb, const slamit_ba_opts* o
         const int its = stage == 0 ? op->its_robust : op->its_final;
         if (op->stop && *op->stop) break;  // S/Optimizer.cc:655-657, 664-666
         if (stage == 1) {
+            for (int k = 0; k < K && kf_pose_stage1; ++k) {
+                Eigen::Matrix<double, 4, 4> T = static_cast<g2o::VertexSE3Expmap*>(optimizer.vertex(k))->estimate().to_homogeneous_matrix();
+                for (int r = 0; r < 3; ++r) {
+                    for (int c = 0; c < 3; ++c) kf_pose_stage1[12 * k + 3 * r + c] = T(r, c);
+                    kf_pose_stage1[12 * k + 9 + r] = T(r, 3);
+                }
+            }
+            for (int p = 0; p < P && pt_xyz_stage1; ++p)
+                for (int c = 0; c < 3; ++c)
+                    pt_xyz_stage1[3 * p + c] = static_cast<g2o::VertexSBAPointXYZ*>(optimizer.vertex(p + maxKFid + 1))->estimate()[c];
             for (int e = 0; e < E; ++e) {
                 if (sedges[e]) {   // S/Optimizer.cc:689-703
                     g2o::EdgeStereoSE3ProjectXYZ* ed = sedges[e];
@@ -188,6 +201,10 @@ extern "C" int ba_ref_solve(const slamit_ba_problem* pb, const slamit_ba_opts* o
         for (int c = 0; c < 3; ++c) res->pt_xyz[3 * p + c] = v->estimate()[c];
     }
     return 0;
+}
+
+extern "C" int ba_ref_solve(const slamit_ba_problem* pb, const slamit_ba_opts* op, slamit_ba_result* res) {
+    return ba_ref_solve_ex(pb, op, res, 0, 0);
 }
 
 

@@ -419,7 +419,7 @@ def _ba_fn(which):
     return _ba[which]
 
 
-def _ba_call(which, prob, its_robust, its_final, huber_delta, chi2_gate, stop):
+def _ba_call(which, prob, its_robust, its_final, huber_delta, chi2_gate, stop, stage1=False):
     keep = {}
     for k, dt in (("kf_pose", np.float64), ("kf_fixed", np.uint8), ("kf_intr", np.float64), ("pt_xyz", np.float64),
                   ("edge_kf", np.int32), ("edge_pt", np.int32), ("edge_uv", np.float64), ("edge_inv_sigma2", np.float64)):
@@ -438,7 +438,13 @@ def _ba_call(which, prob, its_robust, its_final, huber_delta, chi2_gate, stop):
     st = _BaStats()
     r = _BaResult(out["kf_pose"].ctypes.data, out["pt_xyz"].ctypes.data, out["edge_chi2"].ctypes.data,
                   out["edge_outlier"].ctypes.data, out["edge_stage1_outlier"].ctypes.data, C.addressof(st))
-    rc = _ba_fn(which)(C.byref(p), C.byref(o), C.byref(r))
+    if stage1:   # the reference's estimates between the stages (ba_ref_harness.cc: ba_ref_solve_ex)
+        out["kf_pose_stage1"], out["pt_xyz_stage1"] = np.zeros((nk, 12)), np.zeros((npt, 3))
+        fn = C.CDLL(os.path.join(HERE, "_ref", "libba_ref.so")).ba_ref_solve_ex
+        fn.argtypes = [C.POINTER(_BaProblem), C.POINTER(_BaOpts), C.POINTER(_BaResult), C.c_void_p, C.c_void_p]
+        rc = fn(C.byref(p), C.byref(o), C.byref(r), out["kf_pose_stage1"].ctypes.data, out["pt_xyz_stage1"].ctypes.data)
+    else:
+        rc = _ba_fn(which)(C.byref(p), C.byref(o), C.byref(r))
     assert rc == 0, "BA %s failed" % which
     n = list(st.n_its)
     out["stats"] = {"n_its": n, "chi2": [list(st.chi2[s])[:n[s]] for s in range(2)],
@@ -452,9 +458,9 @@ def ba_solve(prob, its_robust=5, its_final=10, huber_delta=HUBER_MONO, chi2_gate
     return _ba_call("oracle", prob, its_robust, its_final, huber_delta, chi2_gate, stop)
 
 
-def ba_ref_solve(prob, its_robust=5, its_final=10, huber_delta=HUBER_MONO, chi2_gate=5.991, stop=None):
-    """The reference's own g2o (authoring container only)."""
-    return _ba_call("ref", prob, its_robust, its_final, huber_delta, chi2_gate, stop)
+def ba_ref_solve(prob, its_robust=5, its_final=10, huber_delta=HUBER_MONO, chi2_gate=5.991, stop=None, stage1=False):
+    """The reference's own g2o (authoring container only).  stage1=True: also kf_pose_stage1 / pt_xyz_stage1, the estimates between the stages."""
+    return _ba_call("ref", prob, its_robust, its_final, huber_delta, chi2_gate, stop, stage1)
 
 
 # ---------------------------------------------------------------------------------------------

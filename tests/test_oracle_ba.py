@@ -142,3 +142,45 @@ def test_sim3_oracle_matches_live_reference_g2o():
         sim3_close(res, ref_case("sim3(%d,)" % seed, pr), tol=1e-6)
         if ob.ba_ref_available():
             sim3_close(res, ob.sim3_ref_solve(pr), tol=1e-6)
+
+
+def test_oracle_vs_large_hard_golden():
+    """starved100 (tests/golden/ba_large_hard_ref.json.gz): a map-sized window with a starved keyframe and mirrored observations of points
+    that other keyframes see in front -- every pose, the sampled points, both flag sets, the LM path, the state between the stages."""
+    from tests.helpers import b64_bits, b64_f64, large_hard_cases, large_hard_problem
+
+    c = large_hard_cases()["starved100"]
+    prob = large_hard_problem(c)
+    sched = c["schedule"]
+    res = ob.ba_solve(prob, *sched)
+    pose, idx = b64_f64(c["kf_pose"]).reshape(-1, 12), np.array(c["pt_index"])
+    assert np.abs(res["kf_pose"] - pose).max() <= 1e-9 * max(np.abs(pose).max(), 1.0)
+    assert np.abs(res["pt_xyz"][idx] - b64_f64(c["pt_xyz"]).reshape(-1, 3)).max() <= 1e-9 * max(np.abs(res["pt_xyz"]).max(), 1.0)
+    for key in ("edge_stage1_outlier", "edge_outlier"):
+        assert np.array_equal(res[key], b64_bits(c[key], len(prob["edge_kf"]))), key
+    s = res["stats"]
+    assert s["n_its"] == c["n_its"] and [list(t) for t in s["trials"]] == c["trials"]
+    for st in range(2):
+        assert np.allclose(s["chi2"][st], b64_f64(c["chi2"][st]), rtol=1e-7, atol=1e-12)
+        assert np.allclose(s["lambda"][st], b64_f64(c["lambda"][st]), rtol=1e-7)
+    pose1 = b64_f64(c["kf_pose_stage1"]).reshape(-1, 12)
+    one = ob.ba_solve(prob, sched[0], 0, sched[2])
+    assert np.abs(one["kf_pose"] - pose1).max() <= 1e-9 * max(np.abs(pose1).max(), 1.0)
+    kfs = [k for k, _ in c["hard"]["starve_kf"]]
+    assert np.array_equal(res["kf_pose"][kfs], one["kf_pose"][kfs])   # the starved keyframe: its stage-1 estimate, bit for bit
+
+
+@pytest.mark.parametrize("name", ["starved_kf", "starved_pts"])
+def test_oracle_keeps_starved_vertices_bit_for_bit(name):
+    """What g2o does by dropping a vertex without active edges (ref_kf_pose == ref_kf_pose_stage1 there, tests/test_hard_geometry_fixtures.py)
+    the oracle does too: the full schedule leaves them exactly where the robust stage put them."""
+    path = os.path.join(ROOT, "tests", "golden", "ba_%s.npz" % name)
+    prob, ref = load_ba_golden(path)
+    z = np.load(path)
+    full, one = ob.ba_solve(prob), ob.ba_solve(prob, its_final=0)
+    alive = ref["edge_stage1_outlier"] == 0
+    pts = np.flatnonzero(np.bincount(prob["edge_pt"][alive], minlength=len(prob["pt_xyz"])) == 0)
+    assert len(z["starved_kf"]) and np.array_equal(full["kf_pose"][z["starved_kf"]], one["kf_pose"][z["starved_kf"]])
+    assert np.array_equal(full["pt_xyz"][pts], one["pt_xyz"][pts]) and (name != "starved_pts" or len(pts) >= 6)
+    assert np.abs(one["kf_pose"] - z["ref_kf_pose_stage1"]).max() <= 1e-9 * max(np.abs(z["ref_kf_pose_stage1"]).max(), 1.0)
+    assert np.abs(one["pt_xyz"] - z["ref_pt_xyz_stage1"]).max() <= 1e-9 * max(np.abs(z["ref_pt_xyz_stage1"]).max(), 1.0)

@@ -99,10 +99,11 @@ def test_shim_orbmatcher(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["fixed3", "stereo_mixed"])
+@pytest.mark.parametrize("name", ["fixed3", "stereo_mixed", "behind"])
 def test_shim_optimizer_local_ba(tmp_path, name):
     """LocalMapping.cc:84's call against mock KeyFrame / MapPoint / Map types; "stereo_mixed": keyframes with mvuRight >= 0 on half
-    of their keypoints and an mbf (the EdgeStereoSE3ProjectXYZ edges of Optimizer.cc:621-650), against the reference-g2o golden."""
+    of their keypoints and an mbf (the EdgeStereoSE3ProjectXYZ edges of Optimizer.cc:621-650), against the reference-g2o golden;
+    "behind": mirrored triangulations, whose observations only the depth test flags (Optimizer.cc:715-728) -- the erased count holds them."""
     _build()
     prob, ref = load_ba_golden(os.path.join(ROOT, "tests", "golden", "ba_%s.npz" % name))
     K, P, E = len(prob["kf_fixed"]), len(prob["pt_xyz"]), len(prob["edge_kf"])

@@ -4,6 +4,21 @@ oracle/Makefile.ref from /root/reference).  Authoring container only.  Each file
 inputs of one local-BA window (as include/slamit.h lays them out) and what the reference's g2o
 produced for it through the Optimizer.cc:507-743 schedule: final poses / points, per-edge chi2,
 stage-1 and final outlier flags, per-iteration robust cost, lambda and LM trial counts.
+
+HARD holds windows that synth.synth_ba never makes by itself; a case names a synth_ba window and post-processing steps
+(weiner_slamit_v2_amd/synth.py), applied in this order:
+  mirror     dict(n, obs, seed[, first_kfs, stereo_frac]): synth.ba_mirror_points -- n new points BEHIND `obs` consecutive keyframes,
+             observed by them through the pinhole formula at the negative depth plus pixel noise (small residuals: only the depth
+             half of the gate flags these edges).  The cameras of a synth_ba window all look along +z, so a point is behind all of
+             its observers or none -- a mirrored triangulation; the map-sized case (tools/gen_ba_large_golden.py) has points
+             in front of some observers and behind others.
+  starve_pt  dict(one, zero, seed): synth.ba_starve_pt -- the points in `one` keep one good observation, those in `zero` none; the
+             rest become gross outliers, so the gate leaves them one / no active edge.
+  starve_kf  list of (keyframe, seed): synth.ba_starve_kf -- every observation of a free keyframe becomes a gross outlier: the gate
+             sends all of its edges to level 1 and the second stage runs without it.
+Their files also hold the indices the steps touched (mirror_edges, starved_kf, starved_pt1, starved_pt0) and the reference's
+estimates between the two stages (ref_kf_pose_stage1, ref_pt_xyz_stage1; oracle/ba_ref_harness.cc: ba_ref_solve_ex), which a
+vertex left without active edges keeps to the end.  tests/test_hard_geometry_fixtures.py states what each file must contain.
 """
 import os
 import sys
@@ -37,8 +52,35 @@ CASES = {
     # the free keyframes are renumbered on the host (csrc/ba_plan.cc ba_order_columns) -- an 8th field = the seed of the permutation
     "shuffled": (50, 1000, 8, 61, 2, 1.0, 0.0, 9),
 }
+HARD = {
+    "behind": dict(base=(12, 250, 4, 81, 2), mirror=dict(n=30, obs=4, seed=181, first_kfs=(0, 0, 0, 0, 1, 1))),
+    "stereo_behind": dict(base=(12, 250, 4, 82, 1, 1.0, 0.5), mirror=dict(n=36, obs=4, seed=182, stereo_frac=0.5)),
+    "starved_kf": dict(base=(12, 250, 3, 83, 1), starve_kf=[(6, 183)]),                     # an interior keyframe; a narrow band
+    "starved_pts": dict(base=(12, 300, 5, 84, 1), starve_pt=dict(one=(3, 40, 77, 120, 199, 260), zero=(9, 51, 93, 150, 222, 281), seed=184),
+                        starve_kf=[(8, 187)]),
+    "behind_global": dict(base=(14, 300, 5, 85, 1), mirror=dict(n=30, obs=4, seed=186)),    # BundleAdjustment: no gate, only the final flags
+}
 # name -> (its_robust, its_final, huber_delta); everything else uses the local-BA schedule of Optimizer.cc:507-743
-SCHEDULE = {"global_init": (20, 0, float(np.float32(np.sqrt(5.99)))), "global_map": (10, 0, float(np.float32(np.sqrt(5.99))))}
+SCHEDULE = {"global_init": (20, 0, float(np.float32(np.sqrt(5.99)))), "global_map": (10, 0, float(np.float32(np.sqrt(5.99)))),
+            "behind_global": (10, 0, float(np.float32(np.sqrt(5.99))))}
+
+
+def make_hard(name):
+    """-> (problem, {name of an index array: indices}) of a HARD case."""
+    case = HARD[name]
+    k, p, o, seed, nfix = case["base"][:5]
+    prob = synth.synth_ba(k, p, o, seed=seed, n_fixed=nfix, stereo_frac=case["base"][6] if len(case["base"]) > 6 else 0.0)
+    marks = {}
+    if "mirror" in case:
+        prob, _, marks["mirror_edges"] = synth.ba_mirror_points(prob, **case["mirror"])
+    if "starve_pt" in case:
+        prob = synth.ba_starve_pt(prob, **case["starve_pt"])
+        marks["starved_pt1"], marks["starved_pt0"] = np.array(case["starve_pt"]["one"]), np.array(case["starve_pt"]["zero"])
+    for kf, sd in case.get("starve_kf", ()):
+        prob = synth.ba_starve_kf(prob, kf, sd)
+    if "starve_kf" in case:
+        marks["starved_kf"] = np.array([kf for kf, _ in case["starve_kf"]])
+    return prob, marks
 
 
 def make(name):
@@ -68,12 +110,14 @@ def main():
     assert ob.ba_ref_available(), "build oracle/_ref first: make -C oracle -f Makefile.ref"
     out_dir = os.path.join(ROOT, "tests", "golden")
     only = sys.argv[1:]   # optional: the case names to (re)generate; default all
-    for name in CASES:
+    for name in list(CASES) + list(HARD):
         if only and not any(name.startswith(o) for o in only):
             continue
-        prob = make(name)
+        prob, marks = make_hard(name) if name in HARD else (make(name), {})
         sched = SCHEDULE.get(name)
-        ref = ob.ba_ref_solve(prob, *sched) if sched else ob.ba_ref_solve(prob)
+        ref = ob.ba_ref_solve(prob, *(sched or ()), stage1=name in HARD)
+        if name in HARD:
+            marks.update(ref_kf_pose_stage1=ref["kf_pose_stage1"], ref_pt_xyz_stage1=ref["pt_xyz_stage1"])
         st = ref["stats"]
         pad = lambda rows: np.array([list(r) + [np.nan] * (32 - len(r)) for r in rows], dtype=np.float64)
         np.savez_compressed(
@@ -85,7 +129,7 @@ def main():
             ref_kf_pose=ref["kf_pose"], ref_pt_xyz=ref["pt_xyz"], ref_edge_chi2=ref["edge_chi2"],
             ref_edge_outlier=ref["edge_outlier"], ref_edge_stage1_outlier=ref["edge_stage1_outlier"],
             ref_n_its=np.array(st["n_its"]), ref_chi2=pad(st["chi2"]), ref_lambda=pad(st["lambda"]),
-            ref_trials=pad(st["trials"]), ref_chi2_init=np.array(st["chi2_init"]),
+            ref_trials=pad(st["trials"]), ref_chi2_init=np.array(st["chi2_init"]), **marks,
             schedule=np.array(sched if sched else (5, 10, ob.HUBER_MONO), np.float64))
         print(name, "edges", len(prob["edge_kf"]), "its", st["n_its"], "trials", st["trials"],
               "outliers", int(ref["edge_outlier"].sum()))

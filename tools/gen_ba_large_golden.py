@@ -4,6 +4,10 @@ schedule, CRC32s of the problem's arrays, and the result -- every pose, a seeded
 bits), the LM path (iterations, trials, chi2 and lambda per iteration) and the stage start costs.  Float64 values are stored as
 base64 of their little-endian bytes (exact, and the fixture stays small).
 
+HARD windows (synth.synth_map_hard: mirrored observations of points on the far side of the circle, a free keyframe whose
+observations are all gross outliers) go to a sibling file, tests/golden/ba_large_hard_ref.json.gz, with their post-processing
+arguments ("hard"), the mirrored edges' indices and every pose between the two stages ("kf_pose_stage1").
+
     python tools/gen_ba_large_golden.py
 """
 import base64
@@ -33,6 +37,11 @@ WINDOWS = {
     "global150": (dict(n_kf=150, n_pt=1500, obs_per_pt=6, n_fixed=1, seed=14), GLOBAL),                      # 894 / 896: side table
     "global300": (dict(n_kf=300, n_pt=3000, obs_per_pt=6, n_fixed=1, seed=15), GLOBAL),                      # 1794 / 1856
 }
+OUT_HARD = os.path.join(ROOT, "tests", "golden", "ba_large_hard_ref.json.gz")
+# name -> synth_map arguments, synth_map_hard's post-processing, schedule
+HARD = {
+    "starved100": (dict(n_kf=100, n_pt=1000, obs_per_pt=6, n_fixed=1, seed=21), dict(mirror=dict(n=60, seed=121), starve_kf=[[50, 124]]), LOCAL),   # 594 / 640: tiled
+}
 PROBLEM_KEYS = ("kf_pose", "kf_fixed", "kf_intr", "pt_xyz", "edge_kf", "edge_pt", "edge_uv", "edge_inv_sigma2", "edge_ur", "kf_bf")
 N_SAMPLE = 300
 
@@ -49,17 +58,24 @@ def point_sample(name, n_pt):
     return np.sort(np.random.RandomState(zlib.crc32(name.encode())).choice(n_pt, min(N_SAMPLE, n_pt), replace=False))
 
 
-def main():
-    if not ob.ba_ref_available():
-        raise SystemExit("oracle/_ref/libba_ref.so is not built (build() makes it where the reference source exists)")
+def solve_all(windows, out, what):
     cases = {}
-    for name, (kw, sched) in WINDOWS.items():
-        prob = synth.synth_map(**kw)
-        r = ob.ba_ref_solve(prob, its_robust=sched[0], its_final=sched[1], huber_delta=sched[2])
+    for name, spec in windows.items():
+        kw, sched = spec[0], spec[-1]
+        extra = {}
+        if len(spec) == 3:
+            prob, mirrored = synth.synth_map_hard(kw, **spec[1])
+            extra = {"hard": spec[1], "mirror_edges": mirrored.tolist()}
+        else:
+            prob = synth.synth_map(**kw)
+        r = ob.ba_ref_solve(prob, its_robust=sched[0], its_final=sched[1], huber_delta=sched[2], stage1=len(spec) == 3)
+        if len(spec) == 3:
+            extra["kf_pose_stage1"] = b64(r["kf_pose_stage1"])
+            extra["mirror_edge_chi2"] = b64(r["edge_chi2"][mirrored])
         idx = point_sample(name, len(prob["pt_xyz"]))
         s = r["stats"]
         cases[name] = {
-            "synth_map": kw, "schedule": sched, "crc32": crcs(prob),
+            **extra, "synth_map": kw, "schedule": sched, "crc32": crcs(prob),
             "kf_pose": b64(r["kf_pose"]), "pt_index": idx.tolist(), "pt_xyz": b64(r["pt_xyz"][idx]),
             "edge_outlier": base64.b64encode(np.packbits(r["edge_outlier"].astype(bool))).decode(),
             "edge_stage1_outlier": base64.b64encode(np.packbits(r["edge_stage1_outlier"].astype(bool))).decode(),
@@ -67,10 +83,19 @@ def main():
             "n_its": s["n_its"], "trials": s["trials"], "chi2": [b64(c) for c in s["chi2"]], "lambda": [b64(c) for c in s["lambda"]],
             "chi2_init": b64(s["chi2_init"]),
         }
-    with gzip.GzipFile(OUT, "wb", mtime=0) as f:
-        f.write(json.dumps({"what": "map-sized BA windows solved by the reference's g2o (tools/gen_ba_large_golden.py)", "cases": cases},
-                           sort_keys=True).encode())
-    print(OUT, os.path.getsize(OUT), "bytes")
+        print(name, "its", s["n_its"], "trials", s["trials"], "outliers", int(r["edge_outlier"].sum()))
+    with gzip.GzipFile(out, "wb", mtime=0) as f:
+        f.write(json.dumps({"what": what, "cases": cases}, sort_keys=True).encode())
+    print(out, os.path.getsize(out), "bytes")
+
+
+def main():
+    if not ob.ba_ref_available():
+        raise SystemExit("oracle/_ref/libba_ref.so is not built (build() makes it where the reference source exists)")
+    if "hard" not in sys.argv[1:]:   # (`hard`: only the sibling file)
+        solve_all(WINDOWS, OUT, "map-sized BA windows solved by the reference's g2o (tools/gen_ba_large_golden.py)")
+    solve_all(HARD, OUT_HARD, "map-sized BA windows with mirrored observations and a starved keyframe, solved by the reference's g2o "
+                              "(tools/gen_ba_large_golden.py)")
 
 
 if __name__ == "__main__":

@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Generates tests/golden/pose_*.npz from the REFERENCE's own g2o (oracle/_ref/libba_ref.so:
-pose_ref_solve = Optimizer::PoseOptimization's schedule on POD inputs).  Authoring container only."""
+pose_ref_solve = Optimizer::PoseOptimization's schedule on POD inputs).  Authoring container only.
+
+A case may end with a dict(mirror=(n_small, n_gross, seed)): synth.pose_mirror turns that many correspondences into mirrored ones (the map
+point behind the frame, the keypoint the pinhole formula at the negative depth): n_small with pixel noise only -- PoseOptimization has
+no depth test, they must stay inliers --, n_gross with a gross error besides -- pruned by chi2 alone.  Their files also hold the two
+index lists (mirror_small, mirror_gross)."""
 import os
 import sys
 
@@ -24,6 +29,9 @@ CASES = {  # name: (n, outlier fraction, seed, initial pose perturbation)
     "stereo_mixed": (500, 0.25, 22, 0.05, 0.5),
     "stereo_few": (40, 0.10, 23, 0.02, 0.7),
     "stereo_under10": (9, 0.0, 24, 0.01, 0.6),
+    # correspondences behind the camera (tests/test_hard_geometry_fixtures.py)
+    "behind": (300, 0.10, 31, 0.02, 0.0, dict(mirror=(16, 16, 131))),
+    "stereo_behind": (300, 0.10, 32, 0.02, 0.6, dict(mirror=(20, 16, 132))),
 }
 
 
@@ -35,13 +43,16 @@ def main():
             continue
         n, of, seed, pert = case[:4]
         pr = synth.synth_pose(n, of, seed, pert, stereo_frac=case[4] if len(case) > 4 else 0.0)
+        marks = {}
+        if len(case) > 5:
+            pr, marks["mirror_small"], marks["mirror_gross"] = synth.pose_mirror(pr, *case[5]["mirror"])
         r = ob.pose_ref_solve(pr)
         np.savez_compressed(os.path.join(ROOT, "tests", "golden", "pose_%s.npz" % name),
                             pose=pr["pose"].astype(np.float32), intr=pr["intr"].astype(np.float32), xw=pr["xw"].astype(np.float32),
                             uv=pr["uv"].astype(np.float32), inv_sigma2=pr["inv_sigma2"].astype(np.float32),
                             **({"ur": pr["ur"].astype(np.float32), "bf": np.float32(pr["bf"])} if "ur" in pr else {}),
                             ref_pose=r["pose"], ref_outlier=r["outlier"], ref_n_inliers=r["n_inliers"],
-                            ref_n_its=np.array(r["n_its"]), ref_chi2=np.array(r["chi2"]))
+                            ref_n_its=np.array(r["n_its"]), ref_chi2=np.array(r["chi2"]), **marks)
         print(name, n, "inliers", r["n_inliers"], "its", r["n_its"])
 
 

@@ -498,3 +498,206 @@ def synth_map(n_kf, n_pt, obs_per_pt, n_fixed, seed, stereo_frac=0.0, loop=True,
         "truth_pose": np.array([np.concatenate([Rs[k].reshape(-1), ts[k]]) for k in range(n_kf)]),
         "truth_pt": pts,
     }
+
+
+# ---------------------------------------------------------------------------------------------
+# Hard geometry: post-processing of the problems above (tools/gen_*_golden.py: mirror / starve_kf / starve_pt).  The generators
+# above only make well-posed input -- every point in front of its observers, outliers that are gross pixel errors spread evenly.
+# A front end also hands over mirrored triangulations (a point behind the cameras that observe it, with a small reprojection
+# error: only the depth test removes it) and keyframes / points whose observations all fail the gate.
+# ---------------------------------------------------------------------------------------------
+
+def _append_edges(prob, kf, pt, uv, isig, ur=None):
+    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
+    q = dict(prob)
+    q["edge_kf"] = np.concatenate([prob["edge_kf"], np.asarray(kf, np.int32)])
+    q["edge_pt"] = np.concatenate([prob["edge_pt"], np.asarray(pt, np.int32)])
+    q["edge_uv"] = np.concatenate([prob["edge_uv"], f32(uv).reshape(-1, 2)])
+    q["edge_inv_sigma2"] = np.concatenate([prob["edge_inv_sigma2"], f32(isig)])
+    if "edge_ur" in prob:
+        q["edge_ur"] = np.concatenate([prob["edge_ur"], f32(ur)])
+    return q
+
+
+def _truth_cam(prob, kf, X):
+    tp = prob["truth_pose"][kf]
+    return tp[:9].reshape(3, 3) @ X + tp[9:]
+
+
+def ba_mirror_points(prob, n, obs, seed, stereo_frac=0.0, sigma=1.0, first_kfs=()):
+    """`prob` (synth_ba: every camera looks along +z) plus n mirrored triangulations: new points BEHIND `obs` consecutive keyframes
+    (depth -8 .. -4 in their frames at the true state), each observed by all of them with u = fx x / z + cx, v likewise (stereo:
+    ur = u - bf / z) evaluated at that negative depth, plus N(0, sigma) pixel noise.  The residuals are small at the truth, so only
+    the depth test flags these edges.  Point i < len(first_kfs) starts its run of observers at keyframe first_kfs[i] (to put
+    mirrored edges on chosen -- e.g. fixed -- keyframes).  -> (problem, indices of the new points, indices of the new edges)."""
+    rs = np.random.RandomState(seed)
+    fx, fy, cx, cy = INTRINSICS
+    n_kf, n_pt0, n_e0 = len(prob["kf_fixed"]), len(prob["pt_xyz"]), len(prob["edge_kf"])
+    bf = float(prob["kf_bf"][0]) if "kf_bf" in prob else 0.0
+    inv_sig = _inv_sigma2_table()
+    X_new, e_kf, e_pt, e_uv, e_is, e_ur = [], [], [], [], [], []
+    while len(X_new) < n:
+        i = len(X_new)
+        start = int(first_kfs[i]) if i < len(first_kfs) else int(rs.randint(0, n_kf - obs + 1))
+        z = -rs.uniform(4.0, 8.0)
+        Xc = np.array([rs.uniform(-0.4, 0.4) * z, rs.uniform(-0.3, 0.3) * z, z])
+        tp = prob["truth_pose"][start + obs // 2]
+        X = tp[:9].reshape(3, 3).T @ (Xc - tp[9:])
+        cams = [_truth_cam(prob, k, X) for k in range(start, start + obs)]
+        uvs = [(fx * c[0] / c[2] + cx, fy * c[1] / c[2] + cy) for c in cams]
+        if not all(c[2] < -1.0 and 8 <= u <= 632 and 8 <= v <= 472 for c, (u, v) in zip(cams, uvs)):
+            continue
+        for k, c, (u, v) in zip(range(start, start + obs), cams, uvs):
+            u, v = u + rs.normal(0.0, sigma), v + rs.normal(0.0, sigma)
+            e_kf.append(k); e_pt.append(n_pt0 + i); e_uv.append((u, v)); e_is.append(inv_sig[rs.choice(8)])
+            ur = u - bf / c[2] + rs.normal(0.0, sigma)
+            e_ur.append(ur if rs.uniform() < stereo_frac else -1.0)
+        X_new.append(X)
+    X_new = np.array(X_new)
+    q = _append_edges(prob, e_kf, e_pt, e_uv, e_is, e_ur)
+    q["truth_pt"] = np.concatenate([prob["truth_pt"], X_new])
+    q["pt_xyz"] = np.concatenate([prob["pt_xyz"], (X_new + rs.normal(0.0, 0.02, X_new.shape)).astype(np.float32).astype(np.float64)])
+    return q, np.arange(n_pt0, n_pt0 + n), np.arange(n_e0, len(q["edge_kf"]))
+
+
+def ba_mirror_edges(prob, n, seed, sigma=1.0, stereo_frac=0.0):
+    """`prob` (synth_map: cameras on a circle looking outward) plus n mirrored observations of EXISTING points: a point on the far
+    side of the circle lies behind a keyframe and still projects into its image through the pinhole formula at that negative depth.
+    The point keeps its observers in front, so it stays well constrained.  -> (problem, indices of the new edges)."""
+    rs = np.random.RandomState(seed)
+    fx, fy, cx, cy = INTRINSICS
+    tp = prob["truth_pose"]
+    R, t = tp[:, :9].reshape(-1, 3, 3), tp[:, 9:]
+    Xc = np.einsum("kij,pj->kpi", R, prob["truth_pt"]) + t[:, None, :]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u, v = fx * Xc[..., 0] / Xc[..., 2] + cx, fy * Xc[..., 1] / Xc[..., 2] + cy
+    ok = (Xc[..., 2] < -1.0) & (u >= 8) & (u <= 632) & (v >= 8) & (v <= 472)
+    cand = np.argwhere(ok)
+    pick = cand[np.sort(rs.choice(len(cand), n, replace=False))]
+    bf = float(prob["kf_bf"][0]) if "kf_bf" in prob else 0.0
+    inv_sig = _inv_sigma2_table()
+    e_uv, e_is, e_ur = [], [], []
+    for k, p in pick:
+        uu, vv = u[k, p] + rs.normal(0.0, sigma), v[k, p] + rs.normal(0.0, sigma)
+        e_uv.append((uu, vv)); e_is.append(inv_sig[rs.choice(8)])
+        ur = uu - bf / Xc[k, p, 2] + rs.normal(0.0, sigma)
+        e_ur.append(ur if rs.uniform() < stereo_frac else -1.0)
+    n_e0 = len(prob["edge_kf"])
+    q = _append_edges(prob, pick[:, 0], pick[:, 1], e_uv, e_is, e_ur)
+    return q, np.arange(n_e0, len(q["edge_kf"]))
+
+
+def _garble(prob, edges, rs, signs=None):
+    """Gross outliers on `edges`: 45 .. 90 px off in u and in v (past the +-30 px of synth_ba's own outliers, so that none cancels),
+    signs random or as given."""
+    q = dict(prob)
+    q["edge_uv"] = prob["edge_uv"].copy()
+    if signs is None:
+        signs = rs.choice([-1.0, 1.0], (len(edges), 2))
+    off = signs * rs.uniform(45.0, 90.0, (len(edges), 2))
+    q["edge_uv"][edges] = (q["edge_uv"][edges] + off).astype(np.float32).astype(np.float64)
+    if "edge_ur" in prob:
+        q["edge_ur"] = prob["edge_ur"].copy()
+        st = edges[prob["edge_ur"][edges] >= 0]
+        q["edge_ur"][st] = (q["edge_ur"][st] + 700.0 + rs.uniform(20.0, 60.0, len(st))).astype(np.float32).astype(np.float64)   # (stays >= 0: stereo)
+    return q
+
+
+def ba_starve_kf(prob, kf, seed):
+    """Every observation of keyframe `kf` replaced by a gross outlier (45 .. 90 px off in u and in v, random signs): no pose fits them,
+    the gate sends all of the keyframe's edges to level 1 and the second stage runs without it."""
+    return _garble(prob, np.flatnonzero(prob["edge_kf"] == kf), np.random.RandomState(seed))
+
+
+def ba_starve_pt(prob, one, zero, seed):
+    """The points in `one` keep one good observation (their first), the points in `zero` none: the others become gross outliers, so
+    that the gate leaves them exactly one / no active edge.  A Huber edge pulls with a bounded force however wrong it is, and four
+    such pulls would drag the point off its one good observation until that fails the gate too: the wrong observations of a point
+    get signs that cancel in pairs and the coarsest pyramid level's weight, the good one of a point in `one` the finest level's."""
+    pattern = np.array([(1.0, 1.0), (-1.0, -1.0), (1.0, -1.0), (-1.0, 1.0)])
+    inv_sig = _inv_sigma2_table()
+    edges, signs, good = [], [], []
+    for p in list(one) + list(zero):
+        e = np.flatnonzero(prob["edge_pt"] == p)
+        if p in one:
+            good.append(e[0])
+            e = e[1:]
+        edges.append(e)
+        signs.append(pattern[np.arange(len(e)) % 4])
+    edges = np.concatenate(edges)
+    q = _garble(prob, edges, np.random.RandomState(seed), np.concatenate(signs))
+    q["edge_inv_sigma2"] = prob["edge_inv_sigma2"].copy()
+    q["edge_inv_sigma2"][edges] = float(inv_sig[-1])
+    q["edge_inv_sigma2"][good] = float(inv_sig[0])
+    return q
+
+
+def pose_mirror(prob, n_small, n_gross, seed):
+    """A synth_pose problem whose first n_small + n_gross correspondences (random ones) are mirrored: the map point lies behind the
+    frame (depth -9 .. -3 at the true pose), its keypoint is the pinhole formula at that negative depth plus N(0, 1) px; the last
+    n_gross of them are 8 .. 60 px further off.  PoseOptimization has no depth test (Optimizer.cc:239-451): the first kind must stay
+    inliers, the second is pruned by chi2 alone.  -> (problem, indices small, indices gross)."""
+    rs = np.random.RandomState(seed)
+    fx, fy, cx, cy = INTRINSICS
+    n = len(prob["uv"])
+    idx = rs.choice(n, n_small + n_gross, replace=False)
+    m = len(idx)
+    z = -rs.uniform(3.0, 9.0, m)
+    pc = np.stack([rs.uniform(-0.45, 0.45, m) * z, rs.uniform(-0.35, 0.35, m) * z, z], 1)
+    R, t = prob["truth_pose"][:9].reshape(3, 3), prob["truth_pose"][9:]
+    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
+    q = dict(prob)
+    q["xw"], q["uv"] = prob["xw"].copy(), prob["uv"].copy()
+    q["xw"][idx] = f32((pc - t) @ R)
+    u = fx * pc[:, 0] / pc[:, 2] + cx + rs.normal(0, 1, m)
+    v = fy * pc[:, 1] / pc[:, 2] + cy + rs.normal(0, 1, m)
+    u[n_small:] += rs.choice([-1, 1], n_gross) * rs.uniform(8, 60, n_gross)
+    v[n_small:] += rs.choice([-1, 1], n_gross) * rs.uniform(8, 60, n_gross)
+    q["uv"][idx] = f32(np.stack([u, v], 1))
+    if "ur" in prob:
+        q["ur"] = prob["ur"].copy()
+        ur = f32(u - prob["bf"] / pc[:, 2] + rs.normal(0, 1, m))
+        q["ur"][idx] = np.where(prob["ur"][idx] >= 0, ur, -1.0)
+    q["truth_outlier"] = prob["truth_outlier"].copy()
+    q["truth_outlier"][idx] = np.arange(m) >= n_small
+    return q, idx[:n_small], idx[n_small:]
+
+
+def sim3_mirror(prob, n_small, n_gross, seed):
+    """A synth_sim3 problem with n_small + n_gross pairs mirrored: p2 behind camera 2 (depth -9 .. -2.5) and p1 = s R p2 + t behind
+    camera 1, both keypoints the pinhole formula at the negative depths plus N(0, 0.7) px; the last n_gross carry a wrong keypoint in
+    image 1 (20 .. 60 px off).  OptimizeSim3 has no depth test (Optimizer.cc:1046-1247).  -> (problem, indices small, indices gross)."""
+    rs = np.random.RandomState(seed)
+    n = prob["n"]
+    idx = rs.choice(n, n_small + n_gross, replace=False)
+    m = len(idx)
+    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
+    z = -rs.uniform(2.5, 9.0, m)
+    p2 = f32(np.stack([rs.uniform(-0.4, 0.4, m) * z, rs.uniform(-0.3, 0.3, m) * z, z], 1))
+    tr = prob["true"]
+    p1 = f32(tr["s"] * (p2 @ tr["R"].T) + tr["t"] + rs.normal(0, 0.01, (m, 3)))
+    assert (p1[:, 2] < -1.0).all()
+    i1, i2 = prob["intr1"], prob["intr2"]
+    o1 = np.stack([i1[0] * p1[:, 0] / p1[:, 2] + i1[2], i1[1] * p1[:, 1] / p1[:, 2] + i1[3]], 1) + rs.normal(0, 0.7, (m, 2))
+    o2 = np.stack([i2[0] * p2[:, 0] / p2[:, 2] + i2[2], i2[1] * p2[:, 1] / p2[:, 2] + i2[3]], 1) + rs.normal(0, 0.7, (m, 2))
+    o1[n_small:] += rs.choice([-1, 1], (n_gross, 2)) * rs.uniform(20, 60, (n_gross, 2))
+    q = dict(prob)
+    for k, v in (("p1", p1), ("p2", p2), ("obs1", f32(o1)), ("obs2", f32(o2))):
+        q[k] = prob[k].copy()
+        q[k][idx] = v
+    return q, idx[:n_small], idx[n_small:]
+
+
+def synth_map_hard(synth_map, mirror=None, starve_kf=()):
+    """synth_map(**synth_map) with mirror = dict(n, seed) mirrored observations (ba_mirror_edges) and every (keyframe, seed) of starve_kf
+    starved (ba_starve_kf).  -> (problem, indices of the mirrored edges)."""
+    prob = _synth_map_fn(**synth_map)
+    edges = np.zeros(0, np.int64)
+    if mirror:
+        prob, edges = ba_mirror_edges(prob, stereo_frac=synth_map.get("stereo_frac", 0.0), **mirror)
+    for kf, seed in starve_kf:
+        prob = ba_starve_kf(prob, kf, seed)
+    return prob, edges
+
+
+_synth_map_fn = synth_map
