@@ -497,6 +497,40 @@ typedef struct slamit_sim3_result {
 int slamit_sim3_optimize_batch(int device, int nproblems, const slamit_sim3_problem* probs, slamit_sim3_result* results);
 int slamit_sim3_optimize(int device, const slamit_sim3_problem* prob, slamit_sim3_result* res);
 
+/* ---- Sim3Solver: batched RANSAC hypotheses over Horn's closed form (loop closing, between SearchByBoW and SearchBySim3) ----
+ * Sim3Solver::ComputeSim3 + CheckInliers (src/Sim3Solver.cc:226-364) for n_hyp sampled triples of one candidate keyframe:
+ * per hypothesis the closed-form similarity of its three correspondences (float / double exactly where the reference has
+ * them), then both projections of all n correspondences and the count of those with err1 < max_err1 && err2 < max_err2.
+ * One wavefront per (problem, hypothesis); a batch of candidates is one launch.  Sampling and iterate()'s acceptance scan
+ * stay with the caller (shim/Sim3Solver.h, api.Sim3Solver).  The sampler of the reference can repeat an index inside a
+ * triple (:166-177): that is legal input and yields some count in [0, n].  An index outside [0, n), n above
+ * SLAMIT_SIM3_RANSAC_MAX_N or n_hyp above SLAMIT_SIM3_RANSAC_MAX_HYP fails with SLAMIT_ERR_ARG and a message; n == 0 or
+ * n_hyp == 0 is allowed and writes nothing. */
+#define SLAMIT_SIM3_RANSAC_MAX_N 8192      /* correspondences per problem (a keyframe holds a few thousand keypoints at most) */
+#define SLAMIT_SIM3_RANSAC_MAX_HYP 1024    /* hypotheses per problem (LoopClosing asks for 300) */
+
+typedef struct slamit_sim3_ransac_problem {
+    int32_t n;                 /* correspondences kept by the Sim3Solver constructor (:62-103) */
+    const float* x1;           /* n x 3: mvX3Dc1 (Rcw1*X+tcw1, float) */
+    const float* x2;           /* n x 3: mvX3Dc2 */
+    const float* max_err1;     /* n: (float)(size_t)(9.210*sigma2): mvnMaxError1 is a vector<size_t>, the bound is truncated */
+    const float* max_err2;     /* n */
+    float intr1[4], intr2[4];  /* fx fy cx cy of mK1, mK2 */
+    int32_t fix_scale;
+    int32_t n_hyp;             /* hypotheses to evaluate */
+    const int32_t* triples;    /* n_hyp x 3 indices into the n correspondences */
+} slamit_sim3_ransac_problem;
+
+typedef struct slamit_sim3_ransac_result {
+    float* t12;                /* n_hyp x 13: R12 row-major (9), t12 (3), s12 */
+    int32_t* n_inliers;        /* n_hyp: mnInliersi of each hypothesis */
+    uint32_t* inlier_bits;     /* n_hyp x ((n+31)/32), nullable: bit i = mvbInliersi[i] */
+} slamit_sim3_ransac_result;
+
+/* nproblems candidates in one launch (host pointers, synchronous). */
+int slamit_sim3_ransac_batch(int device, int nproblems, const slamit_sim3_ransac_problem* probs, slamit_sim3_ransac_result* results);
+int slamit_sim3_ransac(int device, const slamit_sim3_ransac_problem* prob, slamit_sim3_ransac_result* res);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 
 const char* slamit_last_error(void);

@@ -7,6 +7,7 @@ The classes keep the reference's names and argument meaning:
 There is NO CPU fallback: if the library is missing or no GPU is usable every call raises.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -102,6 +103,18 @@ class Sim3Result(C.Structure):
                 ("n_its", C.c_int32 * 2), ("chi2", C.c_double * 2)]
 
 
+class Sim3RansacProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("x1", C.c_void_p), ("x2", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p),
+                ("intr1", C.c_float * 4), ("intr2", C.c_float * 4), ("fix_scale", C.c_int32), ("n_hyp", C.c_int32), ("triples", C.c_void_p)]
+
+
+class Sim3RansacResult(C.Structure):
+    _fields_ = [("t12", C.c_void_p), ("n_inliers", C.c_void_p), ("inlier_bits", C.c_void_p)]
+
+
+SIM3_RANSAC_MAX_N, SIM3_RANSAC_MAX_HYP = 8192, 1024   # SLAMIT_SIM3_RANSAC_MAX_N / _MAX_HYP
+
+
 class SearchBatch(C.Structure):
     _fields_ = [("nframes", C.c_int32), ("kp_cap", C.c_int32), ("q_cap", C.c_int32), ("d_n", C.c_void_p),
                 ("d_kps_un", C.c_void_p), ("d_desc", C.c_void_p), ("d_kp_taken", C.c_void_p), ("min_x", C.c_float),
@@ -140,7 +153,7 @@ EXPORTS = [
     "slamit_orb_debug_candidates", "slamit_orb_debug_blurred", "slamit_orb_profile", "slamit_hamming_best2", "slamit_hamming_best2_batch_dev",
     "slamit_hamming_matrix", "slamit_distinctive_batch", "slamit_guided_search", "slamit_guided_search_workspace", "slamit_guided_search_batch_dev", "slamit_bow_search", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -186,6 +199,8 @@ def lib():
         f32 = C.c_float
         L.slamit_sim3_optimize_batch.argtypes = [i32, i32, C.POINTER(Sim3Problem), C.POINTER(Sim3Result)]
         L.slamit_sim3_optimize.argtypes = [i32, C.POINTER(Sim3Problem), C.POINTER(Sim3Result)]
+        L.slamit_sim3_ransac_batch.argtypes = [i32, i32, C.POINTER(Sim3RansacProblem), C.POINTER(Sim3RansacResult)]
+        L.slamit_sim3_ransac.argtypes = [i32, C.POINTER(Sim3RansacProblem), C.POINTER(Sim3RansacResult)]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_undistort_points.argtypes = [i32, C.POINTER(Camera), vp, i32, vp]
         L.slamit_frame_finish.argtypes = [i32, C.POINTER(Camera), vp, i32, f32, f32, f32, f32, vp, vp, vp]
@@ -743,3 +758,165 @@ class Optimizer:
         for out, st in zip(outs, sts):
             out["stats"] = self._stats(st)
         return outs
+
+
+class Sim3Solver:
+    """Sim3Solver (include/Sim3Solver.h) on POD inputs: the constructor's gathering (Sim3Solver.cc:62-103) stays with the caller,
+    who hands over a problem dict in the layout of slamit_sim3_ransac_problem (synth.synth_sim3_ransac): x1, x2 (n, 3) float32,
+    max_err1, max_err2 (n) -- see max_error() --, intr1, intr2, fix_scale.  The hypotheses run on the device in one call
+    (evaluate), iterate()'s sequential acceptance scan (:183-200) runs here over the device's counts.  `rand_int(lo, hi)` stands
+    for DUtils::Random::RandomInt; all mRansacMaxIts triples are drawn when the parameters are set."""
+
+    def __init__(self, problem, rand_int=None, device=0):
+        self.problem = problem
+        self.N = len(np.asarray(problem["max_err1"]))
+        self.device = device
+        self.mnIterations = 0
+        self.mnBestInliers = 0
+        self.best = None            # index of the hypothesis that holds the running best
+        self.counts = None          # device results, filled by the first iterate()
+        self.accepted = -1          # index of the hypothesis iterate() returned
+        if rand_int is None:
+            rs = np.random.RandomState(0)
+            rand_int = lambda lo, hi: int(rs.randint(lo, hi + 1))   # noqa: E731
+        self.rand_int = rand_int
+        self.SetRansacParameters()
+
+    @staticmethod
+    def max_error(sigma2):
+        """mvnMaxError (Sim3Solver.h:78-79) is a vector<size_t>: 9.210 * sigma2 is truncated to an integer before err < max."""
+        return np.floor(9.210 * np.asarray(sigma2, np.float32).astype(np.float64)).astype(np.float32)
+
+    @staticmethod
+    def ransac_iterations(N, probability, minInliers, maxIterations):
+        """mRansacMaxIts of SetRansacParameters (:114-138): float epsilon, ceil(log / log), the minInliers == N case, the clamp."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            eps = np.float32(minInliers) / np.float32(N)
+            if minInliers == N:
+                nit = 1
+            else:
+                eps3 = math.pow(float(eps), 3)   # pow(float, int) promotes to double
+                v = np.ceil(np.log(1 - probability) / np.log(np.float64(1) - eps3))
+                nit = int(np.clip(v, -2 ** 31, 2 ** 31 - 1)) if np.isfinite(v) else -2 ** 31   # (int) of an unrepresentable double on x86-64
+        return max(1, min(nit, maxIterations))
+
+    @staticmethod
+    def sample_triples(N, count, rand_int):
+        """The sampler of iterate() (:163-177), with its quirk: the slot overwritten is vAvailableIndices[idx] -- indexed by the
+        VALUE drawn, not by the position randi -- so a value can be drawn twice inside a triple."""
+        out = np.zeros((count, 3), np.int32)
+        for h in range(count):
+            avail, size = list(range(N)), N   # a value drawn may lie past the shrunken end: the store then lands in a popped slot
+            for i in range(3):
+                randi = rand_int(0, size - 1)
+                idx = avail[randi]
+                out[h, i] = idx
+                avail[idx] = avail[size - 1]
+                size -= 1
+        return out
+
+    def SetRansacParameters(self, probability=0.99, minInliers=6, maxIterations=300):
+        self.mRansacProb, self.mRansacMinInliers = probability, minInliers
+        self.mRansacMaxIts = self.ransac_iterations(self.N, probability, minInliers, maxIterations)
+        self.mnIterations = 0
+        self.counts = None
+        self.triples = self.sample_triples(self.N, min(self.mRansacMaxIts, SIM3_RANSAC_MAX_HYP), self.rand_int) if self.N >= max(minInliers, 3) else np.zeros((0, 3), np.int32)
+
+    @staticmethod
+    def evaluate(problems, device=0, want_bits=True):
+        """Raw per-hypothesis results of one problem dict (with "triples" (n_hyp, 3)) or a list of them, in ONE device call:
+        dict(s) with t12 (n_hyp, 13) float32 = R12 row-major, t12, s12; n_inliers (n_hyp); inlier_bits (n_hyp, (n + 31) // 32)."""
+        single = isinstance(problems, dict)
+        plist = [problems] if single else list(problems)
+        m = len(plist)
+        P = (Sim3RansacProblem * m)()
+        R = (Sim3RansacResult * m)()
+        keep, outs = [], []
+        for i, pr in enumerate(plist):
+            k = {"x1": np.ascontiguousarray(pr["x1"], np.float32).reshape(-1, 3), "x2": np.ascontiguousarray(pr["x2"], np.float32).reshape(-1, 3),
+                 "max_err1": np.ascontiguousarray(pr["max_err1"], np.float32), "max_err2": np.ascontiguousarray(pr["max_err2"], np.float32),
+                 "triples": np.ascontiguousarray(pr["triples"], np.int32).reshape(-1, 3)}
+            n, nh = len(k["max_err1"]), len(k["triples"])
+            if len(k["x1"]) != n or len(k["x2"]) != n or len(k["max_err2"]) != n:
+                raise SlamitError("Sim3Solver.evaluate: x1 / x2 / max_err arrays do not have the same length")
+            q = P[i]
+            q.n, q.n_hyp, q.fix_scale = n, nh, int(pr["fix_scale"])
+            for key, a in k.items():
+                setattr(q, key, a.ctypes.data)
+            q.intr1 = (C.c_float * 4)(*[float(v) for v in pr["intr1"]])
+            q.intr2 = (C.c_float * 4)(*[float(v) for v in pr["intr2"]])
+            o = {"t12": np.zeros((nh, 13), np.float32), "n_inliers": np.zeros(nh, np.int32)}
+            R[i].t12, R[i].n_inliers = o["t12"].ctypes.data, o["n_inliers"].ctypes.data
+            if want_bits:
+                o["inlier_bits"] = np.zeros((nh, (n + 31) // 32), np.uint32)
+                R[i].inlier_bits = o["inlier_bits"].ctypes.data
+            keep.append(k)
+            outs.append(o)
+        _check(lib().slamit_sim3_ransac_batch(device, m, P, R), "slamit_sim3_ransac_batch")
+        del keep
+        return outs[0] if single else outs
+
+    @staticmethod
+    def EvaluateAll(solvers, device=0):
+        """Every candidate's hypotheses in one launch (what LoopClosing::ComputeSim3 costs)."""
+        todo = [s for s in solvers if s.counts is None]
+        res = Sim3Solver.evaluate([dict(s.problem, triples=s.triples) for s in todo], device) if todo else []
+        for s, r in zip(todo, res):
+            s.t12, s.counts, s.bits = r["t12"], r["n_inliers"], r["inlier_bits"]
+
+    def flags(self, h):
+        """mvbInliersi of hypothesis h as a bool array (N)."""
+        b = np.unpackbits(self.bits[h].view(np.uint8), bitorder="little")[:self.N]
+        return b.astype(bool)
+
+    @staticmethod
+    def scan(counts, first, nIterations, mnIterations, mRansacMaxIts, mnBestInliers, mRansacMinInliers):
+        """The loop of iterate() (:158-204) over counts[first:]: -> (accepted index or -1, best index or -1 if never updated,
+        mnBestInliers, mnIterations, bNoMore).  The best is replaced on >=, the return is on a strict >."""
+        best, k, cur = -1, first, 0
+        while mnIterations < mRansacMaxIts and cur < nIterations:
+            cur += 1
+            mnIterations += 1
+            c = int(counts[k])
+            k += 1
+            if c >= mnBestInliers:
+                mnBestInliers, best = c, k - 1
+                if c > mRansacMinInliers:
+                    return k - 1, best, mnBestInliers, mnIterations, False
+        return -1, best, mnBestInliers, mnIterations, mnIterations >= mRansacMaxIts
+
+    def iterate(self, nIterations):
+        """-> (T12 (4, 4) float32 or None, bNoMore, vbInliers (N) bool, nInliers)."""
+        vb = np.zeros(self.N, bool)
+        if self.N < self.mRansacMinInliers or self.N < 3:   # (the reference cannot sample three of fewer than three either)
+            return None, True, vb, 0
+        if self.counts is None:
+            Sim3Solver.EvaluateAll([self], self.device)
+        acc, best, self.mnBestInliers, self.mnIterations, no_more = self.scan(
+            self.counts, self.mnIterations, nIterations, self.mnIterations, self.mRansacMaxIts, self.mnBestInliers, self.mRansacMinInliers)
+        if best >= 0:
+            self.best = best
+        if acc < 0:
+            return None, no_more, vb, 0
+        self.accepted = acc
+        return self.T12(acc), False, self.flags(acc), int(self.counts[acc])
+
+    def find(self):
+        T, _, vb, n = self.iterate(self.mRansacMaxIts)
+        return T, vb, n
+
+    def T12(self, h):
+        """mT12i of hypothesis h: [s R | t; 0 0 0 1] in float32."""
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = self.t12[h, 12] * self.t12[h, :9].reshape(3, 3)
+        T[:3, 3] = self.t12[h, 9:12]
+        return T
+
+    def GetEstimatedRotation(self):
+        return self.t12[self.best, :9].reshape(3, 3).copy()
+
+    def GetEstimatedTranslation(self):
+        return self.t12[self.best, 9:12].copy()
+
+    def GetEstimatedScale(self):
+        return float(self.t12[self.best, 12])

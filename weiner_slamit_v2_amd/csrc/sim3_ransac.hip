@@ -1,0 +1,162 @@
+// sim3_ransac.hip — Sim3Solver's hypothesis evaluation on the GPU (include/slamit.h, slamit_sim3_ransac*).
+//
+// Reference: ORB_SLAM2/src/Sim3Solver.cc.  iterate() (:140-207) draws three correspondences, ComputeSim3 (:226-337) solves Horn's
+// closed form on them, CheckInliers (:340-364) projects all N correspondences both ways and counts those under their chi-square
+// bounds.  Every (candidate keyframe, hypothesis) pair is independent: ONE WAVEFRONT takes one pair.  The closed form (sim3_horn.h)
+// runs wave-uniform -- all 64 lanes compute the same 13 numbers, which costs nothing a lane would otherwise use -- then the lanes
+// stride over the correspondences, a ballot builds the inlier words and its popcount the count.  No LDS, no atomics, no
+// cross-wave traffic; a batch of candidates is one launch.  The sampling and iterate()'s sequential acceptance scan stay on
+// the host (shim/Sim3Solver.h, api.Sim3Solver).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/slamit.h"
+#include "sim3_horn.h"
+#include "slamit_internal.h"
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define S3R_G __attribute__((address_space(1)))
+#else
+#define S3R_G
+#endif
+
+struct Sim3RansacProb {
+    int32_t n, n_hyp, fix_scale, words;   // words = (n + 31) / 32
+    float intr1[4], intr2[4];
+    const S3R_G float* x1; const S3R_G float* x2; const S3R_G float* e1; const S3R_G float* e2;
+    const S3R_G int32_t* triples;
+    S3R_G float* t12; S3R_G int32_t* counts; S3R_G uint32_t* bits;
+};
+
+// grid (ceil(max n_hyp / 4), problems), 256 threads: wave w of block b takes hypothesis 4 b + w of problem blockIdx.y.
+// The host has checked every triple index against [0, n).
+__global__ __launch_bounds__(256) void sim3_ransac_kernel(const Sim3RansacProb* __restrict__ probs) {
+    const Sim3RansacProb P = probs[blockIdx.y];
+    const int lane = threadIdx.x & 63;
+    const int h = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    const int n = P.n;
+    if (h >= P.n_hyp) return;
+    float P1[3][3], P2[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int idx = P.triples[3 * h + k];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { P1[k][a] = P.x1[3 * idx + a]; P2[k][a] = P.x2[3 * idx + a]; }
+    }
+    Sim3Hyp H;
+    sim3h_solve(P1, P2, P.fix_scale, H);
+    const float K1[4] = {P.intr1[0], P.intr1[1], P.intr1[2], P.intr1[3]}, K2[4] = {P.intr2[0], P.intr2[1], P.intr2[2], P.intr2[3]};
+    int count = 0;
+    S3R_G uint32_t* bits = P.bits + (size_t)h * P.words;
+    for (int base = 0; base < n; base += 64) {
+        const int i = base + lane;
+        bool in = false;
+        if (i < n) {
+            const float X1[3] = {P.x1[3 * i], P.x1[3 * i + 1], P.x1[3 * i + 2]}, X2[3] = {P.x2[3 * i], P.x2[3 * i + 1], P.x2[3 * i + 2]};
+            float err1, err2;
+            sim3h_errors(H, X1, X2, K1, K2, &err1, &err2);
+            in = err1 < P.e1[i] && err2 < P.e2[i];   // NaN: an outlier
+        }
+        const unsigned long long m = __ballot(in);
+        count += __popcll(m);
+        const int w = base >> 5;
+        if (lane == 0) bits[w] = (uint32_t)m;
+        if (lane == 1 && w + 1 < P.words) bits[w + 1] = (uint32_t)(m >> 32);
+    }
+    if (lane < 13) {
+        float v = H.s;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) v = lane == k ? H.R[k] : v;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v = lane == 9 + k ? H.t[k] : v;
+        P.t12[13 * (size_t)h + lane] = v;
+    }
+    if (lane == 0) P.counts[h] = count;
+}
+
+extern "C" {
+
+int slamit_sim3_ransac_batch(int device, int nprob, const slamit_sim3_ransac_problem* probs, slamit_sim3_ransac_result* results) {
+    const char* const where = "slamit_sim3_ransac_batch";
+    if (nprob < 0 || (nprob && (!probs || !results))) return slamit_fail(SLAMIT_ERR_ARG, "slamit_sim3_ransac_batch: bad argument");
+    if (nprob == 0) return SLAMIT_OK;
+    int max_hyp = 0;
+    for (int f = 0; f < nprob; ++f) {
+        const slamit_sim3_ransac_problem& P = probs[f];
+        if (P.n < 0 || P.n_hyp < 0) return slamit_fail(SLAMIT_ERR_ARG, "slamit_sim3_ransac_batch: negative count");
+        if (P.n > SLAMIT_SIM3_RANSAC_MAX_N) return slamit_fail(SLAMIT_ERR_ARG, "slamit_sim3_ransac_batch: more than SLAMIT_SIM3_RANSAC_MAX_N correspondences");
+        if (P.n_hyp > SLAMIT_SIM3_RANSAC_MAX_HYP) return slamit_fail(SLAMIT_ERR_ARG, "slamit_sim3_ransac_batch: more than SLAMIT_SIM3_RANSAC_MAX_HYP hypotheses");
+        if (P.n == 0 || P.n_hyp == 0) continue;   // nothing to evaluate, nothing written
+        if (!P.x1 || !P.x2 || !P.max_err1 || !P.max_err2 || !P.triples || !results[f].t12 || !results[f].n_inliers)
+            return slamit_fail(SLAMIT_ERR_ARG, "slamit_sim3_ransac_batch: null array");
+        for (int k = 0; k < 3 * P.n_hyp; ++k)
+            if (P.triples[k] < 0 || P.triples[k] >= P.n) return slamit_fail(SLAMIT_ERR_ARG, "slamit_sim3_ransac_batch: triple index outside [0, n)");
+        max_hyp = std::max(max_hyp, (int)P.n_hyp);
+    }
+    if (max_hyp == 0) return SLAMIT_OK;
+    SLAMIT_USE_DEVICE(device);
+    // [per problem: x1 x2 max_err1 max_err2 triples | records] go up; [per problem: t12 counts (bits when asked for)] come down; the bits
+    // nobody asked for stay on the device
+    struct Spans { StageSpan<float> x1, x2, e1, e2, t12; StageSpan<int32_t> triples, counts; StageSpan<uint32_t> bits; int hyp, words; };
+    StageLayout L;
+    std::vector<Spans> sp(nprob);
+    for (int f = 0; f < nprob; ++f) {
+        const slamit_sim3_ransac_problem& P = probs[f];
+        Spans& s = sp[f];
+        s.hyp = (P.n == 0) ? 0 : P.n_hyp;
+        s.words = (P.n + 31) / 32;
+        const size_t n = s.hyp ? (size_t)P.n : 0;
+        s.x1 = L.take<float>(3 * n, 16); s.x2 = L.take<float>(3 * n, 16); s.e1 = L.take<float>(n, 16); s.e2 = L.take<float>(n, 16);
+        s.triples = L.take<int32_t>(3 * (size_t)s.hyp, 16);
+    }
+    const StageSpan<Sim3RansacProb> recs = L.take<Sim3RansacProb>(nprob, 16);
+    L.end_inputs();
+    for (int f = 0; f < nprob; ++f) {
+        Spans& s = sp[f];
+        s.t12 = L.take<float>(13 * (size_t)s.hyp, 16); s.counts = L.take<int32_t>(s.hyp, 16);
+        if (results[f].inlier_bits) s.bits = L.take<uint32_t>((size_t)s.hyp * s.words, 16);
+    }
+    L.end_outputs();
+    for (int f = 0; f < nprob; ++f)
+        if (!results[f].inlier_bits) sp[f].bits = L.take<uint32_t>((size_t)sp[f].hyp * sp[f].words, 16);
+    static thread_local SlamitScratch S;
+    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
+    for (int f = 0; f < nprob; ++f) {
+        const slamit_sim3_ransac_problem& P = probs[f];
+        const Spans& s = sp[f];
+        if (s.hyp) {
+            memcpy(s.x1.at(S.host), P.x1, s.x1.bytes()); memcpy(s.x2.at(S.host), P.x2, s.x2.bytes());
+            memcpy(s.e1.at(S.host), P.max_err1, s.e1.bytes()); memcpy(s.e2.at(S.host), P.max_err2, s.e2.bytes());
+            memcpy(s.triples.at(S.host), P.triples, s.triples.bytes());
+        }
+        Sim3RansacProb& Q = recs.at(S.host)[f];
+        memset(&Q, 0, sizeof(Q));
+        Q.n = P.n; Q.n_hyp = s.hyp; Q.fix_scale = P.fix_scale; Q.words = s.words;
+        memcpy(Q.intr1, P.intr1, sizeof(Q.intr1)); memcpy(Q.intr2, P.intr2, sizeof(Q.intr2));
+        typedef const S3R_G float* cgf;
+        Q.x1 = (cgf)s.x1.at(S.dev); Q.x2 = (cgf)s.x2.at(S.dev); Q.e1 = (cgf)s.e1.at(S.dev); Q.e2 = (cgf)s.e2.at(S.dev);
+        Q.triples = (const S3R_G int32_t*)s.triples.at(S.dev);
+        Q.t12 = (S3R_G float*)s.t12.at(S.dev); Q.counts = (S3R_G int32_t*)s.counts.at(S.dev); Q.bits = (S3R_G uint32_t*)s.bits.at(S.dev);
+    }
+    HIP_TRY_AT(where, slamit_stage_upload(S, L));
+    hipLaunchKernelGGL(sim3_ransac_kernel, dim3((max_hyp + 3) / 4, nprob), dim3(256), 0, S.st, recs.at(S.dev));
+    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
+    for (int f = 0; f < nprob; ++f) {
+        const Spans& s = sp[f];
+        if (!s.hyp) continue;
+        memcpy(results[f].t12, s.t12.at(S.host), s.t12.bytes());
+        memcpy(results[f].n_inliers, s.counts.at(S.host), s.counts.bytes());
+        if (results[f].inlier_bits) memcpy(results[f].inlier_bits, s.bits.at(S.host), s.bits.bytes());
+    }
+    return SLAMIT_OK;
+}
+
+int slamit_sim3_ransac(int device, const slamit_sim3_ransac_problem* prob, slamit_sim3_ransac_result* res) {
+    return slamit_sim3_ransac_batch(device, 1, prob, res);
+}
+
+}  // extern "C"

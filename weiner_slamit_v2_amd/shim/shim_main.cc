@@ -12,6 +12,7 @@
 //     shim_test bow <problem.bin> <out.bin>
 //     shim_test sim3 <problem.bin> <out.bin>
 //     shim_test osim3 <problem.bin> <out.bin>
+//     shim_test sim3solver <problem.bin> <out.bin>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -26,6 +27,7 @@
 #include "ORBmatcher.h"
 #include "Optimizer.h"
 #include "FrameOps.h"
+#include "Sim3Solver.h"
 
 using namespace ORB_SLAM2;
 
@@ -514,7 +516,7 @@ struct MockFuseKF {
     cv::Mat R, t, O, mDescriptors, mK;
     float fx, fy, cx, cy, mfLogScaleFactor;
     float mnMinX, mnMinY, mnMaxX, mnMaxY, mfGridElementWidthInv, mfGridElementHeightInv;
-    std::vector<float> mvScaleFactors, mvInvLevelSigma2, mvuRight;
+    std::vector<float> mvScaleFactors, mvInvLevelSigma2, mvLevelSigma2, mvuRight;
     std::vector<cv::KeyPoint> mvKeysUn;
     std::vector<MockFusePoint*> mps;
     cv::Mat GetRotation() { return R.clone(); }
@@ -848,6 +850,87 @@ static int run_osim3(int argc, char** argv) {
     return 0;
 }
 
+// ---- Sim3Solver through the template: the candidates of one loop query, one EvaluateAll -----------------------------------
+// problem.bin: int32 nsolvers nrand ; uint32 rand[nrand] (RandomInt(lo, hi) = lo + rand[k++] % (hi - lo + 1), one stream for all
+//   solvers in order: each constructor draws for the default parameters, each SetRansacParameters draws again) ; per solver:
+//   int32 n lead fix min_inliers max_its ; float K1[4] K2[4] x1[3n] x2[3n] sigma2_1[n] sigma2_2[n]
+//   (keyframe 1 holds `lead` keypoints without a match in front of the n matched ones; both keyframes sit at the identity pose)
+// out.bin: int32 status ; per solver: int32 accepted n_inliers ncalls max_its ; float T12[16] R[9] t[3] s ; u8 vbInliers[lead + n]
+static std::vector<uint32_t> g_script;
+static size_t g_script_pos = 0;
+static int scripted_random_int(int lo, int hi) {
+    const uint32_t v = g_script_pos < g_script.size() ? g_script[g_script_pos] : 0u;
+    ++g_script_pos;
+    return lo + (int)(v % (uint32_t)(hi - lo + 1));
+}
+static int run_sim3solver(int argc, char** argv) {
+    if (argc < 4) return 2;
+    std::vector<unsigned char> raw = slurp(argv[2]);
+    Reader Rd{raw.data()};
+    const int ns = Rd.get<int>(), nrand = Rd.get<int>();
+    { const uint32_t* r = Rd.arr<uint32_t>(nrand); g_script.assign(r, r + nrand); }
+    sim3solver::RandomInt() = scripted_random_int;
+    typedef Sim3Solver<MockFuseKF, MockFusePoint> Solver;
+    std::vector<MockFuseKF> kfs(2 * (size_t)ns);
+    std::vector<std::vector<MockFusePoint> > pts(2 * (size_t)ns);
+    std::vector<Solver*> solvers;
+    std::vector<int> total(ns);
+    for (int k = 0; k < ns; ++k) {
+        const int n = Rd.get<int>(), ld = Rd.get<int>(), fix = Rd.get<int>(), minInl = Rd.get<int>(), maxIts = Rd.get<int>();
+        const float* K[2]; K[0] = Rd.arr<float>(4); K[1] = Rd.arr<float>(4);
+        const float* x[2]; x[0] = Rd.arr<float>(3 * (size_t)n); x[1] = Rd.arr<float>(3 * (size_t)n);
+        const float* sg[2]; sg[0] = Rd.arr<float>(n); sg[1] = Rd.arr<float>(n);
+        total[k] = ld + n;
+        for (int c = 0; c < 2; ++c) {
+            MockFuseKF& KF = kfs[2 * k + c];
+            KF.mK = cv::Mat::zeros(3, 3, CV_32F);
+            KF.mK.at<float>(0, 0) = K[c][0]; KF.mK.at<float>(1, 1) = K[c][1]; KF.mK.at<float>(0, 2) = K[c][2]; KF.mK.at<float>(1, 2) = K[c][3]; KF.mK.at<float>(2, 2) = 1.f;
+            KF.R = cv::Mat::zeros(3, 3, CV_32F); KF.t = cv::Mat::zeros(3, 1, CV_32F);
+            for (int r = 0; r < 3; ++r) KF.R.at<float>(r, r) = 1.f;
+            const int off = c == 0 ? ld : 0;
+            KF.mvKeysUn.resize(off + n); KF.mps.assign(off + n, (MockFusePoint*)0); KF.mvLevelSigma2.assign(sg[c], sg[c] + n);
+            pts[2 * k + c].resize(n);
+            for (int i = 0; i < n; ++i) {
+                MockFusePoint& p = pts[2 * k + c][i];
+                p.id = i; p.idxInKF2 = off + i; p.pos = mat_from(x[c] + 3 * (size_t)i, 3);
+                KF.mvKeysUn[off + i] = cv::KeyPoint(0.f, 0.f, 31.f, -1.f, 0, i);   // one sigma entry per keypoint keeps sigma2 exact
+                KF.mps[off + i] = &p;
+            }
+        }
+        std::vector<MockFusePoint*> vpMatched12(ld + n, (MockFusePoint*)0);
+        for (int i = 0; i < n; ++i) vpMatched12[ld + i] = &pts[2 * k + 1][i];
+        Solver* s = new Solver(&kfs[2 * k], &kfs[2 * k + 1], vpMatched12, fix != 0);
+        s->SetRansacParameters(0.99, minInl, maxIts);   // LoopClosing.cc:276
+        solvers.push_back(s);
+    }
+    int status = Solver::EvaluateAll(solvers);   // every candidate in one launch
+    if (status != 0) fprintf(stderr, "sim3solver failed: %s\n", slamit_last_error());
+    FILE* f = fopen(argv[3], "wb");
+    fwrite(&status, 4, 1, f);
+    for (int k = 0; k < ns && status == 0; ++k) {
+        Solver* s = solvers[k];
+        std::vector<bool> vbInliers(total[k], false);
+        int nInliers = 0, ncalls = 0;
+        bool bNoMore = false;
+        cv::Mat T;
+        while (T.empty() && !bNoMore) { T = s->iterate(5, bNoMore, vbInliers, nInliers); ++ncalls; }   // LoopClosing.cc:311
+        const int acc = s->AcceptedHypothesis(), its = s->GetRansacMaxIts();
+        fwrite(&acc, 4, 1, f); fwrite(&nInliers, 4, 1, f); fwrite(&ncalls, 4, 1, f); fwrite(&its, 4, 1, f);
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { const float v = T.empty() ? 0.f : T.at<float>(r, c); fwrite(&v, 4, 1, f); }
+        cv::Mat Re = s->GetEstimatedRotation(), te = s->GetEstimatedTranslation();
+        const float se = s->GetEstimatedScale();
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) fwrite(&Re.at<float>(r, c), 4, 1, f);
+        for (int r = 0; r < 3; ++r) fwrite(&te.at<float>(r, 0), 4, 1, f);
+        fwrite(&se, 4, 1, f);
+        for (int i = 0; i < total[k]; ++i) { const unsigned char b = vbInliers[i]; fwrite(&b, 1, 1, f); }
+        printf("solver %d: accepted hypothesis %d, %d inliers, T12 row 0 = %g %g %g %g\n", k, acc, nInliers, T.empty() ? 0.f : T.at<float>(0, 0),
+               T.empty() ? 0.f : T.at<float>(0, 1), T.empty() ? 0.f : T.at<float>(0, 2), T.empty() ? 0.f : T.at<float>(0, 3));
+    }
+    fclose(f);
+    for (size_t k = 0; k < solvers.size(); ++k) delete solvers[k];
+    return status == 0 ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     std::string mode = argv[1];
@@ -862,5 +945,6 @@ int main(int argc, char** argv) {
     if (mode == "bow") return run_bow(argc, argv);
     if (mode == "sim3") return run_sim3(argc, argv);
     if (mode == "osim3") return run_osim3(argc, argv);
+    if (mode == "sim3solver") return run_sim3solver(argc, argv);
     return 2;
 }

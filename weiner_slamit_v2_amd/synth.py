@@ -411,6 +411,42 @@ def synth_sim3(n=200, outlier_frac=0.15, seed=0, perturb=0.03, fix_scale=False, 
                 th2=10.0, fix_scale=int(fix_scale), true=dict(R=R, t=t, s=s_true, bad=bad))
 
 
+def synth_sim3_ransac(n=200, outlier_frac=0.3, seed=0, noise_px=0.5, fix_scale=False):
+    """What the Sim3Solver constructor gathers for one loop candidate (Sim3Solver.cc:62-109): the same physical points as map points
+    of two keyframes, each in its own camera frame (x1 = mvX3Dc1, x2 = mvX3Dc2, float32), related by a known similarity
+    x1 = s R x2 + t.  Each keyframe's estimate of a point is off by about noise_px pixels of its own image (three times that in
+    depth); a fraction outlier_frac of the pairs are wrong associations (x2 is another point).  Every point carries the octave of
+    its keypoint in each image: sigma2_1 / sigma2_2 = mvLevelSigma2[octave] and max_err1 / max_err2 = (float)(size_t)(9.210 sigma2),
+    the truncated bounds of mvnMaxError1/2.  obs1 / obs2 / inv_sigma2_1 / inv_sigma2_2 are the keypoints, so that the accepted
+    similarity can go on to OptimizeSim3.  Layout of slamit_sim3_ransac_problem (without triples)."""
+    rs = np.random.RandomState(11000 + seed)
+    f32 = np.float32
+    intr1 = np.array([517.3, 516.5, 318.6, 255.3], f32)
+    intr2 = np.array([520.9, 521.0, 325.1, 249.7], f32)
+    s_true = 1.0 if fix_scale else 1.08
+    R, t = se3_exp(np.array([0.05, -0.08, 0.03, 0.4, -0.1, 0.2]))
+    X2 = np.stack([rs.uniform(-2.5, 2.5, n), rs.uniform(-1.8, 1.8, n), rs.uniform(2.5, 9.0, n)], 1)
+    X1 = s_true * (X2 @ R.T) + t
+    x1 = X1 + rs.normal(0, noise_px, (n, 3)) * X1[:, 2:3] / float(intr1[0]) * np.array([1.0, 1.0, 3.0])
+    x2 = X2 + rs.normal(0, noise_px, (n, 3)) * X2[:, 2:3] / float(intr2[0]) * np.array([1.0, 1.0, 3.0])
+    bad = rs.rand(n) < outlier_frac
+    nb = int(bad.sum())
+    x2[bad] = np.stack([rs.uniform(-2.5, 2.5, nb), rs.uniform(-1.8, 1.8, nb), rs.uniform(2.5, 9.0, nb)], 1)
+    x1, x2 = x1.astype(f32), x2.astype(f32)
+    scale_f = f32(1.2) ** np.arange(8, dtype=f32)
+    sigma2 = (scale_f * scale_f).astype(f32)
+    lv1, lv2 = rs.randint(0, 8, n), rs.randint(0, 8, n)
+    s1, s2 = sigma2[lv1], sigma2[lv2]
+    d1, d2 = x1.astype(np.float64), x2.astype(np.float64)
+    obs1 = np.stack([intr1[0] * d1[:, 0] / d1[:, 2] + intr1[2], intr1[1] * d1[:, 1] / d1[:, 2] + intr1[3]], 1) + rs.normal(0, noise_px, (n, 2))
+    obs2 = np.stack([intr2[0] * d2[:, 0] / d2[:, 2] + intr2[2], intr2[1] * d2[:, 1] / d2[:, 2] + intr2[3]], 1) + rs.normal(0, noise_px, (n, 2))
+    return dict(n=n, x1=x1, x2=x2, sigma2_1=s1, sigma2_2=s2,
+                max_err1=np.floor(9.210 * s1.astype(np.float64)).astype(f32), max_err2=np.floor(9.210 * s2.astype(np.float64)).astype(f32),
+                intr1=intr1, intr2=intr2, fix_scale=int(fix_scale), obs1=obs1.astype(f32), obs2=obs2.astype(f32),
+                inv_sigma2_1=(f32(1) / s1).astype(f32), inv_sigma2_2=(f32(1) / s2).astype(f32),
+                true=dict(R=R, t=t, s=s_true, bad=bad))
+
+
 def synth_map(n_kf, n_pt, obs_per_pt, n_fixed, seed, stereo_frac=0.0, loop=True, outlier_frac=0.03, baseline=0.08):
     """A map-sized BA window (slamit_ba_problem layout, as synth_ba): n_kf cameras on a circle of radius 2 in the x-z plane, each looking
     outward, and n_pt points on a cylinder of radius 6 around it.  loop=True: the trajectory closes (keyframe k at 2 pi k / n_kf), so the
