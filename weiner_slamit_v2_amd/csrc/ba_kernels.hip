@@ -30,14 +30,15 @@
 #include <float.h>
 #include <stdint.h>
 
-#define BA_GLOBAL_POINTERS   // BaWin members are global-address-space pointers in this file's device code
+#include "slamit_internal.h"
+#define BA_GLOBAL_POINTERS   // BaWin members are SLAMIT_GLOBAL pointers in this file's device code
 #include "ba_types.h"
+#include "lm_step.h"
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
-// A pointer read out of BaWin (a struct in HBM) is a GENERIC pointer to the compiler: every access through it is a
-// flat_load / flat_store, which also counts in lgkmcnt -- so each LDS wait of a software pipeline waits for the
-// prefetched HBM data as well.  The hot kernels cast their matrices to the global address space once.
-typedef __attribute__((address_space(1))) double gdouble;
+// The hot kernels cast their matrices to the global address space once (SLAMIT_GLOBAL, slamit_internal.h: each LDS wait of a
+// software pipeline would otherwise wait for the prefetched HBM data as well).
+typedef SLAMIT_GLOBAL double gdouble;
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
 #include "se3_device.h"
@@ -571,7 +572,7 @@ __device__ __forceinline__ void schur_body(const BaWin& W, const BaState* st, in
     for (int j = 0; j < 4; ++j) acc[j] = (double4_t){0, 0, 0, 0};
     // software pipeline: the next slab is fetched into registers while the current one feeds the MFMAs; 16 bytes per lane and load
     // (a slab row is 32 doubles = 16 lanes; k ranges are multiples of BA_KC, Kpad of BA_KC * BA_SPLITS, so every address is 16-byte aligned)
-    typedef __attribute__((address_space(1))) double2_t gdouble2s;
+    typedef SLAMIT_GLOBAL double2_t gdouble2s;
     const gdouble2s* srcA[4];
     const gdouble2s* srcB[4];
     {
@@ -950,7 +951,7 @@ __device__ __forceinline__ void ldlt_band_solve(const BaWin& W, BaState* st, dou
     if (tid == 0) { st->dbg[0] = tprev; st->dbg[1] = __builtin_amdgcn_s_memrealtime(); }
 #endif
     {   // the band arrives in its LDS layout (k_schur_reduce wrote it that way): a straight copy, 16 bytes per lane and load
-        typedef __attribute__((address_space(1))) double2_t gdouble2;
+        typedef SLAMIT_GLOBAL double2_t gdouble2;
         const gdouble2* src = (const gdouble2*)W.Sb;
         double2_t* dst = reinterpret_cast<double2_t*>(Ab);
         const int cnt = ((n + 1) * RS) >> 1;   // RS is even
@@ -1751,31 +1752,15 @@ __global__ __launch_bounds__(256) void k_decide(BaWin* wins) {
     if (tid == 0) {
         if (!st->ok2) tempChi = DBL_MAX;
         st->tempChi = tempChi;
-        double rho = (st->currentChi - tempChi) / (scale + 1e-3);
-        const bool good = rho > 0 && fabs(tempChi) <= DBL_MAX;
-        if (good) {
-            double alpha = 1. - pow((2 * rho - 1), 3);
-            alpha = fmin(alpha, 2. / 3.);
-            const double sf = fmax(1. / 3., alpha);
-            st->lambda *= sf;
-            st->ni = 2;
-            st->currentChi = tempChi;
-        } else {
-            st->lambda *= st->ni;
-            st->ni *= 2;
-        }
+        bool good;
+        const double rho = lm_accept(st->currentChi, tempChi, scale, st->lambda, st->ni, good);   // lm_step.h
         s_reject = !good;
         st->qmax += 1;
-        const bool again = rho < 0 && st->qmax < 10;
-        if (!again) {  // the iteration is over
+        if (!lm_try_again(rho, st->qmax)) {  // the iteration is over
             const int s = st->stage, it = st->it;
             if (it < BA_MAX_ITS) { st->chi2[s][it] = tempChi; st->lam[s][it] = st->lambda; st->trials[s][it] = st->qmax; }
             st->n_its[s] = it + 1;
-            bool terminate = st->qmax == 10 || rho == 0;
-            if (!terminate) {
-                if ((st->iniChi - st->currentChi) * 1e3 < st->iniChi) st->nBad += 1; else st->nBad = 0;
-                if (st->nBad >= 3) terminate = true;
-            }
+            const bool terminate = lm_stop(st->qmax, rho, st->iniChi, st->currentChi, st->nBad);
             st->it = it + 1;
             st->need_linearize = 1;
             if (terminate || st->it >= st->max_it) st->done = 1;

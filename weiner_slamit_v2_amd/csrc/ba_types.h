@@ -79,15 +79,13 @@ struct BaState {
     unsigned long long dbg[8];  // diagnostic stamps (s_memtime / s_memrealtime); written only when BA_DIAG_STAMPS is defined
 };
 
-// One window.  All pointers are device addresses inside the handle's slabs.  In device code they carry the global
-// address space: a plain pointer read out of a struct in memory is GENERIC to the compiler, and every access through it
-// a flat_load (slower to issue, and it counts in lgkmcnt, so LDS waits also wait for outstanding HBM loads).
-// (Only the kernel translation unit asks for it: host code that fills the struct is also parsed in the device pass.)
-#if defined(BA_GLOBAL_POINTERS) && defined(__HIP_DEVICE_COMPILE__)
-#define BA_G __attribute__((address_space(1)))
+// One window.  All pointers are device addresses inside the handle's slabs.  In the kernels they carry SLAMIT_GLOBAL
+// (slamit_internal.h).  Only the kernel translation unit asks for it, by defining BA_GLOBAL_POINTERS after including that header:
+// ba_api.hip fills the struct from plain pointers in code the device pass parses too, and ba_plan.cc is plain C++.
+#if defined(BA_GLOBAL_POINTERS)
+#define BA_G SLAMIT_GLOBAL
 #else
 #define BA_G
-
 #endif
 struct BaWin {
     int32_t n_kf, n_pt, n_edge, n_free;

@@ -2,6 +2,8 @@
 // Plain C++17 (no HIP): slamit_pose_optimize_batch / slamit_sim3_optimize_batch pack, point the kernel's record at and unpack
 // these spans, and the CPU test (tests/test_stage_layout.py) checks them.  A batch is [doubles of every problem | ints |
 // records | flags of every problem]; the doubles are contiguous, so a problem costs exactly the sizes quoted below.
+// This is the host half of what the two entry points share; the device half is lm_block.h (the workgroup's Levenberg driver) over
+// lm_step.h (its scalar rules, also CPU-tested: tests/test_lm_step.py).
 #ifndef SLAMIT_LM_LAYOUT_H
 #define SLAMIT_LM_LAYOUT_H
 #include <stdint.h>

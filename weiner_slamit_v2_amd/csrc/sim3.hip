@@ -7,7 +7,9 @@
 // delta 1e-9, through oplus = Sim3(update) * estimate); the same is done here: the 14 perturbed similarities and their
 // inverses are built once per iteration, every lane evaluates its pairs at all of them.  The system is one 7x7 block, so
 // the whole schedule — 5 iterations, the chi2 > th2 pruning of pairs, 10 (or 5) more iterations, the inlier count —
-// runs inside ONE workgroup per problem with no host round trip; a batch is one launch.  Reductions are fixed-order.
+// runs inside ONE workgroup per problem with no host round trip; a batch is one launch.  This file holds the pairs (Sim3Model:
+// errors, the perturbed similarities, normal-equation partials, oplus) and the two stages; the Levenberg iterations themselves are
+// lm_block.h's lm_block_run<7, 8>, shared with pose.hip, over the rules of lm_step.h.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <stdint.h>
@@ -17,37 +19,24 @@
 #include <vector>
 
 #include "../../include/slamit.h"
+#include "lm_block.h"
 #include "lm_layout.h"
 #include "se3_device.h"
 #include "slamit_internal.h"
 
-// Device-side record of one problem (pointers into the batch slabs; global address space in device code so that the
-// accesses are global_load, not flat_load -- see ba_types.h).
-#if defined(__HIP_DEVICE_COMPILE__)
-#define SIM3_G __attribute__((address_space(1)))
-#else
-#define SIM3_G
-#endif
+// Device-side record of one problem (pointers into the batch slabs)
 struct Sim3Prob {
     int32_t n, fix_scale;
     double intr1[4], intr2[4], S0[8], th2;   // S = q(x, y, z, w), t, s
-    const SIM3_G double* p1; const SIM3_G double* p2; const SIM3_G double* o1; const SIM3_G double* o2;
-    const SIM3_G double* w1; const SIM3_G double* w2;
-    SIM3_G double* chi12; SIM3_G double* chi21;      // n each: chi2 of the last evaluated trial
-    SIM3_G uint8_t* inlier;                          // n out
-    SIM3_G double* out;                              // 16: R (9), t (3), s, chi2[2], pad
-    SIM3_G int32_t* ints;                            // 4: n_inliers, n_its[2], returned-at-the-10-pair-test flag
+    const SLAMIT_GLOBAL double* p1; const SLAMIT_GLOBAL double* p2; const SLAMIT_GLOBAL double* o1; const SLAMIT_GLOBAL double* o2;
+    const SLAMIT_GLOBAL double* w1; const SLAMIT_GLOBAL double* w2;
+    SLAMIT_GLOBAL double* chi12; SLAMIT_GLOBAL double* chi21;      // n each: chi2 of the last evaluated trial
+    SLAMIT_GLOBAL uint8_t* inlier;                          // n out
+    SLAMIT_GLOBAL double* out;                              // 16: R (9), t (3), s, chi2[2], pad
+    SLAMIT_GLOBAL int32_t* ints;                            // 4: n_inliers, n_its[2], returned-at-the-10-pair-test flag
 };
 
 namespace {
-
-__device__ __forceinline__ double block_sum(double v, double* sh) {  // 256 threads, result in every thread
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
 
 __device__ __forceinline__ void quat_mul(const double* a, const double* b, double* r) {   // Eigen quaternion product, (x, y, z, w)
     r[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
@@ -150,40 +139,77 @@ __device__ double sim3_errors(const Sim3Prob& P, const double* S, const uint8_t*
         P.chi12[k] = c12; P.chi21[k] = c21;
         part += huber(c12, delta, dsqr) + huber(c21, delta, dsqr);
     }
-    return block_sum(part, sh);
+    return lm_block_sum(part, sh);
 }
 
-// 7x7 LDLt without pivoting (H + lambda I) x = b; false on a zero pivot
-__device__ bool solve7(const double* H, double lambda, const double* b, double* x) {
-    double A[49];
-    for (int i = 0; i < 49; ++i) A[i] = H[i] + (i % 8 == 0 ? lambda : 0.0);
-    for (int j = 0; j < 7; ++j) {
-        double d = A[8 * j];
-        for (int k = 0; k < j; ++k) d -= A[7 * j + k] * A[7 * j + k] * A[8 * k];
-        if (d == 0.0 || !(fabs(d) <= DBL_MAX)) return false;
-        A[8 * j] = d;
-        for (int i = j + 1; i < 7; ++i) {
-            double s = A[7 * i + j];
-            for (int k = 0; k < j; ++k) s -= A[7 * i + k] * A[7 * j + k] * A[8 * k];
-            A[7 * i + j] = s / d;
+// the pairs of one problem as lm_block_run sees them (lm_block.h); S = q(x, y, z, w), t, s
+struct Sim3Model {
+    const Sim3Prob& P;
+    const uint8_t* active;     // LDS: the pair is still in the graph
+    double delta;
+    bool fix;
+    double* sSi;               // LDS [8]: S^-1 of the last errors()
+    double (*sPert)[8];        // LDS [28][8]: [2d] = S(+delta e_d), [2d+1] = S(-delta e_d), [14 + ..] their inverses
+    double* sh;                // LDS [4]: the block sum's
+
+    __device__ __forceinline__ double errors(const double* S) const { return sim3_errors(P, S, active, delta, sSi, sh); }
+    __device__ __forceinline__ void oplus(double* S, const double* x) const { sim3_oplus(S, x, fix); }
+    // the 14 perturbed similarities of g2o's numeric differentiation and their inverses
+    __device__ __forceinline__ void prepare(const double* sS) const {
+        const int tid = threadIdx.x;
+        if (tid < 14) {
+            double Sp[8], add[7] = {0, 0, 0, 0, 0, 0, 0};
+            for (int i = 0; i < 8; ++i) Sp[i] = sS[i];
+            add[tid >> 1] = (tid & 1) ? -1e-9 : 1e-9;
+            sim3_oplus(Sp, add, fix);
+            double Ip[8];
+            sim3_inverse(Sp, Ip);
+            for (int i = 0; i < 8; ++i) { sPert[tid][i] = Sp[i]; sPert[14 + tid][i] = Ip[i]; }
+        }
+        __syncthreads();
+    }
+    // H (28 unique), b (7) over this thread's active pairs; chi2 and S^-1 are those errors() left at this very S
+    __device__ __forceinline__ void accumulate(const double* sS, double* h, double* bb) const {
+        const int tid = threadIdx.x, n = P.n;
+        const double dsqr = (double)(float)(delta * delta), scalar = 1.0 / (2 * 1e-9);
+        for (int k = tid; k < n; k += 256) {
+            if (!active[k]) continue;
+            const double p1[3] = {P.p1[3 * k], P.p1[3 * k + 1], P.p1[3 * k + 2]}, p2[3] = {P.p2[3 * k], P.p2[3 * k + 1], P.p2[3 * k + 2]};
+            const double o1[2] = {P.o1[2 * k], P.o1[2 * k + 1]}, o2[2] = {P.o2[2 * k], P.o2[2 * k + 1]};
+            double J12[14], J21[14];
+#pragma unroll
+            for (int d = 0; d < 7; ++d) {
+                double a12[2], a21[2], c12[2], c21[2];
+                pair_error(sPert[2 * d], sPert[14 + 2 * d], P.intr1, P.intr2, p1, p2, o1, o2, a12, a21);
+                pair_error(sPert[2 * d + 1], sPert[14 + 2 * d + 1], P.intr1, P.intr2, p1, p2, o1, o2, c12, c21);
+                J12[d] = scalar * (a12[0] - c12[0]); J12[7 + d] = scalar * (a12[1] - c12[1]);
+                J21[d] = scalar * (a21[0] - c21[0]); J21[7 + d] = scalar * (a21[1] - c21[1]);
+            }
+            double e12[2], e21[2];
+            pair_error(sS, sSi, P.intr1, P.intr2, p1, p2, o1, o2, e12, e21);
+            const double w1 = P.w1[k], w2 = P.w2[k], c12 = P.chi12[k], c21 = P.chi21[k];
+            const double r12 = c12 > dsqr ? delta / sqrt(c12) : 1.0, r21 = c21 > dsqr ? delta / sqrt(c21) : 1.0;
+            const double wa = r12 * w1, wb = r21 * w2;
+            int q = 0;
+#pragma unroll
+            for (int a = 0; a < 7; ++a) {
+                bb[a] -= r12 * (J12[a] * w1 * e12[0] + J12[7 + a] * w1 * e12[1]) + r21 * (J21[a] * w2 * e21[0] + J21[7 + a] * w2 * e21[1]);
+#pragma unroll
+                for (int c = a; c < 7; ++c)
+                    h[q++] += (J12[a] * J12[c] + J12[7 + a] * J12[7 + c]) * wa + (J21[a] * J21[c] + J21[7 + a] * J21[7 + c]) * wb;
+            }
         }
     }
-    for (int i = 0; i < 7; ++i) { double s = b[i]; for (int k = 0; k < i; ++k) s -= A[7 * i + k] * x[k]; x[i] = s; }
-    for (int i = 0; i < 7; ++i) x[i] /= A[8 * i];
-    for (int i = 6; i >= 0; --i) { double s = x[i]; for (int k = i + 1; k < 7; ++k) s -= A[7 * k + i] * x[k]; x[i] = s; }
-    return true;
-}
+};
 
 }  // namespace
 
 __global__ __launch_bounds__(256) void sim3_opt_kernel(const Sim3Prob* probs) {
     const Sim3Prob P = probs[blockIdx.x];
     const int tid = threadIdx.x, n = P.n;
-    __shared__ double sh[4];
-    __shared__ double sS[8], sSbak[8], sSi[8], sPert[28][8];   // sPert: [2d] = S(+delta e_d), [2d+1] = S(-delta e_d), [14 + ..] their inverses
-    __shared__ double sH[49], sb[7], sx[7];
-    __shared__ double s_lambda, s_ni, s_cur, s_rho;
-    __shared__ int s_ok2, s_cnt;
+    __shared__ LmBlock<7, 8> L;
+    __shared__ double sSi[8], sPert[28][8];
+    double* const sS = L.state;
     extern __shared__ uint8_t s_act[];   // n bytes: the pair is still in the graph
     const float th2f = (float)P.th2;
     const double th2 = (double)th2f;
@@ -199,123 +225,11 @@ __global__ __launch_bounds__(256) void sim3_opt_kernel(const Sim3Prob* probs) {
         const int iterations = stage == 0 ? 5 : (nBadPairs > 0 ? 10 : 5);
         int nact = 0;
         for (int k = tid; k < n; k += 256) nact += s_act[k];
-        if (tid == 0) s_cnt = 0;
-        __syncthreads();
-        if (nact) atomicAdd(&s_cnt, nact);
-        __syncthreads();
-        const bool any_active = s_cnt > 0;
+        const bool any_active = lm_block_count(nact, &L.cnt) > 0;
         __syncthreads();
         int done = 0;
         double lastChi = 0;
-        if (any_active) {
-            int lm_nBad = 0;
-            bool ok = true;
-            for (int it = 0; it < iterations && ok; ++it) {
-                // g2o re-evaluates the errors at the top of every iteration; after an accepted trial (the only way to get here
-                // with it > 0) errors, chi2 and S^-1 are the ones that trial just computed at this very S: one pass saved
-                const double currentChi0 = it == 0 ? sim3_errors(P, sS, s_act, delta, sSi, sh) : s_cur;
-                // the 14 perturbed similarities of g2o's numeric differentiation and their inverses
-                if (tid < 14) {
-                    double Sp[8], add[7] = {0, 0, 0, 0, 0, 0, 0};
-                    for (int i = 0; i < 8; ++i) Sp[i] = sS[i];
-                    add[tid >> 1] = (tid & 1) ? -1e-9 : 1e-9;
-                    sim3_oplus(Sp, add, fix);
-                    double Ip[8];
-                    sim3_inverse(Sp, Ip);
-                    for (int i = 0; i < 8; ++i) { sPert[tid][i] = Sp[i]; sPert[14 + tid][i] = Ip[i]; }
-                }
-                __syncthreads();
-                // ---- normal equations H (28 unique), b (7): per-thread partials, shuffle tree, 4 waves in order ----
-                double h[28], bb[7];
-                for (int i = 0; i < 28; ++i) h[i] = 0;
-                for (int i = 0; i < 7; ++i) bb[i] = 0;
-                const double dsqr = (double)(float)(delta * delta), scalar = 1.0 / (2 * 1e-9);
-                for (int k = tid; k < n; k += 256) {
-                    if (!s_act[k]) continue;
-                    const double p1[3] = {P.p1[3 * k], P.p1[3 * k + 1], P.p1[3 * k + 2]}, p2[3] = {P.p2[3 * k], P.p2[3 * k + 1], P.p2[3 * k + 2]};
-                    const double o1[2] = {P.o1[2 * k], P.o1[2 * k + 1]}, o2[2] = {P.o2[2 * k], P.o2[2 * k + 1]};
-                    double J12[14], J21[14];
-#pragma unroll
-                    for (int d = 0; d < 7; ++d) {
-                        double a12[2], a21[2], c12[2], c21[2];
-                        pair_error(sPert[2 * d], sPert[14 + 2 * d], P.intr1, P.intr2, p1, p2, o1, o2, a12, a21);
-                        pair_error(sPert[2 * d + 1], sPert[14 + 2 * d + 1], P.intr1, P.intr2, p1, p2, o1, o2, c12, c21);
-                        J12[d] = scalar * (a12[0] - c12[0]); J12[7 + d] = scalar * (a12[1] - c12[1]);
-                        J21[d] = scalar * (a21[0] - c21[0]); J21[7 + d] = scalar * (a21[1] - c21[1]);
-                    }
-                    double e12[2], e21[2];
-                    pair_error(sS, sSi, P.intr1, P.intr2, p1, p2, o1, o2, e12, e21);
-                    const double w1 = P.w1[k], w2 = P.w2[k], c12 = P.chi12[k], c21 = P.chi21[k];
-                    const double r12 = c12 > dsqr ? delta / sqrt(c12) : 1.0, r21 = c21 > dsqr ? delta / sqrt(c21) : 1.0;
-                    const double wa = r12 * w1, wb = r21 * w2;
-                    int q = 0;
-#pragma unroll
-                    for (int a = 0; a < 7; ++a) {
-                        bb[a] -= r12 * (J12[a] * w1 * e12[0] + J12[7 + a] * w1 * e12[1]) + r21 * (J21[a] * w2 * e21[0] + J21[7 + a] * w2 * e21[1]);
-#pragma unroll
-                        for (int c = a; c < 7; ++c)
-                            h[q++] += (J12[a] * J12[c] + J12[7 + a] * J12[7 + c]) * wa + (J21[a] * J21[c] + J21[7 + a] * J21[7 + c]) * wb;
-                    }
-                }
-                __shared__ double red[4][35];
-                for (int i = 0; i < 28; ++i) { const double v = wave_sum(h[i]); if ((tid & 63) == 0) red[tid >> 6][i] = v; }
-                for (int i = 0; i < 7; ++i) { const double v = wave_sum(bb[i]); if ((tid & 63) == 0) red[tid >> 6][28 + i] = v; }
-                __syncthreads();
-                if (tid == 0) {
-                    int q = 0;
-                    for (int a = 0; a < 7; ++a)
-                        for (int c = a; c < 7; ++c) { const double v = red[0][q] + red[1][q] + red[2][q] + red[3][q]; sH[7 * a + c] = v; sH[7 * c + a] = v; ++q; }
-                    for (int a = 0; a < 7; ++a) sb[a] = red[0][28 + a] + red[1][28 + a] + red[2][28 + a] + red[3][28 + a];
-                    if (it == 0) {
-                        double m = 0;
-                        for (int j = 0; j < 7; ++j) m = fmax(m, fabs(sH[8 * j]));
-                        s_lambda = 1e-5 * m; s_ni = 2;
-                    }
-                    s_cur = currentChi0;
-                }
-                if (it == 0) lm_nBad = 0;
-                __syncthreads();
-                const double iniChi = currentChi0;
-                int qmax = 0;
-                double rho = 0, tempChi = currentChi0;
-                do {
-                    if (tid == 0) {
-                        for (int i = 0; i < 8; ++i) sSbak[i] = sS[i];
-                        double x[7];
-                        const bool ok2 = solve7(sH, s_lambda, sb, x);
-                        if (ok2) { double T[8]; for (int i = 0; i < 8; ++i) T[i] = sS[i]; sim3_oplus(T, x, fix); for (int i = 0; i < 8; ++i) sS[i] = T[i]; }
-                        else for (int i = 0; i < 7; ++i) x[i] = 0;
-                        for (int i = 0; i < 7; ++i) sx[i] = x[i];
-                        s_ok2 = ok2;
-                    }
-                    __syncthreads();
-                    tempChi = sim3_errors(P, sS, s_act, delta, sSi, sh);
-                    if (!s_ok2) tempChi = DBL_MAX;
-                    if (tid == 0) {
-                        double scale = 0;
-                        for (int k = 0; k < 7; ++k) scale += sx[k] * (s_lambda * sx[k] + sb[k]);
-                        const double r = (s_cur - tempChi) / (scale + 1e-3);
-                        if (r > 0 && fabs(tempChi) <= DBL_MAX) {
-                            const double alpha = fmin(1. - pow((2 * r - 1), 3), 2. / 3.);
-                            s_lambda *= fmax(1. / 3., alpha);
-                            s_ni = 2; s_cur = tempChi;
-                        } else {
-                            s_lambda *= s_ni; s_ni *= 2;
-                            for (int i = 0; i < 8; ++i) sS[i] = sSbak[i];
-                        }
-                        s_rho = r;
-                    }
-                    __syncthreads();
-                    rho = s_rho;
-                    ++qmax;
-                } while (rho < 0 && qmax < 10);
-                ++done;
-                lastChi = tempChi;
-                if (qmax == 10 || rho == 0) { ok = false; continue; }
-                if ((iniChi - s_cur) * 1e3 < iniChi) ++lm_nBad; else lm_nBad = 0;
-                if (lm_nBad >= 3) ok = false;
-            }
-        }
+        if (any_active) done = lm_block_run(L, Sim3Model{P, s_act, delta, fix, sSi, sPert, L.sum}, iterations, lastChi);
         if (tid == 0) { P.ints[1 + stage] = done; P.out[13 + stage] = lastChi; }
         // ---- the chi2 tests (:1184-1201, 1218-1234): the chi2 of the LAST EVALUATED trial, accepted or not ----
         int bad = 0;
@@ -327,11 +241,7 @@ __global__ __launch_bounds__(256) void sim3_opt_kernel(const Sim3Prob* probs) {
                 ++bad;
             }
         }
-        if (tid == 0) s_cnt = 0;
-        __syncthreads();
-        if (bad) atomicAdd(&s_cnt, bad);
-        __syncthreads();
-        const int nbad = s_cnt;
+        const int nbad = lm_block_count(bad, &L.cnt);
         __syncthreads();
         if (stage == 0) {
             nBadPairs = nbad;
@@ -399,12 +309,12 @@ int slamit_sim3_optimize_batch(int device, int nprob, const slamit_sim3_problem*
         R_to_quat(P.r12, Q.S0);   // Sim3(R, t, s): Quaterniond(R) by Eigen's rule, not normalised
         for (int i = 0; i < 3; ++i) Q.S0[4 + i] = P.t12[i];
         Q.S0[7] = P.s12;
-        typedef SIM3_G double gd;
+        typedef SLAMIT_GLOBAL double gd;
         Q.p1 = (const gd*)s.p1.at(S.dev); Q.p2 = (const gd*)s.p2.at(S.dev); Q.o1 = (const gd*)s.o1.at(S.dev); Q.o2 = (const gd*)s.o2.at(S.dev);
         Q.w1 = (const gd*)s.w1.at(S.dev); Q.w2 = (const gd*)s.w2.at(S.dev); Q.chi12 = (gd*)s.chi12.at(S.dev); Q.chi21 = (gd*)s.chi21.at(S.dev);
         Q.out = (gd*)s.out.at(S.dev);
-        Q.inlier = (SIM3_G uint8_t*)flags[f].at(S.dev);
-        Q.ints = (SIM3_G int32_t*)(ints.at(S.dev) + 4 * f);
+        Q.inlier = (SLAMIT_GLOBAL uint8_t*)flags[f].at(S.dev);
+        Q.ints = (SLAMIT_GLOBAL int32_t*)(ints.at(S.dev) + 4 * f);
     }
     HIP_TRY_AT(where, slamit_stage_upload(S, L));
     if (nmax > 32 * 1024) HIP_TRY_AT(where, hipFuncSetAttribute(reinterpret_cast<const void*>(sim3_opt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, nmax + 16));

@@ -18,18 +18,12 @@
 #include "sim3_horn.h"
 #include "slamit_internal.h"
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define S3R_G __attribute__((address_space(1)))
-#else
-#define S3R_G
-#endif
-
 struct Sim3RansacProb {
     int32_t n, n_hyp, fix_scale, words;   // words = (n + 31) / 32
     float intr1[4], intr2[4];
-    const S3R_G float* x1; const S3R_G float* x2; const S3R_G float* e1; const S3R_G float* e2;
-    const S3R_G int32_t* triples;
-    S3R_G float* t12; S3R_G int32_t* counts; S3R_G uint32_t* bits;
+    const SLAMIT_GLOBAL float* x1; const SLAMIT_GLOBAL float* x2; const SLAMIT_GLOBAL float* e1; const SLAMIT_GLOBAL float* e2;
+    const SLAMIT_GLOBAL int32_t* triples;
+    SLAMIT_GLOBAL float* t12; SLAMIT_GLOBAL int32_t* counts; SLAMIT_GLOBAL uint32_t* bits;
 };
 
 // grid (ceil(max n_hyp / 4), problems), 256 threads: wave w of block b takes hypothesis 4 b + w of problem blockIdx.y.
@@ -51,7 +45,7 @@ __global__ __launch_bounds__(256) void sim3_ransac_kernel(const Sim3RansacProb* 
     sim3h_solve(P1, P2, P.fix_scale, H);
     const float K1[4] = {P.intr1[0], P.intr1[1], P.intr1[2], P.intr1[3]}, K2[4] = {P.intr2[0], P.intr2[1], P.intr2[2], P.intr2[3]};
     int count = 0;
-    S3R_G uint32_t* bits = P.bits + (size_t)h * P.words;
+    SLAMIT_GLOBAL uint32_t* bits = P.bits + (size_t)h * P.words;
     for (int base = 0; base < n; base += 64) {
         const int i = base + lane;
         bool in = false;
@@ -137,10 +131,10 @@ int slamit_sim3_ransac_batch(int device, int nprob, const slamit_sim3_ransac_pro
         memset(&Q, 0, sizeof(Q));
         Q.n = P.n; Q.n_hyp = s.hyp; Q.fix_scale = P.fix_scale; Q.words = s.words;
         memcpy(Q.intr1, P.intr1, sizeof(Q.intr1)); memcpy(Q.intr2, P.intr2, sizeof(Q.intr2));
-        typedef const S3R_G float* cgf;
+        typedef const SLAMIT_GLOBAL float* cgf;
         Q.x1 = (cgf)s.x1.at(S.dev); Q.x2 = (cgf)s.x2.at(S.dev); Q.e1 = (cgf)s.e1.at(S.dev); Q.e2 = (cgf)s.e2.at(S.dev);
-        Q.triples = (const S3R_G int32_t*)s.triples.at(S.dev);
-        Q.t12 = (S3R_G float*)s.t12.at(S.dev); Q.counts = (S3R_G int32_t*)s.counts.at(S.dev); Q.bits = (S3R_G uint32_t*)s.bits.at(S.dev);
+        Q.triples = (const SLAMIT_GLOBAL int32_t*)s.triples.at(S.dev);
+        Q.t12 = (SLAMIT_GLOBAL float*)s.t12.at(S.dev); Q.counts = (SLAMIT_GLOBAL int32_t*)s.counts.at(S.dev); Q.bits = (SLAMIT_GLOBAL uint32_t*)s.bits.at(S.dev);
     }
     HIP_TRY_AT(where, slamit_stage_upload(S, L));
     hipLaunchKernelGGL(sim3_ransac_kernel, dim3((max_hyp + 3) / 4, nprob), dim3(256), 0, S.st, recs.at(S.dev));

@@ -1,4 +1,4 @@
-// slamit_internal.h — error plumbing shared by the C-ABI translation units.
+// slamit_internal.h — error plumbing, the global-pointer qualifier and the staged-call helper shared by the translation units.
 #ifndef SLAMIT_INTERNAL_H
 #define SLAMIT_INTERNAL_H
 #include <hip/hip_runtime.h>
@@ -15,6 +15,16 @@ int slamit_fail_hip(hipError_t e, const char* where);       // records "<where>:
         if (_e != hipSuccess) return slamit_fail_hip(_e, where);             \
     } while (0)
 #define HIP_TRY(expr) HIP_TRY_AT(#expr, expr)
+
+// Qualifier of a device pointer that a kernel reads out of a record in memory (BaWin, PoseFrame, Sim3Prob, Sim3RansacProb): the global
+// address space in the device pass, nothing on the host.  Without it such a pointer is GENERIC to the compiler and every access through
+// it a flat_load / flat_store (slower to issue, and counted in lgkmcnt, so LDS waits also wait for outstanding HBM loads).  Host code
+// that fills a record is parsed in the device pass too: it casts (`(SLAMIT_GLOBAL double*)p`, a no-op on the host).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SLAMIT_GLOBAL __attribute__((address_space(1)))
+#else
+#define SLAMIT_GLOBAL
+#endif
 
 // Every entry point works on the device it is given and leaves the caller's current device as it found it (a torch
 // host thread must not have its device changed under it).
