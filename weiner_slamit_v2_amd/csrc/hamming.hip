@@ -112,73 +112,87 @@ __global__ __launch_bounds__(256) void hamming_best2_kernel(
 }
 
 // ---- the same reduction on the matrix cores -------------------------------------------------------------------
-// 256-bit Hamming distance as an int8 dot product: a descriptor bit becomes the byte +-64 (query: 1 -> -64, train:
-// 1 -> +64), so a byte product is -4096 where the bits agree and +4096 where they differ and the sum over the 256
-// positions is 4096 * (2 d - 256) = 8192 d - 2^20 -- exact in i32.  The 13 low bits of that sum are zero, so the train
-// index j (< 8192) rides in the accumulator's initial value: v_mfma_i32_32x32x32_i8 leaves  8192 d - 2^20 + j  = the
-// (distance, first index) key itself, and the epilogue per distance is a min and a median (2 VALU ops instead of the
-// 19 of the xor / popcount kernel).  Unpacking costs one shift + one v_bitop3 per four positions:
-//     byte = ((w << (7 - s)) & 0x80) | 0x40            (query; train uses ~w)
+// 256-bit Hamming distance as a block-scaled FP4 dot product: a descriptor bit becomes the e2m1 nibble 0x2 (+1.0) or 0xA
+// (-1.0) (query: 1 -> -1, train: 1 -> +1) and each operand carries the constant block scale 2^6 (e8m0 byte 133), so a
+// product is -4096 where the bits agree and +4096 where they differ and the sum over the 256 positions is
+// 4096 * (2 d - 256) = 8192 d - 2^20.  The 13 low bits of that sum are zero, so the train index j (< 8192) rides in the
+// accumulator's initial value: v_mfma_scale_f32_32x32x64_f8f6f4 leaves  8192 d - 2^20 + j  = the (distance, first index)
+// key itself (plus HMM_BIAS = 2^21, which keeps it positive).  Every term and every partial sum is an integer below 2^22,
+// inside f32's 24-bit significand, so the f32 accumulator holds that key exactly in whatever order the hardware adds; the epilogue per
+// distance is a v_min_i32 and a v_med3_f32 (2 VALU ops instead of the 19 of the xor / popcount kernel) and the keys turn
+// into integers once, in the final write-out.  Unpacking costs one shift + one v_bitop3 per EIGHT positions:
+//     nibbles = ((w << (3 - s)) & 0x88888888) | 0x22222222            (query; train uses ~w)
 // Position order inside the K = 256 axis is whatever (lane half, shift class s, dword) gives -- the same for both operands.
 // A = train tile (32 rows), B = queries (32 columns): a lane's 16 accumulators are 16 train rows of ONE query, so the
-// running (best, second) keys are two registers per lane and query tile.  Workgroup = 4 wavefronts that share 64 queries
-// (two 32-column tiles kept unpacked in 64 VGPRs) and take every 4th train tile; they merge through LDS at the end.
-typedef int hm_v4i __attribute__((ext_vector_type(4)));
-typedef int hm_v16i __attribute__((ext_vector_type(16)));
+// running (best, second) keys are two registers per lane and query tile.
+typedef int hm_v8i __attribute__((ext_vector_type(8)));
+typedef float hm_v16f __attribute__((ext_vector_type(16)));
 #define HMM_MAX_TRAIN 8192
-#define HMM_NONE 0x40000000          // accumulator start of a train row >= nt: its key stays above every real one
-#define HMM_EMPTY 0x7F000000         // "no key yet"
+// Sentinels are powers of two: a sum of +-4096 products on top of one, and the +-32 HMM_WAVES rebasing of the running
+// keys, stay multiples of its ulp (128 at most), so nothing is ever rounded and none can come near the 2^29 test below.
+#define HMM_NONE 0x1p30f             // accumulator start of a train row >= nt: its key stays above every real one
+#define HMM_EMPTY 0x1p30f            // "no key yet"
+#define HMM_BIAS 0x1p21f             // added to every key through the accumulator start: real keys lie in (2^20 - 2^13, 2^22)
+#define HMM_LIVE 0x1p29f             // ... and anything that started from a sentinel is above this
+#define HMM_FP4 4                    // cbsz / blgp: both operands are e2m1, four VGPRs each
+#define HMM_SCALE 133                // e8m0 block scale 2^6 of both operands (byte 0 of the scale register)
 
-__device__ __forceinline__ hm_v4i hm_unpack_q(const uint4 w, const int s) {   // bit 1 -> 0xC0 (-64), bit 0 -> 0x40 (+64)
-    const unsigned hi = 0x80808080u, mid = 0x40404040u;
-    hm_v4i r;
-    r.x = (int)__builtin_amdgcn_bitop3_b32(w.x << (7 - s), hi, mid, 0xEA);
-    r.y = (int)__builtin_amdgcn_bitop3_b32(w.y << (7 - s), hi, mid, 0xEA);
-    r.z = (int)__builtin_amdgcn_bitop3_b32(w.z << (7 - s), hi, mid, 0xEA);
-    r.w = (int)__builtin_amdgcn_bitop3_b32(w.w << (7 - s), hi, mid, 0xEA);
+__device__ __forceinline__ hm_v8i hm_unpack_q(const uint4 w, const int s) {   // bit 1 -> 0xA (-1.0), bit 0 -> 0x2 (+1.0)
+    const unsigned sign = 0x88888888u, one = 0x22222222u;
+    hm_v8i r = {};                                                             // (FP4 operands: the upper four dwords are not read)
+    r[0] = (int)__builtin_amdgcn_bitop3_b32(w.x << (3 - s), sign, one, 0xEA);
+    r[1] = (int)__builtin_amdgcn_bitop3_b32(w.y << (3 - s), sign, one, 0xEA);
+    r[2] = (int)__builtin_amdgcn_bitop3_b32(w.z << (3 - s), sign, one, 0xEA);
+    r[3] = (int)__builtin_amdgcn_bitop3_b32(w.w << (3 - s), sign, one, 0xEA);
     return r;
 }
-__device__ __forceinline__ hm_v4i hm_unpack_t(const uint4 w, const int s) {   // bit 1 -> 0x40 (+64), bit 0 -> 0xC0 (-64)
-    const unsigned hi = 0x80808080u, mid = 0x40404040u;
-    hm_v4i r;
-    r.x = (int)__builtin_amdgcn_bitop3_b32(w.x << (7 - s), hi, mid, 0xAE);
-    r.y = (int)__builtin_amdgcn_bitop3_b32(w.y << (7 - s), hi, mid, 0xAE);
-    r.z = (int)__builtin_amdgcn_bitop3_b32(w.z << (7 - s), hi, mid, 0xAE);
-    r.w = (int)__builtin_amdgcn_bitop3_b32(w.w << (7 - s), hi, mid, 0xAE);
+__device__ __forceinline__ hm_v8i hm_unpack_t(const uint4 w, const int s) {   // bit 1 -> 0x2 (+1.0), bit 0 -> 0xA (-1.0)
+    const unsigned sign = 0x88888888u, one = 0x22222222u;
+    hm_v8i r = {};
+    r[0] = (int)__builtin_amdgcn_bitop3_b32(w.x << (3 - s), sign, one, 0xAE);
+    r[1] = (int)__builtin_amdgcn_bitop3_b32(w.y << (3 - s), sign, one, 0xAE);
+    r[2] = (int)__builtin_amdgcn_bitop3_b32(w.z << (3 - s), sign, one, 0xAE);
+    r[3] = (int)__builtin_amdgcn_bitop3_b32(w.w << (3 - s), sign, one, 0xAE);
     return r;
 }
-// v_med3_i32 has no builtin.  The compiler pads the wait states between an MFMA and a VALU instruction that reads its
-// result only for instructions it knows, not inside asm: `after` is a value computed FROM the same MFMA result by an
-// ordinary instruction (the v_min of the same key), which orders this asm behind that instruction and its padding.
-__device__ __forceinline__ int imed3_after(int a, int b, int c, int after) {
-    int r;
-    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c), "v"(after));
-    return r;
+__device__ __forceinline__ hm_v16f hm_mfma(const hm_v8i a, const hm_v8i b, const hm_v16f c) {
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, HMM_FP4, HMM_FP4, 0, HMM_SCALE, 0, HMM_SCALE);
 }
 
-// The kernel is bound by vector-instruction ISSUE, which the MFMAs share (8 of an MFMA's 32 cycles): per 64 queries x
-// 32 train rows that is 16 MFMAs (128 cycles of issue) + 64 epilogue instructions + the train tile's unpacking (60,
-// shared by all the query tiles of the wave) at ~4 cycles each.  A wave therefore carries FOUR query tiles (128
-// queries, 128 VGPRs of unpacked queries + 64 of accumulators -> 2 waves per SIMD): 30 + 64 instructions per 16 MFMAs.
-// Workgroup = 4 wavefronts = 4 train slices (a slice takes every 4th train tile) of the same 128 queries, one wave per
-// SIMD; they merge through LDS at the end.  Measured (tools/diag/ubench/mfma_i8_rate.hip): a wave's
-// MFMAs (16 ns each per SIMD) and its ~190 vector instructions per tile (~2 ns each) ADD UP -- 0.51 + 0.38 us per tile of 128
-// queries x 32 train rows, the two waves of a SIMD running in step; starting one of them half a period late (s_sleep) or
-// interleaving the epilogue of one half of the query tiles with the MFMAs of the other inside the wave (which doubles the
-// unpacking) both left the time unchanged, so neither is kept.
+// The kernel is bound by the matrix pipe and by vector-instruction ISSUE, which add up (the two waves of a SIMD run in
+// step; staggering them or interleaving epilogue and MFMAs inside a wave changed nothing on the int8 form of this kernel).
+// Per HMM_NG = 4 query tiles (128 queries) x 32 train rows a wave issues 16 MFMAs + 128 epilogue instructions + the train
+// tile's unpacking (28) and the keys' rebasing (8), both shared by all the query tiles of the wave.  Measured
+// (tools/diag/ubench/mfma_fp4_rate.hip, beside mfma_i8_rate.hip in the same run): the FP4 MFMA issues every 16.0-16.8 ns
+// per SIMD, one or two waves, dependent or not -- the time of v_mfma_i32_32x32x32_i8 (15.7-16.0 ns) at twice its K, so
+// 0.26 us per group where the int8 form took 0.51; a 64-key epilogue (add + v_med3_f32 + v_min_i32 per key) takes 305 ns
+// per SIMD, 1.6 ns per instruction, and unpacking the operand between the MFMAs costs them 2-4 %.
+// A wave carries HMM_NT query tiles, their unpacked queries held in 16 VGPRs each, and runs them against a train tile
+// in groups of HMM_NG (64 VGPRs of accumulators) -> 2 waves per SIMD.
+// Workgroup = 4 wavefronts = 4 train slices (a slice takes every 4th train tile) of the same queries, one wave per
+// SIMD; they merge through LDS at the end.
 #define HMM_WAVES 4                   // train slices = wavefronts per workgroup
-#define HMM_NT 4                      // query tiles (32 queries each) per wavefront
+#ifndef HMM_NT
+#define HMM_NT 4                      // query tiles (32 queries each) per wavefront.  8 (256 VGPRs, no scratch) shares the train unpack
+#endif                                // between twice the queries: 40.8 -> 40.4 us per 256 pairs of 1000 x 1000, 35.1 -> 33.0 us per 64 of
+                                      // 2000 x 2000, but the single-pair call (4 workgroups instead of 8) 0.038 -> 0.0415 ms: not kept
+#define HMM_NG 4                      // query tiles per group of accumulators
 
-__device__ __forceinline__ void hm_merge2(int& kb, int& ks, int ob, int os) {   // two smallest of the union of two (best, second) pairs
-    ks = min(min(ks, os), max(kb, ob));
-    kb = min(kb, ob);
+// Keys are positive floats (HMM_BIAS), which order like their bit patterns: the running minimum is a bare v_min_i32.
+// (fminf on an MFMA result first quiets a possible signalling NaN, a v_max_f32 x, x: a third instruction per distance.)
+__device__ __forceinline__ float hm_min(float a, float b) { return __int_as_float(min(__float_as_int(a), __float_as_int(b))); }
+__device__ __forceinline__ float hm_max(float a, float b) { return __int_as_float(max(__float_as_int(a), __float_as_int(b))); }
+
+__device__ __forceinline__ void hm_merge2(float& kb, float& ks, float ob, float os) {   // two smallest of the union of two (best, second) pairs
+    ks = hm_min(hm_min(ks, os), hm_max(kb, ob));
+    kb = hm_min(kb, ob);
 }
 
 __global__ __launch_bounds__(64 * HMM_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2))) void hamming_best2_mfma_kernel(
     const uint8_t* __restrict__ q, const int* __restrict__ nq_arr, int nq_fixed, size_t q_stride,
     const uint8_t* __restrict__ t, const int* __restrict__ nt_arr, int nt_fixed, size_t t_stride,
     int* __restrict__ best_idx, int* __restrict__ best, int* __restrict__ second, size_t out_stride) {
-    __shared__ int s_keys[HMM_WAVES - 1][64][2 * HMM_NT];       // slices 1..: (kb, ks) per query tile and lane
+    __shared__ float s_keys[HMM_WAVES - 1][64][2 * HMM_NT];     // slices 1..: (kb, ks) per query tile and lane
     const int pair = blockIdx.y;
     const int nq = __builtin_amdgcn_readfirstlane(nq_arr ? nq_arr[pair] : nq_fixed);
     const int nt = __builtin_amdgcn_readfirstlane(min(nt_arr ? nt_arr[pair] : nt_fixed, HMM_MAX_TRAIN));
@@ -189,23 +203,23 @@ __global__ __launch_bounds__(64 * HMM_WAVES) __attribute__((amdgpu_waves_per_eu(
     const int col = lane & 31, h = lane >> 5;
     const uint4* Q = reinterpret_cast<const uint4*>(q + (size_t)pair * q_stride);
     const uint4* T = reinterpret_cast<const uint4*>(t + (size_t)pair * t_stride);
-    // this lane's half (dwords 4h .. 4h+3) of its queries, unpacked once: 8 k-steps x 4 VGPRs per query tile
-    hm_v4i bq[HMM_NT][8];
+    // this lane's half (dwords 4h .. 4h+3) of its queries, unpacked once: 4 k-steps x 4 VGPRs per query tile
+    hm_v8i bq[HMM_NT][4];
 #pragma unroll
     for (int u = 0; u < HMM_NT; ++u) {
         const uint4 w = Q[2 * (size_t)min(qbase + 32 * u + col, nq - 1) + h];
 #pragma unroll
-        for (int s = 0; s < 8; ++s) bq[u][s] = hm_unpack_q(w, s);
+        for (int s = 0; s < 4; ++s) bq[u][s] = hm_unpack_q(w, s);
     }
     // Accumulator start = row of (register r, lane half h) inside the tile: (r & 3) + 8 (r >> 2) + 4 h -- the same 16
     // registers for every tile.  The running keys are kept RELATIVE to the current tile's first row (stepping to the next
     // tile subtracts the stride from them) and the last tile's base is added back at the end.
-    hm_v16i cinit;
+    hm_v16f cinit;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) cinit[r] = 4 * h + (r & 3) + 8 * (r >> 2);
-    int kb[HMM_NT], ks[HMM_NT];
+    for (int r = 0; r < 16; ++r) cinit[r] = HMM_BIAS + (float)(4 * h + (r & 3) + 8 * (r >> 2));
+    float kb[HMM_NT], ks[HMM_NT];
 #pragma unroll
-    for (int u = 0; u < HMM_NT; ++u) kb[u] = ks[u] = HMM_EMPTY;   // (room for the +- tile bases)
+    for (int u = 0; u < HMM_NT; ++u) kb[u] = ks[u] = HMM_EMPTY;
     const int ntiles = (nt + 31) >> 5;
     uint4 wt = make_uint4(0u, 0u, 0u, 0u);
     if (wv < ntiles) wt = T[2 * (size_t)min(wv * 32 + col, nt - 1) + h];
@@ -213,39 +227,40 @@ __global__ __launch_bounds__(64 * HMM_WAVES) __attribute__((amdgpu_waves_per_eu(
     for (; tile < ntiles; tile += HMM_WAVES) {
         const uint4 w = wt;
         if (tile + HMM_WAVES < ntiles) wt = T[2 * (size_t)min((tile + HMM_WAVES) * 32 + col, nt - 1) + h];   // travels during this tile
-        hm_v16i c[HMM_NT];
-        {
-            const hm_v4i a = hm_unpack_t(w, 0);
-            hm_v16i cm = cinit;
-            if (tile * 32 + 32 > nt) {   // the set's last, partial tile: rows >= nt start above every real key
+        hm_v8i a[4];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) cm[r] = tile * 32 + cinit[r] < nt ? cinit[r] : HMM_NONE;
-            }
+        for (int s = 0; s < 4; ++s) a[s] = hm_unpack_t(w, s);
+        if (tile * 32 + 32 > nt) {   // the set's last, partial tile (no tile follows it): rows >= nt start above every real key
 #pragma unroll
-            for (int u = 0; u < HMM_NT; ++u) c[u] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[u][0], cm, 0, 0, 0);
-        }
-#pragma unroll
-        for (int s = 1; s < 8; ++s) {
-            const hm_v4i a = hm_unpack_t(w, s);
-#pragma unroll
-            for (int u = 0; u < HMM_NT; ++u) c[u] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[u][s], c[u], 0, 0, 0);
+            for (int r = 0; r < 16; ++r) cinit[r] = tile * 32 + 4 * h + (r & 3) + 8 * (r >> 2) < nt ? cinit[r] : HMM_NONE;
         }
         if (tile != wv) {
 #pragma unroll
             for (int u = 0; u < HMM_NT; ++u) { kb[u] -= 32 * HMM_WAVES; ks[u] -= 32 * HMM_WAVES; }
         }
 #pragma unroll
-        for (int u = 0; u < HMM_NT; ++u) {
+        for (int g = 0; g < HMM_NT; g += HMM_NG) {
+            hm_v16f c[HMM_NG];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int n = min(kb[u], c[u][r]);
-                ks[u] = imed3_after(kb[u], ks[u], c[u][r], n);   // kb <= ks: the median of the three is the new second smallest
-                kb[u] = n;
+            for (int u = 0; u < HMM_NG; ++u) c[u] = hm_mfma(a[0], bq[g + u][0], cinit);
+#pragma unroll
+            for (int s = 1; s < 4; ++s) {
+#pragma unroll
+                for (int u = 0; u < HMM_NG; ++u) c[u] = hm_mfma(a[s], bq[g + u][s], c[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < HMM_NG; ++u) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float k = c[u][r];
+                    ks[g + u] = __builtin_amdgcn_fmed3f(kb[g + u], ks[g + u], k);   // kb <= ks: the median of the three is the new second smallest
+                    kb[g + u] = hm_min(kb[g + u], k);
+                }
             }
         }
     }
     if (tile != wv) {   // this wave saw at least one tile: back to absolute train indices (base of its last tile)
-        const int base = (tile - HMM_WAVES) * 32;
+        const float base = (float)((tile - HMM_WAVES) * 32);
 #pragma unroll
         for (int u = 0; u < HMM_NT; ++u) { kb[u] += base; ks[u] += base; }
     }
@@ -263,16 +278,17 @@ __global__ __launch_bounds__(64 * HMM_WAVES) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
         for (int u = 0; u < HMM_NT; ++u) hm_merge2(kb[u], ks[u], s_keys[o][lane][2 * u], s_keys[o][lane][2 * u + 1]);
     }
-    // key = 8192 d - 2^20 + j; anything from HMM_NONE / the empty start is far above 2^29
+    // key = HMM_BIAS + 8192 d - 2^20 + j, an integer held exactly; anything from HMM_NONE / the empty start is far above 2^29
 #pragma unroll
     for (int u = 0; u < HMM_NT; ++u) {
         const int qi = qbase + 32 * u + col;
         if (qi >= nq) continue;
-        const bool hb = kb[u] < 0x20000000, hs = ks[u] < 0x20000000;
+        const bool hb = kb[u] < HMM_LIVE, hs = ks[u] < HMM_LIVE;
+        const int ib = (int)kb[u] - (1 << 20), is = (int)ks[u] - (1 << 20);   // - HMM_BIAS + 2^20
         const size_t o = (size_t)pair * out_stride + qi;
-        best_idx[o] = hb ? ((kb[u] + (1 << 20)) & 8191) : -1;
-        best[o] = hb ? ((kb[u] + (1 << 20)) >> 13) : 256;
-        second[o] = hs ? ((ks[u] + (1 << 20)) >> 13) : 256;
+        best_idx[o] = hb ? (ib & 8191) : -1;
+        best[o] = hb ? (ib >> 13) : 256;
+        second[o] = hs ? (is >> 13) : 256;
     }
 }
 
