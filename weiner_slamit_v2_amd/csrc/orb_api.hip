@@ -24,6 +24,9 @@ void orbk_resize_rows4(hipStream_t st, const uint8_t* src, size_t sstride, size_
                        size_t dstride, size_t dframe, const uint32_t* d_col, const uint32_t* d_row, int nframes);
 void orbk_resize_rows8(hipStream_t st, const uint8_t* src, size_t sstride, size_t sframe, int sh, uint8_t* dst, int dw, int dh,
                        size_t dstride, size_t dframe, const uint32_t* d_col8, const uint32_t* d_row, int nframes);
+hipError_t orbk_pyramid_bands_prepare(int smem_bytes);
+void orbk_pyramid_bands(hipStream_t st, const BandTab& tab, const uint8_t* d_tables, const BandRows* d_rows, int first, int last, int nbands,
+                        const uint8_t* src, size_t sstride, size_t sframe, int sh, uint8_t* pyr, size_t pyr_frame, int tile0, int smem, int nframes);
 hipError_t orbk_pyramid_prepare(int smem_bytes);
 void orbk_pyramid(hipStream_t st, const OrbLevel* levels, int nlevels, const PyrBox* boxes, const PyrTabs* tabs,
                   int nregions, const uint8_t* img0, size_t img0_stride, size_t img0_frame, uint8_t* pyr, int bufA_bytes,
@@ -57,8 +60,8 @@ inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
-// levels 0 .. ORB_BLUR_SPLIT are blurred on the side stream beside the tail of the pyramid chain, the rest after it
-// (2 until the pyramid chain got its wide loads: its tail is shorter now)
+// per-level chain: levels 0 .. ORB_BLUR_SPLIT are blurred on the side stream beside the tail of the pyramid chain, the rest after it
+// (2 until the pyramid chain got its wide loads: its tail is shorter now); the banded pyramid forks where its first segment ends
 #define ORB_BLUR_SPLIT 1
 
 struct slamit_orb {
@@ -180,6 +183,7 @@ int slamit_orb_create(const slamit_orb_params* p, int device, slamit_orb** out) 
     }
     h->d_levels = dtab<OrbLevel>(h, P.levels_off);
     if (e == hipSuccess && P.pyr_regions) e = orbk_pyramid_prepare(P.pyr_smem);
+    for (const OrbBandSeg& G : P.bands) if (e == hipSuccess) e = orbk_pyramid_bands_prepare(G.smem);
     if (e == hipSuccess) e = orbk_upload_pattern(h->stream);
     if (e == hipSuccess) e = orbk_octree_prepare(P.node_cap, P.oct_key_cap);
     if (e == hipSuccess && !empty) e = orbk_fast_prepare(P.max_wcell, P.max_hcell);
@@ -266,8 +270,27 @@ int slamit_orb_extract_batch_dev(slamit_orb* h, const uint8_t* d_gray, size_t st
     const bool src0_aligned = ((((uintptr_t)d_gray) | stride | frame_stride) & 3) == 0;
     const bool side = h->prof_on != 1;   // while every stage is timed (slamit_orb_profile(h, 1)) everything stays on one stream
     const bool early_blur = side && ORB_BLUR_SPLIT < nl - 1;
-    bool early_done = false;
-    if (P.rows4_ok && src0_aligned) {
+    int early_done = -1;   // the last level the early blur launch took
+    auto fork_early_blur = [&](int l) -> hipError_t {
+        // the blur of the big levels 0 .. l (most of its bytes) runs on the side stream beside the rest of the pyramid: the small
+        // levels are a few microseconds of work behind a barrier or a kernel boundary each and leave the chip idle
+        hipError_t e = hipEventRecord(h->ev_mid, st);
+        if (e == hipSuccess) e = hipStreamWaitEvent(h->stream_b, h->ev_mid, 0);
+        if (e != hipSuccess) return e;
+        launch_blur(h->stream_b, 0, l + 1);
+        early_done = l;
+        return hipSuccess;
+    };
+    if (!P.bands.empty() && src0_aligned) {
+        // one launch per segment: a (frame, band) workgroup walks the segment's levels out of LDS (pyramid_bands_kernel)
+        for (const OrbBandSeg& G : P.bands) {
+            const OrbLevel& S = P.levels[G.first];
+            orbk_pyramid_bands(st, P.band_tab, h->d_tables, dtab<BandRows>(h, G.rows_off), G.first, G.last, G.nbands,
+                               G.first == 0 ? d_gray : h->d_pyr + S.plane_off, G.first == 0 ? stride : (size_t)S.stride,
+                               G.first == 0 ? frame_stride : P.pyr_frame_total, S.h, h->d_pyr, P.pyr_frame_total, G.tile0, G.smem, nframes);
+            if (early_blur && G.last < nl - 1 && early_done < 0) HIP_TRY(fork_early_blur(G.last));   // beside the second segment
+        }
+    } else if (P.rows4_ok && src0_aligned) {
         for (int l = 1; l < nl; ++l) {
             const OrbLevel& S = P.levels[l - 1];
             const OrbLevel& D = P.levels[l];
@@ -281,14 +304,7 @@ int slamit_orb_extract_batch_dev(slamit_orb* h, const uint8_t* d_gray, size_t st
                 orbk_resize_rows4(st, src, l == 1 ? stride : (size_t)S.stride, l == 1 ? frame_stride : P.pyr_frame_total, S.h,
                                   h->d_pyr + D.plane_off, D.w, D.h, (size_t)D.stride, P.pyr_frame_total, dtab<uint32_t>(h, T.col4_off),
                                   dtab<uint32_t>(h, T.row4_off), nframes);
-            if (early_blur && l == ORB_BLUR_SPLIT) {
-                // the blur of the big levels 0 .. l (most of its bytes) runs on the side stream beside the rest of the chain:
-                // the small levels are a few microseconds of work behind a kernel boundary each and leave the chip idle
-                HIP_TRY(hipEventRecord(h->ev_mid, st));
-                HIP_TRY(hipStreamWaitEvent(h->stream_b, h->ev_mid, 0));
-                launch_blur(h->stream_b, 0, l + 1);
-                early_done = true;
-            }
+            if (early_blur && l == ORB_BLUR_SPLIT) HIP_TRY(fork_early_blur(l));
         }
     } else if (P.pyr_regions) {
         orbk_pyramid(st, h->d_levels, nl, dtab<PyrBox>(h, P.boxes_off), dtab<PyrTabs>(h, P.tabs_off), P.pyr_regions, d_gray, stride, frame_stride,
@@ -318,7 +334,7 @@ int slamit_orb_extract_batch_dev(slamit_orb* h, const uint8_t* d_gray, size_t st
     if (side) {
         HIP_TRY(hipEventRecord(h->ev_pyr, st));
         HIP_TRY(hipStreamWaitEvent(h->stream_b, h->ev_pyr, 0));
-        launch_blur(h->stream_b, early_done ? ORB_BLUR_SPLIT + 1 : 0, nl);   // the levels the early launch left
+        launch_blur(h->stream_b, early_done + 1, nl);   // the levels the early launch left
         HIP_TRY(hipEventRecord(h->ev_blur, h->stream_b));
     }
     // K4: octree

@@ -243,6 +243,129 @@ void orbk_resize_rows4(hipStream_t st, const uint8_t* src, size_t sstride, size_
 }
 
 // --------------------------------------------------------------------------------------------
+// K1 (banded): the levels of one SEGMENT of the pyramid in one launch.  A workgroup is (frame, band of rows) and walks the segment's
+// levels; the arithmetic, the column tables and the row tables are rs_item8's.  The segment's first level is computed from its source
+// plane in HBM with the same 16-byte buffer loads; every computed row goes to an LDS tile (two tiles ping-pong, one barrier per
+// level), and each further level reads its windows from the tile of the level below: four aligned dwords at the window's
+// dword-aligned offset, the byte shift by v_alignbyte as on the global path.  A band computes, besides the rows it owns, the halo rows
+// of each level that its rows of the next level read (orb_plan.cc: orb_plan_band_segment); only owned rows are stored to the planes,
+// so a level is written once and not read back inside a segment.
+// --------------------------------------------------------------------------------------------
+#define BAND_THREADS 256   // 512 and 128 threads per band both measured slower
+
+template <bool FROM_LDS, bool TO_LDS>   // four dst rows y0 + 4 yq .. + 3 (clamped to cmp1 - 1: produced again, same bytes) x eight pixels of group g
+__device__ __forceinline__ void band_item(const int item, const BandLevel& V, const uint8_t* __restrict__ tables, const BandRows R,
+                                          const __amdgpu_buffer_rsrc_t rsrc, const unsigned ss, const uint8_t* stile, const int srow0,
+                                          const unsigned spitch, uint8_t* dtile, uint8_t* D) {
+    const int yq = (int)__umulhi((unsigned)item, V.inv_groups);
+    const int g = item - yq * V.ngroups;
+    const uint8_t* ct = tables + V.col_off + 80u * (unsigned)g;
+    const uint4 c0 = *reinterpret_cast<const uint4*>(ct), c1 = *reinterpret_cast<const uint4*>(ct + 16u), c2 = *reinterpret_cast<const uint4*>(ct + 32u),
+                c3 = *reinterpret_cast<const uint4*>(ct + 48u);
+    const uint32_t c4x = *reinterpret_cast<const uint32_t*>(ct + 64u);
+    int yrow[4];
+    uint2 rt[4];
+    const uint8_t* rtab = tables + V.row_off;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        yrow[r] = min((int)R.cmp0 + 4 * yq + r, (int)R.cmp1 - 1);
+        rt[r] = *reinterpret_cast<const uint2*>(rtab + 8u * (unsigned)yrow[r]);
+    }
+    const unsigned b = c0.x & 0xFFFFu, sh = (c0.x >> 16) & 3u;
+    const uint32_t sel[8] = {c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x}, al[8] = {c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w, c4x};
+    uint32_t w[8][4];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const unsigned srow = (r & 1) ? (rt[r >> 1].x >> 16) : (rt[r >> 1].x & 0xFFFFu);
+        if (FROM_LDS) {   // the plan keeps every source row of a computed row inside the band's rows of the level below
+            const uint32_t* p = reinterpret_cast<const uint32_t*>(stile + (__umul24(srow - (unsigned)srow0, spitch) + b));
+            w[r][0] = p[0]; w[r][1] = p[1]; w[r][2] = p[2]; w[r][3] = p[3];
+        } else {
+            const rs_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(__umul24(srow, ss) + b), 0, 0);
+            w[r][0] = v.x; w[r][1] = v.y; w[r][2] = v.z; w[r][3] = v.w;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t h[2][8];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const uint32_t* ww = w[2 * k + r];
+            const uint32_t a0 = __builtin_amdgcn_alignbyte(ww[1], ww[0], sh), a1 = __builtin_amdgcn_alignbyte(ww[2], ww[1], sh), a2 = __builtin_amdgcn_alignbyte(ww[3], ww[2], sh);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) h[r][j] = rs_dot2(__builtin_amdgcn_perm(a1, a0, sel[j]), al[j]) >> 4;
+#pragma unroll
+            for (int j = 4; j < 8; ++j) h[r][j] = rs_dot2(__builtin_amdgcn_perm(a2, a1, sel[j]), al[j]) >> 4;
+        }
+        const unsigned b0 = rt[k].y & 0xFFFFu, b1 = rt[k].y >> 16;
+        uint32_t out[2] = {0, 0};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t v = ((__umul24(b0, h[0][j]) >> 16) + (__umul24(b1, h[1][j]) >> 16) + 2u) >> 2;
+            out[j >> 2] |= (v & 0xFFu) << (8 * (j & 3));
+        }
+        if (TO_LDS) *reinterpret_cast<uint2*>(dtile + (__umul24((unsigned)(yrow[k] - (int)R.cmp0), (unsigned)V.pitch) + 8u * (unsigned)g)) = make_uint2(out[0], out[1]);
+        if (yrow[k] >= (int)R.own0 && yrow[k] < (int)R.own1)
+            *reinterpret_cast<uint2*>(D + (__umul24((unsigned)yrow[k], (unsigned)V.dstride) + 8u * (unsigned)g)) = make_uint2(out[0], out[1]);
+    }
+}
+
+__global__ __launch_bounds__(BAND_THREADS) void pyramid_bands_kernel(
+    const BandTab tab, const uint8_t* __restrict__ tables, const BandRows* __restrict__ rows, const int first, const int last, const int nbands,
+    const uint8_t* __restrict__ src, const unsigned sstride, const size_t sframe, const unsigned sbytes,
+    uint8_t* __restrict__ pyr, const size_t pyr_frame, const int tile0, const int xcd_frames) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t band_lds[];
+    int frame, band;
+    if (xcd_frames) {   // 1-D grid, frames dealt to the XCDs (see describe_kernel): the bands of a frame share their halo rows of the source in one L2
+        const unsigned w = blockIdx.x, k = w >> 3, fq = k / (unsigned)nbands;
+        frame = (int)(8u * fq + ((w + fq) & 7u));
+        if (frame >= xcd_frames) return;
+        band = (int)(k - fq * (unsigned)nbands);
+    } else { band = blockIdx.x; frame = blockIdx.y; }
+    const int nlv = last - first;
+    const BandRows* BR = rows + (size_t)band * nlv;
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src + (size_t)frame * sframe), 0, sbytes, 0x00020000);
+    uint8_t* planes = pyr + (size_t)frame * pyr_frame;
+    int srow0 = 0;
+    for (int k = 0; k < nlv; ++k) {
+        const BandLevel& V = tab.lv[first + 1 + k];
+        const BandRows R = BR[k];
+        uint8_t* dtile = band_lds + ((k & 1) ? tile0 : 0);
+        const uint8_t* stile = band_lds + ((k & 1) ? 0 : tile0);
+        const unsigned spitch = (unsigned)tab.lv[first + k].pitch;
+        uint8_t* D = planes + V.plane_off;
+        const int nitems = V.ngroups * (((int)R.cmp1 - (int)R.cmp0 + 3) >> 2);
+        const bool to_lds = k + 1 < nlv;
+        for (int item = threadIdx.x; item < nitems; item += BAND_THREADS) {
+            if (k == 0) {
+                if (to_lds) band_item<false, true>(item, V, tables, R, rsrc, sstride, stile, srow0, spitch, dtile, D);
+                else band_item<false, false>(item, V, tables, R, rsrc, sstride, stile, srow0, spitch, dtile, D);
+            } else {
+                if (to_lds) band_item<true, true>(item, V, tables, R, rsrc, sstride, stile, srow0, spitch, dtile, D);
+                else band_item<true, false>(item, V, tables, R, rsrc, sstride, stile, srow0, spitch, dtile, D);
+            }
+        }
+        srow0 = R.cmp0;
+        if (to_lds) __syncthreads();
+    }
+}
+
+void orbk_pyramid_bands(hipStream_t st, const BandTab& tab, const uint8_t* d_tables, const BandRows* d_rows, int first, int last, int nbands,
+                        const uint8_t* src, size_t sstride, size_t sframe, int sh, uint8_t* pyr, size_t pyr_frame, int tile0, int smem, int nframes) {
+    const int xcd_frames = nframes >= 16 ? nframes : 0;
+    const dim3 grid = xcd_frames ? dim3((unsigned)(((nframes + 7) / 8) * 8) * (unsigned)nbands) : dim3(nbands, nframes);
+    hipLaunchKernelGGL(pyramid_bands_kernel, grid, dim3(BAND_THREADS), smem, st, tab, d_tables, d_rows, first, last, nbands, src, (unsigned)sstride, sframe,
+                       (unsigned)(sstride * (size_t)sh), pyr, pyr_frame, tile0, xcd_frames);
+}
+
+hipError_t orbk_pyramid_bands_prepare(int smem_bytes) {
+    static int prepared = 0;   // the attribute is per function, not per handle: keep the largest request
+    if (smem_bytes <= prepared) return hipSuccess;
+    prepared = smem_bytes;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(pyramid_bands_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
+}
+
+// --------------------------------------------------------------------------------------------
 // K1 (fused): the whole pyramid in ONE launch.  Workgroup (region, frame) loads its level-0 patch
 // once, then produces level 1, 2, ... each from the previous level kept in LDS (two ping-pong
 // buffers), storing only the pixels it owns.  The chain of integer roundings is exactly the

@@ -311,6 +311,38 @@ void plan_pyramid_boxes(const slamit_orb_params& p, OrbPlan& P) {
     P.boxes.swap(boxes);
 }
 
+// Banded pyramid: which rows of which level a (frame, band) workgroup computes and which of them it stores.
+#ifndef ORB_BAND_COUNT
+#define ORB_BAND_COUNT 8    // bands per frame
+#define ORB_BAND_SPLIT 2    // the first segment ends at this level and the second reads it back from HBM; 0: one segment (measured: DESIGN.md section 4)
+#endif
+
+inline int band_pitch(int w) { return (int)round_up((size_t)((w + 7) / 8) * 8, 16); }   // whole 8-byte groups, rows on 16-byte boundaries
+
+void plan_bands(OrbPlan& P) {
+    const int nl = (int)P.levels.size();
+    if (nl < 2 || !P.rows4_ok) return;
+    for (int l = 1; l < nl; ++l) {
+        const OrbResizeTabs& T = P.rs[l];
+        if (T.col8.empty() || T.row4.empty() || P.levels[l].h >= 65536) return;   // some level keeps the four-pixel kernel
+        BandLevel& V = P.band_tab.lv[l];
+        V.ngroups = (P.levels[l].w + 7) / 8;
+        V.inv_groups = (uint32_t)((0x100000000ull + (unsigned)V.ngroups - 1) / (unsigned)V.ngroups);
+        V.dstride = P.levels[l].stride;
+        V.pitch = band_pitch(P.levels[l].w);
+        V.plane_off = P.levels[l].plane_off;
+    }
+    const int split = ORB_BAND_SPLIT > 0 && ORB_BAND_SPLIT < nl - 1 ? ORB_BAND_SPLIT : nl - 1;
+    std::vector<OrbBandSeg> segs;
+    for (int first = 0; first < nl - 1; first = segs.back().last) {
+        segs.emplace_back();
+        int nb = ORB_BAND_COUNT;   // wider frames than VGA take more, thinner bands until two tiles fit the budget
+        while (!orb_plan_band_segment(P, first, first == 0 ? split : nl - 1, nb, ORB_BAND_LDS_BUDGET, segs.back()))
+            if ((nb *= 2) > 8 * ORB_BAND_COUNT) return;
+    }
+    P.bands.swap(segs);
+}
+
 // offsets of the read-only tables in one block, each on a 256-byte boundary
 void plan_table_block(OrbPlan& P) {
     size_t off = 0;
@@ -328,6 +360,9 @@ void plan_table_block(OrbPlan& P) {
     }
     P.boxes_off = take(sizeof(PyrBox) * P.boxes.size());
     P.tabs_off = take(P.pyr_regions ? sizeof(PyrTabs) * nl : 0);
+    for (OrbBandSeg& G : P.bands) G.rows_off = take(sizeof(BandRows) * G.rows.size());
+    if (!P.bands.empty())
+        for (int l = 1; l < nl; ++l) { P.band_tab.lv[l].col_off = P.rs[l].col8_off; P.band_tab.lv[l].row_off = P.rs[l].row4_off; }
     P.table_bytes = round_up(off, 256);
 }
 
@@ -351,8 +386,41 @@ bool orb_plan(const slamit_orb_params& p, const OrbPlanOptions& o, OrbPlan& plan
     blur_strips(P);
     plan_resize(o, P);
     plan_pyramid_boxes(p, P);
+    plan_bands(P);
     plan_table_block(P);
     return true;
+}
+
+bool orb_plan_band_segment(const OrbPlan& P, int first, int last, int nbands, size_t lds_budget, OrbBandSeg& seg) {
+    const int nl = (int)P.levels.size(), nlv = last - first;
+    if (first < 0 || last >= nl || nlv < 1 || nbands < 1) return false;
+    seg = OrbBandSeg();
+    seg.first = first; seg.last = last; seg.nbands = nbands;
+    seg.rows.assign((size_t)nbands * nlv, BandRows());
+    size_t tile[2] = {0, 0};
+    for (int b = 0; b < nbands; ++b) {
+        BandRows* R = &seg.rows[(size_t)b * nlv];   // R[l - first - 1]
+        int need0 = 0, need1 = 0;                   // the rows of level l that the band's rows of level l + 1 read
+        for (int l = last; l > first; --l) {
+            const int h = P.levels[l].h;
+            if (h < nbands || h >= 65536 || P.rs[l].row4.size() < 2 * (size_t)h) return false;
+            const int own0 = (int)((long)b * h / nbands), own1 = (int)((long)(b + 1) * h / nbands);
+            const int cmp0 = l == last ? own0 : std::min(own0, need0), cmp1 = l == last ? own1 : std::max(own1, need1);
+            R[l - first - 1] = BandRows{(uint16_t)own0, (uint16_t)own1, (uint16_t)cmp0, (uint16_t)cmp1};
+            need0 = 65535; need1 = 0;
+            for (int y = cmp0; y < cmp1; ++y) {     // the row table's clamped source rows (sy0 | sy1 << 16)
+                const uint32_t s = P.rs[l].row4[2 * (size_t)y];
+                need0 = std::min(need0, (int)(s & 0xFFFFu)); need1 = std::max(need1, (int)(s >> 16) + 1);
+            }
+            if (l < last) {   // only the last level of a segment stays out of LDS
+                size_t& t = tile[(l - first - 1) & 1];
+                t = std::max(t, (size_t)(cmp1 - cmp0) * band_pitch(P.levels[l].w) + ORB_BAND_SLACK);
+            }
+        }
+    }
+    seg.tile0 = (int)round_up(tile[0], 16);
+    seg.smem = seg.tile0 + (int)round_up(tile[1], 16);
+    return (size_t)seg.smem <= lds_budget;
 }
 
 void orb_plan_image(const OrbPlan& P, const uint8_t* base, std::vector<uint8_t>& img) {
@@ -368,6 +436,7 @@ void orb_plan_image(const OrbPlan& P, const uint8_t* base, std::vector<uint8_t>&
         put_vec(T.col4_off, T.col4); put_vec(T.row4_off, T.row4); put_vec(T.col8_off, T.col8);
     }
     put_vec(P.boxes_off, P.boxes);
+    for (const OrbBandSeg& G : P.bands) put_vec(G.rows_off, G.rows);
     if (!P.pyr_regions) return;
     std::vector<PyrTabs> tabs(P.levels.size(), PyrTabs{nullptr, nullptr, nullptr, nullptr});   // level 0 has none
     auto at = [&](size_t off) { return (uintptr_t)base + off; };

@@ -1,7 +1,7 @@
 // orb_plan.h — host-side plan of an ORB extractor handle: scale tables and quotas, level geometry, the FAST cell table, the blur
-// strip tables, the cv::resize tables of every pyramid path and the fused pyramid's boxes, and where each read-only table sits in
-// the handle's one device block.  Plain C++17 (no HIP): the extractor (orb_api.hip) and the CPU test of the plan
-// (tests/test_orb_plan.py) both build it.
+// strip tables, the cv::resize tables of every pyramid path, the banded pyramid's row ranges and the fused pyramid's boxes, and where
+// each read-only table sits in the handle's one device block.  Plain C++17 (no HIP): the extractor (orb_api.hip) and the CPU tests
+// of the plan (tests/test_orb_plan.py, tests/test_orb_bands_plan.py) build it.
 #ifndef SLAMIT_ORB_PLAN_H
 #define SLAMIT_ORB_PLAN_H
 
@@ -34,6 +34,16 @@ struct OrbResizeTabs {
     size_t xofs_off, ialpha_off, yofs_off, ibeta_off, col4_off, row4_off, col8_off;   // in the table block
 };
 
+// One segment of the banded pyramid: levels first + 1 .. last of every frame in one launch, level `first` read from HBM.  A level's
+// rows are split into `nbands` owned ranges (band b of level l: rows b h / nbands .. (b + 1) h / nbands); a band computes, besides the
+// rows it owns, the rows of each level that its rows of the next level read (worked out backwards from `last`).
+struct OrbBandSeg {
+    int first, last, nbands;
+    std::vector<BandRows> rows;   // [nbands][last - first], level first + 1 first
+    int tile0, smem;              // bytes of the first LDS tile (levels first + 1, first + 3, ...) and of both tiles
+    size_t rows_off;              // in the table block
+};
+
 struct OrbPlan {
     // ORBextractor's tables (mvScaleFactor, mvInvScaleFactor, mvLevelSigma2, mvInvLevelSigma2, mnFeaturesPerLevel)
     std::vector<float> scale, inv_scale, sigma2, inv_sigma2;
@@ -55,12 +65,21 @@ struct OrbPlan {
     int pyr_regions, pyr_bufA, pyr_smem;
     std::vector<PyrBox> boxes;
     size_t levels_off, boxes_off, tabs_off;
+    // banded pyramid: the segments that build levels 1 .. nlevels - 1 between them and the per-level table; no segments: no banded
+    // plan (some level without rows8 tables, or a band that does not fit the LDS budget)
+    std::vector<OrbBandSeg> bands;
+    BandTab band_tab;
     size_t table_bytes;   // the table block
 };
 
 // Plans a handle for p.  Returns false with *why set when the geometry cannot be extracted (a level smaller than one FAST cell,
 // an aspect ratio beyond ORB_MAX_ROOTS octree roots, or more features than the LDS octree holds).  p is range-checked already.
 bool orb_plan(const slamit_orb_params& p, const OrbPlanOptions& o, OrbPlan& plan, const char** why);
+
+// Plans the rows of one banded segment (levels first + 1 .. last, level `first` the source) over the plan's resize tables; false --
+// nothing truncated -- when a level has fewer rows than bands or a band's two tiles pass lds_budget bytes.  Fills every field of
+// `seg` but rows_off.
+bool orb_plan_band_segment(const OrbPlan& plan, int first, int last, int nbands, size_t lds_budget, OrbBandSeg& seg);
 
 // The table block as the device gets it (table_bytes): every table at its offset, the PyrTabs pointing into `base` (the block's
 // device address; null gives offsets).

@@ -83,6 +83,20 @@ struct PyrTabs {               // cv::resize coefficient tables of level l (from
     const int32_t* yofs; const int16_t* ibeta;
 };
 
+// Banded pyramid (pyramid_bands_kernel): a workgroup is (frame, band of rows) and walks the levels of one segment, each level >= the
+// segment's second out of the previous one's rows held in LDS.  Per level, BY VALUE in the kernel arguments (as FastTab): where the
+// level's resize_rows8 tables sit in the table block, its plane, and the pitch of its LDS tile.
+struct BandLevel {
+    uint64_t col_off, row_off;   // bytes, in the table block: the rows8 column table and the row table
+    uint64_t plane_off;          // OrbLevel::plane_off
+    int32_t ngroups, dstride, pitch;
+    uint32_t inv_groups;         // ceil(2^32 / ngroups)
+};
+struct BandTab { BandLevel lv[ORB_MAX_LEVELS]; };
+struct BandRows { uint16_t own0, own1, cmp0, cmp1; };   // per (band, level): rows stored to HBM, rows computed (a superset)
+#define ORB_BAND_LDS_BUDGET (78 * 1024)   // both tiles of a workgroup: at least two workgroups fit a CU's 160 KB
+#define ORB_BAND_SLACK 16                 // bytes behind a tile: the 16-byte window of a row's last group may pass the row end
+
 struct OrbLevelKp {            // a keypoint in level coordinates, after the octree
     int16_t x, y;
     float response;
