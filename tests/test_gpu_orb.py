@@ -462,12 +462,40 @@ def test_guided_search_fuse_gate():
     assert np.array_equal(gm, om) and gn == on and np.array_equal(g4, o4) and gn > 0
 
 
-@pytest.mark.parametrize("n,seed,window", [(900, 1, 40), (2000, 2, 100), (300, 3, 10), (64, 4, 1000)])
+def _assert_init_case_walks_the_frame(f1, prev, f2, window, om, oacc):
+    """The fixture really reaches mode 1's re-scan of a TRUNCATED candidate list: more level-0 keypoints in every window than
+    SLAMIT_SEARCH_MAX_CAND (1024), a take-over, and a query whose tentative best is excluded at its turn.  From the inputs and the
+    oracle's result alone."""
+    x2, o2 = np.asarray(f2["kp_xy"], np.float32), np.asarray(f2["kp_octave"])
+    cell = [np.floor(((x2[:, a] - np.float32(f2[lo])) * np.float32(f2[inv])).astype(np.float64) + 0.5) for a, lo, inv in ((0, "min_x", "inv_w"), (1, "min_y", "inv_h"))]
+    cand = np.nonzero((o2 == 0) & (cell[0] >= 0) & (cell[0] < 64) & (cell[1] >= 0) & (cell[1] < 48))[0]   # Frame::PosInGrid, level [0, 0]
+    assert len(cand) > 1024, "fixture: a window must hold more than SLAMIT_SEARCH_MAX_CAND candidates"
+    queries = np.nonzero(np.asarray(f1["kp_octave"]) <= 0)[0]
+    assert (np.abs(x2[cand][None] - np.asarray(prev, np.float32)[queries][:, None]) < np.float32(window)).all(), "fixture: the window must cover the frame"
+    assert ((oacc >= 0) & (om < 0)).any(), "fixture: no take-over"
+    cand = cand[np.lexsort((cand, cell[1][cand], cell[0][cand]))]                 # GetFeaturesInArea's scan order: first minimum wins
+    bits = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(1)
+    d1, d2 = np.asarray(f1["desc"], np.uint8), np.asarray(f2["desc"], np.uint8)
+    dist = bits[d1[queries][:, None, :] ^ d2[cand][None, :, :]].sum(2)
+    nearest, dmin = cand[dist.argmin(1)], dist.min(1)
+    held = np.full(len(o2), np.iinfo(np.int32).max)                              # distance of each keypoint's current match
+    stale = 0
+    for q, kp, d in zip(queries, nearest, dmin):
+        stale += held[kp] <= d
+        if oacc[q] >= 0:
+            held[oacc[q]] = bits[d1[q] ^ d2[oacc[q]]].sum()
+    assert stale >= 1, "fixture: no query finds its tentative best excluded"
+
+
+@pytest.mark.parametrize("n,seed,window", [(900, 1, 40), (2000, 2, 100), (300, 3, 10), (64, 4, 1000), (1600, 5, 2000)])
 def test_search_for_initialization_mode(n, seed, window):
-    """Guided-search mode 1 == ORBmatcher::SearchForInitialization's loop (matched-distance gate, take-over)."""
+    """Guided-search mode 1 == ORBmatcher::SearchForInitialization's loop (matched-distance gate, take-over).  The last case puts
+    more keypoints into every window than a stored candidate list holds, so stale queries walk the frame again."""
     f1, prev, f2 = synth.synth_init_pair(n, seed)
-    gm, gn, gacc = api.ORBmatcher.search_for_initialization(f1, prev, f2, window, 0.9, 50)
     om, on, oacc = ob.search_for_initialization(f1, prev, f2, window, 0.9, 50)
+    if window == 2000:
+        _assert_init_case_walks_the_frame(f1, prev, f2, window, om, oacc)
+    gm, gn, gacc = api.ORBmatcher.search_for_initialization(f1, prev, f2, window, 0.9, 50)
     assert np.array_equal(gm, om) and gn == on and np.array_equal(gacc, oacc)
 
 

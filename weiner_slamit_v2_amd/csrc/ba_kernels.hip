@@ -42,6 +42,7 @@ typedef SLAMIT_GLOBAL double gdouble;
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
 #include "se3_device.h"
+#include "wave_ops.h"
 
 // deterministic block sum for 256-thread blocks; result valid in thread 0
 __device__ double block_sum_256(double v, double* sh /*[4]*/) {
@@ -238,9 +239,9 @@ __device__ __forceinline__ void atomic_max_bits(unsigned long long* p, double v)
 __device__ __forceinline__ double group_sum(double v) {   // sum over the BA_PG = 8 consecutive lanes of a point group
     // the xor-1 / xor-2 / xor-4 tree as three DPP exchanges (bit-identical to the __shfl_xor form, without its LDS round trips;
     // after the first two steps a quad is uniform, so the half-row mirror is as good a partner as lane ^ 4)
-    v += dpp_xchg_d<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_xchg_d<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_xchg_d<0x141>(v);   // row_half_mirror
+    v += dpp<0xB1>(v);    // quad_perm [1,0,3,2]
+    v += dpp<0x4E>(v);    // quad_perm [2,3,0,1]
+    v += dpp<0x141>(v);   // row_half_mirror
     return v;
 }
 
@@ -277,21 +278,7 @@ __global__ __launch_bounds__(256) void k_point_reduce(BaWin* wins) {
 }
 
 // ---- S3: pose blocks Hpp, bp: one workgroup of 256 threads per keyframe.  Thread-strided edge loop, then every 16-lane row
-// is summed with four DPP exchanges (no LDS round trip) and the 16 row sums of the workgroup are added in a fixed order ----
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double row16_sum(double v) {   // all 16 lanes of a DPP row end up with the row's sum
-    v += dpp_d<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_d<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_d<0x141>(v);   // row_half_mirror
-    v += dpp_d<0x140>(v);   // row_mirror
-    return v;
-}
-
+// is summed with four DPP exchanges (row16_sum: no LDS round trip) and the 16 row sums of the workgroup are added in a fixed order ----
 __device__ __forceinline__ void pose_reduce_body(const BaWin& W, BaState* st, int kf) {
     if (st->done || !st->need_linearize) return;
     if (kf >= W.n_kf) return;

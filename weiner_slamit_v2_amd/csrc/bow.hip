@@ -7,7 +7,7 @@
 // mode 0 an accepted query removes its candidate from the ones that follow; lanes hold the group's candidates (lane l:
 // list positions l, l + 64, ...; a lane's matched positions are bits of one register).  "best / second best with strict
 // '<', first one wins" is "the two smallest keys (distance << 16 | position)"; mode 1's "minimum distance, last one wins"
-// is the smallest key (distance << 16 | 0xFFFF - position).  Wave-wide minima are DPP reductions.
+// is the smallest key (distance << 16 | 0xFFFF - position).  Wave-wide minima are DPP reductions (wave_ops.h).
 // Float expressions are written exactly as the reference writes them; compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,6 +18,7 @@
 
 #include "../../include/slamit.h"
 #include "slamit_internal.h"
+#include "wave_ops.h"
 
 struct BowDev {
     int n_groups, n1;
@@ -29,21 +30,6 @@ struct BowDev {
     float scale[16], sigma2[16];
     int* match12; int* dist12; int* nmatches;
 };
-
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_u32(unsigned v) {
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
-}
-// wave-wide minimum as a wave-uniform value (four DPP exchanges inside the 16-lane rows, four v_readlane across them)
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-    v = min(v, dpp_u32<0xB1>(v));     // quad_perm [1,0,3,2]
-    v = min(v, dpp_u32<0x4E>(v));     // quad_perm [2,3,0,1]
-    v = min(v, dpp_u32<0x141>(v));    // row_half_mirror
-    v = min(v, dpp_u32<0x140>(v));    // row_mirror
-    const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)v, 0), b = (unsigned)__builtin_amdgcn_readlane((int)v, 16);
-    const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)v, 32), d = (unsigned)__builtin_amdgcn_readlane((int)v, 48);
-    return min(min(a, b), min(c, d));
-}
 
 __global__ __launch_bounds__(256) void bow_init_kernel(BowDev D) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -84,8 +70,7 @@ __global__ __launch_bounds__(64) void bow_search_kernel(BowDev D) {
             const int i2 = D.c_idx[c0 + pos];
             const uint4* dt = reinterpret_cast<const uint4*>(D.desc2 + 32 * (size_t)i2);
             const uint4 t0 = dt[0], t1 = dt[1];
-            const unsigned d = __popc(a0.x ^ t0.x) + __popc(a0.y ^ t0.y) + __popc(a0.z ^ t0.z) + __popc(a0.w ^ t0.w) +
-                               __popc(a1.x ^ t1.x) + __popc(a1.y ^ t1.y) + __popc(a1.z ^ t1.z) + __popc(a1.w ^ t1.w);
+            const unsigned d = (unsigned)hamming256(a0, a1, t0, t1);
             if (D.mode == 0) {
                 if (d >= 256u) continue;             // 'dist < bestDist1' can never hold against the initial 256
                 const unsigned k = (d << 16) | (unsigned)pos;

@@ -18,6 +18,7 @@
 
 #include "../../include/slamit.h"
 #include "slamit_internal.h"
+#include "wave_ops.h"
 
 #define HM_TILE 256      // train rows per LDS tile: two uint4 per thread
 #ifndef HM_SLICES
@@ -309,8 +310,7 @@ __global__ __launch_bounds__(256) void hamming_matrix_kernel(const uint8_t* __re
         if (i >= nq || j >= rows) continue;
         uint4 a0 = Q[2 * (size_t)i], a1 = Q[2 * (size_t)i + 1];
         uint4 t0 = tile[2 * j], t1 = tile[2 * j + 1];
-        int d = __popc(a0.x ^ t0.x) + __popc(a0.y ^ t0.y) + __popc(a0.z ^ t0.z) + __popc(a0.w ^ t0.w) +
-                __popc(a1.x ^ t1.x) + __popc(a1.y ^ t1.y) + __popc(a1.z ^ t1.z) + __popc(a1.w ^ t1.w);
+        int d = hamming256(a0, a1, t0, t1);
         out[(size_t)i * nt + j0 + j] = (uint16_t)d;
     }
 }
@@ -334,8 +334,7 @@ __global__ __launch_bounds__(64) void distinctive_kernel(const uint8_t* __restri
         const uint4 a0 = rowsd[2 * i], a1 = rowsd[2 * i + 1];
         for (int j = 0; j < n; ++j) {
             const uint4 t0 = rowsd[2 * j], t1 = rowsd[2 * j + 1];
-            const int d = __popc(a0.x ^ t0.x) + __popc(a0.y ^ t0.y) + __popc(a0.z ^ t0.z) + __popc(a0.w ^ t0.w) +
-                          __popc(a1.x ^ t1.x) + __popc(a1.y ^ t1.y) + __popc(a1.z ^ t1.z) + __popc(a1.w ^ t1.w);
+            const int d = hamming256(a0, a1, t0, t1);
             D[i * n + j] = (unsigned short)d;
         }
     }

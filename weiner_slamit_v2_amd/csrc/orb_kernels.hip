@@ -19,6 +19,7 @@
 
 #include "orb_types.h"
 #include "slamit_math.h"
+#include "wave_ops.h"
 #include "../../include/slamit.h"
 #include "../../include/slamit_orb_pattern.h"
 
@@ -542,16 +543,9 @@ __device__ __forceinline__ unsigned add_flag(unsigned v, unsigned long long mask
     return d;
 }
 
-// exclusive prefix sum of `v` over the wavefront: four DPP row shifts scan each 16-lane row, two row broadcasts carry the row
-// totals on (lane 15 -> rows 1 and 3, lane 31 -> rows 2 and 3); `total` = the sum over all lanes (wave-uniform)
+// exclusive prefix sum of `v` over the wavefront; `total` = the sum over all lanes (wave-uniform)
 __device__ __forceinline__ int wave_exclusive_scan(int v, int& total) {
-    int incl = v;
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, false);   // row_shr:1
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, false);   // row_shr:2
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, false);   // row_shr:4
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, false);   // row_shr:8
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xA, 0xF, false);   // row_bcast:15 into rows 1, 3
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xC, 0xF, false);   // row_bcast:31 into rows 2, 3
+    const int incl = wave_inclusive_scan_i32(v);
     total = __builtin_amdgcn_readlane(incl, 63);
     return incl - v;
 }
@@ -961,16 +955,7 @@ __device__ int block_exclusive_scan(int* a, int len, int* wave_tmp /*[NT / 64]*/
     const int lo = min(tid * C, len), hi = min(lo + C, len);
     int sum = 0;
     for (int i = lo; i < hi; ++i) sum += a[i];
-    // inclusive scan of `sum` across the wave: four DPP row shifts scan each 16-lane row, two row broadcasts carry the row
-    // totals on (lane 15 -> rows 1 and 3, lane 31 -> rows 2 and 3); shifted-out and masked-off lanes contribute the 0 of `old`.
-    // (As six __shfl_up steps this was six dependent ds_bpermute round trips on the kernel's critical path.)
-    int incl = sum;
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, false);   // row_shr:1
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, false);   // row_shr:2
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, false);   // row_shr:4
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, false);   // row_shr:8
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xA, 0xF, false);   // row_bcast:15 into rows 1, 3
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xC, 0xF, false);   // row_bcast:31 into rows 2, 3
+    const int incl = wave_inclusive_scan_i32(sum);   // (six __shfl_up steps here were six dependent LDS round trips on the critical path)
     if ((tid & 63) == 63) wave_tmp[tid >> 6] = incl;
     __syncthreads();
     int wbase = 0, total = 0;
@@ -1423,16 +1408,6 @@ static DiscTable make_disc() {
 #define IC_ROWS (2 * IC_R + 1)
 #define IC_PITCH 32               // 31 columns in two 16-byte chunks
 
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
-__device__ __forceinline__ int wave_sum_i32(int v) {   // the same value in every lane; no LDS round trips (ds_bpermute) involved
-    v += dpp_i32<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_i32<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_i32<0x141>(v);   // row_half_mirror
-    v += dpp_i32<0x140>(v);   // row_mirror
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
-}
-
 __global__ __launch_bounds__(256) void ic_angle_kernel(
     const OrbLevel* __restrict__ levels, int nlevels,
     const uint8_t* __restrict__ img0, size_t img0_stride, size_t img0_frame,
@@ -1513,19 +1488,19 @@ __global__ __launch_bounds__(256) void ic_angle_kernel(
     {
         const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
 #pragma unroll
-        for (int p = 0; p < 8; ++p) { const int a = V[2 * p], b = V[2 * p + 1]; V[p] = (b0 ? b : a) + dpp_i32<0xB1>(b0 ? a : b); }            // partner lane ^ 1
+        for (int p = 0; p < 8; ++p) { const int a = V[2 * p], b = V[2 * p + 1]; V[p] = (b0 ? b : a) + dpp<0xB1>(b0 ? a : b); }            // partner lane ^ 1
 #pragma unroll
-        for (int p = 0; p < 4; ++p) { const int a = V[2 * p], b = V[2 * p + 1]; V[p] = (b1 ? b : a) + dpp_i32<0x4E>(b1 ? a : b); }            // lane ^ 2
+        for (int p = 0; p < 4; ++p) { const int a = V[2 * p], b = V[2 * p + 1]; V[p] = (b1 ? b : a) + dpp<0x4E>(b1 ? a : b); }            // lane ^ 2
 #pragma unroll
-        for (int p = 0; p < 2; ++p) { const int a = V[2 * p], b = V[2 * p + 1]; V[p] = (b2 ? b : a) + dpp_i32<0x1B>(dpp_i32<0x141>(b2 ? a : b)); }   // lane ^ 4: half-row mirror, then quad reverse
-        { const int a = V[0], b = V[1]; V[0] = (b3 ? b : a) + dpp_i32<0x141>(dpp_i32<0x140>(b3 ? a : b)); }                                     // lane ^ 8: row mirror, then half-row mirror
+        for (int p = 0; p < 2; ++p) { const int a = V[2 * p], b = V[2 * p + 1]; V[p] = (b2 ? b : a) + dpp<0x1B>(dpp<0x141>(b2 ? a : b)); }   // lane ^ 4: half-row mirror, then quad reverse
+        { const int a = V[0], b = V[1]; V[0] = (b3 ? b : a) + dpp<0x141>(dpp<0x140>(b3 ? a : b)); }                                     // lane ^ 8: row mirror, then half-row mirror
     }
     __shared__ int s_rows[4][64];
     int* sr = s_rows[threadIdx.x >> 6];
     sr[lane] = V[0];
     wave_sync_lds();
     const int tot = (sr[lane & 15] + sr[(lane & 15) + 16]) + (sr[(lane & 15) + 32] + sr[(lane & 15) + 48]);   // moment number lane & 15: m10 of keypoint (lane & 15) >> 1 on even lanes, m01 on odd
-    const int my10 = tot, my01 = dpp_i32<0xB1>(tot);   // (meaningful on the even lanes 0 .. 14: keypoint lane >> 1)
+    const int my10 = tot, my01 = dpp<0xB1>(tot);   // (meaningful on the even lanes 0 .. 14: keypoint lane >> 1)
     if (lane < 2 * IC_KP_PER_WAVE && !(lane & 1) && i0 + (lane >> 1) < count) {
         const float ang = slamit_fast_atan2((float)my01, (float)my10);
         float sn, cs;

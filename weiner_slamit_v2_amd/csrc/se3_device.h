@@ -4,6 +4,8 @@
 #define SLAMIT_SE3_DEVICE_H
 #include <hip/hip_runtime.h>
 
+#include "wave_ops.h"   // wave_sum, readlane_d, dpp_quad_d: the kernels that use these helpers reduce with them
+
 // ---- small fp64 helpers (same formulas as Eigen / g2o) ---------------------------------------
 __device__ __forceinline__ void quat_rot(const double* q, const double* v, double* r) {
     double uvx = 2 * (q[1] * v[2] - q[2] * v[1]), uvy = 2 * (q[2] * v[0] - q[0] * v[2]), uvz = 2 * (q[0] * v[1] - q[1] * v[0]);
@@ -85,47 +87,6 @@ __device__ void pose_oplus(double* T, const double* u) {
     quat_normalize(nq);
     T[0] = nq[0]; T[1] = nq[1]; T[2] = nq[2]; T[3] = nq[3];
     T[4] = te[0] + rt[0]; T[5] = te[1] + rt[1]; T[6] = te[2] + rt[2];
-}
-
-// value of lane `l` (compile-time constant) as a wave-uniform scalar: v_readlane_b32 x2, no LDS
-__device__ __forceinline__ double readlane_d(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
-// quad_perm exchange in which every lane has a source (CTRL < 0x100): no zero-initialised "old" operand to set up
-template <int CTRL>
-__device__ __forceinline__ double dpp_quad_d(double v) {
-    const int l = __double2loint(v), h = __double2hiint(v);
-    const int lo = __builtin_amdgcn_update_dpp(l, l, CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(h, h, CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
-// value of lane `l` (wave-uniform, not a constant) as a wave-uniform scalar
-__device__ __forceinline__ double readlane_dyn_d(double v, int l) {
-    const int ls = __builtin_amdgcn_readfirstlane(l);
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), ls);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), ls);
-    return __hiloint2double(hi, lo);
-}
-
-// Sum over the 64 lanes, the same value in every lane, in a fixed order: four DPP exchanges make every 16-lane row hold its
-// row sum (xor 1, xor 2, half-row mirror, row mirror), four v_readlane pairs join the rows.  (The ds_bpermute form of
-// __shfl_xor is an LDS round trip per step: twelve of them per sum, and the optimisers reduce 27-35 sums per iteration.)
-template <int CTRL>
-__device__ __forceinline__ double dpp_xchg_d(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_sum(double v) {
-    v += dpp_xchg_d<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_xchg_d<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_xchg_d<0x141>(v);   // row_half_mirror
-    v += dpp_xchg_d<0x140>(v);   // row_mirror
-    return ((readlane_d(v, 0) + readlane_d(v, 16)) + readlane_d(v, 32)) + readlane_d(v, 48);
 }
 
 #endif

@@ -4,17 +4,20 @@
 // Reference: ORB_SLAM2/src/ORBmatcher.cc:47-131 and :1332-1474 (the per-query loop bodies),
 // ORB_SLAM2/src/Frame.cc:336-357, 447-517 (grid assignment and window query).
 //
-// Two kernels:
+// Two steps:
 //   search_candidates_kernel  one wavefront per query, all queries in parallel: every keypoint is tested
 //       against the window exactly as GetFeaturesInArea does (grid cell range from the reference's float
 //       expressions, level range, |dx| < r && |dy| < r); hits are appended to the query's candidate list
-//       as one u64 key  (distance << 32) | (cell_x * 48 + cell_y) << 13 | keypoint  — sorting by that key IS
-//       the reference's scan order (cells x-major, then y, then insertion = keypoint index) with the
+//       as one u64 key  (distance << 32) | (cell_x * 48 + cell_y) << 17 | keypoint << 4 | octave  — sorting by
+//       that key IS the reference's scan order (cells x-major, then y, then insertion = keypoint index) with the
 //       Hamming distance in front, and "best / second best with strict <" equals "two smallest keys".
-//   search_resolve_kernel     one wavefront walks the queries IN ORDER (the reference marks the winning
-//       keypoint as taken before it looks at the next map point): lanes hold the candidates, keypoints
-//       already taken are masked out, two wave-wide min-reductions give best and second, the acceptance
-//       rule runs, the taken bit is set in LDS.
+//   search_resolve_walk       one wavefront walks the queries IN ORDER (the reference commits the winning
+//       keypoint before it looks at the next map point): the tentative pair stands unless the per-keypoint state
+//       excludes one of the two, otherwise lanes re-scan the candidates and two wave-wide min-reductions (wave_ops.h)
+//       give best and second; then the acceptance rule runs and the state is updated in LDS.  The walk is written once;
+//       what the state is, whom it excludes and how a query is accepted comes in as a model, the way lm_block.h takes
+//       its problems: TakenBits (search_resolve_kernel: SearchByProjection / Fuse) and MatchedDist
+//       (search_resolve_init_kernel: SearchForInitialization).
 // Float expressions are written exactly as the reference writes them; compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -26,6 +29,7 @@
 
 #include "../../include/slamit.h"
 #include "slamit_internal.h"
+#include "wave_ops.h"
 
 #define GRID_COLS 64   // FRAME_GRID_COLS, include/Frame.h:41
 #define GRID_ROWS 48   // FRAME_GRID_ROWS, include/Frame.h:40
@@ -54,30 +58,7 @@ struct SearchDev {
 // scan order; the octave rides along in the low bits so the resolve step never goes back to the keypoint table
 #define KEY_KP(k) ((int)(((k) >> 4) & 8191))
 #define KEY_OCT(k) ((int)((k) & 15))
-
-// wave-wide minimum of a u64 as a wave-uniform value: four DPP exchanges make every 16-lane row uniform (xor 1, xor 2,
-// half-row mirror, row mirror), four v_readlane + scalar mins join the rows.  (The ds_bpermute form of __shfl_xor costs
-// an LDS round trip per step: 12 of them per reduction were the whole microsecond this serial loop spent per query.)
-template <int CTRL>
-__device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xF, 0xF, false);
-    return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
-}
-__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
-    return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l) << 32) |
-           (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-}
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-    unsigned long long o;
-    o = dpp_u64<0xB1>(v); v = o < v ? o : v;     // quad_perm [1,0,3,2]
-    o = dpp_u64<0x4E>(v); v = o < v ? o : v;     // quad_perm [2,3,0,1]
-    o = dpp_u64<0x141>(v); v = o < v ? o : v;    // row_half_mirror
-    o = dpp_u64<0x140>(v); v = o < v ? o : v;    // row_mirror
-    const unsigned long long a = readlane_u64(v, 0), b = readlane_u64(v, 16), c = readlane_u64(v, 32), d = readlane_u64(v, 48);
-    const unsigned long long ab = a < b ? a : b, cd = c < d ? c : d;
-    return ab < cd ? ab : cd;
-}
+#define KEY_NONE (~0ull)
 
 // A query's search window (Frame::GetFeaturesInArea, Frame.cc:452-466) and descriptor; ok = the window meets the grid.
 struct QueryWin {
@@ -119,8 +100,7 @@ __device__ __forceinline__ bool window_key(const SearchDev& D, const QueryWin& W
     if (hit) {
         const uint4* T = reinterpret_cast<const uint4*>(KD + 32 * (size_t)i);
         const uint4 t0 = T[0], t1 = T[1];
-        const int d = __popc(W.a0.x ^ t0.x) + __popc(W.a0.y ^ t0.y) + __popc(W.a0.z ^ t0.z) + __popc(W.a0.w ^ t0.w) +
-                      __popc(W.a1.x ^ t1.x) + __popc(W.a1.y ^ t1.y) + __popc(W.a1.z ^ t1.z) + __popc(W.a1.w ^ t1.w);
+        const int d = hamming256(W.a0, W.a1, t0, t1);
         hit = d < 256;   // bestDist starts at 256 and the test is a strict '<': a complement never wins
         key = ((unsigned long long)d << 32) | ((unsigned long long)(posX * GRID_ROWS + posY) << 17) |
               ((unsigned long long)i << 4) | (unsigned long long)(oct & 15);
@@ -154,197 +134,180 @@ __global__ __launch_bounds__(256) void search_candidates_kernel(SearchDev D) {
         if (hit) {
             const int o = count + __popcll(mk & ((1ull << lane) - 1ull));
             if (o < D.cand_cap) out[o] = key;
-            if (D.mode == 1 || !TK[i]) { if (key < k1) { k2 = k1; k1 = key; } else if (key < k2) k2 = key; }
+            if (D.mode == 1 || !TK[i]) keep2(k1, k2, key);
         }
         count += __popcll(mk);
     }
     // tentative (best, second): exact for the resolve pass unless an EARLIER query of this call takes one of the two
-    const unsigned long long best = wave_min_u64(k1);
-    const unsigned long long second = wave_min_u64(k1 == best ? k2 : k1);
+    unsigned long long best, second;
+    wave_min2(k1, k2, best, second);
     if (lane == 0) { D.cand_n[qo] = count; D.tent[2 * qo] = best; D.tent[2 * qo + 1] = second; }
 }
 
-// One wavefront per frame walks that frame's queries IN ORDER (the reference assigns the winning keypoint before it looks
-// at the next map point).  The candidates kernel already found every query's two smallest keys among the keypoints free
-// on entry; removing OTHER candidates cannot change the two smallest, so that pair is still the answer unless an earlier
-// query of this call took one of the two.  The walk therefore only tests two taken bits per query (64 queries' pairs
-// are loaded at once, lane j holding query j) and re-scans the candidate list on the rare conflict.
-__global__ __launch_bounds__(64) void search_resolve_kernel(SearchDev D) {
-    __shared__ unsigned taken[(SLAMIT_SEARCH_MAX_KP + 32) / 32];
+// One query's answer: the keypoint (or -1) and (best_dist, best_level, second_dist, second_level) as out4 reports them
+struct SearchHit { int res = -1, bd = 256, bl = -1, sd = 256, sl = -1; };
+
+// The serial half.  One wavefront per frame walks that frame's queries IN ORDER (the reference commits the winning keypoint before it
+// looks at the next map point).  The candidates kernel already found every query's two smallest keys among the keypoints free on
+// entry; removing OTHER candidates cannot change the two smallest, so that pair is still the answer unless the state an earlier query
+// of this call left behind excludes one of the two.  The walk therefore only asks the state about two keypoints per query (64 queries'
+// pairs are loaded at once, lane j holding query j) and re-scans the query's candidates on the rare conflict.
+//
+// What the per-keypoint state is comes in as `State`, a small struct of force-inlined members over LDS the kernel owns:
+//     void      init(D, f, n, lane)      fills the state for frame f's n keypoints and publishes it to the wavefront
+//     bool      excluded(key)            may the query this key belongs to not have the key's keypoint?
+//     void      decide(D, best, r, takes_q, lane, qb, j, res, nmatches)
+//                                        the acceptance rule for query qb + j (r: its distances) and its commit to the state; `res`
+//                                        is this lane's pending result of query qb + lane, which a take-over may reset
+//     void      end_chunk()              after a chunk's results are stored
+// The mode is the type: the loop is serial (about 1 us per query), so nothing in it is decided at run time.
+template <class State>
+__device__ __forceinline__ void search_resolve_walk(const SearchDev& D, State& S) {
     const int lane = threadIdx.x, f = blockIdx.x;
     const int n = D.n_arr ? min(D.n_arr[f], D.kp_cap) : D.n_fixed;
     const int m = D.m_arr ? min(D.m_arr[f], D.q_cap) : D.m_fixed;
-    const uint8_t* TK = D.kp_taken + (size_t)f * D.kp_cap;
-    for (int w = lane; w < (n + 31) / 32; w += 64) {
-        unsigned bits = 0;
-        for (int b = 0; b < 32; ++b) { const int i = 32 * w + b; if (i < n && TK[i]) bits |= 1u << b; }
-        taken[w] = bits;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const unsigned long long NONE = ~0ull;
+    S.init(D, f, n, lane);
     const size_t q0 = (size_t)f * D.q_cap;
     int nmatches = 0;
     for (int qb = 0; qb < m; qb += 64) {
         const int qj = qb + lane;
         const bool live = qj < m;
-        unsigned long long tb = NONE, ts = NONE;
+        unsigned long long tb = KEY_NONE, ts = KEY_NONE;
         int ncq = 0, tkq = 0;
         if (live) { tb = D.tent[2 * (q0 + qj)]; ts = D.tent[2 * (q0 + qj) + 1]; ncq = D.cand_n[q0 + qj]; tkq = D.takes[q0 + qj]; }
-        int res = -1, bd = 256, bl = -1, sd = 256, sl = -1;     // lane j collects query qb + j
+        SearchHit mine;     // lane j collects query qb + j
         const int jn = min(64, m - qb);
         for (int j = 0; j < jn; ++j) {
             unsigned long long best = readlane_u64(tb, j), second = readlane_u64(ts, j);
             const int takes_q = __builtin_amdgcn_readlane(tkq, j);
-            if (best != NONE) {
-                const int bi0 = KEY_KP(best), si0 = second != NONE ? KEY_KP(second) : bi0;
-                const bool stale = (((taken[bi0 >> 5] >> (bi0 & 31)) | (taken[si0 >> 5] >> (si0 & 31))) & 1u) != 0;
-                if (stale) {   // an earlier query of this call took one of the two: re-scan this query's candidates
-                    const size_t qo = q0 + qb + j;
-                    const int nc_all = __builtin_amdgcn_readlane(ncq, j);
-                    // The stored list is only read HERE.  The tentative pair was reduced over every hit, so a window that holds
-                    // more than cand_cap keypoints is exact as long as no re-scan of it is needed; a re-scan of a TRUNCATED list
-                    // walks the frame's keypoints again instead (the reference has no limit on a window's size, ORBmatcher.cc:85-117).
-                    unsigned long long k1 = NONE, k2 = NONE;
-                    if (nc_all <= D.cand_cap) {
-                        const unsigned long long* C = D.cand + qo * D.cand_cap;
-                        for (int c = lane; c < nc_all; c += 64) {
-                            const unsigned long long k = C[c];
-                            const int i = KEY_KP(k);
-                            if ((taken[i >> 5] >> (i & 31)) & 1u) continue;   // F.mvpMapPoints[idx] with observations
-                            if (k < k1) { k2 = k1; k1 = k; } else if (k < k2) k2 = k;
-                        }
-                    } else {
-                        QueryWin W;
-                        query_window(D, qo, W);   // (it met the grid: the query has candidates)
-                        const uint8_t* KP = D.kp + (size_t)f * D.kp_cap * D.kp_rec;
-                        const uint8_t* KD = D.kp_desc + (size_t)f * D.kp_cap * 32;
-                        for (int i = lane; i < n; i += 64) {
-                            unsigned long long k;
-                            if (!window_key(D, W, KP, KD, i, k) || ((taken[i >> 5] >> (i & 31)) & 1u)) continue;
-                            if (k < k1) { k2 = k1; k1 = k; } else if (k < k2) k2 = k;
-                        }
+            // both tests unconditionally (a lone best stands in for its second): two independent LDS reads, no branch between them
+            if (best != KEY_NONE && (S.excluded(best) | S.excluded(second != KEY_NONE ? second : best))) {   // stale: re-scan under the state as it is now
+                const size_t qo = q0 + qb + j;
+                const int nc_all = __builtin_amdgcn_readlane(ncq, j);
+                // The stored list is only read HERE.  The tentative pair was reduced over every hit, so a window that holds
+                // more than cand_cap keypoints is exact as long as no re-scan of it is needed; a re-scan of a TRUNCATED list
+                // walks the frame's keypoints again instead (the reference has no limit on a window's size, ORBmatcher.cc:85-117).
+                unsigned long long k1 = KEY_NONE, k2 = KEY_NONE;
+                if (nc_all <= D.cand_cap) {
+                    const unsigned long long* C = D.cand + qo * D.cand_cap;
+                    for (int c = lane; c < nc_all; c += 64) {
+                        const unsigned long long k = C[c];
+                        if (!S.excluded(k)) keep2(k1, k2, k);
                     }
-                    best = wave_min_u64(k1);
-                    second = wave_min_u64(k1 == best ? k2 : k1);
-                }
-            }
-            int r_res = -1, r_bd = 256, r_bl = -1, r_sd = 256, r_sl = -1;
-            if (best != NONE) {
-                const int bi = KEY_KP(best);
-                r_bd = (int)(best >> 32); r_bl = KEY_OCT(best);
-                if (second != NONE) { r_sd = (int)(second >> 32); r_sl = KEY_OCT(second); }
-                if (r_bd <= D.th_dist) {   // ORBmatcher.cc:120-128
-                    const bool reject = D.use_ratio && r_bl == r_sl && (float)r_bd > D.nnratio * (float)r_sd;
-                    if (!reject) {
-                        r_res = bi;
-                        if (takes_q) {
-                            if (lane == 0) taken[bi >> 5] |= 1u << (bi & 31);
-                            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                            __builtin_amdgcn_wave_barrier();
-                        }
-                        ++nmatches;
+                } else {
+                    QueryWin W;
+                    query_window(D, qo, W);   // (it met the grid: the query has candidates)
+                    const uint8_t* KP = D.kp + (size_t)f * D.kp_cap * D.kp_rec;
+                    const uint8_t* KD = D.kp_desc + (size_t)f * D.kp_cap * 32;
+                    for (int i = lane; i < n; i += 64) {
+                        unsigned long long k;
+                        if (window_key(D, W, KP, KD, i, k) && !S.excluded(k)) keep2(k1, k2, k);
                     }
                 }
+                wave_min2(k1, k2, best, second);
             }
-            if (lane == j) { res = r_res; bd = r_bd; bl = r_bl; sd = r_sd; sl = r_sl; }
+            SearchHit r;
+            if (best != KEY_NONE) {
+                r.bd = (int)(best >> 32);
+                if (second != KEY_NONE) { r.sd = (int)(second >> 32); r.sl = KEY_OCT(second); }
+                S.decide(D, best, r, takes_q, lane, qb, j, mine.res, nmatches);
+            }
+            if (lane == j) mine = r;
         }
         if (live) {
             const size_t qo = q0 + qj;
-            D.match_kp[qo] = res;
-            if (D.out4) *reinterpret_cast<int4*>(&D.out4[4 * qo]) = make_int4(bd, bl, sd, sl);
+            D.match_kp[qo] = mine.res;
+            if (D.out4) *reinterpret_cast<int4*>(&D.out4[4 * qo]) = make_int4(mine.bd, mine.bl, mine.sd, mine.sl);
         }
+        S.end_chunk();
     }
     if (lane == 0) D.nmatches[f] = nmatches;
 }
 
-// mode 1 (ORBmatcher::SearchForInitialization): the per-keypoint state is the distance of its current match and the query
-// that holds it.  Same speculation: the tentative pair is exact unless one of the two is excluded by the state
-// (matched distance <= this query's distance to it); otherwise the query's candidates are re-scanned with the exclusion.
-__global__ __launch_bounds__(64) void search_resolve_init_kernel(SearchDev D) {
-    extern __shared__ int s_state[];   // md[kp_cap] | m21[kp_cap]
-    const int lane = threadIdx.x, f = blockIdx.x;
-    const int n = D.n_arr ? min(D.n_arr[f], D.kp_cap) : D.n_fixed;
-    const int m = D.m_arr ? min(D.m_arr[f], D.q_cap) : D.m_fixed;
-    int* md = s_state;
-    int* m21 = s_state + D.kp_cap;
-    for (int i = lane; i < n; i += 64) { md[i] = 0x7FFFFFFF; m21[i] = -1; }
+// publishes lane 0's write to the LDS state before the next query reads it
+__device__ __forceinline__ void search_state_publish() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const unsigned long long NONE = ~0ull;
-    const size_t q0 = (size_t)f * D.q_cap;
-    int nmatches = 0;
-    for (int qb = 0; qb < m; qb += 64) {
-        const int qj = qb + lane;
-        const bool live = qj < m;
-        unsigned long long tb = NONE, ts = NONE;
-        int ncq = 0;
-        if (live) { tb = D.tent[2 * (q0 + qj)]; ts = D.tent[2 * (q0 + qj) + 1]; ncq = D.cand_n[q0 + qj]; }
-        int res = -1, bd = 256, bl = -1, sd = 256, sl = -1;
-        const int jn = min(64, m - qb);
-        for (int j = 0; j < jn; ++j) {
-            unsigned long long best = readlane_u64(tb, j), second = readlane_u64(ts, j);
-            if (best != NONE) {
-                const bool xb = md[KEY_KP(best)] <= (int)(best >> 32);
-                const bool xs = second != NONE && md[KEY_KP(second)] <= (int)(second >> 32);
-                if (xb || xs) {
-                    const size_t qo = q0 + qb + j;
-                    const int nc_all = __builtin_amdgcn_readlane(ncq, j);
-                    unsigned long long k1 = NONE, k2 = NONE;
-                    if (nc_all <= D.cand_cap) {
-                        const unsigned long long* C = D.cand + qo * D.cand_cap;
-                        for (int c = lane; c < nc_all; c += 64) {
-                            const unsigned long long k = C[c];
-                            if (md[KEY_KP(k)] <= (int)(k >> 32)) continue;   // ORBmatcher.cc:448
-                            if (k < k1) { k2 = k1; k1 = k; } else if (k < k2) k2 = k;
-                        }
-                    } else {   // a truncated list: walk the frame's keypoints again (see search_resolve_kernel)
-                        QueryWin W;
-                        query_window(D, qo, W);
-                        const uint8_t* KP = D.kp + (size_t)f * D.kp_cap * D.kp_rec;
-                        const uint8_t* KD = D.kp_desc + (size_t)f * D.kp_cap * 32;
-                        for (int i = lane; i < n; i += 64) {
-                            unsigned long long k;
-                            if (!window_key(D, W, KP, KD, i, k) || md[i] <= (int)(k >> 32)) continue;
-                            if (k < k1) { k2 = k1; k1 = k; } else if (k < k2) k2 = k;
-                        }
-                    }
-                    best = wave_min_u64(k1);
-                    second = wave_min_u64(k1 == best ? k2 : k1);
-                }
-            }
-            int r_res = -1, r_bd = 256, r_bl = -1, r_sd = 256, r_sl = -1;
-            if (best != NONE) {
-                const int bi = KEY_KP(best);
-                r_bd = (int)(best >> 32); r_bl = -1;
-                float second_f = 2147483648.0f;   // (float)INT_MAX
-                if (second != NONE) { r_sd = (int)(second >> 32); r_sl = KEY_OCT(second); second_f = (float)r_sd; }
-                if (r_bd <= D.th_dist && (float)r_bd < second_f * D.nnratio) {   // ORBmatcher.cc:462-464
-                    const int old = m21[bi];
-                    if (old >= 0) {   // the keypoint changes hands: vnMatches12[vnMatches21[bestIdx2]] = -1
-                        if (old >= qb) { if (lane == old - qb) res = -1; }
-                        else if (lane == 0) D.match_kp[q0 + old] = -1;
-                        --nmatches;
-                    }
-                    r_res = bi;
-                    r_bl = bi;   // mode 1 reports the keypoint accepted AT DECISION TIME in the level slot (levels are all 0
-                                 // here); unlike match_kp it is not reset by a later take-over -- the rotation histogram bins it
-                    if (lane == 0) { m21[bi] = qb + j; md[bi] = r_bd; }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    ++nmatches;
-                }
-            }
-            if (lane == j) { res = r_res; bd = r_bd; bl = r_bl; sd = r_sd; sl = r_sl; }
+}
+
+// mode 0 (SearchByProjection, Fuse): a keypoint is free or taken, F.mvpMapPoints[idx] with observations; a query with `takes` set
+// takes the keypoint it is matched to.  ORBmatcher.cc:85-128.
+struct TakenBits {
+    unsigned* taken;   // LDS bit mask, one bit per keypoint
+    __device__ __forceinline__ void init(const SearchDev& D, int f, int n, int lane) {
+        const uint8_t* TK = D.kp_taken + (size_t)f * D.kp_cap;
+        for (int w = lane; w < (n + 31) / 32; w += 64) {
+            unsigned bits = 0;
+            for (int b = 0; b < 32; ++b) { const int i = 32 * w + b; if (i < n && TK[i]) bits |= 1u << b; }
+            taken[w] = bits;
         }
-        if (live) {
-            const size_t qo = q0 + qj;
-            D.match_kp[qo] = res;
-            if (D.out4) *reinterpret_cast<int4*>(&D.out4[4 * qo]) = make_int4(bd, bl, sd, sl);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");   // later chunks may reset entries of this one through global memory
+        search_state_publish();
     }
-    if (lane == 0) D.nmatches[f] = nmatches;
+    __device__ __forceinline__ bool excluded(unsigned long long key) const {
+        const int i = KEY_KP(key);
+        return (taken[i >> 5] >> (i & 31)) & 1u;
+    }
+    __device__ __forceinline__ void decide(const SearchDev& D, unsigned long long best, SearchHit& r, int takes_q, int lane, int, int, int&, int& nmatches) {
+        const int bi = KEY_KP(best);
+        r.bl = KEY_OCT(best);
+        if (r.bd <= D.th_dist) {   // ORBmatcher.cc:120-128
+            const bool reject = D.use_ratio && r.bl == r.sl && (float)r.bd > D.nnratio * (float)r.sd;
+            if (!reject) {
+                r.res = bi;
+                if (takes_q) {
+                    if (lane == 0) taken[bi >> 5] |= 1u << (bi & 31);
+                    search_state_publish();
+                }
+                ++nmatches;
+            }
+        }
+    }
+    __device__ __forceinline__ void end_chunk() const {}
+};
+
+// mode 1 (ORBmatcher::SearchForInitialization, ORBmatcher.cc:409-474): a keypoint carries the distance of its current match and the
+// query that holds it.  A candidate is excluded when that distance is <= the query's own (:448); an accepted query takes the keypoint
+// over and the previous holder loses it (:466-470).
+struct MatchedDist {
+    int* md;    // LDS, per keypoint: distance of its current match (INT_MAX: none)
+    int* m21;   // LDS, per keypoint: the query holding it, or -1
+    __device__ __forceinline__ void init(const SearchDev&, int, int n, int lane) {
+        for (int i = lane; i < n; i += 64) { md[i] = 0x7FFFFFFF; m21[i] = -1; }
+        search_state_publish();
+    }
+    __device__ __forceinline__ bool excluded(unsigned long long key) const { return md[KEY_KP(key)] <= (int)(key >> 32); }
+    __device__ __forceinline__ void decide(const SearchDev& D, unsigned long long best, SearchHit& r, int, int lane, int qb, int j, int& res, int& nmatches) {
+        const int bi = KEY_KP(best);
+        const float second_f = r.sl < 0 ? 2147483648.0f /* no second: (float)INT_MAX */ : (float)r.sd;
+        if (r.bd <= D.th_dist && (float)r.bd < second_f * D.nnratio) {   // ORBmatcher.cc:462-464
+            const int old = m21[bi];
+            if (old >= 0) {   // the keypoint changes hands: vnMatches12[vnMatches21[bestIdx2]] = -1
+                if (old >= qb) { if (lane == old - qb) res = -1; }   // the holder is of this chunk: its result is still in a lane
+                else if (lane == 0) D.match_kp[(size_t)blockIdx.x * D.q_cap + old] = -1;
+                --nmatches;
+            }
+            r.res = bi;
+            r.bl = bi;   // mode 1 reports the keypoint accepted AT DECISION TIME in the level slot (levels are all 0
+                         // here); unlike match_kp it is not reset by a later take-over -- the rotation histogram bins it
+            if (lane == 0) { m21[bi] = qb + j; md[bi] = r.bd; }
+            search_state_publish();
+            ++nmatches;
+        }
+    }
+    // later chunks may reset entries of this one through global memory
+    __device__ __forceinline__ void end_chunk() const { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent"); }
+};
+
+__global__ __launch_bounds__(64) void search_resolve_kernel(SearchDev D) {
+    __shared__ unsigned taken[(SLAMIT_SEARCH_MAX_KP + 32) / 32];
+    TakenBits S{taken};
+    search_resolve_walk(D, S);
+}
+
+__global__ __launch_bounds__(64) void search_resolve_init_kernel(SearchDev D) {
+    extern __shared__ int s_state[];   // md[kp_cap] | m21[kp_cap]
+    MatchedDist S{s_state, s_state + D.kp_cap};
+    search_resolve_walk(D, S);
 }
 
 static void search_launch(hipStream_t st, const SearchDev& D, int max_m) {
@@ -356,6 +319,13 @@ static void search_launch(hipStream_t st, const SearchDev& D, int max_m) {
         hipLaunchKernelGGL(search_resolve_init_kernel, dim3(D.nframes), dim3(64), 2 * sizeof(int) * (size_t)D.kp_cap, st, D);
     } else
         hipLaunchKernelGGL(search_resolve_kernel, dim3(D.nframes), dim3(64), 0, st, D);
+}
+
+// the rule half of SearchDev, the same for both entry points
+static void search_rule_fill(SearchDev& D, const slamit_search_rule* rule) {
+    D.th_dist = rule->th_dist; D.use_ratio = rule->use_ratio; D.nnratio = rule->nnratio;
+    D.chi2_gate = rule->mode == 1 ? 0.f : rule->chi2_gate; memcpy(D.inv_sigma2, rule->inv_level_sigma2, sizeof(D.inv_sigma2));
+    D.mode = rule->mode;
 }
 
 extern "C" int slamit_guided_search(int device, const slamit_frame_view* F, const slamit_search_queries* Q,
@@ -402,9 +372,7 @@ extern "C" int slamit_guided_search(int device, const slamit_frame_view* F, cons
     D.min_x = F->min_x; D.min_y = F->min_y; D.inv_w = F->inv_w; D.inv_h = F->inv_h;
     D.uvr = uvr.at(S.dev); D.lmin = l0.at(S.dev); D.lmax = l1.at(S.dev); D.qdesc = qd.at(S.dev); D.valid = va.at(S.dev); D.takes = tq.at(S.dev);
     D.cand = cand.at(S.dev); D.cand_n = cn.at(S.dev); D.tent = te.at(S.dev);
-    D.th_dist = rule->th_dist; D.use_ratio = rule->use_ratio; D.nnratio = rule->nnratio;
-    D.chi2_gate = rule->mode == 1 ? 0.f : rule->chi2_gate; memcpy(D.inv_sigma2, rule->inv_level_sigma2, sizeof(D.inv_sigma2));
-    D.mode = rule->mode;
+    search_rule_fill(D, rule);
     D.match_kp = mk.at(S.dev); D.out4 = o4.at(S.dev); D.nmatches = nm.at(S.dev);
     search_launch(S.st, D, Q->m);
     HIP_TRY_AT("slamit_guided_search", slamit_stage_download_and_wait(S, L));
@@ -449,9 +417,7 @@ extern "C" int slamit_guided_search_batch_dev(int device, const slamit_search_ba
     D.cand = reinterpret_cast<unsigned long long*>(d_workspace);
     D.tent = D.cand + nq * SLAMIT_SEARCH_BATCH_CAND;
     D.cand_n = reinterpret_cast<int*>(D.tent + 2 * nq);
-    D.th_dist = rule->th_dist; D.use_ratio = rule->use_ratio; D.nnratio = rule->nnratio;
-    D.chi2_gate = rule->mode == 1 ? 0.f : rule->chi2_gate; memcpy(D.inv_sigma2, rule->inv_level_sigma2, sizeof(D.inv_sigma2));
-    D.mode = rule->mode;
+    search_rule_fill(D, rule);
     D.match_kp = d_match_kp; D.out4 = d_out4; D.nmatches = d_nmatches;
     search_launch((hipStream_t)stream, D, B->q_cap);
     HIP_TRY(hipGetLastError());

@@ -1,0 +1,123 @@
+// wave_ops.h — what the kernels do across the 64 lanes of a wavefront: DPP exchanges, v_readlane broadcasts, the reductions and the
+// scan built from them, and the two idioms of the matchers that sit on top (256-bit Hamming distance, two smallest keys).
+//
+// Why DPP: __shfl_xor / __shfl_up compile to ds_bpermute, an LDS round trip per step, six dependent steps per reduction (twelve for a
+// 64-bit value).  In the serial loops that reduce -- one query, one vocabulary node, one Levenberg sum after the other -- those round
+// trips WERE the loop time (the whole microsecond the guided search spent per query; 27-35 sums per optimiser iteration).  A DPP operand
+// reads another lane of the 16-lane row for free, so every reduction here is four exchanges that leave each row uniform (xor 1, xor 2,
+// half-row mirror, row mirror), then four v_readlane (lanes 0 / 16 / 32 / 48) joined on the scalar side: a wave-uniform result.
+#ifndef SLAMIT_WAVE_OPS_H
+#define SLAMIT_WAVE_OPS_H
+#include <hip/hip_runtime.h>
+
+// ---- exchanges and broadcasts ---------------------------------------------------------------------------------------------------
+// lane's partner under DPP control CTRL (0xB1 quad_perm [1,0,3,2], 0x4E quad_perm [2,3,0,1], 0x141 row_half_mirror, 0x140 row_mirror);
+// a lane without a source reads 0.  64-bit values are two 32-bit exchanges.
+template <int CTRL>
+__device__ __forceinline__ int dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false); }
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp(unsigned long long v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xF, 0xF, false);
+    return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+// quad_perm exchange in which every lane has a source (CTRL < 0x100): no zero-initialised "old" operand to set up
+template <int CTRL>
+__device__ __forceinline__ double dpp_quad_d(double v) {
+    const int l = __double2loint(v), h = __double2hiint(v);
+    const int lo = __builtin_amdgcn_update_dpp(l, l, CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(h, h, CTRL, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+
+// value of lane `l` (compile-time constant or wave-uniform) as a wave-uniform scalar: v_readlane_b32 x2, no LDS
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l) << 32) |
+           (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
+}
+__device__ __forceinline__ double readlane_d(double v, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+// the same for a lane index the compiler cannot prove uniform
+__device__ __forceinline__ double readlane_dyn_d(double v, int l) {
+    const int ls = __builtin_amdgcn_readfirstlane(l);
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), ls);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), ls);
+    return __hiloint2double(hi, lo);
+}
+
+// ---- reductions over the 64 lanes, the same value in every lane -----------------------------------------------------------------
+__device__ __forceinline__ double row16_sum(double v) {   // all 16 lanes of a DPP row end up with the row's sum
+    v += dpp<0xB1>(v);
+    v += dpp<0x4E>(v);
+    v += dpp<0x141>(v);
+    v += dpp<0x140>(v);
+    return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {   // in a fixed order, part of the numerics: BA, pose and Sim3 depend on it bit for bit
+    v = row16_sum(v);
+    return ((readlane_d(v, 0) + readlane_d(v, 16)) + readlane_d(v, 32)) + readlane_d(v, 48);
+}
+__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
+    v = min(v, dpp<0xB1>(v));
+    v = min(v, dpp<0x4E>(v));
+    v = min(v, dpp<0x141>(v));
+    v = min(v, dpp<0x140>(v));
+    const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)v, 0), b = (unsigned)__builtin_amdgcn_readlane((int)v, 16);
+    const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)v, 32), d = (unsigned)__builtin_amdgcn_readlane((int)v, 48);
+    return min(min(a, b), min(c, d));
+}
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+    unsigned long long o;
+    o = dpp<0xB1>(v); v = o < v ? o : v;
+    o = dpp<0x4E>(v); v = o < v ? o : v;
+    o = dpp<0x141>(v); v = o < v ? o : v;
+    o = dpp<0x140>(v); v = o < v ? o : v;
+    const unsigned long long a = readlane_u64(v, 0), b = readlane_u64(v, 16), c = readlane_u64(v, 32), d = readlane_u64(v, 48);
+    const unsigned long long ab = a < b ? a : b, cd = c < d ? c : d;
+    return ab < cd ? ab : cd;
+}
+
+// inclusive prefix sum over the wavefront: four DPP row shifts scan each 16-lane row, two row broadcasts carry the row totals on
+// (lane 15 -> rows 1 and 3, lane 31 -> rows 2 and 3); shifted-out and masked-off lanes contribute the 0 of `old`.  Lane 63 holds the total.
+__device__ __forceinline__ int wave_inclusive_scan_i32(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);   // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);   // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);   // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);   // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);   // row_bcast:15 into rows 1, 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);   // row_bcast:31 into rows 2, 3
+    return v;
+}
+
+// ---- matcher idioms -------------------------------------------------------------------------------------------------------------
+// Hamming distance of two 256-bit ORB descriptors held as uint4 halves
+__device__ __forceinline__ int hamming256(uint4 a0, uint4 a1, uint4 t0, uint4 t1) {
+    return __popc(a0.x ^ t0.x) + __popc(a0.y ^ t0.y) + __popc(a0.z ^ t0.z) + __popc(a0.w ^ t0.w) +
+           __popc(a1.x ^ t1.x) + __popc(a1.y ^ t1.y) + __popc(a1.z ^ t1.z) + __popc(a1.w ^ t1.w);
+}
+// (k1, k2) = this lane's two smallest keys so far; keys are unique, ~0 = none
+__device__ __forceinline__ void keep2(unsigned long long& k1, unsigned long long& k2, unsigned long long k) {
+    // (selects on the values: as an if / else on the two references the stores merge into one through a selected address,
+    //  and the pair then lives in scratch memory)
+    const bool first = k < k1;
+    k2 = first ? k1 : (k < k2 ? k : k2);
+    k1 = first ? k : k1;
+}
+// the two smallest keys of the wavefront from every lane's pair: one lane holds the best, its runner-up competes for second
+__device__ __forceinline__ void wave_min2(unsigned long long k1, unsigned long long k2, unsigned long long& best, unsigned long long& second) {
+    best = wave_min_u64(k1);
+    second = wave_min_u64(k1 == best ? k2 : k1);
+}
+
+#endif
