@@ -216,8 +216,8 @@ int slamit_guided_search(int device, const slamit_frame_view* frame, const slami
 /* ---- Vocabulary-node search (beyond SURVEY.md §8f: the BoW drivers of ORBmatcher) ----------------------
  * The loop bodies of ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...) (src/ORBmatcher.cc:161-290),
  * ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, ...) (:526-657) and ORBmatcher::SearchForTriangulation (:659-826):
- * features of the two sides that fall into the same vocabulary node (DBoW2::FeatureVector, built by the reference's
- * vendored DBoW2 on the host) are compared with DescriptorDistance.  A group = one node present on both sides:
+ * features of the two sides that fall into the same vocabulary node (DBoW2::FeatureVector: slamit_voc_transform below, or the
+ * reference's vendored DBoW2 on the host) are compared with DescriptorDistance.  A group = one node present on both sides:
  * its side-1 feature indices in processing order (queries) and its side-2 feature indices in scan order (candidates).
  * A feature belongs to one node, so groups are independent (checked: an index may appear once per side); one
  * wavefront walks a group's queries in order.
@@ -260,6 +260,73 @@ typedef struct slamit_bow_rule {
 int slamit_bow_search(int device, const uint8_t* desc1, int32_t n1, const uint8_t* valid1, const uint8_t* desc2, int32_t n2,
                       const uint8_t* valid2, const slamit_bow_groups* groups, const slamit_bow_rule* rule, int32_t* match12,
                       int32_t* dist12, int32_t* nmatches);
+
+/* ---- Vocabulary transform (Frame::ComputeBoW / KeyFrame::ComputeBoW) -----------------------------------
+ * mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4) (src/Frame.cc:520-527, src/KeyFrame.cc:63-72) of the
+ * reference's vendored DBoW2 (Thirdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1133-1201, :1225-1266): every
+ * descriptor descends the vocabulary tree (per level the child of least Hamming distance, strict '<', first one wins),
+ * then the frame's words become the BowVector (Thirdparty/DBoW2/src/BowVector.cpp:34-46, :62-84) and its nodes `levelsup`
+ * levels above the leaves the FeatureVector (Thirdparty/DBoW2/src/FeatureVector.cpp:31-45) that slamit_bow_groups is
+ * cut from.  Every id in and out is the reference's: node ids count the text file's lines from 1 (0 = root), word ids
+ * count its leaves from 0.  The BowVector equals the reference's bit for bit: its fp64 sums run in the reference's order.
+ *
+ * A vocabulary arrives as arrays (entry i describes node i + 1) or as the text file of
+ * TemplatedVocabulary::loadFromTextFile (:1345-1440).  Built: weighting TF_IDF (0) or TF (1) with scoring L1_NORM (0),
+ * which is what the ORB vocabulary ("10 6 0 0") uses; anything else fails with SLAMIT_ERR_ARG, as does a parent id that
+ * is not smaller than the node's own, more than SLAMIT_VOC_MAX_K children, a depth beyond SLAMIT_VOC_MAX_L, an is_leaf
+ * flag that disagrees with "has no children" (the descent stops on children.empty()), or a header outside the bounds
+ * of :1377.  Two departures from the reference, both where it reads something it never wrote:
+ *  - an empty line (the text file's last one, which the reference's while(!f.eof()) loop at :1396 turns into a phantom
+ *    child of the root) is skipped;
+ *  - a leaf reached ABOVE level L - levelsup (unbalanced trees) leaves the reference's node id uninitialised (:1158,
+ *    :1258); here it is the leaf's own id.  With L - levelsup <= 0 it is the root, 0, as in the reference (:1234). */
+#define SLAMIT_VOC_MAX_K 20          /* children per node (:1377) */
+#define SLAMIT_VOC_MAX_L 10          /* levels below the root (:1377) */
+#define SLAMIT_VOC_MAX_FEATURES 8191 /* descriptors per frame (= SLAMIT_SEARCH_MAX_KP) */
+
+typedef struct slamit_voc_desc {
+    int32_t k, L;              /* the header's branching factor and depth; L - levelsup is the FeatureVector's level */
+    int32_t scoring;           /* 0 = L1_NORM */
+    int32_t weighting;         /* 0 = TF_IDF, 1 = TF */
+    int32_t n_nodes;           /* nodes without the root; entry i of the arrays is node id i + 1 */
+    const int32_t* parent;     /* n_nodes: parent node id, 0 = root */
+    const uint8_t* is_leaf;    /* n_nodes */
+    const uint8_t* desc;       /* n_nodes x 32: centroids */
+    const double* weight;      /* n_nodes: a word's weight; <= 0 stops the word */
+} slamit_voc_desc;
+
+typedef struct slamit_voc slamit_voc;
+
+int slamit_voc_create(const slamit_voc_desc* desc, int device, slamit_voc** out);
+int slamit_voc_load_text(const char* path, int device, slamit_voc** out);
+void slamit_voc_destroy(slamit_voc* v);
+/* any out pointer may be NULL; n_nodes excludes the root, n_words counts the leaves */
+int slamit_voc_info(const slamit_voc* v, int32_t* k, int32_t* L, int32_t* n_nodes, int32_t* n_words);
+
+/* One frame, host pointers.  A vocabulary is shared between threads (tracking and local mapping both call ComputeBoW):
+ * the handle is const here and the call keeps its state in the calling thread's scratch.
+ * word_id / node_id: n entries each, word_id[i] = -1 for a stopped word (weight <= 0), which enters neither vector.
+ * BowVector: *bow_n unique word ids ascending in bow_word with their normalised values in bow_value (capacity n).
+ * FeatureVector as CSR: *fv_n unique node ids ascending in fv_node (capacity n), the features of node j are
+ * fv_items[fv_ptr[j] .. fv_ptr[j + 1]) ascending; fv_ptr has capacity n + 1, fv_items n.  Entries past the counts are
+ * not written.  (bow_n, bow_word, bow_value) and (fv_n, fv_node, fv_ptr, fv_items) may each be NULL as a whole.
+ * n == 0 writes *bow_n = *fv_n = 0; n > SLAMIT_VOC_MAX_FEATURES fails with SLAMIT_ERR_CAPACITY. */
+int slamit_voc_transform(const slamit_voc* v, const uint8_t* desc, int n, int levelsup, int32_t* word_id, int32_t* node_id,
+                         int32_t* bow_n, int32_t* bow_word, double* bow_value, int32_t* fv_n, int32_t* fv_node,
+                         int32_t* fv_ptr, int32_t* fv_items);
+
+/* nframes frames resident in HBM as slamit_orb_extract_batch_dev writes them (frame f: d_desc + f * cap * 32, d_n[f]
+ * descriptors).  Outputs are [nframes][cap] strided (d_fv_ptr [nframes][cap + 1], d_bow_n / d_fv_n [nframes]); the same
+ * pairs may be NULL.  Asynchronous on `stream` (NULL: the legacy default stream of the vocabulary's device), no
+ * synchronisation, no state in the handle: the scratch is the caller's workspace of slamit_voc_transform_workspace()
+ * bytes.  The host cannot see d_n without waiting for the device, so a frame whose d_n[f] lies outside [0, cap] is
+ * reported by the device: it writes d_bow_n[f] = d_fv_n[f] = -1 and nothing else for that frame. */
+size_t slamit_voc_transform_workspace(int nframes, int cap);
+int slamit_voc_transform_batch_dev(const slamit_voc* v, const uint8_t* d_desc, const int32_t* d_n, int cap, int nframes,
+                                   int levelsup, int32_t* d_word_id, int32_t* d_node_id, int32_t* d_bow_n,
+                                   int32_t* d_bow_word, double* d_bow_value, int32_t* d_fv_n, int32_t* d_fv_node,
+                                   int32_t* d_fv_ptr, int32_t* d_fv_items, void* d_workspace, size_t workspace_bytes,
+                                   void* stream);
 
 /* ---- Frame epilogue -------------------------------------------------------
  * What Frame's constructors do right after the extractor: Frame::UndistortKeyPoints (src/Frame.cc:529-559, through

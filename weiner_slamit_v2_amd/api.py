@@ -115,6 +115,14 @@ class Sim3RansacResult(C.Structure):
 SIM3_RANSAC_MAX_N, SIM3_RANSAC_MAX_HYP = 8192, 1024   # SLAMIT_SIM3_RANSAC_MAX_N / _MAX_HYP
 
 
+class VocDesc(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32), ("n_nodes", C.c_int32),
+                ("parent", C.c_void_p), ("is_leaf", C.c_void_p), ("desc", C.c_void_p), ("weight", C.c_void_p)]
+
+
+VOC_MAX_K, VOC_MAX_L, VOC_MAX_FEATURES = 20, 10, 8191   # SLAMIT_VOC_MAX_K / _MAX_L / _MAX_FEATURES
+
+
 class SearchBatch(C.Structure):
     _fields_ = [("nframes", C.c_int32), ("kp_cap", C.c_int32), ("q_cap", C.c_int32), ("d_n", C.c_void_p),
                 ("d_kps_un", C.c_void_p), ("d_desc", C.c_void_p), ("d_kp_taken", C.c_void_p), ("min_x", C.c_float),
@@ -151,7 +159,8 @@ EXPORTS = [
     "slamit_orb_create", "slamit_orb_destroy", "slamit_orb_tables", "slamit_orb_max_keypoints",
     "slamit_orb_extract", "slamit_orb_extract_batch", "slamit_orb_extract_batch_dev", "slamit_orb_level",
     "slamit_orb_debug_candidates", "slamit_orb_debug_blurred", "slamit_orb_profile", "slamit_hamming_best2", "slamit_hamming_best2_batch_dev",
-    "slamit_hamming_matrix", "slamit_distinctive_batch", "slamit_guided_search", "slamit_guided_search_workspace", "slamit_guided_search_batch_dev", "slamit_bow_search", "slamit_undistort_points", "slamit_frame_finish",
+    "slamit_hamming_matrix", "slamit_distinctive_batch", "slamit_guided_search", "slamit_guided_search_workspace", "slamit_guided_search_batch_dev", "slamit_bow_search", "slamit_voc_create", "slamit_voc_load_text", "slamit_voc_destroy", "slamit_voc_info",
+    "slamit_voc_transform", "slamit_voc_transform_workspace", "slamit_voc_transform_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
     "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
@@ -202,6 +211,15 @@ def lib():
         L.slamit_sim3_ransac_batch.argtypes = [i32, i32, C.POINTER(Sim3RansacProblem), C.POINTER(Sim3RansacResult)]
         L.slamit_sim3_ransac.argtypes = [i32, C.POINTER(Sim3RansacProblem), C.POINTER(Sim3RansacResult)]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
+        L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
+        L.slamit_voc_load_text.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
+        L.slamit_voc_destroy.argtypes = [vp]
+        L.slamit_voc_destroy.restype = None
+        L.slamit_voc_info.argtypes = [vp, vp, vp, vp, vp]
+        L.slamit_voc_transform.argtypes = [vp, vp, i32, i32] + [vp] * 9
+        L.slamit_voc_transform_workspace.argtypes = [i32, i32]
+        L.slamit_voc_transform_workspace.restype = sz
+        L.slamit_voc_transform_batch_dev.argtypes = [vp, vp, vp, i32, i32, i32] + [vp] * 9 + [vp, sz, vp]
         L.slamit_undistort_points.argtypes = [i32, C.POINTER(Camera), vp, i32, vp]
         L.slamit_frame_finish.argtypes = [i32, C.POINTER(Camera), vp, i32, f32, f32, f32, f32, vp, vp, vp]
         L.slamit_frame_finish_batch_dev.argtypes = [i32, C.POINTER(Camera), vp, vp, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp]
@@ -591,6 +609,107 @@ class ORBmatcher:
             d_q.data_ptr(), d_nq.data_ptr(), d_q.stride(0), d_t.data_ptr(), d_nt.data_ptr(), d_t.stride(0), p, max_n,
             d_idx.data_ptr(), d_best.data_ptr(), d_second.data_ptr(), d_idx.stride(0), device, stream),
             "slamit_hamming_best2_batch_dev")
+
+
+class ORBVocabulary:
+    """ORBVocabulary (include/ORBVocabulary.h: DBoW2's TemplatedVocabulary over ORB descriptors) on one GPU: the transform of
+    Frame::ComputeBoW / KeyFrame::ComputeBoW.  Node and word ids are the reference's (text-file order)."""
+
+    def __init__(self, handle, device):
+        self._h, self.device = handle, device
+
+    @classmethod
+    def from_arrays(cls, k, L, parent, is_leaf, desc, weight, scoring=0, weighting=0, device=0):
+        """Entry i of the arrays is node i + 1 (0 = root): parent (n) i32, is_leaf (n) u8, desc (n, 32) u8, weight (n) f64."""
+        parent = np.ascontiguousarray(parent, np.int32)
+        n = len(parent)
+        is_leaf = np.ascontiguousarray(is_leaf, np.uint8)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        weight = np.ascontiguousarray(weight, np.float64)
+        if len(is_leaf) != n or len(desc) != n or len(weight) != n:
+            raise SlamitError("ORBVocabulary.from_arrays: parent / is_leaf / desc / weight do not have the same length")
+        d = VocDesc(int(k), int(L), int(scoring), int(weighting), n, parent.ctypes.data, is_leaf.ctypes.data, desc.ctypes.data,
+                    weight.ctypes.data)
+        h = C.c_void_p()
+        _check(lib().slamit_voc_create(C.byref(d), device, C.byref(h)), "slamit_voc_create")
+        return cls(h, device)
+
+    @classmethod
+    def load_text(cls, path, device=0):
+        """TemplatedVocabulary::loadFromTextFile."""
+        h = C.c_void_p()
+        _check(lib().slamit_voc_load_text(os.fsencode(path), device, C.byref(h)), "slamit_voc_load_text")
+        return cls(h, device)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            lib().slamit_voc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{"k", "L", "n_nodes" (without the root), "n_words"}."""
+        v = [C.c_int32() for _ in range(4)]
+        _check(lib().slamit_voc_info(self._h, *[C.byref(x) for x in v]), "slamit_voc_info")
+        return dict(zip(("k", "L", "n_nodes", "n_words"), (x.value for x in v)))
+
+    def transform(self, desc, levelsup=4, bow=True, fv=True):
+        """One frame's descriptors (n, 32) u8 -> dict: word_id (n; -1 = stopped word), node_id (n); with bow: bow_word, bow_value
+        (the BowVector: unique word ids ascending, normalised values); with fv: fv_node, fv_ptr, fv_items (the FeatureVector as
+        CSR: features of node j are fv_items[fv_ptr[j]:fv_ptr[j + 1]])."""
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n = len(desc)
+        m = max(n, 1)
+        word, node = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        bn, fn = C.c_int32(0), C.c_int32(0)
+        bw, bv = np.zeros(m, np.int32), np.zeros(m, np.float64)
+        fnode, fptr, fitems = np.zeros(m, np.int32), np.zeros(m + 1, np.int32), np.zeros(m, np.int32)
+        _check(lib().slamit_voc_transform(
+            self._h, _np_ptr(desc), n, int(levelsup), _np_ptr(word), _np_ptr(node),
+            C.byref(bn) if bow else None, _np_ptr(bw) if bow else None, _np_ptr(bv) if bow else None,
+            C.byref(fn) if fv else None, _np_ptr(fnode) if fv else None, _np_ptr(fptr) if fv else None,
+            _np_ptr(fitems) if fv else None), "slamit_voc_transform")
+        out = {"word_id": word[:n], "node_id": node[:n]}
+        if bow:
+            out.update(bow_word=bw[:bn.value].copy(), bow_value=bv[:bn.value].copy())
+        if fv:
+            out.update(fv_node=fnode[:fn.value].copy(), fv_ptr=fptr[:fn.value + 1].copy(), fv_items=fitems[:fptr[fn.value]].copy())
+        return out
+
+    @staticmethod
+    def transform_workspace(nframes, cap):
+        return int(lib().slamit_voc_transform_workspace(nframes, cap))
+
+    def transform_batch_dev(self, t, levelsup=4, stream=None):
+        """Batched device form.  t: dict of torch CUDA tensors desc (B, cap, 32) u8 and n (B) i32 as extract_batch_dev writes them,
+        word_id / node_id (B, cap) i32, workspace (bytes,) u8, and optionally (as a whole) bow_n (B) i32, bow_word (B, cap) i32,
+        bow_value (B, cap) f64 and / or fv_n (B) i32, fv_node (B, cap) i32, fv_ptr (B, cap + 1) i32, fv_items (B, cap) i32.
+        Asynchronous; a frame whose n lies outside [0, cap] gets bow_n = fv_n = -1."""
+        b, cap = t["desc"].shape[0], t["desc"].shape[1]
+        opt = [t[k].data_ptr() if t.get(k) is not None else None
+               for k in ("bow_n", "bow_word", "bow_value", "fv_n", "fv_node", "fv_ptr", "fv_items")]
+        _check(lib().slamit_voc_transform_batch_dev(
+            self._h, t["desc"].data_ptr(), t["n"].data_ptr(), cap, b, int(levelsup), t["word_id"].data_ptr(), t["node_id"].data_ptr(),
+            *opt, t["workspace"].data_ptr(), t["workspace"].numel(), stream), "slamit_voc_transform_batch_dev")
+
+    @staticmethod
+    def groups(fv1, fv2):
+        """The vocabulary nodes two FeatureVectors share, ascending -- what the lower_bound walk of SearchByBoW visits
+        (ORBmatcher.cc:178-270) -- as the groups dict ORBmatcher.bow_search takes.  fv1 / fv2: dicts with fv_node, fv_ptr, fv_items."""
+        n1, n2 = np.asarray(fv1["fv_node"]), np.asarray(fv2["fv_node"])
+        _, i1, i2 = np.intersect1d(n1, n2, assume_unique=True, return_indices=True)
+        g = {"q_ptr": [0], "q_idx": [], "c_ptr": [0], "c_idx": []}
+        for a, b in zip(i1, i2):
+            g["q_idx"].extend(fv1["fv_items"][fv1["fv_ptr"][a]:fv1["fv_ptr"][a + 1]])
+            g["c_idx"].extend(fv2["fv_items"][fv2["fv_ptr"][b]:fv2["fv_ptr"][b + 1]])
+            g["q_ptr"].append(len(g["q_idx"]))
+            g["c_ptr"].append(len(g["c_idx"]))
+        return {k: np.asarray(v, np.int32) for k, v in g.items()}
 
 
 def _ba_problem(arrs):

@@ -88,6 +88,30 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
     return ab < cd ? ab : cd;
 }
 
+// minimum over a lane group of 16 (one DPP row) or 32 (two rows), the same value in every lane of the group; groups are independent,
+// so a wavefront reduces four (two) of them at once.  The step between the two rows of a 32-group is a ds_swizzle (xor 16), which
+// goes through the LDS crossbar without touching LDS memory.  Every lane of a group must be active.
+__device__ __forceinline__ unsigned long long row16_min_u64(unsigned long long v) {
+    unsigned long long o;
+    o = dpp<0xB1>(v); v = o < v ? o : v;
+    o = dpp<0x4E>(v); v = o < v ? o : v;
+    o = dpp<0x141>(v); v = o < v ? o : v;
+    o = dpp<0x140>(v); v = o < v ? o : v;
+    return v;
+}
+template <int G>
+__device__ __forceinline__ unsigned long long group_min_u64(unsigned long long v) {
+    static_assert(G == 16 || G == 32, "lane groups are one or two DPP rows");
+    v = row16_min_u64(v);
+    if (G == 32) {
+        const int lo = __builtin_amdgcn_ds_swizzle((int)(unsigned)v, 0x401F);           // and 0x1F, or 0, xor 0x10
+        const int hi = __builtin_amdgcn_ds_swizzle((int)(unsigned)(v >> 32), 0x401F);
+        const unsigned long long o = ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
 // inclusive prefix sum over the wavefront: four DPP row shifts scan each 16-lane row, two row broadcasts carry the row totals on
 // (lane 15 -> rows 1 and 3, lane 31 -> rows 2 and 3); shifted-out and masked-off lanes contribute the 0 of `old`.  Lane 63 holds the total.
 __device__ __forceinline__ int wave_inclusive_scan_i32(int v) {

@@ -28,6 +28,7 @@
 #include "Optimizer.h"
 #include "FrameOps.h"
 #include "Sim3Solver.h"
+#include "ORBVocabulary.h"
 
 using namespace ORB_SLAM2;
 
