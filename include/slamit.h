@@ -328,6 +328,49 @@ int slamit_voc_transform_batch_dev(const slamit_voc* v, const uint8_t* d_desc, c
                                    int32_t* d_fv_ptr, int32_t* d_fv_items, void* d_workspace, size_t workspace_bytes,
                                    void* stream);
 
+/* ---- Keyframe database (KeyFrameDatabase, ORBVocabulary::score) -----------------------------------------
+ * What KeyFrameDatabase::DetectLoopCandidates / DetectRelocalizationCandidates (src/KeyFrameDatabase.cc:84-206, :208-328)
+ * read from the inverted file and from L1Scoring::score (Thirdparty/DBoW2/src/ScoringObject.cpp:23-68), computed densely:
+ * the handle keeps every keyframe's BowVector in HBM (the forward index, no inverted file) and one pass compares a query
+ * with all of them.  Per slot that pass gives
+ *   common      how many word ids the two vectors share (mnLoopWords / mnRelocWords); -1 for a dead slot
+ *   first_word  the smallest shared word id, -1 if there is none
+ *   seq         the slot's value of a 64-bit counter that add / add_dev advance and nothing sets back: the keyframe's
+ *               position in every list of the reference's inverted file (push_back at :52-53; erase keeps the order of the
+ *               rest).  The reference's walk (:94-112, :219-237) first meets the keyframes in (first_word, seq) order.
+ *   score       L1Scoring::score as a double, bit for bit: from 0.0, one term fabs(vi - wi) - fabs(vi) - fabs(wi) per shared
+ *               word in ascending word id (vi the query's value), left to right and uncontracted, then -sum / 2.0.
+ *               Written as 0.0, and meaningless, where common < 1.
+ * Everything after that (the minCommonWords filter, the covisibility sums) is host logic over the caller's graph:
+ * shim/KeyFrameDatabase.h, api.KeyFrameDatabase.
+ *
+ * A slot holds up to max_words (<= SLAMIT_VOC_MAX_FEATURES) words; add takes the lowest free slot and fails with
+ * SLAMIT_ERR_CAPACITY when there is none.  Word ids are strictly ascending (a BowVector is a std::map): the host forms check
+ * that, before they look at the handle, and fail with SLAMIT_ERR_ARG; the _dev forms take what slamit_voc_transform_batch_dev
+ * wrote for one frame (d_bow_n: one int) and store or read a count outside [0, max_words] / [0, cap] as an empty vector.
+ * add_dev and query_batch_dev are asynchronous on `stream` and never wait for the device; the handle orders them against
+ * each other and against its host forms with events of its own, so no call sees a slot half written.  A handle is used by
+ * one thread at a time.  erase of a dead slot is a no-op (the reference's erase of an absent keyframe, :56-75). */
+typedef struct slamit_kfdb slamit_kfdb;
+
+int slamit_kfdb_create(int max_kf, int max_words, int device, slamit_kfdb** out);
+void slamit_kfdb_destroy(slamit_kfdb* db);
+int slamit_kfdb_clear(slamit_kfdb* db);
+/* any out pointer may be NULL */
+int slamit_kfdb_info(const slamit_kfdb* db, int32_t* max_kf, int32_t* max_words, int32_t* n_live);
+int slamit_kfdb_add(slamit_kfdb* db, const int32_t* bow_word, const double* bow_value, int n, int32_t* slot);
+int slamit_kfdb_add_dev(slamit_kfdb* db, const int32_t* d_bow_n, const int32_t* d_bow_word, const double* d_bow_value,
+                        void* stream, int32_t* slot);
+int slamit_kfdb_erase(slamit_kfdb* db, int slot);
+/* One query, host pointers; common / first_word / seq / score have max_kf entries each, indexed by slot (seq may be NULL;
+ * it is -1 for a dead slot).  The call's workspace lives in the calling thread's scratch. */
+int slamit_kfdb_query(slamit_kfdb* db, const int32_t* bow_word, const double* bow_value, int n, int32_t* common,
+                      int32_t* first_word, int64_t* seq, double* score);
+/* nq queries resident in HBM as slamit_voc_transform_batch_dev writes them (query q: d_bow_word + q * cap, d_bow_n[q]
+ * entries); outputs are [nq][max_kf]. */
+int slamit_kfdb_query_batch_dev(slamit_kfdb* db, const int32_t* d_bow_n, const int32_t* d_bow_word, const double* d_bow_value,
+                                int cap, int nq, int32_t* d_common, int32_t* d_first_word, double* d_score, void* stream);
+
 /* ---- Frame epilogue -------------------------------------------------------
  * What Frame's constructors do right after the extractor: Frame::UndistortKeyPoints (src/Frame.cc:529-559, through
  * cv::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK)) and Frame::AssignFeaturesToGrid (:336-357, PosInGrid

@@ -160,7 +160,9 @@ EXPORTS = [
     "slamit_orb_extract", "slamit_orb_extract_batch", "slamit_orb_extract_batch_dev", "slamit_orb_level",
     "slamit_orb_debug_candidates", "slamit_orb_debug_blurred", "slamit_orb_profile", "slamit_hamming_best2", "slamit_hamming_best2_batch_dev",
     "slamit_hamming_matrix", "slamit_distinctive_batch", "slamit_guided_search", "slamit_guided_search_workspace", "slamit_guided_search_batch_dev", "slamit_bow_search", "slamit_voc_create", "slamit_voc_load_text", "slamit_voc_destroy", "slamit_voc_info",
-    "slamit_voc_transform", "slamit_voc_transform_workspace", "slamit_voc_transform_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
+    "slamit_voc_transform", "slamit_voc_transform_workspace", "slamit_voc_transform_batch_dev",
+    "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
+    "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
     "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
@@ -220,6 +222,16 @@ def lib():
         L.slamit_voc_transform_workspace.argtypes = [i32, i32]
         L.slamit_voc_transform_workspace.restype = sz
         L.slamit_voc_transform_batch_dev.argtypes = [vp, vp, vp, i32, i32, i32] + [vp] * 9 + [vp, sz, vp]
+        L.slamit_kfdb_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+        L.slamit_kfdb_destroy.argtypes = [vp]
+        L.slamit_kfdb_destroy.restype = None
+        L.slamit_kfdb_clear.argtypes = [vp]
+        L.slamit_kfdb_info.argtypes = [vp, vp, vp, vp]
+        L.slamit_kfdb_add.argtypes = [vp, vp, vp, i32, vp]
+        L.slamit_kfdb_add_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.slamit_kfdb_erase.argtypes = [vp, i32]
+        L.slamit_kfdb_query.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+        L.slamit_kfdb_query_batch_dev.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
         L.slamit_undistort_points.argtypes = [i32, C.POINTER(Camera), vp, i32, vp]
         L.slamit_frame_finish.argtypes = [i32, C.POINTER(Camera), vp, i32, f32, f32, f32, f32, vp, vp, vp]
         L.slamit_frame_finish_batch_dev.argtypes = [i32, C.POINTER(Camera), vp, vp, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp]
@@ -710,6 +722,191 @@ class ORBVocabulary:
             g["q_ptr"].append(len(g["q_idx"]))
             g["c_ptr"].append(len(g["c_idx"]))
         return {k: np.asarray(v, np.int32) for k, v in g.items()}
+
+
+def _min_common_words(max_common):
+    """int minCommonWords = maxCommonWords*0.8f (KeyFrameDatabase.cc:129, :254): the product in float, truncated."""
+    return int(np.float32(max_common) * np.float32(0.8))
+
+
+class KeyFrameDatabase:
+    """KeyFrameDatabase (include/KeyFrameDatabase.h) on one GPU.  Keyframes are slots; the device holds their BowVectors and compares
+    a query with all of them (query), the rest of DetectLoopCandidates / DetectRelocalizationCandidates is host logic in the
+    reference's order over the per-slot members the reference keeps in KeyFrame (mnLoopQuery, mnLoopWords, mLoopScore, mnRelocQuery,
+    mnRelocWords, mRelocScore: self.state, reset when a slot is added; the two scores start at 0.0f, which the reference leaves
+    uninitialised)."""
+
+    STATE_DTYPE = np.dtype([("mnLoopQuery", "<i8"), ("mnLoopWords", "<i4"), ("mLoopScore", "<f4"),
+                            ("mnRelocQuery", "<i8"), ("mnRelocWords", "<i4"), ("mRelocScore", "<f4")])
+
+    def __init__(self, max_kf, max_words, device=0):
+        h = C.c_void_p()
+        _check(lib().slamit_kfdb_create(int(max_kf), int(max_words), device, C.byref(h)), "slamit_kfdb_create")
+        self._h, self.device, self.max_kf, self.max_words = h, device, int(max_kf), int(max_words)
+        self.state = np.zeros(self.max_kf, self.STATE_DTYPE)
+        self._next_loop_id = 1
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            lib().slamit_kfdb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{"max_kf", "max_words", "n_live"}."""
+        v = [C.c_int32() for _ in range(3)]
+        _check(lib().slamit_kfdb_info(self._h, *[C.byref(x) for x in v]), "slamit_kfdb_info")
+        return dict(zip(("max_kf", "max_words", "n_live"), (x.value for x in v)))
+
+    def add(self, bow_word, bow_value):
+        """A keyframe's BowVector (word ids strictly ascending, values) -> its slot, the lowest free one."""
+        w, v = np.ascontiguousarray(bow_word, np.int32), np.ascontiguousarray(bow_value, np.float64)
+        if len(w) != len(v):
+            raise SlamitError("KeyFrameDatabase.add: bow_word and bow_value do not have the same length")
+        s = C.c_int32(-1)
+        _check(lib().slamit_kfdb_add(self._h, _np_ptr(w), _np_ptr(v), len(w), C.byref(s)), "slamit_kfdb_add")
+        self.state[s.value] = 0
+        return s.value
+
+    def add_dev(self, bow_n, bow_word, bow_value, stream=None):
+        """The same from torch CUDA tensors as transform_batch_dev wrote one frame: bow_n (1,) i32, bow_word (cap,) i32, bow_value
+        (cap,) f64.  Asynchronous."""
+        s = C.c_int32(-1)
+        _check(lib().slamit_kfdb_add_dev(self._h, bow_n.data_ptr(), bow_word.data_ptr(), bow_value.data_ptr(), stream, C.byref(s)),
+               "slamit_kfdb_add_dev")
+        self.state[s.value] = 0
+        return s.value
+
+    def erase(self, slot):
+        _check(lib().slamit_kfdb_erase(self._h, int(slot)), "slamit_kfdb_erase")
+
+    def clear(self):
+        _check(lib().slamit_kfdb_clear(self._h), "slamit_kfdb_clear")
+
+    def query(self, bow_word, bow_value):
+        """-> (common i32, first_word i32, seq i64, score f64), max_kf entries each, by slot (slamit.h)."""
+        w, v = np.ascontiguousarray(bow_word, np.int32), np.ascontiguousarray(bow_value, np.float64)
+        if len(w) != len(v):
+            raise SlamitError("KeyFrameDatabase.query: bow_word and bow_value do not have the same length")
+        common, first = np.zeros(self.max_kf, np.int32), np.zeros(self.max_kf, np.int32)
+        seq, score = np.zeros(self.max_kf, np.int64), np.zeros(self.max_kf, np.float64)
+        _check(lib().slamit_kfdb_query(self._h, _np_ptr(w), _np_ptr(v), len(w), _np_ptr(common), _np_ptr(first), _np_ptr(seq), _np_ptr(score)),
+               "slamit_kfdb_query")
+        return common, first, seq, score
+
+    def query_batch_dev(self, t, stream=None):
+        """t: dict of torch CUDA tensors bow_n (nq) i32, bow_word (nq, cap) i32, bow_value (nq, cap) f64 and the outputs common,
+        first_word (nq, max_kf) i32, score (nq, max_kf) f64.  Asynchronous."""
+        nq, cap = t["bow_word"].shape[0], t["bow_word"].shape[1]
+        _check(lib().slamit_kfdb_query_batch_dev(self._h, t["bow_n"].data_ptr(), t["bow_word"].data_ptr(), t["bow_value"].data_ptr(), cap, nq,
+                                                 t["common"].data_ptr(), t["first_word"].data_ptr(), t["score"].data_ptr(), stream),
+               "slamit_kfdb_query_batch_dev")
+
+    def _sharing(self, query_bow):
+        """The slots that share a word with the query, in the order the reference's walk over the inverted file first meets them
+        (KeyFrameDatabase.cc:94-112, :219-237): by (first shared word, position in that word's list)."""
+        common, first, seq, score = self.query(*query_bow)
+        slots = np.flatnonzero(common >= 1)
+        return slots[np.lexsort((seq[slots], first[slots]))].tolist(), common, score
+
+    @staticmethod
+    def _retain(acc, min_to_retain):
+        out, seen = [], set()
+        for a, s in acc:                                                    # :191-202, :313-325
+            if a > min_to_retain and s not in seen:
+                out.append(s)
+                seen.add(s)
+        return out
+
+    def DetectLoopCandidates(self, query_bow, connected_slots, neighbours, min_score, query_id=None):
+        """KeyFrameDatabase::DetectLoopCandidates (:84-206).  query_bow = (bow_word, bow_value) of pKF, connected_slots the slots of
+        pKF->GetConnectedKeyFrames(), neighbours[slot] the slots of GetBestCovisibilityKeyFrames(10) of that keyframe in its order,
+        query_id pKF->mnId (default: a fresh one).  -> the candidates' slots in the reference's order."""
+        if query_id is None:
+            query_id, self._next_loop_id = self._next_loop_id, self._next_loop_id + 1
+        st, f32 = self.state, np.float32
+        min_score = f32(min_score)
+        connected = set(int(s) for s in connected_slots)
+        order, common, score = self._sharing(query_bow)
+        sharing = []
+        for s in order:
+            if st["mnLoopQuery"][s] != query_id:                            # :101
+                if s not in connected:                                      # :104-108
+                    st["mnLoopQuery"][s] = query_id
+                    st["mnLoopWords"][s] = common[s]
+                    sharing.append(s)
+                else:
+                    st["mnLoopWords"][s] = 1                                # :103 at every meeting, :110 after it
+            else:
+                st["mnLoopWords"][s] += common[s]                           # :110 alone
+        if not sharing:
+            return []
+        min_common = _min_common_words(max(int(st["mnLoopWords"][s]) for s in sharing))   # :121-129
+        scored = []
+        for s in sharing:                                                   # :134-148
+            if st["mnLoopWords"][s] > min_common:
+                si = f32(score[s])                                          # :142 float si = score()
+                st["mLoopScore"][s] = si
+                if si >= min_score:
+                    scored.append((si, s))
+        if not scored:
+            return []
+        acc, best_acc = [], min_score                                       # :154
+        for si, s in scored:                                                # :157-182
+            best, a, best_s = si, si, s
+            for s2 in neighbours[s]:
+                if st["mnLoopQuery"][s2] == query_id and st["mnLoopWords"][s2] > min_common:
+                    a = f32(a + st["mLoopScore"][s2])
+                    if st["mLoopScore"][s2] > best:
+                        best_s, best = s2, st["mLoopScore"][s2]
+            acc.append((a, best_s))
+            if a > best_acc:
+                best_acc = a
+        return self._retain(acc, f32(f32(0.75) * best_acc))                 # :185
+
+    def DetectRelocalizationCandidates(self, query_bow, query_id, neighbours):
+        """KeyFrameDatabase::DetectRelocalizationCandidates (:208-328); query_id is F->mnId.  A neighbour counts when it shares any
+        word with this query (:292); its mRelocScore is this query's only if it also passed minCommonWords, else what an earlier
+        query left in self.state."""
+        st, f32 = self.state, np.float32
+        order, common, score = self._sharing(query_bow)
+        sharing = []
+        for s in order:
+            if st["mnRelocQuery"][s] != query_id:                           # :227-234
+                st["mnRelocQuery"][s] = query_id
+                st["mnRelocWords"][s] = common[s]
+                sharing.append(s)
+            else:
+                st["mnRelocWords"][s] += common[s]
+        if not sharing:
+            return []
+        min_common = _min_common_words(max(int(st["mnRelocWords"][s]) for s in sharing))   # :247-254
+        scored = []
+        for s in sharing:                                                   # :261-272
+            if st["mnRelocWords"][s] > min_common:
+                si = f32(score[s])
+                st["mRelocScore"][s] = si
+                scored.append((si, s))
+        if not scored:
+            return []
+        acc, best_acc = [], f32(0)                                          # :278
+        for si, s in scored:                                                # :281-306
+            best, a, best_s = si, si, s
+            for s2 in neighbours[s]:
+                if st["mnRelocQuery"][s2] != query_id:
+                    continue
+                a = f32(a + st["mRelocScore"][s2])
+                if st["mRelocScore"][s2] > best:
+                    best_s, best = s2, st["mRelocScore"][s2]
+            acc.append((a, best_s))
+            if a > best_acc:
+                best_acc = a
+        return self._retain(acc, f32(f32(0.75) * best_acc))                 # :309
 
 
 def _ba_problem(arrs):

@@ -1,12 +1,14 @@
 // ORBVocabulary.h — ORB_SLAM2::ORBVocabulary (include/ORBVocabulary.h: DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>) above the
 // C-ABI: the part of the class that Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cc:520-527, src/KeyFrame.cc:63-72) and
 // System's start-up (loadFromTextFile) use.  transform() runs on the device (slamit_voc_transform); the two maps it fills have the
-// shapes shim/ORBmatcher.h accepts as DBoW2::BowVector / DBoW2::FeatureVector.  Not here: vocabulary creation, score(), the
-// keyframe database.  A loaded vocabulary may be used by several threads at once, as the reference's is: transform() is const and
+// shapes shim/ORBmatcher.h accepts as DBoW2::BowVector / DBoW2::FeatureVector.  score() is L1Scoring::score restated on the host, for
+// the dozen calls of LoopClosing.cc:149; the keyframe database is shim/KeyFrameDatabase.h.  Not here: vocabulary creation.
+// A loaded vocabulary may be used by several threads at once, as the reference's is: transform() is const and
 // the call's state lives in the calling thread.
 #ifndef SLAMIT_SHIM_ORBVOCABULARY_H
 #define SLAMIT_SHIM_ORBVOCABULARY_H
 
+#include <math.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -89,6 +91,28 @@ public:
             fit->second.assign(fitems.begin() + fptr[j], fitems.begin() + fptr[j + 1]);
         }
     }
+
+    // TemplatedVocabulary::score for L1_NORM (Thirdparty/DBoW2/src/ScoringObject.cpp:23-68), the only scoring slamit_voc_create
+    // accepts: one term per shared word in ascending word id, added from 0.0, then -sum / 2.  Both maps ascend, so stepping the one
+    // with the smaller id visits the same words in the same order as the reference's lower_bound walk: the same double, bit for bit
+    // (slamit_kfdb_query returns it for a whole database at once).
+    double score(const DBoW2::BowVector& v1, const DBoW2::BowVector& v2) const {
+        DBoW2::BowVector::const_iterator a = v1.begin(), b = v2.begin();
+        double sum = 0.0;
+        while (a != v1.end() && b != v2.end()) {
+            if (a->first < b->first) ++a;
+            else if (b->first < a->first) ++b;
+            else {
+                const double vi = a->second, wi = b->second;
+                sum += fabs(vi - wi) - fabs(vi) - fabs(wi);
+                ++a;
+                ++b;
+            }
+        }
+        return -sum / 2.0;
+    }
+
+    int device() const { return mDevice; }   // the GPU this vocabulary lives on (shim/KeyFrameDatabase.h puts its handle there too)
 
 private:
     int mDevice;

@@ -29,6 +29,7 @@
 #include "FrameOps.h"
 #include "Sim3Solver.h"
 #include "ORBVocabulary.h"
+#include "KeyFrameDatabase.h"
 
 using namespace ORB_SLAM2;
 
