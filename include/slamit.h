@@ -641,6 +641,46 @@ typedef struct slamit_sim3_ransac_result {
 int slamit_sim3_ransac_batch(int device, int nproblems, const slamit_sim3_ransac_problem* probs, slamit_sim3_ransac_result* results);
 int slamit_sim3_ransac(int device, const slamit_sim3_ransac_problem* prob, slamit_sim3_ransac_result* res);
 
+/* ---- CreateNewMapPoints: batched two-view triangulation (local mapping, between SearchForTriangulation and the new map point) ----
+ * The per-pair body of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:348-483), monocular: parallax of the two rays, the
+ * 4x4 linear triangulation (smallest right singular vector, one-sided Jacobi in float), both depth tests, both reprojection
+ * gates (5.991 sigma2) and the scale-consistency test; float / double exactly where the reference has them (csrc/triangulate.h).
+ * One problem is one (current keyframe, neighbour) pair with its n matched keypoints; one lane per pair, a batch is one launch.
+ * status[i] is the first gate that rejected pair i, in the reference's order:
+ *   0 accepted   1 parallax   2 w == 0   3 z1 <= 0   4 z2 <= 0   5 reprojection in keyframe 1   6 reprojection in keyframe 2
+ *   7 dist1 == 0 or dist2 == 0   8 scale consistency
+ * x3d[3i..] is the point of pair i (zero for codes 1 and 2, which have none).  Stereo keypoints are not handled: there is no
+ * right-image coordinate in the problem.  n above SLAMIT_TRIANGULATE_MAX_N, n_levels outside [1, SLAMIT_MAX_LEVELS], an octave
+ * outside [0, n_levels) or a null array with n > 0 fails with SLAMIT_ERR_ARG and a message before anything is launched;
+ * n == 0 and nproblems == 0 are valid and write nothing but n_accepted = 0. */
+#define SLAMIT_TRIANGULATE_MAX_N 8192      /* pairs per problem (the keypoints of a frame) */
+
+typedef struct slamit_triangulate_problem {
+    float Tcw1[12], Tcw2[12];      /* row-major 3x4 poses of the current keyframe and of the neighbour */
+    float intr1[6], intr2[6];      /* fx fy cx cy invfx invfy of each keyframe */
+    int32_t n;                     /* matched pairs */
+    int32_t n_levels;              /* entries of the four tables */
+    const float* kp1_xy;           /* n x 2: mvKeysUn[idx1].pt, gathered by the match indices */
+    const float* kp2_xy;           /* n x 2 */
+    const int32_t* octave1;        /* n: mvKeysUn[idx1].octave */
+    const int32_t* octave2;        /* n */
+    const float* scale_factors1;   /* n_levels: mvScaleFactors of the current keyframe */
+    const float* level_sigma2_1;   /* n_levels: mvLevelSigma2 */
+    const float* scale_factors2;   /* n_levels: the neighbour's */
+    const float* level_sigma2_2;   /* n_levels */
+    float ratio_factor;            /* 1.5f * mfScaleFactor (:260) */
+} slamit_triangulate_problem;
+
+typedef struct slamit_triangulate_result {
+    uint8_t* status;               /* n out */
+    float* x3d;                    /* n x 3 out */
+    int32_t n_accepted;            /* out: pairs with status 0 */
+} slamit_triangulate_result;
+
+/* nproblems keyframe pairs in one launch (host pointers, synchronous). */
+int slamit_triangulate_batch(int device, int nproblems, const slamit_triangulate_problem* probs, slamit_triangulate_result* results);
+int slamit_triangulate(int device, const slamit_triangulate_problem* prob, slamit_triangulate_result* res);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 
 const char* slamit_last_error(void);

@@ -115,6 +115,20 @@ class Sim3RansacResult(C.Structure):
 SIM3_RANSAC_MAX_N, SIM3_RANSAC_MAX_HYP = 8192, 1024   # SLAMIT_SIM3_RANSAC_MAX_N / _MAX_HYP
 
 
+class TriangulateProblem(C.Structure):
+    _fields_ = [("Tcw1", C.c_float * 12), ("Tcw2", C.c_float * 12), ("intr1", C.c_float * 6), ("intr2", C.c_float * 6), ("n", C.c_int32),
+                ("n_levels", C.c_int32), ("kp1_xy", C.c_void_p), ("kp2_xy", C.c_void_p), ("octave1", C.c_void_p), ("octave2", C.c_void_p),
+                ("scale_factors1", C.c_void_p), ("level_sigma2_1", C.c_void_p), ("scale_factors2", C.c_void_p), ("level_sigma2_2", C.c_void_p),
+                ("ratio_factor", C.c_float)]
+
+
+class TriangulateResult(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("x3d", C.c_void_p), ("n_accepted", C.c_int32)]
+
+
+TRIANGULATE_MAX_N, MAX_LEVELS = 8192, 16   # SLAMIT_TRIANGULATE_MAX_N, SLAMIT_MAX_LEVELS
+
+
 class VocDesc(C.Structure):
     _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32), ("n_nodes", C.c_int32),
                 ("parent", C.c_void_p), ("is_leaf", C.c_void_p), ("desc", C.c_void_p), ("weight", C.c_void_p)]
@@ -164,7 +178,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -212,6 +226,8 @@ def lib():
         L.slamit_sim3_optimize.argtypes = [i32, C.POINTER(Sim3Problem), C.POINTER(Sim3Result)]
         L.slamit_sim3_ransac_batch.argtypes = [i32, i32, C.POINTER(Sim3RansacProblem), C.POINTER(Sim3RansacResult)]
         L.slamit_sim3_ransac.argtypes = [i32, C.POINTER(Sim3RansacProblem), C.POINTER(Sim3RansacResult)]
+        L.slamit_triangulate_batch.argtypes = [i32, i32, C.POINTER(TriangulateProblem), C.POINTER(TriangulateResult)]
+        L.slamit_triangulate.argtypes = [i32, C.POINTER(TriangulateProblem), C.POINTER(TriangulateResult)]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
         L.slamit_voc_load_text.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
@@ -1236,3 +1252,49 @@ class Sim3Solver:
 
     def GetEstimatedScale(self):
         return float(self.t12[self.best, 12])
+
+
+def triangulate_batch(problems, device=0):
+    """LocalMapping::CreateNewMapPoints' per-pair body (LocalMapping.cc:348-483, monocular) for a list of (current keyframe, neighbour)
+    problems in ONE device call.  Each problem is a dict in the layout of slamit_triangulate_problem (synth.synth_triangulation):
+    Tcw1, Tcw2 (12) float32, intr1, intr2 (fx fy cx cy invfx invfy), kp1_xy, kp2_xy (n, 2), octave1, octave2 (n), n_levels,
+    scale_factors1/2 and level_sigma2_1/2 (n_levels), ratio_factor.  -> a list of dicts: status (n) uint8 (0 accepted, else the first
+    gate that rejected the pair), x3d (n, 3) float32, n_accepted."""
+    plist = list(problems)
+    m = len(plist)
+    P = (TriangulateProblem * m)()
+    R = (TriangulateResult * m)()
+    keep, outs = [], []
+    for i, pr in enumerate(plist):
+        k = {"kp1_xy": np.ascontiguousarray(pr["kp1_xy"], np.float32).reshape(-1, 2), "kp2_xy": np.ascontiguousarray(pr["kp2_xy"], np.float32).reshape(-1, 2),
+             "octave1": np.ascontiguousarray(pr["octave1"], np.int32).reshape(-1), "octave2": np.ascontiguousarray(pr["octave2"], np.int32).reshape(-1)}
+        n, nl = len(k["octave1"]), int(pr["n_levels"])
+        if len(k["kp1_xy"]) != n or len(k["kp2_xy"]) != n or len(k["octave2"]) != n:
+            raise SlamitError("triangulate: kp1_xy / kp2_xy / octave1 / octave2 do not have the same length")
+        for key in ("scale_factors1", "level_sigma2_1", "scale_factors2", "level_sigma2_2"):
+            k[key] = np.ascontiguousarray(pr[key], np.float32).reshape(-1)
+            if len(k[key]) != nl:
+                raise SlamitError("triangulate: %s does not have n_levels entries" % key)
+        q = P[i]
+        for key in ("Tcw1", "Tcw2", "intr1", "intr2"):
+            a = np.asarray(pr[key], np.float32).reshape(-1)
+            if len(a) != (12 if key[0] == "T" else 6):
+                raise SlamitError("triangulate: %s has %d entries" % (key, len(a)))
+            setattr(q, key, (C.c_float * len(a))(*[float(v) for v in a]))
+        q.n, q.n_levels, q.ratio_factor = n, nl, float(pr["ratio_factor"])
+        for key, a in k.items():
+            setattr(q, key, a.ctypes.data)
+        o = {"status": np.zeros(n, np.uint8), "x3d": np.zeros((n, 3), np.float32)}
+        R[i].status, R[i].x3d = o["status"].ctypes.data, o["x3d"].ctypes.data
+        keep.append(k)
+        outs.append(o)
+    _check(lib().slamit_triangulate_batch(device, m, P, R), "slamit_triangulate_batch")
+    del keep
+    for i, o in enumerate(outs):
+        o["n_accepted"] = int(R[i].n_accepted)
+    return outs
+
+
+def triangulate(problem, device=0):
+    """One (current keyframe, neighbour) problem: triangulate_batch([problem])[0]."""
+    return triangulate_batch([problem], device)[0]

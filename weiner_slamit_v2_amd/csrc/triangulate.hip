@@ -1,0 +1,133 @@
+// triangulate.hip — the per-pair body of LocalMapping::CreateNewMapPoints on the GPU (include/slamit.h, slamit_triangulate*).
+//
+// Reference: ORB_SLAM2/src/LocalMapping.cc:323-503.  After SearchForTriangulation every matched pair of the (current keyframe,
+// neighbour) pair is independent: ONE LANE takes one pair and runs triangulate.h on it -- rays and parallax, the 4x4 one-sided
+// Jacobi with both matrices in registers, the depth, reprojection and scale gates.  The poses, intrinsics and camera centres of
+// the problem are the same for every lane (scalar loads of the problem record); the level tables sit in the record and are
+// indexed by the lane's octave.  No LDS, no atomics: the accepted pairs of a wavefront are a ballot's popcount, written to one
+// slot per wavefront and summed on the host.  A batch of keyframe pairs is one launch (grid.y).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/slamit.h"
+#include "slamit_internal.h"
+#include "triangulate.h"
+
+static_assert((SLAMIT_MAX_LEVELS & (SLAMIT_MAX_LEVELS - 1)) == 0, "the kernel masks octaves with SLAMIT_MAX_LEVELS - 1");
+
+struct TriProb {
+    TriView c1, c2;
+    float ratio_factor;
+    int32_t n;
+    float sf1[SLAMIT_MAX_LEVELS], s1[SLAMIT_MAX_LEVELS], sf2[SLAMIT_MAX_LEVELS], s2[SLAMIT_MAX_LEVELS];   // entries past n_levels are zero
+    const SLAMIT_GLOBAL float* kp1; const SLAMIT_GLOBAL float* kp2;
+    const SLAMIT_GLOBAL int32_t* o1; const SLAMIT_GLOBAL int32_t* o2;
+    SLAMIT_GLOBAL uint8_t* status; SLAMIT_GLOBAL float* x3d; SLAMIT_GLOBAL int32_t* wave_counts;   // n, 3 n, (n + 63) / 64
+};
+
+// grid (ceil(max n / 256), problems), 256 threads: lane t of block b takes pair 256 b + t of problem blockIdx.y.  The host has
+// checked every octave against [0, n_levels); the mask keeps the table index inside the record whatever it holds.
+__global__ __launch_bounds__(256) void triangulate_kernel(const TriProb* __restrict__ probs) {
+    const TriProb& P = probs[blockIdx.y];
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= P.n) return;
+    const float p1[2] = {P.kp1[2 * i], P.kp1[2 * i + 1]}, p2[2] = {P.kp2[2 * i], P.kp2[2 * i + 1]};
+    const int o1 = P.o1[i] & (SLAMIT_MAX_LEVELS - 1), o2 = P.o2[i] & (SLAMIT_MAX_LEVELS - 1);
+    float X[3];
+    const int st = tri_pair(P.c1, P.c2, p1, p2, P.s1[o1], P.s2[o2], P.sf1[o1], P.sf2[o2], P.ratio_factor, X);
+    P.status[i] = (uint8_t)st;
+    P.x3d[3 * (size_t)i] = X[0]; P.x3d[3 * (size_t)i + 1] = X[1]; P.x3d[3 * (size_t)i + 2] = X[2];
+    const unsigned long long m = __ballot(st == TRI_OK);   // the lanes past n have left: they count as 0
+    if ((threadIdx.x & 63) == 0) P.wave_counts[i >> 6] = __popcll(m);
+}
+
+extern "C" {
+
+int slamit_triangulate_batch(int device, int nprob, const slamit_triangulate_problem* probs, slamit_triangulate_result* results) {
+    const char* const where = "slamit_triangulate_batch";
+    if (nprob < 0 || (nprob && (!probs || !results))) return slamit_fail(SLAMIT_ERR_ARG, "slamit_triangulate_batch: bad argument");
+    if (nprob == 0) return SLAMIT_OK;
+    int max_n = 0;
+    for (int f = 0; f < nprob; ++f) {
+        const slamit_triangulate_problem& P = probs[f];
+        if (P.n < 0) return slamit_fail(SLAMIT_ERR_ARG, "slamit_triangulate_batch: negative count");
+        if (P.n > SLAMIT_TRIANGULATE_MAX_N) return slamit_fail(SLAMIT_ERR_ARG, "slamit_triangulate_batch: more than SLAMIT_TRIANGULATE_MAX_N pairs");
+        if (P.n == 0) continue;   // nothing to triangulate, nothing read
+        if (P.n_levels < 1 || P.n_levels > SLAMIT_MAX_LEVELS) return slamit_fail(SLAMIT_ERR_ARG, "slamit_triangulate_batch: n_levels outside [1, SLAMIT_MAX_LEVELS]");
+        if (!P.kp1_xy || !P.kp2_xy || !P.octave1 || !P.octave2 || !P.scale_factors1 || !P.level_sigma2_1 || !P.scale_factors2 || !P.level_sigma2_2 ||
+            !results[f].status || !results[f].x3d)
+            return slamit_fail(SLAMIT_ERR_ARG, "slamit_triangulate_batch: null array");
+        for (int k = 0; k < P.n; ++k)
+            if (P.octave1[k] < 0 || P.octave1[k] >= P.n_levels || P.octave2[k] < 0 || P.octave2[k] >= P.n_levels)
+                return slamit_fail(SLAMIT_ERR_ARG, "slamit_triangulate_batch: octave outside [0, n_levels)");
+        max_n = std::max(max_n, (int)P.n);
+    }
+    for (int f = 0; f < nprob; ++f) results[f].n_accepted = 0;
+    if (max_n == 0) return SLAMIT_OK;
+    SLAMIT_USE_DEVICE(device);
+    // [per problem: kp1 kp2 octave1 octave2 | records] go up; [per problem: status x3d wave counts] come down
+    struct Spans { StageSpan<float> kp1, kp2, x3d; StageSpan<int32_t> o1, o2, counts; StageSpan<uint8_t> status; };
+    StageLayout L;
+    std::vector<Spans> sp(nprob);
+    for (int f = 0; f < nprob; ++f) {
+        const size_t n = (size_t)probs[f].n;
+        Spans& s = sp[f];
+        s.kp1 = L.take<float>(2 * n, 16); s.kp2 = L.take<float>(2 * n, 16); s.o1 = L.take<int32_t>(n, 16); s.o2 = L.take<int32_t>(n, 16);
+    }
+    const StageSpan<TriProb> recs = L.take<TriProb>(nprob, 16);
+    L.end_inputs();
+    for (int f = 0; f < nprob; ++f) {
+        const size_t n = (size_t)probs[f].n;
+        Spans& s = sp[f];
+        s.status = L.take<uint8_t>(n, 16); s.x3d = L.take<float>(3 * n, 16); s.counts = L.take<int32_t>((n + 63) / 64, 16);
+    }
+    L.end_outputs();
+    static thread_local SlamitScratch S;
+    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
+    for (int f = 0; f < nprob; ++f) {
+        const slamit_triangulate_problem& P = probs[f];
+        const Spans& s = sp[f];
+        TriProb& Q = recs.at(S.host)[f];
+        memset(&Q, 0, sizeof(Q));
+        Q.n = P.n;
+        if (P.n) {
+            memcpy(s.kp1.at(S.host), P.kp1_xy, s.kp1.bytes()); memcpy(s.kp2.at(S.host), P.kp2_xy, s.kp2.bytes());
+            memcpy(s.o1.at(S.host), P.octave1, s.o1.bytes()); memcpy(s.o2.at(S.host), P.octave2, s.o2.bytes());
+            memcpy(Q.c1.T, P.Tcw1, sizeof(Q.c1.T)); memcpy(Q.c2.T, P.Tcw2, sizeof(Q.c2.T));
+            Q.c1.fx = P.intr1[0]; Q.c1.fy = P.intr1[1]; Q.c1.cx = P.intr1[2]; Q.c1.cy = P.intr1[3]; Q.c1.invfx = P.intr1[4]; Q.c1.invfy = P.intr1[5];
+            Q.c2.fx = P.intr2[0]; Q.c2.fy = P.intr2[1]; Q.c2.cx = P.intr2[2]; Q.c2.cy = P.intr2[3]; Q.c2.invfx = P.intr2[4]; Q.c2.invfy = P.intr2[5];
+            tri_centre(Q.c1); tri_centre(Q.c2);
+            Q.ratio_factor = P.ratio_factor;
+            memcpy(Q.sf1, P.scale_factors1, sizeof(float) * P.n_levels); memcpy(Q.s1, P.level_sigma2_1, sizeof(float) * P.n_levels);
+            memcpy(Q.sf2, P.scale_factors2, sizeof(float) * P.n_levels); memcpy(Q.s2, P.level_sigma2_2, sizeof(float) * P.n_levels);
+        }
+        Q.kp1 = (const SLAMIT_GLOBAL float*)s.kp1.at(S.dev); Q.kp2 = (const SLAMIT_GLOBAL float*)s.kp2.at(S.dev);
+        Q.o1 = (const SLAMIT_GLOBAL int32_t*)s.o1.at(S.dev); Q.o2 = (const SLAMIT_GLOBAL int32_t*)s.o2.at(S.dev);
+        Q.status = (SLAMIT_GLOBAL uint8_t*)s.status.at(S.dev); Q.x3d = (SLAMIT_GLOBAL float*)s.x3d.at(S.dev);
+        Q.wave_counts = (SLAMIT_GLOBAL int32_t*)s.counts.at(S.dev);
+    }
+    HIP_TRY_AT(where, slamit_stage_upload(S, L));
+    hipLaunchKernelGGL(triangulate_kernel, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, recs.at(S.dev));
+    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
+    for (int f = 0; f < nprob; ++f) {
+        const Spans& s = sp[f];
+        if (!probs[f].n) continue;
+        memcpy(results[f].status, s.status.at(S.host), s.status.bytes());
+        memcpy(results[f].x3d, s.x3d.at(S.host), s.x3d.bytes());
+        int acc = 0;
+        const int32_t* c = s.counts.at(S.host);
+        for (size_t w = 0; w < s.counts.count; ++w) acc += c[w];
+        results[f].n_accepted = acc;
+    }
+    return SLAMIT_OK;
+}
+
+int slamit_triangulate(int device, const slamit_triangulate_problem* prob, slamit_triangulate_result* res) {
+    return slamit_triangulate_batch(device, 1, prob, res);
+}
+
+}  // extern "C"

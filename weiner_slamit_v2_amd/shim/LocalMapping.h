@@ -1,0 +1,174 @@
+// LocalMapping.h — LocalMapping::CreateNewMapPoints (ORB_SLAM2/src/LocalMapping.cc:224-505) over the caller's KeyFrame type,
+// monocular.  The loop over the neighbours, the baseline gate, ComputeF12 and the bookkeeping stay host code; the matcher is
+// ORBmatcher::SearchForTriangulation (one slamit_bow_search call) and the per-pair body -- parallax, linear triangulation, depth,
+// reprojection and scale gates (:348-483) -- is ONE slamit_triangulate call per neighbour (csrc/triangulate.h).
+//
+// Members used on the caller's type (on top of what ORBmatcher::SearchForTriangulation lists):
+//   KeyFrame : N, mvKeysUn, mvuRight, mvScaleFactors, mvLevelSigma2, mfScaleFactor, fx, fy, cx, cy, invfx, invfy,
+//              GetRotation(), GetTranslation(), GetCameraCenter(), ComputeSceneMedianDepth(q),
+//              mFeatVec, mDescriptors, GetMapPoint(idx)
+// and one callable, make(const cv::Mat& x3D /* 3x1 CV_32F */, int idx1, int idx2, KeyFrameT* pKF2), called for every accepted pair in
+// pair order; it does what :486-500 does (new MapPoint, AddObservation on both keyframes, AddMapPoint on both keyframes,
+// ComputeDistinctiveDescriptors, UpdateNormalAndDepth, Map::AddMapPoint, mlpRecentAddedMapPoints).
+//
+// The neighbours are NOT merged into one launch: a point made for neighbour i gives keypoint idx1 of the current keyframe a map
+// point, which removes it from neighbour i+1's SearchForTriangulation (:700-704) -- the reference's result depends on that order,
+// so each neighbour's search runs after the previous neighbour's make() calls.  slamit_triangulate_batch is for callers that hold
+// the keyframe pairs of several independent streams at once (the pipeline configuration), where no such dependency exists.
+//
+// Stereo is out of scope: monocular == false, or a keyframe with a stereo coordinate (mvuRight >= 0), is refused on
+// stderr with LastStatus() == SLAMIT_ERR_ARG and nothing is created.  Any other non-SLAMIT_OK status of a device call is reported
+// the same way and ends the loop: never a silent return.
+#ifndef SLAMIT_SHIM_LOCALMAPPING_H
+#define SLAMIT_SHIM_LOCALMAPPING_H
+
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <utility>
+#include <vector>
+
+#include "../../include/slamit.h"
+#include "ORBmatcher.h"
+
+namespace ORB_SLAM2 {
+
+class LocalMapping {
+public:
+    // K1^-T [t12]x R12 K2^-1 (:590-607) in float; K^-1 of a pinhole K is written out.
+    template <class KeyFrameT>
+    static cv::Mat ComputeF12(KeyFrameT* pKF1, KeyFrameT* pKF2) {
+        const cv::Mat R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation(), R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
+        float R12[3][3], t12[3];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c)
+                R12[r][c] = R1w.template at<float>(r, 0) * R2w.template at<float>(c, 0) + R1w.template at<float>(r, 1) * R2w.template at<float>(c, 1) +
+                            R1w.template at<float>(r, 2) * R2w.template at<float>(c, 2);
+        for (int r = 0; r < 3; ++r)
+            t12[r] = -(R12[r][0] * t2w.template at<float>(0, 0) + R12[r][1] * t2w.template at<float>(1, 0) + R12[r][2] * t2w.template at<float>(2, 0)) +
+                     t1w.template at<float>(r, 0);
+        const float tx[3][3] = {{0, -t12[2], t12[1]}, {t12[2], 0, -t12[0]}, {-t12[1], t12[0], 0}};
+        const float K1i[3][3] = {{1.f / pKF1->fx, 0, -pKF1->cx / pKF1->fx}, {0, 1.f / pKF1->fy, -pKF1->cy / pKF1->fy}, {0, 0, 1}};
+        const float K2i[3][3] = {{1.f / pKF2->fx, 0, -pKF2->cx / pKF2->fx}, {0, 1.f / pKF2->fy, -pKF2->cy / pKF2->fy}, {0, 0, 1}};
+        float a[3][3], b[3][3];
+        cv::Mat F(3, 3, CV_32F);
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) a[r][c] = K1i[0][r] * tx[0][c] + K1i[1][r] * tx[1][c] + K1i[2][r] * tx[2][c];   // K1^-T [t]x
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) b[r][c] = a[r][0] * R12[0][c] + a[r][1] * R12[1][c] + a[r][2] * R12[2][c];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) F.at<float>(r, c) = b[r][0] * K2i[0][c] + b[r][1] * K2i[1][c] + b[r][2] * K2i[2][c];
+        return F;
+    }
+
+    // The loop of :265-504.  stop() stands for CheckNewKeyFrames(): asked before every neighbour but the first (:267).
+    // Returns the number of make() calls (nnew).
+    template <class KeyFrameT, class NewPointFn, class StopFn>
+    static int CreateNewMapPoints(KeyFrameT* cur, const std::vector<KeyFrameT*>& neigh, bool monocular, NewPointFn&& make, StopFn&& stop, int device = 0) {
+        status() = SLAMIT_OK;
+        if (!monocular) return refuse("CreateNewMapPoints: only the monocular path is on the device");
+        if (hasStereo(cur)) return refuse("CreateNewMapPoints: the current keyframe carries stereo coordinates (mvuRight >= 0)");
+        for (size_t i = 0; i < neigh.size(); ++i)
+            if (hasStereo(neigh[i])) return refuse("CreateNewMapPoints: a neighbour keyframe carries stereo coordinates (mvuRight >= 0)");
+        ORBmatcher matcher(0.6, false);
+        slamit_triangulate_problem P;
+        pose(cur, P.Tcw1, P.intr1);
+        const cv::Mat Ow1 = cur->GetCameraCenter();
+        P.ratio_factor = 1.5f * cur->mfScaleFactor;
+        int nnew = 0;
+        for (size_t i = 0; i < neigh.size(); i++) {
+            if (i > 0 && stop()) return nnew;
+            KeyFrameT* pKF2 = neigh[i];
+            // baseline against the scene's median depth (:273-294)
+            const cv::Mat Ow2 = pKF2->GetCameraCenter();
+            const float vB[3] = {Ow2.template at<float>(0, 0) - Ow1.template at<float>(0, 0), Ow2.template at<float>(1, 0) - Ow1.template at<float>(1, 0),
+                                 Ow2.template at<float>(2, 0) - Ow1.template at<float>(2, 0)};
+            const float baseline = (float)sqrt((double)vB[0] * vB[0] + (double)vB[1] * vB[1] + (double)vB[2] * vB[2]);
+            const float medianDepthKF2 = pKF2->ComputeSceneMedianDepth(2);
+            const float ratioBaselineDepth = baseline / medianDepthKF2;
+            if (ratioBaselineDepth < 0.01) continue;
+            const cv::Mat F12 = ComputeF12(cur, pKF2);
+            std::vector<std::pair<size_t, size_t> > vMatchedIndices;
+            matcher.SearchForTriangulation(cur, pKF2, F12, vMatchedIndices, false);
+            if (ORBmatcher::LastStatus() != SLAMIT_OK) {
+                status() = ORBmatcher::LastStatus();
+                fprintf(stderr, "CreateNewMapPoints: SearchForTriangulation failed (%d): %s\n", status(), slamit_last_error());
+                return nnew;
+            }
+            const int nmatches = (int)vMatchedIndices.size();
+            if (nmatches == 0) continue;
+            std::vector<float> kp1(2 * (size_t)nmatches), kp2(2 * (size_t)nmatches), x3d(3 * (size_t)nmatches);
+            std::vector<int32_t> o1(nmatches), o2(nmatches);
+            std::vector<uint8_t> st(nmatches);
+            for (int k = 0; k < nmatches; ++k) {
+                const cv::KeyPoint& a = cur->mvKeysUn[vMatchedIndices[k].first];
+                const cv::KeyPoint& b = pKF2->mvKeysUn[vMatchedIndices[k].second];
+                kp1[2 * k] = a.pt.x; kp1[2 * k + 1] = a.pt.y; o1[k] = a.octave;
+                kp2[2 * k] = b.pt.x; kp2[2 * k + 1] = b.pt.y; o2[k] = b.octave;
+            }
+            pose(pKF2, P.Tcw2, P.intr2);
+            P.n = nmatches;
+            P.n_levels = (int32_t)cur->mvScaleFactors.size();
+            if (pKF2->mvScaleFactors.size() != cur->mvScaleFactors.size() || cur->mvLevelSigma2.size() != cur->mvScaleFactors.size() ||
+                pKF2->mvLevelSigma2.size() != cur->mvScaleFactors.size()) {
+                refuse("CreateNewMapPoints: the level tables of the two keyframes differ in length");
+                return nnew;
+            }
+            P.kp1_xy = kp1.data(); P.kp2_xy = kp2.data(); P.octave1 = o1.data(); P.octave2 = o2.data();
+            P.scale_factors1 = cur->mvScaleFactors.data(); P.level_sigma2_1 = cur->mvLevelSigma2.data();
+            P.scale_factors2 = pKF2->mvScaleFactors.data(); P.level_sigma2_2 = pKF2->mvLevelSigma2.data();
+            slamit_triangulate_result R;
+            R.status = st.data(); R.x3d = x3d.data(); R.n_accepted = 0;
+            const int rc = slamit_triangulate(device, &P, &R);
+            if (rc != SLAMIT_OK) {
+                status() = rc;
+                fprintf(stderr, "CreateNewMapPoints: slamit_triangulate failed (%d): %s\n", rc, slamit_last_error());
+                return nnew;
+            }
+            for (int k = 0; k < nmatches; ++k) {
+                if (st[k] != 0) continue;
+                cv::Mat x3D(3, 1, CV_32F);
+                for (int r = 0; r < 3; ++r) x3D.at<float>(r, 0) = x3d[3 * (size_t)k + r];
+                make(x3D, (int)vMatchedIndices[k].first, (int)vMatchedIndices[k].second, pKF2);
+                nnew++;
+            }
+        }
+        return nnew;
+    }
+
+    template <class KeyFrameT, class NewPointFn>
+    static int CreateNewMapPoints(KeyFrameT* cur, const std::vector<KeyFrameT*>& neigh, bool monocular, NewPointFn&& make) {
+        return CreateNewMapPoints(cur, neigh, monocular, make, never);
+    }
+
+    static int LastStatus() { return status(); }
+
+private:
+    static bool never() { return false; }
+    static int& status() { static thread_local int s = SLAMIT_OK; return s; }
+    static int refuse(const char* why) {
+        status() = SLAMIT_ERR_ARG;
+        fprintf(stderr, "%s\n", why);
+        return 0;
+    }
+    template <class KeyFrameT>
+    static bool hasStereo(KeyFrameT* kf) {
+        for (size_t i = 0; i < kf->mvuRight.size(); ++i)
+            if (kf->mvuRight[i] >= 0) return true;
+        return false;
+    }
+    template <class KeyFrameT>
+    static void pose(KeyFrameT* kf, float T[12], float K[6]) {
+        const cv::Mat R = kf->GetRotation(), t = kf->GetTranslation();
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) T[4 * r + c] = R.template at<float>(r, c);
+            T[4 * r + 3] = t.template at<float>(r, 0);
+        }
+        K[0] = kf->fx; K[1] = kf->fy; K[2] = kf->cx; K[3] = kf->cy; K[4] = kf->invfx; K[5] = kf->invfy;
+    }
+};
+
+}  // namespace ORB_SLAM2
+
+#endif

@@ -13,6 +13,7 @@
 //     shim_test sim3 <problem.bin> <out.bin>
 //     shim_test osim3 <problem.bin> <out.bin>
 //     shim_test sim3solver <problem.bin> <out.bin>
+//     shim_test triangulate <problem.bin> <out.bin>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -30,6 +31,7 @@
 #include "Sim3Solver.h"
 #include "ORBVocabulary.h"
 #include "KeyFrameDatabase.h"
+#include "LocalMapping.h"
 
 using namespace ORB_SLAM2;
 
@@ -933,6 +935,65 @@ static int run_sim3solver(int argc, char** argv) {
     return status == 0 ? 0 : 1;
 }
 
+// ---- LocalMapping::CreateNewMapPoints through the template -----------------------------------------------------------------------
+struct MockMapKF : MockBowKF {   // the members LocalMapping.h lists on top of the matcher's
+    float invfx, invfy, mfScaleFactor, medianDepth;
+    float ComputeSceneMedianDepth(int) { return medianDepth; }
+};
+// problem.bin: int32 nkf (the current keyframe, then its neighbours in covisibility order) stereo_kf (-1, or the keyframe whose
+//   keypoint 0 gets a right-image coordinate) monocular ; float scale[8] sigma2[8] ; per keyframe: int32 n ; float R[9] t[3] intr[4]
+//   median_depth ; then the side layout of `bow`: u8 desc[32 n], float angle[n], int32 node[n], int32 mp[n], float xy[2 n], int32 octave[n]
+// out.bin: int32 status nnew ; per make() call: int32 neighbour idx1 idx2 ; float x3D[3]
+static int run_triangulate(int argc, char** argv) {
+    if (argc < 4) return 2;
+    std::vector<unsigned char> raw = slurp(argv[2]);
+    Reader R{raw.data()};
+    const int nkf = R.get<int>(), stereo_kf = R.get<int>(), monocular = R.get<int>();
+    const float* scale = R.arr<float>(8); const float* sig = R.arr<float>(8);
+    std::vector<MockMapKF> kfs(nkf);
+    std::vector<std::vector<MockBowPoint> > pts(nkf);
+    for (int k = 0; k < nkf; ++k) {
+        MockMapKF& K = kfs[k];
+        const int n = R.get<int>();
+        const float* Rm = R.arr<float>(9); const float* t = R.arr<float>(3); const float* intr = R.arr<float>(4);
+        K.medianDepth = R.get<float>();
+        fill_side(R, n, K, pts[k]);
+        K.Rcw = cv::Mat(3, 3, CV_32F); K.tcw = mat_from(t, 3);
+        float Ow[3];
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) K.Rcw.at<float>(r, c) = Rm[3 * r + c];
+            Ow[r] = -((Rm[r] * t[0] + Rm[3 + r] * t[1]) + Rm[6 + r] * t[2]);   // KeyFrame::SetPose: Ow = -Rwc * tcw
+        }
+        K.Ow = mat_from(Ow, 3);
+        K.fx = intr[0]; K.fy = intr[1]; K.cx = intr[2]; K.cy = intr[3]; K.invfx = 1.0f / K.fx; K.invfy = 1.0f / K.fy;
+        K.mfScaleFactor = scale[1];
+        K.mvScaleFactors.assign(scale, scale + 8); K.mvLevelSigma2.assign(sig, sig + 8);
+        if (k == stereo_kf && n > 0) K.mvuRight[0] = K.mvKeysUn[0].pt.x - 3.0f;
+    }
+    std::vector<MockMapKF*> neigh;
+    for (int k = 1; k < nkf; ++k) neigh.push_back(&kfs[k]);
+    std::vector<int> rec;
+    std::vector<float> xs;
+    std::vector<MockBowPoint*> made;
+    // what :486-500 does to the two keyframes: the new point sits at idx1 and idx2 from here on
+    auto make = [&](const cv::Mat& x3D, int idx1, int idx2, MockMapKF* pKF2) {
+        MockBowPoint* p = new MockBowPoint();
+        p->id = (int)made.size(); p->bad = false;
+        made.push_back(p);
+        kfs[0].matches[idx1] = p; pKF2->matches[idx2] = p;
+        rec.push_back((int)(pKF2 - &kfs[0]) - 1); rec.push_back(idx1); rec.push_back(idx2);
+        for (int r = 0; r < 3; ++r) xs.push_back(x3D.at<float>(r, 0));
+    };
+    const int nnew = LocalMapping::CreateNewMapPoints(&kfs[0], neigh, monocular != 0, make);
+    const int status = LocalMapping::LastStatus();
+    FILE* f = fopen(argv[3], "wb");
+    fwrite(&status, 4, 1, f); fwrite(&nnew, 4, 1, f);
+    for (int k = 0; k < nnew; ++k) { fwrite(&rec[3 * k], 4, 3, f); fwrite(&xs[3 * k], 4, 3, f); }
+    fclose(f);
+    for (size_t k = 0; k < made.size(); ++k) delete made[k];
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     std::string mode = argv[1];
@@ -948,5 +1009,6 @@ int main(int argc, char** argv) {
     if (mode == "sim3") return run_sim3(argc, argv);
     if (mode == "osim3") return run_osim3(argc, argv);
     if (mode == "sim3solver") return run_sim3solver(argc, argv);
+    if (mode == "triangulate") return run_triangulate(argc, argv);
     return 2;
 }

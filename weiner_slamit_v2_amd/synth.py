@@ -447,6 +447,54 @@ def synth_sim3_ransac(n=200, outlier_frac=0.3, seed=0, noise_px=0.5, fix_scale=F
                 true=dict(R=R, t=t, s=s_true, bad=bad))
 
 
+def synth_triangulation(n=300, seed=0, baseline=0.3, outlier_frac=0.2, noise_px=0.7, depth=(1.5, 12.0), direction=(1.0, 0.05, 0.1),
+                        behind_frac=0.0, octave_jump_frac=0.0, octave_jump=4):
+    """What LocalMapping::CreateNewMapPoints holds for one (current keyframe, neighbour) pair after SearchForTriangulation
+    (LocalMapping.cc:323-346): two posed pinhole keyframes `baseline` apart along `direction` (in keyframe 1's frame) and n matched
+    undistorted keypoints.  The points lie at depths drawn log-uniformly from `depth`, so that with a baseline of a few tenths the
+    rays' parallax spans the 0.9998 gate; each keypoint sits on an octave 0..7 (octave2 = octave1 +- 1, clipped) and carries pixel
+    noise of noise_px times its level's scale factor.  A share outlier_frac of the pairs are gross outliers (keypoint 2 moved by
+    8..60 px), behind_frac of the points lie behind keyframe 1 (negative depth, projected all the same), and octave_jump_frac of
+    the pairs get octave2 = octave1 +- octave_jump, which the scale-consistency test rejects.  A `direction` along the optical
+    axis with a baseline longer than the nearest depth puts points between the two cameras: in front of 1, behind 2.
+    Layout of slamit_triangulate_problem."""
+    rs = np.random.RandomState(13000 + seed)
+    f32 = np.float32
+    fx1, fy1, cx1, cy1 = f32(517.3), f32(516.5), f32(318.6), f32(255.3)
+    fx2, fy2, cx2, cy2 = f32(520.9), f32(521.0), f32(325.1), f32(249.7)
+    intr1 = np.array([fx1, fy1, cx1, cy1, f32(1) / fx1, f32(1) / fy1], f32)
+    intr2 = np.array([fx2, fy2, cx2, cy2, f32(1) / fx2, f32(1) / fy2], f32)
+    R1, t1 = se3_exp(np.array([0.04, -0.3, 0.02, 0.6, -0.2, 1.1]))               # world -> keyframe 1
+    d = np.asarray(direction, np.float64)
+    d = d / np.linalg.norm(d)
+    R21, _ = se3_exp(np.array([0.02, -0.03, 0.01, 0, 0, 0]))                     # keyframe 1 -> keyframe 2: a small turn, then the baseline
+    R2, t2 = R21 @ R1, R21 @ (t1 - baseline * d)
+    z = np.exp(rs.uniform(np.log(depth[0]), np.log(depth[1]), n))
+    behind = rs.rand(n) < behind_frac
+    z[behind] = -z[behind]
+    Xc1 = np.stack([rs.uniform(-0.55, 0.55, n) * z, rs.uniform(-0.42, 0.42, n) * z, z], 1)
+    Xw = (Xc1 - t1) @ R1                                                         # R1^T (Xc1 - t1)
+    Xc2 = Xw @ R2.T + t2
+    nlev = 8
+    scale_f = f32(1.2) ** np.arange(nlev, dtype=f32)
+    sigma2 = (scale_f * scale_f).astype(f32)
+    o1 = rs.randint(0, nlev, n)
+    o2 = np.clip(o1 + rs.choice([-1, 1], n), 0, nlev - 1)
+    jump = rs.rand(n) < octave_jump_frac
+    o2[jump] = np.where(o1[jump] >= octave_jump, o1[jump] - octave_jump, np.minimum(o1[jump] + octave_jump, nlev - 1))
+    kp1 = np.stack([fx1 * Xc1[:, 0] / Xc1[:, 2] + cx1, fy1 * Xc1[:, 1] / Xc1[:, 2] + cy1], 1) + rs.normal(0, noise_px, (n, 2)) * scale_f[o1][:, None]
+    kp2 = np.stack([fx2 * Xc2[:, 0] / Xc2[:, 2] + cx2, fy2 * Xc2[:, 1] / Xc2[:, 2] + cy2], 1) + rs.normal(0, noise_px, (n, 2)) * scale_f[o2][:, None]
+    bad = rs.rand(n) < outlier_frac
+    ang, r = rs.uniform(0, 2 * np.pi, n), rs.uniform(8, 60, n)
+    kp2[bad] += np.stack([r * np.cos(ang), r * np.sin(ang)], 1)[bad]
+    T1 = np.concatenate([R1, t1[:, None]], 1).astype(f32).reshape(12)
+    T2 = np.concatenate([R2, t2[:, None]], 1).astype(f32).reshape(12)
+    return dict(n=n, Tcw1=T1, Tcw2=T2, intr1=intr1, intr2=intr2, kp1_xy=kp1.astype(f32), kp2_xy=kp2.astype(f32),
+                octave1=o1.astype(np.int32), octave2=o2.astype(np.int32), n_levels=nlev,
+                scale_factors1=scale_f.copy(), level_sigma2_1=sigma2.copy(), scale_factors2=scale_f.copy(), level_sigma2_2=sigma2.copy(),
+                ratio_factor=f32(1.5) * f32(1.2), true=dict(X=Xw, bad=bad, behind=behind, jump=jump))
+
+
 def synth_map(n_kf, n_pt, obs_per_pt, n_fixed, seed, stereo_frac=0.0, loop=True, outlier_frac=0.03, baseline=0.08):
     """A map-sized BA window (slamit_ba_problem layout, as synth_ba): n_kf cameras on a circle of radius 2 in the x-z plane, each looking
     outward, and n_pt points on a cylinder of radius 6 around it.  loop=True: the trajectory closes (keyframe k at 2 pi k / n_kf), so the
