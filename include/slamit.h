@@ -161,7 +161,8 @@ int slamit_distinctive_batch(const uint8_t* desc, const int32_t* offsets, int np
  * skip keypoints that already carry a map point, take the nearest (and second nearest) descriptor in
  * the reference's candidate order, accept, and MARK THE KEYPOINT TAKEN for the queries that follow
  * (the reference assigns F.mvpMapPoints[bestIdx] inside the loop).  Projection, viewing-cosine radius
- * and the rotation histogram stay with the caller (shim/ORBmatcher.h).  Mono only (mvuRight < 0). */
+ * and the rotation histogram stay with the caller (shim/ORBmatcher.h), except for SearchLocalPoints, whose
+ * queries slamit_frustum* below writes in this layout.  Mono only (mvuRight < 0). */
 typedef struct slamit_frame_view {
     int32_t n;                 /* keypoints */
     const float* kp_xy;        /* n x 2: mvKeysUn[i].pt */
@@ -680,6 +681,92 @@ typedef struct slamit_triangulate_result {
 /* nproblems keyframe pairs in one launch (host pointers, synchronous). */
 int slamit_triangulate_batch(int device, int nproblems, const slamit_triangulate_problem* probs, slamit_triangulate_result* results);
 int slamit_triangulate(int device, const slamit_triangulate_problem* prob, slamit_triangulate_result* res);
+
+/* ---- SearchLocalPoints: the frustum test that feeds the guided search (tracking, between UpdateLocalMap and SearchByProjection) ----
+ * Frame::isInFrustum with MapPoint::PredictScale (src/Frame.cc:389-445, src/MapPoint.cc:391-400) for every local map point of
+ * Tracking::SearchLocalPoints (src/Tracking.cc:1409-1464), and the query ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>&, th)
+ * builds from what isInFrustum stored (src/ORBmatcher.cc:47-71): float / double exactly where the reference has them
+ * (csrc/frustum.h, which also says which log PredictScale calls and carries its own).  One lane per point; a batch is one launch.
+ * status[i] is the first test that rejected point i, in the reference's order:
+ *   0 in view   1 skipped by the caller (skip[i] != 0: bad, or already seen this frame)   2 depth (PcZ < 0)   3 u outside
+ *   4 v outside   5 distance (outside [0.8 min_dist, 1.2 max_dist])   6 viewing angle   7 level outside the table
+ * ONE DEPARTURE: this reference's PredictScale does not clamp, and a level outside [0, n_levels) then indexes mvScaleFactors out of
+ * bounds.  Here such a point, and one whose max_dist / dist is not finite and positive (level = INT32_MIN), is status 7: it keeps
+ * its projection, viewing cosine and raw level, produces no query and is not counted in view.
+ * proj[3i..] = mTrackProjX, mTrackProjY, mTrackProjXR; view_cos[i] = mTrackViewCos; level[i] = mnTrackScaleLevel; fields the walk
+ * did not reach are zero (csrc/frustum.h lists which).  The query arrays are slamit_search_queries' own: uvr[3i..] = (u, v,
+ * r * scale_factors[level]) with r = (view_cos > 0.998 ? 2.5 : 4.0) * (th != 1 ? th : 1), level_min = level - 1, level_max = level,
+ * valid = 1 for status 0; zeros and valid = 0 otherwise.  Queries are NOT compacted: query i is point i, so the order of the
+ * reference's walk over mvpLocalMapPoints is kept, and a valid = 0 query matches nothing and takes no keypoint.
+ * Monocular: the stereo gate of the search is not built.  n above SLAMIT_FRUSTUM_MAX_N, n_levels outside [1, SLAMIT_MAX_LEVELS] or
+ * a null array with n > 0 fails with SLAMIT_ERR_ARG and a message before anything is launched; n == 0 and nproblems == 0 are
+ * valid and write nothing but n_in_view = 0. */
+#define SLAMIT_FRUSTUM_MAX_N 65536         /* points per problem / q_cap of the device form (a local map holds a few thousand) */
+
+typedef struct slamit_frustum_frame {
+    float Rcw[9], tcw[3], Ow[3];   /* mRcw (row-major), mtcw, mOw: the camera centre AS THE FRAME HOLDS IT */
+    float fx, fy, cx, cy, bf;      /* bf = mbf; 0 for a monocular frame */
+    float min_x, max_x, min_y, max_y; /* mnMinX .. mnMaxY */
+    float view_cos_limit;          /* 0.5 (Tracking.cc:1440) */
+    float log_scale_factor;        /* mfLogScaleFactor */
+    float th;                      /* SearchByProjection's th: 1, 3 (RGBD) or 5 (after relocalisation) */
+    int32_t n_levels;              /* entries of scale_factors in use */
+    float scale_factors[SLAMIT_MAX_LEVELS]; /* mvScaleFactors */
+} slamit_frustum_frame;
+
+typedef struct slamit_frustum_problem {
+    slamit_frustum_frame frame;
+    int32_t n;                     /* local map points */
+    const float* pos;              /* n x 3: GetWorldPos() */
+    const float* normal;           /* n x 3: GetNormal() */
+    const float* max_dist;         /* n: the RAW mfMaxDistance (GetMaxDistanceInvariance() / 1.2f) */
+    const float* min_dist;         /* n: the raw mfMinDistance */
+    const uint8_t* skip;           /* n: 1 = mnLastFrameSeen == the frame's id, or isBad() */
+} slamit_frustum_problem;
+
+typedef struct slamit_frustum_result {
+    uint8_t* status;               /* n out */
+    float* proj;                   /* n x 3 out: u, v, uR */
+    float* view_cos;               /* n out */
+    int32_t* level;                /* n out */
+    float* uvr;                    /* n x 3 out: slamit_search_queries.uvr */
+    int32_t* level_min;            /* n out */
+    int32_t* level_max;            /* n out */
+    uint8_t* valid;                /* n out */
+    int32_t n_in_view;             /* out: points with status 0 (nToMatch) */
+} slamit_frustum_result;
+
+/* nproblems frames in one launch (host pointers, synchronous). */
+int slamit_frustum_batch(int device, int nproblems, const slamit_frustum_problem* probs, slamit_frustum_result* results);
+int slamit_frustum(int device, const slamit_frustum_problem* prob, slamit_frustum_result* res);
+
+/* Everything resident in HBM: nframes frames, frame f with d_m[f] points (clamped to [0, q_cap]; entries past it are neither read
+ * nor written).  The point arrays are PLANES, so that a wavefront's loads are contiguous: coordinate c of point i of frame f is
+ * d_pos[(f * 3 + c) * q_cap + i].  d_uvr, d_level_min, d_level_max and d_valid are the arrays slamit_search_batch reads, in its
+ * layout; the five optional outputs may be NULL.  The host cannot see d_frames: the device accepts a level only below
+ * min(n_levels, SLAMIT_MAX_LEVELS), so an n_levels <= 0 makes every point that reaches the level test status 7.  Asynchronous on `stream` (NULL: the legacy
+ * default stream of `device`), no synchronisation, no state; d_n_in_view is summed by a second launch of one wavefront per
+ * frame over d_valid, on the same stream. */
+typedef struct slamit_frustum_batch_rec {
+    int32_t nframes, q_cap;
+    const slamit_frustum_frame* d_frames; /* [nframes] */
+    const int32_t* d_m;            /* [nframes] points per frame */
+    const float* d_pos;            /* [nframes][3][q_cap] */
+    const float* d_normal;         /* [nframes][3][q_cap] */
+    const float* d_max_dist;       /* [nframes][q_cap] */
+    const float* d_min_dist;       /* [nframes][q_cap] */
+    const uint8_t* d_skip;         /* [nframes][q_cap] */
+    float* d_uvr;                  /* [nframes][q_cap][3] out */
+    int32_t* d_level_min;          /* [nframes][q_cap] out */
+    int32_t* d_level_max;          /* [nframes][q_cap] out */
+    uint8_t* d_valid;              /* [nframes][q_cap] out */
+    uint8_t* d_status;             /* [nframes][q_cap] out, nullable */
+    float* d_proj;                 /* [nframes][q_cap][3] out, nullable */
+    float* d_view_cos;             /* [nframes][q_cap] out, nullable */
+    int32_t* d_level;              /* [nframes][q_cap] out, nullable */
+    int32_t* d_n_in_view;          /* [nframes] out, nullable */
+} slamit_frustum_batch_rec;
+int slamit_frustum_batch_dev(int device, const slamit_frustum_batch_rec* batch, void* stream);
 
 /* ---- misc -------------------------------------------------------------------------------- */
 

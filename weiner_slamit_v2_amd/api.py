@@ -129,6 +129,36 @@ class TriangulateResult(C.Structure):
 TRIANGULATE_MAX_N, MAX_LEVELS = 8192, 16   # SLAMIT_TRIANGULATE_MAX_N, SLAMIT_MAX_LEVELS
 
 
+class FrustumFrame(C.Structure):
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("bf", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("view_cos_limit", C.c_float), ("log_scale_factor", C.c_float), ("th", C.c_float), ("n_levels", C.c_int32),
+                ("scale_factors", C.c_float * 16)]
+
+
+class FrustumProblem(C.Structure):
+    _fields_ = [("frame", FrustumFrame), ("n", C.c_int32), ("pos", C.c_void_p), ("normal", C.c_void_p), ("max_dist", C.c_void_p),
+                ("min_dist", C.c_void_p), ("skip", C.c_void_p)]
+
+
+class FrustumResult(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("proj", C.c_void_p), ("view_cos", C.c_void_p), ("level", C.c_void_p), ("uvr", C.c_void_p),
+                ("level_min", C.c_void_p), ("level_max", C.c_void_p), ("valid", C.c_void_p), ("n_in_view", C.c_int32)]
+
+
+class FrustumBatchRec(C.Structure):
+    _fields_ = [("nframes", C.c_int32), ("q_cap", C.c_int32), ("d_frames", C.c_void_p), ("d_m", C.c_void_p), ("d_pos", C.c_void_p),
+                ("d_normal", C.c_void_p), ("d_max_dist", C.c_void_p), ("d_min_dist", C.c_void_p), ("d_skip", C.c_void_p), ("d_uvr", C.c_void_p),
+                ("d_level_min", C.c_void_p), ("d_level_max", C.c_void_p), ("d_valid", C.c_void_p), ("d_status", C.c_void_p),
+                ("d_proj", C.c_void_p), ("d_view_cos", C.c_void_p), ("d_level", C.c_void_p), ("d_n_in_view", C.c_void_p)]
+
+
+FRUSTUM_MAX_N = 65536   # SLAMIT_FRUSTUM_MAX_N
+FRUSTUM_FRAME_DTYPE = np.dtype([("Rcw", "<f4", 9), ("tcw", "<f4", 3), ("Ow", "<f4", 3), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+                                ("bf", "<f4"), ("min_x", "<f4"), ("max_x", "<f4"), ("min_y", "<f4"), ("max_y", "<f4"), ("view_cos_limit", "<f4"),
+                                ("log_scale_factor", "<f4"), ("th", "<f4"), ("n_levels", "<i4"), ("scale_factors", "<f4", 16)])   # slamit_frustum_frame
+
+
 class VocDesc(C.Structure):
     _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32), ("n_nodes", C.c_int32),
                 ("parent", C.c_void_p), ("is_leaf", C.c_void_p), ("desc", C.c_void_p), ("weight", C.c_void_p)]
@@ -178,7 +208,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -228,6 +258,9 @@ def lib():
         L.slamit_sim3_ransac.argtypes = [i32, C.POINTER(Sim3RansacProblem), C.POINTER(Sim3RansacResult)]
         L.slamit_triangulate_batch.argtypes = [i32, i32, C.POINTER(TriangulateProblem), C.POINTER(TriangulateResult)]
         L.slamit_triangulate.argtypes = [i32, C.POINTER(TriangulateProblem), C.POINTER(TriangulateResult)]
+        L.slamit_frustum_batch.argtypes = [i32, i32, C.POINTER(FrustumProblem), C.POINTER(FrustumResult)]
+        L.slamit_frustum.argtypes = [i32, C.POINTER(FrustumProblem), C.POINTER(FrustumResult)]
+        L.slamit_frustum_batch_dev.argtypes = [i32, C.POINTER(FrustumBatchRec), vp]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
         L.slamit_voc_load_text.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
@@ -1298,3 +1331,95 @@ def triangulate_batch(problems, device=0):
 def triangulate(problem, device=0):
     """One (current keyframe, neighbour) problem: triangulate_batch([problem])[0]."""
     return triangulate_batch([problem], device)[0]
+
+
+_FRUSTUM_SCALARS = ("fx", "fy", "cx", "cy", "bf", "min_x", "max_x", "min_y", "max_y", "view_cos_limit", "log_scale_factor", "th")
+
+
+def frustum_frame_record(pr):
+    """The slamit_frustum_frame of a problem dict as a one-element numpy record array (FRUSTUM_FRAME_DTYPE): what frustum_batch_dev's
+    d_frames holds per frame."""
+    rec = np.zeros(1, FRUSTUM_FRAME_DTYPE)
+    for key, k in (("Rcw", 9), ("tcw", 3), ("Ow", 3)):
+        a = np.asarray(pr[key], np.float32).reshape(-1)
+        if len(a) != k:
+            raise SlamitError("frustum: %s has %d entries" % (key, len(a)))
+        rec[key][0] = a
+    for key in _FRUSTUM_SCALARS:
+        rec[key][0] = np.float32(pr[key])
+    sf = np.asarray(pr["scale_factors"], np.float32).reshape(-1)
+    nl = int(pr["n_levels"])
+    if len(sf) != nl:
+        raise SlamitError("frustum: scale_factors does not have n_levels entries")
+    rec["n_levels"][0] = nl
+    rec["scale_factors"][0, :min(nl, 16)] = sf[:16]
+    return rec
+
+
+def frustum_batch(problems, device=0):
+    """Tracking::SearchLocalPoints' visibility pass (Frame::isInFrustum + MapPoint::PredictScale, Frame.cc:389-445, MapPoint.cc:391-400)
+    and the queries of the SearchByProjection that follows, for a list of frames in ONE device call.  Each problem is a dict in the
+    layout of slamit_frustum_problem (synth.synth_frustum): Rcw (9), tcw, Ow (3), fx fy cx cy bf, min_x max_x min_y max_y,
+    view_cos_limit, log_scale_factor, th, n_levels, scale_factors (n_levels), pos, normal (n, 3), max_dist, min_dist (n) float32, skip
+    (n) uint8.  -> a list of dicts: status (n) uint8 (0 in view, else the first test that rejected the point; 7 = the level outside
+    the table, the stated departure), proj (n, 3) = u, v, uR, view_cos (n), level (n), and the guided search's query arrays uvr
+    (n, 3), level_min, level_max (n), valid (n); n_in_view."""
+    plist = list(problems)
+    m = len(plist)
+    P = (FrustumProblem * m)()
+    R = (FrustumResult * m)()
+    keep, outs = [], []
+    for i, pr in enumerate(plist):
+        k = {"pos": np.ascontiguousarray(pr["pos"], np.float32).reshape(-1, 3), "normal": np.ascontiguousarray(pr["normal"], np.float32).reshape(-1, 3),
+             "max_dist": np.ascontiguousarray(pr["max_dist"], np.float32).reshape(-1), "min_dist": np.ascontiguousarray(pr["min_dist"], np.float32).reshape(-1),
+             "skip": np.ascontiguousarray(pr["skip"], np.uint8).reshape(-1)}
+        n = len(k["skip"])
+        if any(len(a) != n for a in k.values()):
+            raise SlamitError("frustum: pos / normal / max_dist / min_dist / skip do not have the same length")
+        rec = frustum_frame_record(pr)
+        C.memmove(C.byref(P[i].frame), rec.ctypes.data, C.sizeof(FrustumFrame))
+        P[i].n = n
+        for key, a in k.items():
+            setattr(P[i], key, a.ctypes.data)
+        o = {"status": np.zeros(n, np.uint8), "proj": np.zeros((n, 3), np.float32), "view_cos": np.zeros(n, np.float32), "level": np.zeros(n, np.int32),
+             "uvr": np.zeros((n, 3), np.float32), "level_min": np.zeros(n, np.int32), "level_max": np.zeros(n, np.int32), "valid": np.zeros(n, np.uint8)}
+        for key, a in o.items():
+            setattr(R[i], key, a.ctypes.data)
+        keep.append(k)
+        outs.append(o)
+    _check(lib().slamit_frustum_batch(device, m, P, R), "slamit_frustum_batch")
+    del keep
+    for i, o in enumerate(outs):
+        o["n_in_view"] = int(R[i].n_in_view)
+    return outs
+
+
+def frustum(problem, device=0):
+    """One frame: frustum_batch([problem])[0]."""
+    return frustum_batch([problem], device)[0]
+
+
+def frustum_batch_dev(t, device=0, stream=None):
+    """The resident form.  t: dict of torch CUDA tensors frames (B, 44) f32 (rows of FRUSTUM_FRAME_DTYPE viewed as float32), m (B) i32,
+    pos / normal (B, 3, q_cap) f32 PLANES, max_dist / min_dist (B, q_cap) f32, skip (B, q_cap) u8, and the outputs uvr (B, q_cap, 3)
+    f32, level_min / level_max (B, q_cap) i32, valid (B, q_cap) u8 -- the tensors guided_search_batch_dev reads -- plus optionally
+    status (B, q_cap) u8, proj (B, q_cap, 3) f32, view_cos (B, q_cap) f32, level (B, q_cap) i32, n_in_view (B) i32.
+    Asynchronous on `stream`."""
+    b, q_cap = t["pos"].shape[0], t["pos"].shape[2]
+    if t["frames"].numel() * t["frames"].element_size() != b * C.sizeof(FrustumFrame):
+        raise SlamitError("frustum_batch_dev: frames does not hold one slamit_frustum_frame per frame")
+    for key, per in (("pos", 3), ("normal", 3), ("max_dist", 1), ("min_dist", 1), ("skip", 1), ("uvr", 3), ("level_min", 1), ("level_max", 1), ("valid", 1),
+                     ("status", 1), ("proj", 3), ("view_cos", 1), ("level", 1)):
+        if t.get(key) is not None and (t[key].numel() != b * q_cap * per or not t[key].is_contiguous()):
+            raise SlamitError("frustum_batch_dev: %s is not a contiguous (B, q_cap) array" % key)
+    for key in ("m", "n_in_view"):
+        if t.get(key) is not None and t[key].numel() != b:
+            raise SlamitError("frustum_batch_dev: %s does not have one entry per frame" % key)
+
+    def opt(key):
+        return t[key].data_ptr() if t.get(key) is not None else None
+
+    rec = FrustumBatchRec(b, q_cap, t["frames"].data_ptr(), t["m"].data_ptr(), t["pos"].data_ptr(), t["normal"].data_ptr(), t["max_dist"].data_ptr(),
+                          t["min_dist"].data_ptr(), t["skip"].data_ptr(), t["uvr"].data_ptr(), t["level_min"].data_ptr(), t["level_max"].data_ptr(),
+                          t["valid"].data_ptr(), opt("status"), opt("proj"), opt("view_cos"), opt("level"), opt("n_in_view"))
+    _check(lib().slamit_frustum_batch_dev(device, C.byref(rec), stream), "slamit_frustum_batch_dev")

@@ -14,6 +14,7 @@
 //     shim_test osim3 <problem.bin> <out.bin>
 //     shim_test sim3solver <problem.bin> <out.bin>
 //     shim_test triangulate <problem.bin> <out.bin>
+//     shim_test frustum <problem.bin> <out.bin>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -32,6 +33,7 @@
 #include "ORBVocabulary.h"
 #include "KeyFrameDatabase.h"
 #include "LocalMapping.h"
+#include "Tracking.h"
 
 using namespace ORB_SLAM2;
 
@@ -994,6 +996,107 @@ static int run_triangulate(int argc, char** argv) {
     return 0;
 }
 
+// ---- Tracking::SearchLocalPoints through the template -----------------------------------------------------------------------------
+struct MockLocalPoint {   // the members Tracking.h lists on top of the search's
+    bool mbTrackInView, bad;
+    long unsigned int mnLastFrameSeen;
+    int mnTrackScaleLevel, nobs, id, visible;
+    float mTrackViewCos, mTrackProjX, mTrackProjXR, mTrackProjY, maxd, mind;
+    cv::Mat desc, pos, normal;
+    MockLocalPoint() : mbTrackInView(true), bad(false), mnLastFrameSeen(0), mnTrackScaleLevel(-77), nobs(1), id(-1), visible(0), mTrackViewCos(-7.f),
+                       mTrackProjX(-7.f), mTrackProjXR(-7.f), mTrackProjY(-7.f), maxd(0.f), mind(0.f) {}
+    bool isBad() { return bad; }
+    void IncreaseVisible() { ++visible; }
+    int Observations() { return nobs; }
+    float GetMaxDistance() { return maxd; }
+    float GetMinDistance() { return mind; }
+    cv::Mat GetDescriptor() { return desc.clone(); }
+    cv::Mat GetWorldPos() { return pos.clone(); }
+    cv::Mat GetNormal() { return normal.clone(); }
+};
+struct MockLocalFrame {
+    long unsigned int mnId;
+    cv::Mat mRcw, mtcw, mOw, mDescriptors;
+    std::vector<cv::KeyPoint> mvKeysUn;
+    std::vector<MockLocalPoint*> mvpMapPoints;
+    std::vector<float> mvuRight, mvScaleFactors;
+    float fx, fy, cx, cy, mbf, mfLogScaleFactor;
+    static float mnMinX, mnMaxX, mnMinY, mnMaxY, mfGridElementWidthInv, mfGridElementHeightInv;
+};
+float MockLocalFrame::mnMinX, MockLocalFrame::mnMaxX, MockLocalFrame::mnMinY, MockLocalFrame::mnMaxY;
+float MockLocalFrame::mfGridElementWidthInv, MockLocalFrame::mfGridElementHeightInv;
+
+// problem.bin: int32 n ; slamit_frustum_frame ; float pos[3 n] normal[3 n] max_dist[n] min_dist[n] ; u8 skip[n] (0, 1 = bad, 2 = seen in this
+//   frame), padded to 4 ; int32 nobs[n] ; u8 desc[32 n] ; int32 nkp ; float nnratio invw invh ; float xy[2 nkp] ; int32 octave[nkp]
+//   state[nkp] (0 none, 1 the frame's own point with observations, 2 its own point without, 3 its own BAD point) ; u8 desc[32 nkp]
+// out.bin: int32 status nmatches ninview ; per local point: int32 inview level visible, float projx projy projxr viewcos ;
+//   per keypoint int32 owner (-1 none, -2 / -3 the frame's own point with / without observations, else local index) ;
+//   int32 visible of the two own points, int32 their mnLastFrameSeen == mnId
+static int run_frustum(int argc, char** argv) {
+    if (argc < 4) return 2;
+    std::vector<unsigned char> raw = slurp(argv[2]);
+    Reader R{raw.data()};
+    const int n = R.get<int>();
+    const slamit_frustum_frame fr = R.get<slamit_frustum_frame>();
+    const float* pos = R.arr<float>(3 * (size_t)n); const float* nrm = R.arr<float>(3 * (size_t)n);
+    const float* maxd = R.arr<float>(n); const float* mind = R.arr<float>(n);
+    const unsigned char* skip = R.arr<unsigned char>(n);
+    R.p += (4 - n % 4) % 4;
+    const int* nobs = R.arr<int>(n);
+    const unsigned char* qd = R.arr<unsigned char>(32 * (size_t)n);
+    const int nkp = R.get<int>();
+    const float nnratio = R.get<float>();
+    MockLocalFrame::mfGridElementWidthInv = R.get<float>(); MockLocalFrame::mfGridElementHeightInv = R.get<float>();
+    const float* xy = R.arr<float>(2 * (size_t)nkp); const int* oct = R.arr<int>(nkp); const int* state = R.arr<int>(nkp);
+    const unsigned char* kd = R.arr<unsigned char>(32 * (size_t)nkp);
+    MockLocalFrame F;
+    F.mnId = 41;
+    MockLocalFrame::mnMinX = fr.min_x; MockLocalFrame::mnMaxX = fr.max_x; MockLocalFrame::mnMinY = fr.min_y; MockLocalFrame::mnMaxY = fr.max_y;
+    F.mRcw = cv::Mat(3, 3, CV_32F); F.mtcw = mat_from(fr.tcw, 3); F.mOw = mat_from(fr.Ow, 3);
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) F.mRcw.at<float>(r, c) = fr.Rcw[3 * r + c];
+    F.fx = fr.fx; F.fy = fr.fy; F.cx = fr.cx; F.cy = fr.cy; F.mbf = fr.bf; F.mfLogScaleFactor = fr.log_scale_factor;
+    F.mvScaleFactors.assign(fr.scale_factors, fr.scale_factors + fr.n_levels);
+    F.mDescriptors = cv::Mat(nkp, 32, CV_8U);
+    F.mvKeysUn.resize(nkp); F.mvuRight.assign(nkp, -1.f); F.mvpMapPoints.assign(nkp, (MockLocalPoint*)0);
+    MockLocalPoint own1, own2, ownBad;
+    own1.nobs = 3; own1.id = -2; own2.nobs = 0; own2.id = -3; ownBad.bad = true; ownBad.id = -4;
+    for (int i = 0; i < nkp; ++i) {
+        F.mvKeysUn[i] = cv::KeyPoint(xy[2 * i], xy[2 * i + 1], 31.f, -1.f, 0, oct[i]);
+        memcpy(F.mDescriptors.ptr(i), kd + 32 * (size_t)i, 32);
+        if (state[i] == 1) F.mvpMapPoints[i] = &own1;
+        if (state[i] == 2) F.mvpMapPoints[i] = &own2;
+        if (state[i] == 3) F.mvpMapPoints[i] = &ownBad;
+    }
+    std::vector<MockLocalPoint> mps(n);
+    std::vector<MockLocalPoint*> local(n);
+    for (int i = 0; i < n; ++i) {
+        MockLocalPoint& p = mps[i];
+        p.id = i; p.bad = skip[i] == 1; p.mnLastFrameSeen = skip[i] == 2 ? F.mnId : 7; p.nobs = nobs[i]; p.maxd = maxd[i]; p.mind = mind[i];
+        // A point seen in this frame is one of the frame's own, and the loop over those has already cleared its flag (Tracking.cc:1426); a bad
+        // point keeps a stale `true`, which the search must get past by isBad() alone.  Every other point starts `true` too: isInFrustum clears it.
+        if (skip[i] == 2) p.mbTrackInView = false;
+        p.pos = mat_from(pos + 3 * (size_t)i, 3); p.normal = mat_from(nrm + 3 * (size_t)i, 3);
+        p.desc = cv::Mat(1, 32, CV_8U); memcpy(p.desc.ptr(0), qd + 32 * (size_t)i, 32);
+        local[i] = &p;
+    }
+    const int nm = Tracking::SearchLocalPoints(F, local, (int)fr.th, nnratio);
+    const int status = Tracking::LastStatus(), ninview = Tracking::LastInView();
+    if (status != 0) fprintf(stderr, "frustum failed: %s\n", slamit_last_error());
+    FILE* f = fopen(argv[3], "wb");
+    fwrite(&status, 4, 1, f); fwrite(&nm, 4, 1, f); fwrite(&ninview, 4, 1, f);
+    for (int i = 0; i < n; ++i) {
+        const MockLocalPoint& p = mps[i];
+        const int a[3] = {p.mbTrackInView ? 1 : 0, p.mnTrackScaleLevel, p.visible};
+        const float b[4] = {p.mTrackProjX, p.mTrackProjY, p.mTrackProjXR, p.mTrackViewCos};
+        fwrite(a, 4, 3, f); fwrite(b, 4, 4, f);
+    }
+    for (int i = 0; i < nkp; ++i) { int o = F.mvpMapPoints[i] ? F.mvpMapPoints[i]->id : -1; fwrite(&o, 4, 1, f); }
+    const int tail[4] = {own1.visible, own2.visible, own1.mnLastFrameSeen == F.mnId, own2.mnLastFrameSeen == F.mnId};
+    fwrite(tail, 4, 4, f);
+    fclose(f);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     std::string mode = argv[1];
@@ -1010,5 +1113,6 @@ int main(int argc, char** argv) {
     if (mode == "osim3") return run_osim3(argc, argv);
     if (mode == "sim3solver") return run_sim3solver(argc, argv);
     if (mode == "triangulate") return run_triangulate(argc, argv);
+    if (mode == "frustum") return run_frustum(argc, argv);
     return 2;
 }

@@ -495,6 +495,47 @@ def synth_triangulation(n=300, seed=0, baseline=0.3, outlier_frac=0.2, noise_px=
                 ratio_factor=f32(1.5) * f32(1.2), true=dict(X=Xw, bad=bad, behind=behind, jump=jump))
 
 
+def synth_frustum(seed=0, n=1000, th=1.0, n_levels=8, width=640, height=480, skip_frac=0.05, behind_frac=0.08, frontal_frac=0.3,
+                  max_angle_deg=75.0, level_span=(-1.5, 1.5)):
+    """What Tracking::SearchLocalPoints holds for one frame (Tracking.cc:1409-1464): a posed pinhole frame and n local map points
+    around its view cone, so that every test of Frame::isInFrustum rejects a visible share.  The points are drawn in the camera
+    frame -- depth log-uniform in 0.5..20 (a share behind_frac behind the camera), x / y over 1.3 times the field of view -- and
+    moved to the world.  Each carries a mean viewing direction (GetNormal) that is its ray turned by an angle: up to 3 degrees for a
+    share frontal_frac (viewCos > 0.998, the narrow search window), up to max_angle_deg for the rest (viewingCosLimit 0.5 is 60
+    degrees).  Its scale-invariance range is max_dist = dist * 1.2^e with e uniform in [level_span[0], n_levels + level_span[1]]
+    and min_dist = max_dist / 1.2^(n_levels - 1), as MapPoint::UpdateNormalAndDepth sets them: e < -1 and e > n_levels + 0.22 fall
+    to the distance gate, ceil(e) is the predicted level, and n_levels - 1 < e <= n_levels + 0.22 passes the gate with a level
+    outside the table.  skip marks a share skip_frac as bad or already seen.  Layout of slamit_frustum_problem."""
+    rs = np.random.RandomState(14000 + seed)
+    f32 = np.float32
+    fx, fy, cx, cy, bf = f32(517.3), f32(516.5), f32(318.6), f32(255.3), f32(38.6)
+    min_x, max_x, min_y, max_y = f32(-4.3), f32(width + 5.1), f32(-2.7), f32(height + 3.9)
+    R, t = se3_exp(np.concatenate([rs.uniform(-0.4, 0.4, 3), rs.uniform(-2.0, 2.0, 3)]))
+    Rcw, tcw = R.astype(f32), t.astype(f32)
+    Ow = (-(Rcw.astype(np.float64).T @ tcw.astype(np.float64))).astype(f32)         # as Frame::UpdatePoseMatrices stores it
+    z = np.exp(rs.uniform(np.log(0.5), np.log(20.0), n))
+    z[rs.rand(n) < behind_frac] *= -1.0
+    hx, hy = 1.3 * 0.5 * width / float(fx), 1.3 * 0.5 * height / float(fy)
+    Xc = np.stack([rs.uniform(-hx, hx, n) * np.abs(z), rs.uniform(-hy, hy, n) * np.abs(z), z], 1)
+    pos = ((Xc - t) @ R).astype(f32)
+    PO = pos.astype(np.float64) - Ow.astype(np.float64)
+    dist = np.linalg.norm(PO, axis=1)
+    d = PO / dist[:, None]
+    ang = np.deg2rad(np.where(rs.rand(n) < frontal_frac, rs.uniform(0.0, 3.0, n), rs.uniform(0.0, max_angle_deg, n)))
+    side = rs.normal(size=(n, 3))
+    side -= (side * d).sum(1)[:, None] * d
+    side /= np.linalg.norm(side, axis=1)[:, None]
+    normal = (np.cos(ang)[:, None] * d + np.sin(ang)[:, None] * side).astype(f32)
+    e = rs.uniform(level_span[0], n_levels + level_span[1], n)
+    max_dist = (dist * 1.2 ** e).astype(f32)
+    min_dist = (max_dist / f32(1.2) ** f32(n_levels - 1)).astype(f32)
+    skip = (rs.rand(n) < skip_frac).astype(np.uint8)
+    scale_f = (f32(1.2) ** np.arange(n_levels, dtype=f32)).astype(f32)
+    return dict(n=n, Rcw=Rcw.reshape(9), tcw=tcw, Ow=Ow, fx=fx, fy=fy, cx=cx, cy=cy, bf=bf, min_x=min_x, max_x=max_x, min_y=min_y, max_y=max_y,
+                view_cos_limit=f32(0.5), log_scale_factor=f32(np.log(f32(1.2))), th=f32(th), n_levels=n_levels, scale_factors=scale_f,
+                pos=pos, normal=normal, max_dist=max_dist, min_dist=min_dist, skip=skip, true=dict(e=e, angle=ang, Xc=Xc))
+
+
 def synth_map(n_kf, n_pt, obs_per_pt, n_fixed, seed, stereo_frac=0.0, loop=True, outlier_frac=0.03, baseline=0.08):
     """A map-sized BA window (slamit_ba_problem layout, as synth_ba): n_kf cameras on a circle of radius 2 in the x-z plane, each looking
     outward, and n_pt points on a cylinder of radius 6 around it.  loop=True: the trajectory closes (keyframe k at 2 pi k / n_kf), so the
