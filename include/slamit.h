@@ -131,7 +131,9 @@ int slamit_orb_debug_blurred(slamit_orb* h, int frame, int level, uint8_t* dst, 
 #define SLAMIT_HAMMING_MAX_TRAIN 65535   /* train rows per set in the best/second entry points (index packed in 16 bits) */
 /* For each of nq query descriptors: best and second-best Hamming distance over the train
  * descriptors, and the index of the best (strict '<', first index wins; the reference's
- * selection rule, src/ORBmatcher.cc:1404-1428). With nt == 0: best = second = 256, idx = -1. */
+ * selection rule, src/ORBmatcher.cc:1404-1428). With nt == 0: best = second = 256, idx = -1.  A train row 256 bits
+ * away is still a row: when every row is, idx = 0 and best = second = 256 (the reference's loop, which starts from 256, would keep -1;
+ * no caller accepts such a match). */
 int slamit_hamming_best2(const uint8_t* q, int nq, const uint8_t* t, int nt, int32_t* best_idx,
                          int32_t* best, int32_t* second);
 
@@ -386,7 +388,8 @@ typedef struct slamit_camera {
 #define SLAMIT_FRAME_GRID_COLS 64   /* FRAME_GRID_COLS, include/Frame.h:41 */
 #define SLAMIT_FRAME_GRID_ROWS 48   /* FRAME_GRID_ROWS, include/Frame.h:40 */
 #define SLAMIT_FRAME_GRID_CELLS (SLAMIT_FRAME_GRID_COLS * SLAMIT_FRAME_GRID_ROWS)
-#define SLAMIT_FRAME_MAX_KP 30000
+#define SLAMIT_FRAME_MAX_KP 30000    /* one workgroup per frame keeps a short per keypoint slot in LDS: 12,320 B static + 2 B per slot,
+                                       72,320 B at the ceiling; the library raises the kernel's limit itself past 48 KiB */
 
 /* cv::undistortPoints(xy, xy, K, D, Mat(), K) on n points (what Frame::ComputeImageBounds feeds the four image
  * corners to, Frame.cc:561-590).  No k1 == 0 shortcut here: that belongs to Frame::UndistortKeyPoints. */
@@ -571,6 +574,11 @@ typedef struct slamit_pose_result {
     double chi2[4];          /* out: robust cost of the last evaluated trial of each round */
 } slamit_pose_result;
 
+/* One workgroup per frame keeps a flag byte per correspondence in LDS: n + 16 B beside the kernel's 1,496 B of static LDS, 67,048 B
+ * at the ceiling, of the 160 KiB a gfx950 workgroup may hold (a frame has a few thousand correspondences).  A frame with more fails
+ * the whole call with SLAMIT_ERR_CAPACITY before anything is launched. */
+#define SLAMIT_POSE_MAX_N 65536
+
 /* nframes independent frames in one launch (host pointers, synchronous). */
 int slamit_pose_optimize_batch(int device, int nframes, const slamit_pose_problem* probs, slamit_pose_result* results);
 int slamit_pose_optimize(int device, const slamit_pose_problem* prob, slamit_pose_result* res);
@@ -604,6 +612,9 @@ typedef struct slamit_sim3_result {
     int32_t n_its[2];            /* LM iterations run in each stage */
     double chi2[2];              /* robust cost of the last evaluated trial of each stage */
 } slamit_sim3_result;
+
+/* As for the pose: n + 16 B of flags beside 3,680 B of static LDS, 69,232 B at the ceiling; more fails with SLAMIT_ERR_CAPACITY. */
+#define SLAMIT_SIM3_MAX_N 65536
 
 int slamit_sim3_optimize_batch(int device, int nproblems, const slamit_sim3_problem* probs, slamit_sim3_result* results);
 int slamit_sim3_optimize(int device, const slamit_sim3_problem* prob, slamit_sim3_result* res);

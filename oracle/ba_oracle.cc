@@ -644,8 +644,11 @@ int pose_optimize_round(Pose& T, const double* in, std::vector<PEdge>& E, double
 
 }  // namespace
 
-extern "C" int pose_oracle_solve(const slamit_pose_problem* pb, slamit_pose_result* res) {
+// gate_margin (n entries, may be null): per edge the least |chi2 - gate| / gate over the four relabellings, i.e. how close the edge
+// ever came to changing its flag (tests/test_ceiling_fixtures.py keeps the large fixtures clear of the gate with it)
+static int pose_oracle_solve_impl(const slamit_pose_problem* pb, slamit_pose_result* res, double* gate_margin) {
     const int n = pb->n;
+    if (gate_margin) for (int e = 0; e < n; ++e) gate_margin[e] = HUGE_VAL;
     Pose T0;
     R_to_quat(pb->pose, T0.q);
     quat_normalize(T0.q);
@@ -682,6 +685,7 @@ extern "C" int pose_oracle_solve(const slamit_pose_problem* pb, slamit_pose_resu
                 pose_edge_error(ed, Xc, pb->intr, bf);
             }
             const float chi2 = (float)ed.chi2;
+            if (gate_margin) { const double g = ed.stereo ? 7.815f : 5.991f; gate_margin[e] = std::min(gate_margin[e], fabs(ed.chi2 - g) / g); }
             if (chi2 > (ed.stereo ? 7.815f : 5.991f)) { res->outlier[e] = 1; ed.active = false; ++nBad; }   // chi2Mono / chi2Stereo (:369-370)
             else { res->outlier[e] = 0; ed.active = true; }
             if (round == 2) ed.robust = false;
@@ -694,6 +698,11 @@ extern "C" int pose_oracle_solve(const slamit_pose_problem* pb, slamit_pose_resu
     for (int i = 0; i < 3; ++i) res->pose[9 + i] = T.t[i];
     res->n_inliers = n - nBad;
     return 0;
+}
+
+extern "C" int pose_oracle_solve(const slamit_pose_problem* pb, slamit_pose_result* res) { return pose_oracle_solve_impl(pb, res, nullptr); }
+extern "C" int pose_oracle_solve_margin(const slamit_pose_problem* pb, slamit_pose_result* res, double* gate_margin) {
+    return pose_oracle_solve_impl(pb, res, gate_margin);
 }
 
 
@@ -899,8 +908,13 @@ int sim3_optimize_stage(Sim3& S, const double* in1, const double* in2, std::vect
 
 }  // namespace
 
-extern "C" int sim3_oracle_solve(const slamit_sim3_problem* pb, slamit_sim3_result* res) {
+// gate_margin (n entries, may be null): per pair the least |chi2 - th2| / th2 over both edges and both tests (see pose_oracle_solve_impl)
+static int sim3_oracle_solve_impl(const slamit_sim3_problem* pb, slamit_sim3_result* res, double* gate_margin) {
     const int n = pb->n;
+    if (gate_margin) for (int k = 0; k < n; ++k) gate_margin[k] = HUGE_VAL;
+    auto margin = [&](int k, const SPair& P) {
+        if (gate_margin) gate_margin[k] = std::min(gate_margin[k], std::min(fabs(P.chi12 - (double)(float)pb->th2), fabs(P.chi21 - (double)(float)pb->th2)) / (double)(float)pb->th2);
+    };
     Sim3 S;
     R_to_quat(pb->r12, S.q);   // Sim3(R, t, s): Quaterniond(R), not normalised
     for (int i = 0; i < 3; ++i) S.t[i] = pb->t12[i];
@@ -920,14 +934,17 @@ extern "C" int sim3_oracle_solve(const slamit_sim3_problem* pb, slamit_sim3_resu
     memcpy(res->r12, pb->r12, sizeof(res->r12)); memcpy(res->t12, pb->t12, sizeof(res->t12)); res->s12 = pb->s12;
     res->n_its[0] = sim3_optimize_stage(S, pb->intr1, pb->intr2, E, delta, pb->fix_scale != 0, 5, &res->chi2[0]);
     int nBad = 0;
-    for (int k = 0; k < n; ++k)
+    for (int k = 0; k < n; ++k) {
+        margin(k, E[k]);
         if (E[k].chi12 > th2 || E[k].chi21 > th2) { res->inlier[k] = 0; E[k].active = false; ++nBad; }
+    }
     const int more = nBad > 0 ? 10 : 5;
     if (n - nBad < 10) { res->n_inliers = 0; return 0; }
     res->n_its[1] = sim3_optimize_stage(S, pb->intr1, pb->intr2, E, delta, pb->fix_scale != 0, more, &res->chi2[1]);
     int nIn = 0;
     for (int k = 0; k < n; ++k) {
         if (!E[k].active) continue;
+        margin(k, E[k]);
         if (E[k].chi12 > th2 || E[k].chi21 > th2) res->inlier[k] = 0;
         else ++nIn;
     }
@@ -938,4 +955,9 @@ extern "C" int sim3_oracle_solve(const slamit_sim3_problem* pb, slamit_sim3_resu
     res->s12 = S.s;
     res->n_inliers = nIn;
     return 0;
+}
+
+extern "C" int sim3_oracle_solve(const slamit_sim3_problem* pb, slamit_sim3_result* res) { return sim3_oracle_solve_impl(pb, res, nullptr); }
+extern "C" int sim3_oracle_solve_margin(const slamit_sim3_problem* pb, slamit_sim3_result* res, double* gate_margin) {
+    return sim3_oracle_solve_impl(pb, res, gate_margin);
 }

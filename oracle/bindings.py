@@ -478,12 +478,12 @@ class _PoseResult(C.Structure):
 
 def _pose_call(which, prob):
     if ("pose", which) not in _ba:
-        if which == "oracle":
+        if which in ("oracle", "margin"):
             build()
-            fn = C.CDLL(os.path.join(HERE, "libba_oracle.so")).pose_oracle_solve
+            fn = getattr(C.CDLL(os.path.join(HERE, "libba_oracle.so")), "pose_oracle_solve" + ("_margin" if which == "margin" else ""))
         else:
             fn = C.CDLL(os.path.join(HERE, "_ref", "libba_ref.so")).pose_ref_solve
-        fn.argtypes = [C.POINTER(_PoseProblem), C.POINTER(_PoseResult)]
+        fn.argtypes = [C.POINTER(_PoseProblem), C.POINTER(_PoseResult)] + ([C.c_void_p] if which == "margin" else [])
         _ba[("pose", which)] = fn
     keep = {k: np.ascontiguousarray(prob[k], np.float64) for k in ("pose", "intr", "xw", "uv", "inv_sigma2")}
     n = len(keep["inv_sigma2"])
@@ -494,8 +494,12 @@ def _pose_call(which, prob):
     pose = np.zeros(12)
     outl = np.zeros(max(n, 1), np.uint8)
     r = _PoseResult(pose.ctypes.data, outl.ctypes.data, 0)
-    assert _ba[("pose", which)](C.byref(p), C.byref(r)) == 0
-    return {"pose": pose, "outlier": outl[:n].copy(), "n_inliers": r.n_inliers, "n_its": list(r.n_its), "chi2": list(r.chi2)}
+    margin = np.full(max(n, 1), np.inf)
+    assert _ba[("pose", which)](C.byref(p), C.byref(r), *([margin.ctypes.data] if which == "margin" else [])) == 0
+    out = {"pose": pose, "outlier": outl[:n].copy(), "n_inliers": r.n_inliers, "n_its": list(r.n_its), "chi2": list(r.chi2)}
+    if which == "margin":
+        out["gate_margin"] = margin[:n]
+    return out
 
 
 class _Sim3Problem(C.Structure):
@@ -527,25 +531,34 @@ def sim3_problem_struct(prob, cls=_Sim3Problem):
 def _sim3_call(which, prob):
     if ("sim3", which) not in _ba:
         build()
-        if which == "oracle":
-            fn = C.CDLL(os.path.join(HERE, "libba_oracle.so")).sim3_oracle_solve
+        if which in ("oracle", "margin"):
+            fn = getattr(C.CDLL(os.path.join(HERE, "libba_oracle.so")), "sim3_oracle_solve" + ("_margin" if which == "margin" else ""))
         else:
             fn = C.CDLL(os.path.join(HERE, "_ref", "libba_ref.so")).sim3_ref_solve
-        fn.argtypes = [C.POINTER(_Sim3Problem), C.POINTER(_Sim3Result)]
+        fn.argtypes = [C.POINTER(_Sim3Problem), C.POINTER(_Sim3Result)] + ([C.c_void_p] if which == "margin" else [])
         _ba[("sim3", which)] = fn
     p, keep = sim3_problem_struct(prob)
     inl = np.zeros(max(p.n, 1), np.uint8)
     r = _Sim3Result()
     r.inlier = inl.ctypes.data
-    assert _ba[("sim3", which)](C.byref(p), C.byref(r)) == 0
+    margin = np.full(max(p.n, 1), np.inf)
+    assert _ba[("sim3", which)](C.byref(p), C.byref(r), *([margin.ctypes.data] if which == "margin" else [])) == 0
     del keep
-    return {"r12": np.array(r.r12[:]).reshape(3, 3), "t12": np.array(r.t12[:]), "s12": r.s12, "inlier": inl[:p.n].copy(),
-            "n_inliers": r.n_inliers, "n_its": list(r.n_its), "chi2": list(r.chi2)}
+    out = {"r12": np.array(r.r12[:]).reshape(3, 3), "t12": np.array(r.t12[:]), "s12": r.s12, "inlier": inl[:p.n].copy(),
+           "n_inliers": r.n_inliers, "n_its": list(r.n_its), "chi2": list(r.chi2)}
+    if which == "margin":
+        out["gate_margin"] = margin[:p.n]
+    return out
 
 
 def sim3_solve(prob):
     """CPU oracle restatement of Optimizer::OptimizeSim3 (oracle/ba_oracle.cc)."""
     return _sim3_call("oracle", prob)
+
+
+def sim3_solve_margin(prob):
+    """sim3_solve plus "gate_margin": per pair the least |chi2 - th2| / th2 over both edges and both chi2 tests."""
+    return _sim3_call("margin", prob)
 
 
 def sim3_ref_solve(prob):
@@ -556,6 +569,11 @@ def sim3_ref_solve(prob):
 def pose_solve(prob):
     """CPU restatement of PoseOptimization (oracle/ba_oracle.cc)."""
     return _pose_call("oracle", prob)
+
+
+def pose_solve_margin(prob):
+    """pose_solve plus "gate_margin": per edge the least |chi2 - gate| / gate over the four relabellings."""
+    return _pose_call("margin", prob)
 
 
 def pose_ref_solve(prob):

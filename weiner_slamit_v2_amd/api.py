@@ -184,6 +184,8 @@ class BaProfile(C.Structure):
     _fields_ = [("phase_ms", C.c_double * 5), ("slots", C.c_int32), ("nwin", C.c_int32), ("schur_exec_mflop", C.c_double)]
 
 
+POSE_MAX_N, SIM3_MAX_N = 65536, 65536   # SLAMIT_POSE_MAX_N, SLAMIT_SIM3_MAX_N
+FRAME_MAX_KP, HAMMING_MAX_TRAIN, BOW_MAX_GROUP = 30000, 65535, 2048   # SLAMIT_FRAME_MAX_KP, SLAMIT_HAMMING_MAX_TRAIN, SLAMIT_BOW_MAX_GROUP
 BA_PHASES = ("linearize", "schur", "solve", "update", "residuals")   # slamit_ba_profile_out.phase_ms
 
 

@@ -128,6 +128,15 @@ __global__ __launch_bounds__(FF_THREADS) void frame_finish_kernel(
     }
 }
 
+// frame_finish_kernel's LDS: s_cnt + s_wave (static; 12,320 B as built) and one short per keypoint slot: 72,320 B at
+// SLAMIT_FRAME_MAX_KP.  Past 48 KiB the kernel's limit is raised before the launch, like every other kernel here that can pass it.
+#define FF_STATIC_LDS ((FG_CELLS + 1 + FF_THREADS / 64) * sizeof(int) + 16)
+static hipError_t frame_finish_prepare(int cap) {
+    const size_t dyn = sizeof(short) * (size_t)cap;
+    if (FF_STATIC_LDS + dyn <= 48 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(frame_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+}
+
 static CamD make_cam(const slamit_camera* c) {
     CamD d;
     d.fx = c->fx; d.fy = c->fy; d.cx = c->cx; d.cy = c->cy;
@@ -165,6 +174,7 @@ extern "C" int slamit_frame_finish_batch_dev(int device, const slamit_camera* ca
     if (cap > SLAMIT_FRAME_MAX_KP) return slamit_fail(SLAMIT_ERR_CAPACITY, "slamit_frame_finish_batch_dev: cap > SLAMIT_FRAME_MAX_KP");
     if (nframes == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
+    HIP_TRY(frame_finish_prepare(cap));
     hipLaunchKernelGGL(frame_finish_kernel, dim3(nframes), dim3(FF_THREADS), sizeof(short) * (size_t)std::max(cap, 1), (hipStream_t)stream,
                        make_cam(cam), d_kps, d_n, 0, cap, min_x, min_y, inv_w, inv_h, d_kps_un, d_cell_start, d_cell_items);
     HIP_TRY(hipGetLastError());
@@ -190,6 +200,7 @@ extern "C" int slamit_frame_finish(int device, const slamit_camera* cam, const s
         memcpy(in.at(S.host), kps, in.bytes());
         HIP_TRY_AT("slamit_frame_finish", slamit_stage_upload(S, L));
     }
+    HIP_TRY_AT("slamit_frame_finish", frame_finish_prepare(cap));
     hipLaunchKernelGGL(frame_finish_kernel, dim3(1), dim3(FF_THREADS), sizeof(short) * (size_t)cap, S.st, make_cam(cam), in.at(S.dev),
                        (const int*)nullptr, n, cap, min_x, min_y, inv_w, inv_h, un.at(S.dev), cs.at(S.dev), ci.at(S.dev));
     HIP_TRY_AT("slamit_frame_finish", slamit_stage_download_and_wait(S, L));

@@ -226,6 +226,7 @@ int slamit_pose_optimize_batch(int device, int nframes, const slamit_pose_proble
         const slamit_pose_problem& P = probs[f];
         if (P.n < 0 || !P.pose || !P.intr || (P.n && (!P.xw || !P.uv || !P.inv_sigma2)) || !results[f].pose || (P.n && !results[f].outlier))
             return slamit_fail(SLAMIT_ERR_ARG, "slamit_pose_optimize_batch: null array");
+        if (P.n > SLAMIT_POSE_MAX_N) return slamit_fail(SLAMIT_ERR_CAPACITY, "slamit_pose_optimize_batch: more than SLAMIT_POSE_MAX_N correspondences");
     }
     SLAMIT_USE_DEVICE(device);
     // [doubles of every frame (lm_layout.h) | ints | PoseFrame records | flags].  A frame's doubles mix what the kernel reads and
@@ -259,7 +260,7 @@ int slamit_pose_optimize_batch(int device, int nframes, const slamit_pose_proble
         F.n_inliers = (gi*)(ints.at(S.dev) + 5 * f); F.n_its = (gi*)(ints.at(S.dev) + 5 * f + 1);
     }
     HIP_TRY_AT(where, slamit_stage_upload(S, L));
-    if (nmax > 48 * 1024) HIP_TRY_AT(where, hipFuncSetAttribute(reinterpret_cast<const void*>(pose_opt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, nmax + 16));
+    if (nmax > 32 * 1024) HIP_TRY_AT(where, hipFuncSetAttribute(reinterpret_cast<const void*>(pose_opt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, nmax + 16));
     hipLaunchKernelGGL(pose_opt_kernel, dim3(nframes), dim3(256), (size_t)nmax + 16, S.st, frames.at(S.dev));
     HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
     for (int f = 0; f < nframes; ++f) {

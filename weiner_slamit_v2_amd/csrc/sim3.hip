@@ -277,6 +277,7 @@ int slamit_sim3_optimize_batch(int device, int nprob, const slamit_sim3_problem*
         const slamit_sim3_problem& P = probs[f];
         if (P.n < 0 || (P.n && (!P.p1 || !P.p2 || !P.obs1 || !P.obs2 || !P.inv_sigma2_1 || !P.inv_sigma2_2 || !results[f].inlier)))
             return slamit_fail(SLAMIT_ERR_ARG, "slamit_sim3_optimize_batch: null array");
+        if (P.n > SLAMIT_SIM3_MAX_N) return slamit_fail(SLAMIT_ERR_CAPACITY, "slamit_sim3_optimize_batch: more than SLAMIT_SIM3_MAX_N correspondences");
         if (!(P.s12 > 0) || !(P.th2 > 0)) return slamit_fail(SLAMIT_ERR_ARG, "slamit_sim3_optimize_batch: scale and th2 must be positive");
     }
     SLAMIT_USE_DEVICE(device);
