@@ -25,12 +25,13 @@
 #include "cvlite.h"
 #endif
 
-#include "../../include/slamit.h"
+#include "shim_common.h"
 
 namespace ORB_SLAM2 {
 namespace FrameOps {
 
-inline int& lastStatus() { static int s = 0; return s; }
+struct Status {};   // FrameOps is a namespace: the tag of its per-thread status cell
+inline int& lastStatus() { return shim::status<Status>(); }
 inline int LastStatus() { return lastStatus(); }
 
 template <class FrameT>

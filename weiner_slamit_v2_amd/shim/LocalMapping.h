@@ -29,8 +29,8 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/slamit.h"
 #include "ORBmatcher.h"
+#include "shim_common.h"
 
 namespace ORB_SLAM2 {
 
@@ -67,10 +67,10 @@ public:
     template <class KeyFrameT, class NewPointFn, class StopFn>
     static int CreateNewMapPoints(KeyFrameT* cur, const std::vector<KeyFrameT*>& neigh, bool monocular, NewPointFn&& make, StopFn&& stop, int device = 0) {
         status() = SLAMIT_OK;
-        if (!monocular) return refuse("CreateNewMapPoints: only the monocular path is on the device");
-        if (hasStereo(cur)) return refuse("CreateNewMapPoints: the current keyframe carries stereo coordinates (mvuRight >= 0)");
+        if (!monocular) return shim::refuse<LocalMapping>("CreateNewMapPoints: only the monocular path is on the device");
+        if (hasStereo(cur)) return shim::refuse<LocalMapping>("CreateNewMapPoints: the current keyframe carries stereo coordinates (mvuRight >= 0)");
         for (size_t i = 0; i < neigh.size(); ++i)
-            if (hasStereo(neigh[i])) return refuse("CreateNewMapPoints: a neighbour keyframe carries stereo coordinates (mvuRight >= 0)");
+            if (hasStereo(neigh[i])) return shim::refuse<LocalMapping>("CreateNewMapPoints: a neighbour keyframe carries stereo coordinates (mvuRight >= 0)");
         ORBmatcher matcher(0.6, false);
         slamit_triangulate_problem P;
         pose(cur, P.Tcw1, P.intr1);
@@ -92,8 +92,7 @@ public:
             std::vector<std::pair<size_t, size_t> > vMatchedIndices;
             matcher.SearchForTriangulation(cur, pKF2, F12, vMatchedIndices, false);
             if (ORBmatcher::LastStatus() != SLAMIT_OK) {
-                status() = ORBmatcher::LastStatus();
-                fprintf(stderr, "CreateNewMapPoints: SearchForTriangulation failed (%d): %s\n", status(), slamit_last_error());
+                shim::report<LocalMapping>("CreateNewMapPoints: SearchForTriangulation", ORBmatcher::LastStatus());
                 return nnew;
             }
             const int nmatches = (int)vMatchedIndices.size();
@@ -112,7 +111,7 @@ public:
             P.n_levels = (int32_t)cur->mvScaleFactors.size();
             if (pKF2->mvScaleFactors.size() != cur->mvScaleFactors.size() || cur->mvLevelSigma2.size() != cur->mvScaleFactors.size() ||
                 pKF2->mvLevelSigma2.size() != cur->mvScaleFactors.size()) {
-                refuse("CreateNewMapPoints: the level tables of the two keyframes differ in length");
+                shim::refuse<LocalMapping>("CreateNewMapPoints: the level tables of the two keyframes differ in length");
                 return nnew;
             }
             P.kp1_xy = kp1.data(); P.kp2_xy = kp2.data(); P.octave1 = o1.data(); P.octave2 = o2.data();
@@ -122,8 +121,7 @@ public:
             R.status = st.data(); R.x3d = x3d.data(); R.n_accepted = 0;
             const int rc = slamit_triangulate(device, &P, &R);
             if (rc != SLAMIT_OK) {
-                status() = rc;
-                fprintf(stderr, "CreateNewMapPoints: slamit_triangulate failed (%d): %s\n", rc, slamit_last_error());
+                shim::report<LocalMapping>("CreateNewMapPoints: slamit_triangulate", rc);
                 return nnew;
             }
             for (int k = 0; k < nmatches; ++k) {
@@ -146,12 +144,7 @@ public:
 
 private:
     static bool never() { return false; }
-    static int& status() { static thread_local int s = SLAMIT_OK; return s; }
-    static int refuse(const char* why) {
-        status() = SLAMIT_ERR_ARG;
-        fprintf(stderr, "%s\n", why);
-        return 0;
-    }
+    static int& status() { return shim::status<LocalMapping>(); }
     template <class KeyFrameT>
     static bool hasStereo(KeyFrameT* kf) {
         for (size_t i = 0; i < kf->mvuRight.size(); ++i)
@@ -161,10 +154,7 @@ private:
     template <class KeyFrameT>
     static void pose(KeyFrameT* kf, float T[12], float K[6]) {
         const cv::Mat R = kf->GetRotation(), t = kf->GetTranslation();
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) T[4 * r + c] = R.template at<float>(r, c);
-            T[4 * r + 3] = t.template at<float>(r, 0);
-        }
+        shim::load3x3(R, T, 4); shim::load3(t, T + 3, 0, 4);
         K[0] = kf->fx; K[1] = kf->fy; K[2] = kf->cx; K[3] = kf->cy; K[4] = kf->invfx; K[5] = kf->invfy;
     }
 };

@@ -2,15 +2,11 @@
 // acceptance thresholds and the rotation histogram are host logic as in the reference.
 #include "ORBmatcher.h"
 
-#include <math.h>
-
-#include "../../include/slamit.h"
-
 namespace ORB_SLAM2 {
 
 const int ORBmatcher::TH_HIGH = 100;     // ORBmatcher.cc:37
 const int ORBmatcher::TH_LOW = 50;       // :38
-const int ORBmatcher::HISTO_LENGTH = 30; // :39
+const int ORBmatcher::HISTO_LENGTH = shim::RotationHistogram::LENGTH; // :39
 
 ORBmatcher::ORBmatcher(float nnratio, bool checkOri) : mfNNratio(nnratio), mbCheckOrientation(checkOri) {}
 
@@ -46,9 +42,8 @@ bool ORBmatcher::BestTwo(const cv::Mat& query, const cv::Mat& train, std::vector
                                 bestDist.data(), secondDist.data()) == SLAMIT_OK;
 }
 
-static int g_status = 0;
-int ORBmatcher::LastStatus() { return g_status; }
-void ORBmatcher::setStatus(int rc) { g_status = rc; }
+int ORBmatcher::LastStatus() { return shim::status<ORBmatcher>(); }
+void ORBmatcher::setStatus(int rc) { shim::status<ORBmatcher>() = rc; }
 
 bool ORBmatcher::GuidedSearch(const std::vector<cv::KeyPoint>& keysUn, const cv::Mat& descriptors,
                               const std::vector<uint8_t>& kpTaken, float minX, float minY, float invW, float invH,
@@ -56,7 +51,7 @@ bool ORBmatcher::GuidedSearch(const std::vector<cv::KeyPoint>& keysUn, const cv:
                               float chi2Gate, const std::vector<float>* invLevelSigma2, int mode, std::vector<int>* acceptedKp) {
     const int n = (int)keysUn.size(), m = q.size();
     matchKp.assign(m, -1);
-    g_status = SLAMIT_OK;
+    setStatus(SLAMIT_OK);
     if (m == 0) return true;
     std::vector<float> xy(2 * (size_t)n);
     std::vector<int32_t> oct(n);
@@ -75,15 +70,15 @@ bool ORBmatcher::GuidedSearch(const std::vector<cv::KeyPoint>& keysUn, const cv:
     for (int i = 0; i < 16; ++i) rule.inv_level_sigma2[i] = (invLevelSigma2 && i < (int)invLevelSigma2->size()) ? (*invLevelSigma2)[i] : 1.f;
     int nm = 0;
     if (acceptedKp) acceptedKp->assign(m, -1);
-    g_status = slamit_guided_search(0, &fv, &sq, &rule, matchKp.data(), &nm, nullptr, acceptedKp ? acceptedKp->data() : nullptr, nullptr, nullptr);
-    return g_status == SLAMIT_OK;
+    setStatus(slamit_guided_search(0, &fv, &sq, &rule, matchKp.data(), &nm, nullptr, acceptedKp ? acceptedKp->data() : nullptr, nullptr, nullptr));
+    return LastStatus() == SLAMIT_OK;
 }
 
 bool ORBmatcher::BowSearch(const cv::Mat& desc1, const std::vector<uint8_t>& valid1, const cv::Mat& desc2, const std::vector<uint8_t>* valid2,
                            const BowGroups& g, int th, bool thInclusive, float nnratio, const EpipolarGate* gate, std::vector<int>& match12) {
     const int n1 = desc1.rows, n2 = desc2.rows;
     match12.assign(n1, -1);
-    g_status = SLAMIT_OK;
+    setStatus(SLAMIT_OK);
     if (n1 == 0 || n2 == 0 || g.size() == 0) return true;
     std::vector<uint8_t> t1, t2;
     slamit_bow_groups gg;
@@ -105,9 +100,9 @@ bool ORBmatcher::BowSearch(const cv::Mat& desc1, const std::vector<uint8_t>& val
         }
     }
     int nm = 0;
-    g_status = slamit_bow_search(0, packed_rows(desc1, t1), n1, valid1.empty() ? nullptr : valid1.data(), packed_rows(desc2, t2), n2,
-                                 valid2 ? valid2->data() : nullptr, &gg, &rule, match12.data(), nullptr, &nm);
-    return g_status == SLAMIT_OK;
+    setStatus(slamit_bow_search(0, packed_rows(desc1, t1), n1, valid1.empty() ? nullptr : valid1.data(), packed_rows(desc2, t2), n2,
+                                valid2 ? valid2->data() : nullptr, &gg, &rule, match12.data(), nullptr, &nm));
+    return LastStatus() == SLAMIT_OK;
 }
 
 int ORBmatcher::SearchBruteForce(const std::vector<cv::KeyPoint>& keys1, const cv::Mat& desc1,
@@ -117,48 +112,25 @@ int ORBmatcher::SearchBruteForce(const std::vector<cv::KeyPoint>& keys1, const c
     std::vector<int> idx, best, second;
     vnMatches12.assign(desc1.rows, -1);
     if (!BestTwo(desc1, desc2, idx, best, second)) return 0;
-    std::vector<int> rotHist[30];
-    const float factor = 1.0f / HISTO_LENGTH;
+    shim::RotationHistogram rotHist;
     int nmatches = 0;
     for (int i = 0; i < desc1.rows; ++i) {
         if (best[i] <= th && (float)best[i] < mfNNratio * (float)second[i]) {
             vnMatches12[i] = idx[i];
             ++nmatches;
-            if (mbCheckOrientation && i < (int)keys1.size() && idx[i] < (int)keys2.size()) {
-                float rot = keys1[i].angle - keys2[idx[i]].angle;
-                if (rot < 0.0f) rot += 360.0f;
-                int bin = (int)roundf(rot * factor);
-                if (bin == HISTO_LENGTH) bin = 0;
-                if (bin >= 0 && bin < HISTO_LENGTH) rotHist[bin].push_back(i);
-            }
+            if (mbCheckOrientation && i < (int)keys1.size() && idx[i] < (int)keys2.size()) rotHist.add(keys1[i].angle, keys2[idx[i]].angle, i);
         }
     }
-    if (mbCheckOrientation) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int b = 0; b < HISTO_LENGTH; ++b) {
-            if (b == ind1 || b == ind2 || b == ind3) continue;
-            for (size_t j = 0; j < rotHist[b].size(); ++j) {
-                if (vnMatches12[rotHist[b][j]] >= 0) { vnMatches12[rotHist[b][j]] = -1; --nmatches; }
-            }
-        }
-    }
+    if (mbCheckOrientation)
+        rotHist.reject([&](int i) {
+            if (vnMatches12[i] >= 0) { vnMatches12[i] = -1; --nmatches; }
+        });
     return nmatches;
 }
 
-// three most populated bins; the 2nd/3rd are dropped when below 10 % of the first (ORBmatcher.cc:1605-1646)
+// part of the reference's surface; the searches go through shim::RotationHistogram
 void ORBmatcher::ComputeThreeMaxima(std::vector<int>* histo, const int L, int& ind1, int& ind2, int& ind3) {
-    int top[3] = {0, 0, 0};
-    int at[3] = {-1, -1, -1};
-    for (int i = 0; i < L; ++i) {
-        const int s = (int)histo[i].size();
-        int pos = s > top[0] ? 0 : s > top[1] ? 1 : s > top[2] ? 2 : 3;
-        for (int k = 2; k > pos; --k) { top[k] = top[k - 1]; at[k] = at[k - 1]; }
-        if (pos < 3) { top[pos] = s; at[pos] = i; }
-    }
-    if (top[1] < 0.1f * (float)top[0]) { at[1] = -1; at[2] = -1; }
-    else if (top[2] < 0.1f * (float)top[0]) at[2] = -1;
-    ind1 = at[0]; ind2 = at[1]; ind3 = at[2];
+    shim::RotationHistogram::ThreeMaxima(histo, L, ind1, ind2, ind3);
 }
 
 }  // namespace ORB_SLAM2

@@ -28,6 +28,8 @@
 #include "cvlite.h"
 #endif
 
+#include "shim_common.h"
+
 namespace ORB_SLAM2 {
 
 class ORBmatcher {
@@ -165,7 +167,15 @@ public:
                              const GuidedQueries& q, int thDist, bool useRatio, float nnratio, std::vector<int>& matchKp,
                              float chi2Gate = 0.f, const std::vector<float>* invLevelSigma2 = nullptr, int mode = 0,
                              std::vector<int>* acceptedKp = nullptr);
-    static int LastStatus();
+    // The same over the searched frame or keyframe: mvKeysUn, mDescriptors, mnMinX, mnMinY and the two grid inverses are its own.
+    template <class FrameT>
+    static bool GuidedSearch(const FrameT& F, const std::vector<uint8_t>& kpTaken, const GuidedQueries& q, int thDist, bool useRatio,
+                             float nnratio, std::vector<int>& matchKp, float chi2Gate = 0.f,
+                             const std::vector<float>* invLevelSigma2 = nullptr, int mode = 0, std::vector<int>* acceptedKp = nullptr) {
+        return GuidedSearch(F.mvKeysUn, F.mDescriptors, kpTaken, F.mnMinX, F.mnMinY, F.mfGridElementWidthInv, F.mfGridElementHeightInv, q,
+                            thDist, useRatio, nnratio, matchKp, chi2Gate, invLevelSigma2, mode, acceptedKp);
+    }
+    static int LastStatus();   // of the calling thread
 
     static const int TH_LOW;
     static const int TH_HIGH;
@@ -187,7 +197,7 @@ int ORBmatcher::SearchByProjection(FrameT& F, const std::vector<MapPointT*>& vpM
     const int n = (int)F.mvKeysUn.size();
     std::vector<uint8_t> taken(n, 0);
     for (int i = 0; i < n; ++i) {
-        if (F.mvuRight[i] > 0) { setStatus(-2 /*SLAMIT_ERR_ARG*/); return 0; }
+        if (F.mvuRight[i] > 0) { setStatus(SLAMIT_ERR_ARG); return 0; }
         if (F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0) taken[i] = 1;
     }
     GuidedQueries q;
@@ -205,9 +215,7 @@ int ORBmatcher::SearchByProjection(FrameT& F, const std::vector<MapPointT*>& vpM
         who.push_back(pMP);
     }
     std::vector<int> matchKp;
-    if (!GuidedSearch(F.mvKeysUn, F.mDescriptors, taken, F.mnMinX, F.mnMinY, F.mfGridElementWidthInv, F.mfGridElementHeightInv, q,
-                      TH_HIGH, true, mfNNratio, matchKp))
-        return 0;
+    if (!GuidedSearch(F, taken, q, TH_HIGH, true, mfNNratio, matchKp)) return 0;
     int nmatches = 0;
     for (size_t k = 0; k < who.size(); ++k)
         if (matchKp[k] >= 0) { F.mvpMapPoints[matchKp[k]] = who[k]; nmatches++; }
@@ -224,20 +232,24 @@ inline float slamit_gemm_row3(const float r0, const float r1, const float r2, co
     const float t0 = r0 * X + r1 * Y + r2 * Z;
     return (float)((double)t0 + (double)t);
 }
+// x3Dc = R * x3Dw + t: the three rows
+inline void slamit_gemm_rows3(const float R[3][3], const float t[3], const float X, const float Y, const float Z, float& xc, float& yc, float& zc) {
+    xc = slamit_gemm_row3(R[0][0], R[0][1], R[0][2], X, Y, Z, t[0]);
+    yc = slamit_gemm_row3(R[1][0], R[1][1], R[1][2], X, Y, Z, t[1]);
+    zc = slamit_gemm_row3(R[2][0], R[2][1], R[2][2], X, Y, Z, t[2]);
+}
 
 template <class FrameT>
 int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame, const float th, const bool bMono) {
     const int n = (int)CurrentFrame.mvKeysUn.size();
     std::vector<uint8_t> taken(n, 0);
     for (int i = 0; i < n; ++i) {
-        if (CurrentFrame.mvuRight[i] > 0) { setStatus(-2 /*SLAMIT_ERR_ARG*/); return 0; }
+        if (CurrentFrame.mvuRight[i] > 0) { setStatus(SLAMIT_ERR_ARG); return 0; }
         if (CurrentFrame.mvpMapPoints[i] && CurrentFrame.mvpMapPoints[i]->Observations() > 0) taken[i] = 1;
     }
     float Rcw[3][3], tcw[3], Rlw[3][3], tlw[3];
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) { Rcw[r][c] = CurrentFrame.mTcw.template at<float>(r, c); Rlw[r][c] = LastFrame.mTcw.template at<float>(r, c); }
-        tcw[r] = CurrentFrame.mTcw.template at<float>(r, 3); tlw[r] = LastFrame.mTcw.template at<float>(r, 3);
-    }
+    shim::load3x3(CurrentFrame.mTcw, &Rcw[0][0]); shim::load3(CurrentFrame.mTcw, tcw, 3);
+    shim::load3x3(LastFrame.mTcw, &Rlw[0][0]); shim::load3(LastFrame.mTcw, tlw, 3);
     float twc[3];
     // -Rcw.t() * tcw: cv::gemm's generic path (GEMM_1_T) sums in double and rounds once
     for (int r = 0; r < 3; ++r) twc[r] = (float)((double)-Rcw[0][r] * tcw[0] + (double)-Rcw[1][r] * tcw[1] + (double)-Rcw[2][r] * tcw[2]);
@@ -252,9 +264,8 @@ int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame
         if (!pMP || LastFrame.mvbOutlier[i]) continue;
         const cv::Mat x3Dw = pMP->GetWorldPos();
         const float X = x3Dw.template at<float>(0, 0), Y = x3Dw.template at<float>(1, 0), Z = x3Dw.template at<float>(2, 0);
-        const float xc = slamit_gemm_row3(Rcw[0][0], Rcw[0][1], Rcw[0][2], X, Y, Z, tcw[0]);
-        const float yc = slamit_gemm_row3(Rcw[1][0], Rcw[1][1], Rcw[1][2], X, Y, Z, tcw[1]);
-        const float zc = slamit_gemm_row3(Rcw[2][0], Rcw[2][1], Rcw[2][2], X, Y, Z, tcw[2]);
+        float xc, yc, zc;
+        slamit_gemm_rows3(Rcw, tcw, X, Y, Z, xc, yc, zc);
         const float invzc = 1.0 / zc;
         if (invzc < 0) continue;
         const float u = CurrentFrame.fx * xc * invzc + CurrentFrame.cx;
@@ -271,35 +282,17 @@ int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame
         who.push_back(i);
     }
     std::vector<int> matchKp;
-    if (!GuidedSearch(CurrentFrame.mvKeysUn, CurrentFrame.mDescriptors, taken, CurrentFrame.mnMinX, CurrentFrame.mnMinY,
-                      CurrentFrame.mfGridElementWidthInv, CurrentFrame.mfGridElementHeightInv, q, TH_HIGH, false, mfNNratio, matchKp))
-        return 0;
+    if (!GuidedSearch(CurrentFrame, taken, q, TH_HIGH, false, mfNNratio, matchKp)) return 0;
     int nmatches = 0;
-    std::vector<int> rotHist[30];
-    const float factor = 1.0f / HISTO_LENGTH;
+    shim::RotationHistogram rotHist;
     for (size_t k = 0; k < who.size(); ++k) {
         const int bestIdx2 = matchKp[k];
         if (bestIdx2 < 0) continue;
         CurrentFrame.mvpMapPoints[bestIdx2] = LastFrame.mvpMapPoints[who[k]];
         nmatches++;
-        if (mbCheckOrientation) {
-            float rot = LastFrame.mvKeysUn[who[k]].angle - CurrentFrame.mvKeysUn[bestIdx2].angle;
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == HISTO_LENGTH) bin = 0;
-            if (bin >= 0 && bin < HISTO_LENGTH) rotHist[bin].push_back(bestIdx2);
-        }
+        if (mbCheckOrientation) rotHist.add(LastFrame.mvKeysUn[who[k]].angle, CurrentFrame.mvKeysUn[bestIdx2].angle, bestIdx2);
     }
-    if (mbCheckOrientation) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++)
-            if (i != ind1 && i != ind2 && i != ind3)
-                for (size_t j = 0, jend = rotHist[i].size(); j < jend; j++) {
-                    CurrentFrame.mvpMapPoints[rotHist[i][j]] = nullptr;
-                    nmatches--;
-                }
-    }
+    if (mbCheckOrientation) rotHist.reject([&](int idx2) { CurrentFrame.mvpMapPoints[idx2] = nullptr; nmatches--; });
     return nmatches;
 }
 
@@ -309,10 +302,7 @@ int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, KeyFrameT* pKF, const S
     std::vector<uint8_t> taken(n, 0);
     for (int i = 0; i < n; ++i) taken[i] = CurrentFrame.mvpMapPoints[i] ? 1 : 0;   // :1543: any map point blocks the keypoint
     float Rcw[3][3], tcw[3], Ow[3];
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) Rcw[r][c] = CurrentFrame.mTcw.template at<float>(r, c);
-        tcw[r] = CurrentFrame.mTcw.template at<float>(r, 3);
-    }
+    shim::load3x3(CurrentFrame.mTcw, &Rcw[0][0]); shim::load3(CurrentFrame.mTcw, tcw, 3);
     for (int r = 0; r < 3; ++r) Ow[r] = (float)((double)-Rcw[0][r] * tcw[0] + (double)-Rcw[1][r] * tcw[1] + (double)-Rcw[2][r] * tcw[2]);
     const auto vpMPs = pKF->GetMapPointMatches();
     GuidedQueries q;
@@ -323,9 +313,8 @@ int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, KeyFrameT* pKF, const S
         if (pMP->isBad() || sAlreadyFound.count(pMP)) continue;
         const cv::Mat x3Dw = pMP->GetWorldPos();
         const float X = x3Dw.template at<float>(0, 0), Y = x3Dw.template at<float>(1, 0), Z = x3Dw.template at<float>(2, 0);
-        const float xc = slamit_gemm_row3(Rcw[0][0], Rcw[0][1], Rcw[0][2], X, Y, Z, tcw[0]);
-        const float yc = slamit_gemm_row3(Rcw[1][0], Rcw[1][1], Rcw[1][2], X, Y, Z, tcw[1]);
-        const float zc = slamit_gemm_row3(Rcw[2][0], Rcw[2][1], Rcw[2][2], X, Y, Z, tcw[2]);
+        float xc, yc, zc;
+        slamit_gemm_rows3(Rcw, tcw, X, Y, Z, xc, yc, zc);
         const float invzc = 1.0 / zc;
         const float u = CurrentFrame.fx * xc * invzc + CurrentFrame.cx;
         const float v = CurrentFrame.fy * yc * invzc + CurrentFrame.cy;
@@ -341,35 +330,17 @@ int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, KeyFrameT* pKF, const S
         who.push_back((int)i);
     }
     std::vector<int> matchKp;
-    if (!GuidedSearch(CurrentFrame.mvKeysUn, CurrentFrame.mDescriptors, taken, CurrentFrame.mnMinX, CurrentFrame.mnMinY,
-                      CurrentFrame.mfGridElementWidthInv, CurrentFrame.mfGridElementHeightInv, q, ORBdist, false, mfNNratio, matchKp))
-        return 0;
+    if (!GuidedSearch(CurrentFrame, taken, q, ORBdist, false, mfNNratio, matchKp)) return 0;
     int nmatches = 0;
-    std::vector<int> rotHist[30];
-    const float factor = 1.0f / HISTO_LENGTH;
+    shim::RotationHistogram rotHist;
     for (size_t k = 0; k < who.size(); ++k) {
         const int bestIdx2 = matchKp[k];
         if (bestIdx2 < 0) continue;
         CurrentFrame.mvpMapPoints[bestIdx2] = vpMPs[who[k]];
         nmatches++;
-        if (mbCheckOrientation) {
-            float rot = pKF->mvKeysUn[who[k]].angle - CurrentFrame.mvKeysUn[bestIdx2].angle;
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == HISTO_LENGTH) bin = 0;
-            if (bin >= 0 && bin < HISTO_LENGTH) rotHist[bin].push_back(bestIdx2);
-        }
+        if (mbCheckOrientation) rotHist.add(pKF->mvKeysUn[who[k]].angle, CurrentFrame.mvKeysUn[bestIdx2].angle, bestIdx2);
     }
-    if (mbCheckOrientation) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++)
-            if (i != ind1 && i != ind2 && i != ind3)
-                for (size_t j = 0, jend = rotHist[i].size(); j < jend; j++) {
-                    CurrentFrame.mvpMapPoints[rotHist[i][j]] = nullptr;
-                    nmatches--;
-                }
-    }
+    if (mbCheckOrientation) rotHist.reject([&](int idx2) { CurrentFrame.mvpMapPoints[idx2] = nullptr; nmatches--; });
     return nmatches;
 }
 
@@ -401,32 +372,15 @@ int ORBmatcher::SearchByBoW(KeyFrameT* pKF, FrameT& F, std::vector<MapPointT*>& 
     std::vector<int> match12;
     if (!BowSearch(pKF->mDescriptors, valid1, F.mDescriptors, NULL, g, TH_LOW, true, mfNNratio, NULL, match12)) return 0;
     int nmatches = 0;
-    std::vector<int> rotHist[30];
-    const float factor = 1.0f / HISTO_LENGTH;
+    shim::RotationHistogram rotHist;
     for (int i = 0; i < n1; ++i) {
         const int bestIdxF = match12[i];
         if (bestIdxF < 0) continue;
         vpMapPointMatches[bestIdxF] = vpMapPointsKF[i];
-        if (mbCheckOrientation) {
-            float rot = pKF->mvKeysUn[i].angle - F.mvKeys[bestIdxF].angle;
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == HISTO_LENGTH) bin = 0;
-            if (bin >= 0 && bin < HISTO_LENGTH) rotHist[bin].push_back(bestIdxF);
-        }
+        if (mbCheckOrientation) rotHist.add(pKF->mvKeysUn[i].angle, F.mvKeys[bestIdxF].angle, bestIdxF);
         nmatches++;
     }
-    if (mbCheckOrientation) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i == ind1 || i == ind2 || i == ind3) continue;
-            for (size_t j = 0, jend = rotHist[i].size(); j < jend; j++) {
-                vpMapPointMatches[rotHist[i][j]] = static_cast<MapPointT*>(NULL);
-                nmatches--;
-            }
-        }
-    }
+    if (mbCheckOrientation) rotHist.reject([&](int idxF) { vpMapPointMatches[idxF] = static_cast<MapPointT*>(NULL); nmatches--; });
     return nmatches;
 }
 
@@ -443,32 +397,15 @@ int ORBmatcher::SearchByBoW(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPoi
     std::vector<int> match12;
     if (!BowSearch(pKF1->mDescriptors, valid1, pKF2->mDescriptors, &valid2, g, TH_LOW, false, mfNNratio, NULL, match12)) return 0;
     int nmatches = 0;
-    std::vector<int> rotHist[30];
-    const float factor = 1.0f / HISTO_LENGTH;
+    shim::RotationHistogram rotHist;
     for (int idx1 = 0; idx1 < n1; ++idx1) {
         const int bestIdx2 = match12[idx1];
         if (bestIdx2 < 0) continue;
         vpMatches12[idx1] = vpMapPoints2[bestIdx2];
-        if (mbCheckOrientation) {
-            float rot = pKF1->mvKeysUn[idx1].angle - pKF2->mvKeysUn[bestIdx2].angle;
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == HISTO_LENGTH) bin = 0;
-            if (bin >= 0 && bin < HISTO_LENGTH) rotHist[bin].push_back(idx1);
-        }
+        if (mbCheckOrientation) rotHist.add(pKF1->mvKeysUn[idx1].angle, pKF2->mvKeysUn[bestIdx2].angle, idx1);
         nmatches++;
     }
-    if (mbCheckOrientation) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i == ind1 || i == ind2 || i == ind3) continue;
-            for (size_t j = 0, jend = rotHist[i].size(); j < jend; j++) {
-                vpMatches12[rotHist[i][j]] = static_cast<MapPointT*>(NULL);
-                nmatches--;
-            }
-        }
-    }
+    if (mbCheckOrientation) rotHist.reject([&](int idx1) { vpMatches12[idx1] = static_cast<MapPointT*>(NULL); nmatches--; });
     return nmatches;
 }
 
@@ -480,7 +417,7 @@ int ORBmatcher::SearchForTriangulation(KeyFrameT* pKF1, KeyFrameT* pKF2, cv::Mat
     bool stereo = bOnlyStereo;
     for (int i = 0; i < n1 && !stereo; ++i) stereo = pKF1->mvuRight[i] >= 0;
     for (int i = 0; i < n2 && !stereo; ++i) stereo = pKF2->mvuRight[i] >= 0;
-    if (stereo) { setStatus(-1); return 0; }   // monocular path only (the reference application is MONOCULAR)
+    if (stereo) { setStatus(SLAMIT_ERR_ARG); return 0; }   // monocular path only (the reference application is MONOCULAR)
     // epipole of camera 1 in image 2 (:665-673)
     const cv::Mat Cw = pKF1->GetCameraCenter(), R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
     float C2[3];
@@ -503,31 +440,14 @@ int ORBmatcher::SearchForTriangulation(KeyFrameT* pKF1, KeyFrameT* pKF2, cv::Mat
     std::vector<int> vMatches12;
     if (!BowSearch(pKF1->mDescriptors, valid1, pKF2->mDescriptors, &valid2, g, TH_LOW, true, 0.f, &gate, vMatches12)) return 0;
     int nmatches = 0;
-    std::vector<int> rotHist[30];
-    const float factor = 1.0f / HISTO_LENGTH;
+    shim::RotationHistogram rotHist;
     for (int idx1 = 0; idx1 < n1; ++idx1) {
         const int bestIdx2 = vMatches12[idx1];
         if (bestIdx2 < 0) continue;
         nmatches++;
-        if (mbCheckOrientation) {
-            float rot = pKF1->mvKeysUn[idx1].angle - pKF2->mvKeysUn[bestIdx2].angle;
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == HISTO_LENGTH) bin = 0;
-            if (bin >= 0 && bin < HISTO_LENGTH) rotHist[bin].push_back(idx1);
-        }
+        if (mbCheckOrientation) rotHist.add(pKF1->mvKeysUn[idx1].angle, pKF2->mvKeysUn[bestIdx2].angle, idx1);
     }
-    if (mbCheckOrientation) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i == ind1 || i == ind2 || i == ind3) continue;
-            for (size_t j = 0, jend = rotHist[i].size(); j < jend; j++) {
-                vMatches12[rotHist[i][j]] = -1;
-                nmatches--;
-            }
-        }
-    }
+    if (mbCheckOrientation) rotHist.reject([&](int idx1) { vMatches12[idx1] = -1; nmatches--; });
     vMatchedPairs.reserve(nmatches);
     for (size_t i = 0, iend = vMatches12.size(); i < iend; i++) {
         if (vMatches12[i] < 0) continue;
@@ -597,9 +517,7 @@ int ORBmatcher::SearchByProjection(KeyFrameT* pKF, cv::Mat Scw, const std::vecto
     std::vector<uint8_t> taken((size_t)n, 0);
     for (int i = 0; i < n && i < (int)vpMatched.size(); ++i) taken[i] = vpMatched[i] ? 1 : 0;
     std::vector<int> matchKp;
-    if (!GuidedSearch(pKF->mvKeysUn, pKF->mDescriptors, taken, pKF->mnMinX, pKF->mnMinY, pKF->mfGridElementWidthInv,
-                      pKF->mfGridElementHeightInv, q, TH_LOW, false, mfNNratio, matchKp))
-        return 0;
+    if (!GuidedSearch(*pKF, taken, q, TH_LOW, false, mfNNratio, matchKp)) return 0;
     int nmatches = 0;
     for (size_t k = 0; k < who.size(); ++k)
         if (matchKp[k] >= 0) { vpMatched[matchKp[k]] = who[k]; nmatches++; }
@@ -642,9 +560,7 @@ int ORBmatcher::Fuse(KeyFrameT* pKF, cv::Mat Scw, const std::vector<MapPointT*>&
     }
     std::vector<int> matchKp;
     const std::vector<uint8_t> none((size_t)n, 0);
-    if (!GuidedSearch(pKF->mvKeysUn, pKF->mDescriptors, none, pKF->mnMinX, pKF->mnMinY, pKF->mfGridElementWidthInv,
-                      pKF->mfGridElementHeightInv, q, TH_LOW, false, mfNNratio, matchKp))
-        return 0;
+    if (!GuidedSearch(*pKF, none, q, TH_LOW, false, mfNNratio, matchKp)) return 0;
     int nFused = 0;
     for (size_t k = 0; k < who.size(); ++k) {   // the bookkeeping of :1074-1091, in map-point order
         const int bestIdx = matchKp[k];
@@ -725,9 +641,7 @@ int ORBmatcher::SearchBySim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPo
             }
             std::vector<int> matchKp;
             const std::vector<uint8_t> none(to->mvKeysUn.size(), 0);
-            if (!GuidedSearch(to->mvKeysUn, to->mDescriptors, none, to->mnMinX, to->mnMinY, to->mfGridElementWidthInv, to->mfGridElementHeightInv, q,
-                              TH_HIGH, false, self->mfNNratio, matchKp))
-                return false;
+            if (!GuidedSearch(*to, none, q, TH_HIGH, false, self->mfNNratio, matchKp)) return false;
             for (size_t k = 0; k < who.size(); ++k) vnMatch[who[k]] = matchKp[k];
             return true;
         }
@@ -758,33 +672,18 @@ int ORBmatcher::SearchForInitialization(FrameT& F1, FrameT& F2, std::vector<cv::
     }
     std::vector<int> matchKp, acceptedKp;
     const std::vector<uint8_t> none((size_t)n2, 0);
-    if (!GuidedSearch(F2.mvKeysUn, F2.mDescriptors, none, F2.mnMinX, F2.mnMinY, F2.mfGridElementWidthInv, F2.mfGridElementHeightInv, q,
-                      TH_LOW, false, mfNNratio, matchKp, 0.f, nullptr, 1, &acceptedKp))
-        return 0;
+    if (!GuidedSearch(F2, none, q, TH_LOW, false, mfNNratio, matchKp, 0.f, nullptr, 1, &acceptedKp)) return 0;
     int nmatches = 0;
     for (int i1 = 0; i1 < n1; ++i1) { vnMatches12[i1] = matchKp[i1]; nmatches += matchKp[i1] >= 0; }
     if (mbCheckOrientation) {
         // the reference bins a match when it is made (:467-477) -- also the ones a later query takes over, which stay in
         // their bin (and count for the three maxima) but are skipped by the vnMatches12[idx1] >= 0 test below
-        std::vector<int> rotHist[30];
-        const float factor = 1.0f / HISTO_LENGTH;
-        for (int i1 = 0; i1 < n1; ++i1) {
-            if (acceptedKp[i1] < 0) continue;
-            float rot = F1.mvKeysUn[i1].angle - F2.mvKeysUn[acceptedKp[i1]].angle;
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == HISTO_LENGTH) bin = 0;
-            if (bin >= 0 && bin < HISTO_LENGTH) rotHist[bin].push_back(i1);
-        }
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        ComputeThreeMaxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i == ind1 || i == ind2 || i == ind3) continue;
-            for (size_t j = 0, jend = rotHist[i].size(); j < jend; j++) {
-                const int idx1 = rotHist[i][j];
-                if (vnMatches12[idx1] >= 0) { vnMatches12[idx1] = -1; nmatches--; }
-            }
-        }
+        shim::RotationHistogram rotHist;
+        for (int i1 = 0; i1 < n1; ++i1)
+            if (acceptedKp[i1] >= 0) rotHist.add(F1.mvKeysUn[i1].angle, F2.mvKeysUn[acceptedKp[i1]].angle, i1);
+        rotHist.reject([&](int idx1) {
+            if (vnMatches12[idx1] >= 0) { vnMatches12[idx1] = -1; nmatches--; }
+        });
     }
     for (int i1 = 0; i1 < n1; ++i1)   // update prev matched
         if (vnMatches12[i1] >= 0) vbPrevMatched[i1] = F2.mvKeysUn[vnMatches12[i1]].pt;
@@ -795,14 +694,11 @@ template <class KeyFrameT, class MapPointT>
 int ORBmatcher::Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const float th) {
     const cv::Mat Rcw = pKF->GetRotation(), tcw = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
     float R[3][3], t[3], O[3];
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) R[r][c] = Rcw.template at<float>(r, c);
-        t[r] = tcw.template at<float>(r, 0); O[r] = Ow.template at<float>(r, 0);
-    }
+    shim::load3x3(Rcw, &R[0][0]); shim::load3(tcw, t); shim::load3(Ow, O);
     const float fx = pKF->fx, fy = pKF->fy, cx = pKF->cx, cy = pKF->cy;
     const int n = (int)pKF->mvKeysUn.size();
     for (int i = 0; i < n; ++i)
-        if (pKF->mvuRight[i] >= 0) { setStatus(-2 /*SLAMIT_ERR_ARG*/); return 0; }   // stereo keypoints: not on this path
+        if (pKF->mvuRight[i] >= 0) { setStatus(SLAMIT_ERR_ARG); return 0; }   // stereo keypoints: not on this path
     GuidedQueries q;
     std::vector<MapPointT*> who;
     for (size_t i = 0; i < vpMapPoints.size(); i++) {
@@ -811,9 +707,8 @@ int ORBmatcher::Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints,
         if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
         const cv::Mat p3Dw = pMP->GetWorldPos();
         const float X = p3Dw.template at<float>(0, 0), Y = p3Dw.template at<float>(1, 0), Z = p3Dw.template at<float>(2, 0);
-        const float xc = slamit_gemm_row3(R[0][0], R[0][1], R[0][2], X, Y, Z, t[0]);
-        const float yc = slamit_gemm_row3(R[1][0], R[1][1], R[1][2], X, Y, Z, t[1]);
-        const float zc = slamit_gemm_row3(R[2][0], R[2][1], R[2][2], X, Y, Z, t[2]);
+        float xc, yc, zc;
+        slamit_gemm_rows3(R, t, X, Y, Z, xc, yc, zc);
         if (zc < 0.0f) continue;   // depth must be positive
         const float invz = 1 / zc;
         const float x = xc * invz, y = yc * invz;
@@ -833,9 +728,7 @@ int ORBmatcher::Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints,
     }
     std::vector<int> matchKp;
     const std::vector<uint8_t> none((size_t)n, 0);
-    if (!GuidedSearch(pKF->mvKeysUn, pKF->mDescriptors, none, pKF->mnMinX, pKF->mnMinY, pKF->mfGridElementWidthInv,
-                      pKF->mfGridElementHeightInv, q, TH_LOW, false, mfNNratio, matchKp, 5.99f, &pKF->mvInvLevelSigma2))
-        return 0;
+    if (!GuidedSearch(*pKF, none, q, TH_LOW, false, mfNNratio, matchKp, 5.99f, &pKF->mvInvLevelSigma2)) return 0;
     int nFused = 0;
     for (size_t k = 0; k < who.size(); ++k) {
         const int bestIdx = matchKp[k];

@@ -37,7 +37,7 @@
 #include "cvlite.h"
 #endif
 
-#include "../../include/slamit.h"
+#include "shim_common.h"
 
 namespace ORB_SLAM2 {
 
@@ -85,7 +85,7 @@ public:
     static void SetDevice(int device) { deviceRef() = device; }
 
 private:
-    static int& lastStatus() { static thread_local int s = 0; return s; }   // per calling thread: Tracking, LocalMapping and LoopClosing run concurrently
+    static int& lastStatus() { return shim::status<Optimizer>(); }   // per calling thread: Tracking, LocalMapping and LoopClosing run concurrently
     static int& deviceRef() { static int d = 0; return d; }
     static slamit_ba*& handleRef() { static slamit_ba* h = 0; return h; }
     static int* capRef() { static int c[4] = {0, 0, 0, 0}; return c; }   // max_kf, max_pt, max_edge, max_free_kf of the handle

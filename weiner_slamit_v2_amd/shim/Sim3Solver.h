@@ -28,7 +28,7 @@
 #include "cvlite.h"
 #endif
 
-#include "../../include/slamit.h"
+#include "shim_common.h"
 
 namespace ORB_SLAM2 {
 
@@ -222,7 +222,7 @@ public:
     int GetRansacMaxIts() const { return mRansacMaxIts; }
 
 private:
-    static int& lastStatus() { static int s = 0; return s; }
+    static int& lastStatus() { return shim::status<Sim3Solver>(); }
     static void Push(std::vector<float>& v, const cv::Mat& R, const cv::Mat& t, const cv::Mat& X) {
         const float x = X.at<float>(0, 0), y = X.at<float>(1, 0), z = X.at<float>(2, 0);
         for (int r = 0; r < 3; ++r) v.push_back(sim3solver::GemmRow3(R.at<float>(r, 0), R.at<float>(r, 1), R.at<float>(r, 2), x, y, z, t.at<float>(r, 0)));

@@ -25,8 +25,8 @@
 
 #include <vector>
 
-#include "../../include/slamit.h"
 #include "ORBmatcher.h"
+#include "shim_common.h"
 
 namespace ORB_SLAM2 {
 
@@ -52,14 +52,10 @@ public:
         }
         const int n = (int)local.size();
         if (n == 0) return 0;
-        if (F.mvScaleFactors.size() < 1 || F.mvScaleFactors.size() > SLAMIT_MAX_LEVELS) return refuse("SearchLocalPoints: mvScaleFactors outside [1, SLAMIT_MAX_LEVELS] levels");
+        if (F.mvScaleFactors.size() < 1 || F.mvScaleFactors.size() > SLAMIT_MAX_LEVELS) return shim::refuse<Tracking>("SearchLocalPoints: mvScaleFactors outside [1, SLAMIT_MAX_LEVELS] levels");
         // Project points in frame and check its visibility (:1433-1447): every point in one call
         slamit_frustum_problem P;
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) P.frame.Rcw[3 * r + c] = F.mRcw.template at<float>(r, c);
-            P.frame.tcw[r] = F.mtcw.template at<float>(r, 0);
-            P.frame.Ow[r] = F.mOw.template at<float>(r, 0);
-        }
+        shim::load3x3(F.mRcw, P.frame.Rcw); shim::load3(F.mtcw, P.frame.tcw); shim::load3(F.mOw, P.frame.Ow);
         P.frame.fx = F.fx; P.frame.fy = F.fy; P.frame.cx = F.cx; P.frame.cy = F.cy; P.frame.bf = F.mbf;
         P.frame.min_x = F.mnMinX; P.frame.max_x = F.mnMaxX; P.frame.min_y = F.mnMinY; P.frame.max_y = F.mnMaxY;
         P.frame.view_cos_limit = 0.5f;
@@ -73,7 +69,7 @@ public:
             MapPointT* pMP = local[i];
             if (pMP->mnLastFrameSeen == F.mnId || pMP->isBad()) { skip[i] = 1; continue; }
             const cv::Mat Pw = pMP->GetWorldPos(), Pn = pMP->GetNormal();
-            for (int r = 0; r < 3; ++r) { pos[3 * (size_t)i + r] = Pw.template at<float>(r, 0); nrm[3 * (size_t)i + r] = Pn.template at<float>(r, 0); }
+            shim::load3(Pw, &pos[3 * (size_t)i]); shim::load3(Pn, &nrm[3 * (size_t)i]);
             maxd[i] = pMP->GetMaxDistance(); mind[i] = pMP->GetMinDistance();
         }
         P.n = n; P.pos = pos.data(); P.normal = nrm.data(); P.max_dist = maxd.data(); P.min_dist = mind.data(); P.skip = skip.data();
@@ -84,11 +80,7 @@ public:
         R.status = st.data(); R.proj = proj.data(); R.view_cos = vc.data(); R.level = level.data(); R.uvr = uvr.data();
         R.level_min = l0.data(); R.level_max = l1.data(); R.valid = valid.data(); R.n_in_view = 0;
         const int rc = slamit_frustum(device, &P, &R);
-        if (rc != SLAMIT_OK) {
-            status() = rc;
-            fprintf(stderr, "SearchLocalPoints: slamit_frustum failed (%d): %s\n", rc, slamit_last_error());
-            return 0;
-        }
+        if (rc != SLAMIT_OK) return shim::report<Tracking>("SearchLocalPoints: slamit_frustum", rc);
         int nToMatch = 0;
         for (int i = 0; i < n; ++i) {
             if (skip[i]) continue;                       // :1436-1440: the reference does not touch these
@@ -102,15 +94,11 @@ public:
             nToMatch++;
         }
         inView() = nToMatch;
-        if (nToMatch != R.n_in_view) return refuse("SearchLocalPoints: the device's count of points in view disagrees with its statuses");
+        if (nToMatch != R.n_in_view) return shim::refuse<Tracking>("SearchLocalPoints: the device's count of points in view disagrees with its statuses");
         if (nToMatch == 0) return 0;
         ORBmatcher matcher(nnratio);
         const int nmatches = matcher.SearchByProjection(F, local, (float)th);
-        if (ORBmatcher::LastStatus() != SLAMIT_OK) {
-            status() = ORBmatcher::LastStatus();
-            fprintf(stderr, "SearchLocalPoints: SearchByProjection failed (%d): %s\n", status(), slamit_last_error());
-            return 0;
-        }
+        if (ORBmatcher::LastStatus() != SLAMIT_OK) return shim::report<Tracking>("SearchLocalPoints: SearchByProjection", ORBmatcher::LastStatus());
         return nmatches;
     }
 
@@ -118,13 +106,8 @@ public:
     static int LastInView() { return inView(); }
 
 private:
-    static int& status() { static thread_local int s = SLAMIT_OK; return s; }
+    static int& status() { return shim::status<Tracking>(); }
     static int& inView() { static thread_local int s = 0; return s; }
-    static int refuse(const char* why) {
-        status() = SLAMIT_ERR_ARG;
-        fprintf(stderr, "%s\n", why);
-        return 0;
-    }
 };
 
 }  // namespace ORB_SLAM2
