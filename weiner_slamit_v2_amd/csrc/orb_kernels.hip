@@ -160,6 +160,50 @@ __global__ __launch_bounds__(256) void resize_rows4_kernel(
 // register pairs (orb_plan.cc: rows8_table checks it and refuses other geometries, which keep the four-pixel kernel).
 // Column group (5 x uint4): byte offset of the window | shift << 16 ; 8 x v_perm selector ; 8 x (ialpha0 | ialpha1 << 16).
 typedef unsigned rs_u4 __attribute__((ext_vector_type(4)));
+// the horizontal pass of one source row's 16-byte window: h[column] = (left * ialpha0 + right * ialpha1) >> 4
+__device__ __forceinline__ void rs_hpass8(const uint32_t* ww, const unsigned sh, const uint32_t* sel, const uint32_t* al, uint32_t* h) {
+    const uint32_t a0 = __builtin_amdgcn_alignbyte(ww[1], ww[0], sh), a1 = __builtin_amdgcn_alignbyte(ww[2], ww[1], sh), a2 = __builtin_amdgcn_alignbyte(ww[3], ww[2], sh);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) h[j] = rs_dot2(__builtin_amdgcn_perm(a1, a0, sel[j]), al[j]) >> 4;
+#pragma unroll
+    for (int j = 4; j < 8; ++j) h[j] = rs_dot2(__builtin_amdgcn_perm(a2, a1, sel[j]), al[j]) >> 4;
+}
+// The rows of one item, ONE horizontal pass per distinct source row.  Consecutive dst rows share a source row whenever the second source
+// row of dst row k - 1 is the first of dst row k (five times in six at scale 1.2; the row table says so, bottom rows clamp and a
+// clamped repeat row names the same pair twice): that pass's eight values are dead after row k - 1's vertical pass and are taken
+// over in place.  Otherwise the first row is loaded and passed under the lane's own mask -- a wave whose lanes all share skips the
+// block.  The second source row of every dst row is always loaded and passed; every load is issued before the first pass.
+// load(source row, window of four dwords); store(k, dwords of pixels 0 .. 3, of pixels 4 .. 7).
+template <int NR, typename Load, typename Store>
+__device__ __forceinline__ void rs_rows8(const uint2* rt, const unsigned sh, const uint32_t* sel, const uint32_t* al, Load load, Store store) {
+    bool fresh[NR];
+    uint32_t w0[NR][4], w1[NR][4];
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        fresh[k] = k == 0 || (rt[k].x & 0xFFFFu) != (rt[k - 1].x >> 16);
+        if (fresh[k]) load(rt[k].x & 0xFFFFu, w0[k]);
+        load(rt[k].x >> 16, w1[k]);
+    }
+    uint32_t h0[8], h1[8];   // the passes of the dst row's first and second source row
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        if (k) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) h0[j] = h1[j];
+        }
+        if (fresh[k]) rs_hpass8(w0[k], sh, sel, al, h0);
+        rs_hpass8(w1[k], sh, sel, al, h1);
+        const unsigned b0 = rt[k].y & 0xFFFFu, b1 = rt[k].y >> 16;
+        uint32_t out[2] = {0, 0};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {   // (b * (h >> 4)) >> 16 with b <= 2048, h >> 4 <= 32640: 24-bit multiplies
+            const uint32_t v = ((__umul24(b0, h0[j]) >> 16) + (__umul24(b1, h1[j]) >> 16) + 2u) >> 2;
+            out[j >> 2] |= (v & 0xFFu) << (8 * (j & 3));
+        }
+        store(k, out[0], out[1]);
+    }
+}
+
 template <int RP>
 __device__ __forceinline__ void rs_item8(const int item, const uint8_t* S, const unsigned ss, const unsigned sbytes, uint8_t* D, const unsigned dstride,
                                          const uint4* __restrict__ coltab, const uint2* __restrict__ rowtab, const int ngroups,
@@ -184,36 +228,15 @@ __device__ __forceinline__ void rs_item8(const int item, const uint8_t* S, const
     }
     const unsigned b = c0.x & 0xFFFFu, sh = (c0.x >> 16) & 3u;
     const uint32_t sel[8] = {c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x}, al[8] = {c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w, c4x};
-    uint32_t w[4 * RP][4];
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(S), 0, sbytes, 0x00020000);
-#pragma unroll
-    for (int r = 0; r < 4 * RP; ++r) {
-        const unsigned srow = (r & 1) ? (rt[r >> 1].x >> 16) : (rt[r >> 1].x & 0xFFFFu);
-        const unsigned ro = __umul24(srow, ss) + b;
-        const rs_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)ro, 0, 0);
-        w[r][0] = v.x; w[r][1] = v.y; w[r][2] = v.z; w[r][3] = v.w;
-    }
-#pragma unroll
-    for (int k = 0; k < 2 * RP; ++k) {
-        uint32_t h[2][8];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const uint32_t* ww = w[2 * k + r];
-            const uint32_t a0 = __builtin_amdgcn_alignbyte(ww[1], ww[0], sh), a1 = __builtin_amdgcn_alignbyte(ww[2], ww[1], sh), a2 = __builtin_amdgcn_alignbyte(ww[3], ww[2], sh);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) h[r][j] = rs_dot2(__builtin_amdgcn_perm(a1, a0, sel[j]), al[j]) >> 4;
-#pragma unroll
-            for (int j = 4; j < 8; ++j) h[r][j] = rs_dot2(__builtin_amdgcn_perm(a2, a1, sel[j]), al[j]) >> 4;
-        }
-        const unsigned b0 = rt[k].y & 0xFFFFu, b1 = rt[k].y >> 16;
-        uint32_t out[2] = {0, 0};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint32_t v = ((__umul24(b0, h[0][j]) >> 16) + (__umul24(b1, h[1][j]) >> 16) + 2u) >> 2;
-            out[j >> 2] |= (v & 0xFFu) << (8 * (j & 3));
-        }
-        *reinterpret_cast<uint2*>(D + (__umul24((unsigned)yrow[k], dstride) + 8u * (unsigned)g)) = make_uint2(out[0], out[1]);
-    }
+    rs_rows8<2 * RP>(rt, sh, sel, al,
+        [&](const unsigned srow, uint32_t* w) {
+            const rs_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(__umul24(srow, ss) + b), 0, 0);
+            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        },
+        [&](const int k, const uint32_t o0, const uint32_t o1) {
+            *reinterpret_cast<uint2*>(D + (__umul24((unsigned)yrow[k], dstride) + 8u * (unsigned)g)) = make_uint2(o0, o1);
+        });
 }
 
 template <int RP>
@@ -274,41 +297,21 @@ __device__ __forceinline__ void band_item(const int item, const BandLevel& V, co
     }
     const unsigned b = c0.x & 0xFFFFu, sh = (c0.x >> 16) & 3u;
     const uint32_t sel[8] = {c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x}, al[8] = {c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w, c4x};
-    uint32_t w[8][4];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const unsigned srow = (r & 1) ? (rt[r >> 1].x >> 16) : (rt[r >> 1].x & 0xFFFFu);
-        if (FROM_LDS) {   // the plan keeps every source row of a computed row inside the band's rows of the level below
-            const uint32_t* p = reinterpret_cast<const uint32_t*>(stile + (__umul24(srow - (unsigned)srow0, spitch) + b));
-            w[r][0] = p[0]; w[r][1] = p[1]; w[r][2] = p[2]; w[r][3] = p[3];
-        } else {
-            const rs_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(__umul24(srow, ss) + b), 0, 0);
-            w[r][0] = v.x; w[r][1] = v.y; w[r][2] = v.z; w[r][3] = v.w;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        uint32_t h[2][8];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const uint32_t* ww = w[2 * k + r];
-            const uint32_t a0 = __builtin_amdgcn_alignbyte(ww[1], ww[0], sh), a1 = __builtin_amdgcn_alignbyte(ww[2], ww[1], sh), a2 = __builtin_amdgcn_alignbyte(ww[3], ww[2], sh);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) h[r][j] = rs_dot2(__builtin_amdgcn_perm(a1, a0, sel[j]), al[j]) >> 4;
-#pragma unroll
-            for (int j = 4; j < 8; ++j) h[r][j] = rs_dot2(__builtin_amdgcn_perm(a2, a1, sel[j]), al[j]) >> 4;
-        }
-        const unsigned b0 = rt[k].y & 0xFFFFu, b1 = rt[k].y >> 16;
-        uint32_t out[2] = {0, 0};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint32_t v = ((__umul24(b0, h[0][j]) >> 16) + (__umul24(b1, h[1][j]) >> 16) + 2u) >> 2;
-            out[j >> 2] |= (v & 0xFFu) << (8 * (j & 3));
-        }
-        if (TO_LDS) *reinterpret_cast<uint2*>(dtile + (__umul24((unsigned)(yrow[k] - (int)R.cmp0), (unsigned)V.pitch) + 8u * (unsigned)g)) = make_uint2(out[0], out[1]);
-        if (yrow[k] >= (int)R.own0 && yrow[k] < (int)R.own1)
-            *reinterpret_cast<uint2*>(D + (__umul24((unsigned)yrow[k], (unsigned)V.dstride) + 8u * (unsigned)g)) = make_uint2(out[0], out[1]);
-    }
+    rs_rows8<4>(rt, sh, sel, al,
+        [&](const unsigned srow, uint32_t* w) {
+            if (FROM_LDS) {   // the plan keeps every source row of a computed row inside the band's rows of the level below
+                const uint32_t* p = reinterpret_cast<const uint32_t*>(stile + (__umul24(srow - (unsigned)srow0, spitch) + b));
+                w[0] = p[0]; w[1] = p[1]; w[2] = p[2]; w[3] = p[3];
+            } else {
+                const rs_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(__umul24(srow, ss) + b), 0, 0);
+                w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+            }
+        },
+        [&](const int k, const uint32_t o0, const uint32_t o1) {
+            if (TO_LDS) *reinterpret_cast<uint2*>(dtile + (__umul24((unsigned)(yrow[k] - (int)R.cmp0), (unsigned)V.pitch) + 8u * (unsigned)g)) = make_uint2(o0, o1);
+            if (yrow[k] >= (int)R.own0 && yrow[k] < (int)R.own1)
+                *reinterpret_cast<uint2*>(D + (__umul24((unsigned)yrow[k], (unsigned)V.dstride) + 8u * (unsigned)g)) = make_uint2(o0, o1);
+        });
 }
 
 __global__ __launch_bounds__(BAND_THREADS) void pyramid_bands_kernel(
@@ -1735,19 +1738,21 @@ __global__ __launch_bounds__(256) void blur_stream_kernel(
     const int ylast = min(by0 + ORB_BLUR_STRIP_H, h) - 1;
     const int p0 = (by0 - 3) >> 1, p1 = (ylast + 3) >> 1;   // pairs of rows (2p, 2p + 1); arithmetic shift: by0 - 3 may be negative
     typedef unsigned blur_u3 __attribute__((ext_vector_type(3)));
-    auto fetch = [&](int yy) -> blur_u3 {
-        int r = yy < 0 ? -yy : yy;
-        r = r >= h ? 2 * h - 2 - r : r;
-        r = min(max(r, 0), h - 1);   // (rows further out are only read for outputs that are not stored)
+    auto fetch_row = [&](const uint8_t* R) -> blur_u3 {   // the 12-byte window of the row that starts at R
         if (EDGE) {
-            const uint8_t* R = S + __umul24((unsigned)r, ss);
             blur_u3 v;
             v.x = __builtin_amdgcn_perm(*reinterpret_cast<const uint32_t*>(R + bc[0].a1), *reinterpret_cast<const uint32_t*>(R + bc[0].a0), bc[0].sel);
             v.y = __builtin_amdgcn_perm(*reinterpret_cast<const uint32_t*>(R + bc[1].a1), *reinterpret_cast<const uint32_t*>(R + bc[1].a0), bc[1].sel);
             v.z = __builtin_amdgcn_perm(*reinterpret_cast<const uint32_t*>(R + bc[2].a1), *reinterpret_cast<const uint32_t*>(R + bc[2].a0), bc[2].sel);
             return v;
         }
-        return *reinterpret_cast<const blur_u3*>(S + __umul24((unsigned)r, ss));   // rows < 2^16, pitch < 2^24: the full-rate multiply
+        return *reinterpret_cast<const blur_u3*>(R);
+    };
+    auto fetch = [&](int yy) -> blur_u3 {
+        int r = yy < 0 ? -yy : yy;
+        r = r >= h ? 2 * h - 2 - r : r;
+        r = min(max(r, 0), h - 1);   // (rows further out are only read for outputs that are not stored)
+        return fetch_row(S + __umul24((unsigned)r, ss));   // rows < 2^16, pitch < 2^24: the full-rate multiply
     };
     auto rowpass = [&](const blur_u3 v, uint32_t* o) {
         o[0] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(v.z, v.y, 1), TB, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(v.y, v.x, 1), TA, 0u, false), false);
@@ -1755,28 +1760,104 @@ __global__ __launch_bounds__(256) void blur_stream_kernel(
         o[2] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(v.z, v.y, 3), TB, __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(v.y, v.x, 3), TA, 0u, false), false);
         o[3] = __builtin_amdgcn_udot4(v.z, TB, __builtin_amdgcn_udot4(v.y, TA, 0u, false), false);
     };
-    uint32_t P0[4] = {0, 0, 0, 0}, P1[4] = {0, 0, 0, 0}, P2[4] = {0, 0, 0, 0}, P3[4];   // the last four row pairs, oldest first
+    uint32_t P[4][4];   // the last four row pairs; outside the unrolled steady loop P[0] is the oldest and P[3] the pair just completed
     // three pairs of rows in flight: a thread's walk is a chain of ~36 dependent steps, and with one pair ahead every step waited for HBM
-    blur_u3 va = fetch(2 * p0), vb = fetch(2 * p0 + 1), va1 = fetch(2 * p0 + 2), vb1 = fetch(2 * p0 + 3), va2 = fetch(2 * p0 + 4), vb2 = fetch(2 * p0 + 5);
-#pragma unroll 4
-    for (int p = p0; p <= p1; ++p) {
-        const blur_u3 ca = va, cb = vb;
-        va = va1; vb = vb1; va1 = va2; vb1 = vb2;
-        va2 = fetch(2 * p + 6); vb2 = fetch(2 * p + 7);   // (rows past the strip's last pair are clamped reads of rows that exist)
+    blur_u3 qa[3], qb[3];   // (outside the unrolled steady loop slot 0 is the pair consumed next)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { qa[k] = fetch(2 * p0 + 2 * k); qb[k] = fetch(2 * p0 + 2 * k + 1); }
+    // one step of the walk: the pair in queue slot q goes through the row pass into P[f], and (na, nb) take its slot
+    auto advance = [&](const int q, const int f, const blur_u3 na, const blur_u3 nb) {
+        const blur_u3 ca = qa[q], cb = qb[q];
+        qa[q] = na; qb[q] = nb;
         uint32_t oa[4], ob[4];
         rowpass(ca, oa); rowpass(cb, ob);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) P3[j] = oa[j] | (ob[j] << 16);
-        const int ya = 2 * p - 3, yb = 2 * p - 2;
-#define BLUR_OUT(k0, k1, k2, k3, j) min((udot2(P3[j], k3, udot2(P2[j], k2, udot2(P1[j], k1, udot2(P0[j], k0, 1u << 15)))) >> 16), 255u)
-        if (ya >= by0 && ya <= ylast)
-            *reinterpret_cast<uint32_t*>(D + __umul24((unsigned)ya, ds)) = BLUR_OUT(kA0, kA1, kA2, kA3, 0) | (BLUR_OUT(kA0, kA1, kA2, kA3, 1) << 8) | (BLUR_OUT(kA0, kA1, kA2, kA3, 2) << 16) | (BLUR_OUT(kA0, kA1, kA2, kA3, 3) << 24);
-        if (yb >= by0 && yb <= ylast)
-            *reinterpret_cast<uint32_t*>(D + __umul24((unsigned)yb, ds)) = BLUR_OUT(kB0, kB1, kB2, kB3, 0) | (BLUR_OUT(kB0, kB1, kB2, kB3, 1) << 8) | (BLUR_OUT(kB0, kB1, kB2, kB3, 2) << 16) | (BLUR_OUT(kB0, kB1, kB2, kB3, 3) << 24);
-#undef BLUR_OUT
+        for (int j = 0; j < 4; ++j) P[f][j] = oa[j] | (ob[j] << 16);
+    };
+    auto rotate = [&]() {   // back to the canonical order after one generic step
+        const blur_u3 ta = qa[0], tb = qb[0];
+        qa[0] = qa[1]; qb[0] = qb[1]; qa[1] = qa[2]; qb[1] = qb[2]; qa[2] = ta; qb[2] = tb;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { P0[j] = P1[j]; P1[j] = P2[j]; P2[j] = P3[j]; }
+        for (int j = 0; j < 4; ++j) { P[0][j] = P[1][j]; P[1][j] = P[2][j]; P[2][j] = P[3][j]; }
+    };
+    // the column pass of one output row: f is the slot of the pair just completed, the three before it follow it in the ring
+#define BLUR_OUT(f, k0, k1, k2, k3, j) \
+    min((udot2(P[(f) & 3][j], k3, udot2(P[((f) + 3) & 3][j], k2, udot2(P[((f) + 2) & 3][j], k1, udot2(P[((f) + 1) & 3][j], k0, 1u << 15)))) >> 16), 255u)
+#define BLUR_OUT_A(f) (BLUR_OUT(f, kA0, kA1, kA2, kA3, 0) | (BLUR_OUT(f, kA0, kA1, kA2, kA3, 1) << 8) | (BLUR_OUT(f, kA0, kA1, kA2, kA3, 2) << 16) | (BLUR_OUT(f, kA0, kA1, kA2, kA3, 3) << 24))
+#define BLUR_OUT_B(f) (BLUR_OUT(f, kB0, kB1, kB2, kB3, 0) | (BLUR_OUT(f, kB0, kB1, kB2, kB3, 1) << 8) | (BLUR_OUT(f, kB0, kB1, kB2, kB3, 2) << 16) | (BLUR_OUT(f, kB0, kB1, kB2, kB3, 3) << 24))
+    // the generic step: rows reflect by index, each of the two output rows is stored if the strip owns it
+    auto generic = [&](const int p) {
+        const blur_u3 na = fetch(2 * p + 6), nb = fetch(2 * p + 7);   // (rows past the strip's last pair are clamped reads of rows that exist)
+        advance(0, 3, na, nb);
+        const int ya = 2 * p - 3, yb = 2 * p - 2;
+        if (ya >= by0 && ya <= ylast) *reinterpret_cast<uint32_t*>(D + __umul24((unsigned)ya, ds)) = BLUR_OUT_A(3);
+        if (yb >= by0 && yb <= ylast) *reinterpret_cast<uint32_t*>(D + __umul24((unsigned)yb, ds)) = BLUR_OUT_B(3);
+        rotate();
+    };
+    // The walk by relative iteration.  Whatever by0, pairs p0 .. p0 + 2 complete only rows above the strip (2 p - 2 < by0): they fill
+    // P[0] .. P[2] and issue no column pass.  Pair p0 + 3 (<= p1 always) may own one row or two: the generic step.  From p0 + 4 on both
+    // rows are owned until 2 p - 2 > ylast, and the look-ahead rows 2 p + 6, 2 p + 7 (>= 2) need no reflection until 2 p + 7 > h - 1:
+    // the steady range, with running source and destination pointers, no reflection, no multiply and both stores unconditional.
+    // A wave holds four strips that may differ in level, by0 and height, so it runs the steady loop for the smallest count among its
+    // lanes (a scalar trip count); every lane finishes in the generic loop.
+    int p = p0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k, ++p) advance(k, k, fetch(2 * p + 6), fetch(2 * p + 7));
+    generic(p);
+    ++p;
+    const int n = min((ylast + 2) >> 1, (h - 8) >> 1) - p + 1;   // this lane's steady steps (may be <= 0)
+    int nu = 0;
+    {
+        const unsigned long long act = __ballot(1);   // (lanes past the tile list or the image's right edge have left)
+#pragma unroll
+        for (int b = 32; b; b >>= 1) nu += __ballot(n >= nu + b) == act ? b : 0;
     }
+    if (nu > 0) {
+        const uint8_t* sp = S + __umul24((unsigned)(2 * p + 6), ss);   // one running pointer each way, a row per add
+        uint8_t* dp = D + __umul24((unsigned)(2 * p - 3), ds);
+        p += nu;
+        auto steady = [&](const int q, const int f) {
+            const blur_u3 na = fetch_row(sp);
+            sp += ss;
+            const blur_u3 nb = fetch_row(sp);
+            sp += ss;
+            advance(q, f, na, nb);
+            *reinterpret_cast<uint32_t*>(dp) = BLUR_OUT_A(f);
+            dp += ds;
+            *reinterpret_cast<uint32_t*>(dp) = BLUR_OUT_B(f);
+            dp += ds;
+            asm volatile("" : "+v"(sp), "+v"(dp));   // (keeps the two pointers running: the compiler would compute every step's addresses at the trip's top)
+        };
+        // Twelve steps per trip, by hand: the queue turns once in 3 steps and the ring once in 4, so with slot and ring position
+        // compile-time no step moves a register (a rolled step moves 34).  The scheduling barrier keeps a step's loads inside it:
+        // hoisted to the trip's top they cost the kernel its waves (121 VGPRs against 70).  Then trips of three, then single steps.
+        for (; nu >= 12; nu -= 12) {
+#pragma unroll
+            for (int u = 0; u < 12; ++u) {
+                steady(u % 3, (u + 3) & 3);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        for (; nu >= 3; nu -= 3) {   // the queue turns once, the ring is one slot short of a turn
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+                steady(u, (u + 3) & 3);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { P[2][j] = P[1][j]; P[1][j] = P[0][j]; P[0][j] = P[3][j]; }
+        }
+#pragma unroll 1
+        for (; nu > 0; --nu) {
+            steady(0, 3);
+            rotate();
+        }
+    }
+#pragma unroll 4
+    for (; p <= p1; ++p) generic(p);
+#undef BLUR_OUT_B
+#undef BLUR_OUT_A
+#undef BLUR_OUT
 }
 
 // --------------------------------------------------------------------------------------------
