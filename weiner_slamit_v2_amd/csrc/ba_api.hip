@@ -17,16 +17,16 @@
 
 #include "../../include/slamit.h"
 #include "ba_plan.h"
+#include "ba_schedule.h"
 #include "ba_types.h"
 #include "slamit_internal.h"
 
 size_t bak_ldlt_smem(int Npad);
 hipError_t bak_prepare(int Npad);
-void bak_import(hipStream_t st, BaWin* wins, const BaIo* io, int max_kf, int max_pt, int max_edge, int Npad, int nwin);
-void bak_stage_begin(hipStream_t st, BaWin* wins, int nwin, int max_edge, int stage, int max_it, int robust, bool gate);
-void bak_slot(hipStream_t st, BaWin* wins, int nwin, int max_kf, int max_pt, int max_edge, int Npad, int Npad_ldlt, const int* tl_grid, int tl_npanel,
-              bool first, unsigned solvers, hipEvent_t* ev);
-void bak_final(hipStream_t st, BaWin* wins, const BaIo* io, int nwin, int max_kf, int max_pt, int max_edge);
+void bak_import(hipStream_t st, BaWin* wins, const BaIo* io, const BaBatchPlan& B);
+void bak_stage_begin(hipStream_t st, BaWin* wins, const BaBatchPlan& B, int stage, int max_it);
+void bak_slot(hipStream_t st, BaWin* wins, const BaBatchPlan& B, bool first, hipEvent_t* ev);
+void bak_final(hipStream_t st, BaWin* wins, const BaIo* io, const BaBatchPlan& B);
 
 static_assert(BA_MAX_ITS == SLAMIT_BA_MAX_ITS, "stats capacity");
 static_assert(BA_MAX_FREE_KF == SLAMIT_BA_MAX_FREE_KF && BA_NPAD_CEIL == (6 * BA_MAX_FREE_KF + 1 + BA_TILE - 1) / BA_TILE * BA_TILE, "free keyframe ceiling");
@@ -76,6 +76,204 @@ bool for_each_window(int nwin, bool spread, F&& fn) {
     work();
     for (std::thread& t : pool) t.join();
     return !failed;
+}
+
+// One call of slamit_ba_solve_batch: the arguments, and what its steps hand on to each other.
+struct BaSolve {
+    slamit_ba* h; int nwin; const slamit_ba_problem* probs; const slamit_ba_opts* opts; slamit_ba_result* results;
+    BaBatchPlan B;
+    std::vector<BaWin> wins; std::vector<BaIo> io; std::vector<BaWindowPlan> plans;   // per window: the device's record, its io table entry, the host's plan
+    size_t pev_used = 0;   // profiling solves: six events per queued slot
+    bool stopped = false;  // the caller's stop flag was seen up
+};
+
+double tclk() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// every check that does not touch the device (ba_batch_check, ba_plan.cc)
+int ba_validate(const BaSolve& s) {
+    const BaRefusal r = ba_batch_check(s.probs, s.results, s.nwin, BaCaps{s.h->max_kf, s.h->max_free_kf, s.h->max_pt, s.h->max_edge, s.h->max_batch});
+    return r.code == SLAMIT_OK ? SLAMIT_OK : slamit_fail(r.code, r.msg);
+}
+
+// the handle's pinned block, grown (with a quarter to spare) when the batch needs more
+int ba_grow_pinned(slamit_ba* h, size_t need) {
+    if (need <= h->pin_bytes) return SLAMIT_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->h_pin) hipHostFree(h->h_pin);
+    h->h_pin = nullptr; h->pin_bytes = 0;
+    HIP_TRY(hipHostMalloc((void**)&h->h_pin, need + need / 4, hipHostMallocDefault));
+    h->pin_bytes = need + need / 4;
+    return SLAMIT_OK;
+}
+
+// Per-window preparation (the plan, CSR lists, packing into the pinned block) is host work of ~10 ns per edge: windows are
+// independent, so a batch is prepared by a few host threads; the copies are queued afterwards, in order.
+int ba_prepare_windows(BaSolve& s) {
+    slamit_ba* h = s.h;
+    const BaBatchPlan& B = s.B;
+    s.wins.resize(s.nwin); s.io.resize(s.nwin); s.plans.resize(s.nwin);
+    const BaPlanLimits lim{h->Npad_max, s.nwin, h->sw.ba_keep_order, h->sw.ba_no_sf, h->sw.ba_no_band, h->sw.ba_sf_cap};
+    std::atomic<bool> bad_index(false);
+    auto prepare = [&](int b) {
+        const slamit_ba_problem& P = s.probs[b];
+        BaWin& w = s.wins[b];
+        BaIo& io = s.io[b];
+        memset(&w, 0, sizeof(w));
+        if (!ba_plan_window(P, lim, w, s.plans[b])) { bad_index = true; return; }
+        ba_pack_inputs(P, s.plans[b], carve_io(h->h_pin + B.in_off[b], P.n_kf, P.n_pt, P.n_edge, P.edge_ur != nullptr, B.side_w[b]));   // the device's packing, in the pinned block
+        carve_work(h->d_slab + (size_t)b * h->win_bytes + h->io_cap, w, h->max_kf, h->max_pt, h->max_edge, h->Npad_max, h->Kpad_max, h->n_part, h->max_free_kf);
+        const IoLayout& D = B.dio[b];
+        w.side = D.side;   // (null unless the window's structure outgrows BaWin's inline arrays)
+        w.intr = D.intr; w.pose_col = D.pose_col; w.e_kf = D.e_kf; w.e_pt = D.e_pt; w.e_uv = D.e_uv; w.e_w = D.e_w;
+        w.pt_edges = D.pt_edges; w.kf_edges = D.kf_edges; w.pt_ptr = D.pt_ptr; w.kf_ptr = D.kf_ptr;
+        w.e_ur = D.e_ur; w.bf = D.bf;
+        io.in_pose = D.in_pose; io.in_pt = D.in_pt; io.out_pose = D.out_pose; io.out_pt = D.out_pt;
+        io.out_chi2 = D.out_chi2; io.out_flag = D.out_flag; io.out_out1 = D.out_out1; io.out_state = D.out_state;
+        w.n_part = h->n_part;
+        w.huber_delta = s.opts->huber_delta; w.chi2_gate = s.opts->chi2_gate;
+        // stereo observations (EdgeStereoSE3ProjectXYZ): three residual rows per edge in this window, own Huber width and gate
+        w.huber_delta_s = s.opts->huber_delta_stereo > 0 ? s.opts->huber_delta_stereo : (double)(float)sqrt(7.815);   // Optimizer.cc:570
+        w.chi2_gate_s = s.opts->chi2_gate_stereo > 0 ? s.opts->chi2_gate_stereo : 7.815;                           // Optimizer.cc:696, 740
+        w.nrow = P.edge_ur ? 3 : 2;
+        w.st = reinterpret_cast<BaState*>(h->d_wins) - (b + 1);
+    };
+    if (!for_each_window(s.nwin, true, prepare))
+        return slamit_fail(SLAMIT_ERR_DEVICE, "slamit_ba_solve_batch: out of host memory while preparing the windows");
+    if (bad_index) return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_solve_batch: edge index out of range");
+    return SLAMIT_OK;
+}
+
+// one copy per window into its input section, the window and io tables, and the import (which also zeroes the Schur operands' ranges and the LM states)
+int ba_queue_uploads(BaSolve& s) {
+    slamit_ba* h = s.h;
+    for (int b = 0; b < s.nwin; ++b)
+        HIP_TRY(hipMemcpyAsync(h->d_slab + (size_t)b * h->win_bytes, h->h_pin + s.B.in_off[b], s.B.dio[b].in_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_wins, s.wins.data(), sizeof(BaWin) * s.nwin, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_io, s.io.data(), sizeof(BaIo) * s.nwin, hipMemcpyHostToDevice, h->stream));
+    bak_import(h->stream, h->d_wins, h->d_io, s.B);
+    return SLAMIT_OK;
+}
+
+// profiling solves: the six events of the next slot (null otherwise, or when no event can be had)
+hipEvent_t* ba_slot_events(BaSolve& s) {
+    slamit_ba* h = s.h;
+    if (!h->prof) return nullptr;
+    while (h->pev.size() < s.pev_used + 6) {
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return nullptr;
+        h->pev.push_back(e);
+    }
+    s.pev_used += 6;
+    return h->pev.data() + s.pev_used - 6;
+}
+
+// One stage of the two-stage schedule (Optimizer.cc:659-707), its trial slots queued in the chunks BaStageSchedule deals (ba_schedule.h).
+// *stop is polled before every chunk like SparseOptimizer::terminate() (sparse_optimizer.cpp:376) is before every iteration.
+int ba_run_stage(BaSolve& s, int stage) {
+    slamit_ba* h = s.h;
+    const int nwin = s.nwin;
+    hipStream_t st = h->stream;
+    BaState* hs[2] = {reinterpret_cast<BaState*>(h->h_pin + s.B.st_off), reinterpret_cast<BaState*>(h->h_pin + s.B.st_off) + nwin};
+    const int its = stage == 0 ? s.opts->its_robust : s.opts->its_final;
+    bak_stage_begin(st, h->d_wins, s.B, stage, its);
+    BaStageSchedule sched(stage, its);
+    for (bool over = false; !over;) {
+        if (s.opts->stop && *s.opts->stop) { s.stopped = true; break; }
+        const BaChunk c = sched.next();
+        for (int sl = 0; sl < c.nslots; ++sl) bak_slot(st, h->d_wins, s.B, c.first && sl == 0, ba_slot_events(s));
+        if (c.nslots) {
+            HIP_TRY(hipMemcpyAsync(hs[c.qbuf], reinterpret_cast<BaState*>(h->d_wins) - nwin, sizeof(BaState) * nwin, hipMemcpyDeviceToHost, st));   // (reverse order: only `done` of all is read)
+            HIP_TRY(hipEventRecord(h->ev[c.qbuf], st));
+        }
+        bool all_done = false;
+        if (c.wbuf >= 0) {
+            HIP_TRY(hipEventSynchronize(h->ev[c.wbuf]));
+            all_done = true;
+            for (int b = 0; b < nwin; ++b) all_done = all_done && hs[c.wbuf][b].done;
+        }
+        over = sched.finished(all_done);
+    }
+    HIP_TRY(hipGetLastError());
+    return SLAMIT_OK;
+}
+
+// results: one copy per window out of its output section
+int ba_download(BaSolve& s) {
+    slamit_ba* h = s.h;
+    bak_final(h->stream, h->d_wins, h->d_io, s.B);
+    for (int b = 0; b < s.nwin; ++b)
+        HIP_TRY(hipMemcpyAsync(h->h_pin + s.B.out_off[b], h->d_slab + (size_t)b * h->win_bytes + s.B.dio[b].out_off, s.B.dio[b].bytes - s.B.dio[b].out_off,
+                               hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return SLAMIT_OK;
+}
+
+// slamit_ba_profile: the phase sums of the solve's slots
+void ba_profile_sums(const BaSolve& s) {
+    slamit_ba_profile_out& O = s.h->prof_last;
+    memset(&O, 0, sizeof(O));
+    O.nwin = s.nwin; O.slots = (int32_t)(s.pev_used / 6);
+    for (size_t s0 = 0; s0 + 6 <= s.pev_used; s0 += 6)
+        for (int ph = 0; ph < SLAMIT_BA_PHASES; ++ph) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, s.h->pev[s0 + ph], s.h->pev[s0 + ph + 1]) == hipSuccess) O.phase_ms[ph] += ms;
+        }
+    for (int b = 0; b < s.nwin; ++b) O.schur_exec_mflop += s.plans[b].exec_mflop;
+}
+
+// window b's output section as the host sees it: same carve, shifted so that its output part starts at out_off[b]
+IoLayout ba_host_outputs(const BaSolve& s, int b) {
+    const slamit_ba_problem& P = s.probs[b];
+    return carve_io(s.h->h_pin + s.B.out_off[b] - s.B.dio[b].out_off, P.n_kf, P.n_pt, P.n_edge, P.edge_ur != nullptr, s.B.side_w[b]);
+}
+
+void ba_unpack(BaSolve& s) {
+    auto unpack = [&](int b) { ba_unpack_outputs(s.probs[b], s.plans[b], ba_host_outputs(s, b), s.results[b]); };
+    for_each_window(s.nwin, s.nwin >= 4, unpack);   // by the host threads that prepared the windows (nothing in it throws)
+}
+
+// The diagnostics on stderr (SlamitSwitches::ba_diag_waves, ba_diag, ba_timing; tools/diag/* parse them): window 0's in-kernel stamps, and the
+// host phases of the call between the stamps t[0 .. 4] = entry, validated, prepared, uploads queued, LM loop over, and now
+void ba_diagnostics(const BaSolve& s, const double* t) {
+    const SlamitSwitches& sw = s.h->sw;
+    const BaState& S0 = *ba_host_outputs(s, 0).out_state;
+    if (sw.ba_diag_waves) fprintf(stderr, "[ba diag] busy cycles of waves 0..7: %llu %llu %llu %llu %llu %llu %llu %llu\n", S0.dbg[0], S0.dbg[1], S0.dbg[2], S0.dbg[3], S0.dbg[4], S0.dbg[5], S0.dbg[6], S0.dbg[7]);
+    if (sw.ba_diag) {  // diagnostic builds only: in-kernel clock and phases of the last LDLt launch
+        fprintf(stderr, "[ba diag] ldlt shader cycles %llu, realtime ticks (100 MHz) %llu -> %.0f MHz, %.1f us\n",
+                S0.dbg[2] - S0.dbg[0], S0.dbg[3] - S0.dbg[1],
+                100.0 * (double)(S0.dbg[2] - S0.dbg[0]) / (double)(S0.dbg[3] - S0.dbg[1] + 1), (double)(S0.dbg[3] - S0.dbg[1]) / 100.0);
+        fprintf(stderr, "[ba diag] ldlt phase cycles: load %llu factor %llu rows %llu writeback / wave-0 busy %llu trailing / rhs-wave busy %llu backsub %llu, pivot-wave busy %llu\n",
+                S0.dbg[4] >> 32, S0.dbg[4] & 0xffffffffull, S0.dbg[5] >> 32, S0.dbg[5] & 0xffffffffull, S0.dbg[6] >> 32, S0.dbg[6] & 0xffffffffull, S0.dbg[7]);
+    }
+    if (sw.ba_timing)
+        fprintf(stderr, "[ba timing] %d windows: validate %.3f | prepare + pack %.3f | queue uploads %.3f | LM loop %.3f | download + unpack %.3f ms\n",
+                s.nwin, t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], tclk() - t[4]);
+}
+
+int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* probs, const slamit_ba_opts* opts, slamit_ba_result* results) {
+    if (!h || !opts) return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_solve_batch: bad argument");
+    SLAMIT_USE_DEVICE(h->device);
+    BaSolve s{h, nwin, probs, opts, results};
+    double t[5] = {tclk()};
+    if (int rc = ba_validate(s)) return rc;
+    if (nwin == 0) return SLAMIT_OK;
+    t[1] = tclk();
+    ba_batch_layout(probs, nwin, h->win_bytes, h->d_slab, s.B);
+    if (int rc = ba_grow_pinned(h, s.B.pin_need)) return rc;
+    if (int rc = ba_prepare_windows(s)) return rc;
+    t[2] = tclk();
+    ba_batch_launches(s.wins.data(), s.plans.data(), s.B);
+    if (int rc = ba_queue_uploads(s)) return rc;
+    t[3] = tclk();
+    s.stopped = opts->stop && *opts->stop;  // Optimizer.cc:655-657
+    for (int stage = 0; stage < 2 && !s.stopped; ++stage)
+        if (int rc = ba_run_stage(s, stage)) return rc;
+    t[4] = tclk();
+    if (int rc = ba_download(s)) return rc;
+    if (h->prof) ba_profile_sums(s);
+    ba_unpack(s);
+    ba_diagnostics(s, t);
+    return SLAMIT_OK;
 }
 
 }  // namespace
@@ -146,8 +344,6 @@ void slamit_ba_destroy(slamit_ba* h) {
     delete h;
 }
 
-static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* probs, const slamit_ba_opts* opts, slamit_ba_result* results);
-
 int slamit_ba_solve_batch(slamit_ba* h, int nwin, const slamit_ba_problem* probs, const slamit_ba_opts* opts,
                           slamit_ba_result* results) {
     try {
@@ -157,205 +353,6 @@ int slamit_ba_solve_batch(slamit_ba* h, int nwin, const slamit_ba_problem* probs
     } catch (...) {
         return slamit_fail(SLAMIT_ERR_DEVICE, "slamit_ba_solve_batch: unexpected exception");
     }
-}
-
-static int ba_solve_batch_impl(slamit_ba* h, int nwin, const slamit_ba_problem* probs, const slamit_ba_opts* opts,
-                               slamit_ba_result* results) {
-    if (!h || !probs || !opts || !results || nwin < 0) return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_solve_batch: bad argument");
-    if (nwin > h->max_batch) return slamit_fail(SLAMIT_ERR_CAPACITY, "slamit_ba_solve_batch: nwin > max_batch");
-    if (nwin == 0) return SLAMIT_OK;
-    SLAMIT_USE_DEVICE(h->device);
-    hipStream_t st = h->stream;
-    const auto tclk = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_in = tclk();
-    double t_val = 0, t_prep = 0, t_queue = 0, t_loop = 0;
-    // ---- validate ----
-    int mk = 1, mp = 1, me = 1, Npad = BA_TILE, Npad_ldlt = BA_TILE;
-    for (int b = 0; b < nwin; ++b) {
-        const slamit_ba_problem& P = probs[b];
-        if (P.n_kf < 1 || P.n_pt < 0 || P.n_edge < 0 || P.n_kf > h->max_kf || P.n_pt > h->max_pt || P.n_edge > h->max_edge)
-            return slamit_fail(SLAMIT_ERR_CAPACITY, "slamit_ba_solve_batch: window exceeds the handle's capacity");
-        if (!P.kf_pose || !P.kf_fixed || !P.kf_intr || (P.n_pt && !P.pt_xyz) ||
-            (P.n_edge && (!P.edge_kf || !P.edge_pt || !P.edge_uv || !P.edge_inv_sigma2)))
-            return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_solve_batch: null input array");
-        int nfree = 0;
-        for (int k = 0; k < P.n_kf; ++k) nfree += P.kf_fixed[k] ? 0 : 1;
-        if (nfree > h->max_free_kf)
-            return slamit_fail(SLAMIT_ERR_CAPACITY, "slamit_ba_solve_batch: window has more free keyframes than the handle's max_free_kf");
-        if (P.edge_ur && !P.kf_bf)
-            return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_solve_batch: stereo observations (edge_ur) without the keyframes' bf (kf_bf)");
-        if (!results[b].kf_pose || (P.n_pt && !results[b].pt_xyz))
-            return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_solve_batch: null output array");
-        mk = std::max(mk, P.n_kf); mp = std::max(mp, P.n_pt); me = std::max(me, P.n_edge);
-    }
-    // (the edges' indices are checked by the threads that prepare the windows, before anything is packed)
-    t_val = tclk();
-    // ---- one pinned block: [inputs of window 0 | inputs of window 1 | ...][outputs ...][2 x nwin LM states] ----
-    std::vector<size_t> in_off(nwin), out_off(nwin), side_w(nwin);
-    std::vector<IoLayout> dio(nwin);   // device addresses inside the slabs
-    size_t pin_need = 0;
-    for (int b = 0; b < nwin; ++b) {
-        side_w[b] = ba_io_side_words(probs[b]);
-        dio[b] = carve_io(h->d_slab + (size_t)b * h->win_bytes, probs[b].n_kf, probs[b].n_pt, probs[b].n_edge, probs[b].edge_ur != nullptr, side_w[b]);
-        in_off[b] = pin_need; pin_need += dio[b].in_bytes;
-    }
-    for (int b = 0; b < nwin; ++b) { out_off[b] = pin_need; pin_need += dio[b].bytes - dio[b].out_off; }
-    const size_t st_off = ba_rup(pin_need, 256);
-    pin_need = st_off + 2 * sizeof(BaState) * (size_t)nwin;
-    if (pin_need > h->pin_bytes) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (h->h_pin) hipHostFree(h->h_pin);
-        h->h_pin = nullptr; h->pin_bytes = 0;
-        HIP_TRY(hipHostMalloc((void**)&h->h_pin, pin_need + pin_need / 4, hipHostMallocDefault));
-        h->pin_bytes = pin_need + pin_need / 4;
-    }
-    std::vector<BaWin> wins(nwin);
-    std::vector<BaIo> io(nwin);
-    std::vector<BaWindowPlan> plans(nwin);
-    const BaPlanLimits lim{h->Npad_max, nwin, h->sw.ba_keep_order, h->sw.ba_no_sf, h->sw.ba_no_band, h->sw.ba_sf_cap};
-    // per-window preparation (the plan, CSR lists, packing into the pinned block) is host work of ~10 ns per edge: windows
-    // are independent, so a batch is prepared by a few host threads; the copies are queued afterwards, in order
-    std::atomic<bool> bad_index(false);
-    auto prepare = [&](int b) {
-        const slamit_ba_problem& P = probs[b];
-        BaWin& w = wins[b];
-        memset(&w, 0, sizeof(w));
-        if (!ba_plan_window(P, lim, w, plans[b])) { bad_index = true; return; }
-        ba_pack_inputs(P, plans[b], carve_io(h->h_pin + in_off[b], P.n_kf, P.n_pt, P.n_edge, P.edge_ur != nullptr, side_w[b]));   // the device's packing, in the pinned block
-        carve_work(h->d_slab + (size_t)b * h->win_bytes + h->io_cap, w, h->max_kf, h->max_pt, h->max_edge, h->Npad_max, h->Kpad_max, h->n_part, h->max_free_kf);
-        const IoLayout& D = dio[b];
-        w.side = D.side;   // (null unless the window's structure outgrows BaWin's inline arrays)
-        w.intr = D.intr; w.pose_col = D.pose_col; w.e_kf = D.e_kf; w.e_pt = D.e_pt; w.e_uv = D.e_uv; w.e_w = D.e_w;
-        w.pt_edges = D.pt_edges; w.kf_edges = D.kf_edges; w.pt_ptr = D.pt_ptr; w.kf_ptr = D.kf_ptr;
-        w.e_ur = D.e_ur; w.bf = D.bf;
-        io[b].in_pose = D.in_pose; io[b].in_pt = D.in_pt; io[b].out_pose = D.out_pose; io[b].out_pt = D.out_pt;
-        io[b].out_chi2 = D.out_chi2; io[b].out_flag = D.out_flag; io[b].out_out1 = D.out_out1; io[b].out_state = D.out_state;
-        w.n_part = h->n_part;
-        w.huber_delta = opts->huber_delta; w.chi2_gate = opts->chi2_gate;
-        // stereo observations (EdgeStereoSE3ProjectXYZ): three residual rows per edge in this window, own Huber width and gate
-        w.huber_delta_s = opts->huber_delta_stereo > 0 ? opts->huber_delta_stereo : (double)(float)sqrt(7.815);   // Optimizer.cc:570
-        w.chi2_gate_s = opts->chi2_gate_stereo > 0 ? opts->chi2_gate_stereo : 7.815;                           // Optimizer.cc:696, 740
-        w.nrow = P.edge_ur ? 3 : 2;
-        w.st = reinterpret_cast<BaState*>(h->d_wins) - (b + 1);
-    };
-    if (!for_each_window(nwin, true, prepare))
-        return slamit_fail(SLAMIT_ERR_DEVICE, "slamit_ba_solve_batch: out of host memory while preparing the windows");
-    if (bad_index) return slamit_fail(SLAMIT_ERR_ARG, "slamit_ba_solve_batch: edge index out of range");
-    t_prep = tclk();
-    unsigned solvers = 0;
-    // the tiled solve's launches per panel step: {panel workgroups, update workgroups} for the largest need among its windows
-    std::vector<int> tl_grid;
-    for (int b = 0; b < nwin; ++b) {
-        Npad = std::max(Npad, wins[b].Npad);
-        solvers |= 1u << wins[b].solver;
-        HIP_TRY(hipMemcpyAsync(h->d_slab + (size_t)b * h->win_bytes, h->h_pin + in_off[b], dio[b].in_bytes, hipMemcpyHostToDevice, st));
-        if (wins[b].solver != BA_SOLVER_TILED) { Npad_ldlt = std::max(Npad_ldlt, wins[b].Npad); continue; }
-        BaWin wh = wins[b];
-        wh.side = plans[b].side.data();
-        const int n = wh.nS, np = (n + 31) / 32;
-        if ((int)tl_grid.size() < 2 * np) tl_grid.resize(2 * np, 0);
-        for (int i = 0; i < np; ++i) {
-            const int base = std::min(32 * i + 32, n), below = std::max(ba_panel_hi(wh, i) + 1 - base, 0);
-            tl_grid[2 * i] = std::max(tl_grid[2 * i], (below + 1 + BA_TL_CHUNK - 1) / BA_TL_CHUNK);
-            tl_grid[2 * i + 1] = std::max(tl_grid[2 * i + 1], ldlt_tiled_ntiles(below));
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_wins, wins.data(), sizeof(BaWin) * nwin, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_io, io.data(), sizeof(BaIo) * nwin, hipMemcpyHostToDevice, st));
-    bak_import(st, h->d_wins, h->d_io, mk, mp, me, Npad, nwin);   // also zeroes the Schur operands' ranges and the LM states
-
-    // ---- two-stage schedule (Optimizer.cc:659-707) ----
-    // LM trial slots are enqueued in chunks; the windows' states come back through the pinned block one chunk LATE (the
-    // next chunk is already queued when the host looks at the previous one: no bubble between chunks), and *stop is polled
-    // before every chunk like SparseOptimizer::terminate() (sparse_optimizer.cpp:376) is before every iteration.  Slots of
-    // a finished stage return at once, but a slot queued in vain still costs its eleven launches (~30 us): the first chunk
-    // of a stage is the number of trials the stage cannot do without (one per iteration in the robust stage; three in the
-    // final one, whose "no progress three times" rule can end it that early), the chunks after it are single slots.
-    // (Chunks of two throughout queued 20 slots for the 14 trials of a window-8 solve.)
-    t_queue = tclk();
-    BaState* hs[2] = {reinterpret_cast<BaState*>(h->h_pin + st_off), reinterpret_cast<BaState*>(h->h_pin + st_off) + nwin};
-    bool stopped = opts->stop && *opts->stop;  // :655-657
-    size_t pev_used = 0;   // profiling solves: six events per queued slot
-    auto slot_events = [&]() -> hipEvent_t* {
-        if (!h->prof) return nullptr;
-        while (h->pev.size() < pev_used + 6) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return nullptr;
-            h->pev.push_back(e);
-        }
-        pev_used += 6;
-        return h->pev.data() + pev_used - 6;
-    };
-    for (int stage = 0; stage < 2 && !stopped; ++stage) {
-        const int its = stage == 0 ? opts->its_robust : opts->its_final;
-        bak_stage_begin(st, h->d_wins, nwin, me, stage, its, stage == 0 ? 1 : 0, stage == 1);
-        int budget = its * 10 + 1;  // at most 10 LM trials per iteration
-        int cur = 0, pending = -1;
-        bool all_done = false, first = true;
-        while (!all_done) {
-            if (opts->stop && *opts->stop) { stopped = true; break; }
-            if (budget > 0) {
-                const int want = first ? std::max(1, std::min(stage == 0 ? its : 3, std::min(its, 4))) : 1;
-                const int nslots = std::min(want, budget);
-                const bool was_first = first;
-                first = false;
-                for (int sl = 0; sl < nslots; ++sl)
-                    bak_slot(st, h->d_wins, nwin, mk, mp, me, Npad, Npad_ldlt, tl_grid.data(), (int)tl_grid.size() / 2, was_first && sl == 0, solvers, slot_events());
-                budget -= nslots;
-                HIP_TRY(hipMemcpyAsync(hs[cur], reinterpret_cast<BaState*>(h->d_wins) - nwin, sizeof(BaState) * nwin, hipMemcpyDeviceToHost, st));   // (reverse order: only `done` of all is read)
-                HIP_TRY(hipEventRecord(h->ev[cur], st));
-            }
-            if (pending >= 0) {
-                HIP_TRY(hipEventSynchronize(h->ev[pending]));
-                all_done = true;
-                for (int b = 0; b < nwin; ++b) all_done = all_done && hs[pending][b].done;
-            }
-            if (budget <= 0 && pending == cur) break;   // nothing new was queued: the last read-back has been looked at
-            pending = cur;
-            if (budget > 0) cur ^= 1;
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    t_loop = tclk();
-    // ---- results: one copy per window out of its output section ----
-    bak_final(st, h->d_wins, h->d_io, nwin, mk, mp, me);
-    for (int b = 0; b < nwin; ++b)
-        HIP_TRY(hipMemcpyAsync(h->h_pin + out_off[b], h->d_slab + (size_t)b * h->win_bytes + dio[b].out_off, dio[b].bytes - dio[b].out_off,
-                               hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (h->prof) {
-        slamit_ba_profile_out& O = h->prof_last;
-        memset(&O, 0, sizeof(O));
-        O.nwin = nwin; O.slots = (int32_t)(pev_used / 6);
-        for (size_t s0 = 0; s0 + 6 <= pev_used; s0 += 6)
-            for (int ph = 0; ph < SLAMIT_BA_PHASES; ++ph) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, h->pev[s0 + ph], h->pev[s0 + ph + 1]) == hipSuccess) O.phase_ms[ph] += ms;
-            }
-        for (int b = 0; b < nwin; ++b) O.schur_exec_mflop += plans[b].exec_mflop;
-    }
-    auto unpack = [&](int b) {
-        const slamit_ba_problem& P = probs[b];
-        // the output section as the host sees it: same carve, shifted so that its output part starts at out_off[b]
-        const IoLayout H = carve_io(h->h_pin + out_off[b] - dio[b].out_off, P.n_kf, P.n_pt, P.n_edge, P.edge_ur != nullptr, side_w[b]);
-        ba_unpack_outputs(P, plans[b], H, results[b]);
-        const BaState& S0 = *H.out_state;
-        if (b == 0 && h->sw.ba_diag_waves) fprintf(stderr, "[ba diag] busy cycles of waves 0..7: %llu %llu %llu %llu %llu %llu %llu %llu\n", S0.dbg[0], S0.dbg[1], S0.dbg[2], S0.dbg[3], S0.dbg[4], S0.dbg[5], S0.dbg[6], S0.dbg[7]);
-        if (b == 0 && h->sw.ba_diag) {  // diagnostic builds only: in-kernel clock and phases of the last LDLt launch
-            fprintf(stderr, "[ba diag] ldlt shader cycles %llu, realtime ticks (100 MHz) %llu -> %.0f MHz, %.1f us\n",
-                    S0.dbg[2] - S0.dbg[0], S0.dbg[3] - S0.dbg[1],
-                    100.0 * (double)(S0.dbg[2] - S0.dbg[0]) / (double)(S0.dbg[3] - S0.dbg[1] + 1), (double)(S0.dbg[3] - S0.dbg[1]) / 100.0);
-            fprintf(stderr, "[ba diag] ldlt phase cycles: load %llu factor %llu rows %llu writeback / wave-0 busy %llu trailing / rhs-wave busy %llu backsub %llu, pivot-wave busy %llu\n",
-                    S0.dbg[4] >> 32, S0.dbg[4] & 0xffffffffull, S0.dbg[5] >> 32, S0.dbg[5] & 0xffffffffull, S0.dbg[6] >> 32, S0.dbg[6] & 0xffffffffull, S0.dbg[7]);
-        }
-    };
-    for_each_window(nwin, nwin >= 4, unpack);   // by the host threads that prepared the windows (nothing in it throws)
-    if (h->sw.ba_timing) {   // diagnostic: host phases of the call on stderr
-        const double t_out = tclk();
-        fprintf(stderr, "[ba timing] %d windows: validate %.3f | prepare + pack %.3f | queue uploads %.3f | LM loop %.3f | download + unpack %.3f ms\n",
-                nwin, t_val - t_in, t_prep - t_val, t_queue - t_prep, t_loop - t_queue, t_out - t_loop);
-    }
-    return SLAMIT_OK;
 }
 
 int slamit_ba_solve(slamit_ba* h, const slamit_ba_problem* prob, const slamit_ba_opts* opts, slamit_ba_result* res) {

@@ -33,6 +33,7 @@
 #include "slamit_internal.h"
 #define BA_GLOBAL_POINTERS   // BaWin members are SLAMIT_GLOBAL pointers in this file's device code
 #include "ba_types.h"
+#include "ba_plan.h"   // BaBatchPlan: what the launch wrappers size their grids by
 #include "lm_step.h"
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
@@ -1895,16 +1896,18 @@ hipError_t bak_prepare(int Npad) {
     return e;
 }
 
-void bak_import(hipStream_t st, BaWin* wins, const BaIo* io, int max_kf, int max_pt, int max_edge, int Npad, int nwin) {
-    const int nb = std::max(std::max(max_edge, 3 * max_pt), std::max(max_kf, (int)(sizeof(BaState) / 8)));
-    hipLaunchKernelGGL(k_import, dim3((nb + 255) / 256, nwin), dim3(256), 0, st, wins, io);
-    hipLaunchKernelGGL(k_zero_operands, dim3(64, Npad / BA_TILE, nwin), dim3(256), 0, st, wins);
+void bak_import(hipStream_t st, BaWin* wins, const BaIo* io, const BaBatchPlan& B) {
+    const int nb = std::max(std::max(B.me, 3 * B.mp), std::max(B.mk, (int)(sizeof(BaState) / 8)));
+    hipLaunchKernelGGL(k_import, dim3((nb + 255) / 256, B.nwin), dim3(256), 0, st, wins, io);
+    hipLaunchKernelGGL(k_zero_operands, dim3(64, B.Npad / BA_TILE, B.nwin), dim3(256), 0, st, wins);
 }
 
-void bak_stage_begin(hipStream_t st, BaWin* wins, int nwin, int max_edge, int stage, int max_it, int robust, bool gate) {
-    const dim3 ge((max_edge + 255) / 256, nwin);
-    if (gate) hipLaunchKernelGGL(k_gate, ge, dim3(256), 0, st, wins);
-    hipLaunchKernelGGL(k_stage_begin, dim3(1, nwin), dim3(256), 0, st, wins, stage, max_it, robust);
+// (the robust stage, 0, runs with the Huber kernel; the final one, 1, first gates the edges by their chi2)
+void bak_stage_begin(hipStream_t st, BaWin* wins, const BaBatchPlan& B, int stage, int max_it) {
+    const int nwin = B.nwin;
+    const dim3 ge((B.me + 255) / 256, nwin);
+    if (stage == 1) hipLaunchKernelGGL(k_gate, ge, dim3(256), 0, st, wins);
+    hipLaunchKernelGGL(k_stage_begin, dim3(1, nwin), dim3(256), 0, st, wins, stage, max_it, stage == 0 ? 1 : 0);
     hipLaunchKernelGGL(k_errors, ge, dim3(256), 0, st, wins);
     hipLaunchKernelGGL(k_stage_begin2, dim3(1, nwin), dim3(256), 0, st, wins);
 }
@@ -1915,11 +1918,11 @@ void bak_stage_begin(hipStream_t st, BaWin* wins, int nwin, int max_edge, int st
 // instead of 11)
 // `ev` (profiling solves only, slamit_ba_profile): six events recorded at the phase boundaries of the slot -- before the
 // linearisation, after it, after the Schur complement, after the reduced solve, after the update, after residuals + decision
-// `Npad`: the batch's largest system (grids of the Schur product and its reduction); `Npad_ldlt`: the largest among the windows of the
-// LDS-resident solves (their dynamic LDS, <= BA_BLOCKED_MAX_NPAD); `tl_grid`: per panel step of the tiled solve {panel, update} workgroups
-void bak_slot(hipStream_t st, BaWin* wins, int nwin, int max_kf, int max_pt, int max_edge, int Npad, int Npad_ldlt, const int* tl_grid, int tl_npanel,
-              bool first, unsigned solvers, hipEvent_t* ev) {
-    const int nsplit = bak_nsplit(nwin);
+// `B`: the batch's launch maxima (BaBatchPlan, ba_plan.h)
+void bak_slot(hipStream_t st, BaWin* wins, const BaBatchPlan& B, bool first, hipEvent_t* ev) {
+    const int nwin = B.nwin, max_kf = B.mk, max_pt = B.mp, max_edge = B.me, Npad = B.Npad, Npad_ldlt = B.Npad_ldlt, nsplit = bak_nsplit(nwin);
+    const unsigned solvers = B.solvers;
+    const std::vector<int>& tl_grid = B.tl_grid;
     const dim3 ge((max_edge + 255) / 256, nwin), gp((max_pt * BA_PG + 255) / 256, nwin);
     if (ev) (void)hipEventRecord(ev[0], st);
     if (first) {
@@ -1951,7 +1954,7 @@ void bak_slot(hipStream_t st, BaWin* wins, int nwin, int max_kf, int max_pt, int
     if (solvers & (1u << BA_SOLVER_BLOCKED)) hipLaunchKernelGGL(k_ldlt_blocked, dim3(1, nwin), dim3(LD_THREADS), bak_ldlt_smem(Npad_ldlt), st, wins);
     if (solvers & (1u << BA_SOLVER_TILED)) {
         hipLaunchKernelGGL(k_ldlt_tiled_begin, dim3(8, nwin), dim3(256), 0, st, wins);
-        for (int i = 0; i < tl_npanel; ++i) {
+        for (int i = 0; i < (int)tl_grid.size() / 2; ++i) {
             if (tl_grid[2 * i] > 0) hipLaunchKernelGGL(k_ldlt_tiled_panel, dim3(tl_grid[2 * i], nwin), dim3(LD_THREADS), 0, st, wins, i);
             if (tl_grid[2 * i + 1] > 0) hipLaunchKernelGGL(k_ldlt_tiled_update, dim3(tl_grid[2 * i + 1], nwin), dim3(256), 0, st, wins, i);
         }
@@ -1966,7 +1969,7 @@ void bak_slot(hipStream_t st, BaWin* wins, int nwin, int max_kf, int max_pt, int
     if (ev) (void)hipEventRecord(ev[5], st);
 }
 
-void bak_final(hipStream_t st, BaWin* wins, const BaIo* io, int nwin, int max_kf, int max_pt, int max_edge) {
-    const int nb = std::max(std::max(max_edge, 3 * max_pt), std::max(max_kf, (int)(sizeof(BaState) / 8)));
-    hipLaunchKernelGGL(k_final, dim3((nb + 255) / 256, nwin), dim3(256), 0, st, wins, io);
+void bak_final(hipStream_t st, BaWin* wins, const BaIo* io, const BaBatchPlan& B) {
+    const int nb = std::max(std::max(B.me, 3 * B.mp), std::max(B.mk, (int)(sizeof(BaState) / 8)));
+    hipLaunchKernelGGL(k_final, dim3((nb + 255) / 256, B.nwin), dim3(256), 0, st, wins, io);
 }

@@ -385,3 +385,63 @@ void ba_unpack_outputs(const slamit_ba_problem& P, const BaWindowPlan& plan, con
         for (int i = 0; i < SLAMIT_BA_MAX_ITS; ++i) { S->chi2[sg][i] = S0.chi2[sg][i]; S->lambda[sg][i] = S0.lam[sg][i]; S->trials[sg][i] = S0.trials[sg][i]; }
     }
 }
+
+// ---- a batch of windows ----
+
+BaRefusal ba_batch_check(const slamit_ba_problem* probs, const slamit_ba_result* results, int nwin, const BaCaps& caps) {
+    if (!probs || !results || nwin < 0) return {SLAMIT_ERR_ARG, "slamit_ba_solve_batch: bad argument"};
+    if (nwin > caps.max_batch) return {SLAMIT_ERR_CAPACITY, "slamit_ba_solve_batch: nwin > max_batch"};
+    for (int b = 0; b < nwin; ++b) {
+        const slamit_ba_problem& P = probs[b];
+        if (P.n_kf < 1 || P.n_pt < 0 || P.n_edge < 0 || P.n_kf > caps.max_kf || P.n_pt > caps.max_pt || P.n_edge > caps.max_edge)
+            return {SLAMIT_ERR_CAPACITY, "slamit_ba_solve_batch: window exceeds the handle's capacity"};
+        if (!P.kf_pose || !P.kf_fixed || !P.kf_intr || (P.n_pt && !P.pt_xyz) ||
+            (P.n_edge && (!P.edge_kf || !P.edge_pt || !P.edge_uv || !P.edge_inv_sigma2)))
+            return {SLAMIT_ERR_ARG, "slamit_ba_solve_batch: null input array"};
+        int nfree = 0;
+        for (int k = 0; k < P.n_kf; ++k) nfree += P.kf_fixed[k] ? 0 : 1;
+        if (nfree > caps.max_free_kf)
+            return {SLAMIT_ERR_CAPACITY, "slamit_ba_solve_batch: window has more free keyframes than the handle's max_free_kf"};
+        if (P.edge_ur && !P.kf_bf)
+            return {SLAMIT_ERR_ARG, "slamit_ba_solve_batch: stereo observations (edge_ur) without the keyframes' bf (kf_bf)"};
+        if (!results[b].kf_pose || (P.n_pt && !results[b].pt_xyz))
+            return {SLAMIT_ERR_ARG, "slamit_ba_solve_batch: null output array"};
+    }
+    return {SLAMIT_OK, nullptr};
+}
+
+void ba_batch_layout(const slamit_ba_problem* probs, int nwin, size_t win_bytes, uint8_t* slab, BaBatchPlan& B) {
+    B.nwin = nwin;
+    B.side_w.resize(nwin); B.dio.resize(nwin); B.in_off.resize(nwin); B.out_off.resize(nwin);
+    B.mk = B.mp = B.me = 1;
+    size_t off = 0;
+    for (int b = 0; b < nwin; ++b) {
+        const slamit_ba_problem& P = probs[b];
+        B.mk = std::max(B.mk, P.n_kf); B.mp = std::max(B.mp, P.n_pt); B.me = std::max(B.me, P.n_edge);
+        B.side_w[b] = ba_io_side_words(P);
+        B.dio[b] = carve_io(slab ? slab + (size_t)b * win_bytes : nullptr, P.n_kf, P.n_pt, P.n_edge, P.edge_ur != nullptr, B.side_w[b]);
+        B.in_off[b] = off; off += B.dio[b].in_bytes;
+    }
+    for (int b = 0; b < nwin; ++b) { B.out_off[b] = off; off += B.dio[b].bytes - B.dio[b].out_off; }
+    B.st_off = ba_rup(off, 256);
+    B.pin_need = B.st_off + 2 * sizeof(BaState) * (size_t)nwin;
+    B.Npad = B.Npad_ldlt = BA_TILE; B.solvers = 0; B.tl_grid.clear();
+}
+
+void ba_batch_launches(const BaWin* wins, const BaWindowPlan* plans, BaBatchPlan& B) {
+    B.Npad = B.Npad_ldlt = BA_TILE; B.solvers = 0; B.tl_grid.clear();
+    for (int b = 0; b < B.nwin; ++b) {
+        B.Npad = std::max(B.Npad, wins[b].Npad);
+        B.solvers |= 1u << wins[b].solver;
+        if (wins[b].solver != BA_SOLVER_TILED) { B.Npad_ldlt = std::max(B.Npad_ldlt, wins[b].Npad); continue; }
+        BaWin wh = wins[b];
+        wh.side = plans[b].side.data();   // (ba_panel_hi reads the host copy of the side table)
+        const int n = wh.nS, np = (n + 31) / 32;
+        if ((int)B.tl_grid.size() < 2 * np) B.tl_grid.resize(2 * np, 0);
+        for (int i = 0; i < np; ++i) {
+            const int base = std::min(32 * i + 32, n), below = std::max(ba_panel_hi(wh, i) + 1 - base, 0);
+            B.tl_grid[2 * i] = std::max(B.tl_grid[2 * i], (below + 1 + BA_TL_CHUNK - 1) / BA_TL_CHUNK);
+            B.tl_grid[2 * i + 1] = std::max(B.tl_grid[2 * i + 1], ldlt_tiled_ntiles(below));
+        }
+    }
+}

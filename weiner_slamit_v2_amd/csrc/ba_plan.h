@@ -1,6 +1,7 @@
 // ba_plan.h — host-side planning of one local-BA window: how it is laid out on the device (column and point order, the Schur
-// product's k ranges and floating-window groups, the LDLt row envelope and solver), and how its inputs and outputs are packed.
-// Plain C++17 (no HIP): the solve (ba_api.hip) and the CPU test of the plan (tests/test_ba_plan.py) both build it.
+// product's k ranges and floating-window groups, the LDLt row envelope and solver), and how its inputs and outputs are packed; and of a
+// batch of them (BaBatchPlan: the windows' places in the slabs and the pinned block, the launch maxima, the checks that refuse a batch).
+// Plain C++17 (no HIP): the solve (ba_api.hip) and the CPU tests of the plan (tests/test_ba_plan.py, test_ba_batch_plan.py) both build it.
 #ifndef SLAMIT_BA_PLAN_H
 #define SLAMIT_BA_PLAN_H
 
@@ -77,5 +78,47 @@ void ba_pack_inputs(const slamit_ba_problem& P, const BaWindowPlan& plan, const 
 
 // The output part of H back to the caller: poses, points in the caller's order, the edge arrays R asks for, and R.stats from the LM state.
 void ba_unpack_outputs(const slamit_ba_problem& P, const BaWindowPlan& plan, const IoLayout& H, slamit_ba_result& R);
+
+// ---- a batch of windows ----
+
+// The capacities of a handle that a batch is checked against.
+struct BaCaps {
+    int max_kf, max_free_kf, max_pt, max_edge, max_batch;
+};
+
+// A refused batch: the code slamit_ba_solve_batch returns and the text slamit_last_error gives (code SLAMIT_OK, msg null: accepted).
+struct BaRefusal {
+    int code;
+    const char* msg;
+};
+
+// Every check of a batch that does not touch the device: the arrays are there, the batch and each window fit the handle, stereo
+// observations come with their bf.  (The edges' indices are checked by ba_plan_window, before anything is packed.)
+BaRefusal ba_batch_check(const slamit_ba_problem* probs, const slamit_ba_result* results, int nwin, const BaCaps& caps);
+
+// What a batch needs beyond its windows: where each window sits in the device slabs and in the pinned block
+//   [inputs of window 0 | inputs of window 1 | ...][outputs ...][2 x nwin LM states, on a 256-byte boundary]
+// and the maxima its launches are sized by (the grids themselves: ba_kernels.hip).
+struct BaBatchPlan {
+    int nwin;
+    // ba_batch_layout
+    std::vector<size_t> side_w;     // per window: ba_io_side_words
+    std::vector<IoLayout> dio;      // its io section at its device address
+    std::vector<size_t> in_off;     // its packed inputs in the pinned block (dio.in_bytes of them)
+    std::vector<size_t> out_off;    // its outputs there (dio.bytes - dio.out_off)
+    size_t st_off;                  // the two buffers of LM states
+    size_t pin_need;                // bytes of the pinned block
+    int mk, mp, me;                 // largest n_kf, n_pt, n_edge (>= 1)
+    // ba_batch_launches
+    int Npad;                       // largest reduced system (grids of the Schur product and its reduction)
+    int Npad_ldlt;                  // largest among the windows of the LDS-resident solves (their dynamic LDS, <= BA_BLOCKED_MAX_NPAD)
+    unsigned solvers;               // bit BA_SOLVER_* set when a window takes that reduced solve
+    std::vector<int> tl_grid;       // per panel step of the tiled solve {k_ldlt_tiled_panel, k_ldlt_tiled_update} workgroups: the largest need among its windows
+};
+
+// Before the windows are planned.  `slab`: the device address of window 0's slab, one every `win_bytes` (null: sizes and offsets only).
+void ba_batch_layout(const slamit_ba_problem* probs, int nwin, size_t win_bytes, uint8_t* slab, BaBatchPlan& B);
+// After: from the planned windows and their host side tables (BaWindowPlan::side; wins[b].side itself may point anywhere).
+void ba_batch_launches(const BaWin* wins, const BaWindowPlan* plans, BaBatchPlan& B);
 
 #endif
