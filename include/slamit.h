@@ -779,6 +779,117 @@ typedef struct slamit_frustum_batch_rec {
 } slamit_frustum_batch_rec;
 int slamit_frustum_batch_dev(int device, const slamit_frustum_batch_rec* batch, void* stream);
 
+/* ---- The projections in front of the guided search: the other six ORBmatcher drivers ----
+ * World -> camera, the depth, bounds, distance and viewing-angle gates, MapPoint::PredictScale and the window radius of
+ *   form 0 LAST_FRAME  SearchByProjection(CurrentFrame, LastFrame, th, bMono)   src/ORBmatcher.cc:1332-1474
+ *        1 RELOC       SearchByProjection(CurrentFrame, pKF, sAlreadyFound, ..) :1476-1603
+ *        2 FUSE        Fuse(pKF, vpMapPoints, th)                               :829-979
+ *        3 SIM3_PROJ   SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)    :293-407
+ *        4 SIM3_FUSE   Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)             :981-1100
+ *        5 SIM3_PAIR   SearchBySim3, one direction                              :1102-1330
+ * float / double exactly where the loops of shim/ORBmatcher.h have them (csrc/project.h restates them and lists every split).  One
+ * lane per point, a batch of cameras per launch; the problems of a batch may differ in form.  status[i] is the first test that
+ * rejected point i:  0 accepted  1 skipped by the caller  2 depth  3 u outside  4 v outside  5 distance  6 viewing angle
+ * 7 level outside the table (the departure of slamit_frustum: no query, level = INT32_MIN, whether the level was predicted or
+ * given as an octave).  proj[2i..] = u, v; level[i]; fields the walk did not reach are zero.  The query arrays are
+ * slamit_search_queries' own, NOT compacted: query i is point i, valid = 1 for status 0, zeros otherwise.
+ * The camera record is computed on the host, once per camera, as the shim computes it.  Monocular: no uR, no `er` gate.
+ * Arrays a form does not read may be NULL in the host form: normal is read by forms 2, 3, 4; max_dist / min_dist by all but form
+ * 0; octave by form 0 only.  n above SLAMIT_PROJECT_MAX_N, an unknown form or direction, n_levels outside [1, SLAMIT_MAX_LEVELS]
+ * or a missing array with n > 0 fails with SLAMIT_ERR_ARG and a message before anything is launched; n == 0 and nproblems == 0
+ * are valid and write nothing but n_valid = 0. */
+#define SLAMIT_PROJECT_MAX_N 65536
+enum { SLAMIT_PROJECT_LAST_FRAME = 0, SLAMIT_PROJECT_RELOC = 1, SLAMIT_PROJECT_FUSE = 2, SLAMIT_PROJECT_SIM3_PROJ = 3,
+       SLAMIT_PROJECT_SIM3_FUSE = 4, SLAMIT_PROJECT_SIM3_PAIR = 5 };
+
+typedef struct slamit_project_camera {
+    int32_t form;                  /* SLAMIT_PROJECT_* */
+    float R[9], t[3], O[3];        /* world -> camera, row-major, and the camera centre; form 5: the pose of the keyframe the points come from */
+    float R2[9], t2[3];            /* form 5: the similarity into the searched camera (sR21, t21 or sR12, t12) */
+    float fx, fy, cx, cy;
+    float min_x, max_x, min_y, max_y; /* mnMinX .. mnMaxY */
+    float log_scale_factor;        /* mfLogScaleFactor */
+    float th;                      /* the driver's th: the radius is th * scale_factors[level] */
+    int32_t n_levels;
+    float scale_factors[SLAMIT_MAX_LEVELS];
+    int32_t direction;             /* form 0: 0 = levels l-1..l+1, 1 (forward) = l.., 2 (backward) = 0..l */
+} slamit_project_camera;
+
+typedef struct slamit_project_problem {
+    slamit_project_camera camera;
+    int32_t n;
+    const float* pos;              /* n x 3: GetWorldPos() */
+    const float* normal;           /* n x 3: GetNormal() */
+    const float* max_dist;         /* n: the RAW mfMaxDistance */
+    const float* min_dist;         /* n: the raw mfMinDistance */
+    const int32_t* octave;         /* n: LastFrame.mvKeys[i].octave */
+    const uint8_t* skip;           /* n: 1 = the driver's own `continue` before the projection (null, bad, outlier, already found) */
+} slamit_project_problem;
+
+typedef struct slamit_project_result {
+    uint8_t* status;               /* n out */
+    float* proj;                   /* n x 2 out: u, v */
+    int32_t* level;                /* n out */
+    float* uvr;                    /* n x 3 out: slamit_search_queries.uvr */
+    int32_t* level_min;            /* n out */
+    int32_t* level_max;            /* n out */
+    uint8_t* valid;                /* n out */
+    int32_t n_valid;               /* out: points with status 0 */
+} slamit_project_result;
+
+/* nproblems cameras in one launch (host pointers, synchronous). */
+int slamit_project_batch(int device, int nproblems, const slamit_project_problem* probs, slamit_project_result* results);
+int slamit_project(int device, const slamit_project_problem* prob, slamit_project_result* res);
+
+/* Everything resident in HBM, in slamit_frustum_batch_dev's conventions: frame f has d_m[f] points (clamped to [0, q_cap]; entries
+ * past it are neither read nor written), the point arrays are PLANES [nframes][3][q_cap], the four query arrays are the ones
+ * slamit_search_batch reads.  The host cannot see d_cameras: all six input arrays must be present whatever the forms, a level is
+ * accepted only below min(n_levels, SLAMIT_MAX_LEVELS), and a form outside 0..5 makes every point of that frame status 1.
+ * Asynchronous on `stream`, no synchronisation, no state. */
+typedef struct slamit_project_batch_rec {
+    int32_t nframes, q_cap;
+    const slamit_project_camera* d_cameras; /* [nframes] */
+    const int32_t* d_m;            /* [nframes] points per frame */
+    const float* d_pos;            /* [nframes][3][q_cap] */
+    const float* d_normal;         /* [nframes][3][q_cap] */
+    const float* d_max_dist;       /* [nframes][q_cap] */
+    const float* d_min_dist;       /* [nframes][q_cap] */
+    const int32_t* d_octave;       /* [nframes][q_cap] */
+    const uint8_t* d_skip;         /* [nframes][q_cap] */
+    float* d_uvr;                  /* [nframes][q_cap][3] out */
+    int32_t* d_level_min;          /* [nframes][q_cap] out */
+    int32_t* d_level_max;          /* [nframes][q_cap] out */
+    uint8_t* d_valid;              /* [nframes][q_cap] out */
+    uint8_t* d_status;             /* [nframes][q_cap] out, nullable */
+    float* d_proj;                 /* [nframes][q_cap][2] out, nullable */
+    int32_t* d_level;              /* [nframes][q_cap] out, nullable */
+    int32_t* d_n_valid;            /* [nframes] out, nullable */
+} slamit_project_batch_rec;
+int slamit_project_batch_dev(int device, const slamit_project_batch_rec* batch, void* stream);
+
+/* The rotation-consistency check of the searches that follow a projection (src/ORBmatcher.cc:1430-1471, ComputeThreeMaxima
+ * :1605-1646) on what slamit_guided_search_batch_dev left in HBM, one wavefront per frame.  The queries of frame f are walked in
+ * order; a query q matched to keypoint k = d_match_kp[f][q] makes d_kp_query[f][k] = q (a later query overwrites an earlier one:
+ * that happens when the earlier point had takes = 0) and enters the histogram: rot = d_qangle[f][q] - d_kps_un[f][k].angle,
+ * + 360 when negative, bin = (int)roundf(rot * (1.0f / 30)), 30 -> 0, an entry outside [0, 30) is dropped.  Then every entry of a
+ * bin that is not one of the three maxima (the first bin on ties; the second and third fall when below 10 % of the first, in
+ * float) sets d_kp_query[f][k] = -1 and takes 1 from d_nmatches[f], once per ENTRY as the reference does.
+ * d_kp_query [nframes][kp_cap] out: the query that owns keypoint k (CurrentFrame.mvpMapPoints[k]) or -1; d_nmatches [nframes] in /
+ * out; d_bins [nframes][3] out: the three maxima, -1 for none.  A match outside [0, min(d_n[f], kp_cap)) is ignored.
+ * Asynchronous on `stream`, no synchronisation, no state; the result does not depend on scheduling. */
+typedef struct slamit_rotation_batch {
+    int32_t nframes, kp_cap, q_cap;
+    const int32_t* d_n;            /* [nframes] keypoints per frame */
+    const slamit_kp* d_kps_un;     /* [nframes][kp_cap] (angle is read) */
+    const int32_t* d_m;            /* [nframes] queries per frame */
+    const int32_t* d_match_kp;     /* [nframes][q_cap] */
+    const float* d_qangle;         /* [nframes][q_cap]: LastFrame.mvKeysUn[q].angle */
+    int32_t* d_kp_query;           /* [nframes][kp_cap] out */
+    int32_t* d_nmatches;           /* [nframes] in / out */
+    int32_t* d_bins;               /* [nframes][3] out */
+} slamit_rotation_batch;
+int slamit_rotation_check_batch_dev(int device, const slamit_rotation_batch* batch, void* stream);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 
 const char* slamit_last_error(void);

@@ -159,6 +159,44 @@ FRUSTUM_FRAME_DTYPE = np.dtype([("Rcw", "<f4", 9), ("tcw", "<f4", 3), ("Ow", "<f
                                 ("log_scale_factor", "<f4"), ("th", "<f4"), ("n_levels", "<i4"), ("scale_factors", "<f4", 16)])   # slamit_frustum_frame
 
 
+class ProjectCamera(C.Structure):
+    _fields_ = [("form", C.c_int32), ("R", C.c_float * 9), ("t", C.c_float * 3), ("O", C.c_float * 3), ("R2", C.c_float * 9), ("t2", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float),
+                ("min_y", C.c_float), ("max_y", C.c_float), ("log_scale_factor", C.c_float), ("th", C.c_float), ("n_levels", C.c_int32),
+                ("scale_factors", C.c_float * 16), ("direction", C.c_int32)]
+
+
+class ProjectProblem(C.Structure):
+    _fields_ = [("camera", ProjectCamera), ("n", C.c_int32), ("pos", C.c_void_p), ("normal", C.c_void_p), ("max_dist", C.c_void_p),
+                ("min_dist", C.c_void_p), ("octave", C.c_void_p), ("skip", C.c_void_p)]
+
+
+class ProjectResult(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("proj", C.c_void_p), ("level", C.c_void_p), ("uvr", C.c_void_p), ("level_min", C.c_void_p),
+                ("level_max", C.c_void_p), ("valid", C.c_void_p), ("n_valid", C.c_int32)]
+
+
+class ProjectBatchRec(C.Structure):
+    _fields_ = [("nframes", C.c_int32), ("q_cap", C.c_int32), ("d_cameras", C.c_void_p), ("d_m", C.c_void_p), ("d_pos", C.c_void_p),
+                ("d_normal", C.c_void_p), ("d_max_dist", C.c_void_p), ("d_min_dist", C.c_void_p), ("d_octave", C.c_void_p), ("d_skip", C.c_void_p),
+                ("d_uvr", C.c_void_p), ("d_level_min", C.c_void_p), ("d_level_max", C.c_void_p), ("d_valid", C.c_void_p), ("d_status", C.c_void_p),
+                ("d_proj", C.c_void_p), ("d_level", C.c_void_p), ("d_n_valid", C.c_void_p)]
+
+
+class RotationBatch(C.Structure):
+    _fields_ = [("nframes", C.c_int32), ("kp_cap", C.c_int32), ("q_cap", C.c_int32), ("d_n", C.c_void_p), ("d_kps_un", C.c_void_p),
+                ("d_m", C.c_void_p), ("d_match_kp", C.c_void_p), ("d_qangle", C.c_void_p), ("d_kp_query", C.c_void_p), ("d_nmatches", C.c_void_p),
+                ("d_bins", C.c_void_p)]
+
+
+PROJECT_MAX_N = 65536   # SLAMIT_PROJECT_MAX_N
+PROJECT_FORMS = ("LAST_FRAME", "RELOC", "FUSE", "SIM3_PROJ", "SIM3_FUSE", "SIM3_PAIR")   # SLAMIT_PROJECT_*: the index is the form
+PROJECT_CAMERA_DTYPE = np.dtype([("form", "<i4"), ("R", "<f4", 9), ("t", "<f4", 3), ("O", "<f4", 3), ("R2", "<f4", 9), ("t2", "<f4", 3), ("fx", "<f4"),
+                                 ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("min_x", "<f4"), ("max_x", "<f4"), ("min_y", "<f4"), ("max_y", "<f4"),
+                                 ("log_scale_factor", "<f4"), ("th", "<f4"), ("n_levels", "<i4"), ("scale_factors", "<f4", 16),
+                                 ("direction", "<i4")])   # slamit_project_camera
+
+
 class VocDesc(C.Structure):
     _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring", C.c_int32), ("weighting", C.c_int32), ("n_nodes", C.c_int32),
                 ("parent", C.c_void_p), ("is_leaf", C.c_void_p), ("desc", C.c_void_p), ("weight", C.c_void_p)]
@@ -210,7 +248,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_rotation_check_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -263,6 +301,10 @@ def lib():
         L.slamit_frustum_batch.argtypes = [i32, i32, C.POINTER(FrustumProblem), C.POINTER(FrustumResult)]
         L.slamit_frustum.argtypes = [i32, C.POINTER(FrustumProblem), C.POINTER(FrustumResult)]
         L.slamit_frustum_batch_dev.argtypes = [i32, C.POINTER(FrustumBatchRec), vp]
+        L.slamit_project_batch.argtypes = [i32, i32, C.POINTER(ProjectProblem), C.POINTER(ProjectResult)]
+        L.slamit_project.argtypes = [i32, C.POINTER(ProjectProblem), C.POINTER(ProjectResult)]
+        L.slamit_project_batch_dev.argtypes = [i32, C.POINTER(ProjectBatchRec), vp]
+        L.slamit_rotation_check_batch_dev.argtypes = [i32, C.POINTER(RotationBatch), vp]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
         L.slamit_voc_load_text.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
@@ -607,6 +649,20 @@ class ORBmatcher:
     @staticmethod
     def guided_search_workspace(nframes, q_cap):
         return int(lib().slamit_guided_search_workspace(nframes, q_cap))
+
+    @staticmethod
+    def rotation_check_batch_dev(t, device=0, stream=None):
+        """The rotation-consistency check of SearchByProjection(CurrentFrame, LastFrame, ...) (ORBmatcher.cc:1430-1471) on what
+        guided_search_batch_dev left on the device.  t: its tensors n (B) i32, kps_un (B, kp_cap, 7) f32, m (B) i32, match_kp
+        (B, q_cap) i32, nmatches (B) i32 (updated in place), plus qangle (B, q_cap) f32 (the query keypoints' angles) and the outputs
+        kp_query (B, kp_cap) i32 (the query that owns each keypoint, or -1) and bins (B, 3) i32.  Asynchronous on `stream`."""
+        b, kp_cap, q_cap = t["kps_un"].shape[0], t["kps_un"].shape[1], t["match_kp"].shape[1]
+        for key, count in (("n", b), ("m", b), ("nmatches", b), ("bins", 3 * b), ("match_kp", b * q_cap), ("qangle", b * q_cap), ("kp_query", b * kp_cap)):
+            if t[key].numel() != count or not t[key].is_contiguous():
+                raise SlamitError("rotation_check_batch_dev: %s is not a contiguous array of %d entries" % (key, count))
+        rec = RotationBatch(b, kp_cap, q_cap, t["n"].data_ptr(), t["kps_un"].data_ptr(), t["m"].data_ptr(), t["match_kp"].data_ptr(),
+                            t["qangle"].data_ptr(), t["kp_query"].data_ptr(), t["nmatches"].data_ptr(), t["bins"].data_ptr())
+        _check(lib().slamit_rotation_check_batch_dev(device, C.byref(rec), stream), "slamit_rotation_check_batch_dev")
 
     @staticmethod
     def search_for_initialization(f1, prev_xy, f2, window=100, nnratio=0.9, th_low=50, device=0):
@@ -1425,3 +1481,101 @@ def frustum_batch_dev(t, device=0, stream=None):
                           t["min_dist"].data_ptr(), t["skip"].data_ptr(), t["uvr"].data_ptr(), t["level_min"].data_ptr(), t["level_max"].data_ptr(),
                           t["valid"].data_ptr(), opt("status"), opt("proj"), opt("view_cos"), opt("level"), opt("n_in_view"))
     _check(lib().slamit_frustum_batch_dev(device, C.byref(rec), stream), "slamit_frustum_batch_dev")
+
+
+_PROJECT_SCALARS = ("fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y", "log_scale_factor", "th")
+
+
+def project_camera_record(pr):
+    """The slamit_project_camera of a problem dict as a one-element numpy record array (PROJECT_CAMERA_DTYPE): what
+    project_batch_dev's d_cameras holds per frame.  form is an index into PROJECT_FORMS or one of its names; R2 / t2 (SIM3_PAIR) and
+    direction (LAST_FRAME) default to zero."""
+    rec = np.zeros(1, PROJECT_CAMERA_DTYPE)
+    form = pr["form"]
+    rec["form"][0] = PROJECT_FORMS.index(form) if isinstance(form, str) else int(form)
+    for key, k in (("R", 9), ("t", 3), ("O", 3), ("R2", 9), ("t2", 3)):
+        if key in ("R2", "t2") and pr.get(key) is None:
+            continue
+        a = np.asarray(pr[key], np.float32).reshape(-1)
+        if len(a) != k:
+            raise SlamitError("project: %s has %d entries" % (key, len(a)))
+        rec[key][0] = a
+    for key in _PROJECT_SCALARS:
+        rec[key][0] = np.float32(pr[key])
+    sf = np.asarray(pr["scale_factors"], np.float32).reshape(-1)
+    nl = int(pr["n_levels"])
+    if len(sf) != nl:
+        raise SlamitError("project: scale_factors does not have n_levels entries")
+    rec["n_levels"][0] = nl
+    rec["scale_factors"][0, :min(nl, 16)] = sf[:16]
+    rec["direction"][0] = int(pr.get("direction", 0))
+    return rec
+
+
+def project_batch(problems, device=0):
+    """The projection loops in front of the guided search of six ORBmatcher drivers (csrc/project.h) for a list of
+    cameras in ONE device call; the problems may differ in form.  Each problem is a dict in the layout of slamit_project_problem
+    (synth.synth_project): the camera's fields (project_camera_record), pos (n, 3) float32, skip (n) uint8 and, where the form reads
+    them (None otherwise), normal (n, 3), max_dist, min_dist (n) float32, octave (n) int32.  -> a list of dicts: status (n) uint8
+    (0 accepted, else the first test that rejected the point; 7 = the level outside the table), proj (n, 2) = u, v, level (n), the
+    guided search's query arrays uvr (n, 3), level_min, level_max (n), valid (n); n_valid."""
+    plist = list(problems)
+    m = len(plist)
+    P = (ProjectProblem * m)()
+    R = (ProjectResult * m)()
+    keep, outs = [], []
+    for i, pr in enumerate(plist):
+        k = {"pos": np.ascontiguousarray(pr["pos"], np.float32).reshape(-1, 3), "skip": np.ascontiguousarray(pr["skip"], np.uint8).reshape(-1)}
+        for key, dt, shape in (("normal", np.float32, (-1, 3)), ("max_dist", np.float32, (-1,)), ("min_dist", np.float32, (-1,)), ("octave", np.int32, (-1,))):
+            if pr.get(key) is not None:
+                k[key] = np.ascontiguousarray(pr[key], dt).reshape(shape)
+        n = len(k["skip"])
+        if any(len(a) != n for a in k.values()):
+            raise SlamitError("project: pos / normal / max_dist / min_dist / octave / skip do not have the same length")
+        rec = project_camera_record(pr)
+        C.memmove(C.byref(P[i].camera), rec.ctypes.data, C.sizeof(ProjectCamera))
+        P[i].n = n
+        for key, a in k.items():
+            setattr(P[i], key, a.ctypes.data)
+        o = {"status": np.zeros(n, np.uint8), "proj": np.zeros((n, 2), np.float32), "level": np.zeros(n, np.int32), "uvr": np.zeros((n, 3), np.float32),
+             "level_min": np.zeros(n, np.int32), "level_max": np.zeros(n, np.int32), "valid": np.zeros(n, np.uint8)}
+        for key, a in o.items():
+            setattr(R[i], key, a.ctypes.data)
+        keep.append(k)
+        outs.append(o)
+    _check(lib().slamit_project_batch(device, m, P, R), "slamit_project_batch")
+    del keep
+    for i, o in enumerate(outs):
+        o["n_valid"] = int(R[i].n_valid)
+    return outs
+
+
+def project(problem, device=0):
+    """One camera: project_batch([problem])[0]."""
+    return project_batch([problem], device)[0]
+
+
+def project_batch_dev(t, device=0, stream=None):
+    """The resident form.  t: dict of torch CUDA tensors cameras (B, 56) f32 (rows of PROJECT_CAMERA_DTYPE viewed as float32), m (B)
+    i32, pos / normal (B, 3, q_cap) f32 PLANES, max_dist / min_dist (B, q_cap) f32, octave (B, q_cap) i32, skip (B, q_cap) u8, and the
+    outputs uvr (B, q_cap, 3) f32, level_min / level_max (B, q_cap) i32, valid (B, q_cap) u8 -- the tensors guided_search_batch_dev
+    reads -- plus optionally status (B, q_cap) u8, proj (B, q_cap, 2) f32, level (B, q_cap) i32, n_valid (B) i32.
+    Asynchronous on `stream`."""
+    b, q_cap = t["pos"].shape[0], t["pos"].shape[2]
+    if t["cameras"].numel() * t["cameras"].element_size() != b * C.sizeof(ProjectCamera):
+        raise SlamitError("project_batch_dev: cameras does not hold one slamit_project_camera per frame")
+    for key, per in (("pos", 3), ("normal", 3), ("max_dist", 1), ("min_dist", 1), ("octave", 1), ("skip", 1), ("uvr", 3), ("level_min", 1),
+                     ("level_max", 1), ("valid", 1), ("status", 1), ("proj", 2), ("level", 1)):
+        if t.get(key) is not None and (t[key].numel() != b * q_cap * per or not t[key].is_contiguous()):
+            raise SlamitError("project_batch_dev: %s is not a contiguous (B, q_cap) array" % key)
+    for key in ("m", "n_valid"):
+        if t.get(key) is not None and t[key].numel() != b:
+            raise SlamitError("project_batch_dev: %s does not have one entry per frame" % key)
+
+    def opt(key):
+        return t[key].data_ptr() if t.get(key) is not None else None
+
+    rec = ProjectBatchRec(b, q_cap, t["cameras"].data_ptr(), t["m"].data_ptr(), t["pos"].data_ptr(), t["normal"].data_ptr(), t["max_dist"].data_ptr(),
+                          t["min_dist"].data_ptr(), t["octave"].data_ptr(), t["skip"].data_ptr(), t["uvr"].data_ptr(), t["level_min"].data_ptr(),
+                          t["level_max"].data_ptr(), t["valid"].data_ptr(), opt("status"), opt("proj"), opt("level"), opt("n_valid"))
+    _check(lib().slamit_project_batch_dev(device, C.byref(rec), stream), "slamit_project_batch_dev")

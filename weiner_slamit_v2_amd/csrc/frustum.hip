@@ -113,6 +113,11 @@ __global__ __launch_bounds__(64) void frustum_count_kernel(const uint8_t* __rest
     if (threadIdx.x == 0) n_in_view[f] = count;
 }
 
+hipError_t slamit_launch_valid_count(const uint8_t* d_valid, const int32_t* d_m, int q_cap, int nframes, int32_t* d_count, hipStream_t stream) {
+    hipLaunchKernelGGL(frustum_count_kernel, dim3(nframes), dim3(64), 0, stream, d_valid, d_m, q_cap, d_count);
+    return hipGetLastError();
+}
+
 extern "C" {
 
 int slamit_frustum_batch(int device, int nprob, const slamit_frustum_problem* probs, slamit_frustum_result* results) {
@@ -233,8 +238,7 @@ int slamit_frustum_batch_dev(int device, const slamit_frustum_batch_rec* B, void
     hipLaunchKernelGGL(frustum_dev_kernel, dim3((B->q_cap + 255) / 256, B->nframes), dim3(256), 0, (hipStream_t)stream, D);
     HIP_TRY_AT("slamit_frustum_batch_dev", hipGetLastError());
     if (B->d_n_in_view) {
-        hipLaunchKernelGGL(frustum_count_kernel, dim3(B->nframes), dim3(64), 0, (hipStream_t)stream, B->d_valid, B->d_m, B->q_cap, B->d_n_in_view);
-        HIP_TRY_AT("slamit_frustum_batch_dev", hipGetLastError());
+        HIP_TRY_AT("slamit_frustum_batch_dev", slamit_launch_valid_count(B->d_valid, B->d_m, B->q_cap, B->nframes, B->d_n_in_view, (hipStream_t)stream));
     }
     return SLAMIT_OK;
 }

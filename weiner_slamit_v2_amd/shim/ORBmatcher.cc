@@ -8,7 +8,9 @@ const int ORBmatcher::TH_HIGH = 100;     // ORBmatcher.cc:37
 const int ORBmatcher::TH_LOW = 50;       // :38
 const int ORBmatcher::HISTO_LENGTH = shim::RotationHistogram::LENGTH; // :39
 
-ORBmatcher::ORBmatcher(float nnratio, bool checkOri) : mfNNratio(nnratio), mbCheckOrientation(checkOri) {}
+ORBmatcher::ORBmatcher(float nnratio, bool checkOri) : mfNNratio(nnratio), mbCheckOrientation(checkOri), mbDeviceProjection(false) {}
+ORBmatcher::ORBmatcher(float nnratio, bool checkOri, bool deviceProjection)
+    : mfNNratio(nnratio), mbCheckOrientation(checkOri), mbDeviceProjection(deviceProjection) {}
 
 namespace {
 // descriptor tables may be row-padded cv::Mat views; the C-ABI wants 32-byte rows
@@ -72,6 +74,26 @@ bool ORBmatcher::GuidedSearch(const std::vector<cv::KeyPoint>& keysUn, const cv:
     if (acceptedKp) acceptedKp->assign(m, -1);
     setStatus(slamit_guided_search(0, &fv, &sq, &rule, matchKp.data(), &nm, nullptr, acceptedKp ? acceptedKp->data() : nullptr, nullptr, nullptr));
     return LastStatus() == SLAMIT_OK;
+}
+
+bool ORBmatcher::Project(std::vector<ProjectPoints>& batch) {
+    setStatus(SLAMIT_OK);
+    std::vector<slamit_project_problem> P(batch.size());
+    std::vector<slamit_project_result> R(batch.size());
+    for (size_t k = 0; k < batch.size(); ++k) {
+        ProjectPoints& b = batch[k];
+        const size_t n = (size_t)b.size();
+        b.status.assign(n, 0); b.valid.assign(n, 0); b.proj.assign(2 * n, 0.f); b.uvr.assign(3 * n, 0.f);
+        b.level.assign(n, 0); b.lmin.assign(n, 0); b.lmax.assign(n, 0);
+        P[k].camera = b.cam; P[k].n = (int32_t)n;
+        P[k].pos = b.pos.data(); P[k].normal = b.normal.data(); P[k].max_dist = b.maxd.data(); P[k].min_dist = b.mind.data();
+        P[k].octave = b.octave.data(); P[k].skip = b.skip.data();
+        R[k].status = b.status.data(); R[k].proj = b.proj.data(); R[k].level = b.level.data(); R[k].uvr = b.uvr.data();
+        R[k].level_min = b.lmin.data(); R[k].level_max = b.lmax.data(); R[k].valid = b.valid.data(); R[k].n_valid = 0;
+    }
+    const int rc = slamit_project_batch(0, (int)batch.size(), P.data(), R.data());
+    if (rc != SLAMIT_OK) { shim::report<ORBmatcher>("slamit_project_batch", rc); return false; }
+    return true;
 }
 
 bool ORBmatcher::BowSearch(const cv::Mat& desc1, const std::vector<uint8_t>& valid1, const cv::Mat& desc2, const std::vector<uint8_t>* valid2,

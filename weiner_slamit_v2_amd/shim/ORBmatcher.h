@@ -34,7 +34,14 @@ namespace ORB_SLAM2 {
 
 class ORBmatcher {
 public:
-    ORBmatcher(float nnratio = 0.6, bool checkOri = true);
+    // deviceProjection: the six guided-search drivers below that project map points themselves -- SearchByProjection(CurrentFrame,
+    // LastFrame), the relocalisation search, both Fuse, SearchByProjection(pKF, Scw) and SearchBySim3 -- build their queries with ONE
+    // slamit_project call (csrc/project.h) instead of their host loop; the search and the bookkeeping after it are
+    // the same code.  That path does not call the caller's PredictScale: it reads MapPoint::GetMaxDistance() / GetMinDistance(), the RAW
+    // mfMaxDistance / mfMinDistance (shim/Tracking.h), and KeyFrame / Frame::mfLogScaleFactor, mnMaxX, mnMaxY.  A point whose level falls
+    // outside mvScaleFactors, which the host loop indexes unchecked, is not searched there.  Off in the reference's own constructor: nothing changes.
+    ORBmatcher(float nnratio = 0.6, bool checkOri = true);                 // the reference's constructor: deviceProjection off
+    ORBmatcher(float nnratio, bool checkOri, bool deviceProjection);
 
     // Hamming distance between two 1x32 CV_8U descriptors (ORBmatcher.cc:1651-1667).  One pair per
     // call is a poor fit for a GPU; loops should use DistanceMatrix / BestTwo instead.
@@ -84,6 +91,16 @@ public:
     //              AddObservation(pKF, idx)
     template <class KeyFrameT, class MapPointT>
     int Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const float th = 3.0);
+
+    // The first loop of LocalMapping::SearchInNeighbors (LocalMapping.cc:535-543): vpMapPoints fused into every target keyframe, in
+    // order; returns the sum of the targets' counts.  With deviceProjection the projections of ALL targets are one
+    // slamit_project_batch call made before the first target's turn; the search and the bookkeeping then run per target, in order, as
+    // the per-target calls do.  That is the same computation: an earlier target's Replace can make a point bad and can change a
+    // survivor's descriptor (ComputeDistinctiveDescriptors), but it never changes a position, a normal or a distance, so the geometry
+    // may be batched ahead; isBad() / IsInKeyFrame() are tested again on the host at each target's turn, and descriptors are read at
+    // that turn.  Without deviceProjection this is the loop of per-target calls.  It stops at the first target that fails.
+    template <class KeyFrameT, class MapPointT>
+    int Fuse(const std::vector<KeyFrameT*>& targets, const std::vector<MapPointT*>& vpMapPoints, const float th = 3.0);
 
     // Tracking::Relocalization's search (ORBmatcher.cc:1476-1603): the map points of a candidate keyframe projected into the
     // current frame.  Additional members: KeyFrame : GetMapPointMatches(), mvKeysUn ; Frame : mfLogScaleFactor ;
@@ -175,6 +192,38 @@ public:
         return GuidedSearch(F.mvKeysUn, F.mDescriptors, kpTaken, F.mnMinX, F.mnMinY, F.mfGridElementWidthInv, F.mfGridElementHeightInv, q,
                             thDist, useRatio, nnratio, matchKp, chi2Gate, invLevelSigma2, mode, acceptedKp);
     }
+    // One camera's points for slamit_project, in the order the driver visits them (a point the driver's own tests drop before the
+    // projection travels as skipped, so that query i is point i), and the call's results.
+    struct ProjectPoints {
+        slamit_project_camera cam;
+        std::vector<float> pos, normal, maxd, mind;
+        std::vector<int32_t> octave;
+        std::vector<uint8_t> skip;
+        std::vector<uint8_t> status, valid;
+        std::vector<float> proj, uvr;
+        std::vector<int32_t> level, lmin, lmax;
+        ProjectPoints() { memset(&cam, 0, sizeof(cam)); }
+        int size() const { return (int)skip.size(); }
+        void add(bool skipped, const float P[3], const float Pn[3], float maxDist, float minDist, int oct) {
+            for (int c = 0; c < 3; ++c) { pos.push_back(skipped ? 0.f : P[c]); normal.push_back(skipped || !Pn ? 0.f : Pn[c]); }
+            maxd.push_back(maxDist); mind.push_back(minDist); octave.push_back(oct); skip.push_back(skipped ? 1 : 0);
+        }
+        void query(int i, GuidedQueries& q, const cv::Mat& d, bool takesKp) const {
+            q.add(uvr[3 * i], uvr[3 * i + 1], uvr[3 * i + 2], lmin[i], lmax[i], d, takesKp);
+        }
+    };
+    // ONE slamit_project_batch call for all of them; false: reported, LastStatus() != 0
+    static bool Project(std::vector<ProjectPoints>& batch);
+    // intrinsics, bounds, scale table and th of the searched frame or keyframe; the pose is the driver's to fill
+    template <class CamT>
+    static void ProjectCamera(slamit_project_camera& c, int form, const CamT& F, float fx, float fy, float cx, float cy, float th) {
+        memset(&c, 0, sizeof(c));
+        c.form = form; c.fx = fx; c.fy = fy; c.cx = cx; c.cy = cy; c.th = th;
+        c.min_x = F.mnMinX; c.max_x = F.mnMaxX; c.min_y = F.mnMinY; c.max_y = F.mnMaxY;
+        c.log_scale_factor = F.mfLogScaleFactor;
+        c.n_levels = (int)F.mvScaleFactors.size();   // more than SLAMIT_MAX_LEVELS: slamit_project refuses
+        for (int i = 0; i < c.n_levels && i < SLAMIT_MAX_LEVELS; ++i) c.scale_factors[i] = F.mvScaleFactors[i];
+    }
     static int LastStatus();   // of the calling thread
 
     static const int TH_LOW;
@@ -185,8 +234,20 @@ protected:
     static void setStatus(int rc);
     void ComputeThreeMaxima(std::vector<int>* histo, const int L, int& ind1, int& ind2, int& ind3);
 
+    // Fuse(pKF, vpMapPoints, th) in its parts: the refusal of stereo keyframes, the projection input of one target, the queries of the
+    // points the device accepted (re-testing isBad / IsInKeyFrame, reading descriptors NOW), and the search with its bookkeeping
+    template <class KeyFrameT>
+    bool fuseAdmits(KeyFrameT* pKF);
+    template <class KeyFrameT, class MapPointT>
+    void fuseProjection(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, float th, ProjectPoints& pp);
+    template <class KeyFrameT, class MapPointT>
+    void fuseQueries(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const ProjectPoints& pp, GuidedQueries& q, std::vector<MapPointT*>& who);
+    template <class KeyFrameT, class MapPointT>
+    int fuseTail(KeyFrameT* pKF, const GuidedQueries& q, const std::vector<MapPointT*>& who);
+
     float mfNNratio;
     bool mbCheckOrientation;
+    bool mbDeviceProjection;
 };
 
 // ---- templates --------------------------------------------------------------------------------
@@ -259,6 +320,26 @@ int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame
 
     GuidedQueries q;
     std::vector<int> who;   // index into LastFrame
+    if (mbDeviceProjection) {
+        std::vector<ProjectPoints> pp(1);
+        ProjectCamera(pp[0].cam, SLAMIT_PROJECT_LAST_FRAME, CurrentFrame, CurrentFrame.fx, CurrentFrame.fy, CurrentFrame.cx, CurrentFrame.cy, th);
+        memcpy(pp[0].cam.R, Rcw, sizeof(Rcw)); memcpy(pp[0].cam.t, tcw, sizeof(tcw));
+        pp[0].cam.direction = bForward ? 1 : bBackward ? 2 : 0;
+        for (int i = 0; i < LastFrame.N; i++) {
+            auto* pMP = LastFrame.mvpMapPoints[i];
+            const bool skipped = !pMP || LastFrame.mvbOutlier[i];
+            float P[3] = {0.f, 0.f, 0.f};
+            if (!skipped) shim::load3(pMP->GetWorldPos(), P);
+            pp[0].add(skipped, P, nullptr, 0.f, 0.f, LastFrame.mvKeys[i].octave);
+        }
+        if (!Project(pp)) return 0;
+        for (int i = 0; i < LastFrame.N; i++) {
+            if (!pp[0].valid[i]) continue;
+            auto* pMP = LastFrame.mvpMapPoints[i];
+            pp[0].query(i, q, pMP->GetDescriptor(), pMP->Observations() > 0);
+            who.push_back(i);
+        }
+    } else
     for (int i = 0; i < LastFrame.N; i++) {
         auto* pMP = LastFrame.mvpMapPoints[i];
         if (!pMP || LastFrame.mvbOutlier[i]) continue;
@@ -307,6 +388,24 @@ int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, KeyFrameT* pKF, const S
     const auto vpMPs = pKF->GetMapPointMatches();
     GuidedQueries q;
     std::vector<int> who;   // index into vpMPs (= keypoint of pKF)
+    if (mbDeviceProjection) {
+        std::vector<ProjectPoints> pp(1);
+        ProjectCamera(pp[0].cam, SLAMIT_PROJECT_RELOC, CurrentFrame, CurrentFrame.fx, CurrentFrame.fy, CurrentFrame.cx, CurrentFrame.cy, th);
+        memcpy(pp[0].cam.R, Rcw, sizeof(Rcw)); memcpy(pp[0].cam.t, tcw, sizeof(tcw)); memcpy(pp[0].cam.O, Ow, sizeof(Ow));
+        for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {
+            auto* pMP = vpMPs[i];
+            const bool skipped = !pMP || pMP->isBad() || sAlreadyFound.count(pMP);
+            float P[3] = {0.f, 0.f, 0.f};
+            if (!skipped) shim::load3(pMP->GetWorldPos(), P);
+            pp[0].add(skipped, P, nullptr, skipped ? 0.f : pMP->GetMaxDistance(), skipped ? 0.f : pMP->GetMinDistance(), 0);
+        }
+        if (!Project(pp)) return 0;
+        for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {
+            if (!pp[0].valid[i]) continue;
+            pp[0].query((int)i, q, vpMPs[i]->GetDescriptor(), true);
+            who.push_back((int)i);
+        }
+    } else
     for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {
         auto* pMP = vpMPs[i];
         if (!pMP) continue;
@@ -488,6 +587,26 @@ int ORBmatcher::SearchByProjection(KeyFrameT* pKF, cv::Mat Scw, const std::vecto
     std::vector<MapPointT*> found(vpMatched.begin(), vpMatched.end());   // spAlreadyFound (:309-310)
     GuidedQueries q;
     std::vector<MapPointT*> who;
+    if (mbDeviceProjection) {
+        std::vector<ProjectPoints> pp(1);
+        ProjectCamera(pp[0].cam, SLAMIT_PROJECT_SIM3_PROJ, *pKF, fx, fy, cx, cy, (float)th);
+        memcpy(pp[0].cam.R, R, sizeof(R)); memcpy(pp[0].cam.t, t, sizeof(t)); memcpy(pp[0].cam.O, O, sizeof(O));
+        for (int iMP = 0, iendMP = (int)vpPoints.size(); iMP < iendMP; iMP++) {
+            MapPointT* pMP = vpPoints[iMP];
+            bool seen = false;
+            for (size_t k = 0; k < found.size() && !seen; ++k) seen = found[k] == pMP;
+            const bool skipped = pMP->isBad() || seen;
+            float P[3] = {0.f, 0.f, 0.f}, Pn[3] = {0.f, 0.f, 0.f};
+            if (!skipped) { shim::load3(pMP->GetWorldPos(), P); shim::load3(pMP->GetNormal(), Pn); }
+            pp[0].add(skipped, P, Pn, skipped ? 0.f : pMP->GetMaxDistance(), skipped ? 0.f : pMP->GetMinDistance(), 0);
+        }
+        if (!Project(pp)) return 0;
+        for (int iMP = 0, iendMP = (int)vpPoints.size(); iMP < iendMP; iMP++) {
+            if (!pp[0].valid[iMP]) continue;
+            pp[0].query(iMP, q, vpPoints[iMP]->GetDescriptor(), true);
+            who.push_back(vpPoints[iMP]);
+        }
+    } else
     for (int iMP = 0, iendMP = (int)vpPoints.size(); iMP < iendMP; iMP++) {
         MapPointT* pMP = vpPoints[iMP];
         bool seen = false;
@@ -534,6 +653,24 @@ int ORBmatcher::Fuse(KeyFrameT* pKF, cv::Mat Scw, const std::vector<MapPointT*>&
     GuidedQueries q;
     std::vector<int> who;
     const int nPoints = (int)vpPoints.size();
+    if (mbDeviceProjection) {
+        std::vector<ProjectPoints> pp(1);
+        ProjectCamera(pp[0].cam, SLAMIT_PROJECT_SIM3_FUSE, *pKF, fx, fy, cx, cy, th);
+        memcpy(pp[0].cam.R, R, sizeof(R)); memcpy(pp[0].cam.t, t, sizeof(t)); memcpy(pp[0].cam.O, O, sizeof(O));
+        for (int iMP = 0; iMP < nPoints; iMP++) {
+            MapPointT* pMP = vpPoints[iMP];
+            const bool skipped = pMP->isBad() || spAlreadyFound.count(pMP);
+            float P[3] = {0.f, 0.f, 0.f}, Pn[3] = {0.f, 0.f, 0.f};
+            if (!skipped) { shim::load3(pMP->GetWorldPos(), P); shim::load3(pMP->GetNormal(), Pn); }
+            pp[0].add(skipped, P, Pn, skipped ? 0.f : pMP->GetMaxDistance(), skipped ? 0.f : pMP->GetMinDistance(), 0);
+        }
+        if (!Project(pp)) return 0;
+        for (int iMP = 0; iMP < nPoints; iMP++) {
+            if (!pp[0].valid[iMP]) continue;
+            pp[0].query(iMP, q, vpPoints[iMP]->GetDescriptor(), false);
+            who.push_back(iMP);
+        }
+    } else
     for (int iMP = 0; iMP < nPoints; iMP++) {
         MapPointT* pMP = vpPoints[iMP];
         if (pMP->isBad() || spAlreadyFound.count(pMP)) continue;
@@ -617,6 +754,25 @@ int ORBmatcher::SearchBySim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPo
             vnMatch.assign(N, -1);
             GuidedQueries q;
             std::vector<int> who;
+            if (self->mbDeviceProjection) {
+                std::vector<ProjectPoints> pp(1);
+                ProjectCamera(pp[0].cam, SLAMIT_PROJECT_SIM3_PAIR, *to, fx, fy, cx, cy, th);
+                memcpy(pp[0].cam.R, Rf, 9 * sizeof(float)); memcpy(pp[0].cam.t, tf, 3 * sizeof(float));
+                memcpy(pp[0].cam.R2, sR, 9 * sizeof(float)); memcpy(pp[0].cam.t2, ts, 3 * sizeof(float));
+                for (int i = 0; i < N; i++) {
+                    MapPointT* pMP = pts[i];
+                    const bool skipped = !pMP || done[i] || pMP->isBad();
+                    float P[3] = {0.f, 0.f, 0.f};
+                    if (!skipped) shim::load3(pMP->GetWorldPos(), P);
+                    pp[0].add(skipped, P, nullptr, skipped ? 0.f : pMP->GetMaxDistance(), skipped ? 0.f : pMP->GetMinDistance(), 0);
+                }
+                if (!Project(pp)) return false;
+                for (int i = 0; i < N; i++) {
+                    if (!pp[0].valid[i]) continue;
+                    pp[0].query(i, q, pts[i]->GetDescriptor(), false);
+                    who.push_back(i);
+                }
+            } else
             for (int i = 0; i < N; i++) {
                 MapPointT* pMP = pts[i];
                 if (!pMP || done[i]) continue;
@@ -690,17 +846,54 @@ int ORBmatcher::SearchForInitialization(FrameT& F1, FrameT& F2, std::vector<cv::
     return nmatches;
 }
 
+template <class KeyFrameT>
+bool ORBmatcher::fuseAdmits(KeyFrameT* pKF) {
+    for (size_t i = 0; i < pKF->mvKeysUn.size(); ++i)
+        if (pKF->mvuRight[i] >= 0) { setStatus(SLAMIT_ERR_ARG); return false; }   // stereo keypoints: not on this path
+    return true;
+}
+
+template <class KeyFrameT, class MapPointT>
+void ORBmatcher::fuseProjection(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, float th, ProjectPoints& pp) {
+    ProjectCamera(pp.cam, SLAMIT_PROJECT_FUSE, *pKF, pKF->fx, pKF->fy, pKF->cx, pKF->cy, th);
+    shim::load3x3(pKF->GetRotation(), pp.cam.R); shim::load3(pKF->GetTranslation(), pp.cam.t); shim::load3(pKF->GetCameraCenter(), pp.cam.O);
+    for (size_t i = 0; i < vpMapPoints.size(); i++) {
+        MapPointT* pMP = vpMapPoints[i];
+        const bool skipped = !pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF);
+        float P[3] = {0.f, 0.f, 0.f}, Pn[3] = {0.f, 0.f, 0.f};
+        if (!skipped) { shim::load3(pMP->GetWorldPos(), P); shim::load3(pMP->GetNormal(), Pn); }
+        pp.add(skipped, P, Pn, skipped ? 0.f : pMP->GetMaxDistance(), skipped ? 0.f : pMP->GetMinDistance(), 0);
+    }
+}
+
+template <class KeyFrameT, class MapPointT>
+void ORBmatcher::fuseQueries(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const ProjectPoints& pp, GuidedQueries& q,
+                             std::vector<MapPointT*>& who) {
+    for (size_t i = 0; i < vpMapPoints.size(); i++) {
+        if (!pp.valid[i]) continue;
+        MapPointT* pMP = vpMapPoints[i];
+        if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;   // an earlier target of a batch may have changed either since the projection
+        pp.query((int)i, q, pMP->GetDescriptor(), false);
+        who.push_back(pMP);
+    }
+}
+
 template <class KeyFrameT, class MapPointT>
 int ORBmatcher::Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const float th) {
+    if (!fuseAdmits(pKF)) return 0;
+    GuidedQueries q;
+    std::vector<MapPointT*> who;
+    if (mbDeviceProjection) {
+        std::vector<ProjectPoints> pp(1);
+        fuseProjection(pKF, vpMapPoints, th, pp[0]);
+        if (!Project(pp)) return 0;
+        fuseQueries(pKF, vpMapPoints, pp[0], q, who);
+        return fuseTail(pKF, q, who);
+    }
     const cv::Mat Rcw = pKF->GetRotation(), tcw = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
     float R[3][3], t[3], O[3];
     shim::load3x3(Rcw, &R[0][0]); shim::load3(tcw, t); shim::load3(Ow, O);
     const float fx = pKF->fx, fy = pKF->fy, cx = pKF->cx, cy = pKF->cy;
-    const int n = (int)pKF->mvKeysUn.size();
-    for (int i = 0; i < n; ++i)
-        if (pKF->mvuRight[i] >= 0) { setStatus(SLAMIT_ERR_ARG); return 0; }   // stereo keypoints: not on this path
-    GuidedQueries q;
-    std::vector<MapPointT*> who;
     for (size_t i = 0; i < vpMapPoints.size(); i++) {
         MapPointT* pMP = vpMapPoints[i];
         if (!pMP) continue;
@@ -726,8 +919,13 @@ int ORBmatcher::Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints,
         q.add(u, v, radius, nPredictedLevel - 1, nPredictedLevel, pMP->GetDescriptor(), false);
         who.push_back(pMP);
     }
+    return fuseTail(pKF, q, who);
+}
+
+template <class KeyFrameT, class MapPointT>
+int ORBmatcher::fuseTail(KeyFrameT* pKF, const GuidedQueries& q, const std::vector<MapPointT*>& who) {
     std::vector<int> matchKp;
-    const std::vector<uint8_t> none((size_t)n, 0);
+    const std::vector<uint8_t> none(pKF->mvKeysUn.size(), 0);
     if (!GuidedSearch(*pKF, none, q, TH_LOW, false, mfNNratio, matchKp, 5.99f, &pKF->mvInvLevelSigma2)) return 0;
     int nFused = 0;
     for (size_t k = 0; k < who.size(); ++k) {
@@ -748,6 +946,32 @@ int ORBmatcher::Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints,
             pKF->AddMapPoint(pMP, bestIdx);
         }
         nFused++;
+    }
+    return nFused;
+}
+
+template <class KeyFrameT, class MapPointT>
+int ORBmatcher::Fuse(const std::vector<KeyFrameT*>& targets, const std::vector<MapPointT*>& vpMapPoints, const float th) {
+    setStatus(SLAMIT_OK);
+    int nFused = 0;
+    if (!mbDeviceProjection) {
+        for (size_t k = 0; k < targets.size(); ++k) {
+            nFused += Fuse(targets[k], vpMapPoints, th);
+            if (LastStatus() != SLAMIT_OK) return nFused;
+        }
+        return nFused;
+    }
+    for (size_t k = 0; k < targets.size(); ++k)
+        if (!fuseAdmits(targets[k])) return 0;
+    std::vector<ProjectPoints> pp(targets.size());
+    for (size_t k = 0; k < targets.size(); ++k) fuseProjection(targets[k], vpMapPoints, th, pp[k]);
+    if (!Project(pp)) return 0;
+    for (size_t k = 0; k < targets.size(); ++k) {
+        GuidedQueries q;
+        std::vector<MapPointT*> who;
+        fuseQueries(targets[k], vpMapPoints, pp[k], q, who);
+        nFused += fuseTail(targets[k], q, who);
+        if (LastStatus() != SLAMIT_OK) return nFused;
     }
     return nFused;
 }

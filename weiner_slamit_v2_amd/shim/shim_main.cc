@@ -34,6 +34,7 @@
 #include "KeyFrameDatabase.h"
 #include "LocalMapping.h"
 #include "Tracking.h"
+#include "../csrc/frustum.h"   // fru_predict_scale for the mocks
 
 using namespace ORB_SLAM2;
 
@@ -51,6 +52,22 @@ static std::vector<unsigned char> slurp(const char* path) {
 }
 
 // ---- mock data model: just the members Optimizer.h documents --------------------------------
+// The projection drivers' commands (search 1 / 2, fuse, fuse_targets, sim3) take a trailing "host" or "device": the matcher is then
+// built without or with deviceProjection, the blob's maxd / mind are the RAW mfMaxDistance / mfMinDistance, and the mocks' PredictScale is
+// the real formula (MapPoint.cc:391-400) over csrc/frustum.h's fru_logf, so both paths must agree exactly.  Without it the mocks return
+// the blob's stored level and its distances are the invariance bounds, as before.
+static bool g_real_scale = false, g_device_projection = false;
+static void projection_mode(int argc, char** argv, int at) {
+    g_real_scale = argc > at;
+    g_device_projection = argc > at && std::string(argv[at]) == "device";
+}
+static int mock_predict_scale(int stored, float rawMax, float dist, float logScaleFactor) {
+    if (!g_real_scale) return stored;
+    int level;
+    fru_predict_scale(rawMax, dist, logScaleFactor, level);
+    return level;
+}
+
 struct MockKeyFrame;
 struct MockMapPoint {
     long unsigned int mnId, mnBALocalForKF;
@@ -293,9 +310,11 @@ struct MockTrackPoint {
     int mnTrackScaleLevel, nobs, id;
     float mTrackViewCos, mTrackProjX, mTrackProjY, maxd, mind;
     cv::Mat desc, pos;
-    float GetMaxDistanceInvariance() { return maxd; }
-    float GetMinDistanceInvariance() { return mind; }
-    int PredictScale(const float&, const float&) { return mnTrackScaleLevel; }   // the caller's method: stored level
+    float GetMaxDistance() { return maxd; }   // raw (projection mode only)
+    float GetMinDistance() { return mind; }
+    float GetMaxDistanceInvariance() { return g_real_scale ? 1.2f * maxd : maxd; }
+    float GetMinDistanceInvariance() { return g_real_scale ? 0.8f * mind : mind; }
+    int PredictScale(const float& dist, const float& lsf) { return mock_predict_scale(mnTrackScaleLevel, maxd, dist, lsf); }   // the caller's method
     bool isBad() { return bad; }
     int Observations() { return nobs; }
     cv::Mat GetDescriptor() { return desc.clone(); }
@@ -353,6 +372,7 @@ static int run_search(int argc, char** argv) {
     Reader R{raw.data()};
     const int variant = R.get<int>(), n = R.get<int>(), m = R.get<int>();
     const float th = R.get<float>(), nnratio = R.get<float>();
+    projection_mode(argc, argv, 4);
     MockSearchFrame::mnMinX = R.get<float>(); MockSearchFrame::mnMaxX = R.get<float>();
     MockSearchFrame::mnMinY = R.get<float>(); MockSearchFrame::mnMaxY = R.get<float>();
     MockSearchFrame::mfGridElementWidthInv = R.get<float>(); MockSearchFrame::mfGridElementHeightInv = R.get<float>();
@@ -364,6 +384,7 @@ static int run_search(int argc, char** argv) {
     const unsigned char* desc = R.arr<unsigned char>(32 * (size_t)n);
     MockSearchFrame F;
     F.N = n;
+    F.mfLogScaleFactor = 0.18232f;
     F.mvScaleFactors.assign(scale, scale + 8);
     F.mDescriptors = cv::Mat(n, 32, CV_8U);
     F.mvKeysUn.resize(n); F.mvuRight.assign(n, -1.f); F.mvpMapPoints.assign(n, (MockTrackPoint*)0); F.mvbOutlier.assign(n, false);
@@ -414,7 +435,7 @@ static int run_search(int argc, char** argv) {
             if (has[q]) KF.matches[q] = &p;
             if (found[q]) sFound.insert(&p);
         }
-        ORBmatcher matcher(0.9f, true);
+        ORBmatcher matcher(0.9f, true, g_device_projection);
         nm = matcher.SearchByProjection(F, &KF, sFound, th, orbdist);
     } else {
         const float* Tcw = R.arr<float>(12); const float* Tlw = R.arr<float>(12); const float* intr = R.arr<float>(5);
@@ -435,7 +456,7 @@ static int run_search(int argc, char** argv) {
             L.mvbOutlier[q] = outl[q] != 0;
         }
         L.mvKeysUn = L.mvKeys;
-        ORBmatcher matcher(0.9f, true);
+        ORBmatcher matcher(0.9f, true, g_device_projection);
         nm = matcher.SearchByProjection(F, L, th, mono != 0);
     }
     const int status = ORBmatcher::LastStatus();
@@ -511,11 +532,17 @@ struct MockFusePoint {
     cv::Mat GetWorldPos() { return pos.clone(); }
     cv::Mat GetNormal() { return normal.clone(); }
     cv::Mat GetDescriptor() { return desc.clone(); }
-    float GetMaxDistanceInvariance() { return maxd; }
-    float GetMinDistanceInvariance() { return mind; }
-    int PredictScale(const float&, const float&) { return level; }   // the caller's method: the mock returns a stored level
+    float GetMaxDistance() { return maxd; }   // raw (projection mode only)
+    float GetMinDistance() { return mind; }
+    float GetMaxDistanceInvariance() { return g_real_scale ? 1.2f * maxd : maxd; }
+    float GetMinDistanceInvariance() { return g_real_scale ? 0.8f * mind : mind; }
+    int PredictScale(const float& dist, const float& lsf) { return mock_predict_scale(level, maxd, dist, lsf); }   // the caller's method
     int Observations() { return nobs; }
-    void Replace(MockFusePoint* p) { replacedBy = p; bad = true; }
+    void Replace(MockFusePoint* p) {
+        replacedBy = p; bad = true;
+        // projection mode: the survivor's descriptor changes, as ComputeDistinctiveDescriptors may change it (it takes over bytes 0 .. 15; the plain fuse command's own points carry no descriptor)
+        if (g_real_scale && p->desc.rows > 0 && desc.rows > 0) { p->desc = p->desc.clone(); memcpy(p->desc.ptr(0), desc.ptr(0), 16); p->nobs += nobs; }
+    }
     void AddObservation(MockFuseKF*, size_t idx) { addedAt = (int)idx; inKF = true; ++nobs; }
 };
 struct MockFuseKF {
@@ -547,6 +574,7 @@ static int run_fuse(int argc, char** argv) {
     Reader Rd{raw.data()};
     const int n = Rd.get<int>(), m = Rd.get<int>();
     const float th = Rd.get<float>();
+    projection_mode(argc, argv, 4);
     const float* Rv = Rd.arr<float>(9); const float* tv = Rd.arr<float>(3); const float* Ov = Rd.arr<float>(3);
     const float* intr = Rd.arr<float>(4); const float* b = Rd.arr<float>(6);
     const float* scale = Rd.arr<float>(8); const float* invsig = Rd.arr<float>(8);
@@ -579,7 +607,7 @@ static int run_fuse(int argc, char** argv) {
         p.desc = cv::Mat(1, 32, CV_8U); memcpy(p.desc.ptr(0), md + 32 * (size_t)j, 32);
         vp[j] = isnull[j] ? (MockFusePoint*)0 : &p;
     }
-    ORBmatcher matcher(0.6f, true);
+    ORBmatcher matcher(0.6f, true, g_device_projection);
     const int nf = matcher.Fuse(&KF, vp, th);
     const int status = ORBmatcher::LastStatus();
     if (status != 0) fprintf(stderr, "fuse failed: %s\n", slamit_last_error());
@@ -591,6 +619,85 @@ static int run_fuse(int argc, char** argv) {
     }
     for (int i = 0; i < n; ++i) { int o = KF.mps[i] ? KF.mps[i]->id : -1; fwrite(&o, 4, 1, f); }
     for (int i = 0; i < n; ++i) { int r = own[i].replacedBy ? own[i].replacedBy->id : -1; fwrite(&r, 4, 1, f); }
+    fclose(f);
+    return 0;
+}
+
+// The multi-target Fuse (the first loop of LocalMapping::SearchInNeighbors).  fuse_targets <in> <out> host|device batch|single:
+// `batch` is ONE Fuse(targets, points, th) call, `single` the loop of per-target calls.
+// problem.bin: int32 nkf m ; float th ; map points: float pos[3m] normal[3m] maxd[m] mind[m] (raw), int32 nobs[m], u8 desc[32m] ;
+//   per target: float R[9] t[3] O[3] intr[4] bounds[6] scale[8] invsig[8] ; int32 n ; float xy[2n] ; int32 octave[n] kf_state[n]
+//   (0 none, k > 0: a point of the target's own with k - 1 observations) ; u8 desc[32n]
+// out.bin: int32 status nFused ; per map point int32 addedAt replacedBy (-1 none, -2 a target's own point, else id) bad nobs, u8 desc[32] ;
+//   per target per keypoint int32 owner, int32 own point replacedBy
+static int run_fuse_targets(int argc, char** argv) {
+    if (argc < 6) return 2;
+    std::vector<unsigned char> raw = slurp(argv[2]);
+    Reader Rd{raw.data()};
+    const int nkf = Rd.get<int>(), m = Rd.get<int>();
+    const float th = Rd.get<float>();
+    projection_mode(argc, argv, 4);
+    const bool batch = std::string(argv[5]) == "batch";
+    const float* pos = Rd.arr<float>(3 * (size_t)m); const float* nrm = Rd.arr<float>(3 * (size_t)m);
+    const float* maxd = Rd.arr<float>(m); const float* mind = Rd.arr<float>(m);
+    const int* nobs = Rd.arr<int>(m);
+    const unsigned char* md = Rd.arr<unsigned char>(32 * (size_t)m);
+    std::vector<MockFusePoint> pts(m);
+    std::vector<MockFusePoint*> vp(m);
+    for (int j = 0; j < m; ++j) {
+        MockFusePoint& p = pts[j];
+        p.id = j; p.nobs = nobs[j]; p.maxd = maxd[j]; p.mind = mind[j];
+        p.pos = mat_from(pos + 3 * (size_t)j, 3); p.normal = mat_from(nrm + 3 * (size_t)j, 3);
+        p.desc = cv::Mat(1, 32, CV_8U); memcpy(p.desc.ptr(0), md + 32 * (size_t)j, 32);
+        vp[j] = &p;
+    }
+    std::vector<MockFuseKF> KF(nkf);
+    std::vector<std::vector<MockFusePoint> > own(nkf);
+    std::vector<MockFuseKF*> targets(nkf);
+    for (int k = 0; k < nkf; ++k) {
+        const float* Rv = Rd.arr<float>(9); const float* tv = Rd.arr<float>(3); const float* Ov = Rd.arr<float>(3);
+        const float* intr = Rd.arr<float>(4); const float* b = Rd.arr<float>(6);
+        const float* scale = Rd.arr<float>(8); const float* invsig = Rd.arr<float>(8);
+        const int n = Rd.get<int>();
+        const float* xy = Rd.arr<float>(2 * (size_t)n); const int* oct = Rd.arr<int>(n); const int* kfs = Rd.arr<int>(n);
+        const unsigned char* kd = Rd.arr<unsigned char>(32 * (size_t)n);
+        MockFuseKF& K = KF[k];
+        K.R = cv::Mat(3, 3, CV_32F); K.t = mat_from(tv, 3); K.O = mat_from(Ov, 3);
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) K.R.at<float>(r, c) = Rv[3 * r + c];
+        K.fx = intr[0]; K.fy = intr[1]; K.cx = intr[2]; K.cy = intr[3]; K.mfLogScaleFactor = 0.18232f;
+        K.mnMinX = b[0]; K.mnMaxX = b[1]; K.mnMinY = b[2]; K.mnMaxY = b[3]; K.mfGridElementWidthInv = b[4]; K.mfGridElementHeightInv = b[5];
+        K.mvScaleFactors.assign(scale, scale + 8); K.mvInvLevelSigma2.assign(invsig, invsig + 8);
+        K.mvuRight.assign(n, -1.f); K.mvKeysUn.resize(n); K.mps.assign(n, (MockFusePoint*)0);
+        K.mDescriptors = cv::Mat(n, 32, CV_8U);
+        own[k].resize(n);
+        for (int i = 0; i < n; ++i) {
+            K.mvKeysUn[i] = cv::KeyPoint(xy[2 * i], xy[2 * i + 1], 31.f, -1.f, 0, oct[i]);
+            memcpy(K.mDescriptors.ptr(i), kd + 32 * (size_t)i, 32);
+            if (kfs[i] > 0) {
+                MockFusePoint& o = own[k][i];
+                o.id = -2; o.nobs = kfs[i] - 1; o.desc = cv::Mat(1, 32, CV_8U); memcpy(o.desc.ptr(0), kd + 32 * (size_t)i, 32);
+                K.mps[i] = &o;
+            }
+        }
+        targets[k] = &K;
+    }
+    ORBmatcher matcher(0.6f, true, g_device_projection);
+    int nf = 0, status = 0;
+    if (batch) { nf = matcher.Fuse(targets, vp, th); status = ORBmatcher::LastStatus(); }
+    else
+        for (int k = 0; k < nkf && status == 0; ++k) { nf += matcher.Fuse(targets[k], vp, th); status = ORBmatcher::LastStatus(); }
+    if (status != 0) fprintf(stderr, "fuse_targets failed: %s\n", slamit_last_error());
+    FILE* f = fopen(argv[3], "wb");
+    fwrite(&status, 4, 1, f); fwrite(&nf, 4, 1, f);
+    for (int j = 0; j < m; ++j) {
+        int v[4] = {pts[j].addedAt, pts[j].replacedBy ? pts[j].replacedBy->id : -1, pts[j].bad ? 1 : 0, pts[j].nobs};
+        fwrite(v, 4, 4, f); fwrite(pts[j].desc.ptr(0), 1, 32, f);
+    }
+    for (int k = 0; k < nkf; ++k)
+        for (size_t i = 0; i < KF[k].mps.size(); ++i) {
+            int v[2] = {KF[k].mps[i] ? KF[k].mps[i]->id : -1, own[k][i].replacedBy ? own[k][i].replacedBy->id : -1};
+            fwrite(v, 4, 2, f);
+        }
     fclose(f);
     return 0;
 }
@@ -749,6 +856,7 @@ static int run_sim3(int argc, char** argv) {
     Reader Rd{raw.data()};
     const int variant = Rd.get<int>(), nkf = Rd.get<int>();
     const float th = Rd.get<float>();
+    projection_mode(argc, argv, 4);
     const int m = Rd.get<int>();
     const float* pos = Rd.arr<float>(3 * (size_t)m); const float* nrm = Rd.arr<float>(3 * (size_t)m);
     const float* maxd = Rd.arr<float>(m); const float* mind = Rd.arr<float>(m);
@@ -763,7 +871,7 @@ static int run_sim3(int argc, char** argv) {
     }
     MockFuseKF KF[2];
     for (int k = 0; k < nkf && k < 2; ++k) read_kf(Rd, KF[k], pts);
-    ORBmatcher matcher(0.75f, true);
+    ORBmatcher matcher(0.75f, true, g_device_projection);
     std::vector<int> out;
     int count = 0;
     if (variant == 0 || variant == 1) {
@@ -1107,6 +1215,7 @@ int main(int argc, char** argv) {
     if (mode == "search") return run_search(argc, argv);
     if (mode == "frame") return run_frame(argc, argv);
     if (mode == "fuse") return run_fuse(argc, argv);
+    if (mode == "fuse_targets") return run_fuse_targets(argc, argv);
     if (mode == "init") return run_init(argc, argv);
     if (mode == "bow") return run_bow(argc, argv);
     if (mode == "sim3") return run_sim3(argc, argv);

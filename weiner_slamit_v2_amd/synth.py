@@ -536,6 +536,56 @@ def synth_frustum(seed=0, n=1000, th=1.0, n_levels=8, width=640, height=480, ski
                 pos=pos, normal=normal, max_dist=max_dist, min_dist=min_dist, skip=skip, true=dict(e=e, angle=ang, Xc=Xc))
 
 
+PROJECT_FORMS = ("LAST_FRAME", "RELOC", "FUSE", "SIM3_PROJ", "SIM3_FUSE", "SIM3_PAIR")   # api.PROJECT_FORMS: the index is slamit_project_camera.form
+
+
+def synth_project(seed=0, n=1000, form="FUSE", th=3.0, direction=0, n_levels=8, scale=1.3, octave_frac=0.06, **kw):
+    """One camera of one of the six projection loops in front of the guided search (csrc/project.h) and n map points around its view
+    cone, so that every test of every form rejects a visible share: synth_frustum's construction (its camera, points, normals,
+    distance ranges and skip flags; **kw goes to it), recast per form.
+      LAST_FRAME  R, t, O are the frame's; octave is uniform over the table, with a share octave_frac each of -1 and of n_levels
+                  (the level outside the table); direction 0, 1 (forward) or 2 (backward) picks the level window
+      RELOC, FUSE R, t, O are the frame's / keyframe's
+      SIM3_PROJ, SIM3_FUSE  Scw = [scale R | scale t] in float32, and R, t, O out of it as sim3detail::decompose takes them
+      SIM3_PAIR   the points' keyframe has a pose of its own (R, t); (R2, t2) = (sR21, t21) of SearchBySim3 with s12 = scale, so the
+                  point arrives in the searched camera at 1 / scale of its depth; max_dist and min_dist are divided by scale with it
+    Arrays the form does not read are None.  Layout of slamit_project_problem."""
+    f32, f64 = np.float32, np.float64
+    k = PROJECT_FORMS.index(form) if isinstance(form, str) else int(form)
+    b = synth_frustum(seed, n, th, n_levels=n_levels, **kw)
+    rs = np.random.RandomState(16000 + 8 * seed + k)
+    Rcw, tcw = b["Rcw"].reshape(3, 3), b["tcw"]
+    out = dict(n=n, form=k, direction=int(direction), R=b["Rcw"], t=tcw, O=b["Ow"], R2=np.zeros(9, f32), t2=np.zeros(3, f32), th=f32(th),
+               pos=b["pos"], normal=b["normal"], max_dist=b["max_dist"], min_dist=b["min_dist"], octave=None, skip=b["skip"], true=dict(b["true"]))
+    for key in ("fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y", "log_scale_factor", "n_levels", "scale_factors"):
+        out[key] = b[key]
+    if k == 0:
+        octave = rs.randint(0, n_levels, n).astype(np.int32)
+        pick = rs.rand(n)
+        octave[pick < octave_frac] = -1
+        octave[pick > 1.0 - octave_frac] = n_levels
+        out.update(octave=octave, normal=None, max_dist=None, min_dist=None)
+    elif k == 1:
+        out.update(normal=None)
+    elif k in (3, 4):
+        Scw = np.concatenate([f32(scale) * Rcw, (f32(scale) * tcw)[:, None]], 1).astype(f32)
+        scw = f32(np.sqrt((Scw[0, :3].astype(f64) ** 2).sum()))
+        R, t = (Scw[:, :3] / scw).astype(f32), (Scw[:, 3] / scw).astype(f32)
+        O = (-(R.astype(f64).T @ t.astype(f64))).astype(f32)
+        out.update(R=R.reshape(9), t=t, O=O, true=dict(out["true"], Scw=Scw))
+    elif k == 5:
+        R1, t1 = se3_exp(np.concatenate([rs.uniform(-0.3, 0.3, 3), rs.uniform(-1.0, 1.0, 3)]))
+        R1w, t1w = R1.astype(f32), t1.astype(f32)
+        R12 = (R1w.astype(f64) @ Rcw.astype(f64).T).astype(f32)                       # x1 = s12 R12 x2 + t12
+        t12 = (t1w.astype(f64) - R12.astype(f64) @ tcw.astype(f64)).astype(f32)
+        s12 = f32(scale)
+        sR21 = ((1.0 / f64(s12)) * R12.T.astype(f64)).astype(f32)                       # ORBmatcher.cc:1120
+        t21 = (-(sR21.astype(f64) @ t12.astype(f64))).astype(f32)                       # :1121
+        out.update(R=R1w.reshape(9), t=t1w, O=np.zeros(3, f32), R2=sR21.reshape(9), t2=t21, normal=None,
+                   max_dist=(b["max_dist"] / s12).astype(f32), min_dist=(b["min_dist"] / s12).astype(f32))
+    return out
+
+
 def synth_map(n_kf, n_pt, obs_per_pt, n_fixed, seed, stereo_frac=0.0, loop=True, outlier_frac=0.03, baseline=0.08):
     """A map-sized BA window (slamit_ba_problem layout, as synth_ba): n_kf cameras on a circle of radius 2 in the x-z plane, each looking
     outward, and n_pt points on a cylinder of radius 6 around it.  loop=True: the trajectory closes (keyframe k at 2 pi k / n_kf), so the
