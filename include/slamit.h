@@ -10,6 +10,7 @@
  *   slamit_orb_level    <- public member ORBextractor::mvImagePyramid    include/ORBextractor.h:85
  *   slamit_hamming_*    <- ORBmatcher::DescriptorDistance + best/second  src/ORBmatcher.cc:1651-1667, 85-117,
  *                          selection loops                               440-461, 1404-1428
+ *   slamit_stereo_*     <- Frame::ComputeStereoMatches                   src/Frame.cc:591-763
  *   slamit_ba_*         <- Optimizer::LocalBundleAdjustment (the g2o     src/Optimizer.cc:453-778 and
  *                          BlockSolver_6_3 + Levenberg it instantiates)  Thirdparty/g2o/g2o/core/block_solver.hpp
  *
@@ -113,6 +114,26 @@ int slamit_orb_profile(slamit_orb* h, int enable, float* stage_ms, int32_t* stag
  * *w,*h are the un-padded level size, the plane is (*h+38) rows of (*w+38) bytes. */
 int slamit_orb_level(slamit_orb* h, int frame, int level, uint8_t* dst, size_t dst_bytes, int* w,
                      int* h_out);
+
+/* Where mvImagePyramid of the last extract call lives in HBM, for callers that read the planes on the device (slamit_stereo_match*):
+ * frame f of level l is level[l].plane + f * level[l].frame_stride, h rows of `stride` bytes of which the first w are pixels (no
+ * border).  Level 0 is the image the extract call was given (the caller's device buffer for the _dev form, the handle's staging
+ * copy for the host forms) with that call's strides; levels >= 1 are the handle's own planes.  The pointers are valid until the
+ * next extract call on the handle.  SLAMIT_ERR_STATE before the first extract call, and for a handle created with an empty image. */
+typedef struct slamit_pyramid_level {
+    const uint8_t* plane;   /* DEVICE pointer: frame 0 of the level */
+    int32_t w, h;
+    size_t stride;          /* bytes between rows */
+    size_t frame_stride;    /* bytes between the frames of a batch */
+} slamit_pyramid_level;
+
+typedef struct slamit_pyramid_view {
+    int32_t nlevels;
+    int32_t nframes;        /* frames of the extract call the planes belong to */
+    slamit_pyramid_level level[SLAMIT_MAX_LEVELS];
+} slamit_pyramid_view;
+
+int slamit_orb_pyramid_view(const slamit_orb* h, slamit_pyramid_view* out);
 
 /* Stage outputs of the last extract call, for parity debugging (host buffers):
  *  candidates of (frame, level) before the octree as (x, y, score) int32 triplets, x/y relative
@@ -889,6 +910,72 @@ typedef struct slamit_rotation_batch {
     int32_t* d_bins;               /* [nframes][3] out */
 } slamit_rotation_batch;
 int slamit_rotation_check_batch_dev(int device, const slamit_rotation_batch* batch, void* stream);
+
+/* ---- Stereo matching: Frame::ComputeStereoMatches (src/Frame.cc:591-763) -------------------------------------------
+ * From two ORBextractor calls on a rectified pair to mvuRight / mvDepth, on the pyramids the two calls left in HBM.  Per left
+ * keypoint: the right keypoints whose row band (y +- 2 scale[octave]) holds row (int)vL, gated by octave (+-1) and by
+ * uR in [uL - mbf / mb, uL + 3]; the least Hamming distance strictly below TH_HIGH = 100, the smallest right index on ties; at the
+ * left keypoint's level an 11 x 11 patch minus its centre against 11 shifts of the right image (L1, exact integers); a parabola
+ * through the best shift and its neighbours; disparity and depth; then, over the frame, every match whose SAD is not below
+ * 1.5f * 1.4f * median is removed.  float / double exactly where the reference has them (csrc/stereo.h).
+ * status[i] is where the walk of left keypoint i ended:
+ *   0 matched   1 no right keypoint in the row, or uL + 3 < 0   2 none under TH_HIGH   3 the reference's right-window test
+ *   4 best shift at -5 or +5   5 deltaR outside [-1, 1]   6 disparity outside [0, mbf / mb) (a NaN deltaR ends here)
+ *   7 removed by the median filter   8 departure
+ * u_right = depth = -1 unless status is 0; best_r / ham_dist are the chosen right keypoint and its distance (statuses 0, 3 .. 7, and
+ * 8 when it was reached after the selection), sad_dist the best shift's sum (0, 4 .. 7); -1 where the walk did not get there.
+ * DEPARTURES, where the reference reads out of bounds, throws or has undefined behaviour: a left keypoint is status 8 when its
+ * octave, or its chosen right keypoint's, is outside [0, nlevels); when uL or vL is not finite; when (int)vL is outside [0, rows);
+ * when its 11 x 11 window leaves the left plane of its level; when the right 11 x 21 strip (columns scaleduR0 - 10 .. scaleduR0 + 10,
+ * rows scaledvL +- 5) leaves the right plane, which the reference's own test admits for scaleduR0 in [0, 10).  A right keypoint's
+ * band is clamped to [0, rows); one with a coordinate that is not finite has none; one with an octave outside the table takes the
+ * nearest level's.  An empty match list skips the median (the reference indexes an empty vector).  No device read depends on
+ * these being absent; the extractor's own keypoints never meet them (they lie 16 level pixels inside their plane).
+ * At most SLAMIT_STEREO_MAX_KP keypoints per side (the selection packs the right index into 16 bits beside the distance): more
+ * fails with SLAMIT_ERR_CAPACITY and a message before anything is launched. */
+#define SLAMIT_STEREO_MAX_KP 8191          /* = SLAMIT_SEARCH_MAX_KP */
+
+/* Everything resident in HBM; frame f of the batch is frame f of both views.  Keypoints, descriptors and counts are in the layout
+ * slamit_orb_extract_batch_dev writes ([nframes][cap], d_n clamped to [0, cap]; descriptors 16-byte aligned); d_mb / d_mbf hold one
+ * float per frame, d_scale / d_inv_scale SLAMIT_MAX_LEVELS floats (mvScaleFactors, mvInvScaleFactors).  The views may be
+ * slamit_orb_pyramid_view's or describe any planes of the caller's; both need the same nlevels and nframes >= the batch's; the
+ * row table has left.level[0].h rows.  Outputs are [nframes][cap_left], d_n_matched [nframes] (matches with status 0).  Entries
+ * past a frame's count are neither read nor written.  Asynchronous on `stream` (NULL: the legacy default stream of `device`), no
+ * synchronisation, no state: three launches, with nothing through the host. */
+typedef struct slamit_stereo_batch {
+    int32_t nframes, cap_left, cap_right, reserved;
+    slamit_pyramid_view left, right;
+    const slamit_kp* d_kps_left;   /* [nframes][cap_left] (pt and octave are read) */
+    const uint8_t* d_desc_left;    /* [nframes][cap_left][32] */
+    const int32_t* d_n_left;       /* [nframes] */
+    const slamit_kp* d_kps_right;  /* [nframes][cap_right] */
+    const uint8_t* d_desc_right;   /* [nframes][cap_right][32] */
+    const int32_t* d_n_right;      /* [nframes] */
+    const float* d_mb;             /* [nframes]: Frame::mb */
+    const float* d_mbf;            /* [nframes]: Frame::mbf */
+    const float* d_scale;          /* [SLAMIT_MAX_LEVELS] */
+    const float* d_inv_scale;      /* [SLAMIT_MAX_LEVELS] */
+    void* d_workspace;             /* slamit_stereo_match_workspace(nframes, cap_right) bytes, 16-byte aligned */
+    size_t workspace_bytes;
+    float* d_u_right;              /* [nframes][cap_left] out: mvuRight */
+    float* d_depth;                /* [nframes][cap_left] out: mvDepth */
+    uint8_t* d_status;             /* [nframes][cap_left] out */
+    int32_t* d_best_r;             /* [nframes][cap_left] out */
+    int32_t* d_ham_dist;           /* [nframes][cap_left] out */
+    int32_t* d_sad_dist;           /* [nframes][cap_left] out */
+    int32_t* d_n_matched;          /* [nframes] out */
+} slamit_stereo_batch;
+size_t slamit_stereo_match_workspace(int nframes, int cap_right);
+int slamit_stereo_match_batch_dev(int device, const slamit_stereo_batch* batch, void* stream);
+
+/* One pair, host pointers, synchronous: frame `frame` of the two handles' last extract calls (which must have completed: the
+ * host extract forms have, after a _dev form the caller synchronises its stream first), keypoints and descriptors as the
+ * reference's Frame holds them (mvKeys / mvKeysRight, mDescriptors / mDescriptorsRight).  One staged call.  Handles that differ in
+ * device, image size, level count or scale factor fail with SLAMIT_ERR_ARG; outputs have n_left entries; best_r, ham_dist,
+ * sad_dist and n_matched may be NULL. */
+int slamit_stereo_match(slamit_orb* left, slamit_orb* right, int frame, const slamit_kp* kps_left, const uint8_t* desc_left, int n_left,
+                        const slamit_kp* kps_right, const uint8_t* desc_right, int n_right, float mb, float mbf, float* u_right, float* depth,
+                        uint8_t* status, int32_t* best_r, int32_t* ham_dist, int32_t* sad_dist, int32_t* n_matched);
 
 /* ---- misc -------------------------------------------------------------------------------- */
 

@@ -189,6 +189,27 @@ class RotationBatch(C.Structure):
                 ("d_bins", C.c_void_p)]
 
 
+class PyramidLevel(C.Structure):
+    _fields_ = [("plane", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32), ("stride", C.c_size_t), ("frame_stride", C.c_size_t)]
+
+
+class PyramidView(C.Structure):
+    _fields_ = [("nlevels", C.c_int32), ("nframes", C.c_int32), ("level", PyramidLevel * 16)]
+
+
+class StereoBatch(C.Structure):
+    _fields_ = [("nframes", C.c_int32), ("cap_left", C.c_int32), ("cap_right", C.c_int32), ("reserved", C.c_int32), ("left", PyramidView),
+                ("right", PyramidView), ("d_kps_left", C.c_void_p), ("d_desc_left", C.c_void_p), ("d_n_left", C.c_void_p),
+                ("d_kps_right", C.c_void_p), ("d_desc_right", C.c_void_p), ("d_n_right", C.c_void_p), ("d_mb", C.c_void_p), ("d_mbf", C.c_void_p),
+                ("d_scale", C.c_void_p), ("d_inv_scale", C.c_void_p), ("d_workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("d_u_right", C.c_void_p), ("d_depth", C.c_void_p), ("d_status", C.c_void_p), ("d_best_r", C.c_void_p), ("d_ham_dist", C.c_void_p),
+                ("d_sad_dist", C.c_void_p), ("d_n_matched", C.c_void_p)]
+
+
+STEREO_MAX_KP = 8191   # SLAMIT_STEREO_MAX_KP
+STEREO_STATUS = ("matched", "no_candidate", "no_descriptor", "right_window", "edge_shift", "delta", "disparity", "median", "departure")
+
+
 PROJECT_MAX_N = 65536   # SLAMIT_PROJECT_MAX_N
 PROJECT_FORMS = ("LAST_FRAME", "RELOC", "FUSE", "SIM3_PROJ", "SIM3_FUSE", "SIM3_PAIR")   # SLAMIT_PROJECT_*: the index is the form
 PROJECT_CAMERA_DTYPE = np.dtype([("form", "<i4"), ("R", "<f4", 9), ("t", "<f4", 3), ("O", "<f4", 3), ("R2", "<f4", 9), ("t2", "<f4", 3), ("fx", "<f4"),
@@ -248,7 +269,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_rotation_check_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -305,6 +326,11 @@ def lib():
         L.slamit_project.argtypes = [i32, C.POINTER(ProjectProblem), C.POINTER(ProjectResult)]
         L.slamit_project_batch_dev.argtypes = [i32, C.POINTER(ProjectBatchRec), vp]
         L.slamit_rotation_check_batch_dev.argtypes = [i32, C.POINTER(RotationBatch), vp]
+        L.slamit_orb_pyramid_view.argtypes = [vp, C.POINTER(PyramidView)]
+        L.slamit_stereo_match_workspace.argtypes = [i32, i32]
+        L.slamit_stereo_match_workspace.restype = sz
+        L.slamit_stereo_match_batch_dev.argtypes = [i32, C.POINTER(StereoBatch), vp]
+        L.slamit_stereo_match.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, i32, f32, f32] + [vp] * 7
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
         L.slamit_voc_load_text.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
@@ -479,6 +505,14 @@ class ORBextractor:
         _check(lib().slamit_orb_level(self._h, frame, level, _np_ptr(out), out.size, C.byref(w), C.byref(h)),
                "slamit_orb_level")
         return out
+
+    def pyramid_view(self):
+        """slamit_pyramid_view of the last extract call: where its planes lie in HBM (valid until the next call)."""
+        v = PyramidView()
+        if self._h is None:
+            raise SlamitError("slamit_orb_pyramid_view failed (-4): no extract call yet")
+        _check(lib().slamit_orb_pyramid_view(self._h, C.byref(v)), "slamit_orb_pyramid_view")
+        return v
 
     def blurred(self, frame, level):
         """The blurred level (h, w) the descriptors of `frame` of the last call were sampled from."""
@@ -1579,3 +1613,76 @@ def project_batch_dev(t, device=0, stream=None):
                           t["min_dist"].data_ptr(), t["octave"].data_ptr(), t["skip"].data_ptr(), t["uvr"].data_ptr(), t["level_min"].data_ptr(),
                           t["level_max"].data_ptr(), t["valid"].data_ptr(), opt("status"), opt("proj"), opt("level"), opt("n_valid"))
     _check(lib().slamit_project_batch_dev(device, C.byref(rec), stream), "slamit_project_batch_dev")
+
+
+# ---- Frame::ComputeStereoMatches ------------------------------------------------------------------------------------------------
+
+_STEREO_OUT = (("u_right", np.float32), ("depth", np.float32), ("status", np.uint8), ("best_r", np.int32), ("ham_dist", np.int32), ("sad_dist", np.int32))
+
+
+def stereo_match(ext_left, ext_right, kps_left, desc_left, kps_right, desc_right, mb, mbf, frame=0):
+    """Frame::ComputeStereoMatches on frame `frame` of the two extractors' last calls; keypoints (KP_DTYPE) and descriptors (n, 32)
+    from the host, as the reference's Frame holds them.  -> dict u_right, depth (mvuRight, mvDepth), status, best_r, ham_dist,
+    sad_dist (n_left each) and n_matched."""
+    for e in (ext_left, ext_right):
+        if e._h is None:
+            raise SlamitError("stereo_match failed (-4): an extractor has no extract call yet")
+    kl, kr = np.ascontiguousarray(kps_left, KP_DTYPE), np.ascontiguousarray(kps_right, KP_DTYPE)
+    dl, dr = np.ascontiguousarray(desc_left, np.uint8).reshape(-1, 32), np.ascontiguousarray(desc_right, np.uint8).reshape(-1, 32)
+    if len(dl) != len(kl) or len(dr) != len(kr):
+        raise SlamitError("stereo_match: one descriptor row per keypoint")
+    n = len(kl)
+    out = {k: np.zeros(n, t) for k, t in _STEREO_OUT}
+    nm = C.c_int32(0)
+    _check(lib().slamit_stereo_match(ext_left._h, ext_right._h, frame, _np_ptr(kl), _np_ptr(dl), n, _np_ptr(kr), _np_ptr(dr), len(kr), float(mb),
+                                     float(mbf), *[_np_ptr(out[k]) for k, _ in _STEREO_OUT], C.byref(nm)), "slamit_stereo_match")
+    out["n_matched"] = int(nm.value)
+    return out
+
+
+def stereo_planes_view(planes):
+    """slamit_pyramid_view over the caller's own planes: a list, one torch uint8 CUDA tensor (B, h, w) per level; rows and frames
+    may be strided, pixels of a row are adjacent."""
+    v = PyramidView()
+    v.nlevels, v.nframes = len(planes), int(planes[0].shape[0]) if planes else 0
+    if len(planes) > MAX_LEVELS:
+        raise SlamitError("stereo_planes_view: more than SLAMIT_MAX_LEVELS levels")
+    for l, p in enumerate(planes):
+        if p.dim() != 3 or p.element_size() != 1 or (p.shape[2] > 1 and p.stride(2) != 1) or p.shape[0] != v.nframes:
+            raise SlamitError("stereo_planes_view: level %d is not a (B, h, w) byte tensor with adjacent pixels" % l)
+        v.level[l] = PyramidLevel(p.data_ptr(), int(p.shape[2]), int(p.shape[1]), int(p.stride(1)), int(p.stride(0)))
+    return v
+
+
+def stereo_match_workspace(nframes, cap_right):
+    return int(lib().slamit_stereo_match_workspace(nframes, cap_right))
+
+
+def stereo_match_batch_dev(t, device=0, stream=None):
+    """The resident form.  t: dict with left / right: a PyramidView (ORBextractor.pyramid_view()) or a list of per-level torch
+    tensors (stereo_planes_view); torch CUDA tensors kps_left (B, cap_l, 7) f32 rows of KP_DTYPE, desc_left (B, cap_l, 32) u8,
+    n_left (B) i32, the same for right, mb / mbf (B) f32, scale / inv_scale (16) f32, workspace (u8, stereo_match_workspace bytes)
+    and the outputs u_right / depth (B, cap_l) f32, status (B, cap_l) u8, best_r / ham_dist / sad_dist (B, cap_l) i32, n_matched (B)
+    i32.  Asynchronous on `stream`."""
+    views = [v if isinstance(v, PyramidView) else stereo_planes_view(v) for v in (t["left"], t["right"])]
+    b, cap_l, cap_r = t["n_left"].numel(), t["kps_left"].shape[1], t["kps_right"].shape[1]
+    for side, cap in (("left", cap_l), ("right", cap_r)):
+        k, d = t["kps_" + side], t["desc_" + side]
+        if k.numel() * k.element_size() != b * cap * KP_DTYPE.itemsize or d.numel() != b * cap * 32 or not k.is_contiguous() or not d.is_contiguous():
+            raise SlamitError("stereo_match_batch_dev: %s keypoints / descriptors are not contiguous (B, cap) arrays" % side)
+    for key, _ in _STEREO_OUT:
+        if t[key].numel() != b * cap_l or not t[key].is_contiguous():
+            raise SlamitError("stereo_match_batch_dev: %s is not a contiguous (B, cap_left) array" % key)
+    for key in ("n_right", "mb", "mbf", "n_matched"):
+        if t[key].numel() != b:
+            raise SlamitError("stereo_match_batch_dev: %s does not have one entry per frame" % key)
+    for key in ("scale", "inv_scale"):
+        if t[key].numel() != MAX_LEVELS or t[key].element_size() != 4:
+            raise SlamitError("stereo_match_batch_dev: %s does not hold SLAMIT_MAX_LEVELS floats" % key)
+    ws = t.get("workspace")
+    rec = StereoBatch(b, cap_l, cap_r, 0, views[0], views[1], t["kps_left"].data_ptr(), t["desc_left"].data_ptr(), t["n_left"].data_ptr(),
+                      t["kps_right"].data_ptr(), t["desc_right"].data_ptr(), t["n_right"].data_ptr(), t["mb"].data_ptr(), t["mbf"].data_ptr(),
+                      t["scale"].data_ptr(), t["inv_scale"].data_ptr(), ws.data_ptr() if ws is not None else None,
+                      ws.numel() * ws.element_size() if ws is not None else 0, t["u_right"].data_ptr(), t["depth"].data_ptr(), t["status"].data_ptr(),
+                      t["best_r"].data_ptr(), t["ham_dist"].data_ptr(), t["sad_dist"].data_ptr(), t["n_matched"].data_ptr())
+    _check(lib().slamit_stereo_match_batch_dev(device, C.byref(rec), stream), "slamit_stereo_match_batch_dev")

@@ -448,6 +448,23 @@ int slamit_orb_level(slamit_orb* h, int frame, int level, uint8_t* dst, size_t d
     return SLAMIT_OK;
 }
 
+int slamit_orb_pyramid_view(const slamit_orb* h, slamit_pyramid_view* out) {
+    if (!h || !out) return slamit_fail(SLAMIT_ERR_ARG, "slamit_orb_pyramid_view: null argument");
+    memset(out, 0, sizeof(*out));
+    if (h->p.width == 0 || h->p.height == 0) return slamit_fail(SLAMIT_ERR_STATE, "slamit_orb_pyramid_view: empty image");
+    if (!h->last_img0 || h->last_nframes < 1) return slamit_fail(SLAMIT_ERR_STATE, "slamit_orb_pyramid_view: no extract call yet");
+    out->nlevels = h->nlevels; out->nframes = h->last_nframes;
+    for (int l = 0; l < h->nlevels; ++l) {
+        const OrbLevel& L = h->pl.levels[l];
+        slamit_pyramid_level& V = out->level[l];
+        V.plane = l == 0 ? h->last_img0 : h->d_pyr + L.plane_off;
+        V.w = L.w; V.h = L.h;
+        V.stride = l == 0 ? h->last_stride : (size_t)L.stride;
+        V.frame_stride = l == 0 ? h->last_frame : h->pl.pyr_frame_total;
+    }
+    return SLAMIT_OK;
+}
+
 int slamit_orb_debug_blurred(slamit_orb* h, int frame, int level, uint8_t* dst, size_t dst_bytes, int* w, int* h_out) {
     if (!h || level < 0 || level >= h->nlevels) return slamit_fail(SLAMIT_ERR_ARG, "slamit_orb_debug_blurred: bad level");
     if (h->p.width == 0 || h->p.height == 0) return slamit_fail(SLAMIT_ERR_STATE, "slamit_orb_debug_blurred: empty image");
@@ -492,3 +509,6 @@ int slamit_orb_debug_candidates(slamit_orb* h, int frame, int level, int32_t* xy
 }
 
 }  // extern "C"
+
+// stereo.hip: the device a handle was created on
+int slamit_orb_device_of(const slamit_orb* h) { return h ? h->device : -1; }

@@ -46,6 +46,9 @@ struct SlamitDeviceGuard {
 // frustum.hip: d_count[f] = number of nonzero flags among the first min(d_m[f], q_cap) of d_valid[f][q_cap], one wavefront per frame
 hipError_t slamit_launch_valid_count(const uint8_t* d_valid, const int32_t* d_m, int q_cap, int nframes, int32_t* d_count, hipStream_t stream);
 
+struct slamit_orb;
+int slamit_orb_device_of(const slamit_orb* h);   // orb_api.hip: the device of a handle (-1 for none)
+
 int slamit_default_device();   // slamit_set_device() of this thread, or the current device
 
 // The library's environment switches, read by slamit_read_switches() when a handle is created.

@@ -10,6 +10,14 @@
 // Members used on the caller's type (all from include/Frame.h): N, mvKeys, mvKeysUn, mK (3x3 CV_32F), mDistCoef (4x1 or
 // 5x1 CV_32F), mGrid[FRAME_GRID_COLS][FRAME_GRID_ROWS] (std::vector<std::size_t>), and the statics mnMinX, mnMaxX, mnMinY,
 // mnMaxY, mfGridElementWidthInv, mfGridElementHeightInv.
+//
+// Frame::ComputeStereoMatches (:591-763) forwards the same way:
+//
+//     void Frame::ComputeStereoMatches() { ORB_SLAM2::FrameOps::ComputeStereoMatches(*this); }
+//
+// It reads mvKeys, mvKeysRight, mDescriptors, mDescriptorsRight, mb, mbf and the two extractors (mpORBextractorLeft / Right, the
+// shim's, whose last calls left both pyramids in HBM: no SetPyramidExport) and writes mvuRight and mvDepth.  include/slamit.h lists
+// where the device walk departs from the reference (status 8: out-of-range octaves, rows and windows the reference reads anyway).
 #ifndef SLAMIT_SHIM_FRAMEOPS_H
 #define SLAMIT_SHIM_FRAMEOPS_H
 
@@ -84,6 +92,35 @@ void UndistortAndAssign(FrameT& F) {
             cell.reserve(c1 - c0);
             for (int j = c0; j < c1; ++j) cell.push_back((std::size_t)items[j]);
         }
+}
+
+// Frame::ComputeStereoMatches: one staged device call on the two extractors' pyramids.  A failure leaves every keypoint unmatched
+// (-1) and its code in LastStatus(); `status` (optional) receives the per-keypoint codes of include/slamit.h.
+template <class FrameT>
+void ComputeStereoMatches(FrameT& F, std::vector<uint8_t>* status = 0) {
+    static_assert(sizeof(cv::KeyPoint) == sizeof(slamit_kp), "cv::KeyPoint must be the 28-byte record");
+    const int nl = (int)F.mvKeys.size(), nr = (int)F.mvKeysRight.size();
+    F.mvuRight.assign(nl, -1.0f);
+    F.mvDepth.assign(nl, -1.0f);
+    if (status) status->assign(nl, 1);
+    lastStatus() = SLAMIT_OK;
+    if (nl == 0) return;
+    if (!F.mpORBextractorLeft || !F.mpORBextractorRight || F.mDescriptors.rows != nl || F.mDescriptorsRight.rows != nr) {
+        shim::refuse<Status>("FrameOps::ComputeStereoMatches: extractors or descriptors missing");
+        return;
+    }
+    std::vector<uint8_t> dl((size_t)nl * 32), dr((size_t)std::max(nr, 1) * 32), st((size_t)nl);
+    for (int i = 0; i < nl; ++i) memcpy(&dl[(size_t)i * 32], F.mDescriptors.ptr(i), 32);
+    for (int i = 0; i < nr; ++i) memcpy(&dr[(size_t)i * 32], F.mDescriptorsRight.ptr(i), 32);
+    std::vector<float> u(nl), d(nl);
+    const int rc = slamit_stereo_match(F.mpORBextractorLeft->Handle(), F.mpORBextractorRight->Handle(), 0,
+                                       reinterpret_cast<const slamit_kp*>(F.mvKeys.data()), dl.data(), nl,
+                                       reinterpret_cast<const slamit_kp*>(F.mvKeysRight.data()), dr.data(), nr, F.mb, F.mbf, u.data(), d.data(),
+                                       st.data(), 0, 0, 0, 0);
+    if (rc != SLAMIT_OK) { shim::report<Status>("slamit_stereo_match", rc); return; }
+    F.mvuRight.swap(u);
+    F.mvDepth.swap(d);
+    if (status) status->swap(st);
 }
 
 }  // namespace FrameOps

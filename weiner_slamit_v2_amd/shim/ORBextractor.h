@@ -40,14 +40,16 @@ public:
     std::vector<float> GetScaleSigmaSquares() { return mvLevelSigma2; }
     std::vector<float> GetInverseScaleSigmaSquares() { return mvInvLevelSigma2; }
 
-    // Filled after each operator() only when pyramid export is on (stereo matching reads it,
-    // Frame.cc:596-703; the monocular path never does, so the default skips the 1.2 MB copy).
+    // Filled after each operator() only when pyramid export is on.  Nothing in the shim needs it: stereo matching
+    // (Frame.cc:596-703) runs on the device through FrameOps::ComputeStereoMatches and Handle(); a caller that reads
+    // the planes on the host switches the 1.2 MB copy on.
     std::vector<cv::Mat> mvImagePyramid;
     void SetPyramidExport(bool on) { exportPyramid = on; }
 
     // slamit additions
     void SetDevice(int device);          // before the first call; default 0
     bool ok() const { return lastStatus == 0; }
+    slamit_orb* Handle() const { return handle; }   // for FrameOps::ComputeStereoMatches: the pyramid of the last call stays in HBM
     const char* lastError() const;
 
 private:

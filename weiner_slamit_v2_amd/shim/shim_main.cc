@@ -15,6 +15,7 @@
 //     shim_test sim3solver <problem.bin> <out.bin>
 //     shim_test triangulate <problem.bin> <out.bin>
 //     shim_test frustum <problem.bin> <out.bin>
+//     shim_test stereo <pair.bin> <out.bin>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1205,6 +1206,49 @@ static int run_frustum(int argc, char** argv) {
     return 0;
 }
 
+// Frame::ComputeStereoMatches through FrameOps.h: a mock Frame with the members the reference's has, two shim extractors, no pyramid export.
+// pair.bin: int32 w h nfeatures nlevels ; float mb mbf ; u8 left[w h] right[w h]
+// out.bin: int32 status nL nR ; cv::KeyPoint left[nL] ; u8 desc[32 nL] ; cv::KeyPoint right[nR] ; u8 desc[32 nR] ; float mvuRight[nL] mvDepth[nL] ;
+//   u8 status[nL]
+struct MockStereoFrame {
+    std::vector<cv::KeyPoint> mvKeys, mvKeysRight;
+    cv::Mat mDescriptors, mDescriptorsRight;
+    float mb, mbf;
+    ORBextractor* mpORBextractorLeft;
+    ORBextractor* mpORBextractorRight;
+    std::vector<float> mvuRight, mvDepth;
+};
+
+static int run_stereo(int argc, char** argv) {
+    if (argc < 4) return 2;
+    std::vector<unsigned char> raw = slurp(argv[2]);
+    Reader R{raw.data()};
+    const int w = R.get<int>(), h = R.get<int>(), nfeatures = R.get<int>(), nlevels = R.get<int>();
+    MockStereoFrame F;
+    F.mb = R.get<float>(); F.mbf = R.get<float>();
+    if (raw.size() != 24 + 2 * (size_t)w * h) return 2;
+    cv::Mat imL(h, w, CV_8UC1, (void*)R.arr<unsigned char>((size_t)w * h)), imR(h, w, CV_8UC1, (void*)R.arr<unsigned char>((size_t)w * h));
+    ORBextractor left(nfeatures, 1.2f, nlevels, 20, 7), right(nfeatures, 1.2f, nlevels, 20, 7);   // Tracking.cc:149-159
+    F.mpORBextractorLeft = &left; F.mpORBextractorRight = &right;
+    left(imL, cv::Mat(), F.mvKeys, F.mDescriptors);                                                // Frame.cc:93-96, without the threads
+    right(imR, cv::Mat(), F.mvKeysRight, F.mDescriptorsRight);
+    if (!left.ok() || !right.ok()) { fprintf(stderr, "extract failed: %s\n", left.lastError()); return 1; }
+    std::vector<uint8_t> st;
+    FrameOps::ComputeStereoMatches(F, &st);
+    const int status = FrameOps::LastStatus(), nL = (int)F.mvKeys.size(), nR = (int)F.mvKeysRight.size();
+    if (status != 0) fprintf(stderr, "stereo failed: %s\n", slamit_last_error());
+    FILE* f = fopen(argv[3], "wb");
+    if (!f) return 2;
+    fwrite(&status, 4, 1, f); fwrite(&nL, 4, 1, f); fwrite(&nR, 4, 1, f);
+    if (nL) fwrite(&F.mvKeys[0], sizeof(cv::KeyPoint), nL, f);
+    for (int i = 0; i < nL; ++i) fwrite(F.mDescriptors.ptr(i), 1, 32, f);
+    if (nR) fwrite(&F.mvKeysRight[0], sizeof(cv::KeyPoint), nR, f);
+    for (int i = 0; i < nR; ++i) fwrite(F.mDescriptorsRight.ptr(i), 1, 32, f);
+    fwrite(F.mvuRight.data(), 4, nL, f); fwrite(F.mvDepth.data(), 4, nL, f); fwrite(st.data(), 1, nL, f);
+    fclose(f);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     std::string mode = argv[1];
@@ -1223,5 +1267,6 @@ int main(int argc, char** argv) {
     if (mode == "sim3solver") return run_sim3solver(argc, argv);
     if (mode == "triangulate") return run_triangulate(argc, argv);
     if (mode == "frustum") return run_frustum(argc, argv);
+    if (mode == "stereo") return run_stereo(argc, argv);
     return 2;
 }

@@ -89,6 +89,26 @@ def warp_frame(frame, index=0, seed=FRAME_SEED):
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
+def synth_stereo_pair(width, height, index=0, d_min=2.0, d_max=None, seed=FRAME_SEED):
+    """A rectified pair for Frame::ComputeStereoMatches: left = synth_frame(width, height, index); right(x, y) = left(x + d(x, y), y)
+    with a smooth disparity field d in [d_min, d_max] (d_max: width / 16), linearly interpolated along the row, + noise +-1.
+    -> (left, right, d): a left column uL reappears near uR = uL - d in the right image."""
+    left = synth_frame(width, height, index, seed=seed)
+    rs = np.random.RandomState(((seed ^ 0x57E7E0) + index) & 0x7FFFFFFF)
+    if d_max is None:
+        d_max = width / 16.0
+    d = d_min + (d_max - d_min) * (0.5 + 0.5 * np.clip(_value_noise(rs, height, width, 96, 1.0), -1.0, 1.0))
+    sx = np.arange(width, dtype=np.float64)[None, :] + d
+    x0 = np.floor(sx)
+    fx = sx - x0
+    i0 = np.clip(x0.astype(np.int64), 0, width - 1)
+    i1 = np.clip(i0 + 1, 0, width - 1)
+    rows = np.arange(height)[:, None]
+    L = left.astype(np.float64)
+    right = L[rows, i0] * (1.0 - fx) + L[rows, i1] * fx + rs.randint(-1, 2, size=(height, width))
+    return left, np.ascontiguousarray(np.clip(np.rint(right), 0, 255).astype(np.uint8)), d
+
+
 def synth_batch(width, height, n, first=0, seed=FRAME_SEED):
     return np.stack([synth_frame(width, height, first + i, seed=seed) for i in range(n)])
 
