@@ -185,7 +185,8 @@ int slamit_distinctive_batch(const uint8_t* desc, const int32_t* offsets, int np
  * the reference's candidate order, accept, and MARK THE KEYPOINT TAKEN for the queries that follow
  * (the reference assigns F.mvpMapPoints[bestIdx] inside the loop).  Projection, viewing-cosine radius
  * and the rotation histogram stay with the caller (shim/ORBmatcher.h), except for SearchLocalPoints, whose
- * queries slamit_frustum* below writes in this layout.  Mono only (mvuRight < 0). */
+ * queries slamit_frustum* below writes in this layout.  slamit_guided_search is the monocular loop; the right-image test that
+ * three of the drivers apply to a stereo keypoint (mvuRight) is slamit_guided_search_stereo below. */
 typedef struct slamit_frame_view {
     int32_t n;                 /* keypoints */
     const float* kp_xy;        /* n x 2: mvKeysUn[i].pt */
@@ -236,6 +237,34 @@ typedef struct slamit_search_rule {
 int slamit_guided_search(int device, const slamit_frame_view* frame, const slamit_search_queries* queries,
                          const slamit_search_rule* rule, int32_t* match_kp, int32_t* nmatches, int32_t* best_dist,
                          int32_t* best_level, int32_t* second_dist, int32_t* second_level);
+
+/* The right-image gate of the three guided-search loops that read mvuRight.  It is one more test on a candidate
+ * keypoint idx, after the window and level tests and before the descriptor distance:
+ *   SLAMIT_SEARCH_ER_RADIUS  SearchByProjection(F, vpMapPoints, th) (src/ORBmatcher.cc:93-98; q_ur = mTrackProjXR) and
+ *       SearchByProjection(CurrentFrame, LastFrame, th, bMono) (:1411-1417; q_ur = u - mbf * invzc): when kp_ur[idx] > 0 the
+ *       candidate is skipped if fabs(q_ur - kp_ur[idx]) > r, r being the query's own uvr[3q + 2].  A NaN passes, as there; a
+ *       kp_ur of exactly 0 counts as monocular.
+ *   SLAMIT_SEARCH_ER_CHI2    Fuse(pKF, vpMapPoints, th) (:918-942), with rule->chi2_gate > 0: when kp_ur[idx] >= 0 the candidate is
+ *       skipped if ((u - x)^2 + (v - y)^2 + (q_ur - kp_ur[idx])^2) * inv_level_sigma2[octave] > chi2_gate_stereo (7.8); a keypoint
+ *       with kp_ur < 0 keeps the two-term test against rule->chi2_gate (5.99).  A kp_ur of exactly 0 counts as stereo.
+ * The relocalisation search and the three Sim3 drivers have no stereo branch in the reference: they use slamit_guided_search.
+ * NOT built: the mapping side (SearchForTriangulation with stereo keypoints or bOnlyStereo, CreateNewMapPoints' stereo branch).
+ * st == NULL or er_mode == SLAMIT_SEARCH_ER_NONE is slamit_guided_search.  An er_mode outside 0..2, q_ur_stride < 1, an er_mode
+ * other than 0 with rule->mode == 1, or with a null kp_ur / q_ur where there is work, fails with SLAMIT_ERR_ARG and a message
+ * before anything is launched or written. */
+enum { SLAMIT_SEARCH_ER_NONE = 0, SLAMIT_SEARCH_ER_RADIUS = 1, SLAMIT_SEARCH_ER_CHI2 = 2 };
+
+typedef struct slamit_search_stereo {
+    int32_t er_mode;            /* SLAMIT_SEARCH_ER_* */
+    float chi2_gate_stereo;     /* mode 2: 7.8 (ORBmatcher.cc:929) */
+    const float* kp_ur;         /* n: mvuRight of the searched frame / keyframe */
+    const float* q_ur;          /* query q at q_ur[q * q_ur_stride] */
+    int32_t q_ur_stride;        /* 1, or 3 with q_ur = slamit_frustum_result.proj + 2 */
+} slamit_search_stereo;
+
+int slamit_guided_search_stereo(int device, const slamit_frame_view* frame, const slamit_search_queries* queries,
+                                const slamit_search_rule* rule, const slamit_search_stereo* st, int32_t* match_kp, int32_t* nmatches,
+                                int32_t* best_dist, int32_t* best_level, int32_t* second_dist, int32_t* second_level);
 
 /* ---- Vocabulary-node search (beyond SURVEY.md §8f: the BoW drivers of ORBmatcher) ----------------------
  * The loop bodies of ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...) (src/ORBmatcher.cc:161-290),
@@ -456,6 +485,21 @@ size_t slamit_guided_search_workspace(int nframes, int q_cap);
 int slamit_guided_search_batch_dev(int device, const slamit_search_batch* batch, const slamit_search_rule* rule,
                                    int32_t* d_match_kp, int32_t* d_nmatches, int32_t* d_out4, void* d_workspace,
                                    size_t workspace_bytes, void* stream);
+
+/* The batch form with the right-image gate of slamit_guided_search_stereo, resident: the chain extract -> stereo match -> frustum
+ * or projection -> search needs no host copy of mvuRight or mTrackProjXR.  The workspace is slamit_guided_search_workspace's.  The
+ * host cannot see d_n / d_m: with er_mode != 0 a null d_q_ur (or a null d_kp_ur with kp_cap > 0) is refused whenever nframes and
+ * q_cap are not zero. */
+typedef struct slamit_search_stereo_dev {
+    int32_t er_mode;
+    float chi2_gate_stereo;
+    const float* d_kp_ur;       /* [nframes][kp_cap]: what slamit_stereo_match_batch_dev writes as d_u_right when cap_left == kp_cap */
+    const float* d_q_ur;        /* frame f, query q at d_q_ur[(f * q_cap + q) * q_ur_stride] */
+    int32_t q_ur_stride;        /* 1 (slamit_project_batch_dev_stereo's d_ur) or 3 (slamit_frustum_batch_dev's d_proj + 2) */
+} slamit_search_stereo_dev;
+int slamit_guided_search_stereo_batch_dev(int device, const slamit_search_batch* batch, const slamit_search_rule* rule,
+                                          const slamit_search_stereo_dev* st, int32_t* d_match_kp, int32_t* d_nmatches, int32_t* d_out4,
+                                          void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* Full distance matrix (nq x nt, uint16), the batched form of DescriptorDistance. */
 int slamit_hamming_matrix(const uint8_t* q, int nq, const uint8_t* t, int nt, uint16_t* out);
@@ -730,7 +774,8 @@ int slamit_triangulate(int device, const slamit_triangulate_problem* prob, slami
  * r * scale_factors[level]) with r = (view_cos > 0.998 ? 2.5 : 4.0) * (th != 1 ? th : 1), level_min = level - 1, level_max = level,
  * valid = 1 for status 0; zeros and valid = 0 otherwise.  Queries are NOT compacted: query i is point i, so the order of the
  * reference's walk over mvpLocalMapPoints is kept, and a valid = 0 query matches nothing and takes no keypoint.
- * Monocular: the stereo gate of the search is not built.  n above SLAMIT_FRUSTUM_MAX_N, n_levels outside [1, SLAMIT_MAX_LEVELS] or
+ * proj[3i + 2] is mTrackProjXR = u - bf * invz (src/Frame.cc:439): slamit_guided_search_stereo reads it in place as q_ur = proj + 2 with
+ * q_ur_stride 3 (device form: d_proj + 2), mode SLAMIT_SEARCH_ER_RADIUS; with bf = 0 it equals u and nothing reads it.  n above SLAMIT_FRUSTUM_MAX_N, n_levels outside [1, SLAMIT_MAX_LEVELS] or
  * a null array with n > 0 fails with SLAMIT_ERR_ARG and a message before anything is launched; n == 0 and nproblems == 0 are
  * valid and write nothing but n_in_view = 0. */
 #define SLAMIT_FRUSTUM_MAX_N 65536         /* points per problem / q_cap of the device form (a local map holds a few thousand) */
@@ -814,7 +859,9 @@ int slamit_frustum_batch_dev(int device, const slamit_frustum_batch_rec* batch, 
  * 7 level outside the table (the departure of slamit_frustum: no query, level = INT32_MIN, whether the level was predicted or
  * given as an octave).  proj[2i..] = u, v; level[i]; fields the walk did not reach are zero.  The query arrays are
  * slamit_search_queries' own, NOT compacted: query i is point i, valid = 1 for status 0, zeros otherwise.
- * The camera record is computed on the host, once per camera, as the shim computes it.  Monocular: no uR, no `er` gate.
+ * The camera record is computed on the host, once per camera, as the shim computes it.  The records carry no mbf: the right-image
+ * column ur = u - bf * invz of the two forms whose search reads one (0 LAST_FRAME, :1413; 2 FUSE, :874) is the extra output of
+ * slamit_project_batch_stereo / slamit_project_batch_dev_stereo below.
  * Arrays a form does not read may be NULL in the host form: normal is read by forms 2, 3, 4; max_dist / min_dist by all but form
  * 0; octave by form 0 only.  n above SLAMIT_PROJECT_MAX_N, an unknown form or direction, n_levels outside [1, SLAMIT_MAX_LEVELS]
  * or a missing array with n > 0 fails with SLAMIT_ERR_ARG and a message before anything is launched; n == 0 and nproblems == 0
@@ -887,6 +934,17 @@ typedef struct slamit_project_batch_rec {
     int32_t* d_n_valid;            /* [nframes] out, nullable */
 } slamit_project_batch_rec;
 int slamit_project_batch_dev(int device, const slamit_project_batch_rec* batch, void* stream);
+
+/* The same two calls with the right-image column of every accepted point as one more output, for slamit_guided_search_stereo's
+ * q_ur (stride 1): ur[i] = u - bf * invz, two roundings, with the invz the point's form already has -- (float)(1.0 / (double)zc) for
+ * form 0 (src/ORBmatcher.cc:1369, :1413), 1.0f / zc for form 2 (:860, :874).  It is written for every point of status 0 and is zero
+ * otherwise.  ONLY FORMS 0 AND 2 HAVE A READER of ur in the reference; for the other forms the same expression is written and
+ * means nothing.  bf[f] is problem f's mbf (device form: d_bf[f], frame f's); ur[f] points at problem f's n floats (device form:
+ * d_ur is [nframes][q_cap]).  bf and ur both NULL is slamit_project_batch / slamit_project_batch_dev; exactly one of them NULL
+ * fails with SLAMIT_ERR_ARG, as does a NULL ur[f] for a problem with n > 0.  Every other output is that of the plain call. */
+int slamit_project_batch_stereo(int device, int nproblems, const slamit_project_problem* probs, slamit_project_result* results,
+                                const float* bf, float* const* ur);
+int slamit_project_batch_dev_stereo(int device, const slamit_project_batch_rec* batch, const float* d_bf, float* d_ur, void* stream);
 
 /* The rotation-consistency check of the searches that follow a projection (src/ORBmatcher.cc:1430-1471, ComputeThreeMaxima
  * :1605-1646) on what slamit_guided_search_batch_dev left in HBM, one wavefront per frame.  The queries of frame f are walked in

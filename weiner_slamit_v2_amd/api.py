@@ -74,6 +74,19 @@ class SearchRule(C.Structure):
                 ("inv_level_sigma2", C.c_float * 16), ("mode", C.c_int32)]
 
 
+SEARCH_ER_NONE, SEARCH_ER_RADIUS, SEARCH_ER_CHI2 = 0, 1, 2   # SLAMIT_SEARCH_ER_*
+
+
+class SearchStereo(C.Structure):
+    _fields_ = [("er_mode", C.c_int32), ("chi2_gate_stereo", C.c_float), ("kp_ur", C.c_void_p), ("q_ur", C.c_void_p),
+                ("q_ur_stride", C.c_int32)]
+
+
+class SearchStereoDev(C.Structure):
+    _fields_ = [("er_mode", C.c_int32), ("chi2_gate_stereo", C.c_float), ("d_kp_ur", C.c_void_p), ("d_q_ur", C.c_void_p),
+                ("q_ur_stride", C.c_int32)]
+
+
 def _search_rule(th_dist, use_ratio, nnratio, chi2_gate=0.0, inv_level_sigma2=None, mode=0):
     sig = [1.0] * 16
     if inv_level_sigma2 is not None:
@@ -264,12 +277,12 @@ EXPORTS = [
     "slamit_orb_create", "slamit_orb_destroy", "slamit_orb_tables", "slamit_orb_max_keypoints",
     "slamit_orb_extract", "slamit_orb_extract_batch", "slamit_orb_extract_batch_dev", "slamit_orb_level",
     "slamit_orb_debug_candidates", "slamit_orb_debug_blurred", "slamit_orb_profile", "slamit_hamming_best2", "slamit_hamming_best2_batch_dev",
-    "slamit_hamming_matrix", "slamit_distinctive_batch", "slamit_guided_search", "slamit_guided_search_workspace", "slamit_guided_search_batch_dev", "slamit_bow_search", "slamit_voc_create", "slamit_voc_load_text", "slamit_voc_destroy", "slamit_voc_info",
+    "slamit_hamming_matrix", "slamit_distinctive_batch", "slamit_guided_search", "slamit_guided_search_workspace", "slamit_guided_search_batch_dev", "slamit_guided_search_stereo", "slamit_guided_search_stereo_batch_dev", "slamit_bow_search", "slamit_voc_create", "slamit_voc_load_text", "slamit_voc_destroy", "slamit_voc_info",
     "slamit_voc_transform", "slamit_voc_transform_workspace", "slamit_voc_transform_batch_dev",
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -312,6 +325,10 @@ def lib():
         L.slamit_guided_search_workspace.argtypes = [i32, i32]
         L.slamit_guided_search_workspace.restype = sz
         L.slamit_guided_search_batch_dev.argtypes = [i32, C.POINTER(SearchBatch), C.POINTER(SearchRule), vp, vp, vp, vp, sz, vp]
+        L.slamit_guided_search_stereo.argtypes = [i32, C.POINTER(FrameView), C.POINTER(SearchQueries), C.POINTER(SearchRule),
+                                                  C.POINTER(SearchStereo), vp, vp, vp, vp, vp, vp]
+        L.slamit_guided_search_stereo_batch_dev.argtypes = [i32, C.POINTER(SearchBatch), C.POINTER(SearchRule), C.POINTER(SearchStereoDev),
+                                                            vp, vp, vp, vp, sz, vp]
         f32 = C.c_float
         L.slamit_sim3_optimize_batch.argtypes = [i32, i32, C.POINTER(Sim3Problem), C.POINTER(Sim3Result)]
         L.slamit_sim3_optimize.argtypes = [i32, C.POINTER(Sim3Problem), C.POINTER(Sim3Result)]
@@ -325,6 +342,8 @@ def lib():
         L.slamit_project_batch.argtypes = [i32, i32, C.POINTER(ProjectProblem), C.POINTER(ProjectResult)]
         L.slamit_project.argtypes = [i32, C.POINTER(ProjectProblem), C.POINTER(ProjectResult)]
         L.slamit_project_batch_dev.argtypes = [i32, C.POINTER(ProjectBatchRec), vp]
+        L.slamit_project_batch_stereo.argtypes = [i32, i32, C.POINTER(ProjectProblem), C.POINTER(ProjectResult), vp, vp]
+        L.slamit_project_batch_dev_stereo.argtypes = [i32, C.POINTER(ProjectBatchRec), vp, vp, vp]
         L.slamit_rotation_check_batch_dev.argtypes = [i32, C.POINTER(RotationBatch), vp]
         L.slamit_orb_pyramid_view.argtypes = [vp, C.POINTER(PyramidView)]
         L.slamit_stereo_match_workspace.argtypes = [i32, i32]
@@ -626,12 +645,15 @@ class ORBmatcher:
         return idx[:n], med[:n]
 
     @staticmethod
-    def guided_search(frame, queries, th_dist=100, use_ratio=True, nnratio=0.8, device=0, chi2_gate=0.0, inv_level_sigma2=None, mode=0):
+    def guided_search(frame, queries, th_dist=100, use_ratio=True, nnratio=0.8, device=0, chi2_gate=0.0, inv_level_sigma2=None, mode=0,
+                      stereo=None):
         """The loop body of ORBmatcher::SearchByProjection (ORBmatcher.cc:47-131, :1332-1474) for all
         queries in order: window query over the frame grid, best/second Hamming, accept, mark taken.
         frame: dict kp_xy (n,2) f32, kp_octave (n) i32, desc (n,32) u8, kp_taken (n) u8, min_x, min_y,
         inv_w, inv_h.  queries: dict uvr (m,3) f32, level_min, level_max (m) i32, desc (m,32) u8,
-        optional valid / takes (m) u8.  Returns (match_kp[m], nmatches, out4[m,4])."""
+        optional valid / takes (m) u8.  stereo: None (the monocular call), or a dict er_mode (SEARCH_ER_*), kp_ur (n) f32 = mvuRight,
+        q_ur f32 with query q at q_ur[q * q_ur_stride], q_ur_stride = 1, chi2_gate_stereo = 7.8: the right-image gate of
+        slamit_guided_search_stereo.  Returns (match_kp[m], nmatches, out4[m,4])."""
         f = dict(kp_xy=np.ascontiguousarray(frame["kp_xy"], np.float32).reshape(-1, 2),
                  kp_octave=np.ascontiguousarray(frame["kp_octave"], np.int32),
                  desc=np.ascontiguousarray(frame["desc"], np.uint8).reshape(-1, 32),
@@ -657,6 +679,21 @@ class ORBmatcher:
         match = np.full(max(m, 1), -1, np.int32)
         out4 = np.zeros((4, max(m, 1)), np.int32)
         nm = C.c_int32(0)
+        if stereo is not None:
+            stride = int(stereo.get("q_ur_stride", 1))
+            kur = np.ascontiguousarray(stereo["kp_ur"], np.float32).reshape(-1) if stereo.get("kp_ur") is not None else None
+            qur = np.ascontiguousarray(stereo["q_ur"], np.float32).reshape(-1) if stereo.get("q_ur") is not None else None
+            if int(stereo["er_mode"]) != SEARCH_ER_NONE:
+                if kur is not None and len(kur) != n:
+                    raise SlamitError("guided_search: stereo[kp_ur] has %d entries, expected %d" % (len(kur), n))
+                if qur is not None and stride >= 1 and m and len(qur) < (m - 1) * stride + 1:
+                    raise SlamitError("guided_search: stereo[q_ur] has %d entries, %d queries of stride %d" % (len(qur), m, stride))
+            st = SearchStereo(int(stereo["er_mode"]), float(stereo.get("chi2_gate_stereo", 7.8)), _np_ptr(kur) if kur is not None and len(kur) else None,
+                              _np_ptr(qur) if qur is not None and len(qur) else None, stride)
+            _check(lib().slamit_guided_search_stereo(device, C.byref(fv), C.byref(sq), C.byref(rule), C.byref(st), _np_ptr(match), C.byref(nm),
+                                                     _np_ptr(out4[0]), _np_ptr(out4[1]), _np_ptr(out4[2]), _np_ptr(out4[3])),
+                   "slamit_guided_search_stereo")
+            return match[:m], nm.value, out4[:, :m].T.copy()
         _check(lib().slamit_guided_search(device, C.byref(fv), C.byref(sq), C.byref(rule), _np_ptr(match), C.byref(nm),
                                           _np_ptr(out4[0]), _np_ptr(out4[1]), _np_ptr(out4[2]), _np_ptr(out4[3])),
                "slamit_guided_search")
@@ -664,11 +701,13 @@ class ORBmatcher:
 
     @staticmethod
     def guided_search_batch_dev(t, bounds, th_dist=100, use_ratio=True, nnratio=0.8, device=0, stream=None, chi2_gate=0.0,
-                                inv_level_sigma2=None):
+                                inv_level_sigma2=None, stereo=None):
         """Batched device form.  t: dict of torch CUDA tensors n (B) i32, kps_un (B, kp_cap, 7) f32 view of cv::KeyPoint,
         desc (B, kp_cap, 32) u8, kp_taken (B, kp_cap) u8, m (B) i32, uvr (B, q_cap, 3) f32, level_min / level_max
         (B, q_cap) i32, qdesc (B, q_cap, 32) u8, valid / takes (B, q_cap) u8, match_kp (B, q_cap) i32, nmatches (B) i32,
-        out4 (B, q_cap, 4) i32 or None, workspace (bytes,) u8.  bounds = (min_x, min_y, inv_w, inv_h)."""
+        out4 (B, q_cap, 4) i32 or None, workspace (bytes,) u8.  bounds = (min_x, min_y, inv_w, inv_h).  stereo: None, or a dict
+        er_mode, kp_ur (B, kp_cap) f32 tensor, q_ur f32 tensor whose element (f * q_cap + q) * q_ur_stride is query q of frame f (it
+        may be a view into frustum_batch_dev's proj at offset 2, with q_ur_stride = 3), q_ur_stride = 1, chi2_gate_stereo = 7.8."""
         b, kp_cap, q_cap = t["kps_un"].shape[0], t["kps_un"].shape[1], t["uvr"].shape[1]
         sb = SearchBatch(b, kp_cap, q_cap, t["n"].data_ptr(), t["kps_un"].data_ptr(), t["desc"].data_ptr(), t["kp_taken"].data_ptr(),
                          float(bounds[0]), float(bounds[1]), float(bounds[2]), float(bounds[3]), t["m"].data_ptr(), t["uvr"].data_ptr(),
@@ -676,6 +715,15 @@ class ORBmatcher:
                          t["takes"].data_ptr())
         rule = _search_rule(th_dist, use_ratio, nnratio, chi2_gate, inv_level_sigma2)
         out4 = t.get("out4")
+        if stereo is not None:
+            st = SearchStereoDev(int(stereo["er_mode"]), float(stereo.get("chi2_gate_stereo", 7.8)),
+                                 stereo["kp_ur"].data_ptr() if stereo.get("kp_ur") is not None else None,
+                                 stereo["q_ur"].data_ptr() if stereo.get("q_ur") is not None else None, int(stereo.get("q_ur_stride", 1)))
+            _check(lib().slamit_guided_search_stereo_batch_dev(device, C.byref(sb), C.byref(rule), C.byref(st), t["match_kp"].data_ptr(),
+                                                               t["nmatches"].data_ptr(), out4.data_ptr() if out4 is not None else None,
+                                                               t["workspace"].data_ptr(), t["workspace"].numel(), stream),
+                   "slamit_guided_search_stereo_batch_dev")
+            return
         _check(lib().slamit_guided_search_batch_dev(device, C.byref(sb), C.byref(rule), t["match_kp"].data_ptr(), t["nmatches"].data_ptr(),
                                                     out4.data_ptr() if out4 is not None else None, t["workspace"].data_ptr(),
                                                     t["workspace"].numel(), stream), "slamit_guided_search_batch_dev")
@@ -1546,15 +1594,21 @@ def project_camera_record(pr):
     return rec
 
 
-def project_batch(problems, device=0):
+def project_batch(problems, device=0, bf=None):
     """The projection loops in front of the guided search of six ORBmatcher drivers (csrc/project.h) for a list of
     cameras in ONE device call; the problems may differ in form.  Each problem is a dict in the layout of slamit_project_problem
     (synth.synth_project): the camera's fields (project_camera_record), pos (n, 3) float32, skip (n) uint8 and, where the form reads
     them (None otherwise), normal (n, 3), max_dist, min_dist (n) float32, octave (n) int32.  -> a list of dicts: status (n) uint8
     (0 accepted, else the first test that rejected the point; 7 = the level outside the table), proj (n, 2) = u, v, level (n), the
-    guided search's query arrays uvr (n, 3), level_min, level_max (n), valid (n); n_valid."""
+    guided search's query arrays uvr (n, 3), level_min, level_max (n), valid (n); n_valid.  bf: None, or one mbf per problem: every
+    result then also holds ur (n) = u - bf * invz for the accepted points, zero otherwise (slamit_project_batch_stereo; forms
+    LAST_FRAME and FUSE are the ones whose search reads it)."""
     plist = list(problems)
     m = len(plist)
+    if bf is not None:
+        bf = np.ascontiguousarray(np.atleast_1d(bf), np.float32)
+        if len(bf) != m:
+            raise SlamitError("project: bf does not have one entry per problem")
     P = (ProjectProblem * m)()
     R = (ProjectResult * m)()
     keep, outs = [], []
@@ -1577,32 +1631,40 @@ def project_batch(problems, device=0):
             setattr(R[i], key, a.ctypes.data)
         keep.append(k)
         outs.append(o)
-    _check(lib().slamit_project_batch(device, m, P, R), "slamit_project_batch")
+    if bf is not None:
+        urp = (C.c_void_p * max(m, 1))()
+        for i, o in enumerate(outs):
+            o["ur"] = np.zeros(len(o["status"]), np.float32)
+            urp[i] = o["ur"].ctypes.data if len(o["ur"]) else None
+        _check(lib().slamit_project_batch_stereo(device, m, P, R, bf.ctypes.data, C.cast(urp, C.c_void_p)), "slamit_project_batch_stereo")
+    else:
+        _check(lib().slamit_project_batch(device, m, P, R), "slamit_project_batch")
     del keep
     for i, o in enumerate(outs):
         o["n_valid"] = int(R[i].n_valid)
     return outs
 
 
-def project(problem, device=0):
-    """One camera: project_batch([problem])[0]."""
-    return project_batch([problem], device)[0]
+def project(problem, device=0, bf=None):
+    """One camera: project_batch([problem])[0]; bf: its mbf, for the ur output."""
+    return project_batch([problem], device, None if bf is None else [bf])[0]
 
 
 def project_batch_dev(t, device=0, stream=None):
     """The resident form.  t: dict of torch CUDA tensors cameras (B, 56) f32 (rows of PROJECT_CAMERA_DTYPE viewed as float32), m (B)
     i32, pos / normal (B, 3, q_cap) f32 PLANES, max_dist / min_dist (B, q_cap) f32, octave (B, q_cap) i32, skip (B, q_cap) u8, and the
     outputs uvr (B, q_cap, 3) f32, level_min / level_max (B, q_cap) i32, valid (B, q_cap) u8 -- the tensors guided_search_batch_dev
-    reads -- plus optionally status (B, q_cap) u8, proj (B, q_cap, 2) f32, level (B, q_cap) i32, n_valid (B) i32.
+    reads -- plus optionally status (B, q_cap) u8, proj (B, q_cap, 2) f32, level (B, q_cap) i32, n_valid (B) i32.  With bf (B) f32 and
+    ur (B, q_cap) f32 both present, ur is written as well (slamit_project_batch_dev_stereo): guided_search_batch_dev's q_ur, stride 1.
     Asynchronous on `stream`."""
     b, q_cap = t["pos"].shape[0], t["pos"].shape[2]
     if t["cameras"].numel() * t["cameras"].element_size() != b * C.sizeof(ProjectCamera):
         raise SlamitError("project_batch_dev: cameras does not hold one slamit_project_camera per frame")
     for key, per in (("pos", 3), ("normal", 3), ("max_dist", 1), ("min_dist", 1), ("octave", 1), ("skip", 1), ("uvr", 3), ("level_min", 1),
-                     ("level_max", 1), ("valid", 1), ("status", 1), ("proj", 2), ("level", 1)):
+                     ("level_max", 1), ("valid", 1), ("status", 1), ("proj", 2), ("level", 1), ("ur", 1)):
         if t.get(key) is not None and (t[key].numel() != b * q_cap * per or not t[key].is_contiguous()):
             raise SlamitError("project_batch_dev: %s is not a contiguous (B, q_cap) array" % key)
-    for key in ("m", "n_valid"):
+    for key in ("m", "n_valid", "bf"):
         if t.get(key) is not None and t[key].numel() != b:
             raise SlamitError("project_batch_dev: %s does not have one entry per frame" % key)
 
@@ -1612,6 +1674,9 @@ def project_batch_dev(t, device=0, stream=None):
     rec = ProjectBatchRec(b, q_cap, t["cameras"].data_ptr(), t["m"].data_ptr(), t["pos"].data_ptr(), t["normal"].data_ptr(), t["max_dist"].data_ptr(),
                           t["min_dist"].data_ptr(), t["octave"].data_ptr(), t["skip"].data_ptr(), t["uvr"].data_ptr(), t["level_min"].data_ptr(),
                           t["level_max"].data_ptr(), t["valid"].data_ptr(), opt("status"), opt("proj"), opt("level"), opt("n_valid"))
+    if t.get("bf") is not None or t.get("ur") is not None:
+        _check(lib().slamit_project_batch_dev_stereo(device, C.byref(rec), opt("bf"), opt("ur"), stream), "slamit_project_batch_dev_stereo")
+        return
     _check(lib().slamit_project_batch_dev(device, C.byref(rec), stream), "slamit_project_batch_dev")
 
 

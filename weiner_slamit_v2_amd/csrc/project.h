@@ -2,7 +2,8 @@
 // camera, the depth, bounds, distance and viewing-angle gates, MapPoint::PredictScale and the window radius.  Plain C++ over IEEE
 // +,-,*,/ and sqrt, float and double exactly where the shim's loops have them; it must be compiled with -ffp-contract=off.
 // project.hip runs it one lane per point; the CPU test of the restatement and tools build the same text with g++ for the host.
-// fru_gemm_row3, fru_logf and fru_predict_scale are csrc/frustum.h's.  Monocular only: no uR, no `er` gate.
+// fru_gemm_row3, fru_logf and fru_predict_scale are csrc/frustum.h's.  project_point_stereo also gives the right-image column the
+// guided search's `er` gate reads.
 //
 // THE PINNED READING is the host loop of each driver in shim/ORBmatcher.h; a difference from it is a bug here.
 //
@@ -23,6 +24,9 @@
 //   level       LAST_FRAME: the octave given; the others: fru_predict_scale(max_dist, dist, log_scale_factor)
 //   window      r = th * scale_factors[level].  Levels: LAST_FRAME by direction (0: l-1..l+1; 1 forward: l..-1 = no upper bound;
 //               2 backward: 0..l); RELOC l-1..l+1; the others l-1..l
+//
+//   ur          project_point_stereo only: u - bf * invz, two roundings, with the form's own invz above (LAST_FRAME :1413, FUSE :874).
+//               Only LAST_FRAME and FUSE have a reader of it in the reference.  Status 0 only; zero otherwise.
 //
 // ONE STATED DEPARTURE, csrc/frustum.h's: the loops index mvScaleFactors with the level unchecked.  Here a level outside
 // [0, n_levels), predicted or given as an octave, and a ratio no level comes from, is status PRJ_LEVEL (7): no query, and the level
@@ -68,10 +72,11 @@ FRU_HD bool prj_form_reads_distances(int form) { return form != PRJ_LAST_FRAME; 
 FRU_HD bool prj_form_reads_octave(int form) { return form == PRJ_LAST_FRAME; }
 
 // One point: the code of the first test that rejects it (0 = a query).  Pn, max_dist, min_dist and octave are read only by the
-// forms the three predicates above name.
-FRU_HD int project_point(const ProjectCamera& C, const float P[3], const float Pn[3], float max_dist, float min_dist, int octave, bool skip,
-                         ProjectOut& o) {
+// forms the three predicates above name.  bf is the camera's mbf, ur the right-image column of an accepted point.
+FRU_HD int project_point_stereo(const ProjectCamera& C, const float P[3], const float Pn[3], float max_dist, float min_dist, int octave, bool skip,
+                                float bf, ProjectOut& o, float& ur) {
     o.u = 0.f; o.v = 0.f; o.r = 0.f; o.level = 0;
+    ur = 0.f;
     if (skip) return PRJ_SKIPPED;
     const int form = C.form;
     float pc[3];
@@ -128,7 +133,15 @@ FRU_HD int project_point(const ProjectCamera& C, const float P[3], const float P
     if (level < 0 || level >= C.n_levels || level >= FRU_MAX_LEVELS) { o.level = FRU_LEVEL_NONE; return PRJ_LEVEL; }
     o.level = level;
     o.r = C.th * C.scale_factors[level & (FRU_MAX_LEVELS - 1)];
+    ur = u - bf * invz;
     return PRJ_OK;
+}
+
+// The same without the right-image column
+FRU_HD int project_point(const ProjectCamera& C, const float P[3], const float Pn[3], float max_dist, float min_dist, int octave, bool skip,
+                         ProjectOut& o) {
+    float ur;
+    return project_point_stereo(C, P, Pn, max_dist, min_dist, octave, skip, 0.f, o, ur);
 }
 
 // The slamit_search_queries row of a point; queries are not compacted: a rejected point is a query with valid = 0 and zeros.

@@ -33,17 +33,19 @@ struct PrjArrays {
     const SLAMIT_GLOBAL int32_t* octave; const SLAMIT_GLOBAL uint8_t* skip;
     SLAMIT_GLOBAL float* uvr; SLAMIT_GLOBAL int32_t* level_min; SLAMIT_GLOBAL int32_t* level_max; SLAMIT_GLOBAL uint8_t* valid;
     SLAMIT_GLOBAL uint8_t* status; SLAMIT_GLOBAL float* proj; SLAMIT_GLOBAL int32_t* level;
+    SLAMIT_GLOBAL float* ur;   // the right-image column of the stereo calls, or null (wave-uniform)
 };
 
 struct PrjProb {
     ProjectCamera C;
     int32_t n, plane;
+    float bf;   // mbf of the stereo call (0 without)
     PrjArrays A;
     SLAMIT_GLOBAL int32_t* wave_counts;   // (n + 63) / 64
 };
 
 // point i (< n, checked by the caller) of a camera: true = accepted
-__device__ __forceinline__ bool project_lane(const ProjectCamera& C, const PrjArrays& A, size_t plane, size_t i) {
+__device__ __forceinline__ bool project_lane(const ProjectCamera& C, const PrjArrays& A, float bf, size_t plane, size_t i) {
     const int form = C.form;   // wave-uniform
     const float P[3] = {A.pos[i], A.pos[plane + i], A.pos[2 * plane + i]};
     float Pn[3] = {0.f, 0.f, 0.f};
@@ -54,7 +56,8 @@ __device__ __forceinline__ bool project_lane(const ProjectCamera& C, const PrjAr
     if (prj_form_reads_octave(form)) octave = A.octave[i];
     ProjectOut o;
     // a form the header does not know (device form only: the host form refuses it) skips every point
-    const int st = project_point(C, P, Pn, max_dist, min_dist, octave, A.skip[i] != 0 || (unsigned)form >= (unsigned)PRJ_FORMS, o);
+    float ur;
+    const int st = project_point_stereo(C, P, Pn, max_dist, min_dist, octave, A.skip[i] != 0 || (unsigned)form >= (unsigned)PRJ_FORMS, bf, o, ur);
     float uvr[3];
     int l0, l1;
     unsigned char valid;
@@ -64,6 +67,7 @@ __device__ __forceinline__ bool project_lane(const ProjectCamera& C, const PrjAr
     if (A.status) A.status[i] = (uint8_t)st;
     if (A.proj) { A.proj[2 * i] = o.u; A.proj[2 * i + 1] = o.v; }
     if (A.level) A.level[i] = o.level;
+    if (A.ur) A.ur[i] = ur;
     return st == PRJ_OK;
 }
 
@@ -72,7 +76,7 @@ __global__ __launch_bounds__(256) void project_kernel(const PrjProb* __restrict_
     const PrjProb& P = probs[blockIdx.y];
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     if (i >= P.n) return;
-    const bool in = project_lane(P.C, P.A, (size_t)P.plane, (size_t)i);
+    const bool in = project_lane(P.C, P.A, P.bf, (size_t)P.plane, (size_t)i);
     const unsigned long long m = __ballot(in);   // the lanes past n have left: they count as 0
     // the point index rises with the lane, so lane 0 of a wavefront that has any live lane is live itself
     if ((threadIdx.x & 63) == 0) P.wave_counts[i >> 6] = __popcll(m);
@@ -82,6 +86,7 @@ __global__ __launch_bounds__(256) void project_kernel(const PrjProb* __restrict_
 struct PrjDev {
     int32_t q_cap;
     const ProjectCamera* cameras; const int32_t* m;
+    const float* bf;   // [nframes] or null
     PrjArrays A;   // frame 0's; frame f's start f * q_cap entries (3 f * q_cap for the planes and uvr, 2 f * q_cap for proj) further on
 };
 
@@ -96,15 +101,18 @@ __global__ __launch_bounds__(256) void project_dev_kernel(PrjDev D) {
     A.octave = D.A.octave + o; A.skip = D.A.skip + o;
     A.uvr = D.A.uvr + 3 * o; A.level_min = D.A.level_min + o; A.level_max = D.A.level_max + o; A.valid = D.A.valid + o;
     A.status = D.A.status ? D.A.status + o : nullptr; A.proj = D.A.proj ? D.A.proj + 2 * o : nullptr; A.level = D.A.level ? D.A.level + o : nullptr;
+    A.ur = D.A.ur ? D.A.ur + o : nullptr;
     // n_levels is the caller's, unchecked: project_point accepts a level only below min(n_levels, FRU_MAX_LEVELS) and masks the index
-    project_lane(D.cameras[f], A, q_cap, (size_t)i);
+    project_lane(D.cameras[f], A, D.bf ? D.bf[f] : 0.f, q_cap, (size_t)i);
 }
 
 extern "C" {
 
-int slamit_project_batch(int device, int nprob, const slamit_project_problem* probs, slamit_project_result* results) {
+int slamit_project_batch_stereo(int device, int nprob, const slamit_project_problem* probs, slamit_project_result* results, const float* bf,
+                                float* const* ur) {
     const char* const where = "slamit_project_batch";
     if (nprob < 0 || (nprob && (!probs || !results))) return slamit_fail(SLAMIT_ERR_ARG, "slamit_project_batch: bad argument");
+    if (!bf != !ur) return slamit_fail(SLAMIT_ERR_ARG, "slamit_project_batch_stereo: exactly one of bf / ur is null");
     if (nprob == 0) return SLAMIT_OK;
     if (nprob > 65535) return slamit_fail(SLAMIT_ERR_ARG, "slamit_project_batch: more than 65535 problems");
     int max_n = 0;
@@ -122,6 +130,7 @@ int slamit_project_batch(int device, int nprob, const slamit_project_problem* pr
         if (!P.pos || !P.skip || (prj_form_reads_normal(form) && !P.normal) || (prj_form_reads_distances(form) && (!P.max_dist || !P.min_dist)) ||
             (prj_form_reads_octave(form) && !P.octave) || !R.status || !R.proj || !R.level || !R.uvr || !R.level_min || !R.level_max || !R.valid)
             return slamit_fail(SLAMIT_ERR_ARG, "slamit_project_batch: null array");
+        if (ur && !ur[f]) return slamit_fail(SLAMIT_ERR_ARG, "slamit_project_batch_stereo: null ur of a problem with points");
         max_n = std::max(max_n, (int)P.n);
     }
     for (int f = 0; f < nprob; ++f) results[f].n_valid = 0;
@@ -130,7 +139,7 @@ int slamit_project_batch(int device, int nprob, const slamit_project_problem* pr
     // [per problem: pos normal (planes) max_dist min_dist octave skip | records] go up; [per problem: the seven outputs, wave counts] come down;
     // an input the form does not read takes no room
     struct Spans {
-        StageSpan<float> pos, normal, maxd, mind, proj, uvr;
+        StageSpan<float> pos, normal, maxd, mind, proj, uvr, ur;
         StageSpan<int32_t> octave, level, l0, l1, counts;
         StageSpan<uint8_t> skip, status, valid;
     };
@@ -152,6 +161,7 @@ int slamit_project_batch(int device, int nprob, const slamit_project_problem* pr
         s.status = L.take<uint8_t>(n, 16); s.proj = L.take<float>(2 * n, 16); s.level = L.take<int32_t>(n, 16);
         s.uvr = L.take<float>(3 * n, 16); s.l0 = L.take<int32_t>(n, 16); s.l1 = L.take<int32_t>(n, 16); s.valid = L.take<uint8_t>(n, 16);
         s.counts = L.take<int32_t>((n + 63) / 64, 16);
+        s.ur = L.take<float>(ur ? n : 0, 16);
     }
     L.end_outputs();
     static thread_local SlamitScratch S;
@@ -161,7 +171,7 @@ int slamit_project_batch(int device, int nprob, const slamit_project_problem* pr
         const Spans& s = sp[f];
         PrjProb& Q = recs.at(S.host)[f];
         memset(&Q, 0, sizeof(Q));
-        Q.n = P.n; Q.plane = P.n;
+        Q.n = P.n; Q.plane = P.n; Q.bf = bf ? bf[f] : 0.f;
         if (P.n) {
             memcpy(&Q.C, &P.camera, sizeof(Q.C));
             const size_t n = (size_t)P.n;
@@ -184,6 +194,7 @@ int slamit_project_batch(int device, int nprob, const slamit_project_problem* pr
         Q.A.level_max = (SLAMIT_GLOBAL int32_t*)s.l1.at(S.dev); Q.A.valid = (SLAMIT_GLOBAL uint8_t*)s.valid.at(S.dev);
         Q.A.status = (SLAMIT_GLOBAL uint8_t*)s.status.at(S.dev); Q.A.proj = (SLAMIT_GLOBAL float*)s.proj.at(S.dev);
         Q.A.level = (SLAMIT_GLOBAL int32_t*)s.level.at(S.dev);
+        Q.A.ur = ur && P.n ? (SLAMIT_GLOBAL float*)s.ur.at(S.dev) : nullptr;
         Q.wave_counts = (SLAMIT_GLOBAL int32_t*)s.counts.at(S.dev);
     }
     HIP_TRY_AT(where, slamit_stage_upload(S, L));
@@ -197,6 +208,7 @@ int slamit_project_batch(int device, int nprob, const slamit_project_problem* pr
         memcpy(R.level, s.level.at(S.host), s.level.bytes());
         memcpy(R.uvr, s.uvr.at(S.host), s.uvr.bytes()); memcpy(R.level_min, s.l0.at(S.host), s.l0.bytes());
         memcpy(R.level_max, s.l1.at(S.host), s.l1.bytes()); memcpy(R.valid, s.valid.at(S.host), s.valid.bytes());
+        if (ur) memcpy(ur[f], s.ur.at(S.host), s.ur.bytes());
         int acc = 0;
         const int32_t* c = s.counts.at(S.host);
         for (size_t w = 0; w < s.counts.count; ++w) acc += c[w];
@@ -205,12 +217,17 @@ int slamit_project_batch(int device, int nprob, const slamit_project_problem* pr
     return SLAMIT_OK;
 }
 
+int slamit_project_batch(int device, int nprob, const slamit_project_problem* probs, slamit_project_result* results) {
+    return slamit_project_batch_stereo(device, nprob, probs, results, nullptr, nullptr);
+}
+
 int slamit_project(int device, const slamit_project_problem* prob, slamit_project_result* res) {
     return slamit_project_batch(device, 1, prob, res);
 }
 
-int slamit_project_batch_dev(int device, const slamit_project_batch_rec* B, void* stream) {
+int slamit_project_batch_dev_stereo(int device, const slamit_project_batch_rec* B, const float* d_bf, float* d_ur, void* stream) {
     if (!B || B->nframes < 0 || B->q_cap < 0) return slamit_fail(SLAMIT_ERR_ARG, "slamit_project_batch_dev: bad argument");
+    if (!d_bf != !d_ur) return slamit_fail(SLAMIT_ERR_ARG, "slamit_project_batch_dev_stereo: exactly one of d_bf / d_ur is null");
     if (B->q_cap > SLAMIT_PROJECT_MAX_N) return slamit_fail(SLAMIT_ERR_ARG, "slamit_project_batch_dev: q_cap above SLAMIT_PROJECT_MAX_N");
     if (B->nframes == 0 || B->q_cap == 0) return SLAMIT_OK;
     if (!B->d_cameras || !B->d_m || !B->d_pos || !B->d_normal || !B->d_max_dist || !B->d_min_dist || !B->d_octave || !B->d_skip || !B->d_uvr ||
@@ -227,11 +244,16 @@ int slamit_project_batch_dev(int device, const slamit_project_batch_rec* B, void
     D.A.uvr = (SLAMIT_GLOBAL float*)B->d_uvr; D.A.level_min = (SLAMIT_GLOBAL int32_t*)B->d_level_min;
     D.A.level_max = (SLAMIT_GLOBAL int32_t*)B->d_level_max; D.A.valid = (SLAMIT_GLOBAL uint8_t*)B->d_valid;
     D.A.status = (SLAMIT_GLOBAL uint8_t*)B->d_status; D.A.proj = (SLAMIT_GLOBAL float*)B->d_proj; D.A.level = (SLAMIT_GLOBAL int32_t*)B->d_level;
+    D.bf = d_bf; D.A.ur = (SLAMIT_GLOBAL float*)d_ur;
     hipLaunchKernelGGL(project_dev_kernel, dim3((B->q_cap + 255) / 256, B->nframes), dim3(256), 0, (hipStream_t)stream, D);
     HIP_TRY_AT("slamit_project_batch_dev", hipGetLastError());
     if (B->d_n_valid)
         HIP_TRY_AT("slamit_project_batch_dev", slamit_launch_valid_count(B->d_valid, B->d_m, B->q_cap, B->nframes, B->d_n_valid, (hipStream_t)stream));
     return SLAMIT_OK;
+}
+
+int slamit_project_batch_dev(int device, const slamit_project_batch_rec* B, void* stream) {
+    return slamit_project_batch_dev_stereo(device, B, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

@@ -52,6 +52,11 @@ struct SearchDev {
     int mode;                                 // 0 taken flags, 1 SearchForInitialization's matched-distance state
     int* match_kp; int* out4;   // [nframes][q_cap], [nframes][q_cap][4] (best_dist, best_level, second_dist, second_level) or null
     int* nmatches;              // [nframes]
+    // The right-image gate of the three stereo drivers.  Read only by the kernels instantiated for er_mode != 0.
+    const float* kp_ur;         // [nframes][kp_cap]: mvuRight of the searched frame
+    const float* q_ur; int q_ur_stride;   // query q of frame f: q_ur[(f * q_cap + q) * q_ur_stride]
+    int er_mode;                // SLAMIT_SEARCH_ER_*: uniform per launch, and the kernels' template argument
+    float chi2_gate_stereo;     // CHI2: the three-term gate (7.8)
 };
 
 // key = distance << 32 | cell << 17 | keypoint << 4 | octave: ordered by (distance, cell, keypoint) = the reference's
@@ -62,12 +67,14 @@ struct SearchDev {
 
 // A query's search window (Frame::GetFeaturesInArea, Frame.cc:452-466) and descriptor; ok = the window meets the grid.
 struct QueryWin {
-    float x, y, r;
+    float x, y, r, ur;   // ur: the query's right-image column, loaded only when the launch has a gate
     int nMinCellX, nMaxCellX, nMinCellY, nMaxCellY, minLevel, maxLevel;
     uint4 a0, a1;
 };
+template <int ER>
 __device__ __forceinline__ bool query_window(const SearchDev& D, size_t qo, QueryWin& W) {
     W.x = D.uvr[3 * qo]; W.y = D.uvr[3 * qo + 1]; W.r = D.uvr[3 * qo + 2];
+    W.ur = ER != SLAMIT_SEARCH_ER_NONE ? D.q_ur[qo * (size_t)D.q_ur_stride] : 0.f;
     W.nMinCellX = max(0, (int)floorf((W.x - D.min_x - W.r) * D.inv_w));
     if (W.nMinCellX >= GRID_COLS) return false;
     W.nMaxCellX = min(GRID_COLS - 1, (int)ceilf((W.x - D.min_x + W.r) * D.inv_w));
@@ -81,8 +88,13 @@ __device__ __forceinline__ bool query_window(const SearchDev& D, size_t qo, Quer
     W.a0 = Q[0]; W.a1 = Q[1];
     return true;
 }
-// keypoint i against the window: is it a candidate, and its key (distance, cell, keypoint, octave)
-__device__ __forceinline__ bool window_key(const SearchDev& D, const QueryWin& W, const uint8_t* KP, const uint8_t* KD, int i, unsigned long long& key) {
+// keypoint i against the window: is it a candidate, and its key (distance, cell, keypoint, octave).  ER is the launch's er_mode: the
+// monocular instantiation (ER = 0) is the code as it stood, without a load or a branch for the gate.  KUR: the frame's mvuRight.
+//   RADIUS (ORBmatcher.cc:93-98, :1411-1417)  a keypoint with uR > 0 is skipped when fabs(q_ur - uR) > r; a NaN passes, 0 is monocular
+//   CHI2   (ORBmatcher.cc:918-942)            a keypoint with uR >= 0 takes the three-term e2 against chi2_gate_stereo; 0 is stereo
+template <int ER>
+__device__ __forceinline__ bool window_key(const SearchDev& D, const QueryWin& W, const uint8_t* KP, const uint8_t* KD, const float* KUR, int i,
+                                           unsigned long long& key) {
     const uint8_t* rec = KP + (size_t)i * D.kp_rec;
     const float px = *reinterpret_cast<const float*>(rec), py = *reinterpret_cast<const float*>(rec + 4);
     // Frame::PosInGrid, Frame.cc:505-517 (round = half away from zero)
@@ -93,9 +105,23 @@ __device__ __forceinline__ bool window_key(const SearchDev& D, const QueryWin& W
     const float distx = px - W.x, disty = py - W.y;
     bool hit = ingrid && posX >= W.nMinCellX && posX <= W.nMaxCellX && posY >= W.nMinCellY && posY <= W.nMaxCellY && lev &&
                fabsf(distx) < W.r && fabsf(disty) < W.r;
-    if (hit && D.chi2_gate > 0.f) {   // ORBmatcher::Fuse, ORBmatcher.cc:925-936 (mono branch)
-        const float e2 = distx * distx + disty * disty;
-        if (e2 * D.inv_sigma2[oct & 15] > D.chi2_gate) hit = false;
+    if (ER == SLAMIT_SEARCH_ER_RADIUS && hit) {
+        const float kur = KUR[i];
+        if (kur > 0) {
+            const float er = fabsf(W.ur - kur);
+            if (er > W.r) hit = false;
+        }
+    }
+    if (hit && D.chi2_gate > 0.f) {   // ORBmatcher::Fuse, ORBmatcher.cc:918-942
+        const float kur = ER == SLAMIT_SEARCH_ER_CHI2 ? KUR[i] : -1.f;
+        if (ER == SLAMIT_SEARCH_ER_CHI2 && kur >= 0) {
+            const float er = W.ur - kur;
+            const float e2 = (distx * distx + disty * disty) + er * er;
+            if (e2 * D.inv_sigma2[oct & 15] > D.chi2_gate_stereo) hit = false;
+        } else {
+            const float e2 = distx * distx + disty * disty;
+            if (e2 * D.inv_sigma2[oct & 15] > D.chi2_gate) hit = false;
+        }
     }
     if (hit) {
         const uint4* T = reinterpret_cast<const uint4*>(KD + 32 * (size_t)i);
@@ -108,6 +134,7 @@ __device__ __forceinline__ bool window_key(const SearchDev& D, const QueryWin& W
     return hit;
 }
 
+template <int ER>
 __global__ __launch_bounds__(256) void search_candidates_kernel(SearchDev D) {
     const int lane = threadIdx.x & 63;
     const int f = blockIdx.y;
@@ -119,17 +146,18 @@ __global__ __launch_bounds__(256) void search_candidates_kernel(SearchDev D) {
     if (lane == 0) { D.cand_n[qo] = 0; D.tent[2 * qo] = ~0ull; D.tent[2 * qo + 1] = ~0ull; }
     if (!D.valid[qo]) return;
     QueryWin W;
-    if (!query_window(D, qo, W)) return;
+    if (!query_window<ER>(D, qo, W)) return;
     unsigned long long* out = D.cand + qo * D.cand_cap;
     const uint8_t* KP = D.kp + (size_t)f * D.kp_cap * D.kp_rec;
     const uint8_t* KD = D.kp_desc + (size_t)f * D.kp_cap * 32;
     const uint8_t* TK = D.kp_taken + (size_t)f * D.kp_cap;
+    const float* KUR = ER != SLAMIT_SEARCH_ER_NONE ? D.kp_ur + (size_t)f * D.kp_cap : nullptr;
     int count = 0;
     unsigned long long k1 = ~0ull, k2 = ~0ull;   // this lane's two smallest keys among keypoints free on entry
     for (int i0 = 0; i0 < n; i0 += 64) {
         const int i = i0 + lane;
         unsigned long long key = 0;
-        const bool hit = i < n && window_key(D, W, KP, KD, i, key);
+        const bool hit = i < n && window_key<ER>(D, W, KP, KD, KUR, i, key);
         const unsigned long long mk = __ballot(hit);
         if (hit) {
             const int o = count + __popcll(mk & ((1ull << lane) - 1ull));
@@ -161,7 +189,7 @@ struct SearchHit { int res = -1, bd = 256, bl = -1, sd = 256, sl = -1; };
 //                                        is this lane's pending result of query qb + lane, which a take-over may reset
 //     void      end_chunk()              after a chunk's results are stored
 // The mode is the type: the loop is serial (about 1 us per query), so nothing in it is decided at run time.
-template <class State>
+template <int ER, class State>
 __device__ __forceinline__ void search_resolve_walk(const SearchDev& D, State& S) {
     const int lane = threadIdx.x, f = blockIdx.x;
     const int n = D.n_arr ? min(D.n_arr[f], D.kp_cap) : D.n_fixed;
@@ -196,12 +224,13 @@ __device__ __forceinline__ void search_resolve_walk(const SearchDev& D, State& S
                     }
                 } else {
                     QueryWin W;
-                    query_window(D, qo, W);   // (it met the grid: the query has candidates)
+                    query_window<ER>(D, qo, W);   // (it met the grid: the query has candidates)
                     const uint8_t* KP = D.kp + (size_t)f * D.kp_cap * D.kp_rec;
                     const uint8_t* KD = D.kp_desc + (size_t)f * D.kp_cap * 32;
+                    const float* KUR = ER != SLAMIT_SEARCH_ER_NONE ? D.kp_ur + (size_t)f * D.kp_cap : nullptr;
                     for (int i = lane; i < n; i += 64) {
                         unsigned long long k;
-                        if (window_key(D, W, KP, KD, i, k) && !S.excluded(k)) keep2(k1, k2, k);
+                        if (window_key<ER>(D, W, KP, KD, KUR, i, k) && !S.excluded(k)) keep2(k1, k2, k);
                     }
                 }
                 wave_min2(k1, k2, best, second);
@@ -298,27 +327,38 @@ struct MatchedDist {
     __device__ __forceinline__ void end_chunk() const { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent"); }
 };
 
+template <int ER>
 __global__ __launch_bounds__(64) void search_resolve_kernel(SearchDev D) {
     __shared__ unsigned taken[(SLAMIT_SEARCH_MAX_KP + 32) / 32];
     TakenBits S{taken};
-    search_resolve_walk(D, S);
+    search_resolve_walk<ER>(D, S);
 }
 
 __global__ __launch_bounds__(64) void search_resolve_init_kernel(SearchDev D) {
     extern __shared__ int s_state[];   // md[kp_cap] | m21[kp_cap]
     MatchedDist S{s_state, s_state + D.kp_cap};
-    search_resolve_walk(D, S);
+    search_resolve_walk<SLAMIT_SEARCH_ER_NONE>(D, S);   // SearchForInitialization has no stereo branch
+}
+
+// the two launches of mode 0 for one er_mode
+template <int ER>
+static void search_launch_taken(hipStream_t st, const SearchDev& D, int max_m) {
+    if (max_m > 0)
+        hipLaunchKernelGGL(search_candidates_kernel<ER>, dim3((max_m + 3) / 4, D.nframes), dim3(256), 0, st, D);
+    hipLaunchKernelGGL(search_resolve_kernel<ER>, dim3(D.nframes), dim3(64), 0, st, D);
 }
 
 static void search_launch(hipStream_t st, const SearchDev& D, int max_m) {
+    if (D.er_mode == SLAMIT_SEARCH_ER_RADIUS) return search_launch_taken<SLAMIT_SEARCH_ER_RADIUS>(st, D, max_m);
+    if (D.er_mode == SLAMIT_SEARCH_ER_CHI2) return search_launch_taken<SLAMIT_SEARCH_ER_CHI2>(st, D, max_m);
+    if (D.mode != 1) return search_launch_taken<SLAMIT_SEARCH_ER_NONE>(st, D, max_m);
     if (max_m > 0)
-        hipLaunchKernelGGL(search_candidates_kernel, dim3((max_m + 3) / 4, D.nframes), dim3(256), 0, st, D);
-    if (D.mode == 1) {
+        hipLaunchKernelGGL(search_candidates_kernel<SLAMIT_SEARCH_ER_NONE>, dim3((max_m + 3) / 4, D.nframes), dim3(256), 0, st, D);
+    {
         static bool prepared = false;   // 2 x 4 x 8191 bytes of state sit just under the 64 KB default; ask explicitly
         if (!prepared) { hipFuncSetAttribute(reinterpret_cast<const void*>(search_resolve_init_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024); prepared = true; }
         hipLaunchKernelGGL(search_resolve_init_kernel, dim3(D.nframes), dim3(64), 2 * sizeof(int) * (size_t)D.kp_cap, st, D);
-    } else
-        hipLaunchKernelGGL(search_resolve_kernel, dim3(D.nframes), dim3(64), 0, st, D);
+    }
 }
 
 // the rule half of SearchDev, the same for both entry points
@@ -328,10 +368,31 @@ static void search_rule_fill(SearchDev& D, const slamit_search_rule* rule) {
     D.mode = rule->mode;
 }
 
-extern "C" int slamit_guided_search(int device, const slamit_frame_view* F, const slamit_search_queries* Q,
-                                    const slamit_search_rule* rule, int32_t* match_kp, int32_t* nmatches, int32_t* best_dist,
-                                    int32_t* best_level, int32_t* second_dist, int32_t* second_level) {
+// The stereo record's own checks, the same for both entry points (dev: the message names the batch form); null arrays are each entry
+// point's to test, where it knows whether there is work.  0: fine.
+static int search_stereo_check(bool dev, const slamit_search_rule* rule, int er_mode, int q_ur_stride) {
+    if (er_mode < SLAMIT_SEARCH_ER_NONE || er_mode > SLAMIT_SEARCH_ER_CHI2)
+        return slamit_fail(SLAMIT_ERR_ARG, dev ? "slamit_guided_search_stereo_batch_dev: er_mode outside 0..2" : "slamit_guided_search_stereo: er_mode outside 0..2");
+    if (er_mode == SLAMIT_SEARCH_ER_NONE) return SLAMIT_OK;
+    if (q_ur_stride < 1)
+        return slamit_fail(SLAMIT_ERR_ARG, dev ? "slamit_guided_search_stereo_batch_dev: q_ur_stride < 1" : "slamit_guided_search_stereo: q_ur_stride < 1");
+    if (rule->mode == 1)
+        return slamit_fail(SLAMIT_ERR_ARG, dev ? "slamit_guided_search_stereo_batch_dev: er_mode with rule mode 1 (SearchForInitialization has no stereo branch)"
+                                               : "slamit_guided_search_stereo: er_mode with rule mode 1 (SearchForInitialization has no stereo branch)");
+    return SLAMIT_OK;
+}
+
+extern "C" int slamit_guided_search_stereo(int device, const slamit_frame_view* F, const slamit_search_queries* Q,
+                                           const slamit_search_rule* rule, const slamit_search_stereo* st, int32_t* match_kp, int32_t* nmatches,
+                                           int32_t* best_dist, int32_t* best_level, int32_t* second_dist, int32_t* second_level) {
     if (!F || !Q || !rule || !nmatches || F->n < 0 || Q->m < 0) return slamit_fail(SLAMIT_ERR_ARG, "slamit_guided_search: bad argument");
+    const int er_mode = st ? st->er_mode : SLAMIT_SEARCH_ER_NONE;
+    if (st) {
+        const int rc = search_stereo_check(false, rule, er_mode, st->q_ur_stride);
+        if (rc != SLAMIT_OK) return rc;
+        if (er_mode != SLAMIT_SEARCH_ER_NONE && Q->m && (!st->q_ur || (F->n && !st->kp_ur)))
+            return slamit_fail(SLAMIT_ERR_ARG, "slamit_guided_search_stereo: er_mode set with a null kp_ur or q_ur");
+    }
     *nmatches = 0;
     if (Q->m == 0) return SLAMIT_OK;
     if (!match_kp || !Q->uvr || !Q->level_min || !Q->level_max || !Q->desc || !Q->valid ||
@@ -348,6 +409,7 @@ extern "C" int slamit_guided_search(int device, const slamit_frame_view* F, cons
     const StageSpan<float> uvr = L.take<float>(3 * m);
     const StageSpan<int> l0 = L.take<int>(m), l1 = L.take<int>(m);
     const StageSpan<uint8_t> qd = L.take<uint8_t>(32 * m), va = L.take<uint8_t>(m), tq = L.take<uint8_t>(m);
+    const StageSpan<float> kur = L.take<float>(er_mode ? n : 0), qur = L.take<float>(er_mode ? m : 0);   // no gate: no room taken
     L.end_inputs();
     const StageSpan<int> mk = L.take<int>(m), o4 = L.take<int>(4 * m), nm = L.take<int>(1);
     L.end_outputs();
@@ -364,6 +426,11 @@ extern "C" int slamit_guided_search(int device, const slamit_frame_view* F, cons
     memcpy(uvr.at(S.host), Q->uvr, uvr.bytes()); memcpy(l0.at(S.host), Q->level_min, l0.bytes()); memcpy(l1.at(S.host), Q->level_max, l1.bytes());
     memcpy(qd.at(S.host), Q->desc, qd.bytes()); memcpy(va.at(S.host), Q->valid, va.bytes());
     if (Q->takes) memcpy(tq.at(S.host), Q->takes, tq.bytes()); else memset(tq.at(S.host), 1, tq.bytes());
+    if (er_mode) {
+        if (n) memcpy(kur.at(S.host), st->kp_ur, kur.bytes());
+        float* qu = qur.at(S.host);
+        for (size_t q = 0; q < m; ++q) qu[q] = st->q_ur[q * (size_t)st->q_ur_stride];   // packed on the way up: the device reads stride 1
+    }
     HIP_TRY_AT("slamit_guided_search", slamit_stage_upload(S, L));
     SearchDev D;
     D.nframes = 1; D.kp_cap = std::max(F->n, 1); D.q_cap = Q->m; D.cand_cap = (int)cap;
@@ -373,6 +440,8 @@ extern "C" int slamit_guided_search(int device, const slamit_frame_view* F, cons
     D.uvr = uvr.at(S.dev); D.lmin = l0.at(S.dev); D.lmax = l1.at(S.dev); D.qdesc = qd.at(S.dev); D.valid = va.at(S.dev); D.takes = tq.at(S.dev);
     D.cand = cand.at(S.dev); D.cand_n = cn.at(S.dev); D.tent = te.at(S.dev);
     search_rule_fill(D, rule);
+    D.er_mode = er_mode; D.chi2_gate_stereo = er_mode ? st->chi2_gate_stereo : 0.f;
+    D.kp_ur = er_mode ? kur.at(S.dev) : nullptr; D.q_ur = er_mode ? qur.at(S.dev) : nullptr; D.q_ur_stride = 1;
     D.match_kp = mk.at(S.dev); D.out4 = o4.at(S.dev); D.nmatches = nm.at(S.dev);
     search_launch(S.st, D, Q->m);
     HIP_TRY_AT("slamit_guided_search", slamit_stage_download_and_wait(S, L));
@@ -388,16 +457,30 @@ extern "C" int slamit_guided_search(int device, const slamit_frame_view* F, cons
     return SLAMIT_OK;
 }
 
+extern "C" int slamit_guided_search(int device, const slamit_frame_view* F, const slamit_search_queries* Q,
+                                    const slamit_search_rule* rule, int32_t* match_kp, int32_t* nmatches, int32_t* best_dist,
+                                    int32_t* best_level, int32_t* second_dist, int32_t* second_level) {
+    return slamit_guided_search_stereo(device, F, Q, rule, nullptr, match_kp, nmatches, best_dist, best_level, second_dist, second_level);
+}
+
 extern "C" size_t slamit_guided_search_workspace(int nframes, int q_cap) {
     if (nframes < 0 || q_cap < 0) return 0;
     return (size_t)nframes * q_cap * (8 * (size_t)SLAMIT_SEARCH_BATCH_CAND + 16 + 4) + 256;
 }
 
-extern "C" int slamit_guided_search_batch_dev(int device, const slamit_search_batch* B, const slamit_search_rule* rule,
-                                              int32_t* d_match_kp, int32_t* d_nmatches, int32_t* d_out4, void* d_workspace,
-                                              size_t workspace_bytes, void* stream) {
+extern "C" int slamit_guided_search_stereo_batch_dev(int device, const slamit_search_batch* B, const slamit_search_rule* rule,
+                                                     const slamit_search_stereo_dev* st, int32_t* d_match_kp, int32_t* d_nmatches, int32_t* d_out4,
+                                                     void* d_workspace, size_t workspace_bytes, void* stream) {
     if (!B || !rule || !d_match_kp || !d_nmatches || B->nframes < 0 || B->kp_cap < 0 || B->q_cap < 0)
         return slamit_fail(SLAMIT_ERR_ARG, "slamit_guided_search_batch_dev: bad argument");
+    const int er_mode = st ? st->er_mode : SLAMIT_SEARCH_ER_NONE;
+    if (st) {
+        const int rc = search_stereo_check(true, rule, er_mode, st->q_ur_stride);
+        if (rc != SLAMIT_OK) return rc;
+        // the host cannot see d_n / d_m: a batch with frames and room for queries has work to do
+        if (er_mode != SLAMIT_SEARCH_ER_NONE && B->nframes && B->q_cap && (!st->d_q_ur || (B->kp_cap && !st->d_kp_ur)))
+            return slamit_fail(SLAMIT_ERR_ARG, "slamit_guided_search_stereo_batch_dev: er_mode set with a null d_kp_ur or d_q_ur");
+    }
     if (B->nframes == 0) return SLAMIT_OK;
     if (!B->d_n || !B->d_kps_un || !B->d_desc || !B->d_kp_taken || !B->d_m || !B->d_uvr || !B->d_level_min || !B->d_level_max ||
         !B->d_qdesc || !B->d_valid || !B->d_takes || !d_workspace)
@@ -418,8 +501,16 @@ extern "C" int slamit_guided_search_batch_dev(int device, const slamit_search_ba
     D.tent = D.cand + nq * SLAMIT_SEARCH_BATCH_CAND;
     D.cand_n = reinterpret_cast<int*>(D.tent + 2 * nq);
     search_rule_fill(D, rule);
+    D.er_mode = er_mode; D.chi2_gate_stereo = er_mode ? st->chi2_gate_stereo : 0.f;
+    D.kp_ur = er_mode ? st->d_kp_ur : nullptr; D.q_ur = er_mode ? st->d_q_ur : nullptr; D.q_ur_stride = er_mode ? st->q_ur_stride : 1;
     D.match_kp = d_match_kp; D.out4 = d_out4; D.nmatches = d_nmatches;
     search_launch((hipStream_t)stream, D, B->q_cap);
     HIP_TRY(hipGetLastError());
     return SLAMIT_OK;
+}
+
+extern "C" int slamit_guided_search_batch_dev(int device, const slamit_search_batch* B, const slamit_search_rule* rule,
+                                              int32_t* d_match_kp, int32_t* d_nmatches, int32_t* d_out4, void* d_workspace,
+                                              size_t workspace_bytes, void* stream) {
+    return slamit_guided_search_stereo_batch_dev(device, B, rule, nullptr, d_match_kp, d_nmatches, d_out4, d_workspace, workspace_bytes, stream);
 }

@@ -50,7 +50,8 @@ void ORBmatcher::setStatus(int rc) { shim::status<ORBmatcher>() = rc; }
 bool ORBmatcher::GuidedSearch(const std::vector<cv::KeyPoint>& keysUn, const cv::Mat& descriptors,
                               const std::vector<uint8_t>& kpTaken, float minX, float minY, float invW, float invH,
                               const GuidedQueries& q, int thDist, bool useRatio, float nnratio, std::vector<int>& matchKp,
-                              float chi2Gate, const std::vector<float>* invLevelSigma2, int mode, std::vector<int>* acceptedKp) {
+                              float chi2Gate, const std::vector<float>* invLevelSigma2, int mode, std::vector<int>* acceptedKp,
+                              const StereoGate* stereo) {
     const int n = (int)keysUn.size(), m = q.size();
     matchKp.assign(m, -1);
     setStatus(SLAMIT_OK);
@@ -72,6 +73,14 @@ bool ORBmatcher::GuidedSearch(const std::vector<cv::KeyPoint>& keysUn, const cv:
     for (int i = 0; i < 16; ++i) rule.inv_level_sigma2[i] = (invLevelSigma2 && i < (int)invLevelSigma2->size()) ? (*invLevelSigma2)[i] : 1.f;
     int nm = 0;
     if (acceptedKp) acceptedKp->assign(m, -1);
+    if (stereo && stereo->erMode != SLAMIT_SEARCH_ER_NONE) {
+        slamit_search_stereo st;
+        st.er_mode = stereo->erMode; st.chi2_gate_stereo = stereo->chi2GateStereo;
+        st.kp_ur = stereo->kpUr.data(); st.q_ur = q.ur.data(); st.q_ur_stride = 1;
+        if ((int)stereo->kpUr.size() != n || (int)q.ur.size() != m) { setStatus(SLAMIT_ERR_ARG); return false; }
+        setStatus(slamit_guided_search_stereo(0, &fv, &sq, &rule, &st, matchKp.data(), &nm, nullptr, acceptedKp ? acceptedKp->data() : nullptr, nullptr, nullptr));
+        return LastStatus() == SLAMIT_OK;
+    }
     setStatus(slamit_guided_search(0, &fv, &sq, &rule, matchKp.data(), &nm, nullptr, acceptedKp ? acceptedKp->data() : nullptr, nullptr, nullptr));
     return LastStatus() == SLAMIT_OK;
 }
@@ -90,6 +99,20 @@ bool ORBmatcher::Project(std::vector<ProjectPoints>& batch) {
         P[k].octave = b.octave.data(); P[k].skip = b.skip.data();
         R[k].status = b.status.data(); R[k].proj = b.proj.data(); R[k].level = b.level.data(); R[k].uvr = b.uvr.data();
         R[k].level_min = b.lmin.data(); R[k].level_max = b.lmax.data(); R[k].valid = b.valid.data(); R[k].n_valid = 0;
+    }
+    bool wantUr = false;
+    for (size_t k = 0; k < batch.size(); ++k) wantUr = wantUr || batch[k].wantUr;
+    if (wantUr) {   // one camera of the batch searches a stereo frame: every problem gets its ur (bf = 0 and unread for the others)
+        std::vector<float> bf(batch.size());
+        std::vector<float*> ur(batch.size());
+        for (size_t k = 0; k < batch.size(); ++k) {
+            batch[k].ur.assign((size_t)batch[k].size() + 1, 0.f);   // + 1: never a null pointer for an empty problem
+            batch[k].wantUr = true;
+            bf[k] = batch[k].bf; ur[k] = batch[k].ur.data();
+        }
+        const int rc = slamit_project_batch_stereo(0, (int)batch.size(), P.data(), R.data(), bf.data(), ur.data());
+        if (rc != SLAMIT_OK) { shim::report<ORBmatcher>("slamit_project_batch_stereo", rc); return false; }
+        return true;
     }
     const int rc = slamit_project_batch(0, (int)batch.size(), P.data(), R.data());
     if (rc != SLAMIT_OK) { shim::report<ORBmatcher>("slamit_project_batch", rc); return false; }

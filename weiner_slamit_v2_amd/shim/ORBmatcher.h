@@ -69,17 +69,21 @@ public:
     //              mfGridElementWidthInv, mfGridElementHeightInv
     //   MapPoint : mbTrackInView, isBad(), mnTrackScaleLevel, mTrackViewCos, mTrackProjX, mTrackProjY,
     //              GetDescriptor(), Observations()
-    // Mono only: a frame with a stereo keypoint (mvuRight > 0) is refused (returns 0, LastStatus() != 0).
+    // A frame with a stereo keypoint (mvuRight > 0) is searched with the right-image test of ORBmatcher.cc:93-98 when MapPointT has
+    // mTrackProjXR (the reference's has); a MapPointT without it keeps the monocular code, which refuses such a frame (returns 0,
+    // LastStatus() != 0).
     template <class FrameT, class MapPointT>
     int SearchByProjection(FrameT& F, const std::vector<MapPointT*>& vpMapPoints, const float th = 3);
 
     // Tracking::TrackWithMotionModel's search (ORBmatcher.cc:1332-1474).  Additional members:
     //   Frame    : N, mTcw, mvbOutlier, mvKeys, fx, fy, cx, cy, mb, static mnMaxX, mnMaxY
     //   MapPoint : GetWorldPos()
+    // Stereo keypoints in CurrentFrame (mvuRight > 0): ur = u - mbf * invzc and the test of :1411-1417 when FrameT has mbf; refused otherwise.
     template <class FrameT>
     int SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame, const float th, const bool bMono);
 
-    // LocalMapping::SearchInNeighbors' projection fuse (ORBmatcher.cc:829-979), mono.  Projection, depth / viewing-angle
+    // LocalMapping::SearchInNeighbors' projection fuse (ORBmatcher.cc:829-979).  A keyframe with stereo keypoints (mvuRight >= 0) takes
+    // the three-term reprojection gate of :918-931 (ur = u - mbf * invz, chi2 7.8) when KeyFrameT has mbf; refused otherwise.  Projection, depth / viewing-angle
     // checks and the Replace / AddObservation bookkeeping are host code; the per-point window query with the level and
     // reprojection (chi2 5.99) gates and the nearest-descriptor choice of ALL points is one device call (no keypoint is
     // "taken" here: the choices are independent).  Additional members:
@@ -170,8 +174,9 @@ public:
         std::vector<float> uvr;
         std::vector<int32_t> lmin, lmax;
         std::vector<uint8_t> desc, valid, takes;
-        void add(float u, float v, float r, int l0, int l1, const cv::Mat& d, bool takesKp) {
-            uvr.push_back(u); uvr.push_back(v); uvr.push_back(r);
+        std::vector<float> ur;   // per query: its right-image column (mTrackProjXR, or u - mbf * invz); read only with a StereoGate
+        void add(float u, float v, float r, int l0, int l1, const cv::Mat& d, bool takesKp, float uR = 0.f) {
+            uvr.push_back(u); uvr.push_back(v); uvr.push_back(r); ur.push_back(uR);
             lmin.push_back(l0); lmax.push_back(l1);
             const uint8_t* p = d.ptr<uint8_t>(0);
             desc.insert(desc.end(), p, p + 32);
@@ -179,18 +184,35 @@ public:
         }
         int size() const { return (int)lmin.size(); }
     };
+    // The stereo record of a search (slamit_search_stereo): the searched frame's mvuRight and the rule; the queries' side is q.ur.
+    struct StereoGate {
+        int erMode;                 // SLAMIT_SEARCH_ER_RADIUS (the two SearchByProjection) or SLAMIT_SEARCH_ER_CHI2 (Fuse)
+        float chi2GateStereo;       // 7.8 for CHI2
+        std::vector<float> kpUr;    // mvuRight
+        StereoGate() : erMode(SLAMIT_SEARCH_ER_NONE), chi2GateStereo(7.8f) {}
+        // fills kpUr from the frame and says whether it has a keypoint the mode counts as stereo (> 0 for RADIUS, >= 0 for CHI2)
+        template <class VecT>
+        bool load(const VecT& mvuRight, size_t n, int mode) {
+            erMode = mode;
+            kpUr.resize(n);
+            bool any = false;
+            for (size_t i = 0; i < n; ++i) { kpUr[i] = mvuRight[i]; any = any || (mode == SLAMIT_SEARCH_ER_CHI2 ? kpUr[i] >= 0 : kpUr[i] > 0); }
+            return any;
+        }
+    };
     static bool GuidedSearch(const std::vector<cv::KeyPoint>& keysUn, const cv::Mat& descriptors,
                              const std::vector<uint8_t>& kpTaken, float minX, float minY, float invW, float invH,
                              const GuidedQueries& q, int thDist, bool useRatio, float nnratio, std::vector<int>& matchKp,
                              float chi2Gate = 0.f, const std::vector<float>* invLevelSigma2 = nullptr, int mode = 0,
-                             std::vector<int>* acceptedKp = nullptr);
+                             std::vector<int>* acceptedKp = nullptr, const StereoGate* stereo = nullptr);
     // The same over the searched frame or keyframe: mvKeysUn, mDescriptors, mnMinX, mnMinY and the two grid inverses are its own.
     template <class FrameT>
     static bool GuidedSearch(const FrameT& F, const std::vector<uint8_t>& kpTaken, const GuidedQueries& q, int thDist, bool useRatio,
                              float nnratio, std::vector<int>& matchKp, float chi2Gate = 0.f,
-                             const std::vector<float>* invLevelSigma2 = nullptr, int mode = 0, std::vector<int>* acceptedKp = nullptr) {
+                             const std::vector<float>* invLevelSigma2 = nullptr, int mode = 0, std::vector<int>* acceptedKp = nullptr,
+                             const StereoGate* stereo = nullptr) {
         return GuidedSearch(F.mvKeysUn, F.mDescriptors, kpTaken, F.mnMinX, F.mnMinY, F.mfGridElementWidthInv, F.mfGridElementHeightInv, q,
-                            thDist, useRatio, nnratio, matchKp, chi2Gate, invLevelSigma2, mode, acceptedKp);
+                            thDist, useRatio, nnratio, matchKp, chi2Gate, invLevelSigma2, mode, acceptedKp, stereo);
     }
     // One camera's points for slamit_project, in the order the driver visits them (a point the driver's own tests drop before the
     // projection travels as skipped, so that query i is point i), and the call's results.
@@ -202,14 +224,17 @@ public:
         std::vector<uint8_t> status, valid;
         std::vector<float> proj, uvr;
         std::vector<int32_t> level, lmin, lmax;
-        ProjectPoints() { memset(&cam, 0, sizeof(cam)); }
+        float bf;                 // the camera's mbf
+        bool wantUr;              // also ask for ur = u - bf * invz (slamit_project_batch_stereo); forms LAST_FRAME and FUSE read it
+        std::vector<float> ur;
+        ProjectPoints() : bf(0.f), wantUr(false) { memset(&cam, 0, sizeof(cam)); }
         int size() const { return (int)skip.size(); }
         void add(bool skipped, const float P[3], const float Pn[3], float maxDist, float minDist, int oct) {
             for (int c = 0; c < 3; ++c) { pos.push_back(skipped ? 0.f : P[c]); normal.push_back(skipped || !Pn ? 0.f : Pn[c]); }
             maxd.push_back(maxDist); mind.push_back(minDist); octave.push_back(oct); skip.push_back(skipped ? 1 : 0);
         }
         void query(int i, GuidedQueries& q, const cv::Mat& d, bool takesKp) const {
-            q.add(uvr[3 * i], uvr[3 * i + 1], uvr[3 * i + 2], lmin[i], lmax[i], d, takesKp);
+            q.add(uvr[3 * i], uvr[3 * i + 1], uvr[3 * i + 2], lmin[i], lmax[i], d, takesKp, wantUr ? ur[i] : 0.f);
         }
     };
     // ONE slamit_project_batch call for all of them; false: reported, LastStatus() != 0
@@ -234,10 +259,12 @@ protected:
     static void setStatus(int rc);
     void ComputeThreeMaxima(std::vector<int>* histo, const int L, int& ind1, int& ind2, int& ind3);
 
-    // Fuse(pKF, vpMapPoints, th) in its parts: the refusal of stereo keyframes, the projection input of one target, the queries of the
+    // Fuse(pKF, vpMapPoints, th) in its parts: the refusal of stereo keyframes whose type has no mbf, the projection input of one target, the queries of the
     // points the device accepted (re-testing isBad / IsInKeyFrame, reading descriptors NOW), and the search with its bookkeeping
     template <class KeyFrameT>
     bool fuseAdmits(KeyFrameT* pKF);
+    template <class KeyFrameT>
+    static bool fuseIsStereo(KeyFrameT* pKF);
     template <class KeyFrameT, class MapPointT>
     void fuseProjection(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, float th, ProjectPoints& pp);
     template <class KeyFrameT, class MapPointT>
@@ -257,10 +284,11 @@ int ORBmatcher::SearchByProjection(FrameT& F, const std::vector<MapPointT*>& vpM
     const bool bFactor = th != 1.0;
     const int n = (int)F.mvKeysUn.size();
     std::vector<uint8_t> taken(n, 0);
-    for (int i = 0; i < n; ++i) {
-        if (F.mvuRight[i] > 0) { setStatus(SLAMIT_ERR_ARG); return 0; }
+    StereoGate gate;
+    const bool stereo = gate.load(F.mvuRight, (size_t)n, SLAMIT_SEARCH_ER_RADIUS);
+    if (stereo && !shim::has_member_mTrackProjXR<MapPointT>::value) { setStatus(SLAMIT_ERR_ARG); return 0; }   // a map point type without mTrackProjXR: monocular only
+    for (int i = 0; i < n; ++i)
         if (F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0) taken[i] = 1;
-    }
     GuidedQueries q;
     std::vector<MapPointT*> who;
     for (size_t iMP = 0; iMP < vpMapPoints.size(); iMP++) {
@@ -272,11 +300,11 @@ int ORBmatcher::SearchByProjection(FrameT& F, const std::vector<MapPointT*>& vpM
         float r = pMP->mTrackViewCos > 0.998 ? 2.5f : 4.0f;
         if (bFactor) r *= th;
         q.add(pMP->mTrackProjX, pMP->mTrackProjY, r * F.mvScaleFactors[nPredictedLevel], nPredictedLevel - 1, nPredictedLevel,
-              pMP->GetDescriptor(), pMP->Observations() > 0);
+              pMP->GetDescriptor(), pMP->Observations() > 0, shim::member_or_mTrackProjXR(*pMP, 0.f));
         who.push_back(pMP);
     }
     std::vector<int> matchKp;
-    if (!GuidedSearch(F, taken, q, TH_HIGH, true, mfNNratio, matchKp)) return 0;
+    if (!GuidedSearch(F, taken, q, TH_HIGH, true, mfNNratio, matchKp, 0.f, nullptr, 0, nullptr, stereo ? &gate : nullptr)) return 0;
     int nmatches = 0;
     for (size_t k = 0; k < who.size(); ++k)
         if (matchKp[k] >= 0) { F.mvpMapPoints[matchKp[k]] = who[k]; nmatches++; }
@@ -304,10 +332,12 @@ template <class FrameT>
 int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame, const float th, const bool bMono) {
     const int n = (int)CurrentFrame.mvKeysUn.size();
     std::vector<uint8_t> taken(n, 0);
-    for (int i = 0; i < n; ++i) {
-        if (CurrentFrame.mvuRight[i] > 0) { setStatus(SLAMIT_ERR_ARG); return 0; }
+    StereoGate gate;
+    const bool stereo = gate.load(CurrentFrame.mvuRight, (size_t)n, SLAMIT_SEARCH_ER_RADIUS);
+    if (stereo && !shim::has_member_mbf<FrameT>::value) { setStatus(SLAMIT_ERR_ARG); return 0; }   // a frame type without mbf: monocular only
+    const float mbf = shim::member_or_mbf(CurrentFrame, 0.f);
+    for (int i = 0; i < n; ++i)
         if (CurrentFrame.mvpMapPoints[i] && CurrentFrame.mvpMapPoints[i]->Observations() > 0) taken[i] = 1;
-    }
     float Rcw[3][3], tcw[3], Rlw[3][3], tlw[3];
     shim::load3x3(CurrentFrame.mTcw, &Rcw[0][0]); shim::load3(CurrentFrame.mTcw, tcw, 3);
     shim::load3x3(LastFrame.mTcw, &Rlw[0][0]); shim::load3(LastFrame.mTcw, tlw, 3);
@@ -325,6 +355,7 @@ int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame
         ProjectCamera(pp[0].cam, SLAMIT_PROJECT_LAST_FRAME, CurrentFrame, CurrentFrame.fx, CurrentFrame.fy, CurrentFrame.cx, CurrentFrame.cy, th);
         memcpy(pp[0].cam.R, Rcw, sizeof(Rcw)); memcpy(pp[0].cam.t, tcw, sizeof(tcw));
         pp[0].cam.direction = bForward ? 1 : bBackward ? 2 : 0;
+        pp[0].bf = mbf; pp[0].wantUr = stereo;
         for (int i = 0; i < LastFrame.N; i++) {
             auto* pMP = LastFrame.mvpMapPoints[i];
             const bool skipped = !pMP || LastFrame.mvbOutlier[i];
@@ -359,11 +390,12 @@ int ORBmatcher::SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame
         if (bForward) { l0 = nLastOctave; l1 = -1; }
         else if (bBackward) { l0 = 0; l1 = nLastOctave; }
         else { l0 = nLastOctave - 1; l1 = nLastOctave + 1; }
-        q.add(u, v, radius, l0, l1, pMP->GetDescriptor(), pMP->Observations() > 0);
+        const float ur = u - mbf * invzc;   // :1413
+        q.add(u, v, radius, l0, l1, pMP->GetDescriptor(), pMP->Observations() > 0, ur);
         who.push_back(i);
     }
     std::vector<int> matchKp;
-    if (!GuidedSearch(CurrentFrame, taken, q, TH_HIGH, false, mfNNratio, matchKp)) return 0;
+    if (!GuidedSearch(CurrentFrame, taken, q, TH_HIGH, false, mfNNratio, matchKp, 0.f, nullptr, 0, nullptr, stereo ? &gate : nullptr)) return 0;
     int nmatches = 0;
     shim::RotationHistogram rotHist;
     for (size_t k = 0; k < who.size(); ++k) {
@@ -847,9 +879,16 @@ int ORBmatcher::SearchForInitialization(FrameT& F1, FrameT& F2, std::vector<cv::
 }
 
 template <class KeyFrameT>
-bool ORBmatcher::fuseAdmits(KeyFrameT* pKF) {
+bool ORBmatcher::fuseIsStereo(KeyFrameT* pKF) {
     for (size_t i = 0; i < pKF->mvKeysUn.size(); ++i)
-        if (pKF->mvuRight[i] >= 0) { setStatus(SLAMIT_ERR_ARG); return false; }   // stereo keypoints: not on this path
+        if (pKF->mvuRight[i] >= 0) return true;
+    return false;
+}
+
+template <class KeyFrameT>
+bool ORBmatcher::fuseAdmits(KeyFrameT* pKF) {
+    if (shim::has_member_mbf<KeyFrameT>::value) return true;                     // the three-term gate needs the keyframe's mbf
+    if (fuseIsStereo(pKF)) { setStatus(SLAMIT_ERR_ARG); return false; }          // a keyframe type without it: monocular only
     return true;
 }
 
@@ -857,6 +896,7 @@ template <class KeyFrameT, class MapPointT>
 void ORBmatcher::fuseProjection(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, float th, ProjectPoints& pp) {
     ProjectCamera(pp.cam, SLAMIT_PROJECT_FUSE, *pKF, pKF->fx, pKF->fy, pKF->cx, pKF->cy, th);
     shim::load3x3(pKF->GetRotation(), pp.cam.R); shim::load3(pKF->GetTranslation(), pp.cam.t); shim::load3(pKF->GetCameraCenter(), pp.cam.O);
+    pp.bf = shim::member_or_mbf(*pKF, 0.f); pp.wantUr = shim::has_member_mbf<KeyFrameT>::value && fuseIsStereo(pKF);
     for (size_t i = 0; i < vpMapPoints.size(); i++) {
         MapPointT* pMP = vpMapPoints[i];
         const bool skipped = !pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF);
@@ -893,7 +933,7 @@ int ORBmatcher::Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints,
     const cv::Mat Rcw = pKF->GetRotation(), tcw = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
     float R[3][3], t[3], O[3];
     shim::load3x3(Rcw, &R[0][0]); shim::load3(tcw, t); shim::load3(Ow, O);
-    const float fx = pKF->fx, fy = pKF->fy, cx = pKF->cx, cy = pKF->cy;
+    const float fx = pKF->fx, fy = pKF->fy, cx = pKF->cx, cy = pKF->cy, bf = shim::member_or_mbf(*pKF, 0.f);
     for (size_t i = 0; i < vpMapPoints.size(); i++) {
         MapPointT* pMP = vpMapPoints[i];
         if (!pMP) continue;
@@ -907,6 +947,7 @@ int ORBmatcher::Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints,
         const float x = xc * invz, y = yc * invz;
         const float u = fx * x + cx, v = fy * y + cy;
         if (!pKF->IsInImage(u, v)) continue;
+        const float ur = u - bf * invz;   // :874
         const float maxDistance = pMP->GetMaxDistanceInvariance(), minDistance = pMP->GetMinDistanceInvariance();
         const float PO[3] = {X - O[0], Y - O[1], Z - O[2]};
         const float dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);   // cv::norm: double accumulation
@@ -916,7 +957,7 @@ int ORBmatcher::Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints,
         if (dot < 0.5 * dist3D) continue;   // viewing angle below 60 degrees
         const int nPredictedLevel = pMP->PredictScale(dist3D, pKF->mfLogScaleFactor);
         const float radius = th * pKF->mvScaleFactors[nPredictedLevel];
-        q.add(u, v, radius, nPredictedLevel - 1, nPredictedLevel, pMP->GetDescriptor(), false);
+        q.add(u, v, radius, nPredictedLevel - 1, nPredictedLevel, pMP->GetDescriptor(), false, ur);
         who.push_back(pMP);
     }
     return fuseTail(pKF, q, who);
@@ -926,7 +967,9 @@ template <class KeyFrameT, class MapPointT>
 int ORBmatcher::fuseTail(KeyFrameT* pKF, const GuidedQueries& q, const std::vector<MapPointT*>& who) {
     std::vector<int> matchKp;
     const std::vector<uint8_t> none(pKF->mvKeysUn.size(), 0);
-    if (!GuidedSearch(*pKF, none, q, TH_LOW, false, mfNNratio, matchKp, 5.99f, &pKF->mvInvLevelSigma2)) return 0;
+    StereoGate gate;   // :918-931: a keypoint with mvuRight >= 0 is gated by the three-term e2 against 7.8 (fuseAdmits let it through)
+    const bool stereo = gate.load(pKF->mvuRight, pKF->mvKeysUn.size(), SLAMIT_SEARCH_ER_CHI2);
+    if (!GuidedSearch(*pKF, none, q, TH_LOW, false, mfNNratio, matchKp, 5.99f, &pKF->mvInvLevelSigma2, 0, nullptr, stereo ? &gate : nullptr)) return 0;
     int nFused = 0;
     for (size_t k = 0; k < who.size(); ++k) {
         const int bestIdx = matchKp[k];

@@ -46,6 +46,26 @@ inline void load3(const MatT& m, float* out, int col = 0, int stride = 1) {
     for (int r = 0; r < 3; ++r) out[stride * r] = m.template at<float>(r, col);
 }
 
+// Does the caller's type have a data member of this name?  C++11 member detection: has_member_<name><T>::value, and
+// member_or_<name>(obj, fallback) reads it where it exists.  The stereo paths of the guided searches are chosen by it at compile time
+// (mTrackProjXR on the map point, mbf on the frame or keyframe): a type without the member keeps the monocular code and its refusal
+// of stereo frames, and never names the member.
+template <bool B> struct bool_tag {};
+#define SLAMIT_SHIM_HAS_MEMBER(name)                                                                                   \
+    template <class T>                                                                                                 \
+    struct has_member_##name {                                                                                         \
+        template <class U> static char test(decltype(&U::name));                                                       \
+        template <class U> static long test(...);                                                                      \
+        static const bool value = sizeof(test<T>(0)) == sizeof(char);                                                  \
+    };                                                                                                                 \
+    template <class T> inline float member_or_##name(const T& o, float, bool_tag<true>) { return o.name; }             \
+    template <class T> inline float member_or_##name(const T&, float fallback, bool_tag<false>) { return fallback; }   \
+    template <class T> inline float member_or_##name(const T& o, float fallback) {                                     \
+        return member_or_##name(o, fallback, bool_tag<has_member_##name<T>::value>());                                 \
+    }
+SLAMIT_SHIM_HAS_MEMBER(mTrackProjXR)
+SLAMIT_SHIM_HAS_MEMBER(mbf)
+
 // The rotation-consistency filter of the reference's searches (ORBmatcher.cc:240-250 with :271-289, and its copies): matches
 // are binned by the difference of their keypoint angles, and those outside the three most populated bins are undone.
 class RotationHistogram {

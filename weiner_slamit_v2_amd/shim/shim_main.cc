@@ -309,8 +309,9 @@ static int run_pose(int argc, char** argv) {
 struct MockTrackPoint {
     bool mbTrackInView, bad;
     int mnTrackScaleLevel, nobs, id;
-    float mTrackViewCos, mTrackProjX, mTrackProjY, maxd, mind;
+    float mTrackViewCos, mTrackProjX, mTrackProjXR, mTrackProjY, maxd, mind;
     cv::Mat desc, pos;
+    MockTrackPoint() : mTrackProjXR(0.f) {}
     float GetMaxDistance() { return maxd; }   // raw (projection mode only)
     float GetMinDistance() { return mind; }
     float GetMaxDistanceInvariance() { return g_real_scale ? 1.2f * maxd : maxd; }
@@ -328,7 +329,7 @@ struct MockSearchFrame {
     std::vector<MockTrackPoint*> mvpMapPoints;
     std::vector<float> mvuRight, mvScaleFactors;
     std::vector<bool> mvbOutlier;
-    float fx, fy, cx, cy, mb, mfLogScaleFactor;
+    float fx, fy, cx, cy, mb, mbf, mfLogScaleFactor;
     static float mnMinX, mnMaxX, mnMinY, mnMaxY, mfGridElementWidthInv, mfGridElementHeightInv;
 };
 struct MockRelocKF {
@@ -366,11 +367,13 @@ static cv::Mat pose_from(const float* p12) {   // R row-major (9) then t (3)
 //                           int32 has[m] outlier[m] octave[m] nobs[m] ; u8 desc[32m]
 //   variant 2 (relocalization, keyframe map points): float Tcw[12] intr[4] ; int32 orbdist ; float world[3m] angle[m] maxd[m]
 //                           mind[m] ; int32 has[m] bad[m] found[m] level[m] ; u8 desc[32m]
+//   optional tail, a stereo frame: variant 0: float mvuRight[n] ; float mTrackProjXR[m].  variant 1: float mbf ; float mvuRight[n]
 // out.bin: int32 status nmatches ; int32 owner[n] (-1 none, -2 the frame's own earlier point, else query index)
 static int run_search(int argc, char** argv) {
     if (argc < 4) return 2;
     std::vector<unsigned char> raw = slurp(argv[2]);
     Reader R{raw.data()};
+    const unsigned char* const end = raw.data() + raw.size();
     const int variant = R.get<int>(), n = R.get<int>(), m = R.get<int>();
     const float th = R.get<float>(), nnratio = R.get<float>();
     projection_mode(argc, argv, 4);
@@ -412,6 +415,11 @@ static int run_search(int argc, char** argv) {
             p.mTrackViewCos = vc[q]; p.mTrackProjX = proj[2 * q]; p.mTrackProjY = proj[2 * q + 1];
             p.desc = cv::Mat(1, 32, CV_8U); memcpy(p.desc.ptr(0), qd + 32 * (size_t)q, 32);
             vp[q] = &p;
+        }
+        if (R.p < end) {
+            const float* ur = R.arr<float>(n); const float* xr = R.arr<float>(m);
+            F.mvuRight.assign(ur, ur + n);
+            for (int q = 0; q < m; ++q) mps[q].mTrackProjXR = xr[q];
         }
         ORBmatcher matcher(nnratio, true);
         nm = matcher.SearchByProjection(F, vp, th);
@@ -457,6 +465,12 @@ static int run_search(int argc, char** argv) {
             L.mvbOutlier[q] = outl[q] != 0;
         }
         L.mvKeysUn = L.mvKeys;
+        F.mbf = 0.f;
+        if (R.p < end) {
+            F.mbf = R.get<float>();
+            const float* ur = R.arr<float>(n);
+            F.mvuRight.assign(ur, ur + n);
+        }
         ORBmatcher matcher(0.9f, true, g_device_projection);
         nm = matcher.SearchByProjection(F, L, th, mono != 0);
     }
@@ -548,9 +562,10 @@ struct MockFusePoint {
 };
 struct MockFuseKF {
     cv::Mat R, t, O, mDescriptors, mK;
-    float fx, fy, cx, cy, mfLogScaleFactor;
+    float fx, fy, cx, cy, mbf, mfLogScaleFactor;
     float mnMinX, mnMinY, mnMaxX, mnMaxY, mfGridElementWidthInv, mfGridElementHeightInv;
     std::vector<float> mvScaleFactors, mvInvLevelSigma2, mvLevelSigma2, mvuRight;
+    MockFuseKF() : mbf(0.f) {}
     std::vector<cv::KeyPoint> mvKeysUn;
     std::vector<MockFusePoint*> mps;
     cv::Mat GetRotation() { return R.clone(); }
@@ -566,13 +581,14 @@ struct MockFuseKF {
 // problem.bin: int32 n m ; float th ; float R[9] t[3] O[3] ; float intr[4] ; float bounds[6] (minx maxx miny maxy invw invh) ;
 //   float scale[8] invsig[8] ; keypoints: float xy[2n], int32 octave[n], int32 kf_state[n] (0 none, k>0: own point with k-1
 //   observations), u8 desc[32n] ; map points: float pos[3m] normal[3m] maxd[m] mind[m], int32 level[m] nobs[m] bad[m] inkf[m]
-//   null[m], u8 desc[32m]
+//   null[m], u8 desc[32m] ; optional tail, a stereo keyframe: float mbf ; float mvuRight[n]
 // out.bin: int32 status nFused ; per map point int32 addedAt, replacedBy (-1 none, -2 a keyframe-own point, else id), bad ;
 //   per keypoint int32 owner (-1 none, -2 own, else map point id)
 static int run_fuse(int argc, char** argv) {
     if (argc < 4) return 2;
     std::vector<unsigned char> raw = slurp(argv[2]);
     Reader Rd{raw.data()};
+    const unsigned char* const end = raw.data() + raw.size();
     const int n = Rd.get<int>(), m = Rd.get<int>();
     const float th = Rd.get<float>();
     projection_mode(argc, argv, 4);
@@ -608,6 +624,11 @@ static int run_fuse(int argc, char** argv) {
         p.desc = cv::Mat(1, 32, CV_8U); memcpy(p.desc.ptr(0), md + 32 * (size_t)j, 32);
         vp[j] = isnull[j] ? (MockFusePoint*)0 : &p;
     }
+    if (Rd.p < end) {
+        KF.mbf = Rd.get<float>();
+        const float* ur = Rd.arr<float>(n);
+        KF.mvuRight.assign(ur, ur + n);
+    }
     ORBmatcher matcher(0.6f, true, g_device_projection);
     const int nf = matcher.Fuse(&KF, vp, th);
     const int status = ORBmatcher::LastStatus();
@@ -629,12 +650,14 @@ static int run_fuse(int argc, char** argv) {
 // problem.bin: int32 nkf m ; float th ; map points: float pos[3m] normal[3m] maxd[m] mind[m] (raw), int32 nobs[m], u8 desc[32m] ;
 //   per target: float R[9] t[3] O[3] intr[4] bounds[6] scale[8] invsig[8] ; int32 n ; float xy[2n] ; int32 octave[n] kf_state[n]
 //   (0 none, k > 0: a point of the target's own with k - 1 observations) ; u8 desc[32n]
+//   optional tail, stereo keyframes: per target float mbf ; float mvuRight[n]
 // out.bin: int32 status nFused ; per map point int32 addedAt replacedBy (-1 none, -2 a target's own point, else id) bad nobs, u8 desc[32] ;
 //   per target per keypoint int32 owner, int32 own point replacedBy
 static int run_fuse_targets(int argc, char** argv) {
     if (argc < 6) return 2;
     std::vector<unsigned char> raw = slurp(argv[2]);
     Reader Rd{raw.data()};
+    const unsigned char* const end = raw.data() + raw.size();
     const int nkf = Rd.get<int>(), m = Rd.get<int>();
     const float th = Rd.get<float>();
     projection_mode(argc, argv, 4);
@@ -682,6 +705,12 @@ static int run_fuse_targets(int argc, char** argv) {
         }
         targets[k] = &K;
     }
+    if (Rd.p < end)
+        for (int k = 0; k < nkf; ++k) {
+            KF[k].mbf = Rd.get<float>();
+            const float* ur = Rd.arr<float>(KF[k].mvKeysUn.size());
+            KF[k].mvuRight.assign(ur, ur + KF[k].mvKeysUn.size());
+        }
     ORBmatcher matcher(0.6f, true, g_device_projection);
     int nf = 0, status = 0;
     if (batch) { nf = matcher.Fuse(targets, vp, th); status = ORBmatcher::LastStatus(); }
@@ -1138,6 +1167,7 @@ float MockLocalFrame::mfGridElementWidthInv, MockLocalFrame::mfGridElementHeight
 // problem.bin: int32 n ; slamit_frustum_frame ; float pos[3 n] normal[3 n] max_dist[n] min_dist[n] ; u8 skip[n] (0, 1 = bad, 2 = seen in this
 //   frame), padded to 4 ; int32 nobs[n] ; u8 desc[32 n] ; int32 nkp ; float nnratio invw invh ; float xy[2 nkp] ; int32 octave[nkp]
 //   state[nkp] (0 none, 1 the frame's own point with observations, 2 its own point without, 3 its own BAD point) ; u8 desc[32 nkp]
+//   optional tail, a stereo frame: float mvuRight[nkp]
 // out.bin: int32 status nmatches ninview ; per local point: int32 inview level visible, float projx projy projxr viewcos ;
 //   per keypoint int32 owner (-1 none, -2 / -3 the frame's own point with / without observations, else local index) ;
 //   int32 visible of the two own points, int32 their mnLastFrameSeen == mnId
@@ -1145,6 +1175,7 @@ static int run_frustum(int argc, char** argv) {
     if (argc < 4) return 2;
     std::vector<unsigned char> raw = slurp(argv[2]);
     Reader R{raw.data()};
+    const unsigned char* const end = raw.data() + raw.size();
     const int n = R.get<int>();
     const slamit_frustum_frame fr = R.get<slamit_frustum_frame>();
     const float* pos = R.arr<float>(3 * (size_t)n); const float* nrm = R.arr<float>(3 * (size_t)n);
@@ -1175,6 +1206,10 @@ static int run_frustum(int argc, char** argv) {
         if (state[i] == 1) F.mvpMapPoints[i] = &own1;
         if (state[i] == 2) F.mvpMapPoints[i] = &own2;
         if (state[i] == 3) F.mvpMapPoints[i] = &ownBad;
+    }
+    if (R.p < end) {
+        const float* ur = R.arr<float>(nkp);
+        F.mvuRight.assign(ur, ur + nkp);
     }
     std::vector<MockLocalPoint> mps(n);
     std::vector<MockLocalPoint*> local(n);

@@ -323,6 +323,59 @@ def synth_search(n_kp=1500, m=600, seed=0, width=640, height=480, th=3.0, crowd=
     return frame, queries
 
 
+def synth_search_stereo(n_kp=300, m=200, seed=0, er_mode=1, displaced_frac=0.5, stereo_frac=0.5, zero_count=3, **kw):
+    """synth_search with the right-image columns of a stereo frame: (frame, queries, stereo), stereo = dict(er_mode, kp_ur (n_kp) =
+    mvuRight, q_ur (m), q_ur_stride = 1, chi2_gate_stereo = 7.8, and for er_mode 2 inv_level_sigma2 (8) and chi2_gate = 5.99).  A
+    query's target is the keypoint its descriptor was derived from (the nearest one in Hamming distance).
+      * about stereo_frac of the keypoints are stereo (kp_ur = x - disparity > 0), the others carry -1;
+      * q_ur sits within a quarter of the window radius of its target's kp_ur (er_mode 2: within half a pixel), so the gate keeps it;
+      * displaced_frac of the stereo TARGET keypoints then have kp_ur moved by 200 px, more than any window radius (th * 4 * 1.2^7 =
+        43 px at th = 3): the gate removes the Hamming-best candidate of the queries that aim at them;
+      * zero_count keypoints carry exactly 0.0f: monocular under RADIUS (`> 0`), stereo under CHI2 (`>= 0`).
+    er_mode 2 (Fuse's gate) also re-centres every query within a pixel of its target, where the two-term 5.99 gate passes, so that
+    what rejects a candidate is the third term."""
+    frame, queries = synth_search(n_kp, m, seed, **kw)
+    rs = np.random.RandomState(7000 + seed)
+    xy, desc = frame["kp_xy"], frame["desc"]
+    if n_kp:
+        bits = np.unpackbits(desc, axis=1).astype(np.int16)
+        qbits = np.unpackbits(queries["desc"], axis=1).astype(np.int16)
+        ham = qbits @ (1 - bits).T + (1 - qbits) @ bits.T
+        tgt = np.argmin(ham, axis=1)
+    else:
+        tgt = np.zeros(m, np.int64)
+    disparity = rs.uniform(2.0, 40.0, n_kp).astype(np.float32)
+    kp_ur = (xy[:, 0] - disparity).astype(np.float32) if n_kp else np.zeros(0, np.float32)
+    mono = (rs.rand(n_kp) >= stereo_frac) | (kp_ur <= 0)
+    kp_ur[mono] = np.float32(-1.0)
+    q_ur = np.zeros(m, np.float32)
+    uvr = queries["uvr"].copy()
+    if er_mode == 2 and n_kp:
+        off = rs.uniform(-0.6, 0.6, (m, 2)).astype(np.float32)
+        grid_out = np.arange(m) % 37 == 0            # synth_search's windows outside the grid stay where they are
+        uvr[~grid_out, :2] = xy[tgt[~grid_out]] + off[~grid_out]
+    for q in range(m):
+        k = int(tgt[q]) if n_kp else 0
+        r = uvr[q, 2]
+        if n_kp and kp_ur[k] > 0:
+            q_ur[q] = kp_ur[k] + np.float32(rs.uniform(-0.25, 0.25)) * (r if er_mode != 2 else np.float32(2.0))
+        else:
+            q_ur[q] = uvr[q, 0] - np.float32(rs.uniform(2.0, 40.0))
+    if n_kp:
+        targets = np.unique(tgt)
+        st_targets = targets[kp_ur[targets] > 0]
+        moved = st_targets[rs.rand(len(st_targets)) < displaced_frac]
+        kp_ur[moved] += np.float32(200.0)
+        zeros = rs.permutation(targets)[:min(zero_count, len(targets))] if n_kp > 3 else np.zeros(0, np.int64)
+        kp_ur[zeros] = np.float32(0.0)
+    queries = dict(queries, uvr=uvr)
+    stereo = dict(er_mode=int(er_mode), kp_ur=kp_ur, q_ur=q_ur, q_ur_stride=1, chi2_gate_stereo=7.8)
+    if er_mode == 2:
+        stereo["inv_level_sigma2"] = _inv_sigma2_table(8, 1.2)
+        stereo["chi2_gate"] = 5.99
+    return frame, queries, stereo
+
+
 def synth_init_pair(n=1500, seed=0):
     """Two frames for ORBmatcher::SearchForInitialization: F2's keypoints are F1's moved by a few pixels (plus clutter),
     descriptors a few bits apart, so that several F1 keypoints compete for one F2 keypoint (the take-over path)."""
