@@ -278,7 +278,7 @@ int slamit_guided_search_stereo(int device, const slamit_frame_view* frame, cons
  * mode 0 (SearchByBoW): per query best / second best with strict '<' over the candidates that are allowed (valid2)
  *   and not yet matched by an earlier query; accepted iff best <= th (th_inclusive, :243) or best < th (:601) and
  *   (float)best < nnratio * (float)second (second = 256 without one); an accepted query takes its candidate.
- * mode 1 (SearchForTriangulation, monocular): per query the candidate of minimum distance among those with
+ * mode 1 (SearchForTriangulation; stereo keypoints through slamit_bow_search_stereo): per query the candidate of minimum distance among those with
  *   dist <= th that pass the epipole test (:737-743) and CheckDistEpipolarLine (:135-158), the LAST such candidate on
  *   ties (:731 'dist > bestDist' lets an equal one replace); candidates are never marked (the reference declares
  *   vbMatched2 but does not set it).  Float expressions are evaluated as written, without contraction.
@@ -313,6 +313,22 @@ typedef struct slamit_bow_rule {
 int slamit_bow_search(int device, const uint8_t* desc1, int32_t n1, const uint8_t* valid1, const uint8_t* desc2, int32_t n2,
                       const uint8_t* valid2, const slamit_bow_groups* groups, const slamit_bow_rule* rule, int32_t* match12,
                       int32_t* dist12, int32_t* nmatches);
+
+/* SearchForTriangulation on stereo keyframes (src/ORBmatcher.cc:695-793): bStereo = mvuRight >= 0 (0.0f counts, NaN does not).
+ * The epipole test (:747-753) runs only when neither the query nor the candidate is stereo; with only_stereo a query that is not
+ * stereo is skipped (:711-713: match12 = -1, dist12 = 256) and so is a candidate that is not (:734-736).  Everything else is
+ * mode 1 of slamit_bow_search.  st == NULL is slamit_bow_search; a record with rule->mode == 0 (SearchByBoW has no stereo branch)
+ * or with a null ur1 / ur2 where there is work to do fails with SLAMIT_ERR_ARG. */
+struct slamit_bow_stereo {
+    const float* ur1;          /* n1: mvuRight of side 1 */
+    const float* ur2;          /* n2 */
+    int32_t only_stereo;       /* bOnlyStereo */
+};
+typedef struct slamit_bow_stereo slamit_bow_stereo;
+
+int slamit_bow_search_stereo(int device, const uint8_t* desc1, int32_t n1, const uint8_t* valid1, const uint8_t* desc2, int32_t n2,
+                             const uint8_t* valid2, const slamit_bow_groups* groups, const slamit_bow_rule* rule,
+                             const slamit_bow_stereo* st, int32_t* match12, int32_t* dist12, int32_t* nmatches);
 
 /* ---- Vocabulary transform (Frame::ComputeBoW / KeyFrame::ComputeBoW) -----------------------------------
  * mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4) (src/Frame.cc:520-527, src/KeyFrame.cc:63-72) of the
@@ -726,8 +742,8 @@ int slamit_sim3_ransac(int device, const slamit_sim3_ransac_problem* prob, slami
  * status[i] is the first gate that rejected pair i, in the reference's order:
  *   0 accepted   1 parallax   2 w == 0   3 z1 <= 0   4 z2 <= 0   5 reprojection in keyframe 1   6 reprojection in keyframe 2
  *   7 dist1 == 0 or dist2 == 0   8 scale consistency
- * x3d[3i..] is the point of pair i (zero for codes 1 and 2, which have none).  Stereo keypoints are not handled: there is no
- * right-image coordinate in the problem.  n above SLAMIT_TRIANGULATE_MAX_N, n_levels outside [1, SLAMIT_MAX_LEVELS], an octave
+ * x3d[3i..] is the point of pair i (zero for codes 1 and 2, which have none).  Stereo keypoints go through
+ * slamit_triangulate_stereo* below: there is no right-image coordinate in this problem.  n above SLAMIT_TRIANGULATE_MAX_N, n_levels outside [1, SLAMIT_MAX_LEVELS], an octave
  * outside [0, n_levels) or a null array with n > 0 fails with SLAMIT_ERR_ARG and a message before anything is launched;
  * n == 0 and nproblems == 0 are valid and write nothing but n_accepted = 0. */
 #define SLAMIT_TRIANGULATE_MAX_N 8192      /* pairs per problem (the keypoints of a frame) */
@@ -757,6 +773,36 @@ typedef struct slamit_triangulate_result {
 /* nproblems keyframe pairs in one launch (host pointers, synchronous). */
 int slamit_triangulate_batch(int device, int nproblems, const slamit_triangulate_problem* probs, slamit_triangulate_result* results);
 int slamit_triangulate(int device, const slamit_triangulate_problem* prob, slamit_triangulate_result* res);
+
+/* Stereo keypoints in CreateNewMapPoints (src/LocalMapping.cc:335-465, src/KeyFrame.cc:623-639).  A pair whose keypoint in either
+ * keyframe has mvuRight >= 0 (0.0f counts, NaN does not) takes the reference's stereo branches: the stereo cosine
+ * cos(2 atan2(mb / 2, mvDepth)) of keyframe 1, ELSE of keyframe 2, beside the parallax of the rays; triangulation without the
+ * 0.9998 gate; otherwise KeyFrame::UnprojectStereo of the keyframe with the smaller stereo cosine, from the RAW keypoint mvKeys;
+ * the three-term reprojection gate 7.8 sigma2 with u_r = u - bf / z, bf being the CURRENT keyframe's mbf for both keyframes (:458).
+ * Codes 0..8 keep their meaning; 9 = the keypoint chosen for UnprojectStereo has depth <= 0 (the reference would read an empty
+ * matrix; Frame::ComputeStereoMatches never produces it), x3d zero.  source[i]: 0 no point (codes 1, 2, 9), 1 triangulated,
+ * 2 UnprojectStereo of keyframe 1, 3 of keyframe 2.  The record's tag is also the name of the single-problem entry point, so the
+ * type is written with its struct keyword or as slamit_triangulate_stereo_rec. */
+struct slamit_triangulate_stereo {
+    const float* ur1;              /* n: mvuRight[idx1] of the current keyframe */
+    const float* ur2;              /* n: mvuRight[idx2] of the neighbour */
+    const float* depth1;           /* n: mvDepth[idx1] */
+    const float* depth2;           /* n */
+    const float* raw1_xy;          /* n x 2: mvKeys[idx1].pt, the distorted keypoint */
+    const float* raw2_xy;          /* n x 2 */
+    float mb1, mb2;                /* mb of the current keyframe and of the neighbour */
+    float bf;                      /* mbf of the current keyframe */
+};
+typedef struct slamit_triangulate_stereo slamit_triangulate_stereo_rec;
+
+/* stereo (may be NULL) has nproblems entries; a NULL entry makes that problem monocular: it computes exactly what
+ * slamit_triangulate_batch computes.  source (may be NULL) has nproblems entries, each NULL or n bytes out.  A null per-pair
+ * array in a present record with n > 0 fails with SLAMIT_ERR_ARG before anything is launched. */
+int slamit_triangulate_stereo_batch(int device, int nproblems, const slamit_triangulate_problem* probs,
+                                    const struct slamit_triangulate_stereo* const* stereo, slamit_triangulate_result* results,
+                                    uint8_t* const* source);
+int slamit_triangulate_stereo(int device, const slamit_triangulate_problem* prob, const struct slamit_triangulate_stereo* stereo,
+                              slamit_triangulate_result* res, uint8_t* source);
 
 /* ---- SearchLocalPoints: the frustum test that feeds the guided search (tracking, between UpdateLocalMap and SearchByProjection) ----
  * Frame::isInFrustum with MapPoint::PredictScale (src/Frame.cc:389-445, src/MapPoint.cc:391-400) for every local map point of

@@ -139,6 +139,15 @@ class TriangulateResult(C.Structure):
     _fields_ = [("status", C.c_void_p), ("x3d", C.c_void_p), ("n_accepted", C.c_int32)]
 
 
+class TriangulateStereo(C.Structure):   # struct slamit_triangulate_stereo
+    _fields_ = [("ur1", C.c_void_p), ("ur2", C.c_void_p), ("depth1", C.c_void_p), ("depth2", C.c_void_p), ("raw1_xy", C.c_void_p),
+                ("raw2_xy", C.c_void_p), ("mb1", C.c_float), ("mb2", C.c_float), ("bf", C.c_float)]
+
+
+class BowStereo(C.Structure):
+    _fields_ = [("ur1", C.c_void_p), ("ur2", C.c_void_p), ("only_stereo", C.c_int32)]
+
+
 TRIANGULATE_MAX_N, MAX_LEVELS = 8192, 16   # SLAMIT_TRIANGULATE_MAX_N, SLAMIT_MAX_LEVELS
 
 
@@ -282,7 +291,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -336,6 +345,8 @@ def lib():
         L.slamit_sim3_ransac.argtypes = [i32, C.POINTER(Sim3RansacProblem), C.POINTER(Sim3RansacResult)]
         L.slamit_triangulate_batch.argtypes = [i32, i32, C.POINTER(TriangulateProblem), C.POINTER(TriangulateResult)]
         L.slamit_triangulate.argtypes = [i32, C.POINTER(TriangulateProblem), C.POINTER(TriangulateResult)]
+        L.slamit_triangulate_stereo_batch.argtypes = [i32, i32, C.POINTER(TriangulateProblem), C.POINTER(C.POINTER(TriangulateStereo)), C.POINTER(TriangulateResult), C.POINTER(vp)]
+        L.slamit_triangulate_stereo.argtypes = [i32, C.POINTER(TriangulateProblem), C.POINTER(TriangulateStereo), C.POINTER(TriangulateResult), vp]
         L.slamit_frustum_batch.argtypes = [i32, i32, C.POINTER(FrustumProblem), C.POINTER(FrustumResult)]
         L.slamit_frustum.argtypes = [i32, C.POINTER(FrustumProblem), C.POINTER(FrustumResult)]
         L.slamit_frustum_batch_dev.argtypes = [i32, C.POINTER(FrustumBatchRec), vp]
@@ -351,6 +362,7 @@ def lib():
         L.slamit_stereo_match_batch_dev.argtypes = [i32, C.POINTER(StereoBatch), vp]
         L.slamit_stereo_match.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, i32, f32, f32] + [vp] * 7
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
+        L.slamit_bow_search_stereo.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), C.POINTER(BowStereo), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
         L.slamit_voc_load_text.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
         L.slamit_voc_destroy.argtypes = [vp]
@@ -760,12 +772,13 @@ class ORBmatcher:
         return m12, nm, out4[:, 1].copy()   # the level slot carries the keypoint accepted at the query's own turn
 
     @staticmethod
-    def bow_search(side1, side2, groups, mode=0, th=50, th_inclusive=True, nnratio=0.6, epi=None, device=0):
+    def bow_search(side1, side2, groups, mode=0, th=50, th_inclusive=True, nnratio=0.6, epi=None, device=0, stereo=None):
         """The matching loops of SearchByBoW (mode 0; ORBmatcher.cc:161-290, 526-657) and SearchForTriangulation (mode 1;
         :659-826) over vocabulary-node groups.  side1 / side2: dicts with desc (n, 32), optional valid (n) and, for mode 1,
         kp_xy (n, 2) (+ kp_octave on side 2); groups: dict q_ptr, q_idx, c_ptr, c_idx (CSR per common node); epi (mode 1):
         dict F12 (9, row-major), ex, ey, scale_factor (16), level_sigma2 (16).  Returns (match12, dist12, nmatches)
-        before the rotation-histogram filter."""
+        before the rotation-histogram filter.  stereo (mode 1 only): dict ur1 (n1), ur2 (n2) = mvuRight of the two keyframes and
+        only_stereo = bOnlyStereo; None is the monocular search."""
         d1 = np.ascontiguousarray(side1["desc"], np.uint8).reshape(-1, 32)
         d2 = np.ascontiguousarray(side2["desc"], np.uint8).reshape(-1, 32)
         n1, n2 = len(d1), len(d2)
@@ -788,9 +801,18 @@ class ORBmatcher:
             rule.level_sigma2 = (C.c_float * 16)(*[float(v) for v in list(epi["level_sigma2"])[:16] + [1.0] * (16 - len(epi["level_sigma2"]))])
         m12, dd = np.full(max(n1, 1), -1, np.int32), np.full(max(n1, 1), 256, np.int32)
         nm = C.c_int32(0)
-        _check(lib().slamit_bow_search(device, _np_ptr(d1), n1, _np_ptr(v1) if v1 is not None else None, _np_ptr(d2), n2,
-                                       _np_ptr(v2) if v2 is not None else None, C.byref(g), C.byref(rule), _np_ptr(m12),
-                                       _np_ptr(dd), C.byref(nm)), "slamit_bow_search")
+        if stereo is None:
+            _check(lib().slamit_bow_search(device, _np_ptr(d1), n1, _np_ptr(v1) if v1 is not None else None, _np_ptr(d2), n2,
+                                           _np_ptr(v2) if v2 is not None else None, C.byref(g), C.byref(rule), _np_ptr(m12),
+                                           _np_ptr(dd), C.byref(nm)), "slamit_bow_search")
+        else:
+            u1, u2 = np.ascontiguousarray(stereo["ur1"], np.float32).reshape(-1), np.ascontiguousarray(stereo["ur2"], np.float32).reshape(-1)
+            if len(u1) != n1 or len(u2) != n2:
+                raise SlamitError("bow_search: stereo ur1 / ur2 do not have n1 / n2 entries")
+            st = BowStereo(u1.ctypes.data if n1 else None, u2.ctypes.data if n2 else None, int(bool(stereo.get("only_stereo", False))))
+            _check(lib().slamit_bow_search_stereo(device, _np_ptr(d1), n1, _np_ptr(v1) if v1 is not None else None, _np_ptr(d2), n2,
+                                                  _np_ptr(v2) if v2 is not None else None, C.byref(g), C.byref(rule), C.byref(st),
+                                                  _np_ptr(m12), _np_ptr(dd), C.byref(nm)), "slamit_bow_search_stereo")
         del keep
         return m12[:n1], dd[:n1], nm.value
 
@@ -1427,16 +1449,25 @@ class Sim3Solver:
         return float(self.t12[self.best, 12])
 
 
+_TRI_STEREO_ARRAYS = ("ur1", "ur2", "depth1", "depth2", "raw1_xy", "raw2_xy")
+_TRI_STEREO_SCALARS = ("mb1", "mb2", "bf")
+
+
 def triangulate_batch(problems, device=0):
     """LocalMapping::CreateNewMapPoints' per-pair body (LocalMapping.cc:348-483, monocular) for a list of (current keyframe, neighbour)
     problems in ONE device call.  Each problem is a dict in the layout of slamit_triangulate_problem (synth.synth_triangulation):
     Tcw1, Tcw2 (12) float32, intr1, intr2 (fx fy cx cy invfx invfy), kp1_xy, kp2_xy (n, 2), octave1, octave2 (n), n_levels,
     scale_factors1/2 and level_sigma2_1/2 (n_levels), ratio_factor.  -> a list of dicts: status (n) uint8 (0 accepted, else the first
-    gate that rejected the pair), x3d (n, 3) float32, n_accepted."""
+    gate that rejected the pair), x3d (n, 3) float32, n_accepted, source (n) uint8 (0 no point, 1 triangulated, 2 / 3 UnprojectStereo
+    of keyframe 1 / 2).  A problem that also holds the stereo keys ur1, ur2, depth1, depth2 (n), raw1_xy, raw2_xy (n, 2), mb1, mb2, bf
+    (synth.synth_triangulation_stereo) takes the stereo branches (:335-465, status 9 = UnprojectStereo of a depth <= 0); all of the
+    keys or none."""
     plist = list(problems)
     m = len(plist)
     P = (TriangulateProblem * m)()
     R = (TriangulateResult * m)()
+    T = (C.POINTER(TriangulateStereo) * m)()
+    SRC = (C.c_void_p * m)()
     keep, outs = [], []
     for i, pr in enumerate(plist):
         k = {"kp1_xy": np.ascontiguousarray(pr["kp1_xy"], np.float32).reshape(-1, 2), "kp2_xy": np.ascontiguousarray(pr["kp2_xy"], np.float32).reshape(-1, 2),
@@ -1457,11 +1488,26 @@ def triangulate_batch(problems, device=0):
         q.n, q.n_levels, q.ratio_factor = n, nl, float(pr["ratio_factor"])
         for key, a in k.items():
             setattr(q, key, a.ctypes.data)
-        o = {"status": np.zeros(n, np.uint8), "x3d": np.zeros((n, 3), np.float32)}
+        have = [key in pr for key in _TRI_STEREO_ARRAYS + _TRI_STEREO_SCALARS]
+        if any(have):
+            if not all(have):
+                raise SlamitError("triangulate: a stereo problem needs all of " + " ".join(_TRI_STEREO_ARRAYS + _TRI_STEREO_SCALARS))
+            t = TriangulateStereo()
+            for key in _TRI_STEREO_ARRAYS:
+                a = np.ascontiguousarray(pr[key], np.float32).reshape(-1)
+                if len(a) != (2 * n if key[:3] == "raw" else n):
+                    raise SlamitError("triangulate: %s has %d entries" % (key, len(a)))
+                k[key] = a
+                setattr(t, key, a.ctypes.data)
+            t.mb1, t.mb2, t.bf = float(pr["mb1"]), float(pr["mb2"]), float(pr["bf"])
+            k["stereo record"] = t
+            T[i] = C.pointer(t)
+        o = {"status": np.zeros(n, np.uint8), "x3d": np.zeros((n, 3), np.float32), "source": np.zeros(n, np.uint8)}
         R[i].status, R[i].x3d = o["status"].ctypes.data, o["x3d"].ctypes.data
+        SRC[i] = o["source"].ctypes.data
         keep.append(k)
         outs.append(o)
-    _check(lib().slamit_triangulate_batch(device, m, P, R), "slamit_triangulate_batch")
+    _check(lib().slamit_triangulate_stereo_batch(device, m, P, T, R, SRC), "slamit_triangulate_stereo_batch")
     del keep
     for i, o in enumerate(outs):
         o["n_accepted"] = int(R[i].n_accepted)

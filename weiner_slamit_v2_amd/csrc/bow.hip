@@ -1,4 +1,4 @@
-// bow.hip — vocabulary-node search (include/slamit.h, slamit_bow_search).
+// bow.hip — vocabulary-node search (include/slamit.h, slamit_bow_search, slamit_bow_search_stereo).
 //
 // Reference: ORB_SLAM2/src/ORBmatcher.cc:161-290 (SearchByBoW KeyFrame/Frame), :526-657 (SearchByBoW KeyFrame/KeyFrame),
 // :659-826 (SearchForTriangulation), :141-158 (CheckDistEpipolarLine).
@@ -9,6 +9,10 @@
 // '<', first one wins" is "the two smallest keys (distance << 16 | position)"; mode 1's "minimum distance, last one wins"
 // is the smallest key (distance << 16 | 0xFFFF - position).  Wave-wide minima are DPP reductions (wave_ops.h).
 // Float expressions are written exactly as the reference writes them; compiled with -ffp-contract=off.
+//
+// Stereo keyframes in mode 1 (:703-713, :734-753) are the STEREO instantiation of the search kernel: bStereo1 is
+// one value per query (wave-uniform), bStereo2 one more 4-byte load per candidate lane; the epipole test runs only when neither
+// is stereo, and only_stereo skips the queries and candidates that are not.  Without a stereo record the kernel is the one it was.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -29,6 +33,7 @@ struct BowDev {
     const float* kp1; const float* kp2; const int* oct2;
     float scale[16], sigma2[16];
     int* match12; int* dist12; int* nmatches;
+    const float* ur1; const float* ur2; int only_stereo;   // the STEREO instantiation only
 };
 
 __global__ __launch_bounds__(256) void bow_init_kernel(BowDev D) {
@@ -37,6 +42,7 @@ __global__ __launch_bounds__(256) void bow_init_kernel(BowDev D) {
     if (i < D.n1) { D.match12[i] = -1; D.dist12[i] = 256; }
 }
 
+template <bool STEREO>
 __global__ __launch_bounds__(64) void bow_search_kernel(BowDev D) {
     const int g = blockIdx.x, lane = threadIdx.x;
     const int q0 = D.q_ptr[g], q1 = D.q_ptr[g + 1], c0 = D.c_ptr[g], nc = D.c_ptr[g + 1] - c0;
@@ -54,6 +60,11 @@ __global__ __launch_bounds__(64) void bow_search_kernel(BowDev D) {
     for (int qi = q0; qi < q1; ++qi) {
         const int i1 = D.q_idx[qi];
         if (D.valid1 && !D.valid1[i1]) continue;   // wave-uniform
+        bool stereo1 = false;
+        if constexpr (STEREO) {
+            stereo1 = D.ur1[i1] >= 0;               // :703 (wave-uniform)
+            if (D.only_stereo && !stereo1) continue;   // :711-713
+        }
         const uint4* dq = reinterpret_cast<const uint4*>(D.desc1 + 32 * (size_t)i1);
         const uint4 a0 = dq[0], a1 = dq[1];
         float la = 0.f, lb = 0.f, lc = 0.f;       // epipolar line of the query in image 2 (mode 1)
@@ -81,7 +92,13 @@ __global__ __launch_bounds__(64) void bow_search_kernel(BowDev D) {
                 const float x2 = D.kp2[2 * i2], y2 = D.kp2[2 * i2 + 1];
                 const int oc = D.oct2[i2] & 15;
                 const float distex = D.ex - x2, distey = D.ey - y2;
-                if (distex * distex + distey * distey < 100 * D.scale[oc]) continue;   // :741
+                if constexpr (STEREO) {
+                    const bool stereo2 = D.ur2[i2] >= 0;                               // :732
+                    if (D.only_stereo && !stereo2) continue;                           // :734-736
+                    if (!stereo1 && !stereo2 && distex * distex + distey * distey < 100 * D.scale[oc]) continue;   // :747-753
+                } else {
+                    if (distex * distex + distey * distey < 100 * D.scale[oc]) continue;   // :741
+                }
                 const float num = la * x2 + lb * y2 + lc;
                 const float den = la * la + lb * lb;
                 if (den == 0) continue;
@@ -110,11 +127,13 @@ __global__ __launch_bounds__(64) void bow_search_kernel(BowDev D) {
     if (lane == 0 && accepted) atomicAdd(D.nmatches, accepted);
 }
 
-extern "C" int slamit_bow_search(int device, const uint8_t* desc1, int32_t n1, const uint8_t* valid1, const uint8_t* desc2,
-                                 int32_t n2, const uint8_t* valid2, const slamit_bow_groups* G, const slamit_bow_rule* rule,
-                                 int32_t* match12, int32_t* dist12, int32_t* nmatches) {
+extern "C" int slamit_bow_search_stereo(int device, const uint8_t* desc1, int32_t n1, const uint8_t* valid1, const uint8_t* desc2,
+                                        int32_t n2, const uint8_t* valid2, const slamit_bow_groups* G, const slamit_bow_rule* rule,
+                                        const slamit_bow_stereo* st, int32_t* match12, int32_t* dist12, int32_t* nmatches) {
     if (!G || !rule || !nmatches || n1 < 0 || n2 < 0 || G->n_groups < 0 || (rule->mode != 0 && rule->mode != 1))
         return slamit_fail(SLAMIT_ERR_ARG, "slamit_bow_search: bad argument");
+    if (st && rule->mode != 1) return slamit_fail(SLAMIT_ERR_ARG, "slamit_bow_search_stereo: a stereo record needs mode 1 (SearchByBoW has no stereo branch)");
+    if (st && ((n1 > 0 && !st->ur1) || (n1 > 0 && n2 > 0 && !st->ur2))) return slamit_fail(SLAMIT_ERR_ARG, "slamit_bow_search_stereo: null ur1 / ur2");
     *nmatches = 0;
     if (n1 == 0) return SLAMIT_OK;
     if (!match12 || !desc1 || (n2 && !desc2)) return slamit_fail(SLAMIT_ERR_ARG, "slamit_bow_search: null array");
@@ -154,6 +173,7 @@ extern "C" int slamit_bow_search(int device, const uint8_t* desc1, int32_t n1, c
     const StageSpan<int> qp = L.take<int>((size_t)ng + 1), cp = L.take<int>((size_t)ng + 1), qi = L.take<int>(nq), ci = L.take<int>(ncand);
     const StageSpan<float> k1 = L.take<float>(m1 ? 2 * N1 : 0), k2 = L.take<float>(m1 ? 2 * N2 : 0);
     const StageSpan<int> oc = L.take<int>(m1 ? N2 : 0);
+    const StageSpan<float> u1 = L.take<float>(st ? N1 : 0), u2 = L.take<float>(st ? N2 : 0);
     L.end_inputs();
     const StageSpan<int> om = L.take<int>(N1), od = L.take<int>(N1), nm = L.take<int>(1);
     L.end_outputs();
@@ -165,6 +185,7 @@ extern "C" int slamit_bow_search(int device, const uint8_t* desc1, int32_t n1, c
     memcpy(qp.at(S.host), G->q_ptr, qp.bytes()); memcpy(cp.at(S.host), G->c_ptr, cp.bytes());
     memcpy(qi.at(S.host), G->q_idx, qi.bytes()); memcpy(ci.at(S.host), G->c_idx, ci.bytes());
     if (m1) { memcpy(k1.at(S.host), rule->kp1_xy, k1.bytes()); memcpy(k2.at(S.host), rule->kp2_xy, k2.bytes()); memcpy(oc.at(S.host), rule->kp2_octave, oc.bytes()); }
+    if (st) { memcpy(u1.at(S.host), st->ur1, u1.bytes()); memcpy(u2.at(S.host), st->ur2, u2.bytes()); }
     HIP_TRY_AT("slamit_bow_search", slamit_stage_upload(S, L));
     BowDev D;
     D.n_groups = ng; D.n1 = n1;
@@ -176,10 +197,18 @@ extern "C" int slamit_bow_search(int device, const uint8_t* desc1, int32_t n1, c
     memcpy(D.scale, rule->scale_factor, sizeof(D.scale)); memcpy(D.sigma2, rule->level_sigma2, sizeof(D.sigma2));
     D.match12 = om.at(S.dev); D.dist12 = od.at(S.dev); D.nmatches = nm.at(S.dev);
     hipLaunchKernelGGL(bow_init_kernel, dim3((n1 + 255) / 256), dim3(256), 0, S.st, D);
-    hipLaunchKernelGGL(bow_search_kernel, dim3(ng), dim3(64), 0, S.st, D);
+    D.ur1 = u1.at(S.dev); D.ur2 = u2.at(S.dev); D.only_stereo = st ? st->only_stereo : 0;
+    if (st) hipLaunchKernelGGL(bow_search_kernel<true>, dim3(ng), dim3(64), 0, S.st, D);
+    else hipLaunchKernelGGL(bow_search_kernel<false>, dim3(ng), dim3(64), 0, S.st, D);
     HIP_TRY_AT("slamit_bow_search", slamit_stage_download_and_wait(S, L));
     memcpy(match12, om.at(S.host), om.bytes());
     if (dist12) memcpy(dist12, od.at(S.host), od.bytes());
     *nmatches = *nm.at(S.host);
     return SLAMIT_OK;
+}
+
+extern "C" int slamit_bow_search(int device, const uint8_t* desc1, int32_t n1, const uint8_t* valid1, const uint8_t* desc2, int32_t n2,
+                                 const uint8_t* valid2, const slamit_bow_groups* G, const slamit_bow_rule* rule, int32_t* match12,
+                                 int32_t* dist12, int32_t* nmatches) {
+    return slamit_bow_search_stereo(device, desc1, n1, valid1, desc2, n2, valid2, G, rule, nullptr, match12, dist12, nmatches);
 }

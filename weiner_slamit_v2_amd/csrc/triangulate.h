@@ -2,7 +2,8 @@
 // parallax test of the two rays, the 4x4 linear triangulation, both depth tests, both reprojection gates and the scale-consistency
 // test.  Plain C++ over IEEE +,-,*,/ and sqrt, float and double exactly where the reference has them; it must be compiled with
 // -ffp-contract=off.  triangulate.hip runs it one lane per pair; the CPU test of the restatement and tools/bench_triangulate.py
-// build the same text with g++ for the host.  Stereo (bStereo1/2, UnprojectStereo, the 7.8 gates) is out of scope.
+// build the same text with g++ for the host.  tri_pair is the monocular pair; tri_pair_stereo adds bStereo1/2, the stereo cosines,
+// KeyFrame::UnprojectStereo and the 7.8 gates and returns what tri_pair returns when neither keypoint is stereo.
 //
 // Where the reference goes through OpenCV the evaluation order below is the statement of it (PARITY UNPINNED):
 //   xn                ((pt.x - cx) * invfx, (pt.y - cy) * invfy, 1) in float                      :348-349, cv::Mat_<float> <<
@@ -21,6 +22,15 @@
 //   Ow                -((r0 t0 + r1 t1) + r2 t2) in float over the transposed rotation               KeyFrame.cc:80-81
 //   dist              (float)sqrt(double sum of squares of the float differences)                    :468-472, cv::norm
 //   ratios            float                                                                          :477-482
+// tri_pair_stereo:
+//   bStereo           ur >= 0 (0.0f is stereo, NaN is not)                                           :337, :345
+//   cosParallaxStereo cos 2t = (d d - h h) / (d d + h h) with h = mb / 2 in float, d = mvDepth,       :360, :362, cos(2*atan2(mb/2, d))
+//                     evaluated in double and rounded once to float (PARITY UNPINNED)
+//   min               b < a ? b : a                                                                  :364, std::min
+//   UnprojectStereo   x = ((u - cx) * z) * invfx, y = ((v - cy) * z) * invfy on the RAW keypoint,    KeyFrame.cc:623-639
+//                     ((r0 x + r1 y) + r2 z) + Ow in float over the transposed rotation               cv::gemm on CV_32F
+//   u_r               u - bf * invz, two roundings                                                   :430, :458
+//   err > 7.8 s2      (double)(float (ex ex + ey ey) + er er) > 7.8 * (double)s2                     :435, :463
 #ifndef SLAMIT_TRIANGULATE_H
 #define SLAMIT_TRIANGULATE_H
 #include <math.h>
@@ -40,8 +50,10 @@
 #endif
 
 enum {
-    TRI_OK = 0, TRI_PARALLAX = 1, TRI_W_ZERO = 2, TRI_Z1 = 3, TRI_Z2 = 4, TRI_REPROJ1 = 5, TRI_REPROJ2 = 6, TRI_DIST_ZERO = 7, TRI_SCALE = 8
+    TRI_OK = 0, TRI_PARALLAX = 1, TRI_W_ZERO = 2, TRI_Z1 = 3, TRI_Z2 = 4, TRI_REPROJ1 = 5, TRI_REPROJ2 = 6, TRI_DIST_ZERO = 7, TRI_SCALE = 8,
+    TRI_UNPROJECT_DEPTH = 9   // tri_pair_stereo only: the keypoint chosen for UnprojectStereo has depth <= 0 (the reference reads an empty Mat)
 };
+enum { TRI_SRC_NONE = 0, TRI_SRC_TRIANGULATED = 1, TRI_SRC_UNPROJECT1 = 2, TRI_SRC_UNPROJECT2 = 3 };
 
 struct TriView {
     float T[12];                          // Tcw, row-major 3x4
@@ -186,6 +198,77 @@ TRI_HD int tri_pair(const TriView& c1, const TriView& c2, const float p1[2], con
     tri_null_vector(A, v);
     if (!tri_dehomogenise(v, X)) return TRI_W_ZERO;
     return tri_gates(c1, c2, p1, p2, sigma2_1, sigma2_2, sf1, sf2, ratioFactor, X);
+}
+
+// ---- stereo keypoints (LocalMapping.cc:335-465, KeyFrame.cc:623-639) ----
+
+// the right-image side of one pair: mvuRight, mvDepth and the raw (distorted) keypoint mvKeys[idx].pt of each keyframe
+struct TriStereoPair {
+    float ur1, ur2, depth1, depth2;
+    float raw1[2], raw2[2];
+};
+
+// :360 / :362, cos(2 * atan2(mb / 2, depth)) as the double-angle identity, one rounding
+TRI_HD float tri_cos_stereo(float mb, float depth) {
+    const float h = mb / 2;
+    const double d2 = (double)depth * (double)depth, h2 = (double)h * (double)h;
+    return (float)((d2 - h2) / (d2 + h2));
+}
+
+// KeyFrame::UnprojectStereo on a depth that is > 0
+TRI_HD void tri_unproject_stereo(const TriView& c, const float raw[2], float z, float X[3]) {
+    const float x = (raw[0] - c.cx) * z * c.invfx, y = (raw[1] - c.cy) * z * c.invfy;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) X[i] = ((c.T[i] * x + c.T[4 + i] * y) + c.T[8 + i] * z) + c.O[i];
+}
+
+// :427-437 / :455-465 for a stereo keypoint: true = rejected
+TRI_HD bool tri_reproj_rejects_stereo(const TriView& c, const float X[3], float z, const float p[2], float ur, float bf, float sigma2) {
+    const float x = tri_row(c, 0, X), y = tri_row(c, 1, X);
+    const float invz = (float)(1.0 / (double)z);
+    const float u = c.fx * x * invz + c.cx, v = c.fy * y * invz + c.cy;
+    const float u_r = u - bf * invz;
+    const float ex = u - p[0], ey = v - p[1], er = u_r - ur;
+    return (double)(ex * ex + ey * ey + er * er) > 7.8 * (double)sigma2;
+}
+
+// One pair with its right-image side.  mb1 / mb2 are the two keyframes' baselines in metres, bf the CURRENT keyframe's mbf: the
+// reference uses it for the neighbour's gate too (:458).  source says where X came from (TRI_SRC_*; 0 with codes 1, 2 and 9).
+TRI_HD int tri_pair_stereo(const TriView& c1, const TriView& c2, const float p1[2], const float p2[2], const TriStereoPair& s, float mb1, float mb2,
+                           float bf, float sigma2_1, float sigma2_2, float sf1, float sf2, float ratioFactor, float X[3], int& source) {
+    X[0] = 0.f; X[1] = 0.f; X[2] = 0.f;
+    source = TRI_SRC_NONE;
+    const bool bStereo1 = s.ur1 >= 0, bStereo2 = s.ur2 >= 0;
+    float xn1[2], xn2[2];
+    const float cosParallaxRays = tri_cos_parallax(c1, c2, p1, p2, xn1, xn2);
+    float cosParallaxStereo1 = cosParallaxRays + 1, cosParallaxStereo2 = cosParallaxRays + 1;
+    if (bStereo1) cosParallaxStereo1 = tri_cos_stereo(mb1, s.depth1);
+    else if (bStereo2) cosParallaxStereo2 = tri_cos_stereo(mb2, s.depth2);
+    const float cosParallaxStereo = cosParallaxStereo2 < cosParallaxStereo1 ? cosParallaxStereo2 : cosParallaxStereo1;
+    if (cosParallaxRays < cosParallaxStereo && cosParallaxRays > 0 && (bStereo1 || bStereo2 || cosParallaxRays < 0.9998)) {
+        float A[4][4], v[4];
+        tri_build_A(c1, c2, xn1, xn2, A);
+        tri_null_vector(A, v);
+        if (!tri_dehomogenise(v, X)) return TRI_W_ZERO;
+        source = TRI_SRC_TRIANGULATED;
+    } else if (bStereo1 && cosParallaxStereo1 < cosParallaxStereo2) {
+        if (s.depth1 <= 0) return TRI_UNPROJECT_DEPTH;
+        tri_unproject_stereo(c1, s.raw1, s.depth1, X);
+        source = TRI_SRC_UNPROJECT1;
+    } else if (bStereo2 && cosParallaxStereo2 < cosParallaxStereo1) {
+        if (s.depth2 <= 0) return TRI_UNPROJECT_DEPTH;
+        tri_unproject_stereo(c2, s.raw2, s.depth2, X);
+        source = TRI_SRC_UNPROJECT2;
+    } else {
+        return TRI_PARALLAX;
+    }
+    const float z1 = tri_row(c1, 2, X);
+    if (z1 <= 0) return TRI_Z1;
+    const float z2 = tri_row(c2, 2, X);
+    if (z2 <= 0) return TRI_Z2;
+    if (bStereo1 ? tri_reproj_rejects_stereo(c1, X, z1, p1, s.ur1, bf, sigma2_1) : tri_reproj_rejects(c1, X, z1, p1, sigma2_1)) return TRI_REPROJ1;
+    if (bStereo2 ? tri_reproj_rejects_stereo(c2, X, z2, p2, s.ur2, bf, sigma2_2) : tri_reproj_rejects(c2, X, z2, p2, sigma2_2)) return TRI_REPROJ2;
+    return tri_scale_gate(X, c1.O, c2.O, sf1, sf2, ratioFactor);
 }
 
 #endif

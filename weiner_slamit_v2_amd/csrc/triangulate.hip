@@ -6,6 +6,10 @@
 // the problem are the same for every lane (scalar loads of the problem record); the level tables sit in the record and are
 // indexed by the lane's octave.  No LDS, no atomics: the accepted pairs of a wavefront are a ballot's popcount, written to one
 // slot per wavefront and summed on the host.  A batch of keyframe pairs is one launch (grid.y).
+//
+// Stereo keypoints (slamit_triangulate_stereo*) are the STEREO instantiation of the same kernel: six more coalesced
+// per-pair arrays and three scalars of the record feed tri_pair_stereo, and a wavefront may hold triangulated, unprojected and
+// skipped lanes side by side.  A batch without a stereo record launches the monocular instantiation, which is the kernel it was.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -27,10 +31,16 @@ struct TriProb {
     const SLAMIT_GLOBAL float* kp1; const SLAMIT_GLOBAL float* kp2;
     const SLAMIT_GLOBAL int32_t* o1; const SLAMIT_GLOBAL int32_t* o2;
     SLAMIT_GLOBAL uint8_t* status; SLAMIT_GLOBAL float* x3d; SLAMIT_GLOBAL int32_t* wave_counts;   // n, 3 n, (n + 63) / 64
+    // the STEREO instantiation only; ur1 == null: this problem of the batch is monocular
+    const SLAMIT_GLOBAL float* ur1; const SLAMIT_GLOBAL float* ur2; const SLAMIT_GLOBAL float* depth1; const SLAMIT_GLOBAL float* depth2;
+    const SLAMIT_GLOBAL float* raw1; const SLAMIT_GLOBAL float* raw2;
+    SLAMIT_GLOBAL uint8_t* source;   // n
+    float mb1, mb2, bf;
 };
 
 // grid (ceil(max n / 256), problems), 256 threads: lane t of block b takes pair 256 b + t of problem blockIdx.y.  The host has
 // checked every octave against [0, n_levels); the mask keeps the table index inside the record whatever it holds.
+template <bool STEREO>
 __global__ __launch_bounds__(256) void triangulate_kernel(const TriProb* __restrict__ probs) {
     const TriProb& P = probs[blockIdx.y];
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
@@ -38,7 +48,20 @@ __global__ __launch_bounds__(256) void triangulate_kernel(const TriProb* __restr
     const float p1[2] = {P.kp1[2 * i], P.kp1[2 * i + 1]}, p2[2] = {P.kp2[2 * i], P.kp2[2 * i + 1]};
     const int o1 = P.o1[i] & (SLAMIT_MAX_LEVELS - 1), o2 = P.o2[i] & (SLAMIT_MAX_LEVELS - 1);
     float X[3];
-    const int st = tri_pair(P.c1, P.c2, p1, p2, P.s1[o1], P.s2[o2], P.sf1[o1], P.sf2[o2], P.ratio_factor, X);
+    int st;
+    if constexpr (STEREO) {
+        int src;
+        if (P.ur1) {   // uniform over the block
+            const TriStereoPair s = {P.ur1[i], P.ur2[i], P.depth1[i], P.depth2[i], {P.raw1[2 * i], P.raw1[2 * i + 1]}, {P.raw2[2 * i], P.raw2[2 * i + 1]}};
+            st = tri_pair_stereo(P.c1, P.c2, p1, p2, s, P.mb1, P.mb2, P.bf, P.s1[o1], P.s2[o2], P.sf1[o1], P.sf2[o2], P.ratio_factor, X, src);
+        } else {
+            st = tri_pair(P.c1, P.c2, p1, p2, P.s1[o1], P.s2[o2], P.sf1[o1], P.sf2[o2], P.ratio_factor, X);
+            src = st == TRI_PARALLAX || st == TRI_W_ZERO ? TRI_SRC_NONE : TRI_SRC_TRIANGULATED;
+        }
+        P.source[i] = (uint8_t)src;
+    } else {
+        st = tri_pair(P.c1, P.c2, p1, p2, P.s1[o1], P.s2[o2], P.sf1[o1], P.sf2[o2], P.ratio_factor, X);
+    }
     P.status[i] = (uint8_t)st;
     P.x3d[3 * (size_t)i] = X[0]; P.x3d[3 * (size_t)i + 1] = X[1]; P.x3d[3 * (size_t)i + 2] = X[2];
     const unsigned long long m = __ballot(st == TRI_OK);   // the lanes past n have left: they count as 0
@@ -47,11 +70,13 @@ __global__ __launch_bounds__(256) void triangulate_kernel(const TriProb* __restr
 
 extern "C" {
 
-int slamit_triangulate_batch(int device, int nprob, const slamit_triangulate_problem* probs, slamit_triangulate_result* results) {
+int slamit_triangulate_stereo_batch(int device, int nprob, const slamit_triangulate_problem* probs, const struct slamit_triangulate_stereo* const* stereo,
+                                    slamit_triangulate_result* results, uint8_t* const* source) {
     const char* const where = "slamit_triangulate_batch";
     if (nprob < 0 || (nprob && (!probs || !results))) return slamit_fail(SLAMIT_ERR_ARG, "slamit_triangulate_batch: bad argument");
     if (nprob == 0) return SLAMIT_OK;
     int max_n = 0;
+    bool any_stereo = false;   // a problem with pairs and a stereo record: the STEREO instantiation runs the batch
     for (int f = 0; f < nprob; ++f) {
         const slamit_triangulate_problem& P = probs[f];
         if (P.n < 0) return slamit_fail(SLAMIT_ERR_ARG, "slamit_triangulate_batch: negative count");
@@ -64,19 +89,29 @@ int slamit_triangulate_batch(int device, int nprob, const slamit_triangulate_pro
         for (int k = 0; k < P.n; ++k)
             if (P.octave1[k] < 0 || P.octave1[k] >= P.n_levels || P.octave2[k] < 0 || P.octave2[k] >= P.n_levels)
                 return slamit_fail(SLAMIT_ERR_ARG, "slamit_triangulate_batch: octave outside [0, n_levels)");
+        if (stereo && stereo[f]) {
+            const struct slamit_triangulate_stereo& T = *stereo[f];
+            if (!T.ur1 || !T.ur2 || !T.depth1 || !T.depth2 || !T.raw1_xy || !T.raw2_xy)
+                return slamit_fail(SLAMIT_ERR_ARG, "slamit_triangulate_stereo_batch: null array in a stereo record");
+            any_stereo = true;
+        }
         max_n = std::max(max_n, (int)P.n);
     }
     for (int f = 0; f < nprob; ++f) results[f].n_accepted = 0;
     if (max_n == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
-    // [per problem: kp1 kp2 octave1 octave2 | records] go up; [per problem: status x3d wave counts] come down
-    struct Spans { StageSpan<float> kp1, kp2, x3d; StageSpan<int32_t> o1, o2, counts; StageSpan<uint8_t> status; };
+    // [per problem: kp1 kp2 octave1 octave2, with a stereo record its six arrays | records] go up; [per problem: status x3d wave counts,
+    // in a stereo launch source] come down
+    struct Spans { StageSpan<float> kp1, kp2, x3d, ur1, ur2, depth1, depth2, raw1, raw2; StageSpan<int32_t> o1, o2, counts; StageSpan<uint8_t> status, source; };
     StageLayout L;
     std::vector<Spans> sp(nprob);
     for (int f = 0; f < nprob; ++f) {
         const size_t n = (size_t)probs[f].n;
         Spans& s = sp[f];
         s.kp1 = L.take<float>(2 * n, 16); s.kp2 = L.take<float>(2 * n, 16); s.o1 = L.take<int32_t>(n, 16); s.o2 = L.take<int32_t>(n, 16);
+        const size_t ns = stereo && stereo[f] ? n : 0;
+        s.ur1 = L.take<float>(ns, 16); s.ur2 = L.take<float>(ns, 16); s.depth1 = L.take<float>(ns, 16); s.depth2 = L.take<float>(ns, 16);
+        s.raw1 = L.take<float>(2 * ns, 16); s.raw2 = L.take<float>(2 * ns, 16);
     }
     const StageSpan<TriProb> recs = L.take<TriProb>(nprob, 16);
     L.end_inputs();
@@ -84,6 +119,7 @@ int slamit_triangulate_batch(int device, int nprob, const slamit_triangulate_pro
         const size_t n = (size_t)probs[f].n;
         Spans& s = sp[f];
         s.status = L.take<uint8_t>(n, 16); s.x3d = L.take<float>(3 * n, 16); s.counts = L.take<int32_t>((n + 63) / 64, 16);
+        s.source = L.take<uint8_t>(any_stereo ? n : 0, 16);
     }
     L.end_outputs();
     static thread_local SlamitScratch S;
@@ -104,20 +140,36 @@ int slamit_triangulate_batch(int device, int nprob, const slamit_triangulate_pro
             Q.ratio_factor = P.ratio_factor;
             memcpy(Q.sf1, P.scale_factors1, sizeof(float) * P.n_levels); memcpy(Q.s1, P.level_sigma2_1, sizeof(float) * P.n_levels);
             memcpy(Q.sf2, P.scale_factors2, sizeof(float) * P.n_levels); memcpy(Q.s2, P.level_sigma2_2, sizeof(float) * P.n_levels);
+            if (stereo && stereo[f]) {
+                const struct slamit_triangulate_stereo& T = *stereo[f];
+                memcpy(s.ur1.at(S.host), T.ur1, s.ur1.bytes()); memcpy(s.ur2.at(S.host), T.ur2, s.ur2.bytes());
+                memcpy(s.depth1.at(S.host), T.depth1, s.depth1.bytes()); memcpy(s.depth2.at(S.host), T.depth2, s.depth2.bytes());
+                memcpy(s.raw1.at(S.host), T.raw1_xy, s.raw1.bytes()); memcpy(s.raw2.at(S.host), T.raw2_xy, s.raw2.bytes());
+                Q.mb1 = T.mb1; Q.mb2 = T.mb2; Q.bf = T.bf;
+                Q.ur1 = (const SLAMIT_GLOBAL float*)s.ur1.at(S.dev); Q.ur2 = (const SLAMIT_GLOBAL float*)s.ur2.at(S.dev);
+                Q.depth1 = (const SLAMIT_GLOBAL float*)s.depth1.at(S.dev); Q.depth2 = (const SLAMIT_GLOBAL float*)s.depth2.at(S.dev);
+                Q.raw1 = (const SLAMIT_GLOBAL float*)s.raw1.at(S.dev); Q.raw2 = (const SLAMIT_GLOBAL float*)s.raw2.at(S.dev);
+            }
         }
+        Q.source = (SLAMIT_GLOBAL uint8_t*)s.source.at(S.dev);
         Q.kp1 = (const SLAMIT_GLOBAL float*)s.kp1.at(S.dev); Q.kp2 = (const SLAMIT_GLOBAL float*)s.kp2.at(S.dev);
         Q.o1 = (const SLAMIT_GLOBAL int32_t*)s.o1.at(S.dev); Q.o2 = (const SLAMIT_GLOBAL int32_t*)s.o2.at(S.dev);
         Q.status = (SLAMIT_GLOBAL uint8_t*)s.status.at(S.dev); Q.x3d = (SLAMIT_GLOBAL float*)s.x3d.at(S.dev);
         Q.wave_counts = (SLAMIT_GLOBAL int32_t*)s.counts.at(S.dev);
     }
     HIP_TRY_AT(where, slamit_stage_upload(S, L));
-    hipLaunchKernelGGL(triangulate_kernel, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, recs.at(S.dev));
+    if (any_stereo) hipLaunchKernelGGL(triangulate_kernel<true>, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, recs.at(S.dev));
+    else hipLaunchKernelGGL(triangulate_kernel<false>, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, recs.at(S.dev));
     HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
     for (int f = 0; f < nprob; ++f) {
         const Spans& s = sp[f];
         if (!probs[f].n) continue;
         memcpy(results[f].status, s.status.at(S.host), s.status.bytes());
         memcpy(results[f].x3d, s.x3d.at(S.host), s.x3d.bytes());
+        if (source && source[f]) {
+            if (any_stereo) memcpy(source[f], s.source.at(S.host), s.source.bytes());
+            else for (int k = 0; k < probs[f].n; ++k) source[f][k] = results[f].status[k] == TRI_PARALLAX || results[f].status[k] == TRI_W_ZERO ? TRI_SRC_NONE : TRI_SRC_TRIANGULATED;
+        }
         int acc = 0;
         const int32_t* c = s.counts.at(S.host);
         for (size_t w = 0; w < s.counts.count; ++w) acc += c[w];
@@ -126,8 +178,17 @@ int slamit_triangulate_batch(int device, int nprob, const slamit_triangulate_pro
     return SLAMIT_OK;
 }
 
+int slamit_triangulate_stereo(int device, const slamit_triangulate_problem* prob, const struct slamit_triangulate_stereo* stereo,
+                              slamit_triangulate_result* res, uint8_t* source) {
+    return slamit_triangulate_stereo_batch(device, 1, prob, &stereo, res, &source);
+}
+
+int slamit_triangulate_batch(int device, int nprob, const slamit_triangulate_problem* probs, slamit_triangulate_result* results) {
+    return slamit_triangulate_stereo_batch(device, nprob, probs, nullptr, results, nullptr);
+}
+
 int slamit_triangulate(int device, const slamit_triangulate_problem* prob, slamit_triangulate_result* res) {
-    return slamit_triangulate_batch(device, 1, prob, res);
+    return slamit_triangulate_stereo_batch(device, 1, prob, nullptr, res, nullptr);
 }
 
 }  // extern "C"

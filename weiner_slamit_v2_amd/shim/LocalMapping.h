@@ -1,7 +1,8 @@
 // LocalMapping.h — LocalMapping::CreateNewMapPoints (ORB_SLAM2/src/LocalMapping.cc:224-505) over the caller's KeyFrame type,
-// monocular.  The loop over the neighbours, the baseline gate, ComputeF12 and the bookkeeping stay host code; the matcher is
+// monocular and stereo.  The loop over the neighbours, the baseline gate, ComputeF12 and the bookkeeping stay host code; the matcher is
 // ORBmatcher::SearchForTriangulation (one slamit_bow_search call) and the per-pair body -- parallax, linear triangulation, depth,
-// reprojection and scale gates (:348-483) -- is ONE slamit_triangulate call per neighbour (csrc/triangulate.h).
+// reprojection and scale gates (:348-483) -- is ONE slamit_triangulate call per neighbour (csrc/triangulate.h), or ONE
+// slamit_triangulate_stereo call with the stereo branches of :335-465.
 //
 // Members used on the caller's type (on top of what ORBmatcher::SearchForTriangulation lists):
 //   KeyFrame : N, mvKeysUn, mvuRight, mvScaleFactors, mvLevelSigma2, mfScaleFactor, fx, fy, cx, cy, invfx, invfy,
@@ -16,9 +17,14 @@
 // so each neighbour's search runs after the previous neighbour's make() calls.  slamit_triangulate_batch is for callers that hold
 // the keyframe pairs of several independent streams at once (the pipeline configuration), where no such dependency exists.
 //
-// Stereo is out of scope: monocular == false, or a keyframe with a stereo coordinate (mvuRight >= 0), is refused on
-// stderr with LastStatus() == SLAMIT_ERR_ARG and nothing is created.  Any other non-SLAMIT_OK status of a device call is reported
-// the same way and ends the loop: never a silent return.
+// The stereo path is chosen at compile time (shim_common.h's member detection): a KeyFrameT with all of
+//   mb, mbf, mvDepth, mvKeys
+// takes stereo keyframes and monocular == false.  There the baseline gate is baseline < pKF2->mb when !monocular (:278-283), the
+// right-image side of every pair is mvuRight / mvDepth of its keypoints and the RAW keypoint mvKeys[idx].pt (KeyFrame::UnprojectStereo
+// reads it, not mvKeysUn), mb of each keyframe, and the CURRENT keyframe's mbf for both reprojection gates (:430, :458).
+// A KeyFrameT without these members keeps the monocular code: monocular == false, or a keyframe with a stereo coordinate
+// (mvuRight >= 0), is refused on stderr with LastStatus() == SLAMIT_ERR_ARG and nothing is created.  Any other non-SLAMIT_OK status
+// of a device call is reported the same way and ends the loop: never a silent return.
 #ifndef SLAMIT_SHIM_LOCALMAPPING_H
 #define SLAMIT_SHIM_LOCALMAPPING_H
 
@@ -67,10 +73,8 @@ public:
     template <class KeyFrameT, class NewPointFn, class StopFn>
     static int CreateNewMapPoints(KeyFrameT* cur, const std::vector<KeyFrameT*>& neigh, bool monocular, NewPointFn&& make, StopFn&& stop, int device = 0) {
         status() = SLAMIT_OK;
-        if (!monocular) return shim::refuse<LocalMapping>("CreateNewMapPoints: only the monocular path is on the device");
-        if (hasStereo(cur)) return shim::refuse<LocalMapping>("CreateNewMapPoints: the current keyframe carries stereo coordinates (mvuRight >= 0)");
-        for (size_t i = 0; i < neigh.size(); ++i)
-            if (hasStereo(neigh[i])) return shim::refuse<LocalMapping>("CreateNewMapPoints: a neighbour keyframe carries stereo coordinates (mvuRight >= 0)");
+        const StereoTag<KeyFrameT> tag = StereoTag<KeyFrameT>();
+        if (!accepts(cur, neigh, monocular, tag)) return 0;
         ORBmatcher matcher(0.6, false);
         slamit_triangulate_problem P;
         pose(cur, P.Tcw1, P.intr1);
@@ -80,14 +84,12 @@ public:
         for (size_t i = 0; i < neigh.size(); i++) {
             if (i > 0 && stop()) return nnew;
             KeyFrameT* pKF2 = neigh[i];
-            // baseline against the scene's median depth (:273-294)
+            // baseline against the scene's median depth, or against the rig's baseline (:273-294)
             const cv::Mat Ow2 = pKF2->GetCameraCenter();
             const float vB[3] = {Ow2.template at<float>(0, 0) - Ow1.template at<float>(0, 0), Ow2.template at<float>(1, 0) - Ow1.template at<float>(1, 0),
                                  Ow2.template at<float>(2, 0) - Ow1.template at<float>(2, 0)};
             const float baseline = (float)sqrt((double)vB[0] * vB[0] + (double)vB[1] * vB[1] + (double)vB[2] * vB[2]);
-            const float medianDepthKF2 = pKF2->ComputeSceneMedianDepth(2);
-            const float ratioBaselineDepth = baseline / medianDepthKF2;
-            if (ratioBaselineDepth < 0.01) continue;
+            if (baselineTooShort(pKF2, baseline, monocular, tag)) continue;
             const cv::Mat F12 = ComputeF12(cur, pKF2);
             std::vector<std::pair<size_t, size_t> > vMatchedIndices;
             matcher.SearchForTriangulation(cur, pKF2, F12, vMatchedIndices, false);
@@ -119,7 +121,7 @@ public:
             P.scale_factors2 = pKF2->mvScaleFactors.data(); P.level_sigma2_2 = pKF2->mvLevelSigma2.data();
             slamit_triangulate_result R;
             R.status = st.data(); R.x3d = x3d.data(); R.n_accepted = 0;
-            const int rc = slamit_triangulate(device, &P, &R);
+            const int rc = triangulate(cur, pKF2, vMatchedIndices, device, P, R, tag);
             if (rc != SLAMIT_OK) {
                 shim::report<LocalMapping>("CreateNewMapPoints: slamit_triangulate", rc);
                 return nnew;
@@ -145,6 +147,60 @@ public:
 private:
     static bool never() { return false; }
     static int& status() { return shim::status<LocalMapping>(); }
+    template <class KeyFrameT>
+    struct StereoTag : shim::bool_tag<shim::has_member_mb<KeyFrameT>::value && shim::has_member_mbf<KeyFrameT>::value &&
+                                      shim::has_member_mvDepth<KeyFrameT>::value && shim::has_member_mvKeys<KeyFrameT>::value> {};
+
+    // a keyframe type without the stereo members: the monocular path only
+    template <class KeyFrameT>
+    static bool accepts(KeyFrameT* cur, const std::vector<KeyFrameT*>& neigh, bool monocular, shim::bool_tag<false>) {
+        if (!monocular) { shim::refuse<LocalMapping>("CreateNewMapPoints: only the monocular path is on the device"); return false; }
+        if (hasStereo(cur)) { shim::refuse<LocalMapping>("CreateNewMapPoints: the current keyframe carries stereo coordinates (mvuRight >= 0)"); return false; }
+        for (size_t i = 0; i < neigh.size(); ++i)
+            if (hasStereo(neigh[i])) { shim::refuse<LocalMapping>("CreateNewMapPoints: a neighbour keyframe carries stereo coordinates (mvuRight >= 0)"); return false; }
+        return true;
+    }
+    template <class KeyFrameT>
+    static bool accepts(KeyFrameT*, const std::vector<KeyFrameT*>&, bool, shim::bool_tag<true>) { return true; }
+
+    // :273-294
+    template <class KeyFrameT>
+    static bool baselineTooShort(KeyFrameT* pKF2, float baseline, bool, shim::bool_tag<false>) {
+        const float medianDepthKF2 = pKF2->ComputeSceneMedianDepth(2);
+        const float ratioBaselineDepth = baseline / medianDepthKF2;
+        return ratioBaselineDepth < 0.01;
+    }
+    template <class KeyFrameT>
+    static bool baselineTooShort(KeyFrameT* pKF2, float baseline, bool monocular, shim::bool_tag<true>) {
+        if (!monocular) return baseline < pKF2->mb;
+        return baselineTooShort(pKF2, baseline, monocular, shim::bool_tag<false>());
+    }
+
+    // the device call of one neighbour: the monocular entry point, or the stereo one with the right-image side of every pair
+    template <class KeyFrameT>
+    static int triangulate(KeyFrameT*, KeyFrameT*, const std::vector<std::pair<size_t, size_t> >&, int device, slamit_triangulate_problem& P,
+                           slamit_triangulate_result& R, shim::bool_tag<false>) {
+        return slamit_triangulate(device, &P, &R);
+    }
+    template <class KeyFrameT>
+    static int triangulate(KeyFrameT* cur, KeyFrameT* pKF2, const std::vector<std::pair<size_t, size_t> >& pairs, int device, slamit_triangulate_problem& P,
+                           slamit_triangulate_result& R, shim::bool_tag<true>) {
+        const size_t n = pairs.size();
+        std::vector<float> ur1(n), ur2(n), depth1(n), depth2(n), raw1(2 * n), raw2(2 * n);
+        for (size_t k = 0; k < n; ++k) {
+            const size_t i1 = pairs[k].first, i2 = pairs[k].second;
+            ur1[k] = cur->mvuRight[i1]; depth1[k] = cur->mvDepth[i1];
+            ur2[k] = pKF2->mvuRight[i2]; depth2[k] = pKF2->mvDepth[i2];
+            raw1[2 * k] = cur->mvKeys[i1].pt.x; raw1[2 * k + 1] = cur->mvKeys[i1].pt.y;      // KeyFrame::UnprojectStereo reads mvKeys
+            raw2[2 * k] = pKF2->mvKeys[i2].pt.x; raw2[2 * k + 1] = pKF2->mvKeys[i2].pt.y;
+        }
+        slamit_triangulate_stereo_rec T;
+        T.ur1 = ur1.data(); T.ur2 = ur2.data(); T.depth1 = depth1.data(); T.depth2 = depth2.data(); T.raw1_xy = raw1.data(); T.raw2_xy = raw2.data();
+        T.mb1 = cur->mb; T.mb2 = pKF2->mb;
+        T.bf = cur->mbf;                                                                       // :430 and :458: the current keyframe's
+        return slamit_triangulate_stereo(device, &P, &T, &R, NULL);
+    }
+
     template <class KeyFrameT>
     static bool hasStereo(KeyFrameT* kf) {
         for (size_t i = 0; i < kf->mvuRight.size(); ++i)

@@ -145,6 +145,14 @@ bool ORBmatcher::BowSearch(const cv::Mat& desc1, const std::vector<uint8_t>& val
         }
     }
     int nm = 0;
+    if (gate && gate->uRight1 && gate->uRight2) {
+        if ((int)gate->uRight1->size() < n1 || (int)gate->uRight2->size() < n2) { shim::refuse<ORBmatcher>("SearchForTriangulation: mvuRight is shorter than N"); return false; }
+        slamit_bow_stereo st;
+        st.ur1 = gate->uRight1->data(); st.ur2 = gate->uRight2->data(); st.only_stereo = gate->onlyStereo ? 1 : 0;
+        setStatus(slamit_bow_search_stereo(0, packed_rows(desc1, t1), n1, valid1.empty() ? nullptr : valid1.data(), packed_rows(desc2, t2), n2,
+                                           valid2 ? valid2->data() : nullptr, &gg, &rule, &st, match12.data(), nullptr, &nm));
+        return LastStatus() == SLAMIT_OK;
+    }
     setStatus(slamit_bow_search(0, packed_rows(desc1, t1), n1, valid1.empty() ? nullptr : valid1.data(), packed_rows(desc2, t2), n2,
                                 valid2 ? valid2->data() : nullptr, &gg, &rule, match12.data(), nullptr, &nm));
     return LastStatus() == SLAMIT_OK;

@@ -131,10 +131,11 @@ public:
     template <class KeyFrameT, class MapPointT>
     int SearchByBoW(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12);
 
-    // LocalMapping::CreateNewMapPoints' matcher (ORBmatcher.cc:659-826), monocular: features without a map point, same
-    // vocabulary node, epipolar constraint.  Additional KeyFrame members: N, GetMapPoint(i), GetCameraCenter(),
-    // GetRotation(), GetTranslation(), fx, fy, cx, cy, mvScaleFactors, mvLevelSigma2, mvuRight.  A keyframe with a stereo
-    // keypoint (mvuRight >= 0) or bOnlyStereo is refused (returns 0, LastStatus() != 0).
+    // LocalMapping::CreateNewMapPoints' matcher (ORBmatcher.cc:659-826): features without a map point, same vocabulary
+    // node, epipolar constraint.  Additional KeyFrame members: N, GetMapPoint(i), GetCameraCenter(), GetRotation(),
+    // GetTranslation(), fx, fy, cx, cy, mvScaleFactors, mvLevelSigma2, mvuRight.  With a stereo keypoint (mvuRight >= 0) in
+    // either keyframe, or bOnlyStereo, the call is slamit_bow_search_stereo with both mvuRight: the epipole test runs only
+    // for a pair without a stereo keypoint (:747-753) and bOnlyStereo skips the monocular ones (:711-713, :734-736).
     template <class KeyFrameT>
     int SearchForTriangulation(KeyFrameT* pKF1, KeyFrameT* pKF2, cv::Mat F12, std::vector<std::pair<size_t, size_t> >& vMatchedPairs,
                                const bool bOnlyStereo);
@@ -165,6 +166,10 @@ public:
         const std::vector<cv::KeyPoint>* keys2;
         const std::vector<float>* scaleFactors;
         const std::vector<float>* levelSigma2;
+        const std::vector<float>* uRight1;   // both set: the stereo search (mvuRight of the two keyframes, bOnlyStereo)
+        const std::vector<float>* uRight2;
+        bool onlyStereo;
+        EpipolarGate() : keys1(NULL), keys2(NULL), scaleFactors(NULL), levelSigma2(NULL), uRight1(NULL), uRight2(NULL), onlyStereo(false) {}
     };
     static bool BowSearch(const cv::Mat& desc1, const std::vector<uint8_t>& valid1, const cv::Mat& desc2, const std::vector<uint8_t>* valid2,
                           const BowGroups& g, int th, bool thInclusive, float nnratio, const EpipolarGate* gate, std::vector<int>& match12);
@@ -548,7 +553,6 @@ int ORBmatcher::SearchForTriangulation(KeyFrameT* pKF1, KeyFrameT* pKF2, cv::Mat
     bool stereo = bOnlyStereo;
     for (int i = 0; i < n1 && !stereo; ++i) stereo = pKF1->mvuRight[i] >= 0;
     for (int i = 0; i < n2 && !stereo; ++i) stereo = pKF2->mvuRight[i] >= 0;
-    if (stereo) { setStatus(SLAMIT_ERR_ARG); return 0; }   // monocular path only (the reference application is MONOCULAR)
     // epipole of camera 1 in image 2 (:665-673)
     const cv::Mat Cw = pKF1->GetCameraCenter(), R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
     float C2[3];
@@ -563,6 +567,7 @@ int ORBmatcher::SearchForTriangulation(KeyFrameT* pKF1, KeyFrameT* pKF2, cv::Mat
         for (int c = 0; c < 3; ++c) gate.F12[3 * r + c] = F12.template at<float>(r, c);
     gate.keys1 = &pKF1->mvKeysUn; gate.keys2 = &pKF2->mvKeysUn;
     gate.scaleFactors = &pKF2->mvScaleFactors; gate.levelSigma2 = &pKF2->mvLevelSigma2;
+    if (stereo) { gate.uRight1 = &pKF1->mvuRight; gate.uRight2 = &pKF2->mvuRight; gate.onlyStereo = bOnlyStereo; }   // else: the monocular call, as it was
     std::vector<uint8_t> valid1(n1, 0), valid2(n2, 0);
     for (int i = 0; i < n1; ++i) valid1[i] = pKF1->GetMapPoint(i) ? 0 : 1;   // :700-704: skip features that have a MapPoint
     for (int i = 0; i < n2; ++i) valid2[i] = pKF2->GetMapPoint(i) ? 0 : 1;   // :724-728

@@ -49,7 +49,8 @@ inline void load3(const MatT& m, float* out, int col = 0, int stride = 1) {
 // Does the caller's type have a data member of this name?  C++11 member detection: has_member_<name><T>::value, and
 // member_or_<name>(obj, fallback) reads it where it exists.  The stereo paths of the guided searches are chosen by it at compile time
 // (mTrackProjXR on the map point, mbf on the frame or keyframe): a type without the member keeps the monocular code and its refusal
-// of stereo frames, and never names the member.
+// of stereo frames, and never names the member.  LocalMapping::CreateNewMapPoints takes its stereo path for a keyframe type with all
+// of mb, mbf, mvDepth and mvKeys.
 template <bool B> struct bool_tag {};
 #define SLAMIT_SHIM_HAS_MEMBER(name)                                                                                   \
     template <class T>                                                                                                 \
@@ -65,6 +66,9 @@ template <bool B> struct bool_tag {};
     }
 SLAMIT_SHIM_HAS_MEMBER(mTrackProjXR)
 SLAMIT_SHIM_HAS_MEMBER(mbf)
+SLAMIT_SHIM_HAS_MEMBER(mb)
+SLAMIT_SHIM_HAS_MEMBER(mvDepth)
+SLAMIT_SHIM_HAS_MEMBER(mvKeys)
 
 // The rotation-consistency filter of the reference's searches (ORBmatcher.cc:240-250 with :271-289, and its copies): matches
 // are binned by the difference of their keypoint angles, and those outside the three most populated bins are undone.

@@ -14,6 +14,7 @@
 //     shim_test osim3 <problem.bin> <out.bin>
 //     shim_test sim3solver <problem.bin> <out.bin>
 //     shim_test triangulate <problem.bin> <out.bin>
+//     shim_test triangulate_stereo <problem.bin> <out.bin>
 //     shim_test frustum <problem.bin> <out.bin>
 //     shim_test stereo <pair.bin> <out.bin>
 #include <stdio.h>
@@ -1134,6 +1135,65 @@ static int run_triangulate(int argc, char** argv) {
     return 0;
 }
 
+// ---- LocalMapping::CreateNewMapPoints on stereo keyframes -------------------------------------------------------------------------
+struct MockStereoMapKF : MockMapKF {   // the four members that choose LocalMapping.h's stereo path
+    float mb, mbf;
+    std::vector<float> mvDepth;
+};
+// problem.bin: int32 nkf monocular ; float scale[8] sigma2[8] ; per keyframe: int32 n ; float R[9] t[3] intr[4] median_depth mb mbf ;
+//   the side layout of `bow` (xy = mvKeysUn) ; float ur[n] depth[n] raw_xy[2 n] (mvuRight, mvDepth, mvKeys: the distorted keypoints)
+// out.bin: as `triangulate`
+static int run_triangulate_stereo(int argc, char** argv) {
+    if (argc < 4) return 2;
+    std::vector<unsigned char> raw = slurp(argv[2]);
+    Reader R{raw.data()};
+    const int nkf = R.get<int>(), monocular = R.get<int>();
+    const float* scale = R.arr<float>(8); const float* sig = R.arr<float>(8);
+    std::vector<MockStereoMapKF> kfs(nkf);
+    std::vector<std::vector<MockBowPoint> > pts(nkf);
+    for (int k = 0; k < nkf; ++k) {
+        MockStereoMapKF& K = kfs[k];
+        const int n = R.get<int>();
+        const float* Rm = R.arr<float>(9); const float* t = R.arr<float>(3); const float* intr = R.arr<float>(4);
+        K.medianDepth = R.get<float>(); K.mb = R.get<float>(); K.mbf = R.get<float>();
+        fill_side(R, n, K, pts[k]);
+        const float* ur = R.arr<float>(n); const float* depth = R.arr<float>(n); const float* rawxy = R.arr<float>(2 * (size_t)n);
+        K.mvuRight.assign(ur, ur + n); K.mvDepth.assign(depth, depth + n);
+        for (int i = 0; i < n; ++i) { K.mvKeys[i].pt.x = rawxy[2 * i]; K.mvKeys[i].pt.y = rawxy[2 * i + 1]; }
+        K.Rcw = cv::Mat(3, 3, CV_32F); K.tcw = mat_from(t, 3);
+        float Ow[3];
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) K.Rcw.at<float>(r, c) = Rm[3 * r + c];
+            Ow[r] = -((Rm[r] * t[0] + Rm[3 + r] * t[1]) + Rm[6 + r] * t[2]);   // KeyFrame::SetPose: Ow = -Rwc * tcw
+        }
+        K.Ow = mat_from(Ow, 3);
+        K.fx = intr[0]; K.fy = intr[1]; K.cx = intr[2]; K.cy = intr[3]; K.invfx = 1.0f / K.fx; K.invfy = 1.0f / K.fy;
+        K.mfScaleFactor = scale[1];
+        K.mvScaleFactors.assign(scale, scale + 8); K.mvLevelSigma2.assign(sig, sig + 8);
+    }
+    std::vector<MockStereoMapKF*> neigh;
+    for (int k = 1; k < nkf; ++k) neigh.push_back(&kfs[k]);
+    std::vector<int> rec;
+    std::vector<float> xs;
+    std::vector<MockBowPoint*> made;
+    auto make = [&](const cv::Mat& x3D, int idx1, int idx2, MockStereoMapKF* pKF2) {
+        MockBowPoint* p = new MockBowPoint();
+        p->id = (int)made.size(); p->bad = false;
+        made.push_back(p);
+        kfs[0].matches[idx1] = p; pKF2->matches[idx2] = p;
+        rec.push_back((int)(pKF2 - &kfs[0]) - 1); rec.push_back(idx1); rec.push_back(idx2);
+        for (int r = 0; r < 3; ++r) xs.push_back(x3D.at<float>(r, 0));
+    };
+    const int nnew = LocalMapping::CreateNewMapPoints(&kfs[0], neigh, monocular != 0, make);
+    const int status = LocalMapping::LastStatus();
+    FILE* f = fopen(argv[3], "wb");
+    fwrite(&status, 4, 1, f); fwrite(&nnew, 4, 1, f);
+    for (int k = 0; k < nnew; ++k) { fwrite(&rec[3 * k], 4, 3, f); fwrite(&xs[3 * k], 4, 3, f); }
+    fclose(f);
+    for (size_t k = 0; k < made.size(); ++k) delete made[k];
+    return 0;
+}
+
 // ---- Tracking::SearchLocalPoints through the template -----------------------------------------------------------------------------
 struct MockLocalPoint {   // the members Tracking.h lists on top of the search's
     bool mbTrackInView, bad;
@@ -1301,6 +1361,7 @@ int main(int argc, char** argv) {
     if (mode == "osim3") return run_osim3(argc, argv);
     if (mode == "sim3solver") return run_sim3solver(argc, argv);
     if (mode == "triangulate") return run_triangulate(argc, argv);
+    if (mode == "triangulate_stereo") return run_triangulate_stereo(argc, argv);
     if (mode == "frustum") return run_frustum(argc, argv);
     if (mode == "stereo") return run_stereo(argc, argv);
     return 2;

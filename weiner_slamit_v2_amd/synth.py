@@ -453,6 +453,67 @@ def synth_bow(n1=1000, n2=1000, n_nodes=100, seed=0, mode=0, big_group=0):
     return side1, side2, groups, epi
 
 
+def synth_bow_stereo(n1=300, n2=620, n_nodes=12, seed=0, group_sizes=(1, 63, 64, 65, 130), near_epipole_frac=0.25, stereo_frac=0.6):
+    """Two STEREO keyframes as ORBmatcher::SearchForTriangulation sees them (ORBmatcher.cc:695-793): synth_bow's mode-1 layout
+    (side1, side2, groups, epi) with `ur` (mvuRight) on both sides, and a motion with a forward component, so that the epipole of
+    camera 1 lies INSIDE image 2 and the epipole test (:747-753) has candidates to reject.  Camera 2 is camera 1 moved by
+    (0.06, -0.03, 0.5); every side-1 feature is a point at a depth of 2..15, a share near_epipole_frac of them within 14 px of the
+    focus of expansion; side 2 holds noisy copies of side-1 descriptors in the source's node, at the point's projection into camera 2
+    (a quarter of them ~12 px off).  The first len(group_sizes) nodes hold exactly group_sizes candidates.  A share stereo_frac of
+    the features of each side is stereo (ur = x - bf / z when that is >= 0), the rest has ur = -1, one NaN and one 0.0f per side."""
+    rs = np.random.RandomState(19500 + seed)
+    f32 = np.float32
+    k = len(group_sizes)
+    assert n_nodes > k and n1 >= 4 * k and n2 > sum(group_sizes) + 4
+    d1 = rs.randint(0, 256, (n1, 32)).astype(np.uint8)
+    node1 = rs.randint(0, n_nodes, n1)
+    node1[:4 * k] = np.repeat(np.arange(k), 4)                   # at least four queries in each sized group
+    node2 = np.concatenate([np.full(sz, j) for j, sz in enumerate(group_sizes)] + [rs.randint(k, n_nodes, n2 - sum(group_sizes))])
+    src = np.zeros(n2, np.int64)
+    for i in range(n2):
+        same = np.flatnonzero(node1 == node2[i])
+        src[i] = same[rs.randint(len(same))] if len(same) else rs.randint(n1)
+    d2 = d1[src].copy()
+    for i in range(n2):
+        for b in rs.randint(0, 256, rs.randint(0, 60)):
+            d2[i, b >> 3] ^= np.uint8(1 << (b & 7))
+    fx, fy, cx, cy = f32(517.3), f32(516.5), f32(318.6), f32(255.3)
+    t21 = -np.array([0.06, -0.03, 0.5])                            # X2 = X1 + t21
+    ex, ey = float(fx) * t21[0] / t21[2] + float(cx), float(fy) * t21[1] / t21[2] + float(cy)
+    xy1 = np.stack([rs.uniform(20, 620, n1), rs.uniform(20, 460, n1)], 1)
+    near = rs.rand(n1) < near_epipole_frac
+    xy1[near] = np.array([ex, ey]) + rs.uniform(-14, 14, (int(near.sum()), 2))
+    xy1 = xy1.astype(f32)
+    z1 = rs.uniform(2.0, 15.0, n1)
+    X1 = np.stack([(xy1[:, 0] - float(cx)) / float(fx) * z1, (xy1[:, 1] - float(cy)) / float(fy) * z1, z1], 1)
+    X2 = X1[src] + t21
+    noise = np.where((rs.rand(n2) < 0.75)[:, None], rs.normal(0, 0.8, (n2, 2)), rs.normal(0, 12.0, (n2, 2)))
+    xy2 = (np.stack([float(fx) * X2[:, 0] / X2[:, 2] + float(cx), float(fy) * X2[:, 1] / X2[:, 2] + float(cy)], 1) + noise).astype(f32)
+    a = sum(group_sizes[:2])                                     # exact duplicates inside the 64-candidate group: a tie, the last one wins
+    d2[a + 1], xy2[a + 1], src[a + 1] = d2[a], xy2[a], src[a]
+    oct2 = rs.randint(0, 8, n2).astype(np.int32)
+    bf = 0.12 * float(fx)
+    ur1 = np.where(rs.rand(n1) < stereo_frac, xy1[:, 0] - bf / z1, -1.0)
+    ur2 = np.where(rs.rand(n2) < stereo_frac, xy2[:, 0] - bf / X2[:, 2], -1.0)
+    ur1, ur2 = np.where(ur1 >= 0, ur1, -1.0).astype(f32), np.where(ur2 >= 0, ur2, -1.0).astype(f32)
+    ur1[4 * k], ur1[4 * k + 1], ur2[n2 - 1], ur2[n2 - 2] = np.nan, 0.0, np.nan, 0.0
+    K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float64)
+    tx = np.array([[0, -t21[2], t21[1]], [t21[2], 0, -t21[0]], [-t21[1], t21[0], 0]])
+    Ki = np.linalg.inv(K)
+    F = (Ki.T @ tx.T @ Ki).astype(f32)                           # x2^T [t21]x x1 = 0, so x1^T F12 x2 = 0 with F12 = K^-T [t21]x^T K^-1
+    scale = (f32(1.2) ** np.arange(8, dtype=f32)).astype(f32)
+    side1 = dict(desc=d1, valid=(rs.rand(n1) < 0.85).astype(np.uint8), kp_xy=xy1, ur=ur1)
+    side2 = dict(desc=d2, valid=(rs.rand(n2) < 0.9).astype(np.uint8), kp_xy=xy2, kp_octave=oct2, ur=ur2)
+    qp, qi, cp, ci = [0], [], [0], []
+    for node in sorted(set(node1.tolist()) & set(node2.tolist())):
+        qa, cb = np.nonzero(node1 == node)[0], np.nonzero(node2 == node)[0]
+        qi += qa.tolist(); ci += cb.tolist()
+        qp.append(len(qi)); cp.append(len(ci))
+    groups = dict(q_ptr=np.array(qp, np.int32), q_idx=np.array(qi, np.int32), c_ptr=np.array(cp, np.int32), c_idx=np.array(ci, np.int32))
+    epi = dict(F12=F.reshape(9), ex=ex, ey=ey, scale_factor=scale.tolist(), level_sigma2=(scale * scale).tolist())
+    return side1, side2, groups, epi
+
+
 def synth_sim3(n=200, outlier_frac=0.15, seed=0, perturb=0.03, fix_scale=False, scale=1.08):
     """An Optimizer::OptimizeSim3 problem as the reference assembles it (Optimizer.cc:1099-1178): the same physical points as
     map points of two keyframes, each in its own camera frame (p1, p2, float values), their keypoints in both images, a true
@@ -566,6 +627,46 @@ def synth_triangulation(n=300, seed=0, baseline=0.3, outlier_frac=0.2, noise_px=
                 octave1=o1.astype(np.int32), octave2=o2.astype(np.int32), n_levels=nlev,
                 scale_factors1=scale_f.copy(), level_sigma2_1=sigma2.copy(), scale_factors2=scale_f.copy(), level_sigma2_2=sigma2.copy(),
                 ratio_factor=f32(1.5) * f32(1.2), true=dict(X=Xw, bad=bad, behind=behind, jump=jump))
+
+
+def synth_triangulation_stereo(n=300, seed=0, baseline=0.3, outlier_frac=0.2, noise_px=0.7, mb=0.12, stereo_frac=(0.25, 0.25, 0.25),
+                               ur_outlier_frac=0.06, distortion=4e-8, **opts):
+    """synth_triangulation(n, seed, baseline, outlier_frac, noise_px, **opts) on stereo keyframes: the same problem plus what
+    LocalMapping::CreateNewMapPoints reads of a stereo keypoint (LocalMapping.cc:335-345, KeyFrame::UnprojectStereo).  Shares
+    stereo_frac of the pairs are stereo in keyframe 1 only, in keyframe 2 only and in both (the rest in neither), drawn per pair so
+    that every wavefront mixes them.  A stereo keypoint has ur = u - bf / z of the true point plus the level's pixel noise, moved by a
+    further 2..6 level-scaled pixels for a share ur_outlier_frac (the third error term alone then rejects it), and depth = bf / (u - ur)
+    in float as Frame::ComputeStereoMatches stores it; a keypoint whose point is nearer than 0.3 or behind the camera, or whose ur or
+    disparity is not positive, stays monocular (ur = depth = -1).  raw*_xy is the distorted keypoint mvKeys: the undistorted one moved
+    radially by distortion * r^2 * (p - c), about a pixel at the image border.  mb1 = mb2 = mb, bf = mb * fx1, the current keyframe's."""
+    pr = synth_triangulation(n, seed, baseline, outlier_frac, noise_px, **opts)
+    rs = np.random.RandomState(19000 + seed)
+    f32 = np.float32
+    kind = rs.choice(4, n, p=[1.0 - sum(stereo_frac)] + list(stereo_frac))       # 0 neither, 1 keyframe 1, 2 keyframe 2, 3 both
+    Xw = pr["true"]["X"]
+    out = dict(pr, mb1=f32(mb), mb2=f32(mb), bf=f32(mb) * pr["intr1"][0])
+    for side, flag in ((1, (kind == 1) | (kind == 3)), (2, (kind == 2) | (kind == 3))):
+        T = pr["Tcw%d" % side].astype(np.float64).reshape(3, 4)
+        intr, kp, octv = pr["intr%d" % side], pr["kp%d_xy" % side], pr["octave%d" % side]
+        z = Xw @ T[2, :3] + T[2, 3]
+        bf = float(f32(mb) * intr[0])
+        scale = pr["scale_factors%d" % side][octv].astype(np.float64)
+        with np.errstate(all="ignore"):
+            u_true = intr[0] * (Xw @ T[0, :3] + T[0, 3]) / z + intr[2]
+            ur = u_true - bf / z + rs.normal(0, noise_px, n) * scale
+        far = rs.rand(n) < ur_outlier_frac
+        ur = np.where(far, ur + rs.choice([-1.0, 1.0], n) * rs.uniform(2.0, 6.0, n) * scale, ur).astype(f32)
+        with np.errstate(all="ignore"):
+            disp = kp[:, 0] - ur
+            depth = (out["bf"] / disp).astype(f32)
+        ok = flag & (z > 0.3) & (ur >= 0) & (disp > 0) & np.isfinite(depth)
+        out["ur%d" % side] = np.where(ok, ur, f32(-1)).astype(f32)
+        out["depth%d" % side] = np.where(ok, depth, f32(-1)).astype(f32)
+        c = intr[2:4].astype(np.float64)
+        dxy = kp.astype(np.float64) - c
+        out["raw%d_xy" % side] = (kp.astype(np.float64) + distortion * (dxy ** 2).sum(1)[:, None] * dxy).astype(f32)
+    out["true"] = dict(pr["true"], kind=kind)
+    return out
 
 
 def synth_frustum(seed=0, n=1000, th=1.0, n_levels=8, width=640, height=480, skip_frac=0.05, behind_frac=0.08, frontal_frac=0.3,
