@@ -734,6 +734,63 @@ typedef struct slamit_sim3_ransac_result {
 int slamit_sim3_ransac_batch(int device, int nproblems, const slamit_sim3_ransac_problem* probs, slamit_sim3_ransac_result* results);
 int slamit_sim3_ransac(int device, const slamit_sim3_ransac_problem* prob, slamit_sim3_ransac_result* res);
 
+/* ---- PnPsolver: batched EPnP RANSAC (relocalisation, between SearchByBoW and PoseOptimization) ----
+ * PnPsolver::compute_pose + CheckInliers (src/PnPsolver.cc:316-347, :383-958) for n_hyp sampled quadruples of one candidate
+ * keyframe: per hypothesis the EPnP pose of its four correspondences in double, then the reprojection of all n correspondences
+ * (float / double exactly where the reference has them) and the count of those with error2 < max_err.  One wavefront per
+ * (problem, hypothesis); a batch of candidates is one launch.  slamit_pnp_refine_batch is Refine() (:268-313): the EPnP pose of
+ * a subset given as a bit mask (a hypothesis' inlier_bits), then CheckInliers over all n; one workgroup per problem.  Sampling,
+ * SetRansacParameters and iterate()'s scan stay with the caller (shim/PnPsolver.h, api.PnPsolver).
+ * The reference's pose depends on which basis cvSVD returns for the four-dimensional null space of a four-point set and on the
+ * sign of its PCA axes; both are pinned here (csrc/epnp.h).  Every decomposition runs a fixed number of
+ * sweeps: the reference's sampler can repeat an index inside a quadruple (:196-209), which is legal input and yields a pose that
+ * need not be finite and some count in [0, n].  A subset of four takes the four-point path, one of five is accepted and
+ * unspecified, one of fewer than four fails with SLAMIT_ERR_ARG.  An index outside [0, n), n above SLAMIT_PNP_MAX_N, n_hyp above
+ * SLAMIT_PNP_MAX_HYP or a null array with n > 0 fails with SLAMIT_ERR_ARG and a message before anything is launched; n == 0 or
+ * n_hyp == 0 is allowed and writes nothing.  (The four structs are declared tag first, typedef after, like the stereo record above.) */
+#define SLAMIT_PNP_MAX_N 8192       /* correspondences per problem */
+#define SLAMIT_PNP_MAX_HYP 1024     /* hypotheses per problem (Tracking::Relocalization asks for 300 at most) */
+
+struct slamit_pnp_problem {
+    int32_t n;                 /* correspondences the PnPsolver constructor keeps (:87-109) */
+    const float* p3d;          /* n x 3: mvP3Dw */
+    const float* p2d;          /* n x 2: mvP2D (kpUn.pt) */
+    const float* max_err;      /* n: (float)(mvSigma2[i] * th2) */
+    double intr[4];            /* fu fv uc vc: doubles holding F.fx, F.fy, F.cx, F.cy */
+    int32_t n_hyp;             /* hypotheses to evaluate */
+    const int32_t* quads;      /* n_hyp x 4 indices into the n correspondences */
+};
+typedef struct slamit_pnp_problem slamit_pnp_problem;
+
+struct slamit_pnp_result {
+    double* pose;              /* n_hyp x 12: mRi row-major (9), mti (3) */
+    int32_t* n_inliers;        /* n_hyp: mnInliersi of each hypothesis */
+    uint32_t* inlier_bits;     /* n_hyp x ((n+31)/32), nullable: bit i = mvbInliersi[i] */
+};
+typedef struct slamit_pnp_result slamit_pnp_result;
+
+struct slamit_pnp_refine_problem {
+    int32_t n;
+    const float* p3d;          /* as in slamit_pnp_problem */
+    const float* p2d;
+    const float* max_err;
+    double intr[4];
+    const uint32_t* subset_bits;   /* (n+31)/32 words: bit i = correspondence i takes part (mvbBestInliers); bits past n are ignored */
+};
+typedef struct slamit_pnp_refine_problem slamit_pnp_refine_problem;
+
+struct slamit_pnp_refine_result {
+    double pose[12];           /* out: mRi row-major, mti */
+    int32_t n_inliers;         /* out: mnRefinedInliers */
+    uint32_t* inlier_bits;     /* (n+31)/32 words, nullable: mvbRefinedInliers */
+};
+typedef struct slamit_pnp_refine_result slamit_pnp_refine_result;
+
+/* nproblems candidates in one launch (host pointers, synchronous). */
+int slamit_pnp_ransac_batch(int device, int nproblems, const slamit_pnp_problem* probs, slamit_pnp_result* results);
+int slamit_pnp_ransac(int device, const slamit_pnp_problem* prob, slamit_pnp_result* res);
+int slamit_pnp_refine_batch(int device, int nproblems, const slamit_pnp_refine_problem* probs, slamit_pnp_refine_result* results);
+
 /* ---- CreateNewMapPoints: batched two-view triangulation (local mapping, between SearchForTriangulation and the new map point) ----
  * The per-pair body of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:348-483), monocular: parallax of the two rays, the
  * 4x4 linear triangulation (smallest right singular vector, one-sided Jacobi in float), both depth tests, both reprojection

@@ -128,6 +128,27 @@ class Sim3RansacResult(C.Structure):
 SIM3_RANSAC_MAX_N, SIM3_RANSAC_MAX_HYP = 8192, 1024   # SLAMIT_SIM3_RANSAC_MAX_N / _MAX_HYP
 
 
+class PnpProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("p3d", C.c_void_p), ("p2d", C.c_void_p), ("max_err", C.c_void_p), ("intr", C.c_double * 4),
+                ("n_hyp", C.c_int32), ("quads", C.c_void_p)]
+
+
+class PnpResult(C.Structure):
+    _fields_ = [("pose", C.c_void_p), ("n_inliers", C.c_void_p), ("inlier_bits", C.c_void_p)]
+
+
+class PnpRefineProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("p3d", C.c_void_p), ("p2d", C.c_void_p), ("max_err", C.c_void_p), ("intr", C.c_double * 4),
+                ("subset_bits", C.c_void_p)]
+
+
+class PnpRefineResult(C.Structure):
+    _fields_ = [("pose", C.c_double * 12), ("n_inliers", C.c_int32), ("inlier_bits", C.c_void_p)]
+
+
+PNP_MAX_N, PNP_MAX_HYP = 8192, 1024   # SLAMIT_PNP_MAX_N / _MAX_HYP
+
+
 class TriangulateProblem(C.Structure):
     _fields_ = [("Tcw1", C.c_float * 12), ("Tcw2", C.c_float * 12), ("intr1", C.c_float * 6), ("intr2", C.c_float * 6), ("n", C.c_int32),
                 ("n_levels", C.c_int32), ("kp1_xy", C.c_void_p), ("kp2_xy", C.c_void_p), ("octave1", C.c_void_p), ("octave2", C.c_void_p),
@@ -291,7 +312,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -343,6 +364,9 @@ def lib():
         L.slamit_sim3_optimize.argtypes = [i32, C.POINTER(Sim3Problem), C.POINTER(Sim3Result)]
         L.slamit_sim3_ransac_batch.argtypes = [i32, i32, C.POINTER(Sim3RansacProblem), C.POINTER(Sim3RansacResult)]
         L.slamit_sim3_ransac.argtypes = [i32, C.POINTER(Sim3RansacProblem), C.POINTER(Sim3RansacResult)]
+        L.slamit_pnp_ransac_batch.argtypes = [i32, i32, C.POINTER(PnpProblem), C.POINTER(PnpResult)]
+        L.slamit_pnp_ransac.argtypes = [i32, C.POINTER(PnpProblem), C.POINTER(PnpResult)]
+        L.slamit_pnp_refine_batch.argtypes = [i32, i32, C.POINTER(PnpRefineProblem), C.POINTER(PnpRefineResult)]
         L.slamit_triangulate_batch.argtypes = [i32, i32, C.POINTER(TriangulateProblem), C.POINTER(TriangulateResult)]
         L.slamit_triangulate.argtypes = [i32, C.POINTER(TriangulateProblem), C.POINTER(TriangulateResult)]
         L.slamit_triangulate_stereo_batch.argtypes = [i32, i32, C.POINTER(TriangulateProblem), C.POINTER(C.POINTER(TriangulateStereo)), C.POINTER(TriangulateResult), C.POINTER(vp)]
@@ -1447,6 +1471,223 @@ class Sim3Solver:
 
     def GetEstimatedScale(self):
         return float(self.t12[self.best, 12])
+
+
+class PnPsolver:
+    """PnPsolver (include/PnPsolver.h) on POD inputs: the constructor's gathering (PnPsolver.cc:67-118) stays with the caller, who
+    hands over a problem dict in the layout of slamit_pnp_problem (synth.synth_pnp): p3d (n, 3), p2d (n, 2) float32, sigma2 (n)
+    -- or max_err (n) directly --, intr (fu fv uc vc).  The hypotheses run on the device in one call (ransac), Refine() of every
+    hypothesis the scan can record as best in a second one (refine); iterate()'s sequential scan (:190-263) runs here over both
+    result sets.  `rand_int(lo, hi)` stands for DUtils::Random::RandomInt; all mRansacMaxIts quadruples are drawn when the
+    parameters are set, so the process RNG is consumed in another order than in the reference."""
+
+    def __init__(self, problem, rand_int=None, device=0):
+        self.problem = dict(problem)
+        self.N = len(np.asarray(problem["p3d"]).reshape(-1, 3))
+        self.device = device
+        if rand_int is None:
+            rs = np.random.RandomState(0)
+            rand_int = lambda lo, hi: int(rs.randint(lo, hi + 1))   # noqa: E731
+        self.rand_int = rand_int
+        self.SetRansacParameters(_draw=False)   # the constructor's default parameters (:117) take nothing from the RNG: the first iterate() draws
+
+    @staticmethod
+    def ransac_parameters(N, probability, minInliers, maxIterations, minSet, epsilon):
+        """SetRansacParameters (:137-160) -> (mRansacMinInliers, mRansacMaxIts, mRansacEpsilon): the truncated float product, the two
+        clamps, the epsilon update in float, pow(epsilon, 3) (3 although the set is 4), the == N case, the final clamp."""
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            eps = np.float32(epsilon)
+            nmin = int(np.float32(N) * eps)
+            nmin = max(nmin, minInliers, minSet)
+            ratio = np.float32(nmin) / np.float32(N)
+            if eps < ratio:
+                eps = ratio
+            if nmin == N:
+                nit = 1
+            else:
+                v = np.ceil(np.log(np.float64(1) - np.float64(probability)) / np.log(np.float64(1) - np.float64(eps) ** 3))
+                nit = int(v) if np.isfinite(v) and abs(v) < 2 ** 31 else -2 ** 31   # (int) of an unrepresentable double on x86-64
+        return nmin, max(1, min(nit, maxIterations)), eps
+
+    @staticmethod
+    def sample_quads(N, count, rand_int):
+        """The sampler of iterate() (:196-209), with its quirk: the slot overwritten is vAvailableIndices[idx] -- indexed by the
+        VALUE drawn, not by the position randi -- so a value can be drawn twice inside a quadruple."""
+        out = np.zeros((count, 4), np.int32)
+        for h in range(count):
+            avail, size = list(range(N)), N   # a value drawn may lie past the shrunken end: the store then lands in a popped slot
+            for i in range(4):
+                randi = rand_int(0, size - 1)
+                idx = avail[randi]
+                out[h, i] = idx
+                avail[idx] = avail[size - 1]
+                size -= 1
+        return out
+
+    def SetRansacParameters(self, probability=0.99, minInliers=8, maxIterations=300, minSet=4, epsilon=0.4, th2=5.991, _draw=True):
+        if minSet != 4:
+            raise SlamitError("PnPsolver.SetRansacParameters: minSet must be 4 (SLAMIT_ERR_ARG): the device solves four-point sets only")
+        self.mRansacProb = probability
+        self.mRansacMinInliers, self.mRansacMaxIts, self.mRansacEpsilon = self.ransac_parameters(self.N, probability, minInliers, maxIterations, minSet, epsilon)
+        if "sigma2" in self.problem:
+            self.problem["max_err"] = (np.asarray(self.problem["sigma2"], np.float32) * np.float32(th2)).astype(np.float32)   # mvMaxError: a float product
+        self.mnIterations, self.mnBestInliers, self.best, self.accepted = 0, 0, -1, -1
+        draw = self.mRansacMaxIts if _draw and self.N >= self.mRansacMinInliers else 0
+        self.quads = self.sample_quads(self.N, draw, self.rand_int)
+        w = (self.N + 31) // 32
+        self.pose, self.counts, self.bits = np.zeros((0, 12)), np.zeros(0, np.int32), np.zeros((0, w), np.uint32)
+        self.refined = {}   # recorded best -> dict(pose, n_inliers, inlier_bits)
+
+    # ---- the two device calls ----
+    @staticmethod
+    def _arrays(pr, what):
+        k = {"p3d": np.ascontiguousarray(pr["p3d"], np.float32).reshape(-1, 3), "p2d": np.ascontiguousarray(pr["p2d"], np.float32).reshape(-1, 2),
+             "max_err": np.ascontiguousarray(pr["max_err"], np.float32).reshape(-1)}
+        n = len(k["max_err"])
+        if len(k["p3d"]) != n or len(k["p2d"]) != n:
+            raise SlamitError("PnPsolver.%s: p3d / p2d / max_err do not have the same length" % what)
+        return k, n
+
+    @staticmethod
+    def ransac(problems, device=0, want_bits=True):
+        """Raw per-hypothesis results of one problem dict (with "quads" (n_hyp, 4)) or a list of them, in ONE device call: dict(s)
+        with pose (n_hyp, 12) float64 = mRi row-major, mti; n_inliers (n_hyp); inlier_bits (n_hyp, (n + 31) // 32)."""
+        single = isinstance(problems, dict)
+        plist = [problems] if single else list(problems)
+        m = len(plist)
+        P, R = (PnpProblem * m)(), (PnpResult * m)()
+        keep, outs = [], []
+        for i, pr in enumerate(plist):
+            k, n = PnPsolver._arrays(pr, "ransac")
+            k["quads"] = np.ascontiguousarray(pr["quads"], np.int32).reshape(-1, 4)
+            nh = len(k["quads"])
+            q = P[i]
+            q.n, q.n_hyp = n, nh
+            for key, a in k.items():
+                setattr(q, key, a.ctypes.data)
+            q.intr = (C.c_double * 4)(*[float(v) for v in pr["intr"]])
+            o = {"pose": np.zeros((nh, 12), np.float64), "n_inliers": np.zeros(nh, np.int32)}
+            R[i].pose, R[i].n_inliers = o["pose"].ctypes.data, o["n_inliers"].ctypes.data
+            if want_bits:
+                o["inlier_bits"] = np.zeros((nh, (n + 31) // 32), np.uint32)
+                R[i].inlier_bits = o["inlier_bits"].ctypes.data
+            keep.append(k)
+            outs.append(o)
+        _check(lib().slamit_pnp_ransac_batch(device, m, P, R), "slamit_pnp_ransac_batch")
+        del keep
+        return outs[0] if single else outs
+
+    @staticmethod
+    def refine(problems, device=0):
+        """Refine() (:268-313) of one problem dict or a list of them in ONE device call.  Each carries "subset_bits" ((n + 31) // 32
+        uint32, e.g. a row of ransac()'s inlier_bits) or "subset" (n bool).  -> dict(s) pose (12) float64, n_inliers, inlier_bits."""
+        single = isinstance(problems, dict)
+        plist = [problems] if single else list(problems)
+        m = len(plist)
+        P, R = (PnpRefineProblem * m)(), (PnpRefineResult * m)()
+        keep, outs = [], []
+        for i, pr in enumerate(plist):
+            k, n = PnPsolver._arrays(pr, "refine")
+            if "subset_bits" in pr:
+                k["subset_bits"] = np.ascontiguousarray(pr["subset_bits"], np.uint32).reshape(-1)
+            else:
+                f = np.zeros(((n + 31) // 32) * 32, np.uint8)
+                f[:n] = np.asarray(pr["subset"], bool).reshape(-1)
+                k["subset_bits"] = np.packbits(f, bitorder="little").view(np.uint32)
+            if len(k["subset_bits"]) != (n + 31) // 32:
+                raise SlamitError("PnPsolver.refine: the subset does not have (n + 31) // 32 words")
+            q = P[i]
+            q.n = n
+            for key, a in k.items():
+                setattr(q, key, a.ctypes.data)
+            q.intr = (C.c_double * 4)(*[float(v) for v in pr["intr"]])
+            o = {"inlier_bits": np.zeros((n + 31) // 32, np.uint32)}
+            R[i].inlier_bits = o["inlier_bits"].ctypes.data
+            keep.append(k)
+            outs.append(o)
+        _check(lib().slamit_pnp_refine_batch(device, m, P, R), "slamit_pnp_refine_batch")
+        for i, o in enumerate(outs):
+            o["pose"], o["n_inliers"] = np.array(R[i].pose, np.float64), int(R[i].n_inliers)
+        del keep
+        return outs[0] if single else outs
+
+    @staticmethod
+    def records(counts, minInliers, best=0):
+        """The hypotheses iterate() records as best (:217-232): the strict prefix maxima among counts >= minInliers."""
+        out = []
+        for h, c in enumerate(counts):
+            if c >= minInliers and c > best:
+                best = int(c)
+                out.append(h)
+        return out
+
+    @staticmethod
+    def EvaluateAll(solvers, device=0):
+        """Everything the next iterate() of every solver can need, in two launches: the hypotheses drawn and not yet evaluated, then
+        Refine() of every hypothesis those scans can record as best (what Tracking::Relocalization costs for all its candidates)."""
+        for s in solvers:
+            if len(s.quads) < s.mRansacMaxIts and s.N >= s.mRansacMinInliers:   # parameters set by the constructor alone: draw now
+                s.quads = np.vstack([s.quads, PnPsolver.sample_quads(s.N, s.mRansacMaxIts - len(s.quads), s.rand_int)])
+        todo = [s for s in solvers if len(s.counts) < len(s.quads)]
+        first = [len(s.counts) for s in todo]
+        for lo in range(0, max([len(s.quads) - f for s, f in zip(todo, first)] + [0]), PNP_MAX_HYP):
+            part = [(s, s.quads[f + lo:f + lo + PNP_MAX_HYP]) for s, f in zip(todo, first) if f + lo < len(s.quads)]
+            res = PnPsolver.ransac([dict(s.problem, quads=q) for s, q in part], device)
+            for (s, _), r in zip(part, res):
+                s.pose, s.counts, s.bits = np.vstack([s.pose, r["pose"]]), np.concatenate([s.counts, r["n_inliers"]]), np.vstack([s.bits, r["inlier_bits"]])
+        jobs = []
+        for s in solvers:
+            for h in PnPsolver.records(s.counts[s.mnIterations:], s.mRansacMinInliers, s.mnBestInliers):
+                if s.mnIterations + h not in s.refined:
+                    jobs.append((s, s.mnIterations + h))
+        if jobs:
+            res = PnPsolver.refine([dict(s.problem, subset_bits=s.bits[h]) for s, h in jobs], device)
+            for (s, h), r in zip(jobs, res):
+                s.refined[h] = r
+
+    def flags(self, bits):
+        b = np.unpackbits(np.ascontiguousarray(bits, np.uint32).view(np.uint8), bitorder="little")[:self.N]
+        return b.astype(bool)
+
+    @staticmethod
+    def Tcw(pose):
+        """[R | t; 0 0 0 1] in float32, converted from the double pose as :225-231 does."""
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = np.asarray(pose[:9], np.float64).reshape(3, 3).astype(np.float32)
+        T[:3, 3] = np.asarray(pose[9:12], np.float64).astype(np.float32)
+        return T
+
+    def iterate(self, nIterations):
+        """-> (Tcw (4, 4) float32 or None, bNoMore, vbInliers (N) bool, nInliers).  self.accepted is the hypothesis whose refined
+        (self.kind == "refined") or own (self.kind == "best", the bNoMore tail) pose was returned."""
+        vb = np.zeros(self.N, bool)
+        self.kind = None
+        if self.N < self.mRansacMinInliers:
+            return None, True, vb, 0
+        need = self.mnIterations + max(self.mRansacMaxIts - self.mnIterations, nIterations)
+        if need > len(self.quads):   # a call after bNoMore (or maxIts < nIterations): its further hypotheses, in a call of their own
+            self.quads = np.vstack([self.quads, self.sample_quads(self.N, need - len(self.quads), self.rand_int)])
+        PnPsolver.EvaluateAll([self], self.device)
+        cur = 0
+        while self.mnIterations < self.mRansacMaxIts or cur < nIterations:
+            cur += 1
+            h = self.mnIterations
+            self.mnIterations += 1
+            if self.counts[h] >= self.mRansacMinInliers:
+                if self.counts[h] > self.mnBestInliers:
+                    self.mnBestInliers, self.best = int(self.counts[h]), h
+                r = self.refined[self.best]           # Refine() on an unchanged best gives the same (failing) answer again
+                if r["n_inliers"] > self.mRansacMinInliers:
+                    self.accepted, self.kind = self.best, "refined"
+                    return self.Tcw(r["pose"]), False, self.flags(r["inlier_bits"]), int(r["n_inliers"])
+        if self.mnIterations >= self.mRansacMaxIts and self.mnBestInliers >= self.mRansacMinInliers:
+            self.accepted, self.kind = self.best, "best"
+            return self.Tcw(self.pose[self.best]), True, self.flags(self.bits[self.best]), self.mnBestInliers
+        return None, self.mnIterations >= self.mRansacMaxIts, vb, 0
+
+    def find(self):
+        T, _, vb, n = self.iterate(self.mRansacMaxIts)
+        return T, vb, n
 
 
 _TRI_STEREO_ARRAYS = ("ur1", "ur2", "depth1", "depth2", "raw1_xy", "raw2_xy")

@@ -13,6 +13,7 @@
 //     shim_test sim3 <problem.bin> <out.bin>
 //     shim_test osim3 <problem.bin> <out.bin>
 //     shim_test sim3solver <problem.bin> <out.bin>
+//     shim_test pnpsolver <problem.bin> <out.bin>
 //     shim_test triangulate <problem.bin> <out.bin>
 //     shim_test triangulate_stereo <problem.bin> <out.bin>
 //     shim_test frustum <problem.bin> <out.bin>
@@ -31,6 +32,7 @@
 #include "ORBmatcher.h"
 #include "Optimizer.h"
 #include "FrameOps.h"
+#include "PnPsolver.h"
 #include "Sim3Solver.h"
 #include "ORBVocabulary.h"
 #include "KeyFrameDatabase.h"
@@ -1344,6 +1346,80 @@ static int run_stereo(int argc, char** argv) {
     return 0;
 }
 
+// ---- PnPsolver through the template: the candidates of one relocalisation, one EvaluateAll (two launches) -------------------------
+// problem.bin: int32 nsolvers nrand ; uint32 rand[nrand] (one RandomInt stream for all solvers in order; the constructors draw
+//   nothing) ; per solver: int32 n lead min_inliers max_its min_set ; float epsilon th2 K[4] p3d[3n] p2d[2n] sigma2[n]
+//   (the frame holds `lead` keypoints without a map point in front of the n matched ones)
+// out.bin: int32 status ; per solver: int32 set_status accepted n_inliers ncalls max_its min_inliers no_more ; float Tcw[16] (zeros
+//   for an empty matrix) ; u8 vbInliers[lead + n] (zeros where iterate() left the vector empty)
+struct MockPnpFrame {
+    float fx, fy, cx, cy;
+    std::vector<cv::KeyPoint> mvKeysUn;
+    std::vector<float> mvLevelSigma2;
+};
+static int run_pnpsolver(int argc, char** argv) {
+    if (argc < 4) return 2;
+    std::vector<unsigned char> raw = slurp(argv[2]);
+    Reader Rd{raw.data()};
+    const int ns = Rd.get<int>(), nrand = Rd.get<int>();
+    { const uint32_t* r = Rd.arr<uint32_t>(nrand); g_script.assign(r, r + nrand); g_script_pos = 0; }
+    pnpsolver::RandomInt() = scripted_random_int;
+    typedef PnPsolver<MockPnpFrame, MockFusePoint> Solver;
+    std::vector<MockPnpFrame> frames(ns);
+    std::vector<std::vector<MockFusePoint> > pts(ns);
+    std::vector<Solver*> solvers;
+    std::vector<int> total(ns), set_status(ns);
+    for (int k = 0; k < ns; ++k) {
+        const int n = Rd.get<int>(), ld = Rd.get<int>(), minInl = Rd.get<int>(), maxIts = Rd.get<int>(), minSet = Rd.get<int>();
+        const float eps = Rd.get<float>(), th2 = Rd.get<float>();
+        const float* K = Rd.arr<float>(4);
+        const float* p3d = Rd.arr<float>(3 * (size_t)n);
+        const float* p2d = Rd.arr<float>(2 * (size_t)n);
+        const float* sg = Rd.arr<float>(n);
+        total[k] = ld + n;
+        MockPnpFrame& F = frames[k];
+        F.fx = K[0]; F.fy = K[1]; F.cx = K[2]; F.cy = K[3];
+        F.mvKeysUn.resize(ld + n); F.mvLevelSigma2.assign(sg, sg + n);
+        pts[k].resize(n);
+        std::vector<MockFusePoint*> vpMapPointMatches(ld + n, (MockFusePoint*)0);
+        for (int i = 0; i < n; ++i) {
+            MockFusePoint& p = pts[k][i];
+            p.id = i; p.pos = mat_from(p3d + 3 * (size_t)i, 3);
+            F.mvKeysUn[ld + i] = cv::KeyPoint(p2d[2 * i], p2d[2 * i + 1], 31.f, -1.f, 0, i);   // one sigma entry per keypoint keeps sigma2 exact
+            vpMapPointMatches[ld + i] = &p;
+        }
+        Solver* s = new Solver(F, vpMapPointMatches);
+        set_status[k] = s->SetRansacParameters(0.99, minInl, maxIts, minSet, eps, th2);   // Tracking.cc:1723
+        solvers.push_back(s);
+    }
+    int status = Solver::EvaluateAll(solvers);   // every candidate: one hypothesis launch, one refine launch
+    if (status != 0) fprintf(stderr, "pnpsolver failed: %s\n", slamit_last_error());
+    FILE* f = fopen(argv[3], "wb");
+    fwrite(&status, 4, 1, f);
+    for (int k = 0; k < ns && status == 0; ++k) {
+        Solver* s = solvers[k];
+        std::vector<bool> vbInliers;
+        int nInliers = 0, ncalls = 0;
+        bool bNoMore = false;
+        cv::Mat T;
+        while (T.empty() && !bNoMore && ncalls < 4) {   // Tracking.cc:1740-1760: iterate(5) until a pose or bNoMore
+            T = s->iterate(5, bNoMore, vbInliers, nInliers);
+            ++ncalls;
+        }
+        const int acc = s->AcceptedHypothesis(), its = s->GetRansacMaxIts(), mi = s->GetRansacMinInliers(), nm = bNoMore ? 1 : 0;
+        fwrite(&set_status[k], 4, 1, f); fwrite(&acc, 4, 1, f); fwrite(&nInliers, 4, 1, f); fwrite(&ncalls, 4, 1, f);
+        fwrite(&its, 4, 1, f); fwrite(&mi, 4, 1, f); fwrite(&nm, 4, 1, f);
+        float t16[16] = {0};
+        if (!T.empty()) for (int i = 0; i < 16; ++i) t16[i] = T.at<float>(i / 4, i % 4);
+        fwrite(t16, 4, 16, f);
+        for (int i = 0; i < total[k]; ++i) { const unsigned char b = i < (int)vbInliers.size() && vbInliers[i] ? 1 : 0; fwrite(&b, 1, 1, f); }
+        printf("solver %d: %s hypothesis %d, %d inliers, %d call(s)\n", k, T.empty() ? "no pose," : "pose from", acc, nInliers, ncalls);
+    }
+    fclose(f);
+    for (size_t k = 0; k < solvers.size(); ++k) delete solvers[k];
+    return status;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     std::string mode = argv[1];
@@ -1360,6 +1436,7 @@ int main(int argc, char** argv) {
     if (mode == "sim3") return run_sim3(argc, argv);
     if (mode == "osim3") return run_osim3(argc, argv);
     if (mode == "sim3solver") return run_sim3solver(argc, argv);
+    if (mode == "pnpsolver") return run_pnpsolver(argc, argv);
     if (mode == "triangulate") return run_triangulate(argc, argv);
     if (mode == "triangulate_stereo") return run_triangulate_stereo(argc, argv);
     if (mode == "frustum") return run_frustum(argc, argv);

@@ -1050,3 +1050,30 @@ def synth_map_hard(synth_map, mirror=None, starve_kf=()):
 
 
 _synth_map_fn = synth_map
+
+
+def synth_pnp(n=200, outlier_frac=0.3, seed=0, noise_px=0.5):
+    """What the PnPsolver constructor gathers for one relocalisation candidate (PnPsolver.cc:67-118): n map points in the world
+    frame (p3d = mvP3Dw, float32) and the undistorted keypoints they were matched to (p2d = mvP2D), under a known pose
+    Xc = R Xw + t.  The points lie in x [-2, 2], y [-1.5, 1.5], z [2, 10] of the camera frame, the rotation angle is 0.1 .. 1 rad
+    and the translation in [-1, 1]^3; the keypoints carry noise_px of Gaussian noise, a share outlier_frac of them lie anywhere in
+    the 640 x 480 image.  Every keypoint sits on an octave 0 .. 7: sigma2 = 1.44^octave and max_err = (float)(sigma2 * 5.991), the
+    bound of mvMaxError.  Layout of slamit_pnp_problem (without quads)."""
+    rs = np.random.RandomState(17000 + seed)
+    f32 = np.float32
+    intr = np.array([500.0, 500.0, 320.0, 240.0], np.float64)
+    Xc = np.stack([rs.uniform(-2, 2, n), rs.uniform(-1.5, 1.5, n), rs.uniform(2, 10, n)], 1)
+    axis = rs.normal(0, 1, 3)
+    axis /= np.linalg.norm(axis)
+    R, _ = se3_exp(np.concatenate([axis * rs.uniform(0.1, 1.0), np.zeros(3)]))
+    t = rs.uniform(-1, 1, 3)
+    Xw = (Xc - t) @ R                                   # R^T (Xc - t)
+    uv = np.stack([intr[0] * Xc[:, 0] / Xc[:, 2] + intr[2], intr[1] * Xc[:, 1] / Xc[:, 2] + intr[3]], 1) + rs.normal(0, noise_px, (n, 2))
+    bad = rs.rand(n) < outlier_frac
+    nb = int(bad.sum())
+    uv[bad] = np.stack([rs.uniform(0, 640, nb), rs.uniform(0, 480, nb)], 1)
+    octave = rs.randint(0, 8, n)
+    sigma2 = (f32(1.44) ** octave.astype(f32)).astype(f32)
+    th2 = f32(5.991)
+    return dict(n=n, p3d=Xw.astype(f32), p2d=uv.astype(f32), sigma2=sigma2, max_err=(sigma2 * th2).astype(f32), intr=intr, th2=float(th2),
+                true=dict(R=R, t=t, bad=bad))
