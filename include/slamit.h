@@ -1138,6 +1138,156 @@ int slamit_stereo_match(slamit_orb* left, slamit_orb* right, int frame, const sl
                         const slamit_kp* kps_right, const uint8_t* desc_right, int n_right, float mb, float mbf, float* u_right, float* depth,
                         uint8_t* status, int32_t* best_r, int32_t* ham_dist, int32_t* sad_dist, int32_t* n_matched);
 
+/* ---- RGB-D depth lookup: Frame::ComputeStereoFromRGBD (src/Frame.cc:766-787) ----------------------------------------
+ * Per keypoint: row = (int)kp.pt.y, column = (int)kp.pt.x of the RAW keypoint (truncation), d = (float)plane[row][column] * factor
+ * in float -- Tracking::GrabImageRGBD (src/Tracking.cc:267-268) converts every depth image with convertTo(CV_32F, mDepthMapFactor),
+ * a float one too -- and, when d > 0, depth = d and u_right = kpU.pt.x - mbf / d from the UNDISTORTED keypoint (float, two
+ * roundings); otherwise both are -1.  csrc/unproject.h restates it.  status[i]: 0 no depth (d <= 0 or NaN), 1 depth, 2 DEPARTURE:
+ * the truncated row or column lies outside the plane, or a coordinate is not finite, where the reference reads out of bounds;
+ * u_right = depth = -1.  n above SLAMIT_STEREO_MAX_KP fails with SLAMIT_ERR_CAPACITY; an unknown element type, a pitch below a
+ * row's bytes, a negative size or a missing array with n > 0 fails with SLAMIT_ERR_ARG; both with a message, before anything is
+ * launched.  n == 0 and nproblems == 0 are valid and write nothing. */
+enum { SLAMIT_DEPTH_F32 = 0, SLAMIT_DEPTH_U16 = 1 };
+
+struct slamit_depth_plane {
+    const void* data;              /* first element of row 0 */
+    size_t pitch;                  /* bytes between rows, >= width * element size */
+    int32_t width, height;
+    int32_t type;                  /* SLAMIT_DEPTH_* */
+    float factor;                  /* mDepthMapFactor: 1 / DepthMapFactor of the settings, 1 when that is 0 */
+};
+typedef struct slamit_depth_plane slamit_depth_plane;
+
+struct slamit_rgbd_problem {
+    slamit_depth_plane plane;      /* host memory */
+    float mbf;                     /* Frame::mbf */
+    int32_t n;
+    const slamit_kp* kps;          /* n: mvKeys (pt is read) */
+    const slamit_kp* kps_un;       /* n: mvKeysUn (pt.x is read) */
+};
+typedef struct slamit_rgbd_problem slamit_rgbd_problem;
+
+struct slamit_rgbd_result {
+    float* u_right;                /* n out: mvuRight */
+    float* depth;                  /* n out: mvDepth */
+    uint8_t* status;               /* n out */
+};
+typedef struct slamit_rgbd_result slamit_rgbd_result;
+
+/* nproblems frames in one launch (host pointers, synchronous; the planes travel without their row padding). */
+int slamit_rgbd_depth_batch(int device, int nproblems, const slamit_rgbd_problem* probs, slamit_rgbd_result* results);
+int slamit_rgbd_depth(int device, const slamit_rgbd_problem* prob, slamit_rgbd_result* res);
+
+/* Everything resident in HBM: the keypoints and counts slamit_orb_extract_batch_dev and slamit_frame_finish_batch_dev left
+ * ([nframes][cap], d_n clamped to [0, cap]), one plane record per frame in device memory whose `data` is a device pointer, and the
+ * outputs in the layout slamit_stereo_match_batch_dev writes.  Entries past a frame's count are neither read nor written.  The host
+ * cannot see d_planes: a type other than SLAMIT_DEPTH_U16 is read as float.  Asynchronous on `stream` (NULL: the legacy default
+ * stream of `device`), no synchronisation, no state. */
+struct slamit_rgbd_batch_rec {
+    int32_t nframes, cap;
+    const slamit_depth_plane* d_planes; /* [nframes] */
+    const float* d_mbf;            /* [nframes] */
+    const slamit_kp* d_kps;        /* [nframes][cap] */
+    const slamit_kp* d_kps_un;     /* [nframes][cap] */
+    const int32_t* d_n;            /* [nframes] */
+    float* d_u_right;              /* [nframes][cap] out */
+    float* d_depth;                /* [nframes][cap] out */
+    uint8_t* d_status;             /* [nframes][cap] out, nullable */
+};
+typedef struct slamit_rgbd_batch_rec slamit_rgbd_batch_rec;
+int slamit_rgbd_depth_batch_dev(int device, const slamit_rgbd_batch_rec* batch, void* stream);
+
+/* ---- Closest points: the walk of UpdateLastFrame, CreateNewKeyFrame and StereoInitialization -----------------------
+ * Tracking::UpdateLastFrame (src/Tracking.cc:1039-1091), the stereo branch of CreateNewKeyFrame (:1334-1396) and
+ * StereoInitialization (:712-727) with Frame::UnprojectStereo (src/Frame.cc:789-803) and what the new MapPoint stores
+ * (src/MapPoint.cc:52-77, :336-377); float / double exactly where the reference has them (csrc/unproject.h lists every split).
+ * The candidates are the keypoints with depth > 0 (a NaN is none, +inf is one), sorted by (depth, index).  Mode CLOSEST visits the
+ * first n_visited = min(M, max(c, min_points) + 1) of them, M candidates of which c have !(depth > th_depth): the reference's loop,
+ * which takes one far point beyond the close set whenever there is one.  Mode ALL visits every candidate in index order and does
+ * not look at `tracked`, which may then be NULL.  status[i]:
+ *   0 no depth   1 beyond the cut   2 visited, keeps its tracked point (tracked[i] != 0)   3 visited, point created
+ *   4 DEPARTURE: visited and in need of a point, but the octave lies outside [0, n_levels), where the reference indexes
+ *     mvScaleFactors unchecked; it counts in the walk and nothing is created
+ * order[j] is the keypoint at walk position j < n_visited (-1 from there to n): creating the points in this order gives them the
+ * reference's mnId.  pos, normal, max_dist (the RAW mfMaxDistance), min_dist are written for status 3 and are zero elsewhere.
+ * ctor says which constructor's normal is wanted: they differ in the sign of a zero component only (csrc/unproject.h).
+ * counts: n_candidates = M, n_close = c, n_visited, n_created, and NeedNewKeyFrame's two numbers (src/Tracking.cc:1244-1253):
+ * n_total = keypoints with 0 < depth < th_depth (strict, unlike the cut), n_map = those of them with tracked[i] != 0.
+ * n above SLAMIT_STEREO_MAX_KP fails with SLAMIT_ERR_CAPACITY; n_levels outside [1, SLAMIT_MAX_LEVELS], an unknown mode or ctor,
+ * min_points < 0 or a missing array with n > 0 fails with SLAMIT_ERR_ARG; both with a message, before anything is launched.
+ * n == 0 and nproblems == 0 are valid and write nothing but zero counts. */
+enum { SLAMIT_UNPROJECT_CLOSEST = 0, SLAMIT_UNPROJECT_ALL = 1 };
+enum { SLAMIT_UNPROJECT_CTOR_FRAME = 0, SLAMIT_UNPROJECT_CTOR_KEYFRAME = 1 };
+
+struct slamit_unproject_frame {
+    float fx, fy, cx, cy, invfx, invfy; /* as the frame holds them */
+    float Rwc[9], Ow[3];           /* mRwc (row-major), mOw */
+    float th_depth;                /* mThDepth */
+    int32_t min_points;            /* 100 in both callers */
+    int32_t mode;                  /* SLAMIT_UNPROJECT_CLOSEST / _ALL */
+    int32_t ctor;                  /* SLAMIT_UNPROJECT_CTOR_FRAME (UpdateLastFrame) / _KEYFRAME (the other two) */
+    int32_t n_levels;              /* entries of scale_factors in use */
+    float scale_factors[SLAMIT_MAX_LEVELS]; /* mvScaleFactors */
+};
+typedef struct slamit_unproject_frame slamit_unproject_frame;
+
+struct slamit_unproject_counts {
+    int32_t n_candidates, n_close, n_visited, n_created, n_total, n_map;
+};
+typedef struct slamit_unproject_counts slamit_unproject_counts;
+
+struct slamit_unproject_problem {
+    slamit_unproject_frame frame;
+    int32_t n;
+    const slamit_kp* kps_un;       /* n: mvKeysUn (pt and octave are read) */
+    const float* depth;            /* n: mvDepth */
+    const uint8_t* tracked;        /* n: 1 = mvpMapPoints[i] is non-null with Observations() >= 1 */
+};
+typedef struct slamit_unproject_problem slamit_unproject_problem;
+
+struct slamit_unproject_result {
+    uint8_t* status;               /* n out */
+    int32_t* order;                /* n out */
+    float* pos;                    /* n x 3 out */
+    float* normal;                 /* n x 3 out */
+    float* max_dist;               /* n out */
+    float* min_dist;               /* n out */
+    slamit_unproject_counts counts; /* out */
+};
+typedef struct slamit_unproject_result slamit_unproject_result;
+
+/* nproblems frames in one launch (host pointers, synchronous). */
+int slamit_unproject_closest_batch(int device, int nproblems, const slamit_unproject_problem* probs, slamit_unproject_result* results);
+int slamit_unproject_closest(int device, const slamit_unproject_problem* prob, slamit_unproject_result* res);
+
+/* Everything resident in HBM, MERGED IN PLACE into the arrays slamit_project_batch_dev form 0 reads (q_cap = cap: query i is the
+ * last frame's keypoint i).  The caller has filled the tracked points and set skip = 1 where there is none; for a created point
+ * (status 3) this writes d_pos[f][c][i], d_octave[f][i], d_skip[f][i] = 0 and, where present, d_normal / d_max_dist / d_min_dist
+ * in slamit_frustum_batch_dev's layout; every other entry of those arrays is left alone.  d_status, d_order ([nframes][cap]) and
+ * d_counts ([nframes]) are written in full for the first min(d_n[f], cap) entries when present.  The host cannot see d_frames: an
+ * octave is accepted only below min(n_levels, SLAMIT_MAX_LEVELS), a mode other than ALL is CLOSEST.  Asynchronous on `stream`
+ * (NULL: the legacy default stream of `device`), no synchronisation, no state: UpdateLastFrame, slamit_project_batch_dev_stereo,
+ * slamit_guided_search_stereo_batch_dev and slamit_rotation_check_batch_dev run on one stream without the host. */
+struct slamit_unproject_batch_rec {
+    int32_t nframes, cap;
+    const slamit_unproject_frame* d_frames; /* [nframes] */
+    const int32_t* d_n;            /* [nframes] keypoints per frame */
+    const slamit_kp* d_kps_un;     /* [nframes][cap] */
+    const float* d_depth;          /* [nframes][cap] */
+    const uint8_t* d_tracked;      /* [nframes][cap] */
+    float* d_pos;                  /* [nframes][3][cap] in / out */
+    int32_t* d_octave;             /* [nframes][cap] in / out */
+    uint8_t* d_skip;               /* [nframes][cap] in / out */
+    float* d_normal;               /* [nframes][3][cap] in / out, nullable */
+    float* d_max_dist;             /* [nframes][cap] in / out, nullable */
+    float* d_min_dist;             /* [nframes][cap] in / out, nullable */
+    uint8_t* d_status;             /* [nframes][cap] out, nullable */
+    int32_t* d_order;              /* [nframes][cap] out, nullable */
+    slamit_unproject_counts* d_counts; /* [nframes] out, nullable */
+};
+typedef struct slamit_unproject_batch_rec slamit_unproject_batch_rec;
+int slamit_unproject_closest_batch_dev(int device, const slamit_unproject_batch_rec* batch, void* stream);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 
 const char* slamit_last_error(void);

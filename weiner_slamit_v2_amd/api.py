@@ -253,6 +253,61 @@ STEREO_MAX_KP = 8191   # SLAMIT_STEREO_MAX_KP
 STEREO_STATUS = ("matched", "no_candidate", "no_descriptor", "right_window", "edge_shift", "delta", "disparity", "median", "departure")
 
 
+class DepthPlane(C.Structure):   # slamit_depth_plane
+    _fields_ = [("data", C.c_void_p), ("pitch", C.c_size_t), ("width", C.c_int32), ("height", C.c_int32), ("type", C.c_int32), ("factor", C.c_float)]
+
+
+class RgbdProblem(C.Structure):
+    _fields_ = [("plane", DepthPlane), ("mbf", C.c_float), ("n", C.c_int32), ("kps", C.c_void_p), ("kps_un", C.c_void_p)]
+
+
+class RgbdResult(C.Structure):
+    _fields_ = [("u_right", C.c_void_p), ("depth", C.c_void_p), ("status", C.c_void_p)]
+
+
+class RgbdBatchRec(C.Structure):
+    _fields_ = [("nframes", C.c_int32), ("cap", C.c_int32), ("d_planes", C.c_void_p), ("d_mbf", C.c_void_p), ("d_kps", C.c_void_p),
+                ("d_kps_un", C.c_void_p), ("d_n", C.c_void_p), ("d_u_right", C.c_void_p), ("d_depth", C.c_void_p), ("d_status", C.c_void_p)]
+
+
+class UnprojectFrame(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float),
+                ("Rwc", C.c_float * 9), ("Ow", C.c_float * 3), ("th_depth", C.c_float), ("min_points", C.c_int32), ("mode", C.c_int32),
+                ("ctor", C.c_int32), ("n_levels", C.c_int32), ("scale_factors", C.c_float * 16)]
+
+
+class UnprojectCounts(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_candidates", "n_close", "n_visited", "n_created", "n_total", "n_map")]
+
+
+class UnprojectProblem(C.Structure):
+    _fields_ = [("frame", UnprojectFrame), ("n", C.c_int32), ("kps_un", C.c_void_p), ("depth", C.c_void_p), ("tracked", C.c_void_p)]
+
+
+class UnprojectResult(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("order", C.c_void_p), ("pos", C.c_void_p), ("normal", C.c_void_p), ("max_dist", C.c_void_p),
+                ("min_dist", C.c_void_p), ("counts", UnprojectCounts)]
+
+
+class UnprojectBatchRec(C.Structure):
+    _fields_ = [("nframes", C.c_int32), ("cap", C.c_int32), ("d_frames", C.c_void_p), ("d_n", C.c_void_p), ("d_kps_un", C.c_void_p),
+                ("d_depth", C.c_void_p), ("d_tracked", C.c_void_p), ("d_pos", C.c_void_p), ("d_octave", C.c_void_p), ("d_skip", C.c_void_p),
+                ("d_normal", C.c_void_p), ("d_max_dist", C.c_void_p), ("d_min_dist", C.c_void_p), ("d_status", C.c_void_p), ("d_order", C.c_void_p),
+                ("d_counts", C.c_void_p)]
+
+
+DEPTH_TYPES = ("f32", "u16")   # SLAMIT_DEPTH_*: the index is the type
+DEPTH_PLANE_DTYPE = np.dtype([("data", "<u8"), ("pitch", "<u8"), ("width", "<i4"), ("height", "<i4"), ("type", "<i4"), ("factor", "<f4")])   # slamit_depth_plane
+RGBD_STATUS = ("no_depth", "depth", "outside")
+UNPROJECT_MODES = ("CLOSEST", "ALL")   # SLAMIT_UNPROJECT_*
+UNPROJECT_CTORS = ("FRAME", "KEYFRAME")   # SLAMIT_UNPROJECT_CTOR_*
+UNPROJECT_STATUS = ("no_depth", "beyond", "tracked", "created", "octave")
+UNPROJECT_COUNTS = ("n_candidates", "n_close", "n_visited", "n_created", "n_total", "n_map")   # slamit_unproject_counts
+UNPROJECT_FRAME_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("invfx", "<f4"), ("invfy", "<f4"), ("Rwc", "<f4", 9),
+                                  ("Ow", "<f4", 3), ("th_depth", "<f4"), ("min_points", "<i4"), ("mode", "<i4"), ("ctor", "<i4"), ("n_levels", "<i4"),
+                                  ("scale_factors", "<f4", 16)])   # slamit_unproject_frame
+
+
 PROJECT_MAX_N = 65536   # SLAMIT_PROJECT_MAX_N
 PROJECT_FORMS = ("LAST_FRAME", "RELOC", "FUSE", "SIM3_PROJ", "SIM3_FUSE", "SIM3_PAIR")   # SLAMIT_PROJECT_*: the index is the form
 PROJECT_CAMERA_DTYPE = np.dtype([("form", "<i4"), ("R", "<f4", 9), ("t", "<f4", 3), ("O", "<f4", 3), ("R2", "<f4", 9), ("t2", "<f4", 3), ("fx", "<f4"),
@@ -312,7 +367,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -385,6 +440,12 @@ def lib():
         L.slamit_stereo_match_workspace.restype = sz
         L.slamit_stereo_match_batch_dev.argtypes = [i32, C.POINTER(StereoBatch), vp]
         L.slamit_stereo_match.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, i32, f32, f32] + [vp] * 7
+        L.slamit_rgbd_depth_batch.argtypes = [i32, i32, C.POINTER(RgbdProblem), C.POINTER(RgbdResult)]
+        L.slamit_rgbd_depth.argtypes = [i32, C.POINTER(RgbdProblem), C.POINTER(RgbdResult)]
+        L.slamit_rgbd_depth_batch_dev.argtypes = [i32, C.POINTER(RgbdBatchRec), vp]
+        L.slamit_unproject_closest_batch.argtypes = [i32, i32, C.POINTER(UnprojectProblem), C.POINTER(UnprojectResult)]
+        L.slamit_unproject_closest.argtypes = [i32, C.POINTER(UnprojectProblem), C.POINTER(UnprojectResult)]
+        L.slamit_unproject_closest_batch_dev.argtypes = [i32, C.POINTER(UnprojectBatchRec), vp]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_bow_search_stereo.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), C.POINTER(BowStereo), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
@@ -2038,3 +2099,158 @@ def stereo_match_batch_dev(t, device=0, stream=None):
                       ws.numel() * ws.element_size() if ws is not None else 0, t["u_right"].data_ptr(), t["depth"].data_ptr(), t["status"].data_ptr(),
                       t["best_r"].data_ptr(), t["ham_dist"].data_ptr(), t["sad_dist"].data_ptr(), t["n_matched"].data_ptr())
     _check(lib().slamit_stereo_match_batch_dev(device, C.byref(rec), stream), "slamit_stereo_match_batch_dev")
+
+
+# ---- Frame::ComputeStereoFromRGBD and the closest-point walk (csrc/unproject.h) ------------------------------
+
+def rgbd_depth_batch(problems, device=0):
+    """Frame::ComputeStereoFromRGBD (Frame.cc:766-787) for a list of frames in ONE device call.  Each problem is a dict
+    (synth.synth_rgbd): plane, a 2-D numpy array of uint16 or float32 whose rows may be strided (a view of a wider array), factor
+    (mDepthMapFactor), mbf, kps and kps_un (KP_DTYPE).  -> a list of dicts u_right, depth (mvuRight, mvDepth) float32 and status uint8
+    (RGBD_STATUS: 2 = the truncated row or column lies outside the plane, the stated departure)."""
+    plist = list(problems)
+    m = len(plist)
+    P = (RgbdProblem * max(m, 1))()
+    R = (RgbdResult * max(m, 1))()
+    keep, outs = [], []
+    for i, pr in enumerate(plist):
+        plane = pr["plane"]
+        if plane.ndim != 2 or plane.dtype not in (np.uint16, np.float32) or (plane.shape[1] > 1 and plane.strides[1] != plane.itemsize):
+            raise SlamitError("rgbd_depth: plane is not a 2-D uint16 / float32 array with adjacent pixels")
+        k = {"kps": np.ascontiguousarray(pr["kps"], KP_DTYPE), "kps_un": np.ascontiguousarray(pr["kps_un"], KP_DTYPE)}
+        n = len(k["kps"])
+        if len(k["kps_un"]) != n:
+            raise SlamitError("rgbd_depth: kps and kps_un do not have the same length")
+        P[i].plane = DepthPlane(plane.ctypes.data, plane.strides[0] if plane.shape[0] > 1 else plane.shape[1] * plane.itemsize, plane.shape[1],
+                                plane.shape[0], 1 if plane.dtype == np.uint16 else 0, float(pr["factor"]))
+        P[i].mbf, P[i].n, P[i].kps, P[i].kps_un = float(pr["mbf"]), n, k["kps"].ctypes.data, k["kps_un"].ctypes.data
+        o = {"u_right": np.zeros(n, np.float32), "depth": np.zeros(n, np.float32), "status": np.zeros(n, np.uint8)}
+        for key, a in o.items():
+            setattr(R[i], key, a.ctypes.data)
+        keep.append((k, plane))
+        outs.append(o)
+    _check(lib().slamit_rgbd_depth_batch(device, m, P, R), "slamit_rgbd_depth_batch")
+    del keep
+    return outs
+
+
+def rgbd_depth(problem, device=0):
+    """One frame: rgbd_depth_batch([problem])[0]."""
+    return rgbd_depth_batch([problem], device)[0]
+
+
+def rgbd_depth_batch_dev(t, device=0, stream=None):
+    """The resident form.  t: dict of torch CUDA tensors planes (B, 8) i32 (rows of DEPTH_PLANE_DTYPE viewed as int32; data is a
+    device pointer), mbf (B) f32, kps / kps_un (B, cap, 7) f32 rows of KP_DTYPE, n (B) i32 and the outputs u_right / depth (B, cap)
+    f32, optionally status (B, cap) u8.  Asynchronous on `stream`."""
+    b, cap = t["n"].numel(), t["kps"].shape[1]
+    if t["planes"].numel() * t["planes"].element_size() != b * C.sizeof(DepthPlane):
+        raise SlamitError("rgbd_depth_batch_dev: planes does not hold one slamit_depth_plane per frame")
+    for key in ("kps", "kps_un"):
+        if t[key].numel() * t[key].element_size() != b * cap * KP_DTYPE.itemsize or not t[key].is_contiguous():
+            raise SlamitError("rgbd_depth_batch_dev: %s is not a contiguous (B, cap) keypoint array" % key)
+    for key in ("u_right", "depth", "status"):
+        if t.get(key) is not None and (t[key].numel() != b * cap or not t[key].is_contiguous()):
+            raise SlamitError("rgbd_depth_batch_dev: %s is not a contiguous (B, cap) array" % key)
+    if t["mbf"].numel() != b:
+        raise SlamitError("rgbd_depth_batch_dev: mbf does not have one entry per frame")
+    rec = RgbdBatchRec(b, cap, t["planes"].data_ptr(), t["mbf"].data_ptr(), t["kps"].data_ptr(), t["kps_un"].data_ptr(), t["n"].data_ptr(),
+                       t["u_right"].data_ptr(), t["depth"].data_ptr(), t["status"].data_ptr() if t.get("status") is not None else None)
+    _check(lib().slamit_rgbd_depth_batch_dev(device, C.byref(rec), stream), "slamit_rgbd_depth_batch_dev")
+
+
+_UNPROJECT_SCALARS = ("fx", "fy", "cx", "cy", "invfx", "invfy", "th_depth")
+
+
+def unproject_frame_record(pr):
+    """The slamit_unproject_frame of a problem dict as a one-element numpy record array (UNPROJECT_FRAME_DTYPE): what
+    unproject_closest_batch_dev's d_frames holds per frame.  mode / ctor are indices into UNPROJECT_MODES / UNPROJECT_CTORS or names."""
+    rec = np.zeros(1, UNPROJECT_FRAME_DTYPE)
+    for key, k in (("Rwc", 9), ("Ow", 3)):
+        a = np.asarray(pr[key], np.float32).reshape(-1)
+        if len(a) != k:
+            raise SlamitError("unproject: %s has %d entries" % (key, len(a)))
+        rec[key][0] = a
+    for key in _UNPROJECT_SCALARS:
+        rec[key][0] = np.float32(pr[key])
+    mode, ctor = pr.get("mode", 0), pr.get("ctor", 0)
+    rec["mode"][0] = UNPROJECT_MODES.index(mode) if isinstance(mode, str) else int(mode)
+    rec["ctor"][0] = UNPROJECT_CTORS.index(ctor) if isinstance(ctor, str) else int(ctor)
+    rec["min_points"][0] = int(pr.get("min_points", 100))
+    sf = np.asarray(pr["scale_factors"], np.float32).reshape(-1)
+    nl = int(pr["n_levels"])
+    if 1 <= nl <= 16 and len(sf) != nl:   # an n_levels outside the table goes to the library, which refuses it
+        raise SlamitError("unproject: scale_factors does not have n_levels entries")
+    rec["n_levels"][0] = nl
+    rec["scale_factors"][0, :min(len(sf), 16)] = sf[:16]
+    return rec
+
+
+def unproject_closest_batch(problems, device=0):
+    """The closest-point walk of Tracking::UpdateLastFrame / CreateNewKeyFrame / StereoInitialization with Frame::UnprojectStereo and
+    the new points' constructor (csrc/unproject.h) for a list of frames in ONE device call.  Each problem is a
+    dict in the layout of slamit_unproject_problem (synth.synth_unproject): the frame's fields (unproject_frame_record), kps_un
+    (KP_DTYPE), depth (n) float32, tracked (n) uint8 (None in mode ALL).  -> a list of dicts: status (n) uint8 (UNPROJECT_STATUS),
+    order (n) int32 (the keypoint at walk position j, -1 from n_visited on), pos, normal (n, 3), max_dist, min_dist (n) float32 --
+    written for status 3, zero elsewhere -- and the six counters of UNPROJECT_COUNTS."""
+    plist = list(problems)
+    m = len(plist)
+    P = (UnprojectProblem * max(m, 1))()
+    R = (UnprojectResult * max(m, 1))()
+    keep, outs = [], []
+    for i, pr in enumerate(plist):
+        k = {"kps_un": np.ascontiguousarray(pr["kps_un"], KP_DTYPE), "depth": np.ascontiguousarray(pr["depth"], np.float32).reshape(-1)}
+        if pr.get("tracked") is not None:
+            k["tracked"] = np.ascontiguousarray(pr["tracked"], np.uint8).reshape(-1)
+        n = len(k["depth"])
+        if any(len(a) != n for a in k.values()):
+            raise SlamitError("unproject: kps_un / depth / tracked do not have the same length")
+        rec = unproject_frame_record(pr)
+        C.memmove(C.byref(P[i].frame), rec.ctypes.data, C.sizeof(UnprojectFrame))
+        P[i].n = n
+        for key, a in k.items():
+            setattr(P[i], key, a.ctypes.data)
+        o = {"status": np.zeros(n, np.uint8), "order": np.zeros(n, np.int32), "pos": np.zeros((n, 3), np.float32), "normal": np.zeros((n, 3), np.float32),
+             "max_dist": np.zeros(n, np.float32), "min_dist": np.zeros(n, np.float32)}
+        for key, a in o.items():
+            setattr(R[i], key, a.ctypes.data)
+        keep.append(k)
+        outs.append(o)
+    _check(lib().slamit_unproject_closest_batch(device, m, P, R), "slamit_unproject_closest_batch")
+    del keep
+    for i, o in enumerate(outs):
+        for key in UNPROJECT_COUNTS:
+            o[key] = int(getattr(R[i].counts, key))
+    return outs
+
+
+def unproject_closest(problem, device=0):
+    """One frame: unproject_closest_batch([problem])[0]."""
+    return unproject_closest_batch([problem], device)[0]
+
+
+def unproject_closest_batch_dev(t, device=0, stream=None):
+    """The resident form, merged in place into project_batch_dev's LAST_FRAME arrays.  t: dict of torch CUDA tensors frames (B, 39)
+    f32 (rows of UNPROJECT_FRAME_DTYPE viewed as float32), n (B) i32, kps_un (B, cap, 7) f32 rows of KP_DTYPE, depth (B, cap) f32,
+    tracked (B, cap) u8 and, in / out, pos (B, 3, cap) f32 PLANES, octave (B, cap) i32, skip (B, cap) u8, optionally normal
+    (B, 3, cap), max_dist, min_dist (B, cap) f32 -- written only where a point is created -- plus the optional outputs status (B, cap)
+    u8, order (B, cap) i32, counts (B, 6) i32.  Asynchronous on `stream`."""
+    b, cap = t["pos"].shape[0], t["pos"].shape[2]
+    if t["frames"].numel() * t["frames"].element_size() != b * C.sizeof(UnprojectFrame):
+        raise SlamitError("unproject_closest_batch_dev: frames does not hold one slamit_unproject_frame per frame")
+    if t["kps_un"].numel() * t["kps_un"].element_size() != b * cap * KP_DTYPE.itemsize or not t["kps_un"].is_contiguous():
+        raise SlamitError("unproject_closest_batch_dev: kps_un is not a contiguous (B, cap) keypoint array")
+    for key, per in (("depth", 1), ("tracked", 1), ("pos", 3), ("octave", 1), ("skip", 1), ("normal", 3), ("max_dist", 1), ("min_dist", 1), ("status", 1),
+                     ("order", 1)):
+        if t.get(key) is not None and (t[key].numel() != b * cap * per or not t[key].is_contiguous()):
+            raise SlamitError("unproject_closest_batch_dev: %s is not a contiguous (B, cap) array" % key)
+    if t["n"].numel() != b or (t.get("counts") is not None and t["counts"].numel() != 6 * b):
+        raise SlamitError("unproject_closest_batch_dev: n / counts do not have one entry per frame")
+
+    def opt(key):
+        return t[key].data_ptr() if t.get(key) is not None else None
+
+    rec = UnprojectBatchRec(b, cap, t["frames"].data_ptr(), t["n"].data_ptr(), t["kps_un"].data_ptr(), t["depth"].data_ptr(), t["tracked"].data_ptr(),
+                            t["pos"].data_ptr(), t["octave"].data_ptr(), t["skip"].data_ptr(), opt("normal"), opt("max_dist"), opt("min_dist"),
+                            opt("status"), opt("order"), opt("counts"))
+    _check(lib().slamit_unproject_closest_batch_dev(device, C.byref(rec), stream), "slamit_unproject_closest_batch_dev")

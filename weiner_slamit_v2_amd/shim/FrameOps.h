@@ -18,6 +18,15 @@
 // It reads mvKeys, mvKeysRight, mDescriptors, mDescriptorsRight, mb, mbf and the two extractors (mpORBextractorLeft / Right, the
 // shim's, whose last calls left both pyramids in HBM: no SetPyramidExport) and writes mvuRight and mvDepth.  include/slamit.h lists
 // where the device walk departs from the reference (status 8: out-of-range octaves, rows and windows the reference reads anyway).
+//
+// Frame::ComputeStereoFromRGBD (:766-787) forwards the same way:
+//
+//     void Frame::ComputeStereoFromRGBD(const cv::Mat& imDepth) { ORB_SLAM2::FrameOps::ComputeStereoFromRGBD(*this, imDepth); }
+//
+// It reads mvKeys, mvKeysUn and mbf and writes mvuRight and mvDepth in one staged device call (csrc/unproject.h).  imDepth is the
+// CV_32F image Tracking::GrabImageRGBD converted (factor 1), or the sensor's own 16-bit image with depthMapFactor = mDepthMapFactor,
+// which saves the convertTo: the device multiplies as it reads.  A Frame type without mbf, mvDepth and mvKeys is refused on stderr
+// with LastStatus() == SLAMIT_ERR_ARG, as the other stereo paths are chosen by the members the caller's type has.
 #ifndef SLAMIT_SHIM_FRAMEOPS_H
 #define SLAMIT_SHIM_FRAMEOPS_H
 
@@ -121,6 +130,46 @@ void ComputeStereoMatches(FrameT& F, std::vector<uint8_t>* status = 0) {
     F.mvuRight.swap(u);
     F.mvDepth.swap(d);
     if (status) status->swap(st);
+}
+
+// Frame::ComputeStereoFromRGBD.  A failure leaves every keypoint without depth (-1) and its code in LastStatus(); `status`
+// (optional) receives the per-keypoint codes of include/slamit.h (2 = the truncated pixel lies outside the image, the departure).
+template <class FrameT>
+void ComputeStereoFromRGBD(FrameT& F, const cv::Mat& imDepth, float depthMapFactor, std::vector<uint8_t>* status, shim::bool_tag<true>) {
+    static_assert(sizeof(cv::KeyPoint) == sizeof(slamit_kp), "cv::KeyPoint must be the 28-byte record");
+    const int n = (int)F.mvKeys.size();
+    F.mvuRight.assign(n, -1.0f);
+    F.mvDepth.assign(n, -1.0f);
+    if (status) status->assign(n, 0);
+    lastStatus() = SLAMIT_OK;
+    if (n == 0) return;
+    if ((int)F.mvKeysUn.size() != n) { shim::refuse<Status>("FrameOps::ComputeStereoFromRGBD: mvKeysUn does not have one entry per keypoint"); return; }
+    slamit_rgbd_problem P;
+    P.plane.data = imDepth.data; P.plane.pitch = imDepth.step; P.plane.width = imDepth.cols; P.plane.height = imDepth.rows;
+    if (imDepth.type() == CV_32F) P.plane.type = SLAMIT_DEPTH_F32;
+    else if (imDepth.elemSize() == 2) P.plane.type = SLAMIT_DEPTH_U16;
+    else { shim::refuse<Status>("FrameOps::ComputeStereoFromRGBD: the depth image is neither CV_32F nor 16-bit"); return; }
+    P.plane.factor = depthMapFactor;
+    P.mbf = F.mbf; P.n = n;
+    P.kps = reinterpret_cast<const slamit_kp*>(F.mvKeys.data()); P.kps_un = reinterpret_cast<const slamit_kp*>(F.mvKeysUn.data());
+    std::vector<float> u(n), d(n);
+    std::vector<uint8_t> st(n);
+    slamit_rgbd_result R;
+    R.u_right = u.data(); R.depth = d.data(); R.status = st.data();
+    const int rc = slamit_rgbd_depth(0, &P, &R);
+    if (rc != SLAMIT_OK) { shim::report<Status>("slamit_rgbd_depth", rc); return; }
+    F.mvuRight.swap(u);
+    F.mvDepth.swap(d);
+    if (status) status->swap(st);
+}
+template <class FrameT>
+void ComputeStereoFromRGBD(FrameT&, const cv::Mat&, float, std::vector<uint8_t>*, shim::bool_tag<false>) {
+    shim::refuse<Status>("FrameOps::ComputeStereoFromRGBD: the Frame type has no mbf / mvDepth / mvKeys");
+}
+template <class FrameT>
+void ComputeStereoFromRGBD(FrameT& F, const cv::Mat& imDepth, float depthMapFactor = 1.0f, std::vector<uint8_t>* status = 0) {
+    ComputeStereoFromRGBD(F, imDepth, depthMapFactor, status,
+                          shim::bool_tag<shim::has_member_mbf<FrameT>::value && shim::has_member_mvDepth<FrameT>::value && shim::has_member_mvKeys<FrameT>::value>());
 }
 
 }  // namespace FrameOps

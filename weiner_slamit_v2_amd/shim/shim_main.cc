@@ -18,6 +18,7 @@
 //     shim_test triangulate_stereo <problem.bin> <out.bin>
 //     shim_test frustum <problem.bin> <out.bin>
 //     shim_test stereo <pair.bin> <out.bin>
+//     shim_test unproject <problem.bin> <out.bin>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1420,6 +1421,135 @@ static int run_pnpsolver(int argc, char** argv) {
     return status;
 }
 
+// ---- the closest-point walks of a stereo / RGB-D frame through Tracking.h, and ComputeStereoFromRGBD through FrameOps.h -----------
+static int g_unp_seq = 0;
+struct MockDepthKF;
+struct MockDepthPoint {
+    int id, nobs, seq[5];   // seq: the order of AddObservation, KeyFrame::AddMapPoint, ComputeDistinctiveDescriptors, UpdateNormalAndDepth, Map::AddMapPoint
+    float pos[3], normal[3], maxd, mind;
+    MockDepthPoint() : id(-1), nobs(0), maxd(0.f), mind(0.f) { for (int k = 0; k < 5; ++k) seq[k] = -1; }
+    int Observations() { return nobs; }
+    void AddObservation(MockDepthKF*, size_t) { ++nobs; seq[0] = g_unp_seq++; }
+    void ComputeDistinctiveDescriptors() { seq[2] = g_unp_seq++; }
+    void UpdateNormalAndDepth() { seq[3] = g_unp_seq++; }
+};
+struct MockDepthKF {
+    std::vector<MockDepthPoint*> pts;
+    void AddMapPoint(MockDepthPoint* p, size_t i) { pts[i] = p; p->seq[1] = g_unp_seq++; }
+};
+struct MockDepthMap {
+    std::vector<MockDepthPoint*> pts;
+    void AddMapPoint(MockDepthPoint* p) { pts.push_back(p); p->seq[4] = g_unp_seq++; }
+};
+struct MockDepthFrame {
+    std::vector<cv::KeyPoint> mvKeys, mvKeysUn;
+    std::vector<float> mvuRight, mvDepth, mvScaleFactors;
+    std::vector<MockDepthPoint*> mvpMapPoints;
+    cv::Mat mRwc, mOw;
+    float fx, fy, cx, cy, invfx, invfy, mbf;
+};
+struct MockMonoFrame {   // no mbf, no mvDepth: FrameOps::ComputeStereoFromRGBD refuses it
+    std::vector<cv::KeyPoint> mvKeys, mvKeysUn;
+    std::vector<float> mvuRight;
+};
+
+// problem.bin: int32 variant ;
+//   variant 0 UpdateLastFrame, 1 CreateNewKeyFramePoints, 2 StereoInitializationPoints: int32 n ; slamit_unproject_frame ;
+//     cv::KeyPoint kps_un[n] ; float depth[n] ; u8 state[n] (0 no point, 1 a point with observations, 2 a point without)
+//   out.bin: int32 status made close_ok nmap ntotal ; int32 counts[6] ; int32 ncreated ; per created point, in the order of creation:
+//     int32 id keypoint seq[5], float pos[3] normal[3] maxd mind ; per keypoint int32 owner (-1 none, -2 / -3 the frame's own point
+//     with / without observations, else the new point's id) ; int32 temporal size, keyframe points, map points
+//   variant 3 ComputeStereoFromRGBD: int32 n w h type ; float factor mbf ; cv::KeyPoint kps[n] kps_un[n] ; float plane[w h]
+//   out.bin: int32 status refused_status ; float mvuRight[n] mvDepth[n] ; u8 status[n]
+static int run_unproject(int argc, char** argv) {
+    if (argc < 4) return 2;
+    std::vector<unsigned char> raw = slurp(argv[2]);
+    Reader R{raw.data()};
+    const int variant = R.get<int>();
+    FILE* f = fopen(argv[3], "wb");
+    if (!f) return 2;
+    if (variant == 3) {
+        const int n = R.get<int>(), w = R.get<int>(), h = R.get<int>(), type = R.get<int>();
+        const float factor = R.get<float>();
+        MockDepthFrame F;
+        F.mbf = R.get<float>();
+        const cv::KeyPoint* kps = R.arr<cv::KeyPoint>(n); const cv::KeyPoint* kun = R.arr<cv::KeyPoint>(n);
+        if (type != 0) return 2;   // cvlite holds bytes and floats
+        cv::Mat im(h, w, CV_32F, (void*)R.arr<float>((size_t)w * h));
+        F.mvKeys.assign(kps, kps + n); F.mvKeysUn.assign(kun, kun + n);
+        std::vector<uint8_t> st;
+        FrameOps::ComputeStereoFromRGBD(F, im, factor, &st);
+        const int status = FrameOps::LastStatus();
+        if (status != 0) fprintf(stderr, "rgbd failed: %s\n", slamit_last_error());
+        MockMonoFrame M;
+        M.mvKeys = F.mvKeys; M.mvKeysUn = F.mvKeysUn;
+        FrameOps::ComputeStereoFromRGBD(M, im);
+        const int refused = FrameOps::LastStatus();
+        fwrite(&status, 4, 1, f); fwrite(&refused, 4, 1, f);
+        fwrite(F.mvuRight.data(), 4, n, f); fwrite(F.mvDepth.data(), 4, n, f); fwrite(st.data(), 1, n, f);
+        fclose(f);
+        return 0;
+    }
+    const int n = R.get<int>();
+    const slamit_unproject_frame fr = R.get<slamit_unproject_frame>();
+    const cv::KeyPoint* kun = R.arr<cv::KeyPoint>(n);
+    const float* depth = R.arr<float>(n);
+    const unsigned char* state = R.arr<unsigned char>(n);
+    MockDepthFrame F;
+    F.mvKeysUn.assign(kun, kun + n); F.mvDepth.assign(depth, depth + n);
+    F.mvScaleFactors.assign(fr.scale_factors, fr.scale_factors + fr.n_levels);
+    F.mRwc = cv::Mat(3, 3, CV_32F); F.mOw = mat_from(fr.Ow, 3);
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) F.mRwc.at<float>(r, c) = fr.Rwc[3 * r + c];
+    F.fx = fr.fx; F.fy = fr.fy; F.cx = fr.cx; F.cy = fr.cy; F.invfx = fr.invfx; F.invfy = fr.invfy; F.mbf = 0.f;
+    MockDepthPoint own1, own2;
+    own1.nobs = 3; own1.id = -2; own2.nobs = 0; own2.id = -3;
+    F.mvpMapPoints.assign(n, (MockDepthPoint*)0);
+    for (int i = 0; i < n; ++i) F.mvpMapPoints[i] = state[i] == 1 ? &own1 : state[i] == 2 ? &own2 : (MockDepthPoint*)0;
+    std::vector<MockDepthPoint*> temporal, created;
+    std::vector<int> created_at;
+    MockDepthKF KF;
+    KF.pts.assign(n, (MockDepthPoint*)0);
+    MockDepthMap map;
+    int next_id = 1000;
+    auto make = [&](const cv::Mat& x3D, int i, const float* normal, float maxd, float mind) {
+        MockDepthPoint* p = new MockDepthPoint();
+        p->id = next_id++;   // MapPoint::nNextId: the order of creation
+        for (int r = 0; r < 3; ++r) { p->pos[r] = x3D.at<float>(r, 0); p->normal[r] = normal[r]; }
+        p->maxd = maxd; p->mind = mind;
+        created.push_back(p); created_at.push_back(i);
+        return p;
+    };
+    int made = 0;
+    if (variant == 0) made = Tracking::UpdateLastFrame(F, fr.th_depth, temporal, make);
+    else if (variant == 1) made = Tracking::CreateNewKeyFramePoints(F, &KF, &map, fr.th_depth, make);
+    else made = Tracking::StereoInitializationPoints(F, &KF, &map, make);
+    const int status = Tracking::LastStatus();
+    if (status != 0) fprintf(stderr, "unproject failed: %s\n", slamit_last_error());
+    const slamit_unproject_counts cn = Tracking::LastCounts();
+    // NeedNewKeyFrame's counts on the frame as the walk found it
+    MockDepthFrame G = F;
+    for (int i = 0; i < n; ++i) G.mvpMapPoints[i] = state[i] == 1 ? &own1 : state[i] == 2 ? &own2 : (MockDepthPoint*)0;
+    int nmap = -1, ntotal = -1;
+    const int close_ok = Tracking::CloseRatio(G, fr.th_depth, nmap, ntotal) ? 1 : 0;
+    const int head[5] = {status, made, close_ok, nmap, ntotal};
+    fwrite(head, 4, 5, f); fwrite(&cn, 4, 6, f);
+    const int nc = (int)created.size();
+    fwrite(&nc, 4, 1, f);
+    for (int k = 0; k < nc; ++k) {
+        const MockDepthPoint& p = *created[k];
+        fwrite(&p.id, 4, 1, f); fwrite(&created_at[k], 4, 1, f); fwrite(p.seq, 4, 5, f);
+        fwrite(p.pos, 4, 3, f); fwrite(p.normal, 4, 3, f); fwrite(&p.maxd, 4, 1, f); fwrite(&p.mind, 4, 1, f);
+    }
+    for (int i = 0; i < n; ++i) { const int o = F.mvpMapPoints[i] ? F.mvpMapPoints[i]->id : -1; fwrite(&o, 4, 1, f); }
+    int nkf = 0;
+    for (int i = 0; i < n; ++i) nkf += KF.pts[i] ? 1 : 0;
+    const int tail[3] = {(int)temporal.size(), nkf, (int)map.pts.size()};
+    fwrite(tail, 4, 3, f);
+    fclose(f);
+    for (size_t k = 0; k < created.size(); ++k) delete created[k];
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     std::string mode = argv[1];
@@ -1441,5 +1571,6 @@ int main(int argc, char** argv) {
     if (mode == "triangulate_stereo") return run_triangulate_stereo(argc, argv);
     if (mode == "frustum") return run_frustum(argc, argv);
     if (mode == "stereo") return run_stereo(argc, argv);
+    if (mode == "unproject") return run_unproject(argc, argv);
     return 2;
 }

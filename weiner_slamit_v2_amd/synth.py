@@ -1077,3 +1077,114 @@ def synth_pnp(n=200, outlier_frac=0.3, seed=0, noise_px=0.5):
     th2 = f32(5.991)
     return dict(n=n, p3d=Xw.astype(f32), p2d=uv.astype(f32), sigma2=sigma2, max_err=(sigma2 * th2).astype(f32), intr=intr, th2=float(th2),
                 true=dict(R=R, t=t, bad=bad))
+
+
+def synth_unproject(seed=0, n=300, n_candidates=None, n_close=None, min_points=100, mode=0, ctor=0, n_levels=8, quantised=True, tracked_frac=0.4,
+                    octave_bad_frac=0.06, specials=True, tie_at_cut=False, exact_th=False, all_equal=False, width=640, height=480):
+    """What Tracking::UpdateLastFrame / CreateNewKeyFrame / StereoInitialization hold for one stereo or RGB-D frame
+    (Tracking.cc:1039-1091, :1334-1396, :712-727): a posed pinhole frame (mRwc, mOw, fx .. invfy), n undistorted keypoints with
+    their octaves, their measured depths and the flags of the keypoints that carry a tracked map point.  n_candidates keypoints have
+    a depth > 0, n_close of those have !(depth > th_depth); the others hold what a frame holds without one: -1, and with `specials`
+    also 0, -0 and NaN, while one candidate is a denormal (mode CLOSEST only, and tracked) and one is +inf (in place of a close and of a
+    far depth).
+    quantised: depths are multiples of th_depth / 64, so that equal depths are the rule, as on an RGB-D map; else float32 uniform.
+    tie_at_cut: the keypoints at walk positions max(c, min_points) - 1 .. + 2 (where they exist and are all far or all close) get the
+    depth of position max(c, min_points), so that the index decides which of them is visited.  exact_th: one close depth equals
+    th_depth.  all_equal: every candidate has depth th_depth.  A share octave_bad_frac of the octaves is -1 or n_levels (the level
+    outside the table).  Layout of slamit_unproject_problem."""
+    rs = np.random.RandomState(21000 + seed)
+    f32 = np.float32
+    fx, fy, cx, cy = f32(517.3), f32(516.5), f32(318.6), f32(255.3)
+    invfx, invfy = f32(1.0) / fx, f32(1.0) / fy
+    R, t = se3_exp(np.concatenate([rs.uniform(-0.4, 0.4, 3), rs.uniform(-2.0, 2.0, 3)]))
+    Rcw, tcw = R.astype(f32), t.astype(f32)
+    Rwc = np.ascontiguousarray(Rcw.T)
+    Ow = (-(Rcw.astype(np.float64).T @ tcw.astype(np.float64))).astype(f32)
+    th = f32(3.25)
+    step = f32(3.25 / 64.0)   # 13 / 256: every multiple below 2^11 steps is exact in float32
+    M = int(round(0.85 * n)) if n_candidates is None else int(n_candidates)
+    M = max(0, min(M, n))
+    c = M // 2 if n_close is None else int(n_close)
+    c = max(0, min(c, M))
+    if quantised:
+        close = (rs.randint(1, 65, c).astype(f32) * step).astype(f32)
+        far = (rs.randint(65, 600, M - c).astype(f32) * step).astype(f32)
+    else:
+        close = rs.uniform(0.3, 3.2, c).astype(f32)
+        far = rs.uniform(3.3, 40.0, M - c).astype(f32)
+    if all_equal:
+        close[:] = th
+        far[:] = th   # then they are close too: the true counts are in the result
+    if exact_th and c > 0:
+        close[0] = th
+    if specials and not all_equal:
+        if c > 1 and mode == 0:
+            close[1] = f32(1e-41)        # a denormal: the closest of all, so always visited; it carries a tracked point (below), because
+                                         # unprojected it falls on the camera centre, where Pos - Ow is zero and the normal a NaN
+        if M - c > 1:
+            far[1] = f32(np.inf)
+    depth = np.full(n, -1.0, f32)
+    cand = rs.permutation(n)[:M]
+    depth[cand] = np.concatenate([close, far])[rs.permutation(M)] if M else depth[cand]
+    rest = np.setdiff1d(np.arange(n), cand)
+    if specials and len(rest) >= 4:
+        depth[rest[0]], depth[rest[1]], depth[rest[2]] = f32(0.0), f32(-0.0), f32(np.nan)
+    if tie_at_cut and not all_equal:
+        key = sorted((float(depth[i]), int(i)) for i in cand if not np.isinf(depth[i]))
+        cc = sum(1 for d, _ in key if not d > float(th))
+        p = max(cc, min_points)
+        if p < len(key):
+            for q in (p - 1, p + 1, p + 2):
+                if 0 <= q < len(key) and (q >= cc) == (p >= cc):
+                    depth[key[q][1]] = depth[key[p][1]]
+    kps = np.zeros(n, KP_DTYPE)
+    kps["x"] = rs.uniform(0.0, width, n).astype(f32)
+    kps["y"] = rs.uniform(0.0, height, n).astype(f32)
+    octave = rs.randint(0, n_levels, n).astype(np.int32)
+    pick = rs.rand(n)
+    octave[pick < octave_bad_frac / 2] = -1
+    octave[pick > 1.0 - octave_bad_frac / 2] = n_levels
+    kps["octave"] = octave
+    kps["size"], kps["angle"], kps["class_id"] = 31.0, rs.uniform(0, 360, n).astype(f32), -1
+    tracked = (rs.rand(n) < tracked_frac).astype(np.uint8)
+    tracked[depth.view(np.uint32) - 1 < 0x007fffff] = 1
+    scale_f = (f32(1.2) ** np.arange(n_levels, dtype=f32)).astype(f32)
+    return dict(n=n, fx=fx, fy=fy, cx=cx, cy=cy, invfx=invfx, invfy=invfy, Rwc=Rwc.reshape(9), Ow=Ow, th_depth=th, min_points=int(min_points),
+                mode=int(mode), ctor=int(ctor), n_levels=int(n_levels), scale_factors=scale_f, kps_un=kps, depth=depth, tracked=tracked)
+
+
+KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])   # api.KP_DTYPE
+
+
+def synth_rgbd(seed=0, n=300, width=64, height=48, kind="u16", factor=1.0 / 5000.0, pad=0, zero_frac=0.15, outside=True):
+    """What Frame::ComputeStereoFromRGBD reads (Frame.cc:766-787): a depth plane of `kind` "u16" (raw sensor units, factor
+    1 / DepthMapFactor) or "f32" whose rows are `pad` elements longer than `width` (the padding holds a value no keypoint may read),
+    n raw keypoints with fractional coordinates, their undistorted twins a little beside them, and mbf.  A share zero_frac of the
+    pixels has no measurement (0).  The first keypoints sit on the last row, the last column, both, and on a zero pixel; with
+    `outside`, three more lie off the plane (x = width, y = -1.5, x = NaN).  The plane is quantised (a u16 map is; the f32 one is made
+    the same way), so equal depths are the rule.  Layout of slamit_rgbd_problem; `plane` is the (height, width) view of `storage`."""
+    rs = np.random.RandomState(22000 + seed)
+    f32 = np.float32
+    raw = rs.randint(400, 60000, (height, width))
+    raw[rs.rand(height, width) < zero_frac] = 0
+    raw[0, 0] = 0
+    if kind == "u16":
+        storage = np.full((height, width + pad), 65535, np.uint16)
+        storage[:, :width] = raw.astype(np.uint16)
+    else:
+        storage = np.full((height, width + pad), -7.0, f32)
+        storage[:, :width] = (raw.astype(f32) * f32(1.0 / 5000.0)).astype(f32) if factor == 1.0 else raw.astype(f32)
+    kps = np.zeros(n, KP_DTYPE)
+    kps["x"] = rs.uniform(0.0, width - 0.001, n).astype(f32)
+    kps["y"] = rs.uniform(0.0, height - 0.001, n).astype(f32)
+    fixed = [(width - 0.25, 3.5), (5.5, height - 0.5), (width - 1.0, height - 1.0), (0.75, 0.25), (-0.5, -0.99)]
+    if outside:
+        fixed += [(float(width), 2.0), (3.0, -1.5), (np.nan, 1.0), (2.0, float(height)), (3.0e9, 1.0)]
+    for i, (x, y) in enumerate(fixed[:n]):
+        kps["x"][i], kps["y"][i] = f32(x), f32(y)
+    kps["octave"], kps["class_id"], kps["size"] = rs.randint(0, 8, n), -1, 31.0
+    kps_un = kps.copy()
+    kps_un["x"] = (kps["x"] + rs.uniform(-1.5, 1.5, n).astype(f32)).astype(f32)
+    kps_un["y"] = (kps["y"] + rs.uniform(-1.5, 1.5, n).astype(f32)).astype(f32)
+    return dict(n=n, storage=storage, plane=storage[:, :width], width=width, height=height, kind=kind, factor=f32(factor), mbf=f32(38.6),
+                kps=kps, kps_un=kps_un)
