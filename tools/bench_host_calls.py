@@ -54,6 +54,36 @@ def cases():
     offsets = np.concatenate([[0], np.cumsum(rs.randint(2, 21, 200))]).astype(np.int32)
     desc = rs.randint(0, 256, (int(offsets[-1]), 32)).astype(np.uint8)
     out["distinctive_200pts"] = lambda: api.ORBmatcher.distinctive(desc, offsets)
+    # the "batch of problems" calls, on the generators of their own tools/bench_*.py: one problem, and 64 in one call
+    fru = lambda m, n: [synth.synth_frustum(2000 + k, n, (1.0, 3.0, 5.0)[k % 3]) for k in range(m)]
+    prj = lambda m, n: [synth.synth_project(3000 + k, n, (2 + k) % 6, (3.0, 10.0, 4.0, 7.5, 7.0, 10.0)[k % 6]) for k in range(m)]
+    tri = lambda m, n: [synth.synth_triangulation_stereo(n, 900 + k, 0.05 + 0.7 * (k % 20) / 19.0, 0.2, 0.7, depth=(1.5, 40.0)) for k in range(m)]
+    rgbd = lambda m, n, w, h: [synth.synth_rgbd(seed=k, n=n, width=w, height=h, pad=8) for k in range(m)]
+    unp = lambda m, n: [synth.synth_unproject(seed=3000 + k, n=n, n_candidates=int(0.85 * n), n_close=int(0.3 * n), tie_at_cut=True, octave_bad_frac=0.0)
+                        for k in range(m)]
+
+    def ransac(m, n, nh, gen, key, sample):
+        probs = []
+        for k in range(m):
+            pr, rk = gen(n, 0.3, 500 + k, 0.5), np.random.RandomState(k)
+            pr[key] = sample(n, nh, lambda lo, hi: int(rk.randint(lo, hi + 1)))
+            probs.append(pr)
+        return probs
+
+    def refine_jobs(probs):   # Refine() sees the inliers of a good hypothesis: here the true matches of the scene
+        return [dict(pr, subset=~pr["true"]["bad"]) for pr in probs]
+
+    for m, n in ((1, 1000), (64, 300)):
+        tag = "%dx%d" % (m, n)
+        for name, fn, probs in (("frustum", api.frustum_batch, fru(m, n)), ("project", api.project_batch, prj(m, n)), ("triangulate_stereo", api.triangulate_batch, tri(m, n)),
+                                ("rgbd_depth", api.rgbd_depth_batch, rgbd(m, n, 640 if m == 1 else 160, 480 if m == 1 else 120)),
+                                ("unproject_closest", api.unproject_closest_batch, unp(m, n))):
+            out["%s_%s" % (name, tag)] = lambda fn=fn, probs=probs: fn(probs)
+        pnp = ransac(m, n, 35, synth.synth_pnp, "quads", api.PnPsolver.sample_quads)
+        out["pnp_ransac_%sx35hyp" % tag] = lambda pnp=pnp: api.PnPsolver.ransac(pnp)
+        out["pnp_refine_%s" % tag] = lambda jobs=refine_jobs(pnp): api.PnPsolver.refine(jobs)
+        s3 = ransac(m, n, 300 if m == 1 else 35, synth.synth_sim3_ransac, "triples", api.Sim3Solver.sample_triples)
+        out["sim3_ransac_%sx%dhyp" % (tag, 300 if m == 1 else 35)] = lambda s3=s3: api.Sim3Solver.evaluate(s3, want_bits=False)
     return out
 
 

@@ -142,73 +142,36 @@ int slamit_frustum_batch(int device, int nprob, const slamit_frustum_problem* pr
     for (int f = 0; f < nprob; ++f) results[f].n_in_view = 0;
     if (max_n == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
-    // [per problem: pos normal (planes) max_dist min_dist skip | records] go up; [per problem: the eight outputs, wave counts] come down
-    struct Spans {
-        StageSpan<float> pos, normal, maxd, mind, proj, vc, uvr;
-        StageSpan<int32_t> level, l0, l1, counts;
-        StageSpan<uint8_t> skip, status, valid;
-    };
-    StageLayout L;
-    std::vector<Spans> sp(nprob);
-    for (int f = 0; f < nprob; ++f) {
-        const size_t n = (size_t)probs[f].n;
-        Spans& s = sp[f];
-        s.pos = L.take<float>(3 * n, 16); s.normal = L.take<float>(3 * n, 16); s.maxd = L.take<float>(n, 16); s.mind = L.take<float>(n, 16);
-        s.skip = L.take<uint8_t>(n, 16);
-    }
-    const StageSpan<FruProb> recs = L.take<FruProb>(nprob, 16);
-    L.end_inputs();
-    for (int f = 0; f < nprob; ++f) {
-        const size_t n = (size_t)probs[f].n;
-        Spans& s = sp[f];
-        s.status = L.take<uint8_t>(n, 16); s.proj = L.take<float>(3 * n, 16); s.vc = L.take<float>(n, 16); s.level = L.take<int32_t>(n, 16);
-        s.uvr = L.take<float>(3 * n, 16); s.l0 = L.take<int32_t>(n, 16); s.l1 = L.take<int32_t>(n, 16); s.valid = L.take<uint8_t>(n, 16);
-        s.counts = L.take<int32_t>((n + 63) / 64, 16);
-    }
-    L.end_outputs();
+    // [records | per problem: pos normal (planes) max_dist min_dist skip] go up; [per problem: the eight outputs, wave counts] come down
+    std::vector<StageView<int32_t>> waves(nprob);
     static thread_local SlamitScratch S;
-    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
-    for (int f = 0; f < nprob; ++f) {
-        const slamit_frustum_problem& P = probs[f];
-        const Spans& s = sp[f];
-        FruProb& Q = recs.at(S.host)[f];
-        memset(&Q, 0, sizeof(Q));
-        Q.n = P.n; Q.plane = P.n;
-        if (P.n) {
-            memcpy(&Q.F, &P.frame, sizeof(Q.F));
-            float* pp = s.pos.at(S.host);
-            float* pn = s.normal.at(S.host);
+    const int rc = slamit_staged_batch<FruProb>(
+        where, S, device, nprob,
+        [&](StageBinder& b, int f, FruProb& Q) {
+            const slamit_frustum_problem& P = probs[f];
+            const slamit_frustum_result& R = results[f];
             const size_t n = (size_t)P.n;
-            for (size_t i = 0; i < n; ++i)   // the caller's n x 3 rows become three planes
-                for (int c = 0; c < 3; ++c) { pp[c * n + i] = P.pos[3 * i + c]; pn[c * n + i] = P.normal[3 * i + c]; }
-            memcpy(s.maxd.at(S.host), P.max_dist, s.maxd.bytes()); memcpy(s.mind.at(S.host), P.min_dist, s.mind.bytes());
-            memcpy(s.skip.at(S.host), P.skip, s.skip.bytes());
-        }
-        Q.A.pos = (const SLAMIT_GLOBAL float*)s.pos.at(S.dev); Q.A.normal = (const SLAMIT_GLOBAL float*)s.normal.at(S.dev);
-        Q.A.max_dist = (const SLAMIT_GLOBAL float*)s.maxd.at(S.dev); Q.A.min_dist = (const SLAMIT_GLOBAL float*)s.mind.at(S.dev);
-        Q.A.skip = (const SLAMIT_GLOBAL uint8_t*)s.skip.at(S.dev);
-        Q.A.uvr = (SLAMIT_GLOBAL float*)s.uvr.at(S.dev); Q.A.level_min = (SLAMIT_GLOBAL int32_t*)s.l0.at(S.dev);
-        Q.A.level_max = (SLAMIT_GLOBAL int32_t*)s.l1.at(S.dev); Q.A.valid = (SLAMIT_GLOBAL uint8_t*)s.valid.at(S.dev);
-        Q.A.status = (SLAMIT_GLOBAL uint8_t*)s.status.at(S.dev); Q.A.proj = (SLAMIT_GLOBAL float*)s.proj.at(S.dev);
-        Q.A.view_cos = (SLAMIT_GLOBAL float*)s.vc.at(S.dev); Q.A.level = (SLAMIT_GLOBAL int32_t*)s.level.at(S.dev);
-        Q.wave_counts = (SLAMIT_GLOBAL int32_t*)s.counts.at(S.dev);
-    }
-    HIP_TRY_AT(where, slamit_stage_upload(S, L));
-    hipLaunchKernelGGL(frustum_kernel, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, recs.at(S.dev));
-    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
-    for (int f = 0; f < nprob; ++f) {
-        const Spans& s = sp[f];
-        if (!probs[f].n) continue;
-        slamit_frustum_result& R = results[f];
-        memcpy(R.status, s.status.at(S.host), s.status.bytes()); memcpy(R.proj, s.proj.at(S.host), s.proj.bytes());
-        memcpy(R.view_cos, s.vc.at(S.host), s.vc.bytes()); memcpy(R.level, s.level.at(S.host), s.level.bytes());
-        memcpy(R.uvr, s.uvr.at(S.host), s.uvr.bytes()); memcpy(R.level_min, s.l0.at(S.host), s.l0.bytes());
-        memcpy(R.level_max, s.l1.at(S.host), s.l1.bytes()); memcpy(R.valid, s.valid.at(S.host), s.valid.bytes());
-        int acc = 0;
-        const int32_t* c = s.counts.at(S.host);
-        for (size_t w = 0; w < s.counts.count; ++w) acc += c[w];
-        R.n_in_view = acc;
-    }
+            Q.n = P.n; Q.plane = P.n;
+            if (n) memcpy(&Q.F, &P.frame, sizeof(Q.F));
+            float *pp, *pn;
+            Q.A.pos = slamit_global(b.in_fill<float>(3 * n, &pp)); Q.A.normal = slamit_global(b.in_fill<float>(3 * n, &pn));
+            if (pp)   // the caller's n x 3 rows become three planes
+                for (int c = 0; c < 3; ++c)
+                    for (size_t i = 0; i < n; ++i) { pp[c * n + i] = P.pos[3 * i + c]; pn[c * n + i] = P.normal[3 * i + c]; }
+            Q.A.max_dist = slamit_global(b.in(P.max_dist, n)); Q.A.min_dist = slamit_global(b.in(P.min_dist, n));
+            Q.A.skip = slamit_global(b.in(P.skip, n));
+            Q.A.status = slamit_global(b.out(R.status, n)); Q.A.proj = slamit_global(b.out(R.proj, 3 * n));
+            Q.A.view_cos = slamit_global(b.out(R.view_cos, n)); Q.A.level = slamit_global(b.out(R.level, n));
+            Q.A.uvr = slamit_global(b.out(R.uvr, 3 * n)); Q.A.level_min = slamit_global(b.out(R.level_min, n));
+            Q.A.level_max = slamit_global(b.out(R.level_max, n)); Q.A.valid = slamit_global(b.out(R.valid, n));
+            Q.wave_counts = slamit_global(b.out_view((n + 63) / 64, &waves[f]));
+        },
+        [&](const FruProb* d_recs) {
+            hipLaunchKernelGGL(frustum_kernel, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, d_recs);
+            return hipGetLastError();
+        });
+    if (rc != SLAMIT_OK) return rc;
+    for (int f = 0; f < nprob; ++f) results[f].n_in_view = stage_sum(waves[f].data, waves[f].count);
     return SLAMIT_OK;
 }
 

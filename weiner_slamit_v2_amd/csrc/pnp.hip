@@ -130,59 +130,27 @@ int slamit_pnp_ransac_batch(int device, int nprob, const slamit_pnp_problem* pro
     }
     if (max_hyp == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
-    // [per problem: p3d p2d max_err quads | records] go up; [per problem: pose counts (bits when asked for)] come down; the bits
+    // [records | per problem: p3d p2d max_err quads] go up; [per problem: pose counts (bits when asked for)] come down; the bits
     // nobody asked for stay on the device
-    struct Spans { StageSpan<float> p3d, p2d, err; StageSpan<double> pose; StageSpan<int32_t> quads, counts; StageSpan<uint32_t> bits; int hyp, words; };
-    StageLayout L;
-    std::vector<Spans> sp(nprob);
-    for (int f = 0; f < nprob; ++f) {
-        const slamit_pnp_problem& P = probs[f];
-        Spans& s = sp[f];
-        s.hyp = (P.n == 0) ? 0 : P.n_hyp;
-        s.words = (P.n + 31) / 32;
-        const size_t n = s.hyp ? (size_t)P.n : 0;
-        s.p3d = L.take<float>(3 * n, 16); s.p2d = L.take<float>(2 * n, 16); s.err = L.take<float>(n, 16);
-        s.quads = L.take<int32_t>(4 * (size_t)s.hyp, 16);
-    }
-    const StageSpan<PnpProb> recs = L.take<PnpProb>(nprob, 16);
-    L.end_inputs();
-    for (int f = 0; f < nprob; ++f) {
-        Spans& s = sp[f];
-        s.pose = L.take<double>(12 * (size_t)s.hyp, 16); s.counts = L.take<int32_t>(s.hyp, 16);
-        if (results[f].inlier_bits) s.bits = L.take<uint32_t>((size_t)s.hyp * s.words, 16);
-    }
-    L.end_outputs();
-    for (int f = 0; f < nprob; ++f)
-        if (!results[f].inlier_bits) sp[f].bits = L.take<uint32_t>((size_t)sp[f].hyp * sp[f].words, 16);
     static thread_local SlamitScratch S;
-    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
-    for (int f = 0; f < nprob; ++f) {
-        const slamit_pnp_problem& P = probs[f];
-        const Spans& s = sp[f];
-        if (s.hyp) {
-            memcpy(s.p3d.at(S.host), P.p3d, s.p3d.bytes()); memcpy(s.p2d.at(S.host), P.p2d, s.p2d.bytes());
-            memcpy(s.err.at(S.host), P.max_err, s.err.bytes()); memcpy(s.quads.at(S.host), P.quads, s.quads.bytes());
-        }
-        PnpProb& Q = recs.at(S.host)[f];
-        memset(&Q, 0, sizeof(Q));
-        Q.n = P.n; Q.n_hyp = s.hyp; Q.words = s.words;
-        memcpy(Q.intr, P.intr, sizeof(Q.intr));
-        typedef const SLAMIT_GLOBAL float* cgf;
-        Q.p3d = (cgf)s.p3d.at(S.dev); Q.p2d = (cgf)s.p2d.at(S.dev); Q.max_err = (cgf)s.err.at(S.dev);
-        Q.quads = (const SLAMIT_GLOBAL int32_t*)s.quads.at(S.dev);
-        Q.pose = (SLAMIT_GLOBAL double*)s.pose.at(S.dev); Q.counts = (SLAMIT_GLOBAL int32_t*)s.counts.at(S.dev); Q.bits = (SLAMIT_GLOBAL uint32_t*)s.bits.at(S.dev);
-    }
-    HIP_TRY_AT(where, slamit_stage_upload(S, L));
-    hipLaunchKernelGGL(pnp_hyp_kernel, dim3(max_hyp, nprob), dim3(64), 0, S.st, recs.at(S.dev));
-    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
-    for (int f = 0; f < nprob; ++f) {
-        const Spans& s = sp[f];
-        if (!s.hyp) continue;
-        memcpy(results[f].pose, s.pose.at(S.host), s.pose.bytes());
-        memcpy(results[f].n_inliers, s.counts.at(S.host), s.counts.bytes());
-        if (results[f].inlier_bits) memcpy(results[f].inlier_bits, s.bits.at(S.host), s.bits.bytes());
-    }
-    return SLAMIT_OK;
+    return slamit_staged_batch<PnpProb>(
+        where, S, device, nprob,
+        [&](StageBinder& b, int f, PnpProb& Q) {
+            const slamit_pnp_problem& P = probs[f];
+            const slamit_pnp_result& R = results[f];
+            const size_t hyp = P.n == 0 ? 0 : (size_t)P.n_hyp, words = ((size_t)P.n + 31) / 32;
+            const size_t n = hyp ? (size_t)P.n : 0;
+            Q.n = P.n; Q.n_hyp = (int32_t)hyp; Q.words = (int32_t)words;
+            memcpy(Q.intr, P.intr, sizeof(Q.intr));
+            Q.p3d = slamit_global(b.in(P.p3d, 3 * n)); Q.p2d = slamit_global(b.in(P.p2d, 2 * n)); Q.max_err = slamit_global(b.in(P.max_err, n));
+            Q.quads = slamit_global(b.in(P.quads, 4 * hyp));
+            Q.pose = slamit_global(b.out(R.pose, 12 * hyp)); Q.counts = slamit_global(b.out(R.n_inliers, hyp));
+            Q.bits = slamit_global(R.inlier_bits ? b.out(R.inlier_bits, hyp * words) : b.scratch<uint32_t>(hyp * words));
+        },
+        [&](const PnpProb* d_recs) {
+            hipLaunchKernelGGL(pnp_hyp_kernel, dim3(max_hyp, nprob), dim3(64), 0, S.st, d_recs);
+            return hipGetLastError();
+        });
 }
 
 int slamit_pnp_ransac(int device, const slamit_pnp_problem* prob, slamit_pnp_result* res) {
@@ -193,73 +161,44 @@ int slamit_pnp_refine_batch(int device, int nprob, const slamit_pnp_refine_probl
     const char* const where = "slamit_pnp_refine_batch";
     if (nprob < 0 || (nprob && (!probs || !results))) return slamit_fail(SLAMIT_ERR_ARG, "slamit_pnp_refine_batch: bad argument");
     if (nprob == 0) return SLAMIT_OK;
-    struct Spans { StageSpan<float> p3d, p2d, err; StageSpan<double> pose; StageSpan<int32_t> count; StageSpan<uint32_t> subset, bits; int nc, first, words; };
-    std::vector<Spans> sp(nprob);
-    int live = 0;
+    struct Live { int f, nc, first; };   // a problem with correspondences: the members of its subset and the lowest of them
+    std::vector<Live> live;
     for (int f = 0; f < nprob; ++f) {
         const slamit_pnp_refine_problem& P = probs[f];
         if (P.n < 0) return slamit_fail(SLAMIT_ERR_ARG, "slamit_pnp_refine_batch: negative count");
         if (P.n > SLAMIT_PNP_MAX_N) return slamit_fail(SLAMIT_ERR_ARG, "slamit_pnp_refine_batch: more than SLAMIT_PNP_MAX_N correspondences");
-        sp[f].nc = 0; sp[f].first = -1; sp[f].words = (P.n + 31) / 32;
         if (P.n == 0) continue;   // nothing to solve, nothing written
         if (!P.p3d || !P.p2d || !P.max_err || !P.subset_bits) return slamit_fail(SLAMIT_ERR_ARG, "slamit_pnp_refine_batch: null array");
+        Live l = {f, 0, -1};
         for (int i = 0; i < P.n; ++i)
             if ((P.subset_bits[i >> 5] >> (i & 31)) & 1u) {
-                if (sp[f].first < 0) sp[f].first = i;
-                ++sp[f].nc;
+                if (l.first < 0) l.first = i;
+                ++l.nc;
             }
-        if (sp[f].nc < 4) return slamit_fail(SLAMIT_ERR_ARG, "slamit_pnp_refine_batch: a subset of fewer than four correspondences");
-        ++live;
+        if (l.nc < 4) return slamit_fail(SLAMIT_ERR_ARG, "slamit_pnp_refine_batch: a subset of fewer than four correspondences");
+        live.push_back(l);
     }
-    if (live == 0) return SLAMIT_OK;
+    if (live.empty()) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
-    // [per live problem: p3d p2d max_err subset | records] go up; [per live problem: pose count (bits when asked for)] come down
-    StageLayout L;
-    for (int f = 0; f < nprob; ++f) {
-        Spans& s = sp[f];
-        const size_t n = s.nc ? (size_t)probs[f].n : 0;
-        s.p3d = L.take<float>(3 * n, 16); s.p2d = L.take<float>(2 * n, 16); s.err = L.take<float>(n, 16);
-        s.subset = L.take<uint32_t>(n ? s.words : 0, 16);
-    }
-    const StageSpan<PnpRefineProb> recs = L.take<PnpRefineProb>(live, 16);
-    L.end_inputs();
-    for (int f = 0; f < nprob; ++f) {
-        Spans& s = sp[f];
-        s.pose = L.take<double>(s.nc ? 12 : 0, 16); s.count = L.take<int32_t>(s.nc ? 1 : 0, 16);
-        if (results[f].inlier_bits) s.bits = L.take<uint32_t>(s.nc ? s.words : 0, 16);
-    }
-    L.end_outputs();
-    for (int f = 0; f < nprob; ++f)
-        if (!results[f].inlier_bits) sp[f].bits = L.take<uint32_t>(sp[f].nc ? sp[f].words : 0, 16);
+    // [records | per live problem: p3d p2d max_err subset] go up; [per live problem: pose count (bits when asked for)] come down
     static thread_local SlamitScratch S;
-    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
-    int k = 0;
-    for (int f = 0; f < nprob; ++f) {
-        const slamit_pnp_refine_problem& P = probs[f];
-        const Spans& s = sp[f];
-        if (!s.nc) continue;
-        memcpy(s.p3d.at(S.host), P.p3d, s.p3d.bytes()); memcpy(s.p2d.at(S.host), P.p2d, s.p2d.bytes());
-        memcpy(s.err.at(S.host), P.max_err, s.err.bytes()); memcpy(s.subset.at(S.host), P.subset_bits, s.subset.bytes());
-        PnpRefineProb& Q = recs.at(S.host)[k++];
-        memset(&Q, 0, sizeof(Q));
-        Q.n = P.n; Q.nc = s.nc; Q.first = s.first; Q.words = s.words;
-        memcpy(Q.intr, P.intr, sizeof(Q.intr));
-        typedef const SLAMIT_GLOBAL float* cgf;
-        Q.p3d = (cgf)s.p3d.at(S.dev); Q.p2d = (cgf)s.p2d.at(S.dev); Q.max_err = (cgf)s.err.at(S.dev);
-        Q.subset = (const SLAMIT_GLOBAL uint32_t*)s.subset.at(S.dev);
-        Q.pose = (SLAMIT_GLOBAL double*)s.pose.at(S.dev); Q.count = (SLAMIT_GLOBAL int32_t*)s.count.at(S.dev); Q.bits = (SLAMIT_GLOBAL uint32_t*)s.bits.at(S.dev);
-    }
-    HIP_TRY_AT(where, slamit_stage_upload(S, L));
-    hipLaunchKernelGGL(pnp_refine_kernel, dim3(live), dim3(256), 0, S.st, recs.at(S.dev));
-    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
-    for (int f = 0; f < nprob; ++f) {
-        const Spans& s = sp[f];
-        if (!s.nc) continue;
-        memcpy(results[f].pose, s.pose.at(S.host), s.pose.bytes());
-        results[f].n_inliers = *s.count.at(S.host);
-        if (results[f].inlier_bits) memcpy(results[f].inlier_bits, s.bits.at(S.host), s.bits.bytes());
-    }
-    return SLAMIT_OK;
+    return slamit_staged_batch<PnpRefineProb>(
+        where, S, device, (int)live.size(),
+        [&](StageBinder& b, int k, PnpRefineProb& Q) {
+            const slamit_pnp_refine_problem& P = probs[live[k].f];
+            slamit_pnp_refine_result& R = results[live[k].f];
+            const size_t n = (size_t)P.n, words = (n + 31) / 32;
+            Q.n = P.n; Q.nc = live[k].nc; Q.first = live[k].first; Q.words = (int32_t)words;
+            memcpy(Q.intr, P.intr, sizeof(Q.intr));
+            Q.p3d = slamit_global(b.in(P.p3d, 3 * n)); Q.p2d = slamit_global(b.in(P.p2d, 2 * n)); Q.max_err = slamit_global(b.in(P.max_err, n));
+            Q.subset = slamit_global(b.in(P.subset_bits, words));
+            Q.pose = slamit_global(b.out(R.pose, 12)); Q.count = slamit_global(b.out(&R.n_inliers, 1));
+            Q.bits = slamit_global(R.inlier_bits ? b.out(R.inlier_bits, words) : b.scratch<uint32_t>(words));
+        },
+        [&](const PnpRefineProb* d_recs) {
+            hipLaunchKernelGGL(pnp_refine_kernel, dim3((unsigned)live.size()), dim3(256), 0, S.st, d_recs);
+            return hipGetLastError();
+        });
 }
 
 }  // extern "C"

@@ -136,84 +136,42 @@ int slamit_project_batch_stereo(int device, int nprob, const slamit_project_prob
     for (int f = 0; f < nprob; ++f) results[f].n_valid = 0;
     if (max_n == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
-    // [per problem: pos normal (planes) max_dist min_dist octave skip | records] go up; [per problem: the seven outputs, wave counts] come down;
-    // an input the form does not read takes no room
-    struct Spans {
-        StageSpan<float> pos, normal, maxd, mind, proj, uvr, ur;
-        StageSpan<int32_t> octave, level, l0, l1, counts;
-        StageSpan<uint8_t> skip, status, valid;
-    };
-    StageLayout L;
-    std::vector<Spans> sp(nprob);
-    for (int f = 0; f < nprob; ++f) {
-        const size_t n = (size_t)probs[f].n;
-        const int form = probs[f].camera.form;
-        Spans& s = sp[f];
-        s.pos = L.take<float>(3 * n, 16); s.normal = L.take<float>(n && prj_form_reads_normal(form) ? 3 * n : 0, 16);
-        s.maxd = L.take<float>(n && prj_form_reads_distances(form) ? n : 0, 16); s.mind = L.take<float>(n && prj_form_reads_distances(form) ? n : 0, 16);
-        s.octave = L.take<int32_t>(n && prj_form_reads_octave(form) ? n : 0, 16); s.skip = L.take<uint8_t>(n, 16);
-    }
-    const StageSpan<PrjProb> recs = L.take<PrjProb>(nprob, 16);
-    L.end_inputs();
-    for (int f = 0; f < nprob; ++f) {
-        const size_t n = (size_t)probs[f].n;
-        Spans& s = sp[f];
-        s.status = L.take<uint8_t>(n, 16); s.proj = L.take<float>(2 * n, 16); s.level = L.take<int32_t>(n, 16);
-        s.uvr = L.take<float>(3 * n, 16); s.l0 = L.take<int32_t>(n, 16); s.l1 = L.take<int32_t>(n, 16); s.valid = L.take<uint8_t>(n, 16);
-        s.counts = L.take<int32_t>((n + 63) / 64, 16);
-        s.ur = L.take<float>(ur ? n : 0, 16);
-    }
-    L.end_outputs();
+    // [records | per problem: pos normal (planes) max_dist min_dist octave skip] go up; [per problem: the seven outputs, wave counts, ur] come
+    // down; an input the form does not read takes no room
+    std::vector<StageView<int32_t>> waves(nprob);
     static thread_local SlamitScratch S;
-    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
-    for (int f = 0; f < nprob; ++f) {
-        const slamit_project_problem& P = probs[f];
-        const Spans& s = sp[f];
-        PrjProb& Q = recs.at(S.host)[f];
-        memset(&Q, 0, sizeof(Q));
-        Q.n = P.n; Q.plane = P.n; Q.bf = bf ? bf[f] : 0.f;
-        if (P.n) {
-            memcpy(&Q.C, &P.camera, sizeof(Q.C));
+    const int rc = slamit_staged_batch<PrjProb>(
+        where, S, device, nprob,
+        [&](StageBinder& b, int f, PrjProb& Q) {
+            const slamit_project_problem& P = probs[f];
+            const slamit_project_result& R = results[f];
             const size_t n = (size_t)P.n;
-            float* pp = s.pos.at(S.host);
-            for (size_t i = 0; i < n; ++i)   // the caller's n x 3 rows become three planes
-                for (int c = 0; c < 3; ++c) pp[c * n + i] = P.pos[3 * i + c];
-            if (s.normal.count) {
-                float* pn = s.normal.at(S.host);
-                for (size_t i = 0; i < n; ++i)
-                    for (int c = 0; c < 3; ++c) pn[c * n + i] = P.normal[3 * i + c];
-            }
-            if (s.maxd.count) { memcpy(s.maxd.at(S.host), P.max_dist, s.maxd.bytes()); memcpy(s.mind.at(S.host), P.min_dist, s.mind.bytes()); }
-            if (s.octave.count) memcpy(s.octave.at(S.host), P.octave, s.octave.bytes());
-            memcpy(s.skip.at(S.host), P.skip, s.skip.bytes());
-        }
-        Q.A.pos = (const SLAMIT_GLOBAL float*)s.pos.at(S.dev); Q.A.normal = (const SLAMIT_GLOBAL float*)s.normal.at(S.dev);
-        Q.A.max_dist = (const SLAMIT_GLOBAL float*)s.maxd.at(S.dev); Q.A.min_dist = (const SLAMIT_GLOBAL float*)s.mind.at(S.dev);
-        Q.A.octave = (const SLAMIT_GLOBAL int32_t*)s.octave.at(S.dev); Q.A.skip = (const SLAMIT_GLOBAL uint8_t*)s.skip.at(S.dev);
-        Q.A.uvr = (SLAMIT_GLOBAL float*)s.uvr.at(S.dev); Q.A.level_min = (SLAMIT_GLOBAL int32_t*)s.l0.at(S.dev);
-        Q.A.level_max = (SLAMIT_GLOBAL int32_t*)s.l1.at(S.dev); Q.A.valid = (SLAMIT_GLOBAL uint8_t*)s.valid.at(S.dev);
-        Q.A.status = (SLAMIT_GLOBAL uint8_t*)s.status.at(S.dev); Q.A.proj = (SLAMIT_GLOBAL float*)s.proj.at(S.dev);
-        Q.A.level = (SLAMIT_GLOBAL int32_t*)s.level.at(S.dev);
-        Q.A.ur = ur && P.n ? (SLAMIT_GLOBAL float*)s.ur.at(S.dev) : nullptr;
-        Q.wave_counts = (SLAMIT_GLOBAL int32_t*)s.counts.at(S.dev);
-    }
-    HIP_TRY_AT(where, slamit_stage_upload(S, L));
-    hipLaunchKernelGGL(project_kernel, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, recs.at(S.dev));
-    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
-    for (int f = 0; f < nprob; ++f) {
-        const Spans& s = sp[f];
-        if (!probs[f].n) continue;
-        slamit_project_result& R = results[f];
-        memcpy(R.status, s.status.at(S.host), s.status.bytes()); memcpy(R.proj, s.proj.at(S.host), s.proj.bytes());
-        memcpy(R.level, s.level.at(S.host), s.level.bytes());
-        memcpy(R.uvr, s.uvr.at(S.host), s.uvr.bytes()); memcpy(R.level_min, s.l0.at(S.host), s.l0.bytes());
-        memcpy(R.level_max, s.l1.at(S.host), s.l1.bytes()); memcpy(R.valid, s.valid.at(S.host), s.valid.bytes());
-        if (ur) memcpy(ur[f], s.ur.at(S.host), s.ur.bytes());
-        int acc = 0;
-        const int32_t* c = s.counts.at(S.host);
-        for (size_t w = 0; w < s.counts.count; ++w) acc += c[w];
-        R.n_valid = acc;
-    }
+            const int form = P.camera.form;
+            Q.n = P.n; Q.plane = P.n; Q.bf = bf ? bf[f] : 0.f;
+            if (n) memcpy(&Q.C, &P.camera, sizeof(Q.C));
+            const size_t nn = prj_form_reads_normal(form) ? n : 0, nd = prj_form_reads_distances(form) ? n : 0, no = prj_form_reads_octave(form) ? n : 0;
+            float *pp, *pn;
+            Q.A.pos = slamit_global(b.in_fill<float>(3 * n, &pp)); Q.A.normal = slamit_global(b.in_fill<float>(3 * nn, &pn));
+            if (pp)   // the caller's n x 3 rows become three planes
+                for (int c = 0; c < 3; ++c) {
+                    for (size_t i = 0; i < n; ++i) pp[c * n + i] = P.pos[3 * i + c];
+                    for (size_t i = 0; i < nn; ++i) pn[c * n + i] = P.normal[3 * i + c];
+                }
+            Q.A.max_dist = slamit_global(b.in(P.max_dist, nd)); Q.A.min_dist = slamit_global(b.in(P.min_dist, nd));
+            Q.A.octave = slamit_global(b.in(P.octave, no)); Q.A.skip = slamit_global(b.in(P.skip, n));
+            Q.A.status = slamit_global(b.out(R.status, n)); Q.A.proj = slamit_global(b.out(R.proj, 2 * n));
+            Q.A.level = slamit_global(b.out(R.level, n));
+            Q.A.uvr = slamit_global(b.out(R.uvr, 3 * n)); Q.A.level_min = slamit_global(b.out(R.level_min, n));
+            Q.A.level_max = slamit_global(b.out(R.level_max, n)); Q.A.valid = slamit_global(b.out(R.valid, n));
+            Q.A.ur = ur && n ? slamit_global(b.out(ur[f], n)) : nullptr;
+            Q.wave_counts = slamit_global(b.out_view((n + 63) / 64, &waves[f]));
+        },
+        [&](const PrjProb* d_recs) {
+            hipLaunchKernelGGL(project_kernel, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, d_recs);
+            return hipGetLastError();
+        });
+    if (rc != SLAMIT_OK) return rc;
+    for (int f = 0; f < nprob; ++f) results[f].n_valid = stage_sum(waves[f].data, waves[f].count);
     return SLAMIT_OK;
 }
 

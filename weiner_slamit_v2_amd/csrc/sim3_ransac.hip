@@ -12,7 +12,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <vector>
 
 #include "../../include/slamit.h"
 #include "sim3_horn.h"
@@ -93,60 +92,28 @@ int slamit_sim3_ransac_batch(int device, int nprob, const slamit_sim3_ransac_pro
     }
     if (max_hyp == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
-    // [per problem: x1 x2 max_err1 max_err2 triples | records] go up; [per problem: t12 counts (bits when asked for)] come down; the bits
+    // [records | per problem: x1 x2 max_err1 max_err2 triples] go up; [per problem: t12 counts (bits when asked for)] come down; the bits
     // nobody asked for stay on the device
-    struct Spans { StageSpan<float> x1, x2, e1, e2, t12; StageSpan<int32_t> triples, counts; StageSpan<uint32_t> bits; int hyp, words; };
-    StageLayout L;
-    std::vector<Spans> sp(nprob);
-    for (int f = 0; f < nprob; ++f) {
-        const slamit_sim3_ransac_problem& P = probs[f];
-        Spans& s = sp[f];
-        s.hyp = (P.n == 0) ? 0 : P.n_hyp;
-        s.words = (P.n + 31) / 32;
-        const size_t n = s.hyp ? (size_t)P.n : 0;
-        s.x1 = L.take<float>(3 * n, 16); s.x2 = L.take<float>(3 * n, 16); s.e1 = L.take<float>(n, 16); s.e2 = L.take<float>(n, 16);
-        s.triples = L.take<int32_t>(3 * (size_t)s.hyp, 16);
-    }
-    const StageSpan<Sim3RansacProb> recs = L.take<Sim3RansacProb>(nprob, 16);
-    L.end_inputs();
-    for (int f = 0; f < nprob; ++f) {
-        Spans& s = sp[f];
-        s.t12 = L.take<float>(13 * (size_t)s.hyp, 16); s.counts = L.take<int32_t>(s.hyp, 16);
-        if (results[f].inlier_bits) s.bits = L.take<uint32_t>((size_t)s.hyp * s.words, 16);
-    }
-    L.end_outputs();
-    for (int f = 0; f < nprob; ++f)
-        if (!results[f].inlier_bits) sp[f].bits = L.take<uint32_t>((size_t)sp[f].hyp * sp[f].words, 16);
     static thread_local SlamitScratch S;
-    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
-    for (int f = 0; f < nprob; ++f) {
-        const slamit_sim3_ransac_problem& P = probs[f];
-        const Spans& s = sp[f];
-        if (s.hyp) {
-            memcpy(s.x1.at(S.host), P.x1, s.x1.bytes()); memcpy(s.x2.at(S.host), P.x2, s.x2.bytes());
-            memcpy(s.e1.at(S.host), P.max_err1, s.e1.bytes()); memcpy(s.e2.at(S.host), P.max_err2, s.e2.bytes());
-            memcpy(s.triples.at(S.host), P.triples, s.triples.bytes());
-        }
-        Sim3RansacProb& Q = recs.at(S.host)[f];
-        memset(&Q, 0, sizeof(Q));
-        Q.n = P.n; Q.n_hyp = s.hyp; Q.fix_scale = P.fix_scale; Q.words = s.words;
-        memcpy(Q.intr1, P.intr1, sizeof(Q.intr1)); memcpy(Q.intr2, P.intr2, sizeof(Q.intr2));
-        typedef const SLAMIT_GLOBAL float* cgf;
-        Q.x1 = (cgf)s.x1.at(S.dev); Q.x2 = (cgf)s.x2.at(S.dev); Q.e1 = (cgf)s.e1.at(S.dev); Q.e2 = (cgf)s.e2.at(S.dev);
-        Q.triples = (const SLAMIT_GLOBAL int32_t*)s.triples.at(S.dev);
-        Q.t12 = (SLAMIT_GLOBAL float*)s.t12.at(S.dev); Q.counts = (SLAMIT_GLOBAL int32_t*)s.counts.at(S.dev); Q.bits = (SLAMIT_GLOBAL uint32_t*)s.bits.at(S.dev);
-    }
-    HIP_TRY_AT(where, slamit_stage_upload(S, L));
-    hipLaunchKernelGGL(sim3_ransac_kernel, dim3((max_hyp + 3) / 4, nprob), dim3(256), 0, S.st, recs.at(S.dev));
-    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
-    for (int f = 0; f < nprob; ++f) {
-        const Spans& s = sp[f];
-        if (!s.hyp) continue;
-        memcpy(results[f].t12, s.t12.at(S.host), s.t12.bytes());
-        memcpy(results[f].n_inliers, s.counts.at(S.host), s.counts.bytes());
-        if (results[f].inlier_bits) memcpy(results[f].inlier_bits, s.bits.at(S.host), s.bits.bytes());
-    }
-    return SLAMIT_OK;
+    return slamit_staged_batch<Sim3RansacProb>(
+        where, S, device, nprob,
+        [&](StageBinder& b, int f, Sim3RansacProb& Q) {
+            const slamit_sim3_ransac_problem& P = probs[f];
+            const slamit_sim3_ransac_result& R = results[f];
+            const size_t hyp = P.n == 0 ? 0 : (size_t)P.n_hyp, words = ((size_t)P.n + 31) / 32;
+            const size_t n = hyp ? (size_t)P.n : 0;
+            Q.n = P.n; Q.n_hyp = (int32_t)hyp; Q.fix_scale = P.fix_scale; Q.words = (int32_t)words;
+            memcpy(Q.intr1, P.intr1, sizeof(Q.intr1)); memcpy(Q.intr2, P.intr2, sizeof(Q.intr2));
+            Q.x1 = slamit_global(b.in(P.x1, 3 * n)); Q.x2 = slamit_global(b.in(P.x2, 3 * n));
+            Q.e1 = slamit_global(b.in(P.max_err1, n)); Q.e2 = slamit_global(b.in(P.max_err2, n));
+            Q.triples = slamit_global(b.in(P.triples, 3 * hyp));
+            Q.t12 = slamit_global(b.out(R.t12, 13 * hyp)); Q.counts = slamit_global(b.out(R.n_inliers, hyp));
+            Q.bits = slamit_global(R.inlier_bits ? b.out(R.inlier_bits, hyp * words) : b.scratch<uint32_t>(hyp * words));
+        },
+        [&](const Sim3RansacProb* d_recs) {
+            hipLaunchKernelGGL(sim3_ransac_kernel, dim3((max_hyp + 3) / 4, nprob), dim3(256), 0, S.st, d_recs);
+            return hipGetLastError();
+        });
 }
 
 int slamit_sim3_ransac(int device, const slamit_sim3_ransac_problem* prob, slamit_sim3_ransac_result* res) {

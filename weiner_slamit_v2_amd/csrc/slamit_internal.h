@@ -2,8 +2,10 @@
 #ifndef SLAMIT_INTERNAL_H
 #define SLAMIT_INTERNAL_H
 #include <hip/hip_runtime.h>
+#include <string.h>
 
-#include "stage_layout.h"
+#include "../../include/slamit.h"
+#include "stage_binder.h"
 
 int slamit_fail(int code, const char* msg);                 // records msg, returns code
 int slamit_fail_hip(hipError_t e, const char* where);       // records "<where>: <hip error>", returns SLAMIT_ERR_DEVICE
@@ -25,6 +27,9 @@ int slamit_fail_hip(hipError_t e, const char* where);       // records "<where>:
 #else
 #define SLAMIT_GLOBAL
 #endif
+// the same cast for any element type: a record's field takes slamit_global(pointer the binder returned)
+template <typename T>
+inline SLAMIT_GLOBAL T* slamit_global(T* p) { return (SLAMIT_GLOBAL T*)p; }
 
 // Every entry point works on the device it is given and leaves the caller's current device as it found it (a torch
 // host thread must not have its device changed under it).
@@ -108,7 +113,9 @@ inline hipError_t slamit_scratch_reserve(SlamitScratch& S, int device, size_t ho
 
 // A staged call (the host-pointer entry points): lay the block out (StageLayout: inputs | outputs | device-only), reserve, pack the
 // inputs into S.host through their spans, upload, launch on S.st with pointers from the same spans at S.dev, download and wait,
-// unpack the outputs from S.host.  One copy each way; each step returns the first error.
+// unpack the outputs from S.host.  One copy each way; each step returns the first error.  The single-problem entry points and the
+// pose / Sim3 blocks (lm_layout.h) spell these steps out over their own spans; the batch-of-problems ones go through
+// slamit_staged_batch below, where a StageBinder does the layout, the packing, the pointers and the unpacking from one mention per array.
 inline hipError_t slamit_stage_reserve(SlamitScratch& S, int device, const StageLayout& L) { return slamit_scratch_reserve(S, device, L.io_bytes, L.dev_bytes); }
 inline hipError_t slamit_stage_upload(SlamitScratch& S, const StageLayout& L) { return hipMemcpyAsync(S.dev, S.host, L.in_bytes, hipMemcpyHostToDevice, S.st); }
 inline hipError_t slamit_stage_download_and_wait(SlamitScratch& S, const StageLayout& L) {   // the launches' error, the copy down, the stream
@@ -116,6 +123,38 @@ inline hipError_t slamit_stage_download_and_wait(SlamitScratch& S, const StageLa
     if (e == hipSuccess) e = hipMemcpyAsync(S.host + L.out_off, S.dev + L.out_off, L.io_bytes - L.out_off, hipMemcpyDeviceToHost, S.st);
     if (e == hipSuccess) e = hipStreamSynchronize(S.st);
     return e;
+}
+
+// A staged call over a batch of `nrec` records of type Rec (the "batch of problems" entry points), with the arrays named once
+// (stage_binder.h).  describe(StageBinder& b, int f, Rec& q) fills the zeroed record q of problem f and names every array of the problem
+// as b.in / b.in_fill / b.out / b.out_view / b.scratch, whose result goes into q through slamit_global().  It runs twice per
+// problem: first to measure, with q a dummy and null from every call, then, once the block is reserved, with q in the pinned record
+// array, which is the first thing of the input region.  It must ask for the same sizes both times; what it does with a host pointer
+// (a transpose into an in_fill array) it does only when that pointer is not null.  launch(const Rec* d_recs) starts the kernels on
+// S.st and returns their launch error.  When this returns SLAMIT_OK the b.out arrays are in the caller's hands and the views that
+// b.out_view filled can be read.  A describe function that changed between the passes fails the call before anything is uploaded.
+template <typename Rec, typename Describe, typename Launch>
+int slamit_staged_batch(const char* where, SlamitScratch& S, int device, int nrec, Describe describe, Launch launch) {
+    StageBinder b;
+    auto pass = [&]() -> const Rec* {
+        Rec dummy;
+        Rec* q = nullptr;
+        const Rec* const d_recs = b.in_fill<Rec>((size_t)nrec, &q);
+        memset(q ? q : &dummy, 0, sizeof(Rec) * (q ? (size_t)nrec : 1));
+        for (int f = 0; f < nrec; ++f) describe(b, f, q ? q[f] : dummy);
+        return d_recs;
+    };
+    pass();
+    const StageLayout L = b.plan();
+    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
+    b.bind(S.host, S.dev);
+    const Rec* const d_recs = pass();
+    if (!b.bound()) return slamit_fail(SLAMIT_ERR_STATE, "staged call: the arrays of the bind pass are not those of the plan pass");
+    HIP_TRY_AT(where, slamit_stage_upload(S, L));
+    HIP_TRY_AT(where, launch(d_recs));
+    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
+    b.unpack();
+    return SLAMIT_OK;
 }
 
 #endif

@@ -100,80 +100,48 @@ int slamit_triangulate_stereo_batch(int device, int nprob, const slamit_triangul
     for (int f = 0; f < nprob; ++f) results[f].n_accepted = 0;
     if (max_n == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
-    // [per problem: kp1 kp2 octave1 octave2, with a stereo record its six arrays | records] go up; [per problem: status x3d wave counts,
-    // in a stereo launch source] come down
-    struct Spans { StageSpan<float> kp1, kp2, x3d, ur1, ur2, depth1, depth2, raw1, raw2; StageSpan<int32_t> o1, o2, counts; StageSpan<uint8_t> status, source; };
-    StageLayout L;
-    std::vector<Spans> sp(nprob);
-    for (int f = 0; f < nprob; ++f) {
-        const size_t n = (size_t)probs[f].n;
-        Spans& s = sp[f];
-        s.kp1 = L.take<float>(2 * n, 16); s.kp2 = L.take<float>(2 * n, 16); s.o1 = L.take<int32_t>(n, 16); s.o2 = L.take<int32_t>(n, 16);
-        const size_t ns = stereo && stereo[f] ? n : 0;
-        s.ur1 = L.take<float>(ns, 16); s.ur2 = L.take<float>(ns, 16); s.depth1 = L.take<float>(ns, 16); s.depth2 = L.take<float>(ns, 16);
-        s.raw1 = L.take<float>(2 * ns, 16); s.raw2 = L.take<float>(2 * ns, 16);
-    }
-    const StageSpan<TriProb> recs = L.take<TriProb>(nprob, 16);
-    L.end_inputs();
-    for (int f = 0; f < nprob; ++f) {
-        const size_t n = (size_t)probs[f].n;
-        Spans& s = sp[f];
-        s.status = L.take<uint8_t>(n, 16); s.x3d = L.take<float>(3 * n, 16); s.counts = L.take<int32_t>((n + 63) / 64, 16);
-        s.source = L.take<uint8_t>(any_stereo ? n : 0, 16);
-    }
-    L.end_outputs();
+    // [records | per problem: kp1 kp2 octave1 octave2, with a stereo record its six arrays] go up; [per problem: status x3d wave counts, in
+    // a stereo launch the source the caller asked for] come down; a source nobody asked for stays on the device
+    std::vector<StageView<int32_t>> waves(nprob);
     static thread_local SlamitScratch S;
-    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
-    for (int f = 0; f < nprob; ++f) {
-        const slamit_triangulate_problem& P = probs[f];
-        const Spans& s = sp[f];
-        TriProb& Q = recs.at(S.host)[f];
-        memset(&Q, 0, sizeof(Q));
-        Q.n = P.n;
-        if (P.n) {
-            memcpy(s.kp1.at(S.host), P.kp1_xy, s.kp1.bytes()); memcpy(s.kp2.at(S.host), P.kp2_xy, s.kp2.bytes());
-            memcpy(s.o1.at(S.host), P.octave1, s.o1.bytes()); memcpy(s.o2.at(S.host), P.octave2, s.o2.bytes());
-            memcpy(Q.c1.T, P.Tcw1, sizeof(Q.c1.T)); memcpy(Q.c2.T, P.Tcw2, sizeof(Q.c2.T));
-            Q.c1.fx = P.intr1[0]; Q.c1.fy = P.intr1[1]; Q.c1.cx = P.intr1[2]; Q.c1.cy = P.intr1[3]; Q.c1.invfx = P.intr1[4]; Q.c1.invfy = P.intr1[5];
-            Q.c2.fx = P.intr2[0]; Q.c2.fy = P.intr2[1]; Q.c2.cx = P.intr2[2]; Q.c2.cy = P.intr2[3]; Q.c2.invfx = P.intr2[4]; Q.c2.invfy = P.intr2[5];
-            tri_centre(Q.c1); tri_centre(Q.c2);
-            Q.ratio_factor = P.ratio_factor;
-            memcpy(Q.sf1, P.scale_factors1, sizeof(float) * P.n_levels); memcpy(Q.s1, P.level_sigma2_1, sizeof(float) * P.n_levels);
-            memcpy(Q.sf2, P.scale_factors2, sizeof(float) * P.n_levels); memcpy(Q.s2, P.level_sigma2_2, sizeof(float) * P.n_levels);
-            if (stereo && stereo[f]) {
-                const struct slamit_triangulate_stereo& T = *stereo[f];
-                memcpy(s.ur1.at(S.host), T.ur1, s.ur1.bytes()); memcpy(s.ur2.at(S.host), T.ur2, s.ur2.bytes());
-                memcpy(s.depth1.at(S.host), T.depth1, s.depth1.bytes()); memcpy(s.depth2.at(S.host), T.depth2, s.depth2.bytes());
-                memcpy(s.raw1.at(S.host), T.raw1_xy, s.raw1.bytes()); memcpy(s.raw2.at(S.host), T.raw2_xy, s.raw2.bytes());
-                Q.mb1 = T.mb1; Q.mb2 = T.mb2; Q.bf = T.bf;
-                Q.ur1 = (const SLAMIT_GLOBAL float*)s.ur1.at(S.dev); Q.ur2 = (const SLAMIT_GLOBAL float*)s.ur2.at(S.dev);
-                Q.depth1 = (const SLAMIT_GLOBAL float*)s.depth1.at(S.dev); Q.depth2 = (const SLAMIT_GLOBAL float*)s.depth2.at(S.dev);
-                Q.raw1 = (const SLAMIT_GLOBAL float*)s.raw1.at(S.dev); Q.raw2 = (const SLAMIT_GLOBAL float*)s.raw2.at(S.dev);
+    const int rc = slamit_staged_batch<TriProb>(
+        where, S, device, nprob,
+        [&](StageBinder& b, int f, TriProb& Q) {
+            const slamit_triangulate_problem& P = probs[f];
+            const size_t n = (size_t)P.n;
+            Q.n = P.n;
+            if (n) {
+                memcpy(Q.c1.T, P.Tcw1, sizeof(Q.c1.T)); memcpy(Q.c2.T, P.Tcw2, sizeof(Q.c2.T));
+                Q.c1.fx = P.intr1[0]; Q.c1.fy = P.intr1[1]; Q.c1.cx = P.intr1[2]; Q.c1.cy = P.intr1[3]; Q.c1.invfx = P.intr1[4]; Q.c1.invfy = P.intr1[5];
+                Q.c2.fx = P.intr2[0]; Q.c2.fy = P.intr2[1]; Q.c2.cx = P.intr2[2]; Q.c2.cy = P.intr2[3]; Q.c2.invfx = P.intr2[4]; Q.c2.invfy = P.intr2[5];
+                tri_centre(Q.c1); tri_centre(Q.c2);
+                Q.ratio_factor = P.ratio_factor;
+                memcpy(Q.sf1, P.scale_factors1, sizeof(float) * P.n_levels); memcpy(Q.s1, P.level_sigma2_1, sizeof(float) * P.n_levels);
+                memcpy(Q.sf2, P.scale_factors2, sizeof(float) * P.n_levels); memcpy(Q.s2, P.level_sigma2_2, sizeof(float) * P.n_levels);
             }
-        }
-        Q.source = (SLAMIT_GLOBAL uint8_t*)s.source.at(S.dev);
-        Q.kp1 = (const SLAMIT_GLOBAL float*)s.kp1.at(S.dev); Q.kp2 = (const SLAMIT_GLOBAL float*)s.kp2.at(S.dev);
-        Q.o1 = (const SLAMIT_GLOBAL int32_t*)s.o1.at(S.dev); Q.o2 = (const SLAMIT_GLOBAL int32_t*)s.o2.at(S.dev);
-        Q.status = (SLAMIT_GLOBAL uint8_t*)s.status.at(S.dev); Q.x3d = (SLAMIT_GLOBAL float*)s.x3d.at(S.dev);
-        Q.wave_counts = (SLAMIT_GLOBAL int32_t*)s.counts.at(S.dev);
-    }
-    HIP_TRY_AT(where, slamit_stage_upload(S, L));
-    if (any_stereo) hipLaunchKernelGGL(triangulate_kernel<true>, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, recs.at(S.dev));
-    else hipLaunchKernelGGL(triangulate_kernel<false>, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, recs.at(S.dev));
-    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
+            Q.kp1 = slamit_global(b.in(P.kp1_xy, 2 * n)); Q.kp2 = slamit_global(b.in(P.kp2_xy, 2 * n));
+            Q.o1 = slamit_global(b.in(P.octave1, n)); Q.o2 = slamit_global(b.in(P.octave2, n));
+            if (n && stereo && stereo[f]) {
+                const struct slamit_triangulate_stereo& T = *stereo[f];
+                Q.mb1 = T.mb1; Q.mb2 = T.mb2; Q.bf = T.bf;
+                Q.ur1 = slamit_global(b.in(T.ur1, n)); Q.ur2 = slamit_global(b.in(T.ur2, n));
+                Q.depth1 = slamit_global(b.in(T.depth1, n)); Q.depth2 = slamit_global(b.in(T.depth2, n));
+                Q.raw1 = slamit_global(b.in(T.raw1_xy, 2 * n)); Q.raw2 = slamit_global(b.in(T.raw2_xy, 2 * n));
+            }
+            Q.status = slamit_global(b.out(results[f].status, n)); Q.x3d = slamit_global(b.out(results[f].x3d, 3 * n));
+            Q.wave_counts = slamit_global(b.out_view((n + 63) / 64, &waves[f]));
+            if (any_stereo) Q.source = slamit_global(source && source[f] ? b.out(source[f], n) : b.scratch<uint8_t>(n));
+        },
+        [&](const TriProb* d_recs) {
+            if (any_stereo) hipLaunchKernelGGL(triangulate_kernel<true>, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, d_recs);
+            else hipLaunchKernelGGL(triangulate_kernel<false>, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, d_recs);
+            return hipGetLastError();
+        });
+    if (rc != SLAMIT_OK) return rc;
     for (int f = 0; f < nprob; ++f) {
-        const Spans& s = sp[f];
-        if (!probs[f].n) continue;
-        memcpy(results[f].status, s.status.at(S.host), s.status.bytes());
-        memcpy(results[f].x3d, s.x3d.at(S.host), s.x3d.bytes());
-        if (source && source[f]) {
-            if (any_stereo) memcpy(source[f], s.source.at(S.host), s.source.bytes());
-            else for (int k = 0; k < probs[f].n; ++k) source[f][k] = results[f].status[k] == TRI_PARALLAX || results[f].status[k] == TRI_W_ZERO ? TRI_SRC_NONE : TRI_SRC_TRIANGULATED;
-        }
-        int acc = 0;
-        const int32_t* c = s.counts.at(S.host);
-        for (size_t w = 0; w < s.counts.count; ++w) acc += c[w];
-        results[f].n_accepted = acc;
+        results[f].n_accepted = stage_sum(waves[f].data, waves[f].count);
+        if (!any_stereo && source && source[f])   // a monocular launch writes no source: it follows from the status
+            for (int k = 0; k < probs[f].n; ++k) source[f][k] = results[f].status[k] == TRI_PARALLAX || results[f].status[k] == TRI_W_ZERO ? TRI_SRC_NONE : TRI_SRC_TRIANGULATED;
     }
     return SLAMIT_OK;
 }

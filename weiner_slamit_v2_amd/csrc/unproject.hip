@@ -305,62 +305,31 @@ int slamit_rgbd_depth_batch(int device, int nprob, const slamit_rgbd_problem* pr
     }
     if (max_n == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
-    struct Spans {
-        StageSpan<unsigned char> plane;
-        size_t row_bytes;
-        StageSpan<slamit_kp> kps, kps_un;
-        StageSpan<float> ur, depth;
-        StageSpan<uint8_t> status;
-    };
-    StageLayout L;
-    std::vector<Spans> sp(nprob);
-    for (int f = 0; f < nprob; ++f) {
-        const slamit_rgbd_problem& P = probs[f];
-        Spans& s = sp[f];
-        const size_t n = (size_t)P.n;
-        s.row_bytes = n ? (((P.plane.type == SLAMIT_DEPTH_U16 ? 2 : 4) * (size_t)P.plane.width + 3) & ~(size_t)3) : 0;   // rows go up without their padding
-        s.plane = L.take<unsigned char>(n ? s.row_bytes * (size_t)P.plane.height : 0, 16);
-        s.kps = L.take<slamit_kp>(n, 16); s.kps_un = L.take<slamit_kp>(n, 16);
-    }
-    const StageSpan<RgbdFrame> recs = L.take<RgbdFrame>(nprob, 16);
-    L.end_inputs();
-    for (int f = 0; f < nprob; ++f) {
-        const size_t n = (size_t)probs[f].n;
-        Spans& s = sp[f];
-        s.ur = L.take<float>(n, 16); s.depth = L.take<float>(n, 16); s.status = L.take<uint8_t>(n, 16);
-    }
-    L.end_outputs();
+    // [records | per problem: the depth plane, kps kps_un] go up; [per problem: u_right depth status] come down
     static thread_local SlamitScratch S;
-    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
-    for (int f = 0; f < nprob; ++f) {
-        const slamit_rgbd_problem& P = probs[f];
-        const Spans& s = sp[f];
-        RgbdFrame& Q = recs.at(S.host)[f];
-        memset(&Q, 0, sizeof(Q));
-        Q.n = P.n;
-        if (P.n) {
-            const size_t used = (P.plane.type == SLAMIT_DEPTH_U16 ? 2 : 4) * (size_t)P.plane.width;
-            unsigned char* dst = s.plane.at(S.host);
-            for (int r = 0; r < P.plane.height; ++r) memcpy(dst + (size_t)r * s.row_bytes, (const unsigned char*)P.plane.data + (size_t)r * P.plane.pitch, used);
-            memcpy(s.kps.at(S.host), P.kps, s.kps.bytes()); memcpy(s.kps_un.at(S.host), P.kps_un, s.kps_un.bytes());
-        }
-        Q.data = (const SLAMIT_GLOBAL unsigned char*)s.plane.at(S.dev); Q.pitch = s.row_bytes;
-        Q.width = P.plane.width; Q.height = P.plane.height; Q.type = P.plane.type; Q.factor = P.plane.factor; Q.mbf = P.mbf;
-        Q.kps = (const SLAMIT_GLOBAL slamit_kp*)s.kps.at(S.dev); Q.kps_un = (const SLAMIT_GLOBAL slamit_kp*)s.kps_un.at(S.dev);
-        Q.u_right = (SLAMIT_GLOBAL float*)s.ur.at(S.dev); Q.depth = (SLAMIT_GLOBAL float*)s.depth.at(S.dev); Q.status = (SLAMIT_GLOBAL uint8_t*)s.status.at(S.dev);
-    }
-    HIP_TRY_AT(where, slamit_stage_upload(S, L));
-    RgbdDev none;
-    memset(&none, 0, sizeof(none));
-    hipLaunchKernelGGL(rgbd_depth_kernel, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, recs.at(S.dev), none);
-    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
-    for (int f = 0; f < nprob; ++f) {
-        const Spans& s = sp[f];
-        if (!probs[f].n) continue;
-        memcpy(results[f].u_right, s.ur.at(S.host), s.ur.bytes()); memcpy(results[f].depth, s.depth.at(S.host), s.depth.bytes());
-        memcpy(results[f].status, s.status.at(S.host), s.status.bytes());
-    }
-    return SLAMIT_OK;
+    return slamit_staged_batch<RgbdFrame>(
+        where, S, device, nprob,
+        [&](StageBinder& b, int f, RgbdFrame& Q) {
+            const slamit_rgbd_problem& P = probs[f];
+            const size_t n = (size_t)P.n;
+            const size_t used = n ? (P.plane.type == SLAMIT_DEPTH_U16 ? 2 : 4) * (size_t)P.plane.width : 0, rows = n ? (size_t)P.plane.height : 0;
+            const size_t row_bytes = (used + 3) & ~(size_t)3;   // rows go up without their padding
+            Q.n = P.n;
+            unsigned char* dst;
+            Q.data = slamit_global(b.in_fill<unsigned char>(row_bytes * rows, &dst)); Q.pitch = row_bytes;
+            if (dst)
+                for (size_t r = 0; r < rows; ++r) memcpy(dst + r * row_bytes, (const unsigned char*)P.plane.data + r * P.plane.pitch, used);
+            Q.width = P.plane.width; Q.height = P.plane.height; Q.type = P.plane.type; Q.factor = P.plane.factor; Q.mbf = P.mbf;
+            Q.kps = slamit_global(b.in(P.kps, n)); Q.kps_un = slamit_global(b.in(P.kps_un, n));
+            Q.u_right = slamit_global(b.out(results[f].u_right, n)); Q.depth = slamit_global(b.out(results[f].depth, n));
+            Q.status = slamit_global(b.out(results[f].status, n));
+        },
+        [&](const RgbdFrame* d_recs) {
+            RgbdDev none;
+            memset(&none, 0, sizeof(none));
+            hipLaunchKernelGGL(rgbd_depth_kernel, dim3((max_n + 255) / 256, nprob), dim3(256), 0, S.st, d_recs, none);
+            return hipGetLastError();
+        });
 }
 
 int slamit_rgbd_depth(int device, const slamit_rgbd_problem* prob, slamit_rgbd_result* res) { return slamit_rgbd_depth_batch(device, 1, prob, res); }
@@ -414,63 +383,33 @@ int slamit_unproject_closest_batch(int device, int nprob, const slamit_unproject
     for (int f = 0; f < nprob; ++f) memset(&results[f].counts, 0, sizeof(results[f].counts));
     if (max_n == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
-    struct Spans {
-        StageSpan<slamit_kp> kps;
-        StageSpan<float> depth, pos, normal, maxd, mind;
-        StageSpan<uint8_t> tracked, status;
-        StageSpan<int32_t> order, counts;
-    };
-    StageLayout L;
-    std::vector<Spans> sp(nprob);
-    for (int f = 0; f < nprob; ++f) {
-        const size_t n = (size_t)probs[f].n;
-        Spans& s = sp[f];
-        s.kps = L.take<slamit_kp>(n, 16); s.depth = L.take<float>(n, 16); s.tracked = L.take<uint8_t>(probs[f].tracked ? n : 0, 16);
-    }
-    const StageSpan<UnpProb> recs = L.take<UnpProb>(nprob, 16);
-    L.end_inputs();
-    for (int f = 0; f < nprob; ++f) {
-        const size_t n = (size_t)probs[f].n;
-        Spans& s = sp[f];
-        s.status = L.take<uint8_t>(n, 16); s.order = L.take<int32_t>(n, 16); s.pos = L.take<float>(3 * n, 16); s.normal = L.take<float>(3 * n, 16);
-        s.maxd = L.take<float>(n, 16); s.mind = L.take<float>(n, 16); s.counts = L.take<int32_t>(6, 16);
-    }
-    L.end_outputs();
+    // [records | per problem: kps_un depth, tracked where given] go up; [per problem: the six outputs, the six counters] come down
+    std::vector<StageView<int32_t>> counts(nprob);
     static thread_local SlamitScratch S;
-    HIP_TRY_AT(where, slamit_stage_reserve(S, device, L));
-    for (int f = 0; f < nprob; ++f) {
-        const slamit_unproject_problem& P = probs[f];
-        const Spans& s = sp[f];
-        UnpProb& Q = recs.at(S.host)[f];
-        memset(&Q, 0, sizeof(Q));
-        memcpy(&Q.F, &P.frame, sizeof(Q.F));
-        Q.n = P.n;
-        if (P.n) {
-            memcpy(s.kps.at(S.host), P.kps_un, s.kps.bytes()); memcpy(s.depth.at(S.host), P.depth, s.depth.bytes());
-            if (P.tracked) memcpy(s.tracked.at(S.host), P.tracked, s.tracked.bytes());
-        }
-        Q.A.kps_un = (const SLAMIT_GLOBAL slamit_kp*)s.kps.at(S.dev); Q.A.depth = (const SLAMIT_GLOBAL float*)s.depth.at(S.dev);
-        Q.A.tracked = P.tracked && P.n ? (const SLAMIT_GLOBAL uint8_t*)s.tracked.at(S.dev) : nullptr;
-        Q.A.status = (SLAMIT_GLOBAL uint8_t*)s.status.at(S.dev); Q.A.order = (SLAMIT_GLOBAL int32_t*)s.order.at(S.dev);
-        Q.A.pos = (SLAMIT_GLOBAL float*)s.pos.at(S.dev); Q.A.normal = (SLAMIT_GLOBAL float*)s.normal.at(S.dev);
-        Q.A.max_dist = (SLAMIT_GLOBAL float*)s.maxd.at(S.dev); Q.A.min_dist = (SLAMIT_GLOBAL float*)s.mind.at(S.dev);
-        Q.A.octave = nullptr; Q.A.skip = nullptr; Q.A.counts = (SLAMIT_GLOBAL int32_t*)s.counts.at(S.dev);
-        Q.A.stride_c = 1; Q.A.stride_i = 3; Q.A.merge = 0;
-    }
-    HIP_TRY_AT(where, slamit_stage_upload(S, L));
-    UnpDev none;
-    memset(&none, 0, sizeof(none));
-    HIP_TRY_AT(where, unp_launch(recs.at(S.dev), none, nprob, max_n, S.st));
-    HIP_TRY_AT(where, slamit_stage_download_and_wait(S, L));
-    for (int f = 0; f < nprob; ++f) {
-        const Spans& s = sp[f];
-        slamit_unproject_result& R = results[f];
-        if (!probs[f].n) continue;
-        memcpy(R.status, s.status.at(S.host), s.status.bytes()); memcpy(R.order, s.order.at(S.host), s.order.bytes());
-        memcpy(R.pos, s.pos.at(S.host), s.pos.bytes()); memcpy(R.normal, s.normal.at(S.host), s.normal.bytes());
-        memcpy(R.max_dist, s.maxd.at(S.host), s.maxd.bytes()); memcpy(R.min_dist, s.mind.at(S.host), s.mind.bytes());
-        memcpy(&R.counts, s.counts.at(S.host), sizeof(R.counts));
-    }
+    const int rc = slamit_staged_batch<UnpProb>(
+        where, S, device, nprob,
+        [&](StageBinder& b, int f, UnpProb& Q) {
+            const slamit_unproject_problem& P = probs[f];
+            const slamit_unproject_result& R = results[f];
+            const size_t n = (size_t)P.n;
+            memcpy(&Q.F, &P.frame, sizeof(Q.F));
+            Q.n = P.n;
+            Q.A.kps_un = slamit_global(b.in(P.kps_un, n)); Q.A.depth = slamit_global(b.in(P.depth, n));
+            Q.A.tracked = n ? slamit_global(b.in(P.tracked, n)) : nullptr;   // null without the caller's: mode ALL
+            Q.A.status = slamit_global(b.out(R.status, n)); Q.A.order = slamit_global(b.out(R.order, n));
+            Q.A.pos = slamit_global(b.out(R.pos, 3 * n)); Q.A.normal = slamit_global(b.out(R.normal, 3 * n));
+            Q.A.max_dist = slamit_global(b.out(R.max_dist, n)); Q.A.min_dist = slamit_global(b.out(R.min_dist, n));
+            Q.A.counts = slamit_global(b.out_view(6, &counts[f]));   // written for an empty problem too
+            Q.A.stride_c = 1; Q.A.stride_i = 3; Q.A.merge = 0;
+        },
+        [&](const UnpProb* d_recs) {
+            UnpDev none;
+            memset(&none, 0, sizeof(none));
+            return unp_launch(d_recs, none, nprob, max_n, S.st);
+        });
+    if (rc != SLAMIT_OK) return rc;
+    for (int f = 0; f < nprob; ++f)
+        if (probs[f].n) memcpy(&results[f].counts, counts[f].data, sizeof(results[f].counts));
     return SLAMIT_OK;
 }
 
