@@ -579,3 +579,89 @@ def pose_solve_margin(prob):
 def pose_ref_solve(prob):
     """The reference's own g2o (authoring container only)."""
     return _pose_call("ref", prob)
+
+
+# ---------------------------------------------------------------------------------------------
+# Bag of words: the reference's own DBoW2 (oracle/_ref/libdbow_ref.so, oracle/dbow_ref_harness.cc),
+# where it was built in the authoring container.  No restatement stands behind these calls.
+# ---------------------------------------------------------------------------------------------
+_f64p = C.POINTER(C.c_double)
+_dbow = None
+
+
+def dbow_ref_available():
+    return os.path.exists(os.path.join(HERE, "_ref", "libdbow_ref.so"))
+
+
+def _dbow_lib():
+    global _dbow
+    if _dbow is None:
+        L = C.CDLL(os.path.join(HERE, "_ref", "libdbow_ref.so"))
+        L.dbow_ref_load.restype = C.c_void_p
+        L.dbow_ref_load.argtypes = [C.c_char_p]
+        L.dbow_ref_free.argtypes = [C.c_void_p]
+        L.dbow_ref_info.argtypes = [C.c_void_p, _i32p]
+        L.dbow_ref_features.argtypes = [C.c_void_p, _u8p, C.c_int, C.c_int, _i32p, _i32p, _f64p, _i32p]
+        L.dbow_ref_transform_bow.argtypes = [C.c_void_p, _u8p, C.c_int, _i32p, _i32p, _f64p]
+        L.dbow_ref_transform.argtypes = [C.c_void_p, _u8p, C.c_int, C.c_int, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p]
+        L.dbow_ref_score.restype = C.c_double
+        L.dbow_ref_score.argtypes = [C.c_void_p, C.c_int, _i32p, _f64p, C.c_int, _i32p, _f64p]
+        _dbow = L
+    return _dbow
+
+
+class DbowRef:
+    """The reference's ORBVocabulary (TemplatedVocabulary over FORB) loaded from a vocabulary text file with its own loadFromTextFile."""
+
+    def __init__(self, path):
+        self.L = _dbow_lib()
+        self.h = self.L.dbow_ref_load(os.fsencode(path))
+        if not self.h:
+            raise RuntimeError("the reference's loadFromTextFile refused %s" % path)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.dbow_ref_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def info(self):
+        head = np.zeros(6, np.int32)
+        self.L.dbow_ref_info(self.h, _ptr(head, _i32p))
+        return dict(zip(("k", "L", "scoring", "weighting", "n_nodes", "n_words"), (int(v) for v in head)))
+
+    def features(self, desc, levelsup):
+        """Per feature -> dict: word_pub (the public transform(feature)); word_id, weight, node_id (the protected five-argument
+        overload; node_id -1 where the reference never wrote it)."""
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n, m = len(desc), max(len(desc), 1)
+        pub, wid, nid, w = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.float64)
+        self.L.dbow_ref_features(self.h, _ptr(desc), n, int(levelsup), _ptr(pub, _i32p), _ptr(wid, _i32p), _ptr(w, _f64p), _ptr(nid, _i32p))
+        return {"word_pub": pub[:n], "word_id": wid[:n], "weight": w[:n], "node_id": nid[:n]}
+
+    def transform_bow(self, desc):
+        """transform(features, v) -> (bow_word, bow_value)."""
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n, m = len(desc), max(len(desc), 1)
+        bn, bw, bv = np.zeros(1, np.int32), np.zeros(m, np.int32), np.zeros(m, np.float64)
+        self.L.dbow_ref_transform_bow(self.h, _ptr(desc), n, _ptr(bn, _i32p), _ptr(bw, _i32p), _ptr(bv, _f64p))
+        return bw[:bn[0]].copy(), bv[:bn[0]].copy()
+
+    def transform(self, desc, levelsup):
+        """transform(features, v, fv, levelsup) -> dict bow_word, bow_value, fv_node, fv_ptr, fv_items."""
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n, m = len(desc), max(len(desc), 1)
+        bn, bw, bv = np.zeros(1, np.int32), np.zeros(m, np.int32), np.zeros(m, np.float64)
+        fn, fnode, fptr, fitems = np.zeros(1, np.int32), np.zeros(m, np.int32), np.zeros(m + 1, np.int32), np.zeros(m, np.int32)
+        self.L.dbow_ref_transform(self.h, _ptr(desc), n, int(levelsup), _ptr(bn, _i32p), _ptr(bw, _i32p), _ptr(bv, _f64p), _ptr(fn, _i32p),
+                                  _ptr(fnode, _i32p), _ptr(fptr, _i32p), _ptr(fitems, _i32p))
+        return {"bow_word": bw[:bn[0]].copy(), "bow_value": bv[:bn[0]].copy(), "fv_node": fnode[:fn[0]].copy(),
+                "fv_ptr": fptr[:fn[0] + 1].copy(), "fv_items": fitems[:fptr[fn[0]]].copy()}
+
+    def score(self, a, b):
+        """score(a, b) of two BowVectors (word ids ascending i32, values f64): a's value is vi, b's is wi."""
+        wa, va = np.ascontiguousarray(a[0], np.int32), np.ascontiguousarray(a[1], np.float64)
+        wb, vb = np.ascontiguousarray(b[0], np.int32), np.ascontiguousarray(b[1], np.float64)
+        return float(self.L.dbow_ref_score(self.h, len(wa), _ptr(wa, _i32p), _ptr(va, _f64p), len(wb), _ptr(wb, _i32p), _ptr(vb, _f64p)))
