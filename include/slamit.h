@@ -1288,6 +1288,105 @@ struct slamit_unproject_batch_rec {
 typedef struct slamit_unproject_batch_rec slamit_unproject_batch_rec;
 int slamit_unproject_closest_batch_dev(int device, const slamit_unproject_batch_rec* batch, void* stream);
 
+/* ---- UpdateLocalMap: keyframe votes, local keyframes, local points (tracking, in front of SearchLocalPoints) ----
+ * Tracking::UpdateLocalKeyFrames and ::UpdateLocalPoints (src/Tracking.cc:1467-1626) and the skip flags of SearchLocalPoints' first
+ * loop (:1412-1428), over tables of slots the caller keeps (csrc/local_map.h states the walk).  Integer work and
+ * copies of stored floats only: the results are exact.  Every id is a slot (int32), -1 = none.
+ *   (a) votes[k] = the entries of frame_mp that are non-null, not bad, and that keyframe k observes; a bad point's entry becomes -1
+ *   (b) the voted non-bad keyframes, then the reference's one-hop expansion (first good unmarked of the best ten, first good
+ *       unmarked child, the parent without a bad test, which ends the walk; no visit once the list exceeds 80), and the reference
+ *       keyframe (the first with the strictly largest count).  With no vote at all local_kf, n_local_kf and ref_kf are left as
+ *       they were; with every voted keyframe bad the list becomes empty and ref_kf stays.
+ *   (c) the points of the local keyframes in list order and keypoint order, NULL and bad ones dropped, first occurrence kept;
+ *       skip = 1 for a point among the frame's own non-null entries after (a) or in frame_seen.
+ * ORDER: the reference walks std::map / std::set of pointers, i.e. in address order.  Here voted keyframes are taken in ASCENDING
+ * SLOT order and children AS GIVEN; a caller that numbers keyframes by std::less<KeyFrame*> and lists children in set order
+ * (shim/Tracking.h) gets the reference's own order on that run.
+ * COST: building these tables from host objects costs about what the host loop itself costs, so the host forms are for parity and
+ * tests; the gain is the resident form, where the tables live in HBM and are updated when the map changes.
+ * Status bits, per frame: */
+#define SLAMIT_LOCAL_MAP_BAD_SLOT 1       /* device form: a slot outside its table was skipped (never dereferenced) */
+#define SLAMIT_LOCAL_MAP_KF_OVERFLOW 2    /* more local keyframes than kf_cap: n_local_kf is the number needed, the first kf_cap are written */
+#define SLAMIT_LOCAL_MAP_MP_OVERFLOW 4    /* more local points than q_cap: n_local_mp is the number needed, the first q_cap are written */
+#define SLAMIT_LOCAL_MAP_ROW_CUT 8        /* a keyframe with more than SLAMIT_LOCAL_MAP_MAX_ROW keypoints: the rest were not read */
+#define SLAMIT_LOCAL_MAP_MAX_KF 65535     /* keyframes per map, and kf_cap: the upper 16 bits of the first-occurrence key */
+#define SLAMIT_LOCAL_MAP_MAX_ROW 65536    /* keypoints per keyframe: the key's lower 16 bits */
+#define SLAMIT_LOCAL_MAP_MIN_KF_CAP 83    /* kf_cap at least 80 + 3: the expansion then never overflows */
+#define SLAMIT_LOCAL_MAP_MAX_MAPS 8       /* maps per batch: their records travel as the kernels' argument */
+#define SLAMIT_LOCAL_MAP_BEST 10          /* GetBestCovisibilityKeyFrames(10) */
+
+/* One map.  Host pointers in the host forms, device pointers in slamit_local_map_batch_rec.maps.  The pointer arrays of the three
+ * CSR tables are trusted to ascend from 0; slots are checked. */
+struct slamit_map_index {
+    int32_t n_kf, n_mp;
+    const int32_t* obs_ptr;        /* [n_mp + 1] */
+    const int32_t* obs_kf;         /* the keyframes observing point p: obs_kf[obs_ptr[p] .. obs_ptr[p + 1]), any order */
+    const uint8_t* mp_bad;         /* [n_mp] MapPoint::isBad() */
+    const uint8_t* kf_bad;         /* [n_kf] KeyFrame::isBad() */
+    const int32_t* kf_mp_ptr;      /* [n_kf + 1] */
+    const int32_t* kf_mp;          /* GetMapPointMatches() of keyframe k by keypoint index, -1 for NULL */
+    const int32_t* kf_best;        /* [n_kf][SLAMIT_LOCAL_MAP_BEST] the first ten of mvpOrderedConnectedKeyFrames, padded with -1 */
+    const int32_t* kf_child_ptr;   /* [n_kf + 1] */
+    const int32_t* kf_child;       /* GetChilds() in the order to walk them */
+    const int32_t* kf_parent;      /* [n_kf] GetParent() */
+    const float* mp_pos;           /* [n_mp][3] GetWorldPos()       -- the last four are read by the resident form only */
+    const float* mp_normal;        /* [n_mp][3] GetNormal() */
+    const float* mp_max_dist;      /* [n_mp] the RAW mfMaxDistance, as slamit_frustum_problem documents it */
+    const float* mp_min_dist;      /* [n_mp] the raw mfMinDistance */
+};
+typedef struct slamit_map_index slamit_map_index;
+
+/* (a) + (b) for one frame (host pointers, synchronous).  frame_mp[n] in / out (mvpMapPoints as slots, n <= SLAMIT_FRAME_MAX_KP);
+ * votes[n_kf] out; local_kf[kf_cap], *n_local_kf, *ref_kf in / out; *status out.  Reads obs_*, mp_bad, kf_bad, kf_best, kf_child*,
+ * kf_parent.  A null array, a slot outside its table, n_kf above SLAMIT_LOCAL_MAP_MAX_KF or kf_cap outside
+ * [SLAMIT_LOCAL_MAP_MIN_KF_CAP, SLAMIT_LOCAL_MAP_MAX_KF] fails with SLAMIT_ERR_ARG and a message before anything is launched. */
+int slamit_local_keyframes(int device, const slamit_map_index* map, int32_t n, int32_t* frame_mp, int32_t* votes, int32_t kf_cap,
+                           int32_t* local_kf, int32_t* n_local_kf, int32_t* ref_kf, int32_t* status);
+
+/* (c) for a given keyframe list (host pointers, synchronous).  frame_mp[n] is the list (a) cleaned; frame_seen[n_seen] may be NULL
+ * with n_seen = 0; local_kf[n_local_kf].  local_mp[q_cap] and skip[q_cap] in / out: entries past min(*n_local_mp, q_cap) are left as
+ * the caller filled them.  Reads kf_mp*, mp_bad.  q_cap above SLAMIT_FRUSTUM_MAX_N, n_local_kf above SLAMIT_LOCAL_MAP_MAX_KF, a row
+ * above SLAMIT_LOCAL_MAP_MAX_ROW, a null array or a slot outside its table fails with SLAMIT_ERR_ARG before anything is launched. */
+int slamit_local_points(int device, const slamit_map_index* map, int32_t n, const int32_t* frame_mp, int32_t n_seen,
+                        const int32_t* frame_seen, int32_t n_local_kf, const int32_t* local_kf, int32_t q_cap, int32_t* local_mp,
+                        uint8_t* skip, int32_t* n_local_mp, int32_t* status);
+
+/* All three passes for nframes frames, everything resident in HBM.  `maps` is a HOST array of n_maps records holding DEVICE
+ * pointers; frame f uses maps[d_frame_map[f]] (outside [0, n_maps): the frame is left alone but for n_local_mp = m = 0 and
+ * SLAMIT_LOCAL_MAP_BAD_SLOT).  vote_cap >= every n_kf, mp_cap >= every n_mp.  Counts are clamped to their capacities.  The device
+ * cannot be shown its tables first: a slot outside its table is skipped, never dereferenced, and sets SLAMIT_LOCAL_MAP_BAD_SLOT.
+ * d_pos .. d_m are the arrays slamit_frustum_batch_dev reads, in its layout (d_m = min(n_local_mp, q_cap)), so that call and
+ * slamit_guided_search_batch_dev follow on the same stream with no host visit.  Entries past d_m[f] are not written.
+ * Asynchronous on `stream` (NULL: the legacy default stream of `device`), no synchronisation, no state; the workspace is cleared
+ * on the stream by the call. */
+struct slamit_local_map_batch_rec {
+    int32_t nframes, n_maps, kp_cap, seen_cap, kf_cap, q_cap, vote_cap, mp_cap;
+    const slamit_map_index* maps;  /* HOST [n_maps], device pointers inside; n_maps <= SLAMIT_LOCAL_MAP_MAX_MAPS */
+    const int32_t* d_frame_map;    /* [nframes] */
+    const int32_t* d_n;            /* [nframes] keypoints per frame */
+    int32_t* d_frame_mp;           /* [nframes][kp_cap] in / out */
+    const int32_t* d_n_seen;       /* [nframes], nullable together with d_frame_seen */
+    const int32_t* d_frame_seen;   /* [nframes][seen_cap] */
+    int32_t* d_votes;              /* [nframes][vote_cap] out: the first n_kf of a frame's row, the rest 0 */
+    int32_t* d_local_kf;           /* [nframes][kf_cap] in / out */
+    int32_t* d_n_local_kf;         /* [nframes] in / out */
+    int32_t* d_ref_kf;             /* [nframes] in / out */
+    int32_t* d_local_mp;           /* [nframes][q_cap] out */
+    int32_t* d_n_local_mp;         /* [nframes] out: the number needed */
+    float* d_pos;                  /* [nframes][3][q_cap] out */
+    float* d_normal;               /* [nframes][3][q_cap] out */
+    float* d_max_dist;             /* [nframes][q_cap] out */
+    float* d_min_dist;             /* [nframes][q_cap] out */
+    uint8_t* d_skip;               /* [nframes][q_cap] out */
+    int32_t* d_m;                  /* [nframes] out */
+    int32_t* d_status;             /* [nframes] out */
+    void* d_workspace;             /* slamit_local_map_workspace(nframes, mp_cap, kf_cap) bytes */
+    size_t workspace_bytes;
+};
+typedef struct slamit_local_map_batch_rec slamit_local_map_batch_rec;
+size_t slamit_local_map_workspace(int nframes, int mp_cap, int kf_cap);
+int slamit_local_map_batch_dev(int device, const slamit_local_map_batch_rec* batch, void* stream);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 
 const char* slamit_last_error(void);

@@ -296,6 +296,30 @@ class UnprojectBatchRec(C.Structure):
                 ("d_counts", C.c_void_p)]
 
 
+class MapIndexRec(C.Structure):   # struct slamit_map_index
+    _fields_ = [("n_kf", C.c_int32), ("n_mp", C.c_int32), ("obs_ptr", C.c_void_p), ("obs_kf", C.c_void_p), ("mp_bad", C.c_void_p),
+                ("kf_bad", C.c_void_p), ("kf_mp_ptr", C.c_void_p), ("kf_mp", C.c_void_p), ("kf_best", C.c_void_p), ("kf_child_ptr", C.c_void_p),
+                ("kf_child", C.c_void_p), ("kf_parent", C.c_void_p), ("mp_pos", C.c_void_p), ("mp_normal", C.c_void_p),
+                ("mp_max_dist", C.c_void_p), ("mp_min_dist", C.c_void_p)]
+
+
+class LocalMapBatchRec(C.Structure):   # struct slamit_local_map_batch_rec
+    _fields_ = [("nframes", C.c_int32), ("n_maps", C.c_int32), ("kp_cap", C.c_int32), ("seen_cap", C.c_int32), ("kf_cap", C.c_int32),
+                ("q_cap", C.c_int32), ("vote_cap", C.c_int32), ("mp_cap", C.c_int32), ("maps", C.POINTER(MapIndexRec)), ("d_frame_map", C.c_void_p),
+                ("d_n", C.c_void_p), ("d_frame_mp", C.c_void_p), ("d_n_seen", C.c_void_p), ("d_frame_seen", C.c_void_p), ("d_votes", C.c_void_p),
+                ("d_local_kf", C.c_void_p), ("d_n_local_kf", C.c_void_p), ("d_ref_kf", C.c_void_p), ("d_local_mp", C.c_void_p),
+                ("d_n_local_mp", C.c_void_p), ("d_pos", C.c_void_p), ("d_normal", C.c_void_p), ("d_max_dist", C.c_void_p),
+                ("d_min_dist", C.c_void_p), ("d_skip", C.c_void_p), ("d_m", C.c_void_p), ("d_status", C.c_void_p), ("d_workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
+
+
+# SLAMIT_LOCAL_MAP_*: the status bits, then MAX_KF, MAX_ROW, MIN_KF_CAP, MAX_MAPS, BEST
+LOCAL_MAP_STATUS = {"BAD_SLOT": 1, "KF_OVERFLOW": 2, "MP_OVERFLOW": 4, "ROW_CUT": 8}
+LOCAL_MAP_MAX_KF, LOCAL_MAP_MAX_ROW, LOCAL_MAP_MIN_KF_CAP, LOCAL_MAP_MAX_MAPS, LOCAL_MAP_BEST = 65535, 65536, 83, 8, 10
+# slamit_map_index: the tables and their element types, in the record's order
+MAP_INDEX_TABLES = (("obs_ptr", np.int32), ("obs_kf", np.int32), ("mp_bad", np.uint8), ("kf_bad", np.uint8), ("kf_mp_ptr", np.int32),
+                    ("kf_mp", np.int32), ("kf_best", np.int32), ("kf_child_ptr", np.int32), ("kf_child", np.int32), ("kf_parent", np.int32),
+                    ("mp_pos", np.float32), ("mp_normal", np.float32), ("mp_max_dist", np.float32), ("mp_min_dist", np.float32))
 DEPTH_TYPES = ("f32", "u16")   # SLAMIT_DEPTH_*: the index is the type
 DEPTH_PLANE_DTYPE = np.dtype([("data", "<u8"), ("pitch", "<u8"), ("width", "<i4"), ("height", "<i4"), ("type", "<i4"), ("factor", "<f4")])   # slamit_depth_plane
 RGBD_STATUS = ("no_depth", "depth", "outside")
@@ -367,7 +391,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -446,6 +470,11 @@ def lib():
         L.slamit_unproject_closest_batch.argtypes = [i32, i32, C.POINTER(UnprojectProblem), C.POINTER(UnprojectResult)]
         L.slamit_unproject_closest.argtypes = [i32, C.POINTER(UnprojectProblem), C.POINTER(UnprojectResult)]
         L.slamit_unproject_closest_batch_dev.argtypes = [i32, C.POINTER(UnprojectBatchRec), vp]
+        L.slamit_local_keyframes.argtypes = [i32, C.POINTER(MapIndexRec), i32, vp, vp, i32, vp, vp, vp, vp]
+        L.slamit_local_points.argtypes = [i32, C.POINTER(MapIndexRec), i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp]
+        L.slamit_local_map_workspace.argtypes = [i32, i32, i32]
+        L.slamit_local_map_workspace.restype = sz
+        L.slamit_local_map_batch_dev.argtypes = [i32, C.POINTER(LocalMapBatchRec), vp]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_bow_search_stereo.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), C.POINTER(BowStereo), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
@@ -2254,3 +2283,108 @@ def unproject_closest_batch_dev(t, device=0, stream=None):
                             t["pos"].data_ptr(), t["octave"].data_ptr(), t["skip"].data_ptr(), opt("normal"), opt("max_dist"), opt("min_dist"),
                             opt("status"), opt("order"), opt("counts"))
     _check(lib().slamit_unproject_closest_batch_dev(device, C.byref(rec), stream), "slamit_unproject_closest_batch_dev")
+
+
+def _map_index_host(tables):
+    """A map's tables (dict in the layout of slamit_map_index; a missing table is NULL) as a MapIndexRec of host pointers and the arrays
+    that keep them alive."""
+    keep = {}
+    rec = MapIndexRec(int(tables["n_kf"]), int(tables["n_mp"]))
+    for key, dt in MAP_INDEX_TABLES:
+        if tables.get(key) is not None:
+            keep[key] = np.ascontiguousarray(tables[key], dt).reshape(-1)
+            setattr(rec, key, keep[key].ctypes.data)
+    return rec, keep
+
+
+def local_keyframes(tables, frame_mp, local_kf=(), ref_kf=-1, kf_cap=128, device=0):
+    """Tracking::UpdateLocalKeyFrames (Tracking.cc:1512-1626) for one frame over a map's tables (dict in the layout of slamit_map_index:
+    n_kf, n_mp, obs_ptr, obs_kf, mp_bad, kf_bad, kf_best (n_kf, 10), kf_child_ptr, kf_child, kf_parent; every id a slot, -1 = none).
+    frame_mp: mvpMapPoints as slots; local_kf / ref_kf: the list and the reference keyframe as they stand (they survive a frame in
+    which no keyframe gets a vote).  -> dict(votes (n_kf), frame_mp (bad points set to -1), local_kf (the list), n_local_kf (the
+    size needed: above kf_cap the list is cut), ref_kf, status).  Voted keyframes in ascending slot order, children as given."""
+    rec, keep = _map_index_host(tables)
+    mp = np.array(frame_mp, np.int32).reshape(-1)
+    lk = np.full(max(int(kf_cap), 0), -1, np.int32)
+    cur = np.asarray(local_kf, np.int32).reshape(-1)
+    if len(cur) > len(lk):
+        raise SlamitError("local_keyframes: the list as it stands does not fit kf_cap")
+    lk[:len(cur)] = cur
+    votes = np.zeros(max(rec.n_kf, 0), np.int32)
+    nlk, ref, st = np.array([len(cur)], np.int32), np.array([ref_kf], np.int32), np.zeros(1, np.int32)
+    _check(lib().slamit_local_keyframes(device, C.byref(rec), len(mp), _np_ptr(mp), _np_ptr(votes), int(kf_cap), _np_ptr(lk), _np_ptr(nlk),
+                                        _np_ptr(ref), _np_ptr(st)), "slamit_local_keyframes")
+    del keep
+    return {"votes": votes, "frame_mp": mp, "local_kf": lk[:min(int(nlk[0]), len(lk))].copy(), "n_local_kf": int(nlk[0]), "ref_kf": int(ref[0]),
+            "status": int(st[0])}
+
+
+def local_points(tables, frame_mp, local_kf, frame_seen=(), q_cap=4096, fill=-1, device=0):
+    """Tracking::UpdateLocalPoints (Tracking.cc:1477-1509) for a keyframe list, with the skip flags of SearchLocalPoints (:1412-1437), over a
+    map's tables (n_kf, n_mp, mp_bad, kf_mp_ptr, kf_mp).  frame_mp: the list local_keyframes cleaned; frame_seen: slots already seen
+    this frame.  -> dict(local_mp (q_cap) int32 and skip (q_cap) uint8, entries past min(n_local_mp, q_cap) left at `fill` / 0xff,
+    n_local_mp (the number needed), status)."""
+    rec, keep = _map_index_host(tables)
+    mp = np.ascontiguousarray(frame_mp, np.int32).reshape(-1)
+    seen = np.ascontiguousarray(frame_seen, np.int32).reshape(-1)
+    lk = np.ascontiguousarray(local_kf, np.int32).reshape(-1)
+    out = np.full(max(int(q_cap), 0), fill, np.int32)
+    skip = np.full(max(int(q_cap), 0), 0xff, np.uint8)
+    nmp, st = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    _check(lib().slamit_local_points(device, C.byref(rec), len(mp), _np_ptr(mp), len(seen), _np_ptr(seen) if len(seen) else None, len(lk), _np_ptr(lk),
+                                     int(q_cap), _np_ptr(out), _np_ptr(skip), _np_ptr(nmp), _np_ptr(st)), "slamit_local_points")
+    del keep
+    return {"local_mp": out, "skip": skip, "n_local_mp": int(nmp[0]), "status": int(st[0])}
+
+
+class MapIndex:
+    """A map's tables uploaded once (the resident form's slamit_map_index): MapIndex(tables).rec holds the device pointers.  The caller
+    re-uploads a table when the map changes it; nothing here is per frame."""
+
+    def __init__(self, tables, device=0):
+        import torch
+
+        self.n_kf, self.n_mp, self.device = int(tables["n_kf"]), int(tables["n_mp"]), device
+        self.t = {}
+        self.rec = MapIndexRec(self.n_kf, self.n_mp)
+        for key, dt in MAP_INDEX_TABLES:
+            a = np.ascontiguousarray(tables[key], dt).reshape(-1)
+            # an empty table still needs an address: the resident form refuses NULL
+            self.t[key] = torch.from_numpy(a if len(a) else np.zeros(1, dt)).to("cuda:%d" % device)
+            setattr(self.rec, key, self.t[key].data_ptr())
+
+
+def local_map_workspace(nframes, mp_cap, kf_cap):
+    return int(lib().slamit_local_map_workspace(nframes, mp_cap, kf_cap))
+
+
+def local_map_batch_dev(maps, t, device=0, stream=None):
+    """Tracking::UpdateLocalMap for a batch of frames, resident.  maps: a list of MapIndex; t: dict of torch CUDA tensors frame_map (B) i32,
+    n (B) i32, frame_mp (B, kp_cap) i32 in / out, optionally n_seen (B) and frame_seen (B, seen_cap) i32, votes (B, vote_cap) i32,
+    local_kf (B, kf_cap) i32 / n_local_kf (B) / ref_kf (B) in / out, local_mp (B, q_cap) i32, n_local_mp (B) i32, and the tensors
+    frustum_batch_dev reads: pos / normal (B, 3, q_cap) f32, max_dist / min_dist (B, q_cap) f32, skip (B, q_cap) u8, m (B) i32; status (B)
+    i32; workspace: uint8, local_map_workspace(B, mp_cap, kf_cap) bytes with mp_cap = t["mp_cap"] >= every map's n_mp.
+    Asynchronous on `stream`."""
+    b, kp_cap = t["frame_mp"].shape
+    q_cap, kf_cap, vote_cap = t["local_mp"].shape[1], t["local_kf"].shape[1], t["votes"].shape[1]
+    for key, per in (("frame_mp", kp_cap), ("votes", vote_cap), ("local_kf", kf_cap), ("local_mp", q_cap), ("pos", 3 * q_cap), ("normal", 3 * q_cap),
+                     ("max_dist", q_cap), ("min_dist", q_cap), ("skip", q_cap), ("frame_map", 1), ("n", 1), ("n_local_kf", 1), ("ref_kf", 1),
+                     ("n_local_mp", 1), ("m", 1), ("status", 1)):
+        if t[key].numel() != b * per or not t[key].is_contiguous():
+            raise SlamitError("local_map_batch_dev: %s is not a contiguous array of %d entries per frame" % (key, per))
+    seen_cap = 0
+    if t.get("frame_seen") is not None:
+        seen_cap = t["frame_seen"].shape[1]
+        if t["frame_seen"].numel() != b * seen_cap or not t["frame_seen"].is_contiguous() or t["n_seen"].numel() != b:
+            raise SlamitError("local_map_batch_dev: frame_seen / n_seen do not hold one row per frame")
+    M = (MapIndexRec * max(len(maps), 1))()
+    for i, mi in enumerate(maps):
+        M[i] = mi.rec
+    ws = t["workspace"]
+    rec = LocalMapBatchRec(b, len(maps), kp_cap, seen_cap, kf_cap, q_cap, vote_cap, int(t["mp_cap"]), M, t["frame_map"].data_ptr(), t["n"].data_ptr(),
+                           t["frame_mp"].data_ptr(), t["n_seen"].data_ptr() if seen_cap or t.get("frame_seen") is not None else None,
+                           t["frame_seen"].data_ptr() if t.get("frame_seen") is not None else None, t["votes"].data_ptr(), t["local_kf"].data_ptr(),
+                           t["n_local_kf"].data_ptr(), t["ref_kf"].data_ptr(), t["local_mp"].data_ptr(), t["n_local_mp"].data_ptr(),
+                           t["pos"].data_ptr(), t["normal"].data_ptr(), t["max_dist"].data_ptr(), t["min_dist"].data_ptr(), t["skip"].data_ptr(),
+                           t["m"].data_ptr(), t["status"].data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
+    _check(lib().slamit_local_map_batch_dev(device, C.byref(rec), stream), "slamit_local_map_batch_dev")

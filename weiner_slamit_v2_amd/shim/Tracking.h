@@ -16,6 +16,9 @@
 // mvScaleFactors out of bounds in the search.  Here such a point (status 7) gets mbTrackInView = false: it is not counted in
 // nToMatch, IncreaseVisible is not called for it and it is not searched.
 //
+// Tracking::UpdateLocalMap (:1467-1626) is documented at the function: slot tables built from the caller's objects, two calls
+// (slamit_local_keyframes, slamit_local_points), for parity rather than speed.
+//
 // A non-SLAMIT_OK status of a device call is reported on stderr with LastStatus() set, and ends the function: never a silent return.
 //
 // STEREO AND RGB-D: the closest-point walks of Tracking::UpdateLastFrame (Tracking.cc:1037-1091), of the stereo
@@ -39,7 +42,10 @@
 
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
+#include <map>
+#include <set>
 #include <vector>
 
 #include "ORBmatcher.h"
@@ -119,6 +125,133 @@ public:
         return nmatches;
     }
 
+    // Tracking::UpdateLocalMap (:1467-1626): UpdateLocalKeyFrames, then UpdateLocalPoints.  localKFs / refKF / localMPs are
+    // mvpLocalKeyFrames / mpReferenceKF / mvpLocalMapPoints: in / out, since a frame in which no keyframe gets a vote keeps its list.
+    // Writes them back with F.mvpMapPoints (bad points become NULL), F.mpReferenceKF and the mnTrackReferenceForFrame marks of the
+    // listed keyframes and points.  Returns the number of local points.
+    //
+    // The keyframes that can matter -- the observers of the frame's points, their best ten, children and parent, and the list as it
+    // stands -- are numbered by std::less<KeyFrameT*> and children are listed in set order, so slamit_local_keyframes' "ascending
+    // slot, children as given" is the reference's address order on this run (csrc/local_map.h).
+    // WHAT THIS COSTS: building the tables from host objects walks the same observers, neighbours and point lists as the host loop
+    // itself, so this function is for parity and for integrations that want one code path; the gain is slamit_local_map_batch_dev
+    // with the tables kept in HBM.  Members used: Frame mnId, mvpMapPoints, mpReferenceKF; MapPoint isBad(), GetObservations(),
+    // mnTrackReferenceForFrame; KeyFrame isBad(), GetBestCovisibilityKeyFrames(int), GetChilds(), GetParent(), GetMapPointMatches(),
+    // mnTrackReferenceForFrame.
+    template <class FrameT, class KeyFrameT, class MapPointT>
+    static int UpdateLocalMap(FrameT& F, std::vector<KeyFrameT*>& localKFs, std::vector<MapPointT*>& localMPs, KeyFrameT*& refKF, int device = 0) {
+        status() = SLAMIT_OK;
+        // the observers, then one hop; a std::set orders by std::less
+        std::set<KeyFrameT*> observers, all;
+        for (size_t i = 0; i < F.mvpMapPoints.size(); ++i) {
+            MapPointT* pMP = F.mvpMapPoints[i];
+            if (!pMP || pMP->isBad()) continue;
+            const std::map<KeyFrameT*, size_t> obs = pMP->GetObservations();
+            for (typename std::map<KeyFrameT*, size_t>::const_iterator it = obs.begin(); it != obs.end(); ++it) observers.insert(it->first);
+        }
+        all = observers;
+        for (typename std::set<KeyFrameT*>::const_iterator it = observers.begin(); it != observers.end(); ++it) {
+            const std::vector<KeyFrameT*> best = (*it)->GetBestCovisibilityKeyFrames(SLAMIT_LOCAL_MAP_BEST);
+            all.insert(best.begin(), best.end());
+            const std::set<KeyFrameT*> childs = (*it)->GetChilds();
+            all.insert(childs.begin(), childs.end());
+            if ((*it)->GetParent()) all.insert((*it)->GetParent());
+        }
+        all.insert(localKFs.begin(), localKFs.end());
+        const std::vector<KeyFrameT*> kfs(all.begin(), all.end());
+        std::map<KeyFrameT*, int32_t> kfSlot;
+        for (size_t k = 0; k < kfs.size(); ++k) kfSlot[kfs[k]] = (int32_t)k;
+        const int n_kf = (int)kfs.size();
+        if (n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return shim::refuse<Tracking>("UpdateLocalMap: more than SLAMIT_LOCAL_MAP_MAX_KF keyframes around the frame");
+        // the points: the frame's, then every listed keyframe's, numbered as they come
+        std::map<MapPointT*, int32_t> mpSlot;
+        std::vector<MapPointT*> mps;
+        std::vector<int32_t> frame_mp(F.mvpMapPoints.size(), -1);
+        for (size_t i = 0; i < F.mvpMapPoints.size(); ++i) {
+            MapPointT* pMP = F.mvpMapPoints[i];
+            if (pMP) frame_mp[i] = slotOf(mpSlot, mps, pMP);
+        }
+        std::vector<int32_t> kf_mp_ptr(n_kf + 1, 0), kf_mp, kf_best((size_t)n_kf * SLAMIT_LOCAL_MAP_BEST, -1), kf_child_ptr(n_kf + 1, 0), kf_child, kf_parent(n_kf, -1);
+        std::vector<uint8_t> kf_bad(n_kf, 0);
+        for (int k = 0; k < n_kf; ++k) {
+            KeyFrameT* pKF = kfs[k];
+            kf_bad[k] = pKF->isBad() ? 1 : 0;
+            const std::vector<MapPointT*> vpMPs = pKF->GetMapPointMatches();
+            for (size_t i = 0; i < vpMPs.size(); ++i) kf_mp.push_back(vpMPs[i] ? slotOf(mpSlot, mps, vpMPs[i]) : -1);
+            kf_mp_ptr[k + 1] = (int32_t)kf_mp.size();
+            if (observers.count(pKF)) {   // the walk visits voted keyframes only: the others' neighbours are never read
+                const std::vector<KeyFrameT*> best = pKF->GetBestCovisibilityKeyFrames(SLAMIT_LOCAL_MAP_BEST);
+                for (size_t b = 0; b < best.size() && b < SLAMIT_LOCAL_MAP_BEST; ++b) kf_best[(size_t)k * SLAMIT_LOCAL_MAP_BEST + b] = kfSlot[best[b]];
+                const std::set<KeyFrameT*> childs = pKF->GetChilds();
+                for (typename std::set<KeyFrameT*>::const_iterator c = childs.begin(); c != childs.end(); ++c) kf_child.push_back(kfSlot[*c]);
+                if (pKF->GetParent()) kf_parent[k] = kfSlot[pKF->GetParent()];
+            }
+            kf_child_ptr[k + 1] = (int32_t)kf_child.size();
+        }
+        const int n_mp = (int)mps.size();
+        std::vector<int32_t> obs_ptr(n_mp + 1, 0), obs_kf;
+        std::vector<uint8_t> mp_bad(n_mp, 0);
+        std::vector<uint8_t> inFrame(n_mp, 0);
+        for (size_t i = 0; i < frame_mp.size(); ++i)
+            if (frame_mp[i] >= 0) inFrame[frame_mp[i]] = 1;
+        for (int p = 0; p < n_mp; ++p) {
+            mp_bad[p] = mps[p]->isBad() ? 1 : 0;
+            if (inFrame[p] && !mp_bad[p]) {   // only the frame's points vote
+                const std::map<KeyFrameT*, size_t> obs = mps[p]->GetObservations();
+                for (typename std::map<KeyFrameT*, size_t>::const_iterator it = obs.begin(); it != obs.end(); ++it) obs_kf.push_back(kfSlot[it->first]);
+            }
+            obs_ptr[p + 1] = (int32_t)obs_kf.size();
+        }
+        slamit_map_index M;
+        memset(&M, 0, sizeof(M));
+        uint8_t none8 = 0;
+        int32_t none32 = -1;
+        M.n_kf = n_kf; M.n_mp = n_mp;
+        M.obs_ptr = obs_ptr.data(); M.obs_kf = obs_kf.empty() ? &none32 : obs_kf.data(); M.mp_bad = n_mp ? mp_bad.data() : &none8;
+        M.kf_bad = n_kf ? kf_bad.data() : &none8; M.kf_mp_ptr = kf_mp_ptr.data(); M.kf_mp = kf_mp.empty() ? &none32 : kf_mp.data();
+        M.kf_best = n_kf ? kf_best.data() : &none32; M.kf_child_ptr = kf_child_ptr.data(); M.kf_child = kf_child.empty() ? &none32 : kf_child.data();
+        M.kf_parent = n_kf ? kf_parent.data() : &none32;
+        // UpdateLocalKeyFrames
+        const int kf_cap = n_kf > SLAMIT_LOCAL_MAP_MIN_KF_CAP ? n_kf : SLAMIT_LOCAL_MAP_MIN_KF_CAP;
+        std::vector<int32_t> votes(n_kf + 1, 0), list(kf_cap, -1);
+        for (size_t j = 0; j < localKFs.size(); ++j) list[j] = kfSlot[localKFs[j]];
+        int32_t n_list = (int32_t)localKFs.size(), ref = -1, st = 0;
+        int rc = slamit_local_keyframes(device, &M, (int32_t)frame_mp.size(), frame_mp.empty() ? &none32 : frame_mp.data(), votes.data(), kf_cap, list.data(),
+                                        &n_list, &ref, &st);
+        if (rc != SLAMIT_OK) return shim::report<Tracking>("UpdateLocalMap: slamit_local_keyframes", rc);
+        if (st != 0 || n_list > kf_cap) return shim::refuse<Tracking>("UpdateLocalMap: slamit_local_keyframes reported a status on tables built here", SLAMIT_ERR_STATE);
+        for (size_t i = 0; i < frame_mp.size(); ++i)
+            if (frame_mp[i] < 0) F.mvpMapPoints[i] = static_cast<MapPointT*>(NULL);   // :1535
+        bool voted = false;
+        for (int k = 0; k < n_kf; ++k) voted = voted || votes[k] > 0;
+        if (voted) {   // :1546-1619; without a vote the reference returned before clear()
+            localKFs.clear();
+            for (int j = 0; j < n_list; ++j) {
+                localKFs.push_back(kfs[list[j]]);
+                kfs[list[j]]->mnTrackReferenceForFrame = F.mnId;
+            }
+        }
+        if (ref >= 0) {   // :1621-1625: pKFmax
+            refKF = kfs[ref];
+            F.mpReferenceKF = refKF;
+        }
+        // UpdateLocalPoints
+        localMPs.clear();
+        if (n_mp > SLAMIT_FRUSTUM_MAX_N) return shim::refuse<Tracking>("UpdateLocalMap: more than SLAMIT_FRUSTUM_MAX_N map points around the frame", SLAMIT_ERR_CAPACITY);
+        std::vector<int32_t> local_mp(n_mp + 1, -1);
+        std::vector<uint8_t> skip(n_mp + 1, 0);
+        int32_t n_local = 0;
+        rc = slamit_local_points(device, &M, (int32_t)frame_mp.size(), frame_mp.empty() ? &none32 : frame_mp.data(), 0, NULL, n_list, list.data(), n_mp,
+                                 local_mp.data(), skip.data(), &n_local, &st);
+        if (rc != SLAMIT_OK) return shim::report<Tracking>("UpdateLocalMap: slamit_local_points", rc);
+        if (st != 0 || n_local > n_mp) return shim::refuse<Tracking>("UpdateLocalMap: slamit_local_points reported a status on tables built here", SLAMIT_ERR_STATE);
+        for (int i = 0; i < n_local; ++i) {
+            localMPs.push_back(mps[local_mp[i]]);
+            mps[local_mp[i]]->mnTrackReferenceForFrame = F.mnId;
+        }
+        return n_local;
+    }
+
     // Tracking::UpdateLastFrame after the pose update and the two early returns (:1037-1091): the "visual odometry" points of the last
     // frame.  temporal is mlpTemporalPoints.  Returns the number of points created.
     template <class FrameT, class TemporalT, class MakeFn>
@@ -183,6 +316,17 @@ private:
     static int& status() { return shim::status<Tracking>(); }
     static int& inView() { static thread_local int s = 0; return s; }
     static slamit_unproject_counts& counts() { static thread_local slamit_unproject_counts c = {0, 0, 0, 0, 0, 0}; return c; }
+
+    // the slot of a map point in UpdateLocalMap's numbering: a new one on first sight
+    template <class MapPointT>
+    static int32_t slotOf(std::map<MapPointT*, int32_t>& slots, std::vector<MapPointT*>& mps, MapPointT* p) {
+        typename std::map<MapPointT*, int32_t>::const_iterator it = slots.find(p);
+        if (it != slots.end()) return it->second;
+        const int32_t s = (int32_t)mps.size();
+        slots[p] = s;
+        mps.push_back(p);
+        return s;
+    }
 
     struct Walk {
         std::vector<uint8_t> status;

@@ -19,10 +19,12 @@
 //     shim_test frustum <problem.bin> <out.bin>
 //     shim_test stereo <pair.bin> <out.bin>
 //     shim_test unproject <problem.bin> <out.bin>
+//     shim_test local_map <seed> <keyframes> <points> <keypoints>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <set>
@@ -1550,6 +1552,193 @@ static int run_unproject(int argc, char** argv) {
     return 0;
 }
 
+// ---- local_map: Tracking::UpdateLocalMap over mock types whose addresses are NOT in creation order ------------------------------
+struct MockLmKF;
+struct MockLmPoint {
+    bool bad;
+    std::map<MockLmKF*, size_t> obs;
+    long unsigned int mnTrackReferenceForFrame;
+    MockLmPoint() : bad(false), mnTrackReferenceForFrame(0) {}
+    bool isBad() const { return bad; }
+    std::map<MockLmKF*, size_t> GetObservations() const { return obs; }
+};
+struct MockLmKF {
+    bool bad;
+    std::vector<MockLmPoint*> pts;
+    std::vector<MockLmKF*> ordered;
+    std::set<MockLmKF*> childs;
+    MockLmKF* parent;
+    long unsigned int mnTrackReferenceForFrame;
+    MockLmKF() : bad(false), parent(NULL), mnTrackReferenceForFrame(0) {}
+    bool isBad() const { return bad; }
+    std::vector<MockLmPoint*> GetMapPointMatches() const { return pts; }
+    std::vector<MockLmKF*> GetBestCovisibilityKeyFrames(int n) const {
+        return (int)ordered.size() < n ? ordered : std::vector<MockLmKF*>(ordered.begin(), ordered.begin() + n);
+    }
+    std::set<MockLmKF*> GetChilds() const { return childs; }
+    MockLmKF* GetParent() const { return parent; }
+};
+struct MockLmFrame {
+    long unsigned int mnId;
+    std::vector<MockLmPoint*> mvpMapPoints;
+    MockLmKF* mpReferenceKF;
+};
+
+// The host loops the shim stands in for, over the same mock types: votes per observer in a std::map, the voted keyframes in the map's
+// order, one neighbour, one child and the parent per visited keyframe, then the keyframes' points once each.
+static void plain_update_local_map(MockLmFrame& F, std::vector<MockLmKF*>& localKFs, std::vector<MockLmPoint*>& localMPs, MockLmKF*& refKF) {
+    std::map<MockLmKF*, int> counter;
+    for (size_t i = 0; i < F.mvpMapPoints.size(); ++i) {
+        MockLmPoint* p = F.mvpMapPoints[i];
+        if (!p) continue;
+        if (p->isBad()) { F.mvpMapPoints[i] = NULL; continue; }
+        const std::map<MockLmKF*, size_t> obs = p->GetObservations();
+        for (std::map<MockLmKF*, size_t>::const_iterator it = obs.begin(); it != obs.end(); ++it) counter[it->first]++;
+    }
+    if (!counter.empty()) {
+        int best = 0;
+        MockLmKF* bestKF = NULL;
+        localKFs.clear();
+        for (std::map<MockLmKF*, int>::const_iterator it = counter.begin(); it != counter.end(); ++it) {
+            if (it->first->isBad()) continue;
+            if (it->second > best) { best = it->second; bestKF = it->first; }
+            localKFs.push_back(it->first);
+            it->first->mnTrackReferenceForFrame = F.mnId;
+        }
+        const size_t voted = localKFs.size();
+        for (size_t v = 0; v < voted; ++v) {
+            if (localKFs.size() > 80) break;
+            MockLmKF* kf = localKFs[v];
+            const std::vector<MockLmKF*> neigh = kf->GetBestCovisibilityKeyFrames(10);
+            for (size_t j = 0; j < neigh.size(); ++j)
+                if (!neigh[j]->isBad() && neigh[j]->mnTrackReferenceForFrame != F.mnId) {
+                    localKFs.push_back(neigh[j]);
+                    neigh[j]->mnTrackReferenceForFrame = F.mnId;
+                    break;
+                }
+            const std::set<MockLmKF*> childs = kf->GetChilds();
+            for (std::set<MockLmKF*>::const_iterator c = childs.begin(); c != childs.end(); ++c)
+                if (!(*c)->isBad() && (*c)->mnTrackReferenceForFrame != F.mnId) {
+                    localKFs.push_back(*c);
+                    (*c)->mnTrackReferenceForFrame = F.mnId;
+                    break;
+                }
+            MockLmKF* parent = kf->GetParent();
+            if (parent && parent->mnTrackReferenceForFrame != F.mnId) {
+                localKFs.push_back(parent);
+                parent->mnTrackReferenceForFrame = F.mnId;
+                break;
+            }
+        }
+        if (bestKF) { refKF = bestKF; F.mpReferenceKF = bestKF; }
+    }
+    localMPs.clear();
+    for (size_t k = 0; k < localKFs.size(); ++k) {
+        const std::vector<MockLmPoint*> pts = localKFs[k]->GetMapPointMatches();
+        for (size_t i = 0; i < pts.size(); ++i) {
+            MockLmPoint* p = pts[i];
+            if (!p || p->mnTrackReferenceForFrame == F.mnId || p->isBad()) continue;
+            localMPs.push_back(p);
+            p->mnTrackReferenceForFrame = F.mnId;
+        }
+    }
+}
+
+//     shim_test local_map <seed> <keyframes> <points> <keypoints>
+// Three scenarios on one generated map (a frame with observers, one whose points nobody observes, one whose observers are all bad);
+// each runs the plain loops and Tracking::UpdateLocalMap from the same state and prints one line ending in MATCH or MISMATCH.
+static int run_local_map(int argc, char** argv) {
+    if (argc != 6) return 2;
+    unsigned long long rng = 0x9e3779b97f4a7c15ULL ^ (unsigned long long)atoll(argv[2]);
+    const int K = atoi(argv[3]), NP = atoi(argv[4]), NKP = atoi(argv[5]);
+    if (K < 4 || NP < 2 * K || NKP < 1) return 2;
+    struct Rand {
+        unsigned long long& s;
+        unsigned next(unsigned mod) { s = s * 6364136223846793005ULL + 1442695040888963407ULL; return (unsigned)(s >> 33) % mod; }
+    } R = {rng};
+    std::vector<MockLmKF> kfPool(K);
+    std::vector<MockLmPoint> mpPool(NP + 8);   // the last 8 are in no keyframe
+    std::vector<int> perm(K);
+    for (int i = 0; i < K; ++i) perm[i] = i;
+    for (int i = K - 1; i > 0; --i) std::swap(perm[i], perm[R.next(i + 1)]);   // creation order i lives at address perm[i]
+    std::vector<MockLmKF*> kf(K);
+    for (int i = 0; i < K; ++i) kf[i] = &kfPool[perm[i]];
+    const int width = 3 * NP / K + 4;
+    for (int i = 0; i < K; ++i) {
+        const int lo = (int)((long long)i * (NP - width) / (K - 1));
+        kf[i]->bad = R.next(10) == 0;
+        kf[i]->pts.assign(width + 10, (MockLmPoint*)NULL);
+        for (int j = 0; j < width; ++j) {
+            if (R.next(5) == 0) continue;
+            MockLmPoint* p = &mpPool[lo + j];
+            const size_t at = R.next(width + 10);
+            if (kf[i]->pts[at]) continue;
+            kf[i]->pts[at] = p;
+            p->obs[kf[i]] = at;
+        }
+        if (i > 0) { kf[i]->parent = kf[R.next(3) == 0 && i > 1 ? i - 2 : i - 1]; kf[i]->parent->childs.insert(kf[i]); }
+    }
+    for (int p = 0; p < NP; ++p) mpPool[p].bad = R.next(20) == 0;
+    for (int i = 0; i < K; ++i) {   // neighbours by shared points, the strongest first
+        std::map<MockLmKF*, int> w;
+        for (size_t j = 0; j < kf[i]->pts.size(); ++j)
+            if (kf[i]->pts[j])
+                for (std::map<MockLmKF*, size_t>::const_iterator it = kf[i]->pts[j]->obs.begin(); it != kf[i]->pts[j]->obs.end(); ++it)
+                    if (it->first != kf[i]) w[it->first]++;
+        std::vector<std::pair<int, MockLmKF*> > order;
+        for (std::map<MockLmKF*, int>::const_iterator it = w.begin(); it != w.end(); ++it) order.push_back(std::make_pair(-it->second, it->first));
+        std::sort(order.begin(), order.end());
+        for (size_t j = 0; j < order.size(); ++j) kf[i]->ordered.push_back(order[j].second);
+    }
+    bool shuffled = false;
+    for (int i = 1; i < K; ++i) shuffled = shuffled || kf[i] < kf[i - 1];
+    printf("local_map keyframes=%d points=%d addresses_shuffled=%d\n", K, NP, shuffled ? 1 : 0);
+    int failures = 0;
+    for (int scenario = 0; scenario < 3; ++scenario) {
+        std::vector<bool> wasBad(K);
+        for (int i = 0; i < K; ++i) wasBad[i] = kf[i]->bad;
+        std::vector<MockLmPoint*> tracked(NKP, (MockLmPoint*)NULL);
+        const int lo = NP / 3;
+        for (int i = 0; i < NKP; ++i) {
+            if (R.next(3) == 0) continue;
+            tracked[i] = scenario == 1 ? &mpPool[NP + R.next(8)] : &mpPool[lo + R.next(NP / 4)];
+        }
+        if (scenario == 2)
+            for (int i = 0; i < NKP; ++i)
+                if (tracked[i])
+                    for (std::map<MockLmKF*, size_t>::const_iterator it = tracked[i]->obs.begin(); it != tracked[i]->obs.end(); ++it) it->first->bad = true;
+        const std::vector<MockLmKF*> startKFs(1, kf[K / 2]);
+        MockLmKF* const startRef = kf[K / 2];
+        // the plain loops
+        MockLmFrame FA = {100ul + 2 * scenario, tracked, NULL};
+        std::vector<MockLmKF*> kfsA = startKFs;
+        std::vector<MockLmPoint*> mpsA;
+        MockLmKF* refA = startRef;
+        plain_update_local_map(FA, kfsA, mpsA, refA);
+        // the shim, from the same state under another frame id
+        MockLmFrame FB = {101ul + 2 * scenario, tracked, NULL};
+        std::vector<MockLmKF*> kfsB = startKFs;
+        std::vector<MockLmPoint*> mpsB;
+        MockLmKF* refB = startRef;
+        const int nB = Tracking::UpdateLocalMap(FB, kfsB, mpsB, refB);
+        const int status = Tracking::LastStatus();
+        if (status != 0) fprintf(stderr, "local_map failed: %s\n", slamit_last_error());
+        bool marks = true;
+        for (int i = 0; i < K; ++i) marks = marks && ((kf[i]->mnTrackReferenceForFrame == FB.mnId) == (std::find(kfsB.begin(), kfsB.end(), kf[i]) != kfsB.end() && (scenario != 1)));
+        for (int p = 0; p < NP + 8; ++p)
+            marks = marks && ((mpPool[p].mnTrackReferenceForFrame == FB.mnId) == (std::find(mpsB.begin(), mpsB.end(), &mpPool[p]) != mpsB.end()));
+        const bool same = status == 0 && kfsA == kfsB && mpsA == mpsB && refA == refB && FA.mvpMapPoints == FB.mvpMapPoints && FA.mpReferenceKF == FB.mpReferenceKF &&
+                          nB == (int)mpsA.size() && marks;
+        int refSlot = -1;
+        for (int i = 0; i < K; ++i) refSlot = kf[i] == refB ? i : refSlot;
+        printf("local_map scenario %d: status=%d kfs=%zu mps=%zu ref=%d frame_ref_set=%d %s\n", scenario, status, kfsB.size(), mpsB.size(), refSlot,
+               FB.mpReferenceKF ? 1 : 0, same ? "MATCH" : "MISMATCH");
+        failures += same ? 0 : 1;
+        for (int i = 0; i < K; ++i) kf[i]->bad = wasBad[i];
+    }
+    return failures ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     std::string mode = argv[1];
@@ -1572,5 +1761,6 @@ int main(int argc, char** argv) {
     if (mode == "frustum") return run_frustum(argc, argv);
     if (mode == "stereo") return run_stereo(argc, argv);
     if (mode == "unproject") return run_unproject(argc, argv);
+    if (mode == "local_map") return run_local_map(argc, argv);
     return 2;
 }
