@@ -1387,6 +1387,117 @@ typedef struct slamit_local_map_batch_rec slamit_local_map_batch_rec;
 size_t slamit_local_map_workspace(int nframes, int mp_cap, int kf_cap);
 int slamit_local_map_batch_dev(int device, const slamit_local_map_batch_rec* batch, void* stream);
 
+/* ---- Covisibility: KeyFrame::UpdateConnections and LocalMapping::KeyFrameCulling (local mapping) ----
+ * UpdateConnections (src/KeyFrame.cc:296-386, with AddConnection / UpdateBestCovisibles :127-161) and KeyFrameCulling
+ * (src/LocalMapping.cc:686-752) over the tables of slamit_map_index and the columns and graph rows of slamit_covis_index
+ * (csrc/covis.h states both walks).  Integer work and float compares as the reference writes them: the results are
+ * exact.  Every id is a slot (int32), -1 = none.
+ * THE GRAPH: row j of cw_kf / cw_w (cw_n[j] entries, ASCENDING SLOT) is mConnectedKeyFrameWeights of keyframe j; row j of ord_kf /
+ * ord_w (ord_n[j] entries) is mvpOrderedConnectedKeyFrames / mvOrderedWeights: descending weight and, within equal weight,
+ * DESCENDING slot -- the reference's sort of (weight, pointer) pushed to the front, for a caller that numbers keyframes by
+ * std::less<KeyFrame*> (shim/LocalMapping.h).  Rows hold row_cap entries; what lies past a row's count is neither read nor written.
+ * UpdateConnections for keyframe k:
+ *   (a) counts[j] = the non-null, non-bad points of k that keyframe j != k observes (a bad OBSERVER counts: the reference does not test)
+ *   (b) no count at all: the reference returns; every row, kf_best and *parent stay byte for byte, SLAMIT_COVIS_NO_OBSERVER
+ *   (c) k's cw row = the whole counter; k's ord row = the keyframes with count >= 15, or else the single one with the strictly
+ *       largest count, first in ascending slot order
+ *   (d) AddConnection(k, w) on each listed j: nothing of j changes if its cw row holds (k, w); else the entry is inserted or updated
+ *       and j's ord row becomes the sort of j's WHOLE cw row (UpdateBestCovisibles: below-threshold entries are listed too)
+ *   (e) kf_best rows of k and of every changed j = the first ten of the ord row, padded with -1; *parent = the front of k's list when
+ *       first_connection is set and k != origin_kf, else -1.  The parent / children tables stay the caller's.
+ *   (f) a counter above row_cap: only counts and *n_counted are written, SLAMIT_COVIS_ROW_OVERFLOW; a full row of j that lacks k
+ *       leaves j as it was, with the same status.
+ * KeyFrameCulling for current keyframe c: the candidates are c's ord row, in row order.  origin_kf is skipped (verdict 3).  A keypoint
+ * whose point is non-null and not bad counts in n_mps unless (monocular == 0) depth > th_depth || depth < 0; it is redundant when
+ * Observations() > 3 and at least 3 observers other than the candidate have octave <= own octave + 1; the candidate goes when
+ * n_redundant > 0.9 * n_mps (double).  The cascade is kept: against the set S of keyframes culled earlier in the call an observer in S
+ * is not there, Observations() is mp_nobs - the obs_weight of the observers in S, and a point that lost an observer and is left with
+ * <= 2 is bad (mp_turned_bad).  A candidate with kf_not_erase gets verdict 2 and does not enter S.  No table is modified: applying
+ * the verdicts is the caller's work.
+ * COST: as for the local map, building the tables from host objects costs about what the host loops cost; the gain is the resident form.
+ * Status bits, per item / problem: */
+#define SLAMIT_COVIS_NO_OBSERVER 1        /* UpdateConnections: no keyframe shares a point with k; nothing was changed */
+#define SLAMIT_COVIS_ROW_OVERFLOW 2       /* k's counter above row_cap (nothing changed), or a full row of a neighbour (left as it was) */
+#define SLAMIT_COVIS_BAD_SLOT 4           /* device form: a slot outside its table was skipped (never dereferenced) */
+#define SLAMIT_COVIS_MAX_ROW 1024         /* row_cap: a row is sorted in LDS */
+#define SLAMIT_COVIS_TH 15                /* UpdateConnections' threshold */
+#define SLAMIT_COVIS_KEPT 0               /* verdicts */
+#define SLAMIT_COVIS_CULLED 1
+#define SLAMIT_COVIS_TO_BE_ERASED 2
+#define SLAMIT_COVIS_ORIGIN 3
+
+/* The columns and graph rows beside one slamit_map_index.  Host pointers in the host forms, device pointers in the batch records. */
+struct slamit_covis_index {
+    int32_t row_cap;               /* entries per graph row, <= SLAMIT_COVIS_MAX_ROW */
+    int32_t origin_kf;             /* slot of the keyframe with mnId 0, -1 = none */
+    const uint8_t* obs_octave;     /* beside obs_kf: mvKeysUn[idx].octave of that observation in the observing keyframe */
+    const uint8_t* obs_weight;     /* beside obs_kf: 2 if that keyframe's mvuRight[idx] >= 0, else 1 */
+    const int32_t* mp_nobs;        /* [n_mp] MapPoint::Observations() */
+    const uint8_t* kf_octave;      /* beside kf_mp: mvKeysUn[i].octave */
+    const float* kf_depth;         /* beside kf_mp: mvDepth[i]; NULL = monocular */
+    const float* kf_th_depth;      /* [n_kf] mThDepth; NULL together with kf_depth */
+    const uint8_t* kf_not_erase;   /* [n_kf] mbNotErase */
+    int32_t *cw_kf, *cw_w, *cw_n;      /* [n_kf][row_cap], [n_kf]: mConnectedKeyFrameWeights, ascending slot -- in / out */
+    int32_t *ord_kf, *ord_w, *ord_n;   /* mvpOrderedConnectedKeyFrames / mvOrderedWeights -- in / out */
+    int32_t* kf_best;              /* [n_kf][SLAMIT_LOCAL_MAP_BEST], nullable: the memory the map record's kf_best points to */
+};
+typedef struct slamit_covis_index slamit_covis_index;
+
+/* UpdateConnections for keyframe k of one map (host pointers, synchronous).  Reads obs_*, mp_bad, kf_mp* of `map`; counts[n_kf],
+ * *n_counted (the size of the counter), *n_listed (the length of k's new list, 0 when nothing was done) and *status out; *parent in /
+ * out; the seven graph arrays of `covis` in / out.  A null table, k or a table's slot outside its table, or row_cap outside
+ * [1, SLAMIT_COVIS_MAX_ROW] fails with SLAMIT_ERR_ARG and a message before anything is launched. */
+int slamit_update_connections(int device, const slamit_map_index* map, const slamit_covis_index* covis, int32_t k, int32_t first_connection,
+                              int32_t* counts, int32_t* n_counted, int32_t* n_listed, int32_t* parent, int32_t* status);
+
+/* The same for nitems keyframes of nitems DIFFERENT maps, everything resident.  `maps`, `covis` and `item_map` are HOST arrays; the
+ * records hold DEVICE pointers.  The reference is sequential over the keyframes of one map, so a second keyframe of a map is a second
+ * call on the same stream: a map named twice in item_map fails with SLAMIT_ERR_ARG.  count_cap >= every n_kf.  The device cannot be
+ * shown its tables first: a slot outside its table is skipped, never dereferenced, and sets SLAMIT_COVIS_BAD_SLOT (k itself outside
+ * its map: that item does nothing else).  Asynchronous on `stream`, no synchronisation, no state, no workspace. */
+struct slamit_covis_batch_rec {
+    int32_t nitems, n_maps, count_cap, reserved;
+    const slamit_map_index* maps;      /* HOST [n_maps], device pointers inside; n_maps <= SLAMIT_LOCAL_MAP_MAX_MAPS */
+    const slamit_covis_index* covis;   /* HOST [n_maps], device pointers inside */
+    const int32_t* item_map;           /* HOST [nitems], each in [0, n_maps), no repeat */
+    const int32_t* d_kf;               /* [nitems] k */
+    const int32_t* d_first;            /* [nitems] mbFirstConnection, 0 / 1 */
+    int32_t* d_counts;                 /* [nitems][count_cap] out: the first n_kf of an item's row, the rest 0 */
+    int32_t* d_n_counted;              /* [nitems] out */
+    int32_t* d_n_listed;               /* [nitems] out */
+    int32_t* d_parent;                 /* [nitems] in / out */
+    int32_t* d_status;                 /* [nitems] out */
+};
+typedef struct slamit_covis_batch_rec slamit_covis_batch_rec;
+int slamit_update_connections_batch_dev(int device, const slamit_covis_batch_rec* batch, void* stream);
+
+/* KeyFrameCulling for current keyframe c (host pointers, synchronous).  Reads obs_*, mp_bad, kf_mp* of `map` and the columns, ord_kf
+ * and ord_n of `covis`.  verdict / n_mps / n_redundant hold row_cap entries, in / out: the first *n_cand are written.  mp_turned_bad[n_mp]
+ * in / out: bytes set to 1, the others left alone.  kf_depth NULL with monocular == 0, a null table, a slot outside its table or row_cap
+ * outside [1, SLAMIT_COVIS_MAX_ROW] fails with SLAMIT_ERR_ARG before anything is launched. */
+int slamit_keyframe_culling(int device, const slamit_map_index* map, const slamit_covis_index* covis, int32_t c, int32_t monocular,
+                            uint8_t* verdict, int32_t* n_mps, int32_t* n_redundant, int32_t* n_cand, uint8_t* mp_turned_bad, int32_t* status);
+
+/* The same for nprob current keyframes, resident; problems may share a map (nothing is modified).  Problem f uses
+ * maps[d_prob_map[f]] (outside [0, n_maps): n_cand = 0 and SLAMIT_COVIS_BAD_SLOT).  cand_cap >= every row_cap, mp_cap >= every n_mp.
+ * Asynchronous on `stream`, no state, no workspace. */
+struct slamit_culling_batch_rec {
+    int32_t nprob, n_maps, cand_cap, mp_cap;
+    const slamit_map_index* maps;      /* HOST [n_maps] */
+    const slamit_covis_index* covis;   /* HOST [n_maps] */
+    const int32_t* d_prob_map;         /* [nprob] */
+    const int32_t* d_kf;               /* [nprob] c */
+    const int32_t* d_monocular;        /* [nprob] mbMonocular, 0 / 1 */
+    uint8_t* d_verdict;                /* [nprob][cand_cap] in / out */
+    int32_t* d_n_mps;                  /* [nprob][cand_cap] in / out */
+    int32_t* d_n_redundant;            /* [nprob][cand_cap] in / out */
+    int32_t* d_n_cand;                 /* [nprob] out */
+    uint8_t* d_mp_turned_bad;          /* [nprob][mp_cap] in / out */
+    int32_t* d_status;                 /* [nprob] out */
+};
+typedef struct slamit_culling_batch_rec slamit_culling_batch_rec;
+int slamit_keyframe_culling_batch_dev(int device, const slamit_culling_batch_rec* batch, void* stream);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 
 const char* slamit_last_error(void);

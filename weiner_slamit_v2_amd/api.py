@@ -320,6 +320,36 @@ LOCAL_MAP_MAX_KF, LOCAL_MAP_MAX_ROW, LOCAL_MAP_MIN_KF_CAP, LOCAL_MAP_MAX_MAPS, L
 MAP_INDEX_TABLES = (("obs_ptr", np.int32), ("obs_kf", np.int32), ("mp_bad", np.uint8), ("kf_bad", np.uint8), ("kf_mp_ptr", np.int32),
                     ("kf_mp", np.int32), ("kf_best", np.int32), ("kf_child_ptr", np.int32), ("kf_child", np.int32), ("kf_parent", np.int32),
                     ("mp_pos", np.float32), ("mp_normal", np.float32), ("mp_max_dist", np.float32), ("mp_min_dist", np.float32))
+
+
+class CovisIndexRec(C.Structure):   # struct slamit_covis_index
+    _fields_ = [("row_cap", C.c_int32), ("origin_kf", C.c_int32), ("obs_octave", C.c_void_p), ("obs_weight", C.c_void_p), ("mp_nobs", C.c_void_p),
+                ("kf_octave", C.c_void_p), ("kf_depth", C.c_void_p), ("kf_th_depth", C.c_void_p), ("kf_not_erase", C.c_void_p), ("cw_kf", C.c_void_p),
+                ("cw_w", C.c_void_p), ("cw_n", C.c_void_p), ("ord_kf", C.c_void_p), ("ord_w", C.c_void_p), ("ord_n", C.c_void_p), ("kf_best", C.c_void_p)]
+
+
+class CovisBatchRec(C.Structure):   # struct slamit_covis_batch_rec
+    _fields_ = [("nitems", C.c_int32), ("n_maps", C.c_int32), ("count_cap", C.c_int32), ("reserved", C.c_int32), ("maps", C.POINTER(MapIndexRec)),
+                ("covis", C.POINTER(CovisIndexRec)), ("item_map", C.POINTER(C.c_int32)), ("d_kf", C.c_void_p), ("d_first", C.c_void_p),
+                ("d_counts", C.c_void_p), ("d_n_counted", C.c_void_p), ("d_n_listed", C.c_void_p), ("d_parent", C.c_void_p), ("d_status", C.c_void_p)]
+
+
+class CullingBatchRec(C.Structure):   # struct slamit_culling_batch_rec
+    _fields_ = [("nprob", C.c_int32), ("n_maps", C.c_int32), ("cand_cap", C.c_int32), ("mp_cap", C.c_int32), ("maps", C.POINTER(MapIndexRec)),
+                ("covis", C.POINTER(CovisIndexRec)), ("d_prob_map", C.c_void_p), ("d_kf", C.c_void_p), ("d_monocular", C.c_void_p),
+                ("d_verdict", C.c_void_p), ("d_n_mps", C.c_void_p), ("d_n_redundant", C.c_void_p), ("d_n_cand", C.c_void_p),
+                ("d_mp_turned_bad", C.c_void_p), ("d_status", C.c_void_p)]
+
+
+# SLAMIT_COVIS_*: the status bits, MAX_ROW, TH, and the verdicts (the index is the value)
+COVIS_STATUS = {"NO_OBSERVER": 1, "ROW_OVERFLOW": 2, "BAD_SLOT": 4}
+COVIS_MAX_ROW, COVIS_TH = 1024, 15
+COVIS_VERDICTS = ("kept", "culled", "to_be_erased", "origin")
+# slamit_covis_index: the columns and graph rows and their element types, in the record's order
+COVIS_INDEX_TABLES = (("obs_octave", np.uint8), ("obs_weight", np.uint8), ("mp_nobs", np.int32), ("kf_octave", np.uint8), ("kf_depth", np.float32),
+                      ("kf_th_depth", np.float32), ("kf_not_erase", np.uint8), ("cw_kf", np.int32), ("cw_w", np.int32), ("cw_n", np.int32),
+                      ("ord_kf", np.int32), ("ord_w", np.int32), ("ord_n", np.int32), ("kf_best", np.int32))
+COVIS_GRAPH = ("cw_kf", "cw_w", "cw_n", "ord_kf", "ord_w", "ord_n", "kf_best")   # what UpdateConnections rewrites
 DEPTH_TYPES = ("f32", "u16")   # SLAMIT_DEPTH_*: the index is the type
 DEPTH_PLANE_DTYPE = np.dtype([("data", "<u8"), ("pitch", "<u8"), ("width", "<i4"), ("height", "<i4"), ("type", "<i4"), ("factor", "<f4")])   # slamit_depth_plane
 RGBD_STATUS = ("no_depth", "depth", "outside")
@@ -391,7 +421,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -475,6 +505,10 @@ def lib():
         L.slamit_local_map_workspace.argtypes = [i32, i32, i32]
         L.slamit_local_map_workspace.restype = sz
         L.slamit_local_map_batch_dev.argtypes = [i32, C.POINTER(LocalMapBatchRec), vp]
+        L.slamit_update_connections.argtypes = [i32, C.POINTER(MapIndexRec), C.POINTER(CovisIndexRec), i32, i32, vp, vp, vp, vp, vp]
+        L.slamit_update_connections_batch_dev.argtypes = [i32, C.POINTER(CovisBatchRec), vp]
+        L.slamit_keyframe_culling.argtypes = [i32, C.POINTER(MapIndexRec), C.POINTER(CovisIndexRec), i32, i32, vp, vp, vp, vp, vp, vp]
+        L.slamit_keyframe_culling_batch_dev.argtypes = [i32, C.POINTER(CullingBatchRec), vp]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_bow_search_stereo.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), C.POINTER(BowStereo), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
@@ -2388,3 +2422,122 @@ def local_map_batch_dev(maps, t, device=0, stream=None):
                            t["pos"].data_ptr(), t["normal"].data_ptr(), t["max_dist"].data_ptr(), t["min_dist"].data_ptr(), t["skip"].data_ptr(),
                            t["m"].data_ptr(), t["status"].data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
     _check(lib().slamit_local_map_batch_dev(device, C.byref(rec), stream), "slamit_local_map_batch_dev")
+
+
+def _covis_index_host(covis, copy_graph=False):
+    """A map's covisibility columns and graph rows (dict in the layout of slamit_covis_index; a missing table is NULL) as a CovisIndexRec of
+    host pointers and the arrays that keep them alive.  copy_graph: the graph rows are copies, for a call that rewrites them."""
+    keep = {}
+    rec = CovisIndexRec(int(covis["row_cap"]), int(covis["origin_kf"]))
+    for key, dt in COVIS_INDEX_TABLES:
+        if covis.get(key) is not None:
+            keep[key] = (np.array if copy_graph and key in COVIS_GRAPH else np.ascontiguousarray)(covis[key], dt).reshape(-1)
+            setattr(rec, key, keep[key].ctypes.data)
+    return rec, keep
+
+
+def update_connections(tables, covis, k, first_connection=False, parent=-1, device=0):
+    """KeyFrame::UpdateConnections (KeyFrame.cc:296-386) for keyframe k over a map's tables (slamit_map_index: n_kf, n_mp, obs_ptr, obs_kf,
+    mp_bad, kf_mp_ptr, kf_mp) and its graph (dict in the layout of slamit_covis_index: row_cap, origin_kf, cw_kf / cw_w (n_kf, row_cap), cw_n,
+    ord_kf / ord_w, ord_n, optionally kf_best (n_kf, 10)).  The caller's arrays are not modified.  -> dict(counts (n_kf), n_counted,
+    n_listed, parent (as given unless the list was written), status, and the seven graph arrays after the call)."""
+    rec, keep = _map_index_host(tables)
+    xrec, xkeep = _covis_index_host(covis, copy_graph=True)
+    n_kf = max(rec.n_kf, 0)
+    counts = np.zeros(n_kf, np.int32)
+    nc, nl, par, st = np.zeros(1, np.int32), np.zeros(1, np.int32), np.array([parent], np.int32), np.zeros(1, np.int32)
+    _check(lib().slamit_update_connections(device, C.byref(rec), C.byref(xrec), int(k), int(bool(first_connection)), _np_ptr(counts), _np_ptr(nc),
+                                           _np_ptr(nl), _np_ptr(par), _np_ptr(st)), "slamit_update_connections")
+    out = {"counts": counts, "n_counted": int(nc[0]), "n_listed": int(nl[0]), "parent": int(par[0]), "status": int(st[0])}
+    for key in COVIS_GRAPH:
+        if key in xkeep:
+            out[key] = xkeep[key].reshape(np.shape(covis[key]))
+    del keep
+    return out
+
+
+def keyframe_culling(tables, covis, c, monocular, verdict=None, n_mps=None, n_redundant=None, mp_turned_bad=None, device=0):
+    """LocalMapping::KeyFrameCulling (LocalMapping.cc:686-752) for current keyframe c over a map's tables and the columns of
+    slamit_covis_index (obs_octave, obs_weight, mp_nobs, kf_octave, kf_depth / kf_th_depth unless monocular, kf_not_erase, ord_kf, ord_n).
+    verdict / n_mps / n_redundant (row_cap) and mp_turned_bad (n_mp) may be given as the arrays to write into (copies are returned).
+    -> dict(verdict, n_mps, n_redundant: the first n_cand written; n_cand; mp_turned_bad: bytes set to 1; status).  Nothing is applied."""
+    rec, keep = _map_index_host(tables)
+    xrec, xkeep = _covis_index_host(covis)
+    cap, n_mp = max(xrec.row_cap, 0), max(rec.n_mp, 0)
+    arr = lambda a, n, dt: np.zeros(n, dt) if a is None else np.array(a, dt).reshape(-1)
+    v, nm, nr, tb = arr(verdict, cap, np.uint8), arr(n_mps, cap, np.int32), arr(n_redundant, cap, np.int32), arr(mp_turned_bad, n_mp, np.uint8)
+    if len(v) != cap or len(nm) != cap or len(nr) != cap or len(tb) != n_mp:
+        raise SlamitError("keyframe_culling: verdict / n_mps / n_redundant hold row_cap entries, mp_turned_bad n_mp")
+    ncand, st = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    _check(lib().slamit_keyframe_culling(device, C.byref(rec), C.byref(xrec), int(c), int(bool(monocular)), _np_ptr(v), _np_ptr(nm), _np_ptr(nr),
+                                         _np_ptr(ncand), _np_ptr(tb) if n_mp else None, _np_ptr(st)), "slamit_keyframe_culling")
+    del keep, xkeep
+    return {"verdict": v, "n_mps": nm, "n_redundant": nr, "n_cand": int(ncand[0]), "mp_turned_bad": tb, "status": int(st[0])}
+
+
+class CovisIndex:
+    """A map's covisibility columns and graph rows uploaded once, beside a MapIndex (the resident forms' slamit_covis_index):
+    CovisIndex(covis, map_index).rec holds the device pointers, .t the tensors (cw_* / ord_* are rewritten in place by
+    update_connections_batch_dev).  With share_best the record's kf_best IS map_index's kf_best tensor, so local_map_batch_dev reads the
+    refreshed rows with no copy; otherwise covis["kf_best"] is uploaded (None: no kf_best rows are kept)."""
+
+    def __init__(self, covis, map_index, share_best=True):
+        import torch
+
+        self.row_cap, self.device = int(covis["row_cap"]), map_index.device
+        self.t = {}
+        self.rec = CovisIndexRec(self.row_cap, int(covis["origin_kf"]))
+        for key, dt in COVIS_INDEX_TABLES:
+            if key == "kf_best" and share_best:
+                self.t[key] = map_index.t["kf_best"]
+            elif covis.get(key) is None:
+                continue
+            else:
+                a = np.ascontiguousarray(covis[key], dt).reshape(-1)
+                self.t[key] = torch.from_numpy(a if len(a) else np.zeros(1, dt)).to("cuda:%d" % self.device)
+            setattr(self.rec, key, self.t[key].data_ptr())
+
+
+def _covis_records(maps, covis):
+    M, X = (MapIndexRec * max(len(maps), 1))(), (CovisIndexRec * max(len(maps), 1))()
+    if len(maps) != len(covis):
+        raise SlamitError("covis: one CovisIndex per MapIndex")
+    for i, (mi, ci) in enumerate(zip(maps, covis)):
+        M[i], X[i] = mi.rec, ci.rec
+    return M, X
+
+
+def _rows(t, what, specs, b):
+    for key, per in specs:
+        if t[key].numel() != b * per or not t[key].is_contiguous():
+            raise SlamitError("%s: %s is not a contiguous array of %d entries per row" % (what, key, per))
+
+
+def update_connections_batch_dev(maps, covis, item_map, t, device=0, stream=None):
+    """KeyFrame::UpdateConnections for one keyframe of each of len(item_map) DIFFERENT maps, resident.  maps / covis: lists of MapIndex /
+    CovisIndex; item_map: host list, item i works on maps[item_map[i]]; t: dict of torch CUDA tensors kf (B) i32, first (B) i32, counts
+    (B, count_cap) i32, n_counted (B), n_listed (B), parent (B) in / out, status (B).  The graph rows of the CovisIndex tensors (and the
+    kf_best rows they share with the MapIndex) are rewritten in place.  Asynchronous on `stream`."""
+    b = len(item_map)
+    count_cap = t["counts"].shape[1] if t["counts"].dim() == 2 else 0
+    _rows(t, "update_connections_batch_dev", (("counts", count_cap), ("kf", 1), ("first", 1), ("n_counted", 1), ("n_listed", 1), ("parent", 1), ("status", 1)), b)
+    M, X = _covis_records(maps, covis)
+    im = (C.c_int32 * max(b, 1))(*[int(m) for m in item_map])
+    rec = CovisBatchRec(b, len(maps), count_cap, 0, M, X, im, t["kf"].data_ptr(), t["first"].data_ptr(), t["counts"].data_ptr(), t["n_counted"].data_ptr(),
+                        t["n_listed"].data_ptr(), t["parent"].data_ptr(), t["status"].data_ptr())
+    _check(lib().slamit_update_connections_batch_dev(device, C.byref(rec), stream), "slamit_update_connections_batch_dev")
+
+
+def keyframe_culling_batch_dev(maps, covis, t, device=0, stream=None):
+    """LocalMapping::KeyFrameCulling for a batch of current keyframes, resident.  t: dict of torch CUDA tensors prob_map (B) i32, kf (B) i32,
+    monocular (B) i32, verdict (B, cand_cap) u8 / n_mps / n_redundant (B, cand_cap) i32 in / out, n_cand (B) i32, mp_turned_bad (B, mp_cap) u8
+    in / out, status (B) i32; cand_cap >= every row_cap, mp_cap >= every n_mp.  Asynchronous on `stream`."""
+    b, cand_cap = t["verdict"].shape
+    mp_cap = t["mp_turned_bad"].shape[1]
+    _rows(t, "keyframe_culling_batch_dev", (("verdict", cand_cap), ("n_mps", cand_cap), ("n_redundant", cand_cap), ("mp_turned_bad", mp_cap), ("prob_map", 1),
+                                             ("kf", 1), ("monocular", 1), ("n_cand", 1), ("status", 1)), b)
+    M, X = _covis_records(maps, covis)
+    rec = CullingBatchRec(b, len(maps), cand_cap, mp_cap, M, X, t["prob_map"].data_ptr(), t["kf"].data_ptr(), t["monocular"].data_ptr(),
+                          t["verdict"].data_ptr(), t["n_mps"].data_ptr(), t["n_redundant"].data_ptr(), t["n_cand"].data_ptr(),
+                          t["mp_turned_bad"].data_ptr(), t["status"].data_ptr())
+    _check(lib().slamit_keyframe_culling_batch_dev(device, C.byref(rec), stream), "slamit_keyframe_culling_batch_dev")

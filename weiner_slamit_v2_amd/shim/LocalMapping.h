@@ -25,13 +25,20 @@
 // A KeyFrameT without these members keeps the monocular code: monocular == false, or a keyframe with a stereo coordinate
 // (mvuRight >= 0), is refused on stderr with LastStatus() == SLAMIT_ERR_ARG and nothing is created.  Any other non-SLAMIT_OK status
 // of a device call is reported the same way and ends the loop: never a silent return.
+//
+// KeyFrame::UpdateConnections (src/KeyFrame.cc:296-386) and LocalMapping::KeyFrameCulling (:686-752) are documented at the functions:
+// slot tables built from the caller's objects, one call each (slamit_update_connections, slamit_keyframe_culling), the results
+// written into the objects; for parity rather than speed.
 #ifndef SLAMIT_SHIM_LOCALMAPPING_H
 #define SLAMIT_SHIM_LOCALMAPPING_H
 
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
+#include <map>
+#include <set>
 #include <utility>
 #include <vector>
 
@@ -142,9 +149,238 @@ public:
         return CreateNewMapPoints(cur, neigh, monocular, make, never);
     }
 
+    // KeyFrame::UpdateConnections (KeyFrame.cc:296-386) for pKF.  Writes mConnectedKeyFrameWeights, mvpOrderedConnectedKeyFrames and
+    // mvOrderedWeights of pKF, calls AddConnection(pKF, weight) on the listed neighbours in the reference's order (ascending address,
+    // so their own UpdateBestCovisibles runs as host code on the caller's type), and on a first connection of a keyframe other than
+    // the origin sets mpParent, calls AddChild and clears mbFirstConnection.  Returns the number of listed keyframes; 0 with
+    // LastStatus() == SLAMIT_OK when no other keyframe shares a point (the reference returns there too).
+    //
+    // The keyframes that can matter -- pKF and the observers of its points -- are numbered by std::less<KeyFrameT*>, so
+    // slamit_update_connections' "ascending slot" and "within equal weight the higher slot first" are the reference's address order
+    // and its sort of (weight, pointer) on this run (csrc/covis.h).  The neighbours' rows are passed empty: the call is asked for the
+    // counter and pKF's own list only.
+    // WHAT THIS COSTS: building the tables from host objects walks the same points and observers as the host loop itself, so this
+    // function is for parity and for integrations that want one code path; the gain is slamit_update_connections_batch_dev with the
+    // tables kept in HBM.  Members used: KeyFrame mnId, mbFirstConnection, mpParent, mConnectedKeyFrameWeights,
+    // mvpOrderedConnectedKeyFrames, mvOrderedWeights, GetMapPointMatches(), AddConnection(KeyFrame*, const int&), AddChild(KeyFrame*);
+    // MapPoint isBad(), GetObservations().
+    template <class KeyFrameT>
+    static int UpdateConnections(KeyFrameT* pKF, int device = 0) {
+        status() = SLAMIT_OK;
+        return updateConnections(pKF, pKF->GetMapPointMatches(), device);
+    }
+
+    // LocalMapping::KeyFrameCulling (LocalMapping.cc:686-752) for the current keyframe: the candidates are
+    // cur->GetVectorCovisibleKeyFrames(); SetBadFlag() is called on the culled ones in order (a keyframe with mbNotErase gets the call
+    // too: its own SetBadFlag marks it to be erased, as in the reference).  Returns the number of SetBadFlag() calls.
+    //
+    // The device call evaluates every candidate against the tables as they are at the start and carries the cascade itself (a culled
+    // keyframe's observations are gone for the candidates behind it), so the SetBadFlag() calls are made after it, in order: the
+    // caller's objects see the same sequence of calls as in the reference.  monocular == false needs mvDepth and mThDepth on the
+    // keyframe type; a type without mvDepth is refused.
+    // WHAT THIS COSTS: as above, the tables cost what the host loop costs; the gain is slamit_keyframe_culling_batch_dev.
+    // Members used: KeyFrame mnId, mbNotErase, mvKeysUn, mvuRight, (mvDepth, mThDepth), GetVectorCovisibleKeyFrames(),
+    // GetMapPointMatches(), SetBadFlag(); MapPoint isBad(), Observations(), GetObservations().
+    template <class KeyFrameT>
+    static int KeyFrameCulling(KeyFrameT* cur, bool monocular, int device = 0) {
+        status() = SLAMIT_OK;
+        if (!monocular && !shim::has_member_mvDepth<KeyFrameT>::value) return shim::refuse<LocalMapping>("KeyFrameCulling: monocular == false needs mvDepth and mThDepth on the keyframe type");
+        const std::vector<KeyFrameT*> cands = cur->GetVectorCovisibleKeyFrames();
+        if (cands.empty()) return 0;
+        return keyFrameCulling(cur, cands, cands[0]->GetMapPointMatches(), monocular, device);
+    }
+
     static int LastStatus() { return status(); }
 
 private:
+    // a new slot for a pointer on first sight
+    template <class T>
+    static int32_t slotOf(std::map<T*, int32_t>& slots, std::vector<T*>& all, T* p) {
+        typename std::map<T*, int32_t>::const_iterator it = slots.find(p);
+        if (it != slots.end()) return it->second;
+        const int32_t s = (int32_t)all.size();
+        slots[p] = s;
+        all.push_back(p);
+        return s;
+    }
+
+    template <class KeyFrameT, class MapPointT>
+    static int updateConnections(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMP, int device) {
+        std::set<KeyFrameT*> all;
+        all.insert(pKF);
+        for (size_t i = 0; i < vpMP.size(); ++i) {
+            if (!vpMP[i] || vpMP[i]->isBad()) continue;
+            const std::map<KeyFrameT*, size_t> obs = vpMP[i]->GetObservations();
+            for (typename std::map<KeyFrameT*, size_t>::const_iterator it = obs.begin(); it != obs.end(); ++it) all.insert(it->first);
+        }
+        const std::vector<KeyFrameT*> kfs(all.begin(), all.end());   // a std::set orders by std::less
+        std::map<KeyFrameT*, int32_t> kfSlot;
+        for (size_t k = 0; k < kfs.size(); ++k) kfSlot[kfs[k]] = (int32_t)k;
+        const int n_kf = (int)kfs.size(), k = kfSlot[pKF];
+        if (n_kf - 1 > SLAMIT_COVIS_MAX_ROW) return shim::refuse<LocalMapping>("UpdateConnections: more than SLAMIT_COVIS_MAX_ROW keyframes share a point with this one", SLAMIT_ERR_CAPACITY);
+        const int row_cap = n_kf > 1 ? n_kf - 1 : 1, n_mp = (int)vpMP.size();
+        // one row of points (pKF's), one point per keypoint; only pKF's own points vote
+        std::vector<int32_t> kf_mp_ptr(n_kf + 1, 0), kf_mp(vpMP.size(), -1), obs_ptr(n_mp + 1, 0), obs_kf;
+        std::vector<uint8_t> mp_bad(n_mp + 1, 0);
+        for (int i = 0; i < n_mp; ++i) {
+            if (vpMP[i]) {
+                kf_mp[i] = i;
+                mp_bad[i] = vpMP[i]->isBad() ? 1 : 0;
+                if (!mp_bad[i]) {
+                    const std::map<KeyFrameT*, size_t> obs = vpMP[i]->GetObservations();
+                    for (typename std::map<KeyFrameT*, size_t>::const_iterator it = obs.begin(); it != obs.end(); ++it) obs_kf.push_back(kfSlot[it->first]);
+                }
+            }
+            obs_ptr[i + 1] = (int32_t)obs_kf.size();
+        }
+        for (int j = k + 1; j <= n_kf; ++j) kf_mp_ptr[j] = n_mp;
+        int32_t none32 = -1;
+        slamit_map_index M;
+        memset(&M, 0, sizeof(M));
+        M.n_kf = n_kf; M.n_mp = n_mp;
+        M.obs_ptr = obs_ptr.data(); M.obs_kf = obs_kf.empty() ? &none32 : obs_kf.data(); M.mp_bad = mp_bad.data();
+        M.kf_mp_ptr = kf_mp_ptr.data(); M.kf_mp = kf_mp.empty() ? &none32 : kf_mp.data();
+        const size_t rows = (size_t)n_kf * row_cap;
+        std::vector<int32_t> cw_kf(rows, -1), cw_w(rows, 0), cw_n(n_kf, 0), ord_kf(rows, -1), ord_w(rows, 0), ord_n(n_kf, 0), counts(n_kf, 0);
+        slamit_covis_index X;
+        memset(&X, 0, sizeof(X));
+        X.row_cap = row_cap; X.origin_kf = pKF->mnId == 0 ? k : -1;
+        X.cw_kf = cw_kf.data(); X.cw_w = cw_w.data(); X.cw_n = cw_n.data(); X.ord_kf = ord_kf.data(); X.ord_w = ord_w.data(); X.ord_n = ord_n.data();
+        int32_t n_counted = 0, n_listed = 0, parent = -1, st = 0;
+        const int rc = slamit_update_connections(device, &M, &X, k, pKF->mbFirstConnection ? 1 : 0, counts.data(), &n_counted, &n_listed, &parent, &st);
+        if (rc != SLAMIT_OK) return shim::report<LocalMapping>("UpdateConnections: slamit_update_connections", rc);
+        if (st == SLAMIT_COVIS_NO_OBSERVER) return 0;   // :331
+        if (st != 0) return shim::refuse<LocalMapping>("UpdateConnections: slamit_update_connections reported a status on tables built here", SLAMIT_ERR_STATE);
+        // :347-358: AddConnection on the listed neighbours, in map (address) order
+        std::map<KeyFrameT*, int> KFcounter;
+        bool any = false;
+        for (int j = 0; j < n_kf; ++j) {
+            if (counts[j] <= 0) continue;
+            KFcounter[kfs[j]] = counts[j];
+            if (counts[j] >= SLAMIT_COVIS_TH) { kfs[j]->AddConnection(pKF, counts[j]); any = true; }
+        }
+        if (!any) kfs[ord_kf[(size_t)k * row_cap]]->AddConnection(pKF, ord_w[(size_t)k * row_cap]);
+        pKF->mConnectedKeyFrameWeights = KFcounter;
+        pKF->mvpOrderedConnectedKeyFrames.clear();
+        pKF->mvOrderedWeights.clear();
+        for (int e = 0; e < n_listed; ++e) {
+            pKF->mvpOrderedConnectedKeyFrames.push_back(kfs[ord_kf[(size_t)k * row_cap + e]]);
+            pKF->mvOrderedWeights.push_back(ord_w[(size_t)k * row_cap + e]);
+        }
+        if (parent >= 0) {   // :374-379: mbFirstConnection && mnId != 0
+            pKF->mpParent = kfs[parent];
+            pKF->mpParent->AddChild(pKF);
+            pKF->mbFirstConnection = false;
+        }
+        return n_listed;
+    }
+
+    // mvDepth / mThDepth of a keyframe type that has them
+    template <class KeyFrameT>
+    static float depthOf(KeyFrameT* kf, size_t i, shim::bool_tag<true>) { return kf->mvDepth[i]; }
+    template <class KeyFrameT>
+    static float depthOf(KeyFrameT*, size_t, shim::bool_tag<false>) { return 0.f; }
+    template <class KeyFrameT>
+    static float thDepthOf(KeyFrameT* kf, shim::bool_tag<true>) { return kf->mThDepth; }
+    template <class KeyFrameT>
+    static float thDepthOf(KeyFrameT*, shim::bool_tag<false>) { return 0.f; }
+
+    template <class KeyFrameT, class MapPointT>
+    static int keyFrameCulling(KeyFrameT* cur, const std::vector<KeyFrameT*>& cands, const std::vector<MapPointT*>&, bool monocular, int device) {
+        const shim::bool_tag<shim::has_member_mvDepth<KeyFrameT>::value> depthTag = shim::bool_tag<shim::has_member_mvDepth<KeyFrameT>::value>();
+        if (cands.size() > SLAMIT_COVIS_MAX_ROW) return shim::refuse<LocalMapping>("KeyFrameCulling: more than SLAMIT_COVIS_MAX_ROW covisible keyframes", SLAMIT_ERR_CAPACITY);
+        // the keyframes that can matter: the current one, the candidates and the observers of the candidates' points
+        std::set<KeyFrameT*> all(cands.begin(), cands.end());
+        all.insert(cur);
+        std::map<MapPointT*, int32_t> mpSlot;
+        std::vector<MapPointT*> mps;
+        std::vector<std::vector<MapPointT*> > rowsOf(cands.size());
+        for (size_t c = 0; c < cands.size(); ++c) {
+            rowsOf[c] = cands[c]->GetMapPointMatches();
+            for (size_t i = 0; i < rowsOf[c].size(); ++i) {
+                MapPointT* pMP = rowsOf[c][i];
+                if (!pMP) continue;
+                const size_t before = mps.size();
+                slotOf(mpSlot, mps, pMP);
+                if (mps.size() == before || pMP->isBad()) continue;
+                const std::map<KeyFrameT*, size_t> obs = pMP->GetObservations();
+                for (typename std::map<KeyFrameT*, size_t>::const_iterator it = obs.begin(); it != obs.end(); ++it) all.insert(it->first);
+            }
+        }
+        const std::vector<KeyFrameT*> kfs(all.begin(), all.end());
+        std::map<KeyFrameT*, int32_t> kfSlot;
+        for (size_t k = 0; k < kfs.size(); ++k) kfSlot[kfs[k]] = (int32_t)k;
+        const int n_kf = (int)kfs.size(), n_mp = (int)mps.size(), row_cap = (int)cands.size();
+        if (n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return shim::refuse<LocalMapping>("KeyFrameCulling: more than SLAMIT_LOCAL_MAP_MAX_KF keyframes around the candidates", SLAMIT_ERR_CAPACITY);
+        std::vector<int32_t> kf_mp_ptr(n_kf + 1, 0), kf_mp, obs_ptr(n_mp + 1, 0), obs_kf, mp_nobs(n_mp + 1, 0);
+        std::vector<uint8_t> kf_octave, mp_bad(n_mp + 1, 0), obs_octave, obs_weight, kf_not_erase(n_kf, 0);
+        std::vector<float> kf_depth, kf_th_depth(n_kf, 0.f);
+        std::map<KeyFrameT*, size_t> candOf;
+        for (size_t c = 0; c < cands.size(); ++c) candOf[cands[c]] = c;
+        int origin = -1;
+        for (int k = 0; k < n_kf; ++k) {
+            KeyFrameT* pKF = kfs[k];
+            if (pKF->mnId == 0) origin = k;
+            kf_not_erase[k] = pKF->mbNotErase ? 1 : 0;
+            kf_th_depth[k] = thDepthOf(pKF, depthTag);
+            typename std::map<KeyFrameT*, size_t>::const_iterator c = candOf.find(pKF);
+            if (c != candOf.end()) {   // only the candidates' rows are read
+                const std::vector<MapPointT*>& row = rowsOf[c->second];
+                for (size_t i = 0; i < row.size(); ++i) {
+                    kf_mp.push_back(row[i] ? mpSlot[row[i]] : -1);
+                    kf_octave.push_back((uint8_t)pKF->mvKeysUn[i].octave);
+                    kf_depth.push_back(depthOf(pKF, i, depthTag));
+                }
+            }
+            kf_mp_ptr[k + 1] = (int32_t)kf_mp.size();
+        }
+        for (int p = 0; p < n_mp; ++p) {
+            mp_bad[p] = mps[p]->isBad() ? 1 : 0;
+            mp_nobs[p] = mps[p]->Observations();
+            if (!mp_bad[p]) {
+                const std::map<KeyFrameT*, size_t> obs = mps[p]->GetObservations();
+                for (typename std::map<KeyFrameT*, size_t>::const_iterator it = obs.begin(); it != obs.end(); ++it) {
+                    obs_kf.push_back(kfSlot[it->first]);
+                    obs_octave.push_back((uint8_t)it->first->mvKeysUn[it->second].octave);
+                    obs_weight.push_back(it->first->mvuRight[it->second] >= 0 ? 2 : 1);
+                }
+            }
+            obs_ptr[p + 1] = (int32_t)obs_kf.size();
+        }
+        int32_t none32 = -1;
+        uint8_t none8 = 0;
+        float nonef = 0.f;
+        slamit_map_index M;
+        memset(&M, 0, sizeof(M));
+        M.n_kf = n_kf; M.n_mp = n_mp;
+        M.obs_ptr = obs_ptr.data(); M.obs_kf = obs_kf.empty() ? &none32 : obs_kf.data(); M.mp_bad = mp_bad.data();
+        M.kf_mp_ptr = kf_mp_ptr.data(); M.kf_mp = kf_mp.empty() ? &none32 : kf_mp.data();
+        const int c = kfSlot[cur];
+        std::vector<int32_t> ord_kf((size_t)n_kf * row_cap, -1), ord_n(n_kf, 0);
+        for (size_t e = 0; e < cands.size(); ++e) ord_kf[(size_t)c * row_cap + e] = kfSlot[cands[e]];
+        ord_n[c] = row_cap;
+        slamit_covis_index X;
+        memset(&X, 0, sizeof(X));
+        X.row_cap = row_cap; X.origin_kf = origin;
+        X.obs_octave = obs_octave.empty() ? &none8 : obs_octave.data(); X.obs_weight = obs_weight.empty() ? &none8 : obs_weight.data();
+        X.mp_nobs = mp_nobs.data(); X.kf_octave = kf_octave.empty() ? &none8 : kf_octave.data();
+        X.kf_depth = kf_depth.empty() ? &nonef : kf_depth.data(); X.kf_th_depth = kf_th_depth.data(); X.kf_not_erase = kf_not_erase.data();
+        X.ord_kf = ord_kf.data(); X.ord_n = ord_n.data();
+        std::vector<uint8_t> verdict(row_cap, 0), turned(n_mp + 1, 0);
+        std::vector<int32_t> n_mps(row_cap, 0), n_red(row_cap, 0);
+        int32_t n_cand = 0, st = 0;
+        const int rc = slamit_keyframe_culling(device, &M, &X, c, monocular ? 1 : 0, verdict.data(), n_mps.data(), n_red.data(), &n_cand, turned.data(), &st);
+        if (rc != SLAMIT_OK) return shim::report<LocalMapping>("KeyFrameCulling: slamit_keyframe_culling", rc);
+        if (st != 0 || n_cand != row_cap) return shim::refuse<LocalMapping>("KeyFrameCulling: slamit_keyframe_culling reported a status on tables built here", SLAMIT_ERR_STATE);
+        int calls = 0;
+        for (int e = 0; e < n_cand; ++e)
+            if (verdict[e] == SLAMIT_COVIS_CULLED || verdict[e] == SLAMIT_COVIS_TO_BE_ERASED) {   // :749-750
+                cands[e]->SetBadFlag();
+                ++calls;
+            }
+        return calls;
+    }
+
     static bool never() { return false; }
     static int& status() { return shim::status<LocalMapping>(); }
     template <class KeyFrameT>
