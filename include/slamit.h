@@ -1498,6 +1498,125 @@ struct slamit_culling_batch_rec {
 typedef struct slamit_culling_batch_rec slamit_culling_batch_rec;
 int slamit_keyframe_culling_batch_dev(int device, const slamit_culling_batch_rec* batch, void* stream);
 
+/* ---- Map-point upkeep: UpdateNormalAndDepth, ComputeDistinctiveDescriptors, MapPointCulling (local mapping) ----
+ * MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:336-377), MapPoint::ComputeDistinctiveDescriptors (:248-313) and
+ * LocalMapping::MapPointCulling (src/LocalMapping.cc:184-219) over the tables of slamit_map_index and the columns of
+ * slamit_point_index (csrc/upkeep.h states the walks).  Every id is a slot (int32), -1 = none.
+ * NORMAL AND DEPTH of point p (what & 1): a bad point or one without observations changes nothing.  Otherwise
+ * normal = sum over EVERY observer i (bad keyframes too: the reference does not test) of (Pos - Ow_i) / |Pos - Ow_i|, taken in float
+ * one observer after the other in ASCENDING SLOT (std::map<KeyFrame*, size_t> order for a caller that numbers keyframes by
+ * address; the rows of obs_kf may come in any order), divided by their number; dist = |Pos - Ow_ref|; max_dist =
+ * dist * scale_factors[level], min_dist = max_dist / scale_factors[n_levels - 1], level = obs_octave of the reference keyframe's
+ * observation.  A reference keyframe that is not among the observers takes the octave of its keypoint 0, as observations[pRefKF]
+ * default-inserts index 0 (SLAMIT_UPKEEP_REF_NOT_OBSERVER).  Where the reference reads out of bounds -- mp_ref_kf == -1, that
+ * keyframe without keypoints, a level outside [0, n_levels) -- the normal and both distances stay as they were and the status says why.
+ * The float / double evaluation is the one csrc/unproject.h states for these lines; PARITY UNPINNED as there.
+ * DESCRIPTOR of point p (what & 2): the rows are kf_desc[kf_mp_ptr[k] + obs_idx] of the observers k that are NOT bad, in ascending
+ * slot; the row with the least median distance to the others (vDists[(int)(0.5 * (N - 1))], the first on ties) is copied into
+ * mp_desc[p].  A bad point, no observation or no good observer changes nothing; more than SLAMIT_DISTINCTIVE_MAX good observers
+ * sets SLAMIT_UPKEEP_DESC_OVERFLOW and leaves the descriptor (the normal is still updated).  Exact.
+ * MAPPOINTCULLING of a recent list with the current keyframe's mnId: per entry the first matching verdict of
+ *   1 already bad | 2 (float)found / visible < 0.25f as written (visible == 0: inf or NaN, not below) | 3 (int)cur - (int)first_kf >= 2
+ *   && nobs <= th (2 monocular, 3 otherwise) | 4 (int)cur - (int)first_kf >= 3 | 0 kept,
+ * and the kept entries compacted in list order.  Nothing is applied: SetBadFlag on verdicts 2 and 3 is the caller's work.
+ * COST: as for the local map, building the tables from host objects costs about what the host loops cost; the gain is the resident form.
+ * Status bits, per listed point (the last also per recent list): */
+#define SLAMIT_UPKEEP_REF_NOT_OBSERVER 1  /* the reference keyframe does not observe the point: the octave of its keypoint 0 was used */
+#define SLAMIT_UPKEEP_NO_REF 2            /* mp_ref_kf == -1: normal and distances left as they were */
+#define SLAMIT_UPKEEP_REF_NO_KP 4         /* that odd place with a reference keyframe without keypoints: left as they were */
+#define SLAMIT_UPKEEP_OCTAVE 8            /* the level lies outside [0, n_levels): left as they were */
+#define SLAMIT_UPKEEP_DESC_OVERFLOW 16    /* more than SLAMIT_DISTINCTIVE_MAX good observers: the descriptor was left as it was */
+#define SLAMIT_UPKEEP_OBS_OVERFLOW 32     /* more than SLAMIT_UPKEEP_MAX_OBS observers: the point was left as it was */
+#define SLAMIT_UPKEEP_BAD_SLOT 64         /* device form: a slot outside its table was skipped (never dereferenced) */
+#define SLAMIT_UPKEEP_MAX_OBS 512         /* observers per point: a row is ordered in LDS */
+#define SLAMIT_UPKEEP_MAX_POINTS 65536    /* listed points per call / per item of a batch */
+#define SLAMIT_UPKEEP_MAX_RECENT 65536    /* entries of a recent list */
+#define SLAMIT_UPKEEP_NORMAL 1            /* `what` */
+#define SLAMIT_UPKEEP_DESC 2
+#define SLAMIT_UPKEEP_KEPT 0              /* verdicts */
+#define SLAMIT_UPKEEP_WAS_BAD 1
+#define SLAMIT_UPKEEP_LOW_RATIO 2
+#define SLAMIT_UPKEEP_FEW_OBS 3
+#define SLAMIT_UPKEEP_AGED 4
+
+/* The columns beside one slamit_map_index that map-point upkeep reads and writes.  Host pointers in the host forms, device pointers
+ * in the batch records.  Of the map record these calls read obs_ptr, obs_kf, mp_bad, kf_bad, kf_mp_ptr and mp_pos. */
+struct slamit_point_index {
+    int32_t n_levels;              /* mnScaleLevels, in [1, SLAMIT_MAX_LEVELS] */
+    int32_t reserved;
+    float scale_factors[SLAMIT_MAX_LEVELS]; /* mvScaleFactors */
+    const int32_t* obs_idx;        /* beside obs_kf: mObservations[pKF], the keypoint index in the observing keyframe */
+    const uint8_t* obs_octave;     /* beside obs_kf: as slamit_covis_index.obs_octave (may be the same memory) */
+    const uint8_t* kf_octave;      /* beside kf_mp: mvKeysUn[i].octave */
+    const float* kf_center;        /* [n_kf][3] GetCameraCenter() */
+    const uint8_t* kf_desc;        /* beside kf_mp: 32 bytes per keypoint, mDescriptors.row(i); 16-byte aligned in the device form */
+    const int32_t* mp_ref_kf;      /* [n_mp] mpRefKF */
+    const int32_t* mp_nobs;        /* [n_mp] Observations() */
+    const int32_t* mp_found;       /* [n_mp] mnFound */
+    const int32_t* mp_visible;     /* [n_mp] mnVisible */
+    const int32_t* mp_first_kf;    /* [n_mp] mnFirstKFid */
+    float* mp_normal;              /* [n_mp][3] in / out: the memory the map record's mp_normal points to */
+    float* mp_max_dist;            /* [n_mp] in / out: likewise */
+    float* mp_min_dist;            /* [n_mp] in / out: likewise */
+    uint8_t* mp_desc;              /* [n_mp][32] in / out: mDescriptor; 16-byte aligned in the device form */
+};
+typedef struct slamit_point_index slamit_point_index;
+
+/* The n listed points of one map (host pointers, synchronous).  `what` is SLAMIT_UPKEEP_NORMAL | SLAMIT_UPKEEP_DESC; status[n] out.
+ * With what & 1 the call reads obs_octave, kf_octave, kf_center, mp_ref_kf and mp_pos and rewrites mp_normal, mp_max_dist, mp_min_dist;
+ * with what & 2 it reads kf_bad, obs_idx, kf_desc and rewrites mp_desc; tables of the other part may be NULL.  A point listed twice is
+ * written twice with the same bytes.  A null table, a slot outside its table (points, obs_kf, mp_ref_kf, obs_idx), `what` outside
+ * 1..3 or n_levels outside [1, SLAMIT_MAX_LEVELS] fails with SLAMIT_ERR_ARG, n above SLAMIT_UPKEEP_MAX_POINTS with
+ * SLAMIT_ERR_CAPACITY, each with a message and before anything is launched. */
+int slamit_update_points(int device, const slamit_map_index* map, const slamit_point_index* pts, int32_t n, const int32_t* points,
+                         int32_t what, int32_t* status);
+
+/* The same for nitems lists over up to SLAMIT_LOCAL_MAP_MAX_MAPS maps, everything resident.  `maps` and `pts` are HOST arrays of
+ * records holding DEVICE pointers; item i lists d_n[i] points (clamped to cap) of maps[d_item_map[i]] with d_what[i].  The device
+ * cannot be shown its tables first: a slot outside its table is skipped, never dereferenced, and sets SLAMIT_UPKEEP_BAD_SLOT (a
+ * map index or a listed point outside its table: that entry does nothing else).  Items may share a map; a point listed by two items
+ * with the same `what` is written twice with the same bytes.  d_status entries past an item's count are not written.  Asynchronous
+ * on `stream`, no synchronisation, no state, no workspace. */
+struct slamit_points_batch_rec {
+    int32_t nitems, n_maps, cap, reserved;
+    const slamit_map_index* maps;      /* HOST [n_maps], device pointers inside; n_maps <= SLAMIT_LOCAL_MAP_MAX_MAPS */
+    const slamit_point_index* pts;     /* HOST [n_maps], device pointers inside */
+    const int32_t* d_item_map;         /* [nitems] */
+    const int32_t* d_n;                /* [nitems] */
+    const int32_t* d_what;             /* [nitems] */
+    const int32_t* d_points;           /* [nitems][cap], cap <= SLAMIT_UPKEEP_MAX_POINTS */
+    int32_t* d_status;                 /* [nitems][cap] out */
+};
+typedef struct slamit_points_batch_rec slamit_points_batch_rec;
+int slamit_update_points_batch_dev(int device, const slamit_points_batch_rec* batch, void* stream);
+
+/* MapPointCulling for one recent list (host pointers, synchronous).  Reads mp_bad of `map` and mp_found, mp_visible, mp_first_kf,
+ * mp_nobs of `pts`.  verdict[n] and kept[n] in / out: verdict[j] for every j < n, kept[0 .. *n_kept) the kept slots in list order,
+ * entries past the counts as the caller left them; *status out.  A null table or array, an entry outside [0, n_mp) fails with
+ * SLAMIT_ERR_ARG, n above SLAMIT_UPKEEP_MAX_RECENT with SLAMIT_ERR_CAPACITY, before anything is launched. */
+int slamit_map_point_culling(int device, const slamit_map_index* map, const slamit_point_index* pts, int32_t cur_id, int32_t monocular,
+                             int32_t n, const int32_t* recent, uint8_t* verdict, int32_t* kept, int32_t* n_kept, int32_t* status);
+
+/* The same for nlists recent lists, resident; lists may share a map (nothing is modified).  List f uses maps[d_list_map[f]] (outside
+ * [0, n_maps): n_kept = 0 and SLAMIT_UPKEEP_BAD_SLOT).  An entry outside its table keeps its verdict byte, is not kept and sets
+ * SLAMIT_UPKEEP_BAD_SLOT.  Asynchronous on `stream`, no state, no workspace. */
+struct slamit_point_culling_batch_rec {
+    int32_t nlists, n_maps, cap, reserved;
+    const slamit_map_index* maps;      /* HOST [n_maps] */
+    const slamit_point_index* pts;     /* HOST [n_maps] */
+    const int32_t* d_list_map;         /* [nlists] */
+    const int32_t* d_cur_id;           /* [nlists] mpCurrentKeyFrame->mnId */
+    const int32_t* d_monocular;        /* [nlists] mbMonocular, 0 / 1 */
+    const int32_t* d_n;                /* [nlists] entries, clamped to cap */
+    const int32_t* d_recent;           /* [nlists][cap], cap <= SLAMIT_UPKEEP_MAX_RECENT */
+    uint8_t* d_verdict;                /* [nlists][cap] in / out */
+    int32_t* d_kept;                   /* [nlists][cap] in / out */
+    int32_t* d_n_kept;                 /* [nlists] out */
+    int32_t* d_status;                 /* [nlists] out */
+};
+typedef struct slamit_point_culling_batch_rec slamit_point_culling_batch_rec;
+int slamit_map_point_culling_batch_dev(int device, const slamit_point_culling_batch_rec* batch, void* stream);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 
 const char* slamit_last_error(void);

@@ -350,6 +350,37 @@ COVIS_INDEX_TABLES = (("obs_octave", np.uint8), ("obs_weight", np.uint8), ("mp_n
                       ("kf_th_depth", np.float32), ("kf_not_erase", np.uint8), ("cw_kf", np.int32), ("cw_w", np.int32), ("cw_n", np.int32),
                       ("ord_kf", np.int32), ("ord_w", np.int32), ("ord_n", np.int32), ("kf_best", np.int32))
 COVIS_GRAPH = ("cw_kf", "cw_w", "cw_n", "ord_kf", "ord_w", "ord_n", "kf_best")   # what UpdateConnections rewrites
+
+
+class PointIndexRec(C.Structure):   # struct slamit_point_index
+    _fields_ = [("n_levels", C.c_int32), ("reserved", C.c_int32), ("scale_factors", C.c_float * 16), ("obs_idx", C.c_void_p), ("obs_octave", C.c_void_p),
+                ("kf_octave", C.c_void_p), ("kf_center", C.c_void_p), ("kf_desc", C.c_void_p), ("mp_ref_kf", C.c_void_p), ("mp_nobs", C.c_void_p),
+                ("mp_found", C.c_void_p), ("mp_visible", C.c_void_p), ("mp_first_kf", C.c_void_p), ("mp_normal", C.c_void_p), ("mp_max_dist", C.c_void_p),
+                ("mp_min_dist", C.c_void_p), ("mp_desc", C.c_void_p)]
+
+
+class PointsBatchRec(C.Structure):   # struct slamit_points_batch_rec
+    _fields_ = [("nitems", C.c_int32), ("n_maps", C.c_int32), ("cap", C.c_int32), ("reserved", C.c_int32), ("maps", C.POINTER(MapIndexRec)),
+                ("pts", C.POINTER(PointIndexRec)), ("d_item_map", C.c_void_p), ("d_n", C.c_void_p), ("d_what", C.c_void_p), ("d_points", C.c_void_p),
+                ("d_status", C.c_void_p)]
+
+
+class PointCullingBatchRec(C.Structure):   # struct slamit_point_culling_batch_rec
+    _fields_ = [("nlists", C.c_int32), ("n_maps", C.c_int32), ("cap", C.c_int32), ("reserved", C.c_int32), ("maps", C.POINTER(MapIndexRec)),
+                ("pts", C.POINTER(PointIndexRec)), ("d_list_map", C.c_void_p), ("d_cur_id", C.c_void_p), ("d_monocular", C.c_void_p), ("d_n", C.c_void_p),
+                ("d_recent", C.c_void_p), ("d_verdict", C.c_void_p), ("d_kept", C.c_void_p), ("d_n_kept", C.c_void_p), ("d_status", C.c_void_p)]
+
+
+# SLAMIT_UPKEEP_*: the status bits, the ceilings, `what`, and the verdicts (the index is the value)
+UPKEEP_STATUS = {"REF_NOT_OBSERVER": 1, "NO_REF": 2, "REF_NO_KP": 4, "OCTAVE": 8, "DESC_OVERFLOW": 16, "OBS_OVERFLOW": 32, "BAD_SLOT": 64}
+UPKEEP_MAX_OBS, UPKEEP_MAX_POINTS, UPKEEP_MAX_RECENT, DISTINCTIVE_MAX = 512, 65536, 65536, 128
+UPKEEP_NORMAL, UPKEEP_DESC = 1, 2
+UPKEEP_VERDICTS = ("kept", "was_bad", "low_ratio", "few_obs", "aged")
+# slamit_point_index: the columns and their element types, in the record's order; the last four are rewritten
+POINT_INDEX_TABLES = (("obs_idx", np.int32), ("obs_octave", np.uint8), ("kf_octave", np.uint8), ("kf_center", np.float32), ("kf_desc", np.uint8),
+                      ("mp_ref_kf", np.int32), ("mp_nobs", np.int32), ("mp_found", np.int32), ("mp_visible", np.int32), ("mp_first_kf", np.int32),
+                      ("mp_normal", np.float32), ("mp_max_dist", np.float32), ("mp_min_dist", np.float32), ("mp_desc", np.uint8))
+POINT_PLANES = ("mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc")   # what update_points rewrites
 DEPTH_TYPES = ("f32", "u16")   # SLAMIT_DEPTH_*: the index is the type
 DEPTH_PLANE_DTYPE = np.dtype([("data", "<u8"), ("pitch", "<u8"), ("width", "<i4"), ("height", "<i4"), ("type", "<i4"), ("factor", "<f4")])   # slamit_depth_plane
 RGBD_STATUS = ("no_depth", "depth", "outside")
@@ -421,7 +452,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -509,6 +540,10 @@ def lib():
         L.slamit_update_connections_batch_dev.argtypes = [i32, C.POINTER(CovisBatchRec), vp]
         L.slamit_keyframe_culling.argtypes = [i32, C.POINTER(MapIndexRec), C.POINTER(CovisIndexRec), i32, i32, vp, vp, vp, vp, vp, vp]
         L.slamit_keyframe_culling_batch_dev.argtypes = [i32, C.POINTER(CullingBatchRec), vp]
+        L.slamit_update_points.argtypes = [i32, C.POINTER(MapIndexRec), C.POINTER(PointIndexRec), i32, vp, i32, vp]
+        L.slamit_update_points_batch_dev.argtypes = [i32, C.POINTER(PointsBatchRec), vp]
+        L.slamit_map_point_culling.argtypes = [i32, C.POINTER(MapIndexRec), C.POINTER(PointIndexRec), i32, i32, i32, vp, vp, vp, vp, vp]
+        L.slamit_map_point_culling_batch_dev.argtypes = [i32, C.POINTER(PointCullingBatchRec), vp]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_bow_search_stereo.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), C.POINTER(BowStereo), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
@@ -2541,3 +2576,112 @@ def keyframe_culling_batch_dev(maps, covis, t, device=0, stream=None):
                           t["verdict"].data_ptr(), t["n_mps"].data_ptr(), t["n_redundant"].data_ptr(), t["n_cand"].data_ptr(),
                           t["mp_turned_bad"].data_ptr(), t["status"].data_ptr())
     _check(lib().slamit_keyframe_culling_batch_dev(device, C.byref(rec), stream), "slamit_keyframe_culling_batch_dev")
+
+
+def _point_index_host(pts, copy_planes=False):
+    """A map's point columns (dict in the layout of slamit_point_index: n_levels, scale_factors and the tables; a missing table is NULL) as a
+    PointIndexRec of host pointers and the arrays that keep them alive.  copy_planes: the in / out planes are copies, for a call that rewrites them."""
+    keep = {}
+    rec = PointIndexRec(int(pts["n_levels"]), 0)
+    sf = np.asarray(pts["scale_factors"], np.float32).reshape(-1)[:16]
+    rec.scale_factors[:len(sf)] = sf.tolist()
+    for key, dt in POINT_INDEX_TABLES:
+        if pts.get(key) is not None:
+            keep[key] = (np.array if copy_planes and key in POINT_PLANES else np.ascontiguousarray)(pts[key], dt).reshape(-1)
+            setattr(rec, key, keep[key].ctypes.data)
+    return rec, keep
+
+
+def update_points(tables, pts, points, what=UPKEEP_NORMAL | UPKEEP_DESC, device=0):
+    """MapPoint::UpdateNormalAndDepth (what & 1) and ::ComputeDistinctiveDescriptors (what & 2) (MapPoint.cc:248-377) for the listed points
+    over a map's tables (slamit_map_index: n_kf, n_mp, obs_ptr, obs_kf, mp_bad, kf_bad, kf_mp_ptr, mp_pos) and its point columns (dict in the
+    layout of slamit_point_index).  The caller's arrays are not modified.  -> dict(status (n), mp_normal (n_mp, 3), mp_max_dist, mp_min_dist
+    (n_mp), mp_desc (n_mp, 32) after the call, where given)."""
+    rec, keep = _map_index_host(tables)
+    xrec, xkeep = _point_index_host(pts, copy_planes=True)
+    lst = np.ascontiguousarray(points, np.int32).reshape(-1)
+    st = np.zeros(len(lst), np.int32)
+    _check(lib().slamit_update_points(device, C.byref(rec), C.byref(xrec), len(lst), _np_ptr(lst) if len(lst) else None, int(what),
+                                      _np_ptr(st) if len(lst) else None), "slamit_update_points")
+    out = {"status": st}
+    for key in POINT_PLANES:
+        if key in xkeep:
+            out[key] = xkeep[key].reshape(np.shape(pts[key]))
+    del keep
+    return out
+
+
+def map_point_culling(tables, pts, cur_id, monocular, recent, verdict=None, kept=None, device=0):
+    """LocalMapping::MapPointCulling (LocalMapping.cc:184-219) for a recent list over a map's mp_bad and the columns mp_nobs, mp_found,
+    mp_visible, mp_first_kf.  verdict / kept (n) may be given as the arrays to write into (copies are returned).  -> dict(verdict (n) uint8,
+    kept (n) int32 of which the first n_kept are written, n_kept, status).  Nothing is applied."""
+    rec, keep = _map_index_host(tables)
+    xrec, xkeep = _point_index_host(pts)
+    lst = np.ascontiguousarray(recent, np.int32).reshape(-1)
+    n = len(lst)
+    v = np.zeros(n, np.uint8) if verdict is None else np.array(verdict, np.uint8).reshape(-1)
+    kp = np.full(n, -1, np.int32) if kept is None else np.array(kept, np.int32).reshape(-1)
+    if len(v) != n or len(kp) != n:
+        raise SlamitError("map_point_culling: verdict and kept hold one entry per entry of the list")
+    nk, st = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    ptr = lambda a: _np_ptr(a) if n else None
+    _check(lib().slamit_map_point_culling(device, C.byref(rec), C.byref(xrec), int(cur_id), int(bool(monocular)), n, ptr(lst), ptr(v), ptr(kp),
+                                          _np_ptr(nk), _np_ptr(st)), "slamit_map_point_culling")
+    del keep, xkeep
+    return {"verdict": v, "kept": kp, "n_kept": int(nk[0]), "status": int(st[0])}
+
+
+class PointIndex:
+    """A map's point columns uploaded once, beside a MapIndex (the resident forms' slamit_point_index): PointIndex(pts, map_index).rec holds
+    the device pointers, .t the tensors.  mp_normal, mp_max_dist and mp_min_dist ARE map_index's tensors of the same names, so
+    update_points_batch_dev rewrites the planes local_map_batch_dev gathers, with no copy; mp_desc is uploaded from pts."""
+
+    def __init__(self, pts, map_index):
+        import torch
+
+        self.device = map_index.device
+        self.t = {}
+        self.rec = PointIndexRec(int(pts["n_levels"]), 0)
+        sf = np.asarray(pts["scale_factors"], np.float32).reshape(-1)[:16]
+        self.rec.scale_factors[:len(sf)] = sf.tolist()
+        for key, dt in POINT_INDEX_TABLES:
+            if key in ("mp_normal", "mp_max_dist", "mp_min_dist"):
+                self.t[key] = map_index.t[key]
+            else:
+                a = np.ascontiguousarray(pts[key], dt).reshape(-1)
+                self.t[key] = torch.from_numpy(a if len(a) else np.zeros(32, dt)).to("cuda:%d" % self.device)
+            setattr(self.rec, key, self.t[key].data_ptr())
+
+
+def _point_records(maps, pts):
+    M, X = (MapIndexRec * max(len(maps), 1))(), (PointIndexRec * max(len(maps), 1))()
+    if len(maps) != len(pts):
+        raise SlamitError("upkeep: one PointIndex per MapIndex")
+    for i, (mi, pi) in enumerate(zip(maps, pts)):
+        M[i], X[i] = mi.rec, pi.rec
+    return M, X
+
+
+def update_points_batch_dev(maps, pts, t, device=0, stream=None):
+    """UpdateNormalAndDepth / ComputeDistinctiveDescriptors for a batch of point lists, resident.  maps / pts: lists of MapIndex / PointIndex;
+    t: dict of torch CUDA tensors item_map (B) i32, n (B) i32, what (B) i32, points (B, cap) i32, status (B, cap) i32 out.  The planes of the
+    PointIndex tensors (shared with the MapIndex) are rewritten in place.  Asynchronous on `stream`."""
+    b, cap = t["points"].shape
+    _rows(t, "update_points_batch_dev", (("points", cap), ("status", cap), ("item_map", 1), ("n", 1), ("what", 1)), b)
+    M, X = _point_records(maps, pts)
+    rec = PointsBatchRec(b, len(maps), cap, 0, M, X, t["item_map"].data_ptr(), t["n"].data_ptr(), t["what"].data_ptr(), t["points"].data_ptr(),
+                         t["status"].data_ptr())
+    _check(lib().slamit_update_points_batch_dev(device, C.byref(rec), stream), "slamit_update_points_batch_dev")
+
+
+def map_point_culling_batch_dev(maps, pts, t, device=0, stream=None):
+    """LocalMapping::MapPointCulling for a batch of recent lists, resident.  t: dict of torch CUDA tensors list_map (B) i32, cur_id (B) i32,
+    monocular (B) i32, n (B) i32, recent (B, cap) i32, verdict (B, cap) u8 / kept (B, cap) i32 in / out, n_kept (B) i32, status (B) i32.
+    Asynchronous on `stream`."""
+    b, cap = t["recent"].shape
+    _rows(t, "map_point_culling_batch_dev", (("recent", cap), ("verdict", cap), ("kept", cap), ("list_map", 1), ("cur_id", 1), ("monocular", 1), ("n", 1),
+                                              ("n_kept", 1), ("status", 1)), b)
+    M, X = _point_records(maps, pts)
+    rec = PointCullingBatchRec(b, len(maps), cap, 0, M, X, t["list_map"].data_ptr(), t["cur_id"].data_ptr(), t["monocular"].data_ptr(), t["n"].data_ptr(),
+                               t["recent"].data_ptr(), t["verdict"].data_ptr(), t["kept"].data_ptr(), t["n_kept"].data_ptr(), t["status"].data_ptr())
+    _check(lib().slamit_map_point_culling_batch_dev(device, C.byref(rec), stream), "slamit_map_point_culling_batch_dev")

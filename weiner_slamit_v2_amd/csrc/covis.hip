@@ -397,23 +397,6 @@ static int cv_refuse(const char* where, const char* what) {
     return slamit_fail(SLAMIT_ERR_ARG, msg);
 }
 
-// an in / out array of a host form: staged down as an input, copied on the stream into the output that is staged back
-struct CvInOut { void* dst; const void* src; size_t bytes; };
-template <typename T>
-static T* cv_inout(StageBinder& b, std::vector<CvInOut>& io, T* host, size_t count) {
-    const T* const src = b.in(host, count);
-    T* const dst = b.out(host, count);
-    if (dst && count) io.push_back({dst, src, sizeof(T) * count});
-    return dst;
-}
-static hipError_t cv_copy_inouts(const std::vector<CvInOut>& io, hipStream_t st) {
-    for (const CvInOut& c : io) {
-        const hipError_t e = hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
 extern "C" {
 
 int slamit_update_connections(int device, const slamit_map_index* map, const slamit_covis_index* covis, int32_t k, int32_t first_connection,
@@ -426,7 +409,7 @@ int slamit_update_connections(int device, const slamit_map_index* map, const sla
     const size_t n_obs = (size_t)map->obs_ptr[n_mp], n_kfmp = (size_t)map->kf_mp_ptr[n_kf], rows = (size_t)n_kf * row_cap;
     SLAMIT_USE_DEVICE(device);
     CvConnBatch H;
-    std::vector<CvInOut> io;
+    std::vector<SlamitInOut> io;
     static thread_local SlamitScratch S;
     return slamit_staged_batch<CvConnBatch>(
         where, S, device, 1,
@@ -439,19 +422,19 @@ int slamit_update_connections(int device, const slamit_map_index* map, const sla
             M.kf_mp_ptr = b.in(map->kf_mp_ptr, (size_t)n_kf + 1); M.kf_mp = b.in(map->kf_mp, n_kfmp);
             CvIndex& X = Q.covis[0];
             X.row_cap = row_cap; X.origin_kf = covis->origin_kf;
-            X.cw_kf = cv_inout(b, io, covis->cw_kf, rows); X.cw_w = cv_inout(b, io, covis->cw_w, rows); X.cw_n = cv_inout(b, io, covis->cw_n, (size_t)n_kf);
-            X.ord_kf = cv_inout(b, io, covis->ord_kf, rows); X.ord_w = cv_inout(b, io, covis->ord_w, rows); X.ord_n = cv_inout(b, io, covis->ord_n, (size_t)n_kf);
-            X.kf_best = covis->kf_best ? cv_inout(b, io, covis->kf_best, (size_t)n_kf * LM_BEST) : nullptr;
+            X.cw_kf = slamit_inout(b, io, covis->cw_kf, rows); X.cw_w = slamit_inout(b, io, covis->cw_w, rows); X.cw_n = slamit_inout(b, io, covis->cw_n, (size_t)n_kf);
+            X.ord_kf = slamit_inout(b, io, covis->ord_kf, rows); X.ord_w = slamit_inout(b, io, covis->ord_w, rows); X.ord_n = slamit_inout(b, io, covis->ord_n, (size_t)n_kf);
+            X.kf_best = covis->kf_best ? slamit_inout(b, io, covis->kf_best, (size_t)n_kf * LM_BEST) : nullptr;
             int32_t* h2;
             const int32_t* const d2 = b.in_fill<int32_t>(2, &h2);   // k, first_connection
             if (h2) { h2[0] = k; h2[1] = first_connection != 0; }
             Q.kf = d2; Q.first = d2 ? d2 + 1 : nullptr;
             Q.counts = b.out(counts, (size_t)n_kf); Q.n_counted = b.out(n_counted, 1); Q.n_listed = b.out(n_listed, 1);
-            Q.parent = cv_inout(b, io, parent, 1); Q.status = b.out(status, 1);
+            Q.parent = slamit_inout(b, io, parent, 1); Q.status = b.out(status, 1);
             H = Q;
         },
         [&](const CvConnBatch*) {
-            const hipError_t e = cv_copy_inouts(io, S.st);
+            const hipError_t e = slamit_copy_inouts(io, S.st);
             return e != hipSuccess ? e : cv_launch_connections(H, row_cap, S.st);
         });
 }
@@ -507,7 +490,7 @@ int slamit_keyframe_culling(int device, const slamit_map_index* map, const slami
     if (!cv_slots_ok(covis->ord_kf + (size_t)c * row_cap, (size_t)n_c, 0, n_kf)) return cv_refuse(where, "the candidates hold a keyframe slot outside [0, n_kf)");
     SLAMIT_USE_DEVICE(device);
     CvCullBatch H;
-    std::vector<CvInOut> io;
+    std::vector<SlamitInOut> io;
     static thread_local SlamitScratch S;
     return slamit_staged_batch<CvCullBatch>(
         where, S, device, 1,
@@ -529,13 +512,13 @@ int slamit_keyframe_culling(int device, const slamit_map_index* map, const slami
             const int32_t* const d3 = b.in_fill<int32_t>(3, &h3);   // prob_map, c, monocular
             if (h3) { h3[0] = 0; h3[1] = c; h3[2] = monocular != 0; }
             Q.prob_map = d3; Q.kf = d3 ? d3 + 1 : nullptr; Q.monocular = d3 ? d3 + 2 : nullptr;
-            Q.verdict = cv_inout(b, io, verdict, (size_t)row_cap); Q.n_mps = cv_inout(b, io, n_mps, (size_t)row_cap);
-            Q.n_redundant = cv_inout(b, io, n_redundant, (size_t)row_cap); Q.n_cand = b.out(n_cand, 1);
-            Q.mp_turned_bad = cv_inout(b, io, mp_turned_bad, (size_t)n_mp); Q.status = b.out(status, 1);
+            Q.verdict = slamit_inout(b, io, verdict, (size_t)row_cap); Q.n_mps = slamit_inout(b, io, n_mps, (size_t)row_cap);
+            Q.n_redundant = slamit_inout(b, io, n_redundant, (size_t)row_cap); Q.n_cand = b.out(n_cand, 1);
+            Q.mp_turned_bad = slamit_inout(b, io, mp_turned_bad, (size_t)n_mp); Q.status = b.out(status, 1);
             H = Q;
         },
         [&](const CvCullBatch*) {
-            const hipError_t e = cv_copy_inouts(io, S.st);
+            const hipError_t e = slamit_copy_inouts(io, S.st);
             return e != hipSuccess ? e : cv_launch_culling(H, S.st);
         });
 }

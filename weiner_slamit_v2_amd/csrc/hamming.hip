@@ -19,6 +19,7 @@
 #include "../../include/slamit.h"
 #include "slamit_internal.h"
 #include "wave_ops.h"
+#include "distinctive.h"
 
 #define HM_TILE 256      // train rows per LDS tile: two uint4 per thread
 #ifndef HM_SLICES
@@ -330,28 +331,7 @@ __global__ __launch_bounds__(64) void distinctive_kernel(const uint8_t* __restri
     for (int i = lane; i < 2 * n; i += 64) rowsd[i] = G[i];
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    for (int i = lane; i < n; i += 64) {
-        const uint4 a0 = rowsd[2 * i], a1 = rowsd[2 * i + 1];
-        for (int j = 0; j < n; ++j) {
-            const uint4 t0 = rowsd[2 * j], t1 = rowsd[2 * j + 1];
-            const int d = hamming256(a0, a1, t0, t1);
-            D[i * n + j] = (unsigned short)d;
-        }
-    }
-    const int k = (int)(0.5 * (n - 1));  // index of the median in the sorted row
-    unsigned bestkey = 0xFFFFFFFFu;       // (median << 16) | row
-    for (int i = lane; i < n; i += 64) {
-        int lo = 0, hi = 256;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            int c = 0;
-            for (int j = 0; j < n; ++j) c += D[i * n + j] <= mid;
-            if (c >= k + 1) hi = mid; else lo = mid + 1;
-        }
-        bestkey = min(bestkey, ((unsigned)lo << 16) | (unsigned)i);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) bestkey = min(bestkey, (unsigned)__shfl_xor((int)bestkey, d, 64));
+    DISTINCTIVE_SELECT(rowsd, D, n, lane, bestkey)   // distinctive.h: the distances, each row's median, the first least one
     if (lane == 0) { best_idx[p] = (int)(bestkey & 0xFFFF); best_median[p] = (int)(bestkey >> 16); }
 }
 

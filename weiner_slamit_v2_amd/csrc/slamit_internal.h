@@ -157,4 +157,23 @@ int slamit_staged_batch(const char* where, SlamitScratch& S, int device, int nre
     return SLAMIT_OK;
 }
 
+// An in / out array of a host form (covis.hip, upkeep.hip): staged down as an input, copied on the stream into the output that is
+// staged back, so that what the kernels leave alone returns as the caller gave it.  describe() clears `io` and names the arrays
+// through slamit_inout; launch() calls slamit_copy_inouts first.
+struct SlamitInOut { void* dst; const void* src; size_t bytes; };
+template <typename T>
+static T* slamit_inout(StageBinder& b, std::vector<SlamitInOut>& io, T* host, size_t count) {
+    const T* const src = b.in(host, count);
+    T* const dst = b.out(host, count);
+    if (dst && count) io.push_back({dst, src, sizeof(T) * count});
+    return dst;
+}
+static inline hipError_t slamit_copy_inouts(const std::vector<SlamitInOut>& io, hipStream_t st) {
+    for (const SlamitInOut& c : io) {
+        const hipError_t e = hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 #endif

@@ -120,6 +120,11 @@ UNP_HD int unp_n_visited(int M, int c, int min_points, int mode) {
     return (long long)M < cut ? M : (int)cut;
 }
 
+// cv::norm of a 3 x 1 float Mat: the square root of the double sum of double squares, in order (MapPoint.cc:61, :64, :361, :366)
+UNP_HD double unp_norm3(const float v[3]) { return sqrt(((double)v[0] * (double)v[0] + (double)v[1] * (double)v[1]) + (double)v[2] * (double)v[2]); }
+// Mat / s: a convertTo with scale 1. / s, so every element is multiplied by this float (:61, :361, :375)
+UNP_HD float unp_mat_div(double s) { return (float)(1.0 / s); }
+
 // Frame::UnprojectStereo and what the new point's constructor stores; false = the octave lies outside the table (UNP_OCTAVE)
 UNP_HD bool unp_point(const UnprojectFrame& F, float u, float v, float z, int octave, UnprojectPoint& o) {
     const float x = (u - F.cx) * z * F.invfx;
@@ -130,9 +135,9 @@ UNP_HD bool unp_point(const UnprojectFrame& F, float u, float v, float z, int oc
         o.pos[r] = (float)((double)t0 + (double)F.Ow[r]);
     }
     const float PC[3] = {o.pos[0] - F.Ow[0], o.pos[1] - F.Ow[1], o.pos[2] - F.Ow[2]};
-    const double norm = sqrt(((double)PC[0] * (double)PC[0] + (double)PC[1] * (double)PC[1]) + (double)PC[2] * (double)PC[2]);
+    const double norm = unp_norm3(PC);
     const float dist = (float)norm;
-    const float inv = (float)(1.0 / norm);
+    const float inv = unp_mat_div(norm);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         float nr = PC[r] * inv;

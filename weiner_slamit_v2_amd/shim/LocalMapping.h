@@ -28,7 +28,9 @@
 //
 // KeyFrame::UpdateConnections (src/KeyFrame.cc:296-386) and LocalMapping::KeyFrameCulling (:686-752) are documented at the functions:
 // slot tables built from the caller's objects, one call each (slamit_update_connections, slamit_keyframe_culling), the results
-// written into the objects; for parity rather than speed.
+// written into the objects; for parity rather than speed.  UpdateMapPoints (MapPoint::UpdateNormalAndDepth and
+// ::ComputeDistinctiveDescriptors for a list of points, src/MapPoint.cc:248-377) and MapPointCulling (:184-219) are built the same way
+// over slamit_update_points and slamit_map_point_culling.
 #ifndef SLAMIT_SHIM_LOCALMAPPING_H
 #define SLAMIT_SHIM_LOCALMAPPING_H
 
@@ -188,6 +190,80 @@ public:
         const std::vector<KeyFrameT*> cands = cur->GetVectorCovisibleKeyFrames();
         if (cands.empty()) return 0;
         return keyFrameCulling(cur, cands, cands[0]->GetMapPointMatches(), monocular, device);
+    }
+
+    // MapPoint::UpdateNormalAndDepth (what & 1) and MapPoint::ComputeDistinctiveDescriptors (what & 2) (MapPoint.cc:248-377) for the
+    // listed points (NULL entries are skipped) in ONE slamit_update_points call.  Writes mNormalVector, mfMaxDistance, mfMinDistance
+    // and mDescriptor of the points the reference would have written.  Returns the number of points looked at.
+    //
+    // The keyframes that matter -- the observers and the reference keyframes of the listed points -- are numbered by
+    // std::less<KeyFrameT*>, so slamit_update_points' "ascending slot" is the reference's iteration of mObservations on this run: the
+    // float sum of the normal and the first least median come out in its order (csrc/upkeep.h).  A keyframe's row holds its keypoint 0
+    // (what observations[pRefKF] default-inserts for a reference keyframe that does not observe the point) and then the listed points'
+    // observations, so only the descriptors that can be read travel.  mnScaleLevels / mvScaleFactors are one keyframe's: the
+    // reference's keyframes share them.
+    // Where the reference would read out of bounds (no reference keyframe, a level outside mvScaleFactors) or a ceiling is passed
+    // (SLAMIT_UPKEEP_MAX_OBS observers, SLAMIT_DISTINCTIVE_MAX good ones) the point keeps what the status names, the others are
+    // written, and LastStatus() is SLAMIT_ERR_ARG / SLAMIT_ERR_CAPACITY with a line on stderr.
+    // THROUGH THE SHIM THIS SAVES NOTHING: building the tables walks the same observations as the host loops and copies their
+    // descriptors; it is for parity and for integrations that want one code path.  The gain is slamit_update_points_batch_dev with
+    // the tables kept in HBM.  Members used: MapPoint isBad(), GetObservations(),
+    // GetReferenceKeyFrame(), GetWorldPos(), mNormalVector, mfMaxDistance, mfMinDistance, mDescriptor; KeyFrame isBad(),
+    // GetCameraCenter(), mvKeysUn, mDescriptors, mvScaleFactors, mnScaleLevels.
+    template <class MapPointT>
+    static int UpdateMapPoints(const std::vector<MapPointT*>& vpMP, int what, int device = 0) {
+        status() = SLAMIT_OK;
+        std::vector<MapPointT*> mps;
+        std::map<MapPointT*, int32_t> mpSlot;
+        std::vector<int32_t> points;
+        for (size_t i = 0; i < vpMP.size(); ++i)
+            if (vpMP[i]) points.push_back(slotOf(mpSlot, mps, vpMP[i]));
+        if (points.empty()) return 0;
+        return updateMapPoints(mps, points, mps[0]->GetObservations(), what, device);
+    }
+
+    // LocalMapping::MapPointCulling (LocalMapping.cc:184-219) over mlpRecentAddedMapPoints for the current keyframe: ONE
+    // slamit_map_point_culling call gives every entry its verdict, then SetBadFlag() is called on the points the reference calls it on
+    // and the list is erased from, both in list order.  Returns the number of SetBadFlag() calls.
+    // GetFoundRatio() < 0.25f is evaluated here, on the caller's own float, and travels as found / visible = 0 / 1 or 1 / 1: the
+    // counters behind it are not public in the reference.
+    // THROUGH THE SHIM THIS SAVES NOTHING: the predicate is five loads and three compares per point.  The gain is
+    // slamit_map_point_culling_batch_dev beside the other resident steps.  Members used: MapPoint isBad(), GetFoundRatio(),
+    // Observations(), mnFirstKFid, SetBadFlag(); KeyFrame mnId.
+    template <class ListT, class KeyFrameT>
+    static int MapPointCulling(ListT& mlpRecentAddedMapPoints, KeyFrameT* pCurrentKF, bool mbMonocular, int device = 0) {
+        status() = SLAMIT_OK;
+        const int n = (int)mlpRecentAddedMapPoints.size();
+        if (n == 0) return 0;
+        if (n > SLAMIT_UPKEEP_MAX_RECENT) return shim::refuse<LocalMapping>("MapPointCulling: more than SLAMIT_UPKEEP_MAX_RECENT recent points", SLAMIT_ERR_CAPACITY);
+        std::vector<uint8_t> mp_bad(n), verdict(n, 0);
+        std::vector<int32_t> found(n), visible(n, 1), first(n), nobs(n), recent(n), kept(n, -1);
+        int j = 0;
+        for (typename ListT::iterator lit = mlpRecentAddedMapPoints.begin(); lit != mlpRecentAddedMapPoints.end(); ++lit, ++j) {
+            mp_bad[j] = (*lit)->isBad() ? 1 : 0;
+            found[j] = (*lit)->GetFoundRatio() < 0.25f ? 0 : 1;
+            first[j] = (int32_t)(*lit)->mnFirstKFid;
+            nobs[j] = (*lit)->Observations();
+            recent[j] = j;
+        }
+        slamit_map_index M;
+        memset(&M, 0, sizeof(M));
+        M.n_kf = 0; M.n_mp = n; M.mp_bad = mp_bad.data();
+        slamit_point_index X;
+        memset(&X, 0, sizeof(X));
+        X.mp_nobs = nobs.data(); X.mp_found = found.data(); X.mp_visible = visible.data(); X.mp_first_kf = first.data();
+        int32_t n_kept = 0, st = 0;
+        const int rc = slamit_map_point_culling(device, &M, &X, (int32_t)pCurrentKF->mnId, mbMonocular ? 1 : 0, n, recent.data(), verdict.data(), kept.data(), &n_kept, &st);
+        if (rc != SLAMIT_OK) return shim::report<LocalMapping>("MapPointCulling: slamit_map_point_culling", rc);
+        if (st != 0) return shim::refuse<LocalMapping>("MapPointCulling: slamit_map_point_culling reported a status on tables built here", SLAMIT_ERR_STATE);
+        int calls = 0;
+        j = 0;
+        for (typename ListT::iterator lit = mlpRecentAddedMapPoints.begin(); lit != mlpRecentAddedMapPoints.end(); ++j) {
+            if (verdict[j] == SLAMIT_UPKEEP_KEPT) { ++lit; continue; }
+            if (verdict[j] == SLAMIT_UPKEEP_LOW_RATIO || verdict[j] == SLAMIT_UPKEEP_FEW_OBS) { (*lit)->SetBadFlag(); ++calls; }   // :206, :211
+            lit = mlpRecentAddedMapPoints.erase(lit);
+        }
+        return calls;
     }
 
     static int LastStatus() { return status(); }
@@ -379,6 +455,109 @@ private:
                 ++calls;
             }
         return calls;
+    }
+
+    // mps: the distinct listed points; points: the list as slots of mps; the third argument names the keyframe type
+    template <class MapPointT, class KeyFrameT>
+    static int updateMapPoints(const std::vector<MapPointT*>& mps, const std::vector<int32_t>& points, const std::map<KeyFrameT*, size_t>&, int what, int device) {
+        typedef typename std::map<KeyFrameT*, size_t>::const_iterator ObsIt;
+        if (what < 1 || what > 3) return shim::refuse<LocalMapping>("UpdateMapPoints: `what` outside 1..3");
+        if (points.size() > (size_t)SLAMIT_UPKEEP_MAX_POINTS) return shim::refuse<LocalMapping>("UpdateMapPoints: more than SLAMIT_UPKEEP_MAX_POINTS points", SLAMIT_ERR_CAPACITY);
+        const int n_mp = (int)mps.size();
+        std::vector<std::map<KeyFrameT*, size_t> > obsOf(n_mp);
+        std::vector<KeyFrameT*> refOf(n_mp, (KeyFrameT*)0);
+        std::set<KeyFrameT*> all;
+        for (int p = 0; p < n_mp; ++p) {
+            obsOf[p] = mps[p]->GetObservations();
+            refOf[p] = mps[p]->GetReferenceKeyFrame();
+            if (refOf[p]) all.insert(refOf[p]);
+            for (ObsIt it = obsOf[p].begin(); it != obsOf[p].end(); ++it) all.insert(it->first);
+        }
+        if (all.empty()) return (int)points.size();   // nothing observed, no reference keyframe: the reference returns at :262 / :351
+        const std::vector<KeyFrameT*> kfs(all.begin(), all.end());   // a std::set orders by std::less
+        std::map<KeyFrameT*, int32_t> kfSlot;
+        for (size_t k = 0; k < kfs.size(); ++k) kfSlot[kfs[k]] = (int32_t)k;
+        const int n_kf = (int)kfs.size();
+        if (n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return shim::refuse<LocalMapping>("UpdateMapPoints: more than SLAMIT_LOCAL_MAP_MAX_KF keyframes around the points", SLAMIT_ERR_CAPACITY);
+        // a keyframe's row: its keypoint 0, then the listed points' observations in the order met
+        std::vector<std::vector<size_t> > rowOf(n_kf);
+        for (int k = 0; k < n_kf; ++k)
+            if (!kfs[k]->mvKeysUn.empty()) rowOf[k].push_back(0);
+        std::vector<int32_t> obs_ptr(n_mp + 1, 0), obs_kf, obs_idx, mp_ref(n_mp, -1);
+        std::vector<uint8_t> mp_bad(n_mp, 0), kf_bad(n_kf, 0), mp_desc((size_t)n_mp * 32, 0);
+        std::vector<int> good(n_mp, 0);
+        std::vector<float> mp_pos((size_t)n_mp * 3), mp_normal((size_t)n_mp * 3, 0.f), mp_max(n_mp, 0.f), mp_min(n_mp, 0.f);
+        for (int k = 0; k < n_kf; ++k) kf_bad[k] = kfs[k]->isBad() ? 1 : 0;
+        for (int p = 0; p < n_mp; ++p) {
+            mp_bad[p] = mps[p]->isBad() ? 1 : 0;
+            if (refOf[p]) mp_ref[p] = kfSlot[refOf[p]];
+            shim::load3(mps[p]->GetWorldPos(), &mp_pos[3 * (size_t)p]);
+            for (ObsIt it = obsOf[p].begin(); it != obsOf[p].end(); ++it) {
+                const int k = kfSlot[it->first];
+                obs_kf.push_back(k);
+                obs_idx.push_back((int32_t)rowOf[k].size());
+                rowOf[k].push_back(it->second);
+                good[p] += !kf_bad[k];
+            }
+            obs_ptr[p + 1] = (int32_t)obs_kf.size();
+        }
+        std::vector<int32_t> kf_mp_ptr(n_kf + 1, 0);
+        std::vector<uint8_t> kf_octave, kf_desc, obs_octave(obs_kf.size(), 0);
+        std::vector<float> kf_center((size_t)n_kf * 3);
+        for (int k = 0; k < n_kf; ++k) {
+            shim::load3(kfs[k]->GetCameraCenter(), &kf_center[3 * (size_t)k]);
+            for (size_t e = 0; e < rowOf[k].size(); ++e) {
+                const size_t i = rowOf[k][e];
+                kf_octave.push_back((uint8_t)kfs[k]->mvKeysUn[i].octave);
+                const size_t at = kf_desc.size();
+                kf_desc.resize(at + 32, 0);
+                if ((int)i < kfs[k]->mDescriptors.rows) memcpy(&kf_desc[at], kfs[k]->mDescriptors.ptr((int)i), 32);
+            }
+            kf_mp_ptr[k + 1] = (int32_t)kf_octave.size();
+        }
+        for (size_t o = 0; o < obs_kf.size(); ++o) obs_octave[o] = kf_octave[(size_t)kf_mp_ptr[obs_kf[o]] + obs_idx[o]];
+        int32_t none32 = -1;
+        uint8_t none8 = 0;
+        slamit_map_index M;
+        memset(&M, 0, sizeof(M));
+        M.n_kf = n_kf; M.n_mp = n_mp;
+        M.obs_ptr = obs_ptr.data(); M.obs_kf = obs_kf.empty() ? &none32 : obs_kf.data(); M.mp_bad = mp_bad.data(); M.kf_bad = kf_bad.data();
+        M.kf_mp_ptr = kf_mp_ptr.data(); M.mp_pos = mp_pos.data();
+        slamit_point_index X;
+        memset(&X, 0, sizeof(X));
+        X.n_levels = kfs[0]->mnScaleLevels;
+        for (int l = 0; l < SLAMIT_MAX_LEVELS && l < (int)kfs[0]->mvScaleFactors.size(); ++l) X.scale_factors[l] = kfs[0]->mvScaleFactors[l];
+        X.obs_idx = obs_idx.empty() ? &none32 : obs_idx.data(); X.obs_octave = obs_octave.empty() ? &none8 : obs_octave.data();
+        X.kf_octave = kf_octave.empty() ? &none8 : kf_octave.data(); X.kf_center = kf_center.data(); X.kf_desc = kf_desc.empty() ? &none8 : kf_desc.data();
+        X.mp_ref_kf = mp_ref.data(); X.mp_normal = mp_normal.data(); X.mp_max_dist = mp_max.data(); X.mp_min_dist = mp_min.data(); X.mp_desc = mp_desc.data();
+        std::vector<int32_t> st(points.size(), 0);
+        const int rc = slamit_update_points(device, &M, &X, (int32_t)points.size(), points.data(), what, st.data());
+        if (rc != SLAMIT_OK) return shim::report<LocalMapping>("UpdateMapPoints: slamit_update_points", rc);
+        const int keeps_normal = SLAMIT_UPKEEP_NO_REF | SLAMIT_UPKEEP_REF_NO_KP | SLAMIT_UPKEEP_OCTAVE | SLAMIT_UPKEEP_OBS_OVERFLOW;
+        int any = 0;
+        for (size_t j = 0; j < points.size(); ++j) {
+            const int p = points[j];
+            MapPointT* pMP = mps[p];
+            any |= st[j];
+            if (mp_bad[p] || obsOf[p].empty() || (st[j] & SLAMIT_UPKEEP_OBS_OVERFLOW)) continue;   // :257, :262, :344, :351
+            if ((what & SLAMIT_UPKEEP_NORMAL) && !(st[j] & keeps_normal)) {
+                cv::Mat nrm(3, 1, CV_32F);
+                for (int r = 0; r < 3; ++r) nrm.at<float>(r, 0) = mp_normal[3 * (size_t)p + r];
+                pMP->mNormalVector = nrm;
+                pMP->mfMaxDistance = mp_max[p];
+                pMP->mfMinDistance = mp_min[p];
+            }
+            if ((what & SLAMIT_UPKEEP_DESC) && good[p] > 0 && !(st[j] & SLAMIT_UPKEEP_DESC_OVERFLOW)) {   // :275
+                cv::Mat d(1, 32, CV_8U);
+                memcpy(d.ptr(0), &mp_desc[32 * (size_t)p], 32);
+                pMP->mDescriptor = d;
+            }
+        }
+        if (any & (SLAMIT_UPKEEP_OBS_OVERFLOW | SLAMIT_UPKEEP_DESC_OVERFLOW))
+            shim::refuse<LocalMapping>("UpdateMapPoints: a point above SLAMIT_UPKEEP_MAX_OBS observers or SLAMIT_DISTINCTIVE_MAX good ones was left as it was", SLAMIT_ERR_CAPACITY);
+        else if (any & (keeps_normal | SLAMIT_UPKEEP_BAD_SLOT))
+            shim::refuse<LocalMapping>("UpdateMapPoints: a point without a usable reference keyframe or level kept its normal and distances");
+        return (int)points.size();
     }
 
     static bool never() { return false; }
