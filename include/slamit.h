@@ -1617,6 +1617,100 @@ struct slamit_point_culling_batch_rec {
 typedef struct slamit_point_culling_batch_rec slamit_point_culling_batch_rec;
 int slamit_map_point_culling_batch_dev(int device, const slamit_point_culling_batch_rec* batch, void* stream);
 
+/* ---- Map edits: AddObservation, EraseObservation, SetBadFlag on the resident tables (local mapping) ----
+ * MapPoint::AddObservation, ::EraseObservation and ::SetBadFlag (src/MapPoint.cc:104-174) with KeyFrame::AddMapPoint /
+ * ::EraseMapPointMatch (src/KeyFrame.cc:215-243), applied to the tables of slamit_map_index and the columns of slamit_edit_index by
+ * one call (csrc/map_edit.h states the walk).  A list of n edits is applied AS IF SEQUENTIALLY IN LIST ORDER; the
+ * result equals the sequential walk exactly.  Every id is a slot (int32), -1 = none.
+ *   SLAMIT_EDIT_ADD_OBS    kf already observes mp: nothing of the point changes.  Else (kf, idx, octave, weight) is appended to the
+ *                          point's row and mp_nobs += weight (1, or 2 where mvuRight[idx] >= 0).  No bad test, as in the reference.
+ *                          With SLAMIT_EDIT_MATCH also kf_mp[kf][idx] = mp, unconditional (KeyFrame::AddMapPoint).
+ *   SLAMIT_EDIT_ERASE_OBS  with SLAMIT_EDIT_MATCH first kf_mp[kf][i] = -1 where the point holds kf at index i (EraseMapPointMatch).
+ *                          Then, kf being an observer: mp_nobs -= its obs_weight, the entry goes; mp_ref_kf == kf becomes the remaining
+ *                          observer with the smallest slot, or -1 with SLAMIT_EDIT_REF_END where the reference reads end();
+ *                          mp_nobs <= 2 runs SET_BAD.  kf not an observer: nothing.
+ *   SLAMIT_EDIT_SET_BAD    mp_bad = 1, kf_mp[k][i] = -1 for every observation (k, i) by index, the row is emptied; mp_nobs stays.
+ * kf_mp[kf][idx] after the call is the value of the write with the largest list index.  The observation table is written OUT OF
+ * PLACE: obs_ptr_out .. obs_weight_out are a packed CSR with ascending pointers from 0 that every reader of slamit_map_index takes
+ * unchanged (a caller alternates two buffer sets); a new row is the old row's order with erased entries closed up and added ones
+ * appended in list order.  mp_bad, mp_nobs, mp_ref_kf and kf_mp are rewritten IN PLACE.  MapPoint::Replace and KeyFrame::SetBadFlag's
+ * spanning-tree walk are not here; appending a new keyframe's kf_mp row and Map::EraseMapPoint stay the caller's.
+ * COST: as for the local map, the host form is for parity and tests; the gain is the resident form.
+ * Kinds, flags, status bits (per point; BAD_SLOT and TABLE_OVERFLOW also per call) and ceilings: */
+#define SLAMIT_EDIT_ADD_OBS 1
+#define SLAMIT_EDIT_ERASE_OBS 2
+#define SLAMIT_EDIT_SET_BAD 3
+#define SLAMIT_EDIT_MATCH 1               /* flags: also the keyframe's side of the edit */
+#define SLAMIT_EDIT_REF_END 1             /* the reference keyframe was erased as the last observer: mp_ref_kf = -1 */
+#define SLAMIT_EDIT_EDIT_OVERFLOW 2       /* more than SLAMIT_EDIT_MAX_PER_POINT edits of this point: none of them was applied */
+#define SLAMIT_EDIT_OBS_OVERFLOW 4        /* a row above SLAMIT_UPKEEP_MAX_OBS, or pushed past it: copied unchanged, none applied */
+#define SLAMIT_EDIT_BAD_SLOT 8            /* device form: an edit or an observation with a slot outside its table was skipped */
+#define SLAMIT_EDIT_TABLE_OVERFLOW 16     /* the new table needs more than obs_cap_out entries: NOTHING was written but n_obs_out */
+#define SLAMIT_EDIT_MAX_PER_POINT 64      /* edits of one point per call: a bucket is ordered by one wavefront */
+#define SLAMIT_EDIT_MAX_EDITS (1 << 20)   /* edits per list */
+
+struct slamit_map_edit {
+    int32_t kind, flags;
+    int32_t mp, kf, idx;           /* the point, the keyframe, the keypoint index in it (ADD_OBS only) */
+    uint8_t octave, weight;        /* ADD_OBS: what goes beside the new observation; weight is 1 or 2 */
+    uint8_t pad[2];
+};
+typedef struct slamit_map_edit slamit_map_edit;
+
+/* The arrays beside one slamit_map_index that the edits read and write.  Host pointers in the host form, device pointers in the batch
+ * record.  Of the map record the call reads n_kf, n_mp, obs_ptr, obs_kf and kf_mp_ptr. */
+struct slamit_edit_index {
+    const int32_t* obs_idx;        /* beside obs_kf, read-only: may be the memory of slamit_point_index.obs_idx */
+    const uint8_t* obs_octave;     /* beside obs_kf: as slamit_covis_index.obs_octave */
+    const uint8_t* obs_weight;     /* beside obs_kf: as slamit_covis_index.obs_weight */
+    uint8_t* mp_bad;               /* [n_mp] in / out: the memory the map record's mp_bad points to */
+    int32_t* mp_nobs;              /* [n_mp] in / out: likewise the covis / point records' */
+    int32_t* mp_ref_kf;            /* [n_mp] in / out */
+    int32_t* kf_mp;                /* in / out: the memory the map record's kf_mp points to */
+    int32_t* obs_ptr_out;          /* [n_mp + 1] out */
+    int32_t* obs_kf_out;           /* [obs_cap_out] out, as the next three */
+    int32_t* obs_idx_out;
+    uint8_t* obs_octave_out;
+    uint8_t* obs_weight_out;
+    int32_t obs_cap_out;           /* entries the four output columns hold */
+    int32_t reserved;
+};
+typedef struct slamit_edit_index slamit_edit_index;
+
+/* One list over one map (host pointers, synchronous).  status_mp[n_mp] out: the status of every point (0 for one without edits);
+ * touched[n_mp] in / out: the first *n_touched entries are the points of which an edit appended or removed an observation, in
+ * ascending slot (the layout of slamit_points_batch_rec.d_points / d_n); *n_obs_out: the entries the new table needs; *status out.
+ * Entries of the output columns past *n_obs_out and of touched past *n_touched are left as the caller filled them.  With
+ * SLAMIT_EDIT_TABLE_OVERFLOW only *n_obs_out and *status are written.  A null table, a slot, index, kind or weight outside its range,
+ * a CSR pointer array that does not ascend from 0 fails with SLAMIT_ERR_ARG, n above SLAMIT_EDIT_MAX_EDITS with SLAMIT_ERR_CAPACITY,
+ * each with a message and before anything is launched. */
+int slamit_map_edit_apply(int device, const slamit_map_index* map, const slamit_edit_index* edit, int32_t n, const slamit_map_edit* edits,
+                          int32_t* status_mp, int32_t* touched, int32_t* n_touched, int32_t* n_obs_out, int32_t* status);
+
+/* One list per map for n_maps maps, everything resident.  `maps` and `edit` are HOST arrays of records holding DEVICE pointers; map m
+ * takes the first d_n[m] (clamped to [0, cap]) edits of d_edits[m].  mp_cap >= every n_mp; kfmp_cap >= every map's kf_mp_ptr[n_kf].
+ * The device cannot be shown its tables first: an edit whose point lies outside the table is skipped (SLAMIT_EDIT_BAD_SLOT in
+ * d_status[m]), an edit or an observation whose keyframe or index does is skipped, never dereferenced (the same bit in the point's
+ * status).  Asynchronous on `stream`, no synchronisation, no state; the workspace is cleared on the stream by the call.
+ * slamit_update_points_batch_dev can follow on the stream with d_touched / d_n_touched as its d_points / d_n (cap = mp_cap). */
+struct slamit_map_edit_batch_rec {
+    int32_t n_maps, cap, mp_cap, kfmp_cap;
+    const slamit_map_index* maps;      /* HOST [n_maps], device pointers inside; n_maps <= SLAMIT_LOCAL_MAP_MAX_MAPS */
+    const slamit_edit_index* edit;     /* HOST [n_maps], device pointers inside */
+    const slamit_map_edit* d_edits;    /* [n_maps][cap], cap <= SLAMIT_EDIT_MAX_EDITS */
+    const int32_t* d_n;                /* [n_maps] */
+    int32_t* d_status_mp;              /* [n_maps][mp_cap] out */
+    int32_t* d_touched;                /* [n_maps][mp_cap] in / out */
+    int32_t* d_n_touched;              /* [n_maps] out */
+    int32_t* d_n_obs_out;              /* [n_maps] out */
+    int32_t* d_status;                 /* [n_maps] out */
+    void* d_workspace;                 /* slamit_map_edit_workspace(n_maps, cap, mp_cap, kfmp_cap) bytes, 8-byte aligned */
+    size_t workspace_bytes;
+};
+typedef struct slamit_map_edit_batch_rec slamit_map_edit_batch_rec;
+size_t slamit_map_edit_workspace(int n_maps, int cap, int mp_cap, int kfmp_cap);
+int slamit_map_edit_batch_dev(int device, const slamit_map_edit_batch_rec* batch, void* stream);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 
 const char* slamit_last_error(void);

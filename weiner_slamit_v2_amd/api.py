@@ -381,6 +381,30 @@ POINT_INDEX_TABLES = (("obs_idx", np.int32), ("obs_octave", np.uint8), ("kf_octa
                       ("mp_ref_kf", np.int32), ("mp_nobs", np.int32), ("mp_found", np.int32), ("mp_visible", np.int32), ("mp_first_kf", np.int32),
                       ("mp_normal", np.float32), ("mp_max_dist", np.float32), ("mp_min_dist", np.float32), ("mp_desc", np.uint8))
 POINT_PLANES = ("mp_normal", "mp_max_dist", "mp_min_dist", "mp_desc")   # what update_points rewrites
+
+
+class EditIndexRec(C.Structure):   # struct slamit_edit_index
+    _fields_ = [("obs_idx", C.c_void_p), ("obs_octave", C.c_void_p), ("obs_weight", C.c_void_p), ("mp_bad", C.c_void_p), ("mp_nobs", C.c_void_p),
+                ("mp_ref_kf", C.c_void_p), ("kf_mp", C.c_void_p), ("obs_ptr_out", C.c_void_p), ("obs_kf_out", C.c_void_p), ("obs_idx_out", C.c_void_p),
+                ("obs_octave_out", C.c_void_p), ("obs_weight_out", C.c_void_p), ("obs_cap_out", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MapEditBatchRec(C.Structure):   # struct slamit_map_edit_batch_rec
+    _fields_ = [("n_maps", C.c_int32), ("cap", C.c_int32), ("mp_cap", C.c_int32), ("kfmp_cap", C.c_int32), ("maps", C.POINTER(MapIndexRec)),
+                ("edit", C.POINTER(EditIndexRec)), ("d_edits", C.c_void_p), ("d_n", C.c_void_p), ("d_status_mp", C.c_void_p), ("d_touched", C.c_void_p),
+                ("d_n_touched", C.c_void_p), ("d_n_obs_out", C.c_void_p), ("d_status", C.c_void_p), ("d_workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
+
+
+# SLAMIT_EDIT_*: the kinds, the flag, the status bits, the ceilings; struct slamit_map_edit as a numpy record
+EDIT_ADD_OBS, EDIT_ERASE_OBS, EDIT_SET_BAD, EDIT_MATCH = 1, 2, 3, 1
+EDIT_STATUS = {"REF_END": 1, "EDIT_OVERFLOW": 2, "OBS_OVERFLOW": 4, "BAD_SLOT": 8, "TABLE_OVERFLOW": 16}
+EDIT_MAX_PER_POINT, EDIT_MAX_EDITS = 64, 1 << 20
+EDIT_DTYPE = np.dtype([("kind", "<i4"), ("flags", "<i4"), ("mp", "<i4"), ("kf", "<i4"), ("idx", "<i4"), ("octave", "u1"), ("weight", "u1"), ("pad", "u1", 2)])
+# slamit_edit_index: the columns read, the arrays rewritten in place, the observation table written out of place
+EDIT_INDEX_COLUMNS = (("obs_idx", np.int32), ("obs_octave", np.uint8), ("obs_weight", np.uint8))
+EDIT_INDEX_INPLACE = (("mp_bad", np.uint8), ("mp_nobs", np.int32), ("mp_ref_kf", np.int32), ("kf_mp", np.int32))
+EDIT_INDEX_OUT = (("obs_kf_out", np.int32), ("obs_idx_out", np.int32), ("obs_octave_out", np.uint8), ("obs_weight_out", np.uint8))
 DEPTH_TYPES = ("f32", "u16")   # SLAMIT_DEPTH_*: the index is the type
 DEPTH_PLANE_DTYPE = np.dtype([("data", "<u8"), ("pitch", "<u8"), ("width", "<i4"), ("height", "<i4"), ("type", "<i4"), ("factor", "<f4")])   # slamit_depth_plane
 RGBD_STATUS = ("no_depth", "depth", "outside")
@@ -452,7 +476,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_map_edit_apply", "slamit_map_edit_workspace", "slamit_map_edit_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -544,6 +568,10 @@ def lib():
         L.slamit_update_points_batch_dev.argtypes = [i32, C.POINTER(PointsBatchRec), vp]
         L.slamit_map_point_culling.argtypes = [i32, C.POINTER(MapIndexRec), C.POINTER(PointIndexRec), i32, i32, i32, vp, vp, vp, vp, vp]
         L.slamit_map_point_culling_batch_dev.argtypes = [i32, C.POINTER(PointCullingBatchRec), vp]
+        L.slamit_map_edit_apply.argtypes = [i32, C.POINTER(MapIndexRec), C.POINTER(EditIndexRec), i32, vp, vp, vp, vp, vp, vp]
+        L.slamit_map_edit_workspace.argtypes = [i32, i32, i32, i32]
+        L.slamit_map_edit_workspace.restype = sz
+        L.slamit_map_edit_batch_dev.argtypes = [i32, C.POINTER(MapEditBatchRec), vp]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_bow_search_stereo.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), C.POINTER(BowStereo), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
@@ -2407,8 +2435,9 @@ def local_points(tables, frame_mp, local_kf, frame_seen=(), q_cap=4096, fill=-1,
 
 
 class MapIndex:
-    """A map's tables uploaded once (the resident form's slamit_map_index): MapIndex(tables).rec holds the device pointers.  The caller
-    re-uploads a table when the map changes it; nothing here is per frame."""
+    """A map's tables uploaded once (the resident form's slamit_map_index): MapIndex(tables).rec holds the device pointers.  Nothing here
+    is per frame.  Where the map changes which keyframe observes which point, map_edit_batch_dev rewrites the tables in HBM through an
+    EditIndex beside this record; any other change is a table the caller uploads again."""
 
     def __init__(self, tables, device=0):
         import torch
@@ -2685,3 +2714,150 @@ def map_point_culling_batch_dev(maps, pts, t, device=0, stream=None):
     rec = PointCullingBatchRec(b, len(maps), cap, 0, M, X, t["list_map"].data_ptr(), t["cur_id"].data_ptr(), t["monocular"].data_ptr(), t["n"].data_ptr(),
                                t["recent"].data_ptr(), t["verdict"].data_ptr(), t["kept"].data_ptr(), t["n_kept"].data_ptr(), t["status"].data_ptr())
     _check(lib().slamit_map_point_culling_batch_dev(device, C.byref(rec), stream), "slamit_map_point_culling_batch_dev")
+
+
+def edit_records(edits):
+    """Edits as an array of slamit_map_edit: an EDIT_DTYPE array as it is, else rows (kind, flags, mp, kf, idx, octave, weight)."""
+    if isinstance(edits, np.ndarray) and edits.dtype == EDIT_DTYPE:
+        return np.ascontiguousarray(edits).reshape(-1)
+    rows = list(edits)
+    out = np.zeros(len(rows), EDIT_DTYPE)
+    for i, r in enumerate(rows):
+        out[i] = tuple(int(v) for v in r) + ((0, 0),)
+    return out
+
+
+def map_edit(tables, edit, edits, obs_cap_out=None, fill=None, device=0):
+    """MapPoint::AddObservation / ::EraseObservation / ::SetBadFlag with the keyframes' side (MapPoint.cc:104-174, KeyFrame.cc:215-243) for
+    a list of edits applied as if sequentially, over a map's tables (slamit_map_index: n_kf, n_mp, obs_ptr, obs_kf, kf_mp_ptr, kf_mp,
+    mp_bad) and its edit columns (dict: obs_idx, obs_octave, obs_weight beside obs_kf; mp_nobs, mp_ref_kf; mp_bad / kf_mp where they are
+    not taken from `tables`).  edits: edit_records().  The caller's arrays are not modified.  obs_cap_out: the room of the new table
+    (default: the old table plus one entry per edit).  fill: optional dict of prefilled output arrays (obs_ptr_out, obs_kf_out, obs_idx_out,
+    obs_octave_out, obs_weight_out, status_mp, touched, n_touched), copied.  -> dict: obs_ptr, obs_kf, mp_bad, kf_mp (what MapIndex /
+    _map_index_host take in place of the old ones: dict(tables, **{k: out[k] for k in ("obs_ptr", "obs_kf", "mp_bad", "kf_mp")})),
+    obs_idx, obs_octave, obs_weight, mp_nobs, mp_ref_kf, status_mp (n_mp), touched (the first n_touched of it), n_touched, n_obs_out,
+    status, and `raw`: the output arrays in full.  With EDIT_STATUS["TABLE_OVERFLOW"] the tables returned are the old ones."""
+    rec, keep = _map_index_host(tables)
+    n_mp = max(rec.n_mp, 0)
+    ed = edit_records(edits)
+    src = dict(edit)
+    for key in ("mp_bad", "kf_mp"):
+        src.setdefault(key, tables.get(key))
+    n_obs = int(np.asarray(tables["obs_ptr"]).reshape(-1)[-1]) if tables.get("obs_ptr") is not None and len(np.asarray(tables["obs_ptr"]).reshape(-1)) else 0
+    cap = n_obs + len(ed) if obs_cap_out is None else int(obs_cap_out)
+    fill = fill or {}
+    xrec, xkeep = EditIndexRec(), {}
+    for key, dt in EDIT_INDEX_COLUMNS:
+        if src.get(key) is not None:
+            xkeep[key] = np.ascontiguousarray(src[key], dt).reshape(-1)
+            setattr(xrec, key, xkeep[key].ctypes.data)
+    for key, dt in EDIT_INDEX_INPLACE:
+        if src.get(key) is not None:
+            xkeep[key] = np.array(src[key], dt).reshape(-1)
+            setattr(xrec, key, xkeep[key].ctypes.data)
+    for key, dt, count in (("obs_ptr_out", np.int32, n_mp + 1),) + tuple((k, d, max(cap, 0)) for k, d in EDIT_INDEX_OUT):
+        xkeep[key] = np.zeros(count, dt) if fill.get(key) is None else np.array(fill[key], dt).reshape(-1)
+        if len(xkeep[key]) != count:
+            raise SlamitError("map_edit: fill[%s] does not hold %d entries" % (key, count))
+        setattr(xrec, key, xkeep[key].ctypes.data if count else None)
+    xrec.obs_cap_out = cap
+    st_mp = np.zeros(n_mp, np.int32) if fill.get("status_mp") is None else np.array(fill["status_mp"], np.int32).reshape(-1)
+    tch = np.full(n_mp, -1, np.int32) if fill.get("touched") is None else np.array(fill["touched"], np.int32).reshape(-1)
+    if len(st_mp) != n_mp or len(tch) != n_mp:
+        raise SlamitError("map_edit: status_mp and touched hold n_mp entries")
+    nt, no, st = np.array([fill.get("n_touched", 0)], np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+    _check(lib().slamit_map_edit_apply(device, C.byref(rec), C.byref(xrec), len(ed), _np_ptr(ed) if len(ed) else None, _np_ptr(st_mp) if n_mp else None,
+                                       _np_ptr(tch) if n_mp else None, _np_ptr(nt), _np_ptr(no), _np_ptr(st)), "slamit_map_edit_apply")
+    del keep
+    status, need = int(st[0]), int(no[0])
+    out = {"status": status, "n_obs_out": need, "n_touched": int(nt[0]), "status_mp": st_mp, "raw": dict(xkeep, status_mp=st_mp, touched=tch)}
+    if status & EDIT_STATUS["TABLE_OVERFLOW"]:
+        out.update(obs_ptr=np.array(tables["obs_ptr"], np.int32).reshape(-1), obs_kf=np.array(tables["obs_kf"], np.int32).reshape(-1), touched=tch[:0])
+        for key, _ in EDIT_INDEX_COLUMNS:
+            out[key] = xkeep[key].copy()
+    else:
+        out.update(obs_ptr=xkeep["obs_ptr_out"], obs_kf=xkeep["obs_kf_out"][:need], touched=tch[:int(nt[0])])
+        for key, _ in EDIT_INDEX_COLUMNS:
+            out[key] = xkeep[key + "_out"][:need]
+    for key, _ in EDIT_INDEX_INPLACE:
+        out[key] = xkeep.get(key)
+    return out
+
+
+class EditIndex:
+    """The arrays map_edit_batch_dev reads and writes beside a MapIndex (the resident form's slamit_edit_index), with TWO buffer sets for
+    the observation table.  EditIndex(edit, map_index, obs_cap, covis=None, points=None): obs_idx / obs_octave / obs_weight and mp_nobs /
+    mp_ref_kf are uploaded from `edit` unless a CovisIndex / PointIndex is given, whose tensors are then used (and whose records follow
+    every swap); mp_bad and kf_mp ARE map_index's tensors, rewritten in place.  obs_cap: entries each buffer set of the table holds.
+    .rec reads the current set and writes the other; after map_edit_batch_dev has run, swap() makes the written set the current one in
+    map_index.rec (and the covis / points records) and the old one the next target, so every reader takes the new table unchanged."""
+
+    def __init__(self, edit, map_index, obs_cap, covis=None, points=None):
+        import torch
+
+        self.map_index, self.covis, self.points, self.device, self.obs_cap = map_index, covis, points, map_index.device, int(obs_cap)
+        dev = "cuda:%d" % self.device
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt).reshape(-1) if np.size(a) else np.zeros(1, dt)).to(dev)
+        room = lambda t: torch.cat([t, torch.zeros(max(self.obs_cap, 1) - t.numel(), dtype=t.dtype, device=dev)]) if t.numel() < max(self.obs_cap, 1) else t
+        cur = {"obs_ptr": map_index.t["obs_ptr"], "obs_kf": room(map_index.t["obs_kf"])}
+        cur["obs_idx"] = room(points.t["obs_idx"] if points is not None else up(edit["obs_idx"], np.int32))
+        cur["obs_octave"] = room(covis.t["obs_octave"] if covis is not None else points.t["obs_octave"] if points is not None else up(edit["obs_octave"], np.uint8))
+        cur["obs_weight"] = room(covis.t["obs_weight"] if covis is not None else up(edit["obs_weight"], np.uint8))
+        self.sets = [cur, {k: torch.zeros_like(v) for k, v in cur.items()}]
+        self.t = {"mp_bad": map_index.t["mp_bad"], "kf_mp": map_index.t["kf_mp"]}
+        self.t["mp_nobs"] = covis.t["mp_nobs"] if covis is not None else points.t["mp_nobs"] if points is not None else up(edit["mp_nobs"], np.int32)
+        self.t["mp_ref_kf"] = points.t["mp_ref_kf"] if points is not None else up(edit["mp_ref_kf"], np.int32)
+        if covis is not None and points is not None:   # one memory for what both records name
+            points.t["mp_nobs"] = self.t["mp_nobs"]
+            points.rec.mp_nobs = self.t["mp_nobs"].data_ptr()
+        self.rec = EditIndexRec()
+        self._point()
+
+    def _point(self):
+        cur, nxt = self.sets
+        mi = self.map_index
+        mi.t["obs_ptr"], mi.t["obs_kf"] = cur["obs_ptr"], cur["obs_kf"]
+        mi.rec.obs_ptr, mi.rec.obs_kf = cur["obs_ptr"].data_ptr(), cur["obs_kf"].data_ptr()
+        for idx, keys in ((self.covis, ("obs_octave", "obs_weight")), (self.points, ("obs_idx", "obs_octave"))):
+            if idx is not None:
+                for key in keys:
+                    idx.t[key] = cur[key]
+                    setattr(idx.rec, key, cur[key].data_ptr())
+        for key in ("obs_idx", "obs_octave", "obs_weight"):
+            setattr(self.rec, key, cur[key].data_ptr())
+        for key in ("mp_bad", "mp_nobs", "mp_ref_kf", "kf_mp"):
+            setattr(self.rec, key, self.t[key].data_ptr())
+        self.rec.obs_ptr_out = nxt["obs_ptr"].data_ptr()
+        for key in ("obs_kf", "obs_idx", "obs_octave", "obs_weight"):
+            setattr(self.rec, key + "_out", nxt[key].data_ptr())
+        self.rec.obs_cap_out = self.obs_cap
+
+    def swap(self):
+        """The table the last call wrote becomes the one every record reads; no copy, no synchronisation."""
+        self.sets.reverse()
+        self._point()
+
+
+def map_edit_workspace(n_maps, cap, mp_cap, kfmp_cap):
+    return int(lib().slamit_map_edit_workspace(n_maps, cap, mp_cap, kfmp_cap))
+
+
+def map_edit_batch_dev(maps, edit, t, device=0, stream=None):
+    """One edit list per map, resident.  maps / edit: lists of MapIndex / EditIndex; t: dict of torch CUDA tensors edits (B, cap, 24) u8 (the
+    bytes of EDIT_DTYPE records), n (B) i32, status_mp (B, mp_cap) i32, touched (B, mp_cap) i32 in / out, n_touched (B), n_obs_out (B),
+    status (B) i32, workspace: uint8, map_edit_workspace(B, cap, mp_cap, kfmp_cap) bytes with kfmp_cap = t["kfmp_cap"] >= every map's
+    number of kf_mp entries.  The new tables are written into each EditIndex's other buffer set: call swap() on each before the next
+    reader is ENQUEUED (the swap is host bookkeeping; the stream orders the work).  Asynchronous on `stream`."""
+    b, cap = t["edits"].shape[0], t["edits"].shape[1]
+    mp_cap = t["status_mp"].shape[1]
+    if len(maps) != b or len(edit) != b:
+        raise SlamitError("map_edit_batch_dev: one MapIndex, one EditIndex and one list per map")
+    _rows(t, "map_edit_batch_dev", (("edits", cap * EDIT_DTYPE.itemsize), ("status_mp", mp_cap), ("touched", mp_cap), ("n", 1), ("n_touched", 1), ("n_obs_out", 1),
+                                    ("status", 1)), b)
+    M, X = (MapIndexRec * max(b, 1))(), (EditIndexRec * max(b, 1))()
+    for i, (mi, ei) in enumerate(zip(maps, edit)):
+        M[i], X[i] = mi.rec, ei.rec
+    ws = t["workspace"]
+    rec = MapEditBatchRec(b, cap, mp_cap, int(t["kfmp_cap"]), M, X, t["edits"].data_ptr(), t["n"].data_ptr(), t["status_mp"].data_ptr(), t["touched"].data_ptr(),
+                          t["n_touched"].data_ptr(), t["n_obs_out"].data_ptr(), t["status"].data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
+    _check(lib().slamit_map_edit_batch_dev(device, C.byref(rec), stream), "slamit_map_edit_batch_dev")

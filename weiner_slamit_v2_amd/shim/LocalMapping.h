@@ -30,7 +30,8 @@
 // slot tables built from the caller's objects, one call each (slamit_update_connections, slamit_keyframe_culling), the results
 // written into the objects; for parity rather than speed.  UpdateMapPoints (MapPoint::UpdateNormalAndDepth and
 // ::ComputeDistinctiveDescriptors for a list of points, src/MapPoint.cc:248-377) and MapPointCulling (:184-219) are built the same way
-// over slamit_update_points and slamit_map_point_culling.
+// over slamit_update_points and slamit_map_point_culling, ApplyMapEdits (MapPoint::AddObservation, ::EraseObservation
+// and ::SetBadFlag for a list of edits, src/MapPoint.cc:104-174) over slamit_map_edit_apply (section 26).
 #ifndef SLAMIT_SHIM_LOCALMAPPING_H
 #define SLAMIT_SHIM_LOCALMAPPING_H
 
@@ -264,6 +265,130 @@ public:
             lit = mlpRecentAddedMapPoints.erase(lit);
         }
         return calls;
+    }
+
+    // One edit of ApplyMapEdits over the caller's objects: kind SLAMIT_EDIT_ADD_OBS (pMP->AddObservation(pKF, idx), with flags &
+    // SLAMIT_EDIT_MATCH also pKF->AddMapPoint(pMP, idx)), SLAMIT_EDIT_ERASE_OBS (with MATCH first pKF->EraseMapPointMatch(pMP), then
+    // pMP->EraseObservation(pKF)) or SLAMIT_EDIT_SET_BAD (pMP->SetBadFlag()).
+    template <class MapPointT, class KeyFrameT>
+    struct MapEdit {
+        int kind, flags;
+        MapPointT* pMP;
+        KeyFrameT* pKF;
+        size_t idx;
+    };
+
+    // The point-side mutators of the map (MapPoint.cc:104-174 with KeyFrame.cc:215-234) for a LIST of edits, applied as if one after the
+    // other in ONE slamit_map_edit_apply call.  Writes back mObservations, nObs, mbBad and mpRefKF of the points the edits name and the
+    // changed entries of mvpMapPoints of the keyframes around them, and calls pMap->EraseMapPoint on the points turned bad.  Returns the
+    // number of edits.  Keyframes -- the ones the edits name, the observers and the reference keyframes of the named points -- are
+    // numbered by std::less<KeyFrameT*>, so "the remaining observer with the smallest slot" is mObservations.begin() on this run.  Every
+    // point stored in those keyframes' mvpMapPoints gets a slot (an unnamed one an empty row), so that a SetBadFlag that erases by index
+    // erases whatever is stored there.  Where the reference reads end() (the reference keyframe erased as the last observer) mpRefKF
+    // becomes NULL.  A point with more than SLAMIT_EDIT_MAX_PER_POINT edits or SLAMIT_UPKEEP_MAX_OBS observers is left as it was, the
+    // others are written, and LastStatus() is SLAMIT_ERR_CAPACITY with a line on stderr.
+    // IT SAVES NOTHING THROUGH THE SHIM: building the tables walks the observations and the keyframes' rows that the three mutators
+    // touch a few entries of.  It is for parity and for integrations that want one code path; the gain is slamit_map_edit_batch_dev with
+    // the tables kept in HBM.  Members used (a friend declaration in the reference's classes): MapPoint mObservations, nObs, mbBad,
+    // mpRefKF; KeyFrame mvpMapPoints, mvuRight, mvKeysUn; Map EraseMapPoint().
+    template <class MapPointT, class KeyFrameT, class MapT>
+    static int ApplyMapEdits(const std::vector<MapEdit<MapPointT, KeyFrameT> >& edits, MapT* pMap, int device = 0) {
+        typedef typename std::map<KeyFrameT*, size_t>::const_iterator ObsIt;
+        status() = SLAMIT_OK;
+        const int n = (int)edits.size();
+        if (n == 0) return 0;
+        if (n > SLAMIT_EDIT_MAX_EDITS) return shim::refuse<LocalMapping>("ApplyMapEdits: more than SLAMIT_EDIT_MAX_EDITS edits", SLAMIT_ERR_CAPACITY);
+        std::vector<MapPointT*> mps;
+        std::map<MapPointT*, int32_t> mpSlot;
+        std::set<KeyFrameT*> all;
+        for (int i = 0; i < n; ++i) {
+            if (!edits[i].pMP || (edits[i].kind != SLAMIT_EDIT_SET_BAD && !edits[i].pKF)) return shim::refuse<LocalMapping>("ApplyMapEdits: an edit without its point or keyframe");
+            slotOf(mpSlot, mps, edits[i].pMP);
+            if (edits[i].kind != SLAMIT_EDIT_SET_BAD) all.insert(edits[i].pKF);
+        }
+        const int n_named = (int)mps.size();
+        for (int p = 0; p < n_named; ++p) {
+            if (mps[p]->mpRefKF) all.insert(mps[p]->mpRefKF);
+            for (ObsIt it = mps[p]->mObservations.begin(); it != mps[p]->mObservations.end(); ++it) all.insert(it->first);
+        }
+        const std::vector<KeyFrameT*> kfs(all.begin(), all.end());   // a std::set orders by std::less
+        std::map<KeyFrameT*, int32_t> kfSlot;
+        for (size_t k = 0; k < kfs.size(); ++k) kfSlot[kfs[k]] = (int32_t)k;
+        const int n_kf = (int)kfs.size();
+        if (n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return shim::refuse<LocalMapping>("ApplyMapEdits: more than SLAMIT_LOCAL_MAP_MAX_KF keyframes around the points", SLAMIT_ERR_CAPACITY);
+        std::vector<int32_t> kf_mp_ptr(n_kf + 1, 0), kf_mp;
+        for (int k = 0; k < n_kf; ++k) {
+            for (size_t i = 0; i < kfs[k]->mvpMapPoints.size(); ++i) kf_mp.push_back(kfs[k]->mvpMapPoints[i] ? slotOf(mpSlot, mps, kfs[k]->mvpMapPoints[i]) : -1);
+            kf_mp_ptr[k + 1] = (int32_t)kf_mp.size();
+        }
+        const int n_mp = (int)mps.size();
+        std::vector<int32_t> obs_ptr(n_mp + 1, 0), obs_kf, obs_idx, mp_nobs(n_mp, 0), mp_ref(n_mp, -1);
+        std::vector<uint8_t> obs_octave, obs_weight, mp_bad(n_mp, 0);
+        for (int p = 0; p < n_mp; ++p) {
+            if (p < n_named) {
+                mp_bad[p] = mps[p]->mbBad ? 1 : 0; mp_nobs[p] = mps[p]->nObs;
+                if (mps[p]->mpRefKF) mp_ref[p] = kfSlot[mps[p]->mpRefKF];
+                for (ObsIt it = mps[p]->mObservations.begin(); it != mps[p]->mObservations.end(); ++it) {
+                    KeyFrameT* kf = it->first;
+                    obs_kf.push_back(kfSlot[kf]); obs_idx.push_back((int32_t)it->second);
+                    obs_octave.push_back(it->second < kf->mvKeysUn.size() ? (uint8_t)kf->mvKeysUn[it->second].octave : 0);
+                    obs_weight.push_back(it->second < kf->mvuRight.size() && kf->mvuRight[it->second] >= 0 ? 2 : 1);
+                }
+            }
+            obs_ptr[p + 1] = (int32_t)obs_kf.size();
+        }
+        std::vector<slamit_map_edit> list(n);
+        for (int i = 0; i < n; ++i) {
+            slamit_map_edit& e = list[i];
+            memset(&e, 0, sizeof(e));
+            e.kind = edits[i].kind; e.flags = edits[i].flags; e.mp = mpSlot[edits[i].pMP];
+            if (e.kind == SLAMIT_EDIT_SET_BAD) continue;
+            KeyFrameT* kf = edits[i].pKF;
+            e.kf = kfSlot[kf]; e.idx = (int32_t)edits[i].idx;
+            if (e.kind == SLAMIT_EDIT_ADD_OBS) {
+                e.octave = edits[i].idx < kf->mvKeysUn.size() ? (uint8_t)kf->mvKeysUn[edits[i].idx].octave : 0;
+                e.weight = edits[i].idx < kf->mvuRight.size() && kf->mvuRight[edits[i].idx] >= 0 ? 2 : 1;
+            }
+        }
+        const size_t cap = obs_kf.size() + (size_t)n;
+        std::vector<int32_t> optr(n_mp + 1, 0), okf(cap, 0), oidx(cap, 0), st_mp(n_mp, 0), touched(n_mp, -1), kf_mp_new(kf_mp);
+        std::vector<uint8_t> ooct(cap, 0), owgt(cap, 0), bad_new(mp_bad);
+        std::vector<int32_t> nobs_new(mp_nobs), ref_new(mp_ref);
+        int32_t none32 = -1;
+        uint8_t none8 = 0;
+        slamit_map_index M;
+        memset(&M, 0, sizeof(M));
+        M.n_kf = n_kf; M.n_mp = n_mp; M.obs_ptr = obs_ptr.data(); M.obs_kf = obs_kf.empty() ? &none32 : obs_kf.data(); M.kf_mp_ptr = kf_mp_ptr.data();
+        slamit_edit_index X;
+        memset(&X, 0, sizeof(X));
+        X.obs_idx = obs_idx.empty() ? &none32 : obs_idx.data(); X.obs_octave = obs_octave.empty() ? &none8 : obs_octave.data();
+        X.obs_weight = obs_weight.empty() ? &none8 : obs_weight.data();
+        X.mp_bad = bad_new.data(); X.mp_nobs = nobs_new.data(); X.mp_ref_kf = ref_new.data(); X.kf_mp = kf_mp_new.empty() ? &none32 : kf_mp_new.data();
+        X.obs_ptr_out = optr.data(); X.obs_kf_out = okf.data(); X.obs_idx_out = oidx.data(); X.obs_octave_out = ooct.data(); X.obs_weight_out = owgt.data();
+        X.obs_cap_out = (int32_t)cap;
+        int32_t n_touched = 0, n_obs_out = 0, st = 0;
+        const int rc = slamit_map_edit_apply(device, &M, &X, n, list.data(), st_mp.data(), touched.data(), &n_touched, &n_obs_out, &st);
+        if (rc != SLAMIT_OK) return shim::report<LocalMapping>("ApplyMapEdits: slamit_map_edit_apply", rc);
+        if (st != 0) return shim::refuse<LocalMapping>("ApplyMapEdits: slamit_map_edit_apply reported a status on tables built here", SLAMIT_ERR_STATE);
+        int any = 0;
+        for (int p = 0; p < n_named; ++p) {
+            any |= st_mp[p];
+            if (st_mp[p] & (SLAMIT_EDIT_EDIT_OVERFLOW | SLAMIT_EDIT_OBS_OVERFLOW)) continue;
+            MapPointT* pMP = mps[p];
+            pMP->mObservations.clear();
+            for (int o = optr[p]; o < optr[p + 1]; ++o) pMP->mObservations[kfs[okf[o]]] = (size_t)oidx[o];
+            pMP->nObs = nobs_new[p];
+            pMP->mpRefKF = ref_new[p] < 0 ? (KeyFrameT*)0 : kfs[ref_new[p]];
+            const bool turned = bad_new[p] && !mp_bad[p];
+            pMP->mbBad = bad_new[p] != 0;
+            if (turned) pMap->EraseMapPoint(pMP);                          // MapPoint.cc:173
+        }
+        for (int k = 0; k < n_kf; ++k)
+            for (int e = kf_mp_ptr[k]; e < kf_mp_ptr[k + 1]; ++e)
+                if (kf_mp_new[e] != kf_mp[e]) kfs[k]->mvpMapPoints[e - kf_mp_ptr[k]] = kf_mp_new[e] < 0 ? (MapPointT*)0 : mps[kf_mp_new[e]];
+        if (any & (SLAMIT_EDIT_EDIT_OVERFLOW | SLAMIT_EDIT_OBS_OVERFLOW))
+            shim::refuse<LocalMapping>("ApplyMapEdits: a point above SLAMIT_EDIT_MAX_PER_POINT edits or SLAMIT_UPKEEP_MAX_OBS observers was left as it was", SLAMIT_ERR_CAPACITY);
+        return n;
     }
 
     static int LastStatus() { return status(); }
