@@ -1711,6 +1711,123 @@ typedef struct slamit_map_edit_batch_rec slamit_map_edit_batch_rec;
 size_t slamit_map_edit_workspace(int n_maps, int cap, int mp_cap, int kfmp_cap);
 int slamit_map_edit_batch_dev(int device, const slamit_map_edit_batch_rec* batch, void* stream);
 
+/* ---- MapPoint::Replace on the resident tables: the fuse lists of local mapping and loop closing ----
+ * MapPoint::Replace (src/MapPoint.cc:183-221) as ORBmatcher::Fuse (ORBmatcher.cc:956-973), LoopClosing::SearchAndFuse (:614-625) and
+ * ::CorrectLoop (:532-547) call it, with the AddObservation + AddMapPoint pair Fuse interleaves with it (csrc/map_replace.h states the
+ * ops).  A list of n ops is applied AS IF SEQUENTIALLY IN LIST ORDER; the result equals the sequential walk exactly.
+ *   SLAMIT_REPLACE_REPLACE  a = S, b = D.  a == b: nothing.  Else, for the entries (k, idx, octave, weight) of S's row in ascending
+ *                           keyframe slot: D's row holds k: kf_mp[k][idx] = -1; otherwise kf_mp[k][idx] = D, the entry is appended to
+ *                           D's row and mp_nobs[D] += weight.  S's row is emptied, mp_bad[S] = 1, mp_replaced[S] = D.
+ *                           mp_found[D] += mp_found[S], mp_visible[D] += mp_visible[S] (int32 wrap), with the values held at that
+ *                           moment.  No bad test on D; mp_nobs, mp_found, mp_visible of S stay; a replaced S can be replaced again.
+ *   SLAMIT_REPLACE_ADD_OBS  a = the point, b = the keyframe, with idx, octave, weight: SLAMIT_EDIT_ADD_OBS | SLAMIT_EDIT_MATCH.
+ * kf_mp[k][idx] after the call is the value of the write with the largest list index.  The observation table is written OUT OF PLACE
+ * as for the map edits (a new row: the old order, moved-out entries gone, received ones appended as received); mp_bad, mp_nobs,
+ * mp_found, mp_visible, mp_replaced and kf_mp are rewritten IN PLACE.  Map::EraseMapPoint of the replaced points and
+ * ComputeDistinctiveDescriptors of the receivers (slamit_update_points_batch_dev over `touched`) are the caller's next steps.
+ * ALL-OR-NOTHING: points are coupled, so each ceiling refuses the whole call; then nothing is written but the status (and n_obs_out
+ * with TABLE_OVERFLOW).  Replace never creates an observation, so obs_cap_out = the old table + the number of ADD_OBS ops always
+ * suffices.  Status bits of the call, the first overflow that holds being the one reported, and ceilings: */
+#define SLAMIT_REPLACE_REPLACE 1
+#define SLAMIT_REPLACE_ADD_OBS 2
+#define SLAMIT_REPLACE_OP_OVERFLOW 1      /* a point is named by more than SLAMIT_REPLACE_MAX_PER_POINT ops */
+#define SLAMIT_REPLACE_OBS_OVERFLOW 2     /* an involved row above SLAMIT_UPKEEP_MAX_OBS on input, or pushed past it */
+#define SLAMIT_REPLACE_TABLE_OVERFLOW 4   /* the new table needs more than obs_cap_out entries: n_obs_out says how many */
+#define SLAMIT_REPLACE_BAD_SLOT 8         /* device form: an op or an observation with a slot outside its table was skipped */
+#define SLAMIT_REPLACE_MAX_OPS 16384      /* ops per list */
+#define SLAMIT_REPLACE_MAX_PER_POINT 64   /* ops naming one point, as either side */
+#define SLAMIT_CHECK_REPLACED_MAX_N 65536 /* entries of one frame's list of slamit_check_replaced */
+
+struct slamit_map_replace {
+    int32_t kind;
+    int32_t a, b;                  /* REPLACE: S and D.  ADD_OBS: the point and the keyframe */
+    int32_t idx;                   /* ADD_OBS: the keypoint index in the keyframe */
+    uint8_t octave, weight;        /* ADD_OBS: what goes beside the new observation; weight is 1 or 2 */
+    uint8_t pad[2];
+};
+typedef struct slamit_map_replace slamit_map_replace;
+
+/* The arrays beside one slamit_map_index that the ops read and write: the very memory the map, covis and point records name.  Host
+ * pointers in the host form, device pointers in the batch record.  Of the map record the call reads n_kf, n_mp, obs_ptr, obs_kf and
+ * kf_mp_ptr. */
+struct slamit_replace_index {
+    const int32_t* obs_idx;        /* beside obs_kf, read-only */
+    const uint8_t* obs_octave;
+    const uint8_t* obs_weight;
+    uint8_t* mp_bad;               /* [n_mp] in / out */
+    int32_t* mp_nobs;              /* [n_mp] in / out */
+    int32_t* mp_found;             /* [n_mp] in / out: mnFound, the memory of slamit_point_index.mp_found */
+    int32_t* mp_visible;           /* [n_mp] in / out: mnVisible */
+    int32_t* mp_replaced;          /* [n_mp] in / out: mpReplaced, -1 for none */
+    int32_t* kf_mp;                /* in / out */
+    int32_t* obs_ptr_out;          /* [n_mp + 1] out */
+    int32_t* obs_kf_out;           /* [obs_cap_out] out, as the next three */
+    int32_t* obs_idx_out;
+    uint8_t* obs_octave_out;
+    uint8_t* obs_weight_out;
+    int32_t obs_cap_out;
+    int32_t reserved;
+};
+typedef struct slamit_replace_index slamit_replace_index;
+
+/* One list over one map (host pointers, synchronous).  moved[n] / erased[n] in / out: the entries op i appended to its target and the
+ * ones it dropped (ADD_OBS: 1 or 0, and 0); touched[n_mp] in / out: the first *n_touched entries are the points that received an
+ * observation, in ascending slot (the layout of slamit_points_batch_rec.d_points / d_n); *n_obs_out in / out; *status out.  Entries
+ * past the counts are left as the caller filled them; with an overflow bit everything but *status (and *n_obs_out for
+ * TABLE_OVERFLOW) is.  A null table, a slot, index, kind or weight outside its range, a CSR pointer array that does not ascend from 0
+ * fails with SLAMIT_ERR_ARG, n above SLAMIT_REPLACE_MAX_OPS with SLAMIT_ERR_CAPACITY, each with a message and before anything is
+ * launched. */
+int slamit_map_replace_apply(int device, const slamit_map_index* map, const slamit_replace_index* index, int32_t n, const slamit_map_replace* ops,
+                             int32_t* moved, int32_t* erased, int32_t* touched, int32_t* n_touched, int32_t* n_obs_out, int32_t* status);
+
+/* One list per map for n_maps maps, everything resident.  `maps` and `index` are HOST arrays of records holding DEVICE pointers; map
+ * m takes the first d_n[m] (clamped to [0, cap]) ops of d_ops[m].  The device cannot be shown its tables first: an op with a point,
+ * keyframe, index or weight outside its range is skipped whole, never dereferenced; an observation whose (k, idx) lies outside kf_mp
+ * is carried along without its kf_mp write; both set SLAMIT_REPLACE_BAD_SLOT in d_status[m].  Asynchronous on `stream`, no
+ * synchronisation, no state; the head of the workspace is cleared on the stream by the call.  One workgroup per map walks the list in
+ * rounds of independent ops: a chain of dependent ops costs a round each.
+ * WORKSPACE, with S = mp_cap + 1, ninv = min(2 cap, mp_cap) and every array rounded up to 16 bytes, per map:
+ *   8 kfmp_cap + 32 + 4 (6 S + 2 (ceil(S / 256) + 1)) + 4 * 7 cap + 4 (1 + 7) ninv + 10 * SLAMIT_UPKEEP_MAX_OBS * ninv bytes
+ * -- the kf_mp words, the status words, six rows over the points, the scan's sums, buckets / predecessors / stamps / counts, and a
+ * working row with its columns per involved point. */
+struct slamit_map_replace_batch_rec {
+    int32_t n_maps, cap, mp_cap, kfmp_cap;
+    const slamit_map_index* maps;      /* HOST [n_maps], device pointers inside; n_maps <= SLAMIT_LOCAL_MAP_MAX_MAPS */
+    const slamit_replace_index* index; /* HOST [n_maps], device pointers inside */
+    const slamit_map_replace* d_ops;   /* [n_maps][cap], cap <= SLAMIT_REPLACE_MAX_OPS */
+    const int32_t* d_n;                /* [n_maps] */
+    int32_t* d_moved;                  /* [n_maps][cap] in / out */
+    int32_t* d_erased;                 /* [n_maps][cap] in / out */
+    int32_t* d_touched;                /* [n_maps][mp_cap] in / out */
+    int32_t* d_n_touched;              /* [n_maps] in / out */
+    int32_t* d_n_obs_out;              /* [n_maps] in / out */
+    int32_t* d_status;                 /* [n_maps] out */
+    void* d_workspace;                 /* slamit_map_replace_workspace(n_maps, cap, mp_cap, kfmp_cap) bytes, 8-byte aligned */
+    size_t workspace_bytes;
+};
+typedef struct slamit_map_replace_batch_rec slamit_map_replace_batch_rec;
+size_t slamit_map_replace_workspace(int n_maps, int cap, int mp_cap, int kfmp_cap);
+int slamit_map_replace_batch_dev(int device, const slamit_map_replace_batch_rec* batch, void* stream);
+
+/* Tracking::CheckReplacedInLastFrame (src/Tracking.cc:959-974), the reader of mp_replaced: every entry p >= 0 of a frame's point list
+ * with mp_replaced[p] >= 0 becomes mp_replaced[p] -- one hop, as the reference follows one.  Host form: frame_mp[n] in / out, *status
+ * out; an entry outside [-1, n_mp) fails with SLAMIT_ERR_ARG, n above SLAMIT_CHECK_REPLACED_MAX_N with SLAMIT_ERR_CAPACITY, before a
+ * launch.  Resident form: frame f lists d_n[f] (clamped to cap) entries over map d_frame_map[f]; an entry outside the table is left
+ * alone and sets SLAMIT_REPLACE_BAD_SLOT in d_status[f] (a map index outside [0, n_maps): the frame is left alone, the same bit).
+ * Asynchronous on `stream`, no state, no workspace. */
+int slamit_check_replaced(int device, int32_t n_mp, const int32_t* mp_replaced, int32_t n, int32_t* frame_mp, int32_t* status);
+struct slamit_check_replaced_batch_rec {
+    int32_t nframes, n_maps, cap, reserved;
+    const int32_t* n_mp;                   /* HOST [n_maps] */
+    const int32_t* const* d_mp_replaced;   /* HOST [n_maps] of device pointers, n_maps <= SLAMIT_LOCAL_MAP_MAX_MAPS */
+    const int32_t* d_frame_map;            /* [nframes] */
+    const int32_t* d_n;                    /* [nframes] */
+    int32_t* d_frame_mp;                   /* [nframes][cap] in / out, cap <= SLAMIT_CHECK_REPLACED_MAX_N */
+    int32_t* d_status;                     /* [nframes] out */
+};
+typedef struct slamit_check_replaced_batch_rec slamit_check_replaced_batch_rec;
+int slamit_check_replaced_batch_dev(int device, const slamit_check_replaced_batch_rec* batch, void* stream);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 
 const char* slamit_last_error(void);

@@ -405,6 +405,35 @@ EDIT_DTYPE = np.dtype([("kind", "<i4"), ("flags", "<i4"), ("mp", "<i4"), ("kf", 
 EDIT_INDEX_COLUMNS = (("obs_idx", np.int32), ("obs_octave", np.uint8), ("obs_weight", np.uint8))
 EDIT_INDEX_INPLACE = (("mp_bad", np.uint8), ("mp_nobs", np.int32), ("mp_ref_kf", np.int32), ("kf_mp", np.int32))
 EDIT_INDEX_OUT = (("obs_kf_out", np.int32), ("obs_idx_out", np.int32), ("obs_octave_out", np.uint8), ("obs_weight_out", np.uint8))
+
+
+class ReplaceIndexRec(C.Structure):   # struct slamit_replace_index
+    _fields_ = [("obs_idx", C.c_void_p), ("obs_octave", C.c_void_p), ("obs_weight", C.c_void_p), ("mp_bad", C.c_void_p), ("mp_nobs", C.c_void_p),
+                ("mp_found", C.c_void_p), ("mp_visible", C.c_void_p), ("mp_replaced", C.c_void_p), ("kf_mp", C.c_void_p), ("obs_ptr_out", C.c_void_p),
+                ("obs_kf_out", C.c_void_p), ("obs_idx_out", C.c_void_p), ("obs_octave_out", C.c_void_p), ("obs_weight_out", C.c_void_p),
+                ("obs_cap_out", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MapReplaceBatchRec(C.Structure):   # struct slamit_map_replace_batch_rec
+    _fields_ = [("n_maps", C.c_int32), ("cap", C.c_int32), ("mp_cap", C.c_int32), ("kfmp_cap", C.c_int32), ("maps", C.POINTER(MapIndexRec)),
+                ("index", C.POINTER(ReplaceIndexRec)), ("d_ops", C.c_void_p), ("d_n", C.c_void_p), ("d_moved", C.c_void_p), ("d_erased", C.c_void_p),
+                ("d_touched", C.c_void_p), ("d_n_touched", C.c_void_p), ("d_n_obs_out", C.c_void_p), ("d_status", C.c_void_p), ("d_workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
+
+
+class CheckReplacedBatchRec(C.Structure):   # struct slamit_check_replaced_batch_rec
+    _fields_ = [("nframes", C.c_int32), ("n_maps", C.c_int32), ("cap", C.c_int32), ("reserved", C.c_int32), ("n_mp", C.POINTER(C.c_int32)),
+                ("d_mp_replaced", C.POINTER(C.c_void_p)), ("d_frame_map", C.c_void_p), ("d_n", C.c_void_p), ("d_frame_mp", C.c_void_p), ("d_status", C.c_void_p)]
+
+
+# SLAMIT_REPLACE_*: the kinds, the status bits, the ceilings; struct slamit_map_replace as a numpy record
+REPLACE_REPLACE, REPLACE_ADD_OBS = 1, 2
+REPLACE_STATUS = {"OP_OVERFLOW": 1, "OBS_OVERFLOW": 2, "TABLE_OVERFLOW": 4, "BAD_SLOT": 8}
+REPLACE_REFUSED = 1 | 2 | 4   # with one of these nothing was written but the status (and n_obs_out for TABLE_OVERFLOW)
+REPLACE_MAX_OPS, REPLACE_MAX_PER_POINT, CHECK_REPLACED_MAX_N = 16384, 64, 65536
+REPLACE_DTYPE = np.dtype([("kind", "<i4"), ("a", "<i4"), ("b", "<i4"), ("idx", "<i4"), ("octave", "u1"), ("weight", "u1"), ("pad", "u1", 2)])
+# slamit_replace_index: the columns read and the table written are the edit index's; the arrays rewritten in place
+REPLACE_INDEX_INPLACE = (("mp_bad", np.uint8), ("mp_nobs", np.int32), ("mp_found", np.int32), ("mp_visible", np.int32), ("mp_replaced", np.int32), ("kf_mp", np.int32))
 DEPTH_TYPES = ("f32", "u16")   # SLAMIT_DEPTH_*: the index is the type
 DEPTH_PLANE_DTYPE = np.dtype([("data", "<u8"), ("pitch", "<u8"), ("width", "<i4"), ("height", "<i4"), ("type", "<i4"), ("factor", "<f4")])   # slamit_depth_plane
 RGBD_STATUS = ("no_depth", "depth", "outside")
@@ -476,7 +505,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_map_edit_apply", "slamit_map_edit_workspace", "slamit_map_edit_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_map_edit_apply", "slamit_map_edit_workspace", "slamit_map_edit_batch_dev", "slamit_map_replace_apply", "slamit_map_replace_workspace", "slamit_map_replace_batch_dev", "slamit_check_replaced", "slamit_check_replaced_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -572,6 +601,12 @@ def lib():
         L.slamit_map_edit_workspace.argtypes = [i32, i32, i32, i32]
         L.slamit_map_edit_workspace.restype = sz
         L.slamit_map_edit_batch_dev.argtypes = [i32, C.POINTER(MapEditBatchRec), vp]
+        L.slamit_map_replace_apply.argtypes = [i32, C.POINTER(MapIndexRec), C.POINTER(ReplaceIndexRec), i32, vp, vp, vp, vp, vp, vp, vp]
+        L.slamit_map_replace_workspace.argtypes = [i32, i32, i32, i32]
+        L.slamit_map_replace_workspace.restype = sz
+        L.slamit_map_replace_batch_dev.argtypes = [i32, C.POINTER(MapReplaceBatchRec), vp]
+        L.slamit_check_replaced.argtypes = [i32, i32, vp, i32, vp, vp]
+        L.slamit_check_replaced_batch_dev.argtypes = [i32, C.POINTER(CheckReplacedBatchRec), vp]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_bow_search_stereo.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), C.POINTER(BowStereo), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
@@ -2811,6 +2846,7 @@ class EditIndex:
             points.t["mp_nobs"] = self.t["mp_nobs"]
             points.rec.mp_nobs = self.t["mp_nobs"].data_ptr()
         self.rec = EditIndexRec()
+        self.followers = []   # called after every repointing: a ReplaceIndex over the same buffer sets
         self._point()
 
     def _point(self):
@@ -2831,6 +2867,8 @@ class EditIndex:
         for key in ("obs_kf", "obs_idx", "obs_octave", "obs_weight"):
             setattr(self.rec, key + "_out", nxt[key].data_ptr())
         self.rec.obs_cap_out = self.obs_cap
+        for follow in self.followers:
+            follow()
 
     def swap(self):
         """The table the last call wrote becomes the one every record reads; no copy, no synchronisation."""
@@ -2861,3 +2899,154 @@ def map_edit_batch_dev(maps, edit, t, device=0, stream=None):
     rec = MapEditBatchRec(b, cap, mp_cap, int(t["kfmp_cap"]), M, X, t["edits"].data_ptr(), t["n"].data_ptr(), t["status_mp"].data_ptr(), t["touched"].data_ptr(),
                           t["n_touched"].data_ptr(), t["n_obs_out"].data_ptr(), t["status"].data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
     _check(lib().slamit_map_edit_batch_dev(device, C.byref(rec), stream), "slamit_map_edit_batch_dev")
+
+
+def replace_records(ops):
+    """Ops as an array of slamit_map_replace: a REPLACE_DTYPE array as it is, else rows (kind, a, b, idx, octave, weight)."""
+    if isinstance(ops, np.ndarray) and ops.dtype == REPLACE_DTYPE:
+        return np.ascontiguousarray(ops).reshape(-1)
+    rows = list(ops)
+    out = np.zeros(len(rows), REPLACE_DTYPE)
+    for i, r in enumerate(rows):
+        out[i] = tuple(int(v) for v in r) + ((0, 0),)
+    return out
+
+
+def map_replace(tables, index, ops, obs_cap_out=None, fill=None, device=0):
+    """MapPoint::Replace (MapPoint.cc:183-221) with Fuse's AddObservation + AddMapPoint for a list of ops applied as if sequentially, over
+    a map's tables (slamit_map_index: n_kf, n_mp, obs_ptr, obs_kf, kf_mp_ptr, kf_mp, mp_bad) and the columns beside them (dict: obs_idx,
+    obs_octave, obs_weight; mp_nobs, mp_found, mp_visible, mp_replaced; mp_bad / kf_mp where they are not taken from `tables`).  ops:
+    replace_records().  The caller's arrays are not modified.  obs_cap_out: the room of the new table (default: the old table plus one
+    entry per ADD_OBS op, which always suffices).  fill: optional dict of prefilled outputs (obs_ptr_out, obs_kf_out, obs_idx_out,
+    obs_octave_out, obs_weight_out, moved, erased, touched, n_touched, n_obs_out), copied.  -> dict: obs_ptr, obs_kf, mp_bad, kf_mp (what
+    MapIndex / _map_index_host take in place of the old ones), obs_idx, obs_octave, obs_weight, mp_nobs, mp_found, mp_visible,
+    mp_replaced, moved, erased (per op), touched (the first n_touched of it), n_touched, n_obs_out, status, and `raw`: the output arrays
+    in full.  With a bit of REPLACE_REFUSED in status the tables returned are the old ones."""
+    rec, keep = _map_index_host(tables)
+    n_mp = max(rec.n_mp, 0)
+    ed = replace_records(ops)
+    src = dict(index)
+    for key in ("mp_bad", "kf_mp"):
+        src.setdefault(key, tables.get(key))
+    n_obs = int(np.asarray(tables["obs_ptr"]).reshape(-1)[-1]) if tables.get("obs_ptr") is not None and len(np.asarray(tables["obs_ptr"]).reshape(-1)) else 0
+    cap = n_obs + int(np.count_nonzero(ed["kind"] == REPLACE_ADD_OBS)) if obs_cap_out is None else int(obs_cap_out)
+    fill = fill or {}
+    xrec, xkeep = ReplaceIndexRec(), {}
+    for key, dt in EDIT_INDEX_COLUMNS:
+        if src.get(key) is not None:
+            xkeep[key] = np.ascontiguousarray(src[key], dt).reshape(-1)
+            setattr(xrec, key, xkeep[key].ctypes.data)
+    for key, dt in REPLACE_INDEX_INPLACE:
+        if src.get(key) is not None:
+            xkeep[key] = np.array(src[key], dt).reshape(-1)
+            setattr(xrec, key, xkeep[key].ctypes.data)
+    for key, dt, count in (("obs_ptr_out", np.int32, n_mp + 1),) + tuple((k, d, max(cap, 0)) for k, d in EDIT_INDEX_OUT):
+        xkeep[key] = np.zeros(count, dt) if fill.get(key) is None else np.array(fill[key], dt).reshape(-1)
+        if len(xkeep[key]) != count:
+            raise SlamitError("map_replace: fill[%s] does not hold %d entries" % (key, count))
+        setattr(xrec, key, xkeep[key].ctypes.data if count else None)
+    xrec.obs_cap_out = cap
+    per_op = {key: np.zeros(len(ed), np.int32) if fill.get(key) is None else np.array(fill[key], np.int32).reshape(-1) for key in ("moved", "erased")}
+    tch = np.full(n_mp, -1, np.int32) if fill.get("touched") is None else np.array(fill["touched"], np.int32).reshape(-1)
+    if len(tch) != n_mp or any(len(v) != len(ed) for v in per_op.values()):
+        raise SlamitError("map_replace: moved and erased hold one entry per op, touched n_mp entries")
+    nt, no, st = np.array([fill.get("n_touched", 0)], np.int32), np.array([fill.get("n_obs_out", 0)], np.int32), np.zeros(1, np.int32)
+    some = lambda a: _np_ptr(a) if len(a) else None
+    _check(lib().slamit_map_replace_apply(device, C.byref(rec), C.byref(xrec), len(ed), some(ed), some(per_op["moved"]), some(per_op["erased"]), some(tch),
+                                          _np_ptr(nt), _np_ptr(no), _np_ptr(st)), "slamit_map_replace_apply")
+    del keep
+    status, need = int(st[0]), int(no[0])
+    out = {"status": status, "n_obs_out": need, "n_touched": int(nt[0]), "moved": per_op["moved"], "erased": per_op["erased"],
+           "raw": dict(xkeep, touched=tch, n_touched=int(nt[0]), n_obs_out=need, **per_op)}
+    if status & REPLACE_REFUSED:
+        out.update(obs_ptr=np.array(tables["obs_ptr"], np.int32).reshape(-1), obs_kf=np.array(tables["obs_kf"], np.int32).reshape(-1), touched=tch[:0])
+        for key, _ in EDIT_INDEX_COLUMNS:
+            out[key] = xkeep[key].copy()
+    else:
+        out.update(obs_ptr=xkeep["obs_ptr_out"], obs_kf=xkeep["obs_kf_out"][:need], touched=tch[:int(nt[0])])
+        for key, _ in EDIT_INDEX_COLUMNS:
+            out[key] = xkeep[key + "_out"][:need]
+    for key, _ in REPLACE_INDEX_INPLACE:
+        out[key] = xkeep.get(key)
+    return out
+
+
+class ReplaceIndex:
+    """The arrays map_replace_batch_dev reads and writes beside a MapIndex (the resident form's slamit_replace_index).  ReplaceIndex(
+    edit_index, cols) SHARES the EditIndex's two buffer sets of the observation table and its in-place tensors, so one swap() of the
+    EditIndex repoints this record with every other.  mp_found / mp_visible are the PointIndex's tensors where the EditIndex has one,
+    else uploaded from cols; mp_replaced is uploaded from cols (default: -1 everywhere) and kept in .t for check_replaced_batch_dev."""
+
+    def __init__(self, edit_index, cols=None):
+        import torch
+
+        cols = cols or {}
+        self.edit_index, self.device = edit_index, edit_index.device
+        dev = "cuda:%d" % self.device
+        n_mp = max(int(edit_index.map_index.rec.n_mp), 0)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32).reshape(-1) if np.size(a) else np.zeros(1, np.int32)).to(dev)
+        pts = edit_index.points
+        self.t = {"mp_found": pts.t["mp_found"] if pts is not None else up(cols["mp_found"]),
+                  "mp_visible": pts.t["mp_visible"] if pts is not None else up(cols["mp_visible"]),
+                  "mp_replaced": up(cols["mp_replaced"] if cols.get("mp_replaced") is not None else np.full(max(n_mp, 1), -1, np.int32))}
+        self.rec = ReplaceIndexRec()
+        edit_index.followers.append(self._point)
+        self._point()
+
+    def _point(self):
+        e = self.edit_index.rec
+        for key in ("obs_idx", "obs_octave", "obs_weight", "mp_bad", "mp_nobs", "kf_mp", "obs_ptr_out", "obs_kf_out", "obs_idx_out", "obs_octave_out", "obs_weight_out",
+                    "obs_cap_out"):
+            setattr(self.rec, key, getattr(e, key))
+        for key in ("mp_found", "mp_visible", "mp_replaced"):
+            setattr(self.rec, key, self.t[key].data_ptr())
+
+
+def map_replace_workspace(n_maps, cap, mp_cap, kfmp_cap):
+    return int(lib().slamit_map_replace_workspace(n_maps, cap, mp_cap, kfmp_cap))
+
+
+def map_replace_batch_dev(maps, index, t, device=0, stream=None):
+    """One op list per map, resident.  maps / index: lists of MapIndex / ReplaceIndex; t: dict of torch CUDA tensors ops (B, cap, 20) u8 (the
+    bytes of REPLACE_DTYPE records), n (B) i32, moved (B, cap) / erased (B, cap) / touched (B, mp_cap) i32 in / out, n_touched (B),
+    n_obs_out (B), status (B) i32, workspace: uint8, map_replace_workspace(B, cap, mp_cap, kfmp_cap) bytes with kfmp_cap = t["kfmp_cap"]
+    >= every map's number of kf_mp entries.  The new tables are written into each EditIndex's other buffer set: where status has no bit of
+    REPLACE_REFUSED, call swap() on the EditIndex before the next reader is ENQUEUED.  Asynchronous on `stream`."""
+    b, cap = t["ops"].shape[0], t["ops"].shape[1]
+    mp_cap = t["touched"].shape[1]
+    if len(maps) != b or len(index) != b:
+        raise SlamitError("map_replace_batch_dev: one MapIndex, one ReplaceIndex and one list per map")
+    _rows(t, "map_replace_batch_dev", (("ops", cap * REPLACE_DTYPE.itemsize), ("moved", cap), ("erased", cap), ("touched", mp_cap), ("n", 1), ("n_touched", 1),
+                                       ("n_obs_out", 1), ("status", 1)), b)
+    M, X = (MapIndexRec * max(b, 1))(), (ReplaceIndexRec * max(b, 1))()
+    for i, (mi, ri) in enumerate(zip(maps, index)):
+        M[i], X[i] = mi.rec, ri.rec
+    ws = t["workspace"]
+    rec = MapReplaceBatchRec(b, cap, mp_cap, int(t["kfmp_cap"]), M, X, t["ops"].data_ptr(), t["n"].data_ptr(), t["moved"].data_ptr(), t["erased"].data_ptr(),
+                             t["touched"].data_ptr(), t["n_touched"].data_ptr(), t["n_obs_out"].data_ptr(), t["status"].data_ptr(), ws.data_ptr(),
+                             ws.numel() * ws.element_size())
+    _check(lib().slamit_map_replace_batch_dev(device, C.byref(rec), stream), "slamit_map_replace_batch_dev")
+
+
+def check_replaced(mp_replaced, frame_mp, device=0):
+    """Tracking::CheckReplacedInLastFrame (Tracking.cc:959-974): every entry p >= 0 of a frame's point list with mp_replaced[p] >= 0
+    becomes mp_replaced[p], one hop.  -> (the list, status).  The caller's arrays are not modified."""
+    rep = np.ascontiguousarray(mp_replaced, np.int32).reshape(-1)
+    lst = np.array(frame_mp, np.int32).reshape(-1)
+    st = np.zeros(1, np.int32)
+    _check(lib().slamit_check_replaced(device, len(rep), _np_ptr(rep) if len(rep) else None, len(lst), _np_ptr(lst) if len(lst) else None, _np_ptr(st)),
+           "slamit_check_replaced")
+    return lst, int(st[0])
+
+
+def check_replaced_batch_dev(replaced, t, n_mp=None, device=0, stream=None):
+    """The same for a batch of frames, resident.  replaced: one mp_replaced tensor per map (ReplaceIndex.t["mp_replaced"]); n_mp: the
+    maps' point counts (default: the tensors' lengths); t: dict of torch CUDA tensors frame_map (F) i32, n (F) i32, frame_mp (F, cap) i32
+    in / out, status (F) i32.  Asynchronous on `stream`."""
+    f, cap = t["frame_mp"].shape
+    _rows(t, "check_replaced_batch_dev", (("frame_mp", cap), ("frame_map", 1), ("n", 1), ("status", 1)), f)
+    nm = len(replaced)
+    counts = (C.c_int32 * max(nm, 1))(*[int(r.numel()) if n_mp is None else int(n_mp[i]) for i, r in enumerate(replaced)])
+    ptrs = (C.c_void_p * max(nm, 1))(*[r.data_ptr() for r in replaced])
+    rec = CheckReplacedBatchRec(f, nm, cap, 0, counts, ptrs, t["frame_map"].data_ptr(), t["n"].data_ptr(), t["frame_mp"].data_ptr(), t["status"].data_ptr())
+    _check(lib().slamit_check_replaced_batch_dev(device, C.byref(rec), stream), "slamit_check_replaced_batch_dev")

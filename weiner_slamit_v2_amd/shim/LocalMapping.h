@@ -31,7 +31,8 @@
 // written into the objects; for parity rather than speed.  UpdateMapPoints (MapPoint::UpdateNormalAndDepth and
 // ::ComputeDistinctiveDescriptors for a list of points, src/MapPoint.cc:248-377) and MapPointCulling (:184-219) are built the same way
 // over slamit_update_points and slamit_map_point_culling, ApplyMapEdits (MapPoint::AddObservation, ::EraseObservation
-// and ::SetBadFlag for a list of edits, src/MapPoint.cc:104-174) over slamit_map_edit_apply (section 26).
+// and ::SetBadFlag for a list of edits, src/MapPoint.cc:104-174) over slamit_map_edit_apply (section 26), ReplaceMapPoints (MapPoint::Replace for a fuse list, :183-221) over
+// slamit_map_replace_apply (section 27).
 #ifndef SLAMIT_SHIM_LOCALMAPPING_H
 #define SLAMIT_SHIM_LOCALMAPPING_H
 
@@ -388,6 +389,130 @@ public:
                 if (kf_mp_new[e] != kf_mp[e]) kfs[k]->mvpMapPoints[e - kf_mp_ptr[k]] = kf_mp_new[e] < 0 ? (MapPointT*)0 : mps[kf_mp_new[e]];
         if (any & (SLAMIT_EDIT_EDIT_OVERFLOW | SLAMIT_EDIT_OBS_OVERFLOW))
             shim::refuse<LocalMapping>("ApplyMapEdits: a point above SLAMIT_EDIT_MAX_PER_POINT edits or SLAMIT_UPKEEP_MAX_OBS observers was left as it was", SLAMIT_ERR_CAPACITY);
+        return n;
+    }
+
+    // One op of ReplaceMapPoints over the caller's objects: kind SLAMIT_REPLACE_REPLACE (pMP->Replace(pRep)) or SLAMIT_REPLACE_ADD_OBS
+    // (pMP->AddObservation(pKF, idx) and pKF->AddMapPoint(pMP, idx), the other branch of ORBmatcher::Fuse's tail).
+    template <class MapPointT, class KeyFrameT>
+    struct ReplaceOp {
+        int kind;
+        MapPointT* pMP;
+        MapPointT* pRep;   // REPLACE
+        KeyFrameT* pKF;    // ADD_OBS
+        size_t idx;        // ADD_OBS
+    };
+
+    // MapPoint::Replace (MapPoint.cc:183-221) for a LIST of ops as ORBmatcher::Fuse's tail, LoopClosing::SearchAndFuse and ::CorrectLoop
+    // issue them, applied as if one after the other in ONE slamit_map_replace_apply call.  Writes back mObservations, nObs, mbBad,
+    // mpReplaced, mnFound and mnVisible of the points the ops name and the changed entries of mvpMapPoints of the keyframes around
+    // them, and calls pMap->EraseMapPoint on every replaced point (:220).  Returns the number of ops.  ComputeDistinctiveDescriptors of
+    // the receivers (:218) is UpdateMapPoints' work and stays the caller's next call.  Keyframes -- the ones the ops name and the
+    // observers of the named points -- are numbered by std::less<KeyFrameT*>, so "ascending slot" is the std::map order of this run.
+    // The ceilings are all-or-nothing: a point named by more than SLAMIT_REPLACE_MAX_PER_POINT ops or a row past
+    // SLAMIT_UPKEEP_MAX_OBS observers leaves EVERYTHING as it was, LastStatus() is SLAMIT_ERR_CAPACITY with a line on stderr.
+    // IT SAVES NOTHING THROUGH THE SHIM: building the tables walks the observations and the keyframes' rows that Replace touches a few
+    // entries of.  It is for parity and for integrations that want one code path; the gain is slamit_map_replace_batch_dev with the
+    // tables kept in HBM.  Members used (a friend declaration in the reference's classes): MapPoint mObservations, nObs, mbBad,
+    // mpReplaced, mnFound, mnVisible; KeyFrame mvpMapPoints, mvuRight, mvKeysUn; Map EraseMapPoint().
+    template <class MapPointT, class KeyFrameT, class MapT>
+    static int ReplaceMapPoints(const std::vector<ReplaceOp<MapPointT, KeyFrameT> >& ops, MapT* pMap, int device = 0) {
+        typedef typename std::map<KeyFrameT*, size_t>::const_iterator ObsIt;
+        status() = SLAMIT_OK;
+        const int n = (int)ops.size();
+        if (n == 0) return 0;
+        if (n > SLAMIT_REPLACE_MAX_OPS) return shim::refuse<LocalMapping>("ReplaceMapPoints: more than SLAMIT_REPLACE_MAX_OPS ops", SLAMIT_ERR_CAPACITY);
+        std::vector<MapPointT*> mps;
+        std::map<MapPointT*, int32_t> mpSlot;
+        std::set<KeyFrameT*> all;
+        for (int i = 0; i < n; ++i) {
+            const bool rep = ops[i].kind == SLAMIT_REPLACE_REPLACE;
+            if (!rep && ops[i].kind != SLAMIT_REPLACE_ADD_OBS) return shim::refuse<LocalMapping>("ReplaceMapPoints: an op's kind outside 1..2");
+            if (!ops[i].pMP || (rep ? !ops[i].pRep : !ops[i].pKF)) return shim::refuse<LocalMapping>("ReplaceMapPoints: an op without its point, replacement or keyframe");
+            slotOf(mpSlot, mps, ops[i].pMP);
+            if (rep) slotOf(mpSlot, mps, ops[i].pRep); else all.insert(ops[i].pKF);
+        }
+        const int n_named = (int)mps.size();
+        for (int p = 0; p < n_named; ++p)
+            for (ObsIt it = mps[p]->mObservations.begin(); it != mps[p]->mObservations.end(); ++it) all.insert(it->first);
+        const std::vector<KeyFrameT*> kfs(all.begin(), all.end());   // a std::set orders by std::less
+        std::map<KeyFrameT*, int32_t> kfSlot;
+        for (size_t k = 0; k < kfs.size(); ++k) kfSlot[kfs[k]] = (int32_t)k;
+        const int n_kf = (int)kfs.size();
+        if (n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return shim::refuse<LocalMapping>("ReplaceMapPoints: more than SLAMIT_LOCAL_MAP_MAX_KF keyframes around the points", SLAMIT_ERR_CAPACITY);
+        std::vector<int32_t> kf_mp_ptr(n_kf + 1, 0), kf_mp;
+        for (int k = 0; k < n_kf; ++k) {                                       // every stored point gets a slot: a changed entry is found by comparing
+            for (size_t i = 0; i < kfs[k]->mvpMapPoints.size(); ++i) kf_mp.push_back(kfs[k]->mvpMapPoints[i] ? slotOf(mpSlot, mps, kfs[k]->mvpMapPoints[i]) : -1);
+            kf_mp_ptr[k + 1] = (int32_t)kf_mp.size();
+        }
+        std::vector<int32_t> rep_named(n_named, -1);
+        for (int p = 0; p < n_named; ++p)
+            if (mps[p]->mpReplaced) rep_named[p] = slotOf(mpSlot, mps, mps[p]->mpReplaced);
+        const int n_mp = (int)mps.size();
+        std::vector<int32_t> obs_ptr(n_mp + 1, 0), obs_kf, obs_idx, mp_nobs(n_mp, 0), mp_found(n_mp, 0), mp_visible(n_mp, 0), mp_replaced(n_mp, -1);
+        std::vector<uint8_t> obs_octave, obs_weight, mp_bad(n_mp, 0);
+        for (int p = 0; p < n_mp; ++p) {
+            if (p < n_named) {
+                mp_bad[p] = mps[p]->mbBad ? 1 : 0; mp_nobs[p] = mps[p]->nObs; mp_found[p] = mps[p]->mnFound; mp_visible[p] = mps[p]->mnVisible; mp_replaced[p] = rep_named[p];
+                for (ObsIt it = mps[p]->mObservations.begin(); it != mps[p]->mObservations.end(); ++it) {
+                    KeyFrameT* kf = it->first;
+                    obs_kf.push_back(kfSlot[kf]); obs_idx.push_back((int32_t)it->second);
+                    obs_octave.push_back(it->second < kf->mvKeysUn.size() ? (uint8_t)kf->mvKeysUn[it->second].octave : 0);
+                    obs_weight.push_back(it->second < kf->mvuRight.size() && kf->mvuRight[it->second] >= 0 ? 2 : 1);
+                }
+            }
+            obs_ptr[p + 1] = (int32_t)obs_kf.size();
+        }
+        std::vector<slamit_map_replace> list(n);
+        size_t adds = 0;
+        for (int i = 0; i < n; ++i) {
+            slamit_map_replace& e = list[i];
+            memset(&e, 0, sizeof(e));
+            e.kind = ops[i].kind; e.a = mpSlot[ops[i].pMP];
+            if (e.kind == SLAMIT_REPLACE_REPLACE) { e.b = mpSlot[ops[i].pRep]; continue; }
+            KeyFrameT* kf = ops[i].pKF;
+            e.b = kfSlot[kf]; e.idx = (int32_t)ops[i].idx;
+            e.octave = ops[i].idx < kf->mvKeysUn.size() ? (uint8_t)kf->mvKeysUn[ops[i].idx].octave : 0;
+            e.weight = ops[i].idx < kf->mvuRight.size() && kf->mvuRight[ops[i].idx] >= 0 ? 2 : 1;
+            ++adds;
+        }
+        const size_t cap = obs_kf.size() + adds;                               // Replace never creates an observation
+        std::vector<int32_t> optr(n_mp + 1, 0), okf(cap + 1, 0), oidx(cap + 1, 0), moved(n, 0), erased(n, 0), touched(n_mp, -1), kf_mp_new(kf_mp);
+        std::vector<uint8_t> ooct(cap + 1, 0), owgt(cap + 1, 0), bad_new(mp_bad);
+        std::vector<int32_t> nobs_new(mp_nobs), found_new(mp_found), visible_new(mp_visible), rep_new(mp_replaced);
+        int32_t none32 = -1;
+        uint8_t none8 = 0;
+        slamit_map_index M;
+        memset(&M, 0, sizeof(M));
+        M.n_kf = n_kf; M.n_mp = n_mp; M.obs_ptr = obs_ptr.data(); M.obs_kf = obs_kf.empty() ? &none32 : obs_kf.data(); M.kf_mp_ptr = kf_mp_ptr.data();
+        slamit_replace_index X;
+        memset(&X, 0, sizeof(X));
+        X.obs_idx = obs_idx.empty() ? &none32 : obs_idx.data(); X.obs_octave = obs_octave.empty() ? &none8 : obs_octave.data();
+        X.obs_weight = obs_weight.empty() ? &none8 : obs_weight.data();
+        X.mp_bad = bad_new.data(); X.mp_nobs = nobs_new.data(); X.mp_found = found_new.data(); X.mp_visible = visible_new.data(); X.mp_replaced = rep_new.data();
+        X.kf_mp = kf_mp_new.empty() ? &none32 : kf_mp_new.data();
+        X.obs_ptr_out = optr.data(); X.obs_kf_out = okf.data(); X.obs_idx_out = oidx.data(); X.obs_octave_out = ooct.data(); X.obs_weight_out = owgt.data();
+        X.obs_cap_out = (int32_t)cap;
+        int32_t n_touched = 0, n_obs_out = 0, st = 0;
+        const int rc = slamit_map_replace_apply(device, &M, &X, n, list.data(), moved.data(), erased.data(), touched.data(), &n_touched, &n_obs_out, &st);
+        if (rc != SLAMIT_OK) return shim::report<LocalMapping>("ReplaceMapPoints: slamit_map_replace_apply", rc);
+        if (st & (SLAMIT_REPLACE_OP_OVERFLOW | SLAMIT_REPLACE_OBS_OVERFLOW))
+            return shim::refuse<LocalMapping>("ReplaceMapPoints: a point named by more than SLAMIT_REPLACE_MAX_PER_POINT ops or a row past SLAMIT_UPKEEP_MAX_OBS observers: nothing was changed",
+                                              SLAMIT_ERR_CAPACITY);
+        if (st != 0) return shim::refuse<LocalMapping>("ReplaceMapPoints: slamit_map_replace_apply reported a status on tables built here", SLAMIT_ERR_STATE);
+        for (int p = 0; p < n_named; ++p) {
+            MapPointT* pMP = mps[p];
+            pMP->mObservations.clear();
+            for (int o = optr[p]; o < optr[p + 1]; ++o) pMP->mObservations[kfs[okf[o]]] = (size_t)oidx[o];
+            pMP->nObs = nobs_new[p]; pMP->mnFound = found_new[p]; pMP->mnVisible = visible_new[p];
+            pMP->mbBad = bad_new[p] != 0;
+            if (rep_new[p] != mp_replaced[p]) pMP->mpReplaced = mps[rep_new[p]];
+        }
+        for (int k = 0; k < n_kf; ++k)
+            for (int e = kf_mp_ptr[k]; e < kf_mp_ptr[k + 1]; ++e)
+                if (kf_mp_new[e] != kf_mp[e]) kfs[k]->mvpMapPoints[e - kf_mp_ptr[k]] = kf_mp_new[e] < 0 ? (MapPointT*)0 : mps[kf_mp_new[e]];
+        for (int i = 0; i < n; ++i)
+            if (ops[i].kind == SLAMIT_REPLACE_REPLACE && ops[i].pMP != ops[i].pRep) pMap->EraseMapPoint(ops[i].pMP);   // MapPoint.cc:220
         return n;
     }
 
