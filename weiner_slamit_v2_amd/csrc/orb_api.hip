@@ -43,8 +43,8 @@ void orbk_octree(hipStream_t st, const OrbLevel* levels, int nlevels, const unsi
 void orbk_ic_angle(hipStream_t st, const OrbLevel* levels, int nlevels, const uint8_t* img0, size_t img0_stride,
                    size_t img0_frame, const uint8_t* pyr, OrbLevelKp* lkp, size_t kp_frame_stride,
                    const int* kp_count, int max_kp, int nframes);
-void orbk_blur_stream(hipStream_t st, const OrbLevel* levels, const uint32_t* d_tiles, int ntiles, const uint8_t* img0,
-                      size_t img0_stride, size_t img0_frame, const uint8_t* pyr, uint8_t* blur, int nframes, bool edge);
+void orbk_blur_stream(hipStream_t st, const OrbLevel* levels, const uint32_t* d_inner, int n_inner, const uint32_t* d_edge, int n_edge,
+                      const uint8_t* img0, size_t img0_stride, size_t img0_frame, const uint8_t* pyr, uint8_t* blur, int nframes);
 void orbk_blur(hipStream_t st, const OrbLevel* levels, const uint32_t* d_tiles, int total_tiles, const uint8_t* img0,
                size_t img0_stride, size_t img0_frame, const uint8_t* pyr, uint8_t* blur, int nframes);
 void orbk_describe(hipStream_t st, const OrbLevel* levels, int nlevels, const uint8_t* blur,
@@ -252,15 +252,15 @@ int slamit_orb_extract_batch_dev(slamit_orb* h, const uint8_t* d_gray, size_t st
     // follows a failed one (or the first) clears them itself.
     if (!h->counters_clean) HIP_TRY(hipMemsetAsync(h->d_counts, 0, sizeof(int) * (size_t)h->p.max_batch * nl * ORB_CC_PAD, st));
     h->counters_clean = false;
-    // the blur of levels [l0, l1): every strip streams down its columns (blur_stream_kernel; the strips at the left / right edge
-    // in their own launch); when the caller's level-0 plane is not 4-byte aligned everything takes the tile kernel
+    // the blur of levels [l0, l1): every strip streams down its columns (blur_stream_kernel: one launch for the strips inside the
+    // level and those at its left / right edge); when the caller's level-0 plane is not 4-byte aligned everything takes the tile kernel
     const bool blur_src_aligned = ((((uintptr_t)d_gray) | stride | frame_stride) & 3) == 0;
     auto launch_blur = [&](hipStream_t bs, int l0, int l1) {
         auto strips = [&](const OrbStrips& S) { return dtab<uint32_t>(h, S.off) + 4 * (size_t)S.base[l0]; };
         auto nstrips = [&](const OrbStrips& S) { return S.base[l1] - S.base[l0]; };
         if (h->blur_stream_on && blur_src_aligned) {
-            orbk_blur_stream(bs, h->d_levels, strips(P.blur_str), nstrips(P.blur_str), d_gray, stride, frame_stride, h->d_pyr, h->d_blur, nframes, false);
-            orbk_blur_stream(bs, h->d_levels, strips(P.blur_edge), nstrips(P.blur_edge), d_gray, stride, frame_stride, h->d_pyr, h->d_blur, nframes, true);
+            orbk_blur_stream(bs, h->d_levels, strips(P.blur_str), nstrips(P.blur_str), strips(P.blur_edge), nstrips(P.blur_edge), d_gray, stride, frame_stride,
+                             h->d_pyr, h->d_blur, nframes);
         } else {
             orbk_blur(bs, h->d_levels, strips(P.blur_all), nstrips(P.blur_all), d_gray, stride, frame_stride, h->d_pyr, h->d_blur, nframes);
         }

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 
+#include "blur_window.h"
 #include "orb_types.h"
 #include "slamit_math.h"
 #include "wave_ops.h"
@@ -1705,17 +1706,15 @@ __global__ __launch_bounds__(256) void blur_all_kernel(
 // (16 registers), and every new pair completes TWO output rows (y = 2p - 3 and 2p - 2 for the pair of rows 2p, 2p + 1,
 // with the two tap patterns of v_dot2_u32_u16 above).  No LDS, no barrier, no halo rows staged twice: ~0.2 instructions
 // per pixel and wave against 0.37 (0.66 with the byte path) of the tile form.  Rows reflect by index (REFLECT_101).
-// A workgroup of 256 threads takes 16 strips.  The strips at the left / right image edge take the EDGE instance (their own launch):
-// the same walk with each window dword built from two aligned dwords (blur_col), and no thread for columns past the image.
-template <bool EDGE>   // EDGE: strips that touch the left / right image edge -- each of the three window dwords is a v_perm of two aligned dwords (blur_col)
-__global__ __launch_bounds__(256) void blur_stream_kernel(
-    const OrbLevel* __restrict__ levels, const uint4* __restrict__ tiles,
+// A workgroup of 256 threads takes 16 strips.  The strips at the left / right image edge take the EDGE instance of the walk: the
+// same walk, the same ONE 12-byte load per row, at an offset shifted by 4 where the window would leave the row, and the window
+// built from the three loaded dwords with five v_perm whose selectors a lane works out once (blur_window.h: REFLECT_101 of
+// columns -4 .. -1 and w .. w + 2); no thread for columns past the image.
+template <bool EDGE>
+__device__ __forceinline__ void blur_stream_walk(
+    const OrbLevel* __restrict__ levels, const uint4 tt, const int frame,
     const uint8_t* __restrict__ img0, size_t img0_stride, size_t img0_frame,
-    const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur, unsigned ntiles) {
-    const unsigned tile = blockIdx.x * 16u + (threadIdx.x >> 4);
-    if (tile >= ntiles) return;
-    const int frame = blockIdx.y;
-    const uint4 tt = tiles[tile];
+    const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur) {
     const int level = (int)tt.x, by0 = (int)tt.z;
     const int x0 = (int)tt.y + 4 * (int)(threadIdx.x & 15);
     const OrbLevel& L = levels[level];
@@ -1725,10 +1724,10 @@ __global__ __launch_bounds__(256) void blur_stream_kernel(
     if (level == 0) { S = img0 + (size_t)frame * img0_frame; ss = (unsigned)img0_stride; }
     else { S = pyr + L.plane_off + (size_t)frame * L.plane_bytes; ss = (unsigned)L.stride; }
     if (EDGE && x0 >= L.w) return;   // (a strip at the right edge is rarely 64 columns wide)
-    BlurCol bc[3];
+    BlurWindow bw;
     if (EDGE) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) bc[k] = blur_col(x0 - 4 + 4 * k, L.w, ss);
+        bw = blur_window(x0, L.w, (int)ss);   // one 12-byte load per row here too, shifted by 4 where the window leaves the row (blur_window.h)
+        S += bw.lb;
     } else S += x0 - 4;
     uint8_t* D = blur + L.blur_off + (size_t)frame * L.blur_bytes + x0;
     const unsigned ds = (unsigned)L.stride;
@@ -1738,15 +1737,20 @@ __global__ __launch_bounds__(256) void blur_stream_kernel(
     const int ylast = min(by0 + ORB_BLUR_STRIP_H, h) - 1;
     const int p0 = (by0 - 3) >> 1, p1 = (ylast + 3) >> 1;   // pairs of rows (2p, 2p + 1); arithmetic shift: by0 - 3 may be negative
     typedef unsigned blur_u3 __attribute__((ext_vector_type(3)));
+    // (pointers in the global address space: the steady loop's running pointers pass through an asm statement, after which the
+    // compiler no longer knows where a generic pointer points and emits flat_ loads and stores)
+    typedef __attribute__((address_space(1))) const blur_u3 blur_gsrc;
+    typedef __attribute__((address_space(1))) uint32_t blur_gdst;
     auto fetch_row = [&](const uint8_t* R) -> blur_u3 {   // the 12-byte window of the row that starts at R
+        const blur_u3 l = *(blur_gsrc*)R;
         if (EDGE) {
+            uint32_t win[3];
+            blur_window_apply(bw, l.x, l.y, l.z, win);   // five v_perm
             blur_u3 v;
-            v.x = __builtin_amdgcn_perm(*reinterpret_cast<const uint32_t*>(R + bc[0].a1), *reinterpret_cast<const uint32_t*>(R + bc[0].a0), bc[0].sel);
-            v.y = __builtin_amdgcn_perm(*reinterpret_cast<const uint32_t*>(R + bc[1].a1), *reinterpret_cast<const uint32_t*>(R + bc[1].a0), bc[1].sel);
-            v.z = __builtin_amdgcn_perm(*reinterpret_cast<const uint32_t*>(R + bc[2].a1), *reinterpret_cast<const uint32_t*>(R + bc[2].a0), bc[2].sel);
+            v.x = win[0]; v.y = win[1]; v.z = win[2];
             return v;
         }
-        return *reinterpret_cast<const blur_u3*>(R);
+        return l;
     };
     auto fetch = [&](int yy) -> blur_u3 {
         int r = yy < 0 ? -yy : yy;
@@ -1822,9 +1826,9 @@ __global__ __launch_bounds__(256) void blur_stream_kernel(
             const blur_u3 nb = fetch_row(sp);
             sp += ss;
             advance(q, f, na, nb);
-            *reinterpret_cast<uint32_t*>(dp) = BLUR_OUT_A(f);
+            *(blur_gdst*)dp = BLUR_OUT_A(f);
             dp += ds;
-            *reinterpret_cast<uint32_t*>(dp) = BLUR_OUT_B(f);
+            *(blur_gdst*)dp = BLUR_OUT_B(f);
             dp += ds;
             asm volatile("" : "+v"(sp), "+v"(dp));   // (keeps the two pointers running: the compiler would compute every step's addresses at the trip's top)
         };
@@ -1858,6 +1862,24 @@ __global__ __launch_bounds__(256) void blur_stream_kernel(
 #undef BLUR_OUT_B
 #undef BLUR_OUT_A
 #undef BLUR_OUT
+}
+
+// One launch for both strip tables of a level range: the first ceil(n_in / 16) workgroups take the strips inside the level, the
+// rest the edge strips -- a workgroup (and so every wave) runs one instance of the walk.  An edge wave costs what an inner wave
+// costs, so a launch of their own would only be a second ramp and tail on the side stream.  (Six waves per SIMD: without the hint the
+// two walks in one kernel take 81 VGPRs, one past the step to five waves; with it 80, nothing spilled.)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void blur_stream_kernel(
+    const OrbLevel* __restrict__ levels, const uint4* __restrict__ tiles_in, unsigned n_in, const uint4* __restrict__ tiles_edge, unsigned n_edge,
+    const uint8_t* __restrict__ img0, size_t img0_stride, size_t img0_frame, const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur) {
+    const unsigned wg_in = (n_in + 15u) >> 4, sub = threadIdx.x >> 4;
+    const int frame = blockIdx.y;
+    if (blockIdx.x < wg_in) {
+        const unsigned tile = blockIdx.x * 16u + sub;
+        if (tile < n_in) blur_stream_walk<false>(levels, tiles_in[tile], frame, img0, img0_stride, img0_frame, pyr, blur);
+    } else {
+        const unsigned tile = (blockIdx.x - wg_in) * 16u + sub;
+        if (tile < n_edge) blur_stream_walk<true>(levels, tiles_edge[tile], frame, img0, img0_stride, img0_frame, pyr, blur);
+    }
 }
 
 // --------------------------------------------------------------------------------------------
@@ -2163,15 +2185,12 @@ void orbk_ic_angle(hipStream_t st, const OrbLevel* levels, int nlevels, const ui
                            nlevels, img0, img0_stride, img0_frame, pyr, lkp, kp_frame_stride, kp_count, 0, kblocks);
 }
 
-void orbk_blur_stream(hipStream_t st, const OrbLevel* levels, const uint32_t* d_tiles, int ntiles, const uint8_t* img0,
-                      size_t img0_stride, size_t img0_frame, const uint8_t* pyr, uint8_t* blur, int nframes, bool edge) {
-    if (ntiles <= 0) return;
-    if (edge)
-        hipLaunchKernelGGL(blur_stream_kernel<true>, dim3((ntiles + 15) / 16, nframes), dim3(256), 0, st, levels, reinterpret_cast<const uint4*>(d_tiles), img0,
-                           img0_stride, img0_frame, pyr, blur, (unsigned)ntiles);
-    else
-        hipLaunchKernelGGL(blur_stream_kernel<false>, dim3((ntiles + 15) / 16, nframes), dim3(256), 0, st, levels, reinterpret_cast<const uint4*>(d_tiles), img0,
-                           img0_stride, img0_frame, pyr, blur, (unsigned)ntiles);
+void orbk_blur_stream(hipStream_t st, const OrbLevel* levels, const uint32_t* d_inner, int n_inner, const uint32_t* d_edge, int n_edge,
+                      const uint8_t* img0, size_t img0_stride, size_t img0_frame, const uint8_t* pyr, uint8_t* blur, int nframes) {
+    const int wgs = (std::max(n_inner, 0) + 15) / 16 + (std::max(n_edge, 0) + 15) / 16;
+    if (wgs <= 0) return;
+    hipLaunchKernelGGL(blur_stream_kernel, dim3(wgs, nframes), dim3(256), 0, st, levels, reinterpret_cast<const uint4*>(d_inner), (unsigned)std::max(n_inner, 0),
+                       reinterpret_cast<const uint4*>(d_edge), (unsigned)std::max(n_edge, 0), img0, img0_stride, img0_frame, pyr, blur);
 }
 
 void orbk_blur(hipStream_t st, const OrbLevel* levels, const uint32_t* d_tiles, int total_tiles, const uint8_t* img0,
