@@ -78,6 +78,9 @@ def orb_lib():
         L.orb_oracle_round.argtypes = [C.c_double]
         L.orb_oracle_fast.argtypes = [_u8p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, C.c_int]
         L.orb_oracle_octree.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int]
+        L.orb_oracle_octree_ex.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, _i32p]
+        L.orb_oracle_octree_exits.argtypes = [C.c_void_p, _i32p]
+        L.orb_oracle_set_reverse_tie.argtypes = [C.c_void_p, C.c_int]
         L.orb_oracle_descriptor.argtypes = [C.c_float, C.c_float, C.c_float, _u8p, C.c_int, _u8p]
         L.orb_oracle_cossin.argtypes = [C.c_float, _f32p, _f32p]
         L.orb_oracle_distance.argtypes = [_u8p, _u8p]
@@ -102,11 +105,15 @@ def orb_lib():
 class OrbOracle:
     """ORBextractor restatement (oracle/orb_oracle.cc)."""
 
-    def __init__(self, nfeatures=1000, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7):
+    def __init__(self, nfeatures=1000, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7, reverse_tie=False):
+        """reverse_tie is a TEST-ONLY mutation of the octree's tie rule (orb_oracle.cc, distribute_octree): only the tests that show
+        their fixtures depend on that rule pass True."""
         self.L = orb_lib()
         self.nlevels = nlevels
         self.nfeatures = nfeatures
         self.h = self.L.orb_oracle_create(nfeatures, scale_factor, nlevels, ini_th, min_th)
+        if reverse_tie:
+            self.L.orb_oracle_set_reverse_tie(self.h, 1)
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -156,6 +163,12 @@ class OrbOracle:
         self.L.orb_oracle_candidates(self.h, level, _ptr(out, _i32p), n)
         return out[:n]
 
+    def octree_exits(self):
+        """Per level of the last extract: how DistributeOctTree ended (OCTREE_EXITS), None for a level that was not walked."""
+        out = np.full(self.nlevels, -1, np.int32)
+        self.L.orb_oracle_octree_exits(self.h, _ptr(out, _i32p))
+        return [OCTREE_EXITS[k] if k >= 0 else None for k in out]
+
     def level_kps(self, level):
         n = self.L.orb_oracle_level_kps(self.h, level, None, 0)
         out = np.zeros(max(n, 1), KP_DTYPE)
@@ -199,13 +212,18 @@ def fast(img, threshold):
     return out[:n]
 
 
-def octree(xyr, min_x, max_x, min_y, max_y, n_target):
-    xyr = np.ascontiguousarray(xyr, np.float32)
+OCTREE_EXITS = ("at_once", "sorted_stage", "exhausted")   # distribute_octree's exitKind 0, 1, 2
+
+
+def octree(xyr, min_x, max_x, min_y, max_y, n_target, reverse_tie=False, with_exit=False):
+    """reverse_tie: the TEST-ONLY mutation of the tie rule (see OrbOracle).  with_exit: also which way the loop ended (OCTREE_EXITS)."""
+    xyr = np.ascontiguousarray(xyr, np.float32).reshape(-1, 3)
     cap = n_target + 8 + len(xyr)
     out = np.zeros((cap, 3), np.float32)
-    n = orb_lib().orb_oracle_octree(_ptr(xyr, _f32p), len(xyr), min_x, max_x, min_y, max_y, n_target,
-                                    _ptr(out, _f32p), cap)
-    return out[:n]
+    kind = np.full(1, -1, np.int32)
+    n = orb_lib().orb_oracle_octree_ex(_ptr(xyr, _f32p), len(xyr), min_x, max_x, min_y, max_y, n_target,
+                                       _ptr(out, _f32p), cap, int(bool(reverse_tie)), _ptr(kind, _i32p))
+    return (out[:n], OCTREE_EXITS[kind[0]]) if with_exit else out[:n]
 
 
 def descriptor(img, kx, ky, angle_deg):
@@ -363,6 +381,79 @@ def matrix(q, t):
     t = np.ascontiguousarray(t, np.uint8).reshape(-1, 32)
     out = np.zeros((len(q), len(t)), np.uint16)
     orb_lib().orb_oracle_matrix(_ptr(q), len(q), _ptr(t), len(t), out.ctypes.data_as(C.POINTER(C.c_uint16)))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# The reference's own ORBextractor.cc under a monotone allocator (oracle/_ref/orb_ref_harness, oracle/orb_ref_harness.cc), where it
+# was built in the authoring container.  A stand-alone program, run in a child process; its six OpenCV primitives are orb_oracle.cc's.
+# ---------------------------------------------------------------------------------------------
+ORB_REF_TIMEOUT_S = 120
+
+
+def orb_ref_available():
+    return os.path.exists(os.path.join(HERE, "_ref", "orb_ref_harness"))
+
+
+def _orb_ref_run(request, system_allocator=False):
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        req, rep = os.path.join(d, "request.bin"), os.path.join(d, "reply.bin")
+        with open(req, "wb") as f:
+            f.write(request)
+        cmd = [os.path.join(HERE, "_ref", "orb_ref_harness")] + (["--system-allocator"] if system_allocator else []) + [req, rep]
+        subprocess.run(cmd, check=True, timeout=ORB_REF_TIMEOUT_S, stdin=subprocess.DEVNULL)
+        with open(rep, "rb") as f:
+            return f.read()
+
+
+class _Reader:
+    def __init__(self, buf):
+        self.buf, self.at = buf, 0
+
+    def take(self, dtype, n):
+        dt = np.dtype(dtype)
+        a = np.frombuffer(self.buf, dt, n, self.at).copy()
+        self.at += dt.itemsize * n
+        return a
+
+    def i32(self):
+        return int(self.take("<i4", 1)[0])
+
+
+def orb_ref_extract(img, nfeatures, scale, nlevels, ini_th, min_th, system_allocator=False):
+    """The reference's ORBextractor(nfeatures, scale, nlevels, ini_th, min_th) on one 8-bit image -> dict:
+    kps (KP_DTYPE) and desc in operator()'s output order; levels: the padded plane behind every mvImagePyramid level, (h + 38, w + 38);
+    level_kps: per level the list as it leaves ComputeKeyPointsOctTree (level coordinates, angle set); tables as OrbOracle.tables();
+    arena_bytes: what the monotone allocator handed out."""
+    img = np.ascontiguousarray(img, np.uint8)
+    h, w = img.shape
+    head = np.array([1, nfeatures, 0, nlevels, ini_th, min_th, w, h], "<i4")
+    head[2:3] = np.array([scale], "<f4").view("<i4")
+    r = _Reader(_orb_ref_run(head.tobytes() + img.tobytes(), system_allocator))
+    n = r.i32()
+    out = {"kps": r.take(KP_DTYPE, n), "desc": r.take(np.uint8, 32 * n).reshape(n, 32), "levels": [], "level_kps": []}
+    for _ in range(nlevels):
+        lw, lh = r.i32(), r.i32()
+        out["levels"].append(r.take(np.uint8, (lw + 38) * (lh + 38)).reshape(lh + 38, lw + 38))
+    for _ in range(nlevels):
+        out["level_kps"].append(r.take(KP_DTYPE, r.i32()))
+    t = {k: r.take("<f4", nlevels) for k in ("scale", "inv_scale", "sigma2", "inv_sigma2")}
+    t["per_level"], t["umax"] = r.take("<i4", nlevels), r.take("<i4", 16)
+    out["tables"] = t
+    out["arena_bytes"] = int(r.take("<i8", 1)[0])
+    assert r.at == len(r.buf), "orb_ref_harness: reply length"
+    return out
+
+
+def orb_ref_octree(keys, min_x, max_x, min_y, max_y, n, level=0, system_allocator=False):
+    """The reference's DistributeOctTree on (x, y, response) float triplets -> (m, 3) float32 in list order."""
+    keys = np.ascontiguousarray(keys, "<f4").reshape(-1, 3)
+    head = np.array([2, len(keys), min_x, max_x, min_y, max_y, n, level], "<i4")
+    r = _Reader(_orb_ref_run(head.tobytes() + keys.tobytes(), system_allocator))
+    m = r.i32()
+    out = r.take("<f4", 3 * m).reshape(m, 3)
+    assert r.at == len(r.buf), "orb_ref_harness: reply length"
     return out
 
 

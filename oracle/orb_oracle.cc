@@ -5,25 +5,41 @@
 //
 // What it is: a from-scratch, single-threaded, strict-IEEE (-ffp-contract=off, no fast-math)
 // restatement of ORB_SLAM2::ORBextractor (reference: oRB_SLAM2_Android/src/main/jni/ORB_SLAM2/
-// src/ORBextractor.cc, "S/" below) and of the five OpenCV 2.4.9 primitives it calls
+// src/ORBextractor.cc, "S/" below) and of the six OpenCV 2.4.9 primitives it calls
 // (cv::resize 8UC1 INTER_LINEAR, cv::copyMakeBorder REFLECT_101, cv::FAST 9/16 + NMS,
 // cv::GaussianBlur 7x7 sigma 2 8U, cv::fastAtan2, cvRound), plus ORBmatcher::DescriptorDistance
 // with the reference's best/second-best selection rule.
 //
-// PARITY STATUS: *** parity unpinned *** for the OpenCV primitives.  OpenCV 2.4.9 (Android
+// PARITY STATUS, the reference's own half: PINNED to the compiled reference under a monotone
+// allocator.  oracle/Makefile.ref compiles S/ORBextractor.cc where it lies against the stand-in
+// headers of oracle/cvstub_orb into oracle/_ref/orb_ref_harness (oracle/orb_ref_harness.cc, a
+// stand-alone program whose operator new never reuses memory); the constructor tables, the pyramid
+// views, the cell walk, the minThFAST retry, DistributeOctTree / DivideNode, IC_Angle,
+// computeOrbDescriptor and the order of operator() then run as the reference wrote them, and
+// tests/test_orb_ref_live.py finds this file equal to them bit for bit on the fixtures of
+// tests/orb_ref_fixtures.py (recorded in tests/golden/orb_ref_*.npz for tests/test_orb_ref_golden.py
+// and tests/test_gpu_orb_ref.py).  No difference was found when the pin was made.
+//
+// PARITY STATUS, the six primitives: *** parity unpinned ***.  The harness routes them into THIS
+// file's exported functions (orb_oracle_fast, _resize, _blur, _fill_border, _fast_atan2, _round /
+// _floor / _ceil), so the pin says nothing about them.  OpenCV 2.4.9 (Android
 // SDK, native) is an un-vendored dependency of the reference (jni/Android.mk:30); neither its
 // source nor a binary exists in /root/reference or on this machine, and the reference holds no
 // test, fixture or golden vector for this path.  The primitives are
 // restated from the published OpenCV 2.4 algorithms (generic C code paths) and pinned only by
 // definitional known-answer tests (tests/test_oracle_orb.py): brute-force FAST-9/16 definition,
 // an independent exact-integer numpy model of the bilinear resize and the 7x7 blur, atan2 error
-// bound, umax table, feature quotas.  The ORBextractor.cc logic itself (cells, thresholds,
-// octree, orientation, descriptor, ordering) follows the cited lines one to one.
+// bound, umax table, feature quotas.
 //
 // One deliberate definition: DistributeOctTree sorts
 // pair<int, ExtractorNode*> (S/ORBextractor.cc:697), so equal-sized nodes are ordered by heap
 // address in the reference.  Here the pointer is replaced by the node's creation sequence
-// number (what a bump allocator would produce).
+// number.  That IS the reference under a monotone allocator: 195 direct DistributeOctTree calls,
+// 72 of them decided by this rule, give the same keys in the same order (and the reversed rule,
+// distribute_octree's test-only reverseTie, fails those 72).  Under the C library's allocator the
+// reference itself gives other results on 62 of the 195: the line has no allocator-free meaning.
+// cos / sin of computeOrbDescriptor remain a definition (the correctly rounded float; the harness
+// runs the platform's libm there and agrees on every fixture).
 //
 // Build: oracle/Makefile (g++ -O2 -std=c++11 -ffp-contract=off).
 
@@ -73,20 +89,20 @@ struct Plane {  // a padded pyramid level: (w+38) x (h+38), ROI origin at (19,19
 };
 
 // cv::copyMakeBorder(src, dst, 19,19,19,19, BORDER_REFLECT_101 [| BORDER_ISOLATED])
-// S/ORBextractor.cc:1159-1164.  The ROI of `p` already holds the image; fill the frame.
-void fill_border(Plane& p) {
-    uint8_t* r = p.roi();
+// S/ORBextractor.cc:1159-1164.  The w x h ROI at `r` already holds the image; fill the frame of 19 around it.
+void fill_border(uint8_t* r, int w, int h, int stride) {
     const int B = EDGE_THRESHOLD;
-    for (int y = -B; y < p.h + B; ++y) {
-        int sy = reflect101(y, p.h);
-        uint8_t* drow = r + (ptrdiff_t)y * p.stride;
-        const uint8_t* srow = r + (ptrdiff_t)sy * p.stride;
-        if (y < 0 || y >= p.h)
-            for (int x = 0; x < p.w; ++x) drow[x] = srow[x];
-        for (int x = -B; x < 0; ++x) drow[x] = srow[reflect101(x, p.w)];
-        for (int x = p.w; x < p.w + B; ++x) drow[x] = srow[reflect101(x, p.w)];
+    for (int y = -B; y < h + B; ++y) {
+        int sy = reflect101(y, h);
+        uint8_t* drow = r + (ptrdiff_t)y * stride;
+        const uint8_t* srow = r + (ptrdiff_t)sy * stride;
+        if (y < 0 || y >= h)
+            for (int x = 0; x < w; ++x) drow[x] = srow[x];
+        for (int x = -B; x < 0; ++x) drow[x] = srow[reflect101(x, w)];
+        for (int x = w; x < w + B; ++x) drow[x] = srow[reflect101(x, w)];
     }
 }
+void fill_border(Plane& p) { fill_border(p.roi(), p.w, p.h, p.stride); }
 
 // cv::resize(src, dst, dsize, 0, 0, INTER_LINEAR) for CV_8UC1, OpenCV 2.4 generic C path:
 // fixed-point coefficients (11 bits), horizontal pass to int32, vertical pass
@@ -320,7 +336,7 @@ struct Node {  // ExtractorNode, include/ORBextractor.h:32-44
     int ULx, ULy, URx, URy, BLx, BLy, BRx, BRy;
     std::list<Node>::iterator lit;
     bool noMore;
-    long seq;  // creation sequence number: replaces the heap address in the tie-break
+    long seq;  // creation sequence number: replaces the heap address in the tie-break (negated under reverseTie)
     Node() : noMore(false), seq(0) {}
 };
 
@@ -362,10 +378,11 @@ typedef std::pair<int, std::pair<long, Node*> > SizeSeqNode;  // (size, (seq, no
 
 // children with keys are pushed to the FRONT in the order n1..n4 (S/ORBextractor.cc:634-673)
 inline void push_children(std::list<Node>& lNodes, Node* ch[4], long& seq, int* nToExpand,
-                          std::vector<SizeSeqNode>& vSize) {
+                          std::vector<SizeSeqNode>& vSize, bool reverseTie) {
     for (int c = 0; c < 4; ++c) {
         if (ch[c]->keys.size() > 0) {
-            ch[c]->seq = seq++;
+            ch[c]->seq = reverseTie ? -seq : seq;
+            ++seq;
             lNodes.push_front(*ch[c]);
             if (ch[c]->keys.size() > 1) {
                 if (nToExpand) ++*nToExpand;
@@ -377,9 +394,15 @@ inline void push_children(std::list<Node>& lNodes, Node* ch[4], long& seq, int* 
     }
 }
 
-// ORBextractor::DistributeOctTree, S/ORBextractor.cc:552-776
+// ORBextractor::DistributeOctTree, S/ORBextractor.cc:552-776.  reverseTie is a TEST-ONLY mutation: among equal-sized nodes the
+// earliest-created one expands first, the opposite of the reference under a monotone allocator (tests/test_orb_ref_*.py use it to
+// show that their fixtures would notice a wrong tie rule).  Nothing else may pass true.
+// *exitKind (for the same tests' premises): which way the loop ended -- 0: `>= N` after a full pass (:682), 1: `>= N` inside the sorted
+// stage (:686-751), 2: exhaustion, a pass that changed nothing (`lNodes.size() == prevSize` at :682 or :747).
 std::vector<Key> distribute_octree(const std::vector<Key>& toDistribute, int minX, int maxX,
-                                   int minY, int maxY, int N) {
+                                   int minY, int maxY, int N, bool reverseTie = false, int* exitKind = 0) {
+    int exitKindLocal;
+    if (!exitKind) exitKind = &exitKindLocal;
     const int nIni = (int)round(static_cast<float>(maxX - minX) / (maxY - minY));
     const float hX = static_cast<float>(maxX - minX) / nIni;
     std::list<Node> lNodes;
@@ -417,11 +440,12 @@ std::vector<Key> distribute_octree(const std::vector<Key>& toDistribute, int min
             Node n1, n2, n3, n4;
             divide_node(*lit, n1, n2, n3, n4);
             Node* ch[4] = {&n1, &n2, &n3, &n4};
-            push_children(lNodes, ch, seq, &nToExpand, vSizeAndPointerToNode);
+            push_children(lNodes, ch, seq, &nToExpand, vSizeAndPointerToNode, reverseTie);
             lit = lNodes.erase(lit);
         }
         if ((int)lNodes.size() >= N || (int)lNodes.size() == prevSize) {
             bFinish = true;
+            *exitKind = (int)lNodes.size() >= N ? 0 : 2;
         } else if (((int)lNodes.size() + nToExpand * 3) > N) {
             while (!bFinish) {
                 prevSize = (int)lNodes.size();
@@ -433,11 +457,14 @@ std::vector<Key> distribute_octree(const std::vector<Key>& toDistribute, int min
                     Node* parent = vPrev[j].second.second;
                     divide_node(*parent, n1, n2, n3, n4);
                     Node* ch[4] = {&n1, &n2, &n3, &n4};
-                    push_children(lNodes, ch, seq, 0, vSizeAndPointerToNode);
+                    push_children(lNodes, ch, seq, 0, vSizeAndPointerToNode, reverseTie);
                     lNodes.erase(parent->lit);
                     if ((int)lNodes.size() >= N) break;
                 }
-                if ((int)lNodes.size() >= N || (int)lNodes.size() == prevSize) bFinish = true;
+                if ((int)lNodes.size() >= N || (int)lNodes.size() == prevSize) {
+                    bFinish = true;
+                    *exitKind = (int)lNodes.size() >= N ? 1 : 2;
+                }
             }
         }
     }
@@ -457,6 +484,7 @@ std::vector<Key> distribute_octree(const std::vector<Key>& toDistribute, int min
 struct Oracle {
     // parameters (S/ORBextractor.cc:415-420); scaleFactor is a double member holding a float
     int nfeatures, nlevels, iniThFAST, minThFAST;
+    bool reverseTie;  // test-only, see distribute_octree
     double scaleFactor;
     std::vector<float> mvScaleFactor, mvInvScaleFactor, mvLevelSigma2, mvInvLevelSigma2;
     std::vector<int> mnFeaturesPerLevel, umax;
@@ -465,6 +493,7 @@ struct Oracle {
     std::vector<std::vector<uint8_t> > blurred;       // w*h per level (only levels with keypoints)
     std::vector<std::vector<int32_t> > candidates;    // x,y,score triplets per level
     std::vector<std::vector<slamit_kp> > levelKps;    // after octree + orientation (level coords)
+    std::vector<int> octreeExit;                      // distribute_octree's exitKind per level (-1: level not walked)
     std::vector<slamit_kp> kps;
     std::vector<uint8_t> desc;
 };
@@ -472,6 +501,7 @@ struct Oracle {
 // ORBextractor::ORBextractor, S/ORBextractor.cc:415-482
 void oracle_init(Oracle& o, int nfeatures, float scaleFactor, int nlevels, int iniTh, int minTh) {
     o.nfeatures = nfeatures; o.nlevels = nlevels; o.iniThFAST = iniTh; o.minThFAST = minTh;
+    o.reverseTie = false;
     o.scaleFactor = scaleFactor;
     o.mvScaleFactor.assign(nlevels, 0.f); o.mvLevelSigma2.assign(nlevels, 0.f);
     o.mvScaleFactor[0] = 1.0f; o.mvLevelSigma2[0] = 1.0f;
@@ -572,6 +602,7 @@ void orb_descriptor(float kx, float ky, float angle_deg, const uint8_t* img, int
 void compute_keypoints(Oracle& o) {
     o.candidates.assign(o.nlevels, std::vector<int32_t>());
     o.levelKps.assign(o.nlevels, std::vector<slamit_kp>());
+    o.octreeExit.assign(o.nlevels, -1);
     const float W = 30;
     std::vector<FastKp> cell;
     for (int level = 0; level < o.nlevels; ++level) {
@@ -615,7 +646,7 @@ void compute_keypoints(Oracle& o) {
             }
         }
         std::vector<Key> keys = distribute_octree(toDistribute, minBorderX, maxBorderX, minBorderY,
-                                                  maxBorderY, o.mnFeaturesPerLevel[level]);
+                                                  maxBorderY, o.mnFeaturesPerLevel[level], o.reverseTie, &o.octreeExit[level]);
         const int scaledPatchSize = (int)(PATCH_SIZE * o.mvScaleFactor[level]);
         std::vector<slamit_kp>& out = o.levelKps[level];
         for (size_t i = 0; i < keys.size(); ++i) {
@@ -642,7 +673,7 @@ void run(Oracle& o, const uint8_t* img, int w, int h, int stride) {
     o.kps.clear();
     o.desc.clear();
     o.blurred.assign(o.nlevels, std::vector<uint8_t>());
-    if (w <= 0 || h <= 0 || !img) { o.pyramid.clear(); o.candidates.clear(); o.levelKps.clear(); return; }
+    if (w <= 0 || h <= 0 || !img) { o.pyramid.clear(); o.candidates.clear(); o.levelKps.clear(); o.octreeExit.clear(); return; }
     compute_pyramid(o, img, w, h, stride);
     compute_keypoints(o);
     for (int level = 0; level < o.nlevels; ++level) {
@@ -689,6 +720,8 @@ void* orb_oracle_create(int nfeatures, float scaleFactor, int nlevels, int iniTh
     return o;
 }
 void orb_oracle_destroy(void* h) { delete (Oracle*)h; }
+// TEST-ONLY mutation of the octree's tie rule (see distribute_octree); off by default
+void orb_oracle_set_reverse_tie(void* h, int on) { ((Oracle*)h)->reverseTie = on != 0; }
 
 void orb_oracle_tables(void* h, float* scale, float* inv_scale, float* sigma2, float* inv_sigma2,
                        int32_t* per_level, int32_t* umax16) {
@@ -751,6 +784,13 @@ int orb_oracle_level_kps(void* h, int level, slamit_kp* kps, int cap) {
     return n;
 }
 
+// distribute_octree's exitKind of every level of the last run (nlevels values)
+int orb_oracle_octree_exits(void* h, int32_t* out) {
+    Oracle& o = *(Oracle*)h;
+    for (size_t i = 0; i < o.octreeExit.size(); ++i) out[i] = o.octreeExit[i];
+    return (int)o.octreeExit.size();
+}
+
 // ---- primitives exposed for known-answer tests ----
 void orb_oracle_resize(const uint8_t* src, int sw, int sh, int sstride, uint8_t* dst, int dw, int dh,
                        int dstride) {
@@ -762,6 +802,10 @@ void orb_oracle_blur(const uint8_t* src, int w, int h, int sstride, uint8_t* dst
 void orb_oracle_gauss_taps(int32_t* taps7) { int k[7]; gauss7_taps(k); for (int i = 0; i < 7; ++i) taps7[i] = k[i]; }
 float orb_oracle_fast_atan2(float y, float x) { return fast_atan2(y, x); }
 int orb_oracle_round(double v) { return cv_round(v); }
+int orb_oracle_floor(double v) { return cv_floor(v); }
+int orb_oracle_ceil(double v) { return cv_ceil(v); }
+// cv::copyMakeBorder(.., 19, 19, 19, 19, BORDER_REFLECT_101) around a w x h image that already lies at roi
+void orb_oracle_fill_border(uint8_t* roi, int w, int h, int stride) { fill_border(roi, w, h, stride); }
 // cv::FAST on a sub image; returns count, writes x,y,score triplets (raster order)
 int orb_oracle_fast(const uint8_t* img, int cols, int rows, int step, int threshold, int32_t* xys, int cap) {
     std::vector<FastKp> out;
@@ -771,13 +815,18 @@ int orb_oracle_fast(const uint8_t* img, int cols, int rows, int step, int thresh
     return n;
 }
 // DistributeOctTree on (x,y,response) float triplets; returns count, writes triplets in list order
-int orb_oracle_octree(const float* xyr, int n, int minX, int maxX, int minY, int maxY, int N, float* out, int cap) {
+// (orb_oracle_octree_ex: reverse_tie != 0 is the test-only mutation of distribute_octree)
+int orb_oracle_octree_ex(const float* xyr, int n, int minX, int maxX, int minY, int maxY, int N, float* out, int cap, int reverse_tie,
+                         int* exit_kind) {
     std::vector<Key> in(n);
     for (int i = 0; i < n; ++i) { in[i].x = xyr[3 * i]; in[i].y = xyr[3 * i + 1]; in[i].response = xyr[3 * i + 2]; }
-    std::vector<Key> res = distribute_octree(in, minX, maxX, minY, maxY, N);
+    std::vector<Key> res = distribute_octree(in, minX, maxX, minY, maxY, N, reverse_tie != 0, exit_kind);
     int m = (int)res.size();
     for (int i = 0; i < m && i < cap; ++i) { out[3 * i] = res[i].x; out[3 * i + 1] = res[i].y; out[3 * i + 2] = res[i].response; }
     return m;
+}
+int orb_oracle_octree(const float* xyr, int n, int minX, int maxX, int minY, int maxY, int N, float* out, int cap) {
+    return orb_oracle_octree_ex(xyr, n, minX, maxX, minY, maxY, N, out, cap, 0, 0);
 }
 void orb_oracle_descriptor(float kx, float ky, float angle_deg, const uint8_t* img, int step, uint8_t* desc) {
     orb_descriptor(kx, ky, angle_deg, img, step, desc);

@@ -2,8 +2,13 @@
 """Writes tests/golden/orb_{vga,vga2000,720p}.npz: the CPU restatement's (oracle/orb_oracle.cc) outputs on three
 synthetic frames, frozen as REGRESSION GUARDS.
 
-NON-AUTHORITATIVE: the ORB half is "parity unpinned" (OpenCV 2.4.9 is not available here and the reference holds no
-fixtures for this path), so these vectors pin the restatement against accidental edits, not against the reference.
+REGRESSION GUARDS of the restatement, not recordings of the reference.  What stands behind the restatement: the reference's own half
+of the extractor (constructor tables, pyramid views, cell walk, FAST retry, DistributeOctTree / DivideNode, IC_Angle,
+computeOrbDescriptor, the order of operator()) is pinned to the compiled reference under a monotone allocator
+(oracle/orb_ref_harness.cc; tests/golden/orb_ref_*.npz from tools/gen_orb_ref_golden.py are the authoritative vectors for that half).
+The six OpenCV primitives (FAST, resize, GaussianBlur, copyMakeBorder, fastAtan2, cvRound) remain restated and "parity unpinned":
+OpenCV 2.4.9 is not available here and the reference holds no fixtures for them.  These three files therefore pin the restatement
+against accidental edits at full size; they were not moved when the pin was made (no difference was found).
 The frames come from weiner_slamit_v2_amd.synth (deterministic); only their CRC-32 is stored.
 
     python tools/gen_orb_golden.py
