@@ -1828,6 +1828,105 @@ struct slamit_check_replaced_batch_rec {
 typedef struct slamit_check_replaced_batch_rec slamit_check_replaced_batch_rec;
 int slamit_check_replaced_batch_dev(int device, const slamit_check_replaced_batch_rec* batch, void* stream);
 
+/* ---- KeyFrame::SetBadFlag on the resident tables: graph rows and the spanning tree ----
+ * KeyFrame::SetBadFlag (src/KeyFrame.cc:460-552) with EraseConnection / UpdateBestCovisibles (:560-574, :142-161) and ChangeParent /
+ * AddChild / EraseChild (:388-405) over the tables of slamit_map_index and the arrays of slamit_tree_index (csrc/kf_erase.h states the
+ * walk).  A list of n ops is applied AS IF SEQUENTIALLY IN LIST ORDER; the result equals the sequential walk exactly.
+ *   SLAMIT_KF_ERASE_SET_PARENT  kf = c, parent = p: kf_parent[c] = p, and c enters p's children row (ascending slot) unless it is
+ *                               there.  No bad test, no erase from an old parent.  The caller issues it when
+ *                               slamit_update_connections returned parent >= 0.
+ *   SLAMIT_KF_ERASE_SET_BAD     kf = k.  k == origin_kf: nothing (ORIGIN).  kf_not_erase[k]: kf_to_be_erased[k] = 1, nothing else
+ *                               (NOT_ERASE).  kf_parent[k] == -1, where the reference dereferences a null parent: nothing (NO_PARENT).
+ *                               Else: every j of k's cw row whose own cw row holds k loses that entry, its ord row becomes the sort of
+ *                               its whole remaining cw row and kf_best[j] its first ten (a j whose row lacks k stays byte for byte);
+ *                               one SLAMIT_EDIT_ERASE_OBS edit without MATCH per non-null entry of k's kf_mp row is EMITTED into
+ *                               `edits`, by op and then by keypoint index, from the kf_mp the call was given; cw_n[k] = ord_n[k] = 0,
+ *                               kf_best[k] all -1; the spanning tree is repaired as the reference repairs it (the pair of child and
+ *                               candidate with the strictly largest GetWeight, first in row order, again and again; the children left
+ *                               over go to kf_parent[k] and stay in k's row); k leaves its parent's row; kf_bad[k] = 1; kf_parent[k] stays.
+ * The point side of SetBadFlag is the emitted list handed to slamit_map_edit_batch_dev as the next call on the stream (cap = edit_cap,
+ * d_n = d_n_edits_out).  IN PLACE: kf_bad, kf_parent, kf_to_be_erased and the seven graph arrays, the very memory the map and covis
+ * records point to; a changed graph row is rewritten up to its new count.  OUT OF PLACE: the children table, a packed CSR ascending
+ * from 0 that slamit_map_index takes unchanged (a caller alternates two buffer sets); a row no op touched is copied.
+ * GATES: the new children table above child_cap_out entries, or more edits than edit_cap: NOTHING is written but n_edits_out,
+ * n_child_out (the two needs) and the call's status.  The old table plus one entry per SET_PARENT op and per child of a SET_BAD keyframe
+ * always suffices.  mTcp (the library holds no poses: read kf_parent[k]), Map::EraseKeyFrame, KeyFrameDatabase::erase
+ * (slamit_kfdb_erase), SetErase() and the loop edges stay the caller's.
+ * Kinds, status bits (per op: the first five; per call: BAD_SLOT, ROW_OVERFLOW and the two gates) and ceilings: */
+#define SLAMIT_KF_ERASE_SET_PARENT 1
+#define SLAMIT_KF_ERASE_SET_BAD 2
+#define SLAMIT_KF_ERASE_ORIGIN 1           /* SET_BAD of origin_kf: nothing was done */
+#define SLAMIT_KF_ERASE_NOT_ERASE 2        /* kf_not_erase: kf_to_be_erased = 1, nothing else */
+#define SLAMIT_KF_ERASE_NO_PARENT 4        /* kf_parent == -1 on a keyframe that is not the origin: the op was skipped whole */
+#define SLAMIT_KF_ERASE_BAD_SLOT 8         /* device form: an op or a table entry with a slot outside its table was skipped */
+#define SLAMIT_KF_ERASE_ROW_OVERFLOW 16    /* more than SLAMIT_KF_ERASE_MAX_CHILD children: the op was skipped whole */
+#define SLAMIT_KF_ERASE_CHILD_OVERFLOW 32  /* the new children table needs more than child_cap_out entries: n_child_out says how many */
+#define SLAMIT_KF_ERASE_EDIT_OVERFLOW 64   /* more edits than edit_cap: n_edits_out says how many */
+#define SLAMIT_KF_ERASE_MAX_OPS 1024       /* ops per list: one workgroup walks them */
+#define SLAMIT_KF_ERASE_MAX_CHILD 1024     /* children of one SET_BAD keyframe: the row and the candidates live in LDS */
+
+struct slamit_kf_op {
+    int32_t kind;
+    int32_t kf;                    /* SET_PARENT: the child.  SET_BAD: the keyframe */
+    int32_t parent;                /* SET_PARENT: the new parent */
+    int32_t reserved;
+};
+typedef struct slamit_kf_op slamit_kf_op;
+
+/* The arrays beside one slamit_map_index that the ops read and write.  Host pointers in the host form, device pointers in the batch
+ * record.  Of the map record the call reads n_kf, n_mp, kf_mp_ptr, kf_mp, kf_child_ptr and kf_child. */
+struct slamit_tree_index {
+    int32_t row_cap;               /* entries per graph row, <= SLAMIT_COVIS_MAX_ROW: slamit_covis_index.row_cap */
+    int32_t origin_kf;             /* slot of the keyframe with mnId 0, -1 = none */
+    const uint8_t* kf_not_erase;   /* [n_kf] mbNotErase */
+    uint8_t* kf_bad;               /* [n_kf] in / out: the memory the map record's kf_bad points to */
+    int32_t* kf_parent;            /* [n_kf] in / out: likewise kf_parent */
+    uint8_t* kf_to_be_erased;      /* [n_kf] in / out: mbToBeErased */
+    int32_t *cw_kf, *cw_w, *cw_n;      /* in / out: the memory of slamit_covis_index */
+    int32_t *ord_kf, *ord_w, *ord_n;
+    int32_t* kf_best;              /* in / out, nullable */
+    int32_t* child_ptr_out;        /* [n_kf + 1] out */
+    int32_t* child_out;            /* [child_cap_out] out */
+    int32_t child_cap_out;         /* entries child_out holds */
+    int32_t reserved;
+};
+typedef struct slamit_tree_index slamit_tree_index;
+
+/* One list over one map (host pointers, synchronous).  op_status[n] in / out; edits[edit_cap] in / out: the first *n_edits_out are
+ * written; *n_edits_out, *n_child_out and *status out.  Entries past the counts are left as the caller filled them; with a gate's bit
+ * everything but the two needs and *status is.  A null table, a slot or a row count outside its range, a kind outside 1..2, a CSR
+ * pointer array that does not ascend from 0 or a children row that does not ascend fails with SLAMIT_ERR_ARG, n above
+ * SLAMIT_KF_ERASE_MAX_OPS with SLAMIT_ERR_CAPACITY, each with a message and before anything is launched. */
+int slamit_kf_erase_apply(int device, const slamit_map_index* map, const slamit_tree_index* tree, int32_t n, const slamit_kf_op* ops,
+                          int32_t* op_status, int32_t edit_cap, slamit_map_edit* edits, int32_t* n_edits_out, int32_t* n_child_out, int32_t* status);
+
+/* One list per map for n_maps maps, everything resident.  `maps` and `tree` are HOST arrays of records holding DEVICE pointers; map m
+ * takes the first d_n[m] (clamped to [0, cap]) ops of d_ops[m].  kf_cap >= every n_kf, row_cap >= every map's row_cap, child_cap >=
+ * every map's kf_child_ptr[n_kf].  The device cannot be shown its tables first: an op whose keyframe or parent lies outside the table
+ * is skipped whole, a neighbour or child outside it is skipped, never dereferenced; both set SLAMIT_KF_ERASE_BAD_SLOT.  Asynchronous
+ * on `stream`, no synchronisation, no state; the head of the workspace is cleared on the stream by the call.  One workgroup per map
+ * walks the list; the parallelism is inside an op.
+ * WORKSPACE, every array rounded up to 16 bytes, per map: 16 + 3 kf_cap bytes of flags, 4 (4 row_cap + 15) kf_cap + 4 for the working
+ * graph, columns, list heads and new pointers, 8 (child_cap + cap * min(SLAMIT_KF_ERASE_MAX_CHILD, kf_cap)) for the children lists,
+ * 12 cap + 4 for the ops. */
+struct slamit_kf_erase_batch_rec {
+    int32_t n_maps, cap, kf_cap, row_cap, child_cap, edit_cap;
+    const slamit_map_index* maps;      /* HOST [n_maps], device pointers inside; n_maps <= SLAMIT_LOCAL_MAP_MAX_MAPS */
+    const slamit_tree_index* tree;     /* HOST [n_maps], device pointers inside */
+    const slamit_kf_op* d_ops;         /* [n_maps][cap], cap <= SLAMIT_KF_ERASE_MAX_OPS */
+    const int32_t* d_n;                /* [n_maps] */
+    int32_t* d_op_status;              /* [n_maps][cap] in / out */
+    slamit_map_edit* d_edits;          /* [n_maps][edit_cap] in / out: slamit_map_edit_batch_rec.d_edits with cap = edit_cap */
+    int32_t* d_n_edits_out;            /* [n_maps] out: slamit_map_edit_batch_rec.d_n */
+    int32_t* d_n_child_out;            /* [n_maps] out */
+    int32_t* d_status;                 /* [n_maps] out */
+    void* d_workspace;                 /* slamit_kf_erase_workspace(n_maps, cap, kf_cap, row_cap, child_cap) bytes, 8-byte aligned */
+    size_t workspace_bytes;
+};
+typedef struct slamit_kf_erase_batch_rec slamit_kf_erase_batch_rec;
+size_t slamit_kf_erase_workspace(int n_maps, int cap, int kf_cap, int row_cap, int child_cap);
+int slamit_kf_erase_batch_dev(int device, const slamit_kf_erase_batch_rec* batch, void* stream);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 
 const char* slamit_last_error(void);

@@ -434,6 +434,33 @@ REPLACE_MAX_OPS, REPLACE_MAX_PER_POINT, CHECK_REPLACED_MAX_N = 16384, 64, 65536
 REPLACE_DTYPE = np.dtype([("kind", "<i4"), ("a", "<i4"), ("b", "<i4"), ("idx", "<i4"), ("octave", "u1"), ("weight", "u1"), ("pad", "u1", 2)])
 # slamit_replace_index: the columns read and the table written are the edit index's; the arrays rewritten in place
 REPLACE_INDEX_INPLACE = (("mp_bad", np.uint8), ("mp_nobs", np.int32), ("mp_found", np.int32), ("mp_visible", np.int32), ("mp_replaced", np.int32), ("kf_mp", np.int32))
+
+
+class TreeIndexRec(C.Structure):   # struct slamit_tree_index
+    _fields_ = [("row_cap", C.c_int32), ("origin_kf", C.c_int32), ("kf_not_erase", C.c_void_p), ("kf_bad", C.c_void_p), ("kf_parent", C.c_void_p),
+                ("kf_to_be_erased", C.c_void_p), ("cw_kf", C.c_void_p), ("cw_w", C.c_void_p), ("cw_n", C.c_void_p), ("ord_kf", C.c_void_p), ("ord_w", C.c_void_p),
+                ("ord_n", C.c_void_p), ("kf_best", C.c_void_p), ("child_ptr_out", C.c_void_p), ("child_out", C.c_void_p), ("child_cap_out", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class KfEraseBatchRec(C.Structure):   # struct slamit_kf_erase_batch_rec
+    _fields_ = [("n_maps", C.c_int32), ("cap", C.c_int32), ("kf_cap", C.c_int32), ("row_cap", C.c_int32), ("child_cap", C.c_int32), ("edit_cap", C.c_int32),
+                ("maps", C.POINTER(MapIndexRec)), ("tree", C.POINTER(TreeIndexRec)), ("d_ops", C.c_void_p), ("d_n", C.c_void_p), ("d_op_status", C.c_void_p),
+                ("d_edits", C.c_void_p), ("d_n_edits_out", C.c_void_p), ("d_n_child_out", C.c_void_p), ("d_status", C.c_void_p), ("d_workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
+
+
+# SLAMIT_KF_ERASE_*: the kinds, the status bits, the ceilings; struct slamit_kf_op as a numpy record
+KF_ERASE_SET_PARENT, KF_ERASE_SET_BAD = 1, 2
+KF_ERASE_STATUS = {"ORIGIN": 1, "NOT_ERASE": 2, "NO_PARENT": 4, "BAD_SLOT": 8, "ROW_OVERFLOW": 16, "CHILD_OVERFLOW": 32, "EDIT_OVERFLOW": 64}
+KF_ERASE_REFUSED = 32 | 64   # with one of these nothing was written but the two needs and the status
+KF_ERASE_MAX_OPS, KF_ERASE_MAX_CHILD = 1024, 1024
+KF_OP_DTYPE = np.dtype([("kind", "<i4"), ("kf", "<i4"), ("parent", "<i4"), ("reserved", "<i4")])
+# slamit_tree_index: the column read, the arrays rewritten in place (the last seven are the covis record's graph)
+TREE_INDEX_INPLACE = (("kf_bad", np.uint8), ("kf_parent", np.int32), ("kf_to_be_erased", np.uint8), ("cw_kf", np.int32), ("cw_w", np.int32), ("cw_n", np.int32),
+                      ("ord_kf", np.int32), ("ord_w", np.int32), ("ord_n", np.int32), ("kf_best", np.int32))
+
+
 DEPTH_TYPES = ("f32", "u16")   # SLAMIT_DEPTH_*: the index is the type
 DEPTH_PLANE_DTYPE = np.dtype([("data", "<u8"), ("pitch", "<u8"), ("width", "<i4"), ("height", "<i4"), ("type", "<i4"), ("factor", "<f4")])   # slamit_depth_plane
 RGBD_STATUS = ("no_depth", "depth", "outside")
@@ -505,7 +532,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_map_edit_apply", "slamit_map_edit_workspace", "slamit_map_edit_batch_dev", "slamit_map_replace_apply", "slamit_map_replace_workspace", "slamit_map_replace_batch_dev", "slamit_check_replaced", "slamit_check_replaced_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_map_edit_apply", "slamit_map_edit_workspace", "slamit_map_edit_batch_dev", "slamit_map_replace_apply", "slamit_map_replace_workspace", "slamit_map_replace_batch_dev", "slamit_check_replaced", "slamit_check_replaced_batch_dev", "slamit_kf_erase_apply", "slamit_kf_erase_workspace", "slamit_kf_erase_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -607,6 +634,10 @@ def lib():
         L.slamit_map_replace_batch_dev.argtypes = [i32, C.POINTER(MapReplaceBatchRec), vp]
         L.slamit_check_replaced.argtypes = [i32, i32, vp, i32, vp, vp]
         L.slamit_check_replaced_batch_dev.argtypes = [i32, C.POINTER(CheckReplacedBatchRec), vp]
+        L.slamit_kf_erase_apply.argtypes = [i32, C.POINTER(MapIndexRec), C.POINTER(TreeIndexRec), i32, vp, vp, i32, vp, vp, vp, vp]
+        L.slamit_kf_erase_workspace.argtypes = [i32, i32, i32, i32, i32]
+        L.slamit_kf_erase_workspace.restype = sz
+        L.slamit_kf_erase_batch_dev.argtypes = [i32, C.POINTER(KfEraseBatchRec), vp]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_bow_search_stereo.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), C.POINTER(BowStereo), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
@@ -3050,3 +3081,146 @@ def check_replaced_batch_dev(replaced, t, n_mp=None, device=0, stream=None):
     ptrs = (C.c_void_p * max(nm, 1))(*[r.data_ptr() for r in replaced])
     rec = CheckReplacedBatchRec(f, nm, cap, 0, counts, ptrs, t["frame_map"].data_ptr(), t["n"].data_ptr(), t["frame_mp"].data_ptr(), t["status"].data_ptr())
     _check(lib().slamit_check_replaced_batch_dev(device, C.byref(rec), stream), "slamit_check_replaced_batch_dev")
+
+
+def kf_op_records(ops):
+    """Ops as an array of slamit_kf_op: a KF_OP_DTYPE array as it is, else rows (kind, kf) or (kind, kf, parent)."""
+    if isinstance(ops, np.ndarray) and ops.dtype == KF_OP_DTYPE:
+        return np.ascontiguousarray(ops).reshape(-1)
+    rows = list(ops)
+    out = np.zeros(len(rows), KF_OP_DTYPE)
+    for i, r in enumerate(rows):
+        r = tuple(int(v) for v in r)
+        out[i] = (r + (-1,))[:3] + (0,)
+    return out
+
+
+def kf_erase(tables, tree, ops, child_cap_out=None, edit_cap=None, fill=None, device=0):
+    """KeyFrame::SetBadFlag's graph rows and spanning tree (KeyFrame.cc:460-552, with EraseConnection and ChangeParent) for a list of
+    keyframe ops applied as if sequentially, over a map's tables (slamit_map_index: n_kf, n_mp, kf_mp_ptr, kf_mp, kf_child_ptr, kf_child,
+    kf_bad, kf_parent) and the arrays beside them (dict: row_cap, origin_kf, kf_not_erase, kf_to_be_erased, cw_kf / cw_w (n_kf, row_cap),
+    cw_n, ord_kf / ord_w, ord_n, optionally kf_best (n_kf, 10); kf_bad / kf_parent where they are not taken from `tables`).  ops:
+    kf_op_records().  The caller's arrays are not modified.  child_cap_out: the room of the new children table (default: the old table
+    plus one entry per op and per child of a SET_BAD keyframe); edit_cap: the room of the emitted list (default: k's keypoints summed over the
+    SET_BAD ops).  fill: optional dict of prefilled outputs (child_ptr_out, child_out, op_status, edits), copied.  -> dict:
+    kf_child_ptr, kf_child, kf_bad, kf_parent (what MapIndex / _map_index_host take in place of the old ones), kf_to_be_erased, the
+    seven graph arrays, op_status, edits (EDIT_DTYPE, the first n_edits_out of them), n_edits_out, n_child_out, status, and `raw`: the
+    output arrays in full.  With a bit of KF_ERASE_REFUSED in status the tables returned are the old ones."""
+    rec, keep = _map_index_host(tables)
+    n_kf = max(rec.n_kf, 0)
+    ed = kf_op_records(ops)
+    src = dict(tree)
+    for key in ("kf_bad", "kf_parent"):
+        src.setdefault(key, tables.get(key))
+    cptr = np.asarray(tables["kf_child_ptr"], np.int64).reshape(-1) if tables.get("kf_child_ptr") is not None else np.zeros(1, np.int64)
+    kptr = np.asarray(tables["kf_mp_ptr"], np.int64).reshape(-1) if tables.get("kf_mp_ptr") is not None else np.zeros(1, np.int64)
+    inside = [int(k) for k in ed["kf"][ed["kind"] == KF_ERASE_SET_BAD] if 0 <= k < len(cptr) - 1]
+    if child_cap_out is None:
+        child_cap_out = int(cptr[-1]) + len(ed) + sum(int(cptr[k + 1] - cptr[k]) for k in inside)
+    if edit_cap is None:
+        edit_cap = sum(int(kptr[k + 1] - kptr[k]) for k in inside if k < len(kptr) - 1)
+    child_cap_out, edit_cap = int(child_cap_out), int(edit_cap)
+    fill = fill or {}
+    xrec, xkeep = TreeIndexRec(int(tree["row_cap"]), int(tree["origin_kf"])), {}
+    if src.get("kf_not_erase") is not None:
+        xkeep["kf_not_erase"] = np.ascontiguousarray(src["kf_not_erase"], np.uint8).reshape(-1)
+        xrec.kf_not_erase = xkeep["kf_not_erase"].ctypes.data
+    for key, dt in TREE_INDEX_INPLACE:
+        if src.get(key) is not None:
+            xkeep[key] = np.array(src[key], dt).reshape(-1)
+            setattr(xrec, key, xkeep[key].ctypes.data)
+    for key, count in (("child_ptr_out", n_kf + 1), ("child_out", max(child_cap_out, 0))):
+        xkeep[key] = np.zeros(count, np.int32) if fill.get(key) is None else np.array(fill[key], np.int32).reshape(-1)
+        if len(xkeep[key]) != count:
+            raise SlamitError("kf_erase: fill[%s] does not hold %d entries" % (key, count))
+        setattr(xrec, key, xkeep[key].ctypes.data if count else None)
+    xrec.child_cap_out = child_cap_out
+    ost = np.zeros(len(ed), np.int32) if fill.get("op_status") is None else np.array(fill["op_status"], np.int32).reshape(-1)
+    edits = np.zeros(max(edit_cap, 0), EDIT_DTYPE) if fill.get("edits") is None else np.array(fill["edits"], EDIT_DTYPE).reshape(-1)
+    if len(ost) != len(ed) or len(edits) != max(edit_cap, 0):
+        raise SlamitError("kf_erase: op_status holds one entry per op, edits edit_cap entries")
+    ne, nc, st = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+    some = lambda a: _np_ptr(a) if len(a) else None
+    _check(lib().slamit_kf_erase_apply(device, C.byref(rec), C.byref(xrec), len(ed), some(ed), some(ost), edit_cap, some(edits), _np_ptr(ne), _np_ptr(nc),
+                                       _np_ptr(st)), "slamit_kf_erase_apply")
+    del keep
+    status, n_edits, need = int(st[0]), int(ne[0]), int(nc[0])
+    out = {"status": status, "n_edits_out": n_edits, "n_child_out": need, "op_status": ost, "raw": dict(xkeep, op_status=ost, edits=edits)}
+    if status & KF_ERASE_REFUSED:
+        out.update(kf_child_ptr=np.array(tables["kf_child_ptr"], np.int32).reshape(-1), kf_child=np.array(tables["kf_child"], np.int32).reshape(-1), edits=edits[:0])
+    else:
+        out.update(kf_child_ptr=xkeep["child_ptr_out"], kf_child=xkeep["child_out"][:need], edits=edits[:n_edits])
+    for key, _ in TREE_INDEX_INPLACE:
+        out[key] = xkeep[key].reshape(np.shape(src[key])) if key in xkeep else None
+    return out
+
+
+class TreeIndex:
+    """The arrays kf_erase_batch_dev reads and writes beside a MapIndex (the resident form's slamit_tree_index), with TWO buffer sets for
+    the children table.  TreeIndex(tree, map_index, covis, child_cap): kf_bad and kf_parent ARE map_index's tensors and the seven graph
+    arrays (kf_best included, where the CovisIndex has one) the CovisIndex's, all rewritten in place; kf_not_erase is the CovisIndex's
+    column; kf_to_be_erased is uploaded from tree (default: zeros) and kept in .t.  child_cap: entries each buffer set of the table holds.
+    .rec reads the current set and writes the other; after kf_erase_batch_dev has run without a bit of KF_ERASE_REFUSED, swap() makes the
+    written set the current one in map_index.rec, so every reader takes the new table unchanged."""
+
+    def __init__(self, tree, map_index, covis, child_cap):
+        import torch
+
+        tree = tree or {}
+        self.map_index, self.covis, self.device, self.child_cap = map_index, covis, map_index.device, int(child_cap)
+        dev = "cuda:%d" % self.device
+        n_kf = max(map_index.n_kf, 0)
+        room = lambda t: torch.cat([t, torch.zeros(max(self.child_cap, 1) - t.numel(), dtype=t.dtype, device=dev)]) if t.numel() < max(self.child_cap, 1) else t
+        cur = {"kf_child_ptr": map_index.t["kf_child_ptr"], "kf_child": room(map_index.t["kf_child"])}
+        self.sets = [cur, {k: torch.zeros_like(v) for k, v in cur.items()}]
+        tbe = np.ascontiguousarray(tree["kf_to_be_erased"], np.uint8).reshape(-1) if tree.get("kf_to_be_erased") is not None else np.zeros(max(n_kf, 1), np.uint8)
+        self.t = {"kf_to_be_erased": torch.from_numpy(tbe if len(tbe) else np.zeros(1, np.uint8)).to(dev)}
+        self.rec = TreeIndexRec(covis.row_cap, int(covis.rec.origin_kf))
+        self._point()
+
+    def _point(self):
+        cur, nxt = self.sets
+        mi, ci = self.map_index, self.covis
+        mi.t["kf_child_ptr"], mi.t["kf_child"] = cur["kf_child_ptr"], cur["kf_child"]
+        mi.rec.kf_child_ptr, mi.rec.kf_child = cur["kf_child_ptr"].data_ptr(), cur["kf_child"].data_ptr()
+        self.rec.kf_not_erase = ci.t["kf_not_erase"].data_ptr()
+        self.rec.kf_bad, self.rec.kf_parent = mi.t["kf_bad"].data_ptr(), mi.t["kf_parent"].data_ptr()
+        self.rec.kf_to_be_erased = self.t["kf_to_be_erased"].data_ptr()
+        for key in COVIS_GRAPH:
+            setattr(self.rec, key, ci.t[key].data_ptr() if key in ci.t else None)
+        self.rec.child_ptr_out, self.rec.child_out, self.rec.child_cap_out = nxt["kf_child_ptr"].data_ptr(), nxt["kf_child"].data_ptr(), self.child_cap
+
+    def swap(self):
+        """The children table the last call wrote becomes the one every record reads; no copy, no synchronisation."""
+        self.sets.reverse()
+        self._point()
+
+
+def kf_erase_workspace(n_maps, cap, kf_cap, row_cap, child_cap):
+    return int(lib().slamit_kf_erase_workspace(n_maps, cap, kf_cap, row_cap, child_cap))
+
+
+def kf_erase_batch_dev(maps, tree, t, device=0, stream=None):
+    """One op list per map, resident.  maps / tree: lists of MapIndex / TreeIndex; t: dict of torch CUDA tensors ops (B, cap, 16) u8 (the
+    bytes of KF_OP_DTYPE records; an int32 tensor (B, cap, 4) is the same memory), n (B) i32, op_status (B, cap) i32 in / out, edits (B,
+    edit_cap, 24) u8 in / out (what map_edit_batch_dev takes as its edits, with n_edits_out as its n), n_edits_out (B), n_child_out (B),
+    status (B) i32, workspace: uint8, kf_erase_workspace(B, cap, kf_cap, row_cap, child_cap) bytes with kf_cap = t["kf_cap"] >= every
+    n_kf, row_cap = t["row_cap"] >= every map's, child_cap = t["child_cap"] >= every map's children entries.  The new children tables are
+    written into each TreeIndex's other buffer set: where status has no bit of KF_ERASE_REFUSED, call swap() on the TreeIndex before the
+    next reader is ENQUEUED.  Asynchronous on `stream`."""
+    b, cap = t["ops"].shape[0], t["ops"].shape[1]
+    edit_cap = t["edits"].shape[1]
+    if len(maps) != b or len(tree) != b:
+        raise SlamitError("kf_erase_batch_dev: one MapIndex, one TreeIndex and one list per map")
+    _rows(t, "kf_erase_batch_dev", (("op_status", cap), ("n", 1), ("n_edits_out", 1), ("n_child_out", 1), ("status", 1)), b)
+    for key, per in (("ops", cap * KF_OP_DTYPE.itemsize), ("edits", edit_cap * EDIT_DTYPE.itemsize)):
+        if t[key].numel() * t[key].element_size() != b * per or not t[key].is_contiguous():
+            raise SlamitError("kf_erase_batch_dev: %s is not a contiguous array of %d bytes per map" % (key, per))
+    M, X = (MapIndexRec * max(b, 1))(), (TreeIndexRec * max(b, 1))()
+    for i, (mi, ti) in enumerate(zip(maps, tree)):
+        M[i], X[i] = mi.rec, ti.rec
+    ws = t["workspace"]
+    rec = KfEraseBatchRec(b, cap, int(t["kf_cap"]), int(t["row_cap"]), int(t["child_cap"]), edit_cap, M, X, t["ops"].data_ptr(), t["n"].data_ptr(),
+                          t["op_status"].data_ptr(), t["edits"].data_ptr(), t["n_edits_out"].data_ptr(), t["n_child_out"].data_ptr(), t["status"].data_ptr(),
+                          ws.data_ptr(), ws.numel() * ws.element_size())
+    _check(lib().slamit_kf_erase_batch_dev(device, C.byref(rec), stream), "slamit_kf_erase_batch_dev")

@@ -32,7 +32,8 @@
 // ::ComputeDistinctiveDescriptors for a list of points, src/MapPoint.cc:248-377) and MapPointCulling (:184-219) are built the same way
 // over slamit_update_points and slamit_map_point_culling, ApplyMapEdits (MapPoint::AddObservation, ::EraseObservation
 // and ::SetBadFlag for a list of edits, src/MapPoint.cc:104-174) over slamit_map_edit_apply (section 26), ReplaceMapPoints (MapPoint::Replace for a fuse list, :183-221) over
-// slamit_map_replace_apply (section 27).
+// slamit_map_replace_apply (section 27), SetBadFlagKeyFrames (KeyFrame::SetBadFlag for a list of keyframes, src/KeyFrame.cc:460-552) over
+// slamit_kf_erase_apply and ApplyMapEdits (section 28).
 #ifndef SLAMIT_SHIM_LOCALMAPPING_H
 #define SLAMIT_SHIM_LOCALMAPPING_H
 
@@ -41,6 +42,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <set>
 #include <utility>
@@ -514,6 +516,134 @@ public:
         for (int i = 0; i < n; ++i)
             if (ops[i].kind == SLAMIT_REPLACE_REPLACE && ops[i].pMP != ops[i].pRep) pMap->EraseMapPoint(ops[i].pMP);   // MapPoint.cc:220
         return n;
+    }
+
+    // KeyFrame::SetBadFlag (KeyFrame.cc:460-552) for a LIST of keyframes, applied as if one after the other: ONE slamit_kf_erase_apply call
+    // for the graph rows and the spanning tree plus ONE ApplyMapEdits call with the list it emitted for the point side.  Writes back
+    // mConnectedKeyFrameWeights, mvpOrderedConnectedKeyFrames, mvOrderedWeights, mspChildrens, mpParent, mbBad and mbToBeErased of the
+    // listed keyframes, their neighbours, children and parents (mvOrderedWeights of a keyframe that turned bad is emptied with its
+    // keyframes, where the reference leaves the stale weights), and through ApplyMapEdits the points' side.  Returns the number of
+    // keyframes that turned bad.  Keyframes are numbered by std::less<KeyFrameT*>, so "ascending slot" is the std::map / std::set order of
+    // this run.  A listed keyframe without a parent that is not the origin is skipped whole, where the reference dereferences NULL.  mTcp
+    // (read mpParent), Map::EraseKeyFrame, KeyFrameDatabase::erase, SetErase() and the loop edges stay the caller's.  A keyframe above
+    // SLAMIT_KF_ERASE_MAX_CHILD children is left as it was and LastStatus() is SLAMIT_ERR_CAPACITY with a line on stderr.
+    // THROUGH THE SHIM IT SAVES NOTHING: building the tables walks every row the walk touches a few entries of.  It is for parity and for
+    // integrations that want one code path; the gain is slamit_kf_erase_batch_dev with the tables kept in HBM.  Members used (a friend
+    // declaration in the reference's classes): KeyFrame mnId, mbNotErase, mbToBeErased, mbBad, mpParent, mspChildrens,
+    // mConnectedKeyFrameWeights, mvpOrderedConnectedKeyFrames, mvOrderedWeights, mvpMapPoints, and what ApplyMapEdits names.
+    template <class MapPointT, class KeyFrameT, class MapT>
+    static int SetBadFlagKeyFrames(const std::vector<KeyFrameT*>& list, MapT* pMap, int device = 0) {
+        typedef typename std::map<KeyFrameT*, int>::const_iterator CwIt;
+        typedef typename std::set<KeyFrameT*>::const_iterator SetIt;
+        status() = SLAMIT_OK;
+        const int n = (int)list.size();
+        if (n == 0) return 0;
+        if (n > SLAMIT_KF_ERASE_MAX_OPS) return shim::refuse<LocalMapping>("SetBadFlagKeyFrames: more than SLAMIT_KF_ERASE_MAX_OPS keyframes", SLAMIT_ERR_CAPACITY);
+        // the keyframes whose rows the walk may touch: the listed, their neighbours, children and parents ...
+        std::set<KeyFrameT*> active;
+        for (int i = 0; i < n; ++i) {
+            KeyFrameT* k = list[i];
+            if (!k) return shim::refuse<LocalMapping>("SetBadFlagKeyFrames: a null keyframe");
+            active.insert(k);
+            if (k->mpParent) active.insert(k->mpParent);
+            for (CwIt it = k->mConnectedKeyFrameWeights.begin(); it != k->mConnectedKeyFrameWeights.end(); ++it) active.insert(it->first);
+            for (SetIt it = k->mspChildrens.begin(); it != k->mspChildrens.end(); ++it) active.insert(*it);
+        }
+        // ... and the ones their rows name, which get a slot and empty rows
+        std::set<KeyFrameT*> all(active);
+        for (SetIt a = active.begin(); a != active.end(); ++a) {
+            KeyFrameT* k = *a;
+            if (k->mpParent) all.insert(k->mpParent);
+            for (CwIt it = k->mConnectedKeyFrameWeights.begin(); it != k->mConnectedKeyFrameWeights.end(); ++it) all.insert(it->first);
+            for (SetIt it = k->mspChildrens.begin(); it != k->mspChildrens.end(); ++it) all.insert(*it);
+            for (size_t e = 0; e < k->mvpOrderedConnectedKeyFrames.size(); ++e) all.insert(k->mvpOrderedConnectedKeyFrames[e]);
+        }
+        const std::vector<KeyFrameT*> kfs(all.begin(), all.end());   // a std::set orders by std::less
+        std::map<KeyFrameT*, int32_t> kfSlot;
+        for (size_t k = 0; k < kfs.size(); ++k) kfSlot[kfs[k]] = (int32_t)k;
+        const int n_kf = (int)kfs.size();
+        if (n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return shim::refuse<LocalMapping>("SetBadFlagKeyFrames: more than SLAMIT_LOCAL_MAP_MAX_KF keyframes around the list", SLAMIT_ERR_CAPACITY);
+        size_t rc = 1;
+        for (SetIt a = active.begin(); a != active.end(); ++a) rc = std::max(rc, std::max((*a)->mConnectedKeyFrameWeights.size(), (*a)->mvpOrderedConnectedKeyFrames.size()));
+        if (rc > SLAMIT_COVIS_MAX_ROW) return shim::refuse<LocalMapping>("SetBadFlagKeyFrames: a keyframe with more than SLAMIT_COVIS_MAX_ROW connections", SLAMIT_ERR_CAPACITY);
+        std::vector<int32_t> cw_kf(n_kf * rc, -1), cw_w(n_kf * rc, 0), cw_n(n_kf, 0), ord_kf(n_kf * rc, -1), ord_w(n_kf * rc, 0), ord_n(n_kf, 0);
+        std::vector<int32_t> parent(n_kf, -1), child_ptr(n_kf + 1, 0), child, kf_mp_ptr(n_kf + 1, 0), kf_mp;
+        std::vector<uint8_t> bad(n_kf, 0), tbe(n_kf, 0), not_erase(n_kf, 0), is_active(n_kf, 0), is_listed(n_kf, 0);
+        std::vector<MapPointT*> mps;
+        std::map<MapPointT*, int32_t> mpSlot;
+        int32_t origin = -1;
+        for (int i = 0; i < n; ++i) is_listed[kfSlot[list[i]]] = 1;
+        for (int k = 0; k < n_kf; ++k) {
+            KeyFrameT* kf = kfs[k];
+            if (kf->mnId == 0) origin = k;
+            bad[k] = kf->mbBad ? 1 : 0; tbe[k] = kf->mbToBeErased ? 1 : 0; not_erase[k] = kf->mbNotErase ? 1 : 0;
+            if (active.count(kf)) {
+                is_active[k] = 1;
+                if (kf->mpParent) parent[k] = kfSlot[kf->mpParent];
+                size_t e = 0;
+                for (CwIt it = kf->mConnectedKeyFrameWeights.begin(); it != kf->mConnectedKeyFrameWeights.end(); ++it, ++e) { cw_kf[k * rc + e] = kfSlot[it->first]; cw_w[k * rc + e] = it->second; }
+                cw_n[k] = (int32_t)e;
+                const size_t no = kf->mvpOrderedConnectedKeyFrames.size();
+                for (e = 0; e < no; ++e) { ord_kf[k * rc + e] = kfSlot[kf->mvpOrderedConnectedKeyFrames[e]]; ord_w[k * rc + e] = e < kf->mvOrderedWeights.size() ? kf->mvOrderedWeights[e] : 0; }
+                ord_n[k] = (int32_t)no;
+                for (SetIt it = kf->mspChildrens.begin(); it != kf->mspChildrens.end(); ++it) child.push_back(kfSlot[*it]);   // set order = ascending slot
+            }
+            child_ptr[k + 1] = (int32_t)child.size();
+            if (is_listed[k])
+                for (size_t i = 0; i < kf->mvpMapPoints.size(); ++i) kf_mp.push_back(kf->mvpMapPoints[i] ? slotOf(mpSlot, mps, kf->mvpMapPoints[i]) : -1);
+            kf_mp_ptr[k + 1] = (int32_t)kf_mp.size();
+        }
+        std::vector<slamit_kf_op> ops(n);
+        for (int i = 0; i < n; ++i) {
+            memset(&ops[i], 0, sizeof(ops[i]));
+            ops[i].kind = SLAMIT_KF_ERASE_SET_BAD; ops[i].kf = kfSlot[list[i]]; ops[i].parent = -1;
+        }
+        const size_t child_cap = child.size() + (size_t)n * (size_t)n_kf;   // an op inserts each of its keyframe's children once at the most
+        const size_t edit_cap = kf_mp.size();
+        std::vector<int32_t> child_ptr_new(n_kf + 1, 0), child_new(child_cap + 1, -1), op_status(n, 0);
+        std::vector<slamit_map_edit> emitted(edit_cap + 1);
+        std::vector<int32_t> cw_kf2(cw_kf), cw_w2(cw_w), cw_n2(cw_n), ord_kf2(ord_kf), ord_w2(ord_w), ord_n2(ord_n), parent2(parent);
+        std::vector<uint8_t> bad2(bad), tbe2(tbe);
+        int32_t none32 = -1;
+        slamit_map_index M;
+        memset(&M, 0, sizeof(M));
+        M.n_kf = n_kf; M.n_mp = (int32_t)mps.size(); M.kf_mp_ptr = kf_mp_ptr.data(); M.kf_mp = kf_mp.empty() ? &none32 : kf_mp.data();
+        M.kf_child_ptr = child_ptr.data(); M.kf_child = child.empty() ? &none32 : child.data();
+        slamit_tree_index X;
+        memset(&X, 0, sizeof(X));
+        X.row_cap = (int32_t)rc; X.origin_kf = origin; X.kf_not_erase = not_erase.data();
+        X.kf_bad = bad2.data(); X.kf_parent = parent2.data(); X.kf_to_be_erased = tbe2.data();
+        X.cw_kf = cw_kf2.data(); X.cw_w = cw_w2.data(); X.cw_n = cw_n2.data(); X.ord_kf = ord_kf2.data(); X.ord_w = ord_w2.data(); X.ord_n = ord_n2.data();
+        X.child_ptr_out = child_ptr_new.data(); X.child_out = child_new.data(); X.child_cap_out = (int32_t)child_cap;
+        int32_t n_edits = 0, n_child = 0, st = 0;
+        const int rcode = slamit_kf_erase_apply(device, &M, &X, n, ops.data(), op_status.data(), (int32_t)edit_cap, emitted.data(), &n_edits, &n_child, &st);
+        if (rcode != SLAMIT_OK) return shim::report<LocalMapping>("SetBadFlagKeyFrames: slamit_kf_erase_apply", rcode);
+        if (st & ~SLAMIT_KF_ERASE_ROW_OVERFLOW) return shim::refuse<LocalMapping>("SetBadFlagKeyFrames: slamit_kf_erase_apply reported a status on tables built here", SLAMIT_ERR_STATE);
+        int turned = 0;
+        for (int k = 0; k < n_kf; ++k) {
+            if (!is_active[k]) continue;
+            KeyFrameT* kf = kfs[k];
+            turned += bad2[k] && !bad[k];
+            kf->mbBad = bad2[k] != 0; kf->mbToBeErased = tbe2[k] != 0;
+            kf->mpParent = parent2[k] < 0 ? (KeyFrameT*)0 : kfs[parent2[k]];
+            kf->mspChildrens.clear();
+            for (int e = child_ptr_new[k]; e < child_ptr_new[k + 1]; ++e) kf->mspChildrens.insert(kfs[child_new[e]]);
+            if (cw_n2[k] == cw_n[k] && ord_n2[k] == ord_n[k]) continue;     // a row the walk rewrites loses an entry
+            kf->mConnectedKeyFrameWeights.clear();
+            for (int e = 0; e < cw_n2[k]; ++e) kf->mConnectedKeyFrameWeights[kfs[cw_kf2[k * rc + e]]] = cw_w2[k * rc + e];
+            kf->mvpOrderedConnectedKeyFrames.clear();
+            kf->mvOrderedWeights.clear();                                    // of a keyframe that turned bad too, where :484 leaves stale weights
+            for (int e = 0; e < ord_n2[k]; ++e) { kf->mvpOrderedConnectedKeyFrames.push_back(kfs[ord_kf2[k * rc + e]]); kf->mvOrderedWeights.push_back(ord_w2[k * rc + e]); }
+        }
+        std::vector<MapEdit<MapPointT, KeyFrameT> > edits((size_t)n_edits);
+        for (int i = 0; i < n_edits; ++i) {
+            edits[i].kind = SLAMIT_EDIT_ERASE_OBS; edits[i].flags = 0; edits[i].pMP = mps[emitted[i].mp]; edits[i].pKF = kfs[emitted[i].kf]; edits[i].idx = 0;
+        }
+        ApplyMapEdits(edits, pMap, device);
+        if (status() != SLAMIT_OK) return turned;
+        if (st & SLAMIT_KF_ERASE_ROW_OVERFLOW)
+            shim::refuse<LocalMapping>("SetBadFlagKeyFrames: a keyframe above SLAMIT_KF_ERASE_MAX_CHILD children was left as it was", SLAMIT_ERR_CAPACITY);
+        return turned;
     }
 
     static int LastStatus() { return status(); }
