@@ -89,7 +89,9 @@ def test_map_edit_is_declared_exported_and_built():
         assert callable(getattr(api, f))
     csrc = os.path.join(ROOT, "weiner_slamit_v2_amd", "csrc")
     src = open(os.path.join(csrc, "map_edit.hip")).read()
-    assert "getenv" not in src and '#include "wave_ops.h"' in src and "wave_inclusive_scan_i32" in src and "me_walk(" in src
+    assert "getenv" not in src and '#include "wave_ops.h"' in src and "block_inclusive_scan_i32<ME_NT>(" in src and "me_walk(" in src
+    ops = open(os.path.join(csrc, "wave_ops.h")).read()                                       # the workgroup scan stands on the DPP wave scan, no __shfl
+    assert "wave_inclusive_scan_i32(v)" in ops.split("block_inclusive_scan_i32(int v, int& total) {")[1].split("\n}")[0] and "__shfl" not in ops.split("#ifndef")[1]
     assert "while (" not in src.replace("while (lo < hi)", "")                                # no kernel waits: the one loop is the bisection
     assert "struct slamit_edit_index {" in hdr and "struct slamit_map_edit {" in hdr
     assert api.map_edit_workspace(1, 0, 0, 0) > 0 and api.map_edit_workspace(0, 1, 1, 1) == 0

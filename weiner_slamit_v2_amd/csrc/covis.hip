@@ -21,7 +21,6 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -30,6 +29,7 @@
 #include "../../include/slamit.h"
 #include "slamit_internal.h"
 #include "wave_ops.h"
+#include "map_check.h"
 #include "covis.h"
 
 static_assert(sizeof(CvIndex) == sizeof(slamit_covis_index) && offsetof(CvIndex, mp_nobs) == offsetof(slamit_covis_index, mp_nobs) &&
@@ -363,38 +363,22 @@ static hipError_t cv_launch_culling(const CvCullBatch& B, hipStream_t st) {
     return hipGetLastError();
 }
 
-// ---- what the host forms check before anything is launched -------------------------------------------------------------------
-static bool cv_slots_ok(const int32_t* v, size_t count, int lo, int n) {
-    for (size_t i = 0; i < count; ++i)
-        if (v[i] < lo || v[i] >= n) return false;
-    return true;
-}
-static bool cv_csr_ok(const int32_t* ptr, int rows) {
-    if (ptr[0] != 0) return false;
-    for (int r = 0; r < rows; ++r)
-        if (ptr[r + 1] < ptr[r]) return false;
-    return true;
-}
+// ---- what the host forms check before anything is launched (map_check.h) -------------------------------------------------------
 // the tables both host forms read; null on success, else what is wrong
 static const char* cv_host_tables(const slamit_map_index* map, const slamit_covis_index* X, int32_t k) {
     if (!map || !X) return "null table";
-    if (map->n_kf < 0 || map->n_mp < 0 || map->n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return "n_kf outside [0, SLAMIT_LOCAL_MAP_MAX_KF] or negative n_mp";
+    if (const char* bad = map_sizes_error(map)) return bad;
     if (X->row_cap < 1 || X->row_cap > SLAMIT_COVIS_MAX_ROW) return "row_cap outside [1, SLAMIT_COVIS_MAX_ROW]";
     if (!map->obs_ptr || !map->kf_mp_ptr || (map->n_mp && !map->mp_bad)) return "null table";
     if (map->n_kf && (!X->ord_kf || !X->ord_n)) return "null table";
-    if (!cv_csr_ok(map->obs_ptr, map->n_mp) || !cv_csr_ok(map->kf_mp_ptr, map->n_kf)) return "a CSR pointer array does not ascend from 0";
+    if (!map_csr_ok(map->obs_ptr, map->n_mp) || !map_csr_ok(map->kf_mp_ptr, map->n_kf)) return "a CSR pointer array does not ascend from 0";
     const size_t n_obs = (size_t)map->obs_ptr[map->n_mp], n_kfmp = (size_t)map->kf_mp_ptr[map->n_kf];
     if ((n_obs && !map->obs_kf) || (n_kfmp && !map->kf_mp)) return "null table";
     if (k < 0 || k >= map->n_kf) return "the keyframe is a slot outside [0, n_kf)";
     if (X->origin_kf < -1 || X->origin_kf >= map->n_kf) return "origin_kf is a slot outside [-1, n_kf)";
-    if (!cv_slots_ok(map->obs_kf, n_obs, 0, map->n_kf)) return "obs_kf holds a keyframe slot outside [0, n_kf)";
-    if (!cv_slots_ok(map->kf_mp, n_kfmp, -1, map->n_mp)) return "kf_mp holds a point slot outside [-1, n_mp)";
+    if (const char* bad = map_obs_error(map, nullptr, nullptr)) return bad;
+    if (!map_slots_ok(map->kf_mp, n_kfmp, -1, map->n_mp)) return "kf_mp holds a point slot outside [-1, n_mp)";
     return nullptr;
-}
-static int cv_refuse(const char* where, const char* what) {
-    static thread_local char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", where, what);
-    return slamit_fail(SLAMIT_ERR_ARG, msg);
 }
 
 extern "C" {
@@ -402,9 +386,9 @@ extern "C" {
 int slamit_update_connections(int device, const slamit_map_index* map, const slamit_covis_index* covis, int32_t k, int32_t first_connection,
                               int32_t* counts, int32_t* n_counted, int32_t* n_listed, int32_t* parent, int32_t* status) {
     const char* const where = "slamit_update_connections";
-    if (!counts || !n_counted || !n_listed || !parent || !status) return cv_refuse(where, "null array");
-    if (const char* what = cv_host_tables(map, covis, k)) return cv_refuse(where, what);
-    if (!covis->cw_kf || !covis->cw_w || !covis->cw_n || !covis->ord_w) return cv_refuse(where, "null table");
+    if (!counts || !n_counted || !n_listed || !parent || !status) return slamit_refuse(where, "null array");
+    if (const char* what = cv_host_tables(map, covis, k)) return slamit_refuse(where, what);
+    if (!covis->cw_kf || !covis->cw_w || !covis->cw_n || !covis->ord_w) return slamit_refuse(where, "null table");
     const int n_kf = map->n_kf, n_mp = map->n_mp, row_cap = covis->row_cap;
     const size_t n_obs = (size_t)map->obs_ptr[n_mp], n_kfmp = (size_t)map->kf_mp_ptr[n_kf], rows = (size_t)n_kf * row_cap;
     SLAMIT_USE_DEVICE(device);
@@ -441,28 +425,28 @@ int slamit_update_connections(int device, const slamit_map_index* map, const sla
 
 int slamit_update_connections_batch_dev(int device, const slamit_covis_batch_rec* R, void* stream) {
     const char* const where = "slamit_update_connections_batch_dev";
-    if (!R || R->nitems < 0 || R->n_maps < 0 || R->count_cap < 0) return cv_refuse(where, "bad argument");
+    if (!R || R->nitems < 0 || R->n_maps < 0 || R->count_cap < 0) return slamit_refuse(where, "bad argument");
     if (R->nitems == 0) return SLAMIT_OK;
     if (R->n_maps < 1 || R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->maps || !R->covis)
-        return cv_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
-    if (R->nitems > R->n_maps || !R->item_map) return cv_refuse(where, "more items than maps (one item per map) or no item_map");
-    if (R->count_cap > SLAMIT_LOCAL_MAP_MAX_KF) return cv_refuse(where, "count_cap above SLAMIT_LOCAL_MAP_MAX_KF");
+        return slamit_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
+    if (R->nitems > R->n_maps || !R->item_map) return slamit_refuse(where, "more items than maps (one item per map) or no item_map");
+    if (R->count_cap > SLAMIT_LOCAL_MAP_MAX_KF) return slamit_refuse(where, "count_cap above SLAMIT_LOCAL_MAP_MAX_KF");
     bool used[SLAMIT_LOCAL_MAP_MAX_MAPS] = {};
     int max_row_cap = 1;
     for (int i = 0; i < R->nitems; ++i) {
         const int m = R->item_map[i];
-        if (m < 0 || m >= R->n_maps) return cv_refuse(where, "item_map names a map outside [0, n_maps)");
-        if (used[m]) return cv_refuse(where, "a map is named twice in item_map: a second keyframe of a map is a second call");
+        if (m < 0 || m >= R->n_maps) return slamit_refuse(where, "item_map names a map outside [0, n_maps)");
+        if (used[m]) return slamit_refuse(where, "a map is named twice in item_map: a second keyframe of a map is a second call");
         used[m] = true;
         const slamit_map_index& M = R->maps[m];
         const slamit_covis_index& X = R->covis[m];
-        if (M.n_kf < 0 || M.n_mp < 0 || M.n_kf > R->count_cap) return cv_refuse(where, "a map with n_kf above count_cap");
-        if (X.row_cap < 1 || X.row_cap > SLAMIT_COVIS_MAX_ROW) return cv_refuse(where, "row_cap outside [1, SLAMIT_COVIS_MAX_ROW]");
+        if (M.n_kf < 0 || M.n_mp < 0 || M.n_kf > R->count_cap) return slamit_refuse(where, "a map with n_kf above count_cap");
+        if (X.row_cap < 1 || X.row_cap > SLAMIT_COVIS_MAX_ROW) return slamit_refuse(where, "row_cap outside [1, SLAMIT_COVIS_MAX_ROW]");
         if (!M.obs_ptr || !M.obs_kf || !M.mp_bad || !M.kf_mp_ptr || !M.kf_mp || !X.cw_kf || !X.cw_w || !X.cw_n || !X.ord_kf || !X.ord_w || !X.ord_n)
-            return cv_refuse(where, "null table");
+            return slamit_refuse(where, "null table");
         max_row_cap = std::max(max_row_cap, (int)X.row_cap);
     }
-    if (!R->d_kf || !R->d_first || !R->d_counts || !R->d_n_counted || !R->d_n_listed || !R->d_parent || !R->d_status) return cv_refuse(where, "null array");
+    if (!R->d_kf || !R->d_first || !R->d_counts || !R->d_n_counted || !R->d_n_listed || !R->d_parent || !R->d_status) return slamit_refuse(where, "null array");
     SLAMIT_USE_DEVICE(device);
     CvConnBatch B;
     memset(&B, 0, sizeof(B));
@@ -479,15 +463,15 @@ int slamit_update_connections_batch_dev(int device, const slamit_covis_batch_rec
 int slamit_keyframe_culling(int device, const slamit_map_index* map, const slamit_covis_index* covis, int32_t c, int32_t monocular,
                             uint8_t* verdict, int32_t* n_mps, int32_t* n_redundant, int32_t* n_cand, uint8_t* mp_turned_bad, int32_t* status) {
     const char* const where = "slamit_keyframe_culling";
-    if (!verdict || !n_mps || !n_redundant || !n_cand || !status || (map && map->n_mp > 0 && !mp_turned_bad)) return cv_refuse(where, "null array");
-    if (const char* what = cv_host_tables(map, covis, c)) return cv_refuse(where, what);
+    if (!verdict || !n_mps || !n_redundant || !n_cand || !status || (map && map->n_mp > 0 && !mp_turned_bad)) return slamit_refuse(where, "null array");
+    if (const char* what = cv_host_tables(map, covis, c)) return slamit_refuse(where, what);
     const int n_kf = map->n_kf, n_mp = map->n_mp, row_cap = covis->row_cap;
     const size_t n_obs = (size_t)map->obs_ptr[n_mp], n_kfmp = (size_t)map->kf_mp_ptr[n_kf], rows = (size_t)n_kf * row_cap;
-    if (!monocular && (!covis->kf_depth || !covis->kf_th_depth)) return cv_refuse(where, "kf_depth or kf_th_depth NULL with monocular == 0");
+    if (!monocular && (!covis->kf_depth || !covis->kf_th_depth)) return slamit_refuse(where, "kf_depth or kf_th_depth NULL with monocular == 0");
     if (!covis->kf_not_erase || (n_mp && !covis->mp_nobs) || (n_obs && (!covis->obs_octave || !covis->obs_weight)) || (n_kfmp && !covis->kf_octave))
-        return cv_refuse(where, "null table");
+        return slamit_refuse(where, "null table");
     const int n_c = std::min(std::max(covis->ord_n[c], 0), row_cap);
-    if (!cv_slots_ok(covis->ord_kf + (size_t)c * row_cap, (size_t)n_c, 0, n_kf)) return cv_refuse(where, "the candidates hold a keyframe slot outside [0, n_kf)");
+    if (!map_slots_ok(covis->ord_kf + (size_t)c * row_cap, (size_t)n_c, 0, n_kf)) return slamit_refuse(where, "the candidates hold a keyframe slot outside [0, n_kf)");
     SLAMIT_USE_DEVICE(device);
     CvCullBatch H;
     std::vector<SlamitInOut> io;
@@ -525,23 +509,23 @@ int slamit_keyframe_culling(int device, const slamit_map_index* map, const slami
 
 int slamit_keyframe_culling_batch_dev(int device, const slamit_culling_batch_rec* R, void* stream) {
     const char* const where = "slamit_keyframe_culling_batch_dev";
-    if (!R || R->nprob < 0 || R->n_maps < 0 || R->cand_cap < 0 || R->mp_cap < 0) return cv_refuse(where, "bad argument");
+    if (!R || R->nprob < 0 || R->n_maps < 0 || R->cand_cap < 0 || R->mp_cap < 0) return slamit_refuse(where, "bad argument");
     if (R->nprob == 0) return SLAMIT_OK;
-    if (R->nprob > 65535) return cv_refuse(where, "more than 65535 problems");
+    if (R->nprob > 65535) return slamit_refuse(where, "more than 65535 problems");
     if (R->n_maps < 1 || R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->maps || !R->covis)
-        return cv_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
-    if (R->cand_cap < 1 || R->cand_cap > SLAMIT_COVIS_MAX_ROW) return cv_refuse(where, "cand_cap outside [1, SLAMIT_COVIS_MAX_ROW]");
+        return slamit_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
+    if (R->cand_cap < 1 || R->cand_cap > SLAMIT_COVIS_MAX_ROW) return slamit_refuse(where, "cand_cap outside [1, SLAMIT_COVIS_MAX_ROW]");
     for (int m = 0; m < R->n_maps; ++m) {
         const slamit_map_index& M = R->maps[m];
         const slamit_covis_index& X = R->covis[m];
-        if (M.n_kf < 0 || M.n_mp < 0 || M.n_kf > SLAMIT_LOCAL_MAP_MAX_KF || M.n_mp > R->mp_cap) return cv_refuse(where, "a map with n_kf above SLAMIT_LOCAL_MAP_MAX_KF or n_mp above mp_cap");
-        if (X.row_cap < 1 || X.row_cap > R->cand_cap) return cv_refuse(where, "row_cap outside [1, cand_cap]");
+        if (M.n_kf < 0 || M.n_mp < 0 || M.n_kf > SLAMIT_LOCAL_MAP_MAX_KF || M.n_mp > R->mp_cap) return slamit_refuse(where, "a map with n_kf above SLAMIT_LOCAL_MAP_MAX_KF or n_mp above mp_cap");
+        if (X.row_cap < 1 || X.row_cap > R->cand_cap) return slamit_refuse(where, "row_cap outside [1, cand_cap]");
         if (!M.obs_ptr || !M.obs_kf || !M.mp_bad || !M.kf_mp_ptr || !M.kf_mp || !X.obs_octave || !X.obs_weight || !X.mp_nobs || !X.kf_octave ||
             !X.kf_not_erase || !X.ord_kf || !X.ord_n || (!X.kf_depth) != (!X.kf_th_depth))
-            return cv_refuse(where, "null table");
+            return slamit_refuse(where, "null table");
     }
     if (!R->d_prob_map || !R->d_kf || !R->d_monocular || !R->d_verdict || !R->d_n_mps || !R->d_n_redundant || !R->d_n_cand || !R->d_mp_turned_bad || !R->d_status)
-        return cv_refuse(where, "null array");
+        return slamit_refuse(where, "null array");
     SLAMIT_USE_DEVICE(device);
     CvCullBatch B;
     memset(&B, 0, sizeof(B));

@@ -20,7 +20,6 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -29,6 +28,7 @@
 #include "../../include/slamit.h"
 #include "slamit_internal.h"
 #include "wave_ops.h"
+#include "map_check.h"
 #include "kf_erase.h"
 
 static_assert(sizeof(KeOp) == sizeof(slamit_kf_op) && sizeof(KeOp) == 16 && offsetof(KeOp, kf) == offsetof(slamit_kf_op, kf) &&
@@ -119,12 +119,6 @@ static size_t ke_ws_layout(int n_maps, int cap, int kf_cap, int row_cap, int chi
     return off;
 }
 
-// memory written by some lanes of the wavefront, read by others
-__device__ __forceinline__ void ke_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // a map's working copies
 struct KeView {
     CvIndex G;
@@ -139,7 +133,6 @@ __device__ __forceinline__ KeView ke_view(const KeBatch& B, int m) {
     V.node_kf = B.node_kf + p0; V.node_next = B.node_next + p0; V.flags = B.flags + KE_NFLAGS * m; V.pool = B.pool;
     return V;
 }
-__device__ __forceinline__ int ke_list_n(const KeBatch& B, int m) { return min(max(B.n[m], 0), B.cap); }
 
 // ---- grid (ceil(kf_cap / 4), maps), 256 threads: a wavefront per keyframe ------------------------------------------------------
 __global__ __launch_bounds__(KE_NT) void ke_init_kernel(KeBatch B) {
@@ -196,10 +189,10 @@ __device__ __forceinline__ void ke_erase_connection_dev(const KeView& V, int j, 
         if (mask) pos = e0 + __ffsll((long long)mask) - 1;
     }
     if (pos < 0) return;                                                // j stays byte for byte
-    ke_wave_sync();                                                     // the keys of the neighbour before
+    wave_mem_sync();                                                     // the keys of the neighbour before
     for (int e = lane; e < n; e += 64)
         if (e != pos) keys[e - (e > pos)] = cv_key(cw[e], ckf[e]);
-    ke_wave_sync();
+    wave_mem_sync();
     const int n1 = n - 1;
     for (int e = lane; e < n1; e += 64) {
         ckf[e] = (int32_t)(uint32_t)keys[e]; cw[e] = (int32_t)(keys[e] >> 32);
@@ -221,7 +214,7 @@ __global__ __launch_bounds__(KE_WALK_NT) void ke_walk_kernel(KeBatch B) {
     const LmMap& M = B.maps[m];
     const KeIndex& X = B.X[m];
     const KeView V = ke_view(B, m);
-    const int n = ke_list_n(B, m), rc = X.row_cap, nwords = (M.n_kf + 31) / 32;
+    const int n = lm_list_n(B.n[m], B.cap), rc = X.row_cap, nwords = (M.n_kf + 31) / 32;
     const KeOp* const ops = B.ops + (size_t)m * B.cap;
     int32_t* const ost = B.ost + (size_t)m * B.cap;
     int32_t* const emit = B.emit + (size_t)m * B.cap;
@@ -325,7 +318,7 @@ __global__ __launch_bounds__(KE_WALK_NT) void ke_walk_kernel(KeBatch B) {
 // ---- grid (cap, maps), 64 threads: a wavefront per op -------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void ke_edit_count_kernel(KeBatch B) {
     const int m = blockIdx.y, i = blockIdx.x, lane = threadIdx.x;
-    if (i >= ke_list_n(B, m)) return;
+    if (i >= lm_list_n(B.n[m], B.cap)) return;
     const LmMap& M = B.maps[m];
     int cnt = 0;
     if (B.emit[(size_t)m * B.cap + i]) {
@@ -336,33 +329,19 @@ __global__ __launch_bounds__(64) void ke_edit_count_kernel(KeBatch B) {
     if (lane == 0) B.eoff[(size_t)m * (B.cap + 1) + i] = cnt;
 }
 
-// inclusive scan over the 1024 threads of the workgroup; total = the workgroup's sum.  Every thread calls it.
-__device__ __forceinline__ int ke_block_scan(int v, int& total) {
-    __shared__ int wave_total[KE_FIN_NT / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int incl = wave_inclusive_scan_i32(v);
-    if (lane == 63) wave_total[w] = incl;
-    __syncthreads();
-    int off = 0;
-    total = 0;
-    for (int u = 0; u < KE_FIN_NT / 64; ++u) { const int t = wave_total[u]; off += u < w ? t : 0; total += t; }
-    __syncthreads();
-    return off + incl;
-}
-
 // ---- grid (maps), 1024 threads ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(KE_FIN_NT) void ke_finish_kernel(KeBatch B) {
     const int m = blockIdx.x, tid = threadIdx.x;
     const LmMap& M = B.maps[m];
     const KeIndex& X = B.X[m];
     const KeView V = ke_view(B, m);
-    const int n = ke_list_n(B, m);
+    const int n = lm_list_n(B.n[m], B.cap);
     int32_t* const eoff = B.eoff + (size_t)m * (B.cap + 1);
     int32_t* const cptr = B.cptr + (size_t)m * ((size_t)B.kf_cap + 1);
     int n_edits;
     {
         const int v = tid < n ? eoff[tid] : 0;                          // n <= KE_MAX_OPS <= the workgroup
-        const int incl = ke_block_scan(v, n_edits);
+        const int incl = block_inclusive_scan_i32<KE_FIN_NT>(v, n_edits);
         if (tid < n) eoff[tid] = incl - v;
         if (tid == 0) eoff[n] = n_edits;
     }
@@ -373,7 +352,7 @@ __global__ __launch_bounds__(KE_FIN_NT) void ke_finish_kernel(KeBatch B) {
         if (j < M.n_kf)
             for (int node = V.head[j]; node != -1; node = V.node_next[node]) ++len;
         int total;
-        const int incl = ke_block_scan(len, total);
+        const int incl = block_inclusive_scan_i32<KE_FIN_NT>(len, total);
         if (j < M.n_kf) cptr[j] = need + incl - len;
         need += total;
     }
@@ -393,7 +372,7 @@ __global__ __launch_bounds__(KE_NT) void ke_commit_kernel(KeBatch B) {
     const KeIndex& X = B.X[m];
     const KeView V = ke_view(B, m);
     if (!V.flags[KE_F_COMMIT]) return;
-    if (q < ke_list_n(B, m)) {
+    if (q < lm_list_n(B.n[m], B.cap)) {
         if (lane == 0) B.op_status[(size_t)m * B.cap + q] = B.ost[(size_t)m * B.cap + q];
         if (B.emit[(size_t)m * B.cap + q]) {
             const int k = B.ops[(size_t)m * B.cap + q].kf, e1 = M.kf_mp_ptr[k + 1];
@@ -437,59 +416,35 @@ static hipError_t ke_launch(const KeBatch& B, size_t clear_bytes, hipStream_t st
     return hipGetLastError();
 }
 
-static int ke_refuse(const char* where, const char* what, int code = SLAMIT_ERR_ARG) {
-    static thread_local char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", where, what);
-    return slamit_fail(code, msg);
-}
-static bool ke_csr_ok(const int32_t* ptr, int rows) {
-    if (ptr[0] != 0) return false;
-    for (int r = 0; r < rows; ++r)
-        if (ptr[r + 1] < ptr[r]) return false;
-    return true;
-}
-
-extern "C" {
+extern "C" {   // what the host forms check before anything is launched: map_check.h and their own arguments
 
 int slamit_kf_erase_apply(int device, const slamit_map_index* map, const slamit_tree_index* X, int32_t n, const slamit_kf_op* ops, int32_t* op_status,
                           int32_t edit_cap, slamit_map_edit* edits, int32_t* n_edits_out, int32_t* n_child_out, int32_t* status) {
     const char* const where = "slamit_kf_erase_apply";
     if (n < 0 || edit_cap < 0 || !n_edits_out || !n_child_out || !status || (n && (!ops || !op_status)) || (edit_cap && !edits))
-        return ke_refuse(where, "null array or negative count");
-    if (n > SLAMIT_KF_ERASE_MAX_OPS) return ke_refuse(where, "more than SLAMIT_KF_ERASE_MAX_OPS ops", SLAMIT_ERR_CAPACITY);
-    if (!map || !X) return ke_refuse(where, "null table");
-    if (map->n_kf < 0 || map->n_mp < 0 || map->n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return ke_refuse(where, "n_kf outside [0, SLAMIT_LOCAL_MAP_MAX_KF] or negative n_mp");
-    if (X->row_cap < 1 || X->row_cap > SLAMIT_COVIS_MAX_ROW) return ke_refuse(where, "row_cap outside [1, SLAMIT_COVIS_MAX_ROW]");
-    if (X->child_cap_out < 0) return ke_refuse(where, "negative child_cap_out");
+        return slamit_refuse(where, "null array or negative count");
+    if (n > SLAMIT_KF_ERASE_MAX_OPS) return slamit_refuse(where, "more than SLAMIT_KF_ERASE_MAX_OPS ops", SLAMIT_ERR_CAPACITY);
+    if (!map || !X) return slamit_refuse(where, "null table");
+    if (const char* bad = map_sizes_error(map)) return slamit_refuse(where, bad);
+    if (X->row_cap < 1 || X->row_cap > SLAMIT_COVIS_MAX_ROW) return slamit_refuse(where, "row_cap outside [1, SLAMIT_COVIS_MAX_ROW]");
+    if (X->child_cap_out < 0) return slamit_refuse(where, "negative child_cap_out");
     const int n_kf = map->n_kf, n_mp = map->n_mp, rc = X->row_cap;
-    if (X->origin_kf < -1 || X->origin_kf >= n_kf) return ke_refuse(where, "origin_kf holds a keyframe slot outside [-1, n_kf)");
-    if (!map->kf_mp_ptr || !map->kf_child_ptr || !X->child_ptr_out) return ke_refuse(where, "null table");
-    if (!ke_csr_ok(map->kf_mp_ptr, n_kf) || !ke_csr_ok(map->kf_child_ptr, n_kf)) return ke_refuse(where, "a CSR pointer array does not ascend from 0");
+    if (X->origin_kf < -1 || X->origin_kf >= n_kf) return slamit_refuse(where, "origin_kf holds a keyframe slot outside [-1, n_kf)");
+    if (!map->kf_mp_ptr || !map->kf_child_ptr || !X->child_ptr_out) return slamit_refuse(where, "null table");
+    if (!map_csr_ok(map->kf_mp_ptr, n_kf) || !map_csr_ok(map->kf_child_ptr, n_kf)) return slamit_refuse(where, "a CSR pointer array does not ascend from 0");
     const size_t n_kfmp = (size_t)map->kf_mp_ptr[n_kf], n_child = (size_t)map->kf_child_ptr[n_kf], cap_out = (size_t)X->child_cap_out, nk = (size_t)n_kf;
     if ((n_kfmp && !map->kf_mp) || (n_child && !map->kf_child) || (cap_out && !X->child_out) ||
         (n_kf && (!X->kf_not_erase || !X->kf_bad || !X->kf_parent || !X->kf_to_be_erased || !X->cw_kf || !X->cw_w || !X->cw_n || !X->ord_kf || !X->ord_w || !X->ord_n)))
-        return ke_refuse(where, "null table");
-    for (size_t e = 0; e < n_kfmp; ++e)
-        if (map->kf_mp[e] < -1 || map->kf_mp[e] >= n_mp) return ke_refuse(where, "kf_mp holds a point slot outside [-1, n_mp)");
-    for (int j = 0; j < n_kf; ++j) {
-        if (X->kf_parent[j] < -1 || X->kf_parent[j] >= n_kf) return ke_refuse(where, "kf_parent holds a keyframe slot outside [-1, n_kf)");
-        if (X->cw_n[j] < 0 || X->cw_n[j] > rc || X->ord_n[j] < 0 || X->ord_n[j] > rc) return ke_refuse(where, "a graph row's count outside [0, row_cap]");
-        for (int e = 0; e < X->cw_n[j]; ++e) {
-            const int o = X->cw_kf[(size_t)j * rc + e];
-            if (o < 0 || o >= n_kf || o == j) return ke_refuse(where, "cw_kf holds a keyframe slot outside [0, n_kf) or a keyframe's own");
-        }
-        for (int e = 0; e < X->ord_n[j]; ++e)
-            if (X->ord_kf[(size_t)j * rc + e] < 0 || X->ord_kf[(size_t)j * rc + e] >= n_kf) return ke_refuse(where, "ord_kf holds a keyframe slot outside [0, n_kf)");
-        for (int e = map->kf_child_ptr[j]; e < map->kf_child_ptr[j + 1]; ++e) {
-            if (map->kf_child[e] < 0 || map->kf_child[e] >= n_kf) return ke_refuse(where, "kf_child holds a keyframe slot outside [0, n_kf)");
-            if (e > map->kf_child_ptr[j] && map->kf_child[e - 1] >= map->kf_child[e]) return ke_refuse(where, "a children row does not ascend");
-        }
-    }
+        return slamit_refuse(where, "null table");
+    if (!map_slots_ok(map->kf_mp, n_kfmp, -1, n_mp)) return slamit_refuse(where, "kf_mp holds a point slot outside [-1, n_mp)");
+    if (!map_slots_ok(X->kf_parent, nk, -1, n_kf)) return slamit_refuse(where, "kf_parent holds a keyframe slot outside [-1, n_kf)");
+    if (const char* bad = map_graph_rows_error(n_kf, rc, X->cw_kf, X->cw_n, X->ord_kf, X->ord_n)) return slamit_refuse(where, bad);
+    if (const char* bad = map_children_error(map)) return slamit_refuse(where, bad);
     for (int i = 0; i < n; ++i) {
         const slamit_kf_op& e = ops[i];
-        if (e.kind != SLAMIT_KF_ERASE_SET_PARENT && e.kind != SLAMIT_KF_ERASE_SET_BAD) return ke_refuse(where, "an op's kind outside 1..2");
+        if (e.kind != SLAMIT_KF_ERASE_SET_PARENT && e.kind != SLAMIT_KF_ERASE_SET_BAD) return slamit_refuse(where, "an op's kind outside 1..2");
         if (e.kf < 0 || e.kf >= n_kf || (e.kind == SLAMIT_KF_ERASE_SET_PARENT && (e.parent < 0 || e.parent >= n_kf)))
-            return ke_refuse(where, "ops holds a keyframe slot outside [0, n_kf)");
+            return slamit_refuse(where, "ops holds a keyframe slot outside [0, n_kf)");
     }
     SLAMIT_USE_DEVICE(device);
     KeBatch H;
@@ -540,27 +495,27 @@ size_t slamit_kf_erase_workspace(int n_maps, int cap, int kf_cap, int row_cap, i
 
 int slamit_kf_erase_batch_dev(int device, const slamit_kf_erase_batch_rec* R, void* stream) {
     const char* const where = "slamit_kf_erase_batch_dev";
-    if (!R || R->n_maps < 0 || R->cap < 0 || R->kf_cap < 0 || R->child_cap < 0 || R->edit_cap < 0) return ke_refuse(where, "bad argument");
+    if (!R || R->n_maps < 0 || R->cap < 0 || R->kf_cap < 0 || R->child_cap < 0 || R->edit_cap < 0) return slamit_refuse(where, "bad argument");
     if (R->n_maps == 0) return SLAMIT_OK;
-    if (R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->maps || !R->tree) return ke_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
-    if (R->cap > SLAMIT_KF_ERASE_MAX_OPS) return ke_refuse(where, "cap above SLAMIT_KF_ERASE_MAX_OPS", SLAMIT_ERR_CAPACITY);
-    if (R->row_cap < 1 || R->row_cap > SLAMIT_COVIS_MAX_ROW) return ke_refuse(where, "row_cap outside [1, SLAMIT_COVIS_MAX_ROW]");
-    if (R->kf_cap > SLAMIT_LOCAL_MAP_MAX_KF) return ke_refuse(where, "kf_cap above SLAMIT_LOCAL_MAP_MAX_KF", SLAMIT_ERR_CAPACITY);
+    if (R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->maps || !R->tree) return slamit_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
+    if (R->cap > SLAMIT_KF_ERASE_MAX_OPS) return slamit_refuse(where, "cap above SLAMIT_KF_ERASE_MAX_OPS", SLAMIT_ERR_CAPACITY);
+    if (R->row_cap < 1 || R->row_cap > SLAMIT_COVIS_MAX_ROW) return slamit_refuse(where, "row_cap outside [1, SLAMIT_COVIS_MAX_ROW]");
+    if (R->kf_cap > SLAMIT_LOCAL_MAP_MAX_KF) return slamit_refuse(where, "kf_cap above SLAMIT_LOCAL_MAP_MAX_KF", SLAMIT_ERR_CAPACITY);
     for (int m = 0; m < R->n_maps; ++m) {
         const slamit_map_index& M = R->maps[m];
         const slamit_tree_index& X = R->tree[m];
-        if (M.n_kf < 0 || M.n_mp < 0 || M.n_kf > R->kf_cap) return ke_refuse(where, "a map with n_kf outside [0, kf_cap] or negative n_mp");
-        if (X.row_cap < 1 || X.row_cap > R->row_cap) return ke_refuse(where, "a map with row_cap outside [1, the batch's row_cap]");
-        if (X.child_cap_out < 0) return ke_refuse(where, "negative child_cap_out");
+        if (M.n_kf < 0 || M.n_mp < 0 || M.n_kf > R->kf_cap) return slamit_refuse(where, "a map with n_kf outside [0, kf_cap] or negative n_mp");
+        if (X.row_cap < 1 || X.row_cap > R->row_cap) return slamit_refuse(where, "a map with row_cap outside [1, the batch's row_cap]");
+        if (X.child_cap_out < 0) return slamit_refuse(where, "negative child_cap_out");
         if (!M.kf_mp_ptr || !M.kf_mp || !M.kf_child_ptr || !M.kf_child || !X.kf_not_erase || !X.kf_bad || !X.kf_parent || !X.kf_to_be_erased || !X.cw_kf || !X.cw_w ||
             !X.cw_n || !X.ord_kf || !X.ord_w || !X.ord_n || !X.child_ptr_out || !X.child_out)
-            return ke_refuse(where, "null table");
+            return slamit_refuse(where, "null table");
     }
     if (!R->d_n || !R->d_n_edits_out || !R->d_n_child_out || !R->d_status || (R->cap && (!R->d_ops || !R->d_op_status)) || (R->edit_cap && !R->d_edits))
-        return ke_refuse(where, "null array");
+        return slamit_refuse(where, "null array");
     size_t clear_bytes = 0;
     const size_t need = ke_ws_layout(R->n_maps, R->cap, R->kf_cap, R->row_cap, R->child_cap, nullptr, nullptr, &clear_bytes);
-    if (!R->d_workspace || R->workspace_bytes < need || ((uintptr_t)R->d_workspace & 7)) return ke_refuse(where, "workspace missing, misaligned or below slamit_kf_erase_workspace()");
+    if (!R->d_workspace || R->workspace_bytes < need || ((uintptr_t)R->d_workspace & 7)) return slamit_refuse(where, "workspace missing, misaligned or below slamit_kf_erase_workspace()");
     SLAMIT_USE_DEVICE(device);
     KeBatch B;
     memset(&B, 0, sizeof(B));

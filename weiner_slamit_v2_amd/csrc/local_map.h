@@ -64,6 +64,7 @@ struct LmMap {
 
 LM_HD bool lm_kf_ok(const LmMap& M, int k) { return (unsigned)k < (unsigned)M.n_kf; }
 LM_HD bool lm_mp_ok(const LmMap& M, int p) { return (unsigned)p < (unsigned)M.n_mp; }
+LM_HD int lm_list_n(int n, int cap) { n = n > 0 ? n : 0; return n < cap ? n : cap; }   // a list's length as the device reads it: n clamped to [0, cap]
 LM_HD uint32_t lm_key(int list_pos, int kp) { return ((uint32_t)list_pos << 16) | (uint32_t)kp; }
 
 // mnTrackReferenceForFrame == mCurrentFrame.mnId of the keyframes, as a bit per slot

@@ -26,6 +26,7 @@
 #include "../../include/slamit.h"
 #include "slamit_internal.h"
 #include "wave_ops.h"
+#include "map_check.h"
 #include "local_map.h"
 
 static_assert(sizeof(LmMap) == sizeof(slamit_map_index) && offsetof(LmMap, kf_mp_ptr) == offsetof(slamit_map_index, kf_mp_ptr) &&
@@ -301,20 +302,7 @@ static hipError_t lm_launch_points(const LmBatch& B, hipStream_t st) {
     return hipGetLastError();
 }
 
-// ---- what the host forms check before anything is launched -------------------------------------------------------------------
-static bool lm_slots_ok(const int32_t* v, size_t count, int lo, int n) {
-    for (size_t i = 0; i < count; ++i)
-        if (v[i] < lo || v[i] >= n) return false;
-    return true;
-}
-static bool lm_csr_ok(const int32_t* ptr, int rows) {
-    if (ptr[0] != 0) return false;
-    for (int r = 0; r < rows; ++r)
-        if (ptr[r + 1] < ptr[r]) return false;
-    return true;
-}
-
-extern "C" {
+extern "C" {   // what the host forms check before anything is launched: map_check.h and their own arguments
 
 size_t slamit_local_map_workspace(int nframes, int mp_cap, int kf_cap) {
     if (nframes <= 0 || mp_cap < 0 || kf_cap < 0) return 0;
@@ -326,23 +314,22 @@ int slamit_local_keyframes(int device, const slamit_map_index* map, int32_t n, i
                            int32_t* local_kf, int32_t* n_local_kf, int32_t* ref_kf, int32_t* status) {
     const char* const where = "slamit_local_keyframes";
     if (!map || n < 0 || !votes || !local_kf || !n_local_kf || !ref_kf || !status || (n && !frame_mp))
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_keyframes: null array or negative count");
-    if (n > SLAMIT_FRAME_MAX_KP) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_keyframes: more than SLAMIT_FRAME_MAX_KP keypoints");
-    if (map->n_kf < 0 || map->n_mp < 0 || map->n_kf > SLAMIT_LOCAL_MAP_MAX_KF)
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_keyframes: n_kf outside [0, SLAMIT_LOCAL_MAP_MAX_KF] or negative n_mp");
+        return slamit_refuse(where, "null array or negative count");
+    if (n > SLAMIT_FRAME_MAX_KP) return slamit_refuse(where, "more than SLAMIT_FRAME_MAX_KP keypoints");
+    if (const char* bad = map_sizes_error(map)) return slamit_refuse(where, bad);
     if (kf_cap < SLAMIT_LOCAL_MAP_MIN_KF_CAP || kf_cap > SLAMIT_LOCAL_MAP_MAX_KF)
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_keyframes: kf_cap outside [SLAMIT_LOCAL_MAP_MIN_KF_CAP, SLAMIT_LOCAL_MAP_MAX_KF]");
+        return slamit_refuse(where, "kf_cap outside [SLAMIT_LOCAL_MAP_MIN_KF_CAP, SLAMIT_LOCAL_MAP_MAX_KF]");
     if (!map->obs_ptr || !map->kf_child_ptr || (map->n_mp && !map->mp_bad) || (map->n_kf && (!map->kf_bad || !map->kf_best || !map->kf_parent)))
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_keyframes: null table");
+        return slamit_refuse(where, "null table");
     const int n_kf = map->n_kf, n_mp = map->n_mp;
-    if (!lm_csr_ok(map->obs_ptr, n_mp) || !lm_csr_ok(map->kf_child_ptr, n_kf))
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_keyframes: a CSR pointer array does not ascend from 0");
+    if (!map_csr_ok(map->obs_ptr, n_mp) || !map_csr_ok(map->kf_child_ptr, n_kf))
+        return slamit_refuse(where, "a CSR pointer array does not ascend from 0");
     const size_t n_obs = (size_t)map->obs_ptr[n_mp], n_child = (size_t)map->kf_child_ptr[n_kf];
-    if ((n_obs && !map->obs_kf) || (n_child && !map->kf_child)) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_keyframes: null table");
-    if (!lm_slots_ok(frame_mp, (size_t)n, -1, n_mp)) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_keyframes: frame_mp holds a slot outside [-1, n_mp)");
-    if (!lm_slots_ok(map->obs_kf, n_obs, 0, n_kf) || !lm_slots_ok(map->kf_child, n_child, 0, n_kf) ||
-        !lm_slots_ok(map->kf_best, (size_t)n_kf * LM_BEST, -1, n_kf) || !lm_slots_ok(map->kf_parent, (size_t)n_kf, -1, n_kf))
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_keyframes: a table holds a keyframe slot outside [0, n_kf)");
+    if ((n_obs && !map->obs_kf) || (n_child && !map->kf_child)) return slamit_refuse(where, "null table");
+    if (!map_slots_ok(frame_mp, (size_t)n, -1, n_mp)) return slamit_refuse(where, "frame_mp holds a slot outside [-1, n_mp)");
+    if (!map_slots_ok(map->obs_kf, n_obs, 0, n_kf) || !map_slots_ok(map->kf_child, n_child, 0, n_kf) ||
+        !map_slots_ok(map->kf_best, (size_t)n_kf * LM_BEST, -1, n_kf) || !map_slots_ok(map->kf_parent, (size_t)n_kf, -1, n_kf))
+        return slamit_refuse(where, "a table holds a keyframe slot outside [0, n_kf)");
     SLAMIT_USE_DEVICE(device);
     LmBatch H;   // the bound record, for the launches
     const int32_t *in_mp = nullptr, *in_kf = nullptr, *in_nkf = nullptr, *in_ref = nullptr;
@@ -386,23 +373,22 @@ int slamit_local_points(int device, const slamit_map_index* map, int32_t n, cons
     const char* const where = "slamit_local_points";
     if (!map || n < 0 || n_seen < 0 || n_local_kf < 0 || q_cap < 0 || !n_local_mp || !status || (n && !frame_mp) || (n_seen && !frame_seen) ||
         (n_local_kf && !local_kf) || (q_cap && (!local_mp || !skip)))
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_points: null array or negative count");
-    if (n > SLAMIT_FRAME_MAX_KP) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_points: more than SLAMIT_FRAME_MAX_KP keypoints");
-    if (q_cap > SLAMIT_FRUSTUM_MAX_N) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_points: q_cap above SLAMIT_FRUSTUM_MAX_N");
-    if (n_local_kf > SLAMIT_LOCAL_MAP_MAX_KF) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_points: more than SLAMIT_LOCAL_MAP_MAX_KF local keyframes");
-    if (map->n_kf < 0 || map->n_mp < 0 || map->n_kf > SLAMIT_LOCAL_MAP_MAX_KF)
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_points: n_kf outside [0, SLAMIT_LOCAL_MAP_MAX_KF] or negative n_mp");
-    if (!map->kf_mp_ptr || (map->n_mp && !map->mp_bad)) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_points: null table");
+        return slamit_refuse(where, "null array or negative count");
+    if (n > SLAMIT_FRAME_MAX_KP) return slamit_refuse(where, "more than SLAMIT_FRAME_MAX_KP keypoints");
+    if (q_cap > SLAMIT_FRUSTUM_MAX_N) return slamit_refuse(where, "q_cap above SLAMIT_FRUSTUM_MAX_N");
+    if (n_local_kf > SLAMIT_LOCAL_MAP_MAX_KF) return slamit_refuse(where, "more than SLAMIT_LOCAL_MAP_MAX_KF local keyframes");
+    if (const char* bad = map_sizes_error(map)) return slamit_refuse(where, bad);
+    if (!map->kf_mp_ptr || (map->n_mp && !map->mp_bad)) return slamit_refuse(where, "null table");
     const int n_kf = map->n_kf, n_mp = map->n_mp;
-    if (!lm_csr_ok(map->kf_mp_ptr, n_kf)) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_points: kf_mp_ptr does not ascend from 0");
+    if (!map_csr_ok(map->kf_mp_ptr, n_kf)) return slamit_refuse(where, "kf_mp_ptr does not ascend from 0");
     const size_t n_kfmp = (size_t)map->kf_mp_ptr[n_kf];
-    if (n_kfmp && !map->kf_mp) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_points: null table");
+    if (n_kfmp && !map->kf_mp) return slamit_refuse(where, "null table");
     for (int k = 0; k < n_kf; ++k)
         if (map->kf_mp_ptr[k + 1] - map->kf_mp_ptr[k] > SLAMIT_LOCAL_MAP_MAX_ROW)
-            return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_points: a keyframe with more than SLAMIT_LOCAL_MAP_MAX_ROW keypoints");
-    if (!lm_slots_ok(frame_mp, (size_t)n, -1, n_mp) || !lm_slots_ok(frame_seen, (size_t)n_seen, -1, n_mp) || !lm_slots_ok(map->kf_mp, n_kfmp, -1, n_mp))
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_points: a point slot outside [-1, n_mp)");
-    if (!lm_slots_ok(local_kf, (size_t)n_local_kf, 0, n_kf)) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_points: local_kf holds a slot outside [0, n_kf)");
+            return slamit_refuse(where, "a keyframe with more than SLAMIT_LOCAL_MAP_MAX_ROW keypoints");
+    if (!map_slots_ok(frame_mp, (size_t)n, -1, n_mp) || !map_slots_ok(frame_seen, (size_t)n_seen, -1, n_mp) || !map_slots_ok(map->kf_mp, n_kfmp, -1, n_mp))
+        return slamit_refuse(where, "a point slot outside [-1, n_mp)");
+    if (!map_slots_ok(local_kf, (size_t)n_local_kf, 0, n_kf)) return slamit_refuse(where, "local_kf holds a slot outside [0, n_kf)");
     SLAMIT_USE_DEVICE(device);
     LmBatch H;
     const int32_t* in_mp = nullptr;
@@ -442,31 +428,31 @@ int slamit_local_points(int device, const slamit_map_index* map, int32_t n, cons
 int slamit_local_map_batch_dev(int device, const slamit_local_map_batch_rec* R, void* stream) {
     const char* const where = "slamit_local_map_batch_dev";
     if (!R || R->nframes < 0 || R->n_maps < 0 || R->kp_cap < 0 || R->seen_cap < 0 || R->q_cap < 0 || R->vote_cap < 0 || R->mp_cap < 0)
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_map_batch_dev: bad argument");
+        return slamit_refuse(where, "bad argument");
     if (R->nframes == 0) return SLAMIT_OK;
-    if (R->nframes > 65535) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_map_batch_dev: more than 65535 frames");
+    if (R->nframes > 65535) return slamit_refuse(where, "more than 65535 frames");
     if (R->n_maps < 1 || R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->maps)
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_map_batch_dev: n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
-    if (R->kp_cap > SLAMIT_FRAME_MAX_KP) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_map_batch_dev: kp_cap above SLAMIT_FRAME_MAX_KP");
-    if (R->q_cap > SLAMIT_FRUSTUM_MAX_N) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_map_batch_dev: q_cap above SLAMIT_FRUSTUM_MAX_N");
+        return slamit_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
+    if (R->kp_cap > SLAMIT_FRAME_MAX_KP) return slamit_refuse(where, "kp_cap above SLAMIT_FRAME_MAX_KP");
+    if (R->q_cap > SLAMIT_FRUSTUM_MAX_N) return slamit_refuse(where, "q_cap above SLAMIT_FRUSTUM_MAX_N");
     if (R->kf_cap < SLAMIT_LOCAL_MAP_MIN_KF_CAP || R->kf_cap > SLAMIT_LOCAL_MAP_MAX_KF)
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_map_batch_dev: kf_cap outside [SLAMIT_LOCAL_MAP_MIN_KF_CAP, SLAMIT_LOCAL_MAP_MAX_KF]");
-    if (R->vote_cap > SLAMIT_LOCAL_MAP_MAX_KF) return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_map_batch_dev: vote_cap above SLAMIT_LOCAL_MAP_MAX_KF");
+        return slamit_refuse(where, "kf_cap outside [SLAMIT_LOCAL_MAP_MIN_KF_CAP, SLAMIT_LOCAL_MAP_MAX_KF]");
+    if (R->vote_cap > SLAMIT_LOCAL_MAP_MAX_KF) return slamit_refuse(where, "vote_cap above SLAMIT_LOCAL_MAP_MAX_KF");
     for (int i = 0; i < R->n_maps; ++i) {
         const slamit_map_index& M = R->maps[i];
         if (M.n_kf < 0 || M.n_mp < 0 || M.n_kf > R->vote_cap || M.n_mp > R->mp_cap)
-            return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_map_batch_dev: a map with n_kf above vote_cap or n_mp above mp_cap");
+            return slamit_refuse(where, "a map with n_kf above vote_cap or n_mp above mp_cap");
         if (!M.obs_ptr || !M.obs_kf || !M.mp_bad || !M.kf_bad || !M.kf_mp_ptr || !M.kf_mp || !M.kf_best || !M.kf_child_ptr || !M.kf_child ||
             !M.kf_parent || !M.mp_pos || !M.mp_normal || !M.mp_max_dist || !M.mp_min_dist)
-            return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_map_batch_dev: null table");
+            return slamit_refuse(where, "null table");
     }
     if (!R->d_frame_map || !R->d_n || !R->d_frame_mp || !R->d_votes || !R->d_local_kf || !R->d_n_local_kf || !R->d_ref_kf || !R->d_local_mp ||
         !R->d_n_local_mp || !R->d_pos || !R->d_normal || !R->d_max_dist || !R->d_min_dist || !R->d_skip || !R->d_m || !R->d_status ||
         (!R->d_n_seen) != (!R->d_frame_seen))
-        return slamit_fail(SLAMIT_ERR_ARG, "slamit_local_map_batch_dev: null array");
+        return slamit_refuse(where, "null array");
     const size_t need = slamit_local_map_workspace(R->nframes, R->mp_cap, R->kf_cap);
     if (!R->d_workspace || R->workspace_bytes < need)
-        return slamit_fail(SLAMIT_ERR_CAPACITY, "slamit_local_map_batch_dev: workspace smaller than slamit_local_map_workspace()");
+        return slamit_refuse(where, "workspace smaller than slamit_local_map_workspace()", SLAMIT_ERR_CAPACITY);
     SLAMIT_USE_DEVICE(device);
     LmBatch B;
     memset(&B, 0, sizeof(B));

@@ -22,7 +22,6 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -31,6 +30,7 @@
 #include "../../include/slamit.h"
 #include "slamit_internal.h"
 #include "wave_ops.h"
+#include "map_check.h"
 #include "map_edit.h"
 
 static_assert(sizeof(MeEdit) == sizeof(slamit_map_edit) && offsetof(MeEdit, mp) == offsetof(slamit_map_edit, mp) && offsetof(MeEdit, idx) == offsetof(slamit_map_edit, idx) &&
@@ -100,60 +100,29 @@ static size_t me_ws_layout(int n_maps, int cap, int mp_cap, int kfmp_cap, unsign
     return off;
 }
 
-// LDS written by some lanes of the wavefront, read by others
-__device__ __forceinline__ void me_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ int me_list_n(const MeBatch& B, int m) { return min(max(B.n[m], 0), B.cap); }
-
 // ---- grid (ceil(cap / 256), maps) ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(ME_NT) void me_hist_kernel(MeBatch B) {
     const int m = blockIdx.y, i = blockIdx.x * ME_NT + (int)threadIdx.x;
-    if (i >= me_list_n(B, m)) return;
+    if (i >= lm_list_n(B.n[m], B.cap)) return;
     const LmMap& M = B.maps[m];
     const int p = B.edits[(size_t)m * B.cap + i].mp;
     if (lm_mp_ok(M, p)) atomicAdd(&B.cnt[(size_t)m * (B.mp_cap + 1) + p], 1);
     else atomicOr(&B.flags[4 * m], ME_BAD_SLOT);
 }
 
-// ---- the device scan ------------------------------------------------------------------------------------------------------------
-// inclusive scan over the 256 threads of the workgroup; total = the workgroup's sum.  Every thread calls it.
-__device__ __forceinline__ int me_block_scan(int v, int& total) {
-    __shared__ int wave_total[ME_NT / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int incl = wave_inclusive_scan_i32(v);
-    if (lane == 63) wave_total[w] = incl;
-    __syncthreads();
-    int off = 0;
-    total = 0;
-    for (int u = 0; u < ME_NT / 64; ++u) { const int t = wave_total[u]; off += u < w ? t : 0; total += t; }
-    __syncthreads();
-    return off + incl;
-}
+// ---- the device scan (block_inclusive_scan_i32 and block_scan_parts_i32 of wave_ops.h) ------------------------------------------
 // grid (nparts, maps, arrays): the sum of block x of array z (a, b: rows S apart) over the first n_mp entries
 __global__ __launch_bounds__(ME_NT) void me_scan_sum_kernel(MeBatch B, const int32_t* a, const int32_t* b) {
     const int m = blockIdx.y, i = blockIdx.x * ME_NT + (int)threadIdx.x;
     const size_t S = (size_t)B.mp_cap + 1;
     const int32_t* const src = (blockIdx.z ? b : a) + m * S;
     int total;
-    me_block_scan(i < B.maps[m].n_mp ? src[i] : 0, total);
+    block_inclusive_scan_i32<ME_NT>(i < B.maps[m].n_mp ? src[i] : 0, total);
     if (threadIdx.x == 0) B.parts[((size_t)m * 2 + blockIdx.z) * (B.nparts + 1) + blockIdx.x] = total;
 }
 // grid (maps, arrays): the sums scanned in place by one workgroup, the total at [nparts]
 __global__ __launch_bounds__(ME_NT) void me_scan_parts_kernel(MeBatch B) {
-    int32_t* const parts = B.parts + ((size_t)blockIdx.x * 2 + blockIdx.y) * (B.nparts + 1);
-    int base = 0;
-    for (int c0 = 0; c0 < B.nparts; c0 += ME_NT) {   // every thread walks the same rounds
-        const int t = c0 + (int)threadIdx.x;
-        const int v = t < B.nparts ? parts[t] : 0;
-        int total;
-        const int incl = me_block_scan(v, total);
-        if (t < B.nparts) parts[t] = base + incl - v;
-        base += total;
-    }
-    if (threadIdx.x == 0) parts[B.nparts] = base;
+    block_scan_parts_i32<ME_NT>(B.parts + ((size_t)blockIdx.x * 2 + blockIdx.y) * (B.nparts + 1), B.nparts);
 }
 // grid (nparts, maps, arrays): out[i] = what lies before entry i, out[n_mp] = the total
 __global__ __launch_bounds__(ME_NT) void me_scan_add_kernel(MeBatch B, const int32_t* a, const int32_t* b, int32_t* out_a, int32_t* out_b) {
@@ -164,7 +133,7 @@ __global__ __launch_bounds__(ME_NT) void me_scan_add_kernel(MeBatch B, const int
     const int32_t* const parts = B.parts + ((size_t)m * 2 + blockIdx.z) * (B.nparts + 1);
     const int v = i < n ? src[i] : 0;
     int total;
-    const int incl = me_block_scan(v, total);
+    const int incl = block_inclusive_scan_i32<ME_NT>(v, total);
     if (i < n) out[i] = parts[blockIdx.x] + incl - v;
     else if (i == n) out[i] = parts[B.nparts];     // n <= mp_cap: inside the row
 }
@@ -174,7 +143,7 @@ __global__ __launch_bounds__(ME_NT) void me_scatter_kernel(MeBatch B) {
     const int m = blockIdx.y, i = blockIdx.x * ME_NT + (int)threadIdx.x;
     const LmMap& M = B.maps[m];
     const size_t S = (size_t)B.mp_cap + 1;
-    if (i < me_list_n(B, m)) {
+    if (i < lm_list_n(B.n[m], B.cap)) {
         const int p = B.edits[(size_t)m * B.cap + i].mp;
         if (lm_mp_ok(M, p)) {
             const int at = B.bstart[m * S + p] + atomicAdd(&B.cursor[m * S + p], 1);   // < bstart[p + 1] <= the list's length <= cap
@@ -208,7 +177,7 @@ struct MeRowDev {
         if (lane == 0) { kf[n] = k; idx[n] = i; octave[n] = o; weight[n] = w; }
         if (lane == (n & 63)) alive |= 1u << (n >> 6);
         ++n;
-        me_wave_sync();
+        wave_mem_sync();
     }
     __device__ __forceinline__ void kill(int pos) {
         if (lane == (pos & 63)) alive &= ~(1u << (pos >> 6));
@@ -294,14 +263,14 @@ __global__ __launch_bounds__(64) void me_apply_kernel(MeBatch B) {
         }
     }
     if (lane < ne) raw[lane] = bucket[j + lane];                        // ne <= 64 entries from bstart[p] = j
-    me_wave_sync();
+    wave_mem_sync();
     if (lane < ne) {
         const int li = raw[lane];
         int rank = 0;                                                   // list indices are distinct
         for (int t = 0; t < ne; ++t) rank += raw[t] < li;
         order[rank] = li;
     }
-    me_wave_sync();
+    wave_mem_sync();
     MeState s = {len0, X.mp_nobs[p], X.mp_bad[p], X.mp_ref_kf[p], 0, 0};
     if (!WRITE) {
         MeEmitNoneDev none;
@@ -356,7 +325,7 @@ __global__ __launch_bounds__(ME_NT) void me_copy_kernel(MeBatch B) {
     optr[w][lane] = M.obs_ptr[min(p0 + lane, n_mp)]; nptr[w][lane] = newptr[min(p0 + lane, n_mp)];
     if (lane == 63) { optr[w][64] = M.obs_ptr[min(p0 + 64, n_mp)]; nptr[w][64] = newptr[min(p0 + 64, n_mp)]; }
     skip[w][lane] = sk;
-    me_wave_sync();
+    wave_mem_sync();
     const int e1 = optr[w][64];
     for (int e = optr[w][0] + lane; e < e1; e += 64) {
         int lo = 0, hi = 63;                                            // the row q with optr[q] <= e < optr[q + 1]
@@ -401,56 +370,38 @@ static hipError_t me_launch(const MeBatch& B, size_t clear_bytes, hipStream_t st
     return hipGetLastError();
 }
 
-static int me_refuse(const char* where, const char* what, int code = SLAMIT_ERR_ARG) {
-    static thread_local char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", where, what);
-    return slamit_fail(code, msg);
-}
-static bool me_csr_ok(const int32_t* ptr, int rows) {
-    if (ptr[0] != 0) return false;
-    for (int r = 0; r < rows; ++r)
-        if (ptr[r + 1] < ptr[r]) return false;
-    return true;
-}
-
-extern "C" {
+extern "C" {   // what the host forms check before anything is launched: map_check.h and their own arguments
 
 int slamit_map_edit_apply(int device, const slamit_map_index* map, const slamit_edit_index* X, int32_t n, const slamit_map_edit* edits, int32_t* status_mp,
                           int32_t* touched, int32_t* n_touched, int32_t* n_obs_out, int32_t* status) {
     const char* const where = "slamit_map_edit_apply";
-    if (n < 0 || !n_touched || !n_obs_out || !status || (n && !edits)) return me_refuse(where, "null array or negative n");
-    if (n > SLAMIT_EDIT_MAX_EDITS) return me_refuse(where, "more than SLAMIT_EDIT_MAX_EDITS edits", SLAMIT_ERR_CAPACITY);
-    if (!map || !X) return me_refuse(where, "null table");
-    if (map->n_kf < 0 || map->n_mp < 0 || map->n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return me_refuse(where, "n_kf outside [0, SLAMIT_LOCAL_MAP_MAX_KF] or negative n_mp");
+    if (n < 0 || !n_touched || !n_obs_out || !status || (n && !edits)) return slamit_refuse(where, "null array or negative n");
+    if (n > SLAMIT_EDIT_MAX_EDITS) return slamit_refuse(where, "more than SLAMIT_EDIT_MAX_EDITS edits", SLAMIT_ERR_CAPACITY);
+    if (!map || !X) return slamit_refuse(where, "null table");
+    if (const char* bad = map_sizes_error(map)) return slamit_refuse(where, bad);
     const int n_kf = map->n_kf, n_mp = map->n_mp;
-    if (n_mp && (!status_mp || !touched)) return me_refuse(where, "null array or negative n");
-    if (X->obs_cap_out < 0) return me_refuse(where, "negative obs_cap_out");
-    if (!map->obs_ptr || !map->kf_mp_ptr || !X->obs_ptr_out) return me_refuse(where, "null table");
-    if (!me_csr_ok(map->obs_ptr, n_mp) || !me_csr_ok(map->kf_mp_ptr, n_kf)) return me_refuse(where, "a CSR pointer array does not ascend from 0");
+    if (n_mp && (!status_mp || !touched)) return slamit_refuse(where, "null array or negative n");
+    if (X->obs_cap_out < 0) return slamit_refuse(where, "negative obs_cap_out");
+    if (!map->obs_ptr || !map->kf_mp_ptr || !X->obs_ptr_out) return slamit_refuse(where, "null table");
+    if (!map_csr_ok(map->obs_ptr, n_mp) || !map_csr_ok(map->kf_mp_ptr, n_kf)) return slamit_refuse(where, "a CSR pointer array does not ascend from 0");
     const size_t n_obs = (size_t)map->obs_ptr[n_mp], n_kfmp = (size_t)map->kf_mp_ptr[n_kf], cap_out = (size_t)X->obs_cap_out;
     if ((n_obs && (!map->obs_kf || !X->obs_idx || !X->obs_octave || !X->obs_weight)) || (n_mp && (!X->mp_bad || !X->mp_nobs || !X->mp_ref_kf)) || (n_kfmp && !X->kf_mp) ||
         (cap_out && (!X->obs_kf_out || !X->obs_idx_out || !X->obs_octave_out || !X->obs_weight_out)))
-        return me_refuse(where, "null table");
-    for (size_t o = 0; o < n_obs; ++o) {
-        const int k = map->obs_kf[o];
-        if (k < 0 || k >= n_kf) return me_refuse(where, "obs_kf holds a keyframe slot outside [0, n_kf)");
-        if (X->obs_idx[o] < 0 || X->obs_idx[o] >= map->kf_mp_ptr[k + 1] - map->kf_mp_ptr[k]) return me_refuse(where, "obs_idx holds a keypoint index outside its keyframe's row");
-        if (X->obs_weight[o] != 1 && X->obs_weight[o] != 2) return me_refuse(where, "obs_weight holds a weight other than 1 or 2");
-    }
-    for (int p = 0; p < n_mp; ++p)
-        if (X->mp_ref_kf[p] < -1 || X->mp_ref_kf[p] >= n_kf) return me_refuse(where, "mp_ref_kf holds a keyframe slot outside [-1, n_kf)");
+        return slamit_refuse(where, "null table");
+    if (const char* bad = map_obs_error(map, X->obs_idx, X->obs_weight)) return slamit_refuse(where, bad);
+    if (!map_slots_ok(X->mp_ref_kf, (size_t)n_mp, -1, n_kf)) return slamit_refuse(where, "mp_ref_kf holds a keyframe slot outside [-1, n_kf)");
     for (int i = 0; i < n; ++i) {
         const slamit_map_edit& e = edits[i];
-        if (e.kind < SLAMIT_EDIT_ADD_OBS || e.kind > SLAMIT_EDIT_SET_BAD) return me_refuse(where, "an edit's kind outside 1..3");
-        if (e.flags < 0 || e.flags > SLAMIT_EDIT_MATCH) return me_refuse(where, "an edit's flags outside 0..1");
-        if (e.mp < 0 || e.mp >= n_mp) return me_refuse(where, "edits holds a point slot outside [0, n_mp)");
+        if (e.kind < SLAMIT_EDIT_ADD_OBS || e.kind > SLAMIT_EDIT_SET_BAD) return slamit_refuse(where, "an edit's kind outside 1..3");
+        if (e.flags < 0 || e.flags > SLAMIT_EDIT_MATCH) return slamit_refuse(where, "an edit's flags outside 0..1");
+        if (e.mp < 0 || e.mp >= n_mp) return slamit_refuse(where, "edits holds a point slot outside [0, n_mp)");
         if (e.kind == SLAMIT_EDIT_SET_BAD) continue;
-        if (e.kf < 0 || e.kf >= n_kf) return me_refuse(where, "edits holds a keyframe slot outside [0, n_kf)");
+        if (e.kf < 0 || e.kf >= n_kf) return slamit_refuse(where, "edits holds a keyframe slot outside [0, n_kf)");
         if (e.kind == SLAMIT_EDIT_ERASE_OBS) continue;
-        if (e.idx < 0 || e.idx >= map->kf_mp_ptr[e.kf + 1] - map->kf_mp_ptr[e.kf]) return me_refuse(where, "edits holds a keypoint index outside its keyframe's row");
-        if (e.weight != 1 && e.weight != 2) return me_refuse(where, "an edit's weight other than 1 or 2");
+        if (e.idx < 0 || e.idx >= map->kf_mp_ptr[e.kf + 1] - map->kf_mp_ptr[e.kf]) return slamit_refuse(where, "edits holds a keypoint index outside its keyframe's row");
+        if (e.weight != 1 && e.weight != 2) return slamit_refuse(where, "an edit's weight other than 1 or 2");
     }
-    if (n_obs + (size_t)n > (size_t)0x7fffffff) return me_refuse(where, "the new table may need more than 2^31 - 1 entries", SLAMIT_ERR_CAPACITY);
+    if (n_obs + (size_t)n > (size_t)0x7fffffff) return slamit_refuse(where, "the new table may need more than 2^31 - 1 entries", SLAMIT_ERR_CAPACITY);
     SLAMIT_USE_DEVICE(device);
     MeBatch H;
     size_t clear_bytes = 0;
@@ -497,26 +448,26 @@ size_t slamit_map_edit_workspace(int n_maps, int cap, int mp_cap, int kfmp_cap) 
 
 int slamit_map_edit_batch_dev(int device, const slamit_map_edit_batch_rec* R, void* stream) {
     const char* const where = "slamit_map_edit_batch_dev";
-    if (!R || R->n_maps < 0 || R->cap < 0 || R->mp_cap < 0 || R->kfmp_cap < 0) return me_refuse(where, "bad argument");
+    if (!R || R->n_maps < 0 || R->cap < 0 || R->mp_cap < 0 || R->kfmp_cap < 0) return slamit_refuse(where, "bad argument");
     if (R->n_maps == 0) return SLAMIT_OK;
-    if (R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->maps || !R->edit) return me_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
-    if (R->cap > SLAMIT_EDIT_MAX_EDITS) return me_refuse(where, "cap above SLAMIT_EDIT_MAX_EDITS", SLAMIT_ERR_CAPACITY);
-    if (R->mp_cap == 0x7fffffff) return me_refuse(where, "mp_cap above 2^31 - 2", SLAMIT_ERR_CAPACITY);
+    if (R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->maps || !R->edit) return slamit_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
+    if (R->cap > SLAMIT_EDIT_MAX_EDITS) return slamit_refuse(where, "cap above SLAMIT_EDIT_MAX_EDITS", SLAMIT_ERR_CAPACITY);
+    if (R->mp_cap == 0x7fffffff) return slamit_refuse(where, "mp_cap above 2^31 - 2", SLAMIT_ERR_CAPACITY);
     for (int m = 0; m < R->n_maps; ++m) {
         const slamit_map_index& M = R->maps[m];
         const slamit_edit_index& X = R->edit[m];
-        if (M.n_kf < 0 || M.n_mp < 0 || M.n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return me_refuse(where, "a map with n_kf outside [0, SLAMIT_LOCAL_MAP_MAX_KF] or negative n_mp");
-        if (M.n_mp > R->mp_cap) return me_refuse(where, "a map with n_mp above mp_cap");
-        if (X.obs_cap_out < 0) return me_refuse(where, "negative obs_cap_out");
+        if (const char* bad = map_batch_sizes_error(&M)) return slamit_refuse(where, bad);
+        if (M.n_mp > R->mp_cap) return slamit_refuse(where, "a map with n_mp above mp_cap");
+        if (X.obs_cap_out < 0) return slamit_refuse(where, "negative obs_cap_out");
         if (!M.obs_ptr || !M.obs_kf || !M.kf_mp_ptr || !X.obs_idx || !X.obs_octave || !X.obs_weight || !X.mp_bad || !X.mp_nobs || !X.mp_ref_kf || !X.kf_mp ||
             !X.obs_ptr_out || !X.obs_kf_out || !X.obs_idx_out || !X.obs_octave_out || !X.obs_weight_out)
-            return me_refuse(where, "null table");
+            return slamit_refuse(where, "null table");
     }
     if (!R->d_n || !R->d_n_touched || !R->d_n_obs_out || !R->d_status || (R->cap && !R->d_edits) || (R->mp_cap && (!R->d_status_mp || !R->d_touched)))
-        return me_refuse(where, "null array");
+        return slamit_refuse(where, "null array");
     size_t clear_bytes = 0;
     const size_t need = me_ws_layout(R->n_maps, R->cap, R->mp_cap, R->kfmp_cap, nullptr, nullptr, &clear_bytes);
-    if (!R->d_workspace || R->workspace_bytes < need || ((uintptr_t)R->d_workspace & 7)) return me_refuse(where, "workspace missing, misaligned or below slamit_map_edit_workspace()");
+    if (!R->d_workspace || R->workspace_bytes < need || ((uintptr_t)R->d_workspace & 7)) return slamit_refuse(where, "workspace missing, misaligned or below slamit_map_edit_workspace()");
     SLAMIT_USE_DEVICE(device);
     MeBatch B;
     memset(&B, 0, sizeof(B));

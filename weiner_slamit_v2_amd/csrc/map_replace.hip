@@ -25,7 +25,6 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -34,6 +33,7 @@
 #include "../../include/slamit.h"
 #include "slamit_internal.h"
 #include "wave_ops.h"
+#include "map_check.h"
 #include "map_replace.h"
 
 static_assert(sizeof(MrOp) == sizeof(slamit_map_replace) && sizeof(MrOp) == 20 && offsetof(MrOp, a) == offsetof(slamit_map_replace, a) &&
@@ -123,13 +123,6 @@ static size_t mr_ws_layout(int n_maps, int cap, int mp_cap, int kfmp_cap, unsign
     return off;
 }
 
-// memory written by some lanes of the wavefront, read by others
-__device__ __forceinline__ void mr_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ int mr_list_n(const MrBatch& B, int m) { return min(max(B.n[m], 0), B.cap); }
 __device__ __forceinline__ int32_t* mr_col(const MrBatch& B, int m, int col) { return B.wcol + ((size_t)m * MR_NCOLS + col) * (size_t)B.ninv; }
 __device__ __forceinline__ bool mr_gate(const MrBatch& B, int m) {
     const int32_t* const f = B.flags + MR_NFLAGS * m;
@@ -139,7 +132,7 @@ __device__ __forceinline__ bool mr_gate(const MrBatch& B, int m) {
 // ---- grid (ceil(cap / 256), maps) ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MR_NT) void mr_hist_kernel(MrBatch B) {
     const int m = blockIdx.y, i = blockIdx.x * MR_NT + (int)threadIdx.x;
-    if (i >= mr_list_n(B, m)) return;
+    if (i >= lm_list_n(B.n[m], B.cap)) return;
     const LmMap& M = B.maps[m];
     const size_t S = (size_t)B.mp_cap + 1, c = (size_t)B.cap;
     const MrOp e = B.ops[m * c + i];
@@ -165,39 +158,16 @@ __device__ __forceinline__ int mr_scan_src(const MrBatch& B, int m, int mode, in
     const int ci = B.cidx[m * S + p];                                  // < ninv: the involved points are counted there
     return mr_col(B, m, z ? MR_C_RECEIVED : MR_C_LEN)[ci];
 }
-// inclusive scan over the 256 threads of the workgroup; total = the workgroup's sum.  Every thread calls it.
-__device__ __forceinline__ int mr_block_scan(int v, int& total) {
-    __shared__ int wave_total[MR_NT / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int incl = wave_inclusive_scan_i32(v);
-    if (lane == 63) wave_total[w] = incl;
-    __syncthreads();
-    int off = 0;
-    total = 0;
-    for (int u = 0; u < MR_NT / 64; ++u) { const int t = wave_total[u]; off += u < w ? t : 0; total += t; }
-    __syncthreads();
-    return off + incl;
-}
 // grid (nparts, maps, 2): the sum of block x of array z over the first n_mp entries
 __global__ __launch_bounds__(MR_NT) void mr_scan_sum_kernel(MrBatch B, int mode) {
     const int m = blockIdx.y, i = blockIdx.x * MR_NT + (int)threadIdx.x;
     int total;
-    mr_block_scan(i < B.maps[m].n_mp ? mr_scan_src(B, m, mode, blockIdx.z, i) : 0, total);
+    block_inclusive_scan_i32<MR_NT>(i < B.maps[m].n_mp ? mr_scan_src(B, m, mode, blockIdx.z, i) : 0, total);
     if (threadIdx.x == 0) B.parts[((size_t)m * 2 + blockIdx.z) * (B.nparts + 1) + blockIdx.x] = total;
 }
 // grid (maps, 2): the sums scanned in place by one workgroup, the total at [nparts]
 __global__ __launch_bounds__(MR_NT) void mr_scan_parts_kernel(MrBatch B) {
-    int32_t* const parts = B.parts + ((size_t)blockIdx.x * 2 + blockIdx.y) * (B.nparts + 1);
-    int base = 0;
-    for (int c0 = 0; c0 < B.nparts; c0 += MR_NT) {                      // every thread walks the same rounds
-        const int t = c0 + (int)threadIdx.x;
-        const int v = t < B.nparts ? parts[t] : 0;
-        int total;
-        const int incl = mr_block_scan(v, total);
-        if (t < B.nparts) parts[t] = base + incl - v;
-        base += total;
-    }
-    if (threadIdx.x == 0) parts[B.nparts] = base;
+    block_scan_parts_i32<MR_NT>(B.parts + ((size_t)blockIdx.x * 2 + blockIdx.y) * (B.nparts + 1), B.nparts);
 }
 // grid (nparts, maps, 2): out[i] = what lies before entry i, out[n_mp] = the total
 __global__ __launch_bounds__(MR_NT) void mr_scan_add_kernel(MrBatch B, int mode) {
@@ -207,7 +177,7 @@ __global__ __launch_bounds__(MR_NT) void mr_scan_add_kernel(MrBatch B, int mode)
     const int32_t* const parts = B.parts + ((size_t)m * 2 + blockIdx.z) * (B.nparts + 1);
     const int v = i < n ? mr_scan_src(B, m, mode, blockIdx.z, i) : 0;
     int total;
-    const int incl = mr_block_scan(v, total);
+    const int incl = block_inclusive_scan_i32<MR_NT>(v, total);
     if (i < n) out[i] = parts[blockIdx.x] + incl - v;
     else if (i == n) out[i] = parts[B.nparts];                          // n <= mp_cap: inside the row
 }
@@ -217,7 +187,7 @@ __global__ __launch_bounds__(MR_NT) void mr_scatter_kernel(MrBatch B) {
     const int m = blockIdx.y, i = blockIdx.x * MR_NT + (int)threadIdx.x;
     const LmMap& M = B.maps[m];
     const size_t S = (size_t)B.mp_cap + 1, c = (size_t)B.cap;
-    if (i < mr_list_n(B, m) && B.done[m * c + i] == 0) {                // an op the histogram counted
+    if (i < lm_list_n(B.n[m], B.cap) && B.done[m * c + i] == 0) {                // an op the histogram counted
         const MrOp e = B.ops[m * c + i];
         int at = B.bstart[m * S + e.a] + atomicAdd(&B.cursor[m * S + e.a], 1);   // < the number bucketed <= 2 cap
         B.bucket[m * 2 * c + at] = i;
@@ -246,7 +216,7 @@ __global__ __launch_bounds__(MR_NT) void mr_prep_kernel(MrBatch B) {
     const int b0 = B.bstart[m * S + p];
     const int li = lane < ne ? B.bucket[m * 2 * c + b0 + lane] : 0x7fffffff;
     raw[w][lane] = li;
-    mr_wave_sync();
+    wave_mem_sync();
     if (lane < ne) {
         int prev = -1;                                                  // list indices are distinct: the largest below mine
         for (int t = 0; t < ne; ++t) { const int o = raw[w][t]; if (o < li && o > prev) prev = o; }
@@ -315,16 +285,16 @@ struct MrWorldDev {
     __device__ __forceinline__ void fuse(int S, int D, Emit& emit, int li, int& moved, int& erased) {
         const int cs = cidx[S], cd = cidx[D], len_s = len_of(cs), len_d = len_of(cd);
         const size_t rs = (size_t)cs * MR_MAX_OBS, rd = (size_t)cd * MR_MAX_OBS;
-        mr_wave_sync();                                                 // the LDS of the op before
+        wave_mem_sync();                                                 // the LDS of the op before
         for (int e = lane; e < len_s; e += 64) skf[e] = wkf[rs + e];
-        mr_wave_sync();
+        wave_mem_sync();
         for (int e = lane; e < len_s; e += 64) {                        // ascending slot, row order among equals
             const uint32_t key = (uint32_t)skf[e];
             int rank = 0;
             for (int f = 0; f < len_s; ++f) { const uint32_t o = (uint32_t)skf[f]; rank += (o < key) || (o == key && f < e); }
             sord[rank] = (uint16_t)e;
         }
-        mr_wave_sync();
+        wave_mem_sync();
         int n_moved = 0, add = 0, over = 0;
         for (int j0 = 0; j0 < len_s; j0 += 64) {
             const int j = j0 + lane;
@@ -369,7 +339,7 @@ __global__ __launch_bounds__(MR_ROUND_NT) void mr_round_kernel(MrBatch B) {
     const size_t S = (size_t)B.mp_cap + 1, c = (size_t)B.cap;
     int32_t* const flags = B.flags + MR_NFLAGS * m;
     if (flags[MR_F_OP_OVER]) return;                                    // a bucket above a wavefront: no predecessors were made
-    const int n = mr_list_n(B, m);
+    const int n = lm_list_n(B.n[m], B.cap);
     const MrOp* const ops = B.ops + m * c;
     int32_t* const done = B.done + m * c;
     const int32_t* const pred_a = B.pred + (m * 2 + 0) * c;
@@ -460,7 +430,7 @@ __global__ __launch_bounds__(MR_NT) void mr_copy_kernel(MrBatch B) {
     optr[w][lane] = M.obs_ptr[min(p0 + lane, n_mp)]; nptr[w][lane] = newptr[min(p0 + lane, n_mp)];
     if (lane == 63) { optr[w][64] = M.obs_ptr[min(p0 + 64, n_mp)]; nptr[w][64] = newptr[min(p0 + 64, n_mp)]; }
     skip[w][lane] = sk;
-    mr_wave_sync();
+    wave_mem_sync();
     const int e1 = optr[w][64];
     for (int e = optr[w][0] + lane; e < e1; e += 64) {
         int lo = 0, hi = 63;                                            // the row q with optr[q] <= e < optr[q + 1]
@@ -481,7 +451,7 @@ __global__ __launch_bounds__(MR_NT) void mr_kfmp_kernel(MrBatch B) {
     const MrIndex& X = B.X[m];
     const size_t c = (size_t)B.cap;
     if (mr_gate(B, m)) return;
-    if (i < mr_list_n(B, m)) { B.moved[m * c + i] = B.mv[m * c + i]; B.erased[m * c + i] = B.er[m * c + i]; }
+    if (i < lm_list_n(B.n[m], B.cap)) { B.moved[m * c + i] = B.mv[m * c + i]; B.erased[m * c + i] = B.er[m * c + i]; }
     if (i >= min(M.kf_mp_ptr[M.n_kf], B.kfmp_cap)) return;
     const unsigned long long v = B.kfw[(size_t)m * B.kfmp_cap + i];
     if (v) X.kf_mp[i] = (int)(unsigned)v - 1;
@@ -529,56 +499,39 @@ __global__ __launch_bounds__(MR_NT) void mr_check_replaced_kernel(MrCheck Q) {
     if (threadIdx.x == 0) Q.status[f] = any ? MR_BAD_SLOT : 0;
 }
 
-static int mr_refuse(const char* where, const char* what, int code = SLAMIT_ERR_ARG) {
-    static thread_local char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", where, what);
-    return slamit_fail(code, msg);
-}
-static bool mr_csr_ok(const int32_t* ptr, int rows) {
-    if (ptr[0] != 0) return false;
-    for (int r = 0; r < rows; ++r)
-        if (ptr[r + 1] < ptr[r]) return false;
-    return true;
-}
-
-extern "C" {
+extern "C" {   // what the host forms check before anything is launched: map_check.h and their own arguments
 
 int slamit_map_replace_apply(int device, const slamit_map_index* map, const slamit_replace_index* X, int32_t n, const slamit_map_replace* ops, int32_t* moved,
                              int32_t* erased, int32_t* touched, int32_t* n_touched, int32_t* n_obs_out, int32_t* status) {
     const char* const where = "slamit_map_replace_apply";
-    if (n < 0 || !n_touched || !n_obs_out || !status || (n && (!ops || !moved || !erased))) return mr_refuse(where, "null array or negative n");
-    if (n > SLAMIT_REPLACE_MAX_OPS) return mr_refuse(where, "more than SLAMIT_REPLACE_MAX_OPS ops", SLAMIT_ERR_CAPACITY);
-    if (!map || !X) return mr_refuse(where, "null table");
-    if (map->n_kf < 0 || map->n_mp < 0 || map->n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return mr_refuse(where, "n_kf outside [0, SLAMIT_LOCAL_MAP_MAX_KF] or negative n_mp");
+    if (n < 0 || !n_touched || !n_obs_out || !status || (n && (!ops || !moved || !erased))) return slamit_refuse(where, "null array or negative n");
+    if (n > SLAMIT_REPLACE_MAX_OPS) return slamit_refuse(where, "more than SLAMIT_REPLACE_MAX_OPS ops", SLAMIT_ERR_CAPACITY);
+    if (!map || !X) return slamit_refuse(where, "null table");
+    if (const char* bad = map_sizes_error(map)) return slamit_refuse(where, bad);
     const int n_kf = map->n_kf, n_mp = map->n_mp;
-    if (n_mp && !touched) return mr_refuse(where, "null array or negative n");
-    if (X->obs_cap_out < 0) return mr_refuse(where, "negative obs_cap_out");
-    if (!map->obs_ptr || !map->kf_mp_ptr || !X->obs_ptr_out) return mr_refuse(where, "null table");
-    if (!mr_csr_ok(map->obs_ptr, n_mp) || !mr_csr_ok(map->kf_mp_ptr, n_kf)) return mr_refuse(where, "a CSR pointer array does not ascend from 0");
+    if (n_mp && !touched) return slamit_refuse(where, "null array or negative n");
+    if (X->obs_cap_out < 0) return slamit_refuse(where, "negative obs_cap_out");
+    if (!map->obs_ptr || !map->kf_mp_ptr || !X->obs_ptr_out) return slamit_refuse(where, "null table");
+    if (!map_csr_ok(map->obs_ptr, n_mp) || !map_csr_ok(map->kf_mp_ptr, n_kf)) return slamit_refuse(where, "a CSR pointer array does not ascend from 0");
     const size_t n_obs = (size_t)map->obs_ptr[n_mp], n_kfmp = (size_t)map->kf_mp_ptr[n_kf], cap_out = (size_t)X->obs_cap_out;
     if ((n_obs && (!map->obs_kf || !X->obs_idx || !X->obs_octave || !X->obs_weight)) ||
         (n_mp && (!X->mp_bad || !X->mp_nobs || !X->mp_found || !X->mp_visible || !X->mp_replaced)) || (n_kfmp && !X->kf_mp) ||
         (cap_out && (!X->obs_kf_out || !X->obs_idx_out || !X->obs_octave_out || !X->obs_weight_out)))
-        return mr_refuse(where, "null table");
-    for (size_t o = 0; o < n_obs; ++o) {
-        const int k = map->obs_kf[o];
-        if (k < 0 || k >= n_kf) return mr_refuse(where, "obs_kf holds a keyframe slot outside [0, n_kf)");
-        if (X->obs_idx[o] < 0 || X->obs_idx[o] >= map->kf_mp_ptr[k + 1] - map->kf_mp_ptr[k]) return mr_refuse(where, "obs_idx holds a keypoint index outside its keyframe's row");
-        if (X->obs_weight[o] != 1 && X->obs_weight[o] != 2) return mr_refuse(where, "obs_weight holds a weight other than 1 or 2");
-    }
+        return slamit_refuse(where, "null table");
+    if (const char* bad = map_obs_error(map, X->obs_idx, X->obs_weight)) return slamit_refuse(where, bad);
     for (int i = 0; i < n; ++i) {
         const slamit_map_replace& e = ops[i];
-        if (e.kind != SLAMIT_REPLACE_REPLACE && e.kind != SLAMIT_REPLACE_ADD_OBS) return mr_refuse(where, "an op's kind outside 1..2");
-        if (e.a < 0 || e.a >= n_mp) return mr_refuse(where, "ops holds a point slot outside [0, n_mp)");
+        if (e.kind != SLAMIT_REPLACE_REPLACE && e.kind != SLAMIT_REPLACE_ADD_OBS) return slamit_refuse(where, "an op's kind outside 1..2");
+        if (e.a < 0 || e.a >= n_mp) return slamit_refuse(where, "ops holds a point slot outside [0, n_mp)");
         if (e.kind == SLAMIT_REPLACE_REPLACE) {
-            if (e.b < 0 || e.b >= n_mp) return mr_refuse(where, "ops holds a point slot outside [0, n_mp)");
+            if (e.b < 0 || e.b >= n_mp) return slamit_refuse(where, "ops holds a point slot outside [0, n_mp)");
             continue;
         }
-        if (e.b < 0 || e.b >= n_kf) return mr_refuse(where, "ops holds a keyframe slot outside [0, n_kf)");
-        if (e.idx < 0 || e.idx >= map->kf_mp_ptr[e.b + 1] - map->kf_mp_ptr[e.b]) return mr_refuse(where, "ops holds a keypoint index outside its keyframe's row");
-        if (e.weight != 1 && e.weight != 2) return mr_refuse(where, "an op's weight other than 1 or 2");
+        if (e.b < 0 || e.b >= n_kf) return slamit_refuse(where, "ops holds a keyframe slot outside [0, n_kf)");
+        if (e.idx < 0 || e.idx >= map->kf_mp_ptr[e.b + 1] - map->kf_mp_ptr[e.b]) return slamit_refuse(where, "ops holds a keypoint index outside its keyframe's row");
+        if (e.weight != 1 && e.weight != 2) return slamit_refuse(where, "an op's weight other than 1 or 2");
     }
-    if (n_obs + (size_t)n > (size_t)0x7fffffff) return mr_refuse(where, "the new table may need more than 2^31 - 1 entries", SLAMIT_ERR_CAPACITY);
+    if (n_obs + (size_t)n > (size_t)0x7fffffff) return slamit_refuse(where, "the new table may need more than 2^31 - 1 entries", SLAMIT_ERR_CAPACITY);
     SLAMIT_USE_DEVICE(device);
     MrBatch H;
     size_t clear_bytes = 0;
@@ -627,26 +580,26 @@ size_t slamit_map_replace_workspace(int n_maps, int cap, int mp_cap, int kfmp_ca
 
 int slamit_map_replace_batch_dev(int device, const slamit_map_replace_batch_rec* R, void* stream) {
     const char* const where = "slamit_map_replace_batch_dev";
-    if (!R || R->n_maps < 0 || R->cap < 0 || R->mp_cap < 0 || R->kfmp_cap < 0) return mr_refuse(where, "bad argument");
+    if (!R || R->n_maps < 0 || R->cap < 0 || R->mp_cap < 0 || R->kfmp_cap < 0) return slamit_refuse(where, "bad argument");
     if (R->n_maps == 0) return SLAMIT_OK;
-    if (R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->maps || !R->index) return mr_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
-    if (R->cap > SLAMIT_REPLACE_MAX_OPS) return mr_refuse(where, "cap above SLAMIT_REPLACE_MAX_OPS", SLAMIT_ERR_CAPACITY);
-    if (R->mp_cap == 0x7fffffff) return mr_refuse(where, "mp_cap above 2^31 - 2", SLAMIT_ERR_CAPACITY);
+    if (R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->maps || !R->index) return slamit_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
+    if (R->cap > SLAMIT_REPLACE_MAX_OPS) return slamit_refuse(where, "cap above SLAMIT_REPLACE_MAX_OPS", SLAMIT_ERR_CAPACITY);
+    if (R->mp_cap == 0x7fffffff) return slamit_refuse(where, "mp_cap above 2^31 - 2", SLAMIT_ERR_CAPACITY);
     for (int m = 0; m < R->n_maps; ++m) {
         const slamit_map_index& M = R->maps[m];
         const slamit_replace_index& X = R->index[m];
-        if (M.n_kf < 0 || M.n_mp < 0 || M.n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return mr_refuse(where, "a map with n_kf outside [0, SLAMIT_LOCAL_MAP_MAX_KF] or negative n_mp");
-        if (M.n_mp > R->mp_cap) return mr_refuse(where, "a map with n_mp above mp_cap");
-        if (X.obs_cap_out < 0) return mr_refuse(where, "negative obs_cap_out");
+        if (const char* bad = map_batch_sizes_error(&M)) return slamit_refuse(where, bad);
+        if (M.n_mp > R->mp_cap) return slamit_refuse(where, "a map with n_mp above mp_cap");
+        if (X.obs_cap_out < 0) return slamit_refuse(where, "negative obs_cap_out");
         if (!M.obs_ptr || !M.obs_kf || !M.kf_mp_ptr || !X.obs_idx || !X.obs_octave || !X.obs_weight || !X.mp_bad || !X.mp_nobs || !X.mp_found || !X.mp_visible ||
             !X.mp_replaced || !X.kf_mp || !X.obs_ptr_out || !X.obs_kf_out || !X.obs_idx_out || !X.obs_octave_out || !X.obs_weight_out)
-            return mr_refuse(where, "null table");
+            return slamit_refuse(where, "null table");
     }
     if (!R->d_n || !R->d_n_touched || !R->d_n_obs_out || !R->d_status || (R->cap && (!R->d_ops || !R->d_moved || !R->d_erased)) || (R->mp_cap && !R->d_touched))
-        return mr_refuse(where, "null array");
+        return slamit_refuse(where, "null array");
     size_t clear_bytes = 0;
     const size_t need = mr_ws_layout(R->n_maps, R->cap, R->mp_cap, R->kfmp_cap, nullptr, nullptr, &clear_bytes);
-    if (!R->d_workspace || R->workspace_bytes < need || ((uintptr_t)R->d_workspace & 7)) return mr_refuse(where, "workspace missing, misaligned or below slamit_map_replace_workspace()");
+    if (!R->d_workspace || R->workspace_bytes < need || ((uintptr_t)R->d_workspace & 7)) return slamit_refuse(where, "workspace missing, misaligned or below slamit_map_replace_workspace()");
     SLAMIT_USE_DEVICE(device);
     MrBatch B;
     memset(&B, 0, sizeof(B));
@@ -662,10 +615,9 @@ int slamit_map_replace_batch_dev(int device, const slamit_map_replace_batch_rec*
 
 int slamit_check_replaced(int device, int32_t n_mp, const int32_t* mp_replaced, int32_t n, int32_t* frame_mp, int32_t* status) {
     const char* const where = "slamit_check_replaced";
-    if (n < 0 || n_mp < 0 || !status || (n && !frame_mp) || (n_mp && !mp_replaced)) return mr_refuse(where, "null array or negative count");
-    if (n > SLAMIT_CHECK_REPLACED_MAX_N) return mr_refuse(where, "more than SLAMIT_CHECK_REPLACED_MAX_N entries", SLAMIT_ERR_CAPACITY);
-    for (int i = 0; i < n; ++i)
-        if (frame_mp[i] < -1 || frame_mp[i] >= n_mp) return mr_refuse(where, "frame_mp holds a point slot outside [-1, n_mp)");
+    if (n < 0 || n_mp < 0 || !status || (n && !frame_mp) || (n_mp && !mp_replaced)) return slamit_refuse(where, "null array or negative count");
+    if (n > SLAMIT_CHECK_REPLACED_MAX_N) return slamit_refuse(where, "more than SLAMIT_CHECK_REPLACED_MAX_N entries", SLAMIT_ERR_CAPACITY);
+    if (!map_slots_ok(frame_mp, (size_t)n, -1, n_mp)) return slamit_refuse(where, "frame_mp holds a point slot outside [-1, n_mp)");
     SLAMIT_USE_DEVICE(device);
     MrCheck H;
     std::vector<SlamitInOut> io;
@@ -694,17 +646,17 @@ int slamit_check_replaced(int device, int32_t n_mp, const int32_t* mp_replaced, 
 
 int slamit_check_replaced_batch_dev(int device, const slamit_check_replaced_batch_rec* R, void* stream) {
     const char* const where = "slamit_check_replaced_batch_dev";
-    if (!R || R->nframes < 0 || R->n_maps < 0 || R->cap < 0) return mr_refuse(where, "bad argument");
+    if (!R || R->nframes < 0 || R->n_maps < 0 || R->cap < 0) return slamit_refuse(where, "bad argument");
     if (R->nframes == 0) return SLAMIT_OK;
-    if (R->n_maps < 1 || R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->n_mp || !R->d_mp_replaced) return mr_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
-    if (R->cap > SLAMIT_CHECK_REPLACED_MAX_N) return mr_refuse(where, "cap above SLAMIT_CHECK_REPLACED_MAX_N", SLAMIT_ERR_CAPACITY);
+    if (R->n_maps < 1 || R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->n_mp || !R->d_mp_replaced) return slamit_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
+    if (R->cap > SLAMIT_CHECK_REPLACED_MAX_N) return slamit_refuse(where, "cap above SLAMIT_CHECK_REPLACED_MAX_N", SLAMIT_ERR_CAPACITY);
     MrCheck Q;
     memset(&Q, 0, sizeof(Q));
     for (int m = 0; m < R->n_maps; ++m) {
-        if (R->n_mp[m] < 0 || (R->n_mp[m] && !R->d_mp_replaced[m])) return mr_refuse(where, "a map with negative n_mp or no mp_replaced");
+        if (R->n_mp[m] < 0 || (R->n_mp[m] && !R->d_mp_replaced[m])) return slamit_refuse(where, "a map with negative n_mp or no mp_replaced");
         Q.n_mp[m] = R->n_mp[m]; Q.replaced[m] = R->d_mp_replaced[m];
     }
-    if (!R->d_frame_map || !R->d_n || !R->d_status || (R->cap && !R->d_frame_mp)) return mr_refuse(where, "null array");
+    if (!R->d_frame_map || !R->d_n || !R->d_status || (R->cap && !R->d_frame_mp)) return slamit_refuse(where, "null array");
     SLAMIT_USE_DEVICE(device);
     Q.nframes = R->nframes; Q.n_maps = R->n_maps; Q.cap = R->cap;
     Q.frame_map = R->d_frame_map; Q.n = R->d_n; Q.frame_mp = R->d_frame_mp; Q.status = R->d_status;

@@ -8,6 +8,7 @@
 #include "stage_binder.h"
 
 int slamit_fail(int code, const char* msg);                 // records msg, returns code
+int slamit_refuse(const char* where, const char* what, int code = SLAMIT_ERR_ARG);   // records "<where>: <what>", returns code
 int slamit_fail_hip(hipError_t e, const char* where);       // records "<where>: <hip error>", returns SLAMIT_ERR_DEVICE
 
 // `where` (an entry point, or the expression itself) goes into the error text

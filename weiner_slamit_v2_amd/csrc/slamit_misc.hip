@@ -48,6 +48,12 @@ int slamit_fail(int code, const char* msg) {
     return code;
 }
 
+int slamit_refuse(const char* where, const char* what, int code) {
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s: %s", where, what);
+    return slamit_fail(code, msg);
+}
+
 int slamit_fail_hip(hipError_t e, const char* where) {
     snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(e));
     (void)hipGetLastError();  // clear the sticky error

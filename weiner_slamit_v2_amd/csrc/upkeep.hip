@@ -19,7 +19,6 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -28,6 +27,7 @@
 #include "../../include/slamit.h"
 #include "slamit_internal.h"
 #include "wave_ops.h"
+#include "map_check.h"
 #include "distinctive.h"
 #include "upkeep.h"
 
@@ -64,12 +64,6 @@ struct UpCullBatch {
     const int32_t* list_map; const int32_t* cur_id; const int32_t* monocular; const int32_t* n; const int32_t* recent;
     uint8_t* verdict; int32_t* kept; int32_t* n_kept; int32_t* status;
 };
-
-// LDS written by some lanes of the wavefront, read by others
-__device__ __forceinline__ void up_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // ---- grid (cap, items), 64 threads.  This instantiation takes the points with LO < observers <= ROWS; the one with LO == 0 also
 // reports what has no row (a map or a point outside its table), the LAST one the rows above UP_MAX_OBS. --------------------------
@@ -122,7 +116,7 @@ __global__ __launch_bounds__(64) void up_points_kernel(UpBatch B) {
         }
         n += __popcll(__ballot(key != ~0u));
     }
-    up_wave_sync();
+    wave_mem_sync();
     for (int e = lane; e < n_all; e += 64) {
         const uint32_t key = keys[e];
         if (key == ~0u) continue;
@@ -135,7 +129,7 @@ __global__ __launch_bounds__(64) void up_points_kernel(UpBatch B) {
             con[0][r] = c[0]; con[1][r] = c[1]; con[2][r] = c[2];
         }
     }
-    up_wave_sync();
+    wave_mem_sync();
     if (n > 0 && (what & UP_NORMAL)) {
         const int ref = __builtin_amdgcn_readfirstlane(X.mp_ref_kf[p]);
         int o_ref = -1;                       // the first observation of the reference keyframe in the order above
@@ -172,7 +166,7 @@ __global__ __launch_bounds__(64) void up_points_kernel(UpBatch B) {
         }
         if (N > DROWS) st |= UP_DESC_OVERFLOW;   // DROWS == UP_MAX_DESC wherever a row can hold more
         else if (N > 0) {
-            up_wave_sync();
+            wave_mem_sync();
             DISTINCTIVE_SELECT(rowsd, D, N, lane, bestkey)
             const int b = (int)(bestkey & 0xFFFFu);
             if (lane < 2) reinterpret_cast<uint4*>(X.mp_desc + 32 * (size_t)p)[lane] = rowsd[2 * b + lane];
@@ -233,27 +227,11 @@ static hipError_t up_launch_culling(const UpCullBatch& B, hipStream_t st) {
     return hipGetLastError();
 }
 
-// ---- what the host forms check before anything is launched -------------------------------------------------------------------
-static bool up_slots_ok(const int32_t* v, size_t count, int lo, int n) {
-    for (size_t i = 0; i < count; ++i)
-        if (v[i] < lo || v[i] >= n) return false;
-    return true;
-}
-static bool up_csr_ok(const int32_t* ptr, int rows) {
-    if (ptr[0] != 0) return false;
-    for (int r = 0; r < rows; ++r)
-        if (ptr[r + 1] < ptr[r]) return false;
-    return true;
-}
-static int up_refuse(const char* where, const char* what, int code = SLAMIT_ERR_ARG) {
-    static thread_local char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", where, what);
-    return slamit_fail(code, msg);
-}
+// ---- what the host forms check before anything is launched (map_check.h) -------------------------------------------------------
 // the map's sizes and the CSR arrays a host form walks; null on success, else what is wrong
 static const char* up_host_map(const slamit_map_index* map, const slamit_point_index* X) {
     if (!map || !X) return "null table";
-    if (map->n_kf < 0 || map->n_mp < 0 || map->n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return "n_kf outside [0, SLAMIT_LOCAL_MAP_MAX_KF] or negative n_mp";
+    if (const char* bad = map_sizes_error(map)) return bad;
     if (map->n_mp && !map->mp_bad) return "null table";
     return nullptr;
 }
@@ -263,7 +241,7 @@ static const char* up_batch_maps(int n_maps, const slamit_map_index* maps, const
     for (int m = 0; m < n_maps; ++m) {
         const slamit_map_index& M = maps[m];
         const slamit_point_index& X = pts[m];
-        if (M.n_kf < 0 || M.n_mp < 0 || M.n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return "a map with n_kf outside [0, SLAMIT_LOCAL_MAP_MAX_KF] or negative n_mp";
+        if (const char* bad = map_batch_sizes_error(&M)) return bad;
         if (culling) {
             if (!M.mp_bad || !X.mp_nobs || !X.mp_found || !X.mp_visible || !X.mp_first_kf) return "null table";
             continue;
@@ -282,29 +260,24 @@ extern "C" {
 int slamit_update_points(int device, const slamit_map_index* map, const slamit_point_index* pts, int32_t n, const int32_t* points, int32_t what,
                          int32_t* status) {
     const char* const where = "slamit_update_points";
-    if (n < 0 || (n && (!points || !status))) return up_refuse(where, "null array or negative n");
-    if (what < 1 || what > (UP_NORMAL | UP_DESC)) return up_refuse(where, "`what` outside 1..3");
-    if (n > SLAMIT_UPKEEP_MAX_POINTS) return up_refuse(where, "more than SLAMIT_UPKEEP_MAX_POINTS points", SLAMIT_ERR_CAPACITY);
-    if (const char* bad = up_host_map(map, pts)) return up_refuse(where, bad);
-    if (pts->n_levels < 1 || pts->n_levels > SLAMIT_MAX_LEVELS) return up_refuse(where, "n_levels outside [1, SLAMIT_MAX_LEVELS]");
+    if (n < 0 || (n && (!points || !status))) return slamit_refuse(where, "null array or negative n");
+    if (what < 1 || what > (UP_NORMAL | UP_DESC)) return slamit_refuse(where, "`what` outside 1..3");
+    if (n > SLAMIT_UPKEEP_MAX_POINTS) return slamit_refuse(where, "more than SLAMIT_UPKEEP_MAX_POINTS points", SLAMIT_ERR_CAPACITY);
+    if (const char* bad = up_host_map(map, pts)) return slamit_refuse(where, bad);
+    if (pts->n_levels < 1 || pts->n_levels > SLAMIT_MAX_LEVELS) return slamit_refuse(where, "n_levels outside [1, SLAMIT_MAX_LEVELS]");
     const int n_kf = map->n_kf, n_mp = map->n_mp;
-    if (!map->obs_ptr || !map->kf_mp_ptr) return up_refuse(where, "null table");
-    if (!up_csr_ok(map->obs_ptr, n_mp) || !up_csr_ok(map->kf_mp_ptr, n_kf)) return up_refuse(where, "a CSR pointer array does not ascend from 0");
+    if (!map->obs_ptr || !map->kf_mp_ptr) return slamit_refuse(where, "null table");
+    if (!map_csr_ok(map->obs_ptr, n_mp) || !map_csr_ok(map->kf_mp_ptr, n_kf)) return slamit_refuse(where, "a CSR pointer array does not ascend from 0");
     const size_t n_obs = (size_t)map->obs_ptr[n_mp], n_kfmp = (size_t)map->kf_mp_ptr[n_kf];
-    if (n_obs && !map->obs_kf) return up_refuse(where, "null table");
+    if (n_obs && !map->obs_kf) return slamit_refuse(where, "null table");
     const bool nrm = (what & UP_NORMAL) != 0, dsc = (what & UP_DESC) != 0;
     if (nrm && ((n_obs && !pts->obs_octave) || (n_kfmp && !pts->kf_octave) || (n_kf && !pts->kf_center) ||
                 (n_mp && (!pts->mp_ref_kf || !map->mp_pos || !pts->mp_normal || !pts->mp_max_dist || !pts->mp_min_dist))))
-        return up_refuse(where, "null table");
-    if (dsc && ((n_kf && !map->kf_bad) || (n_obs && !pts->obs_idx) || (n_kfmp && !pts->kf_desc) || (n_mp && !pts->mp_desc))) return up_refuse(where, "null table");
-    if (!up_slots_ok(points, (size_t)n, 0, n_mp)) return up_refuse(where, "points holds a point slot outside [0, n_mp)");
-    if (!up_slots_ok(map->obs_kf, n_obs, 0, n_kf)) return up_refuse(where, "obs_kf holds a keyframe slot outside [0, n_kf)");
-    if (nrm && !up_slots_ok(pts->mp_ref_kf, (size_t)n_mp, -1, n_kf)) return up_refuse(where, "mp_ref_kf holds a keyframe slot outside [-1, n_kf)");
-    if (dsc)
-        for (size_t o = 0; o < n_obs; ++o) {
-            const int k = map->obs_kf[o];
-            if (pts->obs_idx[o] < 0 || pts->obs_idx[o] >= map->kf_mp_ptr[k + 1] - map->kf_mp_ptr[k]) return up_refuse(where, "obs_idx holds a keypoint index outside its keyframe's row");
-        }
+        return slamit_refuse(where, "null table");
+    if (dsc && ((n_kf && !map->kf_bad) || (n_obs && !pts->obs_idx) || (n_kfmp && !pts->kf_desc) || (n_mp && !pts->mp_desc))) return slamit_refuse(where, "null table");
+    if (!map_slots_ok(points, (size_t)n, 0, n_mp)) return slamit_refuse(where, "points holds a point slot outside [0, n_mp)");
+    if (const char* bad = map_obs_error(map, dsc ? pts->obs_idx : nullptr, nullptr)) return slamit_refuse(where, bad);   // no weights here
+    if (nrm && !map_slots_ok(pts->mp_ref_kf, (size_t)n_mp, -1, n_kf)) return slamit_refuse(where, "mp_ref_kf holds a keyframe slot outside [-1, n_kf)");
     if (n == 0) return SLAMIT_OK;
     SLAMIT_USE_DEVICE(device);
     UpBatch H;
@@ -349,13 +322,13 @@ int slamit_update_points(int device, const slamit_map_index* map, const slamit_p
 
 int slamit_update_points_batch_dev(int device, const slamit_points_batch_rec* R, void* stream) {
     const char* const where = "slamit_update_points_batch_dev";
-    if (!R || R->nitems < 0 || R->n_maps < 0 || R->cap < 0) return up_refuse(where, "bad argument");
+    if (!R || R->nitems < 0 || R->n_maps < 0 || R->cap < 0) return slamit_refuse(where, "bad argument");
     if (R->nitems == 0 || R->cap == 0) return SLAMIT_OK;
-    if (R->nitems > 65535) return up_refuse(where, "more than 65535 items", SLAMIT_ERR_CAPACITY);
-    if (R->cap > SLAMIT_UPKEEP_MAX_POINTS) return up_refuse(where, "cap above SLAMIT_UPKEEP_MAX_POINTS", SLAMIT_ERR_CAPACITY);
-    if ((size_t)R->cap * (size_t)R->nitems > ((size_t)1 << 25)) return up_refuse(where, "more than 2^25 list entries (nitems x cap) in one call", SLAMIT_ERR_CAPACITY);
-    if (const char* bad = up_batch_maps(R->n_maps, R->maps, R->pts, false)) return up_refuse(where, bad);
-    if (!R->d_item_map || !R->d_n || !R->d_what || !R->d_points || !R->d_status) return up_refuse(where, "null array");
+    if (R->nitems > 65535) return slamit_refuse(where, "more than 65535 items", SLAMIT_ERR_CAPACITY);
+    if (R->cap > SLAMIT_UPKEEP_MAX_POINTS) return slamit_refuse(where, "cap above SLAMIT_UPKEEP_MAX_POINTS", SLAMIT_ERR_CAPACITY);
+    if ((size_t)R->cap * (size_t)R->nitems > ((size_t)1 << 25)) return slamit_refuse(where, "more than 2^25 list entries (nitems x cap) in one call", SLAMIT_ERR_CAPACITY);
+    if (const char* bad = up_batch_maps(R->n_maps, R->maps, R->pts, false)) return slamit_refuse(where, bad);
+    if (!R->d_item_map || !R->d_n || !R->d_what || !R->d_points || !R->d_status) return slamit_refuse(where, "null array");
     SLAMIT_USE_DEVICE(device);
     UpBatch B;
     memset(&B, 0, sizeof(B));
@@ -370,12 +343,12 @@ int slamit_update_points_batch_dev(int device, const slamit_points_batch_rec* R,
 int slamit_map_point_culling(int device, const slamit_map_index* map, const slamit_point_index* pts, int32_t cur_id, int32_t monocular, int32_t n,
                              const int32_t* recent, uint8_t* verdict, int32_t* kept, int32_t* n_kept, int32_t* status) {
     const char* const where = "slamit_map_point_culling";
-    if (n < 0 || !n_kept || !status || (n && (!recent || !verdict || !kept))) return up_refuse(where, "null array or negative n");
-    if (n > SLAMIT_UPKEEP_MAX_RECENT) return up_refuse(where, "more than SLAMIT_UPKEEP_MAX_RECENT entries", SLAMIT_ERR_CAPACITY);
-    if (const char* bad = up_host_map(map, pts)) return up_refuse(where, bad);
+    if (n < 0 || !n_kept || !status || (n && (!recent || !verdict || !kept))) return slamit_refuse(where, "null array or negative n");
+    if (n > SLAMIT_UPKEEP_MAX_RECENT) return slamit_refuse(where, "more than SLAMIT_UPKEEP_MAX_RECENT entries", SLAMIT_ERR_CAPACITY);
+    if (const char* bad = up_host_map(map, pts)) return slamit_refuse(where, bad);
     const int n_mp = map->n_mp;
-    if (n_mp && (!pts->mp_nobs || !pts->mp_found || !pts->mp_visible || !pts->mp_first_kf)) return up_refuse(where, "null table");
-    if (!up_slots_ok(recent, (size_t)n, 0, n_mp)) return up_refuse(where, "recent holds a point slot outside [0, n_mp)");
+    if (n_mp && (!pts->mp_nobs || !pts->mp_found || !pts->mp_visible || !pts->mp_first_kf)) return slamit_refuse(where, "null table");
+    if (!map_slots_ok(recent, (size_t)n, 0, n_mp)) return slamit_refuse(where, "recent holds a point slot outside [0, n_mp)");
     SLAMIT_USE_DEVICE(device);
     UpCullBatch H;
     std::vector<SlamitInOut> io;
@@ -408,12 +381,12 @@ int slamit_map_point_culling(int device, const slamit_map_index* map, const slam
 
 int slamit_map_point_culling_batch_dev(int device, const slamit_point_culling_batch_rec* R, void* stream) {
     const char* const where = "slamit_map_point_culling_batch_dev";
-    if (!R || R->nlists < 0 || R->n_maps < 0 || R->cap < 0) return up_refuse(where, "bad argument");
+    if (!R || R->nlists < 0 || R->n_maps < 0 || R->cap < 0) return slamit_refuse(where, "bad argument");
     if (R->nlists == 0) return SLAMIT_OK;
-    if (R->cap > SLAMIT_UPKEEP_MAX_RECENT) return up_refuse(where, "cap above SLAMIT_UPKEEP_MAX_RECENT", SLAMIT_ERR_CAPACITY);
-    if (const char* bad = up_batch_maps(R->n_maps, R->maps, R->pts, true)) return up_refuse(where, bad);
+    if (R->cap > SLAMIT_UPKEEP_MAX_RECENT) return slamit_refuse(where, "cap above SLAMIT_UPKEEP_MAX_RECENT", SLAMIT_ERR_CAPACITY);
+    if (const char* bad = up_batch_maps(R->n_maps, R->maps, R->pts, true)) return slamit_refuse(where, bad);
     if (!R->d_list_map || !R->d_cur_id || !R->d_monocular || !R->d_n || !R->d_n_kept || !R->d_status || (R->cap && (!R->d_recent || !R->d_verdict || !R->d_kept)))
-        return up_refuse(where, "null array");
+        return slamit_refuse(where, "null array");
     SLAMIT_USE_DEVICE(device);
     UpCullBatch B;
     memset(&B, 0, sizeof(B));

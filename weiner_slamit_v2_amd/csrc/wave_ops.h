@@ -1,5 +1,6 @@
 // wave_ops.h — what the kernels do across the 64 lanes of a wavefront: DPP exchanges, v_readlane broadcasts, the reductions and the
-// scan built from them, and the two idioms of the matchers that sit on top (256-bit Hamming distance, two smallest keys).
+// scan built from them, the workgroup scan on top of the wave scan, and the two idioms of the matchers (256-bit Hamming distance, two
+// smallest keys).
 //
 // Why DPP: __shfl_xor / __shfl_up compile to ds_bpermute, an LDS round trip per step, six dependent steps per reduction (twelve for a
 // 64-bit value).  In the serial loops that reduce -- one query, one vocabulary node, one Levenberg sum after the other -- those round
@@ -122,6 +123,42 @@ __device__ __forceinline__ int wave_inclusive_scan_i32(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);   // row_bcast:15 into rows 1, 3
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);   // row_bcast:31 into rows 2, 3
     return v;
+}
+
+// memory (LDS or global) written by some lanes of the wavefront, read by others
+__device__ __forceinline__ void wave_mem_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// ---- the workgroup on top of the wave scan --------------------------------------------------------------------------------------
+// inclusive scan over the NT threads of the workgroup; total = the workgroup's sum.  Every thread calls it.
+template <int NT>
+__device__ __forceinline__ int block_inclusive_scan_i32(int v, int& total) {
+    __shared__ int wave_total[NT / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int incl = wave_inclusive_scan_i32(v);
+    if (lane == 63) wave_total[w] = incl;
+    __syncthreads();
+    int off = 0;
+    total = 0;
+    for (int u = 0; u < NT / 64; ++u) { const int t = wave_total[u]; off += u < w ? t : 0; total += t; }
+    __syncthreads();
+    return off + incl;
+}
+// parts[nparts] scanned in place by one workgroup of NT threads (exclusive), the total at parts[nparts]
+template <int NT>
+__device__ __forceinline__ void block_scan_parts_i32(int32_t* parts, int nparts) {
+    int base = 0;
+    for (int c0 = 0; c0 < nparts; c0 += NT) {   // every thread walks the same rounds
+        const int t = c0 + (int)threadIdx.x;
+        const int v = t < nparts ? parts[t] : 0;
+        int total;
+        const int incl = block_inclusive_scan_i32<NT>(v, total);
+        if (t < nparts) parts[t] = base + incl - v;
+        base += total;
+    }
+    if (threadIdx.x == 0) parts[nparts] = base;
 }
 
 // ---- matcher idioms -------------------------------------------------------------------------------------------------------------
