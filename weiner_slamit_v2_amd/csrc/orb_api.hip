@@ -42,14 +42,14 @@ void orbk_octree(hipStream_t st, const OrbLevel* levels, int nlevels, const unsi
                  int level_override);
 void orbk_ic_angle(hipStream_t st, const OrbLevel* levels, int nlevels, const uint8_t* img0, size_t img0_stride,
                    size_t img0_frame, const uint8_t* pyr, OrbLevelKp* lkp, size_t kp_frame_stride,
-                   const int* kp_count, int max_kp, int nframes);
+                   const int* kp_count, const KpBlockTab& tab, int nframes);
 void orbk_blur_stream(hipStream_t st, const OrbLevel* levels, const uint32_t* d_inner, int n_inner, const uint32_t* d_edge, int n_edge,
                       const uint8_t* img0, size_t img0_stride, size_t img0_frame, const uint8_t* pyr, uint8_t* blur, int nframes);
 void orbk_blur(hipStream_t st, const OrbLevel* levels, const uint32_t* d_tiles, int total_tiles, const uint8_t* img0,
                size_t img0_stride, size_t img0_frame, const uint8_t* pyr, uint8_t* blur, int nframes);
 void orbk_describe(hipStream_t st, const OrbLevel* levels, int nlevels, const uint8_t* blur,
                    const OrbLevelKp* lkp, size_t kp_frame_stride, const int* kp_count, slamit_kp* out_kps,
-                   uint8_t* out_desc, int out_cap, int* out_n, int max_kp, int nframes);
+                   uint8_t* out_desc, int out_cap, int* out_n, const KpBlockTab& tab, int nframes);
 void orbk_pad(hipStream_t st, const uint8_t* src, int w, int h, size_t sstride, uint8_t* dst);
 void orbk_decode_candidates(hipStream_t st, const OrbLevel* levels, int level, const unsigned long long* K, int n,
                             unsigned long long* order_out, int* xys);
@@ -345,7 +345,7 @@ int slamit_orb_extract_batch_dev(slamit_orb* h, const uint8_t* d_gray, size_t st
     // K5: orientation
     prof_mark(h, st, ST_ANGLE, true);
     orbk_ic_angle(st, h->d_levels, nl, d_gray, stride, frame_stride, h->d_pyr, h->d_lkp, P.kp_frame_stride, kp_count,
-                  P.max_kp_level, nframes);
+                  P.ic_blocks, nframes);
     prof_mark(h, st, ST_ANGLE, false);
     if (side) {
         HIP_TRY(hipStreamWaitEvent(st, h->ev_blur, 0));
@@ -357,7 +357,7 @@ int slamit_orb_extract_batch_dev(slamit_orb* h, const uint8_t* d_gray, size_t st
     // K7: descriptors + output records
     prof_mark(h, st, ST_DESCRIBE, true);
     orbk_describe(st, h->d_levels, nl, h->d_blur, h->d_lkp, P.kp_frame_stride, kp_count, d_kps, d_desc, cap, d_n_out,
-                  P.max_kp_level, nframes);
+                  P.desc_blocks, nframes);
     prof_mark(h, st, ST_DESCRIBE, false);
     ++h->prof_call;
     HIP_TRY(hipGetLastError());

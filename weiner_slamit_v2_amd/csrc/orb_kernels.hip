@@ -1407,7 +1407,24 @@ static DiscTable make_disc() {
     return t;
 }
 
-#define IC_KP_PER_WAVE 8
+// Workgroup `local` of a frame's keypoint pass -> its level and its index inside the level: the last level whose first workgroup is
+// not behind it (KpBlockTab: levels behind the last one start at the total, which `local` stays below).  Constant indices into the
+// kernel arguments, taken as whole dwords: scalar loads of known addresses and fifteen scalar compares (16-bit accesses at odd
+// halfword offsets make the compiler fetch the table with vector loads).
+struct KpBlockWords { uint32_t w[sizeof(KpBlockTab) / 4]; };
+static_assert(sizeof(KpBlockWords) == sizeof(KpBlockTab) && 2 * (ORB_MAX_LEVELS + 1) <= sizeof(KpBlockTab), "KpBlockTab is whole dwords");
+__device__ __forceinline__ unsigned kp_block_first(const KpBlockWords& t, int l) { return (t.w[l >> 1] >> (16 * (l & 1))) & 0xFFFFu; }
+__device__ __forceinline__ void kp_block_level(const KpBlockWords& t, unsigned local, int& level, int& kb) {
+    unsigned lv = 0, base = 0;
+#pragma unroll
+    for (int l = 1; l < ORB_MAX_LEVELS; ++l) {
+        const unsigned f = kp_block_first(t, l);
+        if (local >= f) { lv = (unsigned)l; base = f; }
+    }
+    level = (int)lv; kb = (int)(local - base);
+}
+
+#define IC_KP_PER_WAVE (ORB_IC_KP_PER_WG / 4)
 #define IC_R 15                   // HALF_PATCH_SIZE
 #define IC_ROWS (2 * IC_R + 1)
 #define IC_PITCH 32               // 31 columns in two 16-byte chunks
@@ -1416,15 +1433,19 @@ __global__ __launch_bounds__(256) void ic_angle_kernel(
     const OrbLevel* __restrict__ levels, int nlevels,
     const uint8_t* __restrict__ img0, size_t img0_stride, size_t img0_frame,
     const uint8_t* __restrict__ pyr,
-    OrbLevelKp* __restrict__ lkp, size_t kp_frame_stride, const int* __restrict__ kp_count, int xcd_frames, int kblocks) {
+    OrbLevelKp* __restrict__ lkp, size_t kp_frame_stride, const int* __restrict__ kp_count, int xcd_frames, const KpBlockTab tab) {
     const int lane = threadIdx.x & 63;
     int level, frame, kb;
+    unsigned local;
+    KpBlockWords tw;
+    __builtin_memcpy(&tw, &tab, sizeof(tw));
     if (xcd_frames) {   // 1-D grid, frames dealt to the XCDs (see describe_kernel)
-        const unsigned w = blockIdx.x, k = w >> 3, P = (unsigned)(nlevels * kblocks), fq = k / P, local = k - fq * P;
+        const unsigned w = blockIdx.x, k = w >> 3, P = kp_block_first(tw, ORB_MAX_LEVELS), fq = k / P;
+        local = k - fq * P;
         frame = (int)(8u * fq + ((w + fq) & 7u));   // (rotated per group of eight frames: an XCD does not keep meeting every eighth frame of a periodic input)
         if (frame >= xcd_frames) return;
-        level = (int)(local / (unsigned)kblocks); kb = (int)(local - (unsigned)level * (unsigned)kblocks);
-    } else { level = blockIdx.y; frame = blockIdx.z; kb = blockIdx.x; }
+    } else { local = blockIdx.x; frame = blockIdx.y; }
+    kp_block_level(tw, local, level, kb);
     const OrbLevel& L = levels[level];
     const int count = kp_count[frame * nlevels + level];
     const int i0 = (kb * 4 + (threadIdx.x >> 6)) * IC_KP_PER_WAVE;
@@ -1889,7 +1910,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void b
 // level 0 writes the frame total.
 // --------------------------------------------------------------------------------------------
 __constant__ __attribute__((aligned(16))) signed char c_pattern[SLAMIT_ORB_PATTERN_INTS];
-#define DESC_KP_PER_WAVE 4
+#define DESC_KP_PER_WAVE (ORB_DESC_KP_PER_WG / 4)
 #define DESC_R 18                 // reach of the rotated pattern
 #define DESC_ROWS (2 * DESC_R + 1)
 #define DESC_PITCH 48             // 37 columns + up to 3 of alignment, in 16-byte chunks
@@ -1900,18 +1921,23 @@ __global__ __launch_bounds__(256) void describe_kernel(
     const uint8_t* __restrict__ blur,
     const OrbLevelKp* __restrict__ lkp, size_t kp_frame_stride, const int* __restrict__ kp_count,
     slamit_kp* __restrict__ out_kps, uint8_t* __restrict__ out_desc, int out_cap,
-    int* __restrict__ out_n, int xcd_frames /* 0: grid (blocks, levels, frames); else the frame count of a 1-D grid */, int kblocks) {
+    int* __restrict__ out_n, int xcd_frames /* 0: grid (blocks of a frame, frames); else the frame count of a 1-D grid */, const KpBlockTab tab) {
     const int lane = threadIdx.x & 63;
     int level, frame, kb;
+    unsigned local;
+    KpBlockWords tw;
+    __builtin_memcpy(&tw, &tab, sizeof(tw));
     if (xcd_frames) {
         // 1-D grid, frames dealt to the XCDs: consecutive workgroup ids go to consecutive XCDs (an L2 each), so workgroup w works on frame
         // 8 (k / P) + (w & 7) with k = w >> 3 and P workgroups per frame -- an XCD walks ITS frames one after the other and the patches of
-        // a frame's neighbouring keypoints meet in one L2 instead of eight
-        const unsigned w = blockIdx.x, k = w >> 3, P = (unsigned)(nlevels * kblocks), fq = k / P, local = k - fq * P;
+        // a frame's neighbouring keypoints meet in one L2 instead of eight.  P comes from the per-level block table: a level has the
+        // workgroups its own kp_cap needs, not level 0's
+        const unsigned w = blockIdx.x, k = w >> 3, P = kp_block_first(tw, ORB_MAX_LEVELS), fq = k / P;
+        local = k - fq * P;
         frame = (int)(8u * fq + ((w + fq) & 7u));   // (rotated per group of eight frames: an XCD does not keep meeting every eighth frame of a periodic input)
         if (frame >= xcd_frames) return;
-        level = (int)(local / (unsigned)kblocks); kb = (int)(local - (unsigned)level * (unsigned)kblocks);
-    } else { level = blockIdx.y; frame = blockIdx.z; kb = blockIdx.x; }
+    } else { local = blockIdx.x; frame = blockIdx.y; }
+    kp_block_level(tw, local, level, kb);
     const int i0 = (kb * 4 + (threadIdx.x >> 6)) * DESC_KP_PER_WAVE;
     const OrbLevel& L = levels[level];
     const int* counts = kp_count + frame * nlevels;
@@ -2175,14 +2201,15 @@ void orbk_octree(hipStream_t st, const OrbLevel* levels, int nlevels, const unsi
 
 void orbk_ic_angle(hipStream_t st, const OrbLevel* levels, int nlevels, const uint8_t* img0,
                    size_t img0_stride, size_t img0_frame, const uint8_t* pyr, OrbLevelKp* lkp,
-                   size_t kp_frame_stride, const int* kp_count, int max_kp, int nframes) {
-    const int kblocks = (max_kp + 4 * IC_KP_PER_WAVE - 1) / (4 * IC_KP_PER_WAVE);
+                   size_t kp_frame_stride, const int* kp_count, const KpBlockTab& tab, int nframes) {
+    const unsigned per_frame = tab.first[ORB_MAX_LEVELS];   // the workgroups of every level's own kp_cap (orb_plan_kp_blocks)
+    if (!per_frame) return;
     if (nframes >= 16)
-        hipLaunchKernelGGL(ic_angle_kernel, dim3((unsigned)(((nframes + 7) / 8) * 8 * nlevels * kblocks)), dim3(256), 0, st, levels,
-                           nlevels, img0, img0_stride, img0_frame, pyr, lkp, kp_frame_stride, kp_count, nframes, kblocks);
+        hipLaunchKernelGGL(ic_angle_kernel, dim3((unsigned)(((nframes + 7) / 8) * 8) * per_frame), dim3(256), 0, st, levels,
+                           nlevels, img0, img0_stride, img0_frame, pyr, lkp, kp_frame_stride, kp_count, nframes, tab);
     else
-        hipLaunchKernelGGL(ic_angle_kernel, dim3(kblocks, nlevels, nframes), dim3(256), 0, st, levels,
-                           nlevels, img0, img0_stride, img0_frame, pyr, lkp, kp_frame_stride, kp_count, 0, kblocks);
+        hipLaunchKernelGGL(ic_angle_kernel, dim3(per_frame, nframes), dim3(256), 0, st, levels,
+                           nlevels, img0, img0_stride, img0_frame, pyr, lkp, kp_frame_stride, kp_count, 0, tab);
 }
 
 void orbk_blur_stream(hipStream_t st, const OrbLevel* levels, const uint32_t* d_inner, int n_inner, const uint32_t* d_edge, int n_edge,
@@ -2204,14 +2231,15 @@ void orbk_blur(hipStream_t st, const OrbLevel* levels, const uint32_t* d_tiles, 
 
 void orbk_describe(hipStream_t st, const OrbLevel* levels, int nlevels, const uint8_t* blur,
                    const OrbLevelKp* lkp, size_t kp_frame_stride, const int* kp_count, slamit_kp* out_kps,
-                   uint8_t* out_desc, int out_cap, int* out_n, int max_kp, int nframes) {
-    const int kblocks = (max_kp + 4 * DESC_KP_PER_WAVE - 1) / (4 * DESC_KP_PER_WAVE);
+                   uint8_t* out_desc, int out_cap, int* out_n, const KpBlockTab& tab, int nframes) {
+    const unsigned per_frame = tab.first[ORB_MAX_LEVELS];
+    if (!per_frame) return;
     if (nframes >= 16)
-        hipLaunchKernelGGL(describe_kernel, dim3((unsigned)(((nframes + 7) / 8) * 8 * nlevels * kblocks)), dim3(256), 0, st, levels,
-                           nlevels, blur, lkp, kp_frame_stride, kp_count, out_kps, out_desc, out_cap, out_n, nframes, kblocks);
+        hipLaunchKernelGGL(describe_kernel, dim3((unsigned)(((nframes + 7) / 8) * 8) * per_frame), dim3(256), 0, st, levels,
+                           nlevels, blur, lkp, kp_frame_stride, kp_count, out_kps, out_desc, out_cap, out_n, nframes, tab);
     else
-        hipLaunchKernelGGL(describe_kernel, dim3(kblocks, nlevels, nframes), dim3(256), 0, st, levels,
-                           nlevels, blur, lkp, kp_frame_stride, kp_count, out_kps, out_desc, out_cap, out_n, 0, kblocks);
+        hipLaunchKernelGGL(describe_kernel, dim3(per_frame, nframes), dim3(256), 0, st, levels,
+                           nlevels, blur, lkp, kp_frame_stride, kp_count, out_kps, out_desc, out_cap, out_n, 0, tab);
 }
 
 void orbk_pad(hipStream_t st, const uint8_t* src, int w, int h, size_t sstride, uint8_t* dst) {

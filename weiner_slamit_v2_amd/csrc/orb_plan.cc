@@ -382,12 +382,28 @@ bool orb_plan(const slamit_orb_params& p, const OrbPlanOptions& o, OrbPlan& plan
         *why = "slamit_orb_create: nfeatures too large for the LDS octree";
         return false;
     }
+    if (!orb_plan_kp_blocks(P.levels, ORB_IC_KP_PER_WG, P.ic_blocks) || !orb_plan_kp_blocks(P.levels, ORB_DESC_KP_PER_WG, P.desc_blocks)) {
+        *why = "slamit_orb_create: nfeatures too large for the keypoint passes";   // (the octree's limit is far below this one)
+        return false;
+    }
     fast_cells(P);
     blur_strips(P);
     plan_resize(o, P);
     plan_pyramid_boxes(p, P);
     plan_bands(P);
     plan_table_block(P);
+    return true;
+}
+
+bool orb_plan_kp_blocks(const std::vector<OrbLevel>& levels, int per, KpBlockTab& tab) {
+    const int nl = (int)levels.size();
+    if (nl > ORB_MAX_LEVELS || per < 1) return false;
+    long at = 0;
+    for (int l = 0; l <= ORB_MAX_LEVELS; ++l) {   // the entries behind [nlevels] repeat the total: the kernels' walk needs no level count
+        if (at > 65535) return false;
+        tab.first[l] = (uint16_t)at;
+        if (l < nl) at += (std::max(levels[l].kp_cap, 0) + per - 1) / per;
+    }
     return true;
 }
 

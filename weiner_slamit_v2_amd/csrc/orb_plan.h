@@ -1,7 +1,7 @@
 // orb_plan.h — host-side plan of an ORB extractor handle: scale tables and quotas, level geometry, the FAST cell table, the blur
-// strip tables, the cv::resize tables of every pyramid path, the banded pyramid's row ranges and the fused pyramid's boxes, and where
-// each read-only table sits in the handle's one device block.  Plain C++17 (no HIP): the extractor (orb_api.hip) and the CPU tests
-// of the plan (tests/test_orb_plan.py, tests/test_orb_bands_plan.py) build it.
+// strip tables, the workgroups of the keypoint passes, the cv::resize tables of every pyramid path, the banded pyramid's row ranges and
+// the fused pyramid's boxes, and where each read-only table sits in the handle's one device block.  Plain C++17 (no HIP): the extractor
+// (orb_api.hip) and the CPU tests of the plan (tests/test_orb_plan.py, tests/test_orb_bands_plan.py, tests/test_orb_kp_blocks.py) build it.
 #ifndef SLAMIT_ORB_PLAN_H
 #define SLAMIT_ORB_PLAN_H
 
@@ -56,6 +56,8 @@ struct OrbPlan {
     std::vector<uint32_t> cells;
     size_t cells_off;
     FastTab fast;
+    // orientation and descriptor passes: the workgroups of every level inside a frame (orb_plan_kp_blocks)
+    KpBlockTab ic_blocks, desc_blocks;
     // blur: every strip (blur_all_kernel), and the same strips split into those inside the level (blur_stream_kernel) and the rest
     OrbStrips blur_all, blur_str, blur_edge;
     // pyramid: per-level tables ([nlevels], entry 0 unused); rows4_ok: every level fits the row kernels
@@ -75,6 +77,10 @@ struct OrbPlan {
 // Plans a handle for p.  Returns false with *why set when the geometry cannot be extracted (a level smaller than one FAST cell,
 // an aspect ratio beyond ORB_MAX_ROOTS octree roots, or more features than the LDS octree holds).  p is range-checked already.
 bool orb_plan(const slamit_orb_params& p, const OrbPlanOptions& o, OrbPlan& plan, const char** why);
+
+// The workgroups of a keypoint pass that handles `per` keypoints per workgroup: level l gets ceil(kp_cap / per) of them, numbered
+// level-major inside a frame.  False when a frame's count does not fit the table's 16 bits.
+bool orb_plan_kp_blocks(const std::vector<OrbLevel>& levels, int per, KpBlockTab& tab);
 
 // Plans the rows of one banded segment (levels first + 1 .. last, level `first` the source) over the plan's resize tables; false --
 // nothing truncated -- when a level has fewer rows than bands or a band's two tiles pass lds_budget bytes.  Fills every field of

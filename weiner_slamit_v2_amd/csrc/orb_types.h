@@ -97,6 +97,14 @@ struct BandRows { uint16_t own0, own1, cmp0, cmp1; };   // per (band, level): ro
 #define ORB_BAND_LDS_BUDGET (78 * 1024)   // both tiles of a workgroup: at least two workgroups fit a CU's 160 KB
 #define ORB_BAND_SLACK 16                 // bytes behind a tile: the 16-byte window of a row's last group may pass the row end
 
+// Orientation and descriptor passes: a workgroup is four waves over consecutive keypoints of one (frame, level).  A frame's
+// workgroups are numbered level-major and every level gets as many as its kp_cap needs (orb_plan_kp_blocks); the table goes BY VALUE
+// in the kernel arguments (as FastTab) and a workgroup finds its level with a scalar walk over it.
+#define ORB_IC_KP_PER_WG 32      // ic_angle_kernel: 4 waves x 8 keypoints
+#define ORB_DESC_KP_PER_WG 16    // describe_kernel: 4 waves x 4 keypoints
+// first workgroup of level l in a frame; from [nlevels] on: the workgroups per frame.  (Dword aligned: the kernels read it with scalar loads.)
+struct alignas(4) KpBlockTab { uint16_t first[ORB_MAX_LEVELS + 1]; };
+
 struct OrbLevelKp {            // a keypoint in level coordinates, after the octree
     int16_t x, y;
     float response;
