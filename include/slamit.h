@@ -791,6 +791,87 @@ int slamit_pnp_ransac_batch(int device, int nproblems, const slamit_pnp_problem*
 int slamit_pnp_ransac(int device, const slamit_pnp_problem* prob, slamit_pnp_result* res);
 int slamit_pnp_refine_batch(int device, int nproblems, const slamit_pnp_refine_problem* probs, slamit_pnp_refine_result* results);
 
+/* ---- Initializer: batched H / F RANSAC and the motion check (monocular initialisation, after SearchForInitialization) ----
+ * slamit_init_hyp_batch is the body of FindHomography and FindFundamental (src/Initializer.cc:133-232) for n_hyp eight-match sets of
+ * one frame pair: per set ComputeH21 and ComputeF21 on the normalised pairs, H21i = T2inv Hn T1 and F21i = T2t Fn T1, then
+ * CheckHomography / CheckFundamental over all n matches; the score is the reference's float sum in match order, bit for bit.  One
+ * wavefront per (problem, hypothesis, model); a batch of frame pairs is one launch.  Normalize runs on the host over ALL keypoints
+ * of each frame.  slamit_init_reconstruct_batch is ReconstructH up to its eight motions or ReconstructF's four (:479-741) with
+ * CheckRT (:807-916) for each over the matches of subset_bits (the kept hypothesis' inlier_bits); one workgroup per (problem,
+ * motion).  Sampling and the scans stay with the caller (shim/Initializer.h, api.Initializer); the scans are the five small
+ * functions below.  cv::SVDecomp is unpinned: every decomposition is a Jacobi in double with a fixed number of sweeps, its
+ * singular vectors carry sign rule (a) and are rounded to float once (csrc/two_view.h).
+ * n < 8, an index outside its table, a set that repeats an index, n above SLAMIT_INIT_MAX_N, n_hyp above SLAMIT_INIT_MAX_HYP or a
+ * null array fails with SLAMIT_ERR_ARG and a message before anything is launched; nproblems == 0 or n_hyp == 0 writes nothing. */
+#define SLAMIT_INIT_MAX_N 8192      /* matches per problem */
+#define SLAMIT_INIT_MAX_HYP 1024    /* hypotheses per problem (Tracking asks for 200) */
+#define SLAMIT_INIT_H 0
+#define SLAMIT_INIT_F 1
+
+struct slamit_init_problem {
+    int32_t n1;                /* keypoints of the reference frame */
+    const float* keys1;        /* n1 x 2: mvKeysUn[i].pt of frame 1 */
+    int32_t n2;
+    const float* keys2;        /* n2 x 2: frame 2 */
+    int32_t n;                 /* matches: mvMatches12 */
+    const int32_t* matches;    /* n x 2: index into keys1, index into keys2 */
+    float sigma;               /* mSigma */
+    int32_t n_hyp;             /* sets to evaluate */
+    const int32_t* sets;       /* n_hyp x 8 indices into the n matches, distinct inside a set */
+};
+typedef struct slamit_init_problem slamit_init_problem;
+
+struct slamit_init_result {    /* every array holds the n_hyp entries of the homographies first, then those of the fundamentals */
+    float* model;              /* 2 x n_hyp x 9: H21i, F21i row-major */
+    float* score;              /* 2 x n_hyp: currentScore */
+    int32_t* n_inliers;        /* 2 x n_hyp: members of vbCurrentInliers */
+    uint32_t* inlier_bits;     /* 2 x n_hyp x ((n+31)/32), nullable: bit i = vbCurrentInliers[i] */
+};
+typedef struct slamit_init_result slamit_init_result;
+
+struct slamit_init_reconstruct_problem {
+    int32_t n1;
+    const float* keys1;        /* as in slamit_init_problem */
+    int32_t n2;
+    const float* keys2;
+    int32_t n;
+    const int32_t* matches;
+    float sigma;
+    int32_t kind;              /* SLAMIT_INIT_H or SLAMIT_INIT_F */
+    float model[9];            /* the kept H21 or F21 */
+    float K[9];                /* mK row-major */
+    const uint32_t* subset_bits;   /* (n+31)/32 words: bit i = vbMatchesInliers[i]; bits past n are ignored */
+};
+typedef struct slamit_init_reconstruct_problem slamit_init_reconstruct_problem;
+
+struct slamit_init_reconstruct_result {
+    int32_t decomposable;      /* out: 0 = ReconstructH's d1/d2, d2/d3 early return (no motion was checked); 1 otherwise */
+    int32_t n_motions;         /* out: 8 for H, 4 for F; only that many entries of the arrays below are written */
+    float R[72];               /* out: n_motions x 9 */
+    float t[24];               /* out: n_motions x 3 */
+    int32_t n_good[8];         /* out: CheckRT's return value */
+    float cos_sel[8];          /* out: the min(50, n_good - 1)-th smallest accepted cosParallax; 1 when n_good is 0 */
+    uint8_t* status;           /* n_motions x n, nullable: 0 counted in n_good, 1 outside the subset, 2 point not finite, 3 / 4 depth in
+                                  camera 1 / 2, 5 / 6 reprojection in image 1 / 2 */
+    float* points;             /* n_motions x n x 3, nullable: p3dC1 of match i (zero for status 1 and 2) */
+    uint32_t* good_bits;       /* n_motions x ((n+31)/32), nullable: bit i = vbGood of match i's keypoint */
+};
+typedef struct slamit_init_reconstruct_result slamit_init_reconstruct_result;
+
+/* nproblems frame pairs in one launch each (host pointers, synchronous). */
+int slamit_init_hyp_batch(int device, int nproblems, const slamit_init_problem* probs, slamit_init_result* results);
+int slamit_init_hyp(int device, const slamit_init_problem* prob, slamit_init_result* res);
+int slamit_init_reconstruct_batch(int device, int nproblems, const slamit_init_reconstruct_problem* probs, slamit_init_reconstruct_result* results);
+int slamit_init_reconstruct(int device, const slamit_init_reconstruct_problem* prob, slamit_init_reconstruct_result* res);
+/* The host scans.  best_hypothesis: the first strict maximum of the scores above 0 (-1: none).  choose_h: SH / (SH + SF) > 0.40.
+ * parallax_deg: acos(cos_sel) * 180 / pi, 0 when n_good is 0.  pick_f / pick_h: the winning motion of ReconstructF's nsimilar /
+ * nMinGood / maxGood cascade and of ReconstructH's best / second-best rule, -1 when the initialisation is rejected. */
+int slamit_init_best_hypothesis(int n_hyp, const float* score);
+int slamit_init_choose_h(float SH, float SF);
+float slamit_init_parallax_deg(int n_good, float cos_sel);
+int slamit_init_pick_f(const int32_t* n_good, const float* parallax, int n_inliers, float min_parallax, int min_triangulated);
+int slamit_init_pick_h(const int32_t* n_good, const float* parallax, int n_inliers, float min_parallax, int min_triangulated);
+
 /* ---- CreateNewMapPoints: batched two-view triangulation (local mapping, between SearchForTriangulation and the new map point) ----
  * The per-pair body of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:348-483), monocular: parallax of the two rays, the
  * 4x4 linear triangulation (smallest right singular vector, one-sided Jacobi in float), both depth tests, both reprojection

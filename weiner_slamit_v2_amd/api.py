@@ -149,6 +149,28 @@ class PnpRefineResult(C.Structure):
 PNP_MAX_N, PNP_MAX_HYP = 8192, 1024   # SLAMIT_PNP_MAX_N / _MAX_HYP
 
 
+class InitProblem(C.Structure):
+    _fields_ = [("n1", C.c_int32), ("keys1", C.c_void_p), ("n2", C.c_int32), ("keys2", C.c_void_p), ("n", C.c_int32), ("matches", C.c_void_p),
+                ("sigma", C.c_float), ("n_hyp", C.c_int32), ("sets", C.c_void_p)]
+
+
+class InitResult(C.Structure):
+    _fields_ = [("model", C.c_void_p), ("score", C.c_void_p), ("n_inliers", C.c_void_p), ("inlier_bits", C.c_void_p)]
+
+
+class InitReconstructProblem(C.Structure):
+    _fields_ = [("n1", C.c_int32), ("keys1", C.c_void_p), ("n2", C.c_int32), ("keys2", C.c_void_p), ("n", C.c_int32), ("matches", C.c_void_p),
+                ("sigma", C.c_float), ("kind", C.c_int32), ("model", C.c_float * 9), ("K", C.c_float * 9), ("subset_bits", C.c_void_p)]
+
+
+class InitReconstructResult(C.Structure):
+    _fields_ = [("decomposable", C.c_int32), ("n_motions", C.c_int32), ("R", C.c_float * 72), ("t", C.c_float * 24), ("n_good", C.c_int32 * 8),
+                ("cos_sel", C.c_float * 8), ("status", C.c_void_p), ("points", C.c_void_p), ("good_bits", C.c_void_p)]
+
+
+INIT_MAX_N, INIT_MAX_HYP, INIT_H, INIT_F = 8192, 1024, 0, 1   # SLAMIT_INIT_MAX_N / _MAX_HYP / _H / _F
+
+
 class TriangulateProblem(C.Structure):
     _fields_ = [("Tcw1", C.c_float * 12), ("Tcw2", C.c_float * 12), ("intr1", C.c_float * 6), ("intr2", C.c_float * 6), ("n", C.c_int32),
                 ("n_levels", C.c_int32), ("kp1_xy", C.c_void_p), ("kp2_xy", C.c_void_p), ("octave1", C.c_void_p), ("octave2", C.c_void_p),
@@ -532,7 +554,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_map_edit_apply", "slamit_map_edit_workspace", "slamit_map_edit_batch_dev", "slamit_map_replace_apply", "slamit_map_replace_workspace", "slamit_map_replace_batch_dev", "slamit_check_replaced", "slamit_check_replaced_batch_dev", "slamit_kf_erase_apply", "slamit_kf_erase_workspace", "slamit_kf_erase_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_init_hyp", "slamit_init_hyp_batch", "slamit_init_reconstruct", "slamit_init_reconstruct_batch", "slamit_init_best_hypothesis", "slamit_init_choose_h", "slamit_init_parallax_deg", "slamit_init_pick_f", "slamit_init_pick_h", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_map_edit_apply", "slamit_map_edit_workspace", "slamit_map_edit_batch_dev", "slamit_map_replace_apply", "slamit_map_replace_workspace", "slamit_map_replace_batch_dev", "slamit_check_replaced", "slamit_check_replaced_batch_dev", "slamit_kf_erase_apply", "slamit_kf_erase_workspace", "slamit_kf_erase_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -587,6 +609,16 @@ def lib():
         L.slamit_pnp_ransac_batch.argtypes = [i32, i32, C.POINTER(PnpProblem), C.POINTER(PnpResult)]
         L.slamit_pnp_ransac.argtypes = [i32, C.POINTER(PnpProblem), C.POINTER(PnpResult)]
         L.slamit_pnp_refine_batch.argtypes = [i32, i32, C.POINTER(PnpRefineProblem), C.POINTER(PnpRefineResult)]
+        L.slamit_init_hyp_batch.argtypes = [i32, i32, C.POINTER(InitProblem), C.POINTER(InitResult)]
+        L.slamit_init_hyp.argtypes = [i32, C.POINTER(InitProblem), C.POINTER(InitResult)]
+        L.slamit_init_reconstruct_batch.argtypes = [i32, i32, C.POINTER(InitReconstructProblem), C.POINTER(InitReconstructResult)]
+        L.slamit_init_reconstruct.argtypes = [i32, C.POINTER(InitReconstructProblem), C.POINTER(InitReconstructResult)]
+        L.slamit_init_best_hypothesis.argtypes = [i32, vp]
+        L.slamit_init_choose_h.argtypes = [f32, f32]
+        L.slamit_init_parallax_deg.argtypes = [i32, f32]
+        L.slamit_init_parallax_deg.restype = f32
+        L.slamit_init_pick_f.argtypes = [vp, vp, i32, f32, i32]
+        L.slamit_init_pick_h.argtypes = [vp, vp, i32, f32, i32]
         L.slamit_triangulate_batch.argtypes = [i32, i32, C.POINTER(TriangulateProblem), C.POINTER(TriangulateResult)]
         L.slamit_triangulate.argtypes = [i32, C.POINTER(TriangulateProblem), C.POINTER(TriangulateResult)]
         L.slamit_triangulate_stereo_batch.argtypes = [i32, i32, C.POINTER(TriangulateProblem), C.POINTER(C.POINTER(TriangulateStereo)), C.POINTER(TriangulateResult), C.POINTER(vp)]
@@ -1941,6 +1973,184 @@ class PnPsolver:
     def find(self):
         T, _, vb, n = self.iterate(self.mRansacMaxIts)
         return T, vb, n
+
+
+def _init_frames(pr, q):
+    """keys1 / keys2 / matches of a problem dict into the record q; -> (arrays kept alive, n)."""
+    k = {"keys1": np.ascontiguousarray(pr["keys1"], np.float32).reshape(-1, 2), "keys2": np.ascontiguousarray(pr["keys2"], np.float32).reshape(-1, 2),
+         "matches": np.ascontiguousarray(pr["matches"], np.int32).reshape(-1, 2)}
+    q.n1, q.n2, q.n = len(k["keys1"]), len(k["keys2"]), len(k["matches"])
+    q.sigma = float(pr.get("sigma", 1.0))
+    for key, a in k.items():
+        setattr(q, key, a.ctypes.data)
+    return k, int(q.n)
+
+
+def init_hypotheses(problems, device=0, want_bits=True):
+    """FindHomography's and FindFundamental's loop bodies (Initializer.cc:133-232) for one problem dict or a list of them in ONE
+    device call.  A problem has keys1 (n1, 2), keys2 (n2, 2) float32, matches (n, 2) int32 (index into keys1, into keys2), sigma and
+    sets (n_hyp, 8) int32 indices into the matches.  -> dict(s) model (2, n_hyp, 9) float32 (row 0 the H21i, row 1 the F21i), score
+    (2, n_hyp) float32, n_inliers (2, n_hyp), inlier_bits (2, n_hyp, (n + 31) // 32)."""
+    single = isinstance(problems, dict)
+    plist = [problems] if single else list(problems)
+    m = len(plist)
+    P, R = (InitProblem * m)(), (InitResult * m)()
+    keep, outs = [], []
+    for i, pr in enumerate(plist):
+        k, n = _init_frames(pr, P[i])
+        k["sets"] = np.ascontiguousarray(pr["sets"], np.int32).reshape(-1, 8)
+        nh = len(k["sets"])
+        P[i].n_hyp, P[i].sets = nh, k["sets"].ctypes.data
+        o = {"model": np.zeros((2, nh, 9), np.float32), "score": np.zeros((2, nh), np.float32), "n_inliers": np.zeros((2, nh), np.int32)}
+        R[i].model, R[i].score, R[i].n_inliers = o["model"].ctypes.data, o["score"].ctypes.data, o["n_inliers"].ctypes.data
+        if want_bits:
+            o["inlier_bits"] = np.zeros((2, nh, (n + 31) // 32), np.uint32)
+            R[i].inlier_bits = o["inlier_bits"].ctypes.data
+        keep.append(k)
+        outs.append(o)
+    _check(lib().slamit_init_hyp_batch(device, m, P, R), "slamit_init_hyp_batch")
+    del keep
+    return outs[0] if single else outs
+
+
+def init_reconstruct(problems, device=0):
+    """ReconstructH's eight motions or ReconstructF's four with CheckRT for each (Initializer.cc:479-916) for one problem dict or a
+    list of them in ONE device call.  A problem has keys1, keys2, matches, sigma as for init_hypotheses, kind (INIT_H / INIT_F), model
+    (9), K (3, 3) and subset_bits ((n + 31) // 32 uint32, a row of inlier_bits) or subset (n bool).  -> dict(s) decomposable, R (m, 9),
+    t (m, 3), n_good (m), cos_sel (m), status (m, n) uint8, points (m, n, 3), good_bits (m, words) with m = 8 or 4."""
+    single = isinstance(problems, dict)
+    plist = [problems] if single else list(problems)
+    m = len(plist)
+    P, R = (InitReconstructProblem * m)(), (InitReconstructResult * m)()
+    keep, outs = [], []
+    for i, pr in enumerate(plist):
+        k, n = _init_frames(pr, P[i])
+        if "subset_bits" in pr:
+            k["subset_bits"] = np.ascontiguousarray(pr["subset_bits"], np.uint32).reshape(-1)
+        else:
+            f = np.zeros(((n + 31) // 32) * 32, np.uint8)
+            f[:n] = np.asarray(pr["subset"], bool).reshape(-1)
+            k["subset_bits"] = np.packbits(f, bitorder="little").view(np.uint32)
+        if len(k["subset_bits"]) != (n + 31) // 32:
+            raise SlamitError("init_reconstruct: the subset does not have (n + 31) // 32 words")
+        kind = int(pr["kind"])
+        nm = 8 if kind == INIT_H else 4
+        P[i].kind, P[i].subset_bits = kind, k["subset_bits"].ctypes.data
+        P[i].model = (C.c_float * 9)(*[float(v) for v in np.asarray(pr["model"], np.float32).reshape(9)])
+        P[i].K = (C.c_float * 9)(*[float(v) for v in np.asarray(pr["K"], np.float32).reshape(9)])
+        o = {"status": np.zeros((nm, n), np.uint8), "points": np.zeros((nm, n, 3), np.float32), "good_bits": np.zeros((nm, (n + 31) // 32), np.uint32)}
+        R[i].status, R[i].points, R[i].good_bits = o["status"].ctypes.data, o["points"].ctypes.data, o["good_bits"].ctypes.data
+        keep.append(k)
+        outs.append(o)
+    _check(lib().slamit_init_reconstruct_batch(device, m, P, R), "slamit_init_reconstruct_batch")
+    for i, o in enumerate(outs):
+        nm = int(R[i].n_motions)
+        o["decomposable"] = int(R[i].decomposable)
+        o["R"] = np.array(R[i].R, np.float32)[:9 * nm].reshape(nm, 9)
+        o["t"] = np.array(R[i].t, np.float32)[:3 * nm].reshape(nm, 3)
+        o["n_good"] = np.array(R[i].n_good, np.int32)[:nm]
+        o["cos_sel"] = np.array(R[i].cos_sel, np.float32)[:nm]
+    del keep
+    return outs[0] if single else outs
+
+
+def init_select(hyp, reco=None, min_parallax=1.0, min_triangulated=50):
+    """The host scans (csrc/two_view.h through the library).  With `hyp` alone: -> dict(best_h, best_f, SH, SF, kind) -- the strict >
+    first-best of each model and RH > 0.40.  With the result `reco` of init_reconstruct on the kept hypothesis and its inlier count
+    n_inliers in `hyp["N"]`: adds parallax (m) in degrees and motion (the winner, -1 = rejected)."""
+    L = lib()
+    sel = {}
+    for r, name in ((0, "h"), (1, "f")):
+        sc = np.ascontiguousarray(hyp["score"][r], np.float32)
+        sel["best_" + name] = int(L.slamit_init_best_hypothesis(len(sc), sc.ctypes.data))
+    sel["SH"] = np.float32(hyp["score"][0][sel["best_h"]]) if sel["best_h"] >= 0 else np.float32(0)
+    sel["SF"] = np.float32(hyp["score"][1][sel["best_f"]]) if sel["best_f"] >= 0 else np.float32(0)
+    sel["kind"] = INIT_H if L.slamit_init_choose_h(float(sel["SH"]), float(sel["SF"])) else INIT_F
+    if reco is not None:
+        ng = np.ascontiguousarray(reco["n_good"], np.int32)
+        par = np.array([L.slamit_init_parallax_deg(int(g), float(c)) for g, c in zip(ng, reco["cos_sel"])], np.float32)
+        pick = L.slamit_init_pick_h if len(ng) == 8 else L.slamit_init_pick_f
+        sel["parallax"] = par
+        sel["motion"] = int(pick(ng.ctypes.data, par.ctypes.data, int(hyp["N"]), float(min_parallax), int(min_triangulated))) if reco["decomposable"] else -1
+    return sel
+
+
+class Initializer:
+    """Initializer (include/Initializer.h) on POD inputs: keys1 (n1, 2) = the reference frame's mvKeysUn, K (3, 3), sigma, iterations.
+    Initialize(keys2, vMatches12) with vMatches12 (n1) int (-1 = unmatched) -> (ok, R21 (3, 3), t21 (3), vP3D (n1, 3), vbTriangulated
+    (n1) bool) and leaves kind, motion and the raw device results in self.last.  `rand_int(lo, hi)` stands for
+    DUtils::Random::RandomInt.  InitializeAll runs a list of (initializer, keys2, vMatches12) in two device calls."""
+
+    def __init__(self, keys1, K, sigma=1.0, iterations=200, rand_int=None, device=0):
+        self.keys1 = np.ascontiguousarray(keys1, np.float32).reshape(-1, 2)
+        self.K = np.ascontiguousarray(K, np.float32).reshape(3, 3)
+        self.sigma, self.iterations, self.device = float(sigma), int(iterations), device
+        if rand_int is None:
+            rs = np.random.RandomState(0)
+            rand_int = lambda lo, hi: int(rs.randint(lo, hi + 1))   # noqa: E731
+        self.rand_int = rand_int
+        self.last = None
+
+    @staticmethod
+    def sample_sets(N, count, rand_int):
+        """The sampler of Initialize (:91-106): eight draws without replacement per set."""
+        out = np.zeros((count, 8), np.int32)
+        for it in range(count):
+            avail = list(range(N))
+            for j in range(8):
+                randi = rand_int(0, len(avail) - 1)
+                out[it, j] = avail[randi]
+                avail[randi] = avail[-1]
+                avail.pop()
+        return out
+
+    def _problem(self, keys2, vMatches12, sets=None):
+        vm = np.asarray(vMatches12, np.int64).reshape(-1)
+        i1 = np.flatnonzero(vm >= 0)
+        matches = np.stack([i1, vm[i1]], axis=1).astype(np.int32)
+        if sets is None:
+            sets = self.sample_sets(len(matches), self.iterations, self.rand_int)
+        return {"keys1": self.keys1, "keys2": np.ascontiguousarray(keys2, np.float32).reshape(-1, 2), "matches": matches, "sigma": self.sigma,
+                "sets": sets, "K": self.K}
+
+    @staticmethod
+    def InitializeAll(jobs, device=0, sets=None):
+        """jobs: (initializer, keys2, vMatches12).  Two device calls for all of them; -> the list of Initialize results."""
+        probs = [ini._problem(k2, vm, None if sets is None else sets[j]) for j, (ini, k2, vm) in enumerate(jobs)]
+        hyps = init_hypotheses(probs, device)
+        recos_in = []
+        for pr, hy in zip(probs, hyps):
+            sel = init_select(hy)
+            kind = sel["kind"]
+            b = sel["best_h"] if kind == INIT_H else sel["best_f"]
+            n = len(pr["matches"])
+            bits = hy["inlier_bits"][kind][b] if b >= 0 else np.zeros((n + 31) // 32, np.uint32)   # no score above 0: an empty model and no inliers
+            model = hy["model"][kind][b] if b >= 0 else np.zeros(9, np.float32)
+            hy["N"] = int(hy["n_inliers"][kind][b]) if b >= 0 else 0
+            hy["sel"] = sel
+            recos_in.append(dict(pr, kind=kind, model=model, subset_bits=bits))
+        recos = init_reconstruct(recos_in, device)
+        outs = []
+        for (ini, _, _), pr, hy, rc in zip(jobs, probs, hyps, recos):
+            sel = dict(hy["sel"], **init_select(hy, rc))
+            n1 = len(ini.keys1)
+            R21, t21 = np.zeros((3, 3), np.float32), np.zeros(3, np.float32)
+            vP3D, vbT = np.zeros((n1, 3), np.float32), np.zeros(n1, bool)
+            mo = sel["motion"]
+            if mo >= 0:
+                R21, t21 = rc["R"][mo].reshape(3, 3).copy(), rc["t"][mo].copy()
+                i1 = pr["matches"][:, 0]
+                counted = rc["status"][mo] == 0
+                vP3D[i1[counted]] = rc["points"][mo][counted]
+                n = len(i1)
+                good = np.unpackbits(rc["good_bits"][mo].view(np.uint8), bitorder="little")[:n].astype(bool)
+                vbT[i1[good]] = True
+            ini.last = {"problem": pr, "hyp": hy, "reco": rc, "sel": sel, "kind": sel["kind"], "motion": mo}
+            outs.append((mo >= 0, R21, t21, vP3D, vbT))
+        return outs
+
+    def Initialize(self, keys2, vMatches12, sets=None):
+        return Initializer.InitializeAll([(self, keys2, vMatches12)], self.device, None if sets is None else [sets])[0]
 
 
 _TRI_STEREO_ARRAYS = ("ur1", "ur2", "depth1", "depth2", "raw1_xy", "raw2_xy")

@@ -44,13 +44,11 @@ namespace ORB_SLAM2 {
 // ---- host logic, free of the device and of the caller's types (tests/test_shim_pnpsolver.py drives it on the CPU) ----
 namespace pnpsolver {
 
-// DUtils::Random::RandomInt(min, max) over rand(); RandomInt() lets a caller (or a test) put its own source in
-inline int DefaultRandomInt(int min, int max) {
-    const int d = max - min + 1;
-    return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min;
-}
-typedef int (*RandomIntFn)(int, int);
-inline RandomIntFn& RandomInt() { static RandomIntFn fn = DefaultRandomInt; return fn; }
+// DUtils::Random::RandomInt(min, max) over rand(); RandomInt() lets a caller (or a test) put its own source in (shim_common.h:
+// the Initializer draws from the same hook)
+using shim::DefaultRandomInt;
+using shim::RandomIntFn;
+using shim::RandomInt;
 
 struct Params { int minInliers, maxIts; float epsilon; };
 

@@ -35,6 +35,14 @@ typedef Point_<int> Point2i;
 typedef Point2i Point;
 typedef Point_<float> Point2f;
 
+template <typename T>
+struct Point3_ {
+    T x, y, z;
+    Point3_() : x(0), y(0), z(0) {}
+    Point3_(T x_, T y_, T z_) : x(x_), y(y_), z(z_) {}
+};
+typedef Point3_<float> Point3f;
+
 struct Size {
     int width, height;
     Size() : width(0), height(0) {}

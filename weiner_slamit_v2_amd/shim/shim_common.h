@@ -1,11 +1,12 @@
 // shim_common.h — what the class headers of the shim share: the per-thread LastStatus() cell with its report / refuse
-// step, the rotation-consistency histogram of the matcher's searches and the cv::Mat loads.  Header only; a program that
+// step, the RandomInt hook of the two RANSAC classes, the rotation-consistency histogram of the matcher's searches and the cv::Mat loads.  Header only; a program that
 // never reports needs no library (the reporting functions are templates: uninstantiated, they reference no slamit_* symbol).
 #ifndef SLAMIT_SHIM_COMMON_H
 #define SLAMIT_SHIM_COMMON_H
 
 #include <math.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include <vector>
 
@@ -34,6 +35,15 @@ inline int refuse(const char* why, int rc = SLAMIT_ERR_ARG) {
     fprintf(stderr, "%s\n", why);
     return 0;
 }
+
+// DUtils::Random::RandomInt(min, max) over rand(); RandomInt() lets a caller (or a test) put its own source in.  One hook for the
+// process: PnPsolver and Initializer both draw from it, as both draw from DUtils::Random in the reference.
+inline int DefaultRandomInt(int min, int max) {
+    const int d = max - min + 1;
+    return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min;
+}
+typedef int (*RandomIntFn)(int, int);
+inline RandomIntFn& RandomInt() { static RandomIntFn fn = DefaultRandomInt; return fn; }
 
 // Loads of a CV_32F cv::Mat, and nothing else: out[stride * r + c] = m(r, c) of the top-left 3 x 3, out[stride * r] = m(r, col).
 template <class MatT>

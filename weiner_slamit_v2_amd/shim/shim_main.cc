@@ -14,6 +14,7 @@
 //     shim_test osim3 <problem.bin> <out.bin>
 //     shim_test sim3solver <problem.bin> <out.bin>
 //     shim_test pnpsolver <problem.bin> <out.bin>
+//     shim_test initializer <pairs.bin> <out.bin>
 //     shim_test triangulate <problem.bin> <out.bin>
 //     shim_test triangulate_stereo <problem.bin> <out.bin>
 //     shim_test frustum <problem.bin> <out.bin>
@@ -36,6 +37,7 @@
 #include "Optimizer.h"
 #include "FrameOps.h"
 #include "PnPsolver.h"
+#include "Initializer.h"
 #include "Sim3Solver.h"
 #include "ORBVocabulary.h"
 #include "KeyFrameDatabase.h"
@@ -1349,6 +1351,84 @@ static int run_stereo(int argc, char** argv) {
     return 0;
 }
 
+// ---- Initializer through the template: a batch of frame pairs in one InitializeAll (two launches), then one Initialize each --------
+// pairs.bin: int32 npairs nrand ; uint32 rand[nrand] (one RandomInt stream, read from its start by each of the two passes) ; per pair:
+//   int32 n1 n2 iterations ; float sigma K[9] keys1[2 n1] keys2[2 n2] ; int32 vMatches12[n1]
+// out.bin: int32 status ; two passes (InitializeAll, then Initialize pair by pair), each per pair: int32 ok kind motion nsets ;
+//   float R21[9] t21[3] (zeros when empty) vP3D[3 n1] ; u8 vbTriangulated[n1] (zeros when empty) ; int32 sets[8 nsets]
+struct MockInitFrame {
+    cv::Mat mK;
+    std::vector<cv::KeyPoint> mvKeysUn;
+};
+static int run_initializer(int argc, char** argv) {
+    if (argc < 4) return 2;
+    std::vector<unsigned char> raw = slurp(argv[2]);
+    Reader Rd{raw.data()};
+    const int np = Rd.get<int>(), nrand = Rd.get<int>();
+    { const uint32_t* r = Rd.arr<uint32_t>(nrand); g_script.assign(r, r + nrand); g_script_pos = 0; }
+    shim::RandomInt() = scripted_random_int;
+    typedef Initializer<MockInitFrame> Init;
+    std::vector<MockInitFrame> ref(np), cur(np);
+    std::vector<std::vector<int> > vm(np);
+    std::vector<int> its(np);
+    std::vector<float> sigma(np);
+    for (int k = 0; k < np; ++k) {
+        const int n1 = Rd.get<int>(), n2 = Rd.get<int>();
+        its[k] = Rd.get<int>(); sigma[k] = Rd.get<float>();
+        const float* K = Rd.arr<float>(9);
+        const float* k1 = Rd.arr<float>(2 * (size_t)n1);
+        const float* k2 = Rd.arr<float>(2 * (size_t)n2);
+        const int32_t* m = Rd.arr<int32_t>(n1);
+        ref[k].mK.create(3, 3, CV_32F);
+        for (int i = 0; i < 9; ++i) ref[k].mK.at<float>(i / 3, i % 3) = K[i];
+        cur[k].mK = ref[k].mK;
+        for (int i = 0; i < n1; ++i) ref[k].mvKeysUn.push_back(cv::KeyPoint(k1[2 * i], k1[2 * i + 1], 31.f));
+        for (int i = 0; i < n2; ++i) cur[k].mvKeysUn.push_back(cv::KeyPoint(k2[2 * i], k2[2 * i + 1], 31.f));
+        vm[k].assign(m, m + n1);
+    }
+    FILE* f = fopen(argv[3], "wb");
+    if (!f) return 2;
+    int status = 0;
+    fwrite(&status, 4, 1, f);
+    for (int pass = 0; pass < 2 && status == 0; ++pass) {
+        g_script_pos = 0;
+        std::vector<Init*> inits;
+        std::vector<Init::Job> jobs;
+        for (int k = 0; k < np; ++k) inits.push_back(new Init(ref[k], sigma[k], its[k]));
+        for (int k = 0; k < np; ++k) jobs.push_back(Init::Job(inits[k], cur[k], vm[k]));
+        if (pass == 0) {
+            status = Init::InitializeAll(jobs);
+        } else {
+            for (int k = 0; k < np && status == 0; ++k) {
+                jobs[k].ok = inits[k]->Initialize(cur[k], vm[k], jobs[k].R21, jobs[k].t21, jobs[k].vP3D, jobs[k].vbTriangulated);
+                status = Init::LastStatus();
+            }
+        }
+        if (status != 0) fprintf(stderr, "initializer failed: %s\n", slamit_last_error());
+        for (int k = 0; k < np && status == 0; ++k) {
+            const Init::Job& J = jobs[k];
+            const int n1 = (int)ref[k].mvKeysUn.size();
+            const int head[4] = {J.ok ? 1 : 0, inits[k]->Kind(), inits[k]->Motion(), (int)(inits[k]->Sets().size() / 8)};
+            fwrite(head, 4, 4, f);
+            float rt[12] = {0};
+            if (!J.R21.empty()) for (int i = 0; i < 9; ++i) rt[i] = J.R21.at<float>(i / 3, i % 3);
+            if (!J.t21.empty()) for (int i = 0; i < 3; ++i) rt[9 + i] = J.t21.at<float>(i, 0);
+            fwrite(rt, 4, 12, f);
+            std::vector<float> p(3 * (size_t)n1, 0.f);
+            std::vector<unsigned char> vb(n1, 0);
+            for (size_t i = 0; i < J.vP3D.size(); ++i) { p[3 * i] = J.vP3D[i].x; p[3 * i + 1] = J.vP3D[i].y; p[3 * i + 2] = J.vP3D[i].z; }
+            for (size_t i = 0; i < J.vbTriangulated.size(); ++i) vb[i] = J.vbTriangulated[i] ? 1 : 0;
+            fwrite(p.data(), 4, p.size(), f); fwrite(vb.data(), 1, vb.size(), f);
+            fwrite(inits[k]->Sets().data(), 4, inits[k]->Sets().size(), f);
+        }
+        for (int k = 0; k < np; ++k) delete inits[k];
+    }
+    fseek(f, 0, SEEK_SET);
+    fwrite(&status, 4, 1, f);
+    fclose(f);
+    return 0;
+}
+
 // ---- PnPsolver through the template: the candidates of one relocalisation, one EvaluateAll (two launches) -------------------------
 // problem.bin: int32 nsolvers nrand ; uint32 rand[nrand] (one RandomInt stream for all solvers in order; the constructors draw
 //   nothing) ; per solver: int32 n lead min_inliers max_its min_set ; float epsilon th2 K[4] p3d[3n] p2d[2n] sigma2[n]
@@ -1756,6 +1836,7 @@ int main(int argc, char** argv) {
     if (mode == "osim3") return run_osim3(argc, argv);
     if (mode == "sim3solver") return run_sim3solver(argc, argv);
     if (mode == "pnpsolver") return run_pnpsolver(argc, argv);
+    if (mode == "initializer") return run_initializer(argc, argv);
     if (mode == "triangulate") return run_triangulate(argc, argv);
     if (mode == "triangulate_stereo") return run_triangulate_stereo(argc, argv);
     if (mode == "frustum") return run_frustum(argc, argv);
