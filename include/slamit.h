@@ -1909,6 +1909,98 @@ struct slamit_check_replaced_batch_rec {
 typedef struct slamit_check_replaced_batch_rec slamit_check_replaced_batch_rec;
 int slamit_check_replaced_batch_dev(int device, const slamit_check_replaced_batch_rec* batch, void* stream);
 
+/* ---- The tail of ORBmatcher::Fuse on the resident tables: an op that picks the replace direction ----
+ * ORBmatcher::Fuse (src/ORBmatcher.cc:853, :955-975) looks at pKF->GetMapPoint(bestIdx) and at both points' Observations() AT THAT
+ * MOMENT and replaces one way, the other way, or adds the observation (csrc/map_fuse.h states the op).  A list of n
+ * ops in slamit_map_replace's record, of kinds SLAMIT_REPLACE_REPLACE, SLAMIT_REPLACE_ADD_OBS (both as above) and SLAMIT_FUSE_FUSE,
+ * is applied AS IF SEQUENTIALLY IN LIST ORDER; the result equals the sequential walk exactly.
+ *   SLAMIT_FUSE_FUSE  a = P, b = the keyframe k, idx = the matched keypoint, octave and weight what goes beside a new observation
+ *                     (weight 2 where mvuRight[idx] >= 0).  Over the state as the earlier ops left it, in this order:
+ *                     idx < 0: OUT_NOMATCH, nothing else is read.  mp_bad[P]: OUT_SKIP_BAD.  P's row holds k: OUT_SKIP_IN_KF.
+ *                     Q = kf_mp[k][idx]; Q == -1: SLAMIT_REPLACE_ADD_OBS of (P, k, idx, octave, weight), OUT_ADDED.  mp_bad[Q]: nothing,
+ *                     OUT_OCCUPANT_BAD.  mp_nobs[Q] > mp_nobs[P]: REPLACE(P -> Q), OUT_P_REPLACED; otherwise REPLACE(Q -> P),
+ *                     OUT_Q_REPLACED (P == Q, on tables that hold one (k, idx) under two points, is Replace's a == b: nothing).
+ * outcome[i] is that code, SLAMIT_FUSE_OUT_PLAIN for the other two kinds; *n_fused counts OUT_ADDED, OUT_OCCUPANT_BAD, OUT_P_REPLACED
+ * and OUT_Q_REPLACED, the reference's return value.  Tables, moved / erased, touched, n_obs_out: as slamit_map_replace_apply.
+ * ALL-OR-NOTHING as there; there is NO per-point ceiling.  obs_cap_out = the old table + the number of ADD_OBS and FUSE ops always
+ * suffices.  Status bits (the values of SLAMIT_REPLACE_*), the first overflow that holds being the one reported: */
+#define SLAMIT_FUSE_FUSE 3
+#define SLAMIT_FUSE_OUT_PLAIN 0
+#define SLAMIT_FUSE_OUT_NOMATCH 1
+#define SLAMIT_FUSE_OUT_SKIP_BAD 2
+#define SLAMIT_FUSE_OUT_SKIP_IN_KF 3
+#define SLAMIT_FUSE_OUT_ADDED 4
+#define SLAMIT_FUSE_OUT_OCCUPANT_BAD 5
+#define SLAMIT_FUSE_OUT_P_REPLACED 6
+#define SLAMIT_FUSE_OUT_Q_REPLACED 7
+#define SLAMIT_FUSE_OBS_OVERFLOW 2        /* an involved row above SLAMIT_UPKEEP_MAX_OBS on input, or pushed past it */
+#define SLAMIT_FUSE_TABLE_OVERFLOW 4      /* the new table needs more than obs_cap_out entries: n_obs_out says how many */
+#define SLAMIT_FUSE_BAD_SLOT 8            /* device form: an op or an observation with a slot outside its table was skipped */
+#define SLAMIT_FUSE_MAX_OPS 16384         /* ops per list */
+
+/* One list over one map (host pointers, synchronous).  outcome[n], moved[n], erased[n], touched[n_mp], *n_touched, *n_fused,
+ * *n_obs_out in / out, *status out: entries past the counts are left as the caller filled them; with an overflow bit everything but
+ * *status (and *n_obs_out for TABLE_OVERFLOW) is.  What slamit_map_replace_apply refuses is refused here (a FUSE op with idx < 0 is
+ * not read further), and so is an entry of kf_mp outside [-1, n_mp); n above SLAMIT_FUSE_MAX_OPS fails with SLAMIT_ERR_CAPACITY;
+ * each with a message and before anything is launched. */
+int slamit_map_fuse_apply(int device, const slamit_map_index* map, const slamit_replace_index* index, int32_t n, const slamit_map_replace* ops,
+                          int32_t* outcome, int32_t* moved, int32_t* erased, int32_t* touched, int32_t* n_touched, int32_t* n_fused, int32_t* n_obs_out,
+                          int32_t* status);
+
+/* One list per map for n_maps maps, everything resident; records as slamit_map_replace_batch_dev takes them.  An op with idx >= 0
+ * whose point, keyframe, index or weight lies outside its range is skipped whole, never dereferenced, and so is a FUSE op that meets
+ * an occupant outside [-1, n_mp); an observation whose (k, idx) lies outside kf_mp is carried along without its kf_mp write; all set
+ * SLAMIT_FUSE_BAD_SLOT in d_status[m].  Asynchronous on `stream`, no synchronisation, no state; the head of the workspace is cleared
+ * on the stream by the call.  One wavefront per map walks the list in order.  ZERO-INITIALISE the record.
+ * WORKSPACE, with S = mp_cap + 1, ninv = min(2 cap, mp_cap) and every array rounded up to 16 bytes, per map:
+ *   32 + 4 (4 S + 2 (ceil(S / 256) + 1)) + 4 * 3 cap + 4 + 4 kfmp_cap + 4 (1 + 7) ninv + 10 * SLAMIT_UPKEEP_MAX_OBS * ninv bytes
+ * -- the status words, four rows over the points, the scan's sums, outcome / moved / erased, the count, the working image of kf_mp,
+ * and a working row with its columns per involved point. */
+struct slamit_map_fuse_batch_rec {
+    int32_t n_maps, cap, mp_cap, kfmp_cap;
+    const slamit_map_index* maps;      /* HOST [n_maps], device pointers inside; n_maps <= SLAMIT_LOCAL_MAP_MAX_MAPS */
+    const slamit_replace_index* index; /* HOST [n_maps], device pointers inside */
+    const slamit_map_replace* d_ops;   /* [n_maps][cap], cap <= SLAMIT_FUSE_MAX_OPS */
+    const int32_t* d_n;                /* [n_maps] */
+    int32_t* d_outcome;                /* [n_maps][cap] in / out */
+    int32_t* d_moved;                  /* [n_maps][cap] in / out */
+    int32_t* d_erased;                 /* [n_maps][cap] in / out */
+    int32_t* d_touched;                /* [n_maps][mp_cap] in / out */
+    int32_t* d_n_touched;              /* [n_maps] in / out */
+    int32_t* d_n_fused;                /* [n_maps] in / out */
+    int32_t* d_n_obs_out;              /* [n_maps] in / out */
+    int32_t* d_status;                 /* [n_maps] out */
+    void* d_workspace;                 /* slamit_map_fuse_workspace(n_maps, cap, mp_cap, kfmp_cap) bytes, 8-byte aligned */
+    size_t workspace_bytes;
+};
+typedef struct slamit_map_fuse_batch_rec slamit_map_fuse_batch_rec;
+size_t slamit_map_fuse_workspace(int n_maps, int cap, int mp_cap, int kfmp_cap);
+int slamit_map_fuse_batch_dev(int device, const slamit_map_fuse_batch_rec* batch, void* stream);
+
+/* The FUSE ops of a guided search, written where slamit_map_fuse_batch_dev reads them: one lane per query, no workspace, asynchronous
+ * on `stream`.  Target f (one frame of the search: the queries are map points projected into one keyframe) fills the slice
+ * [d_base[f], d_base[f] + q_cap) of map d_frame_map[f]'s list: query q < d_m[f] becomes {FUSE, a = d_query_point[f][q], b =
+ * d_frame_kf[f], idx = d_match_kp[f][q] (-1 stays -1), octave = d_kps_un[f][idx].octave, weight = 2 where d_kp_ur is given and
+ * d_kp_ur[f][idx] >= 0, else 1}; a slot past d_m[f] becomes a no-match op, so slices lie back to back without compaction.  d_n[m] =
+ * the end of map m's last slice (0 for a map without one).  A target whose map lies outside [0, n_maps) or whose slice does not fit
+ * in [0, cap) writes nothing and sets SLAMIT_FUSE_BAD_SLOT in d_status[f].  ZERO-INITIALISE the record. */
+struct slamit_fuse_list_batch_rec {
+    int32_t nframes, n_maps, kp_cap, q_cap, cap, reserved;
+    const int32_t* d_m;                /* [nframes] queries per target */
+    const int32_t* d_match_kp;         /* [nframes][q_cap]: what the guided search wrote */
+    const int32_t* d_query_point;      /* [nframes][q_cap]: the slot of query q's map point */
+    const slamit_kp* d_kps_un;         /* [nframes][kp_cap] (octave is read) */
+    const float* d_kp_ur;              /* [nframes][kp_cap] or NULL: mvuRight */
+    const int32_t* d_frame_map;        /* [nframes] */
+    const int32_t* d_frame_kf;         /* [nframes]: the target's keyframe slot */
+    const int32_t* d_base;             /* [nframes]: where the target's slice begins in its map's list */
+    slamit_map_replace* d_ops;         /* [n_maps][cap] out, cap <= SLAMIT_FUSE_MAX_OPS */
+    int32_t* d_n;                      /* [n_maps] out */
+    int32_t* d_status;                 /* [nframes] out */
+};
+typedef struct slamit_fuse_list_batch_rec slamit_fuse_list_batch_rec;
+int slamit_fuse_list_batch_dev(int device, const slamit_fuse_list_batch_rec* batch, void* stream);
+
 /* ---- KeyFrame::SetBadFlag on the resident tables: graph rows and the spanning tree ----
  * KeyFrame::SetBadFlag (src/KeyFrame.cc:460-552) with EraseConnection / UpdateBestCovisibles (:560-574, :142-161) and ChangeParent /
  * AddChild / EraseChild (:388-405) over the tables of slamit_map_index and the arrays of slamit_tree_index (csrc/kf_erase.h states the

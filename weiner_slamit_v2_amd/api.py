@@ -443,6 +443,19 @@ class MapReplaceBatchRec(C.Structure):   # struct slamit_map_replace_batch_rec
                 ("workspace_bytes", C.c_size_t)]
 
 
+class MapFuseBatchRec(C.Structure):   # struct slamit_map_fuse_batch_rec
+    _fields_ = [("n_maps", C.c_int32), ("cap", C.c_int32), ("mp_cap", C.c_int32), ("kfmp_cap", C.c_int32), ("maps", C.POINTER(MapIndexRec)),
+                ("index", C.POINTER(ReplaceIndexRec)), ("d_ops", C.c_void_p), ("d_n", C.c_void_p), ("d_outcome", C.c_void_p), ("d_moved", C.c_void_p),
+                ("d_erased", C.c_void_p), ("d_touched", C.c_void_p), ("d_n_touched", C.c_void_p), ("d_n_fused", C.c_void_p), ("d_n_obs_out", C.c_void_p),
+                ("d_status", C.c_void_p), ("d_workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class FuseListBatchRec(C.Structure):   # struct slamit_fuse_list_batch_rec
+    _fields_ = [("nframes", C.c_int32), ("n_maps", C.c_int32), ("kp_cap", C.c_int32), ("q_cap", C.c_int32), ("cap", C.c_int32), ("reserved", C.c_int32),
+                ("d_m", C.c_void_p), ("d_match_kp", C.c_void_p), ("d_query_point", C.c_void_p), ("d_kps_un", C.c_void_p), ("d_kp_ur", C.c_void_p),
+                ("d_frame_map", C.c_void_p), ("d_frame_kf", C.c_void_p), ("d_base", C.c_void_p), ("d_ops", C.c_void_p), ("d_n", C.c_void_p), ("d_status", C.c_void_p)]
+
+
 class CheckReplacedBatchRec(C.Structure):   # struct slamit_check_replaced_batch_rec
     _fields_ = [("nframes", C.c_int32), ("n_maps", C.c_int32), ("cap", C.c_int32), ("reserved", C.c_int32), ("n_mp", C.POINTER(C.c_int32)),
                 ("d_mp_replaced", C.POINTER(C.c_void_p)), ("d_frame_map", C.c_void_p), ("d_n", C.c_void_p), ("d_frame_mp", C.c_void_p), ("d_status", C.c_void_p)]
@@ -454,6 +467,12 @@ REPLACE_STATUS = {"OP_OVERFLOW": 1, "OBS_OVERFLOW": 2, "TABLE_OVERFLOW": 4, "BAD
 REPLACE_REFUSED = 1 | 2 | 4   # with one of these nothing was written but the status (and n_obs_out for TABLE_OVERFLOW)
 REPLACE_MAX_OPS, REPLACE_MAX_PER_POINT, CHECK_REPLACED_MAX_N = 16384, 64, 65536
 REPLACE_DTYPE = np.dtype([("kind", "<i4"), ("a", "<i4"), ("b", "<i4"), ("idx", "<i4"), ("octave", "u1"), ("weight", "u1"), ("pad", "u1", 2)])
+# SLAMIT_FUSE_*: the third kind of a fuse list, its outcomes, the status bits (REPLACE's values) and the ceiling
+FUSE_FUSE = 3
+FUSE_OUT = {"PLAIN": 0, "NOMATCH": 1, "SKIP_BAD": 2, "SKIP_IN_KF": 3, "ADDED": 4, "OCCUPANT_BAD": 5, "P_REPLACED": 6, "Q_REPLACED": 7}
+FUSE_STATUS = {"OBS_OVERFLOW": 2, "TABLE_OVERFLOW": 4, "BAD_SLOT": 8}
+FUSE_REFUSED = 2 | 4   # with one of these nothing was written but the status (and n_obs_out for TABLE_OVERFLOW)
+FUSE_MAX_OPS = 16384
 # slamit_replace_index: the columns read and the table written are the edit index's; the arrays rewritten in place
 REPLACE_INDEX_INPLACE = (("mp_bad", np.uint8), ("mp_nobs", np.int32), ("mp_found", np.int32), ("mp_visible", np.int32), ("mp_replaced", np.int32), ("kf_mp", np.int32))
 
@@ -554,7 +573,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_init_hyp", "slamit_init_hyp_batch", "slamit_init_reconstruct", "slamit_init_reconstruct_batch", "slamit_init_best_hypothesis", "slamit_init_choose_h", "slamit_init_parallax_deg", "slamit_init_pick_f", "slamit_init_pick_h", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_map_edit_apply", "slamit_map_edit_workspace", "slamit_map_edit_batch_dev", "slamit_map_replace_apply", "slamit_map_replace_workspace", "slamit_map_replace_batch_dev", "slamit_check_replaced", "slamit_check_replaced_batch_dev", "slamit_kf_erase_apply", "slamit_kf_erase_workspace", "slamit_kf_erase_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_init_hyp", "slamit_init_hyp_batch", "slamit_init_reconstruct", "slamit_init_reconstruct_batch", "slamit_init_best_hypothesis", "slamit_init_choose_h", "slamit_init_parallax_deg", "slamit_init_pick_f", "slamit_init_pick_h", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_map_edit_apply", "slamit_map_edit_workspace", "slamit_map_edit_batch_dev", "slamit_map_replace_apply", "slamit_map_replace_workspace", "slamit_map_replace_batch_dev", "slamit_check_replaced", "slamit_check_replaced_batch_dev", "slamit_map_fuse_apply", "slamit_map_fuse_workspace", "slamit_map_fuse_batch_dev", "slamit_fuse_list_batch_dev", "slamit_kf_erase_apply", "slamit_kf_erase_workspace", "slamit_kf_erase_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -664,6 +683,11 @@ def lib():
         L.slamit_map_replace_workspace.argtypes = [i32, i32, i32, i32]
         L.slamit_map_replace_workspace.restype = sz
         L.slamit_map_replace_batch_dev.argtypes = [i32, C.POINTER(MapReplaceBatchRec), vp]
+        L.slamit_map_fuse_apply.argtypes = [i32, C.POINTER(MapIndexRec), C.POINTER(ReplaceIndexRec), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.slamit_map_fuse_workspace.argtypes = [i32, i32, i32, i32]
+        L.slamit_map_fuse_workspace.restype = sz
+        L.slamit_map_fuse_batch_dev.argtypes = [i32, C.POINTER(MapFuseBatchRec), vp]
+        L.slamit_fuse_list_batch_dev.argtypes = [i32, C.POINTER(FuseListBatchRec), vp]
         L.slamit_check_replaced.argtypes = [i32, i32, vp, i32, vp, vp]
         L.slamit_check_replaced_batch_dev.argtypes = [i32, C.POINTER(CheckReplacedBatchRec), vp]
         L.slamit_kf_erase_apply.argtypes = [i32, C.POINTER(MapIndexRec), C.POINTER(TreeIndexRec), i32, vp, vp, i32, vp, vp, vp, vp]
@@ -3154,6 +3178,20 @@ def replace_records(ops):
 
 
 def map_replace(tables, index, ops, obs_cap_out=None, fill=None, device=0):
+    """MapPoint::Replace with Fuse's add pair for a list of ops: the arguments and the result are stated at _map_list_apply."""
+    return _map_list_apply(False, tables, index, ops, obs_cap_out, fill, device)
+
+
+def map_fuse(tables, cols, ops, obs_cap_out=None, fill=None, device=0):
+    """The tail of ORBmatcher::Fuse (ORBmatcher.cc:853, :955-975) for a list of ops applied as if sequentially: map_replace's arguments
+    and result, with ops of kind FUSE_FUSE (a = P, b = the keyframe, idx = the matched keypoint or -1, octave, weight) beside the other
+    two, obs_cap_out defaulting to the old table plus one entry per ADD_OBS and FUSE op, `outcome` among the prefilled outputs, and in
+    the result outcome (FUSE_OUT per op) and n_fused (the reference's return value).  With a bit of FUSE_REFUSED in status the tables
+    returned are the old ones."""
+    return _map_list_apply(True, tables, cols, ops, obs_cap_out, fill, device)
+
+
+def _map_list_apply(fuse, tables, index, ops, obs_cap_out, fill, device):
     """MapPoint::Replace (MapPoint.cc:183-221) with Fuse's AddObservation + AddMapPoint for a list of ops applied as if sequentially, over
     a map's tables (slamit_map_index: n_kf, n_mp, obs_ptr, obs_kf, kf_mp_ptr, kf_mp, mp_bad) and the columns beside them (dict: obs_idx,
     obs_octave, obs_weight; mp_nobs, mp_found, mp_visible, mp_replaced; mp_bad / kf_mp where they are not taken from `tables`).  ops:
@@ -3170,7 +3208,8 @@ def map_replace(tables, index, ops, obs_cap_out=None, fill=None, device=0):
     for key in ("mp_bad", "kf_mp"):
         src.setdefault(key, tables.get(key))
     n_obs = int(np.asarray(tables["obs_ptr"]).reshape(-1)[-1]) if tables.get("obs_ptr") is not None and len(np.asarray(tables["obs_ptr"]).reshape(-1)) else 0
-    cap = n_obs + int(np.count_nonzero(ed["kind"] == REPLACE_ADD_OBS)) if obs_cap_out is None else int(obs_cap_out)
+    cap = n_obs + int(np.count_nonzero((ed["kind"] == REPLACE_ADD_OBS) | (fuse & (ed["kind"] == FUSE_FUSE)))) if obs_cap_out is None else int(obs_cap_out)
+    name = "map_fuse" if fuse else "map_replace"
     fill = fill or {}
     xrec, xkeep = ReplaceIndexRec(), {}
     for key, dt in EDIT_INDEX_COLUMNS:
@@ -3184,21 +3223,29 @@ def map_replace(tables, index, ops, obs_cap_out=None, fill=None, device=0):
     for key, dt, count in (("obs_ptr_out", np.int32, n_mp + 1),) + tuple((k, d, max(cap, 0)) for k, d in EDIT_INDEX_OUT):
         xkeep[key] = np.zeros(count, dt) if fill.get(key) is None else np.array(fill[key], dt).reshape(-1)
         if len(xkeep[key]) != count:
-            raise SlamitError("map_replace: fill[%s] does not hold %d entries" % (key, count))
+            raise SlamitError("%s: fill[%s] does not hold %d entries" % (name, key, count))
         setattr(xrec, key, xkeep[key].ctypes.data if count else None)
     xrec.obs_cap_out = cap
-    per_op = {key: np.zeros(len(ed), np.int32) if fill.get(key) is None else np.array(fill[key], np.int32).reshape(-1) for key in ("moved", "erased")}
+    per_op = {key: np.zeros(len(ed), np.int32) if fill.get(key) is None else np.array(fill[key], np.int32).reshape(-1) for key in ("moved", "erased") + (("outcome",) if fuse else ())}
     tch = np.full(n_mp, -1, np.int32) if fill.get("touched") is None else np.array(fill["touched"], np.int32).reshape(-1)
     if len(tch) != n_mp or any(len(v) != len(ed) for v in per_op.values()):
-        raise SlamitError("map_replace: moved and erased hold one entry per op, touched n_mp entries")
+        raise SlamitError("%s: moved and erased hold one entry per op, touched n_mp entries" % name)
     nt, no, st = np.array([fill.get("n_touched", 0)], np.int32), np.array([fill.get("n_obs_out", 0)], np.int32), np.zeros(1, np.int32)
+    nf = np.array([fill.get("n_fused", 0)], np.int32)
     some = lambda a: _np_ptr(a) if len(a) else None
-    _check(lib().slamit_map_replace_apply(device, C.byref(rec), C.byref(xrec), len(ed), some(ed), some(per_op["moved"]), some(per_op["erased"]), some(tch),
-                                          _np_ptr(nt), _np_ptr(no), _np_ptr(st)), "slamit_map_replace_apply")
+    if fuse:
+        _check(lib().slamit_map_fuse_apply(device, C.byref(rec), C.byref(xrec), len(ed), some(ed), some(per_op["outcome"]), some(per_op["moved"]),
+                                           some(per_op["erased"]), some(tch), _np_ptr(nt), _np_ptr(nf), _np_ptr(no), _np_ptr(st)), "slamit_map_fuse_apply")
+    else:
+        _check(lib().slamit_map_replace_apply(device, C.byref(rec), C.byref(xrec), len(ed), some(ed), some(per_op["moved"]), some(per_op["erased"]), some(tch),
+                                              _np_ptr(nt), _np_ptr(no), _np_ptr(st)), "slamit_map_replace_apply")
     del keep
     status, need = int(st[0]), int(no[0])
     out = {"status": status, "n_obs_out": need, "n_touched": int(nt[0]), "moved": per_op["moved"], "erased": per_op["erased"],
            "raw": dict(xkeep, touched=tch, n_touched=int(nt[0]), n_obs_out=need, **per_op)}
+    if fuse:
+        out.update(outcome=per_op["outcome"], n_fused=int(nf[0]))
+        out["raw"]["n_fused"] = int(nf[0])
     if status & REPLACE_REFUSED:
         out.update(obs_ptr=np.array(tables["obs_ptr"], np.int32).reshape(-1), obs_kf=np.array(tables["obs_kf"], np.int32).reshape(-1), touched=tch[:0])
         for key, _ in EDIT_INDEX_COLUMNS:
@@ -3267,6 +3314,52 @@ def map_replace_batch_dev(maps, index, t, device=0, stream=None):
                              t["touched"].data_ptr(), t["n_touched"].data_ptr(), t["n_obs_out"].data_ptr(), t["status"].data_ptr(), ws.data_ptr(),
                              ws.numel() * ws.element_size())
     _check(lib().slamit_map_replace_batch_dev(device, C.byref(rec), stream), "slamit_map_replace_batch_dev")
+
+
+def map_fuse_workspace(n_maps, cap, mp_cap, kfmp_cap):
+    return int(lib().slamit_map_fuse_workspace(n_maps, cap, mp_cap, kfmp_cap))
+
+
+def map_fuse_batch_dev(maps, index, t, device=0, stream=None):
+    """One fuse list per map, resident: map_replace_batch_dev's arguments, the lists holding FUSE ops too, with outcome (B, cap) and n_fused
+    (B) i32 in / out beside the others and workspace of map_fuse_workspace(B, cap, mp_cap, kfmp_cap) bytes.  Where status has no bit of
+    FUSE_REFUSED, call swap() on the EditIndex before the next reader is ENQUEUED.  Asynchronous on `stream`."""
+    b, cap = t["ops"].shape[0], t["ops"].shape[1]
+    mp_cap = t["touched"].shape[1]
+    if len(maps) != b or len(index) != b:
+        raise SlamitError("map_fuse_batch_dev: one MapIndex, one ReplaceIndex and one list per map")
+    _rows(t, "map_fuse_batch_dev", (("ops", cap * REPLACE_DTYPE.itemsize), ("outcome", cap), ("moved", cap), ("erased", cap), ("touched", mp_cap), ("n", 1),
+                                    ("n_touched", 1), ("n_fused", 1), ("n_obs_out", 1), ("status", 1)), b)
+    M, X = (MapIndexRec * max(b, 1))(), (ReplaceIndexRec * max(b, 1))()
+    for i, (mi, ri) in enumerate(zip(maps, index)):
+        M[i], X[i] = mi.rec, ri.rec
+    ws = t["workspace"]
+    rec = MapFuseBatchRec(b, cap, mp_cap, int(t["kfmp_cap"]), M, X, t["ops"].data_ptr(), t["n"].data_ptr(), t["outcome"].data_ptr(), t["moved"].data_ptr(),
+                          t["erased"].data_ptr(), t["touched"].data_ptr(), t["n_touched"].data_ptr(), t["n_fused"].data_ptr(), t["n_obs_out"].data_ptr(),
+                          t["status"].data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
+    _check(lib().slamit_map_fuse_batch_dev(device, C.byref(rec), stream), "slamit_map_fuse_batch_dev")
+
+
+def fuse_list_batch_dev(t, n_maps, device=0, stream=None):
+    """The FUSE ops of a guided search into the lists map_fuse_batch_dev reads, resident.  t: dict of torch CUDA tensors match_kp (F, q_cap)
+    i32 and m (F) i32 as the search left them, query_point (F, q_cap) i32, kps_un (F, kp_cap, 28) u8 or (F, kp_cap, 7) f32 (slamit_kp records), kp_ur (F, kp_cap)
+    f32 or None, frame_map / frame_kf / base (F) i32, and the outputs ops (n_maps, cap, 20) u8, n (n_maps) i32, list_status (F) i32.
+    Asynchronous on `stream`."""
+    f, q_cap = t["match_kp"].shape[0], t["match_kp"].shape[1]
+    kp_cap, cap = t["kps_un"].shape[1], t["ops"].shape[1]
+    if t["ops"].shape[0] != n_maps or t["n"].numel() < n_maps:
+        raise SlamitError("fuse_list_batch_dev: one list and one length per map")
+    if t["kps_un"].numel() * t["kps_un"].element_size() != f * kp_cap * 28 or not t["kps_un"].is_contiguous():
+        raise SlamitError("fuse_list_batch_dev: kps_un does not hold kp_cap slamit_kp records per target")
+    _rows(t, "fuse_list_batch_dev", (("match_kp", q_cap), ("query_point", q_cap), ("m", 1), ("frame_map", 1), ("frame_kf", 1), ("base", 1),
+                                     ("list_status", 1)), f)
+    ur = t.get("kp_ur")
+    if ur is not None and (not ur.is_contiguous() or ur.numel() < f * kp_cap):
+        raise SlamitError("fuse_list_batch_dev: kp_ur holds one float per keypoint")
+    rec = FuseListBatchRec(f, n_maps, kp_cap, q_cap, cap, 0, t["m"].data_ptr(), t["match_kp"].data_ptr(), t["query_point"].data_ptr(), t["kps_un"].data_ptr(),
+                           ur.data_ptr() if ur is not None else None, t["frame_map"].data_ptr(), t["frame_kf"].data_ptr(), t["base"].data_ptr(),
+                           t["ops"].data_ptr(), t["n"].data_ptr(), t["list_status"].data_ptr())
+    _check(lib().slamit_fuse_list_batch_dev(device, C.byref(rec), stream), "slamit_fuse_list_batch_dev")
 
 
 def check_replaced(mp_replaced, frame_mp, device=0):

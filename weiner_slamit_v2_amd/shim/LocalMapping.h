@@ -33,7 +33,8 @@
 // over slamit_update_points and slamit_map_point_culling, ApplyMapEdits (MapPoint::AddObservation, ::EraseObservation
 // and ::SetBadFlag for a list of edits, src/MapPoint.cc:104-174) over slamit_map_edit_apply (section 26), ReplaceMapPoints (MapPoint::Replace for a fuse list, :183-221) over
 // slamit_map_replace_apply (section 27), SetBadFlagKeyFrames (KeyFrame::SetBadFlag for a list of keyframes, src/KeyFrame.cc:460-552) over
-// slamit_kf_erase_apply and ApplyMapEdits (section 28).
+// slamit_kf_erase_apply and ApplyMapEdits (section 28), FuseMapPoints (the tail of ORBmatcher::Fuse for a list of matched points,
+// src/ORBmatcher.cc:955-975) over slamit_map_fuse_apply (section 31).
 #ifndef SLAMIT_SHIM_LOCALMAPPING_H
 #define SLAMIT_SHIM_LOCALMAPPING_H
 
@@ -516,6 +517,121 @@ public:
         for (int i = 0; i < n; ++i)
             if (ops[i].kind == SLAMIT_REPLACE_REPLACE && ops[i].pMP != ops[i].pRep) pMap->EraseMapPoint(ops[i].pMP);   // MapPoint.cc:220
         return n;
+    }
+
+    // One op of FuseMapPoints over the caller's objects: the point pMP that ORBmatcher::Fuse projected into pKF and the keypoint its
+    // search ended with (bestIdx < 0, or a null pMP: bestDist > TH_LOW, nothing happens).
+    template <class MapPointT, class KeyFrameT>
+    struct FuseOp {
+        MapPointT* pMP;
+        KeyFrameT* pKF;
+        int bestIdx;
+    };
+
+    // The tail of ORBmatcher::Fuse (ORBmatcher.cc:853, :955-975) for a LIST of (point, keyframe, matched keypoint) as the searches of
+    // SearchInNeighbors end, applied as if one after the other in ONE slamit_map_fuse_apply call: which way a Replace goes, or whether
+    // the observation is added, is decided by the library from the state the earlier ops of the list left.  Writes back what
+    // ReplaceMapPoints writes back (mObservations, nObs, mbBad, mpReplaced, mnFound, mnVisible of the points the ops name and of the
+    // points that stood at the matched keypoints; the changed entries of mvpMapPoints) and calls pMap->EraseMapPoint on every point that
+    // was replaced.  Returns nFused, the reference's return value summed over the list.  A row past SLAMIT_UPKEEP_MAX_OBS observers
+    // leaves EVERYTHING as it was, LastStatus() is SLAMIT_ERR_CAPACITY with a line on stderr.  NOTHING IS SAVED THROUGH THE SHIM, as
+    // ReplaceMapPoints: the gain is slamit_fuse_list_batch_dev + slamit_map_fuse_batch_dev with the tables kept in HBM.  ORBmatcher::Fuse
+    // in shim/ORBmatcher.h stays as it is.  Members used: those of ReplaceMapPoints.
+    template <class MapPointT, class KeyFrameT, class MapT>
+    static int FuseMapPoints(const std::vector<FuseOp<MapPointT, KeyFrameT> >& ops, MapT* pMap, int device = 0) {
+        typedef typename std::map<KeyFrameT*, size_t>::const_iterator ObsIt;
+        status() = SLAMIT_OK;
+        const int n = (int)ops.size();
+        if (n == 0) return 0;
+        if (n > SLAMIT_FUSE_MAX_OPS) return shim::refuse<LocalMapping>("FuseMapPoints: more than SLAMIT_FUSE_MAX_OPS ops", SLAMIT_ERR_CAPACITY);
+        std::vector<MapPointT*> mps;
+        std::map<MapPointT*, int32_t> mpSlot;
+        std::set<KeyFrameT*> all;
+        for (int i = 0; i < n; ++i) {                                          // the involved points: P and whoever stands at the matched keypoint NOW
+            if (!ops[i].pMP || ops[i].bestIdx < 0) continue;
+            if (!ops[i].pKF || (size_t)ops[i].bestIdx >= ops[i].pKF->mvpMapPoints.size()) return shim::refuse<LocalMapping>("FuseMapPoints: an op without its keyframe or with a keypoint outside it");
+            slotOf(mpSlot, mps, ops[i].pMP);
+            if (ops[i].pKF->mvpMapPoints[ops[i].bestIdx]) slotOf(mpSlot, mps, ops[i].pKF->mvpMapPoints[ops[i].bestIdx]);
+            all.insert(ops[i].pKF);
+        }
+        const int n_named = (int)mps.size();
+        if (n_named == 0) return 0;
+        for (int p = 0; p < n_named; ++p)
+            for (ObsIt it = mps[p]->mObservations.begin(); it != mps[p]->mObservations.end(); ++it) all.insert(it->first);
+        const std::vector<KeyFrameT*> kfs(all.begin(), all.end());   // a std::set orders by std::less
+        std::map<KeyFrameT*, int32_t> kfSlot;
+        for (size_t k = 0; k < kfs.size(); ++k) kfSlot[kfs[k]] = (int32_t)k;
+        const int n_kf = (int)kfs.size();
+        if (n_kf > SLAMIT_LOCAL_MAP_MAX_KF) return shim::refuse<LocalMapping>("FuseMapPoints: more than SLAMIT_LOCAL_MAP_MAX_KF keyframes around the points", SLAMIT_ERR_CAPACITY);
+        std::vector<int32_t> kf_mp_ptr(n_kf + 1, 0), kf_mp;
+        for (int k = 0; k < n_kf; ++k) {                                       // every stored point gets a slot: a changed entry is found by comparing
+            for (size_t i = 0; i < kfs[k]->mvpMapPoints.size(); ++i) kf_mp.push_back(kfs[k]->mvpMapPoints[i] ? slotOf(mpSlot, mps, kfs[k]->mvpMapPoints[i]) : -1);
+            kf_mp_ptr[k + 1] = (int32_t)kf_mp.size();
+        }
+        std::vector<int32_t> rep_named(n_named, -1);
+        for (int p = 0; p < n_named; ++p)
+            if (mps[p]->mpReplaced) rep_named[p] = slotOf(mpSlot, mps, mps[p]->mpReplaced);
+        const int n_mp = (int)mps.size();
+        std::vector<int32_t> obs_ptr(n_mp + 1, 0), obs_kf, obs_idx, mp_nobs(n_mp, 0), mp_found(n_mp, 0), mp_visible(n_mp, 0), mp_replaced(n_mp, -1);
+        std::vector<uint8_t> obs_octave, obs_weight, mp_bad(n_mp, 0);
+        for (int p = 0; p < n_mp; ++p) {
+            if (p < n_named) {
+                mp_bad[p] = mps[p]->mbBad ? 1 : 0; mp_nobs[p] = mps[p]->nObs; mp_found[p] = mps[p]->mnFound; mp_visible[p] = mps[p]->mnVisible; mp_replaced[p] = rep_named[p];
+                for (ObsIt it = mps[p]->mObservations.begin(); it != mps[p]->mObservations.end(); ++it) {
+                    KeyFrameT* kf = it->first;
+                    obs_kf.push_back(kfSlot[kf]); obs_idx.push_back((int32_t)it->second);
+                    obs_octave.push_back(it->second < kf->mvKeysUn.size() ? (uint8_t)kf->mvKeysUn[it->second].octave : 0);
+                    obs_weight.push_back(it->second < kf->mvuRight.size() && kf->mvuRight[it->second] >= 0 ? 2 : 1);
+                }
+            }
+            obs_ptr[p + 1] = (int32_t)obs_kf.size();
+        }
+        std::vector<slamit_map_replace> list(n);
+        for (int i = 0; i < n; ++i) {
+            slamit_map_replace& e = list[i];
+            memset(&e, 0, sizeof(e));
+            e.kind = SLAMIT_FUSE_FUSE; e.idx = -1;
+            if (!ops[i].pMP || ops[i].bestIdx < 0) continue;
+            KeyFrameT* kf = ops[i].pKF;
+            const size_t idx = (size_t)ops[i].bestIdx;
+            e.a = mpSlot[ops[i].pMP]; e.b = kfSlot[kf]; e.idx = ops[i].bestIdx;
+            e.octave = idx < kf->mvKeysUn.size() ? (uint8_t)kf->mvKeysUn[idx].octave : 0;
+            e.weight = idx < kf->mvuRight.size() && kf->mvuRight[idx] >= 0 ? 2 : 1;
+        }
+        const size_t cap = obs_kf.size() + (size_t)n;                          // an observation is created by an add alone
+        std::vector<int32_t> optr(n_mp + 1, 0), okf(cap + 1, 0), oidx(cap + 1, 0), outcome(n, 0), moved(n, 0), erased(n, 0), touched(n_mp, -1), kf_mp_new(kf_mp);
+        std::vector<uint8_t> ooct(cap + 1, 0), owgt(cap + 1, 0), bad_new(mp_bad);
+        std::vector<int32_t> nobs_new(mp_nobs), found_new(mp_found), visible_new(mp_visible), rep_new(mp_replaced);
+        int32_t none32 = -1;
+        uint8_t none8 = 0;
+        slamit_map_index M;
+        memset(&M, 0, sizeof(M));
+        M.n_kf = n_kf; M.n_mp = n_mp; M.obs_ptr = obs_ptr.data(); M.obs_kf = obs_kf.empty() ? &none32 : obs_kf.data(); M.kf_mp_ptr = kf_mp_ptr.data();
+        slamit_replace_index X;
+        memset(&X, 0, sizeof(X));
+        X.obs_idx = obs_idx.empty() ? &none32 : obs_idx.data(); X.obs_octave = obs_octave.empty() ? &none8 : obs_octave.data();
+        X.obs_weight = obs_weight.empty() ? &none8 : obs_weight.data();
+        X.mp_bad = bad_new.data(); X.mp_nobs = nobs_new.data(); X.mp_found = found_new.data(); X.mp_visible = visible_new.data(); X.mp_replaced = rep_new.data();
+        X.kf_mp = kf_mp_new.empty() ? &none32 : kf_mp_new.data();
+        X.obs_ptr_out = optr.data(); X.obs_kf_out = okf.data(); X.obs_idx_out = oidx.data(); X.obs_octave_out = ooct.data(); X.obs_weight_out = owgt.data();
+        X.obs_cap_out = (int32_t)cap;
+        int32_t n_touched = 0, n_fused = 0, n_obs_out = 0, st = 0;
+        const int rc = slamit_map_fuse_apply(device, &M, &X, n, list.data(), outcome.data(), moved.data(), erased.data(), touched.data(), &n_touched, &n_fused, &n_obs_out, &st);
+        if (rc != SLAMIT_OK) return shim::report<LocalMapping>("FuseMapPoints: slamit_map_fuse_apply", rc);
+        if (st & SLAMIT_FUSE_OBS_OVERFLOW) return shim::refuse<LocalMapping>("FuseMapPoints: a row past SLAMIT_UPKEEP_MAX_OBS observers: nothing was changed", SLAMIT_ERR_CAPACITY);
+        if (st != 0) return shim::refuse<LocalMapping>("FuseMapPoints: slamit_map_fuse_apply reported a status on tables built here", SLAMIT_ERR_STATE);
+        for (int p = 0; p < n_named; ++p) {
+            MapPointT* pMP = mps[p];
+            pMP->mObservations.clear();
+            for (int o = optr[p]; o < optr[p + 1]; ++o) pMP->mObservations[kfs[okf[o]]] = (size_t)oidx[o];
+            pMP->nObs = nobs_new[p]; pMP->mnFound = found_new[p]; pMP->mnVisible = visible_new[p];
+            pMP->mbBad = bad_new[p] != 0;
+            if (rep_new[p] != mp_replaced[p]) { pMP->mpReplaced = mps[rep_new[p]]; pMap->EraseMapPoint(pMP); }   // MapPoint.cc:220
+        }
+        for (int k = 0; k < n_kf; ++k)
+            for (int e = kf_mp_ptr[k]; e < kf_mp_ptr[k + 1]; ++e)
+                if (kf_mp_new[e] != kf_mp[e]) kfs[k]->mvpMapPoints[e - kf_mp_ptr[k]] = kf_mp_new[e] < 0 ? (MapPointT*)0 : mps[kf_mp_new[e]];
+        return n_fused;
     }
 
     // KeyFrame::SetBadFlag (KeyFrame.cc:460-552) for a LIST of keyframes, applied as if one after the other: ONE slamit_kf_erase_apply call
