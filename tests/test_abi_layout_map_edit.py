@@ -89,13 +89,19 @@ def test_map_edit_is_declared_exported_and_built():
         assert callable(getattr(api, f))
     csrc = os.path.join(ROOT, "weiner_slamit_v2_amd", "csrc")
     src = open(os.path.join(csrc, "map_edit.hip")).read()
-    assert "getenv" not in src and '#include "wave_ops.h"' in src and "block_inclusive_scan_i32<ME_NT>(" in src and "me_walk(" in src
+    assert "getenv" not in src and '#include "wave_ops.h"' in src and "me_walk(" in src
+    rows = open(os.path.join(csrc, "map_rows_dev.h")).read()                                  # the scan bodies, shared with map_replace and map_fuse
+    assert all(body + "<ME_NT>(" in src for body in ("map_scan_sum", "map_scan_parts", "map_scan_add")) and "block_inclusive_scan_i32<NT>(" in rows
     ops = open(os.path.join(csrc, "wave_ops.h")).read()                                       # the workgroup scan stands on the DPP wave scan, no __shfl
     assert "wave_inclusive_scan_i32(v)" in ops.split("block_inclusive_scan_i32(int v, int& total) {")[1].split("\n}")[0] and "__shfl" not in ops.split("#ifndef")[1]
     assert "while (" not in src.replace("while (lo < hi)", "")                                # no kernel waits: the one loop is the bisection
     assert "struct slamit_edit_index {" in hdr and "struct slamit_map_edit {" in hdr
     assert api.map_edit_workspace(1, 0, 0, 0) > 0 and api.map_edit_workspace(0, 1, 1, 1) == 0
     assert api.map_edit_workspace(8, 1000, 5000, 70000) >= 8 * (8 * 70000 + 4 * 1000 + 8 * 4 * 5001)   # the kf_mp words, the buckets, eight rows over the points
+    # the workspace's bytes, pinned when the scan and the row copy moved into the shared header: (n_maps, cap, mp_cap, kfmp_cap) -> bytes
+    for dims, want in (((1, 0, 0, 0), 160), ((1, 1, 1, 1), 192), ((1, 4, 7, 30), 544), ((2, 64, 257, 1000), 33104), ((8, 1000, 5000, 70000), 5793728),
+                       ((8, 16384, 255, 3), 590272)):
+        assert api.map_edit_workspace(*dims) == want, dims
 
 
 def _refused(call, word, code=-1):

@@ -73,14 +73,35 @@ def test_map_fuse_is_declared_exported_and_built():
         assert callable(getattr(api, f))
     csrc = os.path.join(ROOT, "weiner_slamit_v2_amd", "csrc")
     src, head = open(os.path.join(csrc, "map_fuse.hip")).read(), open(os.path.join(csrc, "map_fuse.h")).read()
-    assert "getenv" not in src and "double" not in src and "mf_walk_op(" in src and '#include "map_check.h"' in src and '#include "wave_ops.h"' in src
-    assert "while (" not in src.replace("while (lo < hi)", "").replace("while (mask)", "")  # no kernel waits: the bisection and the ballot's bits
-    assert "agent" not in src and "__threadfence" not in src and "__syncthreads" not in src  # one wavefront walks a list; no workgroup waits on another
+    assert "mf_walk_op(" in src and '#include "map_check.h"' in src and '#include "wave_ops.h"' in src and '#include "map_rows_dev.h"' in src
+    for text in (src, open(os.path.join(csrc, "map_rows_dev.h")).read()):                   # the file and the shared device header, each on its own
+        assert "getenv" not in text and "double" not in text
+        assert "while (" not in text.replace("while (lo < hi)", "").replace("while (mask)", "")  # no kernel waits: the bisection and the ballot's bits
+        assert "agent" not in text and "__threadfence" not in text and "__syncthreads" not in text  # one wavefront walks a list; no workgroup waits on another
     assert head.count("mr_walk_op(w, ") == 3 and "MrWorldSeq" in head and "push(" not in head.split("mf_apply_seq")[0]   # every outcome resolves into mr_walk_op
     assert api.map_fuse_workspace(1, 0, 0, 0) > 0 and api.map_fuse_workspace(0, 1, 1, 1) == 0 and api.map_fuse_workspace(1, api.FUSE_MAX_OPS + 1, 1, 1) == 0
     # the formula beside the declaration: four rows over the points, three words per op, the image of kf_mp, a working row per involved point
     want = 8 * (4 * 70000 + 4 * 4 * 5001 + 3 * 4 * 1000 + 2000 * (10 * 512 + 32))
     assert want <= api.map_fuse_workspace(8, 1000, 5000, 70000) <= want + 8 * 1024
+    # the workspace's bytes, pinned before the rows moved into the shared layout: (n_maps, cap, mp_cap, kfmp_cap) -> bytes
+    for dims, bytes_ in (((1, 0, 0, 0), 128), ((1, 1, 1, 1), 5360), ((1, 4, 7, 30), 36448), ((2, 64, 257, 1000), 1336832), ((8, 1000, 5000, 70000), 85409760),
+                         ((8, 16384, 255, 3), 12116224)):
+        assert api.map_fuse_workspace(*dims) == bytes_, dims
+
+
+def test_one_definition_is_left():
+    """The working-row world, the bisection of the row copy and the column enums stand once among the device sources: map_replace.hip and
+    map_fuse.hip run the text of map_rows_dev.h, and MfWorldDev adds only what mf_walk_op asks for beyond mr_walk_op."""
+    import glob
+
+    csrc = os.path.join(ROOT, "weiner_slamit_v2_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip"))) + [os.path.join(csrc, "map_rows_dev.h")]
+    text = {f: open(f).read() for f in files}
+    for once in ("sord[rank] = (uint16_t)e", "while (lo < hi)", "MR_C_LEN = 0, MR_C_BAD, MR_C_NOBS, MR_C_FOUND, MR_C_VISIBLE, MR_C_REPLACED, MR_C_RECEIVED, MR_NCOLS"):
+        assert sum(t.count(once) for t in text.values()) == 1, once
+        assert once in text[files[-1]], once
+    world = text[os.path.join(csrc, "map_fuse.hip")].split("struct MfWorldDev")[1].split("\n};")[0]
+    assert "MapWorldDev" in world and "occupant(" in world and "rank" not in world and "__popcll" not in world
 
 
 def _refused(call, word, code=-1):

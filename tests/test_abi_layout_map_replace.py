@@ -15,6 +15,8 @@ SYMBOLS = ("slamit_map_replace_apply", "slamit_map_replace_workspace", "slamit_m
 MACROS = ("SLAMIT_REPLACE_REPLACE", "SLAMIT_REPLACE_ADD_OBS", "SLAMIT_REPLACE_OP_OVERFLOW", "SLAMIT_REPLACE_OBS_OVERFLOW", "SLAMIT_REPLACE_TABLE_OVERFLOW",
           "SLAMIT_REPLACE_BAD_SLOT", "SLAMIT_REPLACE_MAX_OPS", "SLAMIT_REPLACE_MAX_PER_POINT", "SLAMIT_CHECK_REPLACED_MAX_N", "SLAMIT_UPKEEP_MAX_OBS")
 OP_FIELDS = ("kind", "a", "b", "idx", "octave", "weight", "pad")
+WORKSPACE_BYTES = (((1, 0, 0, 0), 144), ((1, 1, 1, 1), 5408), ((1, 4, 7, 30), 36672), ((2, 64, 257, 1000), 1350992), ((8, 1000, 5000, 70000), 88097792),
+                   ((8, 16384, 255, 3), 14229824))
 
 
 def test_map_replace_struct_layouts_match_the_header(tmp_path):
@@ -88,12 +90,18 @@ def test_map_replace_is_declared_exported_and_built():
     for f in ("map_replace", "map_replace_batch_dev", "map_replace_workspace", "ReplaceIndex", "replace_records", "check_replaced", "check_replaced_batch_dev"):
         assert callable(getattr(api, f))
     csrc = os.path.join(ROOT, "weiner_slamit_v2_amd", "csrc")
-    src = open(os.path.join(csrc, "map_replace.hip")).read()
-    assert "getenv" not in src and "float" not in src.replace("Nothing here is float", "") and "double" not in src
-    assert '#include "wave_ops.h"' in src and "wave_inclusive_scan_i32" in src and "mr_walk_op(" in src and '#include "map_edit' not in src
-    assert "while (" not in src.replace("while (lo < hi)", "").replace("while (mask)", "")    # no kernel waits: the bisection and the ballot's bits
-    assert "agent" not in src and "__threadfence" not in src and "round < n" in src           # workgroup scope only; the round loop is bounded by n
+    src, rows = open(os.path.join(csrc, "map_replace.hip")).read(), open(os.path.join(csrc, "map_rows_dev.h")).read()
+    assert '#include "map_rows_dev.h"' in src
+    for text in (src, rows):                                                                  # the file and the shared device header, each on its own
+        assert "getenv" not in text and "float" not in text.replace("Nothing here is float", "") and "double" not in text
+        assert "while (" not in text.replace("while (lo < hi)", "").replace("while (mask)", "")   # no kernel waits: the bisection and the ballot's bits
+        assert "agent" not in text and "__threadfence" not in text                            # workgroup scope only
+    assert '#include "wave_ops.h"' in src and "wave_inclusive_scan_i32" in rows and "mr_walk_op(" in src and '#include "map_edit' not in src
+    assert "round < n" in src                                                                 # the round loop is bounded by n
     assert "struct slamit_replace_index {" in hdr and "struct slamit_map_replace {" in hdr
+    # the workspace's bytes, pinned before the rows moved into the shared layout: (n_maps, cap, mp_cap, kfmp_cap) -> bytes
+    for dims, want in WORKSPACE_BYTES:
+        assert api.map_replace_workspace(*dims) == want, dims
     assert api.map_replace_workspace(1, 0, 0, 0) > 0 and api.map_replace_workspace(0, 1, 1, 1) == 0 and api.map_replace_workspace(1, api.REPLACE_MAX_OPS + 1, 1, 1) == 0
     # the formula beside the declaration: the kf_mp words, six rows over the points, seven per op, a working row per involved point
     assert api.map_replace_workspace(8, 1000, 5000, 70000) >= 8 * (8 * 70000 + 6 * 4 * 5001 + 7 * 4 * 1000 + 2000 * (10 * 512 + 32))

@@ -1,10 +1,14 @@
 """slamit_map_fuse_apply and slamit_map_fuse_batch_dev on the GPU against the literal sequential restatement (tests/map_fuse_ref.py) on
 every fixture: the new table and its three columns, mp_bad, mp_nobs, mp_found, mp_visible, mp_replaced, kf_mp, outcome, moved and erased
 op by op, touched and the counts, all exact; the all-or-nothing gate of each overflow; the bytes past the counts; the same bytes from
-the same input twice; slots outside their tables; two lists at the ceiling; slamit_fuse_list_batch_dev against three lines of numpy."""
+the same input twice; slots outside their tables; two lists at the ceiling; slamit_fuse_list_batch_dev against three lines of numpy; and
+the lists of the map-replace fixtures, which hold no FUSE op, through both modules: the in-order walk against the rounds over one world."""
+import functools
+
 import numpy as np
 import pytest
 
+from tests import map_replace_fixtures, map_replace_host
 from tests.map_fuse_fixtures import F, all_fixtures, by_name, expected
 from tests.map_fuse_host import FILL, INPLACE, assert_same, default_cap, fills, laid_out, of_api, records
 from tests.map_fuse_ref import ADD_OBS, BAD_SLOT, FUSE, OBS_OVERFLOW, REPLACE, TABLE_OVERFLOW, apply
@@ -31,6 +35,37 @@ def test_the_host_form_equals_the_restatement(name):
         assert np.array_equal(out["outcome"], want["outcome"]) and out["n_fused"] == want["n_fused"]
         rec, keep = api._map_index_host(dict(fx["t"], **{k: out[k] for k in ("obs_ptr", "obs_kf", "mp_bad", "kf_mp")}))
         assert rec.n_mp == fx["t"]["n_mp"] and len(keep["obs_kf"]) == want["n_obs_out"]
+
+
+PLAIN_NAMES = [fx["name"] for fx in map_replace_fixtures.all_fixtures()]
+
+
+@functools.lru_cache(maxsize=None)
+def plain_want(name):
+    fx = map_replace_fixtures.by_name(name)
+    return apply(fx["t"], fx["x"], fx["ops"], map_replace_host.default_cap(fx) + 3)
+
+
+@pytest.mark.parametrize("name", PLAIN_NAMES)
+def test_a_plain_list_equals_the_restatement_and_map_replace(name):
+    """(a) A list of REPLACE and ADD_OBS ops through api.map_fuse equals the restatement, every outcome PLAIN and nothing fused; (b) unless
+    map_replace meets its per-point ceiling of ops, which map_fuse does not have (one fixture of the 19, fan65), every byte both entry points
+    write is the same: the two schedulers run one world (map_rows_dev.h)."""
+    from weiner_slamit_v2_amd import api
+
+    fx, cap = map_replace_fixtures.by_name(name), map_replace_host.default_cap(map_replace_fixtures.by_name(name)) + 3
+    out = api.map_fuse(fx["t"], fx["x"], records(fx["ops"]), obs_cap_out=cap, fill=fills(fx, cap))
+    want = plain_want(name)
+    assert_same(of_api(out), laid_out(fx, want, cap), name)
+    if not want["status"] & api.FUSE_REFUSED:
+        assert np.all(want["outcome"] == api.FUSE_OUT["PLAIN"]) and want["n_fused"] == 0
+        assert np.all(out["outcome"] == api.FUSE_OUT["PLAIN"]) and out["n_fused"] == 0 and len(out["outcome"]) == len(fx["ops"])
+    over = [n for n in PLAIN_NAMES if map_replace_fixtures.expected(n)["status"] & api.REPLACE_STATUS["OP_OVERFLOW"]]
+    assert len(PLAIN_NAMES) - len(over) >= 18                           # what the condition below leaves out
+    if name in over:
+        return
+    rep = api.map_replace(fx["t"], fx["x"], records(fx["ops"]), obs_cap_out=cap, fill=map_replace_host.fills(fx, cap))
+    map_replace_host.assert_same(of_api(out), map_replace_host.of_api(rep), name)   # the table, the columns, kf_mp, moved, erased, touched, the counts, status
 
 
 def resident_run(fxs, caps, pad=5):

@@ -1,7 +1,8 @@
 """csrc/map_check.h, the host-side statement of a valid map table, on the CPU: built with g++ behind a small C driver, first as a
 shared library (one fault at a time, each message against its literal text), then with the driver's own main as a stand-alone program
-under AddressSanitizer and UBSan over the same cases; and the six map modules' entry points against it: for a shared fault the
-library's message is the entry point's name, ": " and the header's text for the same table."""
+under AddressSanitizer and UBSan over the same cases; and the map modules' entry points against it: for a shared fault the
+library's message is the entry point's name, ": " and the header's text for the same table.  The two functions over the pair
+slamit_map_index + slamit_replace_index (the host and the resident form of map_replace and map_fuse) are cases of the same driver."""
 import ctypes as C
 import os
 import subprocess
@@ -19,9 +20,36 @@ DRIVER = r'''
 #include <stdlib.h>
 #include "map_check.h"
 
-enum { FN_CSR, FN_SLOTS, FN_SIZES, FN_BATCH_SIZES, FN_OBS, FN_GRAPH, FN_CHILDREN };
+enum { FN_CSR, FN_SLOTS, FN_SIZES, FN_BATCH_SIZES, FN_OBS, FN_GRAPH, FN_CHILDREN, FN_REPLACE_TABLES, FN_REPLACE_BATCH };
 
-// h: n_kf n_mp row_cap a b c.  FN_CSR: a = 0 obs_ptr, 1 kf_mp_ptr, 2 kf_child_ptr.  FN_SLOTS: v[a] inside [b, c).
+// The replace index of FN_REPLACE_TABLES / FN_REPLACE_BATCH.  nul: bit i set makes the record's i-th pointer null (bit 14 `touched`,
+// bit 15 the map record, bit 16 the index record).  obs_idx and obs_weight are the case's arrays; every other pointer is only ever
+// tested for null and points at one byte, so a read through it is the sanitizers' to find.
+static const char* drv_replace(int fn, slamit_map_index& M, const int32_t* obs_idx, const uint8_t* obs_weight, int nul, int cap_out, int mp_cap) {
+    static unsigned char one[1];
+    void* const p = one;
+    const auto get = [&](int bit, const void* have) { return (nul >> bit) & 1 ? nullptr : const_cast<void*>(have); };
+    slamit_replace_index X = slamit_replace_index();
+    X.obs_idx = (const int32_t*)get(0, obs_idx); X.obs_octave = (const uint8_t*)get(1, p); X.obs_weight = (const uint8_t*)get(2, obs_weight);
+    X.mp_bad = (uint8_t*)get(3, p); X.mp_nobs = (int32_t*)get(4, p); X.mp_found = (int32_t*)get(5, p); X.mp_visible = (int32_t*)get(6, p);
+    X.mp_replaced = (int32_t*)get(7, p); X.kf_mp = (int32_t*)get(8, p); X.obs_ptr_out = (int32_t*)get(9, p); X.obs_kf_out = (int32_t*)get(10, p);
+    X.obs_idx_out = (int32_t*)get(11, p); X.obs_octave_out = (uint8_t*)get(12, p); X.obs_weight_out = (uint8_t*)get(13, p);
+    X.obs_cap_out = cap_out;
+    if (fn == FN_REPLACE_TABLES) return map_replace_tables_error((nul >> 15) & 1 ? nullptr : &M, (nul >> 16) & 1 ? nullptr : &X, (const int32_t*)get(14, p));
+    // two maps: a clean one of one keyframe and one point in front of the case's, whose pointers the resident form does not read
+    slamit_map_index maps[2] = {slamit_map_index(), M};
+    slamit_replace_index index[2] = {X, X};
+    maps[0].n_kf = maps[0].n_mp = 1;
+    maps[0].obs_ptr = maps[0].obs_kf = maps[0].kf_mp_ptr = (const int32_t*)p;
+    index[0].obs_idx = (const int32_t*)p; index[0].obs_octave = index[0].obs_weight = index[0].mp_bad = index[0].obs_octave_out = index[0].obs_weight_out = one;
+    index[0].mp_nobs = index[0].mp_found = index[0].mp_visible = index[0].mp_replaced = index[0].kf_mp = index[0].obs_ptr_out = index[0].obs_kf_out =
+        index[0].obs_idx_out = (int32_t*)p;
+    index[0].obs_cap_out = 0;
+    return map_replace_batch_error(2, mp_cap, maps, index);
+}
+
+// h: n_kf n_mp row_cap a b c.  FN_CSR: a = 0 obs_ptr, 1 kf_mp_ptr, 2 kf_child_ptr.  FN_SLOTS: v[a] inside [b, c).  FN_REPLACE_*: a = nul,
+// b = obs_cap_out, c = mp_cap.
 extern "C" const char* drv_check(int fn, const int32_t* h, const int32_t* obs_ptr, const int32_t* obs_kf, const int32_t* kf_mp_ptr, const int32_t* kf_child_ptr,
                                  const int32_t* kf_child, const int32_t* obs_idx, const uint8_t* obs_weight, const int32_t* cw_kf, const int32_t* cw_n,
                                  const int32_t* ord_kf, const int32_t* ord_n, const int32_t* v) {
@@ -36,6 +64,7 @@ extern "C" const char* drv_check(int fn, const int32_t* h, const int32_t* obs_pt
     case FN_OBS: return map_obs_error(&M, obs_idx, obs_weight);
     case FN_GRAPH: return map_graph_rows_error(M.n_kf, h[2], cw_kf, cw_n, ord_kf, ord_n);
     case FN_CHILDREN: return map_children_error(&M);
+    case FN_REPLACE_TABLES: case FN_REPLACE_BATCH: return drv_replace(fn, M, obs_idx, obs_weight, h[3], h[4], h[5]);
     }
     return "no such function";
 }
@@ -68,7 +97,9 @@ int main(int argc, char** argv) {
 #endif
 '''
 
-CSR, SLOTS, SIZES, BATCH_SIZES, OBS, GRAPH, CHILDREN = range(7)
+CSR, SLOTS, SIZES, BATCH_SIZES, OBS, GRAPH, CHILDREN, REPLACE_TABLES, REPLACE_BATCH = range(9)
+REPLACE_POINTERS = ("obs_idx", "obs_octave", "obs_weight", "mp_bad", "mp_nobs", "mp_found", "mp_visible", "mp_replaced", "kf_mp", "obs_ptr_out", "obs_kf_out",
+                    "obs_idx_out", "obs_octave_out", "obs_weight_out", "touched", "map", "index")   # the bits of the driver's `nul`
 ARRAYS = (("obs_ptr", np.int32), ("obs_kf", np.int32), ("kf_mp_ptr", np.int32), ("kf_child_ptr", np.int32), ("kf_child", np.int32), ("obs_idx", np.int32),
           ("obs_weight", np.uint8), ("cw_kf", np.int32), ("cw_n", np.int32), ("ord_kf", np.int32), ("ord_n", np.int32), ("v", np.int32))
 
@@ -82,6 +113,11 @@ T_CW = "cw_kf holds a keyframe slot outside [0, n_kf) or a keyframe's own"
 T_ORD = "ord_kf holds a keyframe slot outside [0, n_kf)"
 T_CHILD = "kf_child holds a keyframe slot outside [0, n_kf)"
 T_CHILD_ROW = "a children row does not ascend"
+T_NULL_TABLE = "null table"
+T_NULL_ARRAY = "null array or negative n"
+T_CAP_OUT = "negative obs_cap_out"
+T_CSR_ROWS = "a CSR pointer array does not ascend from 0"
+T_MP_CAP = "a map with n_mp above mp_cap"
 
 
 def base():
@@ -159,6 +195,51 @@ def cases():
     add("obs_kf alone", OBS, dict(put(both, "obs_kf", 5, 3), obs_idx=None, obs_weight=None), T_OBS_KF)
     add("an index fault unseen", OBS, dict(put(b, "obs_idx", 5, 2), obs_idx=None), None)
     add("a weight fault unseen", OBS, dict(put(b, "obs_weight", 5, 3), obs_weight=None), None)
+    # the pair map + replace index of a host form: clean tables, one fault at a time, and the order of two
+    nul = lambda *names: sum(1 << REPLACE_POINTERS.index(k) for k in names)
+    rt = lambda name, tab, want, bits=0, cap_out=6: add(name, REPLACE_TABLES, tab, want, (bits, cap_out, 0))
+    rt("valid pair", b, None)
+    rt("empty pair, every array null but obs_ptr_out", e, None, nul(*(k for k in REPLACE_POINTERS[:15] if k != "obs_ptr_out")), 0)
+    rt("empty pair without obs_ptr_out", e, T_NULL_TABLE, nul("obs_ptr_out"), 0)
+    rt("no room and no new table", b, None, nul("obs_kf_out", "obs_idx_out", "obs_octave_out", "obs_weight_out"), 0)
+    rt("no map record", b, T_NULL_TABLE, nul("map"))
+    rt("no index record", b, T_NULL_TABLE, nul("index"))
+    rt("n_kf one past the ceiling", dict(e, n_kf=MAX_KF + 1), T_SIZES)
+    rt("n_mp = -1", dict(e, n_mp=-1), T_SIZES)
+    rt("no touched", b, T_NULL_ARRAY, nul("touched"))
+    rt("obs_cap_out = -1", b, T_CAP_OUT, 0, -1)
+    for key in ("obs_ptr", "kf_mp_ptr", "obs_kf"):
+        rt("no " + key, dict(b, **{key: None}), T_NULL_TABLE)
+    for key in REPLACE_POINTERS[:14]:
+        rt("no " + key, b, T_NULL_TABLE, nul(key))
+    rt("obs_ptr[0] != 0", put(b, "obs_ptr", 0, 1), T_CSR_ROWS)
+    rt("kf_mp_ptr descending", put(b, "kf_mp_ptr", 1, 5), T_CSR_ROWS)
+    rt("obs_kf at n_kf", put(b, "obs_kf", 5, 3), T_OBS_KF)
+    rt("obs_idx equal to its row's length", put(b, "obs_idx", 2, 2), T_OBS_IDX)
+    rt("weight 3", put(b, "obs_weight", 0, 3), T_OBS_WEIGHT)
+    rt("sizes before touched", dict(b, n_kf=-1), T_SIZES, nul("touched"))
+    rt("touched before obs_cap_out", b, T_NULL_ARRAY, nul("touched"), -1)
+    rt("obs_cap_out before a null table", b, T_CAP_OUT, nul("kf_mp"), -1)
+    rt("a null table before the rows", put(b, "obs_ptr", 0, 1), T_NULL_TABLE, nul("obs_ptr_out"))
+    rt("the rows before the columns", put(b, "kf_mp_ptr", 1, 5), T_CSR_ROWS, nul("mp_nobs"))
+    rt("the columns before the entries", put(b, "obs_kf", 0, -1), T_NULL_TABLE, nul("obs_octave"))
+    # the same pair in a resident form: the second of two maps carries the case
+    rb = lambda name, tab, want, bits=0, cap_out=6, mp_cap=4: add(name, REPLACE_BATCH, tab, want, (bits, cap_out, mp_cap))
+    rb("valid maps", b, None)
+    rb("n_mp = mp_cap", b, None, mp_cap=4)
+    rb("n_mp above mp_cap", b, T_MP_CAP, mp_cap=3)
+    rb("n_kf one past the ceiling", dict(b, n_kf=MAX_KF + 1), "a map with " + T_SIZES)
+    rb("obs_cap_out = -1", b, T_CAP_OUT, 0, -1)
+    rb("obs_cap_out = 0", b, None, 0, 0)
+    for key in ("obs_ptr", "kf_mp_ptr", "obs_kf"):
+        rb("no " + key, dict(b, **{key: None}), T_NULL_TABLE)
+    for key in REPLACE_POINTERS[:14]:
+        rb("no " + key, b, T_NULL_TABLE, nul(key))
+    rb("an empty map still names its arrays", e, T_NULL_TABLE, nul("kf_mp"), 0, 1)
+    rb("sizes before mp_cap", dict(b, n_kf=-1), "a map with " + T_SIZES, mp_cap=3)
+    rb("mp_cap before obs_cap_out", b, T_MP_CAP, 0, -1, 3)
+    rb("obs_cap_out before a null table", b, T_CAP_OUT, nul("mp_bad"), -1)
+    rb("the pointers are not read", put(put(b, "obs_ptr", 0, 1), "obs_kf", 0, -1), None)
     return out
 
 
@@ -316,3 +397,27 @@ def test_kf_erase_agrees_with_the_header(lib):
                        (CHILDREN, dict(t, kf_child=_at(t["kf_child"], 1, 1)), x), (CHILDREN, dict(t, kf_child=_at(_at(t["kf_child"], 0, 5), 1, 1)), x),
                        (CHILDREN, dict(t, kf_child=_at(t["kf_child"], 0, n_kf)), x), (SIZES, _over(t), x)):
         _agree(lib, where, lambda: ke(t1, x1), fn, dict(t1, **{k: v for k, v in x1.items() if k in ("row_cap", "cw_kf", "cw_n", "ord_kf", "ord_n")}))
+
+
+def test_map_replace_and_map_fuse_agree_with_the_pair_check(lib):
+    """What slamit_map_replace_apply and slamit_map_fuse_apply refuse of their tables is map_replace_tables_error's text for the same pair."""
+    from weiner_slamit_v2_amd import api
+    from tests import map_fuse_fixtures, map_fuse_host, map_replace_fixtures, map_replace_host
+
+    fr, ff = map_replace_fixtures.by_name("add_order"), map_fuse_fixtures.by_name("mixed")
+    mr = lambda t, x, cap: api.map_replace(t, x, map_replace_host.records(fr["ops"]), obs_cap_out=cap)
+    mf = lambda t, x, cap: api.map_fuse(t, x, map_fuse_host.records(ff["ops"]), obs_cap_out=cap)
+    for where, call, t, x in (("slamit_map_replace_apply", mr, fr["t"], fr["x"]), ("slamit_map_fuse_apply", mf, ff["t"], ff["x"])):
+        room = len(t["obs_kf"]) + len(fr["ops"]) + len(ff["ops"])
+        faults = [(dict(t, n_kf=MAX_KF + 1), x, room), (dict(t, n_mp=-1), x, room), (t, x, -1), (dict(t, obs_ptr=None), x, room), (dict(t, kf_mp_ptr=None), x, room),
+                  (dict(t, obs_ptr=_at(t["obs_ptr"], 0, 1)), x, room), (dict(t, kf_mp_ptr=np.asarray(t["kf_mp_ptr"])[::-1].copy()), x, room),
+                  (dict(t, obs_kf=None), x, room), (dict(t, mp_bad=None), x, room), (dict(t, kf_mp=None), x, room),
+                  (dict(t, obs_kf=_at(t["obs_kf"], 4, t["n_kf"])), x, room), (t, dict(x, obs_idx=_at(x["obs_idx"], 1, 999)), room),
+                  (t, dict(x, obs_weight=_at(x["obs_weight"], 2, 3)), room), (dict(t, obs_ptr=_at(t["obs_ptr"], 0, 1)), dict(x, mp_nobs=None), -1)]
+        faults += [(t, dict(x, **{key: None}), room) for key in ("obs_idx", "obs_octave", "obs_weight", "mp_nobs", "mp_found", "mp_visible", "mp_replaced")]
+        for t1, x1, cap in faults:
+            tab = dict(t1, **x1)
+            bits = sum(1 << REPLACE_POINTERS.index(k) for k in REPLACE_POINTERS[:9] if tab.get(k) is None)
+            text = check(lib, REPLACE_TABLES, tab, (bits, cap, 0))
+            assert isinstance(text, str), (where, bits, cap)
+            assert _message(lambda: call(t1, x1, cap)) == where + ": " + text, (where, text)

@@ -1,5 +1,5 @@
 // map_check.h — what a valid map table is, for the host forms of the map modules (local_map, covis, upkeep, map_edit, map_replace,
-// kf_erase): the one statement between a caller's host pointers and a kernel that dereferences them.  Plain C++11 over
+// map_fuse, kf_erase): the one statement between a caller's host pointers and a kernel that dereferences them.  Plain C++11 over
 // include/slamit.h, no HIP: tests/test_map_check.py builds it with g++.
 //
 // Every *_error function returns nullptr, or the text of what is wrong without the "where: " prefix; the entry point hands it to
@@ -44,6 +44,39 @@ static inline const char* map_obs_error(const slamit_map_index* map, const int32
         if (k < 0 || k >= map->n_kf) return "obs_kf holds a keyframe slot outside [0, n_kf)";
         if (obs_idx && (obs_idx[o] < 0 || obs_idx[o] >= map->kf_mp_ptr[k + 1] - map->kf_mp_ptr[k])) return "obs_idx holds a keypoint index outside its keyframe's row";
         if (obs_weight && obs_weight[o] != 1 && obs_weight[o] != 2) return "obs_weight holds a weight other than 1 or 2";
+    }
+    return nullptr;
+}
+
+// The pair slamit_map_index + slamit_replace_index of a host form (map_replace, map_fuse), from the two records themselves through
+// map_obs_error, in the order the entry points have always tested.  touched: the entry point's own output of n_mp entries, tested
+// here because its place lies between the tables' tests.
+static inline const char* map_replace_tables_error(const slamit_map_index* map, const slamit_replace_index* X, const int32_t* touched) {
+    if (!map || !X) return "null table";
+    if (const char* bad = map_sizes_error(map)) return bad;
+    const int n_kf = map->n_kf, n_mp = map->n_mp;
+    if (n_mp && !touched) return "null array or negative n";
+    if (X->obs_cap_out < 0) return "negative obs_cap_out";
+    if (!map->obs_ptr || !map->kf_mp_ptr || !X->obs_ptr_out) return "null table";
+    if (!map_csr_ok(map->obs_ptr, n_mp) || !map_csr_ok(map->kf_mp_ptr, n_kf)) return "a CSR pointer array does not ascend from 0";
+    const size_t n_obs = (size_t)map->obs_ptr[n_mp], n_kfmp = (size_t)map->kf_mp_ptr[n_kf], cap_out = (size_t)X->obs_cap_out;
+    if ((n_obs && (!map->obs_kf || !X->obs_idx || !X->obs_octave || !X->obs_weight)) ||
+        (n_mp && (!X->mp_bad || !X->mp_nobs || !X->mp_found || !X->mp_visible || !X->mp_replaced)) || (n_kfmp && !X->kf_mp) ||
+        (cap_out && (!X->obs_kf_out || !X->obs_idx_out || !X->obs_octave_out || !X->obs_weight_out)))
+        return "null table";
+    return map_obs_error(map, X->obs_idx, X->obs_weight);
+}
+// The same pair in a resident form, map by map: the sizes and the pointers, which are the device's and not read here.
+static inline const char* map_replace_batch_error(int n_maps, int mp_cap, const slamit_map_index* maps, const slamit_replace_index* index) {
+    for (int m = 0; m < n_maps; ++m) {
+        const slamit_map_index& M = maps[m];
+        const slamit_replace_index& X = index[m];
+        if (const char* bad = map_batch_sizes_error(&M)) return bad;
+        if (M.n_mp > mp_cap) return "a map with n_mp above mp_cap";
+        if (X.obs_cap_out < 0) return "negative obs_cap_out";
+        if (!M.obs_ptr || !M.obs_kf || !M.kf_mp_ptr || !X.obs_idx || !X.obs_octave || !X.obs_weight || !X.mp_bad || !X.mp_nobs || !X.mp_found || !X.mp_visible ||
+            !X.mp_replaced || !X.kf_mp || !X.obs_ptr_out || !X.obs_kf_out || !X.obs_idx_out || !X.obs_octave_out || !X.obs_weight_out)
+            return "null table";
     }
     return nullptr;
 }

@@ -14,8 +14,8 @@
 //                      scan of the lengths, writes the row and its columns at the new offset, mp_bad / mp_nobs / mp_ref_kf, and issues the
 //                      kf_mp writes as atomicMax of (list index + 1) << 32 | (value + 1) into the 64-bit workspace beside kf_mp.
 // me_copy_kernel       the rows of the points without edits: a wavefront takes 64 consecutive points, whose entries are consecutive in the
-//                      old table, and every lane finds its entry's point by bisection in LDS; the new pointer array, the per-point status,
-//                      touched (compacted through the scan), the counts and the call's status.
+//                      old table, and every lane finds its entry's point by bisection in LDS (map_rows_dev.h); the new pointer array,
+//                      the per-point status, touched (compacted through the scan), the counts and the call's status.
 // me_kfmp_kernel       the winners of the kf_mp workspace into kf_mp.
 // THE GATE: every kernel that writes a caller's array first reads the table's need (the scan's total) from device memory and leaves
 // when it exceeds obs_cap_out; me_copy_kernel writes n_obs_out and the status before it does.
@@ -32,6 +32,7 @@
 #include "wave_ops.h"
 #include "map_check.h"
 #include "map_edit.h"
+#include "map_rows_dev.h"
 
 static_assert(sizeof(MeEdit) == sizeof(slamit_map_edit) && offsetof(MeEdit, mp) == offsetof(slamit_map_edit, mp) && offsetof(MeEdit, idx) == offsetof(slamit_map_edit, idx) &&
                   offsetof(MeEdit, octave) == offsetof(slamit_map_edit, octave) && offsetof(MeEdit, weight) == offsetof(slamit_map_edit, weight),
@@ -110,32 +111,18 @@ __global__ __launch_bounds__(ME_NT) void me_hist_kernel(MeBatch B) {
     else atomicOr(&B.flags[4 * m], ME_BAD_SLOT);
 }
 
-// ---- the device scan (block_inclusive_scan_i32 and block_scan_parts_i32 of wave_ops.h) ------------------------------------------
-// grid (nparts, maps, arrays): the sum of block x of array z (a, b: rows S apart) over the first n_mp entries
+// ---- the device scan: the three kernels over map_rows_dev.h's bodies; a, b, out_a, out_b: rows S apart ---------------------------
+// grid (nparts, maps, arrays), (maps, arrays), (nparts, maps, arrays)
 __global__ __launch_bounds__(ME_NT) void me_scan_sum_kernel(MeBatch B, const int32_t* a, const int32_t* b) {
-    const int m = blockIdx.y, i = blockIdx.x * ME_NT + (int)threadIdx.x;
-    const size_t S = (size_t)B.mp_cap + 1;
-    const int32_t* const src = (blockIdx.z ? b : a) + m * S;
-    int total;
-    block_inclusive_scan_i32<ME_NT>(i < B.maps[m].n_mp ? src[i] : 0, total);
-    if (threadIdx.x == 0) B.parts[((size_t)m * 2 + blockIdx.z) * (B.nparts + 1) + blockIdx.x] = total;
+    const int m = blockIdx.y;
+    const size_t r = m * ((size_t)B.mp_cap + 1);
+    map_scan_sum<ME_NT>(B.parts, B.nparts, B.maps[m].n_mp, [&](int z, int i) { return (z ? b : a)[r + i]; });
 }
-// grid (maps, arrays): the sums scanned in place by one workgroup, the total at [nparts]
-__global__ __launch_bounds__(ME_NT) void me_scan_parts_kernel(MeBatch B) {
-    block_scan_parts_i32<ME_NT>(B.parts + ((size_t)blockIdx.x * 2 + blockIdx.y) * (B.nparts + 1), B.nparts);
-}
-// grid (nparts, maps, arrays): out[i] = what lies before entry i, out[n_mp] = the total
+__global__ __launch_bounds__(ME_NT) void me_scan_parts_kernel(MeBatch B) { map_scan_parts<ME_NT>(B.parts, B.nparts); }
 __global__ __launch_bounds__(ME_NT) void me_scan_add_kernel(MeBatch B, const int32_t* a, const int32_t* b, int32_t* out_a, int32_t* out_b) {
-    const int m = blockIdx.y, i = blockIdx.x * ME_NT + (int)threadIdx.x, n = B.maps[m].n_mp;
-    const size_t S = (size_t)B.mp_cap + 1;
-    const int32_t* const src = (blockIdx.z ? b : a) + m * S;
-    int32_t* const out = (blockIdx.z ? out_b : out_a) + m * S;
-    const int32_t* const parts = B.parts + ((size_t)m * 2 + blockIdx.z) * (B.nparts + 1);
-    const int v = i < n ? src[i] : 0;
-    int total;
-    const int incl = block_inclusive_scan_i32<ME_NT>(v, total);
-    if (i < n) out[i] = parts[blockIdx.x] + incl - v;
-    else if (i == n) out[i] = parts[B.nparts];     // n <= mp_cap: inside the row
+    const int m = blockIdx.y;
+    const size_t r = m * ((size_t)B.mp_cap + 1);
+    map_scan_add<ME_NT>(B.parts, B.nparts, B.maps[m].n_mp, [&](int z, int i) { return (z ? b : a)[r + i]; }, (blockIdx.z ? out_b : out_a) + r);   // n_mp <= mp_cap: inside the row
 }
 
 // ---- grid (ceil(max(cap, mp_cap) / 256), maps) ----------------------------------------------------------------------------------
@@ -301,9 +288,7 @@ __global__ __launch_bounds__(64) void me_apply_kernel(MeBatch B) {
 
 // ---- grid (ceil((mp_cap + 1) / 256), maps) ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(ME_NT) void me_copy_kernel(MeBatch B) {
-    __shared__ int32_t optr[ME_NT / 64][65], nptr[ME_NT / 64][65];
-    __shared__ uint8_t skip[ME_NT / 64][64];
-    const int m = blockIdx.y, p = blockIdx.x * ME_NT + (int)threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int m = blockIdx.y, p = blockIdx.x * ME_NT + (int)threadIdx.x;
     const LmMap& M = B.maps[m];
     const MeIndex& X = B.X[m];
     const size_t S = (size_t)B.mp_cap + 1;
@@ -320,23 +305,8 @@ __global__ __launch_bounds__(ME_NT) void me_copy_kernel(MeBatch B) {
         if (!sk) B.status_mp[(size_t)m * B.mp_cap + p] = 0;
         if (B.tflag[m * S + p]) B.touched[(size_t)m * B.mp_cap + B.tpos[m * S + p]] = p;   // tpos < the touched before p <= p
     }
-    const int p0 = blockIdx.x * ME_NT + w * 64;
-    if (p0 >= n_mp) return;                                             // the whole wavefront
-    optr[w][lane] = M.obs_ptr[min(p0 + lane, n_mp)]; nptr[w][lane] = newptr[min(p0 + lane, n_mp)];
-    if (lane == 63) { optr[w][64] = M.obs_ptr[min(p0 + 64, n_mp)]; nptr[w][64] = newptr[min(p0 + 64, n_mp)]; }
-    skip[w][lane] = sk;
-    wave_mem_sync();
-    const int e1 = optr[w][64];
-    for (int e = optr[w][0] + lane; e < e1; e += 64) {
-        int lo = 0, hi = 63;                                            // the row q with optr[q] <= e < optr[q + 1]
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (optr[w][mid + 1] > e) hi = mid; else lo = mid + 1;
-        }
-        if (skip[w][lo]) continue;
-        const int at = nptr[w][lo] + (e - optr[w][lo]);                 // an unchanged row: inside the new table
-        X.obs_kf_out[at] = M.obs_kf[e]; X.obs_idx_out[at] = X.obs_idx[e]; X.obs_octave_out[at] = X.obs_octave[e]; X.obs_weight_out[at] = X.obs_weight[e];
-    }
+    map_copy_unnamed_rows<ME_NT>(p & ~63, sk, M.obs_ptr, newptr, n_mp, M.obs_kf, X.obs_idx, X.obs_octave, X.obs_weight, X.obs_kf_out, X.obs_idx_out,
+                                 X.obs_octave_out, X.obs_weight_out);
 }
 
 // ---- grid (ceil(kfmp_cap / 256), maps) ------------------------------------------------------------------------------------------

@@ -18,6 +18,8 @@
 // mf_finish_kernel   the working image into kf_mp; outcome / moved / erased.
 // THE GATE: every kernel that writes a caller's array first reads the overflow word and the table's need from device memory.
 // A row that holds one (keyframe, index) pair twice (no std::map does) has its two kf_mp writes in one store instruction.
+// The working rows, the world over them (holds / push / fuse / retire), the scan bodies and the row copy are map_rows_dev.h's, the one
+// text map_replace.hip runs too; MfWorldDev below adds what mf_walk_op asks for beyond mr_walk_op.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -31,6 +33,7 @@
 #include "wave_ops.h"
 #include "map_check.h"
 #include "map_fuse.h"
+#include "map_rows_dev.h"
 
 static_assert(sizeof(MrOp) == sizeof(slamit_map_replace) && sizeof(MrOp) == 20 && sizeof(MrIndex) == sizeof(slamit_replace_index) && sizeof(LmMap) == sizeof(slamit_map_index),
               "the records of map_replace.h are the C-ABI's");
@@ -42,72 +45,42 @@ static_assert(MF_FUSE == SLAMIT_FUSE_FUSE && MF_MAX_OPS == SLAMIT_FUSE_MAX_OPS &
               "map_fuse.h restates the C-ABI's constants, and its status bits are map_replace.h's");
 
 #define MF_NT 256
-enum { MR_F_OP_BAD = 0, MR_F_OBS_BAD = 1, MR_F_OP_OVER = 2, MR_F_OBS_OVER = 3, MR_NFLAGS = 8 };
-enum { MR_C_LEN = 0, MR_C_BAD, MR_C_NOBS, MR_C_FOUND, MR_C_VISIBLE, MR_C_REPLACED, MR_C_RECEIVED, MR_NCOLS };
 #define MF_TO_WALK (-1)   // an op's outcome word until the walk has taken it
 
-// The batch as the kernels' argument.  The workspace rows of a map lie S = mp_cap + 1 apart; an involved point has a compact number
-// below ninv = min(2 cap, mp_cap) and a working row of MR_MAX_OBS entries.
+// The batch as the kernels' argument: W the workspace rows of map_rows_dev.h (cnt: 1 for an involved point), then this module's own.
 struct MfBatch {
     int32_t n_maps, cap, mp_cap, kfmp_cap;
     LmMap maps[SLAMIT_LOCAL_MAP_MAX_MAPS];
     MrIndex X[SLAMIT_LOCAL_MAP_MAX_MAPS];
     const MrOp* ops; const int32_t* n;
     int32_t* outcome; int32_t* moved; int32_t* erased; int32_t* touched; int32_t* n_touched; int32_t* n_fused; int32_t* n_obs_out; int32_t* status;
-    int32_t* flags;            // [n_maps][MR_NFLAGS]     cleared
-    int32_t* cnt;              // [n_maps][S]             cleared: 1 for an involved point
-    int32_t* cidx;             // [n_maps][S]             the compact number of an involved point, their count at [n_mp]
-    int32_t* newptr;           // [n_maps][S]             the new pointer array, the table's need at [n_mp]
-    int32_t* tpos;             // [n_maps][S]
-    int32_t* parts;            // [n_maps][2][nparts + 1]
+    MapRows W;
     int32_t* oc;               // [n_maps][cap]           MF_TO_WALK, then the outcome
     int32_t* mv;               // [n_maps][cap]
     int32_t* er;               // [n_maps][cap]
     int32_t* fused;            // [n_maps]
-    int32_t* inv;              // [n_maps][ninv]          the slot of a compact number
-    int32_t* wcol;             // [n_maps][MR_NCOLS][ninv]
     int32_t* image;            // [n_maps][kfmp_cap]      kf_mp as the walk has it
-    int32_t* wkf;              // [n_maps][ninv][MR_MAX_OBS]
-    int32_t* widx;
-    uint8_t* woct;
-    uint8_t* wwgt;
-    int32_t nparts, ninv;
 };
 
 static size_t mf_ws_layout(int n_maps, int cap, int mp_cap, int kfmp_cap, unsigned char* base, MfBatch* B, size_t* clear_bytes) {
-    const size_t S = (size_t)mp_cap + 1, nm = (size_t)n_maps, nparts = (S + MF_NT - 1) / MF_NT, c = (size_t)cap;
-    const size_t ninv = std::min(2 * c, (size_t)mp_cap), rows = nm * ninv * MR_MAX_OBS;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 15) & ~(size_t)15; return base ? base + at : nullptr; };
-    unsigned char* const flags = take(4 * nm * MR_NFLAGS);
-    unsigned char* const cnt = take(4 * nm * S);
-    if (clear_bytes) *clear_bytes = off;
-    unsigned char* const cidx = take(4 * nm * S);
-    unsigned char* const newptr = take(4 * nm * S);
-    unsigned char* const tpos = take(4 * nm * S);
-    unsigned char* const parts = take(4 * nm * 2 * (nparts + 1));
-    unsigned char* const oc = take(4 * nm * c);
-    unsigned char* const mv = take(4 * nm * c);
-    unsigned char* const er = take(4 * nm * c);
-    unsigned char* const fused = take(4 * nm);
-    unsigned char* const inv = take(4 * nm * ninv);
-    unsigned char* const wcol = take(4 * nm * MR_NCOLS * ninv);
-    unsigned char* const image = take(4 * nm * (size_t)kfmp_cap);
-    unsigned char* const wkf = take(4 * rows);
-    unsigned char* const widx = take(4 * rows);
-    unsigned char* const woct = take(rows);
-    unsigned char* const wwgt = take(rows);
-    if (B) {
-        B->flags = (int32_t*)flags; B->cnt = (int32_t*)cnt; B->cidx = (int32_t*)cidx; B->newptr = (int32_t*)newptr; B->tpos = (int32_t*)tpos; B->parts = (int32_t*)parts;
-        B->oc = (int32_t*)oc; B->mv = (int32_t*)mv; B->er = (int32_t*)er; B->fused = (int32_t*)fused; B->inv = (int32_t*)inv; B->wcol = (int32_t*)wcol;
-        B->image = (int32_t*)image; B->wkf = (int32_t*)wkf; B->widx = (int32_t*)widx; B->woct = woct; B->wwgt = wwgt; B->nparts = (int32_t)nparts; B->ninv = (int32_t)ninv;
-    }
-    return off;
+    MapRowsLayout L(n_maps, cap, mp_cap, base);
+    const size_t nm = L.nm, c = L.c;
+    L.cleared();
+    if (clear_bytes) *clear_bytes = L.off;
+    L.scanned();
+    int32_t* const oc = L.take<int32_t>(nm * c);
+    int32_t* const mv = L.take<int32_t>(nm * c);
+    int32_t* const er = L.take<int32_t>(nm * c);
+    int32_t* const fused = L.take<int32_t>(nm);
+    L.columns();
+    int32_t* const image = L.take<int32_t>(nm * (size_t)kfmp_cap);
+    L.rows();
+    if (B) { B->W = L.W; B->oc = oc; B->mv = mv; B->er = er; B->fused = fused; B->image = image; }
+    return L.off;
 }
 
-__device__ __forceinline__ int32_t* mf_col(const MfBatch& B, int m, int col) { return B.wcol + ((size_t)m * MR_NCOLS + col) * (size_t)B.ninv; }
 __device__ __forceinline__ bool mf_gate(const MfBatch& B, int m) {
-    return B.flags[MR_NFLAGS * m + MR_F_OBS_OVER] != 0 || B.newptr[(size_t)m * (B.mp_cap + 1) + B.maps[m].n_mp] > B.X[m].obs_cap_out;
+    return B.W.flags[MR_NFLAGS * m + MR_F_OBS_OVER] != 0 || B.W.newptr[(size_t)m * (B.mp_cap + 1) + B.maps[m].n_mp] > B.X[m].obs_cap_out;
 }
 
 // ---- grid (ceil(max(cap, kfmp_cap) / 256), maps) --------------------------------------------------------------------------------
@@ -125,15 +98,15 @@ __global__ __launch_bounds__(MF_NT) void mf_mark_kernel(MfBatch B) {
             at = mr_kfmp_at(M, e.b, e.idx);
             ok = at < B.kfmp_cap;                                        // the occupant is read there
         }
-        if (!ok) atomicOr(&B.flags[MR_NFLAGS * m + MR_F_OP_BAD], 1);
+        if (!ok) atomicOr(&B.W.flags[MR_NFLAGS * m + MR_F_OP_BAD], 1);
         else if (!mf_op_acts(e)) out = e.kind == MF_FUSE ? MF_OUT_NOMATCH : MF_OUT_PLAIN;
         else {
             out = MF_TO_WALK;
-            B.cnt[m * S + e.a] = 1;
-            if (e.kind == MR_REPLACE) B.cnt[m * S + e.b] = 1;
+            B.W.cnt[m * S + e.a] = 1;
+            if (e.kind == MR_REPLACE) B.W.cnt[m * S + e.b] = 1;
             if (e.kind == MF_FUSE) {
                 const int q = X.kf_mp[at];                               // the INITIAL occupant
-                if (lm_mp_ok(M, q)) B.cnt[m * S + q] = 1;
+                if (lm_mp_ok(M, q)) B.W.cnt[m * S + q] = 1;
             }
         }
         B.oc[m * c + i] = out; B.mv[m * c + i] = 0; B.er[m * c + i] = 0;
@@ -146,37 +119,24 @@ __global__ __launch_bounds__(MF_NT) void mf_mark_kernel(MfBatch B) {
 // received an observation.
 __device__ __forceinline__ int mf_scan_src(const MfBatch& B, int m, int mode, int z, int p) {
     const size_t S = (size_t)B.mp_cap + 1;
-    const int c = B.cnt[m * S + p];
+    const int c = B.W.cnt[m * S + p];
     if (mode == 0) return c;
     if (c == 0) return z ? 0 : B.maps[m].obs_ptr[p + 1] - B.maps[m].obs_ptr[p];
-    const int ci = B.cidx[m * S + p];                                  // < ninv: the involved points are counted there
-    return mf_col(B, m, z ? MR_C_RECEIVED : MR_C_LEN)[ci];
+    const int ci = B.W.cidx[m * S + p];                                // < ninv: the involved points are counted there
+    return map_rows_col(B.W, m, z ? MR_C_RECEIVED : MR_C_LEN)[ci];
 }
-// grid (nparts, maps, mode 0: 1, mode 1: 2): the sum of block x of array z over the first n_mp entries
+// the three kernels over map_rows_dev.h's bodies.  grid (nparts, maps, arrays), (maps, arrays), (nparts, maps, arrays); mode 0: one
+// array, mode 1: two.  Mode 0 of the add pass also writes the slot of each compact number.
 __global__ __launch_bounds__(MF_NT) void mf_scan_sum_kernel(MfBatch B, int mode) {
-    const int m = blockIdx.y, i = blockIdx.x * MF_NT + (int)threadIdx.x;
-    int total;
-    block_inclusive_scan_i32<MF_NT>(i < B.maps[m].n_mp ? mf_scan_src(B, m, mode, blockIdx.z, i) : 0, total);
-    if (threadIdx.x == 0) B.parts[((size_t)m * 2 + blockIdx.z) * (B.nparts + 1) + blockIdx.x] = total;
+    const int m = blockIdx.y;
+    map_scan_sum<MF_NT>(B.W.parts, B.W.nparts, B.maps[m].n_mp, [&](int z, int p) { return mf_scan_src(B, m, mode, z, p); });
 }
-// grid (maps, 1 or 2): the sums scanned in place by one workgroup, the total at [nparts]
-__global__ __launch_bounds__(MF_NT) void mf_scan_parts_kernel(MfBatch B) {
-    block_scan_parts_i32<MF_NT>(B.parts + ((size_t)blockIdx.x * 2 + blockIdx.y) * (B.nparts + 1), B.nparts);
-}
-// grid (nparts, maps, 1 or 2): out[i] = what lies before entry i, out[n_mp] = the total; mode 0 also writes the slot of each number
+__global__ __launch_bounds__(MF_NT) void mf_scan_parts_kernel(MfBatch B) { map_scan_parts<MF_NT>(B.W.parts, B.W.nparts); }
 __global__ __launch_bounds__(MF_NT) void mf_scan_add_kernel(MfBatch B, int mode) {
     const int m = blockIdx.y, i = blockIdx.x * MF_NT + (int)threadIdx.x, n = B.maps[m].n_mp;
-    const size_t S = (size_t)B.mp_cap + 1;
-    int32_t* const out = (mode == 0 ? B.cidx : (blockIdx.z ? B.tpos : B.newptr)) + m * S;
-    const int32_t* const parts = B.parts + ((size_t)m * 2 + blockIdx.z) * (B.nparts + 1);
-    const int v = i < n ? mf_scan_src(B, m, mode, blockIdx.z, i) : 0;
-    int total;
-    const int incl = block_inclusive_scan_i32<MF_NT>(v, total);
-    const int before = parts[blockIdx.x] + incl - v;
-    if (i < n) {
-        out[i] = before;
-        if (mode == 0 && v && before < B.ninv) B.inv[(size_t)m * B.ninv + before] = i;   // at most 2 per op and n_mp are involved: always inside
-    } else if (i == n) out[i] = parts[B.nparts];                        // n <= mp_cap: inside the row
+    int32_t* const out = (mode == 0 ? B.W.cidx : (blockIdx.z ? B.W.tpos : B.W.newptr)) + m * ((size_t)B.mp_cap + 1);
+    const MapScanAt at = map_scan_add<MF_NT>(B.W.parts, B.W.nparts, n, [&](int z, int p) { return mf_scan_src(B, m, mode, z, p); }, out);   // n <= mp_cap: inside the row
+    if (mode == 0 && at.v && at.before < B.W.ninv) B.W.inv[(size_t)m * B.W.ninv + at.before] = i;   // v != 0: i < n; at most 2 per op and n_mp are involved: always inside
 }
 
 // ---- grid (ceil(ninv / 4), maps), 256 threads: a wavefront per involved point --------------------------------------------------
@@ -185,26 +145,12 @@ __global__ __launch_bounds__(MF_NT) void mf_prep_kernel(MfBatch B) {
     const LmMap& M = B.maps[m];
     const MrIndex& X = B.X[m];
     const size_t S = (size_t)B.mp_cap + 1;
-    if (ci >= min(B.cidx[m * S + M.n_mp], B.ninv)) return;              // the whole wavefront
-    const int p = __builtin_amdgcn_readfirstlane(B.inv[(size_t)m * B.ninv + ci]);
-    const int o0 = __builtin_amdgcn_readfirstlane(M.obs_ptr[p]);
-    int len0 = __builtin_amdgcn_readfirstlane(M.obs_ptr[p + 1]) - o0;
-    if (len0 > MR_MAX_OBS || len0 < 0) {
-        if (lane == 0) atomicOr(&B.flags[MR_NFLAGS * m + MR_F_OBS_OVER], 1);
-        len0 = 0;
-    }
-    const size_t r0 = ((size_t)m * B.ninv + ci) * MR_MAX_OBS;
-    for (int e = lane; e < len0; e += 64) {
-        B.wkf[r0 + e] = M.obs_kf[o0 + e]; B.widx[r0 + e] = X.obs_idx[o0 + e]; B.woct[r0 + e] = X.obs_octave[o0 + e]; B.wwgt[r0 + e] = X.obs_weight[o0 + e];
-    }
-    if (lane == 0) {
-        mf_col(B, m, MR_C_LEN)[ci] = len0; mf_col(B, m, MR_C_BAD)[ci] = X.mp_bad[p]; mf_col(B, m, MR_C_NOBS)[ci] = X.mp_nobs[p];
-        mf_col(B, m, MR_C_FOUND)[ci] = X.mp_found[p]; mf_col(B, m, MR_C_VISIBLE)[ci] = X.mp_visible[p]; mf_col(B, m, MR_C_REPLACED)[ci] = X.mp_replaced[p];
-        mf_col(B, m, MR_C_RECEIVED)[ci] = 0;
-    }
+    if (ci >= min(B.W.cidx[m * S + M.n_mp], B.W.ninv)) return;          // the whole wavefront
+    const int p = __builtin_amdgcn_readfirstlane(B.W.inv[(size_t)m * B.W.ninv + ci]);
+    map_row_load(B.W, m, M, X, ci, p, lane);
 }
 
-// ---- the world of mf_walk_op on the device: one wavefront, the rows in the workspace, the working image of kf_mp - ----------------------------------
+// ---- the world of mf_walk_op on the device: MapWorldDev of map_rows_dev.h over the rows, and the working image of kf_mp ---------
 struct MfEmitDev {   // one wavefront walks the list, so a later write simply comes later
     const LmMap* M; int32_t* image; int32_t* flags;
     int kfmp_cap, lane;
@@ -217,81 +163,8 @@ struct MfEmitDev {   // one wavefront walks the list, so a later write simply co
         if (lane == 0) mine(k, i, value, li);
     }
 };
-struct MfWorldDev {   // holds / push / fuse / retire: the wavefront form of map_replace.hip's world, restated (that file's text is pinned by its test)
+struct MfWorldDev : MapWorldDev {   // what mf_walk_op asks for beyond mr_walk_op
     const LmMap* M; const int32_t* image;
-    const int32_t* cidx; int32_t* flags;
-    int32_t* col[MR_NCOLS];
-    int32_t* wkf; int32_t* widx; uint8_t* woct; uint8_t* wwgt;          // the map's working rows
-    int32_t* skf; uint16_t* sord;                                       // this wavefront's LDS: S's keyframes, S's entries by rank
-    int lane;
-    __device__ __forceinline__ int len_of(int ci) const { return __builtin_amdgcn_readfirstlane(col[MR_C_LEN][ci]); }
-    __device__ __forceinline__ bool holds(int p, int k) const {
-        const int ci = cidx[p], len = len_of(ci);
-        const size_t r0 = (size_t)ci * MR_MAX_OBS;
-        for (int e0 = 0; e0 < len; e0 += 64)
-            if (__ballot(e0 + lane < len && wkf[r0 + e0 + lane] == k)) return true;
-        return false;
-    }
-    __device__ __forceinline__ int push(int p, int k, int i, uint8_t o, uint8_t wt) {
-        const int ci = cidx[p], len = len_of(ci);
-        if (len >= MR_MAX_OBS) {
-            if (lane == 0) atomicOr(&flags[MR_F_OBS_OVER], 1);
-            return 0;
-        }
-        if (lane == 0) {
-            const size_t at = (size_t)ci * MR_MAX_OBS + len;
-            wkf[at] = k; widx[at] = i; woct[at] = o; wwgt[at] = wt;
-            col[MR_C_LEN][ci] = len + 1; col[MR_C_NOBS][ci] += wt; col[MR_C_RECEIVED][ci] = 1;
-        }
-        return 1;
-    }
-    template <class Emit>
-    __device__ __forceinline__ void fuse(int S, int D, Emit& emit, int li, int& moved, int& erased) {
-        const int cs = cidx[S], cd = cidx[D], len_s = len_of(cs), len_d = len_of(cd);
-        const size_t rs = (size_t)cs * MR_MAX_OBS, rd = (size_t)cd * MR_MAX_OBS;
-        wave_mem_sync();                                                 // the LDS of the op before
-        for (int e = lane; e < len_s; e += 64) skf[e] = wkf[rs + e];
-        wave_mem_sync();
-        for (int e = lane; e < len_s; e += 64) {                        // ascending slot, row order among equals
-            const uint32_t key = (uint32_t)skf[e];
-            int rank = 0;
-            for (int f = 0; f < len_s; ++f) { const uint32_t o = (uint32_t)skf[f]; rank += (o < key) || (o == key && f < e); }
-            sord[rank] = (uint16_t)e;
-        }
-        wave_mem_sync();
-        int n_moved = 0, add = 0, over = 0;
-        for (int j0 = 0; j0 < len_s; j0 += 64) {
-            const int j = j0 + lane;
-            const bool act = j < len_s;
-            const int e = act ? sord[j] : 0, k = act ? skf[e] : 0;
-            bool go = act && (j == 0 || skf[sord[j - 1]] != k);         // the first of a run of one keyframe decides
-            if (go)
-                for (int f = 0; f < len_d; ++f) go = go && wkf[rd + f] != k;     // D's row as the op met it: the received keyframes are S's own
-            const int i = act ? widx[rs + e] : 0, wt = act ? wwgt[rs + e] : 0;
-            const unsigned long long mask = __ballot(go);
-            if (go) {
-                const int at = len_d + n_moved + __popcll(mask & ((1ull << lane) - 1ull));
-                if (at >= MR_MAX_OBS) over = 1;
-                else { wkf[rd + at] = k; widx[rd + at] = i; woct[rd + at] = woct[rs + e]; wwgt[rd + at] = (uint8_t)wt; }
-            }
-            if (act) emit.mine(k, i, go ? D : -1, li);
-            add += __builtin_amdgcn_readlane(wave_inclusive_scan_i32(go ? wt : 0), 63);
-            n_moved += __popcll(mask);
-        }
-        if (__ballot(over != 0)) {
-            if (lane == 0) atomicOr(&flags[MR_F_OBS_OVER], 1);
-            n_moved = MR_MAX_OBS - len_d;
-        }
-        if (lane == 0 && n_moved > 0) { col[MR_C_LEN][cd] = len_d + n_moved; col[MR_C_NOBS][cd] += add; col[MR_C_RECEIVED][cd] = 1; }
-        moved = n_moved; erased = len_s - n_moved;
-    }
-    __device__ __forceinline__ void retire(int S, int D) {
-        if (lane != 0) return;
-        const int cs = cidx[S], cd = cidx[D];
-        col[MR_C_LEN][cs] = 0; col[MR_C_BAD][cs] = 1; col[MR_C_REPLACED][cs] = D;
-        col[MR_C_FOUND][cd] = (int32_t)((uint32_t)col[MR_C_FOUND][cd] + (uint32_t)col[MR_C_FOUND][cs]);
-        col[MR_C_VISIBLE][cd] = (int32_t)((uint32_t)col[MR_C_VISIBLE][cd] + (uint32_t)col[MR_C_VISIBLE][cs]);
-    }
     __device__ __forceinline__ bool bad(int p) const { return __builtin_amdgcn_readfirstlane(col[MR_C_BAD][cidx[p]]) != 0; }
     __device__ __forceinline__ int nobs(int p) const { return __builtin_amdgcn_readfirstlane(col[MR_C_NOBS][cidx[p]]); }
     __device__ __forceinline__ int occupant(int k, int i) const { return __builtin_amdgcn_readfirstlane(image[mr_kfmp_at(*M, k, i)]); }   // marked: inside the image
@@ -308,17 +181,13 @@ __global__ __launch_bounds__(64) void mf_walk_kernel(MfBatch B) {
     const int m = blockIdx.x, lane = threadIdx.x;
     const LmMap& M = B.maps[m];
     const size_t S = (size_t)B.mp_cap + 1, c = (size_t)B.cap;
-    int32_t* const flags = B.flags + MR_NFLAGS * m;
+    int32_t* const flags = B.W.flags + MR_NFLAGS * m;
     if (flags[MR_F_OBS_OVER]) return;                                   // an input row above the ceiling: the call is refused
     const int n = lm_list_n(B.n[m], B.cap);
     const int32_t* const raw = reinterpret_cast<const int32_t*>(B.ops + m * c);   // five words an op
     int32_t* const oc = B.oc + m * c;
-    const size_t r0 = (size_t)m * B.ninv * MR_MAX_OBS;
     MfWorldDev world;
-    world.cidx = B.cidx + m * S; world.flags = flags;
-    for (int q = 0; q < MR_NCOLS; ++q) world.col[q] = mf_col(B, m, q);
-    world.wkf = B.wkf + r0; world.widx = B.widx + r0; world.woct = B.woct + r0; world.wwgt = B.wwgt + r0;
-    world.skf = skf; world.sord = sord; world.lane = lane;
+    world.bind(B.W, m, S, skf, sord, lane);
     world.M = &M; world.image = B.image + (size_t)m * B.kfmp_cap;
     MfEmitDev emit = {&M, B.image + (size_t)m * B.kfmp_cap, flags, B.kfmp_cap, lane};
     int fused = 0;
@@ -354,29 +223,18 @@ __global__ __launch_bounds__(MF_NT) void mf_commit_kernel(MfBatch B) {
     const MrIndex& X = B.X[m];
     const size_t S = (size_t)B.mp_cap + 1;
     if (mf_gate(B, m)) return;
-    if (ci >= min(B.cidx[m * S + M.n_mp], B.ninv)) return;
-    const int p = B.inv[(size_t)m * B.ninv + ci];
-    const int len = mf_col(B, m, MR_C_LEN)[ci], d0 = B.newptr[m * S + p];   // d0 + len <= the need <= obs_cap_out
-    const size_t r0 = ((size_t)m * B.ninv + ci) * MR_MAX_OBS;
-    for (int e = lane; e < len; e += 64) {
-        X.obs_kf_out[d0 + e] = B.wkf[r0 + e]; X.obs_idx_out[d0 + e] = B.widx[r0 + e]; X.obs_octave_out[d0 + e] = B.woct[r0 + e]; X.obs_weight_out[d0 + e] = B.wwgt[r0 + e];
-    }
-    if (lane == 0) {
-        X.mp_bad[p] = (uint8_t)mf_col(B, m, MR_C_BAD)[ci]; X.mp_nobs[p] = mf_col(B, m, MR_C_NOBS)[ci]; X.mp_found[p] = mf_col(B, m, MR_C_FOUND)[ci];
-        X.mp_visible[p] = mf_col(B, m, MR_C_VISIBLE)[ci]; X.mp_replaced[p] = mf_col(B, m, MR_C_REPLACED)[ci];
-    }
+    if (ci >= min(B.W.cidx[m * S + M.n_mp], B.W.ninv)) return;
+    map_row_commit(B.W, m, S, X, ci, lane);
 }
 
 // ---- grid (ceil((mp_cap + 1) / 256), maps) ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MF_NT) void mf_copy_kernel(MfBatch B) {
-    __shared__ int32_t optr[MF_NT / 64][65], nptr[MF_NT / 64][65];
-    __shared__ uint8_t skip[MF_NT / 64][64];
-    const int m = blockIdx.y, p = blockIdx.x * MF_NT + (int)threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int m = blockIdx.y, p = blockIdx.x * MF_NT + (int)threadIdx.x;
     const LmMap& M = B.maps[m];
     const MrIndex& X = B.X[m];
     const size_t S = (size_t)B.mp_cap + 1;
-    const int32_t* const newptr = B.newptr + m * S;
-    const int32_t* const flags = B.flags + MR_NFLAGS * m;
+    const int32_t* const newptr = B.W.newptr + m * S;
+    const int32_t* const flags = B.W.flags + MR_NFLAGS * m;
     const int n_mp = M.n_mp, need = newptr[n_mp];
     const bool obs_over = flags[MR_F_OBS_OVER] != 0, table_over = !obs_over && need > X.obs_cap_out;
     bool committed;
@@ -387,29 +245,14 @@ __global__ __launch_bounds__(MF_NT) void mf_copy_kernel(MfBatch B) {
     }
     if (!committed) return;
     if (p <= n_mp) X.obs_ptr_out[p] = newptr[p];
-    if (p == n_mp) { B.n_touched[m] = B.tpos[m * S + n_mp]; B.n_fused[m] = B.fused[m]; }
+    if (p == n_mp) { B.n_touched[m] = B.W.tpos[m * S + n_mp]; B.n_fused[m] = B.fused[m]; }
     bool sk = true;
     if (p < n_mp) {
-        sk = B.cnt[m * S + p] > 0;                                      // mf_commit_kernel writes that row
-        if (sk && mf_scan_src(B, m, 1, 1, p)) B.touched[(size_t)m * B.mp_cap + B.tpos[m * S + p]] = p;   // tpos < the receivers before p <= p
+        sk = B.W.cnt[m * S + p] > 0;                                    // mf_commit_kernel writes that row
+        if (sk && mf_scan_src(B, m, 1, 1, p)) B.touched[(size_t)m * B.mp_cap + B.W.tpos[m * S + p]] = p;   // tpos < the receivers before p <= p
     }
-    const int p0 = blockIdx.x * MF_NT + w * 64;
-    if (p0 >= n_mp) return;                                             // the whole wavefront
-    optr[w][lane] = M.obs_ptr[min(p0 + lane, n_mp)]; nptr[w][lane] = newptr[min(p0 + lane, n_mp)];
-    if (lane == 63) { optr[w][64] = M.obs_ptr[min(p0 + 64, n_mp)]; nptr[w][64] = newptr[min(p0 + 64, n_mp)]; }
-    skip[w][lane] = sk;
-    wave_mem_sync();
-    const int e1 = optr[w][64];
-    for (int e = optr[w][0] + lane; e < e1; e += 64) {
-        int lo = 0, hi = 63;                                            // the row q with optr[q] <= e < optr[q + 1]
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (optr[w][mid + 1] > e) hi = mid; else lo = mid + 1;
-        }
-        if (skip[w][lo]) continue;
-        const int at = nptr[w][lo] + (e - optr[w][lo]);                 // an unchanged row: inside the new table
-        X.obs_kf_out[at] = M.obs_kf[e]; X.obs_idx_out[at] = X.obs_idx[e]; X.obs_octave_out[at] = X.obs_octave[e]; X.obs_weight_out[at] = X.obs_weight[e];
-    }
+    map_copy_unnamed_rows<MF_NT>(p & ~63, sk, M.obs_ptr, newptr, n_mp, M.obs_kf, X.obs_idx, X.obs_octave, X.obs_weight, X.obs_kf_out, X.obs_idx_out,
+                                 X.obs_octave_out, X.obs_weight_out);
 }
 
 // ---- grid (ceil(max(kfmp_cap, cap) / 256), maps) --------------------------------------------------------------------------------
@@ -426,20 +269,20 @@ __global__ __launch_bounds__(MF_NT) void mf_finish_kernel(MfBatch B) {
 }
 
 static hipError_t mf_launch(const MfBatch& B, size_t clear_bytes, hipStream_t st) {
-    hipError_t e = hipMemsetAsync(B.flags, 0, clear_bytes, st);          // flags is the workspace's first byte
+    hipError_t e = hipMemsetAsync(B.W.flags, 0, clear_bytes, st);        // flags is the workspace's first byte
     if (e != hipSuccess) return e;
-    const unsigned nm = (unsigned)B.n_maps, nparts = (unsigned)B.nparts;
+    const unsigned nm = (unsigned)B.n_maps, nparts = (unsigned)B.W.nparts;
     const auto blocks = [](int n, int per) { return (unsigned)std::max(1, (n + per - 1) / per); };
     hipLaunchKernelGGL(mf_mark_kernel, dim3(blocks(std::max(B.cap, B.kfmp_cap), MF_NT), nm), dim3(MF_NT), 0, st, B);
     hipLaunchKernelGGL(mf_scan_sum_kernel, dim3(nparts, nm, 1), dim3(MF_NT), 0, st, B, 0);
     hipLaunchKernelGGL(mf_scan_parts_kernel, dim3(nm, 1), dim3(MF_NT), 0, st, B);
     hipLaunchKernelGGL(mf_scan_add_kernel, dim3(nparts, nm, 1), dim3(MF_NT), 0, st, B, 0);
-    if (B.ninv > 0) hipLaunchKernelGGL(mf_prep_kernel, dim3(blocks(B.ninv, MF_NT / 64), nm), dim3(MF_NT), 0, st, B);
+    if (B.W.ninv > 0) hipLaunchKernelGGL(mf_prep_kernel, dim3(blocks(B.W.ninv, MF_NT / 64), nm), dim3(MF_NT), 0, st, B);
     hipLaunchKernelGGL(mf_walk_kernel, dim3(nm), dim3(64), 0, st, B);
     hipLaunchKernelGGL(mf_scan_sum_kernel, dim3(nparts, nm, 2), dim3(MF_NT), 0, st, B, 1);
     hipLaunchKernelGGL(mf_scan_parts_kernel, dim3(nm, 2), dim3(MF_NT), 0, st, B);
     hipLaunchKernelGGL(mf_scan_add_kernel, dim3(nparts, nm, 2), dim3(MF_NT), 0, st, B, 1);
-    if (B.ninv > 0) hipLaunchKernelGGL(mf_commit_kernel, dim3(blocks(B.ninv, MF_NT / 64), nm), dim3(MF_NT), 0, st, B);
+    if (B.W.ninv > 0) hipLaunchKernelGGL(mf_commit_kernel, dim3(blocks(B.W.ninv, MF_NT / 64), nm), dim3(MF_NT), 0, st, B);
     hipLaunchKernelGGL(mf_copy_kernel, dim3(nparts, nm), dim3(MF_NT), 0, st, B);
     if (std::max(B.kfmp_cap, B.cap) > 0) hipLaunchKernelGGL(mf_finish_kernel, dim3(blocks(std::max(B.kfmp_cap, B.cap), MF_NT), nm), dim3(MF_NT), 0, st, B);
     return hipGetLastError();
@@ -484,19 +327,9 @@ int slamit_map_fuse_apply(int device, const slamit_map_index* map, const slamit_
     const char* const where = "slamit_map_fuse_apply";
     if (n < 0 || !n_touched || !n_fused || !n_obs_out || !status || (n && (!ops || !outcome || !moved || !erased))) return slamit_refuse(where, "null array or negative n");
     if (n > SLAMIT_FUSE_MAX_OPS) return slamit_refuse(where, "more than SLAMIT_FUSE_MAX_OPS ops", SLAMIT_ERR_CAPACITY);
-    if (!map || !X) return slamit_refuse(where, "null table");
-    if (const char* bad = map_sizes_error(map)) return slamit_refuse(where, bad);
+    if (const char* bad = map_replace_tables_error(map, X, touched)) return slamit_refuse(where, bad);
     const int n_kf = map->n_kf, n_mp = map->n_mp;
-    if (n_mp && !touched) return slamit_refuse(where, "null array or negative n");
-    if (X->obs_cap_out < 0) return slamit_refuse(where, "negative obs_cap_out");
-    if (!map->obs_ptr || !map->kf_mp_ptr || !X->obs_ptr_out) return slamit_refuse(where, "null table");
-    if (!map_csr_ok(map->obs_ptr, n_mp) || !map_csr_ok(map->kf_mp_ptr, n_kf)) return slamit_refuse(where, "a CSR pointer array does not ascend from 0");
-    const size_t n_obs = (size_t)map->obs_ptr[n_mp], n_kfmp = (size_t)map->kf_mp_ptr[n_kf], cap_out = (size_t)X->obs_cap_out;
-    if ((n_obs && (!map->obs_kf || !X->obs_idx || !X->obs_octave || !X->obs_weight)) ||
-        (n_mp && (!X->mp_bad || !X->mp_nobs || !X->mp_found || !X->mp_visible || !X->mp_replaced)) || (n_kfmp && !X->kf_mp) ||
-        (cap_out && (!X->obs_kf_out || !X->obs_idx_out || !X->obs_octave_out || !X->obs_weight_out)))
-        return slamit_refuse(where, "null table");
-    if (const char* bad = map_obs_error(map, X->obs_idx, X->obs_weight)) return slamit_refuse(where, bad);
+    const size_t n_obs = (size_t)map->obs_ptr[n_mp], n_kfmp = (size_t)map->kf_mp_ptr[n_kf];
     if (!map_slots_ok(X->kf_mp, n_kfmp, -1, n_mp)) return slamit_refuse(where, "kf_mp holds a point slot outside [-1, n_mp)");
     for (int i = 0; i < n; ++i) {
         const slamit_map_replace& e = ops[i];
@@ -523,18 +356,7 @@ int slamit_map_fuse_apply(int device, const slamit_map_index* map, const slamit_
         [&](StageBinder& b, int, MfBatch& Q) {
             io.clear();
             Q.n_maps = 1; Q.cap = n; Q.mp_cap = n_mp; Q.kfmp_cap = (int)n_kfmp;
-            LmMap& M = Q.maps[0];
-            M.n_kf = n_kf; M.n_mp = n_mp;
-            M.obs_ptr = b.in(map->obs_ptr, (size_t)n_mp + 1); M.obs_kf = b.in(map->obs_kf, n_obs); M.kf_mp_ptr = b.in(map->kf_mp_ptr, (size_t)n_kf + 1);
-            MrIndex& E = Q.X[0];
-            E.obs_idx = b.in(X->obs_idx, n_obs); E.obs_octave = b.in(X->obs_octave, n_obs); E.obs_weight = b.in(X->obs_weight, n_obs);
-            E.mp_bad = slamit_inout(b, io, X->mp_bad, (size_t)n_mp); E.mp_nobs = slamit_inout(b, io, X->mp_nobs, (size_t)n_mp);
-            E.mp_found = slamit_inout(b, io, X->mp_found, (size_t)n_mp); E.mp_visible = slamit_inout(b, io, X->mp_visible, (size_t)n_mp);
-            E.mp_replaced = slamit_inout(b, io, X->mp_replaced, (size_t)n_mp); E.kf_mp = slamit_inout(b, io, X->kf_mp, n_kfmp);
-            E.obs_ptr_out = slamit_inout(b, io, X->obs_ptr_out, (size_t)n_mp + 1);
-            E.obs_kf_out = slamit_inout(b, io, X->obs_kf_out, cap_out); E.obs_idx_out = slamit_inout(b, io, X->obs_idx_out, cap_out);
-            E.obs_octave_out = slamit_inout(b, io, X->obs_octave_out, cap_out); E.obs_weight_out = slamit_inout(b, io, X->obs_weight_out, cap_out);
-            E.obs_cap_out = X->obs_cap_out;
+            map_stage_tables(b, io, map, X, Q.maps[0], Q.X[0]);
             int32_t* h1;
             Q.n = b.in_fill<int32_t>(1, &h1);
             if (h1) h1[0] = n;
@@ -565,16 +387,7 @@ int slamit_map_fuse_batch_dev(int device, const slamit_map_fuse_batch_rec* R, vo
     if (R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->maps || !R->index) return slamit_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
     if (R->cap > SLAMIT_FUSE_MAX_OPS) return slamit_refuse(where, "cap above SLAMIT_FUSE_MAX_OPS", SLAMIT_ERR_CAPACITY);
     if (R->mp_cap == 0x7fffffff) return slamit_refuse(where, "mp_cap above 2^31 - 2", SLAMIT_ERR_CAPACITY);
-    for (int m = 0; m < R->n_maps; ++m) {
-        const slamit_map_index& M = R->maps[m];
-        const slamit_replace_index& X = R->index[m];
-        if (const char* bad = map_batch_sizes_error(&M)) return slamit_refuse(where, bad);
-        if (M.n_mp > R->mp_cap) return slamit_refuse(where, "a map with n_mp above mp_cap");
-        if (X.obs_cap_out < 0) return slamit_refuse(where, "negative obs_cap_out");
-        if (!M.obs_ptr || !M.obs_kf || !M.kf_mp_ptr || !X.obs_idx || !X.obs_octave || !X.obs_weight || !X.mp_bad || !X.mp_nobs || !X.mp_found || !X.mp_visible ||
-            !X.mp_replaced || !X.kf_mp || !X.obs_ptr_out || !X.obs_kf_out || !X.obs_idx_out || !X.obs_octave_out || !X.obs_weight_out)
-            return slamit_refuse(where, "null table");
-    }
+    if (const char* bad = map_replace_batch_error(R->n_maps, R->mp_cap, R->maps, R->index)) return slamit_refuse(where, bad);
     if (!R->d_n || !R->d_n_touched || !R->d_n_fused || !R->d_n_obs_out || !R->d_status || (R->cap && (!R->d_ops || !R->d_outcome || !R->d_moved || !R->d_erased)) ||
         (R->mp_cap && !R->d_touched))
         return slamit_refuse(where, "null array");

@@ -18,10 +18,11 @@
 //                    op shows nowhere.  __syncthreads_or ends the round and says whether any op is left; the first op not done is always
 //                    ready, so at most n rounds.  Data crosses rounds only inside the workgroup.  LDS: 16 x (2,048 + 1,024) = 49,152 bytes.
 // mr_commit_kernel   a wavefront per involved point: the working row at its new offset, the five columns in place.
-// mr_copy_kernel     the rows of the other points, 64 points to a wavefront as me_copy_kernel does; the new pointer array, touched,
-//                    the counts and the call's status.
+// mr_copy_kernel     the rows of the other points, 64 points to a wavefront; the new pointer array, touched, the counts and the
+//                    call's status.
 // mr_kfmp_kernel     the winners of the kf_mp words into kf_mp; moved / erased.
 // THE GATE: every kernel that writes a caller's array first reads the two overflow words and the table's need from device memory.
+// The working rows, the world over them, the scan bodies and the row copy are map_rows_dev.h's, shared with map_fuse.hip.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -35,6 +36,7 @@
 #include "wave_ops.h"
 #include "map_check.h"
 #include "map_replace.h"
+#include "map_rows_dev.h"
 
 static_assert(sizeof(MrOp) == sizeof(slamit_map_replace) && sizeof(MrOp) == 20 && offsetof(MrOp, a) == offsetof(slamit_map_replace, a) &&
                   offsetof(MrOp, idx) == offsetof(slamit_map_replace, idx) && offsetof(MrOp, octave) == offsetof(slamit_map_replace, octave) &&
@@ -54,79 +56,48 @@ static_assert(MR_MAX_PER_POINT == 64 && MR_SCAN_BLOCK == 256 && MR_MAX_OBS <= 65
 
 #define MR_NT 256
 #define MR_ROUND_NT 1024
-enum { MR_F_OP_BAD = 0, MR_F_OBS_BAD = 1, MR_F_OP_OVER = 2, MR_F_OBS_OVER = 3, MR_NFLAGS = 8 };
-enum { MR_C_LEN = 0, MR_C_BAD, MR_C_NOBS, MR_C_FOUND, MR_C_VISIBLE, MR_C_REPLACED, MR_C_RECEIVED, MR_NCOLS };
 
-// The batch as the kernels' argument.  The workspace rows of a map lie S = mp_cap + 1 apart; an involved point has a compact number
-// below ninv = min(2 cap, mp_cap) and a working row of MR_MAX_OBS entries.
+// The batch as the kernels' argument: W the workspace rows of map_rows_dev.h (cnt: the ops naming the point), then this module's own.
 struct MrBatch {
     int32_t n_maps, cap, mp_cap, kfmp_cap;
     LmMap maps[SLAMIT_LOCAL_MAP_MAX_MAPS];
     MrIndex X[SLAMIT_LOCAL_MAP_MAX_MAPS];
     const MrOp* ops; const int32_t* n;
     int32_t* moved; int32_t* erased; int32_t* touched; int32_t* n_touched; int32_t* n_obs_out; int32_t* status;
+    MapRows W;
     unsigned long long* kfw;   // [n_maps][kfmp_cap]      cleared
-    int32_t* flags;            // [n_maps][MR_NFLAGS]     cleared
-    int32_t* cnt;              // [n_maps][S]             cleared: ops naming the point
     int32_t* cursor;           // [n_maps][S]             cleared
     int32_t* bstart;           // [n_maps][S]             the buckets' first entries
-    int32_t* cidx;             // [n_maps][S]             the compact number of an involved point, their count at [n_mp]
-    int32_t* newptr;           // [n_maps][S]             the new pointer array, the table's need at [n_mp]
-    int32_t* tpos;             // [n_maps][S]
-    int32_t* parts;            // [n_maps][2][nparts + 1]
     int32_t* bucket;           // [n_maps][2 cap]         list indices by point
     int32_t* pred;             // [n_maps][2][cap]        the predecessor on a's side, on b's side, -1 for none
     int32_t* done;             // [n_maps][cap]           0, or 1 + the round the op finished in
     int32_t* mv;               // [n_maps][cap]
     int32_t* er;               // [n_maps][cap]
-    int32_t* inv;              // [n_maps][ninv]          the slot of a compact number
-    int32_t* wcol;             // [n_maps][MR_NCOLS][ninv]
-    int32_t* wkf;              // [n_maps][ninv][MR_MAX_OBS]
-    int32_t* widx;
-    uint8_t* woct;
-    uint8_t* wwgt;
-    int32_t nparts, ninv;
 };
 
 static size_t mr_ws_layout(int n_maps, int cap, int mp_cap, int kfmp_cap, unsigned char* base, MrBatch* B, size_t* clear_bytes) {
-    const size_t S = (size_t)mp_cap + 1, nm = (size_t)n_maps, nparts = (S + MR_SCAN_BLOCK - 1) / MR_SCAN_BLOCK, c = (size_t)cap;
-    const size_t ninv = std::min(2 * c, (size_t)mp_cap), rows = nm * ninv * MR_MAX_OBS;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 15) & ~(size_t)15; return base ? base + at : nullptr; };
-    unsigned char* const kfw = take(8 * nm * (size_t)kfmp_cap);
-    unsigned char* const flags = take(4 * nm * MR_NFLAGS);
-    unsigned char* const cnt = take(4 * nm * S);
-    unsigned char* const cursor = take(4 * nm * S);
-    if (clear_bytes) *clear_bytes = off;
-    unsigned char* const bstart = take(4 * nm * S);
-    unsigned char* const cidx = take(4 * nm * S);
-    unsigned char* const newptr = take(4 * nm * S);
-    unsigned char* const tpos = take(4 * nm * S);
-    unsigned char* const parts = take(4 * nm * 2 * (nparts + 1));
-    unsigned char* const bucket = take(4 * nm * 2 * c);
-    unsigned char* const pred = take(4 * nm * 2 * c);
-    unsigned char* const done = take(4 * nm * c);
-    unsigned char* const mv = take(4 * nm * c);
-    unsigned char* const er = take(4 * nm * c);
-    unsigned char* const inv = take(4 * nm * ninv);
-    unsigned char* const wcol = take(4 * nm * MR_NCOLS * ninv);
-    unsigned char* const wkf = take(4 * rows);
-    unsigned char* const widx = take(4 * rows);
-    unsigned char* const woct = take(rows);
-    unsigned char* const wwgt = take(rows);
-    if (B) {
-        B->kfw = (unsigned long long*)kfw; B->flags = (int32_t*)flags; B->cnt = (int32_t*)cnt; B->cursor = (int32_t*)cursor; B->bstart = (int32_t*)bstart;
-        B->cidx = (int32_t*)cidx; B->newptr = (int32_t*)newptr; B->tpos = (int32_t*)tpos; B->parts = (int32_t*)parts; B->bucket = (int32_t*)bucket;
-        B->pred = (int32_t*)pred; B->done = (int32_t*)done; B->mv = (int32_t*)mv; B->er = (int32_t*)er; B->inv = (int32_t*)inv; B->wcol = (int32_t*)wcol;
-        B->wkf = (int32_t*)wkf; B->widx = (int32_t*)widx; B->woct = woct; B->wwgt = wwgt; B->nparts = (int32_t)nparts; B->ninv = (int32_t)ninv;
-    }
-    return off;
+    MapRowsLayout L(n_maps, cap, mp_cap, base);
+    const size_t nm = L.nm, S = L.S, c = L.c;
+    unsigned long long* const kfw = L.take<unsigned long long>(nm * (size_t)kfmp_cap);
+    L.cleared();
+    int32_t* const cursor = L.take<int32_t>(nm * S);
+    if (clear_bytes) *clear_bytes = L.off;
+    int32_t* const bstart = L.take<int32_t>(nm * S);
+    L.scanned();
+    int32_t* const bucket = L.take<int32_t>(nm * 2 * c);
+    int32_t* const pred = L.take<int32_t>(nm * 2 * c);
+    int32_t* const done = L.take<int32_t>(nm * c);
+    int32_t* const mv = L.take<int32_t>(nm * c);
+    int32_t* const er = L.take<int32_t>(nm * c);
+    L.columns();
+    L.rows();
+    if (B) { B->W = L.W; B->kfw = kfw; B->cursor = cursor; B->bstart = bstart; B->bucket = bucket; B->pred = pred; B->done = done; B->mv = mv; B->er = er; }
+    return L.off;
 }
 
-__device__ __forceinline__ int32_t* mr_col(const MrBatch& B, int m, int col) { return B.wcol + ((size_t)m * MR_NCOLS + col) * (size_t)B.ninv; }
 __device__ __forceinline__ bool mr_gate(const MrBatch& B, int m) {
-    const int32_t* const f = B.flags + MR_NFLAGS * m;
-    return f[MR_F_OP_OVER] != 0 || f[MR_F_OBS_OVER] != 0 || B.newptr[(size_t)m * (B.mp_cap + 1) + B.maps[m].n_mp] > B.X[m].obs_cap_out;
+    const int32_t* const f = B.W.flags + MR_NFLAGS * m;
+    return f[MR_F_OP_OVER] != 0 || f[MR_F_OBS_OVER] != 0 || B.W.newptr[(size_t)m * (B.mp_cap + 1) + B.maps[m].n_mp] > B.X[m].obs_cap_out;
 }
 
 // ---- grid (ceil(cap / 256), maps) ---------------------------------------------------------------------------------------------
@@ -137,11 +108,11 @@ __global__ __launch_bounds__(MR_NT) void mr_hist_kernel(MrBatch B) {
     const size_t S = (size_t)B.mp_cap + 1, c = (size_t)B.cap;
     const MrOp e = B.ops[m * c + i];
     int d = 1;                                                          // an op that does nothing is done
-    if (!mr_op_ok(M, e)) atomicOr(&B.flags[MR_NFLAGS * m + MR_F_OP_BAD], 1);
+    if (!mr_op_ok(M, e)) atomicOr(&B.W.flags[MR_NFLAGS * m + MR_F_OP_BAD], 1);
     else if (mr_op_acts(e)) {
         d = 0;
-        atomicAdd(&B.cnt[m * S + e.a], 1);
-        if (e.kind == MR_REPLACE) atomicAdd(&B.cnt[m * S + e.b], 1);
+        atomicAdd(&B.W.cnt[m * S + e.a], 1);
+        if (e.kind == MR_REPLACE) atomicAdd(&B.W.cnt[m * S + e.b], 1);
     }
     B.done[m * c + i] = d; B.mv[m * c + i] = 0; B.er[m * c + i] = 0;
     B.pred[(m * 2 + 0) * c + i] = -1; B.pred[(m * 2 + 1) * c + i] = -1;
@@ -152,34 +123,22 @@ __global__ __launch_bounds__(MR_NT) void mr_hist_kernel(MrBatch B) {
 // array 1 whether p received an observation.
 __device__ __forceinline__ int mr_scan_src(const MrBatch& B, int m, int mode, int z, int p) {
     const size_t S = (size_t)B.mp_cap + 1;
-    const int c = B.cnt[m * S + p];
+    const int c = B.W.cnt[m * S + p];
     if (mode == 0) return z ? (c > 0) : c;
     if (c == 0) return z ? 0 : B.maps[m].obs_ptr[p + 1] - B.maps[m].obs_ptr[p];
-    const int ci = B.cidx[m * S + p];                                  // < ninv: the involved points are counted there
-    return mr_col(B, m, z ? MR_C_RECEIVED : MR_C_LEN)[ci];
+    const int ci = B.W.cidx[m * S + p];                                // < ninv: the involved points are counted there
+    return map_rows_col(B.W, m, z ? MR_C_RECEIVED : MR_C_LEN)[ci];
 }
-// grid (nparts, maps, 2): the sum of block x of array z over the first n_mp entries
+// the three kernels over map_rows_dev.h's bodies.  grid (nparts, maps, 2), (maps, 2), (nparts, maps, 2)
 __global__ __launch_bounds__(MR_NT) void mr_scan_sum_kernel(MrBatch B, int mode) {
-    const int m = blockIdx.y, i = blockIdx.x * MR_NT + (int)threadIdx.x;
-    int total;
-    block_inclusive_scan_i32<MR_NT>(i < B.maps[m].n_mp ? mr_scan_src(B, m, mode, blockIdx.z, i) : 0, total);
-    if (threadIdx.x == 0) B.parts[((size_t)m * 2 + blockIdx.z) * (B.nparts + 1) + blockIdx.x] = total;
+    const int m = blockIdx.y;
+    map_scan_sum<MR_NT>(B.W.parts, B.W.nparts, B.maps[m].n_mp, [&](int z, int p) { return mr_scan_src(B, m, mode, z, p); });
 }
-// grid (maps, 2): the sums scanned in place by one workgroup, the total at [nparts]
-__global__ __launch_bounds__(MR_NT) void mr_scan_parts_kernel(MrBatch B) {
-    block_scan_parts_i32<MR_NT>(B.parts + ((size_t)blockIdx.x * 2 + blockIdx.y) * (B.nparts + 1), B.nparts);
-}
-// grid (nparts, maps, 2): out[i] = what lies before entry i, out[n_mp] = the total
+__global__ __launch_bounds__(MR_NT) void mr_scan_parts_kernel(MrBatch B) { map_scan_parts<MR_NT>(B.W.parts, B.W.nparts); }
 __global__ __launch_bounds__(MR_NT) void mr_scan_add_kernel(MrBatch B, int mode) {
-    const int m = blockIdx.y, i = blockIdx.x * MR_NT + (int)threadIdx.x, n = B.maps[m].n_mp;
-    const size_t S = (size_t)B.mp_cap + 1;
-    int32_t* const out = (mode == 0 ? (blockIdx.z ? B.cidx : B.bstart) : (blockIdx.z ? B.tpos : B.newptr)) + m * S;
-    const int32_t* const parts = B.parts + ((size_t)m * 2 + blockIdx.z) * (B.nparts + 1);
-    const int v = i < n ? mr_scan_src(B, m, mode, blockIdx.z, i) : 0;
-    int total;
-    const int incl = block_inclusive_scan_i32<MR_NT>(v, total);
-    if (i < n) out[i] = parts[blockIdx.x] + incl - v;
-    else if (i == n) out[i] = parts[B.nparts];                          // n <= mp_cap: inside the row
+    const int m = blockIdx.y;
+    int32_t* const out = (mode == 0 ? (blockIdx.z ? B.W.cidx : B.bstart) : (blockIdx.z ? B.W.tpos : B.W.newptr)) + m * ((size_t)B.mp_cap + 1);
+    map_scan_add<MR_NT>(B.W.parts, B.W.nparts, B.maps[m].n_mp, [&](int z, int p) { return mr_scan_src(B, m, mode, z, p); }, out);   // n_mp <= mp_cap: inside the row
 }
 
 // ---- grid (ceil(max(cap, mp_cap) / 256), maps) ----------------------------------------------------------------------------------
@@ -196,7 +155,7 @@ __global__ __launch_bounds__(MR_NT) void mr_scatter_kernel(MrBatch B) {
             B.bucket[m * 2 * c + at] = i;
         }
     }
-    if (i < M.n_mp && B.cnt[m * S + i] > 0) B.inv[(size_t)m * B.ninv + B.cidx[m * S + i]] = i;   // cidx < the involved points <= ninv
+    if (i < M.n_mp && B.W.cnt[m * S + i] > 0) B.W.inv[(size_t)m * B.W.ninv + B.W.cidx[m * S + i]] = i;   // cidx < the involved points <= ninv
 }
 
 // ---- grid (ceil(ninv / 4), maps), 256 threads: a wavefront per involved point --------------------------------------------------
@@ -206,11 +165,11 @@ __global__ __launch_bounds__(MR_NT) void mr_prep_kernel(MrBatch B) {
     const LmMap& M = B.maps[m];
     const MrIndex& X = B.X[m];
     const size_t S = (size_t)B.mp_cap + 1, c = (size_t)B.cap;
-    if (ci >= B.cidx[m * S + M.n_mp]) return;                           // the whole wavefront, here and below
-    const int p = __builtin_amdgcn_readfirstlane(B.inv[(size_t)m * B.ninv + ci]);
-    const int ne = __builtin_amdgcn_readfirstlane(B.cnt[m * S + p]);
+    if (ci >= B.W.cidx[m * S + M.n_mp]) return;                         // the whole wavefront, here and below
+    const int p = __builtin_amdgcn_readfirstlane(B.W.inv[(size_t)m * B.W.ninv + ci]);
+    const int ne = __builtin_amdgcn_readfirstlane(B.W.cnt[m * S + p]);
     if (ne > MR_MAX_PER_POINT) {
-        if (lane == 0) atomicOr(&B.flags[MR_NFLAGS * m + MR_F_OP_OVER], 1);
+        if (lane == 0) atomicOr(&B.W.flags[MR_NFLAGS * m + MR_F_OP_OVER], 1);
         return;
     }
     const int b0 = B.bstart[m * S + p];
@@ -224,24 +183,10 @@ __global__ __launch_bounds__(MR_NT) void mr_prep_kernel(MrBatch B) {
         const int side = e.kind == MR_REPLACE && e.b == p;              // a != b in a bucketed REPLACE
         B.pred[(m * 2 + side) * c + li] = prev;
     }
-    const int o0 = __builtin_amdgcn_readfirstlane(M.obs_ptr[p]);
-    int len0 = __builtin_amdgcn_readfirstlane(M.obs_ptr[p + 1]) - o0;
-    if (len0 > MR_MAX_OBS || len0 < 0) {
-        if (lane == 0) atomicOr(&B.flags[MR_NFLAGS * m + MR_F_OBS_OVER], 1);
-        len0 = 0;
-    }
-    const size_t r0 = ((size_t)m * B.ninv + ci) * MR_MAX_OBS;
-    for (int e = lane; e < len0; e += 64) {
-        B.wkf[r0 + e] = M.obs_kf[o0 + e]; B.widx[r0 + e] = X.obs_idx[o0 + e]; B.woct[r0 + e] = X.obs_octave[o0 + e]; B.wwgt[r0 + e] = X.obs_weight[o0 + e];
-    }
-    if (lane == 0) {
-        mr_col(B, m, MR_C_LEN)[ci] = len0; mr_col(B, m, MR_C_BAD)[ci] = X.mp_bad[p]; mr_col(B, m, MR_C_NOBS)[ci] = X.mp_nobs[p];
-        mr_col(B, m, MR_C_FOUND)[ci] = X.mp_found[p]; mr_col(B, m, MR_C_VISIBLE)[ci] = X.mp_visible[p]; mr_col(B, m, MR_C_REPLACED)[ci] = X.mp_replaced[p];
-        mr_col(B, m, MR_C_RECEIVED)[ci] = 0;
-    }
+    map_row_load(B.W, m, M, X, ci, p, lane);
 }
 
-// ---- the world of mr_walk_op on the device: one wavefront, the rows in the workspace ------------------------------------------
+// ---- the kf_mp writes of the world (MapWorldDev of map_rows_dev.h): ops of one round run at once, so the largest list index wins -
 struct MrEmitDev {
     const LmMap* M; unsigned long long* kfw; int32_t* flags;
     int kfmp_cap, lane;
@@ -254,81 +199,6 @@ struct MrEmitDev {
         if (lane == 0) mine(k, i, value, li);
     }
 };
-struct MrWorldDev {
-    const int32_t* cidx; int32_t* flags;
-    int32_t* col[MR_NCOLS];
-    int32_t* wkf; int32_t* widx; uint8_t* woct; uint8_t* wwgt;          // the map's working rows
-    int32_t* skf; uint16_t* sord;                                       // this wavefront's LDS: S's keyframes, S's entries by rank
-    int lane;
-    __device__ __forceinline__ int len_of(int ci) const { return __builtin_amdgcn_readfirstlane(col[MR_C_LEN][ci]); }
-    __device__ __forceinline__ bool holds(int p, int k) const {
-        const int ci = cidx[p], len = len_of(ci);
-        const size_t r0 = (size_t)ci * MR_MAX_OBS;
-        for (int e0 = 0; e0 < len; e0 += 64)
-            if (__ballot(e0 + lane < len && wkf[r0 + e0 + lane] == k)) return true;
-        return false;
-    }
-    __device__ __forceinline__ int push(int p, int k, int i, uint8_t o, uint8_t wt) {
-        const int ci = cidx[p], len = len_of(ci);
-        if (len >= MR_MAX_OBS) {
-            if (lane == 0) atomicOr(&flags[MR_F_OBS_OVER], 1);
-            return 0;
-        }
-        if (lane == 0) {
-            const size_t at = (size_t)ci * MR_MAX_OBS + len;
-            wkf[at] = k; widx[at] = i; woct[at] = o; wwgt[at] = wt;
-            col[MR_C_LEN][ci] = len + 1; col[MR_C_NOBS][ci] += wt; col[MR_C_RECEIVED][ci] = 1;
-        }
-        return 1;
-    }
-    template <class Emit>
-    __device__ __forceinline__ void fuse(int S, int D, Emit& emit, int li, int& moved, int& erased) {
-        const int cs = cidx[S], cd = cidx[D], len_s = len_of(cs), len_d = len_of(cd);
-        const size_t rs = (size_t)cs * MR_MAX_OBS, rd = (size_t)cd * MR_MAX_OBS;
-        wave_mem_sync();                                                 // the LDS of the op before
-        for (int e = lane; e < len_s; e += 64) skf[e] = wkf[rs + e];
-        wave_mem_sync();
-        for (int e = lane; e < len_s; e += 64) {                        // ascending slot, row order among equals
-            const uint32_t key = (uint32_t)skf[e];
-            int rank = 0;
-            for (int f = 0; f < len_s; ++f) { const uint32_t o = (uint32_t)skf[f]; rank += (o < key) || (o == key && f < e); }
-            sord[rank] = (uint16_t)e;
-        }
-        wave_mem_sync();
-        int n_moved = 0, add = 0, over = 0;
-        for (int j0 = 0; j0 < len_s; j0 += 64) {
-            const int j = j0 + lane;
-            const bool act = j < len_s;
-            const int e = act ? sord[j] : 0, k = act ? skf[e] : 0;
-            bool go = act && (j == 0 || skf[sord[j - 1]] != k);         // the first of a run of one keyframe decides
-            if (go)
-                for (int f = 0; f < len_d; ++f) go = go && wkf[rd + f] != k;     // D's row as the op met it: the received keyframes are S's own
-            const int i = act ? widx[rs + e] : 0, wt = act ? wwgt[rs + e] : 0;
-            const unsigned long long mask = __ballot(go);
-            if (go) {
-                const int at = len_d + n_moved + __popcll(mask & ((1ull << lane) - 1ull));
-                if (at >= MR_MAX_OBS) over = 1;
-                else { wkf[rd + at] = k; widx[rd + at] = i; woct[rd + at] = woct[rs + e]; wwgt[rd + at] = (uint8_t)wt; }
-            }
-            if (act) emit.mine(k, i, go ? D : -1, li);
-            add += __builtin_amdgcn_readlane(wave_inclusive_scan_i32(go ? wt : 0), 63);
-            n_moved += __popcll(mask);
-        }
-        if (__ballot(over != 0)) {
-            if (lane == 0) atomicOr(&flags[MR_F_OBS_OVER], 1);
-            n_moved = MR_MAX_OBS - len_d;
-        }
-        if (lane == 0 && n_moved > 0) { col[MR_C_LEN][cd] = len_d + n_moved; col[MR_C_NOBS][cd] += add; col[MR_C_RECEIVED][cd] = 1; }
-        moved = n_moved; erased = len_s - n_moved;
-    }
-    __device__ __forceinline__ void retire(int S, int D) {
-        if (lane != 0) return;
-        const int cs = cidx[S], cd = cidx[D];
-        col[MR_C_LEN][cs] = 0; col[MR_C_BAD][cs] = 1; col[MR_C_REPLACED][cs] = D;
-        col[MR_C_FOUND][cd] = (int32_t)((uint32_t)col[MR_C_FOUND][cd] + (uint32_t)col[MR_C_FOUND][cs]);
-        col[MR_C_VISIBLE][cd] = (int32_t)((uint32_t)col[MR_C_VISIBLE][cd] + (uint32_t)col[MR_C_VISIBLE][cs]);
-    }
-};
 
 // ---- grid (maps), 1024 threads --------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MR_ROUND_NT) void mr_round_kernel(MrBatch B) {
@@ -337,16 +207,15 @@ __global__ __launch_bounds__(MR_ROUND_NT) void mr_round_kernel(MrBatch B) {
     const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const LmMap& M = B.maps[m];
     const size_t S = (size_t)B.mp_cap + 1, c = (size_t)B.cap;
-    int32_t* const flags = B.flags + MR_NFLAGS * m;
+    int32_t* const flags = B.W.flags + MR_NFLAGS * m;
     if (flags[MR_F_OP_OVER]) return;                                    // a bucket above a wavefront: no predecessors were made
     const int n = lm_list_n(B.n[m], B.cap);
     const MrOp* const ops = B.ops + m * c;
     int32_t* const done = B.done + m * c;
     const int32_t* const pred_a = B.pred + (m * 2 + 0) * c;
     const int32_t* const pred_b = B.pred + (m * 2 + 1) * c;
-    const size_t r0 = (size_t)m * B.ninv * MR_MAX_OBS;
-    MrWorldDev world = {B.cidx + m * S, flags, {}, B.wkf + r0, B.widx + r0, B.woct + r0, B.wwgt + r0, skf[w], sord[w], lane};
-    for (int q = 0; q < MR_NCOLS; ++q) world.col[q] = mr_col(B, m, q);
+    MapWorldDev world;
+    world.bind(B.W, m, S, skf[w], sord[w], lane);
     MrEmitDev emit = {&M, B.kfw + (size_t)m * B.kfmp_cap, flags, B.kfmp_cap, lane};
     for (int round = 0; round < n; ++round) {                           // the first op not done is ready: at most n rounds
         int pending = 0;
@@ -386,29 +255,18 @@ __global__ __launch_bounds__(MR_NT) void mr_commit_kernel(MrBatch B) {
     const MrIndex& X = B.X[m];
     const size_t S = (size_t)B.mp_cap + 1;
     if (mr_gate(B, m)) return;
-    if (ci >= B.cidx[m * S + M.n_mp]) return;
-    const int p = B.inv[(size_t)m * B.ninv + ci];
-    const int len = mr_col(B, m, MR_C_LEN)[ci], d0 = B.newptr[m * S + p];   // d0 + len <= the need <= obs_cap_out
-    const size_t r0 = ((size_t)m * B.ninv + ci) * MR_MAX_OBS;
-    for (int e = lane; e < len; e += 64) {
-        X.obs_kf_out[d0 + e] = B.wkf[r0 + e]; X.obs_idx_out[d0 + e] = B.widx[r0 + e]; X.obs_octave_out[d0 + e] = B.woct[r0 + e]; X.obs_weight_out[d0 + e] = B.wwgt[r0 + e];
-    }
-    if (lane == 0) {
-        X.mp_bad[p] = (uint8_t)mr_col(B, m, MR_C_BAD)[ci]; X.mp_nobs[p] = mr_col(B, m, MR_C_NOBS)[ci]; X.mp_found[p] = mr_col(B, m, MR_C_FOUND)[ci];
-        X.mp_visible[p] = mr_col(B, m, MR_C_VISIBLE)[ci]; X.mp_replaced[p] = mr_col(B, m, MR_C_REPLACED)[ci];
-    }
+    if (ci >= B.W.cidx[m * S + M.n_mp]) return;
+    map_row_commit(B.W, m, S, X, ci, lane);
 }
 
 // ---- grid (ceil((mp_cap + 1) / 256), maps) ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MR_NT) void mr_copy_kernel(MrBatch B) {
-    __shared__ int32_t optr[MR_NT / 64][65], nptr[MR_NT / 64][65];
-    __shared__ uint8_t skip[MR_NT / 64][64];
-    const int m = blockIdx.y, p = blockIdx.x * MR_NT + (int)threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int m = blockIdx.y, p = blockIdx.x * MR_NT + (int)threadIdx.x;
     const LmMap& M = B.maps[m];
     const MrIndex& X = B.X[m];
     const size_t S = (size_t)B.mp_cap + 1;
-    const int32_t* const newptr = B.newptr + m * S;
-    const int32_t* const flags = B.flags + MR_NFLAGS * m;
+    const int32_t* const newptr = B.W.newptr + m * S;
+    const int32_t* const flags = B.W.flags + MR_NFLAGS * m;
     const int n_mp = M.n_mp, need = newptr[n_mp];
     const bool op_over = flags[MR_F_OP_OVER] != 0, obs_over = flags[MR_F_OBS_OVER] != 0, table_over = !op_over && !obs_over && need > X.obs_cap_out;
     bool committed;
@@ -419,29 +277,14 @@ __global__ __launch_bounds__(MR_NT) void mr_copy_kernel(MrBatch B) {
     }
     if (!committed) return;
     if (p <= n_mp) X.obs_ptr_out[p] = newptr[p];
-    if (p == n_mp) B.n_touched[m] = B.tpos[m * S + n_mp];
+    if (p == n_mp) B.n_touched[m] = B.W.tpos[m * S + n_mp];
     bool sk = true;
     if (p < n_mp) {
-        sk = B.cnt[m * S + p] > 0;                                      // mr_commit_kernel writes that row
-        if (sk && mr_scan_src(B, m, 1, 1, p)) B.touched[(size_t)m * B.mp_cap + B.tpos[m * S + p]] = p;   // tpos < the receivers before p <= p
+        sk = B.W.cnt[m * S + p] > 0;                                    // mr_commit_kernel writes that row
+        if (sk && mr_scan_src(B, m, 1, 1, p)) B.touched[(size_t)m * B.mp_cap + B.W.tpos[m * S + p]] = p;   // tpos < the receivers before p <= p
     }
-    const int p0 = blockIdx.x * MR_NT + w * 64;
-    if (p0 >= n_mp) return;                                             // the whole wavefront
-    optr[w][lane] = M.obs_ptr[min(p0 + lane, n_mp)]; nptr[w][lane] = newptr[min(p0 + lane, n_mp)];
-    if (lane == 63) { optr[w][64] = M.obs_ptr[min(p0 + 64, n_mp)]; nptr[w][64] = newptr[min(p0 + 64, n_mp)]; }
-    skip[w][lane] = sk;
-    wave_mem_sync();
-    const int e1 = optr[w][64];
-    for (int e = optr[w][0] + lane; e < e1; e += 64) {
-        int lo = 0, hi = 63;                                            // the row q with optr[q] <= e < optr[q + 1]
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (optr[w][mid + 1] > e) hi = mid; else lo = mid + 1;
-        }
-        if (skip[w][lo]) continue;
-        const int at = nptr[w][lo] + (e - optr[w][lo]);                 // an unchanged row: inside the new table
-        X.obs_kf_out[at] = M.obs_kf[e]; X.obs_idx_out[at] = X.obs_idx[e]; X.obs_octave_out[at] = X.obs_octave[e]; X.obs_weight_out[at] = X.obs_weight[e];
-    }
+    map_copy_unnamed_rows<MR_NT>(p & ~63, sk, M.obs_ptr, newptr, n_mp, M.obs_kf, X.obs_idx, X.obs_octave, X.obs_weight, X.obs_kf_out, X.obs_idx_out,
+                                 X.obs_octave_out, X.obs_weight_out);
 }
 
 // ---- grid (ceil(max(kfmp_cap, cap) / 256), maps) --------------------------------------------------------------------------------
@@ -460,19 +303,19 @@ __global__ __launch_bounds__(MR_NT) void mr_kfmp_kernel(MrBatch B) {
 static hipError_t mr_launch(const MrBatch& B, size_t clear_bytes, hipStream_t st) {
     hipError_t e = hipMemsetAsync(B.kfw, 0, clear_bytes, st);            // kfw is the workspace's first byte
     if (e != hipSuccess) return e;
-    const unsigned nm = (unsigned)B.n_maps, nparts = (unsigned)B.nparts;
+    const unsigned nm = (unsigned)B.n_maps, nparts = (unsigned)B.W.nparts;
     const auto blocks = [](int n, int per) { return (unsigned)std::max(1, (n + per - 1) / per); };
     hipLaunchKernelGGL(mr_hist_kernel, dim3(blocks(B.cap, MR_NT), nm), dim3(MR_NT), 0, st, B);
     hipLaunchKernelGGL(mr_scan_sum_kernel, dim3(nparts, nm, 2), dim3(MR_NT), 0, st, B, 0);
     hipLaunchKernelGGL(mr_scan_parts_kernel, dim3(nm, 2), dim3(MR_NT), 0, st, B);
     hipLaunchKernelGGL(mr_scan_add_kernel, dim3(nparts, nm, 2), dim3(MR_NT), 0, st, B, 0);
     hipLaunchKernelGGL(mr_scatter_kernel, dim3(blocks(std::max(B.cap, B.mp_cap), MR_NT), nm), dim3(MR_NT), 0, st, B);
-    if (B.ninv > 0) hipLaunchKernelGGL(mr_prep_kernel, dim3(blocks(B.ninv, MR_NT / 64), nm), dim3(MR_NT), 0, st, B);
+    if (B.W.ninv > 0) hipLaunchKernelGGL(mr_prep_kernel, dim3(blocks(B.W.ninv, MR_NT / 64), nm), dim3(MR_NT), 0, st, B);
     if (B.cap > 0) hipLaunchKernelGGL(mr_round_kernel, dim3(nm), dim3(MR_ROUND_NT), 0, st, B);
     hipLaunchKernelGGL(mr_scan_sum_kernel, dim3(nparts, nm, 2), dim3(MR_NT), 0, st, B, 1);
     hipLaunchKernelGGL(mr_scan_parts_kernel, dim3(nm, 2), dim3(MR_NT), 0, st, B);
     hipLaunchKernelGGL(mr_scan_add_kernel, dim3(nparts, nm, 2), dim3(MR_NT), 0, st, B, 1);
-    if (B.ninv > 0) hipLaunchKernelGGL(mr_commit_kernel, dim3(blocks(B.ninv, MR_NT / 64), nm), dim3(MR_NT), 0, st, B);
+    if (B.W.ninv > 0) hipLaunchKernelGGL(mr_commit_kernel, dim3(blocks(B.W.ninv, MR_NT / 64), nm), dim3(MR_NT), 0, st, B);
     hipLaunchKernelGGL(mr_copy_kernel, dim3(nparts, nm), dim3(MR_NT), 0, st, B);
     if (std::max(B.kfmp_cap, B.cap) > 0) hipLaunchKernelGGL(mr_kfmp_kernel, dim3(blocks(std::max(B.kfmp_cap, B.cap), MR_NT), nm), dim3(MR_NT), 0, st, B);
     return hipGetLastError();
@@ -506,19 +349,9 @@ int slamit_map_replace_apply(int device, const slamit_map_index* map, const slam
     const char* const where = "slamit_map_replace_apply";
     if (n < 0 || !n_touched || !n_obs_out || !status || (n && (!ops || !moved || !erased))) return slamit_refuse(where, "null array or negative n");
     if (n > SLAMIT_REPLACE_MAX_OPS) return slamit_refuse(where, "more than SLAMIT_REPLACE_MAX_OPS ops", SLAMIT_ERR_CAPACITY);
-    if (!map || !X) return slamit_refuse(where, "null table");
-    if (const char* bad = map_sizes_error(map)) return slamit_refuse(where, bad);
+    if (const char* bad = map_replace_tables_error(map, X, touched)) return slamit_refuse(where, bad);
     const int n_kf = map->n_kf, n_mp = map->n_mp;
-    if (n_mp && !touched) return slamit_refuse(where, "null array or negative n");
-    if (X->obs_cap_out < 0) return slamit_refuse(where, "negative obs_cap_out");
-    if (!map->obs_ptr || !map->kf_mp_ptr || !X->obs_ptr_out) return slamit_refuse(where, "null table");
-    if (!map_csr_ok(map->obs_ptr, n_mp) || !map_csr_ok(map->kf_mp_ptr, n_kf)) return slamit_refuse(where, "a CSR pointer array does not ascend from 0");
-    const size_t n_obs = (size_t)map->obs_ptr[n_mp], n_kfmp = (size_t)map->kf_mp_ptr[n_kf], cap_out = (size_t)X->obs_cap_out;
-    if ((n_obs && (!map->obs_kf || !X->obs_idx || !X->obs_octave || !X->obs_weight)) ||
-        (n_mp && (!X->mp_bad || !X->mp_nobs || !X->mp_found || !X->mp_visible || !X->mp_replaced)) || (n_kfmp && !X->kf_mp) ||
-        (cap_out && (!X->obs_kf_out || !X->obs_idx_out || !X->obs_octave_out || !X->obs_weight_out)))
-        return slamit_refuse(where, "null table");
-    if (const char* bad = map_obs_error(map, X->obs_idx, X->obs_weight)) return slamit_refuse(where, bad);
+    const size_t n_obs = (size_t)map->obs_ptr[n_mp], n_kfmp = (size_t)map->kf_mp_ptr[n_kf];
     for (int i = 0; i < n; ++i) {
         const slamit_map_replace& e = ops[i];
         if (e.kind != SLAMIT_REPLACE_REPLACE && e.kind != SLAMIT_REPLACE_ADD_OBS) return slamit_refuse(where, "an op's kind outside 1..2");
@@ -543,18 +376,7 @@ int slamit_map_replace_apply(int device, const slamit_map_index* map, const slam
         [&](StageBinder& b, int, MrBatch& Q) {
             io.clear();
             Q.n_maps = 1; Q.cap = n; Q.mp_cap = n_mp; Q.kfmp_cap = (int)n_kfmp;
-            LmMap& M = Q.maps[0];
-            M.n_kf = n_kf; M.n_mp = n_mp;
-            M.obs_ptr = b.in(map->obs_ptr, (size_t)n_mp + 1); M.obs_kf = b.in(map->obs_kf, n_obs); M.kf_mp_ptr = b.in(map->kf_mp_ptr, (size_t)n_kf + 1);
-            MrIndex& E = Q.X[0];
-            E.obs_idx = b.in(X->obs_idx, n_obs); E.obs_octave = b.in(X->obs_octave, n_obs); E.obs_weight = b.in(X->obs_weight, n_obs);
-            E.mp_bad = slamit_inout(b, io, X->mp_bad, (size_t)n_mp); E.mp_nobs = slamit_inout(b, io, X->mp_nobs, (size_t)n_mp);
-            E.mp_found = slamit_inout(b, io, X->mp_found, (size_t)n_mp); E.mp_visible = slamit_inout(b, io, X->mp_visible, (size_t)n_mp);
-            E.mp_replaced = slamit_inout(b, io, X->mp_replaced, (size_t)n_mp); E.kf_mp = slamit_inout(b, io, X->kf_mp, n_kfmp);
-            E.obs_ptr_out = slamit_inout(b, io, X->obs_ptr_out, (size_t)n_mp + 1);
-            E.obs_kf_out = slamit_inout(b, io, X->obs_kf_out, cap_out); E.obs_idx_out = slamit_inout(b, io, X->obs_idx_out, cap_out);
-            E.obs_octave_out = slamit_inout(b, io, X->obs_octave_out, cap_out); E.obs_weight_out = slamit_inout(b, io, X->obs_weight_out, cap_out);
-            E.obs_cap_out = X->obs_cap_out;
+            map_stage_tables(b, io, map, X, Q.maps[0], Q.X[0]);
             int32_t* h1;
             Q.n = b.in_fill<int32_t>(1, &h1);
             if (h1) h1[0] = n;
@@ -585,16 +407,7 @@ int slamit_map_replace_batch_dev(int device, const slamit_map_replace_batch_rec*
     if (R->n_maps > SLAMIT_LOCAL_MAP_MAX_MAPS || !R->maps || !R->index) return slamit_refuse(where, "n_maps outside [1, SLAMIT_LOCAL_MAP_MAX_MAPS] or no maps");
     if (R->cap > SLAMIT_REPLACE_MAX_OPS) return slamit_refuse(where, "cap above SLAMIT_REPLACE_MAX_OPS", SLAMIT_ERR_CAPACITY);
     if (R->mp_cap == 0x7fffffff) return slamit_refuse(where, "mp_cap above 2^31 - 2", SLAMIT_ERR_CAPACITY);
-    for (int m = 0; m < R->n_maps; ++m) {
-        const slamit_map_index& M = R->maps[m];
-        const slamit_replace_index& X = R->index[m];
-        if (const char* bad = map_batch_sizes_error(&M)) return slamit_refuse(where, bad);
-        if (M.n_mp > R->mp_cap) return slamit_refuse(where, "a map with n_mp above mp_cap");
-        if (X.obs_cap_out < 0) return slamit_refuse(where, "negative obs_cap_out");
-        if (!M.obs_ptr || !M.obs_kf || !M.kf_mp_ptr || !X.obs_idx || !X.obs_octave || !X.obs_weight || !X.mp_bad || !X.mp_nobs || !X.mp_found || !X.mp_visible ||
-            !X.mp_replaced || !X.kf_mp || !X.obs_ptr_out || !X.obs_kf_out || !X.obs_idx_out || !X.obs_octave_out || !X.obs_weight_out)
-            return slamit_refuse(where, "null table");
-    }
+    if (const char* bad = map_replace_batch_error(R->n_maps, R->mp_cap, R->maps, R->index)) return slamit_refuse(where, bad);
     if (!R->d_n || !R->d_n_touched || !R->d_n_obs_out || !R->d_status || (R->cap && (!R->d_ops || !R->d_moved || !R->d_erased)) || (R->mp_cap && !R->d_touched))
         return slamit_refuse(where, "null array");
     size_t clear_bytes = 0;
