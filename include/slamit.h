@@ -141,6 +141,9 @@ int slamit_orb_pyramid_view(const slamit_orb* h, slamit_pyramid_view* out);
  *  in the reference's (cell row, cell col, y, x) order. */
 int slamit_orb_debug_candidates(slamit_orb* h, int frame, int level, int32_t* xys, int cap,
                                 int* n_out);
+/*  how the octree pass of (frame, level) ran: bits 0-7 the passes it served from its path table, bit 8 (0x100) set when a pass
+ *  needed a depth the table does not hold (or no table fits) and the keys were walked instead.  0 for a level without candidates. */
+int slamit_orb_debug_octree_path(slamit_orb* h, int frame, int level, int* path_out);
 /*  the blurred level the descriptors were sampled from: GaussianBlur(mvImagePyramid[level].clone(), 7x7, sigma 2,
  *  BORDER_REFLECT_101) of src/ORBextractor.cc:1116-1117, *h_out rows of *w bytes (no border). dst may be NULL
  *  to query the size. */

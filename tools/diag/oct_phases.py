@@ -19,7 +19,9 @@ t0 = r[:, :, 7].min()
 print("realtime (100 MHz): first start 0, last start %.1f us, last end %.1f us" % ((r[:, :, 7].max() - t0) / 100.0, (r[:, :, 5].max() - t0) / 100.0))
 for lvl in (0, 7):
     print("level %d WG duration %.1f us (mean), start offset mean %.1f us" % (lvl, ((r[:, lvl, 5] - r[:, lvl, 7]) / 100.0).mean(), ((r[:, lvl, 7] - t0) / 100.0).mean()))
-names = ["roots", "childcnt sweep", "careful rank", "flags+scan+nodes", "relabel sweep", "best+out"]
+names = ["roots", "childcnt sweep", "careful rank", "flags+scan+nodes", "relabel sweep"]   # octree_body (slot 5 is the end time)
+if len(sys.argv) > 2 and sys.argv[2] == "table":   # octree_table_path: a workgroup that stays in the table writes these three
+    names = ["init+sweep", "node passes (wave 0)", "picks+out"]
 for lvl in range(8):
     x = r[:, lvl].astype(np.float64)
     print("level %d: keys %5.0f passes %4.1f nodes %4.0f  total %7.0f ticks | " % (

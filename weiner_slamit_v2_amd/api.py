@@ -567,7 +567,7 @@ _lib = None
 EXPORTS = [
     "slamit_orb_create", "slamit_orb_destroy", "slamit_orb_tables", "slamit_orb_max_keypoints",
     "slamit_orb_extract", "slamit_orb_extract_batch", "slamit_orb_extract_batch_dev", "slamit_orb_level",
-    "slamit_orb_debug_candidates", "slamit_orb_debug_blurred", "slamit_orb_profile", "slamit_hamming_best2", "slamit_hamming_best2_batch_dev",
+    "slamit_orb_debug_candidates", "slamit_orb_debug_octree_path", "slamit_orb_debug_blurred", "slamit_orb_profile", "slamit_hamming_best2", "slamit_hamming_best2_batch_dev",
     "slamit_hamming_matrix", "slamit_distinctive_batch", "slamit_guided_search", "slamit_guided_search_workspace", "slamit_guided_search_batch_dev", "slamit_guided_search_stereo", "slamit_guided_search_stereo_batch_dev", "slamit_bow_search", "slamit_voc_create", "slamit_voc_load_text", "slamit_voc_destroy", "slamit_voc_info",
     "slamit_voc_transform", "slamit_voc_transform_workspace", "slamit_voc_transform_batch_dev",
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
@@ -607,6 +607,8 @@ def lib():
         L.slamit_orb_debug_blurred.argtypes = [vp, i32, i32, vp, sz, vp, vp]
         L.slamit_orb_profile.argtypes = [vp, i32, vp, vp, i32]
         L.slamit_orb_debug_candidates.argtypes = [vp, i32, i32, vp, i32, vp]
+        if hasattr(L, "slamit_orb_debug_octree_path"):   # absent from earlier libraries loaded through SLAMIT_LIB for A/B runs
+            L.slamit_orb_debug_octree_path.argtypes = [vp, i32, i32, vp]
         L.slamit_hamming_best2.argtypes = [vp, i32, vp, i32, vp, vp, vp]
         L.slamit_hamming_best2_batch_dev.argtypes = [vp, vp, sz, vp, vp, sz, i32, i32, vp, vp, vp, sz, i32, vp]
         L.slamit_hamming_matrix.argtypes = [vp, i32, vp, i32, vp]
@@ -894,6 +896,12 @@ class ORBextractor:
         _check(lib().slamit_orb_debug_candidates(self._h, frame, level, _np_ptr(out), n.value, C.byref(n)),
                "debug_candidates")
         return out[:n.value]
+
+    def debug_octree_path(self, frame, level):
+        """(passes served from the path table, whether the workgroup left it and walked the keys) of the last call's octree pass."""
+        w = C.c_int()
+        _check(lib().slamit_orb_debug_octree_path(self._h, frame, level, C.byref(w)), "debug_octree_path")
+        return w.value & 0xFF, bool(w.value & 0x100)
 
 
 GRID_COLS, GRID_ROWS = 64, 48   # FRAME_GRID_COLS / FRAME_GRID_ROWS (include/Frame.h:40-41)

@@ -508,6 +508,14 @@ int slamit_orb_debug_candidates(slamit_orb* h, int frame, int level, int32_t* xy
     return SLAMIT_OK;
 }
 
+int slamit_orb_debug_octree_path(slamit_orb* h, int frame, int level, int* path_out) {
+    if (!h || level < 0 || level >= h->nlevels || !path_out) return slamit_fail(SLAMIT_ERR_ARG, "slamit_orb_debug_octree_path: bad argument");
+    if (frame < 0 || frame >= h->last_nframes) return slamit_fail(SLAMIT_ERR_STATE, "slamit_orb_debug_octree_path: no such frame");
+    SLAMIT_USE_DEVICE(h->device);
+    HIP_TRY(hipMemcpy(path_out, h->d_counts + (size_t)(frame * h->nlevels + level) * ORB_CC_PAD + 2, sizeof(int), hipMemcpyDeviceToHost));   // word 2: octree_kernel's path word
+    return SLAMIT_OK;
+}
+
 }  // extern "C"
 
 // stereo.hip: the device a handle was created on

@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "blur_window.h"
+#include "octree_table.h"
 #include "orb_types.h"
 #include "slamit_math.h"
 #include "wave_ops.h"
@@ -934,22 +935,7 @@ __global__ __launch_bounds__(256) void fast_cells_kernel(
 // Tie-break of the "largest first" phase: (size desc, creation seq desc) == (size desc, list
 // position asc); see DESIGN.md "octree determinism".
 // --------------------------------------------------------------------------------------------
-struct Box16 { short x0, y0, x1, y1; };
-
-__device__ __forceinline__ int box_quadrant(const Box16& b, int x, int y, int* mx, int* my) {
-    int midx = b.x0 + ((b.x1 - b.x0 + 1) >> 1);  // UL.x + ceil((UR.x-UL.x)/2)
-    int midy = b.y0 + ((b.y1 - b.y0 + 1) >> 1);
-    *mx = midx; *my = midy;
-    return (x < midx ? 0 : 1) + (y < midy ? 0 : 2);  // 0:n1 1:n2 2:n3 3:n4
-}
-__device__ __forceinline__ Box16 child_box(const Box16& b, int q) {
-    int midx = b.x0 + ((b.x1 - b.x0 + 1) >> 1);
-    int midy = b.y0 + ((b.y1 - b.y0 + 1) >> 1);
-    Box16 c;
-    c.x0 = (q & 1) ? midx : b.x0; c.x1 = (q & 1) ? b.x1 : midx;
-    c.y0 = (q & 2) ? midy : b.y0; c.y1 = (q & 2) ? b.y1 : midy;
-    return c;
-}
+// Box16, box_quadrant, child_box, nIniFD and the path table's layout: octree_table.h
 
 // exclusive scan of a[0..len) in place (LDS), returns the total; all NT threads call it
 template <int NT>
@@ -992,12 +978,9 @@ extern "C" int slamit_diag_oct(unsigned long long* out) { return (int)hipMemcpyF
 #ifndef OCT_THREADS
 #define OCT_THREADS 512
 #endif
-
-// depth of the path table the full passes are served from: the deepest of 4, 3, 2 whose table (4 + .. + 4^depth ints per root)
-// fits `room` ints; 0 = no table (a sweep over the keys per pass)
-__device__ __forceinline__ int nIniFD(int nIni, int room) {
-    return nIni * 340 <= room ? 4 : nIni * 84 <= room ? 3 : nIni * 20 <= room ? 2 : 0;
-}
+#ifndef OCT_BIG_BATCH_KEYS
+#define OCT_BIG_BATCH_KEYS 2048   // LDS key room of a workgroup in a call of 96 frames or more (orbk_octree)
+#endif
 
 // XY / ND: per-candidate position and current node, in LDS when the list fits (LK) and in the HBM workspace otherwise.
 template <int NT, bool LK>
@@ -1343,6 +1326,267 @@ __device__ __forceinline__ void octree_body(
 #endif
 }
 
+// The (frame, level) from its path table (octree_table.h; oct_table_seq there is this function on one thread): ONE sweep over the
+// keys by all threads fills the depth-FD histogram and the best key of every depth-FD bin, wavefront 0 alone then runs the passes
+// on the node list -- at most a few hundred nodes, a few to a lane, with wave scans and no workgroup barrier -- while the other
+// wavefronts wait for its verdict, and when the loop ended inside the table every non-empty bin hands its best key to the node that
+// covers it.  No key is stored, labelled or read twice.  Returns false (nothing written but *passes) when a pass needs depth
+// FD + 1: the caller then runs octree_body from the start.
+// LDS: hist | node codes (2 generations) | node best | populations (2 generations) | elist, ekey | scanbuf | rankv | sorted, in the
+// carve of octree_body (the boxes' room holds the codes and the node best: a node of the table needs no box; the children's
+// populations are read from hist where they are needed), and bin_best in the room of the key arrays.
+template <int NT>
+__device__ __forceinline__ bool octree_table_path(
+    const OrbLevel& L, const unsigned long long* __restrict__ K, int n_keys, OrbLevelKp* __restrict__ OUT,
+    int* __restrict__ kp_count_out, unsigned char* smem, int cap, unsigned long long* bin_best, int FD, int* s_vars, int* passes_out) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int nIni = L.nIni, N = L.quota;
+    const int HS = oct_table_ints(FD), NB = oct_bins(FD), leaf0 = oct_depth_off(FD);
+    int* const hist = reinterpret_cast<int*>(smem);                                                  // 2 * cap ints
+    int* const ncode0 = reinterpret_cast<int*>(smem + (size_t)8 * cap);                              // 2 * cap
+    unsigned long long* const nbest = reinterpret_cast<unsigned long long*>(smem + (size_t)16 * cap);   // cap
+    int* const cnt0 = reinterpret_cast<int*>(smem + (size_t)24 * cap);                               // 2 * cap
+    int* const elist = cnt0 + 2 * cap;       // cap: the expandable nodes of a "largest first" pass ...
+    unsigned* const ekey = reinterpret_cast<unsigned*>(elist + cap);   // cap: ... and their rank keys (2 * cap more stay idle)
+    int* const scanbuf = elist + 4 * cap;    // 5 * cap: the root boxes during the sweep, the node labels after the passes
+    int* const rankv = scanbuf + 5 * cap;    // cap
+    int* const sorted = rankv + cap;         // cap
+    Box16* const rootbox = reinterpret_cast<Box16*>(scanbuf);   // the sweep's root boxes (scanbuf is idle until the passes)
+    OD_DECL;
+
+    if (tid < nIni) { Box16 b; b.x0 = (short)L.rootUL[tid]; b.y0 = 0; b.x1 = (short)L.rootUR[tid]; b.y1 = (short)L.boxH; rootbox[tid] = b; }
+    for (int e = tid; e < nIni * HS; e += NT) hist[e] = 0;
+    for (int e = tid; e < nIni * NB; e += NT) bin_best[e] = 0ull;
+    __syncthreads();
+    {
+        const int nCols = L.nCols, wCell = L.wCell, hCell = L.hCell;
+        const unsigned inv_cols = 0xFFFFFFFFu / (unsigned)nCols + 1u;   // cell / nCols == umulhi(cell, inv) while cell * nCols < 2^32
+        const float hX = L.hX;
+        // (every lane stays in the loop: the runs below are taken over whole waves; four keys per thread are in flight)
+        for (int kb4 = 0; kb4 < n_keys; kb4 += 4 * NT) {
+            unsigned long long c4[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) c4[j] = K[min(kb4 + j * NT + tid, n_keys - 1)];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int kb = kb4 + j * NT;
+                if (kb >= n_keys) break;
+                const bool valid = kb + tid < n_keys;
+                const unsigned order = (unsigned)c4[j];
+                const int lx = order & 63, ly = (order >> 6) & 63, cell = order >> 12;
+                const int ci = (int)__umulhi((unsigned)cell, inv_cols), cj = cell - ci * nCols;
+                const int x = cj * wCell + lx, y = ci * hCell + ly;
+                const int r = oct_key_root(x, hX, nIni);
+                const int path = oct_key_path(rootbox[r], x, y, FD);
+                // the keys come in cell order, so neighbouring lanes mostly share a bin: per RUN of equal bins one atomic for
+                // the population and one for the best key (the run's maximum by a segmented reduction towards its first lane)
+                const int bin = valid ? r * NB + path : -1;
+                const int prev = __shfl_up(bin, 1);
+                const bool head = lane == 0 || bin != prev;
+                const unsigned long long heads = __ballot(head);
+                const unsigned long long rest = (heads >> lane) >> 1;
+                const int last = rest ? lane + (int)__builtin_ctzll(rest) : 63;   // last lane of this lane's run
+                unsigned long long pk = valid ? oct_pick_key((unsigned)(c4[j] >> 32), order) : 0ull;
+#pragma unroll
+                for (int s = 1; s < 64; s <<= 1) {
+                    const unsigned long long o = __shfl_down(pk, s);
+                    pk = (lane + s <= last && o > pk) ? o : pk;
+                }
+                if (head && bin >= 0) {
+                    atomicAdd(&hist[r * HS + leaf0 + path], last - lane + 1);
+                    atomicMax(&bin_best[bin], pk);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    OD_STAMP(0);
+
+    if (tid < 64) {   // wavefront 0: the node passes
+        for (int d = FD - 1; d >= 1; --d) {   // populations of the shallower paths
+            const int per = 1 << (2 * d), off = oct_depth_off(d), offc = oct_depth_off(d + 1);
+            for (int e = lane; e < nIni * per; e += 64) {
+                const int r = e >> (2 * d), pth = e & (per - 1);
+                const int* c = &hist[r * HS + offc + 4 * pth];
+                hist[r * HS + off + pth] = (c[0] + c[1]) + (c[2] + c[3]);
+            }
+            wave_mem_sync();
+        }
+        if (lane == 0) {  // roots without keys are erased, the others keep their order (<= 8 roots)
+            int m = 0;
+            for (int i = 0; i < nIni; ++i) {
+                const int c = (hist[i * HS] + hist[i * HS + 1]) + (hist[i * HS + 2] + hist[i * HS + 3]);
+                if (c > 0) { cnt0[m] = c; ncode0[m] = oct_code(i, 0, 0); ++m; }
+            }
+            s_vars[0] = m;
+        }
+        wave_mem_sync();
+        int n = __builtin_amdgcn_readfirstlane(s_vars[0]);
+        int cur = 0, passes = 0;
+        bool finish = false, careful = false, left = false;
+        bool deep = false;   // the list holds a node that has to be split and lies at depth FD (oct_node_leaves_table): only a
+                             // child made by the pass before can be one, so the pass that makes the children finds it out
+        while (!finish) {
+            if (deep) { left = true; break; }
+            const int prevSize = n;
+            const int* ccnt = cnt0 + cur * cap;
+            const int* ccode = ncode0 + cur * cap;
+            int kproc = 0;
+            if (careful) {
+                // "largest first": rank the expandable nodes by (population desc, list position asc), one u32 key each.  They are
+                // compacted first (m of n), then a lane holds one of them and walks all m keys (the same LDS word for every
+                // lane: a broadcast read); the populations stay below 2^20 (octree_kernel)
+                int m = 0;
+                for (int i0 = 0; i0 < n; i0 += 64) {
+                    const int i = i0 + lane;
+                    const int c = i < n ? ccnt[i] : 0;
+                    const bool ex = c > 1;
+                    const unsigned long long mask = __ballot(ex);
+                    const int k = m + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+                    if (i < n) rankv[i] = -1;
+                    if (ex) { elist[k] = i; ekey[k] = oct_rank_key(c, i); }
+                    m += (int)__popcll(mask);
+                }
+                wave_mem_sync();
+                for (int k0 = 0; k0 < m; k0 += 64) {
+                    const int k = k0 + lane;
+                    const unsigned mine = k < m ? ekey[k] : 0xFFFFFFFFu;
+                    int r = 0;
+#pragma unroll 4
+                    for (int j = 0; j < m; ++j) r += ekey[j] > mine;
+                    if (k < m) { const int i = elist[k]; sorted[r] = i; rankv[i] = r; }
+                }
+                wave_mem_sync();
+                // gains in rank order, their prefix, the first rank at which the list reaches N
+                kproc = m;
+                int base = 0;
+                for (int s0 = 0; s0 < m; s0 += 64) {
+                    const int s = s0 + lane;
+                    int g = 0;
+                    if (s < m) {
+                        const int* cc = &hist[oct_child_slot(ccode[sorted[s]], 0, HS)];
+                        g = (cc[0] > 0) + (cc[1] > 0) + (cc[2] > 0) + (cc[3] > 0) - 1;
+                    }
+                    const int incl = wave_inclusive_scan_i32(g);
+                    const unsigned long long reach = __ballot(s < m && n + base + incl >= N);
+                    if (reach) { kproc = s0 + (int)__builtin_ctzll(reach) + 1; break; }
+                    base += __builtin_amdgcn_readlane(incl, 63);
+                }
+            }
+            // The new list: the children of the split parents in reverse processing order (n4..n1 of the last parent first), then
+            // the nodes that stay, in their old order.  A full pass splits every expandable node in list order, a "largest first"
+            // pass ranks 0 .. kproc - 1.  (n_new <= cap by construction, as in octree_body; clamped anyway for memory safety)
+            int* const ncnt = cnt0 + (cur ^ 1) * cap;
+            int* const ncode = ncode0 + (cur ^ 1) * cap;
+            const int nsplit = careful ? kproc : n;
+            int n_new = 0, local_expand = 0;
+            bool deep_l = false;
+            for (int t0 = 0; t0 < nsplit; t0 += 64) {
+                const int t = t0 + lane;
+                int c = 0, nc = 0, cc[4] = {0, 0, 0, 0};
+                if (t < nsplit) {
+                    const int i = careful ? sorted[kproc - 1 - t] : n - 1 - t;
+                    if (ccnt[i] > 1) {
+                        c = ccode[i];
+                        const int* h = &hist[oct_child_slot(c, 0, HS)];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) { cc[q] = h[q]; nc += cc[q] > 0; }
+                    }
+                }
+                const int incl = wave_inclusive_scan_i32(nc);
+                int pos = n_new + incl - nc;
+#pragma unroll
+                for (int q = 3; q >= 0; --q)
+                    if (cc[q] > 0) {
+                        if (pos < cap) { ncnt[pos] = cc[q]; ncode[pos] = oct_code_child(c, q); }
+                        ++pos;
+                        local_expand += cc[q] > 1;
+                        deep_l |= oct_node_leaves_table(cc[q], oct_code_child(c, q), FD);
+                    }
+                n_new += __builtin_amdgcn_readlane(incl, 63);
+            }
+            for (int i0 = 0; i0 < n; i0 += 64) {
+                const int i = i0 + lane;
+                int c = 0, cn = 0, st = 0;
+                if (i < n) {
+                    cn = ccnt[i]; c = ccode[i];
+                    st = careful ? !(rankv[i] >= 0 && rankv[i] < kproc) : cn <= 1;
+                }
+                const int incl = wave_inclusive_scan_i32(st);
+                const int pos = n_new + incl - st;
+                if (st && pos < cap) { ncnt[pos] = cn; ncode[pos] = c; }
+                n_new += __builtin_amdgcn_readlane(incl, 63);
+            }
+            const int nToExpand = __builtin_amdgcn_readlane(wave_inclusive_scan_i32(local_expand), 63);
+            deep = __ballot(deep_l) != 0;
+            wave_mem_sync();
+            cur ^= 1;
+            n = min(n_new, cap);
+            ++passes;
+            if (n >= N || n == prevSize) finish = true;                  // ORBextractor.cc:682, 747
+            else if (!careful && n + nToExpand * 3 > N) careful = true;  // :686
+        }
+        if (!left) {
+            // every node enters its index at its (root, depth, path); the bins look their node up below
+            int* const rootlab = scanbuf;
+            int* const lab = scanbuf + ORB_MAX_ROOTS;
+            for (int e = lane; e < nIni * HS; e += 64) lab[e] = -1;
+            if (lane < ORB_MAX_ROOTS) rootlab[lane] = -1;
+            for (int i = lane; i < n; i += 64) nbest[i] = 0ull;
+            wave_mem_sync();
+            for (int i = lane; i < n; i += 64) {
+                const int c = ncode0[cur * cap + i];
+                if (oct_code_depth(c) == 0) rootlab[oct_code_root(c)] = i;
+                else lab[oct_node_slot(c, HS)] = i;
+            }
+        }
+        if (lane == 0) { s_vars[0] = n; s_vars[2] = passes; s_vars[3] = left; }
+    }
+    __syncthreads();
+    OD_STAMP(1);
+    *passes_out = s_vars[2];
+    if (s_vars[3]) return false;
+    const int n = s_vars[0];
+
+    // ---- best key per node (ORBextractor.cc:755-773): the list's nodes are disjoint, so of a bin's levels exactly one answers ----
+    {
+        const int* rootlab = scanbuf;
+        const int* lab = scanbuf + ORB_MAX_ROOTS;
+        for (int b = tid; b < nIni * NB; b += NT) {
+            const int r = b >> (2 * FD), pth = b & (NB - 1);
+            if (hist[r * HS + leaf0 + pth] <= 0) continue;
+            int node = rootlab[r];
+            for (int d = 1; d <= FD; ++d) {
+                const int v = lab[r * HS + oct_depth_off(d) + (pth >> (2 * (FD - d)))];
+                node = v >= 0 ? v : node;
+            }
+            if (node >= 0) atomicMax(&nbest[node], bin_best[b]);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += NT) {
+        const unsigned long long b = nbest[i];
+        const unsigned order = oct_pick_order(b);
+        int lx = order & 63, ly = (order >> 6) & 63, cell = order >> 12;
+        int ci = cell / L.nCols, cj = cell - ci * L.nCols;
+        OrbLevelKp kp;
+        kp.x = (int16_t)(cj * L.wCell + lx + ORB_MIN_BORDER);  // ORBextractor.cc:863-864
+        kp.y = (int16_t)(ci * L.hCell + ly + ORB_MIN_BORDER);
+        kp.response = (float)oct_pick_response(b);
+        kp.angle = 0.f; kp.cs = 1.f; kp.sn = 0.f;
+        if (i < L.kp_cap) OUT[i] = kp;
+    }
+    if (tid == 0) *kp_count_out = min(n, L.kp_cap);
+#ifdef OCT_DIAG
+    OD_STAMP(2);
+    if (tid == 0) {   // table path: [0] sweep, [1] node passes, [2] pick + output
+        const int w = blockIdx.y * gridDim.x + blockIdx.x;
+        if (w < 4096) { unsigned long long* o = g_oct_ph + 8 * w; for (int k = 0; k < 5; ++k) o[k] = od_ph[k]; o[6] = ((unsigned long long)s_vars[2] << 32) | (unsigned)n_keys; o[7] = od_rt0; o[5] = __builtin_amdgcn_s_memrealtime(); }
+    }
+#endif
+    return true;
+}
+
 template <int OCT_NT>
 __global__ __launch_bounds__(OCT_NT) void octree_kernel(
     const OrbLevel* __restrict__ levels, int nlevels,
@@ -1372,9 +1616,19 @@ __global__ __launch_bounds__(OCT_NT) void octree_kernel(
     const unsigned long long* K = cand + L.cand_off + (size_t)frame * cand_frame_stride;
     OrbLevelKp* OUT = lkp + L.kp_off + (size_t)frame * kp_frame_stride;
     if (n_keys == 0) {
-        if (threadIdx.x == 0) kp_count[kidx] = 0;
+        if (threadIdx.x == 0) { kp_count[kidx] = 0; cand_count[kidx * ORB_CC_PAD + 2] = oct_path_word(0, false); }
         return;
     }
+    // From the path table when it fits (octree_table.h); a workgroup whose passes need a depth the table does not hold walks the
+    // keys instead, from the start.  The line's third word tells slamit_orb_debug_octree_path which way it went.
+    const int FD = nIniFD(L.nIni, 2 * node_cap);
+    int table_passes = 0;
+    bool done = false;
+    if (oct_table_fits(L.nIni, FD, (long)key_cap * 6, n_keys))
+        done = octree_table_path<OCT_NT>(L, K, n_keys, OUT, &kp_count[kidx], smem, node_cap, reinterpret_cast<unsigned long long*>(k_xy), FD,
+                                         s_vars, &table_passes);
+    if (threadIdx.x == 0) cand_count[kidx * ORB_CC_PAD + 2] = oct_path_word(table_passes, !done);
+    if (done) return;
     if (n_keys <= key_cap)
         octree_body<OCT_NT, true>(L, K, n_keys, k_xy, k_nd, OUT, &kp_count[kidx], smem, node_cap, wave_tmp, s_vars);
     else
@@ -2184,7 +2438,7 @@ void orbk_octree(hipStream_t st, const OrbLevel* levels, int nlevels, const unsi
     // handle's full key arrays (48 KB) three fit, with room for 2,048 keys five do, and the lists above that go through the HBM
     // workspace (L2 resident) at little cost: 0.116 -> 0.092 ms per 256 VGA frames.  (1,536 keys = six per CU: the pass alone
     // 0.088 ms, but the step 2 % LONGER -- the side stream's blur finds less of the chip.)  A few frames keep the big arrays.
-    if (nframes >= 96) key_cap = std::min(key_cap, 2048);
+    if (nframes >= 96) key_cap = std::min(key_cap, OCT_BIG_BATCH_KEYS);
     if (nt == 1024)
         hipLaunchKernelGGL(octree_kernel<1024>, grid, dim3(1024), orbk_octree_smem(node_cap, key_cap), st, levels, nlevels, cand,
                            cand_frame_stride, cand_count, ws_xy, ws_node, lkp, kp_frame_stride, kp_count, node_cap,
