@@ -2103,6 +2103,137 @@ typedef struct slamit_kf_erase_batch_rec slamit_kf_erase_batch_rec;
 size_t slamit_kf_erase_workspace(int n_maps, int cap, int kf_cap, int row_cap, int child_cap);
 int slamit_kf_erase_batch_dev(int device, const slamit_kf_erase_batch_rec* batch, void* stream);
 
+/* ---- Essential-graph optimisation (loop closing, between OptimizeSim3 / CorrectLoop's fusion and the global BA) ----------------
+ * Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044) with the g2o it instantiates: one VertexSim3Expmap per good keyframe
+ * (estimate Scw, _fix_scale = fix_scale), per edge an EdgeSim3 (Thirdparty/g2o/g2o/types/types_seven_dof_expmap.h:99-126: error
+ * log(C * S_v0 * S_v1^-1), information I7, no robust kernel, NUMERIC Jacobians -- core/base_binary_edge.hpp:131-200, central
+ * differences with delta 1e-9, a fixed vertex skipped), Levenberg-Marquardt from lambda_init (setUserLambdaInit(1e-16)) for max_its
+ * iterations (20) with the fork's stop rules, then [R | t / s] per keyframe and correctedSwr.map(Srw.map(Xw)) per good point.
+ *
+ * Two steps.  slamit_essential_plan (host only, nothing of the GPU) restates :847-983, the choice of edges, over slot-numbered
+ * tables; slamit_essential_graph* takes that edge list with the Sim3s and runs the rest on the device.
+ *
+ * THE PLAN.  Slots need not be ordered: every `<` of the reference is taken on kf_id (mnId).  Edges come in the reference's
+ * insertion order: first the LoopConnections ones (kind SLAMIT_EG_LOOP_CONNECTION: measured from Scw on both sides), then per
+ * keyframe its spanning-tree edge, its loop edges and its covisibility edges (SLAMIT_EG_NORMAL: measured from Snc).  Kept as the
+ * reference has them: the sInsertedEdges test applies to covisibility edges only; the (cur, loop) pair is exempt from the weight
+ * gate; parallel edges between one pair are legal; pKFn != parent, !hasChild and !sLoopEdges.count exclude a covisible keyframe;
+ * GetCovisiblesByWeight returns NOTHING for a row none of whose weights is below min_feat (KeyFrame.cc:195-197).
+ * Departures: the reference walks std::map / std::set<KeyFrame*> in pointer order, this walks ascending slots;
+ * GetWeight is read from the ordered row; a bad keyframe is skipped as a source (Map::GetAllKeyFrames holds none); an edge that
+ * names a bad or out-of-range keyframe refuses the whole call with SLAMIT_ERR_ARG (the reference would hand g2o a NULL vertex).
+ * inc_ptr / inc_edge: per keyframe slot the incident edges in list order, entry = 2 * edge + side (side 1: the slot is v1).
+ * More than edge_cap edges fails with SLAMIT_ERR_CAPACITY (*n_edge then holds the count needed, nothing else is written). */
+#define SLAMIT_EG_NORMAL 0
+#define SLAMIT_EG_LOOP_CONNECTION 1
+struct slamit_eg_graph {
+    int32_t n_kf, row_cap;          /* keyframe slots; entries per ordered covisibility row */
+    int32_t loop_kf, cur_kf;        /* slots of pLoopKF, pCurKF */
+    int32_t min_feat, reserved;     /* 100 */
+    const uint8_t* kf_bad;          /* [n_kf] */
+    const int32_t* kf_id;           /* [n_kf] mnId */
+    const int32_t* kf_parent;       /* [n_kf] slot, -1 = none */
+    const int32_t* child_ptr;       /* [n_kf + 1] */
+    const int32_t* child_kf;        /* mspChildrens */
+    const int32_t* loop_ptr;        /* [n_kf + 1] */
+    const int32_t* loop_kf_list;    /* mspLoopEdges (GetLoopEdges) */
+    const int32_t* ord_kf;          /* [n_kf][row_cap] as slamit_covis_index.ord_kf */
+    const int32_t* ord_w;           /* [n_kf][row_cap] */
+    const int32_t* ord_n;           /* [n_kf] */
+    const int32_t* conn_ptr;        /* [n_kf + 1] LoopConnections: row i = the set of keyframe i (empty: i is no key of the map) */
+    const int32_t* conn_kf;
+};
+typedef struct slamit_eg_graph slamit_eg_graph;
+int slamit_essential_plan(const slamit_eg_graph* g, int32_t edge_cap, int32_t* edge_v0, int32_t* edge_v1, int32_t* edge_kind,
+                          int32_t* n_edge, int32_t* inc_ptr /* [n_kf + 1] */, int32_t* inc_edge /* [2 * edge_cap] */);
+
+/* THE OPTIMISATION.  Ceilings: SLAMIT_EG_MAX_KF keyframes that are neither fixed nor bad (7,168 unknowns: the dense lower triangle,
+ * 32 x 32 tiles, is 206 MB of the workspace), SLAMIT_EG_MAX_EDGES edges (64 per free keyframe at the ceiling -- the essential graph
+ * is the spanning tree plus the covisibility edges of weight >= 100 plus the loop edges, a handful per keyframe; an edge keeps 120
+ * doubles on the device, 63 MB at the ceiling), SLAMIT_EG_MAX_ITS iterations, SLAMIT_EG_MAX_POINTS points.  One past any of them
+ * refuses the call with SLAMIT_ERR_CAPACITY; an edge or a point's reference outside [0, n_kf) or on a bad keyframe, an edge from a
+ * keyframe to itself, a negative count or a missing array refuses it with SLAMIT_ERR_ARG; both before anything is launched or written.
+ *
+ * Numerics: double throughout.  (H + lambda I) x = b is solved DENSE by LDLt without pivoting (32-column panels, the trailing
+ * update on v_mfma_f64_16x16x4_f64) where the reference runs Eigen's sparse SimplicialLDLT under an AMD ordering: the same system,
+ * another elimination order, so results agree to rounding (1e-5 relative is what the tests hold them to), not bit for bit.  H and b
+ * are summed edge by edge in list order, chi2 and the gain ratio's scale in a fixed order: two runs give identical bits.  A zero or
+ * non-finite pivot fails the trial as SimplicialLDLT's NumericalIssue does (its cost counts as DBL_MAX; the state is not moved, where
+ * g2o would apply the previous trial's x before undoing it).  The verdict of every trial is read back by the host (one 8-byte copy
+ * and a stream wait per trial): the calls return when the result is complete.
+ *
+ * A keyframe that is fixed or bad keeps its Scw; its pose is still written from it.  A bad point keeps its position and is not listed
+ * in `touched`; `touched` holds the good points ascending, in the layout slamit_points_batch_rec.d_points / d_n read (one item,
+ * cap >= n_pt), so that UpdateNormalAndDepth follows on the stream.  Entries past *n_touched: -1 in the host form, as the caller left
+ * them in the device form. */
+#define SLAMIT_EG_MAX_KF 1024
+#define SLAMIT_EG_MAX_EDGES 65536
+#define SLAMIT_EG_MAX_ITS 32
+#define SLAMIT_EG_MAX_TRIALS 320          /* SLAMIT_EG_MAX_ITS x _maxTrialsAfterFailure */
+#define SLAMIT_EG_MAX_POINTS (1 << 24)
+struct slamit_eg_problem {
+    int32_t n_kf, n_edge, n_pt;
+    int32_t n_free;                  /* device form: keyframes neither fixed nor bad, which the caller states (the flags are on the
+                                        device; a count that does not match fails the call with SLAMIT_ERR_ARG after the first launch,
+                                        nothing of the result written; so does an edge, a good point's reference keyframe or an incidence
+                                        pointer outside its table or on a bad keyframe, which a first kernel looks for before any other
+                                        indexes by them).  Host form: ignored. */
+    int32_t fix_scale;               /* bFixScale */
+    int32_t max_its;                 /* 20 */
+    double lambda_init;              /* 1e-16 */
+    const double* scw_r;             /* [n_kf][9] CorrectedSim3 where it has the keyframe, else (Rcw, tcw, 1): r row-major, */
+    const double* scw_t;             /* [n_kf][3]   t, */
+    const double* scw_s;             /* [n_kf]      s, as slamit_sim3_problem states a Sim3 */
+    const double* snc_r;             /* [n_kf][9] NonCorrectedSim3 where it has the keyframe, else the keyframe's Scw */
+    const double* snc_t;             /* [n_kf][3] */
+    const double* snc_s;             /* [n_kf] */
+    const uint8_t* fixed;            /* [n_kf] 1 = pLoopKF */
+    const uint8_t* bad;              /* [n_kf] */
+    const int32_t* edge_v0;          /* [n_edge] */
+    const int32_t* edge_v1;          /* [n_edge] */
+    const int32_t* edge_kind;        /* [n_edge] SLAMIT_EG_NORMAL / SLAMIT_EG_LOOP_CONNECTION */
+    const int32_t* inc_ptr;          /* [n_kf + 1] as slamit_essential_plan writes them; host form: nullable (built from the edges) */
+    const int32_t* inc_edge;         /* [2 n_edge] */
+    const float* pt_pos;             /* [n_pt][3] GetWorldPos() */
+    const int32_t* pt_ref;           /* [n_pt] slot of mnCorrectedReference where mnCorrectedByKF == pCurKF->mnId, else of the reference keyframe */
+    const uint8_t* pt_bad;           /* [n_pt] */
+};
+typedef struct slamit_eg_problem slamit_eg_problem;
+
+struct slamit_eg_stats {
+    int32_t n_its;                               /* LM iterations run */
+    int32_t n_trials;                            /* LM trials over all of them */
+    int32_t n_free;                              /* keyframes in the system */
+    int32_t status;                              /* 0 (a refused call does not write the record) */
+    double chi2_init;                            /* cost before the first iteration */
+    double chi2[SLAMIT_EG_MAX_ITS];              /* cost of the last evaluated trial of each iteration */
+    double lambda[SLAMIT_EG_MAX_ITS];            /* lambda after each iteration */
+    int32_t trials[SLAMIT_EG_MAX_ITS];           /* trials of each iteration */
+    double trial_chi2[SLAMIT_EG_MAX_TRIALS];     /* per trial: cost at the tentative state (DBL_MAX: the factorisation failed) */
+    double trial_rho[SLAMIT_EG_MAX_TRIALS];      /* per trial: the gain ratio; the step stood iff rho > 0 and the cost is finite */
+};
+typedef struct slamit_eg_stats slamit_eg_stats;
+
+struct slamit_eg_result {
+    double* sim3_r;                  /* [n_kf][9] corrected Siw */
+    double* sim3_t;                  /* [n_kf][3] */
+    double* sim3_s;                  /* [n_kf] */
+    double* pose;                    /* [n_kf][12] R row-major, t / s */
+    float* pt_pos;                   /* [n_pt][3] */
+    int32_t* touched;                /* [n_pt] */
+    int32_t* n_touched;              /* [1] */
+    slamit_eg_stats* stats;          /* host form: nullable.  Device form: required, a DEVICE pointer */
+};
+typedef struct slamit_eg_result slamit_eg_result;
+
+/* Host pointers, synchronous. */
+int slamit_essential_graph(int device, const slamit_eg_problem* prob, slamit_eg_result* res);
+/* Device pointers in both records, a caller-owned workspace of slamit_essential_graph_workspace(n_free, n_kf, n_edge, n_pt) bytes
+ * (256-byte aligned).  Runs on `stream` and waits on it once per LM trial; complete when it returns. */
+size_t slamit_essential_graph_workspace(int n_free, int n_kf, int n_edge, int n_pt);
+int slamit_essential_graph_dev(int device, const slamit_eg_problem* prob, const slamit_eg_result* res, void* d_workspace,
+                               size_t workspace_bytes, void* stream);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 
 const char* slamit_last_error(void);

@@ -562,9 +562,37 @@ class PoseResult(C.Structure):
                 ("n_its", C.c_int32 * 4), ("chi2", C.c_double * 4)]
 
 
+EG_NORMAL, EG_LOOP_CONNECTION = 0, 1
+EG_MAX_KF, EG_MAX_EDGES, EG_MAX_ITS, EG_MAX_TRIALS, EG_MAX_POINTS = 1024, 65536, 32, 320, 1 << 24
+
+
+class EgGraph(C.Structure):   # struct slamit_eg_graph
+    _fields_ = [("n_kf", C.c_int32), ("row_cap", C.c_int32), ("loop_kf", C.c_int32), ("cur_kf", C.c_int32), ("min_feat", C.c_int32), ("reserved", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("kf_bad", "kf_id", "kf_parent", "child_ptr", "child_kf", "loop_ptr", "loop_kf_list", "ord_kf", "ord_w", "ord_n",
+                                          "conn_ptr", "conn_kf")]
+
+
+class EgProblem(C.Structure):   # struct slamit_eg_problem
+    _fields_ = [("n_kf", C.c_int32), ("n_edge", C.c_int32), ("n_pt", C.c_int32), ("n_free", C.c_int32), ("fix_scale", C.c_int32), ("max_its", C.c_int32),
+                ("lambda_init", C.c_double)] + \
+               [(k, C.c_void_p) for k in ("scw_r", "scw_t", "scw_s", "snc_r", "snc_t", "snc_s", "fixed", "bad", "edge_v0", "edge_v1", "edge_kind", "inc_ptr",
+                                          "inc_edge", "pt_pos", "pt_ref", "pt_bad")]
+
+
+class EgStats(C.Structure):   # struct slamit_eg_stats
+    _fields_ = [("n_its", C.c_int32), ("n_trials", C.c_int32), ("n_free", C.c_int32), ("status", C.c_int32), ("chi2_init", C.c_double),
+                ("chi2", C.c_double * EG_MAX_ITS), ("lambda", C.c_double * EG_MAX_ITS), ("trials", C.c_int32 * EG_MAX_ITS),
+                ("trial_chi2", C.c_double * EG_MAX_TRIALS), ("trial_rho", C.c_double * EG_MAX_TRIALS)]
+
+
+class EgResult(C.Structure):   # struct slamit_eg_result
+    _fields_ = [(k, C.c_void_p) for k in ("sim3_r", "sim3_t", "sim3_s", "pose", "pt_pos", "touched", "n_touched", "stats")]
+
+
 _lib = None
 
 EXPORTS = [
+    "slamit_essential_plan", "slamit_essential_graph", "slamit_essential_graph_workspace", "slamit_essential_graph_dev",
     "slamit_orb_create", "slamit_orb_destroy", "slamit_orb_tables", "slamit_orb_max_keypoints",
     "slamit_orb_extract", "slamit_orb_extract_batch", "slamit_orb_extract_batch_dev", "slamit_orb_level",
     "slamit_orb_debug_candidates", "slamit_orb_debug_octree_path", "slamit_orb_debug_blurred", "slamit_orb_profile", "slamit_hamming_best2", "slamit_hamming_best2_batch_dev",
@@ -734,6 +762,12 @@ def lib():
         if hasattr(L, "slamit_pose_optimize_batch"):
             L.slamit_pose_optimize_batch.argtypes = [i32, i32, C.POINTER(PoseProblem), C.POINTER(PoseResult)]
             L.slamit_pose_optimize.argtypes = [i32, C.POINTER(PoseProblem), C.POINTER(PoseResult)]
+        if hasattr(L, "slamit_essential_graph"):   # absent from earlier libraries loaded through SLAMIT_LIB for A/B runs
+            L.slamit_essential_plan.argtypes = [C.POINTER(EgGraph), i32, vp, vp, vp, vp, vp, vp]
+            L.slamit_essential_graph.argtypes = [i32, C.POINTER(EgProblem), C.POINTER(EgResult)]
+            L.slamit_essential_graph_workspace.argtypes = [i32, i32, i32, i32]
+            L.slamit_essential_graph_workspace.restype = sz
+            L.slamit_essential_graph_dev.argtypes = [i32, C.POINTER(EgProblem), C.POINTER(EgResult), vp, sz, vp]
         L.slamit_last_error.restype = C.c_char_p
         L.slamit_version.restype = C.c_char_p
         _lib = L
@@ -3535,3 +3569,82 @@ def kf_erase_batch_dev(maps, tree, t, device=0, stream=None):
                           t["op_status"].data_ptr(), t["edits"].data_ptr(), t["n_edits_out"].data_ptr(), t["n_child_out"].data_ptr(), t["status"].data_ptr(),
                           ws.data_ptr(), ws.numel() * ws.element_size())
     _check(lib().slamit_kf_erase_batch_dev(device, C.byref(rec), stream), "slamit_kf_erase_batch_dev")
+
+
+# ---- essential-graph optimisation (Optimizer::OptimizeEssentialGraph) -----------------------------------------------------------
+_EG_GRAPH_ARRAYS = (("kf_bad", np.uint8), ("kf_id", np.int32), ("kf_parent", np.int32), ("child_ptr", np.int32), ("child_kf", np.int32),
+                    ("loop_ptr", np.int32), ("loop_kf_list", np.int32), ("ord_kf", np.int32), ("ord_w", np.int32), ("ord_n", np.int32),
+                    ("conn_ptr", np.int32), ("conn_kf", np.int32))
+_EG_PROBLEM_ARRAYS = (("scw_r", np.float64), ("scw_t", np.float64), ("scw_s", np.float64), ("snc_r", np.float64), ("snc_t", np.float64),
+                      ("snc_s", np.float64), ("fixed", np.uint8), ("bad", np.uint8), ("edge_v0", np.int32), ("edge_v1", np.int32),
+                      ("edge_kind", np.int32), ("inc_ptr", np.int32), ("inc_edge", np.int32), ("pt_pos", np.float32), ("pt_ref", np.int32),
+                      ("pt_bad", np.uint8))
+
+
+def essential_plan(graph, edge_cap=None):
+    """The edge list of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:847-983) from slot-numbered tables: `graph` holds the
+    fields of slamit_eg_graph (synth.synth_essential makes one).  Host only.  Returns edge_v0, edge_v1, edge_kind in the reference's
+    insertion order and inc_ptr, inc_edge, the incidence lists slamit_essential_graph_dev needs."""
+    n = int(graph["n_kf"])
+    keep = {k: np.ascontiguousarray(graph[k], dt) for k, dt in _EG_GRAPH_ARRAYS}
+    g = EgGraph(n, int(graph["row_cap"]), int(graph["loop_kf"]), int(graph["cur_kf"]), int(graph.get("min_feat", 100)), 0,
+                *[_np_ptr(keep[k]) if keep[k].size else None for k, _ in _EG_GRAPH_ARRAYS])
+    if edge_cap is None:
+        edge_cap = int(keep["conn_kf"].size + keep["loop_kf_list"].size + keep["ord_n"].sum() + n)
+    v0, v1, kind = (np.zeros(max(edge_cap, 1), np.int32) for _ in range(3))
+    inc_ptr, inc_edge = np.zeros(n + 1, np.int32), np.zeros(2 * max(edge_cap, 1), np.int32)
+    ne = C.c_int32(0)
+    _check(lib().slamit_essential_plan(C.byref(g), edge_cap, _np_ptr(v0), _np_ptr(v1), _np_ptr(kind), C.byref(ne), _np_ptr(inc_ptr), _np_ptr(inc_edge)),
+           "slamit_essential_plan")
+    e = ne.value
+    return dict(edge_v0=v0[:e].copy(), edge_v1=v1[:e].copy(), edge_kind=kind[:e].copy(), inc_ptr=inc_ptr, inc_edge=inc_edge[:2 * e].copy())
+
+
+def _eg_stats(st):
+    n, q = int(st.n_its), min(int(st.n_trials), EG_MAX_TRIALS)
+    return dict(n_its=n, n_trials=int(st.n_trials), n_free=int(st.n_free), chi2_init=float(st.chi2_init), chi2=np.array(st.chi2[:n]),
+                lam=np.array(getattr(st, "lambda")[:n]), trials=np.array(st.trials[:n], np.int32), trial_chi2=np.array(st.trial_chi2[:q]),
+                trial_rho=np.array(st.trial_rho[:q]))
+
+
+def essential_graph(prob, device=0):
+    """Optimizer::OptimizeEssentialGraph on host arrays: `prob` holds the fields of slamit_eg_problem (the edges as essential_plan
+    returns them; inc_ptr / inc_edge optional).  Returns sim3_r (n_kf, 9), sim3_t, sim3_s, pose (n_kf, 12), points (n_pt, 3) f32, touched
+    (the good points, ascending) and the LM record (n_its, chi2, lam, trials per iteration; trial_chi2, trial_rho per trial)."""
+    n, ne = int(prob["n_kf"]), len(prob["edge_v0"])
+    keep = {k: np.ascontiguousarray(prob[k], dt) for k, dt in _EG_PROBLEM_ARRAYS if prob.get(k) is not None}
+    npt = len(keep["pt_ref"]) if "pt_ref" in keep else 0
+    p = EgProblem(n, ne, npt, 0, int(prob["fix_scale"]), int(prob.get("max_its", 20)), float(prob.get("lambda_init", 1e-16)),
+                  *[_np_ptr(keep[k]) if k in keep and keep[k].size else None for k, _ in _EG_PROBLEM_ARRAYS])
+    out = dict(sim3_r=np.zeros((n, 9)), sim3_t=np.zeros((n, 3)), sim3_s=np.zeros(n), pose=np.zeros((n, 12)), points=np.zeros((npt, 3), np.float32),
+               touched=np.zeros(npt, np.int32))
+    nt, st = np.zeros(1, np.int32), EgStats()
+    r = EgResult(*[_np_ptr(out[k]) if out[k].size else None for k in ("sim3_r", "sim3_t", "sim3_s", "pose", "points", "touched")], _np_ptr(nt),
+                 C.cast(C.byref(st), C.c_void_p))
+    _check(lib().slamit_essential_graph(device, C.byref(p), C.byref(r)), "slamit_essential_graph")
+    out["touched"] = out["touched"][:int(nt[0])]
+    out.update(_eg_stats(st))
+    return out
+
+
+def essential_graph_workspace(n_free, n_kf, n_edge, n_pt):
+    return int(lib().slamit_essential_graph_workspace(n_free, n_kf, n_edge, n_pt))
+
+
+def essential_graph_dev(t, n_free, fix_scale, max_its=20, lambda_init=1e-16, device=0, stream=None):
+    """The same, resident.  t: dict of torch CUDA tensors -- the arrays of slamit_eg_problem (inc_ptr and inc_edge required) and of
+    slamit_eg_result (sim3_r, sim3_t, sim3_s, pose f64; points f32; touched, n_touched i32; stats: uint8 of ctypes.sizeof(EgStats)) and
+    workspace (uint8, essential_graph_workspace(...) bytes, 256-byte aligned).  n_free: the keyframes neither fixed nor bad.  Waits on
+    `stream` once per LM trial; the result is complete on return (the stream's later work may go on reading it there)."""
+    n, ne, npt = t["scw_s"].shape[0], t["edge_v0"].shape[0], t["pt_ref"].shape[0]
+    ptr = lambda k: t[k].data_ptr() if t[k].numel() else None
+    p = EgProblem(n, ne, npt, int(n_free), int(fix_scale), int(max_its), float(lambda_init), *[ptr(k) for k, _ in _EG_PROBLEM_ARRAYS])
+    r = EgResult(*[ptr(k) for k in ("sim3_r", "sim3_t", "sim3_s", "pose", "points", "touched", "n_touched", "stats")])
+    ws = t["workspace"]
+    _check(lib().slamit_essential_graph_dev(device, C.byref(p), C.byref(r), ws.data_ptr(), ws.numel() * ws.element_size(), stream),
+           "slamit_essential_graph_dev")
+
+
+def eg_stats_from_bytes(buf):
+    """The LM record out of the bytes of a slamit_eg_stats (essential_graph_dev's `stats` tensor, copied to the host)."""
+    return _eg_stats(EgStats.from_buffer_copy(bytes(buf)))

@@ -23,6 +23,7 @@
 
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <list>
@@ -76,6 +77,18 @@ public:
     // slamit_shim_sim3_{get,set} overloads exist.
     template <class KeyFrameT, class MapPointT, class Sim3T>
     static int OptimizeSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches1, Sim3T& g2oS12, const float th2, const bool bFixScale);
+
+    // Optimizer::OptimizeEssentialGraph (Optimizer.cc:781-1044; LoopClosing::CorrectLoop) with the reference's signature, on whatever
+    // types the caller has.  It numbers the map's keyframes into slots (ascending mnId), flattens the graph for slamit_essential_plan
+    // (:847-983, the choice of edges), makes ONE slamit_essential_graph call and writes poses and points back under mMutexMapUpdate.
+    // PoseMapT = LoopClosing::KeyFrameAndPose (a map KeyFrame* -> Sim3, read through slamit_shim_sim3_get), ConnT = map<KeyFrame*,
+    // set<KeyFrame*>>.  Members used: Map: GetAllKeyFrames(), GetAllMapPoints(), mMutexMapUpdate; KeyFrame: mnId, isBad(), GetRotation(),
+    // GetTranslation(), GetParent(), GetChilds(), GetLoopEdges(), GetVectorCovisibleKeyFrames(), GetWeight(), SetPose(); MapPoint:
+    // isBad(), mnCorrectedByKF, mnCorrectedReference, GetReferenceKeyFrame(), GetWorldPos(), SetWorldPos(), UpdateNormalAndDepth().
+    // A keyframe named by the graph that the map does not hold, or any refusal of the two calls, leaves the map as it was: LastStatus().
+    template <class MapT, class KeyFrameT, class PoseMapT, class ConnT>
+    static void OptimizeEssentialGraph(MapT* pMap, KeyFrameT* pLoopKF, KeyFrameT* pCurKF, const PoseMapT& NonCorrectedSim3, const PoseMapT& CorrectedSim3,
+                                       const ConnT& LoopConnections, const bool& bFixScale);
 
     // POD form: the window already flattened (what the template above produces).
     static int LocalBundleAdjustmentPOD(const slamit_ba_problem& prob, const volatile bool* stop, slamit_ba_result& res);
@@ -285,6 +298,137 @@ int Optimizer::OptimizeSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPoi
         if (!inlier[k]) vpMatches1[vnIndexEdge[k]] = static_cast<MapPointT*>(NULL);
     if (R.n_its[1] > 0 || R.n_inliers > 0) slamit_shim_sim3_set(g2oS12, R.r12, R.t12, R.s12);   // the early return 0 leaves g2oS12 alone (:1212-1213)
     return R.n_inliers;
+}
+
+template <class KeyFrameT>
+struct slamit_shim_kf_by_id {
+    bool operator()(const KeyFrameT* a, const KeyFrameT* b) const { return a->mnId < b->mnId; }
+};
+
+template <class MapT, class KeyFrameT, class PoseMapT, class ConnT>
+void Optimizer::OptimizeEssentialGraph(MapT* pMap, KeyFrameT* pLoopKF, KeyFrameT* pCurKF, const PoseMapT& NonCorrectedSim3, const PoseMapT& CorrectedSim3,
+                                       const ConnT& LoopConnections, const bool& bFixScale) {
+    std::vector<KeyFrameT*> kfs = pMap->GetAllKeyFrames();
+    std::sort(kfs.begin(), kfs.end(), slamit_shim_kf_by_id<KeyFrameT>());
+    const int n = (int)kfs.size();
+    std::map<const KeyFrameT*, int> slot;
+    std::map<long, int> slotOfId;
+    for (int i = 0; i < n; ++i) { slot[kfs[i]] = i; slotOfId[(long)kfs[i]->mnId] = i; }
+    bool missing = false;
+    auto at = [&](const KeyFrameT* k) -> int {
+        typename std::map<const KeyFrameT*, int>::const_iterator it = slot.find(k);
+        if (it == slot.end()) { missing = true; return 0; }
+        return it->second;
+    };
+    // ---- the tables of slamit_eg_graph ----
+    std::vector<uint8_t> bad(n, 0), fixed(n, 0);
+    std::vector<int32_t> id(n), parent(n, -1), childPtr(n + 1, 0), childKf, loopPtr(n + 1, 0), loopKf, ordN(n, 0), connPtr(n + 1, 0), connKf;
+    std::vector<std::vector<int32_t> > rowKf(n), rowW(n);
+    size_t rowCap = 1;
+    for (int i = 0; i < n; ++i) {
+        KeyFrameT* k = kfs[i];
+        bad[i] = k->isBad() ? 1 : 0;
+        id[i] = (int32_t)k->mnId;
+        fixed[i] = k == pLoopKF ? 1 : 0;
+        if (!bad[i]) {
+            if (k->GetParent()) parent[i] = at(k->GetParent());
+            const auto childs = k->GetChilds();
+            for (auto it = childs.begin(); it != childs.end(); ++it) childKf.push_back(at(*it));
+            const auto loops = k->GetLoopEdges();
+            for (auto it = loops.begin(); it != loops.end(); ++it) loopKf.push_back(at(*it));
+            const auto ordered = k->GetVectorCovisibleKeyFrames();
+            for (size_t j = 0; j < ordered.size(); ++j) { rowKf[i].push_back(at(ordered[j])); rowW[i].push_back(k->GetWeight(ordered[j])); }
+            typename ConnT::const_iterator c = LoopConnections.find(k);
+            if (c != LoopConnections.end())
+                for (auto it = c->second.begin(); it != c->second.end(); ++it) connKf.push_back(at(*it));
+        }
+        childPtr[i + 1] = (int32_t)childKf.size(); loopPtr[i + 1] = (int32_t)loopKf.size(); connPtr[i + 1] = (int32_t)connKf.size();
+        ordN[i] = (int32_t)rowKf[i].size();
+        rowCap = std::max(rowCap, rowKf[i].size());
+    }
+    for (typename ConnT::const_iterator c = LoopConnections.begin(); c != LoopConnections.end(); ++c) at(c->first);
+    const int loopSlot = at(pLoopKF), curSlot = at(pCurKF);
+    if (missing || n == 0) { lastStatus() = SLAMIT_ERR_ARG; return; }
+    std::vector<int32_t> ordKf((size_t)n * rowCap, -1), ordW((size_t)n * rowCap, 0);
+    for (int i = 0; i < n; ++i)
+        for (size_t j = 0; j < rowKf[i].size(); ++j) { ordKf[i * rowCap + j] = rowKf[i][j]; ordW[i * rowCap + j] = rowW[i][j]; }
+    slamit_eg_graph g;
+    memset(&g, 0, sizeof(g));
+    g.n_kf = n; g.row_cap = (int32_t)rowCap; g.loop_kf = loopSlot; g.cur_kf = curSlot; g.min_feat = 100;   // minFeat, :806
+    g.kf_bad = bad.data(); g.kf_id = id.data(); g.kf_parent = parent.data(); g.child_ptr = childPtr.data(); g.child_kf = childKf.data();
+    g.loop_ptr = loopPtr.data(); g.loop_kf_list = loopKf.data(); g.ord_kf = ordKf.data(); g.ord_w = ordW.data(); g.ord_n = ordN.data();
+    g.conn_ptr = connPtr.data(); g.conn_kf = connKf.data();
+    int32_t cap = (int32_t)(connKf.size() + loopKf.size() + n), ne = 0;
+    for (int i = 0; i < n; ++i) cap += ordN[i];
+    std::vector<int32_t> v0(cap + 1), v1(cap + 1), kind(cap + 1), incPtr(n + 1), incEdge(2 * (size_t)cap + 1);
+    if ((lastStatus() = slamit_essential_plan(&g, cap, v0.data(), v1.data(), kind.data(), &ne, incPtr.data(), incEdge.data())) != SLAMIT_OK) return;
+    // ---- the Sim3s (:809-844, :889-896): corrected / non-corrected where the maps have the keyframe, else (Rcw, tcw, 1) ----
+    std::vector<double> scwR(9 * (size_t)n), scwT(3 * (size_t)n), scwS(n), sncR(9 * (size_t)n), sncT(3 * (size_t)n), sncS(n);
+    for (int i = 0; i < n; ++i) {
+        KeyFrameT* k = kfs[i];
+        typename PoseMapT::const_iterator it = CorrectedSim3.find(k);
+        if (it != CorrectedSim3.end()) slamit_shim_sim3_get(it->second, &scwR[9 * i], &scwT[3 * i], scwS[i]);
+        else {
+            const cv::Mat R = k->GetRotation(), t = k->GetTranslation();
+            for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) scwR[9 * i + 3 * r + c] = (double)R.template at<float>(r, c); scwT[3 * i + r] = (double)t.template at<float>(r, 0); }
+            scwS[i] = 1.0;
+        }
+        typename PoseMapT::const_iterator in = NonCorrectedSim3.find(k);
+        if (in != NonCorrectedSim3.end()) slamit_shim_sim3_get(in->second, &sncR[9 * i], &sncT[3 * i], sncS[i]);
+        else { memcpy(&sncR[9 * i], &scwR[9 * i], 72); memcpy(&sncT[3 * i], &scwT[3 * i], 24); sncS[i] = scwS[i]; }
+    }
+    // ---- the points (:1013-1037) ----
+    const auto mps = pMap->GetAllMapPoints();
+    const int m = (int)mps.size();
+    std::vector<float> pos(3 * (size_t)m + 1, 0.f), outPos(3 * (size_t)m + 1);
+    std::vector<int32_t> ref(m + 1, -1), touched(m + 1);
+    std::vector<uint8_t> ptBad(m + 1, 1);
+    for (int p = 0; p < m; ++p) {
+        if (mps[p]->isBad()) continue;
+        ptBad[p] = 0;
+        if ((long)mps[p]->mnCorrectedByKF == (long)pCurKF->mnId) {
+            std::map<long, int>::const_iterator it = slotOfId.find((long)mps[p]->mnCorrectedReference);
+            ref[p] = it == slotOfId.end() ? -1 : it->second;
+        } else {
+            typename std::map<const KeyFrameT*, int>::const_iterator it = slot.find(mps[p]->GetReferenceKeyFrame());
+            ref[p] = it == slot.end() ? -1 : it->second;
+        }
+        const cv::Mat X = mps[p]->GetWorldPos();
+        for (int r = 0; r < 3; ++r) pos[3 * p + r] = X.template at<float>(r, 0);
+    }
+    slamit_eg_problem P;
+    memset(&P, 0, sizeof(P));
+    P.n_kf = n; P.n_edge = ne; P.n_pt = m; P.fix_scale = bFixScale ? 1 : 0; P.max_its = 20; P.lambda_init = 1e-16;   // :794, :987
+    P.scw_r = scwR.data(); P.scw_t = scwT.data(); P.scw_s = scwS.data(); P.snc_r = sncR.data(); P.snc_t = sncT.data(); P.snc_s = sncS.data();
+    P.fixed = fixed.data(); P.bad = bad.data(); P.edge_v0 = v0.data(); P.edge_v1 = v1.data(); P.edge_kind = kind.data();
+    P.inc_ptr = incPtr.data(); P.inc_edge = incEdge.data(); P.pt_pos = pos.data(); P.pt_ref = ref.data(); P.pt_bad = ptBad.data();
+    std::vector<double> oR(9 * (size_t)n), oT(3 * (size_t)n), oS(n), oPose(12 * (size_t)n);
+    int32_t nTouched = 0;
+    slamit_eg_result R;
+    memset(&R, 0, sizeof(R));
+    R.sim3_r = oR.data(); R.sim3_t = oT.data(); R.sim3_s = oS.data(); R.pose = oPose.data(); R.pt_pos = outPos.data(); R.touched = touched.data();
+    R.n_touched = &nTouched;
+    if ((lastStatus() = slamit_essential_graph(deviceRef(), &P, &R)) != SLAMIT_OK) return;
+    // ---- write back (:989-1043) ----
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+    for (int i = 0; i < n; ++i) {
+        if (bad[i]) continue;
+        cv::Mat T(4, 4, CV_32F);
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) T.template at<float>(r, c) = (float)oPose[12 * i + 3 * r + c];
+            T.template at<float>(r, 3) = (float)oPose[12 * i + 9 + r];
+            T.template at<float>(3, r) = 0.f;
+        }
+        T.template at<float>(3, 3) = 1.f;
+        kfs[i]->SetPose(T);
+    }
+    for (int j = 0; j < nTouched; ++j) {
+        const int p = touched[j];
+        cv::Mat X(3, 1, CV_32F);
+        for (int r = 0; r < 3; ++r) X.template at<float>(r, 0) = outPos[3 * p + r];
+        mps[p]->SetWorldPos(X);
+        mps[p]->UpdateNormalAndDepth();
+    }
 }
 
 template <class FrameT>

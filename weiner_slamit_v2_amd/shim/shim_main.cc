@@ -12,6 +12,7 @@
 //     shim_test bow <problem.bin> <out.bin>
 //     shim_test sim3 <problem.bin> <out.bin>
 //     shim_test osim3 <problem.bin> <out.bin>
+//     shim_test essential <problem.bin> <out.bin>
 //     shim_test sim3solver <problem.bin> <out.bin>
 //     shim_test pnpsolver <problem.bin> <out.bin>
 //     shim_test initializer <pairs.bin> <out.bin>
@@ -1819,6 +1820,101 @@ static int run_local_map(int argc, char** argv) {
     return failures ? 1 : 0;
 }
 
+// ---- Optimizer::OptimizeEssentialGraph through the class surface ----
+struct MockEgKF {
+    long unsigned int mnId; bool bad; cv::Mat R, t, pose; bool poseSet;
+    MockEgKF* parent; std::set<MockEgKF*> children, loopEdges; std::vector<MockEgKF*> ordered; std::vector<int> weights;
+    bool isBad() { return bad; }
+    cv::Mat GetRotation() { return R; }
+    cv::Mat GetTranslation() { return t; }
+    MockEgKF* GetParent() { return parent; }
+    std::set<MockEgKF*> GetChilds() { return children; }
+    std::set<MockEgKF*> GetLoopEdges() { return loopEdges; }
+    std::vector<MockEgKF*> GetVectorCovisibleKeyFrames() { return ordered; }
+    int GetWeight(MockEgKF* k) { for (size_t i = 0; i < ordered.size(); ++i) if (ordered[i] == k) return weights[i]; return 0; }
+    void SetPose(const cv::Mat& T) { pose = T.clone(); poseSet = true; }
+};
+struct MockEgPoint {
+    bool bad; cv::Mat pos; long unsigned int mnCorrectedByKF, mnCorrectedReference; MockEgKF* ref; int updated;
+    bool isBad() { return bad; }
+    cv::Mat GetWorldPos() { return pos.clone(); }
+    void SetWorldPos(const cv::Mat& X) { pos = X.clone(); }
+    MockEgKF* GetReferenceKeyFrame() { return ref; }
+    void UpdateNormalAndDepth() { ++updated; }
+};
+struct MockEgMap {
+    std::vector<MockEgKF*> kfs; std::vector<MockEgPoint*> pts; std::mutex mMutexMapUpdate;
+    std::vector<MockEgKF*> GetAllKeyFrames() { return std::vector<MockEgKF*>(kfs.rbegin(), kfs.rend()); }   // (no order promised)
+    std::vector<MockEgPoint*> GetAllMapPoints() { return pts; }
+};
+// problem.bin: int32 n m loop cur fix row_cap ; int32 bad[n] id[n] parent[n] ; CSRs as int32 ptr[n + 1] + values: children, loop edges,
+//   LoopConnections ; int32 ord_n[n] ord_kf[n row_cap] ord_w[n row_cap] ; double scw[13 n] snc[13 n] (R, t, s) ; int32 corrected[n] (the
+//   keyframe is a key of CorrectedSim3 / NonCorrectedSim3) ; float pos[3 m] ; int32 pt_bad[m] pt_ref[m] pt_by_cur[m]
+// out.bin: int32 status ; per keyframe int32 pose_set, float pose[12] (R row-major, t) ; per point float pos[3], int32 updated
+static int run_essential(int argc, char** argv) {
+    if (argc < 4) return 2;
+    std::vector<unsigned char> raw = slurp(argv[2]);
+    Reader Rd{raw.data()};
+    const int n = Rd.get<int>(), m = Rd.get<int>(), loop = Rd.get<int>(), cur = Rd.get<int>(), fix = Rd.get<int>(), cap = Rd.get<int>();
+    const int* bad = Rd.arr<int>(n); const int* id = Rd.arr<int>(n); const int* par = Rd.arr<int>(n);
+    const int* cp = Rd.arr<int>(n + 1); const int* ck = Rd.arr<int>(cp[n]);
+    const int* lp = Rd.arr<int>(n + 1); const int* lk = Rd.arr<int>(lp[n]);
+    const int* qp = Rd.arr<int>(n + 1); const int* qk = Rd.arr<int>(qp[n]);
+    const int* on = Rd.arr<int>(n); const int* okf = Rd.arr<int>((size_t)n * cap); const int* ow = Rd.arr<int>((size_t)n * cap);
+    const double* scw = Rd.arr<double>(13 * (size_t)n); const double* snc = Rd.arr<double>(13 * (size_t)n);
+    const int* corrected = Rd.arr<int>(n);
+    const float* pos = Rd.arr<float>(3 * (size_t)m); const int* pbad = Rd.arr<int>(m); const int* pref = Rd.arr<int>(m); const int* pcur = Rd.arr<int>(m);
+    std::vector<MockEgKF> K(n);
+    std::vector<MockEgPoint> Pt(m);
+    MockEgMap map;
+    std::map<MockEgKF*, MockSim3> NonCorrected, Corrected;
+    std::map<MockEgKF*, std::set<MockEgKF*> > Conn;
+    for (int i = 0; i < n; ++i) {
+        MockEgKF& k = K[i];
+        k.mnId = (long unsigned int)id[i]; k.bad = bad[i] != 0; k.poseSet = false; k.parent = par[i] >= 0 ? &K[par[i]] : (MockEgKF*)0;
+        const double* map_pose = snc + 13 * (size_t)i;   // the map's own pose: the non-corrected Sim3 (scale 1)
+        k.R = cv::Mat(3, 3, CV_32F); k.t = cv::Mat(3, 1, CV_32F);
+        for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) k.R.at<float>(r, c) = (float)map_pose[3 * r + c]; k.t.at<float>(r, 0) = (float)map_pose[9 + r]; }
+        for (int j = cp[i]; j < cp[i + 1]; ++j) k.children.insert(&K[ck[j]]);
+        for (int j = lp[i]; j < lp[i + 1]; ++j) k.loopEdges.insert(&K[lk[j]]);
+        for (int j = 0; j < on[i]; ++j) { k.ordered.push_back(&K[okf[(size_t)i * cap + j]]); k.weights.push_back(ow[(size_t)i * cap + j]); }
+        for (int j = qp[i]; j < qp[i + 1]; ++j) Conn[&k].insert(&K[qk[j]]);
+        if (corrected[i]) {
+            MockSim3 a, b;
+            memcpy(a.R, scw + 13 * (size_t)i, 72); memcpy(a.t, scw + 13 * (size_t)i + 9, 24); a.s = scw[13 * (size_t)i + 12];
+            memcpy(b.R, map_pose, 72); memcpy(b.t, map_pose + 9, 24); b.s = map_pose[12];
+            Corrected[&k] = a; NonCorrected[&k] = b;
+        }
+        map.kfs.push_back(&k);
+    }
+    for (int p = 0; p < m; ++p) {
+        MockEgPoint& q = Pt[p];
+        q.bad = pbad[p] != 0; q.pos = mat_from(pos + 3 * (size_t)p, 3); q.updated = 0; q.ref = 0;
+        q.mnCorrectedByKF = 0xFFFFFFFFul; q.mnCorrectedReference = 0;
+        if (pcur[p]) { q.mnCorrectedByKF = K[cur].mnId; q.mnCorrectedReference = K[pref[p]].mnId; q.ref = &K[loop]; }   // (the reference keyframe is then not read)
+        else q.ref = &K[pref[p]];
+        map.pts.push_back(&q);
+    }
+    const bool bFix = fix != 0;
+    Optimizer::OptimizeEssentialGraph(&map, &K[loop], &K[cur], NonCorrected, Corrected, Conn, bFix);
+    const int status = Optimizer::LastStatus();
+    if (status != 0) fprintf(stderr, "essential failed: %s\n", slamit_last_error());
+    FILE* f = fopen(argv[3], "wb");
+    fwrite(&status, 4, 1, f);
+    for (int i = 0; i < n; ++i) {
+        const int set = K[i].poseSet ? 1 : 0;
+        float T[12] = {0};
+        if (set) for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) T[3 * r + c] = K[i].pose.at<float>(r, c); T[9 + r] = K[i].pose.at<float>(r, 3); }
+        fwrite(&set, 4, 1, f); fwrite(T, 4, 12, f);
+    }
+    for (int p = 0; p < m; ++p) {
+        float X[3] = {Pt[p].pos.at<float>(0, 0), Pt[p].pos.at<float>(1, 0), Pt[p].pos.at<float>(2, 0)};
+        fwrite(X, 4, 3, f); fwrite(&Pt[p].updated, 4, 1, f);
+    }
+    fclose(f);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     std::string mode = argv[1];
@@ -1834,6 +1930,7 @@ int main(int argc, char** argv) {
     if (mode == "bow") return run_bow(argc, argv);
     if (mode == "sim3") return run_sim3(argc, argv);
     if (mode == "osim3") return run_osim3(argc, argv);
+    if (mode == "essential") return run_essential(argc, argv);
     if (mode == "sim3solver") return run_sim3solver(argc, argv);
     if (mode == "pnpsolver") return run_pnpsolver(argc, argv);
     if (mode == "initializer") return run_initializer(argc, argv);

@@ -1188,3 +1188,147 @@ def synth_rgbd(seed=0, n=300, width=64, height=48, kind="u16", factor=1.0 / 5000
     kps_un["y"] = (kps["y"] + rs.uniform(-1.5, 1.5, n).astype(f32)).astype(f32)
     return dict(n=n, storage=storage, plane=storage[:, :width], width=width, height=height, kind=kind, factor=f32(factor), mbf=f32(38.6),
                 kps=kps, kps_un=kps_un)
+
+
+def _rodrigues(w):
+    th = float(np.sqrt((w * w).sum()))
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]], np.float64)
+    if th < 1e-12:
+        return np.eye(3) + K
+    return np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / (th * th) * (K @ K)
+
+
+def synth_essential(n_kf=12, seed=0, drift=0.004, scale_drift=0.01, fix_scale=False, n_corrected=3, n_pt=60, mixed=False, chain=False,
+                    min_feat=100):
+    """A loop closure for Optimizer::OptimizeEssentialGraph (slamit_eg_graph + slamit_eg_problem without its edge list, which
+    slamit_essential_plan derives from the tables here).  n_kf keyframes on a ring (one camera per slot, looking along the tangent),
+    the map's poses drifted step by step (rotation noise `drift` rad, translation noise, and a scale that grows by `scale_drift` per
+    step unless fix_scale), float32-rounded and widened as Converter::toMatrix3d does.  The last keyframe is pCurKF, slot 0 pLoopKF:
+    CorrectedSim3 holds pCurKF (its true pose, at the drifted scale) and its n_corrected spanning-tree ancestors (propagated as
+    LoopClosing::CorrectLoop does, Sic * CorrectedScw), NonCorrectedSim3 their map poses.  Spanning tree: slot i's parent is i - 1;
+    covisibility rows: the neighbours at distance 1, 2, 3 along the ring with weights around min_feat; LoopConnections: the
+    corrected keyframes to the first slots.  chain=True leaves only the tree and the one (cur, loop) connection: the ceiling's graph.
+
+    mixed=True adds what eg_mixed40 covers: a bad keyframe (a slot without a vertex), mnIds that are not the slots' order, an old loop
+    edge, a spanning-tree edge beside a LoopConnections edge of the same pair, covisibility pairs that LoopConnections inserted
+    first, a row whose weights are all >= min_feat (GetCovisiblesByWeight returns nothing for it), and points whose
+    mnCorrectedByKF is pCurKF (their reference slot is then a corrected keyframe's)."""
+    rs = np.random.RandomState(0xE55E + 7919 * seed + n_kf)
+    n = int(n_kf)
+    cur, loop = n - 1, 0
+    T = []
+    for i in range(n):
+        a = 2 * np.pi * i / n
+        Rwc = _rodrigues(np.array([0.0, 0.0, a])) @ _rodrigues(np.array([0.1 * np.sin(3 * a), 0.0, 0.0]))
+        C = np.array([5 * np.cos(a), 5 * np.sin(a), 0.3 * np.sin(2 * a)])
+        R = Rwc.T
+        T.append((R, -R @ C))
+    Td = [T[0]]
+    sc = 1.0
+    for i in range(1, n):
+        Rrel = T[i][0] @ T[i - 1][0].T
+        trel = T[i][1] - Rrel @ T[i - 1][1]
+        if not fix_scale:
+            sc *= 1.0 + scale_drift
+        Rrel = _rodrigues(rs.normal(0, drift, 3)) @ Rrel
+        trel = sc * trel + rs.normal(0, drift, 3)
+        Td.append((Rrel @ Td[-1][0], Rrel @ Td[-1][1] + trel))
+    f32 = lambda x: np.asarray(x, np.float32).astype(np.float64)
+    scw_r = np.stack([f32(R).reshape(9) for R, _ in Td])
+    scw_t = np.stack([f32(t) for _, t in Td])
+    scw_s = np.ones(n)
+    snc_r, snc_t, snc_s = scw_r.copy(), scw_t.copy(), scw_s.copy()
+    s_c = sc   # the map near pCurKF has grown by sc: Scw = (R, sc t, sc) takes a loop-side point into its units
+    Rc, tc = T[cur][0], T[cur][1]
+    corrected = [cur - k for k in range(min(n_corrected, n - 2) + 1)]
+    for i in corrected:   # Sic = Tiw * Twc (map poses), CorrectedSiw = Sic * CorrectedScw (LoopClosing.cc:447-460)
+        Ri, ti = scw_r[i].reshape(3, 3), scw_t[i]
+        Rcm, tcm = scw_r[cur].reshape(3, 3), scw_t[cur]
+        Ric = Ri @ Rcm.T
+        tic = ti - Ric @ tcm
+        scw_r[i] = (Ric @ Rc).reshape(9)
+        scw_t[i] = Ric @ (s_c * tc) + tic   # the Sim3 product with s_ic = 1: t = R_ic t_c + t_ic, s = s_c
+        scw_s[i] = s_c
+    kf_id = np.arange(n, dtype=np.int32)
+    kf_bad = np.zeros(n, np.uint8)
+    parent = np.arange(-1, n - 1, dtype=np.int32)
+    loop_edges = [[] for _ in range(n)]
+    covis = [dict() for _ in range(n)]
+    if not chain:
+        for i in range(n):
+            for d, w in ((1, 2 * min_feat + 37), (2, min_feat + 20), (3, min_feat - 25)):
+                for j in (i - d, i + d):
+                    if 0 <= j < n:
+                        covis[i][j] = w + int((i + j) % 5)
+    conn = {}
+    if chain:
+        conn[cur] = [loop]
+    else:
+        for i in corrected[:3]:
+            conn[i] = [j for j in (loop, loop + 1, loop + 2) if j < corrected[-1] - 1]
+        for i in conn:
+            for j in conn[i]:
+                w = min_feat + 30 if (i + j) % 2 == 0 or (i == cur and j == loop) else min_feat - 40
+                if i == cur and j == loop:
+                    w = min_feat - 10   # the pair that is exempt from the weight gate
+                covis[i][j] = covis[j][i] = w
+    if mixed:
+        assert n >= 24
+        kf_bad[n // 2] = 1
+        kf_id = (3 * np.arange(n) + 5).astype(np.int32)
+        kf_id[[7, 8]] = kf_id[[8, 7]]                      # mnId order differs from slot order
+        parent[n // 2 + 1] = n // 2 - 1                    # the bad keyframe's child was re-parented (SetBadFlag)
+        parent[8], parent[7] = 6, 8                        # the parent has the smaller mnId
+        for j in list(covis[n // 2]):
+            covis[j].pop(n // 2, None)
+        covis[n // 2] = {}
+        loop_edges[n - 10].append(4)                       # an old loop: n - 10 <-> 4
+        loop_edges[4].append(n - 10)
+        covis[n - 10][4] = covis[4][n - 10] = min_feat + 50  # ... which also see each other (excluded by sLoopEdges.count)
+        parent[cur - 1] = loop + 1                         # a tree edge beside the LoopConnections edge of the same pair
+        conn.setdefault(cur - 1, [])
+        if loop + 1 not in conn[cur - 1]:
+            conn[cur - 1].append(loop + 1)
+        covis[cur - 1][loop + 1] = covis[loop + 1][cur - 1] = min_feat + 60
+        covis[15] = {j: w + min_feat for j, w in covis[15].items()}   # no weight below min_feat: the row yields nothing
+    children = [[] for _ in range(n)]
+    for i in range(n):
+        if parent[i] >= 0 and not kf_bad[i]:
+            children[parent[i]].append(i)
+    row_cap = max(1, max(len(c) for c in covis))
+    ord_kf = -np.ones((n, row_cap), np.int32)
+    ord_w = np.zeros((n, row_cap), np.int32)
+    ord_n = np.zeros(n, np.int32)
+    for i in range(n):
+        row = sorted(covis[i].items(), key=lambda jw: (-jw[1], jw[0]))
+        ord_n[i] = len(row)
+        for k, (j, w) in enumerate(row):
+            ord_kf[i, k], ord_w[i, k] = j, w
+
+    def csr(rows):
+        ptr = np.zeros(n + 1, np.int32)
+        flat = []
+        for i in range(n):
+            flat += sorted(rows[i])
+            ptr[i + 1] = len(flat)
+        return ptr, np.array(flat, np.int32).reshape(-1)
+
+    child_ptr, child_kf = csr(children)
+    loop_ptr, loop_list = csr(loop_edges)
+    conn_ptr, conn_kf = csr([conn.get(i, []) for i in range(n)])
+    fixed = np.zeros(n, np.uint8)
+    fixed[loop] = 1
+    good_kf = np.flatnonzero(kf_bad == 0)
+    pt_ref = good_kf[rs.randint(0, len(good_kf), n_pt)].astype(np.int32)
+    if mixed:
+        pt_ref[: n_pt // 4] = np.array(corrected, np.int32)[rs.randint(0, len(corrected), n_pt // 4)]   # mnCorrectedByKF == pCurKF
+    pt_pos = np.zeros((n_pt, 3), np.float32)
+    for p in range(n_pt):   # a few metres in front of the reference keyframe, in the MAP's (drifted) frame
+        R, t = Td[pt_ref[p]]
+        pt_pos[p] = (R.T @ (np.array([rs.uniform(-1, 1), rs.uniform(-1, 1), rs.uniform(2, 6)]) - t)).astype(np.float32)
+    pt_bad = (rs.uniform(size=n_pt) < 0.1).astype(np.uint8)
+    return dict(n_kf=n, row_cap=row_cap, loop_kf=loop, cur_kf=cur, min_feat=min_feat, kf_bad=kf_bad, kf_id=kf_id, kf_parent=parent,
+                child_ptr=child_ptr, child_kf=child_kf, loop_ptr=loop_ptr, loop_kf_list=loop_list, ord_kf=ord_kf, ord_w=ord_w,
+                ord_n=ord_n, conn_ptr=conn_ptr, conn_kf=conn_kf,
+                scw_r=scw_r, scw_t=scw_t, scw_s=scw_s, snc_r=snc_r, snc_t=snc_t, snc_s=snc_s, fixed=fixed, bad=kf_bad.copy(),
+                fix_scale=int(bool(fix_scale)), max_its=20, lambda_init=1e-16, pt_pos=pt_pos, pt_ref=pt_ref, pt_bad=pt_bad)
