@@ -2160,7 +2160,8 @@ int slamit_essential_plan(const slamit_eg_graph* g, int32_t edge_cap, int32_t* e
  * are summed edge by edge in list order, chi2 and the gain ratio's scale in a fixed order: two runs give identical bits.  A zero or
  * non-finite pivot fails the trial as SimplicialLDLT's NumericalIssue does (its cost counts as DBL_MAX; the state is not moved, where
  * g2o would apply the previous trial's x before undoing it).  The verdict of every trial is read back by the host (one 8-byte copy
- * and a stream wait per trial): the calls return when the result is complete.
+ * and a stream wait per trial): the calls return when the result is complete.  lambda_init is taken literally: 0 (or less) is not
+ * "choose for me" as g2o's setUserLambdaInit(0) is, it is the damping of the first trial, and a trial that fails leaves 0 at 0.
  *
  * A keyframe that is fixed or bad keeps its Scw; its pose is still written from it.  A bad point keeps its position and is not listed
  * in `touched`; `touched` holds the good points ascending, in the layout slamit_points_batch_rec.d_points / d_n read (one item,
@@ -2180,7 +2181,7 @@ struct slamit_eg_problem {
                                         indexes by them).  Host form: ignored. */
     int32_t fix_scale;               /* bFixScale */
     int32_t max_its;                 /* 20 */
-    double lambda_init;              /* 1e-16 */
+    double lambda_init;              /* 1e-16; used as given, 0 included (see Numerics) */
     const double* scw_r;             /* [n_kf][9] CorrectedSim3 where it has the keyframe, else (Rcw, tcw, 1): r row-major, */
     const double* scw_t;             /* [n_kf][3]   t, */
     const double* scw_s;             /* [n_kf]      s, as slamit_sim3_problem states a Sim3 */

@@ -119,6 +119,15 @@ def _abc(sigma, s, theta, small_theta):
     return A, B, C
 
 
+# the two small-angle tests, named so that tests/test_sim3_probes_ref.py can swap them: exp asks theta, log asks d = (tr R - 1) / 2
+def exp_small(theta):
+    return theta < 0.00001
+
+
+def log_small(d, theta):
+    return d > 1 - 0.00001
+
+
 def sim3_exp(u):
     """Sim3(const Vector7d& update), sim3.h:70-142."""
     u = np.asarray(u, np.float64)
@@ -127,7 +136,7 @@ def sim3_exp(u):
     O = skew(omega)
     O2 = O @ O
     s = np.exp(sigma)
-    small = theta < 0.00001
+    small = exp_small(theta)
     A, B, C = _abc(sigma, s, theta, small)
     I = np.eye(3)
     with np.errstate(invalid="ignore", divide="ignore"):
@@ -145,9 +154,9 @@ def sim3_log(a):
     R = q2R(q)
     d = 0.5 * (R[..., 0, 0] + R[..., 1, 1] + R[..., 2, 2] - 1)
     dR = np.stack([R[..., 2, 1] - R[..., 1, 2], R[..., 0, 2] - R[..., 2, 0], R[..., 1, 0] - R[..., 0, 1]], -1)
-    small = d > 1 - 0.00001
     with np.errstate(invalid="ignore", divide="ignore"):
         theta = np.arccos(d)
+        small = log_small(d, theta)
         k = np.where(small, 0.5, theta / (2 * np.sqrt(1 - d * d)))
     omega = k[..., None] * dR
     A, B, C = _abc(sigma, s, theta, small)
@@ -225,7 +234,7 @@ def optimize(prob, record=None):
     scw = from_rts(prob["scw_r"], prob["scw_t"], prob["scw_s"])
     est = (scw[0].copy(), scw[1].copy(), scw[2].copy())
     meas = measurements(prob) if E else None
-    lam, ni, nbad = float(prob["lambda_init"]), 2.0, 0
+    lam, ni, nbad, chi2_init = float(prob["lambda_init"]), 2.0, 0, 0.0
     its_chi2, its_lambda, its_trials, t_rho, t_chi2, t_lambda = [], [], [], [], [], []
 
     def chi2_of(e):
@@ -240,6 +249,8 @@ def optimize(prob, record=None):
         e = edge_errors(meas, est, v0, v1)
         cur = chi2_of(e)
         ini = cur
+        if it == 0:
+            chi2_init = cur
         J0, J1 = linearize(meas, est, v0, v1, fix_scale)
         H, b = np.zeros((N, N)), np.zeros(N)
         for k in range(E):   # constructQuadraticForm, edge by edge in list order
@@ -298,7 +309,7 @@ def optimize(prob, record=None):
         if nbad >= 3:
             break
     out = recover(prob, est)
-    out.update(n_its=len(its_chi2), chi2=np.array(its_chi2), lam=np.array(its_lambda), trials=np.array(its_trials, np.int32),
+    out.update(n_its=len(its_chi2), chi2_init=chi2_init, chi2=np.array(its_chi2), lam=np.array(its_lambda), trials=np.array(its_trials, np.int32),
                trial_rho=np.array(t_rho), trial_chi2=np.array(t_chi2), trial_lambda=np.array(t_lambda))
     return out
 

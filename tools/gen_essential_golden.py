@@ -8,6 +8,9 @@ slamit_essential_plan derives), the reference's corrected Sim3s, poses and point
 rho.  The generator asserts that every trial's |rho| exceeds 1e-6 (the accept / reject path cannot flip on rounding) and that no
 linear solve failed.
 
+Also tests/golden/sim3probe_<family>.npz (PROBES): synth.synth_sim3_probes problems, whose edge list is their own (no plan), with the
+same contents and the same assertions, and one more: the single iteration of every family ends in an accepted trial.
+
     python tools/gen_essential_golden.py [case prefix ...]
 """
 import ctypes as C
@@ -49,6 +52,11 @@ CASES = {  # name: synth.synth_essential arguments
     "eg_rough30": dict(n_kf=30, seed=27, drift=0.03, scale_drift=0.02, lambda_init=1.0),
     "eg_panels75": dict(n_kf=75, seed=8, n_pt=100, drift=0.001, scale_drift=0.002),                      # 518 unknowns: 17 panels, not a multiple of 16
 }
+
+
+# tests/golden/sim3probe_<family>.npz: synth.synth_sim3_probes problems (48 disjoint pairs, one iteration; the edge list is the
+# problem's own, no plan).  The families and what each isolates: tests/sim3_probe_checks.py.
+PROBES = {"sim3probe_" + family: dict(family=family) for family in synth.SIM3_PROBE_FAMILIES}
 
 
 def build_harness():
@@ -98,6 +106,17 @@ def main():
                             **{"ref_" + k: v for k, v in r.items() if k != "trial_failed"})
         print(name, "edges", len(pr["edge_v0"]), "its", r["n_its"], "trials", list(r["trials"]), "chi2 %.6g -> %.6g" % (r["chi2_init"], r["chi2"][-1] if r["n_its"] else 0),
               "rejects", int((r["trial_rho"] <= 0).sum()))
+    for name, kw in PROBES.items():
+        if only and not any(name.startswith(o) for o in only):
+            continue
+        pr = synth.synth_sim3_probes(**kw)
+        r = ref_solve(L, pr)
+        assert not r["trial_failed"].any(), "%s: a linear solve failed" % name
+        assert np.all(np.abs(r["trial_rho"]) > 1e-6), "%s: a gain ratio within 1e-6 of zero: %s" % (name, r["trial_rho"])
+        assert r["n_its"] == 1 and r["trial_rho"][-1] > 0, "%s: the iteration does not end in an accepted trial: %s" % (name, r["trial_rho"])
+        np.savez_compressed(os.path.join(ROOT, "tests", "golden", name + ".npz"), **pr,
+                            **{"ref_" + k: v for k, v in r.items() if k != "trial_failed"})
+        print(name, "trials", list(r["trials"]), "rho", list(r["trial_rho"]), "chi2 %.6g -> %.6g" % (r["chi2_init"], r["chi2"][-1]))
 
 
 if __name__ == "__main__":

@@ -1332,3 +1332,126 @@ def synth_essential(n_kf=12, seed=0, drift=0.004, scale_drift=0.01, fix_scale=Fa
                 ord_n=ord_n, conn_ptr=conn_ptr, conn_kf=conn_kf,
                 scw_r=scw_r, scw_t=scw_t, scw_s=scw_s, snc_r=snc_r, snc_t=snc_t, snc_s=snc_s, fixed=fixed, bad=kf_bad.copy(),
                 fix_scale=int(bool(fix_scale)), max_its=20, lambda_init=1e-16, pt_pos=pt_pos, pt_ref=pt_ref, pt_bad=pt_bad)
+
+
+SIM3_PROBE_FAMILIES = ("gn", "damped", "fixscale", "noturn", "edges", "twoedge")
+
+
+def synth_sim3_probes(family, n_pairs=48, seed=0):
+    """A slamit_eg_problem (edge list included, written by hand: no planner) that probes the Sim3 algebra of the essential-graph
+    optimisation branch by branch.  n_pairs disjoint pairs: keyframe 2p is fixed, 2p + 1 free, one NORMAL edge (2p, 2p + 1), so the
+    system is block diagonal and the error of pair p, log(Snc_j Snc_i^-1 Scw_i Scw_j^-1), is set freely: Snc_i = Scw_i, and
+    Snc_j = D Scw_j with D = (R(theta axis), t, exp(sigma)) the pair's relative error.  Rotations and translations are float32-rounded
+    and widened as in synth_essential (so a stated theta holds to about 1e-7 rad); scales stay doubles (sigma = 0 is exact).
+
+    Absolute orientations cycle over four kinds, which select the four branches of Quaterniond(R): generic (trace > 0), and within
+    0.05 rad of pi about x, about y, about z.  Every keyframe is the reference of one good point; one bad point is appended.
+
+    family: `damped` (theta 0.3 .. 2.5 rad about random axes, sigma +-(0.2 .. 1), a translation error of 0.4 .. 1.2 units, keyframes
+    within a unit of the origin; lambda_init 1), `gn` (the same pairs with the angles mapped into 0.3 .. 1.5, lambda_init 1e-16),
+    `fixscale` (theta 0.3 .. 2.0, every scale 1, fix_scale; every other edge is (2p + 1, 2p), the free keyframe first), `noturn` (rotation error identity or 3e-6 / 9e-6 rad, sigma +-(0.2 .. 1), a
+    third of the pairs with sigma = 0: pure translation, 1 .. 3 units), `edges` (theta in {0.9e-5, 1.1e-5, 4.4e-3, 4.6e-3} x sigma in
+    {+-0.9e-5, +-1.1e-5, 0.3}: both sides of every threshold of exp and log), `twoedge` (noturn's rotations with sigma +-(0.2 .. 1)
+    on every pair, and per pair a second fixed keyframe 2 n_pairs + p with a second edge to the free one that turns by 0.3 .. 1.5 rad:
+    144 keyframes, 96 edges, still block diagonal).  max_its 1.  The sizes are the largest at which the
+    reference's g2o and the numpy restatement still agree to 1e-6 (tests/sim3_probe_checks.PROBE_WORST)."""
+    assert family in SIM3_PROBE_FAMILIES
+    P = int(n_pairs)
+    n = 2 * P
+    rs = np.random.RandomState(0x51B3 + 101 * seed)   # the same stream for every family: gn and damped are the same pairs
+    f32 = lambda x: np.asarray(x, np.float32).astype(np.float64)
+
+    def unit(rs=rs):
+        v = rs.normal(size=3)
+        return v / np.sqrt((v * v).sum())
+
+    flips = (None, np.diag([1.0, -1.0, -1.0]), np.diag([-1.0, 1.0, -1.0]), np.diag([-1.0, -1.0, 1.0]))
+
+    def orientation(kind, rs=rs):
+        if kind == 0:
+            return _rodrigues(unit(rs) * rs.uniform(0.2, 1.8))   # below 2 pi / 3: trace > 0
+        return flips[kind] @ _rodrigues(unit(rs) * rs.uniform(0.005, 0.05))
+
+    kind_i, kind_j = rs.permutation(np.arange(P) % 4), rs.permutation(np.arange(P) % 4)
+    Ri = [orientation(k) for k in kind_i]
+    Rj = [orientation(k) for k in kind_j]
+    ti, tj = rs.uniform(-1, 1, (P, 3)), rs.uniform(-1, 1, (P, 3))
+    axis = np.stack([unit() for _ in range(P)])
+    theta = rs.uniform(0.3, 2.5, P)
+    sign = np.where(rs.uniform(size=P) < 0.5, -1.0, 1.0)
+    sigma = sign * rs.uniform(0.2, 1.0, P)
+    td = np.stack([unit() for _ in range(P)]) * rs.uniform(0.4, 1.2, P)[:, None]
+    fix_scale, lambda_init = 0, 1.0
+    p = np.arange(P)
+    if family == "gn":
+        # the undamped step carries the noise of the 1e-9 differences in full, in proportion to the error's size: beyond 1.5 rad the
+        # reference's g2o and the numpy restatement land more than 1e-6 apart (2.1e-6 at 2.5 rad), so gn maps the angles into 0.3 .. 1.5
+        lambda_init, theta = 1e-16, 0.3 + (theta - 0.3) * (1.2 / 2.2)
+    elif family == "fixscale":
+        # (angles into 0.3 .. 2.0: a reversed pair's translation error is the larger one, and with it beyond 2 rad the reference and the
+        # restatement part by 2e-6)
+        sigma, fix_scale, theta = np.zeros(P), 1, 0.3 + (theta - 0.3) * (1.7 / 2.2)
+    elif family == "noturn":
+        theta = np.array([0.0, 3e-6, 9e-6])[p % 3]
+        sigma = np.where((p // 3) % 3 == 2, 0.0, sigma)
+        td = 2.5 * td   # 1 .. 3 units: with W = C I the translation is all these pairs have, and they stay well conditioned
+    elif family == "twoedge":
+        theta, td = np.array([0.0, 3e-6, 9e-6])[p % 3], 2.5 * td
+    elif family == "edges":
+        c = p % 20
+        theta = np.array([0.9e-5, 1.1e-5, 4.4e-3, 4.6e-3])[c % 4]
+        sigma = np.array([0.9e-5, -0.9e-5, 1.1e-5, -1.1e-5, 0.3])[c // 4]
+        # |sigma| just above the threshold with a small theta takes sim3.h's B = (sigma^2 / 2 - sigma + 1) s / sigma^3, which lacks the
+        # series' "- 1": 7.5e14 at 1.1e-5, so W = C + A O + B O^2 has a condition of 1e5 .. 1e10 at these thetas and any translation
+        # makes the reference's own 1e-9 differences rounding noise.  Those pairs carry an error without translation, exactly.
+        still = np.abs(np.abs(sigma) - 1.1e-5) < 1e-12
+        td[still], tj[still] = 0.0, 0.0
+    scw_r, scw_t, scw_s = np.zeros((n, 9)), np.zeros((n, 3)), np.ones(n)
+    for q in range(P):
+        scw_r[2 * q], scw_r[2 * q + 1] = f32(Ri[q]).reshape(9), f32(Rj[q]).reshape(9)
+        scw_t[2 * q], scw_t[2 * q + 1] = f32(ti[q]), f32(tj[q])
+    snc_r, snc_t, snc_s = scw_r.copy(), scw_t.copy(), scw_s.copy()
+    for q in range(P):
+        j = 2 * q + 1
+        sd = float(np.exp(sigma[q]))
+        if theta[q] != 0.0:
+            Rd = _rodrigues(axis[q] * theta[q])
+            snc_r[j] = f32(Rd @ Rj[q]).reshape(9)
+        else:
+            Rd = np.eye(3)   # (the rotation kept bit for bit: the error's rotation is the identity)
+        snc_t[j] = f32(sd * (Rd @ scw_t[j]) + td[q])
+        snc_s[j] = sd * scw_s[j]
+    fixed = np.zeros(n, np.uint8)
+    fixed[0::2] = 1
+    v0, v1 = 2 * p, 2 * p + 1
+    if family == "fixscale":
+        # every other pair reversed, the free keyframe as vertex 0: a scale perturbation of vertex 1 leaves the translation of an error
+        # with sigma = 0 alone, so nothing there couples into coordinate 6 and a fix_scale that is not honoured would go unseen
+        v0, v1 = np.where(p % 2 == 1, v1, v0), np.where(p % 2 == 1, v0, v1)
+    if family == "twoedge":
+        # a second fixed keyframe n + p per pair and a second edge (n + p, 2 p + 1): Scw_k = Snc_k G with G a rotation by 0.3 .. 1.5 rad
+        # and a short translation, so its error is Snc_j (Snc_k^-1 Scw_k) Scw_j^-1 = D Scw_j G Scw_j^-1, which turns by G's angle.  The
+        # first edge's small-theta coefficients then stand in the free keyframe's H beside a gradient that is not small.  (A single edge
+        # cannot show A10 to first order: its cost holds A only as A^2 theta^2, theta < 4.5e-3.)
+        rs2 = np.random.RandomState(0x2ED6 + 101 * seed)   # its own stream: the pairs stay those of the other families
+        Rk = [orientation(k, rs2) for k in rs2.permutation(np.arange(P) % 4)]
+        Rg = [_rodrigues(unit(rs2) * a) for a in rs2.uniform(0.3, 1.5, P)]
+        tg = np.stack([unit(rs2) for _ in range(P)]) * rs2.uniform(0.1, 0.3, P)[:, None]
+        tk = rs2.uniform(-1, 1, (P, 3))
+        kr, kt = np.stack([f32(R).reshape(9) for R in Rk]), f32(tk)
+        scw_r, snc_r = np.concatenate([scw_r, np.stack([f32(Rk[q] @ Rg[q]).reshape(9) for q in range(P)])]), np.concatenate([snc_r, kr])
+        scw_t, snc_t = np.concatenate([scw_t, f32(np.stack([Rk[q] @ tg[q] for q in range(P)]) + kt)]), np.concatenate([snc_t, kt])
+        scw_s, snc_s = np.concatenate([scw_s, np.ones(P)]), np.concatenate([snc_s, np.ones(P)])
+        fixed = np.concatenate([fixed, np.ones(P, np.uint8)])
+        v0, v1 = np.concatenate([v0, n + p]), np.concatenate([v1, 2 * p + 1])
+        n += P
+    pt_ref = np.concatenate([np.arange(n), [1]]).astype(np.int32)
+    pt_pos = np.zeros((n + 1, 3), np.float32)
+    for k in range(n + 1):   # a few metres in front of the reference keyframe
+        R, t = scw_r[pt_ref[k]].reshape(3, 3), scw_t[pt_ref[k]]
+        pt_pos[k] = (R.T @ (np.array([rs.uniform(-1, 1), rs.uniform(-1, 1), rs.uniform(2, 6)]) - t)).astype(np.float32)
+    pt_bad = np.zeros(n + 1, np.uint8)
+    pt_bad[n] = 1
+    return dict(n_kf=n, scw_r=scw_r, scw_t=scw_t, scw_s=scw_s, snc_r=snc_r, snc_t=snc_t, snc_s=snc_s, fixed=fixed, bad=np.zeros(n, np.uint8),
+                edge_v0=v0.astype(np.int32), edge_v1=v1.astype(np.int32), edge_kind=np.zeros(len(v0), np.int32),
+                fix_scale=fix_scale, max_its=1, lambda_init=lambda_init, pt_pos=pt_pos, pt_ref=pt_ref, pt_bad=pt_bad)
