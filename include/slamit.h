@@ -1718,7 +1718,7 @@ int slamit_map_point_culling_batch_dev(int device, const slamit_point_culling_ba
  * PLACE: obs_ptr_out .. obs_weight_out are a packed CSR with ascending pointers from 0 that every reader of slamit_map_index takes
  * unchanged (a caller alternates two buffer sets); a new row is the old row's order with erased entries closed up and added ones
  * appended in list order.  mp_bad, mp_nobs, mp_ref_kf and kf_mp are rewritten IN PLACE.  MapPoint::Replace and KeyFrame::SetBadFlag's
- * spanning-tree walk are not here; appending a new keyframe's kf_mp row and Map::EraseMapPoint stay the caller's.
+ * spanning-tree walk are not here; appending a new keyframe's kf_mp row is slamit_map_grow_batch_dev's; Map::EraseMapPoint stays the caller's.
  * COST: as for the local map, the host form is for parity and tests; the gain is the resident form.
  * Kinds, flags, status bits (per point; BAD_SLOT and TABLE_OVERFLOW also per call) and ceilings: */
 #define SLAMIT_EDIT_ADD_OBS 1
@@ -2102,6 +2102,148 @@ struct slamit_kf_erase_batch_rec {
 typedef struct slamit_kf_erase_batch_rec slamit_kf_erase_batch_rec;
 size_t slamit_kf_erase_workspace(int n_maps, int cap, int kf_cap, int row_cap, int child_cap);
 int slamit_kf_erase_batch_dev(int device, const slamit_kf_erase_batch_rec* batch, void* stream);
+
+/* ---- Map growth on the resident tables: new keyframes, new map points, the association loop of ProcessNewKeyFrame ----
+ * KeyFrame::KeyFrame(Frame&, ...) with Map::AddKeyFrame, MapPoint::MapPoint(Pos, pRefKF, pMap) with its AddObservation / AddMapPoint /
+ * Map::AddMapPoint (src/LocalMapping.cc:486-500, src/Tracking.cc:1376-1383, :718-723, :875-891) and the loop of
+ * LocalMapping::ProcessNewKeyFrame (:156-175), appended IN PLACE to tables that have room (csrc/map_grow.h states the walk; DESIGN.md
+ * §33).  A list of ops is applied AS IF SEQUENTIALLY IN LIST ORDER; the result equals the sequential walk exactly.  Every id is a slot.
+ *   SLAMIT_GROW_NEW_KF     kf = the next free slot (n_kf + the NEW_KF ops applied before it), src = a frame record, kf_id = mnId (carried,
+ *                          not stored).  Appends kf_mp_ptr[kf + 1], the kf_mp row as mvpMapPoints is copied (bad points stay), kf_octave,
+ *                          kf_desc, kf_depth (-1 from a source without depth), kf_bad = 0, kf_parent = -1, kf_to_be_erased = 0,
+ *                          kf_not_erase = 0, kf_th_depth, a kf_best row of -1, cw_n = ord_n = 0, kf_child_ptr[kf + 1] = kf_child_ptr[kf] and
+ *                          kf_center = -Rcw^T tcw in float, each component ((R0j t0 + R1j t1) + R2j t2) negated (OpenCV's own evaluation
+ *                          of that line is unpinned, as for the upkeep calls).
+ *   SLAMIT_GROW_NEW_POINT  kf = ref, kf_id = first_kf_id, observers (kf_a, idx_a, weight_a) and (kf_b, idx_b, weight_b), kf_b = -1 for the
+ *                          one-observer stereo point.  The point exists iff cand == -1 (position pos) or d_cand_status[cand] == 0
+ *                          (position d_cand_x3d[3 cand ..], the layout of slamit_triangulate_result), so the list can be written before
+ *                          the triangulation's verdicts exist; otherwise SLAMIT_GROW_OP_REJECTED.  Accepted points take slots n_mp, n_mp +
+ *                          1, ... in list order with mp_pos, mp_normal = 0, both distances 0, mp_bad = 0, mp_nobs = 0, mp_ref_kf = ref,
+ *                          mp_found = mp_visible = 1, mp_first_kf, mp_replaced = -1, mp_desc = 0 and an empty row of obs_ptr.  For a then
+ *                          b: kf_mp[kf][idx] = the slot, unconditional (the last op of the list that names an entry wins), and one
+ *                          SLAMIT_EDIT_ADD_OBS edit without MATCH is EMITTED into `edits` (octave from kf_octave).  SLAMIT_GROW_RECENT
+ *                          appends the slot to the recent list (CreateNewMapPoints sets it, Tracking's stereo points do not).
+ *   SLAMIT_GROW_ASSOCIATE  kf, src (its row has src's n_kp entries).  Over kf_mp[kf] as the ops before left it, in keypoint order: -1 and
+ *                          bad points are skipped; a point for which IsInKeyFrame(kf) holds at that moment -- its row of the table the
+ *                          call was given holds kf, or an ADD_OBS(p, kf) was emitted earlier in this call -- goes to the recent list; any
+ *                          other emits ADD_OBS(p, kf, i, kf_octave, 2 where src.uright[i] >= 0 else 1).
+ * The point side of every observation is the emitted list handed to slamit_map_edit_batch_dev as the next call on the stream (cap =
+ * edit_cap, d_n = d_n_edits_out); its `touched` are the points UpdateNormalAndDepth / ComputeDistinctiveDescriptors is due for.  The
+ * call READS THE TABLES AS THEY ARE: edits emitted by an earlier grow call must have been applied (and the edit index swapped) before a
+ * call that depends on them.  UpdateConnections and SET_PARENT are the existing calls.
+ * THE INERT TAIL: of the P NEW_POINT ops of a list A are accepted (d_n_new); slots n_mp + A .. n_mp + P - 1 become mp_bad = 1, mp_nobs =
+ * 0, mp_ref_kf = mp_replaced = -1, empty rows, everything else 0, so records with n_kf + the NEW_KF ops and n_mp + P are valid at once,
+ * without a host visit; a caller that later reads A may shrink to n_mp + A.  The call moves no record's n_kf / n_mp: the caller does.
+ * ONE GATE per map, decided before anything is written, from the list and the frame records alone (upper bounds): kf_cap against n_kf +
+ * the NEW_KF ops; mp_cap against n_mp + P; kfmp_cap against kf_mp_ptr[n_kf] + their n_kp; edit_cap against 2 P + the n_kp of the
+ * ASSOCIATE ops; recent_cap against n_recent + the RECENT ops + that sum.  A map that fails one, names a frame record above
+ * SLAMIT_FRAME_MAX_KP or has d_n above cap gets d_need and a status bit per failure and NOTHING else; its neighbours are written.
+ * Not here: slot recycling and Map::EraseMapPoint, the temporal points of UpdateLastFrame, KeyFrameDatabase::add (slamit_kfdb_add_dev),
+ * ComputeBoW (slamit_voc_transform_batch_dev).  Kinds, flag, op codes, status bits per map and ceilings: */
+#define SLAMIT_GROW_NEW_KF 1
+#define SLAMIT_GROW_NEW_POINT 2
+#define SLAMIT_GROW_ASSOCIATE 3
+#define SLAMIT_GROW_RECENT 1               /* flags of a NEW_POINT op */
+#define SLAMIT_GROW_OP_REJECTED (-1)       /* d_op_status: the candidate's status was not 0 */
+#define SLAMIT_GROW_OP_BAD (-2)            /* d_op_status: a slot, index, weight, kind or frame record outside its range: skipped whole, never dereferenced */
+#define SLAMIT_GROW_KF_OVERFLOW 1
+#define SLAMIT_GROW_MP_OVERFLOW 2
+#define SLAMIT_GROW_KFMP_OVERFLOW 4
+#define SLAMIT_GROW_EDIT_OVERFLOW 8
+#define SLAMIT_GROW_RECENT_OVERFLOW 16
+#define SLAMIT_GROW_KP_OVERFLOW 32         /* an op names a frame record with more than SLAMIT_FRAME_MAX_KP keypoints */
+#define SLAMIT_GROW_OPS_OVERFLOW 64        /* d_n above cap */
+#define SLAMIT_GROW_BAD_SLOT 128           /* an op was skipped (SLAMIT_GROW_OP_BAD), or an entry of a row outside the points that exist was skipped */
+#define SLAMIT_GROW_REFUSED 127            /* with one of these bits nothing was written but d_need and d_status */
+#define SLAMIT_GROW_MAX_OPS 65536          /* ops per list (cap); edit_cap is at most SLAMIT_EDIT_MAX_EDITS, recent_cap at most SLAMIT_UPKEEP_MAX_RECENT */
+#define SLAMIT_GROW_MAX_FRAMES 16          /* frame records per call: they travel as the kernel's argument */
+#define SLAMIT_GROW_NEEDS 5                /* d_need per map: keyframes, points, keypoints, edits, recent entries */
+
+struct slamit_grow_op {
+    int32_t kind, flags;
+    int32_t kf;                    /* NEW_KF / ASSOCIATE: the keyframe.  NEW_POINT: ref */
+    int32_t src;                   /* NEW_KF / ASSOCIATE: the frame record */
+    int32_t kf_id;                 /* NEW_KF: mnId.  NEW_POINT: first_kf_id */
+    int32_t cand;                  /* NEW_POINT: the candidate, -1 = accepted with pos */
+    int32_t kf_a, idx_a, kf_b, idx_b;
+    uint8_t weight_a, weight_b;    /* 1, or 2 where mvuRight[idx] >= 0 */
+    uint8_t pad[2];
+    float pos[3];                  /* NEW_POINT with cand = -1 */
+};
+typedef struct slamit_grow_op slamit_grow_op;
+
+/* A frame that becomes a keyframe: DEVICE pointers in a HOST record. */
+struct slamit_grow_frame {
+    int32_t n_kp;                  /* <= SLAMIT_FRAME_MAX_KP */
+    float th_depth;                /* mThDepth */
+    const int32_t* frame_mp;       /* [n_kp] mvpMapPoints as slots, the layout of slamit_local_map_batch_rec.d_frame_mp */
+    const uint8_t* octave;         /* [n_kp] mvKeysUn[i].octave */
+    const uint8_t* desc;           /* [n_kp][32], 16-byte aligned */
+    const float* depth;            /* [n_kp] mvDepth, nullable */
+    const float* uright;           /* [n_kp] mvuRight, nullable: NULL = monocular */
+    const float* Tcw;              /* [12] row-major 3x4 */
+};
+typedef struct slamit_grow_frame slamit_grow_frame;
+
+/* The appendable arrays of one map, named once: the memory the map, covis, point, edit, replace and tree records point to, each with
+ * room for kf_cap keyframes, mp_cap points (obs_ptr: mp_cap + 1, kf_mp_ptr and kf_child_ptr: kf_cap + 1) and kfmp_cap keypoints.  All in /
+ * out device pointers.  obs_ptr and kf_child_ptr are the CURRENT sets of the edit and tree records' alternating tables. */
+struct slamit_grow_index {
+    int32_t kf_cap, mp_cap, kfmp_cap, reserved;
+    int32_t* kf_mp_ptr; int32_t* kf_mp; uint8_t* kf_octave; uint8_t* kf_desc /* 16-byte aligned */; float* kf_depth /* nullable with kf_th_depth */;
+    uint8_t* kf_bad; int32_t* kf_parent; uint8_t* kf_to_be_erased; uint8_t* kf_not_erase; float* kf_th_depth;
+    int32_t* kf_best; int32_t* cw_n; int32_t* ord_n; int32_t* kf_child_ptr; float* kf_center;
+    float* mp_pos; float* mp_normal; float* mp_max_dist; float* mp_min_dist;
+    uint8_t* mp_bad; int32_t* mp_nobs; int32_t* mp_ref_kf; int32_t* mp_found; int32_t* mp_visible; int32_t* mp_first_kf; int32_t* mp_replaced;
+    uint8_t* mp_desc; int32_t* obs_ptr;
+};
+typedef struct slamit_grow_index slamit_grow_index;
+
+/* One list over one map (host pointers everywhere, the frame records' included; synchronous).  The arrays of `grow` hold their full
+ * capacities and are in / out; of the map record the call reads n_kf, n_mp and obs_kf.  op_status[n], edits[edit_cap], recent[recent_cap],
+ * *n_recent, *n_edits_out and *n_new in / out, need[SLAMIT_GROW_NEEDS] and *status out: what lies past every count is left as the caller
+ * filled it, and with a bit of SLAMIT_GROW_REFUSED everything but need and *status is.  Where the resident form skips an op, this form
+ * refuses the call: a NEW_KF that does not name the next free slot, a slot, index, weight, kind, cand or src outside its range, an
+ * ASSOCIATE whose frame record does not have its keyframe's keypoints, a frame_mp, kf_mp or obs_kf entry outside its table, a null
+ * table or a CSR pointer array that does not ascend from 0 fails with SLAMIT_ERR_ARG; n above SLAMIT_GROW_MAX_OPS, n_frames above
+ * SLAMIT_GROW_MAX_FRAMES, edit_cap above SLAMIT_EDIT_MAX_EDITS or recent_cap above SLAMIT_UPKEEP_MAX_RECENT with SLAMIT_ERR_CAPACITY; each
+ * with a message and before anything is launched.  COST: as for the other host forms, it stages every table both ways: for parity and tests. */
+int slamit_map_grow_apply(int device, const slamit_map_index* map, const slamit_grow_index* grow, int32_t n_frames, const slamit_grow_frame* frames,
+                          int32_t n, const slamit_grow_op* ops, int32_t cand_cap, const uint8_t* cand_status, const float* cand_x3d, int32_t* op_status,
+                          int32_t edit_cap, slamit_map_edit* edits, int32_t* n_edits_out, int32_t recent_cap, int32_t* recent, int32_t* n_recent,
+                          int32_t* n_new, int32_t* need, int32_t* status);
+
+/* One list per map for n_maps maps, everything resident.  `maps`, `grow` and `frames` are HOST arrays of records holding DEVICE
+ * pointers; of the map record the call reads n_kf, n_mp and obs_kf.  Map m takes the first d_n[m] ops of d_ops[m].  The device cannot be
+ * shown its tables first: an op with a slot, index, weight or frame record outside its range is skipped whole, never dereferenced; the
+ * pointer arrays kf_mp_ptr, obs_ptr and kf_child_ptr are trusted to ascend from 0 inside their tables, as everywhere in this family.
+ * cap above SLAMIT_GROW_MAX_OPS, n_frames above SLAMIT_GROW_MAX_FRAMES, edit_cap above SLAMIT_EDIT_MAX_EDITS or recent_cap above
+ * SLAMIT_UPKEEP_MAX_RECENT (the ceilings of the calls that read the two lists) fails with SLAMIT_ERR_CAPACITY before anything is launched.
+ * What lies past every count is left as the caller filled it.  Asynchronous on `stream`, no synchronisation, no state; the workspace
+ * (8 mp_cap bytes per map, rounded up to 16) is cleared on the stream by the call.  One workgroup per map walks the list. */
+struct slamit_map_grow_batch_rec {
+    int32_t n_maps, cap, n_frames, cand_cap, edit_cap, recent_cap, mp_cap, reserved;
+    const slamit_map_index* maps;          /* HOST [n_maps], device pointers inside; n_maps <= SLAMIT_LOCAL_MAP_MAX_MAPS */
+    const slamit_grow_index* grow;         /* HOST [n_maps], device pointers inside */
+    const slamit_grow_frame* frames;       /* HOST [n_frames], device pointers inside; n_frames <= SLAMIT_GROW_MAX_FRAMES */
+    const slamit_grow_op* d_ops;           /* [n_maps][cap], cap <= SLAMIT_GROW_MAX_OPS */
+    const int32_t* d_n;                    /* [n_maps] */
+    const uint8_t* d_cand_status;          /* [n_maps][cand_cap]: slamit_triangulate_result.status */
+    const float* d_cand_x3d;               /* [n_maps][cand_cap][3]: slamit_triangulate_result.x3d */
+    int32_t* d_op_status;                  /* [n_maps][cap] in / out: the slot given (NEW_KF, NEW_POINT), kf (ASSOCIATE), or a code below 0 */
+    slamit_map_edit* d_edits;              /* [n_maps][edit_cap] in / out: slamit_map_edit_batch_rec.d_edits with cap = edit_cap */
+    int32_t* d_n_edits_out;                /* [n_maps] out: slamit_map_edit_batch_rec.d_n */
+    int32_t* d_recent;                     /* [n_maps][recent_cap] in / out: slamit_point_culling_batch_rec.d_recent with cap = recent_cap */
+    int32_t* d_n_recent;                   /* [n_maps] in / out: slamit_point_culling_batch_rec.d_n */
+    int32_t* d_n_new;                      /* [n_maps] out: A */
+    int32_t* d_need;                       /* [n_maps][SLAMIT_GROW_NEEDS] out */
+    int32_t* d_status;                     /* [n_maps] out */
+    void* d_workspace;                     /* slamit_map_grow_workspace(n_maps, mp_cap) bytes, 8-byte aligned */
+    size_t workspace_bytes;
+};
+typedef struct slamit_map_grow_batch_rec slamit_map_grow_batch_rec;
+size_t slamit_map_grow_workspace(int n_maps, int mp_cap);
+int slamit_map_grow_batch_dev(int device, const slamit_map_grow_batch_rec* batch, void* stream);
 
 /* ---- Essential-graph optimisation (loop closing, between OptimizeSim3 / CorrectLoop's fusion and the global BA) ----------------
  * Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044) with the g2o it instantiates: one VertexSim3Expmap per good keyframe

@@ -502,6 +502,42 @@ TREE_INDEX_INPLACE = (("kf_bad", np.uint8), ("kf_parent", np.int32), ("kf_to_be_
                       ("ord_kf", np.int32), ("ord_w", np.int32), ("ord_n", np.int32), ("kf_best", np.int32))
 
 
+# slamit_grow_index: the appendable arrays and their element types, in the record's order (after kf_cap, mp_cap, kfmp_cap, reserved)
+GROW_INDEX_ARRAYS = (("kf_mp_ptr", np.int32), ("kf_mp", np.int32), ("kf_octave", np.uint8), ("kf_desc", np.uint8), ("kf_depth", np.float32), ("kf_bad", np.uint8),
+                     ("kf_parent", np.int32), ("kf_to_be_erased", np.uint8), ("kf_not_erase", np.uint8), ("kf_th_depth", np.float32), ("kf_best", np.int32),
+                     ("cw_n", np.int32), ("ord_n", np.int32), ("kf_child_ptr", np.int32), ("kf_center", np.float32), ("mp_pos", np.float32),
+                     ("mp_normal", np.float32), ("mp_max_dist", np.float32), ("mp_min_dist", np.float32), ("mp_bad", np.uint8), ("mp_nobs", np.int32),
+                     ("mp_ref_kf", np.int32), ("mp_found", np.int32), ("mp_visible", np.int32), ("mp_first_kf", np.int32), ("mp_replaced", np.int32),
+                     ("mp_desc", np.uint8), ("obs_ptr", np.int32))
+
+
+class GrowIndexRec(C.Structure):   # struct slamit_grow_index
+    _fields_ = [("kf_cap", C.c_int32), ("mp_cap", C.c_int32), ("kfmp_cap", C.c_int32), ("reserved", C.c_int32)] + [(k, C.c_void_p) for k, _ in GROW_INDEX_ARRAYS]
+
+
+class GrowFrameRec(C.Structure):   # struct slamit_grow_frame
+    _fields_ = [("n_kp", C.c_int32), ("th_depth", C.c_float), ("frame_mp", C.c_void_p), ("octave", C.c_void_p), ("desc", C.c_void_p), ("depth", C.c_void_p),
+                ("uright", C.c_void_p), ("Tcw", C.c_void_p)]
+
+
+class MapGrowBatchRec(C.Structure):   # struct slamit_map_grow_batch_rec
+    _fields_ = [("n_maps", C.c_int32), ("cap", C.c_int32), ("n_frames", C.c_int32), ("cand_cap", C.c_int32), ("edit_cap", C.c_int32), ("recent_cap", C.c_int32),
+                ("mp_cap", C.c_int32), ("reserved", C.c_int32), ("maps", C.POINTER(MapIndexRec)), ("grow", C.POINTER(GrowIndexRec)), ("frames", C.POINTER(GrowFrameRec)),
+                ("d_ops", C.c_void_p), ("d_n", C.c_void_p), ("d_cand_status", C.c_void_p), ("d_cand_x3d", C.c_void_p), ("d_op_status", C.c_void_p),
+                ("d_edits", C.c_void_p), ("d_n_edits_out", C.c_void_p), ("d_recent", C.c_void_p), ("d_n_recent", C.c_void_p), ("d_n_new", C.c_void_p),
+                ("d_need", C.c_void_p), ("d_status", C.c_void_p), ("d_workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+# SLAMIT_GROW_*: the kinds, the flag, the op codes, the status bits per map, the ceilings; struct slamit_grow_op as a numpy record
+GROW_NEW_KF, GROW_NEW_POINT, GROW_ASSOCIATE, GROW_RECENT = 1, 2, 3, 1
+GROW_OP_REJECTED, GROW_OP_BAD = -1, -2
+GROW_STATUS = {"KF_OVERFLOW": 1, "MP_OVERFLOW": 2, "KFMP_OVERFLOW": 4, "EDIT_OVERFLOW": 8, "RECENT_OVERFLOW": 16, "KP_OVERFLOW": 32, "OPS_OVERFLOW": 64, "BAD_SLOT": 128}
+GROW_REFUSED = 127   # with one of these nothing was written but the needs and the status
+GROW_MAX_OPS, GROW_MAX_FRAMES, GROW_NEEDS = 65536, 16, 5
+GROW_OP_DTYPE = np.dtype([("kind", "<i4"), ("flags", "<i4"), ("kf", "<i4"), ("src", "<i4"), ("kf_id", "<i4"), ("cand", "<i4"), ("kf_a", "<i4"), ("idx_a", "<i4"),
+                          ("kf_b", "<i4"), ("idx_b", "<i4"), ("weight_a", "u1"), ("weight_b", "u1"), ("pad", "u1", 2), ("pos", "<f4", 3)])
+
+
 DEPTH_TYPES = ("f32", "u16")   # SLAMIT_DEPTH_*: the index is the type
 DEPTH_PLANE_DTYPE = np.dtype([("data", "<u8"), ("pitch", "<u8"), ("width", "<i4"), ("height", "<i4"), ("type", "<i4"), ("factor", "<f4")])   # slamit_depth_plane
 RGBD_STATUS = ("no_depth", "depth", "outside")
@@ -601,7 +637,7 @@ EXPORTS = [
     "slamit_kfdb_create", "slamit_kfdb_destroy", "slamit_kfdb_clear", "slamit_kfdb_info", "slamit_kfdb_add", "slamit_kfdb_add_dev", "slamit_kfdb_erase",
     "slamit_kfdb_query", "slamit_kfdb_query_batch_dev", "slamit_undistort_points", "slamit_frame_finish",
     "slamit_frame_finish_batch_dev", "slamit_ba_create", "slamit_ba_create_ex", "slamit_ba_destroy", "slamit_ba_solve",
-    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_init_hyp", "slamit_init_hyp_batch", "slamit_init_reconstruct", "slamit_init_reconstruct_batch", "slamit_init_best_hypothesis", "slamit_init_choose_h", "slamit_init_parallax_deg", "slamit_init_pick_f", "slamit_init_pick_h", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_map_edit_apply", "slamit_map_edit_workspace", "slamit_map_edit_batch_dev", "slamit_map_replace_apply", "slamit_map_replace_workspace", "slamit_map_replace_batch_dev", "slamit_check_replaced", "slamit_check_replaced_batch_dev", "slamit_map_fuse_apply", "slamit_map_fuse_workspace", "slamit_map_fuse_batch_dev", "slamit_fuse_list_batch_dev", "slamit_kf_erase_apply", "slamit_kf_erase_workspace", "slamit_kf_erase_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
+    "slamit_ba_solve_batch", "slamit_ba_profile", "slamit_ba_profile_read", "slamit_pose_optimize", "slamit_pose_optimize_batch", "slamit_sim3_optimize", "slamit_sim3_optimize_batch", "slamit_sim3_ransac", "slamit_sim3_ransac_batch", "slamit_pnp_ransac", "slamit_pnp_ransac_batch", "slamit_pnp_refine_batch", "slamit_init_hyp", "slamit_init_hyp_batch", "slamit_init_reconstruct", "slamit_init_reconstruct_batch", "slamit_init_best_hypothesis", "slamit_init_choose_h", "slamit_init_parallax_deg", "slamit_init_pick_f", "slamit_init_pick_h", "slamit_triangulate", "slamit_triangulate_batch", "slamit_triangulate_stereo", "slamit_triangulate_stereo_batch", "slamit_bow_search_stereo", "slamit_frustum", "slamit_frustum_batch", "slamit_frustum_batch_dev", "slamit_project", "slamit_project_batch", "slamit_project_batch_dev", "slamit_project_batch_stereo", "slamit_project_batch_dev_stereo", "slamit_rotation_check_batch_dev", "slamit_orb_pyramid_view", "slamit_stereo_match_workspace", "slamit_stereo_match_batch_dev", "slamit_stereo_match", "slamit_rgbd_depth", "slamit_rgbd_depth_batch", "slamit_rgbd_depth_batch_dev", "slamit_unproject_closest", "slamit_unproject_closest_batch", "slamit_unproject_closest_batch_dev", "slamit_local_keyframes", "slamit_local_points", "slamit_local_map_workspace", "slamit_local_map_batch_dev", "slamit_update_connections", "slamit_update_connections_batch_dev", "slamit_keyframe_culling", "slamit_keyframe_culling_batch_dev", "slamit_update_points", "slamit_update_points_batch_dev", "slamit_map_point_culling", "slamit_map_point_culling_batch_dev", "slamit_map_edit_apply", "slamit_map_edit_workspace", "slamit_map_edit_batch_dev", "slamit_map_replace_apply", "slamit_map_replace_workspace", "slamit_map_replace_batch_dev", "slamit_check_replaced", "slamit_check_replaced_batch_dev", "slamit_map_fuse_apply", "slamit_map_fuse_workspace", "slamit_map_fuse_batch_dev", "slamit_fuse_list_batch_dev", "slamit_kf_erase_apply", "slamit_kf_erase_workspace", "slamit_kf_erase_batch_dev", "slamit_map_grow_apply", "slamit_map_grow_workspace", "slamit_map_grow_batch_dev", "slamit_last_error", "slamit_version", "slamit_device_count", "slamit_set_device", "slamit_release_thread_scratch",
 ]
 
 
@@ -724,6 +760,11 @@ def lib():
         L.slamit_kf_erase_workspace.argtypes = [i32, i32, i32, i32, i32]
         L.slamit_kf_erase_workspace.restype = sz
         L.slamit_kf_erase_batch_dev.argtypes = [i32, C.POINTER(KfEraseBatchRec), vp]
+        L.slamit_map_grow_apply.argtypes = [i32, C.POINTER(MapIndexRec), C.POINTER(GrowIndexRec), i32, C.POINTER(GrowFrameRec), i32, vp, i32, vp, vp, vp, i32, vp, vp, i32,
+                                            vp, vp, vp, vp, vp]
+        L.slamit_map_grow_workspace.argtypes = [i32, i32]
+        L.slamit_map_grow_workspace.restype = sz
+        L.slamit_map_grow_batch_dev.argtypes = [i32, C.POINTER(MapGrowBatchRec), vp]
         L.slamit_bow_search.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), vp, vp, vp]
         L.slamit_bow_search_stereo.argtypes = [i32, vp, i32, vp, vp, i32, vp, C.POINTER(BowGroups), C.POINTER(BowRule), C.POINTER(BowStereo), vp, vp, vp]
         L.slamit_voc_create.argtypes = [C.POINTER(VocDesc), i32, C.POINTER(vp)]
@@ -2779,7 +2820,8 @@ def local_points(tables, frame_mp, local_kf, frame_seen=(), q_cap=4096, fill=-1,
 class MapIndex:
     """A map's tables uploaded once (the resident form's slamit_map_index): MapIndex(tables).rec holds the device pointers.  Nothing here
     is per frame.  Where the map changes which keyframe observes which point, map_edit_batch_dev rewrites the tables in HBM through an
-    EditIndex beside this record; any other change is a table the caller uploads again."""
+    EditIndex beside this record; new keyframes and new points are appended by map_grow_batch_dev into buffers with room (GrowIndexRec
+    names them); any other change is a table the caller uploads again."""
 
     def __init__(self, tables, device=0):
         import torch
@@ -3569,6 +3611,262 @@ def kf_erase_batch_dev(maps, tree, t, device=0, stream=None):
                           t["op_status"].data_ptr(), t["edits"].data_ptr(), t["n_edits_out"].data_ptr(), t["n_child_out"].data_ptr(), t["status"].data_ptr(),
                           ws.data_ptr(), ws.numel() * ws.element_size())
     _check(lib().slamit_kf_erase_batch_dev(device, C.byref(rec), stream), "slamit_kf_erase_batch_dev")
+
+
+# ---- map growth: new keyframes, new map points, ProcessNewKeyFrame's association loop -----------------------------------------------
+def grow_op_records(ops):
+    """A list of dicts (the fields of GROW_OP_DTYPE; those left out are 0, kf_b and cand -1) as slamit_grow_op records."""
+    out = np.zeros(len(ops), GROW_OP_DTYPE)
+    out["kf_b"], out["cand"] = -1, -1
+    for i, e in enumerate(ops):
+        for k, v in e.items():
+            out[i][k] = v
+    return out
+
+
+def grow_index_rec(tensors, kf_cap, mp_cap, kfmp_cap):
+    """slamit_grow_index over a dict of torch CUDA tensors under the names of GROW_INDEX_ARRAYS, each with room for kf_cap keyframes,
+    mp_cap points and kfmp_cap keypoints (kf_depth and kf_th_depth may be left out together).  The tensors are the memory the other
+    records of the map point to; the caller keeps them alive."""
+    rec = GrowIndexRec(int(kf_cap), int(mp_cap), int(kfmp_cap), 0)
+    room = {"kf_mp_ptr": kf_cap + 1, "kf_child_ptr": kf_cap + 1, "obs_ptr": mp_cap + 1, "kf_mp": kfmp_cap, "kf_octave": kfmp_cap, "kf_desc": 32 * kfmp_cap,
+            "kf_depth": kfmp_cap, "kf_best": LOCAL_MAP_BEST * kf_cap, "kf_center": 3 * kf_cap, "mp_pos": 3 * mp_cap, "mp_normal": 3 * mp_cap, "mp_desc": 32 * mp_cap}
+    for key, dt in GROW_INDEX_ARRAYS:
+        t = tensors.get(key)
+        if t is None:
+            if key in ("kf_depth", "kf_th_depth"):
+                continue
+            raise SlamitError("grow_index_rec: no %s" % key)
+        need = room.get(key, kf_cap if key.startswith(("kf_", "cw_", "ord_")) else mp_cap)
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != np.dtype(dt).itemsize or t.numel() < need:
+            raise SlamitError("grow_index_rec: %s is not a contiguous CUDA tensor of at least %d %s" % (key, need, np.dtype(dt).name))
+        setattr(rec, key, t.data_ptr())
+    return rec
+
+
+def grow_frame_rec(frame):
+    """slamit_grow_frame over a dict of torch CUDA tensors frame_mp (n_kp) i32, octave (n_kp) u8, desc (n_kp, 32) u8, Tcw (12) f32 and
+    optionally depth, uright (n_kp) f32, with th_depth a float.  The caller keeps the tensors alive."""
+    n_kp = int(frame["frame_mp"].numel())
+    rec = GrowFrameRec(n_kp, float(frame.get("th_depth", 0.0)))
+    for key, per in (("frame_mp", 1), ("octave", 1), ("desc", 32), ("depth", 1), ("uright", 1)):
+        t = frame.get(key)
+        if t is None:
+            if key in ("depth", "uright"):
+                continue
+            raise SlamitError("grow_frame_rec: no %s" % key)
+        if t.numel() != n_kp * per or not t.is_contiguous():
+            raise SlamitError("grow_frame_rec: %s does not hold %d entries per keypoint" % (key, per))
+        setattr(rec, key, t.data_ptr())
+    if frame["Tcw"].numel() != 12:
+        raise SlamitError("grow_frame_rec: Tcw holds 12 floats")
+    rec.Tcw = frame["Tcw"].data_ptr()
+    return rec
+
+
+def map_grow(tables, cols, ops, frames, cands=None, recent=(), caps=None, fill=None, device=0):
+    """New keyframes, new map points and ProcessNewKeyFrame's association loop for a list of ops applied as if sequentially, over a map's
+    tables and column records, host form (for parity and tests: it stages every table both ways).  tables / cols: dicts that together hold
+    n_kf, n_mp, obs_kf and the arrays of GROW_INDEX_ARRAYS (the dicts MapIndex, CovisIndex, PointIndex, EditIndex, ReplaceIndex and
+    TreeIndex take; kf_depth and kf_th_depth may be None together).  ops: grow_op_records().  frames: a list of dicts frame_mp, octave, desc,
+    Tcw, th_depth and optionally depth, uright (numpy).  cands: dict status (u8), x3d (n, 3) f32, or None.  recent: the recent list so far.
+    caps: dict kf_cap, mp_cap, kfmp_cap, edit_cap, recent_cap (default: what the gate needs).  fill: optional dict of prefilled arrays, each
+    at its capacity, under the names of GROW_INDEX_ARRAYS, op_status, edits (bytes) and recent: what lies past the tables and the counts.
+    The caller's arrays are not modified.  -> dict: the grown arrays under their names, cut to n_kf / n_mp as they now stand (what the index
+    classes take in place of the old ones), n_kf, n_mp, op_status, edits (the first n_edits_out, EDIT_DTYPE), recent (the first n_recent),
+    n_new, need, status, and raw: every array in full."""
+    ops = np.ascontiguousarray(ops, GROW_OP_DTYPE).reshape(-1)
+    src = dict(tables)
+    src.update(cols or {})
+    n_kf, n_mp = int(src["n_kf"]), int(src["n_mp"])
+    n_new_kf, P = int((ops["kind"] == GROW_NEW_KF).sum()), int((ops["kind"] == GROW_NEW_POINT).sum())
+    kp = lambda kind: sum(len(frames[s]["frame_mp"]) for s in ops["src"][ops["kind"] == kind] if 0 <= s < len(frames))
+    end = int(np.asarray(src["kf_mp_ptr"]).reshape(-1)[n_kf]) if src.get("kf_mp_ptr") is not None and len(np.asarray(src["kf_mp_ptr"]).reshape(-1)) > n_kf else 0
+    c = {"kf_cap": n_kf + n_new_kf, "mp_cap": n_mp + P, "kfmp_cap": end + kp(GROW_NEW_KF), "edit_cap": 2 * P + kp(GROW_ASSOCIATE),
+         "recent_cap": len(recent) + int(((ops["kind"] == GROW_NEW_POINT) & (ops["flags"] & GROW_RECENT != 0)).sum()) + kp(GROW_ASSOCIATE)}
+    c.update(caps or {})
+    fill = fill or {}
+    room = {"kf_mp_ptr": c["kf_cap"] + 1, "kf_child_ptr": c["kf_cap"] + 1, "obs_ptr": c["mp_cap"] + 1, "kf_mp": c["kfmp_cap"], "kf_octave": c["kfmp_cap"],
+            "kf_desc": 32 * c["kfmp_cap"], "kf_depth": c["kfmp_cap"], "kf_best": LOCAL_MAP_BEST * c["kf_cap"], "kf_center": 3 * c["kf_cap"], "mp_pos": 3 * c["mp_cap"],
+            "mp_normal": 3 * c["mp_cap"], "mp_desc": 32 * c["mp_cap"]}
+
+    def held(key, dt, count, front):
+        a = np.array(fill[key], dt).reshape(-1) if fill.get(key) is not None else np.zeros(max(count, 0), dt)
+        if len(a) != count:
+            raise SlamitError("map_grow: fill[%s] does not hold %d entries" % (key, count))
+        if front is not None:
+            f = np.ascontiguousarray(front, dt).reshape(-1)
+            if len(f) > count:
+                raise SlamitError("map_grow: %s holds more than its capacity" % key)
+            a[:len(f)] = f
+        return a
+
+    raw, rec = {}, GrowIndexRec(c["kf_cap"], c["mp_cap"], c["kfmp_cap"], 0)
+    for key, dt in GROW_INDEX_ARRAYS:
+        if src.get(key) is None:
+            continue
+        raw[key] = held(key, dt, room.get(key, c["kf_cap"] if key.startswith(("kf_", "cw_", "ord_")) else c["mp_cap"]), src[key])
+        setattr(rec, key, _np_ptr(raw[key]))
+    obs_kf = np.ascontiguousarray(src["obs_kf"], np.int32).reshape(-1) if src.get("obs_kf") is not None else np.zeros(0, np.int32)
+    mrec = MapIndexRec(n_kf, n_mp)
+    mrec.obs_kf = _np_ptr(obs_kf) if len(obs_kf) else None
+    F, keep = (GrowFrameRec * max(len(frames), 1))(), []
+    for i, f in enumerate(frames):
+        n_kp = len(f["frame_mp"])
+        F[i].n_kp, F[i].th_depth = n_kp, float(f.get("th_depth", 0.0))
+        for key, dt, per in (("frame_mp", np.int32, 1), ("octave", np.uint8, 1), ("desc", np.uint8, 32), ("depth", np.float32, 1), ("uright", np.float32, 1), ("Tcw", np.float32, 0)):
+            if f.get(key) is None:
+                continue
+            a = np.ascontiguousarray(f[key], dt).reshape(-1)
+            if len(a) != (n_kp * per if per else 12):
+                raise SlamitError("map_grow: a frame's %s does not hold its entries" % key)
+            keep.append(a if len(a) else np.zeros(1, dt))
+            setattr(F[i], key, _np_ptr(keep[-1]))
+    cs = np.ascontiguousarray(cands["status"], np.uint8).reshape(-1) if cands else np.zeros(0, np.uint8)
+    cx = np.ascontiguousarray(cands["x3d"], np.float32).reshape(-1) if cands else np.zeros(0, np.float32)
+    if len(cx) != 3 * len(cs):
+        raise SlamitError("map_grow: cands x3d holds three floats per status")
+    ost = held("op_status", np.int32, len(ops), None)
+    edits = held("edits", np.uint8, c["edit_cap"] * EDIT_DTYPE.itemsize, None)
+    rct = held("recent", np.int32, c["recent_cap"], np.asarray(recent, np.int32) if len(recent) <= c["recent_cap"] else None)
+    ne, nn = np.array([int(fill.get("n_edits_out", 0))], np.int32), np.array([int(fill.get("n_new", 0))], np.int32)   # left as they are by a refused call
+    nr, need, st = np.array([len(recent)], np.int32), np.zeros(GROW_NEEDS, np.int32), np.zeros(1, np.int32)
+    some = lambda a: _np_ptr(a) if len(a) else None
+    _check(lib().slamit_map_grow_apply(device, C.byref(mrec), C.byref(rec), len(frames), F, len(ops), some(ops), len(cs), some(cs), some(cx), some(ost), c["edit_cap"],
+                                       some(edits), _np_ptr(ne), c["recent_cap"], some(rct), _np_ptr(nr), _np_ptr(nn), _np_ptr(need), _np_ptr(st)), "slamit_map_grow_apply")
+    out = {"raw": dict(raw, op_status=ost, edits=edits, recent=rct), "status": int(st[0]), "need": need.tolist(), "n_new": int(nn[0]), "n_edits_out": int(ne[0]),
+           "n_recent": int(nr[0]), "op_status": ost, "caps": c}
+    grown = not out["status"] & GROW_REFUSED
+    out["n_kf"], out["n_mp"] = n_kf + (n_new_kf if grown else 0), n_mp + (P if grown else 0)
+    cut = {"kf_mp_ptr": out["n_kf"] + 1, "kf_child_ptr": out["n_kf"] + 1, "obs_ptr": out["n_mp"] + 1, "kf_best": LOCAL_MAP_BEST * out["n_kf"], "kf_center": 3 * out["n_kf"],
+           "mp_pos": 3 * out["n_mp"], "mp_normal": 3 * out["n_mp"], "mp_desc": 32 * out["n_mp"]}
+    n_kfmp = int(raw["kf_mp_ptr"][out["n_kf"]])
+    for key, _ in GROW_INDEX_ARRAYS:
+        if key in raw:
+            k = cut.get(key, n_kfmp * (32 if key == "kf_desc" else 1) if key in ("kf_mp", "kf_octave", "kf_desc", "kf_depth") else
+                        out["n_kf"] if key.startswith(("kf_", "cw_", "ord_")) else out["n_mp"])
+            out[key] = raw[key][:k]
+    out["edits"] = edits[:out["n_edits_out"] * EDIT_DTYPE.itemsize].view(EDIT_DTYPE) if grown else edits[:0].view(EDIT_DTYPE)
+    out["recent"] = rct[:out["n_recent"]]
+    return out
+
+
+class GrowIndex:
+    """The index classes of one map re-housed in buffers with room, and the record map_grow_batch_dev takes (the resident form's
+    slamit_grow_index).  GrowIndex(map_index, covis=, points=, edit=, replace=, tree=, kf_cap=, mp_cap=, kfmp_cap=): every tensor the
+    records share that grows with the keyframes, the points or the keypoints -- the MapIndex's tables, the CovisIndex's columns and graph
+    rows, the PointIndex's columns, the in-place tensors of the EditIndex / ReplaceIndex / TreeIndex and the pointer arrays of BOTH buffer
+    sets of the EditIndex and the TreeIndex -- is copied once into a tensor that holds kf_cap keyframes, mp_cap points or kfmp_cap keypoints
+    (zeros behind what it held), a tensor two records shared stays one tensor, and all records are repointed.  covis, points, edit (built
+    with that covis and those points) and tree are required: between them they hold every array a new keyframe or point needs; without
+    replace, mp_replaced is kept here.  The PointIndex's kf_octave becomes the CovisIndex's tensor.  The observation and children tables
+    keep the room their EditIndex / TreeIndex were given.  .rec is built from the tensors as they stand (after any swap()).  After
+    map_grow_batch_dev has run without a bit of GROW_REFUSED, grown(n_new_kf, n_point_ops) advances n_kf / n_mp of the map record, the one
+    every sibling call reads them from: host bookkeeping with what the caller listed, no synchronisation."""
+
+    def __init__(self, map_index, covis=None, points=None, edit=None, replace=None, tree=None, kf_cap=0, mp_cap=0, kfmp_cap=0):
+        import torch
+
+        if covis is None or points is None or edit is None or tree is None:
+            raise SlamitError("GrowIndex: covis, points, edit and tree hold arrays a new keyframe or point needs: all four are required")
+        if edit.covis is not covis or edit.points is not points or edit.map_index is not map_index or tree.map_index is not map_index or tree.covis is not covis:
+            raise SlamitError("GrowIndex: the EditIndex and the TreeIndex must have been built over this MapIndex, CovisIndex and PointIndex")
+        mi = map_index
+        self.map_index, self.covis, self.points, self.edit, self.replace, self.tree = mi, covis, points, edit, replace, tree
+        self.kf_cap, self.mp_cap, self.kfmp_cap, self.device = int(kf_cap), int(mp_cap), int(kfmp_cap), mi.device
+        n_kfmp = int(mi.t["kf_mp_ptr"][mi.rec.n_kf]) if mi.rec.n_kf else 0     # read once, when the index is set up
+        if self.kf_cap < mi.rec.n_kf or self.mp_cap < mi.rec.n_mp or self.kfmp_cap < n_kfmp:
+            raise SlamitError("GrowIndex: a capacity below what the map holds")
+        rc, K, P, E = covis.row_cap, self.kf_cap, self.mp_cap, self.kfmp_cap
+        points.t["kf_octave"] = covis.t["kf_octave"]
+        self.t = {} if replace is not None else {"mp_replaced": torch.full((max(mi.rec.n_mp, 1),), -1, dtype=torch.int32, device="cuda:%d" % self.device)}
+        rooms = [(mi.t, {"kf_bad": K, "kf_parent": K, "kf_best": LOCAL_MAP_BEST * K, "kf_mp_ptr": K + 1, "kf_mp": E, "mp_bad": P, "mp_pos": 3 * P, "mp_normal": 3 * P,
+                         "mp_max_dist": P, "mp_min_dist": P}),
+                 (covis.t, {"kf_octave": E, "kf_depth": E, "kf_th_depth": K, "kf_not_erase": K, "cw_kf": K * rc, "cw_w": K * rc, "cw_n": K, "ord_kf": K * rc, "ord_w": K * rc,
+                            "ord_n": K, "kf_best": LOCAL_MAP_BEST * K, "mp_nobs": P}),
+                 (points.t, {"kf_octave": E, "kf_center": 3 * K, "kf_desc": 32 * E, "mp_ref_kf": P, "mp_nobs": P, "mp_found": P, "mp_visible": P, "mp_first_kf": P,
+                             "mp_normal": 3 * P, "mp_max_dist": P, "mp_min_dist": P, "mp_desc": 32 * P}),
+                 (edit.t, {"mp_bad": P, "mp_nobs": P, "mp_ref_kf": P, "kf_mp": E}), (edit.sets[0], {"obs_ptr": P + 1}), (edit.sets[1], {"obs_ptr": P + 1}),
+                 (tree.t, {"kf_to_be_erased": K}), (tree.sets[0], {"kf_child_ptr": K + 1}), (tree.sets[1], {"kf_child_ptr": K + 1}), (self.t, {"mp_replaced": P})]
+        if replace is not None:
+            rooms.append((replace.t, {"mp_found": P, "mp_visible": P, "mp_replaced": P}))
+        housed = {}                                                      # the old tensor's address -> its new house: what two records shared stays one tensor
+
+        def house(t, count):
+            key = (t.data_ptr(), t.dtype)
+            if key not in housed:
+                new = torch.zeros(max(count, 1), dtype=t.dtype, device=t.device)   # a table longer than its room is an empty one's padding
+                new[:min(t.numel(), count)] = t.reshape(-1)[:count]
+                housed[key] = new
+            if housed[key].numel() < count:
+                raise SlamitError("GrowIndex: one tensor is named with two different rooms")
+            return housed[key]
+
+        for d, room in rooms:
+            for key, count in room.items():
+                if key in d:
+                    d[key] = house(d[key], count)
+        for idx, tables in ((mi, MAP_INDEX_TABLES), (covis, COVIS_INDEX_TABLES), (points, POINT_INDEX_TABLES)):
+            for key, _ in tables:
+                if key in idx.t:
+                    setattr(idx.rec, key, idx.t[key].data_ptr())
+        edit._point()                                                    # its followers (a ReplaceIndex) repoint with it
+        if replace is not None:
+            replace._point()
+        tree._point()
+
+    @property
+    def rec(self):
+        mi, ci, pi = self.map_index.t, self.covis.t, self.points.t
+        t = {k: mi[k] for k in ("kf_mp_ptr", "kf_mp", "kf_bad", "kf_parent", "kf_best", "kf_child_ptr", "mp_pos", "mp_normal", "mp_max_dist", "mp_min_dist", "mp_bad", "obs_ptr")}
+        t.update({k: ci[k] for k in ("kf_octave", "kf_depth", "kf_th_depth", "kf_not_erase", "cw_n", "ord_n", "mp_nobs") if k in ci})
+        t.update({k: pi[k] for k in ("kf_desc", "kf_center", "mp_ref_kf", "mp_found", "mp_visible", "mp_first_kf", "mp_desc")})
+        t["kf_to_be_erased"] = self.tree.t["kf_to_be_erased"]
+        t["mp_replaced"] = (self.replace.t if self.replace is not None else self.t)["mp_replaced"]
+        return grow_index_rec(t, self.kf_cap, self.mp_cap, self.kfmp_cap)
+
+    def grown(self, n_new_kf, n_point_ops):
+        mi = self.map_index
+        mi.n_kf, mi.n_mp = mi.n_kf + int(n_new_kf), mi.n_mp + int(n_point_ops)
+        if mi.n_kf > self.kf_cap or mi.n_mp > self.mp_cap:
+            raise SlamitError("GrowIndex.grown: past the capacity")
+        mi.rec.n_kf, mi.rec.n_mp = mi.n_kf, mi.n_mp
+
+
+def map_grow_workspace(n_maps, mp_cap):
+    return int(lib().slamit_map_grow_workspace(n_maps, mp_cap))
+
+
+def map_grow_batch_dev(map_recs, grow_recs, frame_recs, t, device=0, stream=None):
+    """One op list per map, resident: new keyframes, new points and the association loop appended to tables with room.  map_recs: a list of
+    MapIndex (any object with .rec, as the sibling calls take) or of bare MapIndexRec; grow_recs: a list of GrowIndexRec (grow_index_rec); frame_recs: a list of GrowFrameRec
+    (grow_frame_rec), at most GROW_MAX_FRAMES.  t: dict of torch CUDA tensors ops (B, cap, 56) u8 (the bytes of GROW_OP_DTYPE records), n (B)
+    i32, cand_status (B, cand_cap) u8, cand_x3d (B, cand_cap, 3) f32, op_status (B, cap) i32 in / out, edits (B, edit_cap, 24) u8 in / out
+    (what map_edit_batch_dev takes as its edits, with n_edits_out as its n), n_edits_out (B) i32, recent (B, recent_cap) i32 and n_recent (B)
+    i32 in / out (what map_point_culling_batch_dev takes), n_new (B) i32, need (B, GROW_NEEDS) i32, status (B) i32, workspace: uint8,
+    map_grow_workspace(B, mp_cap) bytes with mp_cap = t["mp_cap"] >= every grow record's mp_cap.  Where status has no bit of
+    GROW_REFUSED the caller advances n_kf / n_mp of its records by the NEW_KF ops and by the NEW_POINT ops it listed.  Asynchronous on
+    `stream`."""
+    b, cap = t["ops"].shape[0], t["ops"].shape[1]
+    edit_cap, recent_cap, cand_cap = t["edits"].shape[1], t["recent"].shape[1], t["cand_status"].shape[1]
+    if len(map_recs) != b or len(grow_recs) != b:
+        raise SlamitError("map_grow_batch_dev: one MapIndexRec, one GrowIndexRec and one list per map")
+    _rows(t, "map_grow_batch_dev", (("op_status", cap), ("n", 1), ("n_edits_out", 1), ("recent", recent_cap), ("n_recent", 1), ("n_new", 1), ("need", GROW_NEEDS),
+                                    ("status", 1), ("cand_status", cand_cap), ("cand_x3d", 3 * cand_cap)), b)
+    for key, per in (("ops", cap * GROW_OP_DTYPE.itemsize), ("edits", edit_cap * EDIT_DTYPE.itemsize)):
+        if t[key].numel() * t[key].element_size() != b * per or not t[key].is_contiguous():
+            raise SlamitError("map_grow_batch_dev: %s is not a contiguous array of %d bytes per map" % (key, per))
+    M, X, F = (MapIndexRec * max(b, 1))(), (GrowIndexRec * max(b, 1))(), (GrowFrameRec * max(len(frame_recs), 1))()
+    for i, (mr, gr) in enumerate(zip(map_recs, grow_recs)):
+        M[i], X[i] = getattr(mr, "rec", mr), getattr(gr, "rec", gr)     # MapIndex and its like, as the sibling calls take them, or the bare records
+    for i, fr in enumerate(frame_recs):
+        F[i] = fr
+    ws = t["workspace"]
+    rec = MapGrowBatchRec(b, cap, len(frame_recs), cand_cap, edit_cap, recent_cap, int(t["mp_cap"]), 0, M, X, F, t["ops"].data_ptr(), t["n"].data_ptr(),
+                          t["cand_status"].data_ptr(), t["cand_x3d"].data_ptr(), t["op_status"].data_ptr(), t["edits"].data_ptr(), t["n_edits_out"].data_ptr(),
+                          t["recent"].data_ptr(), t["n_recent"].data_ptr(), t["n_new"].data_ptr(), t["need"].data_ptr(), t["status"].data_ptr(),
+                          ws.data_ptr(), ws.numel() * ws.element_size())
+    _check(lib().slamit_map_grow_batch_dev(device, C.byref(rec), stream), "slamit_map_grow_batch_dev")
 
 
 # ---- essential-graph optimisation (Optimizer::OptimizeEssentialGraph) -----------------------------------------------------------

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libslamit_hip.so")
-SOURCES = ["slamit_misc.hip", "orb_kernels.hip", "orb_plan.cc", "orb_api.hip", "hamming.hip", "ba_kernels.hip", "ba_plan.cc", "ba_api.hip", "pose.hip", "search.hip", "frame.hip", "bow.hip", "voc_pack.cc", "voc.hip", "kfdb.hip", "sim3.hip", "sim3_ransac.hip", "pnp.hip", "initializer.hip", "triangulate.hip", "frustum.hip", "project.hip", "rotation.hip", "stereo.hip", "unproject.hip", "local_map.hip", "covis.hip", "upkeep.hip", "map_edit.hip", "map_replace.hip", "map_fuse.hip", "kf_erase.hip", "essential_plan.cc", "essential.hip"]
+SOURCES = ["slamit_misc.hip", "orb_kernels.hip", "orb_plan.cc", "orb_api.hip", "hamming.hip", "ba_kernels.hip", "ba_plan.cc", "ba_api.hip", "pose.hip", "search.hip", "frame.hip", "bow.hip", "voc_pack.cc", "voc.hip", "kfdb.hip", "sim3.hip", "sim3_ransac.hip", "pnp.hip", "initializer.hip", "triangulate.hip", "frustum.hip", "project.hip", "rotation.hip", "stereo.hip", "unproject.hip", "local_map.hip", "covis.hip", "upkeep.hip", "map_edit.hip", "map_replace.hip", "map_fuse.hip", "kf_erase.hip", "map_grow.hip", "essential_plan.cc", "essential.hip"]
 # BA is fp64 with a 1e-5 tolerance, not bit-exact: let the compiler fuse multiply-adds there
 # hamming.hip: the MFMA results feed VALU min / median directly, so its accumulators stay in VGPRs (no v_accvgpr moves)
 PER_FILE = {"ba_kernels.hip": ["-ffp-contract=fast"], "pose.hip": ["-ffp-contract=fast"],

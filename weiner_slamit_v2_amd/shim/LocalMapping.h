@@ -762,6 +762,194 @@ public:
         return turned;
     }
 
+    // One op of GrowMap over the caller's objects.  SLAMIT_GROW_NEW_KF: pKF is a keyframe the caller has constructed from its frame
+    // (KeyFrame::KeyFrame(Frame&, ...): mvpMapPoints, mvKeysUn, mvuRight are the frame's) and that no object of the map names yet.
+    // SLAMIT_GROW_ASSOCIATE: pKF is the keyframe whose row ProcessNewKeyFrame walks.  SLAMIT_GROW_NEW_POINT: pKF is pRefKF, (pKFa, idxA) and
+    // (pKFb, idxB) the observers (pKFb null: the one-observer stereo point), accepted what the triangulation said, pos the point, recent
+    // whether CreateNewMapPoints would push it to mlpRecentAddedMapPoints.
+    template <class KeyFrameT>
+    struct GrowOp {
+        int kind;
+        KeyFrameT* pKF;
+        KeyFrameT* pKFa; size_t idxA;
+        KeyFrameT* pKFb; size_t idxB;
+        bool accepted, recent;
+        float pos[3];
+    };
+
+    // The places where the map grows -- Map::AddKeyFrame of a new keyframe, MapPoint::MapPoint(Pos, pRefKF, pMap) with AddObservation /
+    // AddMapPoint on one or two keyframes and Map::AddMapPoint (LocalMapping.cc:486-500, Tracking.cc:1376-1383, :718-723, :875-891), the loop
+    // of ProcessNewKeyFrame (:156-175) -- for a LIST of ops applied as if one after the other: ONE slamit_map_grow_apply call, then ONE
+    // ApplyMapEdits call (one slamit_map_edit_apply) with the ADD_OBS list it emitted.  make(pos, pRefKF) constructs a map point; it is called
+    // for the accepted points in slot order, which is list order, so the points get the reference's mnId.  Writes back the changed entries
+    // of mvpMapPoints, through ApplyMapEdits mObservations / nObs, calls pMap->AddKeyFrame / pMap->AddMapPoint, and appends to `recent`
+    // what the reference appends to mlpRecentAddedMapPoints.  Returns the number of points created.  Existing keyframes are numbered by
+    // std::less<KeyFrameT*>, the new ones behind them in list order.  UpdateNormalAndDepth, ComputeDistinctiveDescriptors, ComputeBoW and
+    // UpdateConnections stay the caller's next calls.  At most SLAMIT_GROW_MAX_FRAMES keyframes may be named by NEW_KF and ASSOCIATE ops.
+    // THROUGH THE SHIM IT SAVES NOTHING: building the tables walks every row the ops touch a few entries of.  It is for parity and for
+    // integrations that want one code path; the gain is slamit_map_grow_batch_dev with the tables kept in HBM.  Members used (a friend
+    // declaration in the reference's classes): KeyFrame mvpMapPoints, mvKeysUn, mvuRight; MapPoint mObservations, mbBad, and what
+    // ApplyMapEdits names.
+    template <class MapPointT, class KeyFrameT, class MapT, class RecentT, class MakeT>
+    static int GrowMap(const std::vector<GrowOp<KeyFrameT> >& ops, MapT* pMap, RecentT& recent, MakeT make, int device = 0) {
+        typedef typename std::map<KeyFrameT*, size_t>::const_iterator ObsIt;
+        status() = SLAMIT_OK;
+        const int n = (int)ops.size();
+        if (n == 0) return 0;
+        if (n > SLAMIT_GROW_MAX_OPS) return shim::refuse<LocalMapping>("GrowMap: more than SLAMIT_GROW_MAX_OPS ops", SLAMIT_ERR_CAPACITY);
+        std::set<KeyFrameT*> fresh, named;
+        std::vector<KeyFrameT*> fresh_order, framed;                          // the new keyframes in list order; the keyframes that need a frame record
+        std::map<KeyFrameT*, int32_t> frameOf;
+        for (int i = 0; i < n; ++i) {
+            const GrowOp<KeyFrameT>& e = ops[i];
+            if (!e.pKF || (e.kind == SLAMIT_GROW_NEW_POINT && !e.pKFa)) return shim::refuse<LocalMapping>("GrowMap: an op without its keyframe");
+            if (e.kind == SLAMIT_GROW_NEW_KF) {
+                if (!fresh.insert(e.pKF).second || named.count(e.pKF)) return shim::refuse<LocalMapping>("GrowMap: a NEW_KF op names a keyframe an earlier op named");
+                fresh_order.push_back(e.pKF);
+            } else if (e.kind == SLAMIT_GROW_ASSOCIATE || e.kind == SLAMIT_GROW_NEW_POINT) {
+                KeyFrameT* const ks[3] = {e.pKF, e.kind == SLAMIT_GROW_NEW_POINT ? e.pKFa : (KeyFrameT*)0, e.kind == SLAMIT_GROW_NEW_POINT ? e.pKFb : (KeyFrameT*)0};
+                for (int q = 0; q < 3; ++q)
+                    if (ks[q] && !fresh.count(ks[q])) named.insert(ks[q]);
+            } else return shim::refuse<LocalMapping>("GrowMap: an op's kind outside 1..3");
+            if (e.kind != SLAMIT_GROW_NEW_POINT && !frameOf.count(e.pKF)) { frameOf[e.pKF] = (int32_t)framed.size(); framed.push_back(e.pKF); }
+        }
+        if (framed.size() > SLAMIT_GROW_MAX_FRAMES) return shim::refuse<LocalMapping>("GrowMap: more than SLAMIT_GROW_MAX_FRAMES keyframes named by NEW_KF and ASSOCIATE ops", SLAMIT_ERR_CAPACITY);
+        // the points the rows of the named and the new keyframes hold, and the keyframes that observe them
+        std::vector<MapPointT*> mps;
+        std::map<MapPointT*, int32_t> mpSlot;
+        std::set<KeyFrameT*> old(named);
+        for (int pass = 0; pass < 2; ++pass) {
+            const std::vector<KeyFrameT*> rows(pass ? fresh_order : std::vector<KeyFrameT*>(named.begin(), named.end()));
+            for (size_t k = 0; k < rows.size(); ++k)
+                for (size_t i = 0; i < rows[k]->mvpMapPoints.size(); ++i) {
+                    MapPointT* p = rows[k]->mvpMapPoints[i];
+                    if (!p) continue;
+                    slotOf(mpSlot, mps, p);
+                    for (ObsIt it = p->mObservations.begin(); it != p->mObservations.end(); ++it)
+                        if (!fresh.count(it->first)) old.insert(it->first);
+                }
+        }
+        std::vector<KeyFrameT*> kfs(old.begin(), old.end());                  // a std::set orders by std::less
+        const int n_kf = (int)kfs.size(), n_mp = (int)mps.size();
+        kfs.insert(kfs.end(), fresh_order.begin(), fresh_order.end());        // the new ones behind them, in list order
+        std::map<KeyFrameT*, int32_t> kfSlot;
+        for (size_t k = 0; k < kfs.size(); ++k) kfSlot[kfs[k]] = (int32_t)k;
+        if (kfs.size() > SLAMIT_LOCAL_MAP_MAX_KF) return shim::refuse<LocalMapping>("GrowMap: more than SLAMIT_LOCAL_MAP_MAX_KF keyframes around the ops", SLAMIT_ERR_CAPACITY);
+        int P = 0, n_rec_ops = 0;
+        size_t kp_new = 0, kp_assoc = 0;
+        for (int i = 0; i < n; ++i) {
+            if (ops[i].kind == SLAMIT_GROW_NEW_POINT) { ++P; n_rec_ops += ops[i].recent; }
+            else (ops[i].kind == SLAMIT_GROW_NEW_KF ? kp_new : kp_assoc) += ops[i].pKF->mvpMapPoints.size();
+        }
+        const int kf_cap = (int)kfs.size(), mp_cap = n_mp + P;
+        // the tables: the rows of the old keyframes that are named (the others: empty rows), the observers of every point
+        std::vector<int32_t> kf_mp_ptr(kf_cap + 1, 0), kf_mp;
+        std::vector<uint8_t> kf_octave;
+        for (int k = 0; k < n_kf; ++k) {
+            if (named.count(kfs[k]))
+                for (size_t i = 0; i < kfs[k]->mvpMapPoints.size(); ++i) {
+                    kf_mp.push_back(kfs[k]->mvpMapPoints[i] ? mpSlot[kfs[k]->mvpMapPoints[i]] : -1);
+                    kf_octave.push_back(i < kfs[k]->mvKeysUn.size() ? (uint8_t)kfs[k]->mvKeysUn[i].octave : 0);
+                }
+            kf_mp_ptr[k + 1] = (int32_t)kf_mp.size();
+        }
+        const std::vector<int32_t> kf_mp_old(kf_mp);
+        const size_t kfmp_cap = kf_mp.size() + kp_new;
+        kf_mp.resize(kfmp_cap + 1, -1); kf_octave.resize(kfmp_cap + 1, 0);
+        std::vector<int32_t> obs_ptr(mp_cap + 1, 0), obs_kf;
+        std::vector<uint8_t> mp_bad(mp_cap + 1, 0);
+        for (int p = 0; p < n_mp; ++p) {
+            mp_bad[p] = mps[p]->mbBad ? 1 : 0;
+            for (ObsIt it = mps[p]->mObservations.begin(); it != mps[p]->mObservations.end(); ++it)
+                if (!fresh.count(it->first)) obs_kf.push_back(kfSlot[it->first]);
+            obs_ptr[p + 1] = (int32_t)obs_kf.size();
+        }
+        // the frame records: what KeyFrame::KeyFrame copies from the frame is what the keyframe object holds
+        std::vector<std::vector<int32_t> > f_mp(framed.size());
+        std::vector<std::vector<uint8_t> > f_oct(framed.size()), f_desc(framed.size());
+        std::vector<std::vector<float> > f_ur(framed.size());
+        const float eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        std::vector<slamit_grow_frame> frames(framed.size());
+        for (size_t f = 0; f < framed.size(); ++f) {
+            KeyFrameT* kf = framed[f];
+            const size_t nk = kf->mvpMapPoints.size();
+            f_mp[f].resize(nk + 1, -1); f_oct[f].resize(nk + 1, 0); f_desc[f].resize(32 * nk + 32, 0); f_ur[f].resize(nk + 1, -1.f);
+            for (size_t i = 0; i < nk; ++i) {
+                f_mp[f][i] = kf->mvpMapPoints[i] ? mpSlot[kf->mvpMapPoints[i]] : -1;
+                f_oct[f][i] = i < kf->mvKeysUn.size() ? (uint8_t)kf->mvKeysUn[i].octave : 0;
+                f_ur[f][i] = i < kf->mvuRight.size() ? kf->mvuRight[i] : -1.f;
+            }
+            memset(&frames[f], 0, sizeof(frames[f]));
+            frames[f].n_kp = (int32_t)nk; frames[f].frame_mp = f_mp[f].data(); frames[f].octave = f_oct[f].data(); frames[f].desc = f_desc[f].data();
+            frames[f].uright = f_ur[f].data(); frames[f].Tcw = eye;
+        }
+        std::vector<slamit_grow_op> list(n);
+        for (int i = 0; i < n; ++i) {
+            const GrowOp<KeyFrameT>& e = ops[i];
+            slamit_grow_op& o = list[i];
+            memset(&o, 0, sizeof(o));
+            o.kind = e.kind; o.kf = kfSlot[e.pKF]; o.cand = -1; o.kf_b = -1;
+            if (e.kind != SLAMIT_GROW_NEW_POINT) { o.src = frameOf[e.pKF]; continue; }
+            o.flags = e.recent ? SLAMIT_GROW_RECENT : 0; o.cand = e.accepted ? -1 : 0;
+            o.kf_a = kfSlot[e.pKFa]; o.idx_a = (int32_t)e.idxA; o.weight_a = e.idxA < e.pKFa->mvuRight.size() && e.pKFa->mvuRight[e.idxA] >= 0 ? 2 : 1;
+            if (e.pKFb) { o.kf_b = kfSlot[e.pKFb]; o.idx_b = (int32_t)e.idxB; o.weight_b = e.idxB < e.pKFb->mvuRight.size() && e.pKFb->mvuRight[e.idxB] >= 0 ? 2 : 1; }
+            for (int c = 0; c < 3; ++c) o.pos[c] = e.pos[c];
+        }
+        const uint8_t rejected = 1;                                           // candidate 0: the status of every op that is not accepted
+        const float no_pos[3] = {0, 0, 0};
+        // the columns the call appends to and the caller's objects already hold or do not keep: scratch
+        const size_t K = (size_t)kf_cap + 1, Q = (size_t)mp_cap + 1;
+        std::vector<uint8_t> kf_desc(32 * (kfmp_cap + 1), 0), kf_bad(K, 0), kf_tbe(K, 0), kf_ne(K, 0), mp_desc(32 * Q, 0);
+        std::vector<int32_t> kf_parent(K, -1), kf_best(SLAMIT_LOCAL_MAP_BEST * K, -1), cw_n(K, 0), ord_n(K, 0), child_ptr(K + 1, 0), mp_nobs(Q, 0), mp_ref(Q, -1), mp_found(Q, 0),
+            mp_visible(Q, 0), mp_first(Q, 0), mp_replaced(Q, -1);
+        std::vector<float> kf_center(3 * K, 0.f), mp_pos(3 * Q, 0.f), mp_normal(3 * Q, 0.f), mp_max(Q, 0.f), mp_min(Q, 0.f);
+        int32_t none32 = -1;
+        slamit_map_index M;
+        memset(&M, 0, sizeof(M));
+        M.n_kf = n_kf; M.n_mp = n_mp; M.obs_kf = obs_kf.empty() ? &none32 : obs_kf.data();
+        slamit_grow_index X;
+        memset(&X, 0, sizeof(X));
+        X.kf_cap = kf_cap; X.mp_cap = mp_cap; X.kfmp_cap = (int32_t)kfmp_cap;
+        X.kf_mp_ptr = kf_mp_ptr.data(); X.kf_mp = kf_mp.data(); X.kf_octave = kf_octave.data(); X.kf_desc = kf_desc.data(); X.kf_bad = kf_bad.data(); X.kf_parent = kf_parent.data();
+        X.kf_to_be_erased = kf_tbe.data(); X.kf_not_erase = kf_ne.data(); X.kf_best = kf_best.data(); X.cw_n = cw_n.data(); X.ord_n = ord_n.data(); X.kf_child_ptr = child_ptr.data();
+        X.kf_center = kf_center.data(); X.mp_pos = mp_pos.data(); X.mp_normal = mp_normal.data(); X.mp_max_dist = mp_max.data(); X.mp_min_dist = mp_min.data(); X.mp_bad = mp_bad.data();
+        X.mp_nobs = mp_nobs.data(); X.mp_ref_kf = mp_ref.data(); X.mp_found = mp_found.data(); X.mp_visible = mp_visible.data(); X.mp_first_kf = mp_first.data();
+        X.mp_replaced = mp_replaced.data(); X.mp_desc = mp_desc.data(); X.obs_ptr = obs_ptr.data();
+        const size_t edit_cap = 2 * (size_t)P + kp_assoc, recent_cap = (size_t)n_rec_ops + kp_assoc;
+        if (edit_cap > SLAMIT_EDIT_MAX_EDITS || recent_cap > SLAMIT_UPKEEP_MAX_RECENT) return shim::refuse<LocalMapping>("GrowMap: the ops may emit more edits or recent entries than a list holds", SLAMIT_ERR_CAPACITY);
+        std::vector<int32_t> op_status(n, 0), rec_slots(recent_cap + 1, -1);
+        std::vector<slamit_map_edit> emitted(edit_cap + 1);
+        int32_t n_edits = 0, n_recent = 0, n_new = 0, need[SLAMIT_GROW_NEEDS], st = 0;
+        const int rcode = slamit_map_grow_apply(device, &M, &X, (int32_t)frames.size(), frames.data(), n, list.data(), 1, &rejected, no_pos, op_status.data(), (int32_t)edit_cap,
+                                                emitted.data(), &n_edits, (int32_t)recent_cap, rec_slots.data(), &n_recent, &n_new, need, &st);
+        if (rcode != SLAMIT_OK) return shim::report<LocalMapping>("GrowMap: slamit_map_grow_apply", rcode);
+        if (st != 0) return shim::refuse<LocalMapping>("GrowMap: slamit_map_grow_apply reported a status on tables built here", SLAMIT_ERR_STATE);
+        // write back: the new objects in slot order, the rows, the map, the recent list; then the observations through ApplyMapEdits
+        for (int i = 0; i < n; ++i) {
+            if (ops[i].kind == SLAMIT_GROW_NEW_KF) pMap->AddKeyFrame(ops[i].pKF);
+            if (ops[i].kind != SLAMIT_GROW_NEW_POINT || op_status[i] < 0) continue;
+            if (op_status[i] != (int32_t)mps.size()) return shim::refuse<LocalMapping>("GrowMap: the slots of the new points do not ascend in list order", SLAMIT_ERR_STATE);
+            MapPointT* pMP = make(ops[i].pos, ops[i].pKF);
+            mps.push_back(pMP);
+            pMap->AddMapPoint(pMP);
+        }
+        for (size_t k = 0; k < kfs.size(); ++k) {
+            const bool is_new = (int)k >= n_kf;
+            if (!is_new && !named.count(kfs[k])) continue;
+            for (int e = kf_mp_ptr[k]; e < kf_mp_ptr[k + 1]; ++e) {
+                MapPointT* now = kf_mp[e] < 0 ? (MapPointT*)0 : mps[kf_mp[e]];
+                if (kfs[k]->mvpMapPoints[e - kf_mp_ptr[k]] != now) kfs[k]->mvpMapPoints[e - kf_mp_ptr[k]] = now;
+            }
+        }
+        for (int r = 0; r < n_recent; ++r) recent.push_back(mps[rec_slots[r]]);
+        std::vector<MapEdit<MapPointT, KeyFrameT> > edits((size_t)n_edits);
+        for (int i = 0; i < n_edits; ++i) {
+            edits[i].kind = SLAMIT_EDIT_ADD_OBS; edits[i].flags = 0; edits[i].pMP = mps[emitted[i].mp]; edits[i].pKF = kfs[emitted[i].kf]; edits[i].idx = (size_t)emitted[i].idx;
+        }
+        ApplyMapEdits(edits, pMap, device);
+        return n_new;
+    }
+
     static int LastStatus() { return status(); }
 
 private:

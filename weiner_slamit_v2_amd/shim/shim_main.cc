@@ -1915,6 +1915,79 @@ static int run_essential(int argc, char** argv) {
     return 0;
 }
 
+// map_grow: LocalMapping::GrowMap over a world small enough to follow by hand.  Two keyframes of four keypoints, three points (point 2
+// bad); a new keyframe whose frame tracked points 0, 2 and 1 at keypoints 0, 2 and 3; a stereo point at its keypoint 1, the association
+// loop, a pair with keyframe 0's keypoint 3 at the same keypoint 1, and a rejected pair.  Prints what the objects hold afterwards.
+namespace grow_case {
+struct MPt;
+struct KFr {
+    int id;
+    std::vector<MPt*> mvpMapPoints; std::vector<float> mvuRight; std::vector<cv::KeyPoint> mvKeysUn;
+};
+struct MapG {
+    std::set<int> points, keyframes;
+    void AddKeyFrame(KFr* k) { keyframes.insert(k->id); }
+    void AddMapPoint(MPt* p);
+    void EraseMapPoint(MPt* p);
+};
+struct MPt {
+    int id; bool mbBad; int nObs;
+    std::map<KFr*, size_t> mObservations; KFr* mpRefKF;
+};
+void MapG::AddMapPoint(MPt* p) { points.insert(p->id); }
+void MapG::EraseMapPoint(MPt* p) { points.erase(p->id); }
+struct Make {
+    std::vector<MPt>* pool; int* next;
+    MPt* operator()(const float*, KFr* ref) const {
+        MPt* p = &(*pool)[(size_t)*next];
+        p->id = (*next)++; p->mbBad = false; p->nObs = 0; p->mpRefKF = ref;
+        return p;
+    }
+};
+}  // namespace grow_case
+
+static int run_map_grow(int, char**) {
+    using namespace grow_case;
+    typedef ORB_SLAM2::LocalMapping::GrowOp<KFr> Op;
+    std::vector<KFr> K(3);
+    std::vector<MPt> P(6);
+    for (int k = 0; k < 3; ++k) { K[k].id = k; K[k].mvpMapPoints.assign(4, (MPt*)NULL); K[k].mvuRight.assign(4, -1.f); K[k].mvKeysUn.assign(4, cv::KeyPoint(0, 0, 1, -1, 0, k)); }
+    K[0].mvuRight[3] = 5.f;                                               // a stereo keypoint: its observation weighs 2
+    for (int p = 0; p < 3; ++p) { P[p].id = p; P[p].mbBad = p == 2; P[p].nObs = 0; P[p].mpRefKF = &K[0]; }
+    const int obs[4][3] = {{0, 0, 0}, {0, 1, 0}, {1, 0, 1}, {2, 1, 2}};   // point, keyframe, keypoint
+    for (int o = 0; o < 4; ++o) { P[obs[o][0]].mObservations[&K[obs[o][1]]] = (size_t)obs[o][2]; P[obs[o][0]].nObs++; K[obs[o][1]].mvpMapPoints[obs[o][2]] = &P[obs[o][0]]; }
+    K[2].mvpMapPoints[0] = &P[0]; K[2].mvpMapPoints[2] = &P[2]; K[2].mvpMapPoints[3] = &P[1];
+    MapG map;
+    map.keyframes.insert(0); map.keyframes.insert(1);
+    for (int p = 0; p < 3; ++p) map.points.insert(p);
+    const Op proto = {0, &K[2], &K[2], 1, (KFr*)NULL, 0, true, false, {1.f, 2.f, 3.f}};
+    std::vector<Op> ops(5, proto);
+    ops[0].kind = SLAMIT_GROW_NEW_KF;
+    ops[1].kind = SLAMIT_GROW_NEW_POINT;
+    ops[2].kind = SLAMIT_GROW_ASSOCIATE;
+    ops[3].kind = SLAMIT_GROW_NEW_POINT; ops[3].pKFb = &K[0]; ops[3].idxB = 3; ops[3].recent = true;
+    ops[4] = ops[3]; ops[4].accepted = false;
+    std::list<MPt*> recent;
+    int next = 3;
+    Make mk = {&P, &next};
+    const int made = ORB_SLAM2::LocalMapping::GrowMap<MPt>(ops, &map, recent, mk);
+    const int st = ORB_SLAM2::LocalMapping::LastStatus();
+    if (st != 0) fprintf(stderr, "grow_map failed: %s\n", slamit_last_error());
+    printf("map_grow: status=%d made=%d", st, made);
+    for (int k = 0; k < 3; k += 2) {
+        printf(" kf%d=", k);
+        for (int i = 0; i < 4; ++i) printf("%s%d", i ? "," : "", K[k].mvpMapPoints[i] ? K[k].mvpMapPoints[i]->id : -1);
+    }
+    printf(" recent=");
+    for (std::list<MPt*>::const_iterator it = recent.begin(); it != recent.end(); ++it) printf("%s%d", it == recent.begin() ? "" : ",", (*it)->id);
+    printf(" nobs=");
+    for (int p = 0; p < next; ++p) printf("%s%d", p ? "," : "", P[p].nObs);
+    printf(" observers=");
+    for (int p = 0; p < next; ++p) printf("%s%zu", p ? "," : "", P[p].mObservations.size());
+    printf(" map_points=%zu map_kfs=%zu\n", map.points.size(), map.keyframes.size());
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     std::string mode = argv[1];
@@ -1940,5 +2013,6 @@ int main(int argc, char** argv) {
     if (mode == "stereo") return run_stereo(argc, argv);
     if (mode == "unproject") return run_unproject(argc, argv);
     if (mode == "local_map") return run_local_map(argc, argv);
+    if (mode == "map_grow") return run_map_grow(argc, argv);
     return 2;
 }
